@@ -3,6 +3,9 @@
     python bench.py --gpus N --steps K --warmup W            (N > 1 without a launcher: spawns its own ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
+A plain run sets up, warms up, times exactly K steps (wall clock; ms_per_step and value come from it) and prints the line.
+--full adds every other measurement (see --help); --dump-outputs DIR writes what the last timed step computed as .npy files.
+
 A "step" is one pass of the hot path over one synthetic batch already resident in HBM:
 teacher forward + student forward + BCE/MSE losses + student backward (+ gradient all-reduce over
 RCCL when N > 1) + fused Adam + EMA, exactly what baseline/main.py:84-157 does per batch.
@@ -378,19 +381,21 @@ def collective_bench(pg, device, world, rank, iters=50):
     return out
 
 
+def barrier(world, device):
+    if world > 1:
+        import torch.distributed as dist
+        dist.barrier()
+    torch.cuda.synchronize(device)
+
+
 def time_steps(step, steps, world, device):
-    def barrier():
-        if world > 1:
-            import torch.distributed as dist
-            dist.barrier()
-        torch.cuda.synchronize(device)
-    barrier()
+    barrier(world, device)
     t0 = time.perf_counter()
     for _ in range(steps):
         step.run()
     torch.cuda.synchronize(device)
     elapsed = time.perf_counter() - t0
-    barrier()
+    barrier(world, device)
     per_rank = [elapsed]
     if world > 1:
         import torch.distributed as dist
@@ -400,9 +405,14 @@ def time_steps(step, steps, world, device):
         per_rank = [float(v.item()) for v in tl]
         elapsed = max(per_rank)
     time_steps.per_rank = per_rank
-    # SURVEY 8(d)'s prescription beside the wall clock: a hipEvent pair on the launch stream around the same number of steps,
-    # recorded right behind up to 50 more (untimed) replays with NO host synchronisation in between - the first dozen replays
-    # after a synchronise run 3 - 10 % slow (tools/first_replays.py), which is what a 20-step wall-clock region mostly measures
+    return elapsed
+
+
+def time_steps_events(step, steps, world, device):
+    """SURVEY 8(d)'s prescription beside the wall clock of time_steps (--full): a hipEvent pair on the launch stream around the
+    same number of steps, recorded right behind up to 50 more (untimed) replays with NO host synchronisation in between - the
+    first dozen replays after a synchronise run 3 - 10 % slow (tools/first_replays.py), which is what a 20-step wall-clock region
+    mostly measures.  Seconds for `steps` steps (MAX over ranks)."""
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for _ in range(min(steps, 50)):
         step.run()
@@ -417,9 +427,8 @@ def time_steps(step, steps, world, device):
         t = torch.tensor([ev], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         ev = float(t.item())
-    barrier()
-    time_steps.events_s = ev
-    return elapsed
+    barrier(world, device)
+    return ev
 
 
 def replicas_bit_identical(step, world, device):
@@ -450,6 +459,28 @@ def same_on_all_ranks(step, world, device):
     if any(v != allv[0] for v in allv):
         raise SystemExit(f"[bench] data-parallel schedules differ across ranks: {allv}")
     return allv
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(step, out_dir):
+    """--dump-outputs DIR: what the timed step hands its caller after its last step, one float32 DIR/<name>.npy each - the
+    meters main.train logs (train.LOSS_NAMES order), the student's (and teacher's) flat parameters and BatchNorm running
+    statistics, the Adam moments, and the strong / weak posteriors of that step.  34 MB at the wide model, well under the limit."""
+    arrays = {"meters": step.losses[:8], "student_params": step.student._flat, "student_bn_running": step.student._bn_flat,
+              "adam_exp_avg": step.exp_avg, "adam_exp_avg_sq": step.exp_avg_sq, "strong": step.strong, "weak": step.weak}
+    if step.teacher is not None:
+        arrays.update(teacher_params=step.teacher._flat, teacher_bn_running=step.teacher._bn_flat,
+                      strong_ema=step.strong_ema, weak_ema=step.weak_ema)
+    torch.cuda.synchronize(step.device)
+    host = {name: t.detach().float().cpu().numpy() for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"[bench] --dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 ARITH = {"f32": "fp32 (exact fp32 MFMA; block 0's backward sums on split bf16 operands, DESIGN.md 3.10)",
@@ -526,16 +557,17 @@ def extra_config_legs(device, steps=300):
     """The other single-GPU BASELINE.json workloads, timed in the SAME driver run as the headline line (round 3's numbers
     for them were builder-printed): configs[2] (waveform-bf16, batch 64), configs[4]'s model at its per-GPU shape (wide-bf16,
     wide-bf16x3), and configs[1]'s workload in the two reduced-precision modes.  `steps` hipGraph replays each after warm-up.
-    Every leg runs in a process of its own (this script with --config <c> --no-extras --no-cpu-baseline): a process that has
-    already built and replayed four other steps holds their streams, and a later step's graph branches then share hardware
-    queues with them - measured in-process, the fifth leg came out at 0.90 ms against 0.66 ms alone."""
+    Every leg runs in a process of its own (this script with --config <c> --full --no-extras --no-cpu-baseline: the headline's
+    fields plus ms_per_step_events): a process that has already built and replayed four other steps holds their streams, and a
+    later step's graph branches then share hardware queues with them - measured in-process, the fifth leg came out at 0.90 ms
+    against 0.66 ms alone."""
     out = {}
     for name in ("mt-f32-b64", "mt-f32-T864", "mt-f32-strict", "waveform-bf16", "waveform-f16", "wide-bf16", "wide-f16", "wide-bf16x3",
                  "mt-bf16", "mt-f16", "mt-bf16x3"):
         try:
             wide, mfma_dtype, waveform, B = CONFIGS[name]
-            cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--steps", str(steps), "--warmup", "8", "--no-extras",
-                   "--no-cpu-baseline"]
+            cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--steps", str(steps), "--warmup", "8", "--full",
+                   "--no-extras", "--no-cpu-baseline"]
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
             if r.returncode != 0:
                 raise RuntimeError(r.stderr[-300:])
@@ -565,14 +597,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="mt-f32", choices=sorted(CONFIGS))
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the kernel table, feature-path and config3 legs")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline line: ms_per_step_events, the CPU baseline, the other workloads "
+                         "(extra_configs), steady_state, the kernel table, the feature path and, at N > 1, the schedule A/B, "
+                         "collective-only and configs[3] / [4] legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip every leg but ms_per_step_events and the CPU baseline")
     ap.add_argument("--batch", type=int, default=None)
     ap.add_argument("--trace-only-this-config", action="store_true",
-                    help="for rocprofv3 runs (tools/collect_profiles.sh): keep the headline's kernel-table leg (solo re-launches) "
-                         "but skip the extra_configs child processes and the feature-path leg, so that the trace holds ONE "
-                         "process and only this workload's kernels")
+                    help="for rocprofv3 runs with --full (tools/collect_profiles.sh): keep the headline's kernel-table leg (solo "
+                         "re-launches) but skip the extra_configs child processes and the feature-path leg, so that the trace "
+                         "holds ONE process and only this workload's kernels")
     args = ap.parse_args()
+    extras_on = args.full and not args.no_extras
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)
@@ -611,22 +651,25 @@ def main():
     headline = args.config == "mt-f32"
     T_cfg = CONFIG_FRAMES.get(args.config, T_FRAMES)
     runner, step, B = make_runner(args.config, device, rank, pg, use_graph=not args.no_graph, batch=args.batch)
-    x, xe, tgt, wm, sm = synthetic_batch(B, T_cfg, 1000 + rank, device)          # (the same batch again, for the A/B legs below)
     for _ in range(max(args.warmup, 3)):       # >= 3: two eager warm-ups + graph capture/first replay
         runner.run()
     elapsed = time_steps(runner, args.steps, world, device)
-    events_s = time_steps.events_s
     per_rank_s = list(time_steps.per_rank)
+    # the loss, the checks and the dumped outputs all belong to the last of the timed steps, with or without --full
     meters = step.meters()
     assert np.isfinite(meters["loss"]), meters
     step.check_health()
     schedules = same_on_all_ranks(step, world, device) if step.dp else None
     replicas_identical = replicas_bit_identical(step, world, device) if (step.dp and world > 1) else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(step, args.dump_outputs)
+    events_s = time_steps_events(runner, args.steps, world, device) if args.full else None
 
     # N > 1: the same workload under the other data-parallel schedules, so that ONE driver run yields the comparison
     # (captured overlap = the default above | single all-reduce, eager | overlap with eager collectives)
     ab_legs = None
-    if world > 1 and headline and not args.no_extras and args.batch is None:
+    if world > 1 and headline and extras_on and args.batch is None:
+        x, xe, tgt, wm, sm = synthetic_batch(B, T_cfg, 1000 + rank, device)          # the headline's batch again
         ab_legs = {}
         # (the headline runs the default: overlap schedule, collectives captured, the library's own peer-memory all-reduce when
         # its self-check passes - config.dp_collective says which ran; these legs price the alternatives)
@@ -656,11 +699,11 @@ def main():
                 os.environ.pop("SED_DP_CAPTURE", None)
 
     coll_bench = None
-    if step.dp and headline and not args.no_extras and args.batch is None:
+    if step.dp and headline and extras_on and args.batch is None:
         coll_bench = collective_bench(pg, device, world, rank)
 
     config3 = None
-    if world > 1 and headline and not args.no_extras and args.batch is None:
+    if world > 1 and headline and extras_on and args.batch is None:
         # BASELINE.json configs[3]: global batch 512 at N = 8 = 64 clips per GPU ([16|32|16] per rank)
         try:                                        # the headline line must not depend on this extra leg
             s3, t3 = build_models(device, seed=0)
@@ -680,7 +723,7 @@ def main():
             config3 = {"error": repr(e)[:300]}
 
     config4 = None
-    if world > 1 and headline and not args.no_extras and args.batch is None:
+    if world > 1 and headline and extras_on and args.batch is None:
         # BASELINE.json configs[4]: the wide CRNN in bf16 under the data-parallel step, 24 clips per GPU
         try:
             r4, step4, B4 = make_runner("wide-bf16", device, rank, pg, use_graph=not args.no_graph, seed=2468)
@@ -702,18 +745,19 @@ def main():
 
     # the driver times 20 steps (15 ms): a steady-state figure of the same workload beside it
     steady = None
-    if world == 1 and headline and not args.no_extras and args.steps < 1000:
+    if world == 1 and headline and extras_on and args.steps < 1000:
         for _ in range(20):
             runner.run()
         n_ss = 3000
         el_ss = time_steps(runner, n_ss, world, device)
-        steady = {"steps": n_ss, "ms_per_step": round(el_ss / n_ss * 1e3, 4), "ms_per_step_events": round(time_steps.events_s / n_ss * 1e3, 4),
+        ev_ss = time_steps_events(runner, n_ss, world, device)
+        steady = {"steps": n_ss, "ms_per_step": round(el_ss / n_ss * 1e3, 4), "ms_per_step_events": round(ev_ss / n_ss * 1e3, 4),
                   "value": round(B * n_ss / el_ss, 1), "unit": "clips/s",
                   "note": "same step, same buffers, 3000 hipGraph replays timed the same way (the headline's timed region is "
                           "K steps as the driver asks: 20 steps = 15 ms is dominated by the first replays)"}
 
     extras = None
-    if world == 1 and headline and not args.no_extras and args.batch is None and rank == 0 and not args.trace_only_this_config:
+    if world == 1 and headline and extras_on and args.batch is None and rank == 0 and not args.trace_only_this_config:
         extras = extra_config_legs(device)
 
     if rank == 0:
@@ -724,9 +768,6 @@ def main():
             "metric": "10-s clips/sec mean-teacher train step (64-mel x 628)",
             "value": round(clips, 1), "unit": "clips/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms, 4),
-            # (hipEvent pair on the launch stream around the same K steps, recorded behind further replays with no host
-            # synchronisation in between - SURVEY 8(d)'s method; ms_per_step above is the wall clock the contract asks for)
-            "ms_per_step_events": round(events_s / args.steps * 1e3, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": mfma_dtype, "data": "synthetic",
             "config": {"workload": wl, "global_batch": B * world, "frames": T_cfg, "n_mels": N_MELS,
@@ -741,6 +782,10 @@ def main():
                        "dp_collective_record": getattr(step, "collective_record", None) if step.dp else None},
             "loss": round(meters["loss"], 5),
         }
+        if events_s is not None:
+            # (hipEvent pair on the launch stream around another K steps, recorded behind further replays with no host
+            # synchronisation in between - SURVEY 8(d)'s method; ms_per_step above is the wall clock the contract asks for)
+            res["ms_per_step_events"] = round(events_s / args.steps * 1e3, 4)
         if dist_info:
             res["distributed"] = dist_info
             dist_info["ms_per_step_per_rank"] = {"min": round(min(per_rank_s) / args.steps * 1e3, 4),
@@ -787,7 +832,7 @@ def main():
                             "that run on bf16 operands are listed in config.workload; the recurrences, heads, BatchNorm and all "
                             "element-wise work are not MFMA work at all, so this fraction is NOT an MFMA-utilisation figure "
                             "(frac_of_f32_mfma_peak beside it)")
-        if not args.no_extras and headline:
+        if extras_on and headline:
             kr = kernel_roofline(step)
             dom = max(kr, key=lambda k: kr[k]["us"] * kr[k]["launches_per_step"])
             roof["dominant_kernel"] = dict(kr[dom], name=dom,
@@ -798,12 +843,12 @@ def main():
                               "step's own buffers (sed_kernel_replay) after the timed region; conv*_wgrad = the Winograd "
                               "wgrad kernel + its ordered partial-sum reduction (the whole operator)")
         res["roofline"] = roof
-        if world == 1 and not args.no_extras and headline and not args.trace_only_this_config:
+        if world == 1 and extras_on and headline and not args.trace_only_this_config:
             try:
                 res["feature_path"] = feature_path(device)
             except Exception as e:                      # the headline number must not depend on the extra leg
                 res["feature_path"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline and headline:
+        if world == 1 and args.full and not args.no_cpu_baseline and headline:
             res["cpu_baseline"] = cpu_baseline()
     if pg is not None:
         import torch.distributed as dist

@@ -475,7 +475,7 @@ def test_waveform_front_end_world2():
 
 
 def test_bench_gpus_2_code_path_on_a_shared_gpu():
-    """`bench.py --gpus 2` end to end - self-launch through torch.distributed.run, process group, data-parallel step with the
+    """`bench.py --gpus 2 --full` end to end - self-launch through torch.distributed.run, process group, data-parallel step with the
     default collective choice, the schedule A/B legs, configs[3] / configs[4] legs, the replica fingerprint - with the two ranks
     sharing this box's GPU over gloo (SED_BENCH_SHARE_GPU=1).  The number means nothing; what is checked is that the command the
     driver runs on an 8-GPU node produces ONE JSON line with the contract's fields, that the library's own all-reduce was chosen
@@ -484,7 +484,7 @@ def test_bench_gpus_2_code_path_on_a_shared_gpu():
     import subprocess
     env = dict(os.environ, SED_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("SED_POISON", None)
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "3"],
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "3", "--full"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads(r.stdout.strip().split("\n")[-1])
