@@ -693,15 +693,51 @@ __device__ __forceinline__ double amp_db(double a) {
 //                  log + sqrt + cospi in fp64
 //   k_logmel_apply every output element: dB, clamp, pad, normalise; folds the LM_CHUNKS partials of its clip itself
 // No atomics, no initialisation, fixed reduction order: bit-reproducible.
+// Both passes read their input through an addressing policy P - where clip c's linear mel starts, how many frames it has,
+// which noise counter its element 0 draws - so the dense batch (sed_logmel_transform) and the gather from a resident pool
+// (sed_gather_logmel_transform) share every line of the arithmetic.
 #define LM_CHUNKS 16
-template <int F32>
-__global__ __launch_bounds__(256) void k_logmel_max(const float* __restrict__ mel, int frames, int n_mels, int max_frames,
+struct LmDense {                 // clip c = rows [c * frames, (c + 1) * frames) of a dense [n_clips][frames][n_mels] batch
+    const float* mel;
+    int frames, n_mels;
+    __device__ __forceinline__ const float* src(int c) const { return mel + (size_t)c * frames * n_mels; }
+    __device__ __forceinline__ int len(int c) const { return frames; }
+    __device__ __forceinline__ size_t noise_base(int c) const { return (size_t)c * frames * n_mels; }
+    __device__ __forceinline__ void copy_target(int, int, int) const {}
+};
+struct LmGather {                // clip c = pool clip idx[c] (any length); counters b * S + e with S = L_max * n_mels
+    const float* pool;
+    const int64_t* offset;       // [n_pool] first frame of each clip in the pool
+    const int32_t* frames;       // [n_pool]
+    const int32_t* idx;          // [B] pool clips of this batch, validated on the host: every entry is in [0, n_pool)
+    int n_mels;
+    size_t stride;               // S
+    const float* tgt_pool;       // [n_pool][tgt_elems] or NULL
+    float* tgt_out;              // [B][tgt_elems]
+    int tgt_elems;
+    __device__ __forceinline__ const float* src(int c) const { return pool + (size_t)offset[idx[c]] * n_mels; }
+    __device__ __forceinline__ int len(int c) const { return frames[idx[c]]; }
+    __device__ __forceinline__ size_t noise_base(int c) const { return (size_t)c * stride; }
+    // the clip's encoded target rows travel with its features: the LM_CHUNKS workgroups of clip c copy them
+    __device__ __forceinline__ void copy_target(int c, int chunk, int tid) const {
+        if (!tgt_pool) return;
+        const float* s = tgt_pool + (size_t)idx[c] * tgt_elems;
+        float* d = tgt_out + (size_t)c * tgt_elems;
+        for (int j = chunk * 256 + tid; j < tgt_elems; j += LM_CHUNKS * 256) d[j] = s[j];
+    }
+};
+
+template <int F32, typename P>
+__global__ __launch_bounds__(256) void k_logmel_max(const P p, int n_mels, int max_frames,
                                                      const uint64_t* __restrict__ seed_ptr, double* __restrict__ part,
                                                      float* __restrict__ out_noisy) {
     __shared__ double red[2][4];
     const int tid = threadIdx.x, chunk = blockIdx.x, clip = blockIdx.y, lane = tid & 63, wv = tid >> 6;
+    const int frames = p.len(clip);
     const int n = frames * n_mels, n_keep = min(frames, max_frames) * n_mels;
-    const float* src = mel + (size_t)clip * n;
+    const float* src = p.src(clip);
+    const size_t nb = p.noise_base(clip);
+    p.copy_target(clip, chunk, tid);
     const uint64_t seed = out_noisy ? seed_ptr[0] : 0ull;
     const int per = (((n + LM_CHUNKS - 1) / LM_CHUNKS) + 1) & ~1, e0 = chunk * per, e1 = min(n, e0 + per);   // even chunks: pairs never straddle
     double mc = 0.0, mn = 0.0;
@@ -715,11 +751,11 @@ __global__ __launch_bounds__(256) void k_logmel_max(const float* __restrict__ me
                 if constexpr (F32 != 0) { float f0, f1; teacher_noise_pair_f32(pair, seed, f0, f1); a_ = f0; b_ = f1; }
                 else teacher_noise_pair(pair, seed, a_, b_);
             };
-            draw((uint32_t)(((size_t)clip * n + e) >> 1), z0, z1);
-            if ((((size_t)clip * n + e) & 1) != 0) {      // odd clip size x odd clip index: the pair starts one element earlier
+            draw((uint32_t)((nb + e) >> 1), z0, z1);
+            if (((nb + e) & 1) != 0) {                    // odd clip size x odd clip index: the pair starts one element earlier
                 // (only reachable when n is odd; keep the definition element-wise exact)
                 double y0, y1;
-                draw((uint32_t)((((size_t)clip * n + e) >> 1) + 1), y0, y1);
+                draw((uint32_t)(((nb + e) >> 1) + 1), y0, y1);
                 z0 = z1; z1 = y0;
             }
             mn = fmax(mn, fabs(a0 + z0));
@@ -737,14 +773,14 @@ __global__ __launch_bounds__(256) void k_logmel_max(const float* __restrict__ me
     if (tid < 2) part[((size_t)clip * LM_CHUNKS + chunk) * 2 + tid] = fmax(fmax(red[tid][0], red[tid][1]), fmax(red[tid][2], red[tid][3]));
 }
 
-template <int F32>
-__global__ __launch_bounds__(256) void k_logmel_apply(const float* __restrict__ mel, int frames, int n_mels, int max_frames,
+template <int F32, typename P>
+__global__ __launch_bounds__(256) void k_logmel_apply(const P p, int n_mels, int max_frames,
                                                        const double* __restrict__ mean, const double* __restrict__ stdv,
                                                        const double* __restrict__ part, float* __restrict__ out_clean,
                                                        float* __restrict__ out_noisy) {
     const int tid = threadIdx.x, clip = blockIdx.y;
-    const int n = frames * n_mels, n_out = max_frames * n_mels;
-    const float* src = mel + (size_t)clip * n;
+    const int frames = p.len(clip), n_out = max_frames * n_mels;
+    const float* src = p.src(clip);
     double mc = 0.0, mn = 0.0;
 #pragma unroll
     for (int k = 0; k < LM_CHUNKS; ++k) {
@@ -901,6 +937,20 @@ extern "C" int sed_seed_advance(uint64_t* key_dev, void* stream) {
 
 extern "C" size_t sed_logmel_transform_ws_bytes(int n_clips) { return (size_t)(n_clips > 0 ? n_clips : 0) * LM_CHUNKS * 2 * sizeof(double); }
 
+template <typename P>
+static int launch_logmel(const P& p, int n_clips, int n_mels, int max_frames, const double* mean, const double* std,
+                         const uint64_t* seed_dev, float* out_clean, float* out_noisy, void* ws, int math_dtype, hipStream_t st) {
+    if (math_dtype == SED_FFT_F32) k_logmel_max<1><<<dim3(LM_CHUNKS, n_clips), 256, 0, st>>>(p, n_mels, max_frames, seed_dev, (double*)ws, out_noisy);
+    else k_logmel_max<0><<<dim3(LM_CHUNKS, n_clips), 256, 0, st>>>(p, n_mels, max_frames, seed_dev, (double*)ws, out_noisy);
+    SED_CHECK_LAUNCH();
+    const int n_out = max_frames * n_mels;
+    const dim3 ga((n_out + 1023) / 1024, n_clips);
+    if (math_dtype == SED_FFT_F32) k_logmel_apply<1><<<ga, 256, 0, st>>>(p, n_mels, max_frames, mean, std, (const double*)ws, out_clean, out_noisy);
+    else k_logmel_apply<0><<<ga, 256, 0, st>>>(p, n_mels, max_frames, mean, std, (const double*)ws, out_clean, out_noisy);
+    SED_CHECK_LAUNCH();
+    return SED_OK;
+}
+
 extern "C" int sed_logmel_transform(const float* mel, int n_clips, int frames, int n_mels, int max_frames,
                                     const double* mean, const double* std, const uint64_t* seed_dev, float* out_clean,
                                     float* out_noisy, void* ws, size_t ws_bytes, int math_dtype, void* stream) {
@@ -915,16 +965,31 @@ extern "C" int sed_logmel_transform(const float* mel, int n_clips, int frames, i
         sed_set_error("sed_logmel_transform: workspace has %zu bytes, needs %zu", ws_bytes, sed_logmel_transform_ws_bytes(n_clips));
         return SED_ERR_WORKSPACE;
     }
-    hipStream_t st = (hipStream_t)stream;
-    if (math_dtype == SED_FFT_F32) k_logmel_max<1><<<dim3(LM_CHUNKS, n_clips), 256, 0, st>>>(mel, frames, n_mels, max_frames, seed_dev, (double*)ws, out_noisy);
-    else k_logmel_max<0><<<dim3(LM_CHUNKS, n_clips), 256, 0, st>>>(mel, frames, n_mels, max_frames, seed_dev, (double*)ws, out_noisy);
-    SED_CHECK_LAUNCH();
-    const int n_out = max_frames * n_mels;
-    const dim3 ga((n_out + 1023) / 1024, n_clips);
-    if (math_dtype == SED_FFT_F32) k_logmel_apply<1><<<ga, 256, 0, st>>>(mel, frames, n_mels, max_frames, mean, std, (const double*)ws, out_clean, out_noisy);
-    else k_logmel_apply<0><<<ga, 256, 0, st>>>(mel, frames, n_mels, max_frames, mean, std, (const double*)ws, out_clean, out_noisy);
-    SED_CHECK_LAUNCH();
-    return SED_OK;
+    return launch_logmel(LmDense{mel, frames, n_mels}, n_clips, n_mels, max_frames, mean, std, seed_dev, out_clean, out_noisy, ws,
+                         math_dtype, (hipStream_t)stream);
+}
+
+extern "C" int sed_gather_logmel_transform(const float* pool, const int64_t* clip_offset, const int32_t* clip_frames, int n_pool,
+                                           int max_clip_frames, const int32_t* idx, int B, int n_mels, int max_frames,
+                                           const double* mean, const double* std, const uint64_t* seed_dev, float* out_clean,
+                                           float* out_noisy, const float* tgt_pool, int tgt_elems, float* out_target, void* ws,
+                                           size_t ws_bytes, int math_dtype, void* stream) {
+    SED_CHECK_ARG(math_dtype == SED_FFT_F64 || math_dtype == SED_FFT_F32, "sed_gather_logmel_transform: math_dtype must be SED_FFT_F64 or SED_FFT_F32");
+    SED_CHECK_ARG(pool && clip_offset && clip_frames && idx && out_clean, "sed_gather_logmel_transform: null argument");
+    SED_CHECK_ARG((mean == nullptr) == (std == nullptr), "sed_gather_logmel_transform: mean and std go together");
+    SED_CHECK_ARG(!out_noisy || seed_dev, "sed_gather_logmel_transform: noise requested but seed_dev is null");
+    SED_CHECK_ARG((tgt_pool == nullptr) == (out_target == nullptr), "sed_gather_logmel_transform: tgt_pool and out_target go together");
+    SED_CHECK_ARG(!tgt_pool || tgt_elems >= 1, "sed_gather_logmel_transform: tgt_elems < 1");
+    SED_CHECK_ARG(n_pool >= 1 && max_clip_frames >= 1 && B >= 1 && n_mels >= 1 && max_frames >= 1, "sed_gather_logmel_transform: bad sizes");
+    SED_CHECK_ARG((int64_t)max_clip_frames * n_mels < (1ll << 31), "sed_gather_logmel_transform: clip too long");
+    SED_CHECK_ARG((int64_t)B * max_clip_frames * n_mels < (1ll << 32), "sed_gather_logmel_transform: too many elements for the noise stream");
+    SED_CHECK_ARG(ws != nullptr, "sed_gather_logmel_transform: null workspace");
+    if (ws_bytes < sed_logmel_transform_ws_bytes(B)) {
+        sed_set_error("sed_gather_logmel_transform: workspace has %zu bytes, needs %zu", ws_bytes, sed_logmel_transform_ws_bytes(B));
+        return SED_ERR_WORKSPACE;
+    }
+    const LmGather p{pool, clip_offset, clip_frames, idx, n_mels, (size_t)max_clip_frames * n_mels, tgt_pool, out_target, tgt_elems};
+    return launch_logmel(p, B, n_mels, max_frames, mean, std, seed_dev, out_clean, out_noisy, ws, math_dtype, (hipStream_t)stream);
 }
 
 // ---- Scaler statistics pass (baseline/utils/Scaler.py:34-87) ---------------------------------------------------------

@@ -347,29 +347,26 @@ def get_transforms(frames, scaler=None, add_axis_conv=True, augment_type=None, d
     return _SampleTransforms(frames, scaler, add_axis_conv, augment_type, device, seed)
 
 
-class WaveformFrontEnd:
-    """BASELINE.json configs[2]: the mean-teacher step fed from raw waveforms resident in HBM.  Feature extraction =
-    calculate_mel_spec for the whole batch (sed_mel_frames) -> the train-time transform chain with the teacher's noisy copy
-    (sed_logmel_transform, utils.py:397-412 with augment_type="noise").  Persistent buffers, no allocation and no host
-    value on the hot path; the noise key is a device word of the front-end's own, advanced in stream order.
+class OneBatchAheadFrontEnd:
+    """The protocol every front-end that feeds MeanTeacherStep ONE BATCH AHEAD shares (WaveformFrontEnd: raw waveforms;
+    resident.ResidentFrontEnd: linear-mel features resident in HBM); a subclass supplies only ``extract`` - how the staged
+    batch becomes (x, x_ema, target).
 
-    The features depend on no weight, so they are computed ONE BATCH AHEAD - the way the reference's DataLoader workers
+    The features depend on no weight, so they are computed one batch ahead - the way the reference's DataLoader workers
     prepare batch k + 1 while the model trains on batch k (DataLoad.py:47-186 behind torch's DataLoader,
     main.py:238-247).  There are two slots of (x, x_ema, target); ``run()`` trains on the slot extracted last and extracts the
-    staged waveforms (``load_batch``) into the other slot, target travelling with its features.  With ``overlap=True``
-    (default; needs a step that replays ONE hipGraph per step: single process, or data-parallel with captured
-    collectives) the extraction is part of that graph: a second stream, forked after the forwards (or, SED_FE_FORK=gru, from
-    inside the student forward between its conv stack and its recurrence: sed_crnn_fork_callback), runs the persistent STFT
-    kernel on ``fe_workgroups`` CUs - beside the heads / BiGRU backward, which occupy one workgroup per (clip, direction)
-    and cannot share a CU with an STFT workgroup (registers + LDS), so neither delays the other.  Without overlap the same protocol
-    runs serially (train, then extract).
+    staged batch into the other slot, target travelling with its features.  With ``overlap=True`` (default; needs a step that
+    replays ONE hipGraph per step: single process, or data-parallel with captured collectives) the extraction is part of that
+    graph: a second, lowest-priority stream, forked after the forwards (or, SED_FE_FORK=gru, from inside the student forward
+    between its conv stack and its recurrence: sed_crnn_fork_callback), runs it beside the heads / BiGRU backward.  Two
+    graphs, one per slot.  Without overlap the same protocol runs serially (train, then extract).
 
-    Streaming real data:  ``feed(waves, target)`` per batch and ``flush()`` at the end train on every batch exactly once, in
-    order, in both modes (bit-identical results: tests/test_gpu_features.py).  Resident / constant data (bench.py): ``run()``."""
+    The noise key is a device word of the front-end's own, advanced in stream order after every extraction
+    (sed_seed_advance): extraction k (0-based) draws with key_0 + (k + 1) strides, key_0 a function of ``seed``."""
 
-    def __init__(self, step, waves, cfg=None, scaler=None, overlap=True, seed=0, fe_workgroups=None, fft_dtype="f64"):
+    def __init__(self, step, overlap=True, seed=0, fe_workgroups=None):
         self.step = step
-        # This front-end writes the step's input slots itself, one batch ahead - so it also computes block 0's patch moments of
+        # The front-end writes the step's input slots itself, one batch ahead - so it also computes block 0's patch moments of
         # that batch (sed_crnn_moments) right behind the extraction, on the extraction's own stream: the step's forwards then
         # start at k_blk0_prep (26 + 16 us -> 16 us at the head of the B = 64 step), and the graph gets no new branch.
         # Measured (bench.py, 800 replays, B = 64): waveform-bf16 0.8445 -> 0.8233 ms, waveform-f16 0.8698 -> 0.8442; the fp32 step
@@ -380,25 +377,11 @@ class WaveformFrontEnd:
         self.moments = (env == "1") if env in ("0", "1") else (step.student._dtype != _lib.DTYPE_F32)
         step._mom_external = self.moments
         self.l = _lib.lib()
-        self.fx = FeatureExtractor(cfg or FeatureConfig.baseline_16k(), device=step.device, fft_dtype=fft_dtype)
-        c = self.fx.cfg
-        self.waves = torch.as_tensor(waves).to(step.device, torch.float32).contiguous()
-        n, ns = self.waves.shape
-        if n != step.B:
-            raise ValueError(f"{n} waveforms for a step of batch {step.B}")
-        self.n, self.ns, self.frames = n, ns, self.fx.n_frames(ns)
-        self.mel = torch.empty(n, self.frames, c.n_mels, device=step.device, dtype=torch.float32)
-        self.ws = self.fx.tables(exact_window=True)
-        self.ws_t = torch.empty(self.l.sed_logmel_transform_ws_bytes(n), device=step.device, dtype=torch.uint8)
-        self.mean = self.std = None
-        if scaler is not None:
-            self.mean = torch.tensor(np.asarray(scaler.mean_), dtype=torch.float64, device=step.device)
-            self.std = torch.tensor(np.asarray(scaler.std_), dtype=torch.float64, device=step.device)
         self.key = torch.tensor([(int(seed) * 0x9E3779B97F4A7C15 + 0x2545F4914F6CDD1D) & 0x7FFFFFFFFFFFFFFF],
                                 dtype=torch.int64, device=step.device)
         _lib.check(self.l.sed_seed_advance(_lib.ptr(self.key), _lib.stream_ptr()), "sed_seed_advance")
         self.overlap = bool(overlap) and step.single_graph and step.teacher is not None
-        # how much of the chip the next batch's STFT may take while the step's recurrences run (one workgroup = one CU):
+        # how much of the chip the next batch's extraction may take while the step's recurrences run (one workgroup = one CU):
         # B x 2 recurrence workgroups need their CUs first.  Serial extraction uses the whole chip.
         n_cu = torch.cuda.get_device_properties(step.device).multi_processor_count
         if fe_workgroups is None:
@@ -407,7 +390,6 @@ class WaveformFrontEnd:
         # slot i = (x, x_ema, target); slot 0 are the step's own buffers
         self._slots = [(step.x, step.x_ema, step.target),
                        (torch.empty_like(step.x), torch.empty_like(step.x_ema), torch.empty_like(step.target))]
-        self._staged_target = step.target.clone()      # until load_batch stages another one: the target the step holds now
         self._graphs = None
         self._cur = 0                                  # slot the next run() trains on
         self._primed = False
@@ -418,36 +400,21 @@ class WaveformFrontEnd:
             self._fe_stream = step._stream("front-end", int(os.environ.get("SED_FE_PRIO", lo)))     # (released by step.close())
             _lib.check(self.l.sed_stream_prepare(C.c_void_p(self._fe_stream.cuda_stream)), "sed_stream_prepare")
 
-    # ---- staging ---------------------------------------------------------------------------------------------------------------
-    def load_waves(self, waves):
-        self.waves.copy_(torch.as_tensor(waves).reshape(self.waves.shape), non_blocking=True)
-
-    def load_batch(self, waves, target):
-        """Stage the NEXT batch to extract: its waveforms and the target that belongs to them."""
-        self.load_waves(waves)
-        self._staged_target.copy_(torch.as_tensor(target).reshape(self._staged_target.shape), non_blocking=True)
+    # ---- extraction ------------------------------------------------------------------------------------------------------------
+    def extract(self, x, x_ema, target, workgroups):
+        """The staged batch -> x (and x_ema, target unless None) on the current stream, drawing its noise with self.key."""
+        raise NotImplementedError
 
     def features(self, x=None, x_ema=None, target=None, workgroups=0):
-        """staged waveforms -> (x, x_ema) on the current stream (default: the step's own input buffers); the staged target
-        is copied beside them when `target` is given."""
-        c = self.fx.cfg
+        """staged batch -> (x, x_ema) on the current stream (default: the step's own input buffers), plus the target when
+        `target` is given; then the key moves on and, if the front-end owns them, the batch's patch moments follow."""
         st = self.step
         x = st.x if x is None else x
         x_ema = (st.x_ema if st.teacher is not None else None) if x_ema is None else x_ema
-        _lib.check(self.l.sed_mel_frames(_lib.ptr(self.waves), self.n, self.ns, c.hop_length, c.n_window,
-                                         _lib.ptr(self.fx.mel_basis), c.n_mels, _lib.ptr(self.mel), _lib.ptr(self.ws),
-                                         self.ws.numel(), _lib.FFT_DTYPES[self.fx.fft_dtype], int(workgroups), _lib.stream_ptr()),
-                   "sed_mel_frames")
-        _lib.check(self.l.sed_logmel_transform(_lib.ptr(self.mel), self.n, self.frames, c.n_mels, st.T, _lib.ptr(self.mean),
-                                               _lib.ptr(self.std), _lib.ptr(self.key), _lib.ptr(x), _lib.ptr(x_ema),
-                                               _lib.ptr(self.ws_t), self.ws_t.numel(), _lib.FFT_DTYPES[self.fx.fft_dtype],
-                                               _lib.stream_ptr()),
-                   "sed_logmel_transform")
+        self.extract(x, x_ema, target, workgroups)
         # the key moves on AFTER the extraction (one tiny kernel at the tail of the chain instead of its head, where it delayed
         # the STFT by a launch); the constructor advanced it once, so extraction k draws with key_0 + (k + 1) strides as before
         _lib.check(self.l.sed_seed_advance(_lib.ptr(self.key), _lib.stream_ptr()), "sed_seed_advance")
-        if target is not None:
-            target.copy_(self._staged_target, non_blocking=True)
         if self.moments:
             st._moments(x, st.ctx_s)
             if x_ema is not None:
@@ -556,14 +523,6 @@ class WaveformFrontEnd:
         st._warm += 1
         st.steps_done += 1
 
-    def feed(self, waves, target):
-        """Streaming interface: every batch fed is trained on exactly once, in order (the last one by ``flush``)."""
-        self.load_batch(waves, target)
-        if not self._primed:
-            self.prime()
-            return
-        self.run()
-
     def flush(self):
         """Train on the batch extracted last without extracting another one."""
         if not self._primed:
@@ -580,3 +539,64 @@ class WaveformFrontEnd:
             st._warm += 1
             st.steps_done += 1
         self._primed = False
+
+
+class WaveformFrontEnd(OneBatchAheadFrontEnd):
+    """BASELINE.json configs[2]: the mean-teacher step fed from raw waveforms resident in HBM.  Feature extraction =
+    calculate_mel_spec for the whole batch (sed_mel_frames) -> the train-time transform chain with the teacher's noisy copy
+    (sed_logmel_transform, utils.py:397-412 with augment_type="noise").  Persistent buffers, no allocation and no host
+    value on the hot path; the one-batch-ahead protocol is OneBatchAheadFrontEnd's.  With overlap the persistent STFT kernel
+    runs on ``fe_workgroups`` CUs beside the heads / BiGRU backward, which occupy one workgroup per (clip, direction) and
+    cannot share a CU with an STFT workgroup (registers + LDS), so neither delays the other.
+
+    Streaming real data:  ``feed(waves, target)`` per batch and ``flush()`` at the end train on every batch exactly once, in
+    order, in both modes (bit-identical results: tests/test_gpu_features.py).  Resident / constant data (bench.py): ``run()``."""
+
+    def __init__(self, step, waves, cfg=None, scaler=None, overlap=True, seed=0, fe_workgroups=None, fft_dtype="f64"):
+        super().__init__(step, overlap=overlap, seed=seed, fe_workgroups=fe_workgroups)
+        self.fx = FeatureExtractor(cfg or FeatureConfig.baseline_16k(), device=step.device, fft_dtype=fft_dtype)
+        c = self.fx.cfg
+        self.waves = torch.as_tensor(waves).to(step.device, torch.float32).contiguous()
+        n, ns = self.waves.shape
+        if n != step.B:
+            raise ValueError(f"{n} waveforms for a step of batch {step.B}")
+        self.n, self.ns, self.frames = n, ns, self.fx.n_frames(ns)
+        self.mel = torch.empty(n, self.frames, c.n_mels, device=step.device, dtype=torch.float32)
+        self.ws = self.fx.tables(exact_window=True)
+        self.ws_t = torch.empty(self.l.sed_logmel_transform_ws_bytes(n), device=step.device, dtype=torch.uint8)
+        self.mean = self.std = None
+        if scaler is not None:
+            self.mean = torch.tensor(np.asarray(scaler.mean_), dtype=torch.float64, device=step.device)
+            self.std = torch.tensor(np.asarray(scaler.std_), dtype=torch.float64, device=step.device)
+        self._staged_target = step.target.clone()      # until load_batch stages another one: the target the step holds now
+
+    # ---- staging ---------------------------------------------------------------------------------------------------------------
+    def load_waves(self, waves):
+        self.waves.copy_(torch.as_tensor(waves).reshape(self.waves.shape), non_blocking=True)
+
+    def load_batch(self, waves, target):
+        """Stage the NEXT batch to extract: its waveforms and the target that belongs to them."""
+        self.load_waves(waves)
+        self._staged_target.copy_(torch.as_tensor(target).reshape(self._staged_target.shape), non_blocking=True)
+
+    def extract(self, x, x_ema, target, workgroups):
+        c = self.fx.cfg
+        _lib.check(self.l.sed_mel_frames(_lib.ptr(self.waves), self.n, self.ns, c.hop_length, c.n_window,
+                                         _lib.ptr(self.fx.mel_basis), c.n_mels, _lib.ptr(self.mel), _lib.ptr(self.ws),
+                                         self.ws.numel(), _lib.FFT_DTYPES[self.fx.fft_dtype], int(workgroups), _lib.stream_ptr()),
+                   "sed_mel_frames")
+        _lib.check(self.l.sed_logmel_transform(_lib.ptr(self.mel), self.n, self.frames, c.n_mels, self.step.T, _lib.ptr(self.mean),
+                                               _lib.ptr(self.std), _lib.ptr(self.key), _lib.ptr(x), _lib.ptr(x_ema),
+                                               _lib.ptr(self.ws_t), self.ws_t.numel(), _lib.FFT_DTYPES[self.fx.fft_dtype],
+                                               _lib.stream_ptr()),
+                   "sed_logmel_transform")
+        if target is not None:
+            target.copy_(self._staged_target, non_blocking=True)
+
+    def feed(self, waves, target):
+        """Streaming interface: every batch fed is trained on exactly once, in order (the last one by ``flush``)."""
+        self.load_batch(waves, target)
+        if not self._primed:
+            self.prime()
+            return
+        self.run()

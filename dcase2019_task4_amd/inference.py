@@ -46,7 +46,14 @@ def get_predictions(model, valid_dataset, decoder, pooling_time_ratio=1, save_pr
     ``decoder`` is ``many_hot_encoder.decode_strong`` (main.py:326): when it is a bound method of an object with
     ``.labels`` the run-length decode happens on the device, otherwise the callable gets the device-filtered 0/1 matrix
     of each clip, exactly as in the reference.  ``cfg`` supplies sample_rate / hop_length / median_window
-    (default: the values of baseline/config.py)."""
+    (default: the values of baseline/config.py).
+
+    ``valid_dataset`` may also be a ``resident.ResidentFeatureSet.for_eval(...)``: its clips are then gathered and
+    transformed ``batch_size`` per launch straight into the forward's input, with no host copy."""
+    from .resident import ResidentFeatureSet
+    resident = isinstance(valid_dataset, ResidentFeatureSet)
+    if resident and valid_dataset.noise:
+        raise ValueError("get_predictions needs a validation set without noise (ResidentFeatureSet.for_eval)")
     cfg = cfg or _Cfg
     labels = getattr(getattr(decoder, "__self__", None), "labels", None)
     dev = next(model.parameters()).device
@@ -61,13 +68,16 @@ def get_predictions(model, valid_dataset, decoder, pooling_time_ratio=1, save_pr
         with torch.no_grad():
             for i0 in range(0, n, batch_size):
                 idx = range(i0, min(n, i0 + batch_size))
-                items = [torch.as_tensor(valid_dataset[i][0]) for i in idx]
-                if stage is None or stage.shape[1:] != items[0].shape or stage.dtype != items[0].dtype:
-                    # one reusable pinned staging buffer: a fresh pageable torch.stack per batch cost more than the forward
-                    stage = torch.empty((batch_size,) + tuple(items[0].shape), dtype=items[0].dtype).pin_memory()
-                for k, it in enumerate(items):
-                    stage[k].copy_(it)
-                x = stage[:len(items)].to(dev, non_blocking=True).float()
+                if resident:
+                    x = valid_dataset.eval_batch(i0, len(idx))
+                else:
+                    items = [torch.as_tensor(valid_dataset[i][0]) for i in idx]
+                    if stage is None or stage.shape[1:] != items[0].shape or stage.dtype != items[0].dtype:
+                        # one reusable pinned staging buffer: a fresh pageable torch.stack per batch cost more than the forward
+                        stage = torch.empty((batch_size,) + tuple(items[0].shape), dtype=items[0].dtype).pin_memory()
+                    for k, it in enumerate(items):
+                        stage[k].copy_(it)
+                    x = stage[:len(items)].to(dev, non_blocking=True).float()
                 strong, _ = model(x)
                 if labels is not None:
                     cnt, pairs = postprocess(strong, threshold, cfg.median_window)

@@ -764,23 +764,87 @@ class MeanTeacherStep:
         return sd
 
 
+def _check_loss(m):
+    loss = m["loss"]
+    assert not (loss != loss or loss > 1e5), 'Loss explosion: {}'.format(loss)       # main.py:147
+    assert not loss < 0, 'Loss problem, cannot be negative'                            # main.py:148
+
+
+def _epoch_start(step_obj, pg0, epoch, n_batches):
+    step_obj.set_lr(pg0["lr"])        # an lr the caller changed between epochs is honoured (utils.py:227-241)
+    # main.py:74: global_step = epoch * len(train_loader) + i - recomputed from `epoch` at every call.  A call sequence
+    # epoch = 0, 1, 2 ... over one loader finds the device counter already there; a fresh step object entered with
+    # epoch = k (a resumed run that did not load_checkpoint), a repeated or a skipped epoch gets the reference's value
+    if step_obj.global_step_host != int(epoch) * n_batches:
+        step_obj.set_global_step(int(epoch) * n_batches)
+
+
+def _epoch_end(step_obj, epoch, start, log):
+    m = step_obj.meters()
+    _check_loss(m)
+    step_obj.check_health()
+    log('Epoch: {}\tTime {:.2f}\t{}'.format(epoch, time.time() - start,
+                                            "\t".join(f"{k} {v:.4g}" for k, v in m.items())))
+    return m
+
+
+def _train_resident(rset, model, optimizer, epoch, ema_model, weak_mask, strong_mask, n_epoch, log, check_every):
+    """train() over a ResidentFeatureSet: one fe.run() per step, no host batch.  The front-end's batch sequence runs on across
+    calls (batch 0 of the next epoch is gathered during this epoch's last step); ``epoch`` sets global_step as in train()."""
+    from .resident import ResidentFrontEnd
+    start = time.time()
+    n_batches = len(rset)
+    pg0 = optimizer.param_groups[0]
+    # with a process group the step works on this rank's share of each batch: main.py's global masks become dist.local_masks
+    weak_mask, strong_mask = rset.step_masks(weak_mask, strong_mask)
+    step_obj = getattr(model, "_mt_step", None)
+    if step_obj is not None and rset.process_group is not None:
+        B = step_obj.B
+        have = (step_obj.wlo, step_obj.whi, step_obj.slo, step_obj.shi)
+        want = (_slice_range(weak_mask, B) if weak_mask is not None else (0, 0)) + \
+               (_slice_range(strong_mask, B) if strong_mask is not None else (0, 0))
+        if have != want:
+            raise ValueError(f"the model's step was built with masks {have} (weak lo, hi, strong lo, hi); this rank's share of the "
+                             f"set needs {want}")
+    if step_obj is None:
+        model.to(rset.device)
+        if ema_model is not None:
+            ema_model.to(rset.device)
+        step_obj = MeanTeacherStep(model, ema_model, rset.batch, rset.frames, n_batches * n_epoch // 2, weak_mask, strong_mask,
+                                   lr=pg0["lr"], betas=pg0["betas"], eps=pg0["eps"], process_group=rset.process_group)
+        model._mt_step = step_obj
+    fe = getattr(model, "_mt_frontend", None)
+    if fe is None or fe.rs is not rset or fe.step is not step_obj:
+        fe = model._mt_frontend = ResidentFrontEnd(step_obj, rset)
+    _epoch_start(step_obj, pg0, epoch, n_batches)
+    for i in range(n_batches):
+        fe.run()
+        if (i + 1) % check_every == 0:
+            _check_loss(step_obj.meters())
+            step_obj.check_health()
+    return _epoch_end(step_obj, epoch, start, log)
+
+
 def train(train_loader, model, optimizer, epoch, ema_model=None, weak_mask=None, strong_mask=None, n_epoch=100,
           log=print, check_every=50):
     """main.train (main.py:52-165) with the loop body replaced by MeanTeacherStep.  With ``ema_model=None`` and
     two-element batches ``(batch_input, target)`` it is main_simple_CRNN.train (main_simple_CRNN.py:31-82).
 
     ``optimizer`` supplies lr / betas / eps (its per-tensor state is not used: Adam moments live in the
-    step object's flat buffers, kept on ``model._mt_step`` across epochs)."""
+    step object's flat buffers, kept on ``model._mt_step`` across epochs).
+
+    ``train_loader`` may also be a ``resident.ResidentFeatureSet``: the epoch's batches are then gathered from HBM one
+    batch ahead inside the step's hipGraph (``resident.ResidentFrontEnd``, kept on ``model._mt_frontend`` across epochs) -
+    same meters, loss checks, log line and global_step."""
+    from .resident import ResidentFeatureSet
+    if isinstance(train_loader, ResidentFeatureSet):
+        return _train_resident(train_loader, model, optimizer, epoch, ema_model, weak_mask, strong_mask, n_epoch, log,
+                               check_every)
     start = time.time()
     step_obj = getattr(model, "_mt_step", None)
     it = iter(train_loader)
     n_batches = len(train_loader)
     pg0 = optimizer.param_groups[0]
-
-    def check(m):
-        loss = m["loss"]
-        assert not (loss != loss or loss > 1e5), 'Loss explosion: {}'.format(loss)       # main.py:147
-        assert not loss < 0, 'Loss problem, cannot be negative'                            # main.py:148
 
     for i in range(n_batches):
         batch = next(it)
@@ -798,23 +862,13 @@ def train(train_loader, model, optimizer, epoch, ema_model=None, weak_mask=None,
                                        lr=pg0["lr"], betas=pg0["betas"], eps=pg0["eps"])
             model._mt_step = step_obj
         if i == 0:
-            step_obj.set_lr(pg0["lr"])        # an lr the caller changed between epochs is honoured (utils.py:227-241)
-            # main.py:74: global_step = epoch * len(train_loader) + i - recomputed from `epoch` at every call.  A call sequence
-            # epoch = 0, 1, 2 ... over one loader finds the device counter already there; a fresh step object entered with
-            # epoch = k (a resumed run that did not load_checkpoint), a repeated or a skipped epoch gets the reference's value
-            if step_obj.global_step_host != int(epoch) * n_batches:
-                step_obj.set_global_step(int(epoch) * n_batches)
+            _epoch_start(step_obj, pg0, epoch, n_batches)
         step_obj.step(batch_input.to(step_obj.device, non_blocking=True),
                       ema_batch_input.to(step_obj.device, non_blocking=True) if ema_batch_input is not None else None,
                       target.to(step_obj.device, non_blocking=True))
         # the reference asserts on the loss after EVERY batch (main.py:147-148), which costs it a host sync per step;
         # here the meters are read back every `check_every` steps and after the last one
         if (i + 1) % check_every == 0:
-            check(step_obj.meters())
+            _check_loss(step_obj.meters())
             step_obj.check_health()
-    m = step_obj.meters()
-    check(m)
-    step_obj.check_health()
-    log('Epoch: {}\tTime {:.2f}\t{}'.format(epoch, time.time() - start,
-                                            "\t".join(f"{k} {v:.4g}" for k, v in m.items())))
-    return m
+    return _epoch_end(step_obj, epoch, start, log)

@@ -371,6 +371,25 @@ int sed_seed_advance(uint64_t* key_dev, void* stream);
 int sed_logmel_transform(const float* mel, int n_clips, int frames, int n_mels, int max_frames,
                          const double* mean, const double* std, const uint64_t* seed_dev,
                          float* out_clean, float* out_noisy, void* ws, size_t ws_bytes, int math_dtype, void* stream);
+/* sed_gather_logmel_transform: the same transform chain on B clips GATHERED from a device-resident pool of linear mel
+ * (features stored once in HBM, every batch of an epoch addressed through a device index list).
+ *   pool        every clip's linear mel, fp32, concatenated along frames; clip i = frames [clip_offset[i],
+ *               clip_offset[i] + clip_frames[i]) x n_mels, of any length (the top_db clamp covers the whole clip, then
+ *               pad / truncate to max_frames as above)
+ *   idx [B]     device int32 pool clips of this batch (repeats allowed); NOT range-checked by the kernel - the caller
+ *               validates every entry against [0, n_pool) when it builds its index tables
+ *   max_clip_frames  L_max, the longest clip of the pool: noise counters of batch position b, element e are b * S + e with
+ *               S = L_max * n_mels (Philox pair (b S + e) >> 1) - with equal-length clips this is sed_logmel_transform's
+ *               layout, bit for bit
+ *   tgt_pool [n_pool][tgt_elems], out_target [B][tgt_elems]: the clips' encoded targets, copied by the same launch
+ *               (both NULL: no targets)
+ *   mean/std, seed_dev, out_clean, out_noisy (NULL: validation form), ws = sed_logmel_transform_ws_bytes(B), math_dtype:
+ *               as sed_logmel_transform                                                                                  */
+int sed_gather_logmel_transform(const float* pool, const int64_t* clip_offset, const int32_t* clip_frames, int n_pool,
+                                int max_clip_frames, const int32_t* idx, int B, int n_mels, int max_frames,
+                                const double* mean, const double* std, const uint64_t* seed_dev, float* out_clean,
+                                float* out_noisy, const float* tgt_pool, int tgt_elems, float* out_target, void* ws,
+                                size_t ws_bytes, int math_dtype, void* stream);
 
 /* Resampling step of read_audio (utils/utils.py:175-193: librosa.resample(audio, orig_sr, target_sr),
  * res_type "kaiser_best" = resampy's windowed-sinc interpolation, then fix_length).

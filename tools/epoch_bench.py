@@ -1,0 +1,232 @@
+"""What a training epoch on precomputed features costs per step - resident front-end against the resident-batch step and the
+drop-in feeding path - at DESED's sizes (1 262 weak / 14 412 unlabelled / 1 637 synthetic clips, ragged lengths, some longer
+than `frames`).  Device-event timing; prints one JSON object (and writes it to --out).
+
+  (a) one full epoch through resident.ResidentFrontEnd (the gather of batch k + 1 inside step k's hipGraph), ms / step
+  (b) the resident-batch step of the same shape (bench.py's mt-* leg: one batch in HBM, MeanTeacherStep.run() replayed)
+  (c) 20 steps of the drop-in path: DataLoadDf-style dataset (np.load per clip) + features.get_transforms, num_workers=0,
+      host collate, step.step
+  (d) get_predictions over 400 validation clips: per-clip dataset (np.load + get_transforms per clip) against the resident set
+
+Usage: python tools/epoch_bench.py [--shapes 24:f32,64:bf16] [--only-a] [--out FILE]"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+
+import bench                                                    # noqa: E402  (build_models / synthetic_batch of the mt-* legs)
+from dcase2019_task4_amd.features import Scaler, get_transforms  # noqa: E402
+from dcase2019_task4_amd.resident import ResidentFeatureSet, ResidentFrontEnd  # noqa: E402
+from dcase2019_task4_amd.train import MeanTeacherStep  # noqa: E402
+
+SIZES = (1262, 14412, 1637)
+T, N_MELS, NCLASS = 628, 64, 10
+
+
+def synthetic_pool(seed=0):
+    """Ragged linear-mel clips: 85 % of the full 628 frames, the rest 300 .. 900 frames; targets weak / -1 / strong."""
+    rs = np.random.RandomState(seed)
+    n = sum(SIZES)
+    lengths = np.where(rs.uniform(size=n) < 0.85, T, rs.randint(300, 901, size=n))
+    flat = np.random.default_rng(seed).random(int(lengths.sum()) * N_MELS, dtype=np.float32)
+    flat *= 3.0
+    offs = np.r_[0, np.cumsum(lengths)[:-1]] * N_MELS
+    feats = [flat[o:o + l * N_MELS].reshape(l, N_MELS) for o, l in zip(offs, lengths)]
+    T3 = T // 8
+    weak = np.repeat((rs.uniform(size=(SIZES[0], 1, NCLASS)) < 0.2).astype(np.float32), T3, axis=1)
+    strong = (rs.uniform(size=(SIZES[2], T3, NCLASS)) < 0.1).astype(np.float32)
+    tgts = list(weak) + [-np.ones((T3, NCLASS), np.float32)] * SIZES[1] + list(strong)
+    return feats, tgts, lengths
+
+
+def scaler_of(feats):
+    from oracle import features_np
+    sc = Scaler()
+    sc.calculate_scaler([features_np.transform_chain(f, T) for f in feats[:64]])
+    return sc
+
+
+def event_ms(fn, n):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n
+
+
+def leg_a(rs, B, dtype):
+    student, teacher = bench.build_models("cuda", seed=0, mfma_dtype=dtype)
+    st = MeanTeacherStep(student, teacher, B, T, 210 * 100 // 2, rs.weak_mask, rs.strong_mask, seed=1234)
+    fe = ResidentFrontEnd(st, rs)
+    for _ in range(10):                    # eager steps + capture of the two graphs + warm replays
+        fe.run()
+    torch.cuda.synchronize()
+    n = len(rs)
+    ms = event_ms(fe.run, n)               # one full epoch (it crosses into the next one: the table was drawn ahead)
+    assert np.isfinite(st.meters()["loss"])
+    st.close()
+    return ms, n
+
+
+def leg_b(B, dtype, n):
+    student, teacher = bench.build_models("cuda", seed=0, mfma_dtype=dtype)
+    x, xe, tgt, wm, sm = bench.synthetic_batch(B, T, 1000, "cuda")
+    st = MeanTeacherStep(student, teacher, B, T, 210 * 100 // 2, wm, sm, seed=1234)
+    st.load_batch(x, xe, tgt)
+    for _ in range(10):
+        st.run()
+    torch.cuda.synchronize()
+    ms = event_ms(st.run, n)
+    st.close()
+    return ms
+
+
+class _NpyDataset:
+    """DataLoadDf.__getitem__ (DataLoad.py:120-140): np.load of the clip's feature file + transform((features, label))."""
+
+    def __init__(self, paths, tgts, transform):
+        self.paths, self.tgts, self.transform = paths, tgts, transform
+
+    def __len__(self):
+        return len(self.paths)
+
+    def __getitem__(self, i):
+        return self.transform((np.load(self.paths[i]), self.tgts[i]))
+
+
+def leg_c(rs, feats, tgts, sc, B, dtype, tmp, n_steps=20):
+    np.random.seed(3)
+    rows = rs.epoch_table()[:n_steps + 2]
+    used = sorted(set(rows.reshape(-1).tolist()))
+    paths = {}
+    for i in used:
+        paths[i] = os.path.join(tmp, f"c{i}.npy")
+        np.save(paths[i], feats[i])
+    ds = _NpyDataset([paths.get(i) for i in range(len(feats))], tgts, get_transforms(T, sc, augment_type="noise"))
+    loader = torch.utils.data.DataLoader(ds, batch_sampler=[list(r) for r in rows], num_workers=0)
+    student, teacher = bench.build_models("cuda", seed=0, mfma_dtype=dtype)
+    st = MeanTeacherStep(student, teacher, B, T, 210 * 100 // 2, rs.weak_mask, rs.strong_mask, seed=1234)
+    it = iter(loader)
+    for _ in range(2):
+        x, xe, y = next(it)
+        st.step(x.cuda(non_blocking=True), xe.cuda(non_blocking=True), y.cuda(non_blocking=True))
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0 = time.perf_counter()
+    e0.record()
+    for _ in range(n_steps):
+        x, xe, y = next(it)
+        st.step(x.cuda(non_blocking=True), xe.cuda(non_blocking=True), y.cuda(non_blocking=True))
+    e1.record()
+    torch.cuda.synchronize()
+    wall = (time.perf_counter() - t0) * 1e3 / n_steps
+    st.close()
+    return e0.elapsed_time(e1) / n_steps, wall
+
+
+def leg_d(feats, sc, tmp, n=400):
+    import pandas as pd
+    from dcase2019_task4_amd.inference import get_predictions
+    from oracle import postprocess_np as pp
+    base = sum(SIZES[:2])                             # 400 of the synthetic-stream clips as the validation set
+    idx = list(range(base, base + n))
+    paths = []
+    for i in idx:
+        p = os.path.join(tmp, f"v{i}.npy")
+        np.save(p, feats[i])
+        paths.append(p)
+
+    class PerClip:
+        def __init__(self):
+            self.tr = get_transforms(T, sc)
+            self.filenames = pd.Series([f"clip_{i}.wav" for i in idx])
+
+        def __len__(self):
+            return n
+
+        def __getitem__(self, k):
+            return self.tr((np.load(paths[k]), np.zeros(1)))
+
+        def get_sample(self, k):
+            return np.load(paths[k]), np.zeros(1)
+
+    per = PerClip()
+    res = ResidentFeatureSet.for_eval(per, T, sc)
+    model, _ = bench.build_models("cuda", seed=0)
+    model.eval()
+    labels = [f"c{i}" for i in range(NCLASS)]
+    enc = type("Enc", (), {"labels": labels, "decode_strong": lambda self, m: pp.decode_strong(m, labels)})()
+    out = {}
+    for name, ds in (("per_clip", per), ("resident", res)):
+        get_predictions(model, ds, enc.decode_strong, 8, batch_size=64)           # warm-up
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        df = get_predictions(model, ds, enc.decode_strong, 8, batch_size=64)
+        torch.cuda.synchronize()
+        out[name] = ((time.perf_counter() - t0) * 1e3, df)
+    same = out["per_clip"][1].equals(out["resident"][1])
+    return {"clips": n, "batch_size": 64, "per_clip_ms": round(out["per_clip"][0], 2), "resident_ms": round(out["resident"][0], 2),
+            "same_dataframe": bool(same)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="24:f32,64:bf16")
+    ap.add_argument("--only-a", action="store_true", help="leg (a) only (for a kernel trace of the resident epoch)")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    dev = torch.cuda.get_device_properties(0)
+    t0 = time.perf_counter()
+    feats, tgts, lengths = synthetic_pool()
+    sc = scaler_of(feats)
+    result = {"device": dev.name, "pool": {"clips": list(SIZES), "frames_min": int(lengths.min()), "frames_max": int(lengths.max()),
+                                           "longer_than_frames": int((lengths > T).sum()), "frames": T,
+                                           "bytes": int(lengths.sum()) * N_MELS * 4}, "legs": []}
+    build_s = None
+    with tempfile.TemporaryDirectory() as tmp:
+        for shape in a.shapes.split(","):
+            B, dtype = int(shape.split(":")[0]), shape.split(":")[1]
+            bs = [B // 4, B // 2, B // 4]
+            tb = time.perf_counter()
+            rs = ResidentFeatureSet.from_arrays(feats, tgts, SIZES, bs, frames=T, scaler=sc, augment_type="noise")
+            torch.cuda.synchronize()
+            build_s = build_s or round(time.perf_counter() - tb, 2)
+            np.random.seed(0)
+            ms_a, n = leg_a(rs, B, dtype)
+            leg = {"B": B, "mfma_dtype": dtype, "batch_sizes": bs, "steps_per_epoch": n,
+                   "a_resident_epoch_ms_per_step": round(ms_a, 4)}
+            if not a.only_a:
+                ms_b = leg_b(B, dtype, n)
+                ms_c, wall_c = leg_c(rs, feats, tgts, sc, B, dtype, tmp)
+                leg.update({"b_resident_batch_ms_per_step": round(ms_b, 4),
+                            "a_over_b": round(ms_a / ms_b, 4),
+                            "c_dropin_ms_per_step": round(ms_c, 3), "c_dropin_wall_ms_per_step": round(wall_c, 3),
+                            "c_steps": 20})
+            result["legs"].append(leg)
+            print(json.dumps(leg), flush=True)
+            del rs
+            torch.cuda.empty_cache()
+        if not a.only_a:
+            result["d_get_predictions"] = leg_d(feats, sc, tmp)
+    result["pool"]["build_s"] = build_s
+    result["total_s"] = round(time.perf_counter() - t0, 1)
+    line = json.dumps(result)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(result, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
