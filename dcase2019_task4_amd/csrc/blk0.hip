@@ -603,7 +603,7 @@ __global__ __launch_bounds__(256, (NH == 2 ? 3 : 2)) void k_blk0_fwd(const float
 // NHT: channel slices of the whole block; a workgroup handles NH of them, those from blockIdx.y * NH on (C = 128 runs as two
 // 64-channel halves: the accumulators of all four slices need 290 registers = ONE wave per SIMD with every LDS / MFMA
 // latency of its in-order stream exposed - 197 us against 2 x 53 for the halves at two waves per SIMD)
-// STRICT (fp32 only, debug bit 27 / SED_STRICT_F32=1): the 2 x 10 sums per channel as plain fp32 FMAs on the VALU instead of
+// STRICT (fp32 only, SED_DEBUG_STRICT_F32 / SED_STRICT_F32=1): the 2 x 10 sums per channel as plain fp32 FMAs on the VALU instead of
 // split-bf16 MFMA products - the all-fp32 twin of the `dtype: f32` headline (bench.py extra_configs["mt-f32-strict"]).
 #ifndef BLK0_BWD_OCC16
 #define BLK0_BWD_OCC16 2
@@ -616,7 +616,7 @@ __global__ __launch_bounds__(256, (NH == 2 ? (MODE == 1 ? BLK0_BWD_OCC16 : 2) : 
                                                    const float* __restrict__ wl, const float* __restrict__ dp0, int B,
                                                    int T, int H1, int tiles_per_clip, int n_tiles, int use_drop,
                                                    float p_drop, const uint16_t* __restrict__ mask_in,
-                                                   double* __restrict__ de /* [2][C][10] */, int no_atomic,
+                                                   double* __restrict__ de /* [2][C][10] */,
                                                    const uint4* __restrict__ sg_in = nullptr /* SG: the forward's gate bytes */) {
     __shared__ float xs[XS_H * XS_W];
     __shared__ __attribute__((aligned(16))) float P[4][32 * 12];
@@ -883,7 +883,7 @@ __global__ __launch_bounds__(256, (NH == 2 ? (MODE == 1 ? BLK0_BWD_OCC16 : 2) : 
         const int h = c >> 5, nn = c & 31;
         double v = (double)red[0][which][h][nn][t] + (double)red[1][which][h][nn][t] + (double)red[2][which][h][nn][t] +
                    (double)red[3][which][h][nn][t];
-        if (!no_atomic) atomicAdd(&de[(which * C + 32 * h0 + c) * 10 + t], v);
+        atomicAdd(&de[(which * C + 32 * h0 + c) * 10 + t], v);
     }
 }
 
@@ -997,7 +997,6 @@ static int resident_workgroups(const void* fn, int threads) {
     int per_cu = 0, dev = 0, cus = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, 0) != hipSuccess || per_cu < 1) per_cu = 2;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-    if (g_sed_debug & 8192) fprintf(stderr, "[sed] occupancy: %d workgroups per CU, %d CUs\n", per_cu, cus);
     return cache[fn] = per_cu * cus;
 }
 int launch_blk0_forward(const Geo& g, const float* x, const float* w0, const float* b0, const float* gamma,
@@ -1036,8 +1035,6 @@ int launch_blk0_forward(const Geo& g, const float* x, const float* w0, const flo
     // persistent grid: R full rounds of the workgroups that are resident at once (asked of the runtime per instantiation)
     auto grid_for = [&](const void* fn) {
         const int slots = resident_workgroups(fn, 256), rounds = (nt + slots - 1) / slots;
-        const int per_cu = 0, cus = slots;
-        if (g_sed_debug & 8192) fprintf(stderr, "[sed] blk0 forward: %d resident workgroups, %d tiles, %d rounds\n", per_cu + cus, nt, rounds);
         return (nt + rounds - 1) / rounds;
     };
 #define BLK0_FWD_M(NH, DROP, SAVE, MODE) \
@@ -1089,16 +1086,16 @@ int launch_blk0_backward(const Geo& g, const float* x, const float* w0, const fl
 #define BLK0_YGRID(y) (y)
 #endif
 #define BLK0_BWD(NH, MODE, NHT, GRID) \
-    k_blk0_bwd<NH, MODE, NHT><<<dim3(nt < (GRID) ? nt : (GRID), BLK0_YGRID((NHT) / (NH))), 256, 0, st>>>(x, wz, wl, dp0, g.B, g.T, g.H1, tpc, nt, use_drop, g.p, mask_in, de, g_sed_debug & 1)
+    k_blk0_bwd<NH, MODE, NHT><<<dim3(nt < (GRID) ? nt : (GRID), BLK0_YGRID((NHT) / (NH))), 256, 0, st>>>(x, wz, wl, dp0, g.B, g.T, g.H1, tpc, nt, use_drop, g.p, mask_in, de)
     if (g.C == 64 && g.mode == 1 && sg_in)
-        k_blk0_bwd<2, 1, 2, 0, 1><<<dim3(nt < 512 ? nt : 512, 1), 256, 0, st>>>(x, wz, wl, dp0, g.B, g.T, g.H1, tpc, nt, use_drop, g.p, mask_in, de, g_sed_debug & 1, (const uint4*)sg_in);
+        k_blk0_bwd<2, 1, 2, 0, 1><<<dim3(nt < 512 ? nt : 512, 1), 256, 0, st>>>(x, wz, wl, dp0, g.B, g.T, g.H1, tpc, nt, use_drop, g.p, mask_in, de, (const uint4*)sg_in);
     else if (g.C == 128 && g.mode == 1 && sg_in)
-        k_blk0_bwd<2, 1, 4, 0, 1><<<dim3(nt < (BLK0_GRID128) ? nt : (BLK0_GRID128), BLK0_YGRID(2)), 256, 0, st>>>(x, wz, wl, dp0, g.B, g.T, g.H1, tpc, nt, use_drop, g.p, mask_in, de, g_sed_debug & 1, (const uint4*)sg_in);
+        k_blk0_bwd<2, 1, 4, 0, 1><<<dim3(nt < (BLK0_GRID128) ? nt : (BLK0_GRID128), BLK0_YGRID(2)), 256, 0, st>>>(x, wz, wl, dp0, g.B, g.T, g.H1, tpc, nt, use_drop, g.p, mask_in, de, (const uint4*)sg_in);
     else if (g.C == 64 && g.mode == 1) BLK0_BWD(2, 1, 2, 512);
     else if (g.C == 64 && g.mode == 2) BLK0_BWD(2, 2, 2, 512);
     else if (g.C == 128 && g.mode == 2) BLK0_BWD(2, 2, 4, BLK0_GRID128);
-    else if (g.C == 64 && (g_sed_debug & 134217728))      // debug bit 27: strict fp32 (no split-bf16 products anywhere in the step)
-        k_blk0_bwd<2, 0, 2, 1><<<dim3(nt < 512 ? nt : 512, 1), 256, 0, st>>>(x, wz, wl, dp0, g.B, g.T, g.H1, tpc, nt, use_drop, g.p, mask_in, de, g_sed_debug & 1);
+    else if (g.C == 64 && (g_sed_debug & SED_DEBUG_STRICT_F32))      // strict fp32 (no split-bf16 products anywhere in the step)
+        k_blk0_bwd<2, 0, 2, 1><<<dim3(nt < 512 ? nt : 512, 1), 256, 0, st>>>(x, wz, wl, dp0, g.B, g.T, g.H1, tpc, nt, use_drop, g.p, mask_in, de);
     else if (g.C == 64) BLK0_BWD(2, 0, 2, 512);
     else if (g.C == 128 && g.mode == 1) BLK0_BWD(2, 1, 4, BLK0_GRID128);
     else if (g.C == 128) BLK0_BWD(2, 0, 4, BLK0_GRID128);

@@ -45,7 +45,7 @@ __device__ __forceinline__ int rb_pixel(int q, int dt, int df, int H, int W, int
 // A row block's conv output y (32 pixels x 64 channels) goes global -> registers -> LDS in two separately
 // callable halves, so that the loads of row block k+1 are issued BEFORE the MFMAs of row block k: these kernels
 // run one or two waves per SIMD, and a load consumed right after its issue exposes a full memory round trip
-// (~2 us per row block in the first version; MFMA pipe busy 21 % in k_glu_pool_bwd).
+// (~2 us per row block in the first version; MFMA pipe busy 21 % in round 1's GLU backward).
 struct YTile { float4 v[8]; };
 __device__ __forceinline__ void tile_load(YTile& t, const float* __restrict__ y, int q0, int Q, int H, int W, int Ho,
                                           int Wo, int lane) {
@@ -195,276 +195,8 @@ __global__ __launch_bounds__(256, 2) void k_glu_pool_fwd(const float* __restrict
 
 // (BnBwdPrepArgs, bn_bwd_coef, bn_bwd_prep_body: kernels.h - shared with the conv kernels that consume the result)
 
-__global__ __launch_bounds__(256) void k_glu_pool_bwd(const float* __restrict__ y, const float* __restrict__ bn,
-                                                       const float* __restrict__ wglu, const float* __restrict__ bglu,
-                                                       const float* __restrict__ dp, const float* __restrict__ dp_b,
-                                                       float* __restrict__ dz, double* __restrict__ accg, int H, int W, int Ho, int Wo, int Q,
-                                                       int block_id, int use_drop, float p_drop,
-                                                       const uint16_t* __restrict__ mask_in, int no_atomic) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int n = lane & 31, kh = lane >> 5;
-    float* WsT = smem + 4 * (3 * 32 * ZS);               // Wglu transposed [c][co], stride 65
-    float* zt = smem + wv * (3 * 32 * ZS);
-    float* yt = zt + 32 * ZS;
-    float* dlt = yt + 32 * ZS;
-    TS(0); TSC(14);
-    if (H & 1) {        // the floor-mode pool drops the last row of an odd-height image: its gradient is 0
-        const int per_clip = W * 64, nb = Q / (Ho * Wo);
-        for (int i = blockIdx.x * 256 + tid; i < nb * per_clip; i += gridDim.x * 256) {
-            const int bb = i / per_clip, r = i % per_clip;
-            dz[((size_t)bb * H + (H - 1)) * W * 64 + r] = 0.f;
-        }
-    }
-    for (int e = tid; e < 4096; e += 256) WsT[(e & 63) * ZS + (e >> 6)] = wglu[e];
-    __syncthreads();
-    // forward operand B[k=c][j=co] = Wglu[co][c] lives in registers; the transposed one for dz = dlin @ Wglu,
-    // B[k=co][j=c] = WsT[c][co], is read from LDS per use (conflict-free at stride 65): its 64 registers hold
-    // the next row block's prefetched tile instead
-    float bw[32][2];
-#pragma unroll
-    for (int s = 0; s < 32; ++s) {
-        bw[s][0] = WsT[(2 * s + kh) * ZS + n];
-        bw[s][1] = WsT[(2 * s + kh) * ZS + 32 + n];
-    }
-    const float* BT = WsT + n * ZS + kh;
-    const float bg[2] = {bglu[n], bglu[32 + n]};
-    const float sc = 0.125f * (use_drop ? drop_scale8(p_drop) : 1.0f);
-    (void)block_id;
-    f32x16 dW[2][2];   // [co block][c block]
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b2 = 0; b2 < 2; ++b2)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) dW[a][b2][r] = 0.f;
-    float sdb[2] = {0.f, 0.f}, sdz[2] = {0.f, 0.f}, sdzy[2] = {0.f, 0.f};
-    const int n_rb = (Q + 3) / 4;
-    const float4 bsc = *(const float4*)(bn + 128 + (lane & 15) * 4), bsh = *(const float4*)(bn + 192 + (lane & 15) * 4);
-    // Addressing without per-element divisions or 64-bit arithmetic: po[j] = BYTE offset (into y / dz, both
-    // [pixels][64] fp32 < 4 GB) of the image pixel of pooled pixel q0+j at (dt, df) = (0, 0); MFMA row i of the
-    // row block is pixel po[i>>3]/256 + ((i>>2)&1)*W + (i&3).  Pooled pixels past Q (only in the last row block,
-    // only if Q % 4 != 0) get offset 0 - a harmless load - and are masked where it matters.
-    // (integer division by a run-time value is ~50 instructions with quarter-rate multiplies - 4 of them per row
-    // block were 0.8 us of an in-order wave's time; q < 2^24, so a float reciprocal plus one correction is exact)
-    const float inv_wo = 1.0f / (float)Wo, inv_ho = 1.0f / (float)Ho;
-    auto divmod = [](int a, int d, float inv, int& rem) {
-        int qd = (int)((float)a * inv);
-        int r = a - qd * d;
-        if (r < 0) { r += d; --qd; }
-        if (r >= d) { r -= d; ++qd; }
-        rem = r;
-        return qd;
-    };
-    auto pixel_offsets = [&](int q0, uint32_t (&po)[4]) {
-        int wo, ho;
-        const int t = divmod(q0, Wo, inv_wo, wo);
-        int bb = divmod(t, Ho, inv_ho, ho);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            po[j] = (q0 + j < Q) ? (uint32_t)((bb * H + 2 * ho) * W + 4 * wo) * 256u : 0u;
-            if (++wo == Wo) { wo = 0; if (++ho == Ho) { ho = 0; ++bb; } }
-        }
-    };
-    const uint32_t ld_off = (uint32_t)((lane >> 4) * 64 + (lane & 15) * 4) * 4u;   // tile_load lane: pixel df, 4 channels
-    const uint32_t st_off = (uint32_t)(kh * W * 64 + n) * 4u;                      // D-fragment lane: row dt = kh, channel n
-    YTile yt_n;
-    float gq_n[2][4];
-    uint32_t m_n[2];
-    uint32_t po_n[4];
-    // The next row block's operands are fetched in 8 slices spread over the groups of phase 1 rather than in one
-    // burst: 41 KB per CU issued at once (and by all 256 CUs at the same moment) exceeds what a CU can keep in
-    // flight, and the in-order wave sat ~1.5 us per row block in the ISSUE of those loads.
-    int q_n = 0;                       // first pooled pixel of the row block being prefetched
-    auto prefetch_begin = [&](int rbn, bool valid) {
-        q_n = valid ? rbn * 4 : 0;     // past the end: re-read row block 0 (harmless, never consumed)
-        pixel_offsets(q_n, po_n);
-    };
-    auto prefetch_slice = [&](int k) {
-        yt_n.v[k] = *(const float4*)((const char*)y + (po_n[k >> 1] + (uint32_t)((k & 1) * W) * 256u + ld_off));
-        const int h = k >> 2, jx = k & 3;
-        const int q = q_n + jx;
-        const uint32_t goff = (uint32_t)((q < Q ? q : 0) * 64 + 32 * h + n) * 4u;
-        gq_n[h][jx] = *(const float*)((const char*)dp + goff);
-        if (dp_b) gq_n[h][jx] += *(const float*)((const char*)dp_b + goff);     // second direction plane of the GRU's dX
-        if (q >= Q) gq_n[h][jx] = 0.f;
-        if (jx == 0) m_n[h] = use_drop ? (uint32_t)mask_in[((size_t)(q_n >> 2) * 2 + h) * 64 + lane] : 0xffffu;
-    };
-    auto prefetch = [&](int rbn) {
-        prefetch_begin(rbn, true);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) prefetch_slice(k);
-    };
-    if (blockIdx.x * 4 + wv < n_rb) prefetch(blockIdx.x * 4 + wv);
-    TS(1);
-    int ts_k = 2;
-    (void)ts_k;
-    // one row block; FULL = all four pooled pixels exist (always, unless it is the last row block and Q % 4 != 0)
-    auto body = [&](int rb, auto full_c) {
-        constexpr bool FULL = decltype(full_c)::value;
-        const int q0 = rb * 4;
-        tile_store<true>(yt_n, bsc, bsh, zt, yt, q0, FULL ? q0 + 4 : Q, lane);
-        TS(ts_k); ++ts_k;
-        float gq_c[2][4];
-        uint32_t m_c[2];
-        uint32_t po[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) po[j] = po_n[j] + st_off;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            m_c[h] = m_n[h];
-#pragma unroll
-            for (int jx = 0; jx < 4; ++jx) gq_c[h][jx] = gq_n[h][jx] * sc;
-        }
-        prefetch_begin(rb + gridDim.x * 4, rb + gridDim.x * 4 < n_rb);
-        if (ts_k == 3) TS(7);
-        // The three MFMA phases (64 x v_mfma_f32_32x32x2 each) carry the element-wise work of the row block in
-        // their shadow: one wave per SIMD issues in order, so VALU / LDS work placed BETWEEN independent MFMAs is
-        // free, while the same work in a phase of its own leaves the MFMA pipe idle (21 % busy in the first version).
-        // ---- phase 1: lin = z @ Wglu^T   ||   sigma(z), dlin = g*sigma -> LDS, t = g*sigma*(1-sigma) -------------
-        f32x16 lin[2];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { lin[0][r] = 0.f; lin[1][r] = 0.f; }
-        float dzg[2][16];
-        {
-            // Groups of 4 K-steps (8 MFMAs = 512 MFMA-pipe cycles) carry 4 elements' VALU work side by side: one
-            // element's mul -> exp -> add -> rcp -> mul -> ds_write is a dependent chain of ~100 cycles on a lone
-            // in-order wave, four of them interleave.  The LDS operands of group g+1 are read during group g.
-            const float* A = zt + n * ZS + kh;
-            float a_c[4], z_c[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { a_c[u] = A[2 * u]; z_c[u] = zt[mfma32_row(u, lane) * ZS + n]; }
-#pragma unroll
-            for (int g4 = 0; g4 < 8; ++g4) {
-                float a_n[4] = {0.f, 0.f, 0.f, 0.f}, z_n[4] = {0.f, 0.f, 0.f, 0.f};
-                if (g4 + 1 < 8) {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int s1 = 4 * (g4 + 1) + u;
-                        a_n[u] = A[2 * s1];
-                        z_n[u] = zt[mfma32_row(s1 & 15, lane) * ZS + 32 * (s1 >> 4) + n];
-                    }
-                }
-                prefetch_slice(g4);
-                float sg[4], gg[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int s = 4 * g4 + u, h = s >> 4, r = s & 15;
-                    lin[0] = mfma32(a_c[u], bw[s][0], lin[0]);
-                    lin[1] = mfma32(a_c[u], bw[s][1], lin[1]);
-                    gg[u] = ((m_c[h] >> r) & 1u) ? gq_c[h][r >> 2] : 0.f;
-                    sg[u] = sigmoidf_fast(z_c[u]);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int s = 4 * g4 + u, h = s >> 4, r = s & 15;
-                    const float dl = gg[u] * sg[u];
-                    dlt[mfma32_row(r, lane) * ZS + 32 * h + n] = dl;
-                    sdb[h] += dl;
-                    dzg[h][r] = dl * (1.0f - sg[u]);
-                    a_c[u] = a_n[u]; z_c[u] = z_n[u];
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        if (ts_k == 3) TS(11);
-        // ---- phase 2: dz_lin = dlin @ Wglu   ||   gate path dzg = t * (lin + b) -----------------------------------
-        f32x16 acc[2];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { acc[0][r] = 0.f; acc[1][r] = 0.f; }
-        {
-            const float* A = dlt + n * ZS + kh;
-            float a_c = A[0], b0_c = BT[0], b1_c = BT[32 * ZS];
-#pragma unroll
-            for (int s = 0; s < 32; ++s) {
-                const int h = s >> 4, r = s & 15;
-                float a_n = 0.f, b0_n = 0.f, b1_n = 0.f;
-                if (s + 1 < 32) { a_n = A[2 * (s + 1)]; b0_n = BT[2 * (s + 1)]; b1_n = BT[32 * ZS + 2 * (s + 1)]; }
-                acc[0] = mfma32(a_c, b0_c, acc[0]);
-                acc[1] = mfma32(a_c, b1_c, acc[1]);
-                dzg[h][r] *= lin[h][r] + bg[h];
-                a_c = a_n; b0_c = b0_n; b1_c = b1_n;
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        if (ts_k == 3) TS(12);
-        // vmcnt counts loads and stores alike and cannot tell them apart: claim the prefetched registers HERE, while
-        // only the (long issued) loads are outstanding - at the top of the next row block the same wait would also
-        // drain the 32 dz stores per lane that phase 3 is about to issue (a full store round trip per row block)
-#pragma unroll
-        for (int it = 0; it < 8; ++it)
-            asm volatile("" : "+v"(yt_n.v[it].x), "+v"(yt_n.v[it].y), "+v"(yt_n.v[it].z), "+v"(yt_n.v[it].w));
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            asm volatile("" : "+v"(gq_n[h][0]), "+v"(gq_n[h][1]), "+v"(gq_n[h][2]), "+v"(gq_n[h][3]), "+v"(m_n[h]));
-        }
-        // ---- phase 3: dWglu += dlin^T z   ||   dz = dz_lin + dzg -> global, BatchNorm-backward sums ----------------
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            const int mrow = 2 * s + kh;
-            const float a0 = dlt[mrow * ZS + n], a1 = dlt[mrow * ZS + 32 + n];
-            const float b0 = zt[mrow * ZS + n], b1 = zt[mrow * ZS + 32 + n];
-            dW[0][0] = mfma32(a0, b0, dW[0][0]);
-            dW[0][1] = mfma32(a0, b1, dW[0][1]);
-            dW[1][0] = mfma32(a1, b0, dW[1][0]);
-            dW[1][1] = mfma32(a1, b1, dW[1][1]);
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int r = s, c = 32 * h + n;
-                const int i = mfma32_row(r, lane);
-                const float v = acc[h][r] + dzg[h][r];
-                if (FULL || q0 + (r >> 2) < Q) {
-                    *(float*)((char*)dz + (po[r >> 2] + (uint32_t)(((r & 3) * 64 + 32 * h) * 4))) = v;
-                    sdz[h] += v;
-                    sdzy[h] += v * yt[i * ZS + c];
-                }
-            }
-        }
-        if (ts_k == 3) TS(13);
-    };
-    for (int rb = blockIdx.x * 4 + wv; rb < n_rb; rb += gridDim.x * 4) {
-        if (rb * 4 + 3 < Q) body(rb, std::true_type{});
-        else body(rb, std::false_type{});
-    }
-    // ---- reduce across the 4 waves through LDS, then fp64 atomics ------------------------------
-    TS(8);
-    __syncthreads();
-    TS(9);
-    float* red = smem;   // needs 4 * 4096 floats = 64 KB <= 4 * 3 * 32 * 65 * 4 = 99,840 B
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b2 = 0; b2 < 2; ++b2)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) red[wv * 4096 + (32 * a + mfma32_row(r, lane)) * 64 + 32 * b2 + n] = dW[a][b2][r];
-    __syncthreads();
-    for (int i = tid; i < 4096 && !no_atomic; i += 256)
-        atomicAdd(&accg[i], (double)red[i] + (double)red[4096 + i] + (double)red[8192 + i] + (double)red[12288 + i]);
-    __syncthreads();
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const float v0 = sdb[h] + __shfl_xor(sdb[h], 32);
-        const float v1 = sdz[h] + __shfl_xor(sdz[h], 32);
-        const float v2 = sdzy[h] + __shfl_xor(sdzy[h], 32);
-        if (kh == 0) {
-            red[(wv * 3 + 0) * 64 + 32 * h + n] = v0;
-            red[(wv * 3 + 1) * 64 + 32 * h + n] = v1;
-            red[(wv * 3 + 2) * 64 + 32 * h + n] = v2;
-        }
-    }
-    __syncthreads();
-    if (tid < 192) {
-        const int which = tid >> 6, c = tid & 63;
-        double v = 0;
-#pragma unroll
-        for (int w2 = 0; w2 < 4; ++w2) v += (double)red[(w2 * 3 + which) * 64 + c];
-        if (!no_atomic) atomicAdd(&accg[4096 + which * 64 + c], v);
-    }
-    TS(10); TSC(15);
-}
-
-// ---- 8-wave variant: two waves per SIMD share one row block, split by channel half ---------------------------------
-// k_glu_pool_bwd above runs one wave per SIMD (415 registers) and that wave issues in order: whatever VALU / LDS /
+// ---- backward: two waves per SIMD share one row block, split by channel half ---------------------------------------
+// Round 1's k_glu_pool_bwd (one wave per SIMD, 415 registers; removed) issued in order: whatever VALU / LDS /
 // global work is not perfectly interleaved with its MFMAs leaves the MFMA pipe idle (phase timestamps: 9.5 us per row
 // block for 5.7 us of MFMAs).  Here waves w and w+4 - same SIMD - work on the SAME row block: wave half h owns the 32
 // channels [32h, 32h+32) everywhere a channel index is an OUTPUT (lin columns, dz columns, dW rows), so each wave has
@@ -695,7 +427,7 @@ __global__ __launch_bounds__(512, 1) void k_glu_pool_bwd8(const float* __restric
 }
 
 // BatchNorm-backward coefficients + the block's parameter gradients: a kernel of its own again.  Folding it into the
-// last workgroup of k_glu_pool_bwd (ticket after a workgroup-scope release) was a RACE: about 1 step in 10 the last
+// last workgroup of the GLU backward (ticket after a workgroup-scope release) was a RACE: about 1 step in 10 the last
 // workgroup read the Sdz / Sdzy accumulators before every other workgroup's fp64 atomics had been performed
 // (tools/determinism.py: bn1 / conv1 / block-0 gradients off by up to 7e-3); ordering those atomics device-wide needs
 // __threadfence(), whose L2 write-back of the 31 MB of dz just produced costs more (17 us) than this launch (5 us).
@@ -719,14 +451,14 @@ int launch_glu_pool_fwd(const float* y, const double* stat, double N, const floa
 }
 
 int launch_glu_pool_bwd(const float* y, const float* bn, const float* wglu, const float* bglu, const float* dp,
-                        const float* dp_b, float* dz, double* acc, int zero_acc, int B, int H, int W, int block_id, int use_drop, float p_drop,
+                        const float* dp_b, float* dz, double* acc, int zero_acc, int B, int H, int W, int use_drop, float p_drop,
                         const uint16_t* mask_in, const float* gamma, float* coef, float* g_gamma, float* g_beta, float* g_wglu,
                         float* g_bglu, float* g_convb, BnBwdPrepArgs* prep_out, hipStream_t st) {
     const int Ho = H / 2, Wo = W / 4, Q = B * Ho * Wo;
     const size_t lds = (size_t)(4 * 3 * 32 * ZS + 64 * ZS) * sizeof(float);
     static thread_local SedAttrOnce attr_done;
     if (attr_done.need()) {
-        SED_CHECK_HIP(hipFuncSetAttribute((const void*)k_glu_pool_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        SED_CHECK_HIP(hipFuncSetAttribute((const void*)k_glu_pool_bwd8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
     if (zero_acc) SED_CHECK_HIP(hipMemsetAsync(acc, 0, GLUACC_N * sizeof(double), st));
     BnBwdPrepArgs a;
@@ -735,15 +467,7 @@ int launch_glu_pool_bwd(const float* y, const float* bn, const float* wglu, cons
     const int n_rb = (Q + 3) / 4;
     int grid = (n_rb + 3) / 4;
     if (grid > 256) grid = 256;
-    if (g_sed_debug & 16) {          // single-wave-per-SIMD variant (A/B timing)
-        k_glu_pool_bwd<<<grid, 256, lds, st>>>(y, bn, wglu, bglu, dp, dp_b, dz, acc, H, W, Ho, Wo, Q, block_id, use_drop, p_drop, mask_in, g_sed_debug & 1);
-    } else {
-        static thread_local SedAttrOnce attr8;
-        if (attr8.need()) {
-            SED_CHECK_HIP(hipFuncSetAttribute((const void*)k_glu_pool_bwd8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        }
-        k_glu_pool_bwd8<<<grid, 512, lds, st>>>(y, bn, wglu, bglu, dp, dp_b, dz, acc, H, W, Ho, Wo, Q, use_drop, p_drop, mask_in);
-    }
+    k_glu_pool_bwd8<<<grid, 512, lds, st>>>(y, bn, wglu, bglu, dp, dp_b, dz, acc, H, W, Ho, Wo, Q, use_drop, p_drop, mask_in);
     SED_CHECK_LAUNCH();
     if (prep_out) {             // the conv dgrad / wgrad kernels derive the coefficients themselves
         *prep_out = a;

@@ -118,7 +118,7 @@ WsLayout make_ws_layout(const Geo& g);
 #ifndef SED_GRU_SPLITK
 #define SED_GRU_SPLITK 16
 #endif
-// fp64 accumulators of k_glu_pool_bwd: [0,4096) dWglu[co][c]; [4096,4160) dbglu; [4160,4224) sum dz; [4224,4288) sum dz*y;
+// fp64 accumulators of k_glu_pool_bwd8: [0,4096) dWglu[co][c]; [4096,4160) dbglu; [4160,4224) sum dz; [4224,4288) sum dz*y;
 // [4288] ticket of the last-workgroup epilogue (uint32 in a double slot); padded to a multiple of 8
 #define SED_GLUACC_N 4296
 #define SED_WINO_OFF (9 * 4096)   // conv weight panels: [9 taps][64][64] followed by the 16 x 64 x 64 Winograd-domain weights
@@ -163,7 +163,7 @@ __device__ __forceinline__ TileWalk xcd_walk(int n_tiles) {
 #endif
     return {w, n_tiles, g};
 }
-// debug knob (sed_debug_set): bit 0 = skip the fp64 atomics of the reduction epilogues (timing experiments only)
+// debug knob (sed_debug_set): the SED_DEBUG_* bits of include/dcase_sed.h
 extern int g_sed_debug;
 
 // mfma_f32_32x32x2f32 fragment maps (cdna_hip_programming.md section 3):

@@ -158,7 +158,7 @@ __global__ __launch_bounds__(256) void k_conv3x3(const float* __restrict__ in0, 
 
 
 // ---- direct (9-tap) weight-stationary persistent kernel for W = 16 -------------------------------------------
-// Kept as the A/B baseline of the Winograd kernel below (debug bit 6); it was the block-1 forward / dgrad kernel until
+// Kept as the reference of the Winograd kernel below (SED_DEBUG_DIRECT_CONV); it was the block-1 forward / dgrad kernel until
 // r01_i.  PMC on the tile kernel above (k_conv3x3<16,..>): MFMA pipe busy 55 % of the kernel, waves parked in
 // s_waitcnt / s_barrier 38 % of their cycles - the per-tap weight slab hand-over (LDS double buffer + barrier) and the
 // un-overlapped halo staging.  Here the WEIGHTS stay in registers for the whole life of a persistent workgroup:
@@ -630,7 +630,7 @@ static int conv16_ws_launch(const float* in0, const float* in1, const float* coe
 }
 
 // Winograd F(2x2, 3x3): the default for both 64 -> 64 convolutions.  Block 1: 59 / 57 us per launch (forward / dgrad)
-// against 91 / 90 us for the direct 8-wave kernel; bit 6 of the debug knob selects the direct kernels.
+// against 91 / 90 us for the direct 8-wave kernel; SED_DEBUG_DIRECT_CONV selects the direct kernels.
 template <int TW, int MODE>
 static int conv_wino_launch(const float* in0, const float* in1, const float* coef, const float* wpk, const float* bias,
                             float* out, double* stat, int B, int H, const BnBwdPrepArgs* prep, hipStream_t st) {
@@ -757,7 +757,6 @@ __global__ __launch_bounds__(256) void k_conv3x3_wgrad(const float* __restrict__
     TS(13); TSC(15);
 }
 
-#ifdef SED_AB   // A/B baseline kernels: only in `make EXTRA=-DSED_AB` builds (the shipped library carries the product path only)
 // ---- block-1 wgrad with the staging hidden under the MFMAs ---------------------------------------------------
 // Phase timestamps of the kernel above at B = 24 (tools/ts_kernel.py): 18 us of MFMAs per tile (95 % of the
 // pipe's rate) but 7.7 us of staging in front of every tile - all 256 workgroups stage at the same moment, so the
@@ -767,6 +766,7 @@ __global__ __launch_bounds__(256) void k_conv3x3_wgrad(const float* __restrict__
 // BatchNorm-backward affine applied) at the start of row c+1, i.e. 2 us later; one LDS-only barrier per tile.
 // (An 8-wave variant - two waves per SIMD splitting the 9 taps 5 + 4, the recipe that helped the forward / dgrad kernels -
 // measured exactly the same, alone and in the step, and was dropped.)
+// Superseded by k_wgrad_wino<16> below; kept as the block-1 reference of SED_DEBUG_DIRECT_WGRAD (tests/test_gpu_parity.py).
 struct Wg16 {
     static constexpr int TH = 8, TW = 16, HW = 18, HH = 10;
     static constexpr int XH_FLOATS = HH * HW * 64, DY_FLOATS = 128 * 64, BUF_FLOATS = XH_FLOATS + DY_FLOATS;
@@ -886,8 +886,6 @@ __global__ __launch_bounds__(256) void k_wgrad16_db(const float* __restrict__ dz
         }
     TS(13); TSC(15);
 }
-
-#endif  // SED_AB
 
 // ---- block-1 wgrad in the Winograd domain -----------------------------------------------------------------------------
 // dW = G^T [ sum over 2x2 output blocks of (B^T d B) (.) (A dY A^T) ] G: 16 multiplies per block and (ci, co) pair instead
@@ -1463,28 +1461,16 @@ static int conv_launch_t(const float* in0, const float* in1, const float* coef, 
     return SED_OK;
 }
 
-#ifdef SED_AB
-#define SED_AB_FLAGS(mask) (g_sed_debug & (mask))
-#else
-#define SED_AB_FLAGS(mask) 0      // the direct (9-tap) A/B kernels are not compiled into the product library
-#endif
-extern "C" int sed_build_flags(void) {
-#ifdef SED_AB
-    return 1;
-#else
-    return 0;
-#endif
-}
+// the direct kernels (SED_DEBUG_DIRECT_CONV / SED_DEBUG_DIRECT_WGRAD) are in every build
+extern "C" int sed_build_flags(void) { return 1; }
 
 int launch_conv_fwd(const float* in, const float* wpk, const float* bias, float* y, double* stat, int zero_stat, int B,
                     int H, int W, hipStream_t st) {
     if (stat && zero_stat) SED_CHECK_HIP(hipMemsetAsync(stat, 0, 128 * sizeof(double), st));
-#ifdef SED_AB
-    const bool direct = (g_sed_debug & (2 | 64)) != 0;          // A/B timing only: the 9-tap kernels
-    if (direct && W == 16) return (g_sed_debug & 2) ? conv_launch_t<16, 0, 1>(in, nullptr, nullptr, wpk, bias, y, stat, B, H, st)
-                                                    : conv16_ws_launch<0>(in, nullptr, nullptr, wpk, bias, y, stat, B, H, st);
-    if (direct && W == 4) return conv_launch_t<4, 0, 2>(in, nullptr, nullptr, wpk, bias, y, stat, B, H, st);
-#endif
+    if (g_sed_debug & SED_DEBUG_DIRECT_CONV) {
+        if (W == 16) return conv16_ws_launch<0>(in, nullptr, nullptr, wpk, bias, y, stat, B, H, st);
+        if (W == 4) return conv_launch_t<4, 0, 2>(in, nullptr, nullptr, wpk, bias, y, stat, B, H, st);
+    }
     if (W == 16) return conv_wino_launch<16, 0>(in, nullptr, nullptr, wpk, bias, y, stat, B, H, nullptr, st);
     if (W == 4) return conv_wino_launch<4, 0>(in, nullptr, nullptr, wpk, bias, y, stat, B, H, nullptr, st);
     sed_set_error("conv: unsupported width %d", W);
@@ -1493,13 +1479,11 @@ int launch_conv_fwd(const float* in, const float* wpk, const float* bias, float*
 
 int launch_conv_dgrad(const float* dz, const float* yin, const float* coef, const float* wpkT, float* dx, int B, int H,
                       int W, const BnBwdPrepArgs* prep, hipStream_t st) {
-#ifdef SED_AB
-    const bool direct = (g_sed_debug & (4 | 64)) != 0;          // A/B timing only: the 9-tap kernels
-    SED_CHECK_ARG(!(direct && prep), "conv dgrad: in-kernel BatchNorm-backward coefficients need the Winograd kernel");
-    if (direct && W == 16) return (g_sed_debug & 4) ? conv_launch_t<16, 1, 1>(dz, yin, coef, wpkT, nullptr, dx, nullptr, B, H, st)
-                                                    : conv16_ws_launch<1>(dz, yin, coef, wpkT, nullptr, dx, nullptr, B, H, st);
-    if (direct && W == 4) return conv_launch_t<4, 1, 2>(dz, yin, coef, wpkT, nullptr, dx, nullptr, B, H, st);
-#endif
+    if (g_sed_debug & SED_DEBUG_DIRECT_CONV) {
+        SED_CHECK_ARG(!prep, "conv dgrad: in-kernel BatchNorm-backward coefficients need the Winograd kernel");
+        if (W == 16) return conv16_ws_launch<1>(dz, yin, coef, wpkT, nullptr, dx, nullptr, B, H, st);
+        if (W == 4) return conv_launch_t<4, 1, 2>(dz, yin, coef, wpkT, nullptr, dx, nullptr, B, H, st);
+    }
     if (W == 16) return conv_wino_launch<16, 1>(dz, yin, coef, wpkT, nullptr, dx, nullptr, B, H, prep, st);
     if (W == 4) return conv_wino_launch<4, 1>(dz, yin, coef, wpkT, nullptr, dx, nullptr, B, H, prep, st);
     sed_set_error("conv dgrad: unsupported width %d", W);
@@ -1511,23 +1495,11 @@ static int wgrad_launch_t(const float* dz, const float* yin, const float* coef, 
                           int n_blocks, float* g_w, int B, int H, const BnBwdPrepArgs* prep, hipStream_t st) {
     BnBwdPrepArgs pa = {};
     if (prep) pa = *prep;
-#ifdef SED_AB
-    using Cfg = WgCfg<TW>;
-    static thread_local SedAttrOnce attr_done;
-    if (attr_done.need()) {
-        SED_CHECK_HIP(hipFuncSetAttribute((const void*)k_conv3x3_wgrad<TW, TS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)Cfg::LDS_BYTES));
-    }
-    const int tpc = (H + Cfg::TH - 1) / Cfg::TH, nt = B * tpc;
-    int nb = nt < n_blocks ? nt : n_blocks;
-#else
-    int nb = 0;
-#endif
-    // block 1: the double-buffered kernel (15 % faster alone; in the step, next to dgrad on the other stream, 1.143 vs
-    // 1.162 ms per step although its 154 KB of LDS keep any other workgroup off its CU); bit 3 of the debug knob = old
-    // default: Winograd-domain kernel (block 1: operator 65 us against 105 us for the direct double-buffered kernel); bits 3 / 7
-    // of the debug knob bring the direct kernels back (bit 7 = k_wgrad16_db for block 1, bit 3 = the tile kernel)
-    if (TW == 4 && !SED_AB_FLAGS(8 | 128) && !(g_sed_debug & 67108864)) {      // (debug bit 26: k_wgrad_wino<4>, the slab form, A/B)
+    // default: Winograd-domain kernel (block 1: operator 65 us against 105 us for the direct double-buffered kernel), and the
+    // output-stationary one for block 2 (SED_DEBUG_SLAB_WGRAD: k_wgrad_wino<4>, the slab form); SED_DEBUG_DIRECT_WGRAD brings
+    // the direct kernels back (k_wgrad16_db for block 1, the tile kernel for block 2)
+    const bool direct = (g_sed_debug & SED_DEBUG_DIRECT_WGRAD) != 0;
+    if (TW == 4 && !direct && !(g_sed_debug & SED_DEBUG_SLAB_WGRAD)) {
         using CW = WgW<4>;
         static thread_local SedAttrOnce attro;
         if (attro.need()) {
@@ -1544,7 +1516,8 @@ static int wgrad_launch_t(const float* dz, const float* yin, const float* coef, 
         SED_CHECK_LAUNCH();
         return SED_OK;
     }
-    if (!SED_AB_FLAGS(8 | 128)) {
+    int nb;
+    if (!direct) {
         using CW = WgW<TW>;
         static thread_local SedAttrOnce attrw;
         if (attrw.need()) {
@@ -1554,18 +1527,25 @@ static int wgrad_launch_t(const float* dz, const float* yin, const float* coef, 
         const int tpcw = (H + CW::TH - 1) / CW::TH, ntw = B * tpcw;
         nb = ntw < n_blocks ? ntw : n_blocks;
         k_wgrad_wino<TW><<<nb, 512, CW::LDS_BYTES, st>>>(dz, yin, coef, xin, part, H, tpcw, ntw, pa);
-    }
-#ifdef SED_AB
-    else if (TW == 16 && TS == 1 && !(g_sed_debug & 8)) {
-        static thread_local SedAttrOnce attr16;
-        if (attr16.need()) {
-            SED_CHECK_HIP(hipFuncSetAttribute((const void*)k_wgrad16_db, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Wg16::LDS_BYTES));
-        }
-        k_wgrad16_db<<<nb, 256, Wg16::LDS_BYTES, st>>>(dz, yin, coef, xin, part, H, tpc, nt);
     } else {
-        k_conv3x3_wgrad<TW, TS><<<dim3(nb, TS), 256, Cfg::LDS_BYTES, st>>>(dz, yin, coef, xin, part, B, H, tpc, nt, pa);
+        using Cfg = WgCfg<TW>;
+        const int tpc = (H + Cfg::TH - 1) / Cfg::TH, nt = B * tpc;
+        nb = nt < n_blocks ? nt : n_blocks;
+        if constexpr (TW == 16) {
+            static thread_local SedAttrOnce attr16;
+            if (attr16.need()) {
+                SED_CHECK_HIP(hipFuncSetAttribute((const void*)k_wgrad16_db, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Wg16::LDS_BYTES));
+            }
+            k_wgrad16_db<<<nb, 256, Wg16::LDS_BYTES, st>>>(dz, yin, coef, xin, part, H, tpc, nt);
+        } else {
+            static thread_local SedAttrOnce attr_done;
+            if (attr_done.need()) {
+                SED_CHECK_HIP(hipFuncSetAttribute((const void*)k_conv3x3_wgrad<TW, TS>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                  (int)Cfg::LDS_BYTES));
+            }
+            k_conv3x3_wgrad<TW, TS><<<dim3(nb, TS), 256, Cfg::LDS_BYTES, st>>>(dz, yin, coef, xin, part, B, H, tpc, nt, pa);
+        }
     }
-#endif
     SED_CHECK_LAUNCH();
     k_wgrad_reduce<<<9 * 4096 / 64, 256, 0, st>>>(part, nb, g_w);
     SED_CHECK_LAUNCH();
@@ -1574,7 +1554,7 @@ static int wgrad_launch_t(const float* dz, const float* yin, const float* coef, 
 
 int launch_conv_wgrad(const float* dz, const float* yin, const float* coef, const float* xin, float* part, int n_blocks,
                       float* g_w, int B, int H, int W, const BnBwdPrepArgs* prep, hipStream_t st) {
-    SED_CHECK_ARG(!(prep && W == 16 && SED_AB_FLAGS(8 | 128)), "conv wgrad: in-kernel BatchNorm-backward coefficients need the default kernels");
+    SED_CHECK_ARG(!(prep && W == 16 && (g_sed_debug & SED_DEBUG_DIRECT_WGRAD)), "conv wgrad: in-kernel BatchNorm-backward coefficients need the default kernels");
     if (W == 16) return wgrad_launch_t<16, 1>(dz, yin, coef, xin, part, n_blocks, g_w, B, H, prep, st);
     if (W == 4) return wgrad_launch_t<4, 3>(dz, yin, coef, xin, part, n_blocks, g_w, B, H, prep, st);
     sed_set_error("conv wgrad: unsupported width %d", W);

@@ -2,7 +2,7 @@
 //
 // Mirrors the operator sequence of CRNN.forward (baseline/models/CRNN.py:59-84):
 //   conv block 0 (blk0.hip, fully fused) -> [conv3x3 + BN stats (conv.hip) -> BN/GLU/dropout/pool
-//   (bnglu.hip)] x 2 -> 2-layer BiGRU (gru.hip: input projection + recurrence per layer) -> heads (heads.hip)
+//   (bnglu.hip)] x 2 -> 2-layer BiGRU (gru4.hip: input projection + recurrence per layer) -> heads (heads.hip)
 // All launches go to the caller's stream; no allocation, no synchronisation.
 #include <stdarg.h>
 #include <map>
@@ -96,7 +96,7 @@ CtxLayout make_ctx_layout(const Geo& g) {
     put(L.wpk2, (9 + 16) * 4096 * 4); put(L.wpkT2, (9 + 16) * 4096 * 4); put(L.y2, n1 * 4); put(L.bn2, 256 * 4); put(L.p2, n2 * 4);
     const size_t bt = (size_t)g.B * g.T3;
     for (int l = 0; l < 2; ++l) {
-        put(L.gates[l], bt * 512 * 4); put(L.out[l], bt * 128 * 4);      // (gi only exists in LDS, gru.hip)
+        put(L.gates[l], bt * 512 * 4); put(L.out[l], bt * 128 * 4);      // (gi only exists in LDS, gru4.hip)
     }
     put(L.logits_s, bt * g.NC * 4); put(L.strong_sv, bt * g.NC * 4);
     put(L.weak_sv, (size_t)g.B * g.NC * 4); put(L.den_sv, (size_t)g.B * g.NC * 4);
@@ -188,8 +188,13 @@ extern "C" int sed_crnn_ctx_view(const sed_dims* d, const char* name, size_t* of
 struct SideStream {
     hipStream_t s = nullptr;
     hipEvent_t fork = nullptr, join = nullptr;          // backward
-    hipStream_t s2 = nullptr;                           // second helper: the GRU / heads weight-gradient GEMMs
-    hipEvent_t join2 = nullptr;
+    // A second stream + event, created and never used.  They served a removed A/B schedule (a helper stream of their own
+    // for the GRU weight gradients), but the streams a process creates decide which hardware queue the HIP runtime gives
+    // each later stream, and without these two the waveform front-end's captured step crashed inside hipGraphLaunch when
+    // two data-parallel ranks shared one GPU (tests/test_gpu_dp.py::test_waveform_front_end_world2).  Kept, in the same
+    // creation order, until that runtime behaviour is understood.
+    hipStream_t idle = nullptr;
+    hipEvent_t idle_ev = nullptr;
     bool ok = false;
 };
 static std::mutex g_side_mu;
@@ -209,8 +214,8 @@ static SideStream& side_stream(hipStream_t caller) {
         if (hipStreamCreateWithFlags(&slot->s, hipStreamNonBlocking) == hipSuccess &&
             hipEventCreateWithFlags(&slot->fork, hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&slot->join, hipEventDisableTiming) == hipSuccess &&
-            hipStreamCreateWithFlags(&slot->s2, hipStreamNonBlocking) == hipSuccess &&
-            hipEventCreateWithFlags(&slot->join2, hipEventDisableTiming) == hipSuccess)
+            hipStreamCreateWithFlags(&slot->idle, hipStreamNonBlocking) == hipSuccess &&
+            hipEventCreateWithFlags(&slot->idle_ev, hipEventDisableTiming) == hipSuccess)
             slot->ok = true;
     }
     return *slot;
@@ -223,11 +228,11 @@ extern "C" int sed_stream_prepare(void* stream) {
     }
     return SED_OK;
 }
-// Releases what sed_stream_prepare / first use created for `stream` on the current device: both helper streams, the three
+// Releases what sed_stream_prepare / first use created for `stream` on the current device: the helper streams, their
 // events and a pending fork hook.  The caller guarantees that no work of the library is in flight or being captured on the
 // stream (synchronise it first); the stream can be prepared again afterwards.  A caller stream that was never prepared is a
 // no-op.  hipStreamDestroy on a helper stream that still has work queued would complete it asynchronously, which is why the
-// helpers are synchronised here first - this is the ONE entry point of the library that blocks the host.
+// helper is synchronised here first - this is the ONE entry point of the library that blocks the host.
 extern "C" int sed_stream_release(void* stream) {
     int dev = 0;
     SED_CHECK_HIP(hipGetDevice(&dev));
@@ -243,10 +248,10 @@ extern "C" int sed_stream_release(void* stream) {
     int rc = SED_OK;
     auto note = [&](hipError_t e) { if (e != hipSuccess && rc == SED_OK) { sed_set_error("sed_stream_release: %s", hipGetErrorString(e)); rc = SED_ERR_LAUNCH; } };
     if (sd->s) { note(hipStreamSynchronize(sd->s)); note(hipStreamDestroy(sd->s)); }
-    if (sd->s2) { note(hipStreamSynchronize(sd->s2)); note(hipStreamDestroy(sd->s2)); }
+    if (sd->idle) note(hipStreamDestroy(sd->idle));
     if (sd->fork) note(hipEventDestroy(sd->fork));
     if (sd->join) note(hipEventDestroy(sd->join));
-    if (sd->join2) note(hipEventDestroy(sd->join2));
+    if (sd->idle_ev) note(hipEventDestroy(sd->idle_ev));
     delete sd;
     return rc;
 }
@@ -413,9 +418,9 @@ static int crnn_backward_impl(const sed_dims* d, const float* params, const floa
         SED_CHECK_ARG(!(g.p > 0.f) || seed_dev, "sed_crnn_backward: dropout enabled but seed_dev is null");
         hipStream_t st0 = (hipStream_t)stream;
         SideStream& sd0 = side_stream(st0);
-        // (debug bit 30: no helper stream - every kernel on the caller's stream, for near-solo kernel times under rocprofv3)
+        // (SED_DEBUG_NO_SIDE_STREAM: every kernel on the caller's stream, for near-solo kernel times under rocprofv3)
         return gen_backward(g, P, params, x, seed_dev, ctx, ctx_bytes, d_strong, d_weak, grads, ws, ws_bytes, parts, st0,
-                            (sd0.ok && !(g_sed_debug & 1073741824)) ? sd0.s : st0, sd0.fork, sd0.join, (sd0.ok && (g_sed_debug & 2048)) ? sd0.s2 : nullptr, sd0.join2, hl, ho);
+                            (sd0.ok && !(g_sed_debug & SED_DEBUG_NO_SIDE_STREAM)) ? sd0.s : st0, sd0.fork, sd0.join, hl, ho);
     }
     const CtxLayout L = make_ctx_layout(g);
     const WsLayout W = make_ws_layout(g);
@@ -428,9 +433,9 @@ static int crnn_backward_impl(const sed_dims* d, const float* params, const floa
     hipStream_t st = (hipStream_t)stream;
     const int BT = g.B * g.T3;
     SideStream& sd = side_stream(st);
-    hipStream_t ss = (sd.ok && !(g_sed_debug & 1073741824)) ? sd.s : st;       // without a side stream everything stays on the caller's
+    hipStream_t ss = (sd.ok && !(g_sed_debug & SED_DEBUG_NO_SIDE_STREAM)) ? sd.s : st;       // without a side stream everything stays on the caller's
     const bool defer_gru_w = (parts & 4) != 0;           // parts == 5: the caller runs them later (parts == 8)
-    bool forked = false, forked2 = false;
+    bool forked = false;
 
     // weight + bias gradients of a GRU layer, both directions (split-K MFMA GEMMs, low occupancy):
     //   dW_ih[g][i] = sum_bt dgi[bt][g] input[bt][i],  db_ih[g] = sum_bt dgi[bt][g]
@@ -453,20 +458,19 @@ static int crnn_backward_impl(const sed_dims* d, const float* params, const floa
         for (int l = g.L - 1; l >= 0; --l) SED_TRY(gru_weight_grads_layer(l, s2));
         return SED_OK;
     };
-    // Debug bit 14 (timing experiment, measured twice and rejected): each layer's weight-gradient GEMMs right behind that
-    // layer's recurrence kernel on the side stream - the upper layer's next to the lower layer's recurrence (48 workgroups
-    // on 256 CUs) - instead of between the two conv weight-gradient kernels.  Round 2, with the four-SIMD recurrence:
-    // 0.816 ms against 0.766 ms per step.  Every extra cross-stream edge of the captured graph becomes a completion
-    // signal between two hardware queues, and two of them on the recurrence chain cost more than the GEMMs' 40 us of
-    // otherwise idle GPU time give back.
-    const bool early_gru_w = parts == 3 && sd.ok && (g_sed_debug & 16384);
+    // (Measured twice and rejected in round 2, then removed: each layer's weight-gradient GEMMs right behind that layer's
+    // recurrence kernel on the side stream - the upper layer's next to the lower layer's recurrence (48 workgroups on 256
+    // CUs) - instead of between the two conv weight-gradient kernels: 0.816 ms against 0.766 ms per step with the four-SIMD
+    // recurrence.  Every extra cross-stream edge of the captured graph becomes a completion signal between two hardware
+    // queues, and two of them on the recurrence chain cost more than the GEMMs' 40 us of otherwise idle GPU time give back.)
 
     // ho != null: the forward left the output heads to this call (sed_mt_step_backward).  Fused form (hfuse.h): heads forward +
     // loss + heads backward run as the prologue phase of the top layer's backward recurrence, the meters' clip sums, the
     // step-state advance and the head weight gradients' column sum in k_heads_fin where the column sum alone used to be.
-    // Otherwise (debug bit 24, T / 8 > 128, gradient outputs asked for): k_heads_fwd here, then the two-kernel form.
+    // Otherwise (SED_DEBUG_SEPARATE_HEADS, T / 8 > 128, gradient outputs asked for): k_heads_fwd here, then the two-kernel form.
     const int head_cols = 2 * (g.NC * 128 + g.NC);
-    const bool fuse = ho && hl && (parts & 1) && heads_fusable(64, g.T3) && !(g_sed_debug & 16777216) && !hl->d_strong_out && !hl->d_weak_out;
+    const bool fuse = ho && hl && (parts & 1) && heads_fusable(64, g.T3) && !(g_sed_debug & SED_DEBUG_SEPARATE_HEADS) && !hl->d_strong_out &&
+                      !hl->d_weak_out;
     auto heads_colsum = [&](hipStream_t s2) -> int {
         if (fuse) return launch_heads_fin(WSF(W.heads_part), grads + P.dense_w, g.B, g.T3, g.NC, head_cols, *hl, s2);
         return launch_heads_colsum(WSF(W.heads_part), grads + P.dense_w, g.B, g.NC, s2);
@@ -488,7 +492,7 @@ static int crnn_backward_impl(const sed_dims* d, const float* params, const floa
     // ---- BiGRU ----------------------------------------------------------------------------------
     // The gradient w.r.t. each layer's input is produced INSIDE the recurrence kernel (two extra waves, one block of
     // steps behind), as two direction planes [2][B*T'][nin] that the consumer adds while loading: the layer below's
-    // recurrence kernel, or k_glu_pool_bwd for layer 0 (planes in W.dp2).
+    // recurrence kernel, or k_glu_pool_bwd8 for layer 0 (planes in W.dp2).
     const float* d_cur = WSF(W.d_out);
     const float* d_cur2 = nullptr;
     for (int l = g.L - 1; l >= 0; --l) {
@@ -512,17 +516,11 @@ static int crnn_backward_impl(const sed_dims* d, const float* params, const floa
                                WSF(W.hprev[l]), d_in, g.B, g.T3, st));
         d_cur = d_in;
         d_cur2 = d_in + (size_t)BT * nin;
-        if (early_gru_w) {
-            SIDE_FORK(st);
-            forked = true;
-            if (l == g.L - 1) SED_TRY(heads_colsum(ss));
-            SED_TRY(gru_weight_grads_layer(l, ss));
-        }
     }
     }
     // parts == 1 (data-parallel: the GRU + heads gradient bucket must be complete when this call returns so that
     // its all-reduce can start): the GEMMs follow the dX chain on the caller's stream.  parts == 3: they are
-    // deferred to the side stream of the conv-block backward below, where they overlap k_glu_pool_bwd.
+    // deferred to the side stream of the conv-block backward below, where they overlap k_glu_pool_bwd8.
     if (parts == 1) SED_TRY(gru_weight_grads(st));
     if (parts == 8) {
         // the weight-gradient tail of a parts == 5 call: head column sum + every GRU dW / db, on the CALLER's stream (which
@@ -531,10 +529,7 @@ static int crnn_backward_impl(const sed_dims* d, const float* params, const floa
         SED_TRY(gru_weight_grads(st));
         return SED_OK;
     }
-    if (!(parts & 2)) {
-        if (forked) SIDE_JOIN(st);
-        return SED_OK;
-    }
+    if (!(parts & 2)) return SED_OK;
     // ---- conv blocks 2, 1 -----------------------------------------------------------------------
     const size_t wpkT[3] = {0, L.wpkT1, L.wpkT2}, yo[3] = {0, L.y1, L.y2}, bo[3] = {0, L.bn1, L.bn2};
     const size_t pin[3] = {0, L.p0, L.p1}, gacc[3] = {0, W.gluacc1, W.gluacc2}, mo[3] = {L.mask0, L.mask1, L.mask2};
@@ -554,21 +549,17 @@ static int crnn_backward_impl(const sed_dims* d, const float* params, const floa
     // (Starting wgrad1 only after dgrad1, next to the VALU-bound k_blk0_bwd, measured the same: dgrad1 drops from
     // 175 to 93 us but k_blk0_bwd, left with one wave per SIMD beside the wgrad wave, goes from 86 to 177 us.)
     // BatchNorm-backward coefficients: derived by the conv dgrad / wgrad kernels themselves from the reduction sums (no
-    // 1-workgroup k_bn_bwd_prep + launch gap between k_glu_pool_bwd and the dgrad, twice per step); bit 9 of the debug
-    // knob, or any of the A/B conv kernels, brings the separate kernel back
-#ifdef SED_AB
-    const bool fuse_prep = (g_sed_debug & (4 | 8 | 64 | 128 | 512)) == 0;
-#else
-    const bool fuse_prep = (g_sed_debug & 512) == 0;
-#endif
+    // 1-workgroup k_bn_bwd_prep + launch gap between the GLU backward and the dgrad, twice per step); the direct conv
+    // kernels need the separate kernel
+    const bool fuse_prep = (g_sed_debug & (SED_DEBUG_DIRECT_CONV | SED_DEBUG_DIRECT_WGRAD)) == 0;
     BnBwdPrepArgs prep[3] = {};
     for (int i = 2; i >= 1; --i) {
         const BnBwdPrepArgs* pp = fuse_prep ? &prep[i] : nullptr;
         // (the BatchNorm-backward coefficients and the block's parameter gradients are produced by the last workgroup
-        // of k_glu_pool_bwd: no separate 1-workgroup kernel between it and the conv dgrad / wgrad)
+        // of k_glu_pool_bwd8: no separate 1-workgroup kernel between it and the conv dgrad / wgrad)
         SED_TRY(launch_glu_pool_bwd(CTXF(yo[i]), CTXF(bo[i]), params + P.glu_w[i], params + P.glu_b[i], WSF(dpo[i]),
                                     i == 2 ? WSF(dpo[i]) + (size_t)BT * 64 : nullptr,
-                                    WSF(dzo[i]), WSD(gacc[i]), 0, g.B, Hs[i], Wd[i], i, use_drop, g.p, CTXM(mo[i]),
+                                    WSF(dzo[i]), WSD(gacc[i]), 0, g.B, Hs[i], Wd[i], use_drop, g.p, CTXM(mo[i]),
                                     params + P.bn_g[i], WSF(W.coef[i]), grads + P.bn_g[i], grads + P.bn_b[i],
                                     grads + P.glu_w[i], grads + P.glu_b[i], grads + P.conv_b[i], fuse_prep ? &prep[i] : nullptr, st));
         if (i == 2) {
@@ -581,23 +572,17 @@ static int crnn_backward_impl(const sed_dims* d, const float* params, const floa
             if (sd.ok) { SED_CHECK_HIP(hipStreamWaitEvent(sd.s, sd.fork, 0)); forked = true; }
             SED_TRY(launch_conv_wgrad(WSF(dzo[i]), CTXF(yo[i]), WSF(W.coef[i]), CTXF(pin[i]), WSF(W.wg_part), W.wgrad_blocks,
                                       grads + P.conv_w[i], g.B, Hs[i], Wd[i], pp, ss));
-            if (parts == 3 && !early_gru_w) {
+            if (parts == 3) {
                 // the head weight-gradient column sum (deferred from part 1): behind wgrad2, long before the tail of the step
                 // (queued right in front of wgrad1 it sat 60 us behind the persistent dgrad kernel and held wgrad1 back; at
                 // the very end of the side stream it was 4 us on the step's tail)
-                // (debug bit 11: on a helper stream of their OWN.  Queued on the conv-wgrad helper they sit between wgrad2 and
-                // wgrad1 and hold wgrad1 - the tail of the step - back by ~80 us (r02_a step timeline: wgrad1 starts at 678 us,
-                // its inputs are ready at 594 us); giving them their own stream measured SLOWER all the same - 0.829 vs
-                // 0.815 ms (fp32), 0.775 vs 0.742 ms (bf16 operands): the step is throughput-bound, a third stream only
-                // takes CUs from the dgrad / block-0 chain.)
-                hipStream_t sg = ss;
-                if (sd.ok && (g_sed_debug & 2048)) {
-                    SED_CHECK_HIP(hipStreamWaitEvent(sd.s2, sd.fork, 0));
-                    sg = sd.s2;
-                    forked2 = true;
-                }
-                if (sd.ok) SED_TRY(heads_colsum(sg));
-                SED_TRY(gru_weight_grads(sg));
+                // (Queued on the conv-wgrad helper they sit between wgrad2 and wgrad1 and hold wgrad1 - the tail of the step -
+                // back by ~80 us (r02_a step timeline: wgrad1 starts at 678 us, its inputs are ready at 594 us); a helper
+                // stream of their OWN measured SLOWER all the same in round 2 - 0.829 vs 0.815 ms (fp32), 0.775 vs 0.742 ms
+                // (bf16 operands): the step is throughput-bound, a third stream only takes CUs from the dgrad / block-0
+                // chain.  Removed.)
+                if (sd.ok) SED_TRY(heads_colsum(ss));
+                SED_TRY(gru_weight_grads(ss));
             }
         } else {
             if (sd.ok) { SIDE_FORK(st); forked = true; }
@@ -612,10 +597,6 @@ static int crnn_backward_impl(const sed_dims* d, const float* params, const floa
                                  WSF(W.dp0), WSD(W.de0), 0, grads + P.conv_w[0], grads + P.conv_b[0], grads + P.bn_g[0],
                                  grads + P.bn_b[0], grads + P.glu_w[0], grads + P.glu_b[0], st));
     if (forked) SIDE_JOIN(st);
-    if (forked2) {
-        SED_CHECK_HIP(hipEventRecord(sd.join2, sd.s2));
-        SED_CHECK_HIP(hipStreamWaitEvent(st, sd.join2, 0));
-    }
     return SED_OK;
 }
 
@@ -699,7 +680,7 @@ extern "C" int sed_kernel_replay(const char* name, const sed_dims* d, const floa
                                                params + P.glu_w[i], params + P.glu_b[i], CTXF(po[i]), g.B, Hs[i], Wd[i], i, use_drop,
                                                g.p, seed_dev, use_drop ? CTXM(mo[i]) : nullptr, st);
         snprintf(nm, sizeof nm, "glu%d_bwd", i);
-        if (is(nm)) return launch_glu_pool_bwd(CTXF(yo[i]), CTXF(bo[i]), params + P.glu_w[i], params + P.glu_b[i], WSF(dpo[i]), i == 2 ? WSF(dpo[i]) + (size_t)BT * 64 : nullptr, WSF(dzo[i]), WSD(gacc[i]), 1, g.B, Hs[i], Wd[i], i, use_drop, g.p, CTXM(mo[i]),
+        if (is(nm)) return launch_glu_pool_bwd(CTXF(yo[i]), CTXF(bo[i]), params + P.glu_w[i], params + P.glu_b[i], WSF(dpo[i]), i == 2 ? WSF(dpo[i]) + (size_t)BT * 64 : nullptr, WSF(dzo[i]), WSD(gacc[i]), 1, g.B, Hs[i], Wd[i], use_drop, g.p, CTXM(mo[i]),
                                                params + P.bn_g[i], WSF(W.coef[i]), grads + P.bn_g[i], grads + P.bn_b[i], grads + P.glu_w[i], grads + P.glu_b[i], grads + P.conv_b[i], nullptr, st);
         snprintf(nm, sizeof nm, "conv%d_wgrad", i);
         if (is(nm)) return launch_conv_wgrad(WSF(dzo[i]), CTXF(yo[i]), WSF(W.coef[i]), CTXF(po[i - 1]), WSF(W.wg_part), W.wgrad_blocks, grads + P.conv_w[i], g.B, Hs[i], Wd[i], nullptr, st);

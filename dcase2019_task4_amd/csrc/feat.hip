@@ -903,11 +903,12 @@ extern "C" int sed_mel_frames(const float* wave, int n_clips, int n_samples, int
     const int* band = (const int*)((const char*)ws + mel_ws_band_off());
     const float* melw = (const float*)((const char*)ws + mel_ws_w_off(n_mels));
     const int frames = 1 + n_samples / hop;
-    // debug bit 19: round 2's kernel (one 256-thread workgroup per frame, five radix-4 passes through LDS); bit 21: round 3's
-    // (one wave per frame, tables walked in global memory) - both fp64, kept for A/B timing and as second implementations in the tests
-    if (g_sed_debug & 524288) {
+    // SED_DEBUG_STFT_R2: round 2's kernel (one 256-thread workgroup per frame, five radix-4 passes through LDS); SED_DEBUG_STFT_R3:
+    // round 3's (one wave per frame, tables walked in global memory) - both fp64, kept as second implementations in the tests
+    // and tools/bench_feat.py
+    if (g_sed_debug & SED_DEBUG_STFT_R2) {
         k_stft_mel<<<dim3(frames, n_clips), 256, 0, st>>>(wave, n_samples, hop, frames, tw, win, mel_basis, band, n_mels, mel);
-    } else if (g_sed_debug & 2097152) {
+    } else if (g_sed_debug & SED_DEBUG_STFT_R3) {
         k_stft_mel16<<<dim3(frames, n_clips), 64, 0, st>>>(wave, n_samples, hop, frames, tw, win, mel_basis, band, n_mels, mel);
     } else if (fft_dtype == SED_FFT_F32) {
         return launch_stft_p<float>(wave, n_clips, n_samples, hop, frames, tw, win, mel_basis, band, melw, n_mels, mel, max_workgroups, st);

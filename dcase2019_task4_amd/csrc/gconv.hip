@@ -839,8 +839,7 @@ int launch_gwgrad(int mode, int C, const void* dz, const void* yin, const float*
     const int nq = (C / 64) * (C / 64);
     int slabs = gwgrad_slabs(C);
     int nt, tpc;
-    if (W == 16 && (mode == SED_DTYPE_BF16 || (mode == SED_DTYPE_BF16X3 && !(g_sed_debug & 4194304)))) {
-        // (debug bit 22: the split-operand mode's weight gradient on the exact-fp32 MFMA kernel, as in round 3 - A/B)
+    if (W == 16 && (mode == SED_DTYPE_BF16 || mode == SED_DTYPE_BF16X3)) {
         static thread_local SedAttrOnce attr;
         if (attr.need()) {
             SED_CHECK_HIP(hipFuncSetAttribute((const void*)k_gwgrad_bf16<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GWgB::STAGE_BYTES));

@@ -3,7 +3,7 @@
 //
 // Operator sequence = CRNN.forward (baseline/models/CRNN.py:59-84) with nb_filters = [C, C, C], n_RNN_cell = H:
 //   block 0 (blk0.hip, templated on C; always fp32) -> [conv3x3 + BN sums (gconv.hip) -> BN / GLU / dropout / pool
-//   (gglu.hip)] x 2 -> BiGRU: input projection (gemm.hip) + recurrence (ggru.hip for H = 256, gru.hip for H = 64)
+//   (gglu.hip)] x 2 -> BiGRU: input projection (ggemm.hip) + recurrence (grec.hip / ggru.hip for H = 256, gru4.hip for H = 64)
 //   -> heads (heads.hip, templated on 2 H).
 #include <string.h>
 #include "common.h"
@@ -38,11 +38,11 @@ struct GCtx {
     size_t sg0;                               // bf16 family: block 0's GLU gate, one byte per element (blk0.hip SG), 0 bytes otherwise
     size_t total;
 };
-// debug bit 28: block 0's forward SAVES its GLU gates (one byte per element) and the backward reads them instead of recomputing
+// SED_DEBUG_SAVED_GATES: block 0's forward SAVES its GLU gates (one byte per element) and the backward reads them instead of recomputing
 // z on the MFMA + exp2 + rcp per element.  Built and measured in round 6, NOT the default: at B = 64 the backward kernel goes
 // 89 -> 81 us but the student's forward 109 -> 128 us (164 MB of byte stores from a kernel that runs beside the teacher's) -
 // waveform-bf16 0.8008 -> 0.8211 ms, mt-bf16 0.4929 -> 0.4944 (profiles/r06_blk0_saved_gates_ab.txt).
-static inline bool blk0_saves_gates(const Geo& g) { return g.mode == SED_DTYPE_BF16 && (g_sed_debug & 268435456); }
+static inline bool blk0_saves_gates(const Geo& g) { return g.mode == SED_DTYPE_BF16 && (g_sed_debug & SED_DEBUG_SAVED_GATES); }
 static size_t mask_bytes(size_t Q, int C) { return ((Q + 3) / 4) * (size_t)(C / 32) * 64 * sizeof(uint16_t); }
 
 static GCtx make_gctx(const Geo& g) {
@@ -67,8 +67,9 @@ static GCtx make_gctx(const Geo& g) {
     if (g.f16) { put(L.ph[0], n0 * 2); put(L.yh[1], n0 * 2); put(L.ph[1], n1 * 2); put(L.yh[2], n1 * 2); }
     const size_t bt = (size_t)g.B * g.T3;
     for (int l = 0; l < 2; ++l) {
-        put(L.gi[l], g.H == 64 ? 0 : bt * 6 * H * 4);          // (H = 64: the projection runs inside gru.hip's kernel)
+        put(L.gi[l], g.H == 64 ? 0 : bt * 6 * H * 4);          // (H = 64: the projection runs inside gru4.hip's kernel)
         put(L.gates[l], bt * 8 * H * 4); put(L.out[l], bt * 2 * H * 4);
+        // (whh / whhT: sized for the fp32 packing of the streaming recurrence, removed; only grec.hip's bf16 layouts use them now)
         put(L.whh[l], g.H == 64 ? 0 : 2 * 3 * H * H * 4); put(L.whhT[l], g.H == 64 ? 0 : 2 * 3 * H * H * 4);
         put(L.xch[l], g.H == 256 ? gclu_xch_bytes(g.B, g.H, 0) : 0); put(L.epoch[l], (size_t)2 * g.B * 4);
         put(L.wihT[l], g.H == 64 ? 0 : (size_t)(l == 0 ? C : 2 * H) * 6 * H * 4);
@@ -99,7 +100,7 @@ static GWs make_gws(const Geo& g) {
     const size_t n0 = (size_t)g.B * g.H1 * g.W1 * C, n1 = (size_t)g.B * g.H2 * g.W2 * C;
     put(W.d_out, bt * 2 * H * 4);
     for (int l = 0; l < 2; ++l) { put(W.dgi[l], bt * 6 * H * 4); put(W.dgh[l], bt * 6 * H * 4); put(W.hprev[l], bt * 2 * H * 4); }
-    put(W.d_in, 2 * bt * 2 * H * 4);          // (H = 64: two direction planes, gru.hip; generic: one tensor)
+    put(W.d_in, 2 * bt * 2 * H * 4);          // (H = 64: two direction planes, gru4.hip; generic: one tensor)
     put(W.heads_part, heads_part_floats(g.B, g.T3, g.NC, 2 * H) * 4);
     const size_t SS = ssz(g);
     put(W.dp[2], 2 * bt * C * 4); put(W.dz[2], n1 * SS); put(W.dp[1], n1 * SS); put(W.dz[1], n0 * SS); put(W.dp[0], n0 * SS);
@@ -216,10 +217,9 @@ int gen_forward(const Geo& g, const ParamOff& P, const float* params, float* bn_
     // hipGraph capture, and ROCm 7.0's hipStreamEndCapture segfaults on that nested fork.  It stays on the caller's stream.)
     (void)ev_fork; (void)ev_join;
     ss = st;
-    // Training forwards: the packing (and the W_ih transposes below) ride in spare workgroups of block 0's moments launch
-    // (gpack.h; debug bit 15 keeps the stand-alone kernels for A/B timing).  Eval forwards have no moments launch.
-    const bool cluster_ = (H == 256) && !(g_sed_debug & 1024);
-    const bool aux_pack = train && (H == 64 || cluster_) && !(g_sed_debug & 32768);
+    // Training forwards: the packing and the W_ih transposes ride in spare workgroups of block 0's moments launch (gpack.h).
+    // Eval forwards have no moments launch and need no transposes.
+    const bool aux_pack = train != 0;
     GenAuxPack aux = {};
     if (aux_pack) {
         aux.pk = pk; aux.mode = g.mode; aux.n_gnt = 0;
@@ -230,7 +230,7 @@ int gen_forward(const Geo& g, const ParamOff& P, const float* params, float* bn_
                 aux.n_gnt = l + 1;
             }
         // the W_hh layouts of the one-CU bf16 recurrence too (k_grec_pack: 6 us in front of every recurrence launch)
-        if (H == 256 && g.mode == SED_DTYPE_BF16 && !(g_sed_debug & (1024 | 65536)))
+        if (H == 256 && g.mode == SED_DTYPE_BF16)
             for (int l = 0; l < g.L && l < 2; ++l) {
                 aux.rw0[l] = params + P.w_hh[l][0]; aux.rw1[l] = params + P.w_hh[l][1];
                 aux.rwp[l] = CTXV(L.whh[l]); aux.rwpT[l] = CTXV(L.whhT[l]);
@@ -239,17 +239,9 @@ int gen_forward(const Geo& g, const ParamOff& P, const float* params, float* bn_
     } else {
         SED_TRY(launch_gen_pack(pk, g.mode, ss));
     }
-    // (debug bit 10: the streaming recurrence kernels instead of the cluster ones - A/B timing)
-    const bool cluster = (H == 256) && !(g_sed_debug & 1024);
-    // SED_DTYPE_BF16 at H = 256: one workgroup per chain, W_hh as bf16 in registers (grec.hip; debug bit 16 falls back to
-    // the fp32 cluster kernels)
-    const bool rec16 = cluster && g.mode == SED_DTYPE_BF16 && !(g_sed_debug & 65536);
-    if (H != 64 && !cluster)
-        for (int l = 0; l < g.L; ++l)
-            SED_TRY(launch_ggru_pack(params + P.w_hh[l][0], params + P.w_hh[l][1], CTXF(L.whh[l]), train ? CTXF(L.whhT[l]) : nullptr, H, ss));
-    if (H != 64 && train && !aux_pack)
-        for (int l = 0; l < g.L; ++l)
-            SED_TRY(launch_gnt_pack_t(params + P.w_ih[l][0], params + P.w_ih[l][1], CTXF(L.wihT[l]), 3 * H, l == 0 ? C : 2 * H, ss));
+    // H = 256: the cluster recurrence (ggru.hip); SED_DTYPE_BF16 runs one workgroup per chain with W_hh as bf16 in registers
+    // instead (grec.hip)
+    const bool rec16 = H == 256 && g.mode == SED_DTYPE_BF16;
 
     // ---- conv block 0 -------------------------------------------------------------------------------------------------
     SED_TRY(launch_blk0_forward(g, x, params + P.conv_w[0], params + P.conv_b[0], params + P.bn_g[0], params + P.bn_b[0],
@@ -288,16 +280,15 @@ int gen_forward(const Geo& g, const ParamOff& P, const float* params, float* bn_
         bn.stat = CTXD(so[i]); bn.N = (double)g.B * Hs[i] * Wd[i]; bn.gamma = params + P.bn_g[i]; bn.beta = params + P.bn_b[i];
         bn.run_mean = bn_running + (2 * i) * C; bn.run_var = bn_running + (2 * i + 1) * C; bn.tracked = trk[i];
         bn.train = train; bn.update = upd; bn.eps = g.eps; bn.momentum = g.mom; bn.bn = CTXF(L.bn[i]);
-        if (g.mode == SED_DTYPE_BF16 && !(g_sed_debug & 262144))      // (debug bit 18: the round-2 GLU kernels, A/B timing)
+        if (g.mode == SED_DTYPE_BF16)
             SED_TRY(launch_bglu_fwd(C, CTXV(L.y[i]), bn, params + P.glu_w[i], params + P.glu_b[i], CTXV(L.p[i]), i == 1 ? 1 : 0, g.B,
                                     Hs[i], Wd[i], i, use_drop, g.p, seed_dev, use_drop ? CTXM(L.mask[i]) : nullptr,
                                     train ? CTXV(L.wg[i]) : nullptr, train ? CTXF(L.bg[i]) : nullptr, st));
-        else if (g.mode == SED_DTYPE_BF16X3 && !(g_sed_debug & 8388608))      // (debug bit 23: the exact-fp32 GLU forward in this mode, A/B)
+        else if (g.mode == SED_DTYPE_BF16X3)
             SED_TRY(launch_bglu_fwd_x3(C, CTXV(L.y[i]), bn, params + P.glu_w[i], params + P.glu_b[i], CTXV(L.p[i]), g.B, Hs[i], Wd[i], i,
                                        use_drop, g.p, seed_dev, use_drop ? CTXM(L.mask[i]) : nullptr, st));
         else
-        SED_TRY(launch_gglu_fwd(gm, C, CTXV(L.y[i]), bn, CTXV(L.wg[i]), CTXF(L.bg[i]), CTXV(L.p[i]),
-                                (g.mode == SED_DTYPE_BF16 && i == 1) ? 1 : 0, g.B, Hs[i], Wd[i], i,
+        SED_TRY(launch_gglu_fwd(gm, C, CTXV(L.y[i]), bn, CTXV(L.wg[i]), CTXF(L.bg[i]), CTXV(L.p[i]), 0, g.B, Hs[i], Wd[i], i,
                                 use_drop, g.p, seed_dev, use_drop ? CTXM(L.mask[i]) : nullptr, st));
     }
     // ---- BiGRU ----------------------------------------------------------------------------------------------------------
@@ -322,13 +313,10 @@ int gen_forward(const Geo& g, const ParamOff& P, const float* params, float* bn_
                     SED_TRY(launch_grec_pack(params + P.w_hh[l][0], params + P.w_hh[l][1], CTXV(L.whh[l]), train ? CTXV(L.whhT[l]) : nullptr, st, g.f16 ? 1 : 0));
                 SED_TRY(launch_grec_fwd(CTXF(L.gi[l]), CTXV(L.whh[l]), params + P.b_hh[l][0], params + P.b_hh[l][1], CTXF(L.out[l]),
                                         train ? CTXF(L.gates[l]) : nullptr, g.B, g.T3, st, g.f16 ? 1 : 0));
-            } else if (cluster)
+            } else
                 SED_TRY(launch_gclu_fwd(CTXF(L.gi[l]), params + P.w_hh[l][0], params + P.w_hh[l][1], params + P.b_hh[l][0],
                                         params + P.b_hh[l][1], CTXF(L.out[l]), train ? CTXF(L.gates[l]) : nullptr, CTXV(L.xch[l]),
                                         (unsigned int*)CTXV(L.epoch[l]), (int*)CTXV(L.err), g.B, g.T3, st));
-            else
-                SED_TRY(launch_ggru_fwd(H, CTXF(L.gi[l]), CTXF(L.whh[l]), params + P.b_hh[l][0], params + P.b_hh[l][1], CTXF(L.out[l]),
-                                        train ? CTXF(L.gates[l]) : nullptr, g.B, g.T3, st));
         }
         in = CTXF(L.out[l]);
         nin = 2 * H;
@@ -344,8 +332,7 @@ int gen_forward(const Geo& g, const ParamOff& P, const float* params, float* bn_
 // Backward.  `side`: the helper stream of the caller's stream (fork / join events owned by crnn.hip), or the caller's own.
 int gen_backward(const Geo& g, const ParamOff& P, const float* params, const float* x, const uint64_t* seed_dev, void* ctx,
                  size_t ctx_bytes, const float* d_strong, const float* d_weak, float* grads, void* ws, size_t ws_bytes, int parts,
-                 hipStream_t st, hipStream_t ss, hipEvent_t ev_fork, hipEvent_t ev_join, hipStream_t ss2, hipEvent_t ev_join2,
-                 const HeadsLoss* hl, const HeadsOut* ho) {
+                 hipStream_t st, hipStream_t ss, hipEvent_t ev_fork, hipEvent_t ev_join, const HeadsLoss* hl, const HeadsOut* ho) {
     const GCtx L = make_gctx(g);
     const GWs W = make_gws(g);
     if (ctx_bytes < L.total || ws_bytes < W.total) {
@@ -357,19 +344,13 @@ int gen_backward(const Geo& g, const ParamOff& P, const float* params, const flo
     const int use_drop = (g.p > 0.f) ? 1 : 0;
     const bool have_side = (ss != st);
     const bool defer_gru_w = (parts & 4) != 0;
-    // (H = 64: measured NEUTRAL to slightly negative - 0.602 against 0.592 ms for the base bf16 step: the conv-block backward is
-    // throughput-bound, the GEMMs only trade places with the weight-gradient kernels and slow the latency-bound recurrence)
-    // (H = 64, re-measured with the round-3 kernels: 0.580 against 0.569 ms - the GEMMs stretch the lower layer's recurrence from
-    // 40 to 52 us)
-    const bool early_gru_w = parts == 3 && have_side && (H != 64 || (g_sed_debug & 536870912)) && !(g_sed_debug & 131072);    // (debug bit 17: old schedule; bit 29: early at H = 64 too)
-    bool forked = false, forked2 = false;
-    auto fork = [&]() -> int {
-        if (!have_side) return SED_OK;
-        SED_CHECK_HIP(hipEventRecord(ev_fork, st));
-        SED_CHECK_HIP(hipStreamWaitEvent(ss, ev_fork, 0));
-        forked = true;
-        return SED_OK;
-    };
+    // H = 256: each GRU layer's weight-gradient GEMMs start on the helper stream right behind its recurrence (below).
+    // (H = 64, measured and removed: NEUTRAL to slightly negative - 0.602 against 0.592 ms for the base bf16 step: the conv-block
+    // backward is throughput-bound, the GEMMs only trade places with the weight-gradient kernels and slow the latency-bound
+    // recurrence; re-measured with the round-3 kernels: 0.580 against 0.569 ms - the GEMMs stretch the lower layer's recurrence
+    // from 40 to 52 us.  The late schedule at H = 256, the GEMMs after the conv blocks' fork, was removed as well.)
+    const bool early_gru_w = parts == 3 && have_side && H != 64;
+    bool forked = false;
     // weight + bias gradients of one GRU layer, both directions (split-K MFMA GEMMs)
     auto gru_weight_grads_layer = [&](int l, hipStream_t s2) -> int {
         const int nin = (l == 0) ? C : 2 * H;
@@ -392,9 +373,10 @@ int gen_backward(const Geo& g, const ParamOff& P, const float* params, const flo
         return SED_OK;
     };
     // ho != null: heads deferred by the forward (sed_mt_step_backward, crnn.hip).  H = 64: fused into the top layer's backward
-    // recurrence (hfuse.h); H = 256 (or debug bit 24): k_heads_fwd here, then the two-kernel form.
+    // recurrence (hfuse.h); H = 256 (or SED_DEBUG_SEPARATE_HEADS): k_heads_fwd here, then the two-kernel form.
     const int head_cols = 2 * (g.NC * 2 * H + g.NC);
-    const bool fuse = ho && hl && (parts & 1) && heads_fusable(H, g.T3) && !(g_sed_debug & 16777216) && !hl->d_strong_out && !hl->d_weak_out;
+    const bool fuse = ho && hl && (parts & 1) && heads_fusable(H, g.T3) && !(g_sed_debug & SED_DEBUG_SEPARATE_HEADS) && !hl->d_strong_out &&
+                      !hl->d_weak_out;
     auto heads_colsum = [&](hipStream_t s2) -> int {
         if (fuse) return launch_heads_fin(WSF(W.heads_part), grads + P.dense_w, g.B, g.T3, g.NC, head_cols, *hl, s2);
         return launch_heads_colsum(WSF(W.heads_part), grads + P.dense_w, g.B * heads_bwd_chunks(2 * H, g.T3), g.NC, s2, 2 * H);
@@ -434,27 +416,16 @@ int gen_backward(const Geo& g, const ParamOff& P, const float* params, const flo
                 SED_TRY(launch_gru_bwd(d_cur, d_cur2, CTXF(L.out[l]), CTXF(L.gates[l]), params + P.w_hh[l][0], params + P.w_hh[l][1],
                                        params + P.w_ih[l][0], params + P.w_ih[l][1], nin, WSF(W.dgi[l]), WSF(W.dgh[l]), WSF(W.hprev[l]),
                                        d_in, g.B, g.T3, st));
-                // this layer's weight-gradient GEMMs start on the helper stream right behind its recurrence: the rest of the GRU
-                // chain keeps 48 CUs busy, and left for the conv blocks' fork they ended the step ~70 us after the caller's
-                // stream had finished (profiles/r03_a_mt-bf16_step_timeline.txt)
-                if (early_gru_w) {
-                    SED_TRY(fork());
-                    if (l == g.L - 1) SED_TRY(heads_colsum(ss));
-                    SED_TRY(gru_weight_grads_layer(l, ss));
-                }
                 d_cur = d_in;
                 d_cur2 = d_in + (size_t)BT * nin;
             } else {
-                if (H == 256 && g.mode == SED_DTYPE_BF16 && !(g_sed_debug & (1024 | 65536)))
+                if (g.mode == SED_DTYPE_BF16)
                     SED_TRY(launch_grec_bwd(d_cur, CTXF(L.out[l]), CTXF(L.gates[l]), CTXV(L.whhT[l]), WSF(W.dgi[l]), WSF(W.dgh[l]),
                                             WSF(W.hprev[l]), g.B, g.T3, st));
-                else if (H == 256 && !(g_sed_debug & 1024))
+                else
                     SED_TRY(launch_gclu_bwd(d_cur, CTXF(L.out[l]), CTXF(L.gates[l]), params + P.w_hh[l][0], params + P.w_hh[l][1],
                                             WSF(W.dgi[l]), WSF(W.dgh[l]), WSF(W.hprev[l]), (void*)((char*)ws + W.xch[l]),
                                             (unsigned int*)((char*)ws + W.epoch[l]), (int*)CTXV(L.err), g.B, g.T3, st));
-                else
-                    SED_TRY(launch_ggru_bwd(H, d_cur, CTXF(L.out[l]), CTXF(L.gates[l]), CTXF(L.whhT[l]), WSF(W.dgi[l]), WSF(W.dgh[l]),
-                                            WSF(W.hprev[l]), g.B, g.T3, st));
                 // dX[bt][i] = sum_dir sum_g dgi[bt][dir][g] W_ih[dir][g][i]: K = 6H, the two W_ih stacked along K (transposed
                 // copy made by the forward)
                 // H = 256: this layer's weight-gradient GEMMs (100 - 160 us of split-K work) start on the helper stream NOW, next
@@ -491,14 +462,13 @@ int gen_backward(const Geo& g, const ParamOff& P, const float* params, const flo
     const int Hs[3] = {0, g.H1, g.H2}, Wd[3] = {0, g.W1, g.W2};
     for (int i = 2; i >= 1; --i) {
         // (H = 64: the GRU's dX arrives as two direction planes; the GLU backward adds them while loading)
-        const bool new_glu = g.mode == SED_DTYPE_BF16 && !(g_sed_debug & 262144);
+        const bool new_glu = g.mode == SED_DTYPE_BF16;
         if (new_glu)
             SED_TRY(launch_bglu_bwd(C, CTXV(L.y[i]), CTXF(L.bn[i]), CTXV(L.wg[i]), CTXF(L.bg[i]), CTXV(L.wgT[i]), WSF(W.dp[i]), i == 1 ? 1 : 0, WSF(W.dz[i]), WSF(W.glu_part), g.B, Hs[i], Wd[i],
                                     use_drop, g.p, CTXM(L.mask[i]), st, (i == 2 && H == 64) ? WSF(W.dp[2]) + (size_t)BT * C : nullptr));
         else
         SED_TRY(launch_gglu_bwd(gm, C, CTXV(L.y[i]), CTXF(L.bn[i]), params + P.bn_g[i], params + P.bn_b[i], CTXV(L.wg[i]),
-                                CTXV(L.wgT[i]), CTXF(L.bg[i]), WSF(W.dp[i]), (g.mode == SED_DTYPE_BF16 && i == 1) ? 1 : 0,
-                                WSF(W.dz[i]), WSF(W.glu_part), g.B, Hs[i], Wd[i], use_drop,
+                                CTXV(L.wgT[i]), CTXF(L.bg[i]), WSF(W.dp[i]), 0, WSF(W.dz[i]), WSF(W.glu_part), g.B, Hs[i], Wd[i], use_drop,
                                 g.p, CTXM(L.mask[i]), st, (i == 2 && H == 64) ? WSF(W.dp[2]) + (size_t)BT * C : nullptr));
         GBnBwdArgs pa;
         pa.part = WSF(W.glu_part); pa.n_part = new_glu ? bglu_bwd_grid(C, g.B, Hs[i], Wd[i]) : gglu_bwd_grid(g.B, Hs[i], Wd[i]); pa.C = C; pa.N = (double)g.B * Hs[i] * Wd[i];
@@ -522,15 +492,8 @@ int gen_backward(const Geo& g, const ParamOff& P, const float* params, const flo
         SED_TRY(launch_gwgrad(g.mode, C, WSF(W.dz[i]), CTXF(L.y[i]), WSF(W.coef[i]), CTXF(L.p[i - 1]), WSF(W.wg_part), grads + P.conv_w[i], g.B,
                               Hs[i], Wd[i], ss));
         if (i == 2 && parts == 3 && !early_gru_w) {
-            // on the second helper stream, so that they do not sit in front of wgrad1 on the first (crnn.hip)
-            hipStream_t sg = ss;
-            if (have_side && ss2 != nullptr) {
-                SED_CHECK_HIP(hipStreamWaitEvent(ss2, ev_fork, 0));
-                sg = ss2;
-                forked2 = true;
-            }
-            if (have_side) SED_TRY(heads_colsum(sg));
-            SED_TRY(gru_weight_grads(sg));
+            if (have_side) SED_TRY(heads_colsum(ss));
+            SED_TRY(gru_weight_grads(ss));
         }
     }
     // ---- conv block 0 -----------------------------------------------------------------------------------------------------
@@ -541,10 +504,6 @@ int gen_backward(const Geo& g, const ParamOff& P, const float* params, const flo
     if (forked) {
         SED_CHECK_HIP(hipEventRecord(ev_join, ss));
         SED_CHECK_HIP(hipStreamWaitEvent(st, ev_join, 0));
-    }
-    if (forked2) {
-        SED_CHECK_HIP(hipEventRecord(ev_join2, ss2));
-        SED_CHECK_HIP(hipStreamWaitEvent(st, ev_join2, 0));
     }
     return SED_OK;
 }

@@ -1,7 +1,7 @@
 // gen.h - building blocks of the GENERIC kernel family (gconv.hip, gglu.hip, ggru.hip, gcrnn.hip): any conv width
 // C in {64, 128}, any GRU width H that is a multiple of 64 up to 256, MFMA operands in fp32 (MODE 0: exact f32,
 // v_mfma_f32_32x32x2_f32) or bf16 (MODE 1: v_mfma_f32_32x32x16_bf16, fp32 accumulate).  The C = 64 / H = 64 / fp32
-// configuration of baseline/config.py:53-58 keeps its own specialised kernels (conv.hip, bnglu.hip, gru.hip); this
+// configuration of baseline/config.py:53-58 keeps its own specialised kernels (conv.hip, bnglu.hip, gru4.hip); this
 // family serves BASELINE.json configs[2] (bf16 operands) and configs[4] (nb_filters 3 x 128, n_RNN_cell 256).
 //
 // Common shape of every GEMM here: C[m][n] += sum_k A[m][k] B[n][k] with BOTH operands k-contiguous - what the bf16

@@ -1,6 +1,6 @@
 // ggemm.hip - C[m][n] = sum_k A[m][k] B[n][k] (+ bias[n]): the "NT" GEMMs of the wide BiGRU - the input projections
 // gi = x W_ih^T + b_ih (baseline/models/RNN.py:12: nn.GRU's first half) and the gradient w.r.t. the layer input
-// dX = [dgi_f | dgi_r] [W_ih_f ; W_ih_r] (with the stacked W_ih transposed once by k_gnt_pack_t) - exact fp32 on the f32 MFMA.
+// dX = [dgi_f | dgi_r] [W_ih_f ; W_ih_r] (with the stacked W_ih transposed once by gpack.h's gnt_pack_t_body) - exact fp32 on the f32 MFMA.
 // gemm.hip's 64 x 64-tile batched kernel served the 192 x 64 .. 128 shapes of the 64-cell GRU; at H = 256 its
 // K-loop (one 64-deep tile per global -> LDS -> MFMA round trip, no overlap) ran at 27 TFLOP/s and the four GEMMs on the
 // critical path of a wide step cost 380 us.  Here: the same 64 x 64 output tile per workgroup (the shapes are too small for
@@ -208,19 +208,6 @@ int launch_gnt_gemm(const GntBatch& gb, hipStream_t st) {
         maxN = q.N > maxN ? q.N : maxN;
     }
     k_gnt_gemm<<<dim3((maxN + GNT_T - 1) / GNT_T, (maxM + GNT_T - 1) / GNT_T, gb.n_prob), 256, 0, st>>>(gb);
-    SED_CHECK_LAUNCH();
-    return SED_OK;
-}
-
-// out[n][dir * R + k] = w_dir[k][n]  (R rows, N columns each): the two W_ih stacked along K and transposed, so that the
-// dX GEMM reads it k-contiguous
-__global__ __launch_bounds__(256) void k_gnt_pack_t(const float* __restrict__ w0, const float* __restrict__ w1, float* __restrict__ out,
-                                                     int R, int N) {
-    gnt_pack_t_body(w0, w1, out, R, N, (int)blockIdx.x, (int)threadIdx.x);
-}
-int launch_gnt_pack_t(const float* w0, const float* w1, float* out, int R, int N, hipStream_t st) {
-    SED_CHECK_ARG(R % 32 == 0 && N % 32 == 0, "gnt pack: R and N must be multiples of 32");
-    k_gnt_pack_t<<<gnt_pack_t_tiles(R, N), 256, 0, st>>>(w0, w1, out, R, N);
     SED_CHECK_LAUNCH();
     return SED_OK;
 }

@@ -191,7 +191,7 @@ int launch_gglu_fwd(int mode, int C, const void* y, const GBnArgs& bn, const voi
                     int H, int W, int block_id, int use_drop, float p_drop, const uint64_t* seed, uint16_t* mask_out, hipStream_t st) {
 #define GGLU_CASE(MD, CC, PP) \
     if (mode == MD && C == CC && p_bf16 == PP) return gglu_fwd_launch<MD, CC, PP>(y, bn, wg, bg, p, B, H, W, block_id, use_drop, p_drop, seed, mask_out, st)
-    GGLU_CASE(0, 64, 0); GGLU_CASE(0, 128, 0); GGLU_CASE(1, 64, 0); GGLU_CASE(1, 128, 0); GGLU_CASE(1, 64, 1); GGLU_CASE(1, 128, 1);
+    GGLU_CASE(0, 64, 0); GGLU_CASE(0, 128, 0);
 #undef GGLU_CASE
     sed_set_error("gglu forward: unsupported mode %d / channels %d", mode, C);
     return SED_ERR_UNSUPPORTED;
@@ -483,7 +483,7 @@ int launch_gglu_bwd(int mode, int C, const void* y, const float* bn, const float
                     int use_drop, float p_drop, const uint16_t* mask_in, hipStream_t st, const float* dp2) {
 #define GGLU_CASE(MD, CC, PP) \
     if (mode == MD && C == CC && dp_bf16 == PP) return gglu_bwd_launch<MD, CC, PP>(y, bn, gamma, beta, wg, wgT, bg, dp, dp2, dz, part, B, H, W, use_drop, p_drop, mask_in, st)
-    GGLU_CASE(0, 64, 0); GGLU_CASE(0, 128, 0); GGLU_CASE(1, 64, 0); GGLU_CASE(1, 128, 0); GGLU_CASE(1, 64, 1); GGLU_CASE(1, 128, 1);
+    GGLU_CASE(0, 64, 0); GGLU_CASE(0, 128, 0);
 #undef GGLU_CASE
     sed_set_error("gglu backward: unsupported mode %d / channels %d", mode, C);
     return SED_ERR_UNSUPPORTED;

@@ -40,7 +40,7 @@ struct GBnArgs {
     int train, update; float eps, momentum;
     float* bn;                                  // out [4][C]: mean, invstd, scale, shift
 };
-// mode 1 (SED_DTYPE_BF16): y is bf16; p is bf16 when p_bf16 (block 1) and fp32 otherwise (block 2: the GRU input)
+// mode 0 (fp32) only: SED_DTYPE_BF16 runs bglu.hip's kernels (p_bf16, dp_bf16 and mode 1 are no longer instantiated)
 int launch_gglu_fwd(int mode, int C, const void* y, const GBnArgs& bn, const void* wg, const float* bg, void* p, int p_bf16, int B,
                     int H, int W, int block_id, int use_drop, float p_drop, const uint64_t* seed, uint16_t* mask_out, hipStream_t st);
 int gglu_bwd_grid(int B, int H, int W);
@@ -59,17 +59,9 @@ struct GBnBwdArgs {
 int launch_gbn_bwd_prep(const GBnBwdArgs& a, hipStream_t st);
 
 // ggru.hip ----------------------------------------------------------------------------------------------------------------
-// W_hh re-laid for coalesced streaming: fwd [k / 4][3H rows][4], bwd (transposed) [g / 4][H columns][4]
-int launch_ggru_pack(const float* w_hh_f, const float* w_hh_r, float* wp /*[2][3H*H]*/, float* wpT /*[2][3H*H] or null*/, int H,
-                     hipStream_t st);
-// gi: [B*T][2][3H] (input projection incl. b_ih, both directions); out [B*T][2H]; gates [B*T][2][4H] (r, z, n, gh_n) or null
-int launch_ggru_fwd(int H, const float* gi, const float* wp, const float* b_hh_f, const float* b_hh_r, float* out, float* gates,
-                    int B, int T, hipStream_t st);
-// d_out [B*T][2H]; dgi / dgh [B*T][2][3H]; hprev [B*T][2][H]
-int launch_ggru_bwd(int H, const float* d_out, const float* out, const float* gates, const float* wpT, float* dgi, float* dgh,
-                    float* hprev, int B, int T, hipStream_t st);
-
 // cluster recurrence (4 workgroups per chain, W_hh in registers, per-step granule exchange through L2); H = 256 only
+// gi: [B*T][2][3H] (input projection incl. b_ih, both directions); out [B*T][2H]; gates [B*T][2][4H] (r, z, n, gh_n) or null
+// d_out [B*T][2H]; dgi / dgh [B*T][2][3H]; hprev [B*T][2][H]
 size_t gclu_xch_bytes(int B, int H, int bwd);
 int launch_gclu_fwd(const float* gi, const float* w_hh_f, const float* w_hh_r, const float* b_hh_f, const float* b_hh_r, float* out,
                     float* gates, void* xch, unsigned int* epoch, int* err, int B, int T, hipStream_t st);
@@ -104,7 +96,6 @@ struct GntBatch { GntProb p[2]; int n_prob; };
 int launch_gnt_gemm(const GntBatch& gb, hipStream_t st);
 // bf16 MFMA operands: x3 = 0 SED_DTYPE_BF16 (single products), x3 = 1 SED_DTYPE_BF16X3 (split operands); K % 64 == 0
 int launch_gnt_gemm_bf16(const GntBatch& gb, hipStream_t st, int x3 = 0);
-int launch_gnt_pack_t(const float* w0, const float* w1, float* out, int R, int N, hipStream_t st);
 
 // gcrnn.hip ---------------------------------------------------------------------------------------------------------------
 struct HeadsLoss;
@@ -118,5 +109,4 @@ int gen_forward(const Geo& g, const ParamOff& P, const float* params, float* bn_
                 hipStream_t st, hipStream_t ss, hipEvent_t ev_fork, hipEvent_t ev_join);
 int gen_backward(const Geo& g, const ParamOff& P, const float* params, const float* x, const uint64_t* seed_dev, void* ctx,
                  size_t ctx_bytes, const float* d_strong, const float* d_weak, float* grads, void* ws, size_t ws_bytes, int parts,
-                 hipStream_t st, hipStream_t ss, hipEvent_t ev_fork, hipEvent_t ev_join, hipStream_t ss2, hipEvent_t ev_join2,
-                 const HeadsLoss* hl, const HeadsOut* ho);
+                 hipStream_t st, hipStream_t ss, hipEvent_t ev_fork, hipEvent_t ev_join, const HeadsLoss* hl, const HeadsOut* ho);

@@ -5,7 +5,7 @@
 //   r = sig(gi_r + gh_r); z = sig(gi_z + gh_z); n = tanh(gi_n + r * gh_n); h' = (1-z) n + z h
 //
 // A chain (clip, direction) is T/8 = 78 serial steps of a 192 x 64 mat-vec + gate math: latency-, not throughput-bound.
-// Round 1 (gru.hip, now only built with SED_AB) gave the whole mat-vec to ONE wave: 394 / 409 ns per step forward (layer
+// Round 1 (gru.hip, measured in rounds 1 - 2; removed) gave the whole mat-vec to ONE wave: 394 / 409 ns per step forward (layer
 // 0 / 1), 563 / 570 ns backward (tools/gru_prologue.py: time = fixed + per-step x steps).  Here one workgroup = 9 (forward)
 // or 10 (backward) waves per chain:
 //   * waves 0-3, one per SIMD, "recurrence".  Forward: wave w owns hidden units 16w .. 16w+15; lane (u = lane >> 2,
@@ -597,21 +597,10 @@ static_assert(2 * G4_SB * 384 + 2 * G4_SB * G4_HS >= HF_TMAX * HF_S + HF_MAXO * 
               "the heads phase's scratch must fit the ops / history rings it aliases");
 static const size_t GRU4_BWD_HEADS_LDS_MAX = GRU4_BWD_LDS + (size_t)HF_TMAX * 64 * sizeof(float);
 
-int launch_gru_fwd_v1(const float* x, int nin, const float* w_ih_f, const float* w_ih_r, const float* b_ih_f, const float* b_ih_r,
-                      const float* w_hh_f, const float* w_hh_r, const float* b_hh_f, const float* b_hh_r, float* out, float* gates,
-                      int B, int T, hipStream_t st);
-int launch_gru_bwd_v1(const float* d_out, const float* d_out2, const float* out, const float* gates, const float* w_hh_f,
-                      const float* w_hh_r, const float* w_ih_f, const float* w_ih_r, int nin, float* dgi, float* dgh, float* hprev,
-                      float* dx_planes, int B, int T, hipStream_t st);
-
 // x: the layer input [B*T][nin] (the input projection runs inside the kernel)
 int launch_gru_fwd(const float* x, int nin, const float* w_ih_f, const float* w_ih_r, const float* b_ih_f, const float* b_ih_r,
                    const float* w_hh_f, const float* w_hh_r, const float* b_hh_f, const float* b_hh_r, float* out, float* gates,
                    int B, int T, hipStream_t st) {
-#ifdef SED_AB
-    if (g_sed_debug & 4096)       // round 1's one-wave recurrence, for A/B timing
-        return launch_gru_fwd_v1(x, nin, w_ih_f, w_ih_r, b_ih_f, b_ih_r, w_hh_f, w_hh_r, b_hh_f, b_hh_r, out, gates, B, T, st);
-#endif
     static thread_local SedAttrOnce attr_done;
     if (attr_done.need()) {
         SED_CHECK_HIP(hipFuncSetAttribute((const void*)k_gru4_fwd<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gru4_fwd_lds<64>()));
@@ -634,10 +623,6 @@ int launch_gru_fwd(const float* x, int nin, const float* w_ih_f, const float* w_
 int launch_gru_bwd(const float* d_out, const float* d_out2, const float* out, const float* gates, const float* w_hh_f,
                    const float* w_hh_r, const float* w_ih_f, const float* w_ih_r, int nin, float* dgi, float* dgh, float* hprev,
                    float* dx_planes, int B, int T, hipStream_t st) {
-#ifdef SED_AB
-    if (g_sed_debug & 4096)
-        return launch_gru_bwd_v1(d_out, d_out2, out, gates, w_hh_f, w_hh_r, w_ih_f, w_ih_r, nin, dgi, dgh, hprev, dx_planes, B, T, st);
-#endif
     static thread_local SedAttrOnce attr_done;
     if (attr_done.need()) {
         SED_CHECK_HIP(hipFuncSetAttribute((const void*)k_gru4_bwd<64, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GRU4_BWD_LDS));

@@ -153,7 +153,7 @@ int launch_glu_pool_fwd(const float* y, const double* stat, double N, const floa
 // backward pass 1: dz (full-res grad wrt BN output), GLU weight grads and BN reduction sums
 //   acc: double [64*64 (dWglu) + 64 (dbglu) + 64 (sum dz) + 64 (sum dz*y)]
 int launch_glu_pool_bwd(const float* y, const float* bn, const float* wglu, const float* bglu, const float* dp, const float* dp_b, float* dz,
-                        double* acc, int zero_acc, int B, int H, int W, int block_id, int use_drop, float p_drop,
+                        double* acc, int zero_acc, int B, int H, int W, int use_drop, float p_drop,
                         const uint16_t* mask_in, const float* gamma, float* coef, float* g_gamma, float* g_beta, float* g_wglu,
                         float* g_bglu, float* g_convb, BnBwdPrepArgs* prep_out /* non-null: no k_bn_bwd_prep, see BnBwdPrepArgs */,
                         hipStream_t st);
@@ -190,7 +190,7 @@ size_t gemm_part_floats(int n_prob, int splits, int max_m, int max_nx);
 int launch_gemm_batch(GemmBatch& gb, hipStream_t st);
 int launch_colsum(const float* A, int M, int N, int64_t lda, float* out, hipStream_t st);
 
-// gru.hip
+// gru4.hip
 // crnn.hip: runs the host callback registered by sed_crnn_fork_callback (if any) for st - called by both forwards between the conv
 // stack and the recurrence
 int sed_fork_point(hipStream_t st);

@@ -434,24 +434,20 @@ int sed_kernel_replay(const char* name, const sed_dims* d, const float* params, 
                       const uint64_t* seed_dev, void* ctx, size_t ctx_bytes, float* grads, void* ws,
                       size_t ws_bytes, void* stream);
 
-/* Debug knob for timing experiments (returns the previous value); 0 = normal operation.
- *   bit 0: skip the fp64 atomics of the reduction epilogues (results are then WRONG);
- *   bit 1 / 2: block-1 conv forward / dgrad by the 9-tap tile kernel; bit 6: both 64 -> 64 convolutions (forward and
- *   dgrad) by the direct 9-tap kernels (8-wave weight-stationary for block 1, tile kernel for block 2) instead of the
- *   Winograd F(2x2, 3x3) kernel - results differ at the 1e-7 level; bit 7: block-1 wgrad by the direct double-buffered
- *   kernel instead of the Winograd-domain one; bit 3: by the single-buffered tile kernel; bit 4: GLU backward with one wave per SIMD instead of two channel-half waves sharing a row block.
- *   bit 9: BatchNorm-backward coefficients by the 1-workgroup kernel k_bn_bwd_prep instead of in the prologue of the conv
- *   dgrad / wgrad kernels (also implied by bits 2, 3, 6, 7).  Kept for A/B timing (profiles/README.md).
- *   Generic kernel set: bit 10 streaming H = 256 recurrence, bit 16 cluster recurrence instead of the one-CU bf16 kernels,
- *   bit 17 late GRU weight-gradient schedule, bit 18 round-2 GLU kernels, bit 19 round-2 STFT kernel, bit 20 block-1
- *   convolution (bf16, C = 128) by the barrier-free k_bconv2.
- *   bit 24: sed_mt_step_backward runs the deferred heads as separate kernels (k_heads_fwd, k_heads_bwd) instead of fused
- *   into the backward recurrence (A/B timing and the bit-identity test); bit 26: the block-2 (W = 4) weight gradient of the fp32
- *   path by k_wgrad_wino<4> (one full partial slab per tile) instead of the output-stationary k_wgrad4_os - same sums, other
- *   order (A/B timing and parity test). */
+/* Debug knob (returns the previous value); 0 = normal operation.  Each bit selects the second implementation a test
+ * compares against, or a measurement aid.  Every other bit is ignored: the A/B variants that earlier rounds kept behind
+ * them were removed. */
+#define SED_DEBUG_DIRECT_CONV    (1 << 6)   /* fp32 64 -> 64 convolutions (forward, dgrad) by the direct 9-tap kernels, not Winograd F(2x2, 3x3) */
+#define SED_DEBUG_DIRECT_WGRAD   (1 << 7)   /* fp32 64 -> 64 conv weight gradients by the direct kernels (k_wgrad16_db, k_conv3x3_wgrad<4, 3>) */
+#define SED_DEBUG_STFT_R2        (1 << 19)  /* log-mel front end by round 2's kernel k_stft_mel (one workgroup per frame) */
+#define SED_DEBUG_STFT_R3        (1 << 21)  /* log-mel front end by round 3's kernel k_stft_mel16 (one wave per frame) */
+#define SED_DEBUG_SEPARATE_HEADS (1 << 24)  /* sed_mt_step_backward: the deferred heads by k_heads_fwd / k_heads_bwd, not fused into the backward recurrence */
+#define SED_DEBUG_SLAB_WGRAD     (1 << 26)  /* fp32 block-2 (W = 4) weight gradient by k_wgrad_wino<4> (one partial slab per tile), not k_wgrad4_os */
+#define SED_DEBUG_STRICT_F32     (1 << 27)  /* strict fp32: no split-bf16 products anywhere in the step */
+#define SED_DEBUG_SAVED_GATES    (1 << 28)  /* bf16: block 0's forward saves its GLU gates and the backward reads them instead of recomputing */
+#define SED_DEBUG_NO_SIDE_STREAM (1 << 30)  /* no helper stream: every kernel on the caller's stream (near-solo kernel times) */
 int sed_debug_set(int flags);
-/* bit 0: the library was built with the A/B baseline kernels (make EXTRA=-DSED_AB); without it debug bits 1, 2, 3, 6, 7
- * are ignored - the shipped library carries the product path only. */
+/* Always 1: the direct kernels behind SED_DEBUG_DIRECT_CONV / SED_DEBUG_DIRECT_WGRAD are part of every build. */
 int sed_build_flags(void);
 
 /* ---- self tests (run on the GPU box by tests/) ---------------------------------------------

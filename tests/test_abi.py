@@ -160,7 +160,7 @@ def test_p2p_flag_never_overtakes_the_payload_in_the_compiled_kernel():
     src = os.path.join(REPO, "dcase2019_task4_amd", "csrc", "p2p.hip")
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "p2p.s")
-        subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-DSED_AB", "-S", "--cuda-device-only", src, "-o", out],
+        subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", src, "-o", out],
                        check=True, capture_output=True)
         text = open(out).read()
     kernels = re.split(r"^(_Z15k_p2p_allreduceILi\d+E[^:\n]*):", text, flags=re.M)

@@ -7,7 +7,7 @@ csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 files = sys.argv[1:] or sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
 for f in files:
     out = f"/tmp/bl_{f}.s"
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-DSED_AB", "-S", "--cuda-device-only",
+    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-S", "--cuda-device-only",
                     os.path.join(csrc, f), "-o", out], check=True, stderr=subprocess.DEVNULL)
     kern, rows = None, {}
     lines = open(out).read().split("\n")

@@ -10,7 +10,7 @@ od="$root/build/ab/obj_$name"; mkdir -p "$od"
 srcs=$(ls *.hip)            # the Makefile builds every .hip of this directory
 pids=""
 for s in $srcs; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -DSED_AB $flags -c $s -o "$od/${s%.hip}.o" &
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $flags -c $s -o "$od/${s%.hip}.o" &
   pids="$pids $!"
   while [ $(jobs -r | wc -l) -ge 8 ]; do sleep 0.2; done
 done

@@ -8,7 +8,7 @@ make -s
 name=$1; src=$2; flags=$3
 mkdir -p ../../build/variants
 obj=build/var_${name}_${src%.hip}.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -DSED_AB $flags -c $src -o $obj
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $flags -c $src -o $obj
 objs=$(ls build/*.o | grep -v "/var_" | grep -v "build/${src%.hip}.o")
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../../build/variants/libvar_${name}.so $objs $obj
 echo "built build/variants/libvar_${name}.so"

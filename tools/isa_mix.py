@@ -5,7 +5,7 @@ csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 src, kern = sys.argv[1], sys.argv[2]
 extra = sys.argv[3:]
 out = f"/tmp/{os.path.basename(src)}.s"
-subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-DSED_AB", "-S", "--cuda-device-only",
+subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-S", "--cuda-device-only",
                 os.path.join(csrc, src), "-o", out] + extra, check=True, stderr=subprocess.DEVNULL)
 lines = open(out).read().split("\n")
 start = next(i for i, l in enumerate(lines) if re.match(r"^_Z\w*" + kern + r"\w*:", l) or l.startswith(kern + ":"))
