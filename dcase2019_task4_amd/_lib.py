@@ -53,6 +53,9 @@ _SIGS = {
     "sed_scaler_stats": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]),
     "sed_postprocess": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_int, C.c_void_p]),
+    "sed_event_counts": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P,
+                                   C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P]),
+    "sed_weak_counts": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
     "sed_version": (C.c_int, []),
     "sed_param_count": (C.c_int, [C.POINTER(SedDims)]),
     "sed_param_layout": (C.c_int, [C.POINTER(SedDims), C.POINTER(C.c_int64)]),

@@ -38,6 +38,32 @@ def postprocess(strong, threshold=0.5, median_window=5, want_binary=False):
     return (cnt, pairs, binary) if want_binary else (cnt, pairs)
 
 
+def eval_batches(valid_dataset, batch_size, dev):
+    """The clips of ``valid_dataset`` (a ``DataLoadDf``-like or a ``ResidentFeatureSet.for_eval``) ``batch_size`` at a time:
+    yields ``(i0, range(i0, i0 + n), x [n, 1, T, F] float32 on dev)``."""
+    from .resident import ResidentFeatureSet
+    resident = isinstance(valid_dataset, ResidentFeatureSet)
+    stage, copied = None, None
+    n = len(valid_dataset)
+    for i0 in range(0, n, batch_size):
+        idx = range(i0, min(n, i0 + batch_size))
+        if resident:
+            x = valid_dataset.eval_batch(i0, len(idx))
+        else:
+            items = [torch.as_tensor(valid_dataset[i][0]) for i in idx]
+            if stage is None or stage.shape[1:] != items[0].shape or stage.dtype != items[0].dtype:
+                # one reusable pinned staging buffer: a fresh pageable torch.stack per batch cost more than the forward
+                stage = torch.empty((batch_size,) + tuple(items[0].shape), dtype=items[0].dtype).pin_memory()
+            if copied is not None:
+                copied.synchronize()      # a caller that never synchronises (metrics.validate) must not overtake the last upload
+            for k, it in enumerate(items):
+                stage[k].copy_(it)
+            x = stage[:len(items)].to(dev, non_blocking=True).float()
+            copied = torch.cuda.Event()
+            copied.record()
+        yield i0, idx, x
+
+
 def get_predictions(model, valid_dataset, decoder, pooling_time_ratio=1, save_predictions=None, batch_size=64, cfg=None,
                     threshold=0.5):
     """Drop-in for evaluation_measures.get_predictions.
@@ -61,23 +87,11 @@ def get_predictions(model, valid_dataset, decoder, pooling_time_ratio=1, save_pr
         raise _lib.SedError("get_predictions needs the model on the GPU (no CPU fallback)")
     was_training = model.training
     model.eval()
-    frames, cols, stage = [], [], None
-    n = len(valid_dataset)
+    frames, cols = [], []
     filenames = valid_dataset.filenames
     try:
         with torch.no_grad():
-            for i0 in range(0, n, batch_size):
-                idx = range(i0, min(n, i0 + batch_size))
-                if resident:
-                    x = valid_dataset.eval_batch(i0, len(idx))
-                else:
-                    items = [torch.as_tensor(valid_dataset[i][0]) for i in idx]
-                    if stage is None or stage.shape[1:] != items[0].shape or stage.dtype != items[0].dtype:
-                        # one reusable pinned staging buffer: a fresh pageable torch.stack per batch cost more than the forward
-                        stage = torch.empty((batch_size,) + tuple(items[0].shape), dtype=items[0].dtype).pin_memory()
-                    for k, it in enumerate(items):
-                        stage[k].copy_(it)
-                    x = stage[:len(items)].to(dev, non_blocking=True).float()
+            for i0, idx, x in eval_batches(valid_dataset, batch_size, dev):
                 strong, _ = model(x)
                 if labels is not None:
                     cnt, pairs = postprocess(strong, threshold, cfg.median_window)

@@ -1,0 +1,413 @@
+"""Validation scoring on the GPU: event-based, segment-based and clip-level (weak) F-measures - the half of the reference's
+epoch that follows ``get_predictions`` (baseline/main.py:328-352, evaluation_measures.py:19-102,124-182,234-246).
+
+The reference turns the device posteriors into a pandas table, then into per-file lists of dicts, and lets ``sed_eval`` match
+the events in Python, once per epoch.  Here ``sed_event_counts`` decodes the posteriors with the code of ``sed_postprocess``,
+keeps the events on the device, matches them against reference annotations that live there too (``RefEvents``) and returns
+integer counts; any number of operating points (threshold, median window) is one more grid dimension of the same launch.
+``sed_weak_counts`` does the same for the clip-level tags.  There is no CPU fallback.
+
+Provenance: ``sed_eval`` is third-party, absent from this image and from the reference tree, so the event / segment
+definitions are restated from its published algorithm - **parity with ``sed_eval`` itself is unpinned**, exactly as
+``oracle/postprocess_np.py`` states for ``dcase_util``.  What is pinned is exact agreement with an independent numpy / scipy
+statement of those definitions (``tests/sed_eval_np.py``).
+
+Definitions (per file and class; label equality is the column):
+
+* event-based: reference event r and estimated event e are compatible iff ``|r.on - e.on| <= t_collar`` and
+  ``|r.off - e.off| <= max(t_collar, percentage_of_length * (r.off - r.on))``; ``Ntp`` is the size of a maximum bipartite
+  matching (sed_eval's ``event_matching_type='optimal'``), ``Nfp = Nsys - Ntp``, ``Nfn = Nref - Ntp``.
+* segment-based: an event covers segments ``max(0, floor(on / res)) .. ceil(off / res) - 1``; a file has
+  ``ceil(max offset over both lists and all classes / res)`` segments.
+* ``P = Ntp / Nsys`` (0 when ``Nsys == 0``: ``empty_system_output_handling='zero_score'``), ``R = Ntp / Nref`` (NaN when
+  ``Nref == 0``), ``F = 2PR / (P + R)`` (0 when both are 0); class-wise average = ``nanmean`` over classes; overall = micro
+  over the summed counts; class-wise ``ER = (Nfn + Nfp) / Nref``.
+
+Limits: at most 64 reference and 64 estimated events per (file, class) - a column beyond that raises, it is never
+truncated -, ``T <= 2048`` output frames, at most 16 classes.  The overall error rate *with substitutions* needs a second,
+label-agnostic matching and is **not provided**: ``results_overall_metrics()['error_rate']`` holds NaN.
+"""
+import logging
+
+import numpy as np
+import torch
+
+from . import _lib
+from .inference import _Cfg, eval_batches
+
+LOG = logging.getLogger(__name__)
+MAX_EVENTS = 64
+MAX_CLASSES = 16
+_ERR_BITS = {1: "a (file, class) column has more than 64 reference events",
+             2: "a (file, class) column has more than 64 estimated events",
+             4: "a file has more than 65 536 segments",
+             8: "a median window outside 1 .. 63",
+             16: "malformed event offsets"}
+
+
+def _pack(df, filenames, labels):
+    """(filename, onset, offset, event_label) rows -> CSR arrays: column (clip, class) = clip * len(labels) + class, events
+    sorted by onset inside a column.  Rows with a NaN label carry no event (get_event_list_current_file,
+    evaluation_measures.py:105-121); rows of files outside ``filenames`` are ignored, as the reference's per-file loop does."""
+    filenames, labels = list(filenames), list(labels)
+    if len(set(filenames)) != len(filenames):
+        raise ValueError("duplicate file names")
+    file_ix = {f: i for i, f in enumerate(filenames)}
+    label_ix = {l: i for i, l in enumerate(labels)}
+    nc = len(labels)
+    ncol = len(filenames) * nc
+    d = df[df["event_label"].notna() & df["filename"].isin(file_ix)] if len(df) else df
+    if len(d) == 0:
+        return np.zeros(ncol + 1, np.int32), np.zeros(0, np.float64), np.zeros(0, np.float64)
+    unknown = sorted(set(d["event_label"]) - set(label_ix))
+    if unknown:
+        raise ValueError(f"event labels outside the label list: {unknown}")
+    col = d["filename"].map(file_ix).to_numpy(np.int64) * nc + d["event_label"].map(label_ix).to_numpy(np.int64)
+    on = d["onset"].to_numpy(np.float64)
+    off = d["offset"].to_numpy(np.float64)
+    order = np.lexsort((off, on, col))
+    ptr = np.zeros(ncol + 1, np.int64)
+    np.cumsum(np.bincount(col, minlength=ncol), out=ptr[1:])
+    return ptr.astype(np.int32), np.ascontiguousarray(on[order]), np.ascontiguousarray(off[order])
+
+
+class RefEvents:
+    """Reference annotations of a validation set on the device, in the CSR form ``sed_event_counts`` reads:
+    ``ptr [N * nclass + 1]`` int32, ``onset / offset [n_events]`` fp64 seconds.  On a CPU device it holds the arrays (what can
+    be checked without a GPU) and refuses to score."""
+
+    def __init__(self, ptr, onset, offset, filenames, labels, device="cuda"):
+        self.filenames, self.labels = list(filenames), list(labels)
+        if not 1 <= len(self.labels) <= MAX_CLASSES:
+            raise _lib.SedError(f"need 1 .. {MAX_CLASSES} classes, got {len(self.labels)}")
+        ptr = np.asarray(ptr, np.int32)
+        if ptr.shape != (len(self.filenames) * len(self.labels) + 1,) or ptr[0] != 0 or np.any(np.diff(ptr) < 0) \
+                or ptr[-1] != len(onset) or len(onset) != len(offset):
+            raise ValueError("malformed CSR arrays")
+        self.device = torch.device(device)
+        self.max_per_column = int(np.diff(ptr).max()) if len(ptr) > 1 else 0
+        self.ptr = torch.as_tensor(ptr).to(self.device)
+        # one trailing element: an empty event list still has an address the library accepts
+        self.onset = torch.as_tensor(np.r_[np.asarray(onset, np.float64), 0.0]).to(self.device)
+        self.offset = torch.as_tensor(np.r_[np.asarray(offset, np.float64), 0.0]).to(self.device)
+
+    @classmethod
+    def from_dataframe(cls, valid_df, filenames, labels, device="cuda"):
+        """``valid_df``: the reference's annotation frame (``filename, onset, offset, event_label``); clips in ``filenames``
+        order (``valid_synth_data.filenames``), classes in ``labels`` order (``many_hot_encoder.labels``).  A file with a
+        single NaN-label row, or absent from the frame, has no events."""
+        ptr, on, off = _pack(valid_df, filenames, labels)
+        return cls(ptr, on, off, filenames, labels, device)
+
+    def __len__(self):
+        return len(self.filenames)
+
+    @property
+    def nclass(self):
+        return len(self.labels)
+
+
+class Counts:
+    """Class totals of one or more ``event_counts`` calls, on the device: ``ev [K, nclass, 3]`` (Ntp, Nref, Nsys) and
+    ``seg [K, nclass, 4]`` (Ntp, Nfp, Nfn, Ntn) int64, and the error word, all in ONE buffer so that ``host()`` is one copy.
+    ``ev_columns [K, N, nclass, 3]`` / ``seg_columns [K, N, nclass, 4]`` int32 hold the last call's per-column counts when it
+    was asked for them."""
+
+    def __init__(self, n_points, nclass, device):
+        self.K, self.NC = n_points, nclass
+        self.buf = torch.zeros(n_points * nclass * 7 + 1, dtype=torch.int64, device=device)
+        n3 = n_points * nclass * 3
+        self.ev = self.buf[:n3].view(n_points, nclass, 3)
+        self.seg = self.buf[n3:-1].view(n_points, nclass, 4)
+        self.err = self.buf[-1:].view(torch.int32)
+        self.ev_columns = self.seg_columns = None
+
+    def host(self):
+        """(ev, seg) as numpy arrays - one device -> host copy; raises when a column was over a limit."""
+        h = self.buf.cpu().numpy()
+        err = int(h[-1:].view(np.int32)[0])
+        if err:
+            raise _lib.SedError("sed_event_counts: " + "; ".join(m for b, m in _ERR_BITS.items() if err & b)
+                                + " - nothing was truncated, the counts are invalid")
+        n3 = self.K * self.NC * 3
+        return h[:n3].reshape(self.K, self.NC, 3), h[n3:-1].reshape(self.K, self.NC, 4)
+
+    check = host
+
+
+def operating_points(thresholds=(0.5,), median_windows=(5,), device="cuda"):
+    """K operating points as device arrays ``(thr [K] float32, win [K] int32)``: sequences of equal length, or one of them of
+    length 1.  Build them once outside a loop or a graph capture."""
+    if torch.is_tensor(thresholds) and torch.is_tensor(median_windows):
+        return thresholds, median_windows
+    thr = np.atleast_1d(np.asarray(thresholds, np.float32))
+    win = np.atleast_1d(np.asarray(median_windows, np.int32))
+    K = max(len(thr), len(win))
+    if len(thr) not in (1, K) or len(win) not in (1, K) or K < 1:
+        raise ValueError("thresholds and median_windows must have equal lengths (or length 1)")
+    if win.min() < 1 or win.max() > 63:
+        raise _lib.SedError("median windows must be in [1, 63]")
+    thr, win = np.broadcast_to(thr, K).copy(), np.broadcast_to(win, K).copy()
+    return torch.as_tensor(thr).to(device), torch.as_tensor(win).to(device)
+
+
+def event_counts(strong, ref, thresholds=(0.5,), median_windows=(5,), pooling_time_ratio=1, cfg=None, t_collar=0.200,
+                 percentage_of_length=0.2, time_resolution=1.0, clip_offset=0, counts=None, per_column=False):
+    """``strong [n, T, nclass]`` cuda float32 posteriors of clips ``clip_offset .. clip_offset + n - 1`` of ``ref`` -> ``Counts``
+    (device tensors, no synchronisation; pass ``counts`` to accumulate batches).  ``thresholds`` / ``median_windows``: see
+    ``operating_points`` (device tensors are taken as they are).  ``cfg`` supplies sample_rate / hop_length (default
+    baseline/config.py): seconds = frame * pooling_time_ratio / (sample_rate / hop_length), evaluation_measures.py:226-227."""
+    if strong.device.type != "cuda" or ref.device.type != "cuda":
+        raise _lib.SedError("event_counts needs GPU tensors and a RefEvents on the GPU (no CPU fallback)")
+    cfg = cfg or _Cfg
+    strong = strong.contiguous().float()
+    n, T, NC = strong.shape
+    if NC != ref.nclass or clip_offset < 0 or clip_offset + n > len(ref):
+        raise ValueError(f"posteriors [{n}, {T}, {NC}] at clip {clip_offset} do not fit the reference ({len(ref)} clips, "
+                         f"{ref.nclass} classes)")
+    thr, win = operating_points(thresholds, median_windows, strong.device)
+    K = thr.numel()
+    if counts is None:
+        counts = Counts(K, NC, strong.device)
+    if (counts.K, counts.NC) != (K, NC):
+        raise ValueError("counts was built for another number of operating points / classes")
+    if per_column:
+        counts.ev_columns = torch.empty(K, n, NC, 3, dtype=torch.int32, device=strong.device)
+        counts.seg_columns = torch.empty(K, n, NC, 4, dtype=torch.int32, device=strong.device)
+    _lib.check(_lib.lib().sed_event_counts(
+        _lib.ptr(strong), n, T, NC, K, _lib.ptr(thr), _lib.ptr(win), float(pooling_time_ratio),
+        float(cfg.sample_rate / cfg.hop_length), None, None, None, _lib.ptr(ref.ptr[clip_offset * NC:]), _lib.ptr(ref.onset),
+        _lib.ptr(ref.offset), float(t_collar), float(percentage_of_length), float(time_resolution),
+        _lib.ptr(counts.ev_columns) if per_column else None, _lib.ptr(counts.seg_columns) if per_column else None,
+        _lib.ptr(counts.ev), _lib.ptr(counts.seg), _lib.ptr(counts.err), _lib.stream_ptr()), "sed_event_counts")
+    return counts
+
+
+def event_counts_from_events(est, ref, t_collar=0.200, percentage_of_length=0.2, time_resolution=1.0, per_column=False):
+    """The matching stage alone: ``est`` is a ``RefEvents`` holding the ESTIMATED events of the same files and classes (they
+    need not be disjoint).  One operating point."""
+    if est.device.type != "cuda" or ref.device.type != "cuda":
+        raise _lib.SedError("event_counts_from_events needs both event sets on the GPU (no CPU fallback)")
+    if est.filenames != ref.filenames or est.labels != ref.labels:
+        raise ValueError("estimated and reference events must cover the same files and classes, in the same order")
+    n, NC = len(ref), ref.nclass
+    counts = Counts(1, NC, ref.device)
+    if per_column:
+        counts.ev_columns = torch.empty(1, n, NC, 3, dtype=torch.int32, device=ref.device)
+        counts.seg_columns = torch.empty(1, n, NC, 4, dtype=torch.int32, device=ref.device)
+    _lib.check(_lib.lib().sed_event_counts(
+        None, n, 0, NC, 1, None, None, 0.0, 0.0, _lib.ptr(est.ptr), _lib.ptr(est.onset), _lib.ptr(est.offset),
+        _lib.ptr(ref.ptr), _lib.ptr(ref.onset), _lib.ptr(ref.offset), float(t_collar), float(percentage_of_length),
+        float(time_resolution), _lib.ptr(counts.ev_columns) if per_column else None,
+        _lib.ptr(counts.seg_columns) if per_column else None, _lib.ptr(counts.ev), _lib.ptr(counts.seg), _lib.ptr(counts.err),
+        _lib.stream_ptr()), "sed_event_counts")
+    return counts
+
+
+def weak_counts(weak, labels, thresholds, counts=None):
+    """``weak [n, nclass]`` cuda float32, ``labels [n, nclass]`` 0/1, ``thresholds [K, nclass]`` (or ``[nclass]``) ->
+    ``[K, nclass, 4]`` int64 (tp, fp, fn, tn) with ``pred = weak > thr`` (intermediate_at_measures,
+    evaluation_measures.py:86-102), on the device, no synchronisation.  Pass ``counts`` to accumulate batches."""
+    if weak.device.type != "cuda":
+        raise _lib.SedError("weak_counts needs GPU tensors (no CPU fallback)")
+    weak = weak.contiguous().float()
+    n, NC = weak.shape
+    labels = labels.to(weak.device).ne(0).to(torch.uint8).contiguous()
+    thr = torch.as_tensor(thresholds, dtype=torch.float32).to(weak.device).reshape(-1, NC).contiguous()
+    if labels.shape != weak.shape:
+        raise ValueError(f"labels {tuple(labels.shape)} do not match the posteriors {tuple(weak.shape)}")
+    K = thr.shape[0]
+    if counts is None:
+        counts = torch.zeros(K, NC, 4, dtype=torch.int64, device=weak.device)
+    if tuple(counts.shape) != (K, NC, 4) or counts.dtype != torch.int64 or not counts.is_contiguous():
+        raise ValueError("counts must be a contiguous int64 [K, nclass, 4] tensor")
+    _lib.check(_lib.lib().sed_weak_counts(_lib.ptr(weak), _lib.ptr(labels), n, NC, _lib.ptr(thr), K, _lib.ptr(counts),
+                                          _lib.stream_ptr()), "sed_weak_counts")
+    return counts
+
+
+# ---- the numbers main.py and its logs read, with sed_eval's key names ------------------------------------------------------
+def _ratio(num, den, empty):
+    return float(num) / float(den) if den > 0 else empty
+
+
+def _f_measure(p, r):
+    if p == 0 and r == 0:
+        return 0.0
+    return 2 * p * r / (p + r)
+
+
+def _nanmean(values):
+    v = np.asarray(values, np.float64)
+    return float(np.nansum(v) / np.count_nonzero(~np.isnan(v))) if np.any(~np.isnan(v)) else float("nan")
+
+
+class _Metrics:
+    """Ratios from per-class (Ntp, Nref, Nsys, Nfp, Nfn[, Ntn]) with sed_eval's result layout."""
+    name = ""
+
+    def __init__(self, labels, ntp, nref, nsys, nfp, nfn):
+        self.event_label_list = list(labels)
+        self.class_wise = {l: {"Ntp": int(a), "Nref": int(b), "Nsys": int(c), "Nfp": int(d), "Nfn": int(e)}
+                           for l, a, b, c, d, e in zip(self.event_label_list, ntp, nref, nsys, nfp, nfn)}
+        if len(self.class_wise) != len(self.event_label_list) or len(ntp) != len(self.event_label_list):
+            raise ValueError("one row of counts per (distinct) label")
+
+    @staticmethod
+    def _scores(c):
+        p = _ratio(c["Ntp"], c["Nsys"], 0.0)                    # empty_system_output_handling = 'zero_score'
+        r = _ratio(c["Ntp"], c["Nref"], float("nan"))
+        return {"f_measure": {"f_measure": _f_measure(p, r), "precision": p, "recall": r},
+                "error_rate": {"error_rate": _ratio(c["Nfn"] + c["Nfp"], c["Nref"], float("nan")),
+                               "deletion_rate": _ratio(c["Nfn"], c["Nref"], float("nan")),
+                               "insertion_rate": _ratio(c["Nfp"], c["Nref"], float("nan"))}}
+
+    def results_class_wise_metrics(self):
+        out = {}
+        for l, c in self.class_wise.items():
+            out[l] = dict(self._scores(c), count={"Nref": c["Nref"], "Nsys": c["Nsys"]})
+        return out
+
+    def results_class_wise_average_metrics(self):
+        cw = list(self.results_class_wise_metrics().values())
+        return {g: {k: _nanmean([c[g][k] for c in cw]) for k in keys}
+                for g, keys in (("f_measure", ("f_measure", "precision", "recall")),
+                                ("error_rate", ("error_rate", "deletion_rate", "insertion_rate")))}
+
+    def results_overall_metrics(self):
+        """Micro-averaged F-measure over the summed counts.  The overall error rate of sed_eval counts substitutions, which
+        needs a second, label-agnostic matching: it is NOT computed - the four error-rate keys hold NaN."""
+        tot = {k: sum(c[k] for c in self.class_wise.values()) for k in ("Ntp", "Nref", "Nsys", "Nfp", "Nfn")}
+        nan = float("nan")
+        return {"f_measure": self._scores(tot)["f_measure"],
+                "error_rate": {"error_rate": nan, "substitution_rate": nan, "deletion_rate": nan, "insertion_rate": nan}}
+
+    def results(self):
+        return {"overall": self.results_overall_metrics(), "class_wise": self.results_class_wise_metrics(),
+                "class_wise_average": self.results_class_wise_average_metrics()}
+
+    def __str__(self):
+        ov, av = self.results_overall_metrics()["f_measure"], self.results_class_wise_average_metrics()
+        lines = [f"{self.name} metrics ({self._params()})",
+                 "  Overall (micro-average): F {:6.2f} %  P {:6.2f} %  R {:6.2f} %".format(
+                     100 * ov["f_measure"], 100 * ov["precision"], 100 * ov["recall"]),
+                 "  Class-wise average (macro-average): F {:6.2f} %  P {:6.2f} %  R {:6.2f} %  ER {:5.2f}".format(
+                     100 * av["f_measure"]["f_measure"], 100 * av["f_measure"]["precision"], 100 * av["f_measure"]["recall"],
+                     av["error_rate"]["error_rate"]),
+                 "  {:30s} {:>6s} {:>6s} {:>8s} {:>8s} {:>8s} {:>6s}".format("Event label", "Nref", "Nsys", "F", "Pre", "Rec", "ER")]
+        for l, c in self.results_class_wise_metrics().items():
+            f, e = c["f_measure"], c["error_rate"]
+            lines.append("  {:30s} {:6d} {:6d} {:7.1f}% {:7.1f}% {:7.1f}% {:6.2f}".format(
+                str(l)[:30], c["count"]["Nref"], c["count"]["Nsys"], 100 * f["f_measure"], 100 * f["precision"],
+                100 * f["recall"], e["error_rate"]))
+        return "\n".join(lines)
+
+
+class EventMetrics(_Metrics):
+    """Event-based metrics from class totals ``[nclass, 3]`` (Ntp, Nref, Nsys) - what ``sed_eval``'s ``EventBasedMetrics``
+    reports to main.py and its logs (``Nfp = Nsys - Ntp``, ``Nfn = Nref - Ntp``)."""
+    name = "Event based"
+
+    def __init__(self, labels, counts, t_collar=0.200, percentage_of_length=0.2):
+        c = np.asarray(counts, np.int64).reshape(-1, 3)
+        self.t_collar, self.percentage_of_length = t_collar, percentage_of_length
+        super().__init__(labels, c[:, 0], c[:, 1], c[:, 2], c[:, 2] - c[:, 0], c[:, 1] - c[:, 0])
+
+    def _params(self):
+        return f"onset-offset, t_collar {self.t_collar:.2f} s, offset (length) {100 * self.percentage_of_length:.0f} %"
+
+
+class SegmentMetrics(_Metrics):
+    """Segment-based metrics from class totals ``[nclass, 4]`` (Ntp, Nfp, Nfn, Ntn) - ``sed_eval``'s ``SegmentBasedMetrics``
+    (``Nref = Ntp + Nfn``, ``Nsys = Ntp + Nfp``)."""
+    name = "Segment based"
+
+    def __init__(self, labels, counts, time_resolution=1.0):
+        c = np.asarray(counts, np.int64).reshape(-1, 4)
+        self.time_resolution = time_resolution
+        self.Ntn = {l: int(v) for l, v in zip(labels, c[:, 3])}
+        super().__init__(labels, c[:, 0], c[:, 0] + c[:, 2], c[:, 0] + c[:, 1], c[:, 1], c[:, 2])
+
+    def _params(self):
+        return f"time resolution {self.time_resolution:.2f} s"
+
+
+# ---- drop-ins with the reference's signatures -------------------------------------------------------------------------------
+def compute_strong_metrics(predictions, valid_df, pooling_time_ratio=None, cfg=None, device="cuda"):
+    """Drop-in for evaluation_measures.compute_strong_metrics (lines 234-246): event tables in, the event-based metric out,
+    both metrics logged.  The two tables are packed and matched by ``sed_event_counts`` (given-events mode): the device
+    matcher serves this route too.  Files = ``valid_df.filename.unique()``, classes = the labels of both tables."""
+    cfg = cfg or _Cfg
+    if pooling_time_ratio is not None:
+        LOG.warning("pooling_time_ratio is deprecated, use it in get_predictions() instead.")
+        predictions.onset = predictions.onset * pooling_time_ratio / (cfg.sample_rate / cfg.hop_length)
+        predictions.offset = predictions.offset * pooling_time_ratio / (cfg.sample_rate / cfg.hop_length)
+    files = list(valid_df["filename"].unique())
+    labels = sorted(set(valid_df.event_label.dropna().unique()) | set(predictions.event_label.dropna().unique()))
+    ref = RefEvents.from_dataframe(valid_df, files, labels, device)
+    est = RefEvents.from_dataframe(predictions, files, labels, device)
+    ev, seg = event_counts_from_events(est, ref).host()
+    metric_event, metric_segment = EventMetrics(labels, ev[0]), SegmentMetrics(labels, seg[0])
+    LOG.info(metric_event)
+    LOG.info(metric_segment)
+    return metric_event
+
+
+def get_f_measure_by_class(torch_model, nb_tags, dataloader_, thresholds_=None):
+    """Drop-in for evaluation_measures.get_f_measure_by_class (lines 19-83): per-class clip-level F1 of ``torch_model`` over
+    ``dataloader_`` (batches ``(batch_x, y)``, ``y`` 0/1).  Forward in the loader's batches, ``sed_weak_counts`` per batch
+    into running totals, one device -> host copy at the end."""
+    dev = next(torch_model.parameters()).device
+    if dev.type != "cuda":
+        raise _lib.SedError("get_f_measure_by_class needs the model on the GPU (no CPU fallback)")
+    if thresholds_ is None:
+        thr = [0.5] * nb_tags
+    else:
+        assert type(thresholds_) is list
+        thr = thresholds_
+    thr = torch.tensor(thr, dtype=torch.float32, device=dev).reshape(1, nb_tags)
+    counts = torch.zeros(1, nb_tags, 4, dtype=torch.int64, device=dev)
+    with torch.no_grad():
+        for batch_x, y in dataloader_:
+            _, pred_weak = torch_model(batch_x.to(dev))
+            if pred_weak.dim() == 3:             # a model predicting only strong outputs (line 49-51)
+                pred_weak = pred_weak.max(dim=1).values
+            y = torch.as_tensor(y)
+            if y.dim() == 3:                     # strong labels: max over time, binarised at 0.5 (lines 53-57)
+                y = y.max(dim=1).values > 0.5
+            weak_counts(pred_weak, y, thr, counts)
+    tp, fp, fn, _ = (v.astype(np.float64) for v in counts.cpu().numpy()[0].T)
+    macro_f_measure = np.zeros(nb_tags)
+    mask_f_score = 2 * tp + fp + fn != 0
+    macro_f_measure[mask_f_score] = 2 * tp[mask_f_score] / (2 * tp + fp + fn)[mask_f_score]
+    return macro_f_measure
+
+
+def validate(model, dataset, ref, pooling_time_ratio, thresholds=(0.5,), median_windows=(5,), batch_size=64, cfg=None):
+    """The fused route for the epoch loop (main.py:324-328 without the event table): ``dataset`` as
+    ``inference.get_predictions`` accepts it, forward ``batch_size`` clips at a time, ``sed_event_counts`` per batch into
+    running totals, ONE device -> host copy at the end.  ``ref``: the ``RefEvents`` of the same clips in the same order.
+    Returns one ``(EventMetrics, SegmentMetrics)`` per operating point."""
+    from .resident import ResidentFeatureSet
+    if not getattr(model, "hot_path", False):
+        raise _lib.SedError("validate needs a CRNN on the HIP hot path")
+    if isinstance(dataset, ResidentFeatureSet) and dataset.noise:
+        raise ValueError("validate needs a validation set without noise (ResidentFeatureSet.for_eval)")
+    dev = next(model.parameters()).device
+    if dev.type != "cuda":
+        raise _lib.SedError("validate needs the model on the GPU (no CPU fallback)")
+    if len(dataset) != len(ref):
+        raise ValueError(f"{len(dataset)} clips but reference events of {len(ref)}")
+    thr, win = operating_points(thresholds, median_windows, dev)
+    counts = Counts(thr.numel(), ref.nclass, dev)
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for i0, _, x in eval_batches(dataset, batch_size, dev):
+                strong, _ = model(x)
+                event_counts(strong, ref, thr, win, pooling_time_ratio, cfg, clip_offset=i0, counts=counts)
+    finally:
+        model.train(was_training)
+    ev, seg = counts.host()
+    return [(EventMetrics(ref.labels, ev[k]), SegmentMetrics(ref.labels, seg[k])) for k in range(thr.numel())]

@@ -422,6 +422,49 @@ int sed_postprocess(const float* strong, int n_clips, int T, int nclass, float t
                     int median_window, uint8_t* binary, int32_t* ev_count, int32_t* ev_pairs,
                     int max_events, void* stream);
 
+/* ---- validation scoring ------------------------------------------------------------------------
+ * Replaces, after get_predictions, the host-side scoring of the epoch loop (baseline/main.py:328-352):
+ *   compute_strong_metrics(predictions, valid_synth_df) (evaluation_measures.py:234-246) = sed_eval's
+ *   EventBasedMetrics(t_collar = 0.2, percentage_of_length = 0.2, 'zero_score', optimal matching) and
+ *   SegmentBasedMetrics(time_resolution = 1) fed per file (evaluation_measures.py:124-182), and
+ *   get_f_measure_by_class / intermediate_at_measures (evaluation_measures.py:19-102).
+ * sed_eval is third-party, absent from this image and from the reference tree: the event / segment definitions
+ * are restated from its published algorithm - parity with sed_eval itself is UNPINNED (as for dcase_util in
+ * sed_postprocess); pinned is exact agreement with an independent numpy / scipy statement of the definitions
+ * (tests/sed_eval_np.py).
+ *
+ * sed_event_counts, per (operating point k, clip, class) column:
+ *   estimated events: strong != NULL: threshold thr[k] -> median filter win[k] (1 .. 63) -> run-length decode exactly
+ *     as sed_postprocess, seconds = (double)frame * num / den (num = pooling_time_ratio, den = sample_rate /
+ *     hop_length: the host's doubles bit for bit); strong == NULL: given as est_ptr / est_on / est_off (CSR like
+ *     the reference events, n_points = 1, need not be disjoint).
+ *   reference events: ref_ptr [n_clips * nclass + 1] int32 offsets into ref_on / ref_off (fp64 seconds), column
+ *     (clip, class) = clip * nclass + class.
+ *   event-based: r and e are compatible iff |r.on - e.on| <= t_collar and |r.off - e.off| <= max(t_collar,
+ *     percentage_of_length * (r.off - r.on)); Ntp = size of a MAXIMUM bipartite matching; Nref, Nsys = list lengths.
+ *   segment-based: an event covers segments max(0, floor(on / res)) .. ceil(off / res) - 1; the file has
+ *     ceil(max offset over both lists and all classes / res) segments; Ntp, Nfp, Nfn, Ntn per class.
+ *   ev_counts  [n_points][n_clips][nclass][3] int32 (Ntp, Nref, Nsys) or NULL
+ *   seg_counts [n_points][n_clips][nclass][4] int32 (Ntp, Nfp, Nfn, Ntn) or NULL
+ *   ev_total   [n_points][nclass][3], seg_total [n_points][nclass][4] int64: ACCUMULATED over clips (zero them
+ *              before the first batch; integer sums: bit-reproducible)
+ *   err        one int32, OR-ed: 1 = a column with more than 64 reference events, 2 = more than 64 estimated
+ *              events, 4 = a file of more than 65 536 segments, 8 = a window outside 1 .. 63, 16 = malformed
+ *              offsets.  Such a column is not scored (never a truncated count): a caller must treat the totals as
+ *              invalid when err != 0.
+ * Limits: T <= 2048, nclass <= 16.  The overall error rate with substitutions (a second, label-agnostic
+ * matching) is not computed.
+ * sed_weak_counts: weak [n_clips][nclass] fp32, labels [n_clips][nclass] uint8, thr [n_points][nclass] ->
+ *   counts [n_points][nclass][4] int64 (tp, fp, fn, tn) with pred = weak > thr, ACCUMULATED (chain the batches).
+ * Both: one launch on `stream`, no allocation, hipGraph-capturable. */
+int sed_event_counts(const float* strong, int n_clips, int T, int nclass, int n_points, const float* thr,
+                     const int32_t* win, double num, double den, const int32_t* est_ptr, const double* est_on,
+                     const double* est_off, const int32_t* ref_ptr, const double* ref_on, const double* ref_off,
+                     double t_collar, double percentage_of_length, double time_resolution, int32_t* ev_counts,
+                     int32_t* seg_counts, int64_t* ev_total, int64_t* seg_total, int32_t* err, void* stream);
+int sed_weak_counts(const float* weak, const uint8_t* labels, int n_clips, int nclass, const float* thr,
+                    int n_points, int64_t* counts, void* stream);
+
 /* ---- single-kernel replay (measurement) ----------------------------------------------------
  * Re-launches ONE kernel of the step on the buffers left by a finished sed_crnn_forward +
  * sed_crnn_backward (same shapes, same data; outputs are rewritten with identical values), so

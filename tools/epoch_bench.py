@@ -7,8 +7,10 @@ than `frames`).  Device-event timing; prints one JSON object (and writes it to -
   (c) 20 steps of the drop-in path: DataLoadDf-style dataset (np.load per clip) + features.get_transforms, num_workers=0,
       host collate, step.step
   (d) get_predictions over 400 validation clips: per-clip dataset (np.load + get_transforms per clip) against the resident set
+  (e) validation scoring over 1 168 and 400 resident clips: metrics.validate at one operating point and at 50 thresholds, the
+      DataFrame route (get_predictions + compute_strong_metrics), and sed_event_counts alone (--only-e: this leg only)
 
-Usage: python tools/epoch_bench.py [--shapes 24:f32,64:bf16] [--only-a] [--out FILE]"""
+Usage: python tools/epoch_bench.py [--shapes 24:f32,64:bf16] [--only-a | --only-e] [--out FILE]"""
 import argparse
 import json
 import os
@@ -180,10 +182,76 @@ def leg_d(feats, sc, tmp, n=400):
             "same_dataframe": bool(same)}
 
 
+def leg_e(feats, sc, sizes=(1168, 400), reps=20):
+    """Median over ``reps`` of a host clock around calls that end in a device -> host copy (warmed up once each); the
+    sed_event_counts share is device-event time of the launches alone on the set's posteriors."""
+    import pandas as pd
+    from dcase2019_task4_amd import metrics
+    from dcase2019_task4_amd.inference import get_predictions
+    from oracle import postprocess_np as pp
+    model, _ = bench.build_models("cuda", seed=0)
+    model.eval()
+    labels = [f"c{i}" for i in range(NCLASS)]
+    enc = type("Enc", (), {"labels": labels, "decode_strong": lambda self, m: pp.decode_strong(m, labels)})()
+    base = sum(SIZES[:2])
+
+    def wall_ms(fn):
+        fn()
+        times = []
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times.append((time.perf_counter() - t0) * 1e3)
+        return round(float(np.median(times)), 3)
+
+    out = []
+    for n in sizes:
+        ds = type("DS", (), {"__len__": lambda self: n, "get_sample": lambda self, k: (feats[base + k], np.zeros(1)),
+                             "filenames": pd.Series([f"clip_{i}.wav" for i in range(n)])})()
+        res = ResidentFeatureSet.for_eval(ds, T, sc)
+        files = res.filenames.tolist()
+        rs = np.random.RandomState(n)                     # DESED-like annotations: 0 .. 5 events per clip, 0.25 .. 10 s
+        rows = []
+        for f in files:
+            for _ in range(rs.randint(0, 6)):
+                on = rs.uniform(0.0, 9.0)
+                rows.append((f, on, min(10.0, on + rs.uniform(0.25, 5.0)), labels[rs.randint(NCLASS)]))
+        valid_df = pd.DataFrame(rows, columns=["filename", "onset", "offset", "event_label"])
+        ref = metrics.RefEvents.from_dataframe(valid_df, files, labels)
+        thr50 = [float(v) for v in np.linspace(0.01, 0.99, 50)]
+        with torch.no_grad():
+            strong = torch.cat([model(res.eval_batch(i0, min(64, n - i0)))[0] for i0 in range(0, n, 64)])
+        thr1, win1 = metrics.operating_points((0.5,), (5,), "cuda")
+        thr_k, win_k = metrics.operating_points(thr50, (5,), "cuda")
+
+        def count_launches(thr, win):
+            counts = metrics.Counts(thr.numel(), NCLASS, "cuda")
+            return lambda: [metrics.event_counts(strong[i0:i0 + 64], ref, thr, win, 8, clip_offset=i0, counts=counts)
+                            for i0 in range(0, n, 64)]
+        n_est = int(count_launches(thr1, win1)()[-1].host()[0][0, :, 2].sum())
+        count_launches(thr_k, win_k)()
+        # (a randomly initialised CRNN: posteriors nearly constant in time, so few estimated events per clip)
+        leg = {"clips": n, "batch_size": 64, "reference_events": len(rows), "estimated_events_at_0.5": n_est,
+               "i_validate_1_point_ms": wall_ms(lambda: metrics.validate(model, res, ref, 8, batch_size=64)),
+               "ii_validate_50_thresholds_ms": wall_ms(lambda: metrics.validate(model, res, ref, 8, thr50, (5,), batch_size=64)),
+               "iii_dataframe_route_ms": wall_ms(lambda: metrics.compute_strong_metrics(
+                   get_predictions(model, res, enc.decode_strong, 8, batch_size=64), valid_df)),
+               "iv_event_counts_only_1_point_ms": round(event_ms(count_launches(thr1, win1), 20), 4),
+               "iv_event_counts_only_50_thresholds_ms": round(event_ms(count_launches(thr_k, win_k), 20), 4)}
+        leg["iv_share_of_i"] = round(leg["iv_event_counts_only_1_point_ms"] / leg["i_validate_1_point_ms"], 4)
+        leg["ii_over_i"] = round(leg["ii_validate_50_thresholds_ms"] / leg["i_validate_1_point_ms"], 3)
+        out.append(leg)
+        print(json.dumps(leg), flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="24:f32,64:bf16")
     ap.add_argument("--only-a", action="store_true", help="leg (a) only (for a kernel trace of the resident epoch)")
+    ap.add_argument("--only-e", action="store_true", help="leg (e) only: validation scoring")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dev = torch.cuda.get_device_properties(0)
@@ -195,7 +263,7 @@ def main():
                                            "bytes": int(lengths.sum()) * N_MELS * 4}, "legs": []}
     build_s = None
     with tempfile.TemporaryDirectory() as tmp:
-        for shape in a.shapes.split(","):
+        for shape in ([] if a.only_e else a.shapes.split(",")):
             B, dtype = int(shape.split(":")[0]), shape.split(":")[1]
             bs = [B // 4, B // 2, B // 4]
             tb = time.perf_counter()
@@ -217,8 +285,11 @@ def main():
             print(json.dumps(leg), flush=True)
             del rs
             torch.cuda.empty_cache()
-        if not a.only_a:
+        if not a.only_a and not a.only_e:
             result["d_get_predictions"] = leg_d(feats, sc, tmp)
+        if not a.only_a:
+            result["e_validation_scoring"] = leg_e(feats, sc)
+            result["command"] = "python tools/epoch_bench.py" + (" --only-e" if a.only_e else f" --shapes {a.shapes}")
     result["pool"]["build_s"] = build_s
     result["total_s"] = round(time.perf_counter() - t0, 1)
     line = json.dumps(result)
