@@ -2,7 +2,7 @@
 //
 // Mirrors the operator sequence of CRNN.forward (baseline/models/CRNN.py:59-84):
 //   conv block 0 (blk0.hip, fully fused) -> [conv3x3 + BN stats (conv.hip) -> BN/GLU/dropout/pool
-//   (bnglu.hip)] x 2 -> 2-layer BiGRU (gru4.hip: input projection + recurrence per layer) -> heads (heads.hip)
+//   (bnglu.hip)] x 2 -> BiGRU + heads (rnn.hip, shared with gcrnn.hip)
 // All launches go to the caller's stream; no allocation, no synchronisation.
 #include <stdarg.h>
 #include <map>
@@ -13,6 +13,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "gkernels.h"
+#include "rnn.h"
 
 static thread_local char g_err[512] = "";
 void sed_set_error(const char* fmt, ...) {
@@ -116,7 +117,7 @@ WsLayout make_ws_layout(const Geo& g) {
     for (int l = 0; l < 2; ++l) { put(W.dgi[l], bt * 384 * 4); put(W.dgh[l], bt * 384 * 4); put(W.hprev[l], bt * 128 * 4); }
     put(W.d_in, 2 * bt * 128 * 4); put(W.heads_part, (size_t)g.B * 2 * (g.NC * 128 + g.NC) * 4);
     put(W.dp2, 2 * bt * 64 * 4); put(W.dz2, n1 * 4); put(W.dp1, n1 * 4); put(W.dz1, n0 * 4); put(W.dp0, n0 * 4);
-    put(W.bnb, 256 * sizeof(double)); W.coef[0] = 0; put(W.coef[1], 192 * 4); put(W.coef[2], 192 * 4);
+    put(W.pad0, 256 * sizeof(double)); W.coef[0] = 0; put(W.coef[1], 192 * 4); put(W.coef[2], 192 * 4);
     put(W.bwd_acc, (2 * SED_GLUACC_N + 2 * 64 * 10) * sizeof(double));
     W.gluacc1 = W.bwd_acc; W.gluacc2 = W.bwd_acc + SED_GLUACC_N * sizeof(double); W.de0 = W.bwd_acc + 2 * SED_GLUACC_N * sizeof(double);
     W.wgrad_blocks = SED_WGRAD_MAX_BLOCKS;
@@ -177,10 +178,7 @@ extern "C" int sed_crnn_ctx_view(const sed_dims* d, const char* name, size_t* of
     return SED_ERR_BAD_ARG;
 }
 
-// ---- side stream: weight-gradient work that is off the backward critical path ---------------------
-// The dX chain (heads -> GRU -> dgrad2 -> dgrad1 -> block 0) is serial; the GRU dW/db GEMMs and the conv
-// wgrads only feed the optimiser.  They are forked onto a helper stream and joined before the call returns, so
-// the caller still sees one stream-ordered op and a hipGraph capture records the fork/join as graph edges.
+// ---- side stream: weight-gradient work that is off the backward critical path (rnn.h: SideFork) ----
 // One helper stream + fork/join event pair exists per (device, caller stream): two host threads (or two models on two
 // GPUs of one process) that call in on different streams never share events.  The pool is created under a mutex, on
 // first use or - preferably, so that nothing is created while the caller's stream is being captured -
@@ -287,22 +285,33 @@ int sed_fork_point(hipStream_t st) {
     if (h.fn) h.fn(h.user);
     return SED_OK;
 }
-#define SIDE_FORK(main_st)                                          \
-    do {                                                            \
-        SED_CHECK_HIP(hipEventRecord(sd.fork, (main_st)));          \
-        SED_CHECK_HIP(hipStreamWaitEvent(sd.s, sd.fork, 0));        \
-    } while (0)
-#define SIDE_JOIN(main_st)                                          \
-    do {                                                            \
-        SED_CHECK_HIP(hipEventRecord(sd.join, sd.s));               \
-        SED_CHECK_HIP(hipStreamWaitEvent((main_st), sd.join, 0));   \
-    } while (0)
+// one backward call's handle (SED_DEBUG_NO_SIDE_STREAM: every kernel on the caller's stream, for near-solo kernel times)
+static SideFork side_fork(hipStream_t st) {
+    SideStream& sd = side_stream(st);
+    const bool ok = sd.ok && !(g_sed_debug & SED_DEBUG_NO_SIDE_STREAM);
+    return SideFork{ok ? sd.s : st, sd.fork, sd.join, ok, false};
+}
 
 #define CTXF(off) ((float*)((char*)ctx + (off)))
 #define CTXD(off) ((double*)((char*)ctx + (off)))
 #define WSF(off) ((float*)((char*)ws + (off)))
 #define WSD(off) ((double*)((char*)ws + (off)))
 #define CTXM(off) ((uint16_t*)((char*)ctx + (off)))
+
+// the recurrent tail's buffers in the specialised layouts (ws == null: a forward)
+static RnnBufs rnn_bufs(const CtxLayout& L, void* ctx, const WsLayout* Wp, void* ws) {
+    RnnBufs R;
+    R.p2 = CTXF(L.p2);
+    for (int l = 0; l < 2; ++l) { R.out[l] = CTXF(L.out[l]); R.gates[l] = CTXF(L.gates[l]); }
+    R.logits_s = CTXF(L.logits_s); R.strong_sv = CTXF(L.strong_sv); R.weak_sv = CTXF(L.weak_sv); R.den_sv = CTXF(L.den_sv);
+    if (ws == nullptr) return R;
+    const WsLayout& W = *Wp;
+    R.d_out = WSF(W.d_out); R.d_in = WSF(W.d_in); R.dp2 = WSF(W.dp2); R.heads_part = WSF(W.heads_part);
+    for (int l = 0; l < 2; ++l) { R.dgi[l] = WSF(W.dgi[l]); R.dgh[l] = WSF(W.dgh[l]); R.hprev[l] = WSF(W.hprev[l]); }
+    R.gemm_part = WSF(W.gemm_part); R.gemm_part_floats = gemm_part_floats(4, SED_GRU_SPLITK, 192, 129); R.splitk = SED_GRU_SPLITK;
+    R.zero = WSD(W.bwd_acc); R.n_zero = 2 * SED_GLUACC_N + 2 * 64 * 10;      // every fp64 accumulator of the conv-block backward
+    return R;
+}
 
 extern "C" int sed_crnn_forward(const sed_dims* d, const float* params, float* bn_running, int64_t* bn_tracked,
                                 const float* x, int train, int update_bn, const uint64_t* seed_dev, void* ctx,
@@ -320,10 +329,9 @@ extern "C" int sed_crnn_forward(const sed_dims* d, const float* params, float* b
     const ParamOff P = make_param_off(g, nullptr);
     if (g.generic) {
         SED_CHECK_ARG(!(train && g.p > 0.f) || seed_dev, "sed_crnn_forward: dropout enabled but seed_dev is null");
-        hipStream_t st0 = (hipStream_t)stream;
-        SideStream& sd0 = side_stream(st0);
+        side_stream((hipStream_t)stream);      // (first use creates the helper streams here, as ever: their ORDER matters, see SideStream)
         return gen_forward(g, P, params, bn_running, bn_tracked, x, train | (mom_ready ? 4 : 0), update_bn, seed_dev, ctx, ctx_bytes, strong,
-                           weak, st0, sd0.ok ? sd0.s : st0, sd0.fork, sd0.join);
+                           weak, (hipStream_t)stream);
     }
     const CtxLayout L = make_ctx_layout(g);
     if (ctx_bytes < L.total) {
@@ -362,23 +370,8 @@ extern "C" int sed_crnn_forward(const sed_dims* d, const float* params, float* b
                                     use_drop, g.p, seed_dev, use_drop ? CTXM(mo[i]) : nullptr, st));
         in = CTXF(po[i]);
     }
-    // ---- BiGRU ----------------------------------------------------------------------------------
-    SED_TRY(sed_fork_point(st));
-    int nin = 64;
-    for (int l = 0; l < g.L; ++l) {
-        // the input projection x W_ih^T + b_ih runs inside the recurrence kernel (gi only exists in LDS)
-        SED_TRY(launch_gru_fwd(in, nin, params + P.w_ih[l][0], params + P.w_ih[l][1], params + P.b_ih[l][0], params + P.b_ih[l][1],
-                               params + P.w_hh[l][0], params + P.w_hh[l][1], params + P.b_hh[l][0], params + P.b_hh[l][1],
-                               CTXF(L.out[l]), train ? CTXF(L.gates[l]) : nullptr, g.B, g.T3, st));
-        in = CTXF(L.out[l]);
-        nin = 128;
-    }
-    // ---- heads ----------------------------------------------------------------------------------
-    if (strong == nullptr) return SED_OK;                 // deferred (sed_mt_step_backward)
-    SED_TRY(launch_heads_fwd(in, params + P.dense_w, params + P.dense_b, params + P.soft_w, params + P.soft_b, strong, weak,
-                             train ? CTXF(L.strong_sv) : nullptr, train ? CTXF(L.weak_sv) : nullptr, CTXF(L.logits_s),
-                             CTXF(L.den_sv), g.B, g.T3, g.NC, use_drop, g.p, seed_dev, st));
-    return SED_OK;
+    // ---- BiGRU + heads --------------------------------------------------------------------------
+    return rnn_forward(g, P, params, rnn_bufs(L, ctx, nullptr, nullptr), train, seed_dev, strong, weak, 0, st);
 }
 
 // The train-mode BatchNorm statistics of conv block 0 come from the 9 + 45 first / second moments of the 3x3 input patch
@@ -416,11 +409,9 @@ static int crnn_backward_impl(const sed_dims* d, const float* params, const floa
     const ParamOff P = make_param_off(g, nullptr);
     if (g.generic) {
         SED_CHECK_ARG(!(g.p > 0.f) || seed_dev, "sed_crnn_backward: dropout enabled but seed_dev is null");
-        hipStream_t st0 = (hipStream_t)stream;
-        SideStream& sd0 = side_stream(st0);
-        // (SED_DEBUG_NO_SIDE_STREAM: every kernel on the caller's stream, for near-solo kernel times under rocprofv3)
-        return gen_backward(g, P, params, x, seed_dev, ctx, ctx_bytes, d_strong, d_weak, grads, ws, ws_bytes, parts, st0,
-                            (sd0.ok && !(g_sed_debug & SED_DEBUG_NO_SIDE_STREAM)) ? sd0.s : st0, sd0.fork, sd0.join, hl, ho);
+        SideFork side0 = side_fork((hipStream_t)stream);
+        return gen_backward(g, P, params, x, seed_dev, ctx, ctx_bytes, d_strong, d_weak, grads, ws, ws_bytes, parts, (hipStream_t)stream,
+                            side0, hl, ho);
     }
     const CtxLayout L = make_ctx_layout(g);
     const WsLayout W = make_ws_layout(g);
@@ -432,103 +423,10 @@ static int crnn_backward_impl(const sed_dims* d, const float* params, const floa
     SED_CHECK_ARG(!use_drop || seed_dev, "sed_crnn_backward: dropout enabled but seed_dev is null");
     hipStream_t st = (hipStream_t)stream;
     const int BT = g.B * g.T3;
-    SideStream& sd = side_stream(st);
-    hipStream_t ss = (sd.ok && !(g_sed_debug & SED_DEBUG_NO_SIDE_STREAM)) ? sd.s : st;       // without a side stream everything stays on the caller's
-    const bool defer_gru_w = (parts & 4) != 0;           // parts == 5: the caller runs them later (parts == 8)
-    bool forked = false;
-
-    // weight + bias gradients of a GRU layer, both directions (split-K MFMA GEMMs, low occupancy):
-    //   dW_ih[g][i] = sum_bt dgi[bt][g] input[bt][i],  db_ih[g] = sum_bt dgi[bt][g]
-    //   dW_hh[g][j] = sum_bt dgh[bt][g] hprev[bt][j],  db_hh[g] = sum_bt dgh[bt][g]
-    auto gru_weight_grads_layer = [&](int l, hipStream_t s2) -> int {
-        const int nin = (l == 0) ? 64 : 128;
-        const float* input = (l == 0) ? CTXF(L.p2) : CTXF(L.out[l - 1]);
-        GemmBatch gb;
-        gb.n_prob = 4; gb.splits = SED_GRU_SPLITK; gb.part = WSF(W.gemm_part); gb.part_floats = gemm_part_floats(4, SED_GRU_SPLITK, 192, 129); gb.part_stride = 0;
-        for (int dir = 0; dir < 2; ++dir) {
-            gb.p[2 * dir] = gemm_prob(WSF(W.dgi[l]) + dir * 192, 1, 384, input, nin, 1, grads + P.w_ih[l][dir], nin, 192, nin, BT);
-            gb.p[2 * dir].Cones = grads + P.b_ih[l][dir];
-            gb.p[2 * dir + 1] = gemm_prob(WSF(W.dgh[l]) + dir * 192, 1, 384, WSF(W.hprev[l]) + dir * 64, 128, 1,
-                                          grads + P.w_hh[l][dir], 64, 192, 64, BT);
-            gb.p[2 * dir + 1].Cones = grads + P.b_hh[l][dir];
-        }
-        return launch_gemm_batch(gb, s2);
-    };
-    auto gru_weight_grads = [&](hipStream_t s2) -> int {
-        for (int l = g.L - 1; l >= 0; --l) SED_TRY(gru_weight_grads_layer(l, s2));
-        return SED_OK;
-    };
-    // (Measured twice and rejected in round 2, then removed: each layer's weight-gradient GEMMs right behind that layer's
-    // recurrence kernel on the side stream - the upper layer's next to the lower layer's recurrence (48 workgroups on 256
-    // CUs) - instead of between the two conv weight-gradient kernels: 0.816 ms against 0.766 ms per step with the four-SIMD
-    // recurrence.  Every extra cross-stream edge of the captured graph becomes a completion signal between two hardware
-    // queues, and two of them on the recurrence chain cost more than the GEMMs' 40 us of otherwise idle GPU time give back.)
-
-    // ho != null: the forward left the output heads to this call (sed_mt_step_backward).  Fused form (hfuse.h): heads forward +
-    // loss + heads backward run as the prologue phase of the top layer's backward recurrence, the meters' clip sums, the
-    // step-state advance and the head weight gradients' column sum in k_heads_fin where the column sum alone used to be.
-    // Otherwise (SED_DEBUG_SEPARATE_HEADS, T / 8 > 128, gradient outputs asked for): k_heads_fwd here, then the two-kernel form.
-    const int head_cols = 2 * (g.NC * 128 + g.NC);
-    const bool fuse = ho && hl && (parts & 1) && heads_fusable(64, g.T3) && !(g_sed_debug & SED_DEBUG_SEPARATE_HEADS) && !hl->d_strong_out &&
-                      !hl->d_weak_out;
-    auto heads_colsum = [&](hipStream_t s2) -> int {
-        if (fuse) return launch_heads_fin(WSF(W.heads_part), grads + P.dense_w, g.B, g.T3, g.NC, head_cols, *hl, s2);
-        return launch_heads_colsum(WSF(W.heads_part), grads + P.dense_w, g.B, g.NC, s2);
-    };
-    const bool defer_colsum = ((parts & 2) && sd.ok) || defer_gru_w;
-    if (parts & 1) {
-    // ---- heads ----------------------------------------------------------------------------------
-    const float* h_last = CTXF(L.out[g.L - 1]);
-    if (ho && !fuse)
-        SED_TRY(launch_heads_fwd(h_last, params + P.dense_w, params + P.dense_b, params + P.soft_w, params + P.soft_b, ho->strong, ho->weak,
-                                 CTXF(L.strong_sv), CTXF(L.weak_sv), CTXF(L.logits_s), CTXF(L.den_sv), g.B, g.T3, g.NC, use_drop, g.p,
-                                 seed_dev, st));
-    if (!fuse)
-    SED_TRY(launch_heads_bwd(h_last, params + P.dense_w, params + P.soft_w, CTXF(L.strong_sv), CTXF(L.weak_sv),
-                             CTXF(L.logits_s), CTXF(L.den_sv), d_strong, d_weak, WSF(W.d_out), WSF(W.heads_part),
-                             grads + P.dense_w, grads + P.dense_b, grads + P.soft_w, grads + P.soft_b, g.B, g.T3, g.NC,
-                             use_drop, g.p, seed_dev, (parts & 2) ? WSD(W.bwd_acc) : nullptr, 2 * SED_GLUACC_N + 2 * 64 * 10,
-                             defer_colsum ? 1 : 0, hl, st));
-    // ---- BiGRU ----------------------------------------------------------------------------------
-    // The gradient w.r.t. each layer's input is produced INSIDE the recurrence kernel (two extra waves, one block of
-    // steps behind), as two direction planes [2][B*T'][nin] that the consumer adds while loading: the layer below's
-    // recurrence kernel, or k_glu_pool_bwd8 for layer 0 (planes in W.dp2).
-    const float* d_cur = WSF(W.d_out);
-    const float* d_cur2 = nullptr;
-    for (int l = g.L - 1; l >= 0; --l) {
-        const int nin = (l == 0) ? 64 : 128;
-        float* d_in = (l == 0) ? WSF(W.dp2) : WSF(W.d_in);
-        if (fuse && l == g.L - 1) {
-            HeadsFuse hf = {};
-            hf.wd = params + P.dense_w; hf.strong = ho->strong; hf.weak = ho->weak; hf.part = WSF(W.heads_part);
-            hf.NC = g.NC; hf.use_drop = use_drop; hf.p_drop = g.p; hf.seed = seed_dev;
-            hf.zero = (parts & 2) ? WSD(W.bwd_acc) : nullptr; hf.n_zero = (parts & 2) ? 2 * SED_GLUACC_N + 2 * 64 * 10 : 0;
-            hf.hl = *hl;
-            SED_TRY(launch_gru_bwd_heads(CTXF(L.out[l]), CTXF(L.gates[l]), params + P.w_hh[l][0], params + P.w_hh[l][1],
-                                         params + P.w_ih[l][0], params + P.w_ih[l][1], nin, WSF(W.dgi[l]), WSF(W.dgh[l]),
-                                         WSF(W.hprev[l]), d_in, g.B, g.T3, hf, st));
-            // the meters / step-state advance (+ column sum unless deferred to the side stream or a parts = 8 call)
-            if (!defer_colsum) SED_TRY(heads_colsum(st));
-            else if (defer_gru_w) SED_TRY(launch_heads_fin(WSF(W.heads_part), grads + P.dense_w, g.B, g.T3, g.NC, 0, *hl, st));
-        } else
-        SED_TRY(launch_gru_bwd(d_cur, d_cur2, CTXF(L.out[l]), CTXF(L.gates[l]), params + P.w_hh[l][0], params + P.w_hh[l][1],
-                               params + P.w_ih[l][0], params + P.w_ih[l][1], nin, WSF(W.dgi[l]), WSF(W.dgh[l]),
-                               WSF(W.hprev[l]), d_in, g.B, g.T3, st));
-        d_cur = d_in;
-        d_cur2 = d_in + (size_t)BT * nin;
-    }
-    }
-    // parts == 1 (data-parallel: the GRU + heads gradient bucket must be complete when this call returns so that
-    // its all-reduce can start): the GEMMs follow the dX chain on the caller's stream.  parts == 3: they are
-    // deferred to the side stream of the conv-block backward below, where they overlap k_glu_pool_bwd8.
-    if (parts == 1) SED_TRY(gru_weight_grads(st));
-    if (parts == 8) {
-        // the weight-gradient tail of a parts == 5 call: head column sum + every GRU dW / db, on the CALLER's stream (which
-        // a data-parallel host makes a second stream, so that this bucket and its all-reduce overlap the conv backward)
-        SED_TRY(launch_heads_colsum(WSF(W.heads_part), grads + P.dense_w, g.B, g.NC, st));
-        SED_TRY(gru_weight_grads(st));
-        return SED_OK;
-    }
+    SideFork side = side_fork(st);
+    // ---- heads, BiGRU (+ the weight-gradient tail of a parts == 1 / parts == 8 call) --------------
+    const RnnBwd rb = rnn_backward_plan(g, P, rnn_bufs(L, ctx, &W, ws), params, grads, seed_dev, hl, ho, parts, &side);
+    SED_TRY(rnn_backward(rb, d_strong, d_weak, st));
     if (!(parts & 2)) return SED_OK;
     // ---- conv blocks 2, 1 -----------------------------------------------------------------------
     const size_t wpkT[3] = {0, L.wpkT1, L.wpkT2}, yo[3] = {0, L.y1, L.y2}, bo[3] = {0, L.bn1, L.bn2};
@@ -540,8 +438,6 @@ static int crnn_backward_impl(const sed_dims* d, const float* params, const floa
     // Stream schedule (kernel timeline of one step, tools/timeline.py): the dgrad chain is the critical path.
     //   main: glu2_bwd  prep | dgrad2            | glu1_bwd  prep | dgrad1          | blk0_bwd  finalize |
     //   side:                | wgrad2  GRU dW/db |                | wgrad1  reduce                       | join
-    // (Forking right behind each recurrence kernel - the upper layer's GEMMs next to the lower layer's 48-workgroup
-    // recurrence - measured slower still, 1.043 ms: every event record splits the critical chain.)
     // (Forking before glu2_bwd so that the GRU GEMMs run first and wgrad1 starts on time measured slower, 1.061 vs
     // 1.029 ms: they then compete with the critical-path kernels glu2_bwd / dgrad2 / glu1_bwd.)
     // (Same experiment again with the Winograd convolutions, where the side stream has become the tail of the step: still
@@ -562,42 +458,21 @@ static int crnn_backward_impl(const sed_dims* d, const float* params, const floa
                                     WSF(dzo[i]), WSD(gacc[i]), 0, g.B, Hs[i], Wd[i], use_drop, g.p, CTXM(mo[i]),
                                     params + P.bn_g[i], WSF(W.coef[i]), grads + P.bn_g[i], grads + P.bn_b[i],
                                     grads + P.glu_w[i], grads + P.glu_b[i], grads + P.conv_b[i], fuse_prep ? &prep[i] : nullptr, st));
-        if (i == 2) {
-            // The fork event is recorded here, but the dgrad - the critical chain - is CAPTURED FIRST: the graph executor keeps the
-            // first-captured child of a node on its parent's hardware queue; with the helper stream's wgrad captured first the
-            // dgrad hopped to another queue and started 10 us after k_glu_pool_bwd8 had finished
-            // (profiles/r05b_mt-f32_step_timeline.txt: 447.6 -> 457.7 us).  Both still depend on the same event.
-            if (sd.ok) SED_CHECK_HIP(hipEventRecord(sd.fork, st));
-            SED_TRY(launch_conv_dgrad(WSF(dzo[i]), CTXF(yo[i]), WSF(W.coef[i]), CTXF(wpkT[i]), WSF(dpo[i - 1]), g.B, Hs[i], Wd[i], pp, st));
-            if (sd.ok) { SED_CHECK_HIP(hipStreamWaitEvent(sd.s, sd.fork, 0)); forked = true; }
-            SED_TRY(launch_conv_wgrad(WSF(dzo[i]), CTXF(yo[i]), WSF(W.coef[i]), CTXF(pin[i]), WSF(W.wg_part), W.wgrad_blocks,
-                                      grads + P.conv_w[i], g.B, Hs[i], Wd[i], pp, ss));
-            if (parts == 3) {
-                // the head weight-gradient column sum (deferred from part 1): behind wgrad2, long before the tail of the step
-                // (queued right in front of wgrad1 it sat 60 us behind the persistent dgrad kernel and held wgrad1 back; at
-                // the very end of the side stream it was 4 us on the step's tail)
-                // (Queued on the conv-wgrad helper they sit between wgrad2 and wgrad1 and hold wgrad1 - the tail of the step -
-                // back by ~80 us (r02_a step timeline: wgrad1 starts at 678 us, its inputs are ready at 594 us); a helper
-                // stream of their OWN measured SLOWER all the same in round 2 - 0.829 vs 0.815 ms (fp32), 0.775 vs 0.742 ms
-                // (bf16 operands): the step is throughput-bound, a third stream only takes CUs from the dgrad / block-0
-                // chain.  Removed.)
-                if (sd.ok) SED_TRY(heads_colsum(ss));
-                SED_TRY(gru_weight_grads(ss));
-            }
-        } else {
-            if (sd.ok) { SIDE_FORK(st); forked = true; }
-            SED_TRY(launch_conv_dgrad(WSF(dzo[i]), CTXF(yo[i]), WSF(W.coef[i]), CTXF(wpkT[i]), WSF(dpo[i - 1]), g.B, Hs[i], Wd[i], pp, st));
-            SED_TRY(launch_conv_wgrad(WSF(dzo[i]), CTXF(yo[i]), WSF(W.coef[i]), CTXF(pin[i]), WSF(W.wg_part), W.wgrad_blocks,
-                                      grads + P.conv_w[i], g.B, Hs[i], Wd[i], pp, ss));
-        }
+        // block 2: the dgrad - the critical chain - is captured between the two halves of the fork (SideFork); block 1: behind both
+        SED_TRY(side.mark(st));
+        if (i == 1) SED_TRY(side.start());
+        SED_TRY(launch_conv_dgrad(WSF(dzo[i]), CTXF(yo[i]), WSF(W.coef[i]), CTXF(wpkT[i]), WSF(dpo[i - 1]), g.B, Hs[i], Wd[i], pp, st));
+        if (i == 2) SED_TRY(side.start());
+        SED_TRY(launch_conv_wgrad(WSF(dzo[i]), CTXF(yo[i]), WSF(W.coef[i]), CTXF(pin[i]), WSF(W.wg_part), W.wgrad_blocks,
+                                  grads + P.conv_w[i], g.B, Hs[i], Wd[i], pp, side.s));
+        if (i == 2) SED_TRY(rnn_deferred_weight_grads(rb));      // parts == 3: head column sum + GRU dW / db behind wgrad2
     }
     // ---- conv block 0 ---------------------------------------------------------------------------
     SED_TRY(launch_blk0_backward(g, x, params + P.conv_w[0], params + P.conv_b[0], params + P.bn_g[0], params + P.bn_b[0],
                                  params + P.glu_w[0], CTXM(L.mask0), CTXD(L.mom0), CTXF(L.wz0), CTXF(L.wl0), CTXF(L.bn0),
                                  WSF(W.dp0), WSD(W.de0), 0, grads + P.conv_w[0], grads + P.conv_b[0], grads + P.bn_g[0],
                                  grads + P.bn_b[0], grads + P.glu_w[0], grads + P.glu_b[0], st));
-    if (forked) SIDE_JOIN(st);
-    return SED_OK;
+    return side.join(st);
 }
 
 extern "C" int sed_crnn_backward(const sed_dims* d, const float* params, const float* x, const uint64_t* seed_dev,
@@ -663,8 +538,6 @@ extern "C" int sed_kernel_replay(const char* name, const sed_dims* d, const floa
     auto is = [&](const char* n) { return strcmp(name, n) == 0; };
     if (is("x_moments")) return launch_x_moments(g, x, CTXD(L.mompart), nullptr, st);
     if (is("blk0_fwd")) {
-        const int tpc = (g.H1 + 3) / 4;
-        (void)tpc;
         return launch_blk0_forward(g, x, params + P.conv_w[0], params + P.conv_b[0], params + P.bn_g[0], params + P.bn_b[0],
                                    params + P.glu_w[0], params + P.glu_b[0], WSF(W.coef[1]), WSF(W.coef[1]) + 64, nullptr, 1, 0,
                                    seed_dev, CTXD(L.mom0), CTXD(L.mompart), CTXF(L.wz0), CTXF(L.wl0), CTXF(L.bn0), CTXF(L.p0),
@@ -712,7 +585,6 @@ extern "C" int sed_kernel_replay(const char* name, const sed_dims* d, const floa
                                     params + P.glu_w[0], CTXM(L.mask0), CTXD(L.mom0), CTXF(L.wz0), CTXF(L.wl0), CTXF(L.bn0), WSF(W.dp0),
                                     WSD(W.de0), 1, grads + P.conv_w[0], grads + P.conv_b[0], grads + P.bn_g[0], grads + P.bn_b[0],
                                     grads + P.glu_w[0], grads + P.glu_b[0], st);
-    (void)BT;
     sed_set_error("sed_kernel_replay: unknown kernel '%s'", name);
     return SED_ERR_BAD_ARG;
 }

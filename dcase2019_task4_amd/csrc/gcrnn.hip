@@ -3,13 +3,13 @@
 //
 // Operator sequence = CRNN.forward (baseline/models/CRNN.py:59-84) with nb_filters = [C, C, C], n_RNN_cell = H:
 //   block 0 (blk0.hip, templated on C; always fp32) -> [conv3x3 + BN sums (gconv.hip) -> BN / GLU / dropout / pool
-//   (gglu.hip)] x 2 -> BiGRU: input projection (ggemm.hip) + recurrence (grec.hip / ggru.hip for H = 256, gru4.hip for H = 64)
-//   -> heads (heads.hip, templated on 2 H).
+//   (gglu.hip)] x 2 -> BiGRU + heads (rnn.hip, shared with crnn.hip).
 #include <string.h>
 #include "common.h"
 #include "kernels.h"
 #include "gkernels.h"
 #include "gpack.h"
+#include "rnn.h"
 
 static inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline size_t esz(const Geo& g) { return g.mode == SED_DTYPE_BF16 ? 2 : 4; }
@@ -168,6 +168,27 @@ int gen_buffers_init(const Geo& g, void* ctx, size_t ctx_bytes, void* ws, size_t
 #define WSF(off) ((float*)((char*)ws + (off)))
 #define WSD(off) ((double*)((char*)ws + (off)))
 
+// the recurrent tail's buffers in the generic layouts (ws == null: a forward)
+static RnnBufs rnn_bufs(const Geo& g, const GCtx& L, void* ctx, const GWs* Wp, void* ws) {
+    RnnBufs R;
+    R.p2 = CTXF(L.p[2]);
+    R.logits_s = CTXF(L.logits_s); R.strong_sv = CTXF(L.strong_sv); R.weak_sv = CTXF(L.weak_sv); R.den_sv = CTXF(L.den_sv);
+    R.err = (int*)CTXV(L.err);
+    for (int l = 0; l < 2; ++l) {
+        R.out[l] = CTXF(L.out[l]); R.gates[l] = CTXF(L.gates[l]);
+        R.gi[l] = CTXF(L.gi[l]); R.wihT[l] = CTXF(L.wihT[l]); R.whh[l] = CTXV(L.whh[l]); R.whhT[l] = CTXV(L.whhT[l]);
+        R.xch[l] = ws ? (void*)((char*)ws + Wp->xch[l]) : CTXV(L.xch[l]);
+        R.epoch[l] = (unsigned int*)(ws ? (void*)((char*)ws + Wp->epoch[l]) : CTXV(L.epoch[l]));
+    }
+    if (ws == nullptr) return R;
+    const GWs& W = *Wp;
+    R.d_out = WSF(W.d_out); R.d_in = WSF(W.d_in); R.dp2 = WSF(W.dp[2]); R.heads_part = WSF(W.heads_part);
+    for (int l = 0; l < 2; ++l) { R.dgi[l] = WSF(W.dgi[l]); R.dgh[l] = WSF(W.dgh[l]); R.hprev[l] = WSF(W.hprev[l]); }
+    R.gemm_part = WSF(W.gemm_part); R.gemm_part_floats = R.gemm_part_stride = gru_gemm_part_floats(g); R.splitk = gru_splitk(g);
+    R.zero = WSD(W.de0); R.n_zero = 2 * g.C * 10;
+    return R;
+}
+
 int gen_mompart(const Geo& g, void* ctx, size_t ctx_bytes, double** out) {
     const GCtx L = make_gctx(g);
     if (ctx_bytes < L.total) {
@@ -180,7 +201,7 @@ int gen_mompart(const Geo& g, void* ctx, size_t ctx_bytes, double** out) {
 
 int gen_forward(const Geo& g, const ParamOff& P, const float* params, float* bn_running, int64_t* bn_tracked, const float* x,
                 int train, int update_bn, const uint64_t* seed_dev, void* ctx, size_t ctx_bytes, float* strong, float* weak,
-                hipStream_t st, hipStream_t ss, hipEvent_t ev_fork, hipEvent_t ev_join) {
+                hipStream_t st) {
     const int mom_ready = (train & 4) ? 1 : 0;      // (sed_crnn_forward's train bit 2)
     train &= 3;
     const GCtx L = make_gctx(g);
@@ -210,13 +231,10 @@ int gen_forward(const Geo& g, const ParamOff& P, const float* params, float* bn_
     pk.wgT1 = train ? CTXV(L.wgT[1]) : nullptr; pk.wgT2 = train ? CTXV(L.wgT[2]) : nullptr;
     pk.bg1 = CTXF(L.bg[1]); pk.bg2 = CTXF(L.bg[2]);
     pk.zero = CTXD(L.stat1); pk.n_zero = train ? 4 * C : 0;
-    pk.err = nullptr;                         // sticky: never cleared by a forward (sed_crnn_buffers_init does)
     pk.f16 = g.f16 ? 1 : 0;
     // (The packing is independent of block 0, but forking it onto the helper stream is not an option: a forward that
     // itself runs on a forked stream - the teacher's, next to the student's - would fork a second time inside the same
     // hipGraph capture, and ROCm 7.0's hipStreamEndCapture segfaults on that nested fork.  It stays on the caller's stream.)
-    (void)ev_fork; (void)ev_join;
-    ss = st;
     // Training forwards: the packing and the W_ih transposes ride in spare workgroups of block 0's moments launch (gpack.h).
     // Eval forwards have no moments launch and need no transposes.
     const bool aux_pack = train != 0;
@@ -237,11 +255,8 @@ int gen_forward(const Geo& g, const ParamOff& P, const float* params, float* bn_
                 aux.n_grec = l + 1;
             }
     } else {
-        SED_TRY(launch_gen_pack(pk, g.mode, ss));
+        SED_TRY(launch_gen_pack(pk, g.mode, st));
     }
-    // H = 256: the cluster recurrence (ggru.hip); SED_DTYPE_BF16 runs one workgroup per chain with W_hh as bf16 in registers
-    // instead (grec.hip)
-    const bool rec16 = H == 256 && g.mode == SED_DTYPE_BF16;
 
     // ---- conv block 0 -------------------------------------------------------------------------------------------------
     SED_TRY(launch_blk0_forward(g, x, params + P.conv_w[0], params + P.conv_b[0], params + P.bn_g[0], params + P.bn_b[0],
@@ -291,48 +306,14 @@ int gen_forward(const Geo& g, const ParamOff& P, const float* params, float* bn_
         SED_TRY(launch_gglu_fwd(gm, C, CTXV(L.y[i]), bn, CTXV(L.wg[i]), CTXF(L.bg[i]), CTXV(L.p[i]), 0, g.B, Hs[i], Wd[i], i,
                                 use_drop, g.p, seed_dev, use_drop ? CTXM(L.mask[i]) : nullptr, st));
     }
-    // ---- BiGRU ----------------------------------------------------------------------------------------------------------
-    SED_TRY(sed_fork_point(st));
-    const float* in = CTXF(L.p[2]);
-    int nin = C;
-    const int BT = g.B * g.T3;
-    for (int l = 0; l < g.L; ++l) {
-        if (H == 64) {
-            SED_TRY(launch_gru_fwd(in, nin, params + P.w_ih[l][0], params + P.w_ih[l][1], params + P.b_ih[l][0], params + P.b_ih[l][1],
-                                   params + P.w_hh[l][0], params + P.w_hh[l][1], params + P.b_hh[l][0], params + P.b_hh[l][1],
-                                   CTXF(L.out[l]), train ? CTXF(L.gates[l]) : nullptr, g.B, g.T3, st));
-        } else {
-            // gi[bt][dir][3H] = x W_ih[dir]^T + b_ih[dir]: both directions in one launch (ggemm.hip)
-            GntBatch gb;
-            gb.n_prob = 2;
-            for (int dir = 0; dir < 2; ++dir)
-                gb.p[dir] = GntProb{in, nin, params + P.w_ih[l][dir], nin, CTXF(L.gi[l]) + dir * 3 * H, 6 * H, params + P.b_ih[l][dir], BT, 3 * H, nin};
-            SED_TRY(g.mode != SED_DTYPE_F32 ? launch_gnt_gemm_bf16(gb, st, g.f16 ? 2 : (g.mode == SED_DTYPE_BF16X3 ? 1 : 0)) : launch_gnt_gemm(gb, st));
-            if (rec16) {
-                if (!(aux_pack && l < aux.n_grec))
-                    SED_TRY(launch_grec_pack(params + P.w_hh[l][0], params + P.w_hh[l][1], CTXV(L.whh[l]), train ? CTXV(L.whhT[l]) : nullptr, st, g.f16 ? 1 : 0));
-                SED_TRY(launch_grec_fwd(CTXF(L.gi[l]), CTXV(L.whh[l]), params + P.b_hh[l][0], params + P.b_hh[l][1], CTXF(L.out[l]),
-                                        train ? CTXF(L.gates[l]) : nullptr, g.B, g.T3, st, g.f16 ? 1 : 0));
-            } else
-                SED_TRY(launch_gclu_fwd(CTXF(L.gi[l]), params + P.w_hh[l][0], params + P.w_hh[l][1], params + P.b_hh[l][0],
-                                        params + P.b_hh[l][1], CTXF(L.out[l]), train ? CTXF(L.gates[l]) : nullptr, CTXV(L.xch[l]),
-                                        (unsigned int*)CTXV(L.epoch[l]), (int*)CTXV(L.err), g.B, g.T3, st));
-        }
-        in = CTXF(L.out[l]);
-        nin = 2 * H;
-    }
-    // ---- heads ----------------------------------------------------------------------------------------------------------
-    if (strong == nullptr) return SED_OK;                 // deferred to sed_mt_step_backward (crnn.hip)
-    SED_TRY(launch_heads_fwd(in, params + P.dense_w, params + P.dense_b, params + P.soft_w, params + P.soft_b, strong, weak,
-                             train ? CTXF(L.strong_sv) : nullptr, train ? CTXF(L.weak_sv) : nullptr, CTXF(L.logits_s),
-                             CTXF(L.den_sv), g.B, g.T3, g.NC, use_drop, g.p, seed_dev, st, 2 * H));
-    return SED_OK;
+    // ---- BiGRU + heads ---------------------------------------------------------------------------------------------------
+    return rnn_forward(g, P, params, rnn_bufs(g, L, ctx, nullptr, nullptr), train, seed_dev, strong, weak, aux.n_grec, st);
 }
 
-// Backward.  `side`: the helper stream of the caller's stream (fork / join events owned by crnn.hip), or the caller's own.
+// Backward.  `side`: the helper stream of the caller's stream (owned by crnn.hip), or the caller's own.
 int gen_backward(const Geo& g, const ParamOff& P, const float* params, const float* x, const uint64_t* seed_dev, void* ctx,
                  size_t ctx_bytes, const float* d_strong, const float* d_weak, float* grads, void* ws, size_t ws_bytes, int parts,
-                 hipStream_t st, hipStream_t ss, hipEvent_t ev_fork, hipEvent_t ev_join, const HeadsLoss* hl, const HeadsOut* ho) {
+                 hipStream_t st, SideFork& side, const HeadsLoss* hl, const HeadsOut* ho) {
     const GCtx L = make_gctx(g);
     const GWs W = make_gws(g);
     if (ctx_bytes < L.total || ws_bytes < W.total) {
@@ -342,120 +323,9 @@ int gen_backward(const Geo& g, const ParamOff& P, const float* params, const flo
     const int C = g.C, H = g.H, BT = g.B * g.T3;
     const int gm = (g.mode == SED_DTYPE_BF16X3) ? SED_DTYPE_F32 : g.mode;
     const int use_drop = (g.p > 0.f) ? 1 : 0;
-    const bool have_side = (ss != st);
-    const bool defer_gru_w = (parts & 4) != 0;
-    // H = 256: each GRU layer's weight-gradient GEMMs start on the helper stream right behind its recurrence (below).
-    // (H = 64, measured and removed: NEUTRAL to slightly negative - 0.602 against 0.592 ms for the base bf16 step: the conv-block
-    // backward is throughput-bound, the GEMMs only trade places with the weight-gradient kernels and slow the latency-bound
-    // recurrence; re-measured with the round-3 kernels: 0.580 against 0.569 ms - the GEMMs stretch the lower layer's recurrence
-    // from 40 to 52 us.  The late schedule at H = 256, the GEMMs after the conv blocks' fork, was removed as well.)
-    const bool early_gru_w = parts == 3 && have_side && H != 64;
-    bool forked = false;
-    // weight + bias gradients of one GRU layer, both directions (split-K MFMA GEMMs)
-    auto gru_weight_grads_layer = [&](int l, hipStream_t s2) -> int {
-        const int nin = (l == 0) ? C : 2 * H;
-        const float* input = (l == 0) ? CTXF(L.p[2]) : CTXF(L.out[l - 1]);
-        GemmBatch gb;
-        gb.n_prob = 4; gb.splits = gru_splitk(g); gb.part = WSF(W.gemm_part) + (size_t)l * gru_gemm_part_floats(g);
-        gb.part_floats = gru_gemm_part_floats(g); gb.part_stride = 0;
-        gb.bf16 = g.mode == SED_DTYPE_BF16 ? 1 : (g.mode == SED_DTYPE_BF16X3 ? 2 : 0);     // GRU weight gradients: operand mode of the MFMA
-        for (int dir = 0; dir < 2; ++dir) {
-            gb.p[2 * dir] = gemm_prob(WSF(W.dgi[l]) + dir * 3 * H, 1, 6 * H, input, nin, 1, grads + P.w_ih[l][dir], nin, 3 * H, nin, BT);
-            gb.p[2 * dir].Cones = grads + P.b_ih[l][dir];
-            gb.p[2 * dir + 1] = gemm_prob(WSF(W.dgh[l]) + dir * 3 * H, 1, 6 * H, WSF(W.hprev[l]) + dir * H, 2 * H, 1,
-                                          grads + P.w_hh[l][dir], H, 3 * H, H, BT);
-            gb.p[2 * dir + 1].Cones = grads + P.b_hh[l][dir];
-        }
-        return launch_gemm_batch(gb, s2);
-    };
-    auto gru_weight_grads = [&](hipStream_t s2) -> int {
-        for (int l = g.L - 1; l >= 0; --l) SED_TRY(gru_weight_grads_layer(l, s2));
-        return SED_OK;
-    };
-    // ho != null: heads deferred by the forward (sed_mt_step_backward, crnn.hip).  H = 64: fused into the top layer's backward
-    // recurrence (hfuse.h); H = 256 (or SED_DEBUG_SEPARATE_HEADS): k_heads_fwd here, then the two-kernel form.
-    const int head_cols = 2 * (g.NC * 2 * H + g.NC);
-    const bool fuse = ho && hl && (parts & 1) && heads_fusable(H, g.T3) && !(g_sed_debug & SED_DEBUG_SEPARATE_HEADS) && !hl->d_strong_out &&
-                      !hl->d_weak_out;
-    auto heads_colsum = [&](hipStream_t s2) -> int {
-        if (fuse) return launch_heads_fin(WSF(W.heads_part), grads + P.dense_w, g.B, g.T3, g.NC, head_cols, *hl, s2);
-        return launch_heads_colsum(WSF(W.heads_part), grads + P.dense_w, g.B * heads_bwd_chunks(2 * H, g.T3), g.NC, s2, 2 * H);
-    };
-    const bool defer_colsum = ((parts & 2) && have_side) || defer_gru_w;
-    if (parts & 1) {
-        // ---- heads ------------------------------------------------------------------------------------------------------
-        if (ho && !fuse)
-            SED_TRY(launch_heads_fwd(CTXF(L.out[g.L - 1]), params + P.dense_w, params + P.dense_b, params + P.soft_w, params + P.soft_b,
-                                     ho->strong, ho->weak, CTXF(L.strong_sv), CTXF(L.weak_sv), CTXF(L.logits_s), CTXF(L.den_sv), g.B, g.T3,
-                                     g.NC, use_drop, g.p, seed_dev, st, 2 * H));
-        if (!fuse)
-        SED_TRY(launch_heads_bwd(CTXF(L.out[g.L - 1]), params + P.dense_w, params + P.soft_w, CTXF(L.strong_sv), CTXF(L.weak_sv),
-                                 CTXF(L.logits_s), CTXF(L.den_sv), d_strong, d_weak, WSF(W.d_out), WSF(W.heads_part),
-                                 grads + P.dense_w, grads + P.dense_b, grads + P.soft_w, grads + P.soft_b, g.B, g.T3, g.NC, use_drop,
-                                 g.p, seed_dev, (parts & 2) ? WSD(W.de0) : nullptr, 2 * C * 10,
-                                 defer_colsum ? 1 : 0, hl, st, 2 * H));
-        // ---- BiGRU --------------------------------------------------------------------------------------------------------
-        const float* d_cur = WSF(W.d_out);
-        const float* d_cur2 = nullptr;
-        for (int l = g.L - 1; l >= 0; --l) {
-            const int nin = (l == 0) ? C : 2 * H;
-            float* d_in = (l == 0) ? WSF(W.dp[2]) : WSF(W.d_in);
-            if (H == 64) {
-                if (fuse && l == g.L - 1) {
-                    HeadsFuse hf = {};
-                    hf.wd = params + P.dense_w; hf.strong = ho->strong; hf.weak = ho->weak; hf.part = WSF(W.heads_part);
-                    hf.NC = g.NC; hf.use_drop = use_drop; hf.p_drop = g.p; hf.seed = seed_dev;
-                    hf.zero = (parts & 2) ? WSD(W.de0) : nullptr; hf.n_zero = (parts & 2) ? 2 * C * 10 : 0;
-                    hf.hl = *hl;
-                    SED_TRY(launch_gru_bwd_heads(CTXF(L.out[l]), CTXF(L.gates[l]), params + P.w_hh[l][0], params + P.w_hh[l][1],
-                                                 params + P.w_ih[l][0], params + P.w_ih[l][1], nin, WSF(W.dgi[l]), WSF(W.dgh[l]),
-                                                 WSF(W.hprev[l]), d_in, g.B, g.T3, hf, st));
-                    if (!defer_colsum) SED_TRY(heads_colsum(st));
-                    else if (defer_gru_w) SED_TRY(launch_heads_fin(WSF(W.heads_part), grads + P.dense_w, g.B, g.T3, g.NC, 0, *hl, st));
-                } else
-                SED_TRY(launch_gru_bwd(d_cur, d_cur2, CTXF(L.out[l]), CTXF(L.gates[l]), params + P.w_hh[l][0], params + P.w_hh[l][1],
-                                       params + P.w_ih[l][0], params + P.w_ih[l][1], nin, WSF(W.dgi[l]), WSF(W.dgh[l]), WSF(W.hprev[l]),
-                                       d_in, g.B, g.T3, st));
-                d_cur = d_in;
-                d_cur2 = d_in + (size_t)BT * nin;
-            } else {
-                if (g.mode == SED_DTYPE_BF16)
-                    SED_TRY(launch_grec_bwd(d_cur, CTXF(L.out[l]), CTXF(L.gates[l]), CTXV(L.whhT[l]), WSF(W.dgi[l]), WSF(W.dgh[l]),
-                                            WSF(W.hprev[l]), g.B, g.T3, st));
-                else
-                    SED_TRY(launch_gclu_bwd(d_cur, CTXF(L.out[l]), CTXF(L.gates[l]), params + P.w_hh[l][0], params + P.w_hh[l][1],
-                                            WSF(W.dgi[l]), WSF(W.dgh[l]), WSF(W.hprev[l]), (void*)((char*)ws + W.xch[l]),
-                                            (unsigned int*)((char*)ws + W.epoch[l]), (int*)CTXV(L.err), g.B, g.T3, st));
-                // dX[bt][i] = sum_dir sum_g dgi[bt][dir][g] W_ih[dir][g][i]: K = 6H, the two W_ih stacked along K (transposed
-                // copy made by the forward)
-                // H = 256: this layer's weight-gradient GEMMs (100 - 160 us of split-K work) start on the helper stream NOW, next
-                // to the rest of the recurrence chain - which keeps 48 of 256 CUs busy for another ~300 us - instead of after
-                // the conv blocks' fork, where they used to be the tail of the step (profiles/r03_*_wide-bf16_step_timeline.txt)
-                // The fork event is recorded in front of the dX GEMM, but the GEMM - the critical chain - is CAPTURED FIRST: the
-                // graph executor keeps the first-captured child of a node on its parent's hardware queue, and with the helper
-                // stream's kernels captured first the dX GEMM hopped to another queue, ~10 us of cross-queue latency per layer
-                // (profiles/r05b_wide-bf16_step_timeline.txt: "idle 9.9" in front of it).  Both still start together.
-                if (early_gru_w && have_side) SED_CHECK_HIP(hipEventRecord(ev_fork, st));
-                GntBatch gb;
-                gb.n_prob = 1;
-                gb.p[0] = GntProb{WSF(W.dgi[l]), 6 * H, CTXF(L.wihT[l]), 6 * H, d_in, nin, nullptr, BT, nin, 6 * H};
-                SED_TRY(g.mode != SED_DTYPE_F32 ? launch_gnt_gemm_bf16(gb, st, g.mode == SED_DTYPE_BF16X3) : launch_gnt_gemm(gb, st));
-                if (early_gru_w) {
-                    if (have_side) { SED_CHECK_HIP(hipStreamWaitEvent(ss, ev_fork, 0)); forked = true; }
-                    if (l == g.L - 1) SED_TRY(heads_colsum(ss));
-                    SED_TRY(gru_weight_grads_layer(l, ss));
-                }
-                d_cur = d_in;
-                d_cur2 = nullptr;
-            }
-        }
-    }
-    if (parts == 1) SED_TRY(gru_weight_grads(st));
-    if (parts == 8) {
-        SED_TRY(launch_heads_colsum(WSF(W.heads_part), grads + P.dense_w, g.B * heads_bwd_chunks(2 * H, g.T3), g.NC, st, 2 * H));
-        SED_TRY(gru_weight_grads(st));
-        return SED_OK;
-    }
+    // ---- heads, BiGRU (+ the weight-gradient tail of a parts == 1 / parts == 8 call) ------------------------------------------
+    const RnnBwd rb = rnn_backward_plan(g, P, rnn_bufs(g, L, ctx, &W, ws), params, grads, seed_dev, hl, ho, parts, &side);
+    SED_TRY(rnn_backward(rb, d_strong, d_weak, st));
     if (!(parts & 2)) return SED_OK;
     // ---- conv blocks 2, 1 -------------------------------------------------------------------------------------------------
     if (!(parts & 1)) SED_CHECK_HIP(hipMemsetAsync(WSD(W.de0), 0, 2 * C * 10 * sizeof(double), st));
@@ -477,34 +347,25 @@ int gen_backward(const Geo& g, const ParamOff& P, const float* params, const flo
         pa.g_gamma = grads + P.bn_g[i]; pa.g_beta = grads + P.bn_b[i]; pa.g_wglu = grads + P.glu_w[i]; pa.g_bglu = grads + P.glu_b[i];
         pa.g_convb = grads + P.conv_b[i];
         SED_TRY(launch_gbn_bwd_prep(pa, st));
-        // The weight gradient (helper stream) and the data gradient (caller's stream) both depend on the coefficients only.
-        // The data gradient is on the critical path: it is CAPTURED FIRST - a replayed hipGraph serialises nodes that its
-        // executor maps to the same hardware queue in creation order, and with the weight gradient created first the 145 us
-        // wgrad kernel sat in front of dgrad1 + block 0 on one queue (profiles/r03_a_wide-bf16_step_timeline.txt)
-        if (have_side) SED_CHECK_HIP(hipEventRecord(ev_fork, st));
+        // The weight gradient (helper stream) and the data gradient (caller's stream) both depend on the coefficients only; the
+        // data gradient - the critical chain - is captured between the two halves of the fork (SideFork)
+        SED_TRY(side.mark(st));
         if (g.mode != SED_DTYPE_F32)
             SED_TRY(launch_bconv_dgrad(g.mode == SED_DTYPE_BF16X3, C, WSF(W.dz[i]), CTXV(L.y[i]), WSF(W.coef[i]), CTXV(L.wpkT[i]),
                                        WSF(W.dp[i - 1]), g.B, Hs[i], Wd[i], st));
         else
             SED_TRY(launch_gconv_dgrad(g.mode, C, WSF(W.dz[i]), CTXF(L.y[i]), WSF(W.coef[i]), CTXV(L.wpkT[i]), WSF(W.dp[i - 1]), g.B, Hs[i],
                                        Wd[i], st));
-        if (have_side) { SED_CHECK_HIP(hipStreamWaitEvent(ss, ev_fork, 0)); forked = true; }
+        SED_TRY(side.start());
         SED_TRY(launch_gwgrad(g.mode, C, WSF(W.dz[i]), CTXF(L.y[i]), WSF(W.coef[i]), CTXF(L.p[i - 1]), WSF(W.wg_part), grads + P.conv_w[i], g.B,
-                              Hs[i], Wd[i], ss));
-        if (i == 2 && parts == 3 && !early_gru_w) {
-            if (have_side) SED_TRY(heads_colsum(ss));
-            SED_TRY(gru_weight_grads(ss));
-        }
+                              Hs[i], Wd[i], side.s));
+        if (i == 2) SED_TRY(rnn_deferred_weight_grads(rb));      // parts == 3, H = 64: head column sum + GRU dW / db behind wgrad2
     }
     // ---- conv block 0 -----------------------------------------------------------------------------------------------------
     SED_TRY(launch_blk0_backward(g, x, params + P.conv_w[0], params + P.conv_b[0], params + P.bn_g[0], params + P.bn_b[0],
                                  params + P.glu_w[0], CTXM(L.mask[0]), CTXD(L.mom0), CTXF(L.wz0), CTXF(L.wl0), CTXF(L.bn0), WSF(W.dp[0]),
                                  WSD(W.de0), 0, grads + P.conv_w[0], grads + P.conv_b[0], grads + P.bn_g[0], grads + P.bn_b[0],
                                  grads + P.glu_w[0], grads + P.glu_b[0], st, blk0_saves_gates(g) ? CTXV(L.sg0) : nullptr));
-    if (forked) {
-        SED_CHECK_HIP(hipEventRecord(ev_join, ss));
-        SED_CHECK_HIP(hipStreamWaitEvent(st, ev_join, 0));
-    }
-    return SED_OK;
+    return side.join(st);
 }
 

@@ -11,7 +11,8 @@ struct GenPackArgs {
     void *wg1, *wg2, *wgT1, *wgT2;              // GLU weights folded with gamma [co][c]; transposed raw [c][co] (may be null)
     float *bg1, *bg2;                           // GLU bias folded with beta [C]
     double* zero; int n_zero;                   // fp64 accumulators to clear
-    int* err;                                   // unused (the spin-timeout counter is sticky: cleared by sed_crnn_buffers_init only)
+    void* pad0;                                 // never read (once `err`): kept because this struct is a kernel argument, and the
+                                                // SGPR counts of k_gen_pack<1> and k_blk0_prep_aux move with its layout
     int f16;                                    // SED_DTYPE_F16 (mode 1 family): the FORWARD panels wpk1 / wpk2 as fp16; everything else bf16
 };
 int launch_gen_pack(const GenPackArgs& a, int mode, hipStream_t st);
@@ -99,6 +100,7 @@ int launch_gnt_gemm_bf16(const GntBatch& gb, hipStream_t st, int x3 = 0);
 
 // gcrnn.hip ---------------------------------------------------------------------------------------------------------------
 struct HeadsLoss;
+struct SideFork;                                // rnn.h: the backward's helper stream
 size_t gen_ctx_bytes(const Geo& g);
 size_t gen_ws_bytes(const Geo& g);
 int gen_buffers_init(const Geo& g, void* ctx, size_t ctx_bytes, void* ws, size_t ws_bytes, hipStream_t st);
@@ -106,7 +108,7 @@ int gen_ctx_view(const Geo& g, const char* name, size_t* offset, size_t* bytes);
 int gen_mompart(const Geo& g, void* ctx, size_t ctx_bytes, double** out);      // where the patch-moment partials live in a generic ctx
 int gen_forward(const Geo& g, const ParamOff& P, const float* params, float* bn_running, int64_t* bn_tracked, const float* x,
                 int train, int update_bn, const uint64_t* seed_dev, void* ctx, size_t ctx_bytes, float* strong, float* weak,
-                hipStream_t st, hipStream_t ss, hipEvent_t ev_fork, hipEvent_t ev_join);
+                hipStream_t st);
 int gen_backward(const Geo& g, const ParamOff& P, const float* params, const float* x, const uint64_t* seed_dev, void* ctx,
                  size_t ctx_bytes, const float* d_strong, const float* d_weak, float* grads, void* ws, size_t ws_bytes, int parts,
-                 hipStream_t st, hipStream_t ss, hipEvent_t ev_fork, hipEvent_t ev_join, const HeadsLoss* hl, const HeadsOut* ho);
+                 hipStream_t st, SideFork& side, const HeadsLoss* hl, const HeadsOut* ho);
