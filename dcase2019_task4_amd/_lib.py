@@ -55,6 +55,8 @@ _SIGS = {
                                   C.c_void_p, C.c_int, C.c_void_p]),
     "sed_event_counts": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P,
                                    C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P]),
+    "sed_psds_counts": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P,
+                                  C.c_double, C.c_double, C.c_double, _P, _P, _P, _P]),
     "sed_weak_counts": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
     "sed_version": (C.c_int, []),
     "sed_param_count": (C.c_int, [C.POINTER(SedDims)]),

@@ -1,5 +1,5 @@
 // post.h - the per-column decode of a strong posterior, shared by k_postprocess (post.hip: event lists out) and
-// k_event_counts (score.hip: events stay in LDS and are scored there).  One wave owns one (clip, class) column.
+// k_event_counts / k_psds_counts (score.hip: events stay in LDS and are scored there).  One wave owns one (clip, class) column.
 #pragma once
 #include "common.h"
 

@@ -26,6 +26,27 @@ Definitions (per file and class; label equality is the column):
 Limits: at most 64 reference and 64 estimated events per (file, class) - a column beyond that raises, it is never
 truncated -, ``T <= 2048`` output frames, at most 16 classes.  The overall error rate *with substitutions* needs a second,
 label-agnostic matching and is **not provided**: ``results_overall_metrics()['error_rate']`` holds NaN.
+
+PSDS (polyphonic sound detection score, Bilen et al., ICASSP 2020): ``sed_psds_counts`` scores the same (operating point,
+clip) grid with the three intersection criteria and returns integer class totals (``psds_counts``, ``PSDSCounts``); the
+PSD-ROC and its area are host arithmetic on those totals (``PSDS``), which also works without a GPU.  ``psds_eval`` is
+third-party and absent from this image and from the reference tree, so the definitions are restated from the paper and,
+where the package's behaviour was uncertain, decided here - **parity with ``psds_eval`` itself is unpinned**; pinned is
+exact agreement of the counts with an independent numpy statement (``tests/psds_np.py``).
+
+* ``I(d, g) = max(0, min(d.off, g.off) - max(d.on, g.on))``, ``len(e) = e.off - e.on``; every sum is a sequential fp64 sum
+  over the other side's events in stored order (references: sorted by onset, then offset), every test is
+  ``sum / len >= threshold``; an event with ``len <= 0`` or a NaN ratio fails every test.
+* DTC: detection ``d`` of class ``c`` is relevant iff ``sum_{g in G_c} I(d, g) / len(d) >= dtc``; ``FP[c]`` counts the
+  detections that are not relevant (cross-triggers included).
+* GTC: ground truth ``g`` is a true positive iff ``sum_{relevant d in D_c} I(d, g) / len(g) >= gtc``.
+* CTTC: a non-relevant detection ``d`` of class ``c`` adds 1 to ``CT[c][k]``, ``k != c``, iff
+  ``sum_{g in G_k} I(d, g) / len(d) >= cttc``.
+* With ``u = 3600`` (rates per hour): ``TPR = TP / n_gt``, ``FPR = u FP / T_data``, ``CTR[c][k] = u CT[c][k] / T_gt[k]`` (0
+  where ``T_gt[k] == 0``), ``eFPR[c] = FPR[c] + alpha_ct * mean_{k != c} CTR[c][k]``; per class the curve is the running
+  maximum of TPR over the points sorted by eFPR (0 below the first); on the union of all eFPR values ``<= e_max`` the
+  effective TPR is ``max(0, mean_c - alpha_st * std_c)`` (population std) and PSDS is the area of that left-continuous
+  staircase up to ``e_max``, over ``e_max``.
 """
 import logging
 
@@ -86,6 +107,9 @@ class RefEvents:
             raise ValueError("malformed CSR arrays")
         self.device = torch.device(device)
         self.max_per_column = int(np.diff(ptr).max()) if len(ptr) > 1 else 0
+        # host copies of the CSR arrays (PSDS.from_counts reads the per-class reference counts and durations from them)
+        self.ptr_host = ptr.copy()
+        self.onset_host, self.offset_host = np.array(onset, np.float64), np.array(offset, np.float64)
         self.ptr = torch.as_tensor(ptr).to(self.device)
         # one trailing element: an empty event list still has an address the library accepts
         self.onset = torch.as_tensor(np.r_[np.asarray(onset, np.float64), 0.0]).to(self.device)
@@ -201,6 +225,88 @@ def event_counts_from_events(est, ref, t_collar=0.200, percentage_of_length=0.2,
         float(time_resolution), _lib.ptr(counts.ev_columns) if per_column else None,
         _lib.ptr(counts.seg_columns) if per_column else None, _lib.ptr(counts.ev), _lib.ptr(counts.seg), _lib.ptr(counts.err),
         _lib.stream_ptr()), "sed_event_counts")
+    return counts
+
+
+class PSDSCounts:
+    """Class totals of one or more ``psds_counts`` calls, on the device: ``totals [K, nclass, 2 + nclass]`` int64 - per class
+    (TP, FP, CT[.][0 .. nclass - 1]) - and the error word, in ONE buffer so that ``host()`` is one copy.  ``columns
+    [K, N, nclass, 2 + nclass]`` int32 holds the last call's per-column counts when it was asked for them.  The criteria
+    ``dtc / gtc / cttc`` belong to the totals: every call that accumulates into them uses these."""
+
+    def __init__(self, n_points, nclass, device, dtc=0.5, gtc=0.5, cttc=0.3):
+        for name, v in (("dtc", dtc), ("gtc", gtc), ("cttc", cttc)):
+            if not 0.0 <= v <= 1.0:                     # (NaN fails too)
+                raise ValueError(f"{name} must be in [0, 1], got {v}")
+        self.K, self.NC = n_points, nclass
+        self.dtc, self.gtc, self.cttc = float(dtc), float(gtc), float(cttc)
+        self.buf = torch.zeros(n_points * nclass * (2 + nclass) + 1, dtype=torch.int64, device=device)
+        self.totals = self.buf[:-1].view(n_points, nclass, 2 + nclass)
+        self.err = self.buf[-1:].view(torch.int32)
+        self.columns = None
+
+    def host(self):
+        """``totals`` as a numpy array - one device -> host copy; raises when a column was over a limit."""
+        h = self.buf.cpu().numpy()
+        err = int(h[-1:].view(np.int32)[0])
+        if err:
+            raise _lib.SedError("sed_psds_counts: " + "; ".join(m for b, m in _ERR_BITS.items() if err & b)
+                                + " - nothing was truncated, the counts are invalid")
+        return h[:-1].reshape(self.K, self.NC, 2 + self.NC)
+
+    check = host
+
+
+def _psds_target(counts, K, NC, n, device, dtc, gtc, cttc, per_column):
+    if counts is None:
+        counts = PSDSCounts(K, NC, device, dtc, gtc, cttc)
+    if (counts.K, counts.NC) != (K, NC):
+        raise ValueError("counts was built for another number of operating points / classes")
+    if (counts.dtc, counts.gtc, counts.cttc) != (float(dtc), float(gtc), float(cttc)):
+        raise ValueError("counts was built for other criteria (dtc, gtc, cttc)")
+    if per_column:
+        counts.columns = torch.empty(K, n, NC, 2 + NC, dtype=torch.int32, device=device)
+    return counts
+
+
+def psds_counts(strong, ref, thresholds=(0.5,), median_windows=(5,), pooling_time_ratio=1, cfg=None, dtc=0.5, gtc=0.5,
+                cttc=0.3, clip_offset=0, counts=None, per_column=False):
+    """``event_counts`` for the PSDS criteria: ``strong [n, T, nclass]`` cuda float32 posteriors of clips ``clip_offset ..
+    clip_offset + n - 1`` of ``ref`` -> ``PSDSCounts`` (device tensors, no synchronisation; pass ``counts`` to accumulate
+    batches - its criteria must be these).  Operating points, ``cfg`` and the seconds as in ``event_counts``."""
+    if strong.device.type != "cuda" or ref.device.type != "cuda":
+        raise _lib.SedError("psds_counts needs GPU tensors and a RefEvents on the GPU (no CPU fallback)")
+    cfg = cfg or _Cfg
+    strong = strong.contiguous().float()
+    n, T, NC = strong.shape
+    if NC != ref.nclass or clip_offset < 0 or clip_offset + n > len(ref):
+        raise ValueError(f"posteriors [{n}, {T}, {NC}] at clip {clip_offset} do not fit the reference ({len(ref)} clips, "
+                         f"{ref.nclass} classes)")
+    thr, win = operating_points(thresholds, median_windows, strong.device)
+    K = thr.numel()
+    counts = _psds_target(counts, K, NC, n, strong.device, dtc, gtc, cttc, per_column)
+    _lib.check(_lib.lib().sed_psds_counts(
+        _lib.ptr(strong), n, T, NC, K, _lib.ptr(thr), _lib.ptr(win), float(pooling_time_ratio),
+        float(cfg.sample_rate / cfg.hop_length), None, None, None, _lib.ptr(ref.ptr[clip_offset * NC:]), _lib.ptr(ref.onset),
+        _lib.ptr(ref.offset), counts.dtc, counts.gtc, counts.cttc, _lib.ptr(counts.columns) if per_column else None,
+        _lib.ptr(counts.totals), _lib.ptr(counts.err), _lib.stream_ptr()), "sed_psds_counts")
+    return counts
+
+
+def psds_counts_from_events(est, ref, dtc=0.5, gtc=0.5, cttc=0.3, per_column=False):
+    """The criteria alone: ``est`` is a ``RefEvents`` holding the DETECTIONS of the same files and classes.  One operating
+    point."""
+    if est.device.type != "cuda" or ref.device.type != "cuda":
+        raise _lib.SedError("psds_counts_from_events needs both event sets on the GPU (no CPU fallback)")
+    if est.filenames != ref.filenames or est.labels != ref.labels:
+        raise ValueError("estimated and reference events must cover the same files and classes, in the same order")
+    n, NC = len(ref), ref.nclass
+    counts = _psds_target(None, 1, NC, n, ref.device, dtc, gtc, cttc, per_column)
+    _lib.check(_lib.lib().sed_psds_counts(
+        None, n, 0, NC, 1, None, None, 0.0, 0.0, _lib.ptr(est.ptr), _lib.ptr(est.onset), _lib.ptr(est.offset),
+        _lib.ptr(ref.ptr), _lib.ptr(ref.onset), _lib.ptr(ref.offset), counts.dtc, counts.gtc, counts.cttc,
+        _lib.ptr(counts.columns) if per_column else None, _lib.ptr(counts.totals), _lib.ptr(counts.err),
+        _lib.stream_ptr()), "sed_psds_counts")
     return counts
 
 
@@ -332,6 +438,89 @@ class SegmentMetrics(_Metrics):
         return f"time resolution {self.time_resolution:.2f} s"
 
 
+class PSDS:
+    """The PSD-ROC and its area from class totals of K operating points - host arithmetic, no GPU needed.
+
+    ``totals [K, nclass, 2 + nclass]`` (TP, FP, CT[.][k]) as ``PSDSCounts.host()`` returns them, ``n_gt [nclass]`` reference
+    events per class, ``gt_duration [nclass]`` their summed lengths in seconds, ``dataset_duration`` the summed file
+    durations in seconds.  Rates are per hour.  Arrays for logging: ``tpr [K, nclass]``, ``fpr [K, nclass]``,
+    ``ctr [K, nclass, nclass]`` and ``efpr(alpha_ct) [K, nclass]``.  Parity with ``psds_eval`` is unpinned (module docstring)."""
+    UNIT = 3600.0
+
+    def __init__(self, labels, totals, n_gt, gt_duration, dataset_duration):
+        self.labels = list(labels)
+        nc = len(self.labels)
+        t = np.asarray(totals, np.int64)
+        if t.ndim != 3 or t.shape[1:] != (nc, 2 + nc):
+            raise ValueError(f"totals must be [K, {nc}, {2 + nc}], got {t.shape}")
+        self.n_gt = np.asarray(n_gt, np.int64).reshape(nc)
+        self.gt_duration = np.asarray(gt_duration, np.float64).reshape(nc)
+        self.dataset_duration = float(dataset_duration)
+        empty = [l for l, n in zip(self.labels, self.n_gt) if n <= 0]
+        if empty:
+            raise ValueError(f"PSDS is undefined: no reference events of class {', '.join(map(str, empty))}")
+        if not self.dataset_duration > 0.0:
+            raise ValueError("the dataset duration must be positive")
+        self.tp, self.fp, self.ct = t[:, :, 0], t[:, :, 1], t[:, :, 2:]
+        self.tpr = self.tp / self.n_gt[None, :].astype(np.float64)
+        self.fpr = self.UNIT * self.fp / self.dataset_duration
+        has = self.gt_duration > 0.0
+        self.ctr = np.zeros(self.ct.shape, np.float64)
+        self.ctr[:, :, has] = self.UNIT * self.ct[:, :, has] / self.gt_duration[has]
+
+    @classmethod
+    def from_counts(cls, counts, ref, durations):
+        """``counts``: a ``PSDSCounts`` (read with ``host()``) or its totals array; ``n_gt`` and ``gt_duration`` come from the
+        ``RefEvents``; ``durations``: seconds per file as one number, or a sequence aligned with ``ref.filenames``."""
+        totals = counts.host() if hasattr(counts, "host") else counts
+        nc = ref.nclass
+        per_column = np.diff(ref.ptr_host.astype(np.int64))
+        n_gt = per_column.reshape(len(ref), nc).sum(0)
+        cls_of_event = np.repeat(np.arange(len(per_column)) % nc, per_column)
+        gt_duration = np.bincount(cls_of_event, weights=ref.offset_host - ref.onset_host, minlength=nc)
+        if np.ndim(durations) == 0:
+            total = float(durations) * len(ref)
+        else:
+            if len(durations) != len(ref):
+                raise ValueError(f"{len(durations)} durations for {len(ref)} files")
+            total = float(np.sum(np.asarray(durations, np.float64)))
+        return cls(ref.labels, totals, n_gt, gt_duration, total)
+
+    def efpr(self, alpha_ct=0.0):
+        """``[K, nclass]``: ``FPR + alpha_ct * mean over the other classes of CTR`` (no other class: the term is 0)."""
+        nc = len(self.labels)
+        if nc == 1:
+            return self.fpr.copy()
+        other = self.ctr.sum(2) - np.einsum("kcc->kc", self.ctr)
+        return self.fpr + alpha_ct * other / (nc - 1)
+
+    def class_curves(self, axis, alpha_ct=0.0):
+        """``[nclass, len(axis)]``: per class the largest TPR among the operating points with ``eFPR <= axis`` (0 below the
+        first) - a left-continuous, monotone staircase."""
+        e = self.efpr(alpha_ct)
+        axis = np.asarray(axis, np.float64)
+        out = np.zeros((len(self.labels), len(axis)), np.float64)
+        for c in range(len(self.labels)):
+            order = np.argsort(e[:, c], kind="stable")
+            xs, best = e[order, c], np.maximum.accumulate(self.tpr[order, c])
+            at = np.searchsorted(xs, axis, side="right")             # points with eFPR <= x
+            out[c] = np.where(at > 0, best[np.maximum(at, 1) - 1], 0.0)
+        return out
+
+    def psd_roc(self, alpha_ct=0.0, alpha_st=0.0, max_efpr=100.0):
+        """``(axis, eff_tpr)``: the sorted union of all classes' eFPR values ``<= max_efpr`` and, at each,
+        ``max(0, mean - alpha_st * std)`` of the class curves (population standard deviation)."""
+        e = self.efpr(alpha_ct)
+        axis = np.unique(e[e <= max_efpr])
+        curves = self.class_curves(axis, alpha_ct)
+        return axis, np.maximum(0.0, curves.mean(0) - alpha_st * curves.std(0))
+
+    def psds(self, alpha_ct=0.0, alpha_st=0.0, max_efpr=100.0):
+        """Area under the PSD-ROC up to ``max_efpr`` (nothing below the first axis value), normalised by ``max_efpr``."""
+        axis, eff = self.psd_roc(alpha_ct, alpha_st, max_efpr)
+        return float(np.sum(eff * np.diff(np.r_[axis, float(max_efpr)])) / max_efpr)
+
+
 # ---- drop-ins with the reference's signatures -------------------------------------------------------------------------------
 def compute_strong_metrics(predictions, valid_df, pooling_time_ratio=None, cfg=None, device="cuda"):
     """Drop-in for evaluation_measures.compute_strong_metrics (lines 234-246): event tables in, the event-based metric out,
@@ -383,11 +572,14 @@ def get_f_measure_by_class(torch_model, nb_tags, dataloader_, thresholds_=None):
     return macro_f_measure
 
 
-def validate(model, dataset, ref, pooling_time_ratio, thresholds=(0.5,), median_windows=(5,), batch_size=64, cfg=None):
+def validate(model, dataset, ref, pooling_time_ratio, thresholds=(0.5,), median_windows=(5,), batch_size=64, cfg=None,
+             psds=None):
     """The fused route for the epoch loop (main.py:324-328 without the event table): ``dataset`` as
     ``inference.get_predictions`` accepts it, forward ``batch_size`` clips at a time, ``sed_event_counts`` per batch into
     running totals, ONE device -> host copy at the end.  ``ref``: the ``RefEvents`` of the same clips in the same order.
-    Returns one ``(EventMetrics, SegmentMetrics)`` per operating point."""
+    Returns one ``(EventMetrics, SegmentMetrics)`` per operating point.  ``psds``: a ``PSDSCounts`` of the same operating
+    points; every batch's posteriors then also go through ``sed_psds_counts`` into it (same forward, same operating-point
+    tensors; read it with ``PSDS.from_counts``)."""
     from .resident import ResidentFeatureSet
     if not getattr(model, "hot_path", False):
         raise _lib.SedError("validate needs a CRNN on the HIP hot path")
@@ -400,6 +592,8 @@ def validate(model, dataset, ref, pooling_time_ratio, thresholds=(0.5,), median_
         raise ValueError(f"{len(dataset)} clips but reference events of {len(ref)}")
     thr, win = operating_points(thresholds, median_windows, dev)
     counts = Counts(thr.numel(), ref.nclass, dev)
+    if psds is not None and (psds.K, psds.NC) != (counts.K, counts.NC):
+        raise ValueError("psds was built for another number of operating points / classes")
     was_training = model.training
     model.eval()
     try:
@@ -407,6 +601,9 @@ def validate(model, dataset, ref, pooling_time_ratio, thresholds=(0.5,), median_
             for i0, _, x in eval_batches(dataset, batch_size, dev):
                 strong, _ = model(x)
                 event_counts(strong, ref, thr, win, pooling_time_ratio, cfg, clip_offset=i0, counts=counts)
+                if psds is not None:
+                    psds_counts(strong, ref, thr, win, pooling_time_ratio, cfg, psds.dtc, psds.gtc, psds.cttc, clip_offset=i0,
+                                counts=psds)
     finally:
         model.train(was_training)
     ev, seg = counts.host()

@@ -465,6 +465,42 @@ int sed_event_counts(const float* strong, int n_clips, int T, int nclass, int n_
 int sed_weak_counts(const float* weak, const uint8_t* labels, int n_clips, int nclass, const float* thr,
                     int n_points, int64_t* counts, void* stream);
 
+/* ---- PSDS intersection counts ------------------------------------------------------------------
+ * The polyphonic sound detection score (Bilen et al., ICASSP 2020) is the area under a PSD-ROC built from a grid of
+ * operating points, each scored with three intersection criteria.  sed_psds_counts produces the integer counts of
+ * every operating point in one launch; the curve and its area are host arithmetic (metrics.PSDS).
+ * psds_eval is third-party, absent from this image and from the reference tree: the definitions below are restated
+ * from the paper, and where the package's behaviour was uncertain the text below decides - parity with psds_eval
+ * itself is UNPINNED (as for sed_eval above); pinned is exact agreement with an independent numpy statement of
+ * these definitions (tests/psds_np.py).
+ *
+ * Per (operating point k, clip); classes are columns; an event is (on, off) in fp64 seconds.  Detections: decoded
+ * from `strong` exactly as sed_event_counts does (thr[k], win[k], seconds = (double)frame * num / den), or given as
+ * est_ptr / est_on / est_off (strong == NULL, n_points = 1).  Ground truths: ref_ptr / ref_on / ref_off as above,
+ * in stored order.
+ *   I(d, g) = max(0, min(d.off, g.off) - max(d.on, g.on));  len(e) = e.off - e.on.
+ *   Every sum is a sequential fp64 sum over the other side's events in stored index order, starting from 0.0; every
+ *   test is sum / len >= threshold (the division first); an event with len <= 0, or a NaN ratio, fails every test.
+ *   DTC:  detection d of class c is RELEVANT iff (sum over g in G_c of I(d, g)) / len(d) >= dtc.
+ *         FP[c] = detections of c that are not relevant (those that turn out to be cross-triggers included).
+ *   GTC:  ground truth g of class c is a true positive iff (sum over the RELEVANT d in D_c of I(d, g)) / len(g) >= gtc.
+ *         TP[c] = their number.
+ *   CTTC: for every non-relevant detection d of class c and every other class j: CT[c][j] += 1 iff
+ *         (sum over g in G_j of I(d, g)) / len(d) >= cttc.  CT[c][c] = 0.
+ *   dtc, gtc, cttc in [0, 1] (the task's values: 0.5, 0.5, 0.3).
+ *   columns    [n_points][n_clips][nclass][2 + nclass] int32 (TP, FP, CT[.][0 .. nclass - 1]) or NULL
+ *   totals     [n_points][nclass][2 + nclass] int64: ACCUMULATED over clips (zero them before the first batch;
+ *              integer sums: bit-reproducible)
+ *   err        the error word of sed_event_counts, same bits (1, 2: more than 64 reference / estimated events in a
+ *              column, 8: a window outside 1 .. 63, 16: malformed offsets; 4 is never raised here).  Nothing is
+ *              truncated: a caller must treat the totals as invalid when err != 0.
+ * Limits: T <= 2048, nclass <= 16.  One launch on `stream`, no allocation, hipGraph-capturable. */
+int sed_psds_counts(const float* strong, int n_clips, int T, int nclass, int n_points, const float* thr,
+                    const int32_t* win, double num, double den, const int32_t* est_ptr, const double* est_on,
+                    const double* est_off, const int32_t* ref_ptr, const double* ref_on, const double* ref_off,
+                    double dtc, double gtc, double cttc, int32_t* columns, int64_t* totals, int32_t* err,
+                    void* stream);
+
 /* ---- single-kernel replay (measurement) ----------------------------------------------------
  * Re-launches ONE kernel of the step on the buffers left by a finished sed_crnn_forward +
  * sed_crnn_backward (same shapes, same data; outputs are rewritten with identical values), so

@@ -8,7 +8,8 @@ than `frames`).  Device-event timing; prints one JSON object (and writes it to -
       host collate, step.step
   (d) get_predictions over 400 validation clips: per-clip dataset (np.load + get_transforms per clip) against the resident set
   (e) validation scoring over 1 168 and 400 resident clips: metrics.validate at one operating point and at 50 thresholds, the
-      DataFrame route (get_predictions + compute_strong_metrics), and sed_event_counts alone (--only-e: this leg only)
+      DataFrame route (get_predictions + compute_strong_metrics), sed_event_counts alone, and - next to them, in the same
+      run - validate(..., psds=...) and sed_psds_counts alone at the same operating points (--only-e: this leg only)
 
 Usage: python tools/epoch_bench.py [--shapes 24:f32,64:bf16] [--only-a | --only-e] [--out FILE]"""
 import argparse
@@ -230,8 +231,22 @@ def leg_e(feats, sc, sizes=(1168, 400), reps=20):
             counts = metrics.Counts(thr.numel(), NCLASS, "cuda")
             return lambda: [metrics.event_counts(strong[i0:i0 + 64], ref, thr, win, 8, clip_offset=i0, counts=counts)
                             for i0 in range(0, n, 64)]
+
+        def psds_launches(thr, win):
+            counts = metrics.PSDSCounts(thr.numel(), NCLASS, "cuda")
+            return lambda: [metrics.psds_counts(strong[i0:i0 + 64], ref, thr, win, 8, clip_offset=i0, counts=counts)
+                            for i0 in range(0, n, 64)]
+
+        def validate_psds(thresholds):
+            def run():                                      # what a user's epoch does: both sets of totals reach the host
+                psds = metrics.PSDSCounts(len(thresholds), NCLASS, "cuda")
+                metrics.validate(model, res, ref, 8, thresholds, (5,), batch_size=64, psds=psds)
+                psds.host()
+            return run
         n_est = int(count_launches(thr1, win1)()[-1].host()[0][0, :, 2].sum())
         count_launches(thr_k, win_k)()
+        psds_1 = psds_launches(thr1, win1)()[-1].host()[0]
+        psds_launches(thr_k, win_k)()
         # (a randomly initialised CRNN: posteriors nearly constant in time, so few estimated events per clip)
         leg = {"clips": n, "batch_size": 64, "reference_events": len(rows), "estimated_events_at_0.5": n_est,
                "i_validate_1_point_ms": wall_ms(lambda: metrics.validate(model, res, ref, 8, batch_size=64)),
@@ -240,6 +255,14 @@ def leg_e(feats, sc, sizes=(1168, 400), reps=20):
                    get_predictions(model, res, enc.decode_strong, 8, batch_size=64), valid_df)),
                "iv_event_counts_only_1_point_ms": round(event_ms(count_launches(thr1, win1), 20), 4),
                "iv_event_counts_only_50_thresholds_ms": round(event_ms(count_launches(thr_k, win_k), 20), 4)}
+        # PSDS: the same posteriors, references and operating points, timed in the same run as iv
+        leg.update({"psds_tp_fp_ct_at_0.5": [int(psds_1[:, 0].sum()), int(psds_1[:, 1].sum()), int(psds_1[:, 2:].sum())],
+                    "v_validate_with_psds_1_point_ms": wall_ms(validate_psds([0.5])),
+                    "v_validate_with_psds_50_thresholds_ms": wall_ms(validate_psds(thr50)),
+                    "vi_psds_counts_only_1_point_ms": round(event_ms(psds_launches(thr1, win1), 20), 4),
+                    "vi_psds_counts_only_50_thresholds_ms": round(event_ms(psds_launches(thr_k, win_k), 20), 4)})
+        leg["vi_over_iv_50_thresholds"] = round(leg["vi_psds_counts_only_50_thresholds_ms"]
+                                                / leg["iv_event_counts_only_50_thresholds_ms"], 3)
         leg["iv_share_of_i"] = round(leg["iv_event_counts_only_1_point_ms"] / leg["i_validate_1_point_ms"], 4)
         leg["ii_over_i"] = round(leg["ii_validate_50_thresholds_ms"] / leg["i_validate_1_point_ms"], 3)
         out.append(leg)
