@@ -437,7 +437,7 @@ static int crnn_backward_impl(const sed_dims* d, const float* params, const floa
     if (!(parts & 1)) SED_CHECK_HIP(hipMemsetAsync(WSD(W.bwd_acc), 0, (2 * SED_GLUACC_N + 2 * 64 * 10) * sizeof(double), st));
     // Stream schedule (kernel timeline of one step, tools/timeline.py): the dgrad chain is the critical path.
     //   main: glu2_bwd  prep | dgrad2            | glu1_bwd  prep | dgrad1          | blk0_bwd  finalize |
-    //   side:                | wgrad2  GRU dW/db |                | wgrad1  reduce                       | join
+    //   side:                | wgrad2  heads_fin |                | wgrad1  reduce  GRU dW/db  reduce    | join
     // (Forking before glu2_bwd so that the GRU GEMMs run first and wgrad1 starts on time measured slower, 1.061 vs
     // 1.029 ms: they then compete with the critical-path kernels glu2_bwd / dgrad2 / glu1_bwd.)
     // (Same experiment again with the Winograd convolutions, where the side stream has become the tail of the step: still
@@ -465,7 +465,8 @@ static int crnn_backward_impl(const sed_dims* d, const float* params, const floa
         if (i == 2) SED_TRY(side.start());
         SED_TRY(launch_conv_wgrad(WSF(dzo[i]), CTXF(yo[i]), WSF(W.coef[i]), CTXF(pin[i]), WSF(W.wg_part), W.wgrad_blocks,
                                   grads + P.conv_w[i], g.B, Hs[i], Wd[i], pp, side.s));
-        if (i == 2) SED_TRY(rnn_deferred_weight_grads(rb));      // parts == 3: head column sum + GRU dW / db behind wgrad2
+        if (i == 2) SED_TRY(rnn_deferred_weight_grads(rb));      // parts == 3: head column sum behind wgrad2
+        if (i == 1) SED_TRY(rnn_tail_weight_grads(rb));          // parts == 3: every GRU dW / db at the very end of the helper stream
     }
     // ---- conv block 0 ---------------------------------------------------------------------------
     SED_TRY(launch_blk0_backward(g, x, params + P.conv_w[0], params + P.conv_b[0], params + P.bn_g[0], params + P.bn_b[0],
@@ -580,6 +581,11 @@ extern "C" int sed_kernel_replay(const char* name, const sed_dims* d, const floa
         return launch_heads_fwd(CTXF(L.out[g.L - 1]), params + P.dense_w, params + P.dense_b, params + P.soft_w, params + P.soft_b,
                                 CTXF(L.strong_sv), CTXF(L.weak_sv), nullptr, nullptr, CTXF(L.logits_s), CTXF(L.den_sv), g.B, g.T3, g.NC,
                                 use_drop, g.p, seed_dev, st);
+    if (is("gru_wgrad")) {
+        // every GRU dW / db, as a parts == 1 backward issues them (rnn.hip: one k_gru_wgrad launch + its reduce)
+        SideFork side = side_fork(st);
+        return rnn_weight_grads(rnn_backward_plan(g, P, rnn_bufs(L, ctx, &W, ws), params, grads, seed_dev, nullptr, nullptr, 1, &side), st);
+    }
     if (is("blk0_bwd"))
         return launch_blk0_backward(g, x, params + P.conv_w[0], params + P.conv_b[0], params + P.bn_g[0], params + P.bn_b[0],
                                     params + P.glu_w[0], CTXM(L.mask0), CTXD(L.mom0), CTXF(L.wz0), CTXF(L.wl0), CTXF(L.bn0), WSF(W.dp0),

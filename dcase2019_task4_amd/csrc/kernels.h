@@ -190,6 +190,27 @@ size_t gemm_part_floats(int n_prob, int splits, int max_m, int max_nx);
 int launch_gemm_batch(GemmBatch& gb, hipStream_t st);
 int launch_colsum(const float* A, int M, int N, int64_t lda, float* out, hipStream_t st);
 
+// gruw.hip : every GRU weight / bias gradient of the 64-cell fp32 BiGRU (both layers, both directions) in one split-K launch + one
+// small reduce launch, operands straight from global memory into the f32 MFMA
+struct GruWgradLayer {
+    const float *dgi, *dgh;          // [BT][2][192]; of dgh only the n third is read (its r and z thirds equal dgi's, gru4.hip)
+    const float* hprev;              // [BT][2][64]
+    const float* input; int nin;     // [BT][nin], nin = 64 or 128
+    float *w_ih[2], *w_hh[2], *b_ih[2], *b_hh[2];      // gradient outputs per direction: [192][nin], [192][64], [192], [192]
+};
+struct GruWgradTile {                // C[64][64] = A^T B over the BT rows; bias (may be null) = column sums of A
+    const float *A, *B; float *C, *bias;
+    int lda, ldb, ldc;
+};
+#define SED_GRUW_MAX_TILES 36        // 2 directions x (6 + 12): layer 0 with nin = 128 is the wide-conv generic set
+struct GruWgradArgs {
+    GruWgradTile t[SED_GRUW_MAX_TILES];
+    int n_tiles, BT;
+    float* part;                     // n_tiles * 4 partial tiles (gru_wgrad_part_floats)
+};
+size_t gru_wgrad_part_floats(int n_tiles);
+int launch_gru_wgrad(const GruWgradLayer* layers, int n_layers, int BT, float* part, size_t part_floats, hipStream_t st);
+
 // gru4.hip
 // crnn.hip: runs the host callback registered by sed_crnn_fork_callback (if any) for st - called by rnn_forward (rnn.hip), i.e. by
 // both forwards between the conv stack and the recurrence

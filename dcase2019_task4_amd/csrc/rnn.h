@@ -51,8 +51,8 @@ int rnn_forward(const Geo& g, const ParamOff& P, const float* params, const RnnB
                 float* strong, float* weak, int n_whh_packed, hipStream_t st);
 
 // One backward call's view of the tail.  rnn_backward_plan fills it in (the fuse / defer_colsum / early_gru_w decisions are
-// taken there and nowhere else); the orchestrator then calls rnn_backward in front of its conv-block half and
-// rnn_deferred_weight_grads behind its block-2 wgrad launch.
+// taken there and nowhere else); the orchestrator then calls rnn_backward in front of its conv-block half,
+// rnn_deferred_weight_grads behind its block-2 wgrad launch and (crnn.hip) rnn_tail_weight_grads behind its block-1 wgrad launch.
 struct RnnBwd {
     Geo g; ParamOff P; RnnBufs R;
     const float* params; float* grads; const uint64_t* seed_dev; const HeadsLoss* hl; const HeadsOut* ho; int parts; SideFork* side;
@@ -65,3 +65,4 @@ int rnn_weight_grads_layer(const RnnBwd& rb, int l, hipStream_t s2);      // GRU
 int rnn_weight_grads(const RnnBwd& rb, hipStream_t s2);
 int rnn_heads_colsum(const RnnBwd& rb, hipStream_t s2);                    // k_heads_colsum, or (fuse) k_heads_fin
 int rnn_deferred_weight_grads(const RnnBwd& rb);                           // parts == 3: what rnn_backward left to the helper stream
+int rnn_tail_weight_grads(const RnnBwd& rb);                               // ... and what goes behind the block-1 wgrad (k_gru_wgrad)

@@ -89,9 +89,26 @@ int rnn_weight_grads_layer(const RnnBwd& rb, int l, hipStream_t s2) {
     }
     return launch_gemm_batch(gb, s2);
 }
+// H = 64, fp32 operands, 64 or 128 input columns: every layer's dW / db in one launch of k_gru_wgrad (gruw.hip) + its reduce
+static bool rnn_weight_grads_fused(const Geo& g) { return g.H == 64 && g.mode == SED_DTYPE_F32 && (g.C == 64 || g.C == 128); }
 int rnn_weight_grads(const RnnBwd& rb, hipStream_t s2) {
-    for (int l = rb.g.L - 1; l >= 0; --l) SED_TRY(rnn_weight_grads_layer(rb, l, s2));
-    return SED_OK;
+    const Geo& g = rb.g; const ParamOff& P = rb.P; const RnnBufs& R = rb.R;
+    if (!rnn_weight_grads_fused(g)) {
+        for (int l = g.L - 1; l >= 0; --l) SED_TRY(rnn_weight_grads_layer(rb, l, s2));
+        return SED_OK;
+    }
+    GruWgradLayer ly[2];
+    for (int l = 0; l < g.L; ++l) {
+        ly[l].dgi = R.dgi[l]; ly[l].dgh = R.dgh[l]; ly[l].hprev = R.hprev[l];
+        ly[l].input = (l == 0) ? R.p2 : R.out[l - 1];
+        ly[l].nin = (l == 0) ? g.C : 2 * g.H;
+        for (int dir = 0; dir < 2; ++dir) {
+            ly[l].w_ih[dir] = rb.grads + P.w_ih[l][dir]; ly[l].w_hh[dir] = rb.grads + P.w_hh[l][dir];
+            ly[l].b_ih[dir] = rb.grads + P.b_ih[l][dir]; ly[l].b_hh[dir] = rb.grads + P.b_hh[l][dir];
+        }
+    }
+    // (the whole gemm_part region: one layer's share, or - gemm_part_stride != 0 - one share per layer)
+    return launch_gru_wgrad(ly, g.L, g.B * g.T3, R.gemm_part, R.gemm_part_floats + R.gemm_part_stride, s2);
 }
 
 // the column sum of the per-clip head weight-gradient partials; fused form: k_heads_fin (+ the meters' clip sums, the step-state advance)
@@ -106,15 +123,22 @@ int rnn_heads_colsum(const RnnBwd& rb, hipStream_t s2) {
 // behind the block-2 conv wgrad, where it overlaps the block-1 GLU backward, long before the tail of the step.
 // (The column sum queued right in front of wgrad1 sat 60 us behind the persistent dgrad kernel and held wgrad1 back; at the very
 // end of the helper stream it was 4 us on the step's tail.)
-// (Between wgrad2 and wgrad1 the GEMMs hold wgrad1 - the tail of the step - back by ~80 us (r02_a step timeline: wgrad1 starts at
-// 678 us, its inputs are ready at 594 us); a helper stream of their OWN measured SLOWER all the same in round 2 - 0.829 vs
-// 0.815 ms (fp32), 0.775 vs 0.742 ms (bf16 operands): the step is throughput-bound, a third stream only takes CUs from the
-// dgrad / block-0 chain.  Removed.)
+// The GRU dW / db of the specialised fp32 kernel set (k_gru_wgrad, gruw.hip) are NOT queued here but at the very end of the helper
+// stream (rnn_tail_weight_grads).  Here, k_gemm_batched's four launches held wgrad1 - the tail of the step - back: it started at
+// 646 us with its inputs ready at ~520.  k_gru_wgrad in the same place still starves behind the persistent dgrad1 kernel (64 + 39
+// us in the step for 16 solo) and wgrad1 starts at 637; behind wgrad1 + its reduce it takes 19 + 5 us beside the end of k_blk0_bwd
+// and the helper stream ends 4 us BEFORE the main chain.  Replayed step, median of three interleaved runs: 0.7171 ms with the
+// GEMMs, 0.7122 with k_gru_wgrad here, 0.7068 with it at the end (measured with the kernel's first form, 32 K slices in an order
+// of its own; the kept form, which keeps the GEMMs' summation order: 0.7080 at the end against 0.7177 - profiles/gru_wgrad_fused.md).
+// (A helper stream of their OWN for the GEMMs measured SLOWER in round 2 - 0.829 vs 0.815 ms (fp32), 0.775 vs 0.742 ms (bf16
+// operands): the step is throughput-bound, a third stream only takes CUs from the dgrad / block-0 chain.  Removed.)
+static bool rnn_gru_w_at_tail(const RnnBwd& rb) { return rb.parts == 3 && !rb.early_gru_w && !rb.g.generic && rnn_weight_grads_fused(rb.g); }
 int rnn_deferred_weight_grads(const RnnBwd& rb) {
     if (rb.parts != 3 || rb.early_gru_w) return SED_OK;
     if (rb.defer_colsum) SED_TRY(rnn_heads_colsum(rb, rb.side->s));
-    return rnn_weight_grads(rb, rb.side->s);
+    return rnn_gru_w_at_tail(rb) ? SED_OK : rnn_weight_grads(rb, rb.side->s);
 }
+int rnn_tail_weight_grads(const RnnBwd& rb) { return rnn_gru_w_at_tail(rb) ? rnn_weight_grads(rb, rb.side->s) : SED_OK; }
 
 int rnn_backward(const RnnBwd& rb, const float* d_strong, const float* d_weak, hipStream_t st) {
     const Geo& g = rb.g; const ParamOff& P = rb.P; const RnnBufs& R = rb.R;
