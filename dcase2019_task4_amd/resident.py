@@ -19,6 +19,11 @@ arithmetic of ``sed_logmel_transform``, clips of any length, targets copied by t
   the graph reads) and the replay; no feature or target crosses the host.  Tables are double-buffered: the one of epoch
   e + 1 is drawn and uploaded when epoch e's first batch is staged, so batch 0 of e + 1 can be gathered during the last
   step of e.
+* ``augment=AugmentPolicy(...)`` on a training set (augment.py): mixup, circular time shift and time / frequency masks of
+  the gathered batch.  The per-clip parameter rows of an epoch are drawn on the host from the policy's own generator and
+  uploaded beside the index table; per step one more device-to-device row copy (32 B x B) stages the batch's rows, and the
+  extraction becomes gather into staging buffers + one ``sed_batch_augment`` launch into the slot.  ``for_eval`` never
+  augments.
 * ``ResidentFeatureSet.for_eval``: the validation form (no noise) that ``inference.get_predictions`` gathers
   ``batch_size`` clips per launch from.
 """
@@ -27,6 +32,7 @@ import torch
 
 from . import _lib
 from . import dist as sdist
+from .augment import AugmentPolicy, augment_batch, validate_table      # noqa: F401  (the public names live here too)
 from .features import OneBatchAheadFrontEnd
 
 _UPLOAD_CHUNK = 1 << 26            # floats per host->device copy while building the pool (256 MB)
@@ -63,7 +69,7 @@ class ResidentFeatureSet:
     encoded target [T3, nclass])``) in stream order; ``from_arrays`` takes the clips directly."""
 
     def __init__(self, datasets, batch_sizes, frames, scaler=None, augment_type="noise", device="cuda", process_group=None,
-                 math_dtype="f64", seed=0):
+                 math_dtype="f64", seed=0, augment=None):
         feats, tgts, sizes = [], [], []
         for ds in datasets:
             sizes.append(len(ds))
@@ -71,18 +77,20 @@ class ResidentFeatureSet:
                 f, y = ds.get_sample(i)
                 feats.append(f)
                 tgts.append(y)
-        self._setup(feats, tgts, sizes, batch_sizes, frames, scaler, augment_type, device, process_group, math_dtype, seed)
+        self._setup(feats, tgts, sizes, batch_sizes, frames, scaler, augment_type, device, process_group, math_dtype, seed,
+                    augment)
 
     @classmethod
     def from_arrays(cls, features, targets, stream_sizes=None, batch_sizes=None, frames=628, scaler=None, augment_type="noise",
-                    device="cuda", process_group=None, math_dtype="f64", seed=0):
+                    device="cuda", process_group=None, math_dtype="f64", seed=0, augment=None):
         """``features``: sequence of float arrays [L_i, n_mels] (any L_i >= 1); ``targets``: sequence of [T3, nclass] arrays or
         None (no targets); ``stream_sizes``: clips per stream, in order (default: one stream); ``batch_sizes``: clips per stream
-        and batch (None: a set for gather / evaluation only, no epoch tables)."""
+        and batch (None: a set for gather / evaluation only, no epoch tables); ``augment``: an ``AugmentPolicy`` (mixup, time
+        shift, masks on the gathered batch: augment.py) or None - a training set's only, ``augment_type`` keeps its meaning."""
         self = cls.__new__(cls)
         self._setup(list(features), None if targets is None else list(targets),
                     [len(features)] if stream_sizes is None else list(stream_sizes), batch_sizes, frames, scaler, augment_type,
-                    device, process_group, math_dtype, seed)
+                    device, process_group, math_dtype, seed, augment)
         return self
 
     @classmethod
@@ -95,9 +103,15 @@ class ResidentFeatureSet:
         return self
 
     # ---- construction --------------------------------------------------------------------------------------------------------
-    def _setup(self, feats, tgts, sizes, batch_sizes, frames, scaler, augment_type, device, process_group, math_dtype, seed):
+    def _setup(self, feats, tgts, sizes, batch_sizes, frames, scaler, augment_type, device, process_group, math_dtype, seed,
+               augment=None):
         if augment_type not in (None, "noise"):
             raise NotImplementedError("only augment_type='noise' exists (utils.py:404-406)")
+        if augment is not None and not isinstance(augment, AugmentPolicy):
+            raise TypeError(f"augment must be an AugmentPolicy or None, got {type(augment).__name__}")
+        if augment is not None and batch_sizes is None:
+            raise ValueError("only a training set (built with batch sizes) takes an augmentation policy")
+        self.augment = augment
         # (a set on a CPU device holds the pool, the targets and the tables - what can be checked without a GPU - and refuses
         # to gather: there is no CPU path)
         self.device = torch.device(device)
@@ -183,6 +197,8 @@ class ResidentFeatureSet:
                 raise ValueError("a training set needs targets")
             self.batch = sum(bs) // self.world
             self.weak_mask, self.strong_mask = sdist.local_masks(bs, self.world)
+            ends = np.cumsum(sdist.local_batch_sizes(bs, self.world))
+            self.stream_slices = [slice(int(lo), int(hi)) for lo, hi in zip(np.r_[0, ends[:-1]], ends)]
 
     def step_masks(self, weak_mask, strong_mask):
         """The masks for this rank's step (local_step_masks); without a process group the caller's masks are used as given."""
@@ -221,6 +237,14 @@ class ResidentFeatureSet:
         if t.size and (t.min() < 0 or t.max() >= self.n_clips):
             raise _lib.SedError(f"epoch table holds an index outside [0, {self.n_clips})")
         return np.ascontiguousarray(t, dtype=np.int32)
+
+    def augment_table(self, epoch):
+        """This rank's augmentation rows of epoch ``epoch`` (0-based count of drawn epochs) [n_steps, batch, 8] int32, from
+        the policy's own generator - pure host code; a set without a policy raises."""
+        if self.augment is None:
+            raise ValueError("this set was built without an augmentation policy")
+        return self.augment.draw(epoch, self.n_steps, self.stream_slices, self.frames, self.target_shape[0], self.n_mels,
+                                 rank=self.rank)
 
     # ---- the gather ----------------------------------------------------------------------------------------------------------
     def gather(self, idx, out_clean, out_noisy=None, key=None, out_target=None, ws=None):
@@ -277,9 +301,10 @@ class ResidentFrontEnd(OneBatchAheadFrontEnd):
     extraction is one sed_gather_logmel_transform launch - clean + noisy inputs and targets of the staged batch).
 
     ``run()`` trains on the next batch of the epoch sequence and gathers the one after it; the sequence runs on across epochs
-    (epoch e's table is drawn when its predecessor's first batch is staged)."""
+    (epoch e's table is drawn when its predecessor's first batch is staged).  ``aug_epoch``: the epoch index the set's
+    augmentation policy is asked for when this front-end draws its first table (0; a resumed run passes its epoch)."""
 
-    def __init__(self, step, rset, overlap=True, seed=None, rng=None):
+    def __init__(self, step, rset, overlap=True, seed=None, rng=None, aug_epoch=0):
         if rset.batch_sizes is None:
             raise ValueError("ResidentFrontEnd needs a set built with batch sizes")
         if step.B != rset.batch or step.T != rset.frames or step.target.shape[1:] != rset.target_shape:
@@ -299,6 +324,20 @@ class ResidentFrontEnd(OneBatchAheadFrontEnd):
         self._drawn = 0                                # epochs whose table has been drawn
         self._epoch, self._pos = 0, 0                  # the batch the next _stage() puts into self.idx
         self.host_tables = {}                          # epoch -> the host table (kept for the two live epochs)
+        # With a policy on the set: per-epoch parameter tables beside the index tables, the staged batch's rows in a fixed
+        # buffer, and staging tensors - extract = gather into staging, then sed_batch_augment into the slot.  Without one,
+        # none of these exist and the captured graph is the plain one - also with a policy that has everything off.
+        # The policy is asked for epoch aug_epoch + k when the front-end's k-th table is drawn: a front-end built in a resumed
+        # run passes the epoch it resumes at (train.train does), or it would redraw epoch 0's rows.
+        self.aug = rset.augment is not None and rset.augment.active
+        self.aug_epoch = int(aug_epoch)
+        if self.aug:
+            self.aug_row = torch.zeros(step.B, 8, device=dev, dtype=torch.int32)
+            self._aug_tables = [torch.empty(rset.n_steps, step.B, 8, device=dev, dtype=torch.int32) for _ in range(2)]
+            self.host_aug_tables = {}
+            self._stage_x = torch.empty_like(step.x)
+            self._stage_x_ema = torch.empty_like(step.x) if rset.noise else None
+            self._stage_target = torch.empty_like(step.target)
 
     def _draw(self, e):
         while self._drawn <= e:
@@ -307,6 +346,11 @@ class ResidentFrontEnd(OneBatchAheadFrontEnd):
             self.host_tables.pop(self._drawn - 2, None)
             # stream order: every row copy of the epoch that used this buffer before was enqueued earlier on this stream
             self._tables[self._drawn % 2].copy_(torch.from_numpy(t).pin_memory(), non_blocking=True)
+            if self.aug:
+                a = validate_table(self.rs.augment_table(self.aug_epoch + self._drawn), self.step.B)
+                self.host_aug_tables[self._drawn] = a
+                self.host_aug_tables.pop(self._drawn - 2, None)
+                self._aug_tables[self._drawn % 2].copy_(torch.from_numpy(a).pin_memory(), non_blocking=True)
             self._drawn += 1
 
     def _stage(self):
@@ -315,12 +359,24 @@ class ResidentFrontEnd(OneBatchAheadFrontEnd):
         if i == 0:
             self._draw(e + 1)
         self.idx.copy_(self._tables[e % 2][i], non_blocking=True)
+        if self.aug:
+            self.aug_row.copy_(self._aug_tables[e % 2][i], non_blocking=True)
         self._pos += 1
         if self._pos == self.rs.n_steps:
             self._epoch, self._pos = e + 1, 0
 
     def extract(self, x, x_ema, target, workgroups):
-        self.rs.gather(self.idx, x, x_ema if self.rs.noise else None, self.key, target, self.ws_t)
+        if not self.aug:
+            self.rs.gather(self.idx, x, x_ema if self.rs.noise else None, self.key, target, self.ws_t)
+            return
+        noisy = x_ema is not None and self.rs.noise
+        sx, se, sg = self._stage_x, self._stage_x_ema if noisy else None, self._stage_target if target is not None else None
+        self.rs.gather(self.idx, sx, se, self.key, sg, self.ws_t)
+        st = self.step
+        _lib.check(self.l.sed_batch_augment(_lib.ptr(sx), _lib.ptr(se), _lib.ptr(sg), _lib.ptr(self.aug_row), st.B, st.T,
+                                            self.rs.n_mels, self.rs.target_shape[0], self.rs.target_shape[1], _lib.ptr(x),
+                                            _lib.ptr(x_ema) if noisy else None, _lib.ptr(target), _lib.stream_ptr()),
+                   "sed_batch_augment")
 
     def prime(self):
         self._stage()

@@ -815,7 +815,9 @@ def _train_resident(rset, model, optimizer, epoch, ema_model, weak_mask, strong_
         model._mt_step = step_obj
     fe = getattr(model, "_mt_frontend", None)
     if fe is None or fe.rs is not rset or fe.step is not step_obj:
+        # (a front-end built in a resumed run starts its augmentation draws at this epoch, not again at epoch 0's rows)
         fe = model._mt_frontend = ResidentFrontEnd(step_obj, rset)
+        fe.aug_epoch = int(epoch)                      # (nothing is drawn before the first run())
     _epoch_start(step_obj, pg0, epoch, n_batches)
     for i in range(n_batches):
         fe.run()

@@ -391,6 +391,39 @@ int sed_gather_logmel_transform(const float* pool, const int64_t* clip_offset, c
                                 float* out_noisy, const float* tgt_pool, int tgt_elems, float* out_target, void* ws,
                                 size_t ws_bytes, int math_dtype, void* stream);
 
+/* ---- train-time batch augmentation -------------------------------------------------------------
+ * Mixup of features and targets, a circular time shift of features and strong targets, and SpecAugment-style time /
+ * frequency masks, applied to one gathered batch.  The reference has no such code: the definitions below are the
+ * project's own, and no external package's parity is claimed; pinned is exact (bitwise) agreement with an independent
+ * numpy float32 statement of them (tests/augment_np.py).
+ *   x [B][T][M]        fp32 features (gathered, log-scaled, padded, normalised; [B][1][T][M] is the same memory)
+ *   x_ema [B][T][M]    the teacher's noisy copy, or NULL (then out_x_ema is NULL too)
+ *   target [B][T3][NC] the encoded targets, or NULL (then out_target is NULL too and T3 / NC are ignored)
+ *   table [B][8]       device int32; the row of clip b is {partner, lambda_bits, shift_x, shift_y, f0, fw, t0, tw},
+ *                      lambda_bits the bit pattern of an fp32 lambda
+ * With r(s, n) = ((s mod n) + n) mod n, p_b = partner of b, s = the named shift column:
+ *   mix(A, b, t, ., s) = lambda_b (x) A[b, r(t - s_b, n), .]  (+)  (1 - lambda_b) (x) A[p_b, r(t - s_{p_b}, n), .]
+ *   out_x[b,t,m]      = 0                          if f0_b <= m < f0_b + fw_b  or  t0_b <= t < t0_b + tw_b
+ *                     = mix(x, b, t, m, shift_x)   otherwise                                    (n = T)
+ *   out_x_ema[b,t,m]  = the same with x_ema (same partner, lambda, shift and masks: only the noise differs)
+ *   out_target[b,u,c] = mix(target, b, u, c, shift_y)                     (n = T3; masks never touch targets)
+ * Rules:
+ *   - each clip is rolled by ITS OWN shift before mixing: the partner contributes its own shifted clip; the partner's
+ *     lambda and masks play no part;
+ *   - masks are applied last, in output coordinates; the fill value is 0.0f (the band mean after normalisation);
+ *   - (x), (+) and 1 - lambda are individually rounded fp32 operations, never contracted into an FMA;
+ *   - when p_b == b or lambda_b == 1.0f the partner is NOT READ and the value is the rolled clip's own, copied exactly;
+ *   - any int32 shift is legal and is reduced as above;
+ *   - mask intervals are clipped to the tensor; fw <= 0 / tw <= 0: no mask;
+ *   - partner is clamped to [0, B) inside the kernel, so no table content can address outside the batch;
+ *   - labels are mixed softly only (no clamp(a + b) mode).
+ * Output buffers must not overlap input buffers (the table included) or each other: the address ranges are checked
+ * and SED_ERR_BAD_ARG is returned before anything is launched.  16-byte loads / stores when M % 4 == 0 (NC % 4 == 0
+ * for the targets) and the bases are 16-byte aligned, a scalar path otherwise.  Limits: B <= 65535, T * M < 2^31,
+ * T3 * NC < 2^31.  One launch on `stream`, no allocation, no atomics, hipGraph-capturable. */
+int sed_batch_augment(const float* x, const float* x_ema, const float* target, const int32_t* table, int B, int T,
+                      int M, int T3, int NC, float* out_x, float* out_x_ema, float* out_target, void* stream);
+
 /* Resampling step of read_audio (utils/utils.py:175-193: librosa.resample(audio, orig_sr, target_sr),
  * res_type "kaiser_best" = resampy's windowed-sinc interpolation, then fix_length).
  *   x [n_clips][n_in] fp64 (soundfile.read returns float64; channels already averaged)

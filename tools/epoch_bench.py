@@ -3,6 +3,12 @@ drop-in feeding path - at DESED's sizes (1 262 weak / 14 412 unlabelled / 1 637 
 than `frames`).  Device-event timing; prints one JSON object (and writes it to --out).
 
   (a) one full epoch through resident.ResidentFrontEnd (the gather of batch k + 1 inside step k's hipGraph), ms / step
+  (a') the same epoch with an augmentation policy on the set (mixup of every clip, time shift, both masks: the gather goes
+      into staging buffers and sed_batch_augment writes the slot), alternated with the plain epoch in the same run: ms / step
+      of either (median of 5 rounds), their ratio and each leg's spread over the rounds, (max - min) / median (--only-aug: this
+      pair only).  Part of the default run too: a second resident set and 5 + 5 epochs per shape.  The two front-ends draw
+      their index tables alternately from numpy's global generator, so the plain leg's batches are not leg (a)'s - the same
+      pool and shapes, which is what the timing needs
   (b) the resident-batch step of the same shape (bench.py's mt-* leg: one batch in HBM, MeanTeacherStep.run() replayed)
   (c) 20 steps of the drop-in path: DataLoadDf-style dataset (np.load per clip) + features.get_transforms, num_workers=0,
       host collate, step.step
@@ -11,7 +17,7 @@ than `frames`).  Device-event timing; prints one JSON object (and writes it to -
       DataFrame route (get_predictions + compute_strong_metrics), sed_event_counts alone, and - next to them, in the same
       run - validate(..., psds=...) and sed_psds_counts alone at the same operating points (--only-e: this leg only)
 
-Usage: python tools/epoch_bench.py [--shapes 24:f32,64:bf16] [--only-a | --only-e] [--out FILE]"""
+Usage: python tools/epoch_bench.py [--shapes 24:f32,64:bf16] [--only-a | --only-aug | --only-e] [--out FILE]"""
 import argparse
 import json
 import os
@@ -28,6 +34,7 @@ if REPO not in sys.path:
 
 import bench                                                    # noqa: E402  (build_models / synthetic_batch of the mt-* legs)
 from dcase2019_task4_amd.features import Scaler, get_transforms  # noqa: E402
+from dcase2019_task4_amd.augment import AugmentPolicy  # noqa: E402
 from dcase2019_task4_amd.resident import ResidentFeatureSet, ResidentFrontEnd  # noqa: E402
 from dcase2019_task4_amd.train import MeanTeacherStep  # noqa: E402
 
@@ -80,6 +87,36 @@ def leg_a(rs, B, dtype):
     assert np.isfinite(st.meters()["loss"])
     st.close()
     return ms, n
+
+
+def leg_a_aug(rs, rs_aug, B, dtype, rounds=5):
+    """The plain and the augmented resident epoch, alternated: both front-ends are built and warmed first, then ``rounds``
+    times one full plain epoch and one full augmented epoch are timed back to back (device events)."""
+    fes = []
+    for r in (rs, rs_aug):
+        student, teacher = bench.build_models("cuda", seed=0, mfma_dtype=dtype)
+        st = MeanTeacherStep(student, teacher, B, T, 210 * 100 // 2, r.weak_mask, r.strong_mask, seed=1234)
+        fe = ResidentFrontEnd(st, r)
+        for _ in range(10):
+            fe.run()
+        fes.append((st, fe))
+    torch.cuda.synchronize()
+    n = len(rs)
+    plain, aug = [], []
+    for _ in range(rounds):
+        plain.append(event_ms(fes[0][1].run, n))
+        aug.append(event_ms(fes[1][1].run, n))
+    for st, _ in fes:
+        assert np.isfinite(st.meters()["loss"])
+        st.close()
+    mp, ma = float(np.median(plain)), float(np.median(aug))
+    return {"aug_policy": "mixup_alpha 0.2, mixup_prob 1, shift_std 8 label frames, freq_mask_max 8, time_mask_max 64",
+            "aug_rounds": rounds,
+            "a_plain_ms_per_step_rounds": [round(v, 4) for v in plain], "a_aug_ms_per_step_rounds": [round(v, 4) for v in aug],
+            "a_plain_alternated_ms_per_step": round(mp, 4), "a_aug_ms_per_step": round(ma, 4),
+            "a_aug_over_plain": round(ma / mp, 4),
+            "a_plain_spread_max_minus_min_over_median": round((max(plain) - min(plain)) / mp, 4),
+            "a_aug_spread_max_minus_min_over_median": round((max(aug) - min(aug)) / ma, 4)}
 
 
 def leg_b(B, dtype, n):
@@ -274,6 +311,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="24:f32,64:bf16")
     ap.add_argument("--only-a", action="store_true", help="leg (a) only (for a kernel trace of the resident epoch)")
+    ap.add_argument("--only-aug", action="store_true", help="leg (a') only: the plain and the augmented resident epoch, alternated")
     ap.add_argument("--only-e", action="store_true", help="leg (e) only: validation scoring")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -285,6 +323,8 @@ def main():
                                            "longer_than_frames": int((lengths > T).sum()), "frames": T,
                                            "bytes": int(lengths.sum()) * N_MELS * 4}, "legs": []}
     build_s = None
+    if a.only_aug:
+        result["command"] = f"python tools/epoch_bench.py --only-aug --shapes {a.shapes}"
     with tempfile.TemporaryDirectory() as tmp:
         for shape in ([] if a.only_e else a.shapes.split(",")):
             B, dtype = int(shape.split(":")[0]), shape.split(":")[1]
@@ -294,10 +334,18 @@ def main():
             torch.cuda.synchronize()
             build_s = build_s or round(time.perf_counter() - tb, 2)
             np.random.seed(0)
-            ms_a, n = leg_a(rs, B, dtype)
-            leg = {"B": B, "mfma_dtype": dtype, "batch_sizes": bs, "steps_per_epoch": n,
-                   "a_resident_epoch_ms_per_step": round(ms_a, 4)}
+            leg = {"B": B, "mfma_dtype": dtype, "batch_sizes": bs, "steps_per_epoch": len(rs)}
+            if not a.only_aug:
+                ms_a, n = leg_a(rs, B, dtype)
+                leg["a_resident_epoch_ms_per_step"] = round(ms_a, 4)
             if not a.only_a:
+                # the same pool with a policy (worst case for partner reads: every clip mixes); the two sets share nothing
+                rs_aug = ResidentFeatureSet.from_arrays(feats, tgts, SIZES, bs, frames=T, scaler=sc, augment_type="noise",
+                                                        augment=AugmentPolicy(mixup_alpha=0.2, mixup_prob=1.0, shift_std=8.0,
+                                                                              freq_mask_max=8, time_mask_max=64, seed=1))
+                leg.update(leg_a_aug(rs, rs_aug, B, dtype))
+                del rs_aug
+            if not a.only_a and not a.only_aug:
                 ms_b = leg_b(B, dtype, n)
                 ms_c, wall_c = leg_c(rs, feats, tgts, sc, B, dtype, tmp)
                 leg.update({"b_resident_batch_ms_per_step": round(ms_b, 4),
@@ -308,9 +356,9 @@ def main():
             print(json.dumps(leg), flush=True)
             del rs
             torch.cuda.empty_cache()
-        if not a.only_a and not a.only_e:
+        if not a.only_a and not a.only_e and not a.only_aug:
             result["d_get_predictions"] = leg_d(feats, sc, tmp)
-        if not a.only_a:
+        if not a.only_a and not a.only_aug:
             result["e_validation_scoring"] = leg_e(feats, sc)
             result["command"] = "python tools/epoch_bench.py" + (" --only-e" if a.only_e else f" --shapes {a.shapes}")
     result["pool"]["build_s"] = build_s
