@@ -53,6 +53,10 @@ _SIGS = {
     "sed_scaler_stats": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]),
     "sed_postprocess": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_int, C.c_void_p]),
+    "sed_stitch_decode_ws_bytes": (C.c_size_t, [C.c_longlong, C.c_int, C.c_int]),
+    "sed_stitch_tile_frames": (C.c_int, []),
+    "sed_stitch_decode": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_longlong,
+                                    _P, C.c_size_t, _P, _P]),
     "sed_event_counts": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P,
                                    C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P]),
     "sed_psds_counts": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P,

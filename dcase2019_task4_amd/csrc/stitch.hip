@@ -1,0 +1,331 @@
+#pragma clang fp contract(off)       // file-wide: the blend's products and sums are individually rounded (see augment.hip)
+// stitch.hip - long-recording inference: the posteriors of overlapping windows are blended into one timeline per recording,
+// then thresholded, median-filtered and run-length decoded over the WHOLE timeline (sed_stitch_decode; the definitions are
+// in include/dcase_sed.h and are the project's own - the reference scores 10-s clips only).
+//
+// A column (recording, class) has no length limit, so it is split along time: a workgroup owns ST_TILE timeline frames of
+// one recording, all classes (the NC floats of a frame are contiguous in the window posteriors and in the timeline).
+//   k_stitch_tile<VEC, 0>  blends its frames plus a halo of ST_HALO frames per side (or the reflection at a recording end)
+//                          into 0/1 decisions in LDS, median-filters them there (the true neighbours across tile edges),
+//                          writes timeline / binary, and counts the onsets of every class with wave ballots
+//   k_stitch_scan_cols     one wave per column: exclusive scan of the tile counts in place, the column's total
+//   k_stitch_scan_ptr      one workgroup: ev_ptr = exclusive scan of the column totals; capacity check
+//   k_stitch_tile<VEC, 1>  recomputes the tile and writes its (onset, offset) frames at ev_ptr[col] + rank
+// Onsets and offsets alternate along a column, so the offsets in front of a tile are the onsets in front of it minus one
+// when an event is open across the tile's first edge: one count per (tile, class) is enough.
+//
+// Where a tile lives: the tiles of recording r take slots slot0(r) + k, slot0(r) = floor(rec_frame0[r] / ST_TILE) + r.  That
+// is strictly increasing in (r, k) for increasing rec_frame0, needs no table of its own and at most
+// total / ST_TILE + n_rec + 1 slots; a workgroup finds its recording by bisection over rec_frame0, an empty slot returns.
+// Every table entry is validated before it is used as an index (st_rec): no table content can address outside
+// win_strong[0 .. rec_win0[n_rec]) or timeline[0 .. rec_frame0[n_rec]).  Integer results only depend on the inputs: no
+// float atomics, the only atomic is the OR into the error word.
+#include "common.h"
+#include "kernels.h"
+#include "post.h"
+
+#define ST_TILE 512          // timeline frames per workgroup
+#define ST_HALO 32           // 63 / 2 + 1: the widest median window's reach plus the neighbour the edge predicates read
+#define ST_THREADS 256
+#define ST_EXT (ST_TILE + 2 * ST_HALO)
+#define ST_FLT (ST_TILE + 2)  // filtered decisions of frames s - 1 .. e
+#define ST_MAXC 16
+
+__device__ __forceinline__ float st_mul(float a, float b) { return a * b; }
+__device__ __forceinline__ float st_add(float a, float b) { return a + b; }
+__device__ __forceinline__ float st_div(float a, float b) { return a / b; }      // correctly rounded (the compiler's default for HIP)
+
+struct StArgs {
+    const float* win_strong;
+    const int32_t* rec_win0;
+    const int64_t* rec_frame0;
+    const float* thr;
+    const int32_t* win;
+    float* timeline;
+    uint8_t* binary;
+    int64_t* ev_ptr;
+    int32_t* ev_pairs;
+    long long capacity;
+    int64_t* col_total;      // ws: [n_rec * NC]
+    int32_t* cnt;            // ws: [n_slots][NC] onsets per (tile, class); after the scan, the onsets in front of the tile
+    int32_t* err;
+    int n_rec, T3, NC, hop3, weighting, n_slots;
+};
+
+struct StRec {
+    long long f0;            // first timeline frame of the recording
+    int L3, w0, nw;          // its frames, first window, windows
+    int slot0, tiles;
+    int bad;                 // 0, or the err bits that keep the recording from being decoded
+};
+
+__device__ __forceinline__ StRec st_rec(const StArgs& a, int r) {
+    StRec R;
+    const long long f0 = a.rec_frame0[r], f1 = a.rec_frame0[r + 1], ft = a.rec_frame0[a.n_rec];
+    const long long w0 = a.rec_win0[r], w1 = a.rec_win0[r + 1], wt = a.rec_win0[a.n_rec];
+    R.bad = 0;
+    if (f0 < 0 || f1 <= f0 || f1 > ft || f1 - f0 > 0x7fffffffll - ST_EXT || w0 < 0 || w1 < w0 || w1 > wt) R.bad = 16;
+    R.f0 = f0;
+    R.L3 = R.bad ? 0 : (int)(f1 - f0);
+    R.w0 = (int)w0;
+    R.nw = R.bad ? 0 : (int)(w1 - w0);
+    const long long slot0 = f0 / ST_TILE + r;
+    R.tiles = (R.L3 + ST_TILE - 1) / ST_TILE;
+    if (!R.bad && slot0 + R.tiles > a.n_slots) { R.bad = 16; R.tiles = 0; }       // the workspace was sized for other tables
+    R.slot0 = R.bad ? 0 : (int)slot0;
+    // hop3 <= T3: the windows' ranges are contiguous, so the recording is covered iff the last window reaches its end
+    if (!R.bad && !(R.nw >= 1 && (long long)(R.nw - 1) * a.hop3 + a.T3 >= R.L3)) R.bad = 32;
+    return R;
+}
+
+// Blended posterior(s) of timeline frame u of recording R: class q (VEC = false) or classes 4q .. 4q + 3 (VEC = true).
+template <bool VEC>
+__device__ __forceinline__ f32x4 st_blend(const StArgs& a, const StRec& R, int u, int q) {
+    const int T3 = a.T3, hop3 = a.hop3, NC = a.NC;
+    const int j_lo = u >= T3 ? (u - T3) / hop3 + 1 : 0;                          // the windows j with 0 <= u - j hop3 < T3 ...
+    const int j_hi = min(u / hop3, R.nw - 1);                                    // ... that the recording owns
+    const int col = VEC ? 4 * q : q;
+    const float* src = a.win_strong + ((size_t)(R.w0 + j_lo) * T3 + (u - j_lo * hop3)) * NC + col;
+    f32x4 p = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (j_lo == j_hi) {                                                          // one window: its value, copied exactly
+        if (VEC) p = *(const f32x4*)src;
+        else p[0] = *src;
+        return p;
+    }
+    const ptrdiff_t step = (ptrdiff_t)(T3 - hop3) * NC;                          // window j + 1, local frame v - hop3
+    int wsum = 0;
+    for (int j = j_lo; j <= j_hi; ++j, src += step) {
+        const int v = u - j * hop3;
+        const int wi = a.weighting ? min(v + 1, T3 - v) : 1;
+        const float w = (float)wi;
+        wsum += wi;
+        if (VEC) {
+            const f32x4 x = *(const f32x4*)src;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) p[k] = st_add(p[k], st_mul(w, x[k]));
+        } else {
+            p[0] = st_add(p[0], st_mul(w, *src));
+        }
+    }
+    const float ws = (float)wsum;                                                // an integer below 2^24: exact
+#pragma unroll
+    for (int k = 0; k < (VEC ? 4 : 1); ++k) p[k] = st_div(p[k], ws);
+    return p;
+}
+
+template <bool VEC, int PASS>
+__global__ __launch_bounds__(ST_THREADS) void k_stitch_tile(StArgs a) {
+    __shared__ uint8_t raw[ST_MAXC * ST_EXT];
+    __shared__ uint8_t flt[ST_MAXC * ST_FLT];
+    __shared__ float s_thr[ST_MAXC];
+    __shared__ int s_win[ST_MAXC];       // 0: outside 1 .. 63, the column is not decoded
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NC = a.NC;
+    // ---- which recording, which tile (workgroup-uniform) -----------------------------------------------------------------
+    const long long g = blockIdx.x;
+    int lo_r = 0, hi_r = a.n_rec - 1;
+    while (lo_r < hi_r) {                                                        // the last r with slot0(r) <= g
+        const int mid = (lo_r + hi_r + 1) >> 1;
+        if (a.rec_frame0[mid] / ST_TILE + mid <= g) lo_r = mid;
+        else hi_r = mid - 1;
+    }
+    const int r = lo_r;
+    const StRec R = st_rec(a, r);
+    if (R.bad) return;                                                           // (k_stitch_scan_cols reports it)
+    const long long kt = g - R.slot0;
+    if (kt < 0 || kt >= R.tiles) return;                                         // an empty slot
+    const int L3 = R.L3, s = (int)kt * ST_TILE, e = min(s + ST_TILE, L3);
+    const int ext_lo = max(s - ST_HALO, 0), ext_n = min(e + ST_HALO, L3) - ext_lo;
+    if (tid < NC) {
+        const int w = a.win[tid];
+        s_thr[tid] = a.thr[tid];
+        s_win[tid] = (w >= 1 && w <= 63) ? w : 0;
+        if (PASS == 0 && kt == 0 && !(w >= 1 && w <= 63)) atomicOr(a.err, 8);
+    }
+    __syncthreads();
+    // ---- blend + decision: frames ext_lo .. ext_lo + ext_n - 1, all classes ------------------------------------------------
+    {
+        const int G = VEC ? NC >> 2 : NC;
+        float* tl = (PASS == 0 && a.timeline) ? a.timeline + (size_t)R.f0 * NC : nullptr;
+        for (int it = tid; it < ext_n * G; it += ST_THREADS) {
+            const int fl = it / G, q = it - fl * G, u = ext_lo + fl;
+            const f32x4 p = st_blend<VEC>(a, R, u, q);
+            if (VEC) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) raw[(4 * q + k) * ST_EXT + fl] = pp_decision(p[k], s_thr[4 * q + k]);
+                if (tl && u >= s && u < e) *(f32x4*)(tl + (size_t)u * NC + 4 * q) = p;
+            } else {
+                raw[q * ST_EXT + fl] = pp_decision(p[0], s_thr[q]);
+                if (tl && u >= s && u < e) tl[(size_t)u * NC + q] = p[0];
+            }
+        }
+    }
+    __syncthreads();
+    // ---- median filter of frames s - 1 .. e (post.h's rule; reflection only at the recording's two ends) --------------------
+    const int n_flt = e - s + 2;
+    for (int it = tid; it < NC * n_flt; it += ST_THREADS) {
+        const int c = it / n_flt, k = it - c * n_flt, t = s - 1 + k;
+        const int window = s_win[c];
+        uint8_t v = 0;
+        if (t >= 0 && t < L3 && window) {
+            const int lo = window / 2, need = window - window / 2;
+            const uint8_t* col = raw + c * ST_EXT - ext_lo;
+            int ones = 0;
+            for (int d = 0; d < window; ++d) ones += col[pp_reflect(t - lo + d, L3)];
+            v = ones >= need ? 1 : 0;
+        }
+        flt[c * ST_FLT + k] = v;
+    }
+    __syncthreads();
+    if (PASS == 0 && a.binary) {
+        uint8_t* bin = a.binary + (size_t)R.f0 * NC;
+        for (int it = tid; it < (e - s) * NC; it += ST_THREADS) {
+            const int fl = it / NC, c = it - fl * NC;
+            if (s_win[c]) bin[(size_t)(s + fl) * NC + c] = flt[c * ST_FLT + fl + 1];
+        }
+    }
+    // ---- onsets / offsets of the tile: one wave per class, 64 frames per ballot ---------------------------------------------
+    const size_t slot = (size_t)g * NC;
+    for (int c = wave; c < NC; c += ST_THREADS / 64) {
+        const uint8_t* f = flt + c * ST_FLT + 1;                                 // f[t - s], t = s - 1 .. e
+        const long long col = (long long)r * NC + c;
+        int n_on = 0, n_off = 0;
+        long long base = 0;
+        if (PASS == 1) {
+            n_on = a.cnt[slot + c];
+            n_off = n_on - ((f[-1] && f[0]) ? 1 : 0);                            // an event open across the tile's first edge
+            base = a.ev_ptr[col];
+        }
+        const int first = n_on;
+        for (int t0 = s; t0 < e; t0 += 64) {
+            const int t = t0 + lane;
+            const bool act = t < e && f[t - s];
+            const bool prev = act && f[t - s - 1];
+            const bool next = act && f[t - s + 1];
+            pp_emit_chunk(act, prev, next, t, lane, n_on, n_off, [&](int k, int frame, bool is_offset) {
+                if (PASS == 1) {
+                    const long long dst = base + k;
+                    if (dst >= 0 && dst < a.capacity) a.ev_pairs[2 * dst + (is_offset ? 1 : 0)] = frame;
+                }
+            });
+        }
+        if (PASS == 0 && lane == 0) a.cnt[slot + c] = n_on - first;
+    }
+}
+
+// One wave per column (recording, class): the tile counts become the onsets in front of each tile; the total goes to col_total.
+__global__ __launch_bounds__(ST_THREADS) void k_stitch_scan_cols(StArgs a) {
+    const int lane = threadIdx.x & 63;
+    const long long col = (long long)blockIdx.x * (ST_THREADS / 64) + (threadIdx.x >> 6);
+    if (col >= (long long)a.n_rec * a.NC) return;
+    const int r = (int)(col / a.NC), c = (int)(col - (long long)r * a.NC);
+    const StRec R = st_rec(a, r);
+    const int w = a.win[c];
+    if (R.bad && c == 0 && lane == 0) atomicOr(a.err, R.bad);
+    long long carry = 0;
+    if (!R.bad && w >= 1 && w <= 63) {
+        for (int k0 = 0; k0 < R.tiles; k0 += 64) {
+            const int k = k0 + lane;
+            int32_t* p = a.cnt + ((size_t)R.slot0 + k) * a.NC + c;
+            const int v = k < R.tiles ? *p : 0;
+            int incl = v;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int n = __shfl_up(incl, o);
+                if (lane >= o) incl += n;
+            }
+            if (k < R.tiles) *p = (int)carry + incl - v;
+            carry += __shfl(incl, 63);
+        }
+    }
+    if (lane == 0) a.col_total[col] = carry;
+}
+
+// ev_ptr = exclusive scan of the column totals (one workgroup; integer sums in a fixed order).
+__global__ __launch_bounds__(1024) void k_stitch_scan_ptr(StArgs a) {
+    __shared__ long long part[16];
+    __shared__ long long s_carry;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long n = (long long)a.n_rec * a.NC;
+    if (tid == 0) { s_carry = 0; a.ev_ptr[0] = 0; }
+    __syncthreads();
+    for (long long i0 = 0; i0 < n; i0 += 1024) {
+        const long long i = i0 + tid;
+        const long long v = i < n ? a.col_total[i] : 0;
+        long long incl = v;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const long long m = __shfl_up(incl, o);
+            if (lane >= o) incl += m;
+        }
+        if (lane == 63) part[wave] = incl;
+        __syncthreads();
+        long long before = s_carry;
+        for (int k = 0; k < wave; ++k) before += part[k];
+        if (i < n) a.ev_ptr[i + 1] = before + incl;
+        __syncthreads();
+        if (tid == 1023) s_carry = before + incl;
+        __syncthreads();
+    }
+    if (tid == 0 && s_carry > a.capacity) atomicOr(a.err, 2);
+}
+
+extern "C" int sed_stitch_tile_frames(void) { return ST_TILE; }
+
+static size_t st_ws_head(int n_rec, int NC) { return (size_t)n_rec * NC * sizeof(int64_t); }
+
+extern "C" size_t sed_stitch_decode_ws_bytes(long long total_frames, int n_rec, int nclass) {
+    if (total_frames < 1 || n_rec < 1 || nclass < 1 || nclass > ST_MAXC || total_frames * nclass >= (1ll << 31) ||
+        (long long)n_rec * nclass >= (1ll << 31)) {
+        sed_set_error("sed_stitch_decode_ws_bytes: need total_frames >= 1, n_rec >= 1, 1 <= nclass <= 16, total_frames * nclass < 2^31");
+        return 0;
+    }
+    const size_t n_slots = (size_t)(total_frames / ST_TILE) + n_rec + 1;
+    return st_ws_head(n_rec, nclass) + n_slots * nclass * sizeof(int32_t);
+}
+
+extern "C" int sed_stitch_decode(const float* win_strong, const int32_t* rec_win0, const int64_t* rec_frame0, int n_rec, int T3,
+                                 int NC, int hop3, int weighting, const float* thr, const int32_t* win, float* timeline,
+                                 uint8_t* binary, int64_t* ev_ptr, int32_t* ev_pairs, long long capacity, void* ws,
+                                 size_t ws_bytes, int32_t* err, void* stream) {
+    SED_CHECK_ARG(win_strong && rec_win0 && rec_frame0 && thr && win && ev_ptr && ev_pairs && ws && err,
+                  "sed_stitch_decode: null argument");
+    SED_CHECK_ARG(n_rec >= 1 && NC >= 1 && NC <= ST_MAXC && (long long)n_rec * NC < (1ll << 31),
+                  "sed_stitch_decode: need n_rec >= 1, 1 <= NC <= 16 and n_rec * NC < 2^31");
+    SED_CHECK_ARG(T3 >= 1 && T3 <= 4096, "sed_stitch_decode: need 1 <= T3 <= 4096 (the taper's weight sum stays exact in fp32)");
+    SED_CHECK_ARG(hop3 >= 1 && hop3 <= T3, "sed_stitch_decode: need 1 <= hop3 <= T3");
+    SED_CHECK_ARG(weighting == 0 || weighting == 1, "sed_stitch_decode: weighting is 0 (uniform) or 1 (taper)");
+    SED_CHECK_ARG(capacity >= 0, "sed_stitch_decode: capacity must be >= 0");
+    SED_CHECK_ARG(((uintptr_t)ws % 8) == 0, "sed_stitch_decode: ws must be 8-byte aligned");
+    const size_t head = st_ws_head(n_rec, NC), per_slot = (size_t)NC * sizeof(int32_t);
+    if (ws_bytes < head + (size_t)(n_rec + 1) * per_slot) {
+        sed_set_error("sed_stitch_decode: workspace of %zu bytes is too small (sed_stitch_decode_ws_bytes)", ws_bytes);
+        return SED_ERR_WORKSPACE;
+    }
+    const size_t n_slots = (ws_bytes - head) / per_slot;
+    SED_CHECK_ARG(n_slots < (1ull << 31), "sed_stitch_decode: workspace too large for the tile grid");
+    // the slots bound the frames the tables may hold: sum L3 * NC < 2^31
+    SED_CHECK_ARG((long long)(n_slots - n_rec - 1) * ST_TILE * NC < (1ll << 31) + (long long)ST_TILE * NC,
+                  "sed_stitch_decode: sum L3 * NC must stay below 2^31");
+    StArgs a = {};
+    a.win_strong = win_strong; a.rec_win0 = rec_win0; a.rec_frame0 = rec_frame0; a.thr = thr; a.win = win;
+    a.timeline = timeline; a.binary = binary; a.ev_ptr = ev_ptr; a.ev_pairs = ev_pairs; a.capacity = capacity;
+    a.col_total = (int64_t*)ws;
+    a.cnt = (int32_t*)((char*)ws + head);
+    a.err = err;
+    a.n_rec = n_rec; a.T3 = T3; a.NC = NC; a.hop3 = hop3; a.weighting = weighting; a.n_slots = (int)n_slots;
+    const bool vec = NC % 4 == 0 && ((uintptr_t)win_strong % 16) == 0 && (!timeline || ((uintptr_t)timeline % 16) == 0);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 tiles((unsigned)n_slots), thr256(ST_THREADS);
+    if (vec) hipLaunchKernelGGL((k_stitch_tile<true, 0>), tiles, thr256, 0, st, a);
+    else hipLaunchKernelGGL((k_stitch_tile<false, 0>), tiles, thr256, 0, st, a);
+    SED_CHECK_LAUNCH();
+    const long long n_cols = (long long)n_rec * NC;
+    hipLaunchKernelGGL(k_stitch_scan_cols, dim3((unsigned)((n_cols + 3) / 4)), thr256, 0, st, a);
+    SED_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_stitch_scan_ptr, dim3(1), dim3(1024), 0, st, a);
+    SED_CHECK_LAUNCH();
+    if (vec) hipLaunchKernelGGL((k_stitch_tile<true, 1>), tiles, thr256, 0, st, a);
+    else hipLaunchKernelGGL((k_stitch_tile<false, 1>), tiles, thr256, 0, st, a);
+    SED_CHECK_LAUNCH();
+    return SED_OK;
+}

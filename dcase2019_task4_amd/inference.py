@@ -5,6 +5,12 @@ The reference runs ONE clip per forward and post-processes it on the host (thres
 run-length decode) - 1 168 + ~400 forwards per epoch.  Here clips go through the eval-mode CRNN ``batch_size`` at a
 time and ``sed_postprocess`` thresholds, median-filters and run-length-decodes the whole batch on the device; the host
 only assembles the event table.  There is no CPU fallback: the model and its inputs live on the GPU.
+
+Recordings longer than one clip: ``LongRecordingSet`` (longrec.py) holds them as overlapping windows and
+``get_long_predictions`` blends the windows' posteriors and decodes each recording's whole timeline with one
+``sed_stitch_decode`` call.  Out of scope there: scoring long recordings (``sed_event_counts`` / ``sed_psds_counts`` keep
+T <= 2048 and 64 events per column; the long path's event table can still be fed to ``compute_strong_metrics`` within those
+limits), recording-level weak tags, and windows for training.  ``get_predictions`` itself is unchanged.
 """
 import ctypes as C
 
@@ -13,6 +19,7 @@ import pandas as pd
 import torch
 
 from . import _lib
+from .longrec import WEIGHTINGS, LongRecordingSet, check_hop_frames, default_hop_frames, window_plan      # noqa: F401
 
 
 class _Cfg:
@@ -129,3 +136,125 @@ def get_predictions(model, valid_dataset, decoder, pooling_time_ratio=1, save_pr
     if save_predictions is not None:
         prediction_df.to_csv(save_predictions, index=False, sep="\t")
     return prediction_df
+
+
+STITCH_ERR_BITS = {2: "more events than the capacity of ev_pairs", 8: "a median window outside 1 .. 63",
+                   16: "malformed rec_win0 / rec_frame0 tables", 32: "a recording with too few windows to cover it"}
+
+
+def _per_class(value, nclass, dtype, what):
+    a = np.asarray(value, dtype=dtype).reshape(-1)
+    if a.size == 1:
+        a = np.repeat(a, nclass)
+    if a.size != nclass:
+        raise ValueError(f"{what} must be a scalar or a sequence of {nclass} values, got {a.size}")
+    return np.ascontiguousarray(a)
+
+
+def stitch_decode(win_strong, rec_win0, rec_frame0, total_frames, hop3, threshold=0.5, median_window=5, weighting="taper",
+                  capacity=None, want_timeline=True, want_binary=False):
+    """``sed_stitch_decode`` on window posteriors [n_win, T3, nclass] (cuda float32) with the device tables ``rec_win0``
+    [n_rec + 1] int32 / ``rec_frame0`` [n_rec + 1] int64 of ``total_frames`` timeline frames in all: everything stays on the
+    device and nothing synchronises.  Returns a dict: ``ev_ptr`` [n_rec * nclass + 1] int64, ``ev_pairs`` [capacity, 2] int32,
+    ``err`` [1] int32 (non-zero: the outputs are invalid, ``STITCH_ERR_BITS``), ``timeline`` / ``binary``
+    [total_frames, nclass] or None.  ``threshold`` / ``median_window``: scalars, per-class sequences or device tensors."""
+    if win_strong.device.type != "cuda":
+        raise _lib.SedError("stitch_decode needs GPU tensors (no CPU fallback)")
+    if weighting not in WEIGHTINGS:
+        raise ValueError(f"weighting must be one of {sorted(WEIGHTINGS)}, got {weighting!r}")
+    dev = win_strong.device
+    win_strong = win_strong.contiguous().float()
+    n_win, T3, NC = win_strong.shape
+    n_rec = rec_win0.numel() - 1
+    total = int(total_frames)
+    if total * NC >= 2 ** 31:
+        raise ValueError(f"{total} timeline frames x {NC} classes: the product must stay below 2^31")
+    thr = threshold if torch.is_tensor(threshold) else torch.from_numpy(_per_class(threshold, NC, np.float32, "threshold")).to(dev)
+    win = (median_window if torch.is_tensor(median_window)
+           else torch.from_numpy(_per_class(median_window, NC, np.int32, "median_window")).to(dev))
+    if capacity is None:
+        capacity = NC * ((total + n_rec) // 2)              # >= sum over recordings of NC * ceil(L3 / 2)
+    l = _lib.lib()
+    out = {"ev_ptr": torch.empty(n_rec * NC + 1, dtype=torch.int64, device=dev),
+           "ev_pairs": torch.empty(max(int(capacity), 1), 2, dtype=torch.int32, device=dev),
+           "err": torch.zeros(1, dtype=torch.int32, device=dev),
+           "timeline": torch.empty(total, NC, dtype=torch.float32, device=dev) if want_timeline else None,
+           "binary": torch.empty(total, NC, dtype=torch.uint8, device=dev) if want_binary else None}
+    ws = _lib.scratch(l.sed_stitch_decode_ws_bytes(total, n_rec, NC), dev)
+    _lib.check(l.sed_stitch_decode(_lib.ptr(win_strong), _lib.ptr(rec_win0), _lib.ptr(rec_frame0), n_rec, T3, NC, int(hop3),
+                                   WEIGHTINGS[weighting], _lib.ptr(thr), _lib.ptr(win), _lib.ptr(out["timeline"]),
+                                   _lib.ptr(out["binary"]), _lib.ptr(out["ev_ptr"]), _lib.ptr(out["ev_pairs"]), int(capacity),
+                                   _lib.ptr(ws), ws.numel(), _lib.ptr(out["err"]), _lib.stream_ptr()), "sed_stitch_decode")
+    return out
+
+
+def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=None, save_predictions=None, batch_size=64,
+                         cfg=None, threshold=0.5, median_window=None, weighting="taper", return_posteriors=False):
+    """Events of recordings of any lengths (a ``LongRecordingSet``): the windows go through the eval-mode model
+    ``batch_size`` at a time, their strong posteriors are blended into one timeline per recording (``weighting``: "taper"
+    or "uniform"), and ONE threshold, median filter and run-length decode runs over each whole timeline
+    (``sed_stitch_decode``), followed by one host copy of the event table.
+
+    Returns the DataFrame of ``get_predictions`` (event_label, onset, offset, filename; seconds by its formula
+    ``frame * pooling_time_ratio / (sample_rate / hop_length)`` from ``cfg``; the same TSV when ``save_predictions`` is
+    given), rows ordered (recording, class, time).  ``threshold`` / ``median_window`` (default ``cfg.median_window``): a
+    scalar or one value per class.  ``decoder_or_labels``: ``many_hot_encoder.decode_strong`` (the labels are its owner's)
+    or a plain list of labels.  ``return_posteriors=True``: also the list of per-recording [L3_r, nclass] device views of
+    the blended timeline and the [n_win, T3, nclass] window posteriors."""
+    if not isinstance(long_set, LongRecordingSet):
+        raise TypeError(f"long_set must be a LongRecordingSet, got {type(long_set).__name__}")
+    cfg = cfg or _Cfg
+    labels = getattr(getattr(decoder_or_labels, "__self__", None), "labels", None)
+    if labels is None:
+        if callable(decoder_or_labels):
+            raise ValueError("decoder_or_labels: a decode_strong bound to an object with .labels, or a list of labels")
+        labels = list(decoder_or_labels)
+    pool = long_set.pooling_time_ratio if pooling_time_ratio is None else int(pooling_time_ratio)
+    if pool != long_set.pooling_time_ratio:
+        raise ValueError(f"pooling_time_ratio {pool} against a set built with {long_set.pooling_time_ratio}")
+    dev = next(model.parameters()).device
+    if dev.type != "cuda":
+        raise _lib.SedError("get_long_predictions needs the model on the GPU (no CPU fallback)")
+    NC = len(labels)
+    thr = _per_class(threshold, NC, np.float32, "threshold")
+    win = _per_class(cfg.median_window if median_window is None else median_window, NC, np.int32, "median_window")
+    was_training = model.training
+    model.eval()
+    win_strong = None
+    try:
+        with torch.no_grad():
+            for i0, idx, x in eval_batches(long_set, batch_size, dev):
+                strong, _ = model(x)
+                if win_strong is None:
+                    if tuple(strong.shape[1:]) != (long_set.T3, NC):
+                        raise ValueError(f"the model gives {tuple(strong.shape[1:])} per window, the set and the labels "
+                                         f"{(long_set.T3, NC)}")
+                    win_strong = torch.empty(long_set.n_clips, long_set.T3, NC, dtype=torch.float32, device=dev)
+                win_strong[i0:i0 + len(idx)].copy_(strong)
+            out = stitch_decode(win_strong, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3, thr, win,
+                                weighting, long_set.capacity(NC), want_timeline=return_posteriors)
+    finally:
+        model.train(was_training)
+    err = int(out["err"].item())
+    if err:
+        raise _lib.SedError("sed_stitch_decode reported err " + ", ".join(f"bit {b} ({t})" for b, t in STITCH_ERR_BITS.items()
+                                                                          if err & b) + f" (err = {err})")
+    ev_ptr = out["ev_ptr"].cpu().numpy()
+    ev = out["ev_pairs"][:int(ev_ptr[-1])].cpu().numpy()
+    per_col = np.diff(ev_ptr)
+    col = np.repeat(np.arange(per_col.size), per_col)
+    rec, cls = col // NC, col % NC
+    per_rec = per_col.reshape(long_set.n_rec, NC).sum(1)
+    index = np.arange(len(col)) - np.repeat(np.r_[0, np.cumsum(per_rec)[:-1]], per_rec)     # 0 .. k - 1 per recording
+    prediction_df = pd.DataFrame({"event_label": np.asarray(labels, dtype=object)[cls],
+                                  "onset": ev[:, 0].astype(np.int64), "offset": ev[:, 1].astype(np.int64),
+                                  "filename": np.asarray(long_set.filenames, dtype=object)[rec]}, index=index,
+                                 columns=["event_label", "onset", "offset", "filename"])
+    prediction_df.onset = prediction_df.onset * pool / (cfg.sample_rate / cfg.hop_length)
+    prediction_df.offset = prediction_df.offset * pool / (cfg.sample_rate / cfg.hop_length)
+    if save_predictions is not None:
+        prediction_df.to_csv(save_predictions, index=False, sep="\t")
+    if not return_posteriors:
+        return prediction_df
+    f0 = long_set.rec_frame0_host
+    return prediction_df, [out["timeline"][int(f0[r]):int(f0[r + 1])] for r in range(long_set.n_rec)], win_strong

@@ -455,6 +455,56 @@ int sed_postprocess(const float* strong, int n_clips, int T, int nclass, float t
                     int median_window, uint8_t* binary, int32_t* ev_count, int32_t* ev_pairs,
                     int max_events, void* stream);
 
+/* ---- long-recording inference: blend of overlapping windows + decode of the whole timeline --------
+ * A recording longer than one clip is cut into overlapping windows of T3 label frames, hop3 label frames apart; every
+ * window goes through the forward on its own.  sed_stitch_decode blends the windows' strong posteriors into one
+ * timeline per recording and runs ONE threshold, median filter and run-length decode over it.  The reference scores
+ * 10-s clips only: the definitions below are the project's own; pinned is exact (bitwise for the blend) agreement with
+ * an independent numpy float32 statement of them (tests/stitch_np.py) and with scipy / the restated dcase_util decode.
+ *   win_strong [n_win][T3][NC]  fp32 window posteriors
+ *   rec_win0   [n_rec + 1]      device int32: recording r owns windows rec_win0[r] .. rec_win0[r + 1] - 1, in time order;
+ *                               n_win = rec_win0[n_rec]
+ *   rec_frame0 [n_rec + 1]      device int64: recording r owns timeline frames rec_frame0[r] .. rec_frame0[r + 1] - 1
+ *                               (L3_r of them); window j of a recording starts at its frame j * hop3
+ *   thr [NC], win [NC]          device: per-class threshold (fp32) and median window (int32, 1 .. 63)
+ * Blend.  Frame u of a recording is covered by its windows j with 0 <= v = u - j * hop3 < T3, taken in increasing j;
+ *   weighting 0 (uniform): w = 1;  weighting 1 (taper): w = min(v + 1, T3 - v) (an integer held as fp32);
+ *   P[u, c] = (sum_j w_j (x) p_j[v_j, c]) (/) (sum_j w_j): the numerator a sequential fp32 sum from 0.0f in increasing j,
+ *   every product, sum and the division an individually rounded fp32 operation (nothing contracted into an FMA, the
+ *   division correctly rounded); the weight sum is an exact integer.
+ *   A frame covered by exactly ONE window takes that window's value copied exactly (no multiply, no divide): a
+ *   single-window recording's timeline is its window's posteriors bit for bit.
+ *   A recording whose windows do not cover all of its frames (inconsistent tables) raises err bit 32 and is not decoded.
+ * Decode, per column (recording, class c): P > thr[c] -> scipy's median filter of win[c] frames, origin 0 ->
+ *   find_contiguous_regions: the rules of sed_postprocess (one code, csrc/post.h).  The filter reflects at the
+ *   recording's two ends only (repeatedly when the window is longer than the column).
+ * Outputs.
+ *   timeline [sum L3][NC]  fp32 blended posteriors, or NULL
+ *   binary   [sum L3][NC]  uint8 filtered decisions, or NULL
+ *   ev_ptr   [n_rec * NC + 1] int64 CSR offsets, column = rec * NC + c, columns in index order: ALWAYS the true counts
+ *   ev_pairs [capacity][2] int32 (onset, exclusive offset) in timeline frames of the recording, in time order
+ *   err      one int32, OR-ed (zero it first), bits as in sed_event_counts where they exist there:
+ *              2 = more than `capacity` events in all: nothing is written at or beyond capacity and ev_pairs must be
+ *                  treated as invalid (never a silently truncated table); capacity = sum_r NC * ceil(L3_r / 2) cannot overflow
+ *              8 = a window outside 1 .. 63: that class is not decoded
+ *             16 = malformed rec_win0 / rec_frame0 (not increasing, outside their own totals, or more tiles than the
+ *                  workspace was sized for): the recording is not decoded
+ *             32 = a recording with too few windows to cover it: not decoded
+ *            No table content can make a kernel address outside win_strong [0, rec_win0[n_rec]) or the outputs
+ *            [0, rec_frame0[n_rec]).  A caller must treat every output as invalid when err != 0.
+ *   ws       sed_stitch_decode_ws_bytes(sum L3, n_rec, NC) bytes, 8-byte aligned: the per-tile onset counts
+ * The work is split along time: a workgroup owns sed_stitch_tile_frames() frames of one recording plus a halo of at
+ * most 63 / 2 + 1 frames per side; a count pass, two scans and a write pass (four launches on `stream`).  No host
+ * synchronisation, no allocation, no float atomics, integer results bit-reproducible, hipGraph-capturable.  16-byte
+ * accesses when NC % 4 == 0 and win_strong / timeline are 16-byte aligned, a scalar path otherwise.
+ * Limits: sum L3 * NC < 2^31, NC <= 16, 1 <= hop3 <= T3 <= 4096 (the taper's weight sum stays exact). */
+size_t sed_stitch_decode_ws_bytes(long long total_frames, int n_rec, int nclass);
+int sed_stitch_tile_frames(void);
+int sed_stitch_decode(const float* win_strong, const int32_t* rec_win0, const int64_t* rec_frame0, int n_rec, int T3,
+                      int NC, int hop3, int weighting, const float* thr, const int32_t* win, float* timeline,
+                      uint8_t* binary, int64_t* ev_ptr, int32_t* ev_pairs, long long capacity, void* ws,
+                      size_t ws_bytes, int32_t* err, void* stream);
+
 /* ---- validation scoring ------------------------------------------------------------------------
  * Replaces, after get_predictions, the host-side scoring of the epoch loop (baseline/main.py:328-352):
  *   compute_strong_metrics(predictions, valid_synth_df) (evaluation_measures.py:234-246) = sed_eval's
