@@ -61,6 +61,12 @@ _SIGS = {
                                    C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P]),
     "sed_psds_counts": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P,
                                   C.c_double, C.c_double, C.c_double, _P, _P, _P, _P]),
+    "sed_long_score_ws_bytes": (C.c_size_t, [C.c_longlong, C.c_longlong, C.c_int, C.c_int]),
+    "sed_long_tile_events": (C.c_int, []),
+    "sed_long_event_counts": (C.c_int, [_P, _P, C.c_double, C.c_double, _P, _P, C.c_longlong, _P, _P, _P, C.c_longlong, C.c_int,
+                                        C.c_int, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "sed_long_psds_counts": (C.c_int, [_P, _P, C.c_double, C.c_double, _P, _P, C.c_longlong, _P, _P, _P, C.c_longlong, C.c_int,
+                                       C.c_int, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, C.c_size_t, _P]),
     "sed_weak_counts": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
     "sed_version": (C.c_int, []),
     "sed_param_count": (C.c_int, [C.POINTER(SedDims)]),

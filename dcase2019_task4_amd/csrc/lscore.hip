@@ -1,0 +1,622 @@
+// lscore.hip - scoring of long recordings on the device: event-based, segment-based and PSDS counts of (recording, class)
+// columns of ANY length (sed_long_event_counts, sed_long_psds_counts; the definitions are those of score.hip, stated in
+// include/dcase_sed.h, without the limit of 64 events per column).  The estimated events are sed_stitch_decode's table
+// (ev_ptr / ev_pairs, frames) or CSR fp64 seconds; both sides of a column are sorted by onset.
+//
+// Every launch has one kind of worker and no data passes between workgroups inside a launch:
+//   k_ls_prep      one workgroup per (column, side): validates the CSR offsets, turns frames into seconds, checks that the
+//                  onsets do not decrease and writes pmax[i] = max(offset[0 .. i]) (a workgroup scan, 1024 events per step);
+//                  the only pass that walks a column in sequence
+//   k_ls_match     one wave per tile of LS_TILE reference events.  "i starts a cluster" is a local test (two bisections in
+//                  the estimated onsets), so a wave finds the clusters that START in its tile with one ballot, their ends with
+//                  a second ballot over the next tile (further ones only on the error path), and solves each with the augmenting-path ballot search of
+//                  k_event_counts (score.hip; a second copy of that loop: the two have different operand sources)
+//   k_ls_segments  one thread per segment: segment s is covered iff the last event whose first segment is <= s has
+//                  seg(pmax) > s - two bisections, no bitmap, no events x segments loop
+//   k_lp_detect    one thread per detection: DTC and, for the non-relevant ones, CTTC against every other class
+//   k_lp_truth     one thread per ground truth: GTC over the relevant detections
+//   k_ls_final / k_lp_final   per-column outputs and the class totals
+// The PSDS sums skip events that cannot overlap (bisection on the onsets for the upper end, on pmax for the lower end):
+// every skipped term is +0.0 and the sum starts at 0.0, so the bits are those of the full sequential sum.
+// Counts are integers, the atomics are integer atomics: results are bit-reproducible.  Every offset is validated against the
+// capacities the caller passed before it is used as an index.
+#pragma clang fp contract(off)       // seconds are formed as (double)frame * num / den, exactly the host's two operations
+#include "common.h"
+#include "kernels.h"
+
+#define LS_TILE 64                   // reference events per wave of k_ls_match: one lane / one mask bit each
+#define LS_MAXEV 64                  // events per cluster and side
+#define LS_MAXSEG 65536              // segments per file
+#define LS_MAXNC 16
+#define LS_CW 20                     // int32 counters per column: [0] Ntp, [1..3] segment tp / fp / fn, [4] k_ls_match's err bits; PSDS: [0 .. 2 + NC)
+#define LS_PREP_THREADS 1024
+#define LS_SEG_SPLIT 16              // workgroups of 256 segments per column and step
+
+struct LsArgs {
+    const int64_t* est_ptr; const int32_t* ev_pairs; double num, den;
+    const double *est_on, *est_off;  // the given seconds, or the workspace copies of the frames
+    const int64_t* ref_ptr; const double *ref_on, *ref_off;
+    long long est_cap, ref_cap;
+    int n_rec, NC, n_slots;
+    double t_collar, pct, res, dtc, gtc, cttc;
+    int32_t* flags;                  // ws [ncols][2]: err bits of (column, side), written by k_ls_prep
+    int32_t* cnt;                    // ws [ncols][LS_CW]
+    double *ws_on, *ws_off;          // ws [est_cap] each (frames mode)
+    double *est_pmax, *ref_pmax;     // ws [est_cap], [ref_cap]
+    uint8_t* rel;                    // ws [est_cap]: detection is relevant (PSDS)
+    int32_t *out_a, *out_b;          // ev_counts / seg_counts, or columns / unused
+    unsigned long long *tot_a, *tot_b;
+    int32_t* err;
+};
+
+__device__ __forceinline__ int ls_lane_read(int v, int src) {
+    return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(src));
+}
+// segment index of a time, clamped to [0, LS_MAXSEG + 1] (NaN -> 0) so that the cast is defined
+__device__ __forceinline__ int ls_seg_index(double x) {
+    return !(x > 0.0) ? 0 : (x > (double)LS_MAXSEG ? LS_MAXSEG + 1 : (int)x);
+}
+// validated range of a column: false (and an empty range) when the offsets are malformed
+__device__ __forceinline__ bool ls_range(const int64_t* ptr, long long col, long long cap, long long& p0, int& n) {
+    const long long a = ptr[col], b = ptr[col + 1];
+    const bool ok = a >= 0 && b >= a && b <= cap;
+    p0 = ok ? a : 0;
+    n = ok ? (int)(b - a) : 0;
+    return ok;
+}
+
+__global__ __launch_bounds__(LS_PREP_THREADS) void k_ls_prep(LsArgs a) {
+    __shared__ double part[LS_PREP_THREADS / 64];
+    __shared__ double s_carry;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long col = blockIdx.x;
+    const int side = blockIdx.y;                                     // 0: estimated, 1: reference
+    const bool frames = side == 0 && a.ev_pairs != nullptr;
+    long long p0;
+    int n, flags = 0;
+    if (!ls_range(side ? a.ref_ptr : a.est_ptr, col, side ? a.ref_cap : a.est_cap, p0, n)) flags = 16;
+    const double* src_on = side ? a.ref_on : a.est_on;
+    const double* src_off = side ? a.ref_off : a.est_off;
+    double* pmax = side ? a.ref_pmax : a.est_pmax;
+    if (tid == 0) s_carry = -INFINITY;
+    if (side == 0)
+        for (int i = tid; i < LS_CW; i += LS_PREP_THREADS) a.cnt[col * LS_CW + i] = 0;
+    __syncthreads();
+    const double num = a.num, den = a.den;
+    int unsorted = 0;
+    for (int k0 = 0; k0 < n; k0 += LS_PREP_THREADS) {
+        const int k = k0 + tid;
+        const bool valid = k < n;
+        const long long i = p0 + k;
+        double on = 0.0, off = -INFINITY;
+        if (valid) {
+            double prev;
+            if (frames) {
+                on = (double)a.ev_pairs[2 * i] * num / den;
+                off = (double)a.ev_pairs[2 * i + 1] * num / den;
+                prev = k > 0 ? (double)a.ev_pairs[2 * i - 2] * num / den : on;
+                a.ws_on[i] = on;
+                a.ws_off[i] = off;
+            } else {
+                on = src_on[i];
+                off = src_off[i];
+                prev = k > 0 ? src_on[i - 1] : on;
+            }
+            unsorted |= on < prev;
+        }
+        double incl = off;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const double m = __shfl_up(incl, o);
+            if (lane >= o) incl = fmax(incl, m);
+        }
+        if (lane == 63) part[wave] = incl;
+        __syncthreads();
+        double v = s_carry;
+        for (int w = 0; w < wave; ++w) v = fmax(v, part[w]);
+        v = fmax(v, incl);
+        if (valid) pmax[i] = v;
+        __syncthreads();
+        if (tid == LS_PREP_THREADS - 1) s_carry = v;
+        __syncthreads();
+    }
+    if (__syncthreads_or(unsorted)) flags |= 64;
+    if (tid == 0) {
+        a.flags[col * 2 + side] = flags;
+        if (flags) atomicOr(a.err, flags);
+    }
+}
+
+// first j in [0, n) with !(x[j] far below r), i.e. the number of j with r - x[j] > tol (x sorted)
+__device__ __forceinline__ int ls_count_below(const double* x, int n, double r, double tol) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (r - x[mid] > tol) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+// first j in [0, n] with x[j] - r > tol (x sorted)
+__device__ __forceinline__ int ls_first_above(const double* x, int n, double r, double tol) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (x[mid] - r > tol) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+
+// A cut in front of reference i is a pair (i, j): the first i references and the first j estimated events lie before it.  It
+// is valid iff jlo(i) <= j <= jhi(i), jlo(i) = first j with E[j] - R[i - 1] > t_collar, jhi(i) = number of j with
+// R[i] - E[j] > t_collar - the differences are formed as the compatibility test forms them, so that no pair the test accepts
+// can straddle a cut whatever the rounding.  The cluster of references i0 .. i1 - 1 (i0, i1 consecutive indices with a
+// valid cut) holds the estimated events jhi(i0) .. jlo(i1) - 1; estimated events outside these ranges match nothing.
+__global__ __launch_bounds__(256) void k_ls_match(LsArgs a) {
+    const int lane = threadIdx.x & 63;
+    const long long g = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (g >= a.n_slots) return;
+    const long long ncols = (long long)a.n_rec * a.NC;
+    long long lo_c = 0, hi_c = ncols - 1;
+    while (lo_c < hi_c) {                                            // the last column with slot0(col) <= g
+        const long long mid = (lo_c + hi_c + 1) >> 1;
+        if (a.ref_ptr[mid] / LS_TILE + mid <= g) lo_c = mid;
+        else hi_c = mid - 1;
+    }
+    const long long col = lo_c;
+    if (a.flags[col * 2] | a.flags[col * 2 + 1]) return;             // not scored (k_ls_prep reported it)
+    long long pr, pe;
+    int n_ref, n_est;
+    ls_range(a.ref_ptr, col, a.ref_cap, pr, n_ref);
+    ls_range(a.est_ptr, col, a.est_cap, pe, n_est);
+    const long long kt = g - (pr / LS_TILE + col);
+    if (kt < 0 || kt * LS_TILE >= n_ref) return;
+    const int i_base = (int)kt * LS_TILE;
+    const double* R = a.ref_on + pr;
+    const double* Roff = a.ref_off + pr;
+    const double* E = a.est_on + pe;
+    const double* Eoff = a.est_off + pe;
+    const double tc = a.t_collar;
+    // lane l: reference i_base + l (first ballot) and i_base + 64 + l (second); index n_ref is the column's end
+    int jlo[2], jhi[2];
+    unsigned long long starts[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int i = i_base + h * LS_TILE + lane;
+        bool bnd = false;
+        jlo[h] = jhi[h] = 0;
+        if (i <= n_ref) {
+            jlo[h] = i > 0 ? ls_first_above(E, n_est, R[i - 1], tc) : 0;
+            jhi[h] = i < n_ref ? ls_count_below(E, n_est, R[i], tc) : n_est;
+            bnd = jlo[h] <= jhi[h];
+        }
+        starts[h] = __ballot(bnd);
+    }
+    unsigned long long todo = starts[0];
+    if (n_ref - i_base < 64) todo &= (1ull << (n_ref - i_base)) - 1;     // a cluster starts at a reference, not at the end
+    int ntp = 0, flags = 0;
+    while (todo) {
+        const int s = __ffsll((long long)todo) - 1;
+        todo &= todo - 1;
+        const unsigned long long later = starts[0] & ((~0ull << s) << 1);
+        int nr, j1;
+        if (later) {
+            const int t = __ffsll((long long)later) - 1;
+            nr = t - s;
+            j1 = ls_lane_read(jlo[0], t);
+        } else if (starts[1]) {
+            const int t = __ffsll((long long)starts[1]) - 1;
+            nr = 64 + t - s;
+            j1 = ls_lane_read(jlo[1], t);
+        } else {                               // more than 64 references (bit 1): walk on to the cluster's end for bit 2
+            nr = 0;
+            j1 = 0;
+            for (int base = i_base + 2 * LS_TILE; nr == 0; base += LS_TILE) {       // ends: index n_ref is always a cut
+                const int i = base + lane;
+                const int jl = i <= n_ref ? ls_first_above(E, n_est, R[i - 1], tc) : 0;
+                const int jh = i < n_ref ? ls_count_below(E, n_est, R[i], tc) : n_est;
+                const unsigned long long m = __ballot(i <= n_ref && jl <= jh);
+                if (m) {
+                    const int t = __ffsll((long long)m) - 1;
+                    nr = base + t - (i_base + s);
+                    j1 = ls_lane_read(jl, t);
+                }
+            }
+        }
+        const int j0 = ls_lane_read(jhi[0], s);
+        const int ne = j1 - j0;
+        if (nr > LS_MAXEV) flags |= 1;
+        if (ne > LS_MAXEV) flags |= 2;
+        if (nr > LS_MAXEV || ne > LS_MAXEV || ne <= 0) continue;
+        // ---- the cluster: lane r holds reference i0 + r and the mask of the estimated events compatible with it ----------
+        const int i0 = i_base + s;
+        const bool has_ref = lane < nr;
+        double r_on = 0.0, r_off = 0.0;
+        if (has_ref) {
+            r_on = R[i0 + lane];
+            r_off = Roff[i0 + lane];
+        }
+        const double tol_off = fmax(tc, a.pct * (r_off - r_on));
+        unsigned long long adj = 0;
+        for (int e = 0; e < ne; ++e) {
+            const double eo = E[j0 + e], ef = Eoff[j0 + e];
+            const bool hit = has_ref && fabs(r_on - eo) <= tc && fabs(r_off - ef) <= tol_off;
+            adj |= (unsigned long long)hit << e;
+        }
+        int m_est = -1;                        // lane e: the reference matched to estimated event e
+        int parent = 0;                        // lane r: the estimated event that reached reference r in this search
+        unsigned long long matched_ref = 0;
+        for (int root = 0; root < ne; ++root) {
+            unsigned long long frontier = 1ull << root, visited = 0;
+            while (frontier) {
+                const unsigned long long reach = adj & frontier;
+                const bool fresh = reach != 0 && !((visited >> lane) & 1);
+                const unsigned long long new_ref = __ballot(fresh);
+                if (!new_ref) break;
+                if (fresh) parent = __ffsll((long long)reach) - 1;
+                const unsigned long long free_new = new_ref & ~matched_ref;
+                if (free_new) {                // an unmatched reference: flip the path back to the root
+                    int r = __ffsll((long long)free_new) - 1;
+                    matched_ref |= 1ull << r;
+                    for (int hop = 0; hop < LS_MAXEV; ++hop) {
+                        const int e = ls_lane_read(parent, r);
+                        const int prev = ls_lane_read(m_est, e);
+                        if (lane == e) m_est = r;
+                        if (prev < 0) break;
+                        r = prev;
+                    }
+                    ++ntp;
+                    break;
+                }
+                visited |= new_ref;
+                frontier = __ballot(m_est >= 0 && ((new_ref >> (m_est & 63)) & 1));
+            }
+        }
+    }
+    if (lane == 0) {
+        if (ntp > 0) atomicAdd(a.cnt + col * LS_CW, ntp);
+        if (flags) {
+            atomicOr(a.cnt + col * LS_CW + 4, flags);    // only k_ls_final, a later launch, reads it
+            atomicOr(a.err, flags);
+        }
+    }
+}
+
+// ceil(max offset / res) of one column (both sides), and of the whole recording
+__device__ __forceinline__ int ls_col_segments(const LsArgs& a, long long col) {
+    long long p0;
+    int n, seg = 0;
+    if (ls_range(a.est_ptr, col, a.est_cap, p0, n) && n > 0) seg = ls_seg_index(ceil(a.est_pmax[p0 + n - 1] / a.res));
+    if (ls_range(a.ref_ptr, col, a.ref_cap, p0, n) && n > 0) seg = max(seg, ls_seg_index(ceil(a.ref_pmax[p0 + n - 1] / a.res)));
+    return seg;
+}
+__device__ __forceinline__ int ls_file_segments(const LsArgs& a, long long rec) {
+    int seg = 0;
+    for (int c = 0; c < a.NC; ++c) seg = max(seg, ls_col_segments(a, rec * a.NC + c));
+    return seg;
+}
+// is segment s covered by the events on[0 .. n) (sorted), pmax their running maximum offset
+__device__ __forceinline__ bool ls_covered(const double* on, const double* pmax, int n, int s, double res) {
+    int lo = 0, hi = n;
+    while (lo < hi) {                                                // the number of events whose first segment is <= s
+        const int mid = (lo + hi) >> 1;
+        if (ls_seg_index(floor(on[mid] / res)) <= s) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo > 0 && ls_seg_index(ceil(pmax[lo - 1] / res)) > s;
+}
+
+__global__ __launch_bounds__(256) void k_ls_segments(LsArgs a) {
+    const long long col = blockIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int file_seg = ls_file_segments(a, col / a.NC);
+    if (file_seg > LS_MAXSEG) {
+        if (blockIdx.y == 0 && threadIdx.x == 0) atomicOr(a.err, 4);
+        return;
+    }
+    if (a.flags[col * 2] | a.flags[col * 2 + 1]) return;
+    const int col_seg = ls_col_segments(a, col);
+    long long pr, pe;
+    int n_ref, n_est;
+    ls_range(a.ref_ptr, col, a.ref_cap, pr, n_ref);
+    ls_range(a.est_ptr, col, a.est_cap, pe, n_est);
+    int tp = 0, fp = 0, fn = 0;
+    for (int s0 = blockIdx.y * 256; s0 < col_seg; s0 += LS_SEG_SPLIT * 256) {
+        const int s = s0 + threadIdx.x;
+        const bool in = s < col_seg;
+        const bool ra = in && ls_covered(a.ref_on + pr, a.ref_pmax + pr, n_ref, s, a.res);
+        const bool ea = in && ls_covered(a.est_on + pe, a.est_pmax + pe, n_est, s, a.res);
+        tp += __popcll(__ballot(ra && ea));
+        fp += __popcll(__ballot(ea && !ra));
+        fn += __popcll(__ballot(ra && !ea));
+    }
+    if (lane == 0) {
+        if (tp) atomicAdd(a.cnt + col * LS_CW + 1, tp);
+        if (fp) atomicAdd(a.cnt + col * LS_CW + 2, fp);
+        if (fn) atomicAdd(a.cnt + col * LS_CW + 3, fn);
+    }
+}
+
+// one thread per column: the per-column outputs and the class totals
+__global__ __launch_bounds__(256) void k_ls_final(LsArgs a) {
+    const long long col = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (col >= (long long)a.n_rec * a.NC) return;
+    const int c = (int)(col % a.NC);
+    const int32_t* k = a.cnt + col * LS_CW;
+    const int file_seg = ls_file_segments(a, col / a.NC);
+    const bool ok = (a.flags[col * 2] | a.flags[col * 2 + 1] | k[4]) == 0 && file_seg <= LS_MAXSEG;
+    long long p0;
+    int n_ref, n_est;
+    ls_range(a.ref_ptr, col, a.ref_cap, p0, n_ref);
+    ls_range(a.est_ptr, col, a.est_cap, p0, n_est);
+    const int ev[3] = {ok ? k[0] : 0, n_ref, n_est};
+    int sg[4] = {0, 0, 0, 0};
+    if (ok) {
+        sg[0] = k[1]; sg[1] = k[2]; sg[2] = k[3];
+        sg[3] = file_seg - sg[0] - sg[1] - sg[2];
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        if (a.out_a) a.out_a[col * 3 + i] = ev[i];
+        if (ev[i] > 0) atomicAdd(a.tot_a + c * 3 + i, (unsigned long long)ev[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if (a.out_b) a.out_b[col * 4 + i] = sg[i];
+        if (sg[i] > 0) atomicAdd(a.tot_b + c * 4 + i, (unsigned long long)sg[i]);
+    }
+}
+
+// ---- PSDS -------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double lp_overlap(double a_on, double a_off, double b_on, double b_off) {
+    return fmax(0.0, fmin(a_off, b_off) - fmax(a_on, b_on));
+}
+__device__ __forceinline__ bool lp_passes(double sum, double len, double threshold) {
+    return len > 0.0 && sum / len >= threshold;
+}
+// the events x[lo .. hi) that can overlap (q_on, q_off): those before lo end at or before q_on, those from hi on start at or
+// after q_off - every term left out is +0.0
+__device__ __forceinline__ void lp_window(const double* on, const double* pmax, int n, double q_on, double q_off, int& lo,
+                                          int& hi) {
+    int l = 0, h = n;
+    while (l < h) {                                                  // first i with on[i] >= q_off
+        const int mid = (l + h) >> 1;
+        if (on[mid] >= q_off) h = mid;
+        else l = mid + 1;
+    }
+    hi = l;
+    l = 0; h = hi;
+    while (l < h) {                                                  // first i with pmax[i] > q_on
+        const int mid = (l + h) >> 1;
+        if (pmax[mid] > q_on) h = mid;
+        else l = mid + 1;
+    }
+    lo = l;
+}
+// the column of event i of a CSR table (the last column whose offset is <= i); -1 when i is outside it or the column is not scored
+__device__ __forceinline__ long long lp_column(const LsArgs& a, const int64_t* ptr, long long cap, long long i, long long& p0,
+                                               int& n) {
+    const long long ncols = (long long)a.n_rec * a.NC;
+    long long lo = 0, hi = ncols - 1;
+    while (lo < hi) {
+        const long long mid = (lo + hi + 1) >> 1;
+        if (ptr[mid] <= i) lo = mid;
+        else hi = mid - 1;
+    }
+    if (!ls_range(ptr, lo, cap, p0, n) || i < p0 || i >= p0 + n) return -1;
+    if (a.flags[lo * 2] | a.flags[lo * 2 + 1]) return -1;
+    return lo;
+}
+// cnt[col][slot] += 1 for the lanes with `flag`: one atomic per wave when all its lanes are in one column
+__device__ __forceinline__ void lp_count(const LsArgs& a, long long col, bool uniform, int slot, bool flag) {
+    if (uniform) {
+        const int n = __popcll(__ballot(flag));
+        if (n && (threadIdx.x & 63) == 0) atomicAdd(a.cnt + col * LS_CW + slot, n);
+    } else if (flag) {
+        atomicAdd(a.cnt + col * LS_CW + slot, 1);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_lp_detect(LsArgs a) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    long long pe = 0, pr;
+    int n_est = 0, n_ref;
+    const long long col = i < a.est_cap ? lp_column(a, a.est_ptr, a.est_cap, i, pe, n_est) : -1;
+    const bool active = col >= 0;
+    const long long col0 = __shfl(col, 0);
+    const bool uniform = __ballot(col == col0) == ~0ull && col0 >= 0;
+    bool relevant = false;
+    double d_on = 0.0, d_off = 0.0;
+    if (active) {
+        d_on = a.est_on[i];
+        d_off = a.est_off[i];
+        ls_range(a.ref_ptr, col, a.ref_cap, pr, n_ref);
+        int lo, hi;
+        lp_window(a.ref_on + pr, a.ref_pmax + pr, n_ref, d_on, d_off, lo, hi);
+        double sum = 0.0;
+        for (int g = lo; g < hi; ++g) sum += lp_overlap(d_on, d_off, a.ref_on[pr + g], a.ref_off[pr + g]);
+        relevant = lp_passes(sum, d_off - d_on, a.dtc);
+        a.rel[i] = relevant ? 1 : 0;
+    }
+    const bool cross = active && !relevant;
+    lp_count(a, col, uniform, 1, cross);
+    const int c = active ? (int)(col % a.NC) : -1;
+    for (int j = 0; j < a.NC; ++j) {
+        bool ct = false;
+        if (cross && j != c) {
+            const long long cj = col - c + j;
+            if (a.flags[cj * 2 + 1] == 0) {                          // (a malformed or unsorted reference column raised err)
+                ls_range(a.ref_ptr, cj, a.ref_cap, pr, n_ref);
+                int lo, hi;
+                lp_window(a.ref_on + pr, a.ref_pmax + pr, n_ref, d_on, d_off, lo, hi);
+                double sum = 0.0;
+                for (int g = lo; g < hi; ++g) sum += lp_overlap(d_on, d_off, a.ref_on[pr + g], a.ref_off[pr + g]);
+                ct = lp_passes(sum, d_off - d_on, a.cttc);
+            }
+        }
+        lp_count(a, col, uniform, 2 + j, ct);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_lp_truth(LsArgs a) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    long long pr = 0, pe;
+    int n_ref = 0, n_est;
+    const long long col = i < a.ref_cap ? lp_column(a, a.ref_ptr, a.ref_cap, i, pr, n_ref) : -1;
+    const bool active = col >= 0;
+    const long long col0 = __shfl(col, 0);
+    const bool uniform = __ballot(col == col0) == ~0ull && col0 >= 0;
+    bool found = false;
+    if (active) {
+        const double g_on = a.ref_on[i], g_off = a.ref_off[i];
+        ls_range(a.est_ptr, col, a.est_cap, pe, n_est);
+        int lo, hi;
+        lp_window(a.est_on + pe, a.est_pmax + pe, n_est, g_on, g_off, lo, hi);
+        double sum = 0.0;
+        for (int e = lo; e < hi; ++e)
+            if (a.rel[pe + e]) sum += lp_overlap(a.est_on[pe + e], a.est_off[pe + e], g_on, g_off);
+        found = lp_passes(sum, g_off - g_on, a.gtc);
+    }
+    lp_count(a, col, uniform, 0, found);
+}
+
+// one thread per (column, value)
+__global__ __launch_bounds__(256) void k_lp_final(LsArgs a) {
+    const int W = 2 + a.NC;
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long long)a.n_rec * a.NC * W) return;
+    const long long col = t / W;
+    const int v = (int)(t - col * W), c = (int)(col % a.NC);
+    const bool ok = (a.flags[col * 2] | a.flags[col * 2 + 1]) == 0;
+    const int mine = ok ? a.cnt[col * LS_CW + v] : 0;
+    if (a.out_a) a.out_a[t] = mine;
+    if (mine > 0) atomicAdd(a.tot_a + c * W + v, (unsigned long long)mine);
+}
+
+// ---- host -------------------------------------------------------------------------------------------------------------------
+extern "C" int sed_long_tile_events(void) { return LS_TILE; }
+
+static size_t ls_align(size_t v) { return (v + 15) / 16 * 16; }
+struct LsWs { size_t flags, cnt, on, off, epmax, rpmax, rel, total; };
+static LsWs ls_ws(long long est_cap, long long ref_cap, long long ncols) {
+    LsWs w;
+    size_t o = 0;
+    w.flags = o; o += ls_align((size_t)ncols * 2 * sizeof(int32_t));
+    w.cnt = o;   o += ls_align((size_t)ncols * LS_CW * sizeof(int32_t));
+    w.on = o;    o += ls_align((size_t)est_cap * sizeof(double));
+    w.off = o;   o += ls_align((size_t)est_cap * sizeof(double));
+    w.epmax = o; o += ls_align((size_t)est_cap * sizeof(double));
+    w.rpmax = o; o += ls_align((size_t)ref_cap * sizeof(double));
+    w.rel = o;   o += ls_align((size_t)est_cap);
+    w.total = o;
+    return w;
+}
+static bool ls_sizes_ok(long long est_cap, long long ref_cap, int n_rec, int nclass) {
+    return est_cap >= 0 && ref_cap >= 0 && est_cap < (1ll << 31) - 1024 && ref_cap < (1ll << 31) - 1024 && n_rec >= 1 &&
+           nclass >= 1 && nclass <= LS_MAXNC && (long long)n_rec * nclass < (1ll << 26);
+}
+
+extern "C" size_t sed_long_score_ws_bytes(long long est_capacity, long long ref_events, int n_rec, int nclass) {
+    if (!ls_sizes_ok(est_capacity, ref_events, n_rec, nclass)) {
+        sed_set_error("sed_long_score_ws_bytes: need 0 <= est_capacity, ref_events < 2^31 - 1024, n_rec >= 1, 1 <= nclass <= 16, "
+                      "n_rec * nclass < 2^26");
+        return 0;
+    }
+    return ls_ws(est_capacity, ref_events, (long long)n_rec * nclass).total;
+}
+
+static int ls_fill(LsArgs& a, const char* what, const int64_t* ev_ptr, const int32_t* ev_pairs, double num, double den,
+                   const double* est_on, const double* est_off, long long est_cap, const int64_t* ref_ptr, const double* ref_on,
+                   const double* ref_off, long long ref_cap, int n_rec, int nclass, int32_t* err, void* ws, size_t ws_bytes) {
+    if (!(ev_ptr && ref_ptr && ref_on && ref_off && err && ws)) {
+        sed_set_error("%s: null argument", what);
+        return SED_ERR_BAD_ARG;
+    }
+    if (!ls_sizes_ok(est_cap, ref_cap, n_rec, nclass)) {
+        sed_set_error("%s: need 0 <= est_capacity, ref_events < 2^31 - 1024, n_rec >= 1, 1 <= nclass <= 16, n_rec * nclass < 2^26", what);
+        return SED_ERR_BAD_ARG;
+    }
+    if (ev_pairs ? !(num > 0.0 && den > 0.0) : !(est_on && est_off)) {
+        sed_set_error("%s: estimated events are frames (ev_pairs, num / den > 0) or seconds (est_on, est_off)", what);
+        return SED_ERR_BAD_ARG;
+    }
+    if (((uintptr_t)ws % 8) != 0) {
+        sed_set_error("%s: ws must be 8-byte aligned", what);
+        return SED_ERR_BAD_ARG;
+    }
+    const long long ncols = (long long)n_rec * nclass;
+    const LsWs w = ls_ws(est_cap, ref_cap, ncols);
+    if (ws_bytes < w.total) {
+        sed_set_error("%s: workspace of %zu bytes is too small (sed_long_score_ws_bytes: %zu)", what, ws_bytes, w.total);
+        return SED_ERR_WORKSPACE;
+    }
+    char* b = (char*)ws;
+    a = LsArgs{};
+    a.est_ptr = ev_ptr; a.ev_pairs = ev_pairs; a.num = num; a.den = den;
+    a.ws_on = (double*)(b + w.on); a.ws_off = (double*)(b + w.off);
+    a.est_on = ev_pairs ? a.ws_on : est_on; a.est_off = ev_pairs ? a.ws_off : est_off;
+    a.ref_ptr = ref_ptr; a.ref_on = ref_on; a.ref_off = ref_off;
+    a.est_cap = est_cap; a.ref_cap = ref_cap; a.n_rec = n_rec; a.NC = nclass;
+    a.n_slots = (int)(ref_cap / LS_TILE + ncols + 1);
+    a.flags = (int32_t*)(b + w.flags); a.cnt = (int32_t*)(b + w.cnt);
+    a.est_pmax = (double*)(b + w.epmax); a.ref_pmax = (double*)(b + w.rpmax); a.rel = (uint8_t*)(b + w.rel);
+    a.err = err;
+    return SED_OK;
+}
+
+static unsigned ls_blocks(long long n, int per) { return (unsigned)((n + per - 1) / per > 0 ? (n + per - 1) / per : 1); }
+
+extern "C" int sed_long_event_counts(const int64_t* ev_ptr, const int32_t* ev_pairs, double num, double den, const double* est_on,
+                                     const double* est_off, long long est_capacity, const int64_t* ref_ptr, const double* ref_on,
+                                     const double* ref_off, long long ref_events, int n_rec, int nclass, double t_collar,
+                                     double percentage_of_length, double time_resolution, int32_t* ev_counts,
+                                     int32_t* seg_counts, int64_t* ev_total, int64_t* seg_total, int32_t* err, void* ws,
+                                     size_t ws_bytes, void* stream) {
+    SED_CHECK_ARG(ev_total && seg_total, "sed_long_event_counts: null argument");
+    SED_CHECK_ARG(t_collar >= 0.0 && percentage_of_length >= 0.0 && time_resolution > 0.0,
+                  "sed_long_event_counts: need t_collar >= 0, percentage_of_length >= 0, time_resolution > 0");
+    LsArgs a;
+    SED_TRY(ls_fill(a, "sed_long_event_counts", ev_ptr, ev_pairs, num, den, est_on, est_off, est_capacity, ref_ptr, ref_on,
+                    ref_off, ref_events, n_rec, nclass, err, ws, ws_bytes));
+    a.t_collar = t_collar; a.pct = percentage_of_length; a.res = time_resolution;
+    a.out_a = ev_counts; a.out_b = seg_counts;
+    a.tot_a = (unsigned long long*)ev_total; a.tot_b = (unsigned long long*)seg_total;
+    const long long ncols = (long long)n_rec * nclass;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_ls_prep, dim3((unsigned)ncols, 2), dim3(LS_PREP_THREADS), 0, st, a);
+    SED_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_ls_match, dim3(ls_blocks(a.n_slots, 4)), dim3(256), 0, st, a);
+    SED_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_ls_segments, dim3((unsigned)ncols, LS_SEG_SPLIT), dim3(256), 0, st, a);
+    SED_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_ls_final, dim3(ls_blocks(ncols, 256)), dim3(256), 0, st, a);
+    SED_CHECK_LAUNCH();
+    return SED_OK;
+}
+
+extern "C" int sed_long_psds_counts(const int64_t* ev_ptr, const int32_t* ev_pairs, double num, double den, const double* est_on,
+                                    const double* est_off, long long est_capacity, const int64_t* ref_ptr, const double* ref_on,
+                                    const double* ref_off, long long ref_events, int n_rec, int nclass, double dtc, double gtc,
+                                    double cttc, int32_t* columns, int64_t* totals, int32_t* err, void* ws, size_t ws_bytes,
+                                    void* stream) {
+    SED_CHECK_ARG(totals, "sed_long_psds_counts: null argument");
+    SED_CHECK_ARG(dtc >= 0.0 && dtc <= 1.0 && gtc >= 0.0 && gtc <= 1.0 && cttc >= 0.0 && cttc <= 1.0,
+                  "sed_long_psds_counts: need dtc, gtc and cttc in [0, 1]");
+    LsArgs a;
+    SED_TRY(ls_fill(a, "sed_long_psds_counts", ev_ptr, ev_pairs, num, den, est_on, est_off, est_capacity, ref_ptr, ref_on,
+                    ref_off, ref_events, n_rec, nclass, err, ws, ws_bytes));
+    a.dtc = dtc; a.gtc = gtc; a.cttc = cttc;
+    a.out_a = columns; a.tot_a = (unsigned long long*)totals;
+    const long long ncols = (long long)n_rec * nclass;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_ls_prep, dim3((unsigned)ncols, 2), dim3(LS_PREP_THREADS), 0, st, a);
+    SED_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_lp_detect, dim3(ls_blocks(est_capacity, 256)), dim3(256), 0, st, a);
+    SED_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_lp_truth, dim3(ls_blocks(ref_events, 256)), dim3(256), 0, st, a);
+    SED_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_lp_final, dim3(ls_blocks(ncols * (2 + nclass), 256)), dim3(256), 0, st, a);
+    SED_CHECK_LAUNCH();
+    return SED_OK;
+}

@@ -8,9 +8,10 @@ only assembles the event table.  There is no CPU fallback: the model and its inp
 
 Recordings longer than one clip: ``LongRecordingSet`` (longrec.py) holds them as overlapping windows and
 ``get_long_predictions`` blends the windows' posteriors and decodes each recording's whole timeline with one
-``sed_stitch_decode`` call.  Out of scope there: scoring long recordings (``sed_event_counts`` / ``sed_psds_counts`` keep
-T <= 2048 and 64 events per column; the long path's event table can still be fed to ``compute_strong_metrics`` within those
-limits), recording-level weak tags, and windows for training.  ``get_predictions`` itself is unchanged.
+``sed_stitch_decode`` call.  The device-resident event table it leaves is scored by ``metrics.long_event_counts`` /
+``long_psds_counts`` / ``validate_long`` (``sed_long_event_counts``, ``sed_long_psds_counts``: columns of any length).  Out of
+scope there: decoding K operating points from one blend (``validate_long`` blends once per point), recording-level weak tags,
+and windows for training.  ``get_predictions`` itself is unchanged.
 """
 import ctypes as C
 
@@ -188,6 +189,28 @@ def stitch_decode(win_strong, rec_win0, rec_frame0, total_frames, hop3, threshol
     return out
 
 
+def long_window_posteriors(model, long_set, nclass, batch_size=64):
+    """The strong posteriors [n_win, T3, nclass] of every window of ``long_set``, from the eval-mode model ``batch_size``
+    windows at a time; they stay on the device."""
+    dev = next(model.parameters()).device
+    was_training = model.training
+    model.eval()
+    win_strong = None
+    try:
+        with torch.no_grad():
+            for i0, idx, x in eval_batches(long_set, batch_size, dev):
+                strong, _ = model(x)
+                if win_strong is None:
+                    if tuple(strong.shape[1:]) != (long_set.T3, nclass):
+                        raise ValueError(f"the model gives {tuple(strong.shape[1:])} per window, the set and the labels "
+                                         f"{(long_set.T3, nclass)}")
+                    win_strong = torch.empty(long_set.n_clips, long_set.T3, nclass, dtype=torch.float32, device=dev)
+                win_strong[i0:i0 + len(idx)].copy_(strong)
+    finally:
+        model.train(was_training)
+    return win_strong
+
+
 def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=None, save_predictions=None, batch_size=64,
                          cfg=None, threshold=0.5, median_window=None, weighting="taper", return_posteriors=False):
     """Events of recordings of any lengths (a ``LongRecordingSet``): the windows go through the eval-mode model
@@ -218,23 +241,9 @@ def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=
     NC = len(labels)
     thr = _per_class(threshold, NC, np.float32, "threshold")
     win = _per_class(cfg.median_window if median_window is None else median_window, NC, np.int32, "median_window")
-    was_training = model.training
-    model.eval()
-    win_strong = None
-    try:
-        with torch.no_grad():
-            for i0, idx, x in eval_batches(long_set, batch_size, dev):
-                strong, _ = model(x)
-                if win_strong is None:
-                    if tuple(strong.shape[1:]) != (long_set.T3, NC):
-                        raise ValueError(f"the model gives {tuple(strong.shape[1:])} per window, the set and the labels "
-                                         f"{(long_set.T3, NC)}")
-                    win_strong = torch.empty(long_set.n_clips, long_set.T3, NC, dtype=torch.float32, device=dev)
-                win_strong[i0:i0 + len(idx)].copy_(strong)
-            out = stitch_decode(win_strong, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3, thr, win,
-                                weighting, long_set.capacity(NC), want_timeline=return_posteriors)
-    finally:
-        model.train(was_training)
+    win_strong = long_window_posteriors(model, long_set, NC, batch_size)
+    out = stitch_decode(win_strong, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3, thr, win,
+                        weighting, long_set.capacity(NC), want_timeline=return_posteriors)
     err = int(out["err"].item())
     if err:
         raise _lib.SedError("sed_stitch_decode reported err " + ", ".join(f"bit {b} ({t})" for b, t in STITCH_ERR_BITS.items()

@@ -136,3 +136,11 @@ class LongRecordingSet(ResidentFeatureSet):
         """Events ``sed_stitch_decode`` can never exceed: sum over recordings of nclass * ceil(L3 / 2)."""
         L3 = np.diff(self.rec_frame0_host)
         return int(nclass) * int(((L3 + 1) // 2).sum())
+
+    def durations(self, cfg=None):
+        """Seconds of every recording's decoded timeline, ``L3 * pooling_time_ratio / (sample_rate / hop_length)`` - the scale
+        of the event table's seconds; what ``metrics.PSDS.from_counts(..., durations=...)`` takes.  ``cfg``: sample_rate /
+        hop_length (default: baseline/config.py's)."""
+        if cfg is None:
+            from .inference import _Cfg as cfg
+        return np.diff(self.rec_frame0_host) * self.pooling_time_ratio / (cfg.sample_rate / cfg.hop_length)

@@ -27,6 +27,14 @@ Limits: at most 64 reference and 64 estimated events per (file, class) - a colum
 truncated -, ``T <= 2048`` output frames, at most 16 classes.  The overall error rate *with substitutions* needs a second,
 label-agnostic matching and is **not provided**: ``results_overall_metrics()['error_rate']`` holds NaN.
 
+Long recordings (``long_event_counts``, ``long_psds_counts``, ``validate_long``, ``long_*_from_events``): the same definitions
+on the event table ``inference.stitch_decode`` leaves on the device, or on two ``RefEvents``, WITHOUT the limit per column
+(``sed_long_event_counts`` / ``sed_long_psds_counts``, csrc/lscore.hip).  Both sides of a column must be sorted by onset
+(checked on the device).  The matching is exact per CLUSTER - the runs of the merged onset order between cuts across which no
+pair can be compatible (include/dcase_sed.h) -, and a cluster holds at most 64 events per side: beyond that the call raises,
+nothing is truncated.  Not provided there: K operating points from one blend, recording-level weak tags, an exact matching of
+clusters beyond 64 per side.
+
 PSDS (polyphonic sound detection score, Bilen et al., ICASSP 2020): ``sed_psds_counts`` scores the same (operating point,
 clip) grid with the three intersection criteria and returns integer class totals (``psds_counts``, ``PSDSCounts``); the
 PSD-ROC and its area are host arithmetic on those totals (``PSDS``), which also works without a GPU.  ``psds_eval`` is
@@ -64,6 +72,13 @@ _ERR_BITS = {1: "a (file, class) column has more than 64 reference events",
              4: "a file has more than 65 536 segments",
              8: "a median window outside 1 .. 63",
              16: "malformed event offsets"}
+# the long calls (sed_long_event_counts / sed_long_psds_counts): no limit per column, the limit is per cluster
+_LONG_ERR_BITS = {1: "a cluster of more than 64 reference events whose onsets chain within t_collar",
+                  2: "a cluster of more than 64 estimated events whose onsets chain within t_collar",
+                  4: "a recording has more than 65 536 segments",
+                  16: "malformed event offsets",
+                  64: "a column whose onsets decrease (both sides must be sorted by onset)",
+                  128: "the decoded event table is invalid (sed_stitch_decode reported an error)"}
 
 
 def _pack(df, filenames, labels):
@@ -111,6 +126,7 @@ class RefEvents:
         self.ptr_host = ptr.copy()
         self.onset_host, self.offset_host = np.array(onset, np.float64), np.array(offset, np.float64)
         self.ptr = torch.as_tensor(ptr).to(self.device)
+        self.ptr64 = torch.as_tensor(ptr.astype(np.int64)).to(self.device)     # what the long calls read
         # one trailing element: an empty event list still has an address the library accepts
         self.onset = torch.as_tensor(np.r_[np.asarray(onset, np.float64), 0.0]).to(self.device)
         self.offset = torch.as_tensor(np.r_[np.asarray(offset, np.float64), 0.0]).to(self.device)
@@ -145,13 +161,14 @@ class Counts:
         self.seg = self.buf[n3:-1].view(n_points, nclass, 4)
         self.err = self.buf[-1:].view(torch.int32)
         self.ev_columns = self.seg_columns = None
+        self.err_what, self.err_bits = "sed_event_counts", _ERR_BITS          # (the long calls put their own wording here)
 
     def host(self):
         """(ev, seg) as numpy arrays - one device -> host copy; raises when a column was over a limit."""
         h = self.buf.cpu().numpy()
         err = int(h[-1:].view(np.int32)[0])
         if err:
-            raise _lib.SedError("sed_event_counts: " + "; ".join(m for b, m in _ERR_BITS.items() if err & b)
+            raise _lib.SedError(self.err_what + ": " + "; ".join(m for b, m in self.err_bits.items() if err & b)
                                 + " - nothing was truncated, the counts are invalid")
         n3 = self.K * self.NC * 3
         return h[:n3].reshape(self.K, self.NC, 3), h[n3:-1].reshape(self.K, self.NC, 4)
@@ -244,13 +261,14 @@ class PSDSCounts:
         self.totals = self.buf[:-1].view(n_points, nclass, 2 + nclass)
         self.err = self.buf[-1:].view(torch.int32)
         self.columns = None
+        self.err_what, self.err_bits = "sed_psds_counts", _ERR_BITS           # (the long calls put their own wording here)
 
     def host(self):
         """``totals`` as a numpy array - one device -> host copy; raises when a column was over a limit."""
         h = self.buf.cpu().numpy()
         err = int(h[-1:].view(np.int32)[0])
         if err:
-            raise _lib.SedError("sed_psds_counts: " + "; ".join(m for b, m in _ERR_BITS.items() if err & b)
+            raise _lib.SedError(self.err_what + ": " + "; ".join(m for b, m in self.err_bits.items() if err & b)
                                 + " - nothing was truncated, the counts are invalid")
         return h[:-1].reshape(self.K, self.NC, 2 + self.NC)
 
@@ -608,3 +626,159 @@ def validate(model, dataset, ref, pooling_time_ratio, thresholds=(0.5,), median_
         model.train(was_training)
     ev, seg = counts.host()
     return [(EventMetrics(ref.labels, ev[k]), SegmentMetrics(ref.labels, seg[k])) for k in range(thr.numel())]
+
+
+# ---- long recordings: the event table of sed_stitch_decode (or given events) of any length -----------------------------------
+def _long_call(fn, what, est_args, est_cap, ref, tail, err, dev):
+    """One ``sed_long_*`` call: ``est_args`` = (ev_ptr, ev_pairs, num, den, est_on, est_off); ``tail``: the arguments between
+    ``nclass`` and ``err``."""
+    l = _lib.lib()
+    n, NC, n_ref = len(ref), ref.nclass, len(ref.onset_host)
+    ws_bytes = l.sed_long_score_ws_bytes(int(est_cap), n_ref, n, NC)
+    if ws_bytes == 0:
+        raise _lib.SedError(f"sed_long_score_ws_bytes: {l.sed_last_error().decode()}")
+    ws = _lib.scratch(ws_bytes, dev)
+    ev_ptr, ev_pairs, num, den, on, off = est_args
+    _lib.check(getattr(l, fn)(_lib.ptr(ev_ptr), _lib.ptr(ev_pairs), float(num), float(den), _lib.ptr(on), _lib.ptr(off),
+                              int(est_cap), _lib.ptr(ref.ptr64), _lib.ptr(ref.onset), _lib.ptr(ref.offset), n_ref, n, NC, *tail,
+                              _lib.ptr(err), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), what)
+
+
+def _decoded_args(decoded, ref, pooling_time_ratio, cfg, what):
+    cfg = cfg or _Cfg
+    ev_ptr, ev_pairs = decoded["ev_ptr"], decoded["ev_pairs"]
+    if ev_ptr.device.type != "cuda" or ref.device.type != "cuda":
+        raise _lib.SedError(f"{what} needs the decoded table and a RefEvents on the GPU (no CPU fallback)")
+    if ev_ptr.dtype != torch.int64 or ev_pairs.dtype != torch.int32 or ev_ptr.numel() != len(ref) * ref.nclass + 1:
+        raise ValueError(f"decoded: ev_ptr int64 [{len(ref) * ref.nclass + 1}] and ev_pairs int32 [capacity, 2] expected "
+                         f"({len(ref)} recordings, {ref.nclass} classes)")
+    return (ev_ptr, ev_pairs.contiguous(), float(pooling_time_ratio), float(cfg.sample_rate / cfg.hop_length), None, None), \
+        ev_pairs.shape[0]
+
+
+def _events_args(est, ref, what):
+    if est.device.type != "cuda" or ref.device.type != "cuda":
+        raise _lib.SedError(f"{what} needs both event sets on the GPU (no CPU fallback)")
+    if est.filenames != ref.filenames or est.labels != ref.labels:
+        raise ValueError("estimated and reference events must cover the same files and classes, in the same order")
+    return (est.ptr64, None, 0.0, 0.0, est.onset, est.offset), len(est.onset_host)
+
+
+def _fold_decode_err(counts, decoded):
+    """The decoder's error word into the counts' (bit 128), on the device: ``host()`` raises it, nothing synchronises here."""
+    counts.err[:1].bitwise_or_((decoded["err"].reshape(-1)[:1] != 0).to(torch.int32) * 128)
+
+
+def _long_event_call(est_args, est_cap, ref, t_collar, percentage_of_length, time_resolution, counts, point, per_column):
+    n, NC, dev = len(ref), ref.nclass, ref.device
+    if counts is None:
+        counts = Counts(point + 1, NC, dev)
+    if counts.NC != NC or not 0 <= point < counts.K:
+        raise ValueError(f"counts holds {counts.K} operating points of {counts.NC} classes: no row {point} of {NC} classes")
+    counts.err_what, counts.err_bits = "sed_long_event_counts", _LONG_ERR_BITS
+    if per_column:
+        counts.ev_columns = torch.empty(n, NC, 3, dtype=torch.int32, device=dev)
+        counts.seg_columns = torch.empty(n, NC, 4, dtype=torch.int32, device=dev)
+    _long_call("sed_long_event_counts", "sed_long_event_counts", est_args, est_cap, ref,
+               (float(t_collar), float(percentage_of_length), float(time_resolution),
+                _lib.ptr(counts.ev_columns) if per_column else None, _lib.ptr(counts.seg_columns) if per_column else None,
+                _lib.ptr(counts.ev[point]), _lib.ptr(counts.seg[point])), counts.err, dev)
+    return counts
+
+
+def _long_psds_call(est_args, est_cap, ref, dtc, gtc, cttc, counts, point, per_column):
+    n, NC, dev = len(ref), ref.nclass, ref.device
+    if counts is None:
+        counts = PSDSCounts(point + 1, NC, dev, dtc, gtc, cttc)
+    if counts.NC != NC or not 0 <= point < counts.K:
+        raise ValueError(f"counts holds {counts.K} operating points of {counts.NC} classes: no row {point} of {NC} classes")
+    if (counts.dtc, counts.gtc, counts.cttc) != (float(dtc), float(gtc), float(cttc)):
+        raise ValueError("counts was built for other criteria (dtc, gtc, cttc)")
+    counts.err_what, counts.err_bits = "sed_long_psds_counts", _LONG_ERR_BITS
+    if per_column:
+        counts.columns = torch.empty(n, NC, 2 + NC, dtype=torch.int32, device=dev)
+    _long_call("sed_long_psds_counts", "sed_long_psds_counts", est_args, est_cap, ref,
+               (counts.dtc, counts.gtc, counts.cttc, _lib.ptr(counts.columns) if per_column else None,
+                _lib.ptr(counts.totals[point])), counts.err, dev)
+    return counts
+
+
+def long_event_counts(decoded, ref, pooling_time_ratio, cfg=None, t_collar=0.200, percentage_of_length=0.2, time_resolution=1.0,
+                      counts=None, point=0, per_column=False):
+    """Event- and segment-based counts of long recordings: ``decoded`` is the dict ``inference.stitch_decode`` returns (the
+    event table stays on the device), ``ref`` the ``RefEvents`` of the same recordings (files = recordings) and classes.
+    The totals ACCUMULATE into row ``point`` of ``counts`` (a ``Counts`` of K operating points; None: a new one of
+    ``point + 1`` rows); ``per_column``: ``counts.ev_columns [n_rec, nclass, 3]`` / ``seg_columns [n_rec, nclass, 4]`` of this
+    call.  No synchronisation: ``decoded["err"]`` is folded into the counts' error word on the device, ``host()`` raises.
+    Columns have no length limit; a CLUSTER (events whose onsets chain within ``t_collar``) holds at most 64 per side.
+    Seconds as in ``event_counts``: ``frame * pooling_time_ratio / (sample_rate / hop_length)`` from ``cfg``."""
+    est_args, cap = _decoded_args(decoded, ref, pooling_time_ratio, cfg, "long_event_counts")
+    counts = _long_event_call(est_args, cap, ref, t_collar, percentage_of_length, time_resolution, counts, point, per_column)
+    _fold_decode_err(counts, decoded)
+    return counts
+
+
+def long_psds_counts(decoded, ref, pooling_time_ratio, cfg=None, dtc=0.5, gtc=0.5, cttc=0.3, counts=None, point=0,
+                     per_column=False):
+    """``long_event_counts`` for the PSDS criteria: totals into row ``point`` of a ``PSDSCounts`` (its criteria must be
+    these); ``per_column``: ``counts.columns [n_rec, nclass, 2 + nclass]``."""
+    est_args, cap = _decoded_args(decoded, ref, pooling_time_ratio, cfg, "long_psds_counts")
+    counts = _long_psds_call(est_args, cap, ref, dtc, gtc, cttc, counts, point, per_column)
+    _fold_decode_err(counts, decoded)
+    return counts
+
+
+def long_event_counts_from_events(est, ref, t_collar=0.200, percentage_of_length=0.2, time_resolution=1.0, counts=None, point=0,
+                                  per_column=False):
+    """The scoring stage alone on two ``RefEvents`` (``est``: the ESTIMATED events of the same files and classes; they need
+    not be disjoint, both are sorted by onset as ``RefEvents.from_dataframe`` packs them).  No limit of 64 events per column."""
+    est_args, cap = _events_args(est, ref, "long_event_counts_from_events")
+    return _long_event_call(est_args, cap, ref, t_collar, percentage_of_length, time_resolution, counts, point, per_column)
+
+
+def long_psds_counts_from_events(est, ref, dtc=0.5, gtc=0.5, cttc=0.3, counts=None, point=0, per_column=False):
+    """The PSDS criteria alone on two ``RefEvents``; no limit of 64 events per column."""
+    est_args, cap = _events_args(est, ref, "long_psds_counts_from_events")
+    return _long_psds_call(est_args, cap, ref, dtc, gtc, cttc, counts, point, per_column)
+
+
+def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, batch_size=64, cfg=None, weighting="taper",
+                  psds=None):
+    """``validate`` for a ``LongRecordingSet``: the windows go through the model ONCE; per operating point one
+    ``stitch_decode`` of the window posteriors and ``long_event_counts`` into row k (the blend is repeated per point:
+    decoding K points from one blend is not provided); ONE device -> host copy at the end.  ``thresholds``: K entries, each
+    a scalar or one value per class; ``median_windows``: the same (or one entry for all points; None: ``cfg.median_window``).
+    ``ref``: the ``RefEvents`` of the recordings, in the set's order.  ``psds``: a ``PSDSCounts`` of the same K points, filled
+    by ``long_psds_counts`` from the same decodes (read it with ``PSDS.from_counts(psds, ref, long_set.durations())``).
+    Returns one ``(EventMetrics, SegmentMetrics)`` per operating point."""
+    from .inference import long_window_posteriors, stitch_decode
+    from .longrec import LongRecordingSet
+    if not isinstance(long_set, LongRecordingSet):
+        raise TypeError(f"long_set must be a LongRecordingSet, got {type(long_set).__name__}")
+    if not getattr(model, "hot_path", False):
+        raise _lib.SedError("validate_long needs a CRNN on the HIP hot path")
+    dev = next(model.parameters()).device
+    if dev.type != "cuda":
+        raise _lib.SedError("validate_long needs the model on the GPU (no CPU fallback)")
+    if long_set.n_rec != len(ref):
+        raise ValueError(f"{long_set.n_rec} recordings but reference events of {len(ref)}")
+    cfg = cfg or _Cfg
+    NC = ref.nclass
+    thresholds = list(thresholds)
+    median_windows = [cfg.median_window] if median_windows is None else list(median_windows)
+    K = max(len(thresholds), len(median_windows))
+    if len(thresholds) not in (1, K) or len(median_windows) not in (1, K) or K < 1:
+        raise ValueError("thresholds and median_windows must have equal lengths (or length 1)")
+    if psds is not None and (psds.K, psds.NC) != (K, NC):
+        raise ValueError("psds was built for another number of operating points / classes")
+    counts = Counts(K, NC, dev)
+    win_strong = long_window_posteriors(model, long_set, NC, batch_size)
+    for k in range(K):
+        out = stitch_decode(win_strong, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3,
+                            thresholds[k % len(thresholds)], median_windows[k % len(median_windows)], weighting,
+                            long_set.capacity(NC), want_timeline=False)
+        long_event_counts(out, ref, long_set.pooling_time_ratio, cfg, counts=counts, point=k)
+        if psds is not None:
+            long_psds_counts(out, ref, long_set.pooling_time_ratio, cfg, psds.dtc, psds.gtc, psds.cttc, counts=psds, point=k)
+    ev, seg = counts.host()
+    return [(EventMetrics(ref.labels, ev[k]), SegmentMetrics(ref.labels, seg[k])) for k in range(K)]

@@ -584,6 +584,74 @@ int sed_psds_counts(const float* strong, int n_clips, int T, int nclass, int n_p
                     double dtc, double gtc, double cttc, int32_t* columns, int64_t* totals, int32_t* err,
                     void* stream);
 
+/* ---- scoring long recordings -------------------------------------------------------------------
+ * sed_long_event_counts / sed_long_psds_counts score the event table sed_stitch_decode leaves (or events given in
+ * seconds) against reference events, for (recording, class) columns of ANY length.  The definitions are those of
+ * sed_event_counts and sed_psds_counts above - compatibility and Ntp = size of a maximum bipartite matching; segment
+ * coverage, the file's segment count and the four segment counts; DTC / GTC / CTTC with every sum a sequential fp64
+ * sum in stored order from 0.0 and the division first - with ONE exception: there is no limit of 64 events per column.
+ * Pinned: exact agreement with tests/sed_eval_np.py and tests/psds_np.py, which state the definitions for lists of any
+ * length; parity with sed_eval / psds_eval stays UNPINNED as above.
+ *
+ * Columns are (recording, class) = rec * nclass + class.  One operating point per call.
+ *   estimated events  ev_ptr [n_rec * nclass + 1] int64 CSR offsets, and either
+ *                     ev_pairs [est_capacity][2] int32 (onset, exclusive offset) frames as sed_stitch_decode writes them:
+ *                       seconds = (double)frame * num / den, the host's doubles bit for bit (est_on / est_off ignored), or
+ *                     ev_pairs == NULL and est_on / est_off [est_capacity] fp64 seconds (they need not be disjoint)
+ *   reference events  ref_ptr [n_rec * nclass + 1] int64, ref_on / ref_off [ref_events] fp64 seconds
+ *   est_capacity, ref_events   what the arrays hold (the capacity sed_stitch_decode was given, not the true count): every
+ *                     offset is checked against them before it is used, and they size the grids and the workspace - all
+ *                     known on the host without a synchronisation
+ * BOTH SIDES OF A COLUMN MUST BE SORTED BY ONSET, non-decreasing (sed_stitch_decode's tables and arrays packed by
+ * (onset, offset) are).  It is checked on the device: a column whose onsets decrease raises bit 64 and is not scored.
+ * Two consequences of the order carry the long columns:
+ *  1. The matching decomposes at valid cuts.  Merge the two onset lists of a column (ties in any order).  A cut after
+ *     merged position p is VALID iff (last reference onset at or before p) + t_collar < (first estimated onset after p)
+ *     and (last estimated onset at or before p) + t_collar < (first reference onset after p); a missing side counts as
+ *     minus / plus infinity.  No compatible pair straddles a valid cut, so Ntp of the column is the sum of Ntp over the
+ *     CLUSTERS, the maximal runs between valid cuts, and each cluster is matched exactly (the augmenting-path search
+ *     of sed_event_counts).  The kernel evaluates "a + t_collar < b" as "b - a > t_collar", the form the compatibility
+ *     test itself uses, so that no pair that test accepts can straddle a cut whatever the rounding; the two forms agree
+ *     whenever the sum is exact.
+ *     A cluster with more than 64 reference events raises bit 1, with more than 64 estimated events bit 2: events
+ *     whose onsets chain within t_collar.  Such a column is not scored and nothing is truncated.  Estimated events
+ *     between two clusters and reference events without a neighbour are clusters of their own: a column of thousands
+ *     of events raises nothing as long as no single chain exceeds 64 per side.
+ *  2. The PSDS sums skip zero terms.  Every I(d, g) >= 0 and the sum starts at 0.0, so leaving out events that do not
+ *     overlap gives the bits of the full sequential sum; the kernels restrict each sum to the range of the other side
+ *     that can overlap (still in stored order) and never visit every pair.
+ * sed_long_event_counts outputs:
+ *   ev_counts  [n_rec][nclass][3] int32 (Ntp, Nref, Nsys) or NULL;  seg_counts [n_rec][nclass][4] int32 (Ntp, Nfp, Nfn,
+ *   Ntn) or NULL: every element is written (a column that is not scored: Ntp = 0 and four zeros)
+ *   ev_total [nclass][3], seg_total [nclass][4] int64: ACCUMULATED over calls (zero them first)
+ *   err  one int32, OR-ed: 1 / 2 = a cluster of more than 64 reference / estimated events, 4 = a recording of more than
+ *        65 536 segments, 16 = malformed offsets (negative, decreasing or beyond est_capacity / ref_events), 64 = a
+ *        column whose onsets decrease.  A caller must treat the totals as invalid when err != 0.
+ * sed_long_psds_counts outputs: columns [n_rec][nclass][2 + nclass] int32 or NULL, totals [nclass][2 + nclass] int64
+ *   ACCUMULATED, err with bits 16 and 64 only (no matching: 1 and 2 cannot be raised, 4 is not either).
+ * ws: sed_long_score_ws_bytes(est_capacity, ref_events, n_rec, nclass) bytes, 8-byte aligned, for either call: the
+ *   seconds of the frames, the running maxima of the offsets, per-column counters.
+ * The matching is split along a column: one wave owns sed_long_tile_events() consecutive reference events, finds the
+ *   clusters that start among them by a local test (two bisections per event) and follows the last one into the next
+ *   tile.  Segments: one thread per segment.  PSDS: one thread per event.  Data passes between workgroups only from one
+ *   launch to the next (four launches per call on `stream`).  No allocation, no host synchronisation, no float atomics;
+ *   integer results are bit-reproducible; hipGraph-capturable.  No table content can make a kernel address outside the
+ *   arrays as est_capacity / ref_events and n_rec * nclass + 1 describe them.
+ * Limits: nclass <= 16, est_capacity and ref_events < 2^31 - 1024, n_rec * nclass < 2^26.  Not provided: an exact
+ *   matching for clusters beyond 64 per side, the overall error rate with substitutions, recording-level weak tags. */
+size_t sed_long_score_ws_bytes(long long est_capacity, long long ref_events, int n_rec, int nclass);
+int sed_long_tile_events(void);
+int sed_long_event_counts(const int64_t* ev_ptr, const int32_t* ev_pairs, double num, double den, const double* est_on,
+                          const double* est_off, long long est_capacity, const int64_t* ref_ptr, const double* ref_on,
+                          const double* ref_off, long long ref_events, int n_rec, int nclass, double t_collar,
+                          double percentage_of_length, double time_resolution, int32_t* ev_counts, int32_t* seg_counts,
+                          int64_t* ev_total, int64_t* seg_total, int32_t* err, void* ws, size_t ws_bytes, void* stream);
+int sed_long_psds_counts(const int64_t* ev_ptr, const int32_t* ev_pairs, double num, double den, const double* est_on,
+                         const double* est_off, long long est_capacity, const int64_t* ref_ptr, const double* ref_on,
+                         const double* ref_off, long long ref_events, int n_rec, int nclass, double dtc, double gtc,
+                         double cttc, int32_t* columns, int64_t* totals, int32_t* err, void* ws, size_t ws_bytes,
+                         void* stream);
+
 /* ---- single-kernel replay (measurement) ----------------------------------------------------
  * Re-launches ONE kernel of the step on the buffers left by a finished sed_crnn_forward +
  * sed_crnn_backward (same shapes, same data; outputs are rewritten with identical values), so

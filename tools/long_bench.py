@@ -19,7 +19,19 @@ median of --decode-reps (default 30) single calls, for either hop.
 The clips leg needs nothing this tool's commit added, so the tool also runs on a tree without the long path (it then reports
 that leg only).
 
-Usage: python tools/long_bench.py [--rounds 5] [--decode-reps 30] [--out profiles/long_inference.json]"""
+--scoring measures what scoring the long path's event table on the device adds (profiles/long_scoring.json), on the same two
+workloads at the default hop, legs alternated in the same way:
+  predictions       get_long_predictions (inference the user already pays; ends with the host copy of the event table)
+  validate_1        metrics.validate_long at one operating point (forward, decode, sed_long_event_counts, one host copy)
+  validate_50_psds  validate_long at 50 thresholds with a PSDSCounts (50 decodes, 50 + 50 scoring calls, two host copies)
+and metrics.long_event_counts / long_psds_counts alone on a decoded table (device-event pair around each call, median of
+--decode-reps).  The references are the decoded events of the first operating point, jittered (dropped with p = 0.15, both
+ends moved by up to 0.3 s, sorted by onset).  The thresholds are per-class quantiles of the blended posteriors: the lowest of
+0.5 / 0.75 / 0.9 at which no cluster of the scored columns exceeds 64 events per side (the largest cluster is reported; the
+50 points run from that quantile up to 0.99).  There is no earlier route to compare against: the clip scorer raises on these
+columns.
+
+Usage: python tools/long_bench.py [--scoring] [--rounds 5] [--decode-reps 30] [--out profiles/long_inference.json]"""
 import argparse
 import json
 import os
@@ -166,13 +178,134 @@ def workload(name, model, rounds, reps):
     return out
 
 
+def _columns(ev_ptr, on, off):
+    return [(on[a:b], off[a:b]) for a, b in zip(ev_ptr[:-1], ev_ptr[1:])]
+
+
+def largest_cluster(ref_on, est_on, t_collar=0.2):
+    """(reference, estimated) events of the largest cluster of one column (include/dcase_sed.h: runs between valid cuts)."""
+    on = np.r_[ref_on, est_on]
+    side = np.r_[np.zeros(len(ref_on), np.int8), np.ones(len(est_on), np.int8)]
+    if len(on) == 0:
+        return 0, 0
+    order = np.argsort(on, kind="stable")
+    on, side = on[order], side[order]
+    last = [np.maximum.accumulate(np.where(side == k, on, -np.inf)) for k in (0, 1)]
+    nxt = [np.r_[np.minimum.accumulate(np.where(side == k, on, np.inf)[::-1])[::-1][1:], np.inf] for k in (0, 1)]
+    cut = (last[0] + t_collar < nxt[1]) & (last[1] + t_collar < nxt[0])
+    cluster = np.r_[0, np.cumsum(cut)[:-1]]
+    n = cluster[-1] + 1
+    return int(np.bincount(cluster[side == 0], minlength=n).max()), int(np.bincount(cluster[side == 1], minlength=n).max())
+
+
+def scoring_workload(name, model, rounds, reps):
+    from dcase2019_task4_amd import metrics
+    n_rec, per = WORKLOADS[name]
+    recs = recordings(n_rec, per)
+    sc = scaler_of(recs[0])
+    names = [f"{name}_{r}.wav" for r in range(n_rec)]
+    labels = _Enc.labels
+    ls = inference.LongRecordingSet.from_arrays(recs, T, scaler=sc, filenames=names)
+    win_strong = inference.long_window_posteriors(model, ls, NCLASS, BATCH)
+    den = inference._Cfg.sample_rate / inference._Cfg.hop_length
+    window = 7
+    rs = np.random.RandomState(0)
+
+    def decode(thr):
+        return inference.stitch_decode(win_strong, ls.rec_win0, ls.rec_frame0, ls.total_frames, ls.hop3, thr, window, "taper",
+                                       ls.capacity(NCLASS))
+    timeline = decode(0.5)["timeline"]
+    chosen = None
+    for q in (0.5, 0.75, 0.9):
+        thr = torch.quantile(timeline[:: max(1, timeline.shape[0] // 100000)], q, dim=0).cpu().numpy().astype(np.float32)
+        out = decode(thr)
+        assert int(out["err"].item()) == 0
+        ev_ptr = out["ev_ptr"].cpu().numpy()
+        ev = out["ev_pairs"][:int(ev_ptr[-1])].cpu().numpy().astype(np.int64)
+        est = _columns(ev_ptr, ev[:, 0] * POOL / den, ev[:, 1] * POOL / den)
+        ref = []
+        for on, off in est:                                          # jittered references, sorted by onset
+            keep = rs.uniform(size=len(on)) >= 0.15
+            a = np.maximum(0.0, on[keep] + rs.uniform(-0.3, 0.3, keep.sum()))
+            b = off[keep] + rs.uniform(-0.3, 0.3, keep.sum())
+            a, b = np.minimum(a, b).clip(min=0.0), np.maximum(a, b)
+            o = np.lexsort((b, a))
+            ref.append((a[o], b[o]))
+        sizes = [largest_cluster(r[0], e[0]) for r, e in zip(ref, est)]
+        biggest = (max(s[0] for s in sizes), max(s[1] for s in sizes))
+        if max(biggest) <= 64:
+            chosen = q
+            break
+    if chosen is None:
+        raise SystemExit(f"{name}: clusters beyond 64 events per side at every threshold tried ({biggest})")
+    ref_ptr = np.r_[0, np.cumsum([len(r[0]) for r in ref])]
+    ref_ev = metrics.RefEvents(ref_ptr, np.concatenate([r[0] for r in ref]), np.concatenate([r[1] for r in ref]), names, labels)
+    hi = torch.quantile(timeline[:: max(1, timeline.shape[0] // 100000)], 0.99, dim=0).cpu().numpy().astype(np.float32)
+    thr50 = [thr + (hi - thr) * k / 49.0 for k in range(50)]
+    out_info = {"recordings": n_rec, "windows": ls.n_clips, "timeline_frames": ls.total_frames, "threshold_quantile": chosen,
+                "median_window": window, "estimated_events": int(ev_ptr[-1]), "reference_events": int(ref_ptr[-1]),
+                "longest_column": {"estimated": int(np.diff(ev_ptr).max()), "reference": int(np.diff(ref_ptr).max())},
+                "largest_cluster": {"reference": biggest[0], "estimated": biggest[1]}}
+    state = {}
+
+    def validate_50():
+        psds = metrics.PSDSCounts(50, NCLASS, "cuda")
+        state["v50"] = metrics.validate_long(model, ls, ref_ev, thr50, [window], batch_size=BATCH, psds=psds)
+        state["psds"] = psds.host()
+    legs = {"predictions": lambda: inference.get_long_predictions(model, ls, labels, POOL, batch_size=BATCH, threshold=thr,
+                                                                  median_window=window),
+            "validate_1": lambda: state.__setitem__("v1", metrics.validate_long(model, ls, ref_ev, [thr], [window],
+                                                                                 batch_size=BATCH)),
+            "validate_50_psds": validate_50}
+    for leg, fn in list(legs.items()):
+        try:
+            fn()
+        except _lib.SedError as e:                                    # e.g. a cluster beyond 64 at one of the 50 points
+            out_info[leg] = {"error": str(e)}
+            del legs[leg]
+    out_info["event_f_overall_point_0"] = state["v1"][0][0].results_overall_metrics()["f_measure"]["f_measure"]
+    ms = {leg: [] for leg in legs}
+    for _ in range(rounds):
+        for leg, fn in legs.items():
+            ms[leg].append(wall_ms(fn))
+    for leg in legs:
+        out_info[leg] = stats(ms[leg])
+    for leg in ("validate_1", "validate_50_psds"):
+        if leg not in legs:
+            continue
+        out_info[leg]["ratio_to_predictions"] = out_info[leg]["median_ms"] / out_info["predictions"]["median_ms"]
+        out_info[leg]["added_ms"] = out_info[leg]["median_ms"] - out_info["predictions"]["median_ms"]
+    decoded = decode(thr)
+    alone = {"sed_long_event_counts": lambda: metrics.long_event_counts(decoded, ref_ev, POOL),
+             "sed_long_psds_counts": lambda: metrics.long_psds_counts(decoded, ref_ev, POOL)}
+    for what, call in alone.items():
+        for _ in range(5):
+            call()
+        torch.cuda.synchronize()
+        t = []
+        for _ in range(reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            c = call()
+            e1.record()
+            torch.cuda.synchronize()
+            t.append(e0.elapsed_time(e1))
+        c.host()                                                     # raises when the error word is set
+        st = stats(t)
+        out_info[what + "_alone"] = {"median_ms": st["median_ms"], "spread": st["spread"], "reps": reps}
+    return out_info
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--scoring", action="store_true", help="measure the scoring of the long path's event table instead")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--decode-reps", type=int, default=30)
     ap.add_argument("--workloads", default=",".join(WORKLOADS))
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "long_inference.json"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(REPO, "profiles", "long_scoring.json" if args.scoring else "long_inference.json")
     if not torch.cuda.is_available():
         raise SystemExit("long_bench.py measures on the GPU: no device found (nothing is measured on a CPU)")
     if args.rounds < 5 or args.decode_reps < 20:
@@ -186,8 +319,14 @@ def main():
               "not_measured": ["from_waveforms / feature extraction", "other batch sizes, bf16 / wide models",
                                "recordings longer than 1 h", "a run with the GPU to itself (the host is shared)"],
               "workloads": {}}
+    if args.scoring:
+        result["timing"] = ("host clock around each synchronised call, legs alternated; the scoring calls alone: a device-event "
+                            "pair around the Python call (workspace allocation and four launches)")
+        result["note"] = ("validate_long against the same run's get_long_predictions: the cost scoring adds to inference; no "
+                          "earlier route exists (sed_event_counts raises beyond 64 events per column)")
+        result["not_measured"] += ["the kernels one by one", "given-events mode", "other t_collar / resolutions"]
     for name in args.workloads.split(","):
-        result["workloads"][name] = workload(name, model, args.rounds, args.decode_reps)
+        result["workloads"][name] = (scoring_workload if args.scoring else workload)(name, model, args.rounds, args.decode_reps)
         print(json.dumps({name: result["workloads"][name]}), flush=True)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
