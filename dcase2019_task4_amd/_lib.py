@@ -57,6 +57,10 @@ _SIGS = {
     "sed_stitch_tile_frames": (C.c_int, []),
     "sed_stitch_decode": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_longlong,
                                     _P, C.c_size_t, _P, _P]),
+    "sed_stitch_sweep_ws_bytes": (C.c_size_t, [C.c_longlong, C.c_int, C.c_int, C.c_int]),
+    "sed_stitch_sweep_point_group": (C.c_int, []),
+    "sed_stitch_sweep": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P,
+                                   C.c_longlong, _P, C.c_size_t, _P, _P]),
     "sed_event_counts": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P,
                                    C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P]),
     "sed_psds_counts": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P,
@@ -67,6 +71,13 @@ _SIGS = {
                                         C.c_int, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "sed_long_psds_counts": (C.c_int, [_P, _P, C.c_double, C.c_double, _P, _P, C.c_longlong, _P, _P, _P, C.c_longlong, C.c_int,
                                        C.c_int, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, C.c_size_t, _P]),
+    "sed_long_sweep_ws_bytes": (C.c_size_t, [C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int]),
+    "sed_long_sweep_event_counts": (C.c_int, [_P, _P, C.c_double, C.c_double, _P, _P, C.c_longlong, _P, _P, _P, C.c_longlong,
+                                              C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P,
+                                              _P, C.c_size_t, _P]),
+    "sed_long_sweep_psds_counts": (C.c_int, [_P, _P, C.c_double, C.c_double, _P, _P, C.c_longlong, _P, _P, _P, C.c_longlong,
+                                             C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P,
+                                             C.c_size_t, _P]),
     "sed_weak_counts": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
     "sed_version": (C.c_int, []),
     "sed_param_count": (C.c_int, [C.POINTER(SedDims)]),

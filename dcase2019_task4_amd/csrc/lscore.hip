@@ -3,8 +3,12 @@
 // include/dcase_sed.h, without the limit of 64 events per column).  The estimated events are sed_stitch_decode's table
 // (ev_ptr / ev_pairs, frames) or CSR fp64 seconds; both sides of a column are sorted by onset.
 //
+// The sweep calls (sed_long_sweep_*) score K estimated tables - one CSR over the columns (k, rec, c) - against ONE reference
+// side with the same kernels: an estimated column's reference column is its index modulo n_rec * NC, and everything that
+// derives from the reference alone is done once per call.  The one-point calls are K = 1.
+//
 // Every launch has one kind of worker and no data passes between workgroups inside a launch:
-//   k_ls_prep      one workgroup per (column, side): validates the CSR offsets, turns frames into seconds, checks that the
+//   k_ls_prep      one workgroup per estimated column of every point and per reference column: validates the CSR offsets, turns frames into seconds, checks that the
 //                  onsets do not decrease and writes pmax[i] = max(offset[0 .. i]) (a workgroup scan, 1024 events per step);
 //                  the only pass that walks a column in sequence
 //   k_ls_match     one wave per tile of LS_TILE reference events.  "i starts a cluster" is a local test (two bisections in
@@ -37,10 +41,12 @@ struct LsArgs {
     const double *est_on, *est_off;  // the given seconds, or the workspace copies of the frames
     const int64_t* ref_ptr; const double *ref_on, *ref_off;
     long long est_cap, ref_cap;
-    int n_rec, NC, n_slots;
+    int n_rec, NC, n_slots;          // n_slots: tiles of reference events, per point
+    int K;                           // operating points: estimated column (k, rec, c) is scored against reference column (rec, c)
     double t_collar, pct, res, dtc, gtc, cttc;
-    int32_t* flags;                  // ws [ncols][2]: err bits of (column, side), written by k_ls_prep
-    int32_t* cnt;                    // ws [ncols][LS_CW]
+    int32_t* flags;                  // ws [K * ncols]: err bits of an estimated column, written by k_ls_prep
+    int32_t* rflags;                 // ws [ncols]: the same of a reference column
+    int32_t* cnt;                    // ws [K * ncols][LS_CW]
     double *ws_on, *ws_off;          // ws [est_cap] each (frames mode)
     double *est_pmax, *ref_pmax;     // ws [est_cap], [ref_cap]
     uint8_t* rel;                    // ws [est_cap]: detection is relevant (PSDS)
@@ -64,13 +70,17 @@ __device__ __forceinline__ bool ls_range(const int64_t* ptr, long long col, long
     n = ok ? (int)(b - a) : 0;
     return ok;
 }
+// the reference column of an estimated column, and the err bits that keep the pair from being scored
+__device__ __forceinline__ long long ls_rcol(const LsArgs& a, long long ecol) { return ecol % ((long long)a.n_rec * a.NC); }
+__device__ __forceinline__ int ls_col_flags(const LsArgs& a, long long ecol) { return a.flags[ecol] | a.rflags[ls_rcol(a, ecol)]; }
 
 __global__ __launch_bounds__(LS_PREP_THREADS) void k_ls_prep(LsArgs a) {
     __shared__ double part[LS_PREP_THREADS / 64];
     __shared__ double s_carry;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long col = blockIdx.x;
-    const int side = blockIdx.y;                                     // 0: estimated, 1: reference
+    const long long n_est_cols = (long long)a.K * a.n_rec * a.NC;
+    const int side = blockIdx.x >= n_est_cols;                       // 0: estimated (every point's columns), 1: reference (once)
+    const long long col = side ? blockIdx.x - n_est_cols : blockIdx.x;
     const bool frames = side == 0 && a.ev_pairs != nullptr;
     long long p0;
     int n, flags = 0;
@@ -122,7 +132,7 @@ __global__ __launch_bounds__(LS_PREP_THREADS) void k_ls_prep(LsArgs a) {
     }
     if (__syncthreads_or(unsorted)) flags |= 64;
     if (tid == 0) {
-        a.flags[col * 2 + side] = flags;
+        (side ? a.rflags : a.flags)[col] = flags;
         if (flags) atomicOr(a.err, flags);
     }
 }
@@ -156,21 +166,23 @@ __device__ __forceinline__ int ls_first_above(const double* x, int n, double r, 
 __global__ __launch_bounds__(256) void k_ls_match(LsArgs a) {
     const int lane = threadIdx.x & 63;
     const long long g = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (g >= a.n_slots) return;
+    if (g >= (long long)a.K * a.n_slots) return;
+    const int kp = (int)(g / a.n_slots);
+    const long long gl = g - (long long)kp * a.n_slots;
     const long long ncols = (long long)a.n_rec * a.NC;
     long long lo_c = 0, hi_c = ncols - 1;
     while (lo_c < hi_c) {                                            // the last column with slot0(col) <= g
         const long long mid = (lo_c + hi_c + 1) >> 1;
-        if (a.ref_ptr[mid] / LS_TILE + mid <= g) lo_c = mid;
+        if (a.ref_ptr[mid] / LS_TILE + mid <= gl) lo_c = mid;
         else hi_c = mid - 1;
     }
-    const long long col = lo_c;
-    if (a.flags[col * 2] | a.flags[col * 2 + 1]) return;             // not scored (k_ls_prep reported it)
+    const long long rcol = lo_c, col = kp * ncols + rcol;
+    if (a.flags[col] | a.rflags[rcol]) return;                       // not scored (k_ls_prep reported it)
     long long pr, pe;
     int n_ref, n_est;
-    ls_range(a.ref_ptr, col, a.ref_cap, pr, n_ref);
+    ls_range(a.ref_ptr, rcol, a.ref_cap, pr, n_ref);
     ls_range(a.est_ptr, col, a.est_cap, pe, n_est);
-    const long long kt = g - (pr / LS_TILE + col);
+    const long long kt = gl - (pr / LS_TILE + rcol);
     if (kt < 0 || kt * LS_TILE >= n_ref) return;
     const int i_base = (int)kt * LS_TILE;
     const double* R = a.ref_on + pr;
@@ -283,12 +295,14 @@ __global__ __launch_bounds__(256) void k_ls_match(LsArgs a) {
     }
 }
 
-// ceil(max offset / res) of one column (both sides), and of the whole recording
+// ceil(max offset / res) of one estimated column and its reference column, and of the whole recording at one point
+// (rec = k * n_rec + recording)
 __device__ __forceinline__ int ls_col_segments(const LsArgs& a, long long col) {
     long long p0;
     int n, seg = 0;
     if (ls_range(a.est_ptr, col, a.est_cap, p0, n) && n > 0) seg = ls_seg_index(ceil(a.est_pmax[p0 + n - 1] / a.res));
-    if (ls_range(a.ref_ptr, col, a.ref_cap, p0, n) && n > 0) seg = max(seg, ls_seg_index(ceil(a.ref_pmax[p0 + n - 1] / a.res)));
+    if (ls_range(a.ref_ptr, ls_rcol(a, col), a.ref_cap, p0, n) && n > 0)
+        seg = max(seg, ls_seg_index(ceil(a.ref_pmax[p0 + n - 1] / a.res)));
     return seg;
 }
 __device__ __forceinline__ int ls_file_segments(const LsArgs& a, long long rec) {
@@ -315,11 +329,11 @@ __global__ __launch_bounds__(256) void k_ls_segments(LsArgs a) {
         if (blockIdx.y == 0 && threadIdx.x == 0) atomicOr(a.err, 4);
         return;
     }
-    if (a.flags[col * 2] | a.flags[col * 2 + 1]) return;
+    if (ls_col_flags(a, col)) return;
     const int col_seg = ls_col_segments(a, col);
     long long pr, pe;
     int n_ref, n_est;
-    ls_range(a.ref_ptr, col, a.ref_cap, pr, n_ref);
+    ls_range(a.ref_ptr, ls_rcol(a, col), a.ref_cap, pr, n_ref);
     ls_range(a.est_ptr, col, a.est_cap, pe, n_est);
     int tp = 0, fp = 0, fn = 0;
     for (int s0 = blockIdx.y * 256; s0 < col_seg; s0 += LS_SEG_SPLIT * 256) {
@@ -341,14 +355,15 @@ __global__ __launch_bounds__(256) void k_ls_segments(LsArgs a) {
 // one thread per column: the per-column outputs and the class totals
 __global__ __launch_bounds__(256) void k_ls_final(LsArgs a) {
     const long long col = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (col >= (long long)a.n_rec * a.NC) return;
-    const int c = (int)(col % a.NC);
+    const long long ncols = (long long)a.n_rec * a.NC;
+    if (col >= ncols * a.K) return;
+    const int c = (int)(col % a.NC) + (int)(col / ncols) * a.NC;     // the row of the totals: (point, class)
     const int32_t* k = a.cnt + col * LS_CW;
     const int file_seg = ls_file_segments(a, col / a.NC);
-    const bool ok = (a.flags[col * 2] | a.flags[col * 2 + 1] | k[4]) == 0 && file_seg <= LS_MAXSEG;
+    const bool ok = (ls_col_flags(a, col) | k[4]) == 0 && file_seg <= LS_MAXSEG;
     long long p0;
     int n_ref, n_est;
-    ls_range(a.ref_ptr, col, a.ref_cap, p0, n_ref);
+    ls_range(a.ref_ptr, ls_rcol(a, col), a.ref_cap, p0, n_ref);
     ls_range(a.est_ptr, col, a.est_cap, p0, n_est);
     const int ev[3] = {ok ? k[0] : 0, n_ref, n_est};
     int sg[4] = {0, 0, 0, 0};
@@ -394,10 +409,9 @@ __device__ __forceinline__ void lp_window(const double* on, const double* pmax, 
     }
     lo = l;
 }
-// the column of event i of a CSR table (the last column whose offset is <= i); -1 when i is outside it or the column is not scored
-__device__ __forceinline__ long long lp_column(const LsArgs& a, const int64_t* ptr, long long cap, long long i, long long& p0,
+// the column of event i of a CSR table of ncols columns (the last column whose offset is <= i); -1 when i is outside it
+__device__ __forceinline__ long long lp_column(const int64_t* ptr, long long ncols, long long cap, long long i, long long& p0,
                                                int& n) {
-    const long long ncols = (long long)a.n_rec * a.NC;
     long long lo = 0, hi = ncols - 1;
     while (lo < hi) {
         const long long mid = (lo + hi + 1) >> 1;
@@ -405,7 +419,6 @@ __device__ __forceinline__ long long lp_column(const LsArgs& a, const int64_t* p
         else hi = mid - 1;
     }
     if (!ls_range(ptr, lo, cap, p0, n) || i < p0 || i >= p0 + n) return -1;
-    if (a.flags[lo * 2] | a.flags[lo * 2 + 1]) return -1;
     return lo;
 }
 // cnt[col][slot] += 1 for the lanes with `flag`: one atomic per wave when all its lanes are in one column
@@ -422,8 +435,11 @@ __global__ __launch_bounds__(256) void k_lp_detect(LsArgs a) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     long long pe = 0, pr;
     int n_est = 0, n_ref;
-    const long long col = i < a.est_cap ? lp_column(a, a.est_ptr, a.est_cap, i, pe, n_est) : -1;
+    const long long ncols = (long long)a.n_rec * a.NC;
+    long long col = i < a.est_cap ? lp_column(a.est_ptr, ncols * a.K, a.est_cap, i, pe, n_est) : -1;
+    if (col >= 0 && ls_col_flags(a, col)) col = -1;                  // not scored (k_ls_prep reported it)
     const bool active = col >= 0;
+    const long long rcol = active ? col % ncols : 0;
     const long long col0 = __shfl(col, 0);
     const bool uniform = __ballot(col == col0) == ~0ull && col0 >= 0;
     bool relevant = false;
@@ -431,7 +447,7 @@ __global__ __launch_bounds__(256) void k_lp_detect(LsArgs a) {
     if (active) {
         d_on = a.est_on[i];
         d_off = a.est_off[i];
-        ls_range(a.ref_ptr, col, a.ref_cap, pr, n_ref);
+        ls_range(a.ref_ptr, rcol, a.ref_cap, pr, n_ref);
         int lo, hi;
         lp_window(a.ref_on + pr, a.ref_pmax + pr, n_ref, d_on, d_off, lo, hi);
         double sum = 0.0;
@@ -445,8 +461,8 @@ __global__ __launch_bounds__(256) void k_lp_detect(LsArgs a) {
     for (int j = 0; j < a.NC; ++j) {
         bool ct = false;
         if (cross && j != c) {
-            const long long cj = col - c + j;
-            if (a.flags[cj * 2 + 1] == 0) {                          // (a malformed or unsorted reference column raised err)
+            const long long cj = rcol - c + j;
+            if (a.rflags[cj] == 0) {                          // (a malformed or unsorted reference column raised err)
                 ls_range(a.ref_ptr, cj, a.ref_cap, pr, n_ref);
                 int lo, hi;
                 lp_window(a.ref_on + pr, a.ref_pmax + pr, n_ref, d_on, d_off, lo, hi);
@@ -463,7 +479,10 @@ __global__ __launch_bounds__(256) void k_lp_truth(LsArgs a) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     long long pr = 0, pe;
     int n_ref = 0, n_est;
-    const long long col = i < a.ref_cap ? lp_column(a, a.ref_ptr, a.ref_cap, i, pr, n_ref) : -1;
+    const long long ncols = (long long)a.n_rec * a.NC;
+    const long long rcol = i < a.ref_cap ? lp_column(a.ref_ptr, ncols, a.ref_cap, i, pr, n_ref) : -1;
+    long long col = rcol >= 0 ? (long long)blockIdx.y * ncols + rcol : -1;       // blockIdx.y: the operating point
+    if (col >= 0 && ls_col_flags(a, col)) col = -1;
     const bool active = col >= 0;
     const long long col0 = __shfl(col, 0);
     const bool uniform = __ballot(col == col0) == ~0ull && col0 >= 0;
@@ -485,10 +504,11 @@ __global__ __launch_bounds__(256) void k_lp_truth(LsArgs a) {
 __global__ __launch_bounds__(256) void k_lp_final(LsArgs a) {
     const int W = 2 + a.NC;
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= (long long)a.n_rec * a.NC * W) return;
+    const long long ncols = (long long)a.n_rec * a.NC;
+    if (t >= ncols * a.K * W) return;
     const long long col = t / W;
-    const int v = (int)(t - col * W), c = (int)(col % a.NC);
-    const bool ok = (a.flags[col * 2] | a.flags[col * 2 + 1]) == 0;
+    const int v = (int)(t - col * W), c = (int)(col % a.NC) + (int)(col / ncols) * a.NC;
+    const bool ok = ls_col_flags(a, col) == 0;
     const int mine = ok ? a.cnt[col * LS_CW + v] : 0;
     if (a.out_a) a.out_a[t] = mine;
     if (mine > 0) atomicAdd(a.tot_a + c * W + v, (unsigned long long)mine);
@@ -498,12 +518,15 @@ __global__ __launch_bounds__(256) void k_lp_final(LsArgs a) {
 extern "C" int sed_long_tile_events(void) { return LS_TILE; }
 
 static size_t ls_align(size_t v) { return (v + 15) / 16 * 16; }
-struct LsWs { size_t flags, cnt, on, off, epmax, rpmax, rel, total; };
-static LsWs ls_ws(long long est_cap, long long ref_cap, long long ncols) {
+#define LS_MAXK 4096                 // operating points per call (k_lp_truth's second grid dimension)
+struct LsWs { size_t flags, rflags, cnt, on, off, epmax, rpmax, rel, total; };
+// (for K = 1 the two flag arrays take the bytes of the former [ncols][2] array: sed_long_score_ws_bytes is unchanged)
+static LsWs ls_ws(long long est_cap, long long ref_cap, long long ncols, int K) {
     LsWs w;
     size_t o = 0;
-    w.flags = o; o += ls_align((size_t)ncols * 2 * sizeof(int32_t));
-    w.cnt = o;   o += ls_align((size_t)ncols * LS_CW * sizeof(int32_t));
+    w.flags = o;  o += (size_t)K * ncols * sizeof(int32_t);
+    w.rflags = o; o = ls_align(o + (size_t)ncols * sizeof(int32_t));
+    w.cnt = o;   o += ls_align((size_t)K * ncols * LS_CW * sizeof(int32_t));
     w.on = o;    o += ls_align((size_t)est_cap * sizeof(double));
     w.off = o;   o += ls_align((size_t)est_cap * sizeof(double));
     w.epmax = o; o += ls_align((size_t)est_cap * sizeof(double));
@@ -512,29 +535,41 @@ static LsWs ls_ws(long long est_cap, long long ref_cap, long long ncols) {
     w.total = o;
     return w;
 }
-static bool ls_sizes_ok(long long est_cap, long long ref_cap, int n_rec, int nclass) {
+static const char* const LS_NEED = "need 0 <= est_capacity, ref_events < 2^31 - 1024, n_rec >= 1, 1 <= nclass <= 16, "
+                                   "1 <= n_points <= 4096, n_points * n_rec * nclass < 2^26, n_points * reference tiles < 2^31";
+static bool ls_sizes_ok(long long est_cap, long long ref_cap, int n_rec, int nclass, int K) {
     return est_cap >= 0 && ref_cap >= 0 && est_cap < (1ll << 31) - 1024 && ref_cap < (1ll << 31) - 1024 && n_rec >= 1 &&
-           nclass >= 1 && nclass <= LS_MAXNC && (long long)n_rec * nclass < (1ll << 26);
+           nclass >= 1 && nclass <= LS_MAXNC && K >= 1 && K <= LS_MAXK && (long long)K * n_rec * nclass < (1ll << 26) &&
+           (ref_cap / LS_TILE + (long long)n_rec * nclass + 1) * K < (1ll << 31);
+}
+
+extern "C" size_t sed_long_sweep_ws_bytes(long long est_capacity, long long ref_events, int n_rec, int nclass, int n_points) {
+    if (!ls_sizes_ok(est_capacity, ref_events, n_rec, nclass, n_points)) {
+        sed_set_error("sed_long_sweep_ws_bytes: %s", LS_NEED);
+        return 0;
+    }
+    return ls_ws(est_capacity, ref_events, (long long)n_rec * nclass, n_points).total;
 }
 
 extern "C" size_t sed_long_score_ws_bytes(long long est_capacity, long long ref_events, int n_rec, int nclass) {
-    if (!ls_sizes_ok(est_capacity, ref_events, n_rec, nclass)) {
+    if (!ls_sizes_ok(est_capacity, ref_events, n_rec, nclass, 1)) {
         sed_set_error("sed_long_score_ws_bytes: need 0 <= est_capacity, ref_events < 2^31 - 1024, n_rec >= 1, 1 <= nclass <= 16, "
                       "n_rec * nclass < 2^26");
         return 0;
     }
-    return ls_ws(est_capacity, ref_events, (long long)n_rec * nclass).total;
+    return ls_ws(est_capacity, ref_events, (long long)n_rec * nclass, 1).total;
 }
 
 static int ls_fill(LsArgs& a, const char* what, const int64_t* ev_ptr, const int32_t* ev_pairs, double num, double den,
                    const double* est_on, const double* est_off, long long est_cap, const int64_t* ref_ptr, const double* ref_on,
-                   const double* ref_off, long long ref_cap, int n_rec, int nclass, int32_t* err, void* ws, size_t ws_bytes) {
+                   const double* ref_off, long long ref_cap, int n_rec, int nclass, int K, int32_t* err, void* ws,
+                   size_t ws_bytes) {
     if (!(ev_ptr && ref_ptr && ref_on && ref_off && err && ws)) {
         sed_set_error("%s: null argument", what);
         return SED_ERR_BAD_ARG;
     }
-    if (!ls_sizes_ok(est_cap, ref_cap, n_rec, nclass)) {
-        sed_set_error("%s: need 0 <= est_capacity, ref_events < 2^31 - 1024, n_rec >= 1, 1 <= nclass <= 16, n_rec * nclass < 2^26", what);
+    if (!ls_sizes_ok(est_cap, ref_cap, n_rec, nclass, K)) {
+        sed_set_error("%s: %s", what, LS_NEED);
         return SED_ERR_BAD_ARG;
     }
     if (ev_pairs ? !(num > 0.0 && den > 0.0) : !(est_on && est_off)) {
@@ -546,9 +581,9 @@ static int ls_fill(LsArgs& a, const char* what, const int64_t* ev_ptr, const int
         return SED_ERR_BAD_ARG;
     }
     const long long ncols = (long long)n_rec * nclass;
-    const LsWs w = ls_ws(est_cap, ref_cap, ncols);
+    const LsWs w = ls_ws(est_cap, ref_cap, ncols, K);
     if (ws_bytes < w.total) {
-        sed_set_error("%s: workspace of %zu bytes is too small (sed_long_score_ws_bytes: %zu)", what, ws_bytes, w.total);
+        sed_set_error("%s: workspace of %zu bytes is too small (%zu needed)", what, ws_bytes, w.total);
         return SED_ERR_WORKSPACE;
     }
     char* b = (char*)ws;
@@ -557,9 +592,9 @@ static int ls_fill(LsArgs& a, const char* what, const int64_t* ev_ptr, const int
     a.ws_on = (double*)(b + w.on); a.ws_off = (double*)(b + w.off);
     a.est_on = ev_pairs ? a.ws_on : est_on; a.est_off = ev_pairs ? a.ws_off : est_off;
     a.ref_ptr = ref_ptr; a.ref_on = ref_on; a.ref_off = ref_off;
-    a.est_cap = est_cap; a.ref_cap = ref_cap; a.n_rec = n_rec; a.NC = nclass;
+    a.est_cap = est_cap; a.ref_cap = ref_cap; a.n_rec = n_rec; a.NC = nclass; a.K = K;
     a.n_slots = (int)(ref_cap / LS_TILE + ncols + 1);
-    a.flags = (int32_t*)(b + w.flags); a.cnt = (int32_t*)(b + w.cnt);
+    a.flags = (int32_t*)(b + w.flags); a.rflags = (int32_t*)(b + w.rflags); a.cnt = (int32_t*)(b + w.cnt);
     a.est_pmax = (double*)(b + w.epmax); a.ref_pmax = (double*)(b + w.rpmax); a.rel = (uint8_t*)(b + w.rel);
     a.err = err;
     return SED_OK;
@@ -567,32 +602,92 @@ static int ls_fill(LsArgs& a, const char* what, const int64_t* ev_ptr, const int
 
 static unsigned ls_blocks(long long n, int per) { return (unsigned)((n + per - 1) / per > 0 ? (n + per - 1) / per : 1); }
 
+// Four launches whatever n_points is; k_ls_prep walks every point's estimated columns and the reference columns ONCE.
+static int ls_event_counts(const char* what, const int64_t* ev_ptr, const int32_t* ev_pairs, double num, double den,
+                           const double* est_on, const double* est_off, long long est_capacity, const int64_t* ref_ptr,
+                           const double* ref_on, const double* ref_off, long long ref_events, int n_rec, int nclass, int K,
+                           double t_collar, double percentage_of_length, double time_resolution, int32_t* ev_counts,
+                           int32_t* seg_counts, int64_t* ev_total, int64_t* seg_total, int32_t* err, void* ws, size_t ws_bytes,
+                           void* stream) {
+    if (!(ev_total && seg_total)) {
+        sed_set_error("%s: null argument", what);
+        return SED_ERR_BAD_ARG;
+    }
+    if (!(t_collar >= 0.0 && percentage_of_length >= 0.0 && time_resolution > 0.0)) {
+        sed_set_error("%s: need t_collar >= 0, percentage_of_length >= 0, time_resolution > 0", what);
+        return SED_ERR_BAD_ARG;
+    }
+    LsArgs a;
+    SED_TRY(ls_fill(a, what, ev_ptr, ev_pairs, num, den, est_on, est_off, est_capacity, ref_ptr, ref_on, ref_off, ref_events,
+                    n_rec, nclass, K, err, ws, ws_bytes));
+    a.t_collar = t_collar; a.pct = percentage_of_length; a.res = time_resolution;
+    a.out_a = ev_counts; a.out_b = seg_counts;
+    a.tot_a = (unsigned long long*)ev_total; a.tot_b = (unsigned long long*)seg_total;
+    const long long ncols = (long long)n_rec * nclass, ecols = ncols * K;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_ls_prep, dim3((unsigned)(ecols + ncols)), dim3(LS_PREP_THREADS), 0, st, a);
+    SED_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_ls_match, dim3(ls_blocks((long long)a.n_slots * K, 4)), dim3(256), 0, st, a);
+    SED_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_ls_segments, dim3((unsigned)ecols, LS_SEG_SPLIT), dim3(256), 0, st, a);
+    SED_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_ls_final, dim3(ls_blocks(ecols, 256)), dim3(256), 0, st, a);
+    SED_CHECK_LAUNCH();
+    return SED_OK;
+}
+
+static int ls_psds_counts(const char* what, const int64_t* ev_ptr, const int32_t* ev_pairs, double num, double den,
+                          const double* est_on, const double* est_off, long long est_capacity, const int64_t* ref_ptr,
+                          const double* ref_on, const double* ref_off, long long ref_events, int n_rec, int nclass, int K,
+                          double dtc, double gtc, double cttc, int32_t* columns, int64_t* totals, int32_t* err, void* ws,
+                          size_t ws_bytes, void* stream) {
+    if (!totals) {
+        sed_set_error("%s: null argument", what);
+        return SED_ERR_BAD_ARG;
+    }
+    if (!(dtc >= 0.0 && dtc <= 1.0 && gtc >= 0.0 && gtc <= 1.0 && cttc >= 0.0 && cttc <= 1.0)) {
+        sed_set_error("%s: need dtc, gtc and cttc in [0, 1]", what);
+        return SED_ERR_BAD_ARG;
+    }
+    LsArgs a;
+    SED_TRY(ls_fill(a, what, ev_ptr, ev_pairs, num, den, est_on, est_off, est_capacity, ref_ptr, ref_on, ref_off, ref_events,
+                    n_rec, nclass, K, err, ws, ws_bytes));
+    a.dtc = dtc; a.gtc = gtc; a.cttc = cttc;
+    a.out_a = columns; a.tot_a = (unsigned long long*)totals;
+    const long long ncols = (long long)n_rec * nclass, ecols = ncols * K;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_ls_prep, dim3((unsigned)(ecols + ncols)), dim3(LS_PREP_THREADS), 0, st, a);
+    SED_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_lp_detect, dim3(ls_blocks(est_capacity, 256)), dim3(256), 0, st, a);
+    SED_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_lp_truth, dim3(ls_blocks(ref_events, 256), (unsigned)K), dim3(256), 0, st, a);
+    SED_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_lp_final, dim3(ls_blocks(ecols * (2 + nclass), 256)), dim3(256), 0, st, a);
+    SED_CHECK_LAUNCH();
+    return SED_OK;
+}
+
 extern "C" int sed_long_event_counts(const int64_t* ev_ptr, const int32_t* ev_pairs, double num, double den, const double* est_on,
                                      const double* est_off, long long est_capacity, const int64_t* ref_ptr, const double* ref_on,
                                      const double* ref_off, long long ref_events, int n_rec, int nclass, double t_collar,
                                      double percentage_of_length, double time_resolution, int32_t* ev_counts,
                                      int32_t* seg_counts, int64_t* ev_total, int64_t* seg_total, int32_t* err, void* ws,
                                      size_t ws_bytes, void* stream) {
-    SED_CHECK_ARG(ev_total && seg_total, "sed_long_event_counts: null argument");
-    SED_CHECK_ARG(t_collar >= 0.0 && percentage_of_length >= 0.0 && time_resolution > 0.0,
-                  "sed_long_event_counts: need t_collar >= 0, percentage_of_length >= 0, time_resolution > 0");
-    LsArgs a;
-    SED_TRY(ls_fill(a, "sed_long_event_counts", ev_ptr, ev_pairs, num, den, est_on, est_off, est_capacity, ref_ptr, ref_on,
-                    ref_off, ref_events, n_rec, nclass, err, ws, ws_bytes));
-    a.t_collar = t_collar; a.pct = percentage_of_length; a.res = time_resolution;
-    a.out_a = ev_counts; a.out_b = seg_counts;
-    a.tot_a = (unsigned long long*)ev_total; a.tot_b = (unsigned long long*)seg_total;
-    const long long ncols = (long long)n_rec * nclass;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_ls_prep, dim3((unsigned)ncols, 2), dim3(LS_PREP_THREADS), 0, st, a);
-    SED_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_ls_match, dim3(ls_blocks(a.n_slots, 4)), dim3(256), 0, st, a);
-    SED_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_ls_segments, dim3((unsigned)ncols, LS_SEG_SPLIT), dim3(256), 0, st, a);
-    SED_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_ls_final, dim3(ls_blocks(ncols, 256)), dim3(256), 0, st, a);
-    SED_CHECK_LAUNCH();
-    return SED_OK;
+    return ls_event_counts("sed_long_event_counts", ev_ptr, ev_pairs, num, den, est_on, est_off, est_capacity, ref_ptr, ref_on,
+                           ref_off, ref_events, n_rec, nclass, 1, t_collar, percentage_of_length, time_resolution, ev_counts,
+                           seg_counts, ev_total, seg_total, err, ws, ws_bytes, stream);
+}
+
+extern "C" int sed_long_sweep_event_counts(const int64_t* ev_ptr, const int32_t* ev_pairs, double num, double den,
+                                           const double* est_on, const double* est_off, long long est_capacity,
+                                           const int64_t* ref_ptr, const double* ref_on, const double* ref_off,
+                                           long long ref_events, int n_rec, int nclass, int n_points, double t_collar,
+                                           double percentage_of_length, double time_resolution, int32_t* ev_counts,
+                                           int32_t* seg_counts, int64_t* ev_total, int64_t* seg_total, int32_t* err, void* ws,
+                                           size_t ws_bytes, void* stream) {
+    return ls_event_counts("sed_long_sweep_event_counts", ev_ptr, ev_pairs, num, den, est_on, est_off, est_capacity, ref_ptr,
+                           ref_on, ref_off, ref_events, n_rec, nclass, n_points, t_collar, percentage_of_length, time_resolution,
+                           ev_counts, seg_counts, ev_total, seg_total, err, ws, ws_bytes, stream);
 }
 
 extern "C" int sed_long_psds_counts(const int64_t* ev_ptr, const int32_t* ev_pairs, double num, double den, const double* est_on,
@@ -600,23 +695,17 @@ extern "C" int sed_long_psds_counts(const int64_t* ev_ptr, const int32_t* ev_pai
                                     const double* ref_off, long long ref_events, int n_rec, int nclass, double dtc, double gtc,
                                     double cttc, int32_t* columns, int64_t* totals, int32_t* err, void* ws, size_t ws_bytes,
                                     void* stream) {
-    SED_CHECK_ARG(totals, "sed_long_psds_counts: null argument");
-    SED_CHECK_ARG(dtc >= 0.0 && dtc <= 1.0 && gtc >= 0.0 && gtc <= 1.0 && cttc >= 0.0 && cttc <= 1.0,
-                  "sed_long_psds_counts: need dtc, gtc and cttc in [0, 1]");
-    LsArgs a;
-    SED_TRY(ls_fill(a, "sed_long_psds_counts", ev_ptr, ev_pairs, num, den, est_on, est_off, est_capacity, ref_ptr, ref_on,
-                    ref_off, ref_events, n_rec, nclass, err, ws, ws_bytes));
-    a.dtc = dtc; a.gtc = gtc; a.cttc = cttc;
-    a.out_a = columns; a.tot_a = (unsigned long long*)totals;
-    const long long ncols = (long long)n_rec * nclass;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_ls_prep, dim3((unsigned)ncols, 2), dim3(LS_PREP_THREADS), 0, st, a);
-    SED_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_lp_detect, dim3(ls_blocks(est_capacity, 256)), dim3(256), 0, st, a);
-    SED_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_lp_truth, dim3(ls_blocks(ref_events, 256)), dim3(256), 0, st, a);
-    SED_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_lp_final, dim3(ls_blocks(ncols * (2 + nclass), 256)), dim3(256), 0, st, a);
-    SED_CHECK_LAUNCH();
-    return SED_OK;
+    return ls_psds_counts("sed_long_psds_counts", ev_ptr, ev_pairs, num, den, est_on, est_off, est_capacity, ref_ptr, ref_on,
+                          ref_off, ref_events, n_rec, nclass, 1, dtc, gtc, cttc, columns, totals, err, ws, ws_bytes, stream);
+}
+
+extern "C" int sed_long_sweep_psds_counts(const int64_t* ev_ptr, const int32_t* ev_pairs, double num, double den,
+                                          const double* est_on, const double* est_off, long long est_capacity,
+                                          const int64_t* ref_ptr, const double* ref_on, const double* ref_off,
+                                          long long ref_events, int n_rec, int nclass, int n_points, double dtc, double gtc,
+                                          double cttc, int32_t* columns, int64_t* totals, int32_t* err, void* ws, size_t ws_bytes,
+                                          void* stream) {
+    return ls_psds_counts("sed_long_sweep_psds_counts", ev_ptr, ev_pairs, num, den, est_on, est_off, est_capacity, ref_ptr,
+                          ref_on, ref_off, ref_events, n_rec, nclass, n_points, dtc, gtc, cttc, columns, totals, err, ws,
+                          ws_bytes, stream);
 }

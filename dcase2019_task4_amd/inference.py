@@ -9,9 +9,9 @@ only assembles the event table.  There is no CPU fallback: the model and its inp
 Recordings longer than one clip: ``LongRecordingSet`` (longrec.py) holds them as overlapping windows and
 ``get_long_predictions`` blends the windows' posteriors and decodes each recording's whole timeline with one
 ``sed_stitch_decode`` call.  The device-resident event table it leaves is scored by ``metrics.long_event_counts`` /
-``long_psds_counts`` / ``validate_long`` (``sed_long_event_counts``, ``sed_long_psds_counts``: columns of any length).  Out of
-scope there: decoding K operating points from one blend (``validate_long`` blends once per point), recording-level weak tags,
-and windows for training.  ``get_predictions`` itself is unchanged.
+``long_psds_counts`` / ``validate_long`` (``sed_long_event_counts``, ``sed_long_psds_counts``: columns of any length).
+``stitch_sweep`` decodes K operating points from one blend (``sed_stitch_sweep``), scored by ``metrics.long_sweep_*``.  Out of
+scope there: recording-level weak tags and windows for training.  ``get_predictions`` itself is unchanged.
 """
 import ctypes as C
 
@@ -20,7 +20,8 @@ import pandas as pd
 import torch
 
 from . import _lib
-from .longrec import WEIGHTINGS, LongRecordingSet, check_hop_frames, default_hop_frames, window_plan      # noqa: F401
+from .longrec import (WEIGHTINGS, LongRecordingSet, check_hop_frames, default_hop_frames, sweep_chunks,      # noqa: F401
+                      window_plan)
 
 
 class _Cfg:
@@ -186,6 +187,68 @@ def stitch_decode(win_strong, rec_win0, rec_frame0, total_frames, hop3, threshol
                                    WEIGHTINGS[weighting], _lib.ptr(thr), _lib.ptr(win), _lib.ptr(out["timeline"]),
                                    _lib.ptr(out["binary"]), _lib.ptr(out["ev_ptr"]), _lib.ptr(out["ev_pairs"]), int(capacity),
                                    _lib.ptr(ws), ws.numel(), _lib.ptr(out["err"]), _lib.stream_ptr()), "sed_stitch_decode")
+    return out
+
+
+def sweep_points(thresholds, median_windows, nclass):
+    """K operating points as host arrays ``(thr [K, nclass] float32, win [K, nclass] int32)``: two sequences of K entries
+    (one of length 1 is broadcast), every entry a scalar or one value per class.  ValueError otherwise."""
+    thresholds, median_windows = list(thresholds), list(median_windows)
+    K = max(len(thresholds), len(median_windows))
+    if len(thresholds) not in (1, K) or len(median_windows) not in (1, K) or K < 1:
+        raise ValueError("thresholds and median_windows must have equal lengths (or length 1)")
+    thr = np.stack([_per_class(thresholds[k % len(thresholds)], nclass, np.float32, "a threshold") for k in range(K)])
+    win = np.stack([_per_class(median_windows[k % len(median_windows)], nclass, np.int32, "a median window") for k in range(K)])
+    return thr, win
+
+
+def stitch_sweep(win_strong, rec_win0, rec_frame0, total_frames, hop3, thresholds, median_windows, weighting="taper",
+                 capacity=None, want_timeline=False):
+    """``stitch_decode`` at K operating points from ONE blend (``sed_stitch_sweep``: four launches whatever K is).
+    ``thresholds`` / ``median_windows``: sequences of K entries, each a scalar or one value per class (a sequence of length
+    1 is broadcast), or device tensors ``[K, nclass]`` float32 / int32.  Returns the dict of ``stitch_decode`` (``binary``
+    is None: it would be K timelines) plus ``n_points``: ``ev_ptr`` [K * n_rec * nclass + 1] is one CSR over the columns
+    ``(k * n_rec + rec) * nclass + c``, ``ev_pairs`` [capacity, 2] (default: K times ``stitch_decode``'s).  Nothing
+    synchronises."""
+    if weighting not in WEIGHTINGS:
+        raise ValueError(f"weighting must be one of {sorted(WEIGHTINGS)}, got {weighting!r}")
+    if win_strong.dim() != 3:
+        raise ValueError(f"win_strong must be [n_win, T3, nclass], got {tuple(win_strong.shape)}")
+    n_win, T3, NC = win_strong.shape
+    if torch.is_tensor(thresholds) != torch.is_tensor(median_windows):
+        raise ValueError("thresholds and median_windows: both sequences or both device tensors [K, nclass]")
+    if torch.is_tensor(thresholds):
+        thr, win = thresholds, median_windows
+        if thr.dim() != 2 or thr.shape[1] != NC or thr.shape != win.shape or thr.dtype != torch.float32 or win.dtype != torch.int32:
+            raise ValueError(f"device operating points: thresholds float32 and median_windows int32, both [K, {NC}]")
+    else:
+        thr, win = sweep_points(thresholds, median_windows, NC)
+    if win_strong.device.type != "cuda" or (torch.is_tensor(thr) and thr.device.type != "cuda"):
+        raise _lib.SedError("stitch_sweep needs GPU tensors (no CPU fallback)")
+    dev = win_strong.device
+    if not torch.is_tensor(thr):
+        thr, win = torch.from_numpy(thr).to(dev), torch.from_numpy(win).to(dev)
+    thr, win = thr.contiguous(), win.contiguous()
+    K = thr.shape[0]
+    win_strong = win_strong.contiguous().float()
+    n_rec = rec_win0.numel() - 1
+    total = int(total_frames)
+    l = _lib.lib()
+    ws_bytes = l.sed_stitch_sweep_ws_bytes(total, n_rec, NC, K)
+    if ws_bytes == 0:
+        raise ValueError(f"sed_stitch_sweep_ws_bytes: {l.sed_last_error().decode()}")
+    if capacity is None:
+        capacity = K * NC * ((total + n_rec) // 2)          # K times stitch_decode's default
+    out = {"ev_ptr": torch.empty(K * n_rec * NC + 1, dtype=torch.int64, device=dev),
+           "ev_pairs": torch.empty(max(int(capacity), 1), 2, dtype=torch.int32, device=dev),
+           "err": torch.zeros(1, dtype=torch.int32, device=dev),
+           "timeline": torch.empty(total, NC, dtype=torch.float32, device=dev) if want_timeline else None,
+           "binary": None, "n_points": K}
+    ws = _lib.scratch(ws_bytes, dev)
+    _lib.check(l.sed_stitch_sweep(_lib.ptr(win_strong), _lib.ptr(rec_win0), _lib.ptr(rec_frame0), n_rec, T3, NC, int(hop3),
+                                  WEIGHTINGS[weighting], K, _lib.ptr(thr), _lib.ptr(win), _lib.ptr(out["timeline"]),
+                                  _lib.ptr(out["ev_ptr"]), _lib.ptr(out["ev_pairs"]), int(capacity), _lib.ptr(ws), ws.numel(),
+                                  _lib.ptr(out["err"]), _lib.stream_ptr()), "sed_stitch_sweep")
     return out
 
 

@@ -60,6 +60,22 @@ def window_plan(L, frames, pool=8, hop3=None):
     return {"L3": L3, "n_w": n_w, "T3": T3, "hop3": hop3, "start": start, "real": np.minimum(T, L - start), "t0": t0}
 
 
+MAX_SWEEP_POINTS = 4096          # operating points per sed_stitch_sweep / sed_long_sweep_* call
+
+
+def sweep_chunks(K, capacity_per_point, max_table_bytes, limit=2 ** 31 - 1024):
+    """The ranges ``[(k0, k1), ...]`` that split ``K`` operating points into ``sed_stitch_sweep`` calls: consecutive, covering
+    ``0 .. K`` once, each as long as possible with its event table ``(k1 - k0) * capacity_per_point`` rows of 8 bytes
+    (``ev_pairs``) within ``max_table_bytes`` and its capacity below ``limit`` (what the scorers accept); never fewer than one
+    point per chunk, never more than ``MAX_SWEEP_POINTS``."""
+    K, cap = int(K), int(capacity_per_point)
+    if K < 1 or cap < 0:
+        raise ValueError(f"need K >= 1 and capacity_per_point >= 0, got {K}, {cap}")
+    per = K if cap == 0 else min(int(max_table_bytes) // (8 * cap), (int(limit) - 1) // cap)
+    per = max(1, min(per, K, MAX_SWEEP_POINTS))
+    return [(k0, min(k0 + per, K)) for k0 in range(0, K, per)]
+
+
 class LongRecordingSet(ResidentFeatureSet):
     """Recordings of any lengths, resident in one HBM pool; the set's "clips" are their overlapping windows.
 

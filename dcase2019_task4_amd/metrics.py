@@ -32,8 +32,10 @@ on the event table ``inference.stitch_decode`` leaves on the device, or on two `
 (``sed_long_event_counts`` / ``sed_long_psds_counts``, csrc/lscore.hip).  Both sides of a column must be sorted by onset
 (checked on the device).  The matching is exact per CLUSTER - the runs of the merged onset order between cuts across which no
 pair can be compatible (include/dcase_sed.h) -, and a cluster holds at most 64 events per side: beyond that the call raises,
-nothing is truncated.  Not provided there: K operating points from one blend, recording-level weak tags, an exact matching of
-clusters beyond 64 per side.
+nothing is truncated.  K operating points: ``long_sweep_event_counts`` / ``long_sweep_psds_counts`` score the table of
+``inference.stitch_sweep`` (or K ``RefEvents``) against ONE preparation of the reference side, four launches whatever K is
+(``sed_long_sweep_*``); ``validate_long(one_blend=True)`` uses them.  Not provided there: recording-level weak tags, an exact
+matching of clusters beyond 64 per side.
 
 PSDS (polyphonic sound detection score, Bilen et al., ICASSP 2020): ``sed_psds_counts`` scores the same (operating point,
 clip) grid with the three intersection criteria and returns integer class totals (``psds_counts``, ``PSDSCounts``); the
@@ -742,17 +744,147 @@ def long_psds_counts_from_events(est, ref, dtc=0.5, gtc=0.5, cttc=0.3, counts=No
     return _long_psds_call(est_args, cap, ref, dtc, gtc, cttc, counts, point, per_column)
 
 
+# ---- K operating points of long recordings: the table of sed_stitch_sweep (or K given event sets) against one reference ---------
+def _long_sweep_call(fn, est_args, est_cap, ref, K, tail, err, dev):
+    """One ``sed_long_sweep_*`` call; ``est_args`` / ``tail`` as in ``_long_call``."""
+    l = _lib.lib()
+    n, NC, n_ref = len(ref), ref.nclass, len(ref.onset_host)
+    ws_bytes = l.sed_long_sweep_ws_bytes(int(est_cap), n_ref, n, NC, K)
+    if ws_bytes == 0:
+        raise _lib.SedError(f"sed_long_sweep_ws_bytes: {l.sed_last_error().decode()}")
+    ws = _lib.scratch(ws_bytes, dev)
+    ev_ptr, ev_pairs, num, den, on, off = est_args
+    _lib.check(getattr(l, fn)(_lib.ptr(ev_ptr), _lib.ptr(ev_pairs), float(num), float(den), _lib.ptr(on), _lib.ptr(off),
+                              int(est_cap), _lib.ptr(ref.ptr64), _lib.ptr(ref.onset), _lib.ptr(ref.offset), n_ref, n, NC, K,
+                              *tail, _lib.ptr(err), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), fn)
+
+
+def _sweep_decoded_args(decoded, ref, pooling_time_ratio, cfg, what):
+    cfg = cfg or _Cfg
+    ev_ptr, ev_pairs, K = decoded["ev_ptr"], decoded["ev_pairs"], int(decoded.get("n_points", 1))
+    if ev_ptr.device.type != "cuda" or ref.device.type != "cuda":
+        raise _lib.SedError(f"{what} needs the decoded table and a RefEvents on the GPU (no CPU fallback)")
+    if K < 1 or ev_ptr.dtype != torch.int64 or ev_pairs.dtype != torch.int32 or ev_ptr.numel() != K * len(ref) * ref.nclass + 1:
+        raise ValueError(f"decoded: ev_ptr int64 [{K * len(ref) * ref.nclass + 1}] and ev_pairs int32 [capacity, 2] expected "
+                         f"({K} points, {len(ref)} recordings, {ref.nclass} classes)")
+    return (ev_ptr, ev_pairs.contiguous(), float(pooling_time_ratio), float(cfg.sample_rate / cfg.hop_length), None, None), \
+        ev_pairs.shape[0], K
+
+
+def _sweep_events_args(ests, ref, what):
+    """K ``RefEvents`` as one CSR in column order (k, rec, c), assembled on the device (the sizes are known on the host)."""
+    ests = list(ests)
+    if not ests:
+        raise ValueError(f"{what}: need at least one estimated event set")
+    for est in ests:
+        if est.device.type != "cuda" or ref.device.type != "cuda":
+            raise _lib.SedError(f"{what} needs every event set on the GPU (no CPU fallback)")
+        if est.filenames != ref.filenames or est.labels != ref.labels:
+            raise ValueError("estimated and reference events must cover the same files and classes, in the same order")
+    sizes = [len(est.onset_host) for est in ests]
+    base = np.r_[0, np.cumsum(sizes)]
+    ptr = torch.cat([est.ptr64[:-1] + int(base[k]) for k, est in enumerate(ests)] + [ests[-1].ptr64[-1:] + int(base[-2])])
+    on = torch.cat([est.onset[:n] for est, n in zip(ests, sizes)] + [ests[-1].onset[-1:]])        # (one trailing element)
+    off = torch.cat([est.offset[:n] for est, n in zip(ests, sizes)] + [ests[-1].offset[-1:]])
+    return (ptr, None, 0.0, 0.0, on, off), int(base[-1]), len(ests)
+
+
+def _long_sweep_event_call(est_args, est_cap, K, ref, t_collar, percentage_of_length, time_resolution, counts, point0, per_column):
+    n, NC, dev = len(ref), ref.nclass, ref.device
+    if counts is None:
+        counts = Counts(point0 + K, NC, dev)
+    if counts.NC != NC or point0 < 0 or point0 + K > counts.K:
+        raise ValueError(f"counts holds {counts.K} operating points of {counts.NC} classes: no rows {point0} .. "
+                         f"{point0 + K - 1} of {NC} classes")
+    counts.err_what, counts.err_bits = "sed_long_sweep_event_counts", _LONG_ERR_BITS
+    if per_column:
+        counts.ev_columns = torch.empty(K, n, NC, 3, dtype=torch.int32, device=dev)
+        counts.seg_columns = torch.empty(K, n, NC, 4, dtype=torch.int32, device=dev)
+    _long_sweep_call("sed_long_sweep_event_counts", est_args, est_cap, ref, K,
+                     (float(t_collar), float(percentage_of_length), float(time_resolution),
+                      _lib.ptr(counts.ev_columns) if per_column else None, _lib.ptr(counts.seg_columns) if per_column else None,
+                      _lib.ptr(counts.ev[point0]), _lib.ptr(counts.seg[point0])), counts.err, dev)
+    return counts
+
+
+def _long_sweep_psds_call(est_args, est_cap, K, ref, dtc, gtc, cttc, counts, point0, per_column):
+    n, NC, dev = len(ref), ref.nclass, ref.device
+    if counts is None:
+        counts = PSDSCounts(point0 + K, NC, dev, dtc, gtc, cttc)
+    if counts.NC != NC or point0 < 0 or point0 + K > counts.K:
+        raise ValueError(f"counts holds {counts.K} operating points of {counts.NC} classes: no rows {point0} .. "
+                         f"{point0 + K - 1} of {NC} classes")
+    if (counts.dtc, counts.gtc, counts.cttc) != (float(dtc), float(gtc), float(cttc)):
+        raise ValueError("counts was built for other criteria (dtc, gtc, cttc)")
+    counts.err_what, counts.err_bits = "sed_long_sweep_psds_counts", _LONG_ERR_BITS
+    if per_column:
+        counts.columns = torch.empty(K, n, NC, 2 + NC, dtype=torch.int32, device=dev)
+    _long_sweep_call("sed_long_sweep_psds_counts", est_args, est_cap, ref, K,
+                     (counts.dtc, counts.gtc, counts.cttc, _lib.ptr(counts.columns) if per_column else None,
+                      _lib.ptr(counts.totals[point0])), counts.err, dev)
+    return counts
+
+
+def long_sweep_event_counts(decoded, ref, pooling_time_ratio, cfg=None, t_collar=0.200, percentage_of_length=0.2,
+                            time_resolution=1.0, counts=None, point0=0, per_column=False):
+    """``long_event_counts`` for the K operating points ``inference.stitch_sweep`` decoded (``decoded["n_points"]``): ONE
+    ``sed_long_sweep_event_counts`` call, the reference side prepared once.  The totals ACCUMULATE into rows ``point0 ..
+    point0 + K - 1`` of ``counts`` (None: a new ``Counts`` of ``point0 + K`` rows); ``per_column``: ``counts.ev_columns
+    [K, n_rec, nclass, 3]`` / ``seg_columns [K, n_rec, nclass, 4]``.  The decoder's error word is folded in on the device."""
+    est_args, cap, K = _sweep_decoded_args(decoded, ref, pooling_time_ratio, cfg, "long_sweep_event_counts")
+    counts = _long_sweep_event_call(est_args, cap, K, ref, t_collar, percentage_of_length, time_resolution, counts, point0,
+                                    per_column)
+    _fold_decode_err(counts, decoded)
+    return counts
+
+
+def long_sweep_psds_counts(decoded, ref, pooling_time_ratio, cfg=None, dtc=0.5, gtc=0.5, cttc=0.3, counts=None, point0=0,
+                           per_column=False):
+    """``long_sweep_event_counts`` for the PSDS criteria: rows ``point0 .. point0 + K - 1`` of a ``PSDSCounts`` (its criteria
+    must be these); ``per_column``: ``counts.columns [K, n_rec, nclass, 2 + nclass]``."""
+    est_args, cap, K = _sweep_decoded_args(decoded, ref, pooling_time_ratio, cfg, "long_sweep_psds_counts")
+    counts = _long_sweep_psds_call(est_args, cap, K, ref, dtc, gtc, cttc, counts, point0, per_column)
+    _fold_decode_err(counts, decoded)
+    return counts
+
+
+def long_sweep_event_counts_from_events(ests, ref, t_collar=0.200, percentage_of_length=0.2, time_resolution=1.0, counts=None,
+                                        point0=0, per_column=False):
+    """The scoring stage alone: ``ests`` is a list of K ``RefEvents``, the estimated events of K operating points (same files
+    and classes as ``ref``, sorted by onset), scored in one call against the one reference side."""
+    est_args, cap, K = _sweep_events_args(ests, ref, "long_sweep_event_counts_from_events")
+    return _long_sweep_event_call(est_args, cap, K, ref, t_collar, percentage_of_length, time_resolution, counts, point0,
+                                  per_column)
+
+
+def long_sweep_psds_counts_from_events(ests, ref, dtc=0.5, gtc=0.5, cttc=0.3, counts=None, point0=0, per_column=False):
+    """The PSDS criteria alone on a list of K ``RefEvents`` against one reference side."""
+    est_args, cap, K = _sweep_events_args(ests, ref, "long_sweep_psds_counts_from_events")
+    return _long_sweep_psds_call(est_args, cap, K, ref, dtc, gtc, cttc, counts, point0, per_column)
+
+
 def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, batch_size=64, cfg=None, weighting="taper",
-                  psds=None):
-    """``validate`` for a ``LongRecordingSet``: the windows go through the model ONCE; per operating point one
-    ``stitch_decode`` of the window posteriors and ``long_event_counts`` into row k (the blend is repeated per point:
-    decoding K points from one blend is not provided); ONE device -> host copy at the end.  ``thresholds``: K entries, each
+                  psds=None, one_blend=True, max_table_bytes=1 << 30):
+    """``validate`` for a ``LongRecordingSet``: the windows go through the model ONCE, then the K operating points are
+    decoded and scored, and ONE device -> host copy ends the call.  ``one_blend=True``: the points are split into chunks
+    (``longrec.sweep_chunks``: the event table of a chunk stays within ``max_table_bytes``); per chunk ONE
+    ``inference.stitch_sweep`` blends once and decodes all its points, and one ``long_sweep_event_counts`` (and
+    ``long_sweep_psds_counts``) scores them against one preparation of the reference.  ``one_blend=False``: per point one
+    ``stitch_decode`` and ``long_event_counts`` into row k, the blend repeated per point.  The two routes return identical
+    integers; one blend is the default because it measured faster on both workloads of tools/long_bench.py --sweep
+    (profiles/long_sweep.json).  ``thresholds``: K entries, each
     a scalar or one value per class; ``median_windows``: the same (or one entry for all points; None: ``cfg.median_window``).
     ``ref``: the ``RefEvents`` of the recordings, in the set's order.  ``psds``: a ``PSDSCounts`` of the same K points, filled
-    by ``long_psds_counts`` from the same decodes (read it with ``PSDS.from_counts(psds, ref, long_set.durations())``).
+    from the same decodes (read it with ``PSDS.from_counts(psds, ref, long_set.durations())``).
     Returns one ``(EventMetrics, SegmentMetrics)`` per operating point."""
-    from .inference import long_window_posteriors, stitch_decode
-    from .longrec import LongRecordingSet
+    from .inference import long_window_posteriors, stitch_decode, stitch_sweep, sweep_points
+    from .longrec import LongRecordingSet, sweep_chunks
+    cfg = cfg or _Cfg
+    thresholds = list(thresholds)
+    median_windows = [cfg.median_window] if median_windows is None else list(median_windows)
+    K = max(len(thresholds), len(median_windows))
+    if len(thresholds) not in (1, K) or len(median_windows) not in (1, K) or K < 1:
+        raise ValueError("thresholds and median_windows must have equal lengths (or length 1)")
     if not isinstance(long_set, LongRecordingSet):
         raise TypeError(f"long_set must be a LongRecordingSet, got {type(long_set).__name__}")
     if not getattr(model, "hot_path", False):
@@ -762,23 +894,30 @@ def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, 
         raise _lib.SedError("validate_long needs the model on the GPU (no CPU fallback)")
     if long_set.n_rec != len(ref):
         raise ValueError(f"{long_set.n_rec} recordings but reference events of {len(ref)}")
-    cfg = cfg or _Cfg
     NC = ref.nclass
-    thresholds = list(thresholds)
-    median_windows = [cfg.median_window] if median_windows is None else list(median_windows)
-    K = max(len(thresholds), len(median_windows))
-    if len(thresholds) not in (1, K) or len(median_windows) not in (1, K) or K < 1:
-        raise ValueError("thresholds and median_windows must have equal lengths (or length 1)")
     if psds is not None and (psds.K, psds.NC) != (K, NC):
         raise ValueError("psds was built for another number of operating points / classes")
+    if one_blend:
+        thr_all, win_all = sweep_points(thresholds, median_windows, NC)
     counts = Counts(K, NC, dev)
     win_strong = long_window_posteriors(model, long_set, NC, batch_size)
-    for k in range(K):
-        out = stitch_decode(win_strong, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3,
-                            thresholds[k % len(thresholds)], median_windows[k % len(median_windows)], weighting,
-                            long_set.capacity(NC), want_timeline=False)
-        long_event_counts(out, ref, long_set.pooling_time_ratio, cfg, counts=counts, point=k)
-        if psds is not None:
-            long_psds_counts(out, ref, long_set.pooling_time_ratio, cfg, psds.dtc, psds.gtc, psds.cttc, counts=psds, point=k)
+    if one_blend:
+        cap = long_set.capacity(NC)
+        for k0, k1 in sweep_chunks(K, cap, max_table_bytes):
+            out = stitch_sweep(win_strong, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3,
+                               torch.from_numpy(thr_all[k0:k1]).to(dev), torch.from_numpy(win_all[k0:k1]).to(dev), weighting,
+                               (k1 - k0) * cap)
+            long_sweep_event_counts(out, ref, long_set.pooling_time_ratio, cfg, counts=counts, point0=k0)
+            if psds is not None:
+                long_sweep_psds_counts(out, ref, long_set.pooling_time_ratio, cfg, psds.dtc, psds.gtc, psds.cttc, counts=psds,
+                                       point0=k0)
+    else:
+        for k in range(K):
+            out = stitch_decode(win_strong, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3,
+                                thresholds[k % len(thresholds)], median_windows[k % len(median_windows)], weighting,
+                                long_set.capacity(NC), want_timeline=False)
+            long_event_counts(out, ref, long_set.pooling_time_ratio, cfg, counts=counts, point=k)
+            if psds is not None:
+                long_psds_counts(out, ref, long_set.pooling_time_ratio, cfg, psds.dtc, psds.gtc, psds.cttc, counts=psds, point=k)
     ev, seg = counts.host()
     return [(EventMetrics(ref.labels, ev[k]), SegmentMetrics(ref.labels, seg[k])) for k in range(K)]

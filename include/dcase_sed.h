@@ -505,6 +505,36 @@ int sed_stitch_decode(const float* win_strong, const int32_t* rec_win0, const in
                       uint8_t* binary, int64_t* ev_ptr, int32_t* ev_pairs, long long capacity, void* ws,
                       size_t ws_bytes, int32_t* err, void* stream);
 
+/* ---- K operating points from one blend ----------------------------------------------------------
+ * sed_stitch_sweep decodes n_points = K operating points of the same window posteriors in one call: for every point k the
+ * result is what sed_stitch_decode defines for thr[k], win[k] - the same blend with the same rounding, the same decision,
+ * median filter (reflection only at a recording's two ends) and run-length decode (one code: csrc/post.h and the
+ * blend of csrc/stitch.hip).  Nothing new is defined; pinned is byte-for-byte agreement with K calls of sed_stitch_decode.
+ *   thr [K][NC] fp32, win [K][NC] int32  device: per (point, class) threshold and median window
+ *   timeline [sum L3][NC]  fp32 blended posteriors or NULL: written once, it does not depend on k
+ *   ev_ptr   [K * n_rec * NC + 1] int64: ONE CSR over all columns, column (k, rec, c) = (k * n_rec + rec) * NC + c, in index
+ *            order, ALWAYS the true counts; point k is the columns k * n_rec * NC .. (k + 1) * n_rec * NC
+ *   ev_pairs [capacity][2] int32 (onset, exclusive offset) in timeline frames of the recording, in time order
+ *   There is no `binary` output: it would be K timelines.  Use sed_stitch_decode for the filtered decisions of one point.
+ *   err      one int32, OR-ed, the bits of sed_stitch_decode: 2 = more events over ALL points than `capacity` (nothing is
+ *            written at or beyond it, never a truncated table), 8 = a window outside 1 .. 63 at some (point, class): that
+ *            column is not decoded, every other one is; 16 / 32 = malformed tables / an uncovered recording, as above.
+ *            The address guarantee of sed_stitch_decode holds (one validation of the tables gates every access).
+ *   ws       sed_stitch_sweep_ws_bytes(sum L3, n_rec, NC, K) bytes, 8-byte aligned; ws_bytes must be that value (the tile
+ *            slots are derived from it: a size that is not a whole number of slots is refused)
+ * Four launches whatever K is: count pass, column scan, pointer scan, write pass.  A workgroup blends the frames of its
+ * tile ONCE per pass into LDS and takes the decisions, filters and counts of sed_stitch_sweep_point_group() points from
+ * it; the grid's second dimension is the point group, each group blends again.  No host synchronisation, no allocation,
+ * no float atomics (the only atomic is the OR into err), integer results bit-reproducible, hipGraph-capturable.
+ * Limits, checked before any launch (SED_ERR_BAD_ARG): 1 <= K <= 4096, K * n_rec * NC < 2^26, sum L3 * NC < 2^31,
+ * K * tile slots < 2^31, and NC, T3, hop3 as for sed_stitch_decode. */
+size_t sed_stitch_sweep_ws_bytes(long long total_frames, int n_rec, int nclass, int n_points);
+int sed_stitch_sweep_point_group(void);
+int sed_stitch_sweep(const float* win_strong, const int32_t* rec_win0, const int64_t* rec_frame0, int n_rec, int T3,
+                     int NC, int hop3, int weighting, int n_points, const float* thr, const int32_t* win,
+                     float* timeline, int64_t* ev_ptr, int32_t* ev_pairs, long long capacity, void* ws, size_t ws_bytes,
+                     int32_t* err, void* stream);
+
 /* ---- validation scoring ------------------------------------------------------------------------
  * Replaces, after get_predictions, the host-side scoring of the epoch loop (baseline/main.py:328-352):
  *   compute_strong_metrics(predictions, valid_synth_df) (evaluation_measures.py:234-246) = sed_eval's
@@ -593,7 +623,7 @@ int sed_psds_counts(const float* strong, int n_clips, int T, int nclass, int n_p
  * Pinned: exact agreement with tests/sed_eval_np.py and tests/psds_np.py, which state the definitions for lists of any
  * length; parity with sed_eval / psds_eval stays UNPINNED as above.
  *
- * Columns are (recording, class) = rec * nclass + class.  One operating point per call.
+ * Columns are (recording, class) = rec * nclass + class.  One operating point per call (K points: the sweep calls below).
  *   estimated events  ev_ptr [n_rec * nclass + 1] int64 CSR offsets, and either
  *                     ev_pairs [est_capacity][2] int32 (onset, exclusive offset) frames as sed_stitch_decode writes them:
  *                       seconds = (double)frame * num / den, the host's doubles bit for bit (est_on / est_off ignored), or
@@ -651,6 +681,40 @@ int sed_long_psds_counts(const int64_t* ev_ptr, const int32_t* ev_pairs, double 
                          const double* ref_off, long long ref_events, int n_rec, int nclass, double dtc, double gtc,
                          double cttc, int32_t* columns, int64_t* totals, int32_t* err, void* ws, size_t ws_bytes,
                          void* stream);
+
+/* ---- scoring K operating points of long recordings ---------------------------------------------
+ * sed_long_sweep_event_counts / sed_long_sweep_psds_counts are the two calls above for n_points = K estimated tables
+ * against ONE reference side.  The definitions are exactly those of the one-point calls (clusters between valid cuts,
+ * an exact matching per cluster of at most 64 events per side, segments, DTC / GTC / CTTC with sequential fp64 sums in
+ * stored order); pinned is byte-for-byte agreement with K one-point calls.
+ *   estimated side    the table of sed_stitch_sweep: ev_ptr [K * n_rec * nclass + 1] int64, column (k, rec, c) =
+ *                     (k * n_rec + rec) * nclass + c, with ev_pairs [est_capacity][2] frames, or ev_pairs == NULL and
+ *                     est_on / est_off [est_capacity] fp64 seconds in the same column order
+ *   reference side    unchanged: ref_ptr [n_rec * nclass + 1], shared by all points; estimated column (k, rec, c) is
+ *                     scored against reference column (rec, c)
+ *   The recording-level quantities are (k, rec)-level: the segment count of a file is taken over the reference events
+ *   and point k's estimated events only.
+ *   ev_counts [K][n_rec][nclass][3], seg_counts [K][n_rec][nclass][4], columns [K][n_rec][nclass][2 + nclass] int32 or
+ *   NULL (every element is written); ev_total [K][nclass][3], seg_total [K][nclass][4], totals [K][nclass][2 + nclass]
+ *   int64, ACCUMULATED over calls.  err: the bits of the one-point calls; a column that is not scored stays unscored in
+ *   its own point only (a reference column that is not scored is unscored at every point).
+ * Four launches per call whatever K is.  Everything that derives from the reference alone - the validation of its
+ * offsets, the order check, the running maxima of its offsets - is done once per call, not once per point.
+ * ws: sed_long_sweep_ws_bytes(est_capacity, ref_events, n_rec, nclass, K) bytes, 8-byte aligned.
+ * The guarantees are those of the one-point calls.  Limits: 1 <= K <= 4096, K * n_rec * nclass < 2^26, est_capacity
+ * (all points together) and ref_events < 2^31 - 1024, K * (ref_events / sed_long_tile_events() + n_rec * nclass + 1) < 2^31. */
+size_t sed_long_sweep_ws_bytes(long long est_capacity, long long ref_events, int n_rec, int nclass, int n_points);
+int sed_long_sweep_event_counts(const int64_t* ev_ptr, const int32_t* ev_pairs, double num, double den,
+                                const double* est_on, const double* est_off, long long est_capacity,
+                                const int64_t* ref_ptr, const double* ref_on, const double* ref_off, long long ref_events,
+                                int n_rec, int nclass, int n_points, double t_collar, double percentage_of_length,
+                                double time_resolution, int32_t* ev_counts, int32_t* seg_counts, int64_t* ev_total,
+                                int64_t* seg_total, int32_t* err, void* ws, size_t ws_bytes, void* stream);
+int sed_long_sweep_psds_counts(const int64_t* ev_ptr, const int32_t* ev_pairs, double num, double den,
+                               const double* est_on, const double* est_off, long long est_capacity,
+                               const int64_t* ref_ptr, const double* ref_on, const double* ref_off, long long ref_events,
+                               int n_rec, int nclass, int n_points, double dtc, double gtc, double cttc, int32_t* columns,
+                               int64_t* totals, int32_t* err, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- single-kernel replay (measurement) ----------------------------------------------------
  * Re-launches ONE kernel of the step on the buffers left by a finished sed_crnn_forward +

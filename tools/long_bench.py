@@ -23,7 +23,8 @@ that leg only).
 workloads at the default hop, legs alternated in the same way:
   predictions       get_long_predictions (inference the user already pays; ends with the host copy of the event table)
   validate_1        metrics.validate_long at one operating point (forward, decode, sed_long_event_counts, one host copy)
-  validate_50_psds  validate_long at 50 thresholds with a PSDSCounts (50 decodes, 50 + 50 scoring calls, two host copies)
+  validate_50_psds  validate_long at 50 thresholds with a PSDSCounts, by its default route (profiles/long_scoring.json was
+                    recorded with the per-point loop: 50 decodes, 50 + 50 scoring calls; the sweep legs below time both routes)
 and metrics.long_event_counts / long_psds_counts alone on a decoded table (device-event pair around each call, median of
 --decode-reps).  The references are the decoded events of the first operating point, jittered (dropped with p = 0.15, both
 ends moved by up to 0.3 s, sorted by onset).  The thresholds are per-class quantiles of the blended posteriors: the lowest of
@@ -31,7 +32,17 @@ ends moved by up to 0.3 s, sorted by onset).  The thresholds are per-class quant
 50 points run from that quantile up to 0.99).  There is no earlier route to compare against: the clip scorer raises on these
 columns.
 
-Usage: python tools/long_bench.py [--scoring] [--rounds 5] [--decode-reps 30] [--out profiles/long_inference.json]"""
+--scoring also measures the K-point sweep (profiles/long_sweep.json; --sweep measures these legs alone), on the same two
+workloads at the same 50 thresholds with PSDS:
+  validate_long(one_blend=True) against validate_long(one_blend=False) - the per-point loop, the only route before the sweep -
+    alternated in one run, --rounds rounds, medians; the results of the two routes are compared (they are integers).  One
+    blend counts as faster only where the difference of the medians exceeds the larger of the two legs' (max - min).
+  sed_stitch_sweep alone at K = 50 against 50 calls of sed_stitch_decode, and the two sweep scorers alone at K = 50 against 50
+    calls of the one-point scorers: a device-event pair around the call(s), median of --decode-reps, same run.
+  The library's point-group size (sed_stitch_sweep_point_group) is recorded; --sweep-decode-only measures sed_stitch_sweep alone
+  (a variant build with another group size, SED_LIB), and --candidates FILE,... copies such runs into the result.
+
+Usage: python tools/long_bench.py [--scoring | --sweep] [--rounds 5] [--decode-reps 30] [--out profiles/long_inference.json]"""
 import argparse
 import json
 import os
@@ -198,7 +209,7 @@ def largest_cluster(ref_on, est_on, t_collar=0.2):
     return int(np.bincount(cluster[side == 0], minlength=n).max()), int(np.bincount(cluster[side == 1], minlength=n).max())
 
 
-def scoring_workload(name, model, rounds, reps):
+def scoring_workload(name, model, rounds, reps, setup_only=False):
     from dcase2019_task4_amd import metrics
     n_rec, per = WORKLOADS[name]
     recs = recordings(n_rec, per)
@@ -246,6 +257,9 @@ def scoring_workload(name, model, rounds, reps):
                 "median_window": window, "estimated_events": int(ev_ptr[-1]), "reference_events": int(ref_ptr[-1]),
                 "longest_column": {"estimated": int(np.diff(ev_ptr).max()), "reference": int(np.diff(ref_ptr).max())},
                 "largest_cluster": {"reference": biggest[0], "estimated": biggest[1]}}
+    ctx = {"ls": ls, "win_strong": win_strong, "ref_ev": ref_ev, "thr50": thr50, "window": window}
+    if setup_only:                                                   # (--sweep-decode-only: the inputs, nothing timed here)
+        return out_info, ctx
     state = {}
 
     def validate_50():
@@ -293,12 +307,115 @@ def scoring_workload(name, model, rounds, reps):
         c.host()                                                     # raises when the error word is set
         st = stats(t)
         out_info[what + "_alone"] = {"median_ms": st["median_ms"], "spread": st["spread"], "reps": reps}
-    return out_info
+    return out_info, ctx
+
+
+def event_ms(call, reps):
+    """Median and spread of `reps` single device-event pairs around call(), after 5 warm calls."""
+    for _ in range(5):
+        call()
+    torch.cuda.synchronize()
+    t = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        call()
+        e1.record()
+        torch.cuda.synchronize()
+        t.append(e0.elapsed_time(e1))
+    st = stats(t)
+    return {"median_ms": st["median_ms"], "spread": st["spread"], "reps": reps}
+
+
+def sweep_decode_alone(ctx, reps):
+    """sed_stitch_sweep at K = 50 and 50 calls of sed_stitch_decode, the C calls on preallocated buffers."""
+    ls, win_strong = ctx["ls"], ctx["win_strong"]
+    l, dev, ptr = _lib.lib(), win_strong.device, _lib.ptr
+    K, total, n_rec, cap = len(ctx["thr50"]), ls.total_frames, ls.n_rec, ls.capacity(NCLASS)
+    thr = torch.from_numpy(np.stack(ctx["thr50"]).astype(np.float32)).to(dev)
+    win = torch.full((K, NCLASS), ctx["window"], dtype=torch.int32, device=dev)
+    ev_ptr = torch.empty(K * n_rec * NCLASS + 1, dtype=torch.int64, device=dev)
+    ev_pairs = torch.empty(K * cap, 2, dtype=torch.int32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = torch.empty(l.sed_stitch_sweep_ws_bytes(total, n_rec, NCLASS, K), dtype=torch.uint8, device=dev)
+    ws1 = torch.empty(l.sed_stitch_decode_ws_bytes(total, n_rec, NCLASS), dtype=torch.uint8, device=dev)
+
+    def sweep():
+        _lib.check(l.sed_stitch_sweep(ptr(win_strong), ptr(ls.rec_win0), ptr(ls.rec_frame0), n_rec, ls.T3, NCLASS, ls.hop3, 1, K,
+                                      ptr(thr), ptr(win), None, ptr(ev_ptr), ptr(ev_pairs), K * cap, ptr(ws), ws.numel(),
+                                      ptr(err), _lib.stream_ptr()), "sed_stitch_sweep")
+
+    def loop():
+        for k in range(K):
+            _lib.check(l.sed_stitch_decode(ptr(win_strong), ptr(ls.rec_win0), ptr(ls.rec_frame0), n_rec, ls.T3, NCLASS, ls.hop3,
+                                           1, ptr(thr[k]), ptr(win[k]), None, None, ptr(ev_ptr), ptr(ev_pairs), cap, ptr(ws1),
+                                           ws1.numel(), ptr(err), _lib.stream_ptr()), "sed_stitch_decode")
+    out = {"point_group": int(l.sed_stitch_sweep_point_group()), "n_points": K, "sed_stitch_sweep": event_ms(sweep, reps)}
+    events = int(ev_ptr[-1].item())
+    out["events_all_points"] = events
+    out["sed_stitch_decode_x50"] = event_ms(loop, reps)
+    assert int(err.item()) == 0
+    return out
+
+
+def sweep_workload(name, ctx, model, rounds, reps, decode_only):
+    from dcase2019_task4_amd import metrics
+    ls, ref_ev, thr50, window = ctx["ls"], ctx["ref_ev"], ctx["thr50"], ctx["window"]
+    out = sweep_decode_alone(ctx, reps)
+    if decode_only:
+        return out
+    K = len(thr50)
+    state = {}
+
+    def validate(one_blend):
+        def fn():
+            psds = metrics.PSDSCounts(K, NCLASS, "cuda")
+            res = metrics.validate_long(model, ls, ref_ev, thr50, [window], batch_size=BATCH, psds=psds, one_blend=one_blend)
+            state[one_blend] = ([(e.class_wise, s.class_wise, s.Ntn) for e, s in res], psds.host().tobytes())
+        return fn
+    legs = {"validate_50_psds_loop": validate(False), "validate_50_psds_one_blend": validate(True)}
+    for fn in legs.values():
+        fn()
+    out["routes_identical"] = state[True] == state[False]
+    ms = {leg: [] for leg in legs}
+    for _ in range(rounds):
+        for leg, fn in legs.items():
+            ms[leg].append(wall_ms(fn))
+    for leg in legs:
+        out[leg] = stats(ms[leg])
+    a, b = out["validate_50_psds_loop"], out["validate_50_psds_one_blend"]
+    band = max(max(x["samples_ms"]) - min(x["samples_ms"]) for x in (a, b))
+    out["one_blend_minus_loop_ms"] = b["median_ms"] - a["median_ms"]
+    out["larger_max_minus_min_ms"] = band
+    out["one_blend_faster"] = bool(a["median_ms"] - b["median_ms"] > band)
+    # the scorers alone: the sweep table at K = 50 against 50 one-point tables (Python calls: workspace allocation + 4 launches)
+    cap = ls.capacity(NCLASS)
+    sweep_tab = inference.stitch_sweep(ctx["win_strong"], ls.rec_win0, ls.rec_frame0, ls.total_frames, ls.hop3, thr50, [window],
+                                       "taper", K * cap)
+    tabs = [inference.stitch_decode(ctx["win_strong"], ls.rec_win0, ls.rec_frame0, ls.total_frames, ls.hop3, t, window, "taper",
+                                    cap, want_timeline=False) for t in thr50]
+    ec, pc = metrics.Counts(K, NCLASS, "cuda"), metrics.PSDSCounts(K, NCLASS, "cuda")
+
+    def loop(fn):
+        def call():
+            for k, tab in enumerate(tabs):
+                fn(tab, ref_ev, POOL, counts=ec if fn is metrics.long_event_counts else pc, point=k)
+        return call
+    out["sed_long_sweep_event_counts"] = event_ms(lambda: metrics.long_sweep_event_counts(sweep_tab, ref_ev, POOL, counts=ec), reps)
+    out["sed_long_event_counts_x50"] = event_ms(loop(metrics.long_event_counts), reps)
+    out["sed_long_sweep_psds_counts"] = event_ms(lambda: metrics.long_sweep_psds_counts(sweep_tab, ref_ev, POOL, counts=pc), reps)
+    out["sed_long_psds_counts_x50"] = event_ms(loop(metrics.long_psds_counts), reps)
+    ec.host(), pc.host()                                              # raise when an error word is set
+    return out
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scoring", action="store_true", help="measure the scoring of the long path's event table instead")
+    ap.add_argument("--sweep", action="store_true", help="measure the K-point sweep legs alone (profiles/long_sweep.json)")
+    ap.add_argument("--sweep-decode-only", action="store_true", help="with --sweep: sed_stitch_sweep alone (a variant build)")
+    ap.add_argument("--sweep-out", default=os.path.join(REPO, "profiles", "long_sweep.json"))
+    ap.add_argument("--candidates", default="", help="with --sweep: earlier --sweep-decode-only results to copy in")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--decode-reps", type=int, default=30)
     ap.add_argument("--workloads", default=",".join(WORKLOADS))
@@ -319,6 +436,14 @@ def main():
               "not_measured": ["from_waveforms / feature extraction", "other batch sizes, bf16 / wide models",
                                "recordings longer than 1 h", "a run with the GPU to itself (the host is shared)"],
               "workloads": {}}
+    if args.sweep:
+        args.scoring, args.out = True, None
+    sweep = dict(result, workloads={}, timing="validate_long legs: host clock around each synchronised call, alternated; the calls "
+                 "alone: a device-event pair around the call(s), warm, median of --decode-reps",
+                 note="the loop leg (one_blend=False) is the code path of the commit before the sweep; one blend counts as faster "
+                 "only where the difference of the medians exceeds the larger of the two legs' (max - min)",
+                 not_measured=result["not_measured"] + ["other K than 50", "other median windows",
+                                                        "max_table_bytes small enough to split the points into chunks"])
     if args.scoring:
         result["timing"] = ("host clock around each synchronised call, legs alternated; the scoring calls alone: a device-event "
                             "pair around the Python call (workspace allocation and four launches)")
@@ -326,8 +451,25 @@ def main():
                           "earlier route exists (sed_event_counts raises beyond 64 events per column)")
         result["not_measured"] += ["the kernels one by one", "given-events mode", "other t_collar / resolutions"]
     for name in args.workloads.split(","):
-        result["workloads"][name] = (scoring_workload if args.scoring else workload)(name, model, args.rounds, args.decode_reps)
-        print(json.dumps({name: result["workloads"][name]}), flush=True)
+        if args.scoring:
+            result["workloads"][name], ctx = scoring_workload(name, model, args.rounds, args.decode_reps, setup_only=args.sweep)
+            sweep["workloads"][name] = sweep_workload(name, ctx, model, args.rounds, args.decode_reps, args.sweep_decode_only)
+            print(json.dumps({"sweep_" + name: sweep["workloads"][name]}), flush=True)
+            del ctx
+        else:
+            result["workloads"][name] = workload(name, model, args.rounds, args.decode_reps)
+        if not args.sweep:
+            print(json.dumps({name: result["workloads"][name]}), flush=True)
+    if args.scoring:
+        for path in filter(None, args.candidates.split(",")):
+            with open(path) as f:
+                other = json.load(f)
+            for name, w in other["workloads"].items():
+                sweep["workloads"][name].setdefault("point_group_candidates", []).append(
+                    {"point_group": w["point_group"], "sed_stitch_sweep": w["sed_stitch_sweep"]})
+        os.makedirs(os.path.dirname(os.path.abspath(args.sweep_out)), exist_ok=True)
+        with open(args.sweep_out, "w") as f:
+            f.write(json.dumps(sweep, indent=1) + "\n")
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
