@@ -64,18 +64,31 @@ __device__ __forceinline__ void x_moments_body(const float* __restrict__ x, int 
     __shared__ float red[4][10][10];
     const int tid = threadIdx.x, b = blockIdx.y, t0 = blockIdx.x * MOM_ROWS;
     // the tile (rows t0-1 .. t0+MOM_ROWS of 64 floats) is contiguous in x: float4 loads, zero rows outside the clip
+    // All five float4 of a thread are requested back to back from a clamped item and a clamped row, and only then zeroed and
+    // stored.  Written as `load; if (outside) v = 0` per item, the compiler sank every load under an exec mask of its own
+    // (t >= 0, e in range) with its own s_waitcnt vmcnt(0) in front of the LDS stores: five serialized HBM round trips.  The
+    // empty asm pins the five loads in front of one wait: the values must exist, unconditionally, where it stands.
+    constexpr int MOM_ITEMS = (MOM_ROWS + 2) * 16, MOM_LD = (MOM_ITEMS + 255) / 256;
+    float4 v[MOM_LD];
 #pragma unroll
-    for (int k = 0; k < ((MOM_ROWS + 2) * 16 + 255) / 256; ++k) {
+    for (int k = 0; k < MOM_LD; ++k) {
+        const int e = min(tid + 256 * k, MOM_ITEMS - 1);
+        const int r = e >> 4, c4 = e & 15, t = t0 - 1 + r;
+        const int tc = t < 0 ? 0 : (t >= T ? T - 1 : t);
+        v[k] = *(const float4*)&x[((size_t)b * T + tc) * 64 + 4 * c4];
+    }
+    static_assert(MOM_LD == 5, "the asm below names five float4");
+    asm volatile("" : "+v"(v[0].x), "+v"(v[0].y), "+v"(v[0].z), "+v"(v[0].w), "+v"(v[1].x), "+v"(v[1].y), "+v"(v[1].z), "+v"(v[1].w),
+                      "+v"(v[2].x), "+v"(v[2].y), "+v"(v[2].z), "+v"(v[2].w), "+v"(v[3].x), "+v"(v[3].y), "+v"(v[3].z), "+v"(v[3].w),
+                      "+v"(v[4].x), "+v"(v[4].y), "+v"(v[4].z), "+v"(v[4].w));
+#pragma unroll
+    for (int k = 0; k < MOM_LD; ++k) {
         const int e = tid + 256 * k;
-        if (e < (MOM_ROWS + 2) * 16) {
+        if (e < MOM_ITEMS) {
             const int r = e >> 4, c4 = e & 15, t = t0 - 1 + r;
-            // unconditional load from a clamped row, zeroed afterwards: under `if (in range)` every one of the five loads of a
-            // thread was a branch with its own s_waitcnt - five serialized HBM round trips, half of this kernel's 15 us
-            const int tc = t < 0 ? 0 : (t >= T ? T - 1 : t);
-            float4 v = *(const float4*)&x[((size_t)b * T + tc) * 64 + 4 * c4];
-            if (t < 0 || t >= T) v = float4{0.f, 0.f, 0.f, 0.f};
+            if (t < 0 || t >= T) v[k] = float4{0.f, 0.f, 0.f, 0.f};
             float* d = &xs[r * XS_W + 1 + 4 * c4];
-            d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+            d[0] = v[k].x; d[1] = v[k].y; d[2] = v[k].z; d[3] = v[k].w;
         }
     }
     if (tid < 2 * (MOM_ROWS + 2)) xs[(tid >> 1) * XS_W + (tid & 1) * 65] = 0.f;
@@ -906,16 +919,56 @@ __global__ __launch_bounds__(640) void k_blk0_bwd_finalize(Blk0BwdFinArgs a) {
     __shared__ double moms[54];
     __shared__ float Wc[128][16];               // W_glu[co][c0 .. c0 + 16): this workgroup's columns of the S sum below
     const int tid = threadIdx.x, C = a.C, c0 = blockIdx.x * 16;
-    // (requested up front, 64 contiguous bytes per row: as `a.wglu[co * C + c]` inside the S loop every one of its 16 - 32 trips was a
-    // strided global load behind an fp64 accumulation - 20 us solo at C = 128, at the very end of the wide step)
-    for (int e = tid; e < C * 16; e += 640) Wc[e >> 4][e & 15] = a.wglu[(size_t)(e >> 4) * C + c0 + (e & 15)];
-    for (int e = tid; e < C * 10; e += 640) {   // (c, t)
-        const int c = e / 10, t = e % 10;
-        const double scale = a.bn[2 * C + c], shift = a.bn[3 * C + c];
-        wzs[c][t] = (t < 9) ? scale * (double)a.w0[c * 9 + t] : scale * (double)a.b0[c] + shift;
-        Ds[c][t] = a.de[c * 10 + t];
+    // EVERYTHING this kernel reads from global memory is requested here, before anything waits - one round trip instead of ten:
+    // the staging items of the two loops below (C <= 128, the size of the LDS arrays: at most 4 and 2 trips of 640 threads; items
+    // past the end read the last one), the moments, E's element of this thread's (c, t) (it used to be read behind the first
+    // barrier) and the per-channel rows of the last phase (read again by tid < 16 behind the second one).  No load sits under a
+    // branch and every clamped address lies in its own tensor; w0 / b0 of the (c, t) loop are one load through a selected
+    // address.  The empty asm keeps the compiler from sinking the loads back under the `e < ...` / `tid < ...` conditions
+    // of their uses (each a branch with its own s_waitcnt vmcnt(0)).
+    float wc_r[4], sc_r[2], sh_r[2], wb_r[2];
+    double de_r[2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int e = min(tid + 640 * i, C * 16 - 1);
+        // (64 contiguous bytes per row: as `a.wglu[co * C + c]` inside the S loop every one of its 16 - 32 trips was a strided
+        // global load behind an fp64 accumulation - 20 us solo at C = 128, at the very end of the wide step)
+        wc_r[i] = a.wglu[(size_t)(e >> 4) * C + c0 + (e & 15)];
     }
-    if (tid < 54) moms[tid] = a.mom[tid];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int e = min(tid + 640 * i, C * 10 - 1), c = e / 10, t = e % 10;
+        sc_r[i] = a.bn[2 * C + c]; sh_r[i] = a.bn[3 * C + c];
+        wb_r[i] = *((t < 9) ? &a.w0[c * 9 + t] : &a.b0[c]);
+        de_r[i] = a.de[c * 10 + t];
+    }
+    double mom_r = a.mom[min(tid, 53)];
+    double e_ct = a.de[C * 10 + (c0 + (tid >> 2) / 10) * 10 + (tid >> 2) % 10];
+    const int c_fin = c0 + min(tid, 15);
+    float mean_f = a.bn[c_fin], invstd_f = a.bn[C + c_fin], scale_f = a.bn[2 * C + c_fin], b_f = a.b0[c_fin];
+    float w_f[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) w_f[t] = a.w0[c_fin * 9 + t];
+    asm volatile("" : "+v"(wc_r[0]), "+v"(wc_r[1]), "+v"(wc_r[2]), "+v"(wc_r[3]), "+v"(sc_r[0]), "+v"(sc_r[1]), "+v"(sh_r[0]), "+v"(sh_r[1]),
+                      "+v"(wb_r[0]), "+v"(wb_r[1]), "+v"(de_r[0]), "+v"(de_r[1]), "+v"(mom_r), "+v"(e_ct), "+v"(mean_f), "+v"(invstd_f),
+                      "+v"(scale_f), "+v"(b_f), "+v"(w_f[0]), "+v"(w_f[1]), "+v"(w_f[2]), "+v"(w_f[3]), "+v"(w_f[4]), "+v"(w_f[5]),
+                      "+v"(w_f[6]), "+v"(w_f[7]), "+v"(w_f[8]));
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int e = tid + 640 * i;
+        if (e < C * 16) Wc[e >> 4][e & 15] = wc_r[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {                // (c, t)
+        const int e = tid + 640 * i;
+        if (e < C * 10) {
+            const int c = e / 10, t = e % 10;
+            const double scale = sc_r[i], shift = sh_r[i];
+            wzs[c][t] = (t < 9) ? scale * (double)wb_r[i] : scale * (double)wb_r[i] + shift;
+            Ds[c][t] = de_r[i];
+        }
+    }
+    if (tid < 54) moms[tid] = mom_r;
     __syncthreads();
     // GLU linear: dWglu[co][k] = sum_t D[co][t] wz[k][t] for co in this workgroup's 16 rows;  dbglu[co] = D[co][9]
     for (int e = tid; e < 16 * C; e += 640) {
@@ -928,21 +981,21 @@ __global__ __launch_bounds__(640) void k_blk0_bwd_finalize(Blk0BwdFinArgs a) {
     // total dz against the patch: S[c][t] = sum_co Wglu[co][c] D[co][t] + E[c][t], 4 threads per (c, t) over co quarters
     {
         const int e = tid >> 2, part = tid & 3;        // e < 160
-        const int c = c0 + e / 10, t = e % 10;
+        const int t = e % 10;
         double acc = 0;
         for (int co = part; co < C; co += 4) acc += (double)Wc[co][e / 10] * Ds[co][t];
         acc += __shfl_xor(acc, 1);
         acc += __shfl_xor(acc, 2);
-        if (part == 0) Ss[e / 10][t] = acc + a.de[C * 10 + c * 10 + t];
+        if (part == 0) Ss[e / 10][t] = acc + e_ct;
     }
     __syncthreads();
     if (tid < 16) {
         const int cl = tid, c = c0 + cl;
-        const double mean = a.bn[c], invstd = a.bn[C + c], scale = a.bn[2 * C + c];
+        const double mean = mean_f, invstd = invstd_f, scale = scale_f;
         double w[9];
 #pragma unroll
-        for (int t = 0; t < 9; ++t) w[t] = a.w0[c * 9 + t];
-        const double b = a.b0[c];
+        for (int t = 0; t < 9; ++t) w[t] = w_f[t];
+        const double b = b_f;
         a.g_bglu[c] = (float)Ds[c][9];
         const double Sdz = Ss[cl][9];
         double Sdzu = b * Sdz;

@@ -33,7 +33,6 @@ struct BnPrepArgs {
     int train, update; float eps, momentum;
     float* bn;
 };
-__device__ __forceinline__ void bn_prep_body(const BnPrepArgs& a, int c, bool publish, float* bn_s);
 
 // pixel index (into [B][H][W]) of MFMA row m of the row block starting at pooled pixel q0
 __device__ __forceinline__ int rb_pixel(int q, int dt, int df, int H, int W, int Ho, int Wo) {
@@ -52,12 +51,11 @@ __device__ __forceinline__ void tile_load(YTile& t, const float* __restrict__ y,
 #pragma unroll
     for (int it = 0; it < 8; ++it) {
         const int m = (lane >> 4) + 4 * it, c4 = (lane & 15) * 4;
-        const int q = q0 + (m >> 3);
-        t.v[it] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (q < Q) {
-            const int pix = rb_pixel(q, (m >> 2) & 1, m & 3, H, W, Ho, Wo);
-            t.v[it] = *(const float4*)(y + (size_t)pix * 64 + c4);
-        }
+        // rows past the last pooled pixel read the last pixel's window instead of sitting under a branch (a branch per
+        // load, each with a wait of its own); tile_store never uses what they hold
+        const int q = min(q0 + (m >> 3), Q - 1);
+        const int pix = rb_pixel(q, (m >> 2) & 1, m & 3, H, W, Ho, Wo);
+        t.v[it] = *(const float4*)(y + (size_t)pix * 64 + c4);
     }
 }
 template <bool KEEP_Y>
@@ -66,9 +64,10 @@ __device__ __forceinline__ void tile_store(const YTile& t, const float4& sc, con
 #pragma unroll
     for (int it = 0; it < 8; ++it) {
         const int m = (lane >> 4) + 4 * it, c4 = (lane & 15) * 4;
-        const float4 v = t.v[it];
+        float4 v = t.v[it];
         float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (q0 + (m >> 3) < Q) {
+        if (q0 + (m >> 3) >= Q) v = make_float4(0.f, 0.f, 0.f, 0.f);
+        else {
             z.x = fmaf(v.x, sc.x, sh.x); z.y = fmaf(v.y, sc.y, sh.y);
             z.z = fmaf(v.z, sc.z, sh.z); z.w = fmaf(v.w, sc.w, sh.w);
         }
@@ -85,24 +84,33 @@ __device__ __forceinline__ void tile_store(const YTile& t, const float4& sc, con
 // (64 threads, a few fp64 operations) instead of as a 1-workgroup kernel of its own in front: one launch and one
 // dependency gap less on the forward chain per conv block.  Workgroup 0 also publishes bn[] for the backward and
 // updates the running statistics.
-__device__ __forceinline__ void bn_prep_body(const BnPrepArgs& a, int c, bool publish, float* bn_s /* LDS [256] */) {
+// In two halves: bn_prep_load only REQUESTS the operands (every branch in it is uniform over the launch or the workgroup, and nothing
+// in it waits), so that the caller can put its other prologue loads into the same round trip; bn_prep_body does the arithmetic.
+struct BnPrepOperands { double s0, s1; float rm, rv, gamma, beta; };
+__device__ __forceinline__ BnPrepOperands bn_prep_load(const BnPrepArgs& a, int c, bool publish) {
+    BnPrepOperands o = {0.0, 0.0, 0.f, 0.f, a.gamma[c], a.beta[c]};
+    if (a.train) { o.s0 = a.stat[c]; o.s1 = a.stat[64 + c]; }
+    if (!a.train || (a.update && publish)) { o.rm = a.run_mean[c]; o.rv = a.run_var[c]; }
+    return o;
+}
+__device__ __forceinline__ void bn_prep_body(const BnPrepArgs& a, const BnPrepOperands& o, int c, bool publish, float* bn_s /* LDS [256] */) {
     double mean, var;
     if (a.train) {
-        mean = a.stat[c] / a.N;
-        var = a.stat[64 + c] / a.N - mean * mean;
+        mean = o.s0 / a.N;
+        var = o.s1 / a.N - mean * mean;
         if (var < 0) var = 0;
         if (a.update && publish) {
-            a.run_mean[c] = (float)((1.0 - a.momentum) * a.run_mean[c] + a.momentum * mean);
-            a.run_var[c] = (float)((1.0 - a.momentum) * a.run_var[c] + a.momentum * var * a.N / (a.N - 1.0));
+            a.run_mean[c] = (float)((1.0 - a.momentum) * o.rm + a.momentum * mean);
+            a.run_var[c] = (float)((1.0 - a.momentum) * o.rv + a.momentum * var * a.N / (a.N - 1.0));
             if (c == 0 && a.tracked) a.tracked[0] += 1;
         }
     } else {
-        mean = a.run_mean[c];
-        var = a.run_var[c];
+        mean = o.rm;
+        var = o.rv;
     }
     const double invstd = 1.0 / sqrt(var + (double)a.eps);
-    const double scale = a.gamma[c] * invstd;
-    const float v0 = (float)mean, v1 = (float)invstd, v2 = (float)scale, v3 = (float)(a.beta[c] - mean * scale);
+    const double scale = o.gamma * invstd;
+    const float v0 = (float)mean, v1 = (float)invstd, v2 = (float)scale, v3 = (float)(o.beta - mean * scale);
     bn_s[c] = v0; bn_s[64 + c] = v1; bn_s[128 + c] = v2; bn_s[192 + c] = v3;
     if (publish) { a.bn[c] = v0; a.bn[64 + c] = v1; a.bn[128 + c] = v2; a.bn[192 + c] = v3; }
 }
@@ -118,9 +126,31 @@ __global__ __launch_bounds__(256, 2) void k_glu_pool_fwd(const float* __restrict
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int n = lane & 31, kh = lane >> 5;
     float* zt = zts[wv];
-    if (tid < 64) bn_prep_body(bnp, tid, blockIdx.x == 0, bn_s);
+    // One round trip for the whole prologue: the BatchNorm operands (wave 0, requested first so that its fp64 arithmetic
+    // starts while the rest is in flight), bglu, the seed, Wglu (four float4 per thread) and the first y tile are all
+    // requested before anything waits.  (Before: the BN operands in four dependent groups with every other wave at the
+    // barrier, Wglu dword by dword with a wait per trip, bglu and the y tile only behind the barrier - 15 drain points.)
+    const int n_rb = (Q + 3) / 4;
+    BnPrepOperands bno = {};
+    if (tid < 64) bno = bn_prep_load(bnp, tid, blockIdx.x == 0);
+    const float bg[2] = {bglu[n], bglu[32 + n]};
+    const uint64_t seed = use_drop ? seed_ptr[0] : 0ull;
+    float4 wq[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) wq[i] = ((const float4*)wglu)[tid + 256 * i];
+    YTile yt_n;
+    if (blockIdx.x * 4 + wv < n_rb) tile_load(yt_n, y, (blockIdx.x * 4 + wv) * 4, Q, H, W, Ho, Wo, lane);
+    // (the empty asm keeps wave 0's arithmetic - and its wait - behind the requests above: the compiler had merged the two
+    // `tid < 64` blocks in front of them)
+    asm volatile("" : "+v"(bno.s0), "+v"(bno.s1), "+v"(bno.rm), "+v"(bno.rv), "+v"(bno.gamma), "+v"(bno.beta));
+    if (tid < 64) bn_prep_body(bnp, bno, tid, blockIdx.x == 0, bn_s);
     const float* bn = bn_s;
-    for (int e = tid; e < 4096; e += 256) WsT[(e & 63) * ZS + (e >> 6)] = wglu[e];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int e = 4 * (tid + 256 * i);                // Wglu[co = e >> 6][c = e & 63 .. + 3]
+        float* d = &WsT[(e & 63) * ZS + (e >> 6)];
+        d[0] = wq[i].x; d[ZS] = wq[i].y; d[2 * ZS] = wq[i].z; d[3 * ZS] = wq[i].w;
+    }
     __syncthreads();
     float bw[32][2];
 #pragma unroll
@@ -128,15 +158,10 @@ __global__ __launch_bounds__(256, 2) void k_glu_pool_fwd(const float* __restrict
         bw[s][0] = WsT[(2 * s + kh) * ZS + n];            // B[k = c][j = co] = Wglu[co][c]
         bw[s][1] = WsT[(2 * s + kh) * ZS + 32 + n];
     }
-    const float bg[2] = {bglu[n], bglu[32 + n]};
-    const uint64_t seed = use_drop ? seed_ptr[0] : 0ull;
     const uint32_t thr = drop_thresh8(p_drop);
     const bool one_bit = (thr == 128u);
     const float sc = 0.125f * (use_drop ? drop_scale8(p_drop) : 1.0f);
-    const int n_rb = (Q + 3) / 4;
     const float4 bsc = *(const float4*)(bn + 128 + (lane & 15) * 4), bsh = *(const float4*)(bn + 192 + (lane & 15) * 4);
-    YTile yt_n;
-    if (blockIdx.x * 4 + wv < n_rb) tile_load(yt_n, y, (blockIdx.x * 4 + wv) * 4, Q, H, W, Ho, Wo, lane);
     for (int rb = blockIdx.x * 4 + wv; rb < n_rb; rb += gridDim.x * 4) {
         const int q0 = rb * 4;
         tile_store<false>(yt_n, bsc, bsh, zt, nullptr, q0, Q, lane);
@@ -225,12 +250,11 @@ __global__ __launch_bounds__(512, 1) void k_glu_pool_bwd8(const float* __restric
             dz[((size_t)bb * H + (H - 1)) * W * 64 + r] = 0.f;
         }
     }
-    for (int e = tid; e < 4096; e += 512) WsT[(e & 63) * ZS + (e >> 6)] = wglu[e];
-    __syncthreads();
-    float bw[32];                                            // phase 1: B[k = c][j = co own half] = Wglu[co][c]
+    // Wglu is requested here (two float4 per thread) and goes to LDS only behind the first row block's prefetch below: one round
+    // trip for the whole prologue (as `WsT[..] = wglu[e]` dword by dword in front of everything it was two of its own)
+    float4 wq[2];
 #pragma unroll
-    for (int s = 0; s < 32; ++s) bw[s] = WsT[(2 * s + kh) * ZS + c_own];
-    const float* BT = WsT + c_own * ZS + kh;                 // phase 2: B[k = co][j = c own half] = WsT[c][co]
+    for (int i = 0; i < 2; ++i) wq[i] = ((const float4*)wglu)[tid + 512 * i];
     const float bgl = bglu[c_own];
     const float sc = 0.125f * (use_drop ? drop_scale8(p_drop) : 1.0f);
     f32x16 dW[2];                                            // dW[co own half][c block b2]
@@ -271,6 +295,8 @@ __global__ __launch_bounds__(512, 1) void k_glu_pool_bwd8(const float* __restric
         q_n = valid ? rbn * 4 : 0;
         pixel_offsets(q_n, po_n);
     };
+    const bool has_b = dp_b != nullptr;
+    const float* dp_2 = has_b ? dp_b : dp;
     auto prefetch_slice = [&](int k) {                         // k in 0..3
         // rows it = 4 hf + k: pooled pixel 2 hf + (k >> 1) (selected without indexing po_n by a run-time value, which
         // would put the array in scratch), image row dt = k & 1
@@ -278,8 +304,12 @@ __global__ __launch_bounds__(512, 1) void k_glu_pool_bwd8(const float* __restric
         yv[k] = *(const f32x4*)((const char*)y + (pbase + (uint32_t)((k & 1) * W) * 256u + ld_off));
         const int q = q_n + k;
         const uint32_t goff = (uint32_t)((q < Q ? q : 0) * 64 + c_own) * 4u;
-        gq_n[k] = *(const float*)((const char*)dp + goff);
-        if (dp_b) gq_n[k] += *(const float*)((const char*)dp_b + goff);
+        // both planes unconditionally (the second pointer is the first again when there is one plane) and a select: as
+        // `if (dp_b) gq += load` this was a uniform branch whose load was followed at once by s_waitcnt vmcnt(0), which
+        // also drained the yv and dp loads just issued - four times per prefetch, in front of phase 1's MFMAs.
+        // (a select, not `+ 0.f`: that would turn a -0 gradient into +0)
+        const float ga = *(const float*)((const char*)dp + goff), gb = *(const float*)((const char*)dp_2 + goff);
+        gq_n[k] = has_b ? ga + gb : ga;
         if (q >= Q) gq_n[k] = 0.f;
         if (k == 0) m_n = use_drop ? (uint32_t)mask_in[((size_t)(q_n >> 2) * 2 + hf) * 64 + lane] : 0xffffu;
     };
@@ -287,6 +317,20 @@ __global__ __launch_bounds__(512, 1) void k_glu_pool_bwd8(const float* __restric
     prefetch_begin(rb0, rb0 < n_rb);
 #pragma unroll
     for (int k = 0; k < 4; ++k) prefetch_slice(k);
+    // (the empty asm keeps slices 1 - 3 in front of the barrier: y and dp are read-only, so the compiler was free to sink their
+    // loads behind it, and did - the gradient loads behind a wait of their own, the y loads behind a second one)
+    asm volatile("" : "+v"(yv[0]), "+v"(yv[1]), "+v"(yv[2]), "+v"(yv[3]), "+v"(gq_n[0]), "+v"(gq_n[1]), "+v"(gq_n[2]), "+v"(gq_n[3]));
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int e = 4 * (tid + 512 * i);                   // Wglu[co = e >> 6][c = e & 63 .. + 3]
+        float* d = &WsT[(e & 63) * ZS + (e >> 6)];
+        d[0] = wq[i].x; d[ZS] = wq[i].y; d[2 * ZS] = wq[i].z; d[3 * ZS] = wq[i].w;
+    }
+    __syncthreads();
+    float bw[32];                                            // phase 1: B[k = c][j = co own half] = Wglu[co][c]
+#pragma unroll
+    for (int s = 0; s < 32; ++s) bw[s] = WsT[(2 * s + kh) * ZS + c_own];
+    const float* BT = WsT + c_own * ZS + kh;                 // phase 2: B[k = co][j = c own half] = WsT[c][co]
     // every pair runs the same number of trips (the barriers are workgroup-wide); pairs past the end idle through them
     const int trips = (n_rb - blockIdx.x * 4 + gridDim.x * 4 - 1) / (gridDim.x * 4);
     for (int trip = 0; trip < trips; ++trip) {
@@ -441,6 +485,7 @@ int launch_glu_pool_fwd(const float* y, const double* stat, double N, const floa
     BnPrepArgs a;
     a.stat = stat; a.N = N; a.gamma = gamma; a.beta = beta; a.run_mean = run_mean; a.run_var = run_var;
     a.tracked = tracked; a.train = train; a.update = update; a.eps = eps; a.momentum = momentum; a.bn = bn;
+    SED_CHECK_ARG(((uintptr_t)wglu & 15) == 0, "glu weight must be 16-byte aligned (float4 staging loads)");
     const int Ho = H / 2, Wo = W / 4, Q = B * Ho * Wo;
     const int n_rb = (Q + 3) / 4;
     int grid = (n_rb + 3) / 4;
@@ -454,6 +499,7 @@ int launch_glu_pool_bwd(const float* y, const float* bn, const float* wglu, cons
                         const float* dp_b, float* dz, double* acc, int zero_acc, int B, int H, int W, int use_drop, float p_drop,
                         const uint16_t* mask_in, const float* gamma, float* coef, float* g_gamma, float* g_beta, float* g_wglu,
                         float* g_bglu, float* g_convb, BnBwdPrepArgs* prep_out, hipStream_t st) {
+    SED_CHECK_ARG(((uintptr_t)wglu & 15) == 0, "glu weight must be 16-byte aligned (float4 staging loads)");
     const int Ho = H / 2, Wo = W / 4, Q = B * Ho * Wo;
     const size_t lds = (size_t)(4 * 3 * 32 * ZS + 64 * ZS) * sizeof(float);
     static thread_local SedAttrOnce attr_done;
