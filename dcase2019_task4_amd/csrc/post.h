@@ -5,7 +5,8 @@
 
 #define PP_MAXT 2048      // frames per column held in LDS (T/8: clips up to 16 384 input frames)
 
-// The rules every decode shares (k_stitch_tile of stitch.hip holds a column in tiles and applies the same ones):
+// The rules every decode shares (k_stitch_tile<VEC, PASS, SWEEP> of stitch.hip, the one tile kernel of sed_stitch_decode and
+// sed_stitch_sweep, holds a column in tiles and applies the same ones):
 // the decision is p > threshold (dcase_util's global_threshold binarization, strict);
 __device__ __forceinline__ uint8_t pp_decision(float p, float threshold) { return (p > threshold) ? 1 : 0; }
 // scipy's "reflect" of an index into [0, T): -1 -> 0, -2 -> 1, T -> T-1, T+1 -> T-2, repeatedly for windows longer than the column;

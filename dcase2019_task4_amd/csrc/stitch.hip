@@ -5,14 +5,15 @@
 //
 // A column (recording, class) has no length limit, so it is split along time: a workgroup owns ST_TILE timeline frames of
 // one recording, all classes (the NC floats of a frame are contiguous in the window posteriors and in the timeline).
-//   k_stitch_tile<VEC, 0>  blends its frames plus a halo of ST_HALO frames per side (or the reflection at a recording end)
-//                          into 0/1 decisions in LDS, median-filters them there (the true neighbours across tile edges),
-//                          writes timeline / binary, and counts the onsets of every class with wave ballots
+//   k_stitch_tile<VEC, 0, SWEEP>  blends its frames plus a halo of ST_HALO frames per side (or the reflection at a recording
+//                          end) into 0/1 decisions in LDS, median-filters them there (the true neighbours across tile
+//                          edges), writes timeline / binary, and counts the onsets of every class with wave ballots
 //   k_stitch_scan_cols     one wave per column: exclusive scan of the tile counts in place, the column's total
 //   k_stitch_scan_ptr      one workgroup: ev_ptr = exclusive scan of the column totals; capacity check
-//   k_stitch_tile<VEC, 1>  recomputes the tile and writes its (onset, offset) frames at ev_ptr[col] + rank
-// sed_stitch_sweep decodes K operating points from ONE blend per workgroup with the same four launches
-// (k_stitch_sweep_tile below; the two scans are shared: a column is then (point, recording, class)).
+//   k_stitch_tile<VEC, 1, SWEEP>  recomputes the tile and writes its (onset, offset) frames at ev_ptr[col] + rank
+// sed_stitch_sweep decodes K operating points from ONE blend per workgroup with the same four launches and the same
+// kernels: SWEEP = true keeps the blend in LDS and loops over a group of points, a column is then (point, recording, class);
+// sed_stitch_decode is SWEEP = false, one point.  Both entries go through one host path (st_run).
 // Onsets and offsets alternate along a column, so the offsets in front of a tile are the onsets in front of it minus one
 // when an event is open across the tile's first edge: one count per (tile, class) is enough.
 //
@@ -116,8 +117,24 @@ __device__ __forceinline__ f32x4 st_blend(const StArgs& a, const StRec& R, int u
     return p;
 }
 
-template <bool VEC, int PASS>
+// ---- K operating points from one blend --------------------------------------------------------------------------------------
+// The blend does not depend on the threshold or the median window, so sed_stitch_sweep's workgroup (SWEEP = true) blends its
+// tile's ST_EXT frames ONCE into LDS (fp32, all classes) and takes the decisions, filters and counts of ST_SWEEP_GROUP points
+// from it, one point after the other through the same raw / flt arrays.  The grid's second dimension is the point group:
+// blockIdx.y owns the points y * ST_SWEEP_GROUP .. and blends again.  cnt is [K][n_slots][NC] and a column is (point,
+// recording, class).  sed_stitch_decode is the SWEEP = false instantiation: one point, no fp32 array, the decisions are
+// written straight from the blend.
+#ifndef ST_SWEEP_GROUP
+#define ST_SWEEP_GROUP 8
+#endif
+#define ST_SWEEP_MAXK 4096
+
+template <bool SWEEP> struct StBlendLds { float v[ST_MAXC * ST_EXT]; };
+template <> struct StBlendLds<false> {};
+
+template <bool VEC, int PASS, bool SWEEP>
 __global__ __launch_bounds__(ST_THREADS) void k_stitch_tile(StArgs a) {
+    __shared__ StBlendLds<SWEEP> pst;
     __shared__ uint8_t raw[ST_MAXC * ST_EXT];
     __shared__ uint8_t flt[ST_MAXC * ST_FLT];
     __shared__ float s_thr[ST_MAXC];
@@ -138,80 +155,98 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_tile(StArgs a) {
     if (kt < 0 || kt >= R.tiles) return;                                         // an empty slot
     const int L3 = R.L3, s = (int)kt * ST_TILE, e = min(s + ST_TILE, L3);
     const int ext_lo = max(s - ST_HALO, 0), ext_n = min(e + ST_HALO, L3) - ext_lo;
-    if (tid < NC) {
-        const int w = a.win[tid];
-        s_thr[tid] = a.thr[tid];
-        s_win[tid] = (w >= 1 && w <= 63) ? w : 0;
-        if (PASS == 0 && kt == 0 && !(w >= 1 && w <= 63)) atomicOr(a.err, 8);
-    }
-    __syncthreads();
-    // ---- blend + decision: frames ext_lo .. ext_lo + ext_n - 1, all classes ------------------------------------------------
+    const int k_lo = SWEEP ? blockIdx.y * ST_SWEEP_GROUP : 0, k_hi = SWEEP ? min(k_lo + ST_SWEEP_GROUP, a.K) : 1;
+    auto load_point = [&](int kp) {                                              // threshold and window of point kp, per class
+        if (tid < NC) {
+            const int w = a.win[kp * NC + tid];
+            s_thr[tid] = a.thr[kp * NC + tid];
+            s_win[tid] = (w >= 1 && w <= 63) ? w : 0;
+            if (PASS == 0 && kt == 0 && !(w >= 1 && w <= 63)) atomicOr(a.err, 8);
+        }
+        __syncthreads();
+    };
+    if constexpr (!SWEEP) load_point(0);
+    // ---- the blend, once: frames ext_lo .. ext_lo + ext_n - 1, all classes; the decode's decisions straight from it --------
     {
         const int G = VEC ? NC >> 2 : NC;
-        float* tl = (PASS == 0 && a.timeline) ? a.timeline + (size_t)R.f0 * NC : nullptr;
+        float* tl = (PASS == 0 && a.timeline && (!SWEEP || blockIdx.y == 0)) ? a.timeline + (size_t)R.f0 * NC : nullptr;
+        auto keep = [&](int c, int fl, float p) {
+            if constexpr (SWEEP) pst.v[c * ST_EXT + fl] = p;
+            else raw[c * ST_EXT + fl] = pp_decision(p, s_thr[c]);
+        };
         for (int it = tid; it < ext_n * G; it += ST_THREADS) {
             const int fl = it / G, q = it - fl * G, u = ext_lo + fl;
             const f32x4 p = st_blend<VEC>(a, R, u, q);
             if (VEC) {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) raw[(4 * q + k) * ST_EXT + fl] = pp_decision(p[k], s_thr[4 * q + k]);
+                for (int k = 0; k < 4; ++k) keep(4 * q + k, fl, p[k]);
                 if (tl && u >= s && u < e) *(f32x4*)(tl + (size_t)u * NC + 4 * q) = p;
             } else {
-                raw[q * ST_EXT + fl] = pp_decision(p[0], s_thr[q]);
+                keep(q, fl, p[0]);
                 if (tl && u >= s && u < e) tl[(size_t)u * NC + q] = p[0];
             }
         }
     }
-    __syncthreads();
-    // ---- median filter of frames s - 1 .. e (post.h's rule; reflection only at the recording's two ends) --------------------
     const int n_flt = e - s + 2;
-    for (int it = tid; it < NC * n_flt; it += ST_THREADS) {
-        const int c = it / n_flt, k = it - c * n_flt, t = s - 1 + k;
-        const int window = s_win[c];
-        uint8_t v = 0;
-        if (t >= 0 && t < L3 && window) {
-            const int lo = window / 2, need = window - window / 2;
-            const uint8_t* col = raw + c * ST_EXT - ext_lo;
-            int ones = 0;
-            for (int d = 0; d < window; ++d) ones += col[pp_reflect(t - lo + d, L3)];
-            v = ones >= need ? 1 : 0;
+    for (int kp = k_lo; kp < k_hi; ++kp) {
+        if constexpr (SWEEP) {
+            load_point(kp);                                                      // (the first barrier also publishes pst)
+            for (int it = tid; it < NC * ext_n; it += ST_THREADS) {
+                const int c = it / ext_n, fl = it - c * ext_n;
+                raw[c * ST_EXT + fl] = pp_decision(pst.v[c * ST_EXT + fl], s_thr[c]);
+            }
         }
-        flt[c * ST_FLT + k] = v;
-    }
-    __syncthreads();
-    if (PASS == 0 && a.binary) {
-        uint8_t* bin = a.binary + (size_t)R.f0 * NC;
-        for (int it = tid; it < (e - s) * NC; it += ST_THREADS) {
-            const int fl = it / NC, c = it - fl * NC;
-            if (s_win[c]) bin[(size_t)(s + fl) * NC + c] = flt[c * ST_FLT + fl + 1];
+        __syncthreads();
+        // ---- median filter of frames s - 1 .. e (post.h's rule; reflection only at the recording's two ends) ----------------
+        for (int it = tid; it < NC * n_flt; it += ST_THREADS) {
+            const int c = it / n_flt, k = it - c * n_flt, t = s - 1 + k;
+            const int window = s_win[c];
+            uint8_t v = 0;
+            if (t >= 0 && t < L3 && window) {
+                const int lo = window / 2, need = window - window / 2;
+                const uint8_t* col = raw + c * ST_EXT - ext_lo;
+                int ones = 0;
+                for (int d = 0; d < window; ++d) ones += col[pp_reflect(t - lo + d, L3)];
+                v = ones >= need ? 1 : 0;
+            }
+            flt[c * ST_FLT + k] = v;
         }
-    }
-    // ---- onsets / offsets of the tile: one wave per class, 64 frames per ballot ---------------------------------------------
-    const size_t slot = (size_t)g * NC;
-    for (int c = wave; c < NC; c += ST_THREADS / 64) {
-        const uint8_t* f = flt + c * ST_FLT + 1;                                 // f[t - s], t = s - 1 .. e
-        const long long col = (long long)r * NC + c;
-        int n_on = 0, n_off = 0;
-        long long base = 0;
-        if (PASS == 1) {
-            n_on = a.cnt[slot + c];
-            n_off = n_on - ((f[-1] && f[0]) ? 1 : 0);                            // an event open across the tile's first edge
-            base = a.ev_ptr[col];
+        __syncthreads();
+        if (!SWEEP && PASS == 0 && a.binary) {                                   // (the sweep has none: it would be K timelines)
+            uint8_t* bin = a.binary + (size_t)R.f0 * NC;
+            for (int it = tid; it < (e - s) * NC; it += ST_THREADS) {
+                const int fl = it / NC, c = it - fl * NC;
+                if (s_win[c]) bin[(size_t)(s + fl) * NC + c] = flt[c * ST_FLT + fl + 1];
+            }
         }
-        const int first = n_on;
-        for (int t0 = s; t0 < e; t0 += 64) {
-            const int t = t0 + lane;
-            const bool act = t < e && f[t - s];
-            const bool prev = act && f[t - s - 1];
-            const bool next = act && f[t - s + 1];
-            pp_emit_chunk(act, prev, next, t, lane, n_on, n_off, [&](int k, int frame, bool is_offset) {
-                if (PASS == 1) {
-                    const long long dst = base + k;
-                    if (dst >= 0 && dst < a.capacity) a.ev_pairs[2 * dst + (is_offset ? 1 : 0)] = frame;
-                }
-            });
+        // ---- onsets / offsets of the tile: one wave per class, 64 frames per ballot -----------------------------------------
+        const size_t slot = ((size_t)kp * a.n_slots + (size_t)g) * NC;
+        for (int c = wave; c < NC; c += ST_THREADS / 64) {
+            const uint8_t* f = flt + c * ST_FLT + 1;                             // f[t - s], t = s - 1 .. e
+            const long long col = ((long long)kp * a.n_rec + r) * NC + c;
+            int n_on = 0, n_off = 0;
+            long long base = 0;
+            if (PASS == 1) {
+                n_on = a.cnt[slot + c];
+                n_off = n_on - ((f[-1] && f[0]) ? 1 : 0);                        // an event open across the tile's first edge
+                base = a.ev_ptr[col];
+            }
+            const int first = n_on;
+            for (int t0 = s; t0 < e; t0 += 64) {
+                const int t = t0 + lane;
+                const bool act = t < e && f[t - s];
+                const bool prev = act && f[t - s - 1];
+                const bool next = act && f[t - s + 1];
+                pp_emit_chunk(act, prev, next, t, lane, n_on, n_off, [&](int k, int frame, bool is_offset) {
+                    if (PASS == 1) {
+                        const long long dst = base + k;
+                        if (dst >= 0 && dst < a.capacity) a.ev_pairs[2 * dst + (is_offset ? 1 : 0)] = frame;
+                    }
+                });
+            }
+            if (PASS == 0 && lane == 0) a.cnt[slot + c] = n_on - first;
         }
-        if (PASS == 0 && lane == 0) a.cnt[slot + c] = n_on - first;
+        // (the next point's s_thr / raw / flt writes are each behind a barrier that every wave reaches after its reads here)
     }
 }
 
@@ -277,239 +312,117 @@ __global__ __launch_bounds__(1024) void k_stitch_scan_ptr(StArgs a) {
     if (tid == 0 && s_carry > a.capacity) atomicOr(a.err, 2);
 }
 
-// ---- K operating points from one blend (sed_stitch_sweep) ---------------------------------------------------------------------
-// The blend does not depend on the threshold or the median window, so a workgroup blends its tile's ST_EXT frames ONCE into
-// LDS (fp32, all classes) and takes the decisions, filters and counts of ST_SWEEP_GROUP points from it, one point after the
-// other through the same raw / flt arrays.  The grid's second dimension is the point group: blockIdx.y owns the points
-// y * ST_SWEEP_GROUP .. and blends again.  cnt is [K][n_slots][NC] and a column is (point, recording, class), so the two scans
-// are those of sed_stitch_decode with K > 1.
-#ifndef ST_SWEEP_GROUP
-#define ST_SWEEP_GROUP 8
-#endif
-#define ST_SWEEP_MAXK 4096
-
-template <bool VEC, int PASS>
-__global__ __launch_bounds__(ST_THREADS) void k_stitch_sweep_tile(StArgs a) {
-    __shared__ float pst[ST_MAXC * ST_EXT];
-    __shared__ uint8_t raw[ST_MAXC * ST_EXT];
-    __shared__ uint8_t flt[ST_MAXC * ST_FLT];
-    __shared__ float s_thr[ST_MAXC];
-    __shared__ int s_win[ST_MAXC];       // 0: outside 1 .. 63, the column is not decoded
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NC = a.NC;
-    const long long g = blockIdx.x;
-    int lo_r = 0, hi_r = a.n_rec - 1;
-    while (lo_r < hi_r) {                                                        // the last r with slot0(r) <= g
-        const int mid = (lo_r + hi_r + 1) >> 1;
-        if (a.rec_frame0[mid] / ST_TILE + mid <= g) lo_r = mid;
-        else hi_r = mid - 1;
-    }
-    const int r = lo_r;
-    const StRec R = st_rec(a, r);
-    if (R.bad) return;                                                           // (k_stitch_scan_cols reports it)
-    const long long kt = g - R.slot0;
-    if (kt < 0 || kt >= R.tiles) return;                                         // an empty slot
-    const int L3 = R.L3, s = (int)kt * ST_TILE, e = min(s + ST_TILE, L3);
-    const int ext_lo = max(s - ST_HALO, 0), ext_n = min(e + ST_HALO, L3) - ext_lo;
-    const int k_lo = blockIdx.y * ST_SWEEP_GROUP, k_hi = min(k_lo + ST_SWEEP_GROUP, a.K);
-    // ---- the blend, once: frames ext_lo .. ext_lo + ext_n - 1, all classes --------------------------------------------------
-    {
-        const int G = VEC ? NC >> 2 : NC;
-        float* tl = (PASS == 0 && a.timeline && blockIdx.y == 0) ? a.timeline + (size_t)R.f0 * NC : nullptr;
-        for (int it = tid; it < ext_n * G; it += ST_THREADS) {
-            const int fl = it / G, q = it - fl * G, u = ext_lo + fl;
-            const f32x4 p = st_blend<VEC>(a, R, u, q);
-            if (VEC) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) pst[(4 * q + k) * ST_EXT + fl] = p[k];
-                if (tl && u >= s && u < e) *(f32x4*)(tl + (size_t)u * NC + 4 * q) = p;
-            } else {
-                pst[q * ST_EXT + fl] = p[0];
-                if (tl && u >= s && u < e) tl[(size_t)u * NC + q] = p[0];
-            }
-        }
-    }
-    const int n_flt = e - s + 2;
-    for (int kp = k_lo; kp < k_hi; ++kp) {
-        if (tid < NC) {
-            const int w = a.win[kp * NC + tid];
-            s_thr[tid] = a.thr[kp * NC + tid];
-            s_win[tid] = (w >= 1 && w <= 63) ? w : 0;
-            if (PASS == 0 && kt == 0 && !(w >= 1 && w <= 63)) atomicOr(a.err, 8);
-        }
-        __syncthreads();                                                         // (the first one also publishes pst)
-        for (int it = tid; it < NC * ext_n; it += ST_THREADS) {
-            const int c = it / ext_n, fl = it - c * ext_n;
-            raw[c * ST_EXT + fl] = pp_decision(pst[c * ST_EXT + fl], s_thr[c]);
-        }
-        __syncthreads();
-        // ---- median filter of frames s - 1 .. e (post.h's rule; reflection only at the recording's two ends) ----------------
-        for (int it = tid; it < NC * n_flt; it += ST_THREADS) {
-            const int c = it / n_flt, k = it - c * n_flt, t = s - 1 + k;
-            const int window = s_win[c];
-            uint8_t v = 0;
-            if (t >= 0 && t < L3 && window) {
-                const int lo = window / 2, need = window - window / 2;
-                const uint8_t* col = raw + c * ST_EXT - ext_lo;
-                int ones = 0;
-                for (int d = 0; d < window; ++d) ones += col[pp_reflect(t - lo + d, L3)];
-                v = ones >= need ? 1 : 0;
-            }
-            flt[c * ST_FLT + k] = v;
-        }
-        __syncthreads();
-        // ---- onsets / offsets of the tile: one wave per class, 64 frames per ballot -----------------------------------------
-        const size_t slot = ((size_t)kp * a.n_slots + (size_t)g) * NC;
-        for (int c = wave; c < NC; c += ST_THREADS / 64) {
-            const uint8_t* f = flt + c * ST_FLT + 1;                             // f[t - s], t = s - 1 .. e
-            const long long col = ((long long)kp * a.n_rec + r) * NC + c;
-            int n_on = 0, n_off = 0;
-            long long base = 0;
-            if (PASS == 1) {
-                n_on = a.cnt[slot + c];
-                n_off = n_on - ((f[-1] && f[0]) ? 1 : 0);                        // an event open across the tile's first edge
-                base = a.ev_ptr[col];
-            }
-            const int first = n_on;
-            for (int t0 = s; t0 < e; t0 += 64) {
-                const int t = t0 + lane;
-                const bool act = t < e && f[t - s];
-                const bool prev = act && f[t - s - 1];
-                const bool next = act && f[t - s + 1];
-                pp_emit_chunk(act, prev, next, t, lane, n_on, n_off, [&](int k, int frame, bool is_offset) {
-                    if (PASS == 1) {
-                        const long long dst = base + k;
-                        if (dst >= 0 && dst < a.capacity) a.ev_pairs[2 * dst + (is_offset ? 1 : 0)] = frame;
-                    }
-                });
-            }
-            if (PASS == 0 && lane == 0) a.cnt[slot + c] = n_on - first;
-        }
-        // (the next point's s_thr / raw / flt writes are each behind a barrier that every wave reaches after its reads here)
-    }
-}
-
 extern "C" int sed_stitch_tile_frames(void) { return ST_TILE; }
 
-static size_t st_ws_head(int n_rec, int NC) { return (size_t)n_rec * NC * sizeof(int64_t); }
+// The workspace: col_total [K * n_rec * NC] int64, then cnt [K][n_slots][NC] int32 (K = 1: sed_stitch_decode's layout).
+static size_t st_ws_head(int n_rec, int NC, int K) { return (size_t)K * n_rec * NC * sizeof(int64_t); }
+static size_t st_ws_per_slot(int NC, int K) { return (size_t)K * NC * sizeof(int32_t); }
 
-extern "C" size_t sed_stitch_decode_ws_bytes(long long total_frames, int n_rec, int nclass) {
-    if (total_frames < 1 || n_rec < 1 || nclass < 1 || nclass > ST_MAXC || total_frames * nclass >= (1ll << 31) ||
-        (long long)n_rec * nclass >= (1ll << 31)) {
-        sed_set_error("sed_stitch_decode_ws_bytes: need total_frames >= 1, n_rec >= 1, 1 <= nclass <= 16, total_frames * nclass < 2^31");
-        return 0;
-    }
-    const size_t n_slots = (size_t)(total_frames / ST_TILE) + n_rec + 1;
-    return st_ws_head(n_rec, nclass) + n_slots * nclass * sizeof(int32_t);
+// Bytes for tables of total_frames frames, or 0 where the sizes are out of range (the sweep's ranges are the narrower ones).
+static size_t st_ws_size(long long total_frames, int n_rec, int NC, int K, bool sweep) {
+    if (total_frames < 1 || n_rec < 1 || NC < 1 || NC > ST_MAXC || K < 1 || K > ST_SWEEP_MAXK || total_frames * NC >= (1ll << 31) ||
+        (long long)K * n_rec * NC >= (1ll << (sweep ? 26 : 31))) return 0;
+    const long long n_slots = total_frames / ST_TILE + n_rec + 1;
+    if (sweep && n_slots * K >= (1ll << 31)) return 0;
+    return st_ws_head(n_rec, NC, K) + (size_t)n_slots * st_ws_per_slot(NC, K);
 }
 
-extern "C" int sed_stitch_decode(const float* win_strong, const int32_t* rec_win0, const int64_t* rec_frame0, int n_rec, int T3,
-                                 int NC, int hop3, int weighting, const float* thr, const int32_t* win, float* timeline,
-                                 uint8_t* binary, int64_t* ev_ptr, int32_t* ev_pairs, long long capacity, void* ws,
-                                 size_t ws_bytes, int32_t* err, void* stream) {
-    SED_CHECK_ARG(win_strong && rec_win0 && rec_frame0 && thr && win && ev_ptr && ev_pairs && ws && err,
-                  "sed_stitch_decode: null argument");
-    SED_CHECK_ARG(n_rec >= 1 && NC >= 1 && NC <= ST_MAXC && (long long)n_rec * NC < (1ll << 31),
-                  "sed_stitch_decode: need n_rec >= 1, 1 <= NC <= 16 and n_rec * NC < 2^31");
-    SED_CHECK_ARG(T3 >= 1 && T3 <= 4096, "sed_stitch_decode: need 1 <= T3 <= 4096 (the taper's weight sum stays exact in fp32)");
-    SED_CHECK_ARG(hop3 >= 1 && hop3 <= T3, "sed_stitch_decode: need 1 <= hop3 <= T3");
-    SED_CHECK_ARG(weighting == 0 || weighting == 1, "sed_stitch_decode: weighting is 0 (uniform) or 1 (taper)");
-    SED_CHECK_ARG(capacity >= 0, "sed_stitch_decode: capacity must be >= 0");
-    SED_CHECK_ARG(((uintptr_t)ws % 8) == 0, "sed_stitch_decode: ws must be 8-byte aligned");
-    const size_t head = st_ws_head(n_rec, NC), per_slot = (size_t)NC * sizeof(int32_t);
+extern "C" size_t sed_stitch_decode_ws_bytes(long long total_frames, int n_rec, int nclass) {
+    const size_t n = st_ws_size(total_frames, n_rec, nclass, 1, false);
+    if (!n) sed_set_error("sed_stitch_decode_ws_bytes: need total_frames >= 1, n_rec >= 1, 1 <= nclass <= 16, "
+                          "total_frames * nclass < 2^31");
+    return n;
+}
+
+extern "C" size_t sed_stitch_sweep_ws_bytes(long long total_frames, int n_rec, int nclass, int n_points) {
+    const size_t n = st_ws_size(total_frames, n_rec, nclass, n_points, true);
+    if (!n) sed_set_error("sed_stitch_sweep_ws_bytes: need total_frames >= 1, n_rec >= 1, 1 <= nclass <= 16, 1 <= n_points <= %d, "
+                          "total_frames * nclass < 2^31, n_points * n_rec * nclass < 2^26, n_points * slots < 2^31", ST_SWEEP_MAXK);
+    return n;
+}
+
+extern "C" int sed_stitch_sweep_point_group(void) { return ST_SWEEP_GROUP; }
+
+template <int PASS>
+static void st_launch_tile(bool vec, bool sweep, dim3 grid, hipStream_t st, const StArgs& a) {
+    const dim3 thr256(ST_THREADS);
+    if (sweep && vec) hipLaunchKernelGGL((k_stitch_tile<true, PASS, true>), grid, thr256, 0, st, a);
+    else if (sweep) hipLaunchKernelGGL((k_stitch_tile<false, PASS, true>), grid, thr256, 0, st, a);
+    else if (vec) hipLaunchKernelGGL((k_stitch_tile<true, PASS, false>), grid, thr256, 0, st, a);
+    else hipLaunchKernelGGL((k_stitch_tile<false, PASS, false>), grid, thr256, 0, st, a);
+}
+
+#define ST_NEED(cond, msg)                          \
+    do {                                            \
+        if (!(cond)) {                              \
+            sed_set_error("%s: %s", what, msg);     \
+            return SED_ERR_BAD_ARG;                 \
+        }                                           \
+    } while (0)
+
+// Both entries: `what` names the caller in every message; sweep = false is n_points = 1 with sed_stitch_decode's looser
+// workspace rule (any size that holds the tables; the slot count is derived from it) and its binary output.
+static int st_run(const char* what, bool sweep, const float* win_strong, const int32_t* rec_win0, const int64_t* rec_frame0,
+                  int n_rec, int T3, int NC, int hop3, int weighting, int n_points, const float* thr, const int32_t* win,
+                  float* timeline, uint8_t* binary, int64_t* ev_ptr, int32_t* ev_pairs, long long capacity, void* ws,
+                  size_t ws_bytes, int32_t* err, void* stream) {
+    ST_NEED(win_strong && rec_win0 && rec_frame0 && thr && win && ev_ptr && ev_pairs && ws && err, "null argument");
+    ST_NEED(n_points >= 1 && n_points <= ST_SWEEP_MAXK, "need 1 <= n_points <= 4096");
+    ST_NEED(n_rec >= 1 && NC >= 1 && NC <= ST_MAXC && (long long)n_points * n_rec * NC < (1ll << (sweep ? 26 : 31)),
+            sweep ? "need n_rec >= 1, 1 <= NC <= 16 and n_points * n_rec * NC < 2^26"
+                  : "need n_rec >= 1, 1 <= NC <= 16 and n_rec * NC < 2^31");
+    ST_NEED(T3 >= 1 && T3 <= 4096, "need 1 <= T3 <= 4096 (the taper's weight sum stays exact in fp32)");
+    ST_NEED(hop3 >= 1 && hop3 <= T3, "need 1 <= hop3 <= T3");
+    ST_NEED(weighting == 0 || weighting == 1, "weighting is 0 (uniform) or 1 (taper)");
+    ST_NEED(capacity >= 0, "capacity must be >= 0");
+    ST_NEED(((uintptr_t)ws % 8) == 0, "ws must be 8-byte aligned");
+    const size_t head = st_ws_head(n_rec, NC, n_points), per_slot = st_ws_per_slot(NC, n_points);
     if (ws_bytes < head + (size_t)(n_rec + 1) * per_slot) {
-        sed_set_error("sed_stitch_decode: workspace of %zu bytes is too small (sed_stitch_decode_ws_bytes)", ws_bytes);
+        sed_set_error("%s: workspace of %zu bytes is too small (%s_ws_bytes)", what, ws_bytes, what);
         return SED_ERR_WORKSPACE;
     }
+    // the slot count is derived from the size: with K > 1 only a size sed_stitch_sweep_ws_bytes returns describes whole slots
+    ST_NEED(!sweep || (ws_bytes - head) % per_slot == 0,
+            "ws_bytes must be the value sed_stitch_sweep_ws_bytes returned for these tables");
     const size_t n_slots = (ws_bytes - head) / per_slot;
-    SED_CHECK_ARG(n_slots < (1ull << 31), "sed_stitch_decode: workspace too large for the tile grid");
+    ST_NEED(n_slots * n_points < (1ull << 31), "workspace too large for the tile grid (n_points * slots < 2^31)");
     // the slots bound the frames the tables may hold: sum L3 * NC < 2^31
-    SED_CHECK_ARG((long long)(n_slots - n_rec - 1) * ST_TILE * NC < (1ll << 31) + (long long)ST_TILE * NC,
-                  "sed_stitch_decode: sum L3 * NC must stay below 2^31");
+    ST_NEED((long long)(n_slots - n_rec - 1) * ST_TILE * NC < (1ll << 31) + (long long)ST_TILE * NC,
+            "sum L3 * NC must stay below 2^31");
     StArgs a = {};
     a.win_strong = win_strong; a.rec_win0 = rec_win0; a.rec_frame0 = rec_frame0; a.thr = thr; a.win = win;
     a.timeline = timeline; a.binary = binary; a.ev_ptr = ev_ptr; a.ev_pairs = ev_pairs; a.capacity = capacity;
     a.col_total = (int64_t*)ws;
     a.cnt = (int32_t*)((char*)ws + head);
     a.err = err;
-    a.n_rec = n_rec; a.T3 = T3; a.NC = NC; a.hop3 = hop3; a.weighting = weighting; a.n_slots = (int)n_slots; a.K = 1;
+    a.n_rec = n_rec; a.T3 = T3; a.NC = NC; a.hop3 = hop3; a.weighting = weighting; a.n_slots = (int)n_slots; a.K = n_points;
     const bool vec = NC % 4 == 0 && ((uintptr_t)win_strong % 16) == 0 && (!timeline || ((uintptr_t)timeline % 16) == 0);
     hipStream_t st = (hipStream_t)stream;
-    const dim3 tiles((unsigned)n_slots), thr256(ST_THREADS);
-    if (vec) hipLaunchKernelGGL((k_stitch_tile<true, 0>), tiles, thr256, 0, st, a);
-    else hipLaunchKernelGGL((k_stitch_tile<false, 0>), tiles, thr256, 0, st, a);
+    const dim3 tiles((unsigned)n_slots, sweep ? (unsigned)((n_points + ST_SWEEP_GROUP - 1) / ST_SWEEP_GROUP) : 1u);
+    st_launch_tile<0>(vec, sweep, tiles, st, a);
     SED_CHECK_LAUNCH();
-    const long long n_cols = (long long)n_rec * NC;
-    hipLaunchKernelGGL(k_stitch_scan_cols, dim3((unsigned)((n_cols + 3) / 4)), thr256, 0, st, a);
+    const long long n_cols = (long long)n_points * n_rec * NC;
+    hipLaunchKernelGGL(k_stitch_scan_cols, dim3((unsigned)((n_cols + 3) / 4)), dim3(ST_THREADS), 0, st, a);
     SED_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_stitch_scan_ptr, dim3(1), dim3(1024), 0, st, a);
     SED_CHECK_LAUNCH();
-    if (vec) hipLaunchKernelGGL((k_stitch_tile<true, 1>), tiles, thr256, 0, st, a);
-    else hipLaunchKernelGGL((k_stitch_tile<false, 1>), tiles, thr256, 0, st, a);
+    st_launch_tile<1>(vec, sweep, tiles, st, a);
     SED_CHECK_LAUNCH();
     return SED_OK;
 }
 
-extern "C" int sed_stitch_sweep_point_group(void) { return ST_SWEEP_GROUP; }
-
-extern "C" size_t sed_stitch_sweep_ws_bytes(long long total_frames, int n_rec, int nclass, int n_points) {
-    if (total_frames < 1 || n_rec < 1 || nclass < 1 || nclass > ST_MAXC || n_points < 1 || n_points > ST_SWEEP_MAXK ||
-        total_frames * nclass >= (1ll << 31) || (long long)n_points * n_rec * nclass >= (1ll << 26) ||
-        (total_frames / ST_TILE + n_rec + 1) * n_points >= (1ll << 31)) {
-        sed_set_error("sed_stitch_sweep_ws_bytes: need total_frames >= 1, n_rec >= 1, 1 <= nclass <= 16, 1 <= n_points <= %d, "
-                      "total_frames * nclass < 2^31, n_points * n_rec * nclass < 2^26, n_points * slots < 2^31", ST_SWEEP_MAXK);
-        return 0;
-    }
-    const size_t n_slots = (size_t)(total_frames / ST_TILE) + n_rec + 1;
-    return (size_t)n_points * (st_ws_head(n_rec, nclass) + n_slots * nclass * sizeof(int32_t));
+extern "C" int sed_stitch_decode(const float* win_strong, const int32_t* rec_win0, const int64_t* rec_frame0, int n_rec, int T3,
+                                 int NC, int hop3, int weighting, const float* thr, const int32_t* win, float* timeline,
+                                 uint8_t* binary, int64_t* ev_ptr, int32_t* ev_pairs, long long capacity, void* ws,
+                                 size_t ws_bytes, int32_t* err, void* stream) {
+    return st_run("sed_stitch_decode", false, win_strong, rec_win0, rec_frame0, n_rec, T3, NC, hop3, weighting, 1, thr, win,
+                  timeline, binary, ev_ptr, ev_pairs, capacity, ws, ws_bytes, err, stream);
 }
 
 extern "C" int sed_stitch_sweep(const float* win_strong, const int32_t* rec_win0, const int64_t* rec_frame0, int n_rec, int T3,
                                 int NC, int hop3, int weighting, int n_points, const float* thr, const int32_t* win,
                                 float* timeline, int64_t* ev_ptr, int32_t* ev_pairs, long long capacity, void* ws,
                                 size_t ws_bytes, int32_t* err, void* stream) {
-    SED_CHECK_ARG(win_strong && rec_win0 && rec_frame0 && thr && win && ev_ptr && ev_pairs && ws && err,
-                  "sed_stitch_sweep: null argument");
-    SED_CHECK_ARG(n_points >= 1 && n_points <= ST_SWEEP_MAXK, "sed_stitch_sweep: need 1 <= n_points <= 4096");
-    SED_CHECK_ARG(n_rec >= 1 && NC >= 1 && NC <= ST_MAXC && (long long)n_points * n_rec * NC < (1ll << 26),
-                  "sed_stitch_sweep: need n_rec >= 1, 1 <= NC <= 16 and n_points * n_rec * NC < 2^26");
-    SED_CHECK_ARG(T3 >= 1 && T3 <= 4096, "sed_stitch_sweep: need 1 <= T3 <= 4096 (the taper's weight sum stays exact in fp32)");
-    SED_CHECK_ARG(hop3 >= 1 && hop3 <= T3, "sed_stitch_sweep: need 1 <= hop3 <= T3");
-    SED_CHECK_ARG(weighting == 0 || weighting == 1, "sed_stitch_sweep: weighting is 0 (uniform) or 1 (taper)");
-    SED_CHECK_ARG(capacity >= 0, "sed_stitch_sweep: capacity must be >= 0");
-    SED_CHECK_ARG(((uintptr_t)ws % 8) == 0, "sed_stitch_sweep: ws must be 8-byte aligned");
-    const size_t head = (size_t)n_points * st_ws_head(n_rec, NC), per_slot = (size_t)n_points * NC * sizeof(int32_t);
-    if (ws_bytes < head + (size_t)(n_rec + 1) * per_slot) {
-        sed_set_error("sed_stitch_sweep: workspace of %zu bytes is too small (sed_stitch_sweep_ws_bytes)", ws_bytes);
-        return SED_ERR_WORKSPACE;
-    }
-    // the slot count is derived from the size: only a size sed_stitch_sweep_ws_bytes returns describes whole slots
-    SED_CHECK_ARG((ws_bytes - head) % per_slot == 0,
-                  "sed_stitch_sweep: ws_bytes must be the value sed_stitch_sweep_ws_bytes returned for these tables");
-    const size_t n_slots = (ws_bytes - head) / per_slot;
-    SED_CHECK_ARG(n_slots * n_points < (1ull << 31),"sed_stitch_sweep: workspace too large for the tile grid (n_points * slots < 2^31)");
-    // the slots bound the frames the tables may hold: sum L3 * NC < 2^31
-    SED_CHECK_ARG((long long)(n_slots - n_rec - 1) * ST_TILE * NC < (1ll << 31) + (long long)ST_TILE * NC,
-                  "sed_stitch_sweep: sum L3 * NC must stay below 2^31");
-    StArgs a = {};
-    a.win_strong = win_strong; a.rec_win0 = rec_win0; a.rec_frame0 = rec_frame0; a.thr = thr; a.win = win;
-    a.timeline = timeline; a.binary = nullptr; a.ev_ptr = ev_ptr; a.ev_pairs = ev_pairs; a.capacity = capacity;
-    a.col_total = (int64_t*)ws;
-    a.cnt = (int32_t*)((char*)ws + head);
-    a.err = err;
-    a.n_rec = n_rec; a.T3 = T3; a.NC = NC; a.hop3 = hop3; a.weighting = weighting; a.n_slots = (int)n_slots; a.K = n_points;
-    const bool vec = NC % 4 == 0 && ((uintptr_t)win_strong % 16) == 0 && (!timeline || ((uintptr_t)timeline % 16) == 0);
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 tiles((unsigned)n_slots, (unsigned)((n_points + ST_SWEEP_GROUP - 1) / ST_SWEEP_GROUP)), thr256(ST_THREADS);
-    if (vec) hipLaunchKernelGGL((k_stitch_sweep_tile<true, 0>), tiles, thr256, 0, st, a);
-    else hipLaunchKernelGGL((k_stitch_sweep_tile<false, 0>), tiles, thr256, 0, st, a);
-    SED_CHECK_LAUNCH();
-    const long long n_cols = (long long)n_points * n_rec * NC;
-    hipLaunchKernelGGL(k_stitch_scan_cols, dim3((unsigned)((n_cols + 3) / 4)), thr256, 0, st, a);
-    SED_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_stitch_scan_ptr, dim3(1), dim3(1024), 0, st, a);
-    SED_CHECK_LAUNCH();
-    if (vec) hipLaunchKernelGGL((k_stitch_sweep_tile<true, 1>), tiles, thr256, 0, st, a);
-    else hipLaunchKernelGGL((k_stitch_sweep_tile<false, 1>), tiles, thr256, 0, st, a);
-    SED_CHECK_LAUNCH();
-    return SED_OK;
+    return st_run("sed_stitch_sweep", true, win_strong, rec_win0, rec_frame0, n_rec, T3, NC, hop3, weighting, n_points, thr, win,
+                  timeline, nullptr, ev_ptr, ev_pairs, capacity, ws, ws_bytes, err, stream);
 }

@@ -153,6 +153,33 @@ def _per_class(value, nclass, dtype, what):
     return np.ascontiguousarray(a)
 
 
+def _stitch_call(entry, win_strong, rec_win0, rec_frame0, total, hop3, thr, win, weighting, capacity, ws_bytes, want_timeline,
+                 want_binary=False, n_points=None):
+    """The call both stitch entries share: outputs, scratch and ``entry`` (``sed_stitch_sweep`` takes ``n_points``,
+    ``sed_stitch_decode`` a binary timeline).  ``thr`` / ``win``: device tensors, one row of nclass values per point."""
+    dev = win_strong.device
+    win_strong = win_strong.contiguous().float()
+    n_win, T3, NC = win_strong.shape
+    n_rec, K = rec_win0.numel() - 1, n_points or 1
+    if capacity is None:
+        capacity = K * NC * ((total + n_rec) // 2)          # >= K times the sum over recordings of NC * ceil(L3 / 2)
+    out = {"ev_ptr": torch.empty(K * n_rec * NC + 1, dtype=torch.int64, device=dev),
+           "ev_pairs": torch.empty(max(int(capacity), 1), 2, dtype=torch.int32, device=dev),
+           "err": torch.zeros(1, dtype=torch.int32, device=dev),
+           "timeline": torch.empty(total, NC, dtype=torch.float32, device=dev) if want_timeline else None,
+           "binary": torch.empty(total, NC, dtype=torch.uint8, device=dev) if want_binary else None}
+    ws = _lib.scratch(ws_bytes, dev)
+    head = (_lib.ptr(win_strong), _lib.ptr(rec_win0), _lib.ptr(rec_frame0), n_rec, T3, NC, int(hop3), WEIGHTINGS[weighting])
+    if n_points is None:
+        points = (_lib.ptr(thr), _lib.ptr(win), _lib.ptr(out["timeline"]), _lib.ptr(out["binary"]))
+    else:
+        out["n_points"] = K
+        points = (K, _lib.ptr(thr), _lib.ptr(win), _lib.ptr(out["timeline"]))
+    _lib.check(getattr(_lib.lib(), entry)(*head, *points, _lib.ptr(out["ev_ptr"]), _lib.ptr(out["ev_pairs"]), int(capacity),
+                                          _lib.ptr(ws), ws.numel(), _lib.ptr(out["err"]), _lib.stream_ptr()), entry)
+    return out
+
+
 def stitch_decode(win_strong, rec_win0, rec_frame0, total_frames, hop3, threshold=0.5, median_window=5, weighting="taper",
                   capacity=None, want_timeline=True, want_binary=False):
     """``sed_stitch_decode`` on window posteriors [n_win, T3, nclass] (cuda float32) with the device tables ``rec_win0``
@@ -164,30 +191,15 @@ def stitch_decode(win_strong, rec_win0, rec_frame0, total_frames, hop3, threshol
         raise _lib.SedError("stitch_decode needs GPU tensors (no CPU fallback)")
     if weighting not in WEIGHTINGS:
         raise ValueError(f"weighting must be one of {sorted(WEIGHTINGS)}, got {weighting!r}")
-    dev = win_strong.device
-    win_strong = win_strong.contiguous().float()
-    n_win, T3, NC = win_strong.shape
-    n_rec = rec_win0.numel() - 1
-    total = int(total_frames)
+    dev, NC, total = win_strong.device, win_strong.shape[2], int(total_frames)
     if total * NC >= 2 ** 31:
         raise ValueError(f"{total} timeline frames x {NC} classes: the product must stay below 2^31")
     thr = threshold if torch.is_tensor(threshold) else torch.from_numpy(_per_class(threshold, NC, np.float32, "threshold")).to(dev)
     win = (median_window if torch.is_tensor(median_window)
            else torch.from_numpy(_per_class(median_window, NC, np.int32, "median_window")).to(dev))
-    if capacity is None:
-        capacity = NC * ((total + n_rec) // 2)              # >= sum over recordings of NC * ceil(L3 / 2)
-    l = _lib.lib()
-    out = {"ev_ptr": torch.empty(n_rec * NC + 1, dtype=torch.int64, device=dev),
-           "ev_pairs": torch.empty(max(int(capacity), 1), 2, dtype=torch.int32, device=dev),
-           "err": torch.zeros(1, dtype=torch.int32, device=dev),
-           "timeline": torch.empty(total, NC, dtype=torch.float32, device=dev) if want_timeline else None,
-           "binary": torch.empty(total, NC, dtype=torch.uint8, device=dev) if want_binary else None}
-    ws = _lib.scratch(l.sed_stitch_decode_ws_bytes(total, n_rec, NC), dev)
-    _lib.check(l.sed_stitch_decode(_lib.ptr(win_strong), _lib.ptr(rec_win0), _lib.ptr(rec_frame0), n_rec, T3, NC, int(hop3),
-                                   WEIGHTINGS[weighting], _lib.ptr(thr), _lib.ptr(win), _lib.ptr(out["timeline"]),
-                                   _lib.ptr(out["binary"]), _lib.ptr(out["ev_ptr"]), _lib.ptr(out["ev_pairs"]), int(capacity),
-                                   _lib.ptr(ws), ws.numel(), _lib.ptr(out["err"]), _lib.stream_ptr()), "sed_stitch_decode")
-    return out
+    ws_bytes = _lib.lib().sed_stitch_decode_ws_bytes(total, rec_win0.numel() - 1, NC)
+    return _stitch_call("sed_stitch_decode", win_strong, rec_win0, rec_frame0, total, hop3, thr, win, weighting, capacity,
+                        ws_bytes, want_timeline, want_binary)
 
 
 def sweep_points(thresholds, median_windows, nclass):
@@ -214,7 +226,7 @@ def stitch_sweep(win_strong, rec_win0, rec_frame0, total_frames, hop3, threshold
         raise ValueError(f"weighting must be one of {sorted(WEIGHTINGS)}, got {weighting!r}")
     if win_strong.dim() != 3:
         raise ValueError(f"win_strong must be [n_win, T3, nclass], got {tuple(win_strong.shape)}")
-    n_win, T3, NC = win_strong.shape
+    NC = win_strong.shape[2]
     if torch.is_tensor(thresholds) != torch.is_tensor(median_windows):
         raise ValueError("thresholds and median_windows: both sequences or both device tensors [K, nclass]")
     if torch.is_tensor(thresholds):
@@ -229,27 +241,13 @@ def stitch_sweep(win_strong, rec_win0, rec_frame0, total_frames, hop3, threshold
     if not torch.is_tensor(thr):
         thr, win = torch.from_numpy(thr).to(dev), torch.from_numpy(win).to(dev)
     thr, win = thr.contiguous(), win.contiguous()
-    K = thr.shape[0]
-    win_strong = win_strong.contiguous().float()
-    n_rec = rec_win0.numel() - 1
-    total = int(total_frames)
+    K, total = thr.shape[0], int(total_frames)
     l = _lib.lib()
-    ws_bytes = l.sed_stitch_sweep_ws_bytes(total, n_rec, NC, K)
+    ws_bytes = l.sed_stitch_sweep_ws_bytes(total, rec_win0.numel() - 1, NC, K)
     if ws_bytes == 0:
         raise ValueError(f"sed_stitch_sweep_ws_bytes: {l.sed_last_error().decode()}")
-    if capacity is None:
-        capacity = K * NC * ((total + n_rec) // 2)          # K times stitch_decode's default
-    out = {"ev_ptr": torch.empty(K * n_rec * NC + 1, dtype=torch.int64, device=dev),
-           "ev_pairs": torch.empty(max(int(capacity), 1), 2, dtype=torch.int32, device=dev),
-           "err": torch.zeros(1, dtype=torch.int32, device=dev),
-           "timeline": torch.empty(total, NC, dtype=torch.float32, device=dev) if want_timeline else None,
-           "binary": None, "n_points": K}
-    ws = _lib.scratch(ws_bytes, dev)
-    _lib.check(l.sed_stitch_sweep(_lib.ptr(win_strong), _lib.ptr(rec_win0), _lib.ptr(rec_frame0), n_rec, T3, NC, int(hop3),
-                                  WEIGHTINGS[weighting], K, _lib.ptr(thr), _lib.ptr(win), _lib.ptr(out["timeline"]),
-                                  _lib.ptr(out["ev_ptr"]), _lib.ptr(out["ev_pairs"]), int(capacity), _lib.ptr(ws), ws.numel(),
-                                  _lib.ptr(out["err"]), _lib.stream_ptr()), "sed_stitch_sweep")
-    return out
+    return _stitch_call("sed_stitch_sweep", win_strong, rec_win0, rec_frame0, total, hop3, thr, win, weighting, capacity,
+                        ws_bytes, want_timeline, n_points=K)
 
 
 def long_window_posteriors(model, long_set, nclass, batch_size=64):

@@ -149,6 +149,16 @@ class RefEvents:
         return len(self.labels)
 
 
+def _totals_to_host(counts):
+    """The buffer of a ``Counts`` / ``PSDSCounts`` without its error word - one device -> host copy; raises when the word is set."""
+    h = counts.buf.cpu().numpy()
+    err = int(h[-1:].view(np.int32)[0])
+    if err:
+        raise _lib.SedError(counts.err_what + ": " + "; ".join(m for b, m in counts.err_bits.items() if err & b)
+                            + " - nothing was truncated, the counts are invalid")
+    return h[:-1]
+
+
 class Counts:
     """Class totals of one or more ``event_counts`` calls, on the device: ``ev [K, nclass, 3]`` (Ntp, Nref, Nsys) and
     ``seg [K, nclass, 4]`` (Ntp, Nfp, Nfn, Ntn) int64, and the error word, all in ONE buffer so that ``host()`` is one copy.
@@ -167,13 +177,8 @@ class Counts:
 
     def host(self):
         """(ev, seg) as numpy arrays - one device -> host copy; raises when a column was over a limit."""
-        h = self.buf.cpu().numpy()
-        err = int(h[-1:].view(np.int32)[0])
-        if err:
-            raise _lib.SedError(self.err_what + ": " + "; ".join(m for b, m in self.err_bits.items() if err & b)
-                                + " - nothing was truncated, the counts are invalid")
-        n3 = self.K * self.NC * 3
-        return h[:n3].reshape(self.K, self.NC, 3), h[n3:-1].reshape(self.K, self.NC, 4)
+        h, n3 = _totals_to_host(self), self.K * self.NC * 3
+        return h[:n3].reshape(self.K, self.NC, 3), h[n3:].reshape(self.K, self.NC, 4)
 
     check = host
 
@@ -267,12 +272,7 @@ class PSDSCounts:
 
     def host(self):
         """``totals`` as a numpy array - one device -> host copy; raises when a column was over a limit."""
-        h = self.buf.cpu().numpy()
-        err = int(h[-1:].view(np.int32)[0])
-        if err:
-            raise _lib.SedError(self.err_what + ": " + "; ".join(m for b, m in self.err_bits.items() if err & b)
-                                + " - nothing was truncated, the counts are invalid")
-        return h[:-1].reshape(self.K, self.NC, 2 + self.NC)
+        return _totals_to_host(self).reshape(self.K, self.NC, 2 + self.NC)
 
     check = host
 
@@ -630,40 +630,59 @@ def validate(model, dataset, ref, pooling_time_ratio, thresholds=(0.5,), median_
     return [(EventMetrics(ref.labels, ev[k]), SegmentMetrics(ref.labels, seg[k])) for k in range(thr.numel())]
 
 
-# ---- long recordings: the event table of sed_stitch_decode (or given events) of any length -----------------------------------
-def _long_call(fn, what, est_args, est_cap, ref, tail, err, dev):
-    """One ``sed_long_*`` call: ``est_args`` = (ev_ptr, ev_pairs, num, den, est_on, est_off); ``tail``: the arguments between
-    ``nclass`` and ``err``."""
+# ---- long recordings: the event table of sed_stitch_decode / sed_stitch_sweep (or given events) of any length ------------------
+# One helper family serves the one-point functions (``long_*``: K = 1 into row ``point``, the ``sed_long_*`` entries) and the
+# sweep functions (``long_sweep_*``: K points into rows ``point0 ..``, the ``sed_long_sweep_*`` entries, per-column outputs with
+# a leading K).
+def _long_counts_call(fn, ws_fn, points, est_args, est_cap, ref, tail, err):
+    """One ``sed_long_*`` call: ``points`` = ``(K,)`` for the sweep entries, ``()`` for the one-point ones; ``est_args`` =
+    (ev_ptr, ev_pairs, num, den, est_on, est_off); ``tail``: the arguments between ``nclass`` (``n_points``) and ``err``."""
     l = _lib.lib()
     n, NC, n_ref = len(ref), ref.nclass, len(ref.onset_host)
-    ws_bytes = l.sed_long_score_ws_bytes(int(est_cap), n_ref, n, NC)
+    ws_bytes = getattr(l, ws_fn)(int(est_cap), n_ref, n, NC, *points)
     if ws_bytes == 0:
-        raise _lib.SedError(f"sed_long_score_ws_bytes: {l.sed_last_error().decode()}")
-    ws = _lib.scratch(ws_bytes, dev)
+        raise _lib.SedError(f"{ws_fn}: {l.sed_last_error().decode()}")
+    ws = _lib.scratch(ws_bytes, ref.device)
     ev_ptr, ev_pairs, num, den, on, off = est_args
     _lib.check(getattr(l, fn)(_lib.ptr(ev_ptr), _lib.ptr(ev_pairs), float(num), float(den), _lib.ptr(on), _lib.ptr(off),
-                              int(est_cap), _lib.ptr(ref.ptr64), _lib.ptr(ref.onset), _lib.ptr(ref.offset), n_ref, n, NC, *tail,
-                              _lib.ptr(err), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), what)
+                              int(est_cap), _lib.ptr(ref.ptr64), _lib.ptr(ref.onset), _lib.ptr(ref.offset), n_ref, n, NC, *points,
+                              *tail, _lib.ptr(err), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), fn)
 
 
-def _decoded_args(decoded, ref, pooling_time_ratio, cfg, what):
+def _decoded_args(decoded, ref, pooling_time_ratio, cfg, what, K=None):
+    """``(est_args, capacity, K)`` of a decoded table; ``K`` None: the table's own ``n_points`` (1 for ``stitch_decode``'s)."""
     cfg = cfg or _Cfg
     ev_ptr, ev_pairs = decoded["ev_ptr"], decoded["ev_pairs"]
+    if K is None:
+        K = int(decoded.get("n_points", 1))
     if ev_ptr.device.type != "cuda" or ref.device.type != "cuda":
         raise _lib.SedError(f"{what} needs the decoded table and a RefEvents on the GPU (no CPU fallback)")
-    if ev_ptr.dtype != torch.int64 or ev_pairs.dtype != torch.int32 or ev_ptr.numel() != len(ref) * ref.nclass + 1:
-        raise ValueError(f"decoded: ev_ptr int64 [{len(ref) * ref.nclass + 1}] and ev_pairs int32 [capacity, 2] expected "
-                         f"({len(ref)} recordings, {ref.nclass} classes)")
+    if K < 1 or ev_ptr.dtype != torch.int64 or ev_pairs.dtype != torch.int32 or ev_ptr.numel() != K * len(ref) * ref.nclass + 1:
+        raise ValueError(f"decoded: ev_ptr int64 [{K * len(ref) * ref.nclass + 1}] and ev_pairs int32 [capacity, 2] expected "
+                         f"({K} points, {len(ref)} recordings, {ref.nclass} classes)")
     return (ev_ptr, ev_pairs.contiguous(), float(pooling_time_ratio), float(cfg.sample_rate / cfg.hop_length), None, None), \
-        ev_pairs.shape[0]
+        ev_pairs.shape[0], K
 
 
-def _events_args(est, ref, what):
-    if est.device.type != "cuda" or ref.device.type != "cuda":
-        raise _lib.SedError(f"{what} needs both event sets on the GPU (no CPU fallback)")
-    if est.filenames != ref.filenames or est.labels != ref.labels:
-        raise ValueError("estimated and reference events must cover the same files and classes, in the same order")
-    return (est.ptr64, None, 0.0, 0.0, est.onset, est.offset), len(est.onset_host)
+def _events_args(ests, ref, what):
+    """K ``RefEvents`` as one CSR in column order (k, rec, c), assembled on the device (the sizes are known on the host); one
+    set is taken as it is."""
+    ests = list(ests)
+    if not ests:
+        raise ValueError(f"{what}: need at least one estimated event set")
+    for est in ests:
+        if est.device.type != "cuda" or ref.device.type != "cuda":
+            raise _lib.SedError(f"{what} needs every event set on the GPU (no CPU fallback)")
+        if est.filenames != ref.filenames or est.labels != ref.labels:
+            raise ValueError("estimated and reference events must cover the same files and classes, in the same order")
+    sizes = [len(est.onset_host) for est in ests]
+    if len(ests) == 1:
+        return (ests[0].ptr64, None, 0.0, 0.0, ests[0].onset, ests[0].offset), sizes[0], 1
+    base = np.r_[0, np.cumsum(sizes)]
+    ptr = torch.cat([est.ptr64[:-1] + int(base[k]) for k, est in enumerate(ests)] + [ests[-1].ptr64[-1:] + int(base[-2])])
+    on = torch.cat([est.onset[:n] for est, n in zip(ests, sizes)] + [ests[-1].onset[-1:]])        # (one trailing element)
+    off = torch.cat([est.offset[:n] for est, n in zip(ests, sizes)] + [ests[-1].offset[-1:]])
+    return (ptr, None, 0.0, 0.0, on, off), int(base[-1]), len(ests)
 
 
 def _fold_decode_err(counts, decoded):
@@ -671,37 +690,46 @@ def _fold_decode_err(counts, decoded):
     counts.err[:1].bitwise_or_((decoded["err"].reshape(-1)[:1] != 0).to(torch.int32) * 128)
 
 
-def _long_event_call(est_args, est_cap, ref, t_collar, percentage_of_length, time_resolution, counts, point, per_column):
+def _long_rows(counts, K, NC, point0, fn):
+    """Checks that ``counts`` has the rows ``point0 .. point0 + K - 1`` and puts the long calls' error wording on it."""
+    if counts.NC != NC or point0 < 0 or point0 + K > counts.K:
+        raise ValueError(f"counts holds {counts.K} operating points of {counts.NC} classes: no rows {point0} .. "
+                         f"{point0 + K - 1} of {NC} classes")
+    counts.err_what, counts.err_bits = fn, _LONG_ERR_BITS
+
+
+def _long_event_target(sweep, est_args, est_cap, K, ref, t_collar, percentage_of_length, time_resolution, counts, point0,
+                       per_column):
     n, NC, dev = len(ref), ref.nclass, ref.device
+    fn, ws_fn, lead = (("sed_long_sweep_event_counts", "sed_long_sweep_ws_bytes", (K,)) if sweep
+                       else ("sed_long_event_counts", "sed_long_score_ws_bytes", ()))
     if counts is None:
-        counts = Counts(point + 1, NC, dev)
-    if counts.NC != NC or not 0 <= point < counts.K:
-        raise ValueError(f"counts holds {counts.K} operating points of {counts.NC} classes: no row {point} of {NC} classes")
-    counts.err_what, counts.err_bits = "sed_long_event_counts", _LONG_ERR_BITS
+        counts = Counts(point0 + K, NC, dev)
+    _long_rows(counts, K, NC, point0, fn)
     if per_column:
-        counts.ev_columns = torch.empty(n, NC, 3, dtype=torch.int32, device=dev)
-        counts.seg_columns = torch.empty(n, NC, 4, dtype=torch.int32, device=dev)
-    _long_call("sed_long_event_counts", "sed_long_event_counts", est_args, est_cap, ref,
-               (float(t_collar), float(percentage_of_length), float(time_resolution),
-                _lib.ptr(counts.ev_columns) if per_column else None, _lib.ptr(counts.seg_columns) if per_column else None,
-                _lib.ptr(counts.ev[point]), _lib.ptr(counts.seg[point])), counts.err, dev)
+        counts.ev_columns = torch.empty(*lead, n, NC, 3, dtype=torch.int32, device=dev)
+        counts.seg_columns = torch.empty(*lead, n, NC, 4, dtype=torch.int32, device=dev)
+    _long_counts_call(fn, ws_fn, lead, est_args, est_cap, ref,
+                      (float(t_collar), float(percentage_of_length), float(time_resolution),
+                       _lib.ptr(counts.ev_columns) if per_column else None, _lib.ptr(counts.seg_columns) if per_column else None,
+                       _lib.ptr(counts.ev[point0]), _lib.ptr(counts.seg[point0])), counts.err)
     return counts
 
 
-def _long_psds_call(est_args, est_cap, ref, dtc, gtc, cttc, counts, point, per_column):
+def _long_psds_target(sweep, est_args, est_cap, K, ref, dtc, gtc, cttc, counts, point0, per_column):
     n, NC, dev = len(ref), ref.nclass, ref.device
+    fn, ws_fn, lead = (("sed_long_sweep_psds_counts", "sed_long_sweep_ws_bytes", (K,)) if sweep
+                       else ("sed_long_psds_counts", "sed_long_score_ws_bytes", ()))
     if counts is None:
-        counts = PSDSCounts(point + 1, NC, dev, dtc, gtc, cttc)
-    if counts.NC != NC or not 0 <= point < counts.K:
-        raise ValueError(f"counts holds {counts.K} operating points of {counts.NC} classes: no row {point} of {NC} classes")
+        counts = PSDSCounts(point0 + K, NC, dev, dtc, gtc, cttc)
+    _long_rows(counts, K, NC, point0, fn)
     if (counts.dtc, counts.gtc, counts.cttc) != (float(dtc), float(gtc), float(cttc)):
         raise ValueError("counts was built for other criteria (dtc, gtc, cttc)")
-    counts.err_what, counts.err_bits = "sed_long_psds_counts", _LONG_ERR_BITS
     if per_column:
-        counts.columns = torch.empty(n, NC, 2 + NC, dtype=torch.int32, device=dev)
-    _long_call("sed_long_psds_counts", "sed_long_psds_counts", est_args, est_cap, ref,
-               (counts.dtc, counts.gtc, counts.cttc, _lib.ptr(counts.columns) if per_column else None,
-                _lib.ptr(counts.totals[point])), counts.err, dev)
+        counts.columns = torch.empty(*lead, n, NC, 2 + NC, dtype=torch.int32, device=dev)
+    _long_counts_call(fn, ws_fn, lead, est_args, est_cap, ref,
+                      (counts.dtc, counts.gtc, counts.cttc, _lib.ptr(counts.columns) if per_column else None,
+                       _lib.ptr(counts.totals[point0])), counts.err)
     return counts
 
 
@@ -714,8 +742,9 @@ def long_event_counts(decoded, ref, pooling_time_ratio, cfg=None, t_collar=0.200
     call.  No synchronisation: ``decoded["err"]`` is folded into the counts' error word on the device, ``host()`` raises.
     Columns have no length limit; a CLUSTER (events whose onsets chain within ``t_collar``) holds at most 64 per side.
     Seconds as in ``event_counts``: ``frame * pooling_time_ratio / (sample_rate / hop_length)`` from ``cfg``."""
-    est_args, cap = _decoded_args(decoded, ref, pooling_time_ratio, cfg, "long_event_counts")
-    counts = _long_event_call(est_args, cap, ref, t_collar, percentage_of_length, time_resolution, counts, point, per_column)
+    est_args, cap, _ = _decoded_args(decoded, ref, pooling_time_ratio, cfg, "long_event_counts", K=1)
+    counts = _long_event_target(False, est_args, cap, 1, ref, t_collar, percentage_of_length, time_resolution, counts, point,
+                                per_column)
     _fold_decode_err(counts, decoded)
     return counts
 
@@ -724,8 +753,8 @@ def long_psds_counts(decoded, ref, pooling_time_ratio, cfg=None, dtc=0.5, gtc=0.
                      per_column=False):
     """``long_event_counts`` for the PSDS criteria: totals into row ``point`` of a ``PSDSCounts`` (its criteria must be
     these); ``per_column``: ``counts.columns [n_rec, nclass, 2 + nclass]``."""
-    est_args, cap = _decoded_args(decoded, ref, pooling_time_ratio, cfg, "long_psds_counts")
-    counts = _long_psds_call(est_args, cap, ref, dtc, gtc, cttc, counts, point, per_column)
+    est_args, cap, _ = _decoded_args(decoded, ref, pooling_time_ratio, cfg, "long_psds_counts", K=1)
+    counts = _long_psds_target(False, est_args, cap, 1, ref, dtc, gtc, cttc, counts, point, per_column)
     _fold_decode_err(counts, decoded)
     return counts
 
@@ -734,95 +763,15 @@ def long_event_counts_from_events(est, ref, t_collar=0.200, percentage_of_length
                                   per_column=False):
     """The scoring stage alone on two ``RefEvents`` (``est``: the ESTIMATED events of the same files and classes; they need
     not be disjoint, both are sorted by onset as ``RefEvents.from_dataframe`` packs them).  No limit of 64 events per column."""
-    est_args, cap = _events_args(est, ref, "long_event_counts_from_events")
-    return _long_event_call(est_args, cap, ref, t_collar, percentage_of_length, time_resolution, counts, point, per_column)
+    est_args, cap, _ = _events_args([est], ref, "long_event_counts_from_events")
+    return _long_event_target(False, est_args, cap, 1, ref, t_collar, percentage_of_length, time_resolution, counts, point,
+                              per_column)
 
 
 def long_psds_counts_from_events(est, ref, dtc=0.5, gtc=0.5, cttc=0.3, counts=None, point=0, per_column=False):
     """The PSDS criteria alone on two ``RefEvents``; no limit of 64 events per column."""
-    est_args, cap = _events_args(est, ref, "long_psds_counts_from_events")
-    return _long_psds_call(est_args, cap, ref, dtc, gtc, cttc, counts, point, per_column)
-
-
-# ---- K operating points of long recordings: the table of sed_stitch_sweep (or K given event sets) against one reference ---------
-def _long_sweep_call(fn, est_args, est_cap, ref, K, tail, err, dev):
-    """One ``sed_long_sweep_*`` call; ``est_args`` / ``tail`` as in ``_long_call``."""
-    l = _lib.lib()
-    n, NC, n_ref = len(ref), ref.nclass, len(ref.onset_host)
-    ws_bytes = l.sed_long_sweep_ws_bytes(int(est_cap), n_ref, n, NC, K)
-    if ws_bytes == 0:
-        raise _lib.SedError(f"sed_long_sweep_ws_bytes: {l.sed_last_error().decode()}")
-    ws = _lib.scratch(ws_bytes, dev)
-    ev_ptr, ev_pairs, num, den, on, off = est_args
-    _lib.check(getattr(l, fn)(_lib.ptr(ev_ptr), _lib.ptr(ev_pairs), float(num), float(den), _lib.ptr(on), _lib.ptr(off),
-                              int(est_cap), _lib.ptr(ref.ptr64), _lib.ptr(ref.onset), _lib.ptr(ref.offset), n_ref, n, NC, K,
-                              *tail, _lib.ptr(err), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), fn)
-
-
-def _sweep_decoded_args(decoded, ref, pooling_time_ratio, cfg, what):
-    cfg = cfg or _Cfg
-    ev_ptr, ev_pairs, K = decoded["ev_ptr"], decoded["ev_pairs"], int(decoded.get("n_points", 1))
-    if ev_ptr.device.type != "cuda" or ref.device.type != "cuda":
-        raise _lib.SedError(f"{what} needs the decoded table and a RefEvents on the GPU (no CPU fallback)")
-    if K < 1 or ev_ptr.dtype != torch.int64 or ev_pairs.dtype != torch.int32 or ev_ptr.numel() != K * len(ref) * ref.nclass + 1:
-        raise ValueError(f"decoded: ev_ptr int64 [{K * len(ref) * ref.nclass + 1}] and ev_pairs int32 [capacity, 2] expected "
-                         f"({K} points, {len(ref)} recordings, {ref.nclass} classes)")
-    return (ev_ptr, ev_pairs.contiguous(), float(pooling_time_ratio), float(cfg.sample_rate / cfg.hop_length), None, None), \
-        ev_pairs.shape[0], K
-
-
-def _sweep_events_args(ests, ref, what):
-    """K ``RefEvents`` as one CSR in column order (k, rec, c), assembled on the device (the sizes are known on the host)."""
-    ests = list(ests)
-    if not ests:
-        raise ValueError(f"{what}: need at least one estimated event set")
-    for est in ests:
-        if est.device.type != "cuda" or ref.device.type != "cuda":
-            raise _lib.SedError(f"{what} needs every event set on the GPU (no CPU fallback)")
-        if est.filenames != ref.filenames or est.labels != ref.labels:
-            raise ValueError("estimated and reference events must cover the same files and classes, in the same order")
-    sizes = [len(est.onset_host) for est in ests]
-    base = np.r_[0, np.cumsum(sizes)]
-    ptr = torch.cat([est.ptr64[:-1] + int(base[k]) for k, est in enumerate(ests)] + [ests[-1].ptr64[-1:] + int(base[-2])])
-    on = torch.cat([est.onset[:n] for est, n in zip(ests, sizes)] + [ests[-1].onset[-1:]])        # (one trailing element)
-    off = torch.cat([est.offset[:n] for est, n in zip(ests, sizes)] + [ests[-1].offset[-1:]])
-    return (ptr, None, 0.0, 0.0, on, off), int(base[-1]), len(ests)
-
-
-def _long_sweep_event_call(est_args, est_cap, K, ref, t_collar, percentage_of_length, time_resolution, counts, point0, per_column):
-    n, NC, dev = len(ref), ref.nclass, ref.device
-    if counts is None:
-        counts = Counts(point0 + K, NC, dev)
-    if counts.NC != NC or point0 < 0 or point0 + K > counts.K:
-        raise ValueError(f"counts holds {counts.K} operating points of {counts.NC} classes: no rows {point0} .. "
-                         f"{point0 + K - 1} of {NC} classes")
-    counts.err_what, counts.err_bits = "sed_long_sweep_event_counts", _LONG_ERR_BITS
-    if per_column:
-        counts.ev_columns = torch.empty(K, n, NC, 3, dtype=torch.int32, device=dev)
-        counts.seg_columns = torch.empty(K, n, NC, 4, dtype=torch.int32, device=dev)
-    _long_sweep_call("sed_long_sweep_event_counts", est_args, est_cap, ref, K,
-                     (float(t_collar), float(percentage_of_length), float(time_resolution),
-                      _lib.ptr(counts.ev_columns) if per_column else None, _lib.ptr(counts.seg_columns) if per_column else None,
-                      _lib.ptr(counts.ev[point0]), _lib.ptr(counts.seg[point0])), counts.err, dev)
-    return counts
-
-
-def _long_sweep_psds_call(est_args, est_cap, K, ref, dtc, gtc, cttc, counts, point0, per_column):
-    n, NC, dev = len(ref), ref.nclass, ref.device
-    if counts is None:
-        counts = PSDSCounts(point0 + K, NC, dev, dtc, gtc, cttc)
-    if counts.NC != NC or point0 < 0 or point0 + K > counts.K:
-        raise ValueError(f"counts holds {counts.K} operating points of {counts.NC} classes: no rows {point0} .. "
-                         f"{point0 + K - 1} of {NC} classes")
-    if (counts.dtc, counts.gtc, counts.cttc) != (float(dtc), float(gtc), float(cttc)):
-        raise ValueError("counts was built for other criteria (dtc, gtc, cttc)")
-    counts.err_what, counts.err_bits = "sed_long_sweep_psds_counts", _LONG_ERR_BITS
-    if per_column:
-        counts.columns = torch.empty(K, n, NC, 2 + NC, dtype=torch.int32, device=dev)
-    _long_sweep_call("sed_long_sweep_psds_counts", est_args, est_cap, ref, K,
-                     (counts.dtc, counts.gtc, counts.cttc, _lib.ptr(counts.columns) if per_column else None,
-                      _lib.ptr(counts.totals[point0])), counts.err, dev)
-    return counts
+    est_args, cap, _ = _events_args([est], ref, "long_psds_counts_from_events")
+    return _long_psds_target(False, est_args, cap, 1, ref, dtc, gtc, cttc, counts, point, per_column)
 
 
 def long_sweep_event_counts(decoded, ref, pooling_time_ratio, cfg=None, t_collar=0.200, percentage_of_length=0.2,
@@ -831,9 +780,9 @@ def long_sweep_event_counts(decoded, ref, pooling_time_ratio, cfg=None, t_collar
     ``sed_long_sweep_event_counts`` call, the reference side prepared once.  The totals ACCUMULATE into rows ``point0 ..
     point0 + K - 1`` of ``counts`` (None: a new ``Counts`` of ``point0 + K`` rows); ``per_column``: ``counts.ev_columns
     [K, n_rec, nclass, 3]`` / ``seg_columns [K, n_rec, nclass, 4]``.  The decoder's error word is folded in on the device."""
-    est_args, cap, K = _sweep_decoded_args(decoded, ref, pooling_time_ratio, cfg, "long_sweep_event_counts")
-    counts = _long_sweep_event_call(est_args, cap, K, ref, t_collar, percentage_of_length, time_resolution, counts, point0,
-                                    per_column)
+    est_args, cap, K = _decoded_args(decoded, ref, pooling_time_ratio, cfg, "long_sweep_event_counts")
+    counts = _long_event_target(True, est_args, cap, K, ref, t_collar, percentage_of_length, time_resolution, counts, point0,
+                                per_column)
     _fold_decode_err(counts, decoded)
     return counts
 
@@ -842,8 +791,8 @@ def long_sweep_psds_counts(decoded, ref, pooling_time_ratio, cfg=None, dtc=0.5, 
                            per_column=False):
     """``long_sweep_event_counts`` for the PSDS criteria: rows ``point0 .. point0 + K - 1`` of a ``PSDSCounts`` (its criteria
     must be these); ``per_column``: ``counts.columns [K, n_rec, nclass, 2 + nclass]``."""
-    est_args, cap, K = _sweep_decoded_args(decoded, ref, pooling_time_ratio, cfg, "long_sweep_psds_counts")
-    counts = _long_sweep_psds_call(est_args, cap, K, ref, dtc, gtc, cttc, counts, point0, per_column)
+    est_args, cap, K = _decoded_args(decoded, ref, pooling_time_ratio, cfg, "long_sweep_psds_counts")
+    counts = _long_psds_target(True, est_args, cap, K, ref, dtc, gtc, cttc, counts, point0, per_column)
     _fold_decode_err(counts, decoded)
     return counts
 
@@ -852,15 +801,15 @@ def long_sweep_event_counts_from_events(ests, ref, t_collar=0.200, percentage_of
                                         point0=0, per_column=False):
     """The scoring stage alone: ``ests`` is a list of K ``RefEvents``, the estimated events of K operating points (same files
     and classes as ``ref``, sorted by onset), scored in one call against the one reference side."""
-    est_args, cap, K = _sweep_events_args(ests, ref, "long_sweep_event_counts_from_events")
-    return _long_sweep_event_call(est_args, cap, K, ref, t_collar, percentage_of_length, time_resolution, counts, point0,
-                                  per_column)
+    est_args, cap, K = _events_args(ests, ref, "long_sweep_event_counts_from_events")
+    return _long_event_target(True, est_args, cap, K, ref, t_collar, percentage_of_length, time_resolution, counts, point0,
+                              per_column)
 
 
 def long_sweep_psds_counts_from_events(ests, ref, dtc=0.5, gtc=0.5, cttc=0.3, counts=None, point0=0, per_column=False):
     """The PSDS criteria alone on a list of K ``RefEvents`` against one reference side."""
-    est_args, cap, K = _sweep_events_args(ests, ref, "long_sweep_psds_counts_from_events")
-    return _long_sweep_psds_call(est_args, cap, K, ref, dtc, gtc, cttc, counts, point0, per_column)
+    est_args, cap, K = _events_args(ests, ref, "long_sweep_psds_counts_from_events")
+    return _long_psds_target(True, est_args, cap, K, ref, dtc, gtc, cttc, counts, point0, per_column)
 
 
 def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, batch_size=64, cfg=None, weighting="taper",

@@ -10,88 +10,16 @@ import torch
 from oracle import postprocess_np as pp
 from tests import gpu_util as gu
 from tests import stitch_np
+from tests.long_util import SENT, StitchCall, _n_windows, _Scaler, _tables, _tile
 
 pytestmark = pytest.mark.gpu
 
-SENT_I = -7
-
-
-def _tile():
-    from dcase2019_task4_amd import _lib
-    return int(_lib.lib().sed_stitch_tile_frames())
+SENT_I = SENT
 
 
 def _lengths(hop3=8):
     t = _tile()
     return [1, 7, 8, 9, 8 + hop3, t - 1, t, t + 1, 2 * t + 5]
-
-
-def _n_windows(L3, T3, hop3):
-    return 1 if L3 <= T3 else 1 + -(-(L3 - T3) // hop3)
-
-
-def _tables(L3s, T3, hop3):
-    return (np.r_[0, np.cumsum([_n_windows(L, T3, hop3) for L in L3s])].astype(np.int32),
-            np.r_[0, np.cumsum(L3s)].astype(np.int64))
-
-
-class _Call:
-    """One sed_stitch_decode call on sentinel-filled outputs (NaN timeline, 0xEE binary, -7 integers); ``misalign`` shifts the
-    window posteriors and the timeline off 16-byte alignment."""
-
-    def __init__(self, p, rec_win0, rec_frame0, hop3, weighting, thr, win, capacity=None, misalign=False, tail=8):
-        from dcase2019_task4_amd import _lib
-        self.l = _lib.lib()
-        self._lib = _lib
-        p = np.ascontiguousarray(p, dtype=np.float32)
-        self.n_win, self.T3, self.NC = p.shape
-        self.n_rec, self.total = len(rec_win0) - 1, int(rec_frame0[-1])
-        self.hop3, self.weighting = int(hop3), int(weighting)
-        off = 1 if misalign else 0
-        self._p = torch.empty(p.size + off, dtype=torch.float32, device="cuda")
-        self.p = self._p[off:]
-        self.p.copy_(torch.from_numpy(p.reshape(-1)))
-        self.rec_win0 = torch.from_numpy(np.asarray(rec_win0, dtype=np.int32)).cuda()
-        self.rec_frame0 = torch.from_numpy(np.asarray(rec_frame0, dtype=np.int64)).cuda()
-        self.thr = torch.from_numpy(np.asarray(thr, dtype=np.float32)).cuda()
-        self.win = torch.from_numpy(np.asarray(win, dtype=np.int32)).cuda()
-        L3 = np.diff(np.asarray(rec_frame0, dtype=np.int64))
-        self.capacity = int(self.NC * ((np.maximum(L3, 0) + 1) // 2).sum()) if capacity is None else int(capacity)
-        self._tl = torch.empty(self.total * self.NC + off, dtype=torch.float32, device="cuda")
-        self.timeline = self._tl[off:]
-        self.binary = torch.empty(self.total * self.NC, dtype=torch.uint8, device="cuda")
-        self.ev_ptr = torch.empty(self.n_rec * self.NC + 1, dtype=torch.int64, device="cuda")
-        self.ev_pairs = torch.empty(self.capacity + tail, 2, dtype=torch.int32, device="cuda")
-        self.err = torch.empty(1, dtype=torch.int32, device="cuda")
-        self.ws = torch.empty(self.l.sed_stitch_decode_ws_bytes(self.total, self.n_rec, self.NC), dtype=torch.uint8, device="cuda")
-        assert self.ws.numel() > 0
-        assert (self.p.data_ptr() % 16 != 0) == bool(misalign)
-
-    def fill(self):
-        self._tl.fill_(float("nan"))
-        self.binary.fill_(0xEE)
-        self.ev_ptr.fill_(SENT_I)
-        self.ev_pairs.fill_(SENT_I)
-        self.ws.fill_(0xFF)
-        self.err.zero_()
-
-    def launch(self):
-        ptr = self._lib.ptr
-        return self.l.sed_stitch_decode(ptr(self.p), ptr(self.rec_win0), ptr(self.rec_frame0), self.n_rec, self.T3, self.NC,
-                                        self.hop3, self.weighting, ptr(self.thr), ptr(self.win), ptr(self.timeline),
-                                        ptr(self.binary), ptr(self.ev_ptr), ptr(self.ev_pairs), self.capacity, ptr(self.ws),
-                                        self.ws.numel(), ptr(self.err), self._lib.stream_ptr())
-
-    def run(self):
-        self.fill()
-        assert self.launch() == 0, self.l.sed_last_error()
-        return self.get()
-
-    def get(self):
-        torch.cuda.synchronize()
-        return {"timeline": self.timeline.cpu().numpy().reshape(self.total, self.NC),
-                "binary": self.binary.cpu().numpy().reshape(self.total, self.NC),
-                "ev_ptr": self.ev_ptr.cpu().numpy(), "ev_pairs": self.ev_pairs.cpu().numpy(), "err": int(self.err.item())}
 
 
 def _check_decode(got, timeline, rec_frame0, thr, win, capacity):
@@ -118,7 +46,7 @@ def test_blend_is_bitwise_the_numpy_statement(NC, misalign, hop3, weighting):
     p = rs.uniform(size=(rec_win0[-1], T3, NC)).astype(np.float32)
     thr = (0.35 + 0.02 * np.arange(NC)).astype(np.float32)
     win = np.array([1, 5, 63][:NC] * 6)[:NC]
-    call = _Call(p, rec_win0, rec_frame0, hop3, weighting, thr, win, misalign=misalign)
+    call = StitchCall(p, rec_win0, rec_frame0, hop3, weighting, thr, win, misalign=misalign)
     got = call.run()
     want = stitch_np.blend(p, rec_win0, rec_frame0, hop3, weighting)
     np.testing.assert_array_equal(got["timeline"].view(np.uint32), want.view(np.uint32))
@@ -138,7 +66,7 @@ def test_blend_at_the_baseline_geometry_and_mixed_recordings_in_one_call():
     p = np.random.RandomState(5).uniform(size=(rec_win0[-1], T3, NC)).astype(np.float32)
     thr, win = np.full(NC, 0.5, np.float32), np.full(NC, 5)
     for weighting in (0, 1):
-        got = _Call(p, rec_win0, rec_frame0, hop3, weighting, thr, win).run()
+        got = StitchCall(p, rec_win0, rec_frame0, hop3, weighting, thr, win).run()
         want = stitch_np.blend(p, rec_win0, rec_frame0, hop3, weighting)
         np.testing.assert_array_equal(got["timeline"].view(np.uint32), want.view(np.uint32))
         np.testing.assert_array_equal(got["timeline"][rec_frame0[1]:rec_frame0[2]].view(np.uint32), p[rec_win0[1]].view(np.uint32))
@@ -193,7 +121,7 @@ def test_decode_patterns_are_exact(name):
     tls = [_pattern(name, L3, rs) for L3 in L3s]
     p = np.concatenate([np.concatenate([t, np.full((-len(t) % T3, NC_D), 0.95, np.float32)]).reshape(-1, T3, NC_D) for t in tls])
     win = np.ones(NC_D, dtype=int) if name == "alternating" else WIN_D
-    call = _Call(p, rec_win0, rec_frame0, T3, 1, THR_D, win)
+    call = StitchCall(p, rec_win0, rec_frame0, T3, 1, THR_D, win)
     got = call.run()
     timeline = np.concatenate(tls)
     np.testing.assert_array_equal(got["timeline"].view(np.uint32), timeline.view(np.uint32))
@@ -219,7 +147,7 @@ def _alternating_call(**kw):
     p = np.concatenate([np.resize(np.array([[0.9] * NC, [0.1] * NC], np.float32), (_n_windows(L, T3, T3) * T3, NC)).reshape(-1, T3, NC)
                         for L in L3s])
     total = NC * sum((L + 1) // 2 for L in L3s)
-    return _Call(p, rec_win0, rec_frame0, T3, 0, np.full(NC, 0.5, np.float32), np.ones(NC, int), **kw), total, rec_frame0
+    return StitchCall(p, rec_win0, rec_frame0, T3, 0, np.full(NC, 0.5, np.float32), np.ones(NC, int), **kw), total, rec_frame0
 
 
 def test_capacity_one_short_raises_bit_2_and_writes_nothing_beyond():
@@ -250,7 +178,7 @@ def test_too_few_windows_raise_bit_32_without_touching_anything_else():
     rec_win0 = np.array([0, 1, 3, 4], dtype=np.int32)
     rec_frame0 = np.array([0, 8, 38, 46], dtype=np.int64)
     p = np.full((4, T3, NC), 0.9, dtype=np.float32)
-    got = _Call(p, rec_win0, rec_frame0, T3, 0, np.full(NC, 0.5, np.float32), np.ones(NC, int)).run()
+    got = StitchCall(p, rec_win0, rec_frame0, T3, 0, np.full(NC, 0.5, np.float32), np.ones(NC, int)).run()
     assert got["err"] == 32
     per_col = np.diff(got["ev_ptr"]).reshape(3, NC)
     assert (per_col[1] == 0).all() and (per_col[0] == 1).all() and (per_col[2] == 1).all()
@@ -262,7 +190,7 @@ def test_malformed_tables_raise_bit_16():
     T3, NC = 8, 3
     p = np.full((3, T3, NC), 0.9, dtype=np.float32)
     for rec_win0, rec_frame0 in [([0, 1, 3], [0, 8, 8]), ([0, 2, 1], [0, 8, 16]), ([0, 1, 2], [0, 20, 16])]:
-        got = _Call(p, np.array(rec_win0, np.int32), np.array(rec_frame0, np.int64), T3, 0, np.full(NC, 0.5, np.float32),
+        got = StitchCall(p, np.array(rec_win0, np.int32), np.array(rec_frame0, np.int64), T3, 0, np.full(NC, 0.5, np.float32),
                     np.ones(NC, int), capacity=64).run()
         assert got["err"] & 16, (rec_win0, rec_frame0)
 
@@ -276,7 +204,7 @@ def test_bad_host_arguments_return_bad_arg_before_any_launch():
     def go(T3=8, NC=3, hop3=8, weighting=0, n_rec=2, capacity=call.capacity, p=call.p, ws=call.ws, ws_bytes=None):
         return l.sed_stitch_decode(ptr(p), ptr(call.rec_win0), ptr(call.rec_frame0), n_rec, T3, NC, hop3, weighting, ptr(call.thr),
                                    ptr(call.win), ptr(call.timeline), ptr(call.binary), ptr(call.ev_ptr), ptr(call.ev_pairs),
-                                   capacity, ptr(ws), call.ws.numel() if ws_bytes is None else ws_bytes, ptr(call.err),
+                                   capacity, ptr(ws), call.ws_bytes if ws_bytes is None else ws_bytes, ptr(call.err),
                                    _lib.stream_ptr())
 
     for kw in (dict(NC=17), dict(NC=0), dict(hop3=0), dict(hop3=9), dict(T3=0), dict(weighting=2), dict(n_rec=0),
@@ -285,7 +213,7 @@ def test_bad_host_arguments_return_bad_arg_before_any_launch():
     assert go(ws_bytes=8) == -2                                                # SED_ERR_WORKSPACE
     assert l.sed_stitch_decode_ws_bytes(1 << 28, 1, 10) == 0 and l.sed_stitch_decode_ws_bytes(100, 1, 17) == 0
     torch.cuda.synchronize()
-    assert int(call.ev_ptr[0].item()) == SENT_I and int(call.err.item()) == 0  # nothing ran
+    assert int(call.ev_ptr[0].item()) == SENT_I and int(call.err[0].item()) == 0  # nothing ran
     with pytest.raises(ValueError):
         from dcase2019_task4_amd.inference import stitch_decode
         stitch_decode(call.p.view(-1, 8, 3), call.rec_win0, call.rec_frame0, call.total, 8, weighting="hann")
@@ -296,7 +224,7 @@ def test_two_calls_and_a_graph_replay_give_identical_bytes():
     L3s = [_tile() + 9, 5, 40]
     rec_win0, rec_frame0 = _tables(L3s, T3, hop3)
     p = np.random.RandomState(9).uniform(size=(rec_win0[-1], T3, NC)).astype(np.float32)
-    call = _Call(p, rec_win0, rec_frame0, hop3, 1, np.full(NC, 0.5, np.float32), np.array([1, 3, 5, 7, 9] * 2))
+    call = StitchCall(p, rec_win0, rec_frame0, hop3, 1, np.full(NC, 0.5, np.float32), np.array([1, 3, 5, 7, 9] * 2))
     a = call.run()
     b = call.run()
     for k in ("timeline", "binary", "ev_ptr", "ev_pairs"):
@@ -321,7 +249,7 @@ def test_single_window_recordings_agree_with_sed_postprocess(T3, NC, win):
     n = 5
     p = np.random.RandomState(T3).uniform(size=(n, T3, NC)).astype(np.float32)
     rec_win0, rec_frame0 = np.arange(n + 1, dtype=np.int32), np.arange(n + 1, dtype=np.int64) * T3
-    got = _Call(p, rec_win0, rec_frame0, T3, 1, np.full(NC, 0.5, np.float32), np.full(NC, win)).run()
+    got = StitchCall(p, rec_win0, rec_frame0, T3, 1, np.full(NC, 0.5, np.float32), np.full(NC, win)).run()
     cnt, pairs = postprocess(torch.from_numpy(p).cuda(), 0.5, win)
     cnt, pairs = cnt.cpu().numpy().reshape(-1), pairs.cpu().numpy().reshape(n * NC, -1, 2)
     assert got["err"] == 0
@@ -332,13 +260,6 @@ def test_single_window_recordings_agree_with_sed_postprocess(T3, NC, win):
 
 
 # ---- end to end, small model ---------------------------------------------------------------------------------------------------
-class _Scaler:
-    def __init__(self, n_mels):
-        rs = np.random.RandomState(11)
-        self.mean_ = rs.uniform(-30, -10, n_mels)
-        self.std_ = rs.uniform(5, 15, n_mels)
-
-
 class _Enc:
     def __init__(self, labels):
         self.labels = labels

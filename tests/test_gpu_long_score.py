@@ -13,106 +13,13 @@ from tests import gpu_util as gu
 from tests import long_score_np as ls
 from tests import psds_np
 from tests import sed_eval_np as se
+from tests.long_util import SENT, ScoreCall, _ref_events, _Scaler, _stitch_inputs
 
 pytestmark = pytest.mark.gpu
-
-SENT = -7
-TAIL = 8
-
 
 def _tile():
     from dcase2019_task4_amd import _lib
     return int(_lib.lib().sed_long_tile_events())
-
-
-def _ref_events(cols):
-    from dcase2019_task4_amd.metrics import RefEvents
-    ptr, on, off = ls.pack(cols)
-    return RefEvents(ptr, on, off, [f"r{i}" for i in range(len(cols))], [f"c{i}" for i in range(len(cols[0]))])
-
-
-class _Raw:
-    """The two C calls on sentinel-filled outputs with a tail of TAIL elements: given events (``est`` = (ptr, on, off)) or
-    frames (``est`` = (ptr, pairs, num, den)); ``ref`` = (ptr, on, off).  Arrays are numpy; ptr int64."""
-
-    def __init__(self, est, ref, n_rec, NC, est_cap=None, ref_cap=None):
-        from dcase2019_task4_amd import _lib
-        self._lib, self.l = _lib, _lib.lib()
-        self.n_rec, self.NC = n_rec, NC
-        dev = "cuda"
-        self.frames = len(est) == 4
-        self.est_ptr = torch.from_numpy(np.asarray(est[0], np.int64)).to(dev)
-        if self.frames:                                               # the device table as sed_stitch_decode left it
-            self.pairs, self.num, self.den, self.on, self.off = est[1], float(est[2]), float(est[3]), None, None
-            n_est = est[1].shape[0]                                   # its capacity, not the true count
-        else:
-            self.pairs, self.num, self.den = None, 0.0, 0.0
-            self.on = torch.from_numpy(np.r_[np.asarray(est[1], np.float64), 0.0]).to(dev)
-            self.off = torch.from_numpy(np.r_[np.asarray(est[2], np.float64), 0.0]).to(dev)
-            n_est = len(est[1])
-        self.est_cap = n_est if est_cap is None else est_cap
-        self.ref_ptr = torch.from_numpy(np.asarray(ref[0], np.int64)).to(dev)
-        self.ref_on = torch.from_numpy(np.r_[np.asarray(ref[1], np.float64), 0.0]).to(dev)
-        self.ref_off = torch.from_numpy(np.r_[np.asarray(ref[2], np.float64), 0.0]).to(dev)
-        self.ref_cap = len(ref[1]) if ref_cap is None else ref_cap
-        ncols, W = n_rec * NC, 2 + NC
-        mk = lambda n, dt: torch.empty(n + TAIL, dtype=dt, device=dev)
-        self.ev_c, self.seg_c, self.ps_c = mk(ncols * 3, torch.int32), mk(ncols * 4, torch.int32), mk(ncols * W, torch.int32)
-        self.ev_t, self.seg_t, self.ps_t = mk(NC * 3, torch.int64), mk(NC * 4, torch.int64), mk(NC * W, torch.int64)
-        self.err = torch.empty(2, dtype=torch.int32, device=dev)
-        nbytes = self.l.sed_long_score_ws_bytes(self.est_cap, self.ref_cap, n_rec, NC)
-        assert nbytes > 0, self.l.sed_last_error()
-        self.ws = torch.empty(nbytes + TAIL, dtype=torch.uint8, device=dev)
-
-    def fill(self):
-        ncols, NC, W = self.n_rec * self.NC, self.NC, 2 + self.NC
-        for t in (self.ev_c, self.seg_c, self.ps_c):
-            t.fill_(SENT)
-        for t, n in ((self.ev_t, NC * 3), (self.seg_t, NC * 4), (self.ps_t, NC * W)):
-            t.fill_(SENT)
-            t[:n].zero_()
-        self.err.fill_(SENT)
-        self.err[:1].zero_()
-        self.ws.fill_(0xFF)
-
-    def _head(self):
-        p = self._lib.ptr
-        return (p(self.est_ptr), p(self.pairs), self.num, self.den, p(self.on), p(self.off), self.est_cap, p(self.ref_ptr),
-                p(self.ref_on), p(self.ref_off), self.ref_cap, self.n_rec, self.NC)
-
-    def launch_events(self, t_collar=0.2, pct=0.2, res=1.0, columns=True):
-        p = self._lib.ptr
-        return self.l.sed_long_event_counts(*self._head(), float(t_collar), float(pct), float(res),
-                                            p(self.ev_c) if columns else None, p(self.seg_c) if columns else None, p(self.ev_t),
-                                            p(self.seg_t), p(self.err), p(self.ws), self.ws.numel() - TAIL, self._lib.stream_ptr())
-
-    def launch_psds(self, dtc=0.5, gtc=0.5, cttc=0.3, columns=True):
-        p = self._lib.ptr
-        return self.l.sed_long_psds_counts(*self._head(), float(dtc), float(gtc), float(cttc), p(self.ps_c) if columns else None,
-                                           p(self.ps_t), p(self.err), p(self.ws), self.ws.numel() - TAIL, self._lib.stream_ptr())
-
-    def get(self):
-        """Everything as numpy, after checking that nothing beyond the owned elements was written."""
-        torch.cuda.synchronize()
-        ncols, NC, W = self.n_rec * self.NC, self.NC, 2 + self.NC
-        out = {}
-        for name, t, n, shape in (("ev", self.ev_c, ncols * 3, (self.n_rec, NC, 3)), ("seg", self.seg_c, ncols * 4, (self.n_rec, NC, 4)),
-                                  ("ps", self.ps_c, ncols * W, (self.n_rec, NC, W)), ("ev_t", self.ev_t, NC * 3, (NC, 3)),
-                                  ("seg_t", self.seg_t, NC * 4, (NC, 4)), ("ps_t", self.ps_t, NC * W, (NC, W))):
-            h = t.cpu().numpy()
-            assert (h[n:] == SENT).all(), name
-            out[name] = h[:n].reshape(shape)
-        assert int(self.err[1].item()) == SENT and (self.ws[-TAIL:] == 0xFF).all()
-        out["err"] = int(self.err[0].item())
-        return out
-
-    def run(self, events=True, psds=True, **kw):
-        self.fill()
-        if events:
-            assert self.launch_events(**{k: v for k, v in kw.items() if k in ("t_collar", "pct", "res")}) == 0, self.l.sed_last_error()
-        if psds:
-            assert self.launch_psds(**{k: v for k, v in kw.items() if k in ("dtc", "gtc", "cttc")}) == 0, self.l.sed_last_error()
-        return self.get()
 
 
 @functools.lru_cache(maxsize=None)
@@ -157,7 +64,7 @@ def test_given_events_are_exact_and_two_runs_identical(name):
     """main: 3 x 3 columns of 0, 1, 64, 65, ~900 (bursts), tile - 1, tile, tile + 1 and 2 tile + 5 reference events, with
     clusters across tile edges, zero-length events, overlapping references and detections over other classes' references."""
     ref, est, ev, seg, ps = _case(name)
-    raw = _Raw(ls.pack(est), ls.pack(ref), len(ref), len(ref[0]))
+    raw = ScoreCall(ls.pack(est), ls.pack(ref), len(ref), len(ref[0]))
     a = raw.run()
     _check_all(a, ev, seg, ps)
     if name == "main":
@@ -182,12 +89,12 @@ def test_other_criteria_and_resolutions():
     ref, est, _, _, _ = _case("small")
     for kw in (dict(t_collar=0.5, percentage_of_length=0.5, res=0.25), dict(t_collar=0.0, percentage_of_length=0.0, res=7.0)):
         ev, seg = se.set_counts(ref, est, **kw)
-        got = _Raw(ls.pack(est), ls.pack(ref), 3, 3).run(psds=False, t_collar=kw["t_collar"], pct=kw["percentage_of_length"],
+        got = ScoreCall(ls.pack(est), ls.pack(ref), 3, 3).run(psds=False, t_collar=kw["t_collar"], pct=kw["percentage_of_length"],
                                                          res=kw["res"])
         _check_all(got, ev, seg, None, psds=False)
     for kw in (dict(dtc=0.1, gtc=0.1, cttc=0.1), dict(dtc=1.0, gtc=0.9, cttc=0.0)):
         ps = np.array(psds_np.set_counts(ref, est, **kw))
-        _check_all(_Raw(ls.pack(est), ls.pack(ref), 3, 3).run(events=False, **kw), None, None, ps, events=False)
+        _check_all(ScoreCall(ls.pack(est), ls.pack(ref), 3, 3).run(events=False, **kw), None, None, ps, events=False)
 
 
 # ---- the collar boundary -------------------------------------------------------------------------------------------------------------
@@ -196,14 +103,14 @@ def test_exactly_t_collar_apart_is_not_cut_and_one_ulp_more_is():
     80 per side (bits 1 and 2: the pair was not cut); one ulp more and they are two clusters, scored exactly."""
     n = 40
     ref, est = ls.chained_pair(n, 0.0)
-    got = _Raw(ls.pack([[est]]), ls.pack([[ref]]), 1, 1).run(psds=False, t_collar=0.25)
+    got = ScoreCall(ls.pack([[est]]), ls.pack([[ref]]), 1, 1).run(psds=False, t_collar=0.25)
     assert got["err"] == 3 == ls.expected_err([[ref]], [[est]], 0.25)
     long_ref, long_est = ls.chained_pair(70, 0.0)                     # 140 per side: the cluster's end lies beyond the next tile
-    assert _Raw(ls.pack([[long_est]]), ls.pack([[long_ref]]), 1, 1).run(psds=False, t_collar=0.25)["err"] == 3
+    assert ScoreCall(ls.pack([[long_est]]), ls.pack([[long_ref]]), 1, 1).run(psds=False, t_collar=0.25)["err"] == 3
     assert ls.expected_err([[long_ref]], [[long_est]], 0.25) == 3
     ref, est = ls.chained_pair(n, float(np.spacing(ref[n][0])))
     ev, seg = se.set_counts([[ref]], [[est]], t_collar=0.25)
-    got = _Raw(ls.pack([[est]]), ls.pack([[ref]]), 1, 1).run(psds=False, t_collar=0.25)
+    got = ScoreCall(ls.pack([[est]]), ls.pack([[ref]]), 1, 1).run(psds=False, t_collar=0.25)
     _check_all(got, ev, seg, None, psds=False)
     assert ev[0, 0, 0] == 2 * n
     # single pairs: compatible at exactly the collar, not one ulp beyond, on either side
@@ -211,7 +118,7 @@ def test_exactly_t_collar_apart_is_not_cut_and_one_ulp_more_is():
     pairs_est = [(1.25, 2.25), (10.75, 11.75), (float(np.nextafter(21.25, 99)), 22.0), (float(np.nextafter(30.75, 0)), 32.0)]
     ev, seg = se.set_counts([[pairs_ref]], [[pairs_est]], t_collar=0.25)
     assert ev[0, 0, 0] == 2
-    got = _Raw(ls.pack([[pairs_est]]), ls.pack([[pairs_ref]]), 1, 1).run(psds=False, t_collar=0.25)
+    got = ScoreCall(ls.pack([[pairs_est]]), ls.pack([[pairs_ref]]), 1, 1).run(psds=False, t_collar=0.25)
     _check_all(got, ev, seg, None, psds=False)
 
 
@@ -254,22 +161,11 @@ def _decoded_cols(ev_ptr, ev_pairs, n_rec, NC):
 _sorted_refs = ls.sorted_jittered_references
 
 
-def _stitch_inputs():
-    """Window posteriors whose timeline is a prescribed 0.9 / 0.1 pattern (hop3 = T3), three recordings, three classes."""
-    from dcase2019_task4_amd import _lib
-    T3, NC = 8, 3
-    L3s = ls.stitch_lengths(int(_lib.lib().sed_stitch_tile_frames()))
-    tls = [np.where(a, np.float32(0.9), np.float32(0.1)) for a in ls.stitch_patterns(L3s, NC)]
-    n_w = [-(-L // T3) for L in L3s]
-    p = np.concatenate([np.concatenate([t, np.full((-len(t) % T3, NC), 0.1, np.float32)]).reshape(-1, T3, NC) for t in tls])
-    return (torch.from_numpy(p).cuda(), torch.from_numpy(np.r_[0, np.cumsum(n_w)].astype(np.int32)).cuda(),
-            torch.from_numpy(np.r_[0, np.cumsum(L3s)].astype(np.int64)).cuda(), int(sum(L3s)), T3, NC, len(L3s))
-
-
 def test_frames_mode_equals_the_oracle_on_the_hosts_doubles_and_replays_in_a_graph():
     from dcase2019_task4_amd import metrics as M
     from dcase2019_task4_amd.inference import stitch_decode
-    p, rec_win0, rec_frame0, total, T3, NC, n_rec = _stitch_inputs()
+    p, rec_win0, rec_frame0, L3s, T3, NC, _ = _stitch_inputs()
+    total, n_rec = int(sum(L3s)), len(L3s)
     thr = torch.full((NC,), 0.5, device="cuda")
     win = torch.ones(NC, dtype=torch.int32, device="cuda")
     out = stitch_decode(p, rec_win0, rec_frame0, total, T3, thr, win, "uniform", want_timeline=False)
@@ -283,7 +179,7 @@ def test_frames_mode_equals_the_oracle_on_the_hosts_doubles_and_replays_in_a_gra
     ps = np.array(psds_np.set_counts(ref_cols, est_cols))
     ref = _ref_events(ref_cols)
     # the raw call on the table as the decoder left it: capacity, not the true count
-    raw = _Raw((ev_ptr, out["ev_pairs"], NUM, DEN), ls.pack(ref_cols), n_rec, NC)
+    raw = ScoreCall((ev_ptr, out["ev_pairs"], NUM, DEN), ls.pack(ref_cols), n_rec, NC)
     assert raw.est_cap > ev_ptr[-1]
     _check_all(raw.run(), ev, seg, ps)
     # the Python route, eager ...
@@ -313,7 +209,8 @@ def test_a_decoder_error_reaches_host_without_a_synchronisation_of_its_own():
     from dcase2019_task4_amd import _lib
     from dcase2019_task4_amd import metrics as M
     from dcase2019_task4_amd.inference import stitch_decode
-    p, rec_win0, rec_frame0, total, T3, NC, n_rec = _stitch_inputs()
+    p, rec_win0, rec_frame0, L3s, T3, NC, _ = _stitch_inputs()
+    total, n_rec = int(sum(L3s)), len(L3s)
     out = stitch_decode(p, rec_win0, rec_frame0, total, T3, 0.5, 1, "uniform", capacity=10, want_timeline=False)
     ref = _ref_events([[[] for _ in range(NC)] for _ in range(n_rec)])
     c = M.long_event_counts(out, ref, 8)
@@ -324,13 +221,6 @@ def test_a_decoder_error_reaches_host_without_a_synchronisation_of_its_own():
 
 
 # ---- end to end -------------------------------------------------------------------------------------------------------------------------
-class _Scaler:
-    def __init__(self, n_mels):
-        rs = np.random.RandomState(11)
-        self.mean_ = rs.uniform(-30, -10, n_mels)
-        self.std_ = rs.uniform(5, 15, n_mels)
-
-
 def test_validate_long_equals_the_oracle_on_get_long_predictions_at_two_points():
     from dcase2019_task4_amd import metrics as M
     from dcase2019_task4_amd.inference import LongRecordingSet, get_long_predictions
@@ -384,13 +274,13 @@ def test_each_error_bit_alone(ref, est, bit):
     ok_ref, ok_est = ls.spaced_column(np.random.RandomState(2), 30)
     ref_cols, est_cols = [[ok_ref, ref]], [[ok_est, est]]
     assert ls.expected_err(ref_cols, est_cols) == bit
-    got = _Raw(ls.pack(est_cols), ls.pack(ref_cols), 1, 2).run(psds=False)
+    got = ScoreCall(ls.pack(est_cols), ls.pack(ref_cols), 1, 2).run(psds=False)
     assert got["err"] == bit
     assert tuple(got["ev"][0, 1]) == (0, len(ref), len(est)) and (got["seg"][0, 1] == 0).all()      # not scored, not truncated
     if bit != 4:                                                      # (the segment limit is the recording's)
         ev, seg = se.set_counts([[ok_ref]], [[ok_est]])
         np.testing.assert_array_equal(got["ev"][0, 0], ev[0, 0])
-    ps = _Raw(ls.pack(est_cols), ls.pack(ref_cols), 1, 2).run(events=False)
+    ps = ScoreCall(ls.pack(est_cols), ls.pack(ref_cols), 1, 2).run(events=False)
     assert ps["err"] == (64 if bit == 64 else 0)                      # no matching and no segments in PSDS
     if bit != 64:
         np.testing.assert_array_equal(ps["ps"], np.array(psds_np.set_counts(ref_cols, est_cols)))
@@ -403,11 +293,11 @@ def test_the_limit_itself_is_scored():
     """64 onsets inside one collar on both sides: one cluster of 64 + 64, exact; 65 536 segments exactly."""
     ref, est = INSIDE[:64], [(on + 0.001, off) for on, off in INSIDE[:64]]
     ev, seg = se.set_counts([[ref]], [[est]])
-    _check_all(_Raw(ls.pack([[est]]), ls.pack([[ref]]), 1, 1).run(psds=False), ev, seg, None, psds=False)
+    _check_all(ScoreCall(ls.pack([[est]]), ls.pack([[ref]]), 1, 1).run(psds=False), ev, seg, None, psds=False)
     assert ev[0, 0, 0] == 64
     ref, est = [(1.0, 65536.0)], [(65000.5, 65001.0)]
     ev, seg = se.set_counts([[ref]], [[est]])
-    _check_all(_Raw(ls.pack([[est]]), ls.pack([[ref]]), 1, 1).run(psds=False), ev, seg, None, psds=False)
+    _check_all(ScoreCall(ls.pack([[est]]), ls.pack([[ref]]), 1, 1).run(psds=False), ev, seg, None, psds=False)
     assert seg[0, 0].sum() == 65536
 
 
@@ -417,14 +307,14 @@ def test_malformed_offsets_raise_bit_16_and_stay_inside_the_arrays(which, ptr):
     cols = [[[(float(2 * c + k), 2 * c + k + 0.5) for k in range(2)] for c in range(3)]]     # increasing across columns
     good = ls.pack(cols)
     bad = (np.array(ptr, np.int64), good[1], good[2])
-    raw = _Raw(bad if which == "est" else good, bad if which == "ref" else good, 1, 3)
+    raw = ScoreCall(bad if which == "est" else good, bad if which == "ref" else good, 1, 3)
     got = raw.run()
     assert got["err"] == 16
 
 
 def test_bad_host_arguments_return_before_any_launch():
     cols = [[[(0.0, 1.0)]]]
-    raw = _Raw(ls.pack(cols), ls.pack(cols), 1, 1)
+    raw = ScoreCall(ls.pack(cols), ls.pack(cols), 1, 1)
     raw.fill()
     l, p = raw.l, raw._lib.ptr
     head = list(raw._head())

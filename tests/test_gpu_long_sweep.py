@@ -14,101 +14,17 @@ from tests import long_score_np as ls
 from tests import psds_np
 from tests import sed_eval_np as se
 from tests import stitch_np
+from tests.long_util import (SENT, ScoreCall, StitchCall, _group, _l, _n_windows, _ref_events, _Scaler, _stitch_inputs, _tables,
+                             _tile)
 
 pytestmark = pytest.mark.gpu
 
-SENT = -7
-TAIL = 8
 NUM, DEN = 8.0, 44100 / 511
-
-
-def _l():
-    from dcase2019_task4_amd import _lib
-    return _lib.lib()
-
-
-def _tile():
-    return int(_l().sed_stitch_tile_frames())
-
-
-def _group():
-    return int(_l().sed_stitch_sweep_point_group())
-
-
-def _n_windows(L3, T3, hop3):
-    return 1 if L3 <= T3 else 1 + -(-(L3 - T3) // hop3)
-
-
-def _tables(L3s, T3, hop3):
-    return (np.r_[0, np.cumsum([_n_windows(L, T3, hop3) for L in L3s])].astype(np.int32),
-            np.r_[0, np.cumsum(L3s)].astype(np.int64))
+_Sweep = functools.partial(StitchCall, sweep=True)       # sed_stitch_sweep on sentinel-filled outputs; thr / win are [K, NC]
 
 
 def _lengths():
     return [_tile() + 9, 5, 1500]          # one tile edge, a recording shorter than a halo, a multi-tile recording
-
-
-class _Sweep:
-    """One sed_stitch_sweep call on sentinel-filled outputs (NaN timeline, -7 integers, 0xFF workspace); ``misalign`` shifts
-    the window posteriors and the timeline off 16-byte alignment.  thr / win are [K, NC]."""
-
-    def __init__(self, p, rec_win0, rec_frame0, hop3, weighting, thr, win, capacity=None, misalign=False):
-        from dcase2019_task4_amd import _lib
-        self._lib, self.l = _lib, _lib.lib()
-        p = np.ascontiguousarray(p, dtype=np.float32)
-        self.n_win, self.T3, self.NC = p.shape
-        self.n_rec, self.total = len(rec_win0) - 1, int(rec_frame0[-1])
-        self.hop3, self.weighting = int(hop3), int(weighting)
-        thr, win = np.asarray(thr, np.float32).reshape(-1, self.NC), np.asarray(win, np.int32).reshape(-1, self.NC)
-        self.K = thr.shape[0]
-        off = 1 if misalign else 0
-        self._p = torch.empty(p.size + off, dtype=torch.float32, device="cuda")
-        self.p = self._p[off:]
-        self.p.copy_(torch.from_numpy(p.reshape(-1)))
-        self.rec_win0 = torch.from_numpy(np.asarray(rec_win0, dtype=np.int32)).cuda()
-        self.rec_frame0 = torch.from_numpy(np.asarray(rec_frame0, dtype=np.int64)).cuda()
-        self.thr, self.win = torch.from_numpy(thr).cuda(), torch.from_numpy(win).cuda()
-        L3 = np.diff(np.asarray(rec_frame0, dtype=np.int64))
-        self.capacity = int(self.K * self.NC * ((np.maximum(L3, 0) + 1) // 2).sum()) if capacity is None else int(capacity)
-        self._tl = torch.empty(self.total * self.NC + off, dtype=torch.float32, device="cuda")
-        self.timeline = self._tl[off:]
-        self.ev_ptr = torch.empty(self.K * self.n_rec * self.NC + 1 + TAIL, dtype=torch.int64, device="cuda")
-        self.ev_pairs = torch.empty(self.capacity + TAIL, 2, dtype=torch.int32, device="cuda")
-        self.err = torch.empty(2, dtype=torch.int32, device="cuda")
-        self.ws_bytes = self.l.sed_stitch_sweep_ws_bytes(self.total, self.n_rec, self.NC, self.K)
-        assert self.ws_bytes > 0, self.l.sed_last_error()
-        self.ws = torch.empty(self.ws_bytes + TAIL, dtype=torch.uint8, device="cuda")
-        assert (self.p.data_ptr() % 16 != 0) == bool(misalign)
-
-    def fill(self):
-        self._tl.fill_(float("nan"))
-        self.ev_ptr.fill_(SENT)
-        self.ev_pairs.fill_(SENT)
-        self.ws.fill_(0xFF)
-        self.err.fill_(SENT)
-        self.err[:1].zero_()
-
-    def launch(self, **kw):
-        ptr = self._lib.ptr
-        a = dict(n_points=self.K, thr=self.thr, ws_bytes=self.ws_bytes, timeline=self.timeline)
-        a.update(kw)
-        return self.l.sed_stitch_sweep(ptr(self.p), ptr(self.rec_win0), ptr(self.rec_frame0), self.n_rec, self.T3, self.NC,
-                                       self.hop3, self.weighting, a["n_points"], ptr(a["thr"]), ptr(self.win),
-                                       ptr(a["timeline"]), ptr(self.ev_ptr), ptr(self.ev_pairs), self.capacity, ptr(self.ws),
-                                       a["ws_bytes"], ptr(self.err), self._lib.stream_ptr())
-
-    def run(self):
-        self.fill()
-        assert self.launch() == 0, self.l.sed_last_error()
-        return self.get()
-
-    def get(self):
-        torch.cuda.synchronize()
-        n = self.K * self.n_rec * self.NC + 1
-        ev_ptr = self.ev_ptr.cpu().numpy()
-        assert (ev_ptr[n:] == SENT).all() and int(self.err[1].item()) == SENT and (self.ws[-TAIL:] == 0xFF).all()
-        return {"timeline": self.timeline.cpu().numpy().reshape(self.total, self.NC), "ev_ptr": ev_ptr[:n],
-                "ev_pairs": self.ev_pairs.cpu().numpy(), "err": int(self.err[0].item())}
 
 
 def _np_sweep(timeline, rec_frame0, thr, win):
@@ -238,6 +154,28 @@ def test_sweep_equals_k_calls_of_stitch_decode_byte_for_byte(name, k_case):
     assert out["timeline"].cpu().numpy().tobytes() == np.concatenate(tls).tobytes()
 
 
+@pytest.mark.parametrize("weighting", [0, 1])
+@pytest.mark.parametrize("NC,misalign", [(3, False), (12, False), (12, True)])
+def test_decode_and_one_point_sweep_agree_in_both_load_paths(NC, misalign, weighting):
+    """The two instantiations of the one tile kernel on the same inputs: sed_stitch_decode and sed_stitch_sweep at K = 1, in
+    the scalar path (NC = 3), the 16-byte path (NC = 12) and the scalar path taken by alignment (NC = 12, posteriors and
+    timeline one float off), across a tile edge, a recording shorter than a halo and a multi-tile recording."""
+    T3, hop3 = 8, 3
+    rec_win0, rec_frame0 = _tables(_lengths(), T3, hop3)
+    rs = np.random.RandomState(7000 + 10 * NC + weighting)
+    p = rs.uniform(size=(rec_win0[-1], T3, NC)).astype(np.float32)
+    thr = rs.uniform(0.3, 0.7, size=NC).astype(np.float32)
+    win = rs.choice([1, 5, 63], size=NC).astype(np.int32)
+    one = StitchCall(p, rec_win0, rec_frame0, hop3, weighting, thr, win, misalign=misalign).run()
+    swp = _Sweep(p, rec_win0, rec_frame0, hop3, weighting, thr, win, misalign=misalign).run()
+    assert one["err"] == 0 and swp["err"] == 0
+    n = int(one["ev_ptr"][-1])
+    assert n > 0 and not np.isnan(one["timeline"]).any()
+    assert one["timeline"].tobytes() == swp["timeline"].tobytes()
+    assert one["ev_ptr"].tobytes() == swp["ev_ptr"].tobytes()
+    assert one["ev_pairs"][:n].tobytes() == swp["ev_pairs"][:n].tobytes()
+
+
 # ---- 3. decoder errors ------------------------------------------------------------------------------------------------------------------
 def _alternating_sweep(K=3, **kw):
     T3, NC = 8, 3
@@ -319,84 +257,6 @@ def test_bad_host_arguments_return_bad_arg_before_any_launch():
 
 
 # ---- 4. / 5. the scorers, given events -----------------------------------------------------------------------------------------------------
-class _RawSweep:
-    """The two sweep C calls on sentinel-filled outputs with a tail of TAIL elements.  ``ests``: K tuples (ptr, on, off) in
-    seconds, concatenated here into one CSR in column order (k, rec, c); ``ref`` = (ptr, on, off)."""
-
-    def __init__(self, ests, ref, n_rec, NC):
-        from dcase2019_task4_amd import _lib
-        self._lib, self.l = _lib, _lib.lib()
-        self.n_rec, self.NC, self.K = n_rec, NC, len(ests)
-        dev = "cuda"
-        base = np.r_[0, np.cumsum([len(e[1]) for e in ests])]
-        ptr = np.concatenate([np.asarray(e[0], np.int64)[:-1] + base[k] for k, e in enumerate(ests)] + [base[-1:]])
-        self.est_ptr = torch.from_numpy(ptr.astype(np.int64)).to(dev)
-        self.on = torch.from_numpy(np.r_[np.concatenate([np.asarray(e[1], np.float64) for e in ests]), 0.0]).to(dev)
-        self.off = torch.from_numpy(np.r_[np.concatenate([np.asarray(e[2], np.float64) for e in ests]), 0.0]).to(dev)
-        self.est_cap = int(base[-1])
-        self.ref_ptr = torch.from_numpy(np.asarray(ref[0], np.int64)).to(dev)
-        self.ref_on = torch.from_numpy(np.r_[np.asarray(ref[1], np.float64), 0.0]).to(dev)
-        self.ref_off = torch.from_numpy(np.r_[np.asarray(ref[2], np.float64), 0.0]).to(dev)
-        self.ref_cap = len(ref[1])
-        K, ncols, W = self.K, n_rec * NC, 2 + NC
-        mk = lambda n, dt: torch.empty(n + TAIL, dtype=dt, device=dev)
-        self.ev_c, self.seg_c, self.ps_c = mk(K * ncols * 3, torch.int32), mk(K * ncols * 4, torch.int32), mk(K * ncols * W, torch.int32)
-        self.ev_t, self.seg_t, self.ps_t = mk(K * NC * 3, torch.int64), mk(K * NC * 4, torch.int64), mk(K * NC * W, torch.int64)
-        self.err = torch.empty(2, dtype=torch.int32, device=dev)
-        nbytes = self.l.sed_long_sweep_ws_bytes(self.est_cap, self.ref_cap, n_rec, NC, K)
-        assert nbytes > 0, self.l.sed_last_error()
-        self.ws = torch.empty(nbytes + TAIL, dtype=torch.uint8, device=dev)
-
-    def fill(self):
-        K, NC, W = self.K, self.NC, 2 + self.NC
-        for t in (self.ev_c, self.seg_c, self.ps_c):
-            t.fill_(SENT)
-        for t, n in ((self.ev_t, K * NC * 3), (self.seg_t, K * NC * 4), (self.ps_t, K * NC * W)):
-            t.fill_(SENT)
-            t[:n].zero_()
-        self.err.fill_(SENT)
-        self.err[:1].zero_()
-        self.ws.fill_(0xFF)
-
-    def _head(self):
-        p = self._lib.ptr
-        return (p(self.est_ptr), None, 0.0, 0.0, p(self.on), p(self.off), self.est_cap, p(self.ref_ptr), p(self.ref_on),
-                p(self.ref_off), self.ref_cap, self.n_rec, self.NC, self.K)
-
-    def launch_events(self):
-        p = self._lib.ptr
-        return self.l.sed_long_sweep_event_counts(*self._head(), 0.2, 0.2, 1.0, p(self.ev_c), p(self.seg_c), p(self.ev_t),
-                                                  p(self.seg_t), p(self.err), p(self.ws), self.ws.numel() - TAIL,
-                                                  self._lib.stream_ptr())
-
-    def launch_psds(self):
-        p = self._lib.ptr
-        return self.l.sed_long_sweep_psds_counts(*self._head(), 0.5, 0.5, 0.3, p(self.ps_c), p(self.ps_t), p(self.err),
-                                                 p(self.ws), self.ws.numel() - TAIL, self._lib.stream_ptr())
-
-    def get(self):
-        torch.cuda.synchronize()
-        K, n_rec, NC, W = self.K, self.n_rec, self.NC, 2 + self.NC
-        ncols, out = n_rec * NC, {}
-        for name, t, n, shape in (("ev", self.ev_c, K * ncols * 3, (K, n_rec, NC, 3)), ("seg", self.seg_c, K * ncols * 4, (K, n_rec, NC, 4)),
-                                  ("ps", self.ps_c, K * ncols * W, (K, n_rec, NC, W)), ("ev_t", self.ev_t, K * NC * 3, (K, NC, 3)),
-                                  ("seg_t", self.seg_t, K * NC * 4, (K, NC, 4)), ("ps_t", self.ps_t, K * NC * W, (K, NC, W))):
-            h = t.cpu().numpy()
-            assert (h[n:] == SENT).all(), name
-            out[name] = h[:n].reshape(shape)
-        assert int(self.err[1].item()) == SENT and (self.ws[-TAIL:] == 0xFF).all()
-        out["err"] = int(self.err[0].item())
-        return out
-
-    def run(self, events=True, psds=True):
-        self.fill()
-        if events:
-            assert self.launch_events() == 0, self.l.sed_last_error()
-        if psds:
-            assert self.launch_psds() == 0, self.l.sed_last_error()
-        return self.get()
-
-
 def _one_point(est, ref, n_rec, NC):
     """The one-point C calls on the same events: (ev, seg, ps, ev_t, seg_t, ps_t) as numpy."""
     from dcase2019_task4_amd import _lib
@@ -440,7 +300,7 @@ def _score_case(name):
 def test_sweep_scorers_are_exact_per_point_and_equal_one_point_calls(name):
     ref, ests, want = _score_case(name)
     n_rec, NC = len(ref), len(ref[0])
-    raw = _RawSweep([ls.pack(e) for e in ests], ls.pack(ref), n_rec, NC)
+    raw = ScoreCall([ls.pack(e) for e in ests], ls.pack(ref), n_rec, NC)
     a = raw.run()
     assert a["err"] == 0
     for k, (ev, seg, ps) in enumerate(want):
@@ -504,7 +364,7 @@ def test_an_oversized_cluster_in_one_point_leaves_the_other_points_scored(side):
         ref_cols = [[ok_ref, INSIDE]]
         ests = [[[ok_est, ONE]], [[ok_est2, ONE]], [[ok_est, ONE]]]
     assert [ls.expected_err(ref_cols, e) for e in ests] == ([0, 2, 0] if side == "est" else [1, 1, 1])
-    got = _RawSweep([ls.pack(e) for e in ests], ls.pack(ref_cols), 1, 2).run(psds=False)
+    got = ScoreCall([ls.pack(e) for e in ests], ls.pack(ref_cols), 1, 2).run(psds=False)
     assert got["err"] == (2 if side == "est" else 1)
     for k, est in enumerate(ests):
         ev, seg = se.set_counts([[ok_ref]], [[est[0][0]]])
@@ -515,7 +375,7 @@ def test_an_oversized_cluster_in_one_point_leaves_the_other_points_scored(side):
             np.testing.assert_array_equal(got["seg"][k], seg)
         else:                                                                  # not scored, not truncated
             assert tuple(got["ev"][k, 0, 1]) == (0, len(ref_cols[0][1]), len(est[0][1])) and (got["seg"][k, 0, 1] == 0).all()
-    ps = _RawSweep([ls.pack(e) for e in ests], ls.pack(ref_cols), 1, 2).run(events=False)
+    ps = ScoreCall([ls.pack(e) for e in ests], ls.pack(ref_cols), 1, 2).run(events=False)
     assert ps["err"] == 0                                                      # no matching in PSDS
     for k, est in enumerate(ests):
         np.testing.assert_array_equal(ps["ps"][k], np.array(psds_np.set_counts(ref_cols, est)))
@@ -523,7 +383,7 @@ def test_an_oversized_cluster_in_one_point_leaves_the_other_points_scored(side):
 
 def test_scorer_bad_host_arguments_return_before_any_launch():
     cols = [[[(0.0, 1.0)]]]
-    raw = _RawSweep([ls.pack(cols)] * 2, ls.pack(cols), 1, 1)
+    raw = ScoreCall([ls.pack(cols)] * 2, ls.pack(cols), 1, 1)
     raw.fill()
     l, p = raw.l, raw._lib.ptr
     head = list(raw._head())
@@ -539,24 +399,6 @@ def test_scorer_bad_host_arguments_return_before_any_launch():
 
 
 # ---- 6. pipeline and graph -------------------------------------------------------------------------------------------------------------------
-def _stitch_inputs():
-    """Window posteriors whose timeline is a prescribed 0.9 / 0.1 pattern (hop3 = T3), three recordings, three classes."""
-    T3, NC = 8, 3
-    L3s = ls.stitch_lengths(_tile())
-    patterns = ls.stitch_patterns(L3s, NC)
-    tls = [np.where(a, np.float32(0.9), np.float32(0.1)) for a in patterns]
-    n_w = [-(-L // T3) for L in L3s]
-    p = np.concatenate([np.concatenate([t, np.full((-len(t) % T3, NC), 0.1, np.float32)]).reshape(-1, T3, NC) for t in tls])
-    return (torch.from_numpy(p).cuda(), torch.from_numpy(np.r_[0, np.cumsum(n_w)].astype(np.int32)).cuda(),
-            torch.from_numpy(np.r_[0, np.cumsum(L3s)].astype(np.int64)).cuda(), L3s, T3, NC, patterns)
-
-
-def _ref_events(cols):
-    from dcase2019_task4_amd.metrics import RefEvents
-    ptr, on, off = ls.pack(cols)
-    return RefEvents(ptr, on, off, [f"r{i}" for i in range(len(cols))], [f"c{i}" for i in range(len(cols[0]))])
-
-
 def test_sweep_pipeline_equals_the_oracle_and_replays_in_one_graph():
     from dcase2019_task4_amd import metrics as M
     from dcase2019_task4_amd.inference import stitch_sweep
@@ -615,13 +457,6 @@ def test_sweep_pipeline_equals_the_oracle_and_replays_in_one_graph():
 
 
 # ---- 7. validate_long ---------------------------------------------------------------------------------------------------------------------------
-class _Scaler:
-    def __init__(self, n_mels):
-        rs = np.random.RandomState(11)
-        self.mean_ = rs.uniform(-30, -10, n_mels)
-        self.std_ = rs.uniform(5, 15, n_mels)
-
-
 def test_validate_long_one_blend_equals_the_loop_and_the_oracle():
     from dcase2019_task4_amd import _lib
     from dcase2019_task4_amd import metrics as M
