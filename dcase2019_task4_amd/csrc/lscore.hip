@@ -13,8 +13,8 @@
 //                  the only pass that walks a column in sequence
 //   k_ls_match     one wave per tile of LS_TILE reference events.  "i starts a cluster" is a local test (two bisections in
 //                  the estimated onsets), so a wave finds the clusters that START in its tile with one ballot, their ends with
-//                  a second ballot over the next tile (further ones only on the error path), and solves each with the augmenting-path ballot search of
-//                  k_event_counts (score.hip; a second copy of that loop: the two have different operand sources)
+//                  a second ballot over the next tile (further ones only on the error path), and solves each with sc_max_matching
+//                  (score.h: the augmenting-path ballot search k_event_counts runs; only the source of the masks differs)
 //   k_ls_segments  one thread per segment: segment s is covered iff the last event whose first segment is <= s has
 //                  seg(pmax) > s - two bisections, no bitmap, no events x segments loop
 //   k_lp_detect    one thread per detection: DTC and, for the non-relevant ones, CTTC against every other class
@@ -27,11 +27,10 @@
 #pragma clang fp contract(off)       // seconds are formed as (double)frame * num / den, exactly the host's two operations
 #include "common.h"
 #include "kernels.h"
+#include "score.h"
 
 #define LS_TILE 64                   // reference events per wave of k_ls_match: one lane / one mask bit each
-#define LS_MAXEV 64                  // events per cluster and side
-#define LS_MAXSEG 65536              // segments per file
-#define LS_MAXNC 16
+static_assert(LS_TILE == SC_MAXEV, "a tile of references is one adjacency mask's worth of lanes");
 #define LS_CW 20                     // int32 counters per column: [0] Ntp, [1..3] segment tp / fp / fn, [4] k_ls_match's err bits; PSDS: [0 .. 2 + NC)
 #define LS_PREP_THREADS 1024
 #define LS_SEG_SPLIT 16              // workgroups of 256 segments per column and step
@@ -55,13 +54,6 @@ struct LsArgs {
     int32_t* err;
 };
 
-__device__ __forceinline__ int ls_lane_read(int v, int src) {
-    return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(src));
-}
-// segment index of a time, clamped to [0, LS_MAXSEG + 1] (NaN -> 0) so that the cast is defined
-__device__ __forceinline__ int ls_seg_index(double x) {
-    return !(x > 0.0) ? 0 : (x > (double)LS_MAXSEG ? LS_MAXSEG + 1 : (int)x);
-}
 // validated range of a column: false (and an empty range) when the offsets are malformed
 __device__ __forceinline__ bool ls_range(const int64_t* ptr, long long col, long long cap, long long& p0, int& n) {
     const long long a = ptr[col], b = ptr[col + 1];
@@ -84,7 +76,7 @@ __global__ __launch_bounds__(LS_PREP_THREADS) void k_ls_prep(LsArgs a) {
     const bool frames = side == 0 && a.ev_pairs != nullptr;
     long long p0;
     int n, flags = 0;
-    if (!ls_range(side ? a.ref_ptr : a.est_ptr, col, side ? a.ref_cap : a.est_cap, p0, n)) flags = 16;
+    if (!ls_range(side ? a.ref_ptr : a.est_ptr, col, side ? a.ref_cap : a.est_cap, p0, n)) flags = SC_ERR_OFFSETS;
     const double* src_on = side ? a.ref_on : a.est_on;
     const double* src_off = side ? a.ref_off : a.est_off;
     double* pmax = side ? a.ref_pmax : a.est_pmax;
@@ -130,7 +122,7 @@ __global__ __launch_bounds__(LS_PREP_THREADS) void k_ls_prep(LsArgs a) {
         if (tid == LS_PREP_THREADS - 1) s_carry = v;
         __syncthreads();
     }
-    if (__syncthreads_or(unsorted)) flags |= 64;
+    if (__syncthreads_or(unsorted)) flags |= SC_ERR_UNSORTED;
     if (tid == 0) {
         (side ? a.rflags : a.flags)[col] = flags;
         if (flags) atomicOr(a.err, flags);
@@ -216,11 +208,11 @@ __global__ __launch_bounds__(256) void k_ls_match(LsArgs a) {
         if (later) {
             const int t = __ffsll((long long)later) - 1;
             nr = t - s;
-            j1 = ls_lane_read(jlo[0], t);
+            j1 = sc_lane_read(jlo[0], t);
         } else if (starts[1]) {
             const int t = __ffsll((long long)starts[1]) - 1;
             nr = 64 + t - s;
-            j1 = ls_lane_read(jlo[1], t);
+            j1 = sc_lane_read(jlo[1], t);
         } else {                               // more than 64 references (bit 1): walk on to the cluster's end for bit 2
             nr = 0;
             j1 = 0;
@@ -232,15 +224,15 @@ __global__ __launch_bounds__(256) void k_ls_match(LsArgs a) {
                 if (m) {
                     const int t = __ffsll((long long)m) - 1;
                     nr = base + t - (i_base + s);
-                    j1 = ls_lane_read(jl, t);
+                    j1 = sc_lane_read(jl, t);
                 }
             }
         }
-        const int j0 = ls_lane_read(jhi[0], s);
+        const int j0 = sc_lane_read(jhi[0], s);
         const int ne = j1 - j0;
-        if (nr > LS_MAXEV) flags |= 1;
-        if (ne > LS_MAXEV) flags |= 2;
-        if (nr > LS_MAXEV || ne > LS_MAXEV || ne <= 0) continue;
+        if (nr > SC_MAXEV) flags |= SC_ERR_MANY_REF;
+        if (ne > SC_MAXEV) flags |= SC_ERR_MANY_EST;
+        if (nr > SC_MAXEV || ne > SC_MAXEV || ne <= 0) continue;
         // ---- the cluster: lane r holds reference i0 + r and the mask of the estimated events compatible with it ----------
         const int i0 = i_base + s;
         const bool has_ref = lane < nr;
@@ -249,42 +241,13 @@ __global__ __launch_bounds__(256) void k_ls_match(LsArgs a) {
             r_on = R[i0 + lane];
             r_off = Roff[i0 + lane];
         }
-        const double tol_off = fmax(tc, a.pct * (r_off - r_on));
+        const double tol_off = sc_offset_tolerance(r_on, r_off, tc, a.pct);
         unsigned long long adj = 0;
         for (int e = 0; e < ne; ++e) {
-            const double eo = E[j0 + e], ef = Eoff[j0 + e];
-            const bool hit = has_ref && fabs(r_on - eo) <= tc && fabs(r_off - ef) <= tol_off;
+            const bool hit = has_ref && sc_compatible(r_on, r_off, tol_off, E, Eoff, j0 + e, tc);
             adj |= (unsigned long long)hit << e;
         }
-        int m_est = -1;                        // lane e: the reference matched to estimated event e
-        int parent = 0;                        // lane r: the estimated event that reached reference r in this search
-        unsigned long long matched_ref = 0;
-        for (int root = 0; root < ne; ++root) {
-            unsigned long long frontier = 1ull << root, visited = 0;
-            while (frontier) {
-                const unsigned long long reach = adj & frontier;
-                const bool fresh = reach != 0 && !((visited >> lane) & 1);
-                const unsigned long long new_ref = __ballot(fresh);
-                if (!new_ref) break;
-                if (fresh) parent = __ffsll((long long)reach) - 1;
-                const unsigned long long free_new = new_ref & ~matched_ref;
-                if (free_new) {                // an unmatched reference: flip the path back to the root
-                    int r = __ffsll((long long)free_new) - 1;
-                    matched_ref |= 1ull << r;
-                    for (int hop = 0; hop < LS_MAXEV; ++hop) {
-                        const int e = ls_lane_read(parent, r);
-                        const int prev = ls_lane_read(m_est, e);
-                        if (lane == e) m_est = r;
-                        if (prev < 0) break;
-                        r = prev;
-                    }
-                    ++ntp;
-                    break;
-                }
-                visited |= new_ref;
-                frontier = __ballot(m_est >= 0 && ((new_ref >> (m_est & 63)) & 1));
-            }
-        }
+        ntp += sc_max_matching(adj, ne, lane);
     }
     if (lane == 0) {
         if (ntp > 0) atomicAdd(a.cnt + col * LS_CW, ntp);
@@ -300,9 +263,9 @@ __global__ __launch_bounds__(256) void k_ls_match(LsArgs a) {
 __device__ __forceinline__ int ls_col_segments(const LsArgs& a, long long col) {
     long long p0;
     int n, seg = 0;
-    if (ls_range(a.est_ptr, col, a.est_cap, p0, n) && n > 0) seg = ls_seg_index(ceil(a.est_pmax[p0 + n - 1] / a.res));
+    if (ls_range(a.est_ptr, col, a.est_cap, p0, n) && n > 0) seg = sc_seg_index(ceil(a.est_pmax[p0 + n - 1] / a.res));
     if (ls_range(a.ref_ptr, ls_rcol(a, col), a.ref_cap, p0, n) && n > 0)
-        seg = max(seg, ls_seg_index(ceil(a.ref_pmax[p0 + n - 1] / a.res)));
+        seg = max(seg, sc_seg_index(ceil(a.ref_pmax[p0 + n - 1] / a.res)));
     return seg;
 }
 __device__ __forceinline__ int ls_file_segments(const LsArgs& a, long long rec) {
@@ -315,18 +278,18 @@ __device__ __forceinline__ bool ls_covered(const double* on, const double* pmax,
     int lo = 0, hi = n;
     while (lo < hi) {                                                // the number of events whose first segment is <= s
         const int mid = (lo + hi) >> 1;
-        if (ls_seg_index(floor(on[mid] / res)) <= s) lo = mid + 1;
+        if (sc_seg_index(floor(on[mid] / res)) <= s) lo = mid + 1;
         else hi = mid;
     }
-    return lo > 0 && ls_seg_index(ceil(pmax[lo - 1] / res)) > s;
+    return lo > 0 && sc_seg_index(ceil(pmax[lo - 1] / res)) > s;
 }
 
 __global__ __launch_bounds__(256) void k_ls_segments(LsArgs a) {
     const long long col = blockIdx.x;
     const int lane = threadIdx.x & 63;
     const int file_seg = ls_file_segments(a, col / a.NC);
-    if (file_seg > LS_MAXSEG) {
-        if (blockIdx.y == 0 && threadIdx.x == 0) atomicOr(a.err, 4);
+    if (file_seg > SC_MAXSEG) {
+        if (blockIdx.y == 0 && threadIdx.x == 0) atomicOr(a.err, SC_ERR_SEGMENTS);
         return;
     }
     if (ls_col_flags(a, col)) return;
@@ -360,7 +323,7 @@ __global__ __launch_bounds__(256) void k_ls_final(LsArgs a) {
     const int c = (int)(col % a.NC) + (int)(col / ncols) * a.NC;     // the row of the totals: (point, class)
     const int32_t* k = a.cnt + col * LS_CW;
     const int file_seg = ls_file_segments(a, col / a.NC);
-    const bool ok = (ls_col_flags(a, col) | k[4]) == 0 && file_seg <= LS_MAXSEG;
+    const bool ok = (ls_col_flags(a, col) | k[4]) == 0 && file_seg <= SC_MAXSEG;
     long long p0;
     int n_ref, n_est;
     ls_range(a.ref_ptr, ls_rcol(a, col), a.ref_cap, p0, n_ref);
@@ -384,12 +347,6 @@ __global__ __launch_bounds__(256) void k_ls_final(LsArgs a) {
 }
 
 // ---- PSDS -------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double lp_overlap(double a_on, double a_off, double b_on, double b_off) {
-    return fmax(0.0, fmin(a_off, b_off) - fmax(a_on, b_on));
-}
-__device__ __forceinline__ bool lp_passes(double sum, double len, double threshold) {
-    return len > 0.0 && sum / len >= threshold;
-}
 // the events x[lo .. hi) that can overlap (q_on, q_off): those before lo end at or before q_on, those from hi on start at or
 // after q_off - every term left out is +0.0
 __device__ __forceinline__ void lp_window(const double* on, const double* pmax, int n, double q_on, double q_off, int& lo,
@@ -408,6 +365,16 @@ __device__ __forceinline__ void lp_window(const double* on, const double* pmax, 
         else l = mid + 1;
     }
     lo = l;
+}
+// sum of I(d, g) over the ground truths g of reference column rcol: sequential over the window in stored order, from 0.0
+__device__ __forceinline__ double lp_ref_sum(const LsArgs& a, long long rcol, double d_on, double d_off) {
+    long long pr;
+    int n_ref, lo, hi;
+    ls_range(a.ref_ptr, rcol, a.ref_cap, pr, n_ref);
+    lp_window(a.ref_on + pr, a.ref_pmax + pr, n_ref, d_on, d_off, lo, hi);
+    double sum = 0.0;
+    for (int g = lo; g < hi; ++g) sum += sc_overlap(d_on, d_off, a.ref_on[pr + g], a.ref_off[pr + g]);
+    return sum;
 }
 // the column of event i of a CSR table of ncols columns (the last column whose offset is <= i); -1 when i is outside it
 __device__ __forceinline__ long long lp_column(const int64_t* ptr, long long ncols, long long cap, long long i, long long& p0,
@@ -433,8 +400,8 @@ __device__ __forceinline__ void lp_count(const LsArgs& a, long long col, bool un
 
 __global__ __launch_bounds__(256) void k_lp_detect(LsArgs a) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    long long pe = 0, pr;
-    int n_est = 0, n_ref;
+    long long pe = 0;
+    int n_est = 0;
     const long long ncols = (long long)a.n_rec * a.NC;
     long long col = i < a.est_cap ? lp_column(a.est_ptr, ncols * a.K, a.est_cap, i, pe, n_est) : -1;
     if (col >= 0 && ls_col_flags(a, col)) col = -1;                  // not scored (k_ls_prep reported it)
@@ -447,12 +414,7 @@ __global__ __launch_bounds__(256) void k_lp_detect(LsArgs a) {
     if (active) {
         d_on = a.est_on[i];
         d_off = a.est_off[i];
-        ls_range(a.ref_ptr, rcol, a.ref_cap, pr, n_ref);
-        int lo, hi;
-        lp_window(a.ref_on + pr, a.ref_pmax + pr, n_ref, d_on, d_off, lo, hi);
-        double sum = 0.0;
-        for (int g = lo; g < hi; ++g) sum += lp_overlap(d_on, d_off, a.ref_on[pr + g], a.ref_off[pr + g]);
-        relevant = lp_passes(sum, d_off - d_on, a.dtc);
+        relevant = sc_passes(lp_ref_sum(a, rcol, d_on, d_off), d_off - d_on, a.dtc);
         a.rel[i] = relevant ? 1 : 0;
     }
     const bool cross = active && !relevant;
@@ -462,14 +424,8 @@ __global__ __launch_bounds__(256) void k_lp_detect(LsArgs a) {
         bool ct = false;
         if (cross && j != c) {
             const long long cj = rcol - c + j;
-            if (a.rflags[cj] == 0) {                          // (a malformed or unsorted reference column raised err)
-                ls_range(a.ref_ptr, cj, a.ref_cap, pr, n_ref);
-                int lo, hi;
-                lp_window(a.ref_on + pr, a.ref_pmax + pr, n_ref, d_on, d_off, lo, hi);
-                double sum = 0.0;
-                for (int g = lo; g < hi; ++g) sum += lp_overlap(d_on, d_off, a.ref_on[pr + g], a.ref_off[pr + g]);
-                ct = lp_passes(sum, d_off - d_on, a.cttc);
-            }
+            // (a malformed or unsorted reference column raised err)
+            if (a.rflags[cj] == 0) ct = sc_passes(lp_ref_sum(a, cj, d_on, d_off), d_off - d_on, a.cttc);
         }
         lp_count(a, col, uniform, 2 + j, ct);
     }
@@ -494,8 +450,8 @@ __global__ __launch_bounds__(256) void k_lp_truth(LsArgs a) {
         lp_window(a.est_on + pe, a.est_pmax + pe, n_est, g_on, g_off, lo, hi);
         double sum = 0.0;
         for (int e = lo; e < hi; ++e)
-            if (a.rel[pe + e]) sum += lp_overlap(a.est_on[pe + e], a.est_off[pe + e], g_on, g_off);
-        found = lp_passes(sum, g_off - g_on, a.gtc);
+            if (a.rel[pe + e]) sum += sc_overlap(a.est_on[pe + e], a.est_off[pe + e], g_on, g_off);
+        found = sc_passes(sum, g_off - g_on, a.gtc);
     }
     lp_count(a, col, uniform, 0, found);
 }
@@ -539,7 +495,7 @@ static const char* const LS_NEED = "need 0 <= est_capacity, ref_events < 2^31 - 
                                    "1 <= n_points <= 4096, n_points * n_rec * nclass < 2^26, n_points * reference tiles < 2^31";
 static bool ls_sizes_ok(long long est_cap, long long ref_cap, int n_rec, int nclass, int K) {
     return est_cap >= 0 && ref_cap >= 0 && est_cap < (1ll << 31) - 1024 && ref_cap < (1ll << 31) - 1024 && n_rec >= 1 &&
-           nclass >= 1 && nclass <= LS_MAXNC && K >= 1 && K <= LS_MAXK && (long long)K * n_rec * nclass < (1ll << 26) &&
+           nclass >= 1 && nclass <= SC_MAXNC && K >= 1 && K <= LS_MAXK && (long long)K * n_rec * nclass < (1ll << 26) &&
            (ref_cap / LS_TILE + (long long)n_rec * nclass + 1) * K < (1ll << 31);
 }
 

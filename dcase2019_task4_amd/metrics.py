@@ -149,38 +149,66 @@ class RefEvents:
         return len(self.labels)
 
 
-def _totals_to_host(counts):
-    """The buffer of a ``Counts`` / ``PSDSCounts`` without its error word - one device -> host copy; raises when the word is set."""
-    h = counts.buf.cpu().numpy()
-    err = int(h[-1:].view(np.int32)[0])
-    if err:
-        raise _lib.SedError(counts.err_what + ": " + "; ".join(m for b, m in counts.err_bits.items() if err & b)
-                            + " - nothing was truncated, the counts are invalid")
-    return h[:-1]
+class _DeviceCounts:
+    """What ``Counts`` and ``PSDSCounts`` share: ``buf`` - int64 class totals of ``width`` values per (operating point,
+    class) and, last, the error word ``err`` - in ONE device buffer, so that ``host()`` is one copy."""
+
+    def __init__(self, n_points, nclass, width, device, err_what):
+        self.K, self.NC = n_points, nclass
+        self.buf = torch.zeros(n_points * nclass * width + 1, dtype=torch.int64, device=device)
+        self.err = self.buf[-1:].view(torch.int32)
+        self.err_what, self.err_bits = err_what, _ERR_BITS                    # (the long calls put their own wording here)
+
+    def _totals_to_host(self):
+        """The buffer without its error word - one device -> host copy; raises when the word is set."""
+        h = self.buf.cpu().numpy()
+        err = int(h[-1:].view(np.int32)[0])
+        if err:
+            raise _lib.SedError(self.err_what + ": " + "; ".join(m for b, m in self.err_bits.items() if err & b)
+                                + " - nothing was truncated, the counts are invalid")
+        return h[:-1]
+
+    def check(self):
+        return self.host()
 
 
-class Counts:
+class Counts(_DeviceCounts):
     """Class totals of one or more ``event_counts`` calls, on the device: ``ev [K, nclass, 3]`` (Ntp, Nref, Nsys) and
     ``seg [K, nclass, 4]`` (Ntp, Nfp, Nfn, Ntn) int64, and the error word, all in ONE buffer so that ``host()`` is one copy.
     ``ev_columns [K, N, nclass, 3]`` / ``seg_columns [K, N, nclass, 4]`` int32 hold the last call's per-column counts when it
     was asked for them."""
 
     def __init__(self, n_points, nclass, device):
-        self.K, self.NC = n_points, nclass
-        self.buf = torch.zeros(n_points * nclass * 7 + 1, dtype=torch.int64, device=device)
+        _DeviceCounts.__init__(self, n_points, nclass, 7, device, "sed_event_counts")
         n3 = n_points * nclass * 3
         self.ev = self.buf[:n3].view(n_points, nclass, 3)
         self.seg = self.buf[n3:-1].view(n_points, nclass, 4)
-        self.err = self.buf[-1:].view(torch.int32)
         self.ev_columns = self.seg_columns = None
-        self.err_what, self.err_bits = "sed_event_counts", _ERR_BITS          # (the long calls put their own wording here)
 
     def host(self):
         """(ev, seg) as numpy arrays - one device -> host copy; raises when a column was over a limit."""
-        h, n3 = _totals_to_host(self), self.K * self.NC * 3
+        h, n3 = self._totals_to_host(), self.K * self.NC * 3
         return h[:n3].reshape(self.K, self.NC, 3), h[n3:].reshape(self.K, self.NC, 4)
 
-    check = host
+
+class PSDSCounts(_DeviceCounts):
+    """Class totals of one or more ``psds_counts`` calls, on the device: ``totals [K, nclass, 2 + nclass]`` int64 - per class
+    (TP, FP, CT[.][0 .. nclass - 1]) - and the error word, in ONE buffer so that ``host()`` is one copy.  ``columns
+    [K, N, nclass, 2 + nclass]`` int32 holds the last call's per-column counts when it was asked for them.  The criteria
+    ``dtc / gtc / cttc`` belong to the totals: every call that accumulates into them uses these."""
+
+    def __init__(self, n_points, nclass, device, dtc=0.5, gtc=0.5, cttc=0.3):
+        for name, v in (("dtc", dtc), ("gtc", gtc), ("cttc", cttc)):
+            if not 0.0 <= v <= 1.0:                     # (NaN fails too)
+                raise ValueError(f"{name} must be in [0, 1], got {v}")
+        _DeviceCounts.__init__(self, n_points, nclass, 2 + nclass, device, "sed_psds_counts")
+        self.dtc, self.gtc, self.cttc = float(dtc), float(gtc), float(cttc)
+        self.totals = self.buf[:-1].view(n_points, nclass, 2 + nclass)
+        self.columns = None
+
+    def host(self):
+        """``totals`` as a numpy array - one device -> host copy; raises when a column was over a limit."""
+        return self._totals_to_host().reshape(self.K, self.NC, 2 + self.NC)
 
 
 def operating_points(thresholds=(0.5,), median_windows=(5,), device="cuda"):
@@ -199,14 +227,14 @@ def operating_points(thresholds=(0.5,), median_windows=(5,), device="cuda"):
     return torch.as_tensor(thr).to(device), torch.as_tensor(win).to(device)
 
 
-def event_counts(strong, ref, thresholds=(0.5,), median_windows=(5,), pooling_time_ratio=1, cfg=None, t_collar=0.200,
-                 percentage_of_length=0.2, time_resolution=1.0, clip_offset=0, counts=None, per_column=False):
-    """``strong [n, T, nclass]`` cuda float32 posteriors of clips ``clip_offset .. clip_offset + n - 1`` of ``ref`` -> ``Counts``
-    (device tensors, no synchronisation; pass ``counts`` to accumulate batches).  ``thresholds`` / ``median_windows``: see
-    ``operating_points`` (device tensors are taken as they are).  ``cfg`` supplies sample_rate / hop_length (default
-    baseline/config.py): seconds = frame * pooling_time_ratio / (sample_rate / hop_length), evaluation_measures.py:226-227."""
+# ---- clips: posteriors of a batch (or given events) against the RefEvents of the same clips -----------------------------------
+# One helper family serves ``sed_event_counts`` and ``sed_psds_counts``, whose leading arguments - the estimated side, then the
+# reference side - are the same.  ``est`` = (those arguments: strong, n, T, NC, K, thr, win, num, den, est_ptr, est_on, est_off,
+# ref_ptr, ref_on, ref_off; n; K; NC; the device; the tensors behind the pointers that only this tuple keeps alive until the
+# launch).
+def _posterior_args(strong, ref, thresholds, median_windows, pooling_time_ratio, cfg, clip_offset, what):
     if strong.device.type != "cuda" or ref.device.type != "cuda":
-        raise _lib.SedError("event_counts needs GPU tensors and a RefEvents on the GPU (no CPU fallback)")
+        raise _lib.SedError(f"{what} needs GPU tensors and a RefEvents on the GPU (no CPU fallback)")
     cfg = cfg or _Cfg
     strong = strong.contiguous().float()
     n, T, NC = strong.shape
@@ -214,70 +242,42 @@ def event_counts(strong, ref, thresholds=(0.5,), median_windows=(5,), pooling_ti
         raise ValueError(f"posteriors [{n}, {T}, {NC}] at clip {clip_offset} do not fit the reference ({len(ref)} clips, "
                          f"{ref.nclass} classes)")
     thr, win = operating_points(thresholds, median_windows, strong.device)
-    K = thr.numel()
+    K, p = thr.numel(), _lib.ptr
+    # (the offsets of clip clip_offset by address: a view of ref.ptr per batch costs more host time than the rest of this call)
+    ref_ptr = _lib.C.c_void_p(ref.ptr.data_ptr() + clip_offset * NC * ref.ptr.element_size())
+    args = (p(strong), n, T, NC, K, p(thr), p(win), float(pooling_time_ratio), float(cfg.sample_rate / cfg.hop_length),
+            None, None, None, ref_ptr, p(ref.onset), p(ref.offset))
+    return args, n, K, NC, strong.device, (strong, thr, win)
+
+
+def _given_args(est, ref, what):
+    if est.device.type != "cuda" or ref.device.type != "cuda":
+        raise _lib.SedError(f"{what} needs both event sets on the GPU (no CPU fallback)")
+    if est.filenames != ref.filenames or est.labels != ref.labels:
+        raise ValueError("estimated and reference events must cover the same files and classes, in the same order")
+    n, NC, p = len(ref), ref.nclass, _lib.ptr
+    return (None, n, 0, NC, 1, None, None, 0.0, 0.0, p(est.ptr), p(est.onset), p(est.offset), p(ref.ptr), p(ref.onset),
+            p(ref.offset)), n, 1, NC, ref.device, ()
+
+
+def _event_target(est, t_collar, percentage_of_length, time_resolution, counts, per_column):
+    args, n, K, NC, device, _ = est
     if counts is None:
-        counts = Counts(K, NC, strong.device)
+        counts = Counts(K, NC, device)
     if (counts.K, counts.NC) != (K, NC):
         raise ValueError("counts was built for another number of operating points / classes")
     if per_column:
-        counts.ev_columns = torch.empty(K, n, NC, 3, dtype=torch.int32, device=strong.device)
-        counts.seg_columns = torch.empty(K, n, NC, 4, dtype=torch.int32, device=strong.device)
+        counts.ev_columns = torch.empty(K, n, NC, 3, dtype=torch.int32, device=device)
+        counts.seg_columns = torch.empty(K, n, NC, 4, dtype=torch.int32, device=device)
     _lib.check(_lib.lib().sed_event_counts(
-        _lib.ptr(strong), n, T, NC, K, _lib.ptr(thr), _lib.ptr(win), float(pooling_time_ratio),
-        float(cfg.sample_rate / cfg.hop_length), None, None, None, _lib.ptr(ref.ptr[clip_offset * NC:]), _lib.ptr(ref.onset),
-        _lib.ptr(ref.offset), float(t_collar), float(percentage_of_length), float(time_resolution),
+        *args, float(t_collar), float(percentage_of_length), float(time_resolution),
         _lib.ptr(counts.ev_columns) if per_column else None, _lib.ptr(counts.seg_columns) if per_column else None,
         _lib.ptr(counts.ev), _lib.ptr(counts.seg), _lib.ptr(counts.err), _lib.stream_ptr()), "sed_event_counts")
     return counts
 
 
-def event_counts_from_events(est, ref, t_collar=0.200, percentage_of_length=0.2, time_resolution=1.0, per_column=False):
-    """The matching stage alone: ``est`` is a ``RefEvents`` holding the ESTIMATED events of the same files and classes (they
-    need not be disjoint).  One operating point."""
-    if est.device.type != "cuda" or ref.device.type != "cuda":
-        raise _lib.SedError("event_counts_from_events needs both event sets on the GPU (no CPU fallback)")
-    if est.filenames != ref.filenames or est.labels != ref.labels:
-        raise ValueError("estimated and reference events must cover the same files and classes, in the same order")
-    n, NC = len(ref), ref.nclass
-    counts = Counts(1, NC, ref.device)
-    if per_column:
-        counts.ev_columns = torch.empty(1, n, NC, 3, dtype=torch.int32, device=ref.device)
-        counts.seg_columns = torch.empty(1, n, NC, 4, dtype=torch.int32, device=ref.device)
-    _lib.check(_lib.lib().sed_event_counts(
-        None, n, 0, NC, 1, None, None, 0.0, 0.0, _lib.ptr(est.ptr), _lib.ptr(est.onset), _lib.ptr(est.offset),
-        _lib.ptr(ref.ptr), _lib.ptr(ref.onset), _lib.ptr(ref.offset), float(t_collar), float(percentage_of_length),
-        float(time_resolution), _lib.ptr(counts.ev_columns) if per_column else None,
-        _lib.ptr(counts.seg_columns) if per_column else None, _lib.ptr(counts.ev), _lib.ptr(counts.seg), _lib.ptr(counts.err),
-        _lib.stream_ptr()), "sed_event_counts")
-    return counts
-
-
-class PSDSCounts:
-    """Class totals of one or more ``psds_counts`` calls, on the device: ``totals [K, nclass, 2 + nclass]`` int64 - per class
-    (TP, FP, CT[.][0 .. nclass - 1]) - and the error word, in ONE buffer so that ``host()`` is one copy.  ``columns
-    [K, N, nclass, 2 + nclass]`` int32 holds the last call's per-column counts when it was asked for them.  The criteria
-    ``dtc / gtc / cttc`` belong to the totals: every call that accumulates into them uses these."""
-
-    def __init__(self, n_points, nclass, device, dtc=0.5, gtc=0.5, cttc=0.3):
-        for name, v in (("dtc", dtc), ("gtc", gtc), ("cttc", cttc)):
-            if not 0.0 <= v <= 1.0:                     # (NaN fails too)
-                raise ValueError(f"{name} must be in [0, 1], got {v}")
-        self.K, self.NC = n_points, nclass
-        self.dtc, self.gtc, self.cttc = float(dtc), float(gtc), float(cttc)
-        self.buf = torch.zeros(n_points * nclass * (2 + nclass) + 1, dtype=torch.int64, device=device)
-        self.totals = self.buf[:-1].view(n_points, nclass, 2 + nclass)
-        self.err = self.buf[-1:].view(torch.int32)
-        self.columns = None
-        self.err_what, self.err_bits = "sed_psds_counts", _ERR_BITS           # (the long calls put their own wording here)
-
-    def host(self):
-        """``totals`` as a numpy array - one device -> host copy; raises when a column was over a limit."""
-        return _totals_to_host(self).reshape(self.K, self.NC, 2 + self.NC)
-
-    check = host
-
-
-def _psds_target(counts, K, NC, n, device, dtc, gtc, cttc, per_column):
+def _psds_target(est, dtc, gtc, cttc, counts, per_column):
+    args, n, K, NC, device, _ = est
     if counts is None:
         counts = PSDSCounts(K, NC, device, dtc, gtc, cttc)
     if (counts.K, counts.NC) != (K, NC):
@@ -286,7 +286,27 @@ def _psds_target(counts, K, NC, n, device, dtc, gtc, cttc, per_column):
         raise ValueError("counts was built for other criteria (dtc, gtc, cttc)")
     if per_column:
         counts.columns = torch.empty(K, n, NC, 2 + NC, dtype=torch.int32, device=device)
+    _lib.check(_lib.lib().sed_psds_counts(
+        *args, counts.dtc, counts.gtc, counts.cttc, _lib.ptr(counts.columns) if per_column else None, _lib.ptr(counts.totals),
+        _lib.ptr(counts.err), _lib.stream_ptr()), "sed_psds_counts")
     return counts
+
+
+def event_counts(strong, ref, thresholds=(0.5,), median_windows=(5,), pooling_time_ratio=1, cfg=None, t_collar=0.200,
+                 percentage_of_length=0.2, time_resolution=1.0, clip_offset=0, counts=None, per_column=False):
+    """``strong [n, T, nclass]`` cuda float32 posteriors of clips ``clip_offset .. clip_offset + n - 1`` of ``ref`` -> ``Counts``
+    (device tensors, no synchronisation; pass ``counts`` to accumulate batches).  ``thresholds`` / ``median_windows``: see
+    ``operating_points`` (device tensors are taken as they are).  ``cfg`` supplies sample_rate / hop_length (default
+    baseline/config.py): seconds = frame * pooling_time_ratio / (sample_rate / hop_length), evaluation_measures.py:226-227."""
+    est = _posterior_args(strong, ref, thresholds, median_windows, pooling_time_ratio, cfg, clip_offset, "event_counts")
+    return _event_target(est, t_collar, percentage_of_length, time_resolution, counts, per_column)
+
+
+def event_counts_from_events(est, ref, t_collar=0.200, percentage_of_length=0.2, time_resolution=1.0, per_column=False):
+    """The matching stage alone: ``est`` is a ``RefEvents`` holding the ESTIMATED events of the same files and classes (they
+    need not be disjoint).  One operating point."""
+    return _event_target(_given_args(est, ref, "event_counts_from_events"), t_collar, percentage_of_length, time_resolution,
+                         None, per_column)
 
 
 def psds_counts(strong, ref, thresholds=(0.5,), median_windows=(5,), pooling_time_ratio=1, cfg=None, dtc=0.5, gtc=0.5,
@@ -294,40 +314,14 @@ def psds_counts(strong, ref, thresholds=(0.5,), median_windows=(5,), pooling_tim
     """``event_counts`` for the PSDS criteria: ``strong [n, T, nclass]`` cuda float32 posteriors of clips ``clip_offset ..
     clip_offset + n - 1`` of ``ref`` -> ``PSDSCounts`` (device tensors, no synchronisation; pass ``counts`` to accumulate
     batches - its criteria must be these).  Operating points, ``cfg`` and the seconds as in ``event_counts``."""
-    if strong.device.type != "cuda" or ref.device.type != "cuda":
-        raise _lib.SedError("psds_counts needs GPU tensors and a RefEvents on the GPU (no CPU fallback)")
-    cfg = cfg or _Cfg
-    strong = strong.contiguous().float()
-    n, T, NC = strong.shape
-    if NC != ref.nclass or clip_offset < 0 or clip_offset + n > len(ref):
-        raise ValueError(f"posteriors [{n}, {T}, {NC}] at clip {clip_offset} do not fit the reference ({len(ref)} clips, "
-                         f"{ref.nclass} classes)")
-    thr, win = operating_points(thresholds, median_windows, strong.device)
-    K = thr.numel()
-    counts = _psds_target(counts, K, NC, n, strong.device, dtc, gtc, cttc, per_column)
-    _lib.check(_lib.lib().sed_psds_counts(
-        _lib.ptr(strong), n, T, NC, K, _lib.ptr(thr), _lib.ptr(win), float(pooling_time_ratio),
-        float(cfg.sample_rate / cfg.hop_length), None, None, None, _lib.ptr(ref.ptr[clip_offset * NC:]), _lib.ptr(ref.onset),
-        _lib.ptr(ref.offset), counts.dtc, counts.gtc, counts.cttc, _lib.ptr(counts.columns) if per_column else None,
-        _lib.ptr(counts.totals), _lib.ptr(counts.err), _lib.stream_ptr()), "sed_psds_counts")
-    return counts
+    est = _posterior_args(strong, ref, thresholds, median_windows, pooling_time_ratio, cfg, clip_offset, "psds_counts")
+    return _psds_target(est, dtc, gtc, cttc, counts, per_column)
 
 
 def psds_counts_from_events(est, ref, dtc=0.5, gtc=0.5, cttc=0.3, per_column=False):
     """The criteria alone: ``est`` is a ``RefEvents`` holding the DETECTIONS of the same files and classes.  One operating
     point."""
-    if est.device.type != "cuda" or ref.device.type != "cuda":
-        raise _lib.SedError("psds_counts_from_events needs both event sets on the GPU (no CPU fallback)")
-    if est.filenames != ref.filenames or est.labels != ref.labels:
-        raise ValueError("estimated and reference events must cover the same files and classes, in the same order")
-    n, NC = len(ref), ref.nclass
-    counts = _psds_target(None, 1, NC, n, ref.device, dtc, gtc, cttc, per_column)
-    _lib.check(_lib.lib().sed_psds_counts(
-        None, n, 0, NC, 1, None, None, 0.0, 0.0, _lib.ptr(est.ptr), _lib.ptr(est.onset), _lib.ptr(est.offset),
-        _lib.ptr(ref.ptr), _lib.ptr(ref.onset), _lib.ptr(ref.offset), counts.dtc, counts.gtc, counts.cttc,
-        _lib.ptr(counts.columns) if per_column else None, _lib.ptr(counts.totals), _lib.ptr(counts.err),
-        _lib.stream_ptr()), "sed_psds_counts")
-    return counts
+    return _psds_target(_given_args(est, ref, "psds_counts_from_events"), dtc, gtc, cttc, None, per_column)
 
 
 def weak_counts(weak, labels, thresholds, counts=None):

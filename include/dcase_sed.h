@@ -565,7 +565,8 @@ int sed_stitch_sweep(const float* win_strong, const int32_t* rec_win0, const int
  *              events, 4 = a file of more than 65 536 segments, 8 = a window outside 1 .. 63, 16 = malformed
  *              offsets.  Such a column is not scored (never a truncated count): a caller must treat the totals as
  *              invalid when err != 0.
- * Limits: T <= 2048, nclass <= 16.  The overall error rate with substitutions (a second, label-agnostic
+ * Limits: T <= 2048, nclass <= 16 (the scoring limits and the err bits are defined once, in csrc/score.h, for
+ * these calls and the sed_long_* ones).  The overall error rate with substitutions (a second, label-agnostic
  * matching) is not computed.
  * sed_weak_counts: weak [n_clips][nclass] fp32, labels [n_clips][nclass] uint8, thr [n_points][nclass] ->
  *   counts [n_points][nclass][4] int64 (tp, fp, fn, tn) with pred = weak > thr, ACCUMULATED (chain the batches).
