@@ -1,5 +1,6 @@
-// gconv.hip - generic 3x3 convolution family (C -> C channels, C in {64, 128}, images [B][H][W][C] with W in {16, 4}),
-// forward / dgrad / wgrad, MFMA operands in fp32 (MODE 0) or bf16 (MODE 1).  See gen.h for the shared structure.
+// gconv.hip - generic 3x3 convolution family (C -> C channels, C in {64, 128}, images [B][H][W][C] with W in {16, 4}):
+// forward / dgrad on the fp32 MFMA (SED_DTYPE_F32; the bf16 modes' forward / dgrad are bconv.hip), wgrad for every mode,
+// and the per-forward weight packing.  See gen.h for the GEMM loop.
 //
 // Reference ops: Conv2d(C, C, 3, 1, 1) of conv blocks 1 and 2 (baseline/models/CNN.py:46-47) with
 // nb_filters = [C, C, C] (CNN.py:35-38 takes any list; BASELINE.json configs[4] uses 128) and its autograd.
@@ -19,8 +20,8 @@
 // GLU i (1, 2), folded with the BatchNorm affine so that the kernels work on xhat = (y - mean) * invstd:
 //                 wg  [co][c] = Wglu[co][c] * gamma[c]      bg[co] = bglu[co] + sum_c Wglu[co][c] beta[c]   (fp32)
 //                 wgT [c][co] = Wglu[co][c]                               (dz_lin = dlin @ Wglu, n = c)
-template <int MODE>
-__global__ __launch_bounds__(256) void k_gen_pack(GenPackArgs a) { gen_pack_body<MODE>(a, blockIdx.x * 256 + threadIdx.x); }
+template <int DT>
+__global__ __launch_bounds__(256) void k_gen_pack(GenPackArgs a) { gen_pack_body<DT>(a, blockIdx.x * 256 + threadIdx.x); }
 __global__ __launch_bounds__(256) void k_gen_pack_bias(GenPackArgs a) { gen_pack_bias_body(a, blockIdx.x * 4 + (threadIdx.x >> 6), threadIdx.x & 63); }
 
 int launch_gen_pack(const GenPackArgs& a, int mode, hipStream_t st) {
@@ -36,33 +37,30 @@ int launch_gen_pack(const GenPackArgs& a, int mode, hipStream_t st) {
 }
 
 // ---- forward / dgrad ---------------------------------------------------------------------------------------------------
-template <int MODE, int C, int TW>
+template <int C, int TW>
 struct GConvCfg {
-    using M = MM<MODE>;
     static constexpr int TH = 128 / TW, HW = TW + 2, HH = TH + 2;
-    static constexpr int CS = C + M::PAD;                                   // halo pixel stride (elements)
+    static constexpr int CS = C + GEN_PAD;                                  // halo pixel stride (floats)
     static constexpr int HALO_E = HH * HW * CS;
-    static constexpr int WBUF_E = 2 * C * (M::KC + M::PAD);
-    static constexpr size_t HALO_BYTES = ((size_t)HALO_E * sizeof(typename M::E) + 15) & ~(size_t)15;
-    static constexpr size_t LDS_BYTES = HALO_BYTES + (size_t)WBUF_E * sizeof(typename M::E) + 3 * C * 4 + 4 * 2 * C * 4;
+    static constexpr int WBUF_E = 2 * C * (GEN_KC + GEN_PAD);
+    static constexpr size_t HALO_BYTES = ((size_t)HALO_E * 4 + 15) & ~(size_t)15;
+    static constexpr size_t LDS_BYTES = HALO_BYTES + (size_t)WBUF_E * 4 + 3 * C * 4 + 4 * 2 * C * 4;
 };
 
 // DIR 0: forward (in0 = activations; epilogue: bias, BatchNorm sums).  DIR 1: dgrad (in0 = dz, in1 = y, coef = ca | cb | cc).
-template <int MODE, int C, int TW, int DIR>
+template <int C, int TW, int DIR>
 __global__ __launch_bounds__(256) void k_gconv(const float* __restrict__ in0, const float* __restrict__ in1,
                                                 const float* __restrict__ coef, const void* __restrict__ wpk_v,
                                                 const float* __restrict__ bias, float* __restrict__ out,
                                                 double* __restrict__ stat, int H, int tiles_per_clip, int n_tiles) {
-    using Cfg = GConvCfg<MODE, C, TW>;
-    using M = MM<MODE>;
-    using E = typename M::E;
+    using Cfg = GConvCfg<C, TW>;
     constexpr int NB = C / 32, TH = Cfg::TH, HW = Cfg::HW, HH = Cfg::HH, CS = Cfg::CS, C4 = C / 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char gsm[];
-    E* halo = (E*)gsm;
-    E* wbuf = (E*)(gsm + Cfg::HALO_BYTES);
-    float* cf = (float*)(wbuf + Cfg::WBUF_E);            // [3][C] dgrad affine
+    float* halo = (float*)gsm;
+    float* wbuf = (float*)(gsm + Cfg::HALO_BYTES);
+    float* cf = wbuf + Cfg::WBUF_E;                      // [3][C] dgrad affine
     float* red = cf + 3 * C;                             // [4 waves][2][C] BatchNorm partial sums
-    const E* wpk = (const E*)wpk_v;
+    const float* wpk = (const float*)wpk_v;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = lane & 31, kh = lane >> 5;
     if (DIR == 1) {
         for (int e = tid; e < 3 * C; e += 256) cf[e] = coef[e];
@@ -70,7 +68,7 @@ __global__ __launch_bounds__(256) void k_gconv(const float* __restrict__ in0, co
     // this lane's MFMA row m = n: pixel (r, c) of the tile
     const int pr = (TW == 16) ? 2 * wv + (n >> 4) : 8 * wv + (n >> 2);
     const int pc = (TW == 16) ? (n & 15) : (n & 3);
-    const E* a_row = halo + (pr * HW + pc) * CS;
+    const float* a_row = halo + (pr * HW + pc) * CS;
     float s1[NB], s2[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) { s1[nb] = 0.f; s2[nb] = 0.f; }
@@ -80,8 +78,8 @@ __global__ __launch_bounds__(256) void k_gconv(const float* __restrict__ in0, co
     __syncthreads();
     // ---- halo staging: rows r0 - 1 .. r0 + TH, columns -1 .. TW, all C channels; zero outside the image ----------------
     // Split into "issue every load of the tile" and "convert + store to LDS": a load consumed right after its issue costs
-    // a full memory round trip per item on these one-workgroup-per-CU kernels (23 items per thread: 30 us per tile against
-    // 4 us of bf16 MFMAs in the first version).  The forward kernel goes further and issues the NEXT tile's loads before the
+    // a full memory round trip per item on these one-workgroup-per-CU kernels (23 items per thread: 30 us per tile in the
+    // first version).  The forward kernel goes further and issues the NEXT tile's loads before the
     // current tile's MFMAs, so they are in flight while it computes; dgrad (two source tensors: twice the registers) issues
     // its loads in one batch at the top of the tile.
     constexpr int NL = (HH * HW * C4 + 255) / 256;         // float4 items per thread
@@ -125,7 +123,7 @@ __global__ __launch_bounds__(256) void k_gconv(const float* __restrict__ in0, co
                     for (int q = 0; q < 4; ++q)
                         o[q] = in ? cf[4 * c4 + q] * v[i][q] + cf[C + 4 * c4 + q] * w[i][q] + cf[2 * C + 4 * c4 + q] : 0.f;
                 }
-                M::st4(halo + hp * CS + 4 * c4, o[0], o[1], o[2], o[3]);
+                gen_st4(halo + hp * CS + 4 * c4, o);
             }
         }
     };
@@ -146,12 +144,12 @@ __global__ __launch_bounds__(256) void k_gconv(const float* __restrict__ in0, co
         for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
-        constexpr int CPT = C / M::KC;                    // chunks per tap
+        constexpr int CPT = C / GEN_KC;                   // chunks per tap
         auto aoff = [&](int ch) {
             const int tap = ch / CPT, dr = tap / 3, dc = tap % 3;
-            return (dr * HW + dc) * CS + (ch % CPT) * M::KC;
+            return (dr * HW + dc) * CS + (ch % CPT) * GEN_KC;
         };
-        stream_gemm<MODE, NB, NB, M::KC>(a_row, aoff, wpk, 9 * C, 9 * C, wbuf, acc, 0, tid);
+        stream_gemm<NB, NB, GEN_KC>(a_row, aoff, wpk, 9 * C, 9 * C, wbuf, acc, 0, tid);
         // (stream_gemm ends with a barrier: the halo may be overwritten by the next tile's staging)
         // ---- epilogue: D register r of lane (n, kh) is MFMA row m = (r & 3) + 8 (r >> 2) + 4 kh, column n ------------
 #pragma unroll
@@ -187,67 +185,65 @@ __global__ __launch_bounds__(256) void k_gconv(const float* __restrict__ in0, co
     }
 }
 
-template <int MODE, int C, int TW, int DIR>
+template <int C, int TW, int DIR>
 static int gconv_launch(const float* in0, const float* in1, const float* coef, const void* wpk, const float* bias, float* out,
                         double* stat, int B, int H, hipStream_t st) {
-    using Cfg = GConvCfg<MODE, C, TW>;
+    using Cfg = GConvCfg<C, TW>;
     static thread_local SedAttrOnce attr_done;
     if (attr_done.need()) {
-        SED_CHECK_HIP(hipFuncSetAttribute((const void*)k_gconv<MODE, C, TW, DIR>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        SED_CHECK_HIP(hipFuncSetAttribute((const void*)k_gconv<C, TW, DIR>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                           (int)Cfg::LDS_BYTES));
     }
     SED_CHECK_ARG((size_t)B * H * TW * C < ((size_t)1 << 31), "gconv: image too large for 32-bit offsets");
     const int tpc = (H + Cfg::TH - 1) / Cfg::TH, nt = B * tpc;
     const int grid = nt < 256 ? nt : 256;
-    k_gconv<MODE, C, TW, DIR><<<grid, 256, Cfg::LDS_BYTES, st>>>(in0, in1, coef, wpk, bias, out, stat, H, tpc, nt);
+    k_gconv<C, TW, DIR><<<grid, 256, Cfg::LDS_BYTES, st>>>(in0, in1, coef, wpk, bias, out, stat, H, tpc, nt);
     SED_CHECK_LAUNCH();
     return SED_OK;
 }
 
 template <int DIR>
-static int gconv_dispatch(int mode, int C, int W, const float* in0, const float* in1, const float* coef, const void* wpk,
+static int gconv_dispatch(int C, int W, const float* in0, const float* in1, const float* coef, const void* wpk,
                           const float* bias, float* out, double* stat, int B, int H, hipStream_t st) {
-#define GCONV_CASE(MD, CC, WW) \
-    if (mode == MD && C == CC && W == WW) return gconv_launch<MD, CC, WW, DIR>(in0, in1, coef, wpk, bias, out, stat, B, H, st)
-    GCONV_CASE(0, 64, 16); GCONV_CASE(0, 64, 4); GCONV_CASE(0, 128, 16); GCONV_CASE(0, 128, 4);
-    GCONV_CASE(1, 64, 16); GCONV_CASE(1, 64, 4); GCONV_CASE(1, 128, 16); GCONV_CASE(1, 128, 4);
+#define GCONV_CASE(CC, WW) \
+    if (C == CC && W == WW) return gconv_launch<CC, WW, DIR>(in0, in1, coef, wpk, bias, out, stat, B, H, st)
+    GCONV_CASE(64, 16); GCONV_CASE(64, 4); GCONV_CASE(128, 16); GCONV_CASE(128, 4);
 #undef GCONV_CASE
-    sed_set_error("gconv: unsupported mode %d / channels %d / width %d", mode, C, W);
+    sed_set_error("gconv: unsupported channels %d / width %d", C, W);
     return SED_ERR_UNSUPPORTED;
 }
 
-int launch_gconv_fwd(int mode, int C, const float* in, const void* wpk, const float* bias, float* y, double* stat, int B, int H,
-                     int W, hipStream_t st) {
-    return gconv_dispatch<0>(mode, C, W, in, nullptr, nullptr, wpk, bias, y, stat, B, H, st);
+int launch_gconv_fwd(int C, const float* in, const void* wpk, const float* bias, float* y, double* stat, int B, int H, int W,
+                     hipStream_t st) {
+    return gconv_dispatch<0>(C, W, in, nullptr, nullptr, wpk, bias, y, stat, B, H, st);
 }
-int launch_gconv_dgrad(int mode, int C, const float* dz, const float* yin, const float* coef, const void* wpkT, float* dx, int B,
-                       int H, int W, hipStream_t st) {
-    return gconv_dispatch<1>(mode, C, W, dz, yin, coef, wpkT, nullptr, dx, nullptr, B, H, st);
+int launch_gconv_dgrad(int C, const float* dz, const float* yin, const float* coef, const void* wpkT, float* dx, int B, int H,
+                       int W, hipStream_t st) {
+    return gconv_dispatch<1>(C, W, dz, yin, coef, wpkT, nullptr, dx, nullptr, B, H, st);
 }
 
 // ---- wgrad ---------------------------------------------------------------------------------------------------------------
 // dW[co][ci][tap] = sum_p dy[p][co] x[p + tap][ci]: the contraction runs over PIXELS, which is the slow axis of both
 // channels-last operands.  The f32 MFMA takes one float per lane per operand, so lane = channel reads of the natural
-// [pixel][channel] tiles are already the right fragments (the bf16 MFMA would need both tiles transposed on the way into
-// LDS); this kernel therefore computes in fp32 in BOTH modes.  A workgroup owns a 64 x 64 (co, ci) quadrant for all 9 taps
-// (9 accumulators of 32 x 32 per wave, 144 registers) over a slab of 128-pixel tiles and writes ONE partial
-// [9][64][64] slab; k_gwgrad_reduce adds the slabs in fixed order (bit-reproducible, no float atomics).
+// [pixel][channel] tiles are already the right fragments.  This is the exact-fp32 kernel: SED_DTYPE_F32 at both widths and
+// SED_DTYPE_BF16X3 at W = 4 (the bf16 MFMA kernels below need both tiles transposed on the way into LDS).  A workgroup
+// owns a 64 x 64 (co, ci) quadrant for all 9 taps (9 accumulators of 32 x 32 per wave, 144 registers) over a slab of
+// 128-pixel tiles and writes ONE partial [9][64][64] slab; k_gwgrad_reduce adds the slabs in fixed order (bit-reproducible,
+// no float atomics).
 template <int TW>
 struct GWgCfg {
     static constexpr int TH = 128 / TW, HW = TW + 2, HH = TH + 2, PS = 65;
     static constexpr int X_F = HH * HW * PS, DY_F = 128 * PS;
     static constexpr size_t LDS_BYTES = (size_t)(X_F + DY_F + 3 * 64) * 4;
 };
-// BF: dz, yin and xin are stored as bf16 (SED_DTYPE_BF16); the products stay fp32 (this kernel serves block 2 in that mode)
-template <int TW, int BF>
+template <int TW>
 __global__ __launch_bounds__(256) void k_gwgrad(const void* __restrict__ dz_v, const void* __restrict__ yin_v,
                                                  const float* __restrict__ coef, const void* __restrict__ xin_v,
                                                  float* __restrict__ part, int C, int H, int tiles_per_clip, int n_tiles) {
     using Cfg = GWgCfg<TW>;
-    using ST = typename Stor<BF>::T;
-    const ST* dz = (const ST*)dz_v;
-    const ST* yin = (const ST*)yin_v;
-    const ST* xin = (const ST*)xin_v;
+    const float* dz = (const float*)dz_v;
+    const float* yin = (const float*)yin_v;
+    const float* xin = (const float*)xin_v;
     constexpr int TH = Cfg::TH, HW = Cfg::HW, HH = Cfg::HH, PS = Cfg::PS;
     extern __shared__ __attribute__((aligned(16))) float wsm[];
     float* xs = wsm;                       // halo of x: [HH * HW][PS] (this quadrant's 64 input channels)
@@ -355,14 +351,14 @@ __device__ __forceinline__ void gw_split4(const float (&v)[4], gw_u32x2& hi, gw_
 //   X3 = 0  SED_DTYPE_BF16: dz, y, x are stored as bf16; single products; the next tile's loads fly during the MFMAs
 //   X3 = 1  SED_DTYPE_BF16X3: fp32 storage; dy and x are split hi + lo on their way into LDS (two planes each, 148 KB) and
 //           every tap is hi hi + hi lo + lo hi - the weight gradient of conv block 1 on the bf16 MFMA at ~2^-16 per product
-//           (k_gwgrad<16, 0>, the exact-fp32 MFMA kernel it replaces in this mode, was 28 % of the wide step).  The tile
+//           (k_gwgrad<16>, the exact-fp32 MFMA kernel it replaces in this mode, was 28 % of the wide step).  The tile
 //           is loaded at the top of its iteration (fp32 staging registers for a tile in flight do not fit beside the
 //           accumulators).
 template <int X3>
 __global__ __launch_bounds__(512, 1) void k_gwgrad_bf16(const void* __restrict__ dz_v, const void* __restrict__ yin_v,
                                                        const float* __restrict__ coef, const void* __restrict__ xin_v,
                                                        float* __restrict__ part, int C, int H, int tiles_per_clip, int n_tiles) {
-    using M = MM<1>;
+    using M = H16<0>;                                              // the bf16 MFMA
     using S = typename std::conditional<X3 != 0, float, __bf16>::type;
     using LV = typename std::conditional<X3 != 0, f32x4, gw_u32x2>::type;        // four channels of one pixel as loaded
     constexpr int NG = 2;                                          // wave groups (the four-wave NG = 1 form is gone, see above)
@@ -676,7 +672,7 @@ struct GWg4 {
 __global__ __launch_bounds__(256) void k_gwgrad4_bf16(const __bf16* __restrict__ dz, const __bf16* __restrict__ yin,
                                                        const float* __restrict__ coef, const __bf16* __restrict__ xin,
                                                        float* __restrict__ part, int C, int H, int tiles_per_clip, int n_tiles) {
-    using M = MM<1>;
+    using M = H16<0>;                                              // the bf16 MFMA
     constexpr int TH = GWg4::TH, DS = GWg4::DS;
     extern __shared__ __attribute__((aligned(16))) unsigned char wsm4[];
     __bf16* dyT = (__bf16*)wsm4;
@@ -852,10 +848,10 @@ int launch_gwgrad(int mode, int C, const void* dz, const void* yin, const float*
     } else if (W == 16) {
         using Cfg = GWgCfg<16>;
         static thread_local SedAttrOnce attr;
-        if (attr.need()) { SED_CHECK_HIP(hipFuncSetAttribute((const void*)k_gwgrad<16, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES)); }
+        if (attr.need()) { SED_CHECK_HIP(hipFuncSetAttribute((const void*)k_gwgrad<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES)); }
         tpc = (H + Cfg::TH - 1) / Cfg::TH; nt = B * tpc;
         if (slabs > nt) slabs = nt;
-        k_gwgrad<16, 0><<<dim3(slabs, nq), 256, Cfg::LDS_BYTES, st>>>(dz, yin, coef, xin, part, C, H, tpc, nt);
+        k_gwgrad<16><<<dim3(slabs, nq), 256, Cfg::LDS_BYTES, st>>>(dz, yin, coef, xin, part, C, H, tpc, nt);
     } else if (W == 4 && mode == SED_DTYPE_BF16) {
         static thread_local SedAttrOnce attr;
         if (attr.need()) { SED_CHECK_HIP(hipFuncSetAttribute((const void*)k_gwgrad4_bf16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GWg4::LDS_BYTES)); }
@@ -868,14 +864,10 @@ int launch_gwgrad(int mode, int C, const void* dz, const void* yin, const float*
     } else if (W == 4) {
         using Cfg = GWgCfg<4>;
         static thread_local SedAttrOnce attr;
-        if (attr.need()) {
-            SED_CHECK_HIP(hipFuncSetAttribute((const void*)k_gwgrad<4, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES));
-            SED_CHECK_HIP(hipFuncSetAttribute((const void*)k_gwgrad<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES));
-        }
+        if (attr.need()) { SED_CHECK_HIP(hipFuncSetAttribute((const void*)k_gwgrad<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES)); }
         tpc = (H + Cfg::TH - 1) / Cfg::TH; nt = B * tpc;
         if (slabs > nt) slabs = nt;
-        if (mode == SED_DTYPE_BF16) k_gwgrad<4, 1><<<dim3(slabs, nq), 256, Cfg::LDS_BYTES, st>>>(dz, yin, coef, xin, part, C, H, tpc, nt);
-        else k_gwgrad<4, 0><<<dim3(slabs, nq), 256, Cfg::LDS_BYTES, st>>>(dz, yin, coef, xin, part, C, H, tpc, nt);
+        k_gwgrad<4><<<dim3(slabs, nq), 256, Cfg::LDS_BYTES, st>>>(dz, yin, coef, xin, part, C, H, tpc, nt);
     } else {
         sed_set_error("gwgrad: unsupported width %d", W);
         return SED_ERR_UNSUPPORTED;

@@ -12,10 +12,10 @@
 #include "rnn.h"
 
 static inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
+// bytes per element of the packed weights (wpk, wpkT, wg, wgT) and of the conv-block activations / gradients in HBM (p0, y1,
+// p1, y2; dz1, dz2, dp0, dp1): bf16 in SED_DTYPE_BF16 mode, fp32 otherwise (gen.h Stor<>); p2 - the GRU input - and dp2 are
+// always fp32
 static inline size_t esz(const Geo& g) { return g.mode == SED_DTYPE_BF16 ? 2 : 4; }
-// bytes per element of the conv-block activations / gradients in HBM (p0, y1, p1, y2; dz1, dz2, dp0, dp1): bf16 in
-// SED_DTYPE_BF16 mode, fp32 otherwise (gen.h Stor<>); p2 - the GRU input - and dp2 are always fp32
-static inline size_t ssz(const Geo& g) { return g.mode == SED_DTYPE_BF16 ? 2 : 4; }
 static inline int gru_splitk(const Geo& g) { return g.H == 64 ? SED_GRU_SPLITK : 4; }
 // split-K partials of the GRU weight-gradient batch: the W_ih problems have N = nin (C, or 2H for layer 1), the W_hh
 // problems N = H - the batch's stride is set by the LARGEST of them (with one layer and H > C that is H, not C)
@@ -55,13 +55,12 @@ static GCtx make_gctx(const Geo& g) {
     L.mom0 = L.acc0; L.stat1 = L.acc0 + 64 * sizeof(double); L.stat2 = L.stat1 + 2 * C * sizeof(double);
     put(L.wz0, C * 12 * 4); put(L.wl0, C * 12 * 4); put(L.bn0, 4 * C * 4);
     put(L.mompart, (size_t)x_moments_parts(g) * 54 * sizeof(double));
-    const size_t SS = ssz(g);
-    put(L.p0, n0 * SS);
+    put(L.p0, n0 * E);
     L.p[0] = L.p0;
     const size_t nn[3] = {0, n0, n1}, np[3] = {n0, n1, n2};
     for (int i = 1; i <= 2; ++i) {
         put(L.wpk[i], 9 * C * C * E); put(L.wpkT[i], 9 * C * C * E); put(L.wg[i], C * C * E); put(L.wgT[i], C * C * E);
-        put(L.bg[i], C * 4); put(L.y[i], nn[i] * SS); put(L.bn[i], 4 * C * 4); put(L.p[i], np[i] * (i == 2 ? 4 : SS));
+        put(L.bg[i], C * 4); put(L.y[i], nn[i] * E); put(L.bn[i], 4 * C * 4); put(L.p[i], np[i] * (i == 2 ? 4 : E));
     }
     L.ph[0] = L.ph[1] = 0; L.yh[0] = L.yh[1] = L.yh[2] = 0;
     if (g.f16) { put(L.ph[0], n0 * 2); put(L.yh[1], n0 * 2); put(L.ph[1], n1 * 2); put(L.yh[2], n1 * 2); }
@@ -102,8 +101,8 @@ static GWs make_gws(const Geo& g) {
     for (int l = 0; l < 2; ++l) { put(W.dgi[l], bt * 6 * H * 4); put(W.dgh[l], bt * 6 * H * 4); put(W.hprev[l], bt * 2 * H * 4); }
     put(W.d_in, 2 * bt * 2 * H * 4);          // (H = 64: two direction planes, gru4.hip; generic: one tensor)
     put(W.heads_part, heads_part_floats(g.B, g.T3, g.NC, 2 * H) * 4);
-    const size_t SS = ssz(g);
-    put(W.dp[2], 2 * bt * C * 4); put(W.dz[2], n1 * SS); put(W.dp[1], n1 * SS); put(W.dz[1], n0 * SS); put(W.dp[0], n0 * SS);
+    const size_t E = esz(g);
+    put(W.dp[2], 2 * bt * C * 4); put(W.dz[2], n1 * E); put(W.dp[1], n1 * E); put(W.dz[1], n0 * E); put(W.dp[0], n0 * E);
     W.dz[0] = 0; W.coef[0] = 0;
     put(W.coef[1], 3 * C * 4); put(W.coef[2], 3 * C * 4);
     put(W.glu_part, (size_t)(g.mode == SED_DTYPE_BF16 ? bglu_bwd_grid(g.C, g.B, g.H1, g.W1) : gglu_bwd_grid(g.B, g.H1, g.W1)) * (C * C + 3 * C) * 4);
@@ -122,7 +121,7 @@ size_t gen_ws_bytes(const Geo& g) { return make_gws(g).total; }
 int gen_ctx_view(const Geo& g, const char* name, size_t* offset, size_t* bytes) {
     const GCtx L = make_gctx(g);
     const size_t C = g.C, H = g.H, bt = (size_t)g.B * g.T3;
-    const size_t n0 = (size_t)g.B * g.H1 * g.W1 * C * ssz(g), n1 = (size_t)g.B * g.H2 * g.W2 * C * ssz(g);
+    const size_t n0 = (size_t)g.B * g.H1 * g.W1 * C * esz(g), n1 = (size_t)g.B * g.H2 * g.W2 * C * esz(g);
     struct { const char* n; size_t o, b; } tab[] = {
         {"mom0", L.mom0, 64 * 8}, {"bn0", L.bn0, 4 * C * 4}, {"p0", L.p[0], n0}, {"y1", L.y[1], n0}, {"stat1", L.stat1, 2 * C * 8},
         {"bn1", L.bn[1], 4 * C * 4}, {"p1", L.p[1], n1}, {"y2", L.y[2], n1}, {"stat2", L.stat2, 2 * C * 8}, {"bn2", L.bn[2], 4 * C * 4},
@@ -210,7 +209,6 @@ int gen_forward(const Geo& g, const ParamOff& P, const float* params, float* bn_
         return SED_ERR_WORKSPACE;
     }
     const int C = g.C, H = g.H;
-    const int gm = (g.mode == SED_DTYPE_BF16X3) ? SED_DTYPE_F32 : g.mode;      // arithmetic of everything but the 3x3 convolutions
     const int use_drop = (train && g.p > 0.f) ? 1 : 0;
     const int upd = (train && update_bn) ? 1 : 0;
     // train & 2: train-mode arithmetic, but no backward will ever run on this ctx (the teacher's forward, main.py:87-89): what only
@@ -269,17 +267,21 @@ int gen_forward(const Geo& g, const ParamOff& P, const float* params, float* bn_
     // ---- conv blocks 1, 2 -----------------------------------------------------------------------------------------------
     const size_t so[3] = {0, L.stat1, L.stat2};
     const int Hs[3] = {0, g.H1, g.H2}, Wd[3] = {0, g.W1, g.W2};
+    auto bn_args = [&](int i) {
+        GBnArgs bn;
+        bn.stat = CTXD(so[i]); bn.N = (double)g.B * Hs[i] * Wd[i]; bn.gamma = params + P.bn_g[i]; bn.beta = params + P.bn_b[i];
+        bn.run_mean = bn_running + (2 * i) * C; bn.run_var = bn_running + (2 * i + 1) * C; bn.tracked = trk[i];
+        bn.train = train; bn.update = upd; bn.eps = g.eps; bn.momentum = g.mom; bn.bn = CTXF(L.bn[i]);
+        return bn;
+    };
     for (int i = 1; i <= 2; ++i) {
+        const GBnArgs bn = bn_args(i);
         if (g.f16) {
             // SED_DTYPE_F16: the forward chain runs on the fp16 tensors ph / yh; a training forward also leaves the bf16 copies
             // y[i] / p[i] that the (bf16-family) backward kernels read
             SED_TRY(launch_bconv_fwd(2, C, CTXV(L.ph[i - 1]), CTXV(L.wpk[i]), params + P.conv_b[i], CTXV(L.yh[i]),
                                      train ? CTXD(so[i]) : nullptr, g.B, Hs[i], Wd[i], st));
-            GBnArgs bnf;
-            bnf.stat = CTXD(so[i]); bnf.N = (double)g.B * Hs[i] * Wd[i]; bnf.gamma = params + P.bn_g[i]; bnf.beta = params + P.bn_b[i];
-            bnf.run_mean = bn_running + (2 * i) * C; bnf.run_var = bn_running + (2 * i + 1) * C; bnf.tracked = trk[i];
-            bnf.train = train; bnf.update = upd; bnf.eps = g.eps; bnf.momentum = g.mom; bnf.bn = CTXF(L.bn[i]);
-            SED_TRY(launch_bglu_fwd(C, CTXV(L.yh[i]), bnf, params + P.glu_w[i], params + P.glu_b[i], i == 1 ? CTXV(L.ph[1]) : CTXV(L.p[2]),
+            SED_TRY(launch_bglu_fwd(C, CTXV(L.yh[i]), bn, params + P.glu_w[i], params + P.glu_b[i], i == 1 ? CTXV(L.ph[1]) : CTXV(L.p[2]),
                                     i == 1 ? 1 : 0, g.B, Hs[i], Wd[i], i, use_drop, g.p, seed_dev, use_drop ? CTXM(L.mask[i]) : nullptr,
                                     train ? CTXV(L.wg[i]) : nullptr, train ? CTXF(L.bg[i]) : nullptr, st, 1,
                                     (i == 1 && keep_b16) ? CTXV(L.p[1]) : nullptr, keep_b16 ? CTXV(L.y[i]) : nullptr));
@@ -289,12 +291,8 @@ int gen_forward(const Geo& g, const ParamOff& P, const float* params, float* bn_
             SED_TRY(launch_bconv_fwd(g.mode == SED_DTYPE_BF16X3, C, CTXV(L.p[i - 1]), CTXV(L.wpk[i]), params + P.conv_b[i], CTXV(L.y[i]),
                                      train ? CTXD(so[i]) : nullptr, g.B, Hs[i], Wd[i], st));
         else
-            SED_TRY(launch_gconv_fwd(g.mode, C, CTXF(L.p[i - 1]), CTXV(L.wpk[i]), params + P.conv_b[i], CTXF(L.y[i]),
+            SED_TRY(launch_gconv_fwd(C, CTXF(L.p[i - 1]), CTXV(L.wpk[i]), params + P.conv_b[i], CTXF(L.y[i]),
                                      train ? CTXD(so[i]) : nullptr, g.B, Hs[i], Wd[i], st));
-        GBnArgs bn;
-        bn.stat = CTXD(so[i]); bn.N = (double)g.B * Hs[i] * Wd[i]; bn.gamma = params + P.bn_g[i]; bn.beta = params + P.bn_b[i];
-        bn.run_mean = bn_running + (2 * i) * C; bn.run_var = bn_running + (2 * i + 1) * C; bn.tracked = trk[i];
-        bn.train = train; bn.update = upd; bn.eps = g.eps; bn.momentum = g.mom; bn.bn = CTXF(L.bn[i]);
         if (g.mode == SED_DTYPE_BF16)
             SED_TRY(launch_bglu_fwd(C, CTXV(L.y[i]), bn, params + P.glu_w[i], params + P.glu_b[i], CTXV(L.p[i]), i == 1 ? 1 : 0, g.B,
                                     Hs[i], Wd[i], i, use_drop, g.p, seed_dev, use_drop ? CTXM(L.mask[i]) : nullptr,
@@ -303,8 +301,8 @@ int gen_forward(const Geo& g, const ParamOff& P, const float* params, float* bn_
             SED_TRY(launch_bglu_fwd_x3(C, CTXV(L.y[i]), bn, params + P.glu_w[i], params + P.glu_b[i], CTXV(L.p[i]), g.B, Hs[i], Wd[i], i,
                                        use_drop, g.p, seed_dev, use_drop ? CTXM(L.mask[i]) : nullptr, st));
         else
-        SED_TRY(launch_gglu_fwd(gm, C, CTXV(L.y[i]), bn, CTXV(L.wg[i]), CTXF(L.bg[i]), CTXV(L.p[i]), 0, g.B, Hs[i], Wd[i], i,
-                                use_drop, g.p, seed_dev, use_drop ? CTXM(L.mask[i]) : nullptr, st));
+            SED_TRY(launch_gglu_fwd(C, CTXV(L.y[i]), bn, CTXV(L.wg[i]), CTXF(L.bg[i]), CTXV(L.p[i]), g.B, Hs[i], Wd[i], i, use_drop, g.p,
+                                    seed_dev, use_drop ? CTXM(L.mask[i]) : nullptr, st));
     }
     // ---- BiGRU + heads ---------------------------------------------------------------------------------------------------
     return rnn_forward(g, P, params, rnn_bufs(g, L, ctx, nullptr, nullptr), train, seed_dev, strong, weak, aux.n_grec, st);
@@ -321,7 +319,6 @@ int gen_backward(const Geo& g, const ParamOff& P, const float* params, const flo
         return SED_ERR_WORKSPACE;
     }
     const int C = g.C, H = g.H, BT = g.B * g.T3;
-    const int gm = (g.mode == SED_DTYPE_BF16X3) ? SED_DTYPE_F32 : g.mode;
     const int use_drop = (g.p > 0.f) ? 1 : 0;
     // ---- heads, BiGRU (+ the weight-gradient tail of a parts == 1 / parts == 8 call) ------------------------------------------
     const RnnBwd rb = rnn_backward_plan(g, P, rnn_bufs(g, L, ctx, &W, ws), params, grads, seed_dev, hl, ho, parts, &side);
@@ -332,16 +329,17 @@ int gen_backward(const Geo& g, const ParamOff& P, const float* params, const flo
     const int Hs[3] = {0, g.H1, g.H2}, Wd[3] = {0, g.W1, g.W2};
     for (int i = 2; i >= 1; --i) {
         // (H = 64: the GRU's dX arrives as two direction planes; the GLU backward adds them while loading)
-        const bool new_glu = g.mode == SED_DTYPE_BF16;
-        if (new_glu)
-            SED_TRY(launch_bglu_bwd(C, CTXV(L.y[i]), CTXF(L.bn[i]), CTXV(L.wg[i]), CTXF(L.bg[i]), CTXV(L.wgT[i]), WSF(W.dp[i]), i == 1 ? 1 : 0, WSF(W.dz[i]), WSF(W.glu_part), g.B, Hs[i], Wd[i],
-                                    use_drop, g.p, CTXM(L.mask[i]), st, (i == 2 && H == 64) ? WSF(W.dp[2]) + (size_t)BT * C : nullptr));
+        const float* dp2 = (i == 2 && H == 64) ? WSF(W.dp[2]) + (size_t)BT * C : nullptr;
+        const bool bf16_glu = g.mode == SED_DTYPE_BF16;      // bglu.hip (bf16 storage); fp32 and bf16x3: gglu.hip
+        if (bf16_glu)
+            SED_TRY(launch_bglu_bwd(C, CTXV(L.y[i]), CTXF(L.bn[i]), CTXV(L.wg[i]), CTXF(L.bg[i]), CTXV(L.wgT[i]), WSF(W.dp[i]), i == 1 ? 1 : 0,
+                                    WSF(W.dz[i]), WSF(W.glu_part), g.B, Hs[i], Wd[i], use_drop, g.p, CTXM(L.mask[i]), st, dp2));
         else
-        SED_TRY(launch_gglu_bwd(gm, C, CTXV(L.y[i]), CTXF(L.bn[i]), params + P.bn_g[i], params + P.bn_b[i], CTXV(L.wg[i]),
-                                CTXV(L.wgT[i]), CTXF(L.bg[i]), WSF(W.dp[i]), 0, WSF(W.dz[i]), WSF(W.glu_part), g.B, Hs[i], Wd[i], use_drop,
-                                g.p, CTXM(L.mask[i]), st, (i == 2 && H == 64) ? WSF(W.dp[2]) + (size_t)BT * C : nullptr));
+            SED_TRY(launch_gglu_bwd(C, CTXV(L.y[i]), CTXF(L.bn[i]), params + P.bn_g[i], params + P.bn_b[i], CTXV(L.wg[i]), CTXV(L.wgT[i]),
+                                    CTXF(L.bg[i]), WSF(W.dp[i]), WSF(W.dz[i]), WSF(W.glu_part), g.B, Hs[i], Wd[i], use_drop, g.p,
+                                    CTXM(L.mask[i]), st, dp2));
         GBnBwdArgs pa;
-        pa.part = WSF(W.glu_part); pa.n_part = new_glu ? bglu_bwd_grid(C, g.B, Hs[i], Wd[i]) : gglu_bwd_grid(g.B, Hs[i], Wd[i]); pa.C = C; pa.N = (double)g.B * Hs[i] * Wd[i];
+        pa.part = WSF(W.glu_part); pa.n_part = bf16_glu ? bglu_bwd_grid(C, g.B, Hs[i], Wd[i]) : gglu_bwd_grid(g.B, Hs[i], Wd[i]); pa.C = C; pa.N = (double)g.B * Hs[i] * Wd[i];
         pa.part2 = WSF(W.glu_part2);
         pa.gamma = params + P.bn_g[i]; pa.beta = params + P.bn_b[i]; pa.bn = CTXF(L.bn[i]); pa.coef = WSF(W.coef[i]);
         pa.g_gamma = grads + P.bn_g[i]; pa.g_beta = grads + P.bn_b[i]; pa.g_wglu = grads + P.glu_w[i]; pa.g_bglu = grads + P.glu_b[i];
@@ -354,8 +352,8 @@ int gen_backward(const Geo& g, const ParamOff& P, const float* params, const flo
             SED_TRY(launch_bconv_dgrad(g.mode == SED_DTYPE_BF16X3, C, WSF(W.dz[i]), CTXV(L.y[i]), WSF(W.coef[i]), CTXV(L.wpkT[i]),
                                        WSF(W.dp[i - 1]), g.B, Hs[i], Wd[i], st));
         else
-            SED_TRY(launch_gconv_dgrad(g.mode, C, WSF(W.dz[i]), CTXF(L.y[i]), WSF(W.coef[i]), CTXV(L.wpkT[i]), WSF(W.dp[i - 1]), g.B, Hs[i],
-                                       Wd[i], st));
+            SED_TRY(launch_gconv_dgrad(C, WSF(W.dz[i]), CTXF(L.y[i]), WSF(W.coef[i]), CTXV(L.wpkT[i]), WSF(W.dp[i - 1]), g.B, Hs[i], Wd[i],
+                                       st));
         SED_TRY(side.start());
         SED_TRY(launch_gwgrad(g.mode, C, WSF(W.dz[i]), CTXF(L.y[i]), WSF(W.coef[i]), CTXF(L.p[i - 1]), WSF(W.wg_part), grads + P.conv_w[i], g.B,
                               Hs[i], Wd[i], side.s));

@@ -1,14 +1,16 @@
-// gen.h - building blocks of the GENERIC kernel family (gconv.hip, gglu.hip, ggru.hip, gcrnn.hip): any conv width
-// C in {64, 128}, any GRU width H that is a multiple of 64 up to 256, MFMA operands in fp32 (MODE 0: exact f32,
-// v_mfma_f32_32x32x2_f32) or bf16 (MODE 1: v_mfma_f32_32x32x16_bf16, fp32 accumulate).  The C = 64 / H = 64 / fp32
-// configuration of baseline/config.py:53-58 keeps its own specialised kernels (conv.hip, bnglu.hip, gru4.hip); this
-// family serves BASELINE.json configs[2] (bf16 operands) and configs[4] (nb_filters 3 x 128, n_RNN_cell 256).
+// gen.h - building blocks shared by the GENERIC kernel set (gconv.hip, gglu.hip, bconv.hip, bglu.hip, blk0.hip, grec.hip,
+// ggemm.hip, gcrnn.hip): any conv width C in {64, 128}, any GRU width H that is a multiple of 64 up to 256.  The C = 64 / H = 64
+// / fp32 configuration of baseline/config.py:53-58 keeps its own specialised kernels (conv.hip, bnglu.hip, gru4.hip).
 //
-// Common shape of every GEMM here: C[m][n] += sum_k A[m][k] B[n][k] with BOTH operands k-contiguous - what the bf16
-// MFMA wants (a lane supplies 8 consecutive k of one row) and what channels-last activations / [out][in] weights give
-// for free.  A lives in an LDS tile owned by the workgroup (a halo tile of the image, a row block of pixels); B (weights,
-// packed once per forward by k_gen_pack) streams from L2 through a double-buffered LDS chunk.  All HBM tensors stay fp32:
-// operands are rounded to bf16 when they are staged into LDS, accumulators / BatchNorm statistics / gates are fp32.
+// Two things live here:
+//   - the storage helpers every member of the set uses: fp32 / bf16 / fp16 loads and stores of the conv-block activations
+//     (ld1 / ld4 / st1, Stor<>, H16<>), the dropout keep bits (gen_keep16) and the pooled-pixel index (gen_rb_pixel);
+//   - stream_gemm, the fp32 GEMM loop of gconv.hip (forward / dgrad) and gglu.hip: exact-fp32 products on
+//     v_mfma_f32_32x32x2_f32.  The bf16-operand kernels (bconv.hip, bglu.hip, grec.hip) have loops of their own.
+//
+// Shape of the fp32 GEMM: C[m][n] += sum_k A[m][k] B[n][k] with BOTH operands k-contiguous - what channels-last activations
+// and [out][in] weights give for free.  A lives in an LDS tile owned by the workgroup (a halo tile of the image, a row block of
+// pixels); B (weights, packed once per forward by k_gen_pack) streams from L2 through a double-buffered LDS chunk.
 #pragma once
 #include "common.h"
 #include "philox.h"
@@ -55,52 +57,26 @@ template <> struct H16<1> {
     static __device__ __forceinline__ f32x16 mma(V8 a, V8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 };
 
-template <int MODE> struct MM;
-template <> struct MM<0> {
-    using E = float;
-    using Frag = float;
-    static constexpr int KPL = 1;       // k elements one lane supplies per MFMA operand
-    static constexpr int KSTEP = 2;     // k per MFMA (32x32x2)
-    static constexpr int PAD = 1;       // LDS row padding (elements): odd stride -> lane = row reads hit 32 distinct banks
-    static constexpr int KC = 32;       // k-chunk of the streamed B operand
-    static __device__ __forceinline__ Frag ld(const E* p) { return *p; }
-    static __device__ __forceinline__ f32x16 mma(Frag a, Frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ E cvt(float v) { return v; }
-    static __device__ __forceinline__ void st4(E* p, float a, float b, float c, float d) { p[0] = a; p[1] = b; p[2] = c; p[3] = d; }
-};
-template <> struct MM<1> {
-    using E = __bf16;
-    using Frag = bf16x8;
-    static constexpr int KPL = 8;
-    static constexpr int KSTEP = 16;    // 32x32x16
-    static constexpr int PAD = 8;       // row stride (K + 8) * 2 B = odd multiple of 16 B: ds_read_b128 lane groups conflict-free
-    static constexpr int KC = 64;
-    static __device__ __forceinline__ Frag ld(const E* p) { return *(const Frag*)p; }
-    static __device__ __forceinline__ f32x16 mma(Frag a, Frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ E cvt(float v) { return (__bf16)v; }     // v_cvt_pk_bf16_f32: round to nearest even
-    static __device__ __forceinline__ void st4(E* p, float a, float b, float c, float d) {
-        bf16x4 v = {(__bf16)a, (__bf16)b, (__bf16)c, (__bf16)d};
-        *(bf16x4*)p = v;                // 8-byte store (row strides are multiples of 8 B)
-    }
-};
+// ---- the fp32 GEMM loop: B operand streamed through LDS ------------------------------------------------------------------
+// LDS rows of fp32 MFMA operands are padded by one word: an odd stride, so that lane = row reads hit 32 distinct banks
+constexpr int GEN_PAD = 1;
+constexpr int GEN_KC = 32;              // default k-chunk of the streamed B operand
+// four consecutive floats into such a row (odd word stride: no wider store is aligned)
+__device__ __forceinline__ void gen_st4(float* p, f32x4 v) { p[0] = v[0]; p[1] = v[1]; p[2] = v[2]; p[3] = v[3]; }
 
-// ---- B operand streamed through LDS -----------------------------------------------------------------------------------
 // acc[nb][.] += sum_{k < K} A(row of this lane, k) * Bg[(nb0 + nb) * 32 + (lane & 31)][k],  nb < NBW
-//   Bg     global, element type E, row-major [32 * NBT][ldb] (k contiguous), 16-byte aligned rows; ALL 32 * NBT rows are
-//          staged (the waves of a workgroup may each take a different slice nb0 .. nb0 + NBW of them)
+//   Bg     global, row-major [32 * NBT][ldb] (k contiguous), 16-byte aligned rows; ALL 32 * NBT rows are staged (the waves of
+//          a workgroup may each take a different slice nb0 .. nb0 + NBW of them)
 //   a_row  per-lane LDS pointer to the first k of this lane's A row; the A elements of chunk ch start at a_row + aoff(ch)
 //          (a functor: the 3x3 convolution moves to another halo pixel every C / KC chunks)
-//   wbuf   LDS, 2 x [32 * NBT][KC + PAD] elements; every thread of the 256-thread workgroup must call (staging + barriers:
+//   wbuf   LDS, 2 x [32 * NBT][KC + GEN_PAD] floats; every thread of the 256-thread workgroup must call (staging + barriers:
 //          one barrier before the first MFMA - so LDS tiles written before the call are visible to all waves - and one
 //          after the last, so they may be overwritten right after the call)
-template <int MODE, int NBT, int NBW, int KC, class AOff>
-__device__ __forceinline__ void stream_gemm(const typename MM<MODE>::E* a_row, AOff aoff, const typename MM<MODE>::E* __restrict__ Bg,
-                                            int ldb, int K, typename MM<MODE>::E* wbuf, f32x16 (&acc)[NBW], int nb0, int tid) {
-    using M = MM<MODE>;
-    using E = typename M::E;
-    constexpr int N = 32 * NBT, WS = KC + M::PAD;
-    constexpr int EPV = 16 / (int)sizeof(E);                 // elements per 16-byte vector
-    constexpr int VPR = KC / EPV;                            // vectors per row
+template <int NBT, int NBW, int KC, class AOff>
+__device__ __forceinline__ void stream_gemm(const float* a_row, AOff aoff, const float* __restrict__ Bg, int ldb, int K, float* wbuf,
+                                            f32x16 (&acc)[NBW], int nb0, int tid) {
+    constexpr int N = 32 * NBT, WS = KC + GEN_PAD;
+    constexpr int VPR = KC / 4;                              // 16-byte vectors per row
     constexpr int NV = N * VPR / 256;                        // vectors per thread per chunk
     static_assert(N * VPR % 256 == 0 && NV >= 1, "chunk must divide over 256 threads");
     const int lane = tid & 63, kh = lane >> 5, n = lane & 31;
@@ -110,21 +86,17 @@ __device__ __forceinline__ void stream_gemm(const typename MM<MODE>::E* a_row, A
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int u = tid + 256 * i, row = u / VPR, cv = u % VPR;
+            // (16-byte vector cv of the row, addressed in bytes: `+ 4 * cv` floats is the same address, but the kernels come
+            // out in a different instruction order)
             st[i] = *(const f32x4*)((const char*)(Bg + (size_t)row * ldb + (size_t)ch * KC) + 16 * cv);
         }
     };
     auto store = [&](int buf) {
-        E* wb = wbuf + buf * N * WS;
+        float* wb = wbuf + buf * N * WS;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int u = tid + 256 * i, row = u / VPR, cv = u % VPR;
-            E* d = wb + row * WS + cv * EPV;
-            if (MODE == 1) {
-                *(f32x4*)d = st[i];                          // 16-byte aligned: WS * 2 B is a multiple of 16
-            } else {
-                float* df = (float*)d;
-                df[0] = st[i][0]; df[1] = st[i][1]; df[2] = st[i][2]; df[3] = st[i][3];
-            }
+            gen_st4(wb + row * WS + cv * 4, st[i]);
         }
     };
     load(0);
@@ -132,13 +104,13 @@ __device__ __forceinline__ void stream_gemm(const typename MM<MODE>::E* a_row, A
     __syncthreads();
     for (int ch = 0; ch < nch; ++ch) {
         if (ch + 1 < nch) load(ch + 1);
-        const E* ap = a_row + aoff(ch) + M::KPL * kh;
-        const E* bp = wbuf + (ch & 1) * N * WS + (nb0 * 32 + n) * WS + M::KPL * kh;
+        const float* ap = a_row + aoff(ch) + kh;            // 32x32x2: lane (n, kh) supplies k = 2 ks + kh
+        const float* bp = wbuf + (ch & 1) * N * WS + (nb0 * 32 + n) * WS + kh;
 #pragma unroll
-        for (int ks = 0; ks < KC / M::KSTEP; ++ks) {
-            const typename M::Frag a = M::ld(ap + ks * M::KSTEP);
+        for (int ks = 0; ks < KC / 2; ++ks) {
+            const float a = ap[2 * ks];
 #pragma unroll
-            for (int nb = 0; nb < NBW; ++nb) acc[nb] = M::mma(a, M::ld(bp + nb * 32 * WS + ks * M::KSTEP), acc[nb]);
+            for (int nb = 0; nb < NBW; ++nb) acc[nb] = mfma32(a, bp[nb * 32 * WS + 2 * ks], acc[nb]);
         }
         if (ch + 1 < nch) store((ch + 1) & 1);
         __syncthreads();

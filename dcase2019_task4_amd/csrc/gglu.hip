@@ -1,11 +1,12 @@
 // gglu.hip - BatchNorm-apply + GLU + dropout + AvgPool2d((2,4)) for conv blocks 1 and 2, generic in the channel count
-// (C in {64, 128}) and the MFMA operand type (gen.h), forward and backward.
+// (C in {64, 128}), forward and backward, on the fp32 MFMA with fp32 storage: SED_DTYPE_F32, and the backward of
+// SED_DTYPE_BF16X3.  (bf16 storage / operands: bglu.hip.)
 //
 // Reference ops (baseline/models/CNN.py:49-67, GLU CNN.py:11-16):
 //   z = BatchNorm2d(y);  lin = Linear(C, C)(z over channels);  out = lin * sigmoid(z);  p = AvgPool2d((2,4))(Dropout(out))
 // The kernels work on xhat = (y - mean) * invstd: with wg = Wglu diag(gamma) and bg = bglu + Wglu beta (k_gen_pack)
 //   lin = wg xhat + bg,   z = gamma xhat + beta,
-// so the LDS tile holds ONE fp32 quantity that is the MFMA operand (fp32 mode), the source of the gate, and the factor
+// so the LDS tile holds ONE fp32 quantity that is the MFMA operand, the source of the gate, and the factor
 // of the BatchNorm-backward sum (sum dz * xhat) - y itself is not needed again.
 // Row block = 4 consecutive pooled pixels = 32 input pixels ordered as in bnglu.hip (MFMA row m: pooled pixel m >> 3,
 // dt = (m >> 2) & 1, df = m & 3), so that a 2x4 pooling window is 4 registers of a lane pair.
@@ -38,14 +39,14 @@ __device__ __forceinline__ void gbn_prep(const GBnArgs& a, int C, int c, bool pu
     }
 }
 
-// Staging of one row block (32 pixels x C channels) as xhat into xf (fp32) and, in bf16 mode, xb; one wave.  Split into
+// Staging of one row block (32 pixels x C channels) as xhat into xf; one wave.  Split into
 // "issue all loads" and "normalise + store to LDS": a load consumed right after its issue exposes a full memory round
 // trip per item on these one-workgroup-per-CU kernels (16 items per lane: ~30 us per round in the first version); the
 // forward kernel issues the NEXT round's loads before the current round's MFMAs.
 template <int C>
 struct GGluTile { f32x4 v[32 * (C / 4) / 64]; };
-template <int C, class YT>
-__device__ __forceinline__ void gglu_load(GGluTile<C>& t, const YT* __restrict__ y, int q0, int Q, int H, int W, int Ho, int Wo,
+template <int C>
+__device__ __forceinline__ void gglu_load(GGluTile<C>& t, const float* __restrict__ y, int q0, int Q, int H, int W, int Ho, int Wo,
                                           int lane) {
     constexpr int C4 = C / 4;
     int pb[4];
@@ -62,11 +63,9 @@ __device__ __forceinline__ void gglu_load(GGluTile<C>& t, const YT* __restrict__
         if (base < 0) t.v[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
 }
-template <int MODE, int C>
-__device__ __forceinline__ void gglu_store(const GGluTile<C>& t, const float* bn_s, float* xf, typename MM<MODE>::E* xb, int q0, int Q,
-                                           int lane) {
-    using M = MM<MODE>;
-    constexpr int C4 = C / 4, XS = C + 1, BS = C + M::PAD;
+template <int C>
+__device__ __forceinline__ void gglu_store(const GGluTile<C>& t, const float* bn_s, float* xf, int q0, int Q, int lane) {
+    constexpr int C4 = C / 4, XS = C + GEN_PAD;
 #pragma unroll
     for (int i = 0; i < 32 * C4 / 64; ++i) {
         const int g = lane + 64 * i, m = g / C4, c4 = g % C4;
@@ -74,47 +73,36 @@ __device__ __forceinline__ void gglu_store(const GGluTile<C>& t, const float* bn
         f32x4 v;
 #pragma unroll
         for (int q = 0; q < 4; ++q) v[q] = ok ? (t.v[i][q] - bn_s[4 * c4 + q]) * bn_s[C + 4 * c4 + q] : 0.f;
-        float* d = xf + m * XS + 4 * c4;
-        d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
-        if (MODE == 1) M::st4(xb + m * BS + 4 * c4, v[0], v[1], v[2], v[3]);
+        gen_st4(xf + m * XS + 4 * c4, v);
     }
 }
 
-template <int MODE, int C>
+template <int C>
 struct GGluFwdCfg {
-    using M = MM<MODE>;
-    static constexpr int XS = C + 1, BS = C + M::PAD;
-    static constexpr size_t XF_BYTES = (size_t)4 * 32 * XS * 4;
-    static constexpr size_t XB_BYTES = MODE == 1 ? (size_t)4 * 32 * BS * 2 : 0;
-    static constexpr size_t WBUF_BYTES = (size_t)2 * C * (M::KC + M::PAD) * sizeof(typename M::E);
-    static constexpr size_t LDS_BYTES = XF_BYTES + XB_BYTES + WBUF_BYTES + 2 * C * 4 + 64;
+    static constexpr int XS = C + GEN_PAD;
+    static constexpr size_t XF_BYTES = (size_t)4 * 32 * XS * 4;                        // xhat, 4 row blocks (one per wave)
+    static constexpr size_t WBUF_BYTES = (size_t)2 * C * (GEN_KC + GEN_PAD) * 4;
+    static constexpr size_t LDS_BYTES = XF_BYTES + WBUF_BYTES + 2 * C * 4 + 64;
 };
 
-// PB: the pooled output is stored as bf16 (SED_DTYPE_BF16, block 1; block 2's output p2 feeds the fp32 GRU)
-template <int MODE, int C, int PB>
+template <int C>
 __global__ __launch_bounds__(256) void k_gglu_fwd(const void* __restrict__ y_v, GBnArgs bnp, const void* __restrict__ wg_v,
                                                    const float* __restrict__ bg, void* __restrict__ p_v, int H, int W, int Ho,
                                                    int Wo, int Q, int block_id, int use_drop, float p_drop,
                                                    const uint64_t* __restrict__ seed_ptr, uint16_t* __restrict__ mask_out) {
-    using Cfg = GGluFwdCfg<MODE, C>;
-    using M = MM<MODE>;
-    using E = typename M::E;
-    using YT = typename Stor<MODE == 1>::T;
-    using PT = typename Stor<PB>::T;
-    const YT* y = (const YT*)y_v;
-    PT* p = (PT*)p_v;
-    constexpr int NB = C / 32, XS = Cfg::XS, BS = Cfg::BS;
+    using Cfg = GGluFwdCfg<C>;
+    const float* y = (const float*)y_v;
+    float* p = (float*)p_v;
+    constexpr int NB = C / 32, XS = Cfg::XS;
     extern __shared__ __attribute__((aligned(16))) unsigned char gsm[];
     float* xf_all = (float*)gsm;
-    E* xb_all = (E*)(gsm + Cfg::XF_BYTES);
-    E* wbuf = (E*)(gsm + Cfg::XF_BYTES + Cfg::XB_BYTES);
-    float* bn_s = (float*)(gsm + Cfg::XF_BYTES + Cfg::XB_BYTES + Cfg::WBUF_BYTES);
-    const E* wg = (const E*)wg_v;
+    float* wbuf = (float*)(gsm + Cfg::XF_BYTES);
+    float* bn_s = (float*)(gsm + Cfg::XF_BYTES + Cfg::WBUF_BYTES);
+    const float* wg = (const float*)wg_v;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = lane & 31, kh = lane >> 5;
     if (tid < C) gbn_prep(bnp, C, tid, blockIdx.x == 0, bn_s);
     __syncthreads();
     float* xf = xf_all + wv * 32 * XS;
-    E* xb = xb_all + wv * 32 * BS;
     float gam[NB], bet[NB], bgl[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) { gam[nb] = bnp.gamma[32 * nb + n]; bet[nb] = bnp.beta[32 * nb + n]; bgl[nb] = bg[32 * nb + n]; }
@@ -126,24 +114,23 @@ __global__ __launch_bounds__(256) void k_gglu_fwd(const void* __restrict__ y_v, 
     GGluTile<C> yt;
     {
         const int rb0 = blockIdx.x * 4 + wv;
-        gglu_load<C, YT>(yt, y, (rb0 < n_rb ? rb0 : 0) * 4, Q, H, W, Ho, Wo, lane);
+        gglu_load<C>(yt, y, (rb0 < n_rb ? rb0 : 0) * 4, Q, H, W, Ho, Wo, lane);
     }
     for (int round = 0; round < rounds; ++round) {
         const int rb = (round * gridDim.x + blockIdx.x) * 4 + wv;
         const bool live = rb < n_rb;
         const int q0 = rb * 4;
-        if (live) gglu_store<MODE, C>(yt, bn_s, xf, xb, q0, Q, lane);
+        if (live) gglu_store<C>(yt, bn_s, xf, q0, Q, lane);
         {   // the next round's tile flies during this round's MFMAs and epilogue (past the end: row block 0, never used)
             const int rbn = ((round + 1) * gridDim.x + blockIdx.x) * 4 + wv;
-            gglu_load<C, YT>(yt, y, (rbn < n_rb ? rbn : 0) * 4, Q, H, W, Ho, Wo, lane);
+            gglu_load<C>(yt, y, (rbn < n_rb ? rbn : 0) * 4, Q, H, W, Ho, Wo, lane);
         }
         f32x16 acc[NB];
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
-        const E* a_row = (MODE == 1) ? (const E*)(xb + n * BS) : (const E*)(xf + n * XS);
-        stream_gemm<MODE, NB, NB, M::KC>(a_row, [](int ch) { return ch * M::KC; }, wg, C, C, wbuf, acc, 0, tid);
+        stream_gemm<NB, NB, GEN_KC>(xf + n * XS, [](int ch) { return ch * GEN_KC; }, wg, C, C, wbuf, acc, 0, tid);
         if (live) {
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) {
@@ -163,6 +150,7 @@ __global__ __launch_bounds__(256) void k_gglu_fwd(const void* __restrict__ y_v, 
 #pragma unroll
                 for (int jx = 0; jx < 4; ++jx) pooled[jx] += __shfl_xor(pooled[jx], 32);
                 const int j0 = 2 * kh;
+                // (st1, gen.h: its float overload.  A plain `p[..] = ..` here compiles to a different instruction order.)
                 if (q0 + j0 < Q) st1(p + (size_t)(q0 + j0) * C + c, (kh ? pooled[2] : pooled[0]) * sc);
                 if (q0 + j0 + 1 < Q) st1(p + (size_t)(q0 + j0 + 1) * C + c, (kh ? pooled[3] : pooled[1]) * sc);
             }
@@ -171,106 +159,83 @@ __global__ __launch_bounds__(256) void k_gglu_fwd(const void* __restrict__ y_v, 
     }
 }
 
-template <int MODE, int C, int PB>
+template <int C>
 static int gglu_fwd_launch(const void* y, const GBnArgs& bn, const void* wg, const float* bg, void* p, int B, int H, int W,
                            int block_id, int use_drop, float p_drop, const uint64_t* seed, uint16_t* mask_out, hipStream_t st) {
-    using Cfg = GGluFwdCfg<MODE, C>;
+    using Cfg = GGluFwdCfg<C>;
     static thread_local SedAttrOnce attr;
     if (attr.need()) {
-        SED_CHECK_HIP(hipFuncSetAttribute((const void*)k_gglu_fwd<MODE, C, PB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES));
+        SED_CHECK_HIP(hipFuncSetAttribute((const void*)k_gglu_fwd<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES));
     }
     const int Ho = H / 2, Wo = W / 4, Q = B * Ho * Wo, n_rb = (Q + 3) / 4;
     int grid = (n_rb + 3) / 4;
     if (grid > 512) grid = 512;
-    k_gglu_fwd<MODE, C, PB><<<grid, 256, Cfg::LDS_BYTES, st>>>(y, bn, wg, bg, p, H, W, Ho, Wo, Q, block_id, use_drop, p_drop, seed, mask_out);
+    k_gglu_fwd<C><<<grid, 256, Cfg::LDS_BYTES, st>>>(y, bn, wg, bg, p, H, W, Ho, Wo, Q, block_id, use_drop, p_drop, seed, mask_out);
     SED_CHECK_LAUNCH();
     return SED_OK;
 }
 
-int launch_gglu_fwd(int mode, int C, const void* y, const GBnArgs& bn, const void* wg, const float* bg, void* p, int p_bf16, int B,
-                    int H, int W, int block_id, int use_drop, float p_drop, const uint64_t* seed, uint16_t* mask_out, hipStream_t st) {
-#define GGLU_CASE(MD, CC, PP) \
-    if (mode == MD && C == CC && p_bf16 == PP) return gglu_fwd_launch<MD, CC, PP>(y, bn, wg, bg, p, B, H, W, block_id, use_drop, p_drop, seed, mask_out, st)
-    GGLU_CASE(0, 64, 0); GGLU_CASE(0, 128, 0);
-#undef GGLU_CASE
-    sed_set_error("gglu forward: unsupported mode %d / channels %d", mode, C);
+int launch_gglu_fwd(int C, const void* y, const GBnArgs& bn, const void* wg, const float* bg, void* p, int B, int H, int W,
+                    int block_id, int use_drop, float p_drop, const uint64_t* seed, uint16_t* mask_out, hipStream_t st) {
+    if (C == 64) return gglu_fwd_launch<64>(y, bn, wg, bg, p, B, H, W, block_id, use_drop, p_drop, seed, mask_out, st);
+    if (C == 128) return gglu_fwd_launch<128>(y, bn, wg, bg, p, B, H, W, block_id, use_drop, p_drop, seed, mask_out, st);
+    sed_set_error("gglu forward: unsupported channels %d", C);
     return SED_ERR_UNSUPPORTED;
 }
 
 // ---- backward ----------------------------------------------------------------------------------------------------------
 // A workgroup round covers TWO row blocks (64 pixels); the four waves are (row block g = wave >> 1) x (channel half
 // hf = wave & 1): wherever a channel is an OUTPUT index (lin / dz columns) a wave owns C / 2 of them, which halves the
-// accumulators and - above all - the LDS tiles (fp32 xhat + fp32 dlin (+ their bf16 operand copies) for 4 row blocks
-// would not fit next to the weight chunks at C = 128).
+// accumulators and - above all - the LDS tiles (xhat + dlin for 4 row blocks would not fit next to the weight chunks at
+// C = 128).
 //   P1  lin[:, half] = xhat @ wg^T (recomputed)        epilogue: sigma, dlin = g sigma -> LDS, gate path dzg
 //   P2  dzl[:, half] = dlin @ Wglu                      epilogue: dz = dzl + dzg -> HBM, sums of dz and dz * xhat
 //   P3  dWx[co][c] += sum_p dlin[p][co] xhat[p][c]      contraction over the round's 64 PIXELS; wave w owns (C / 32)^2 / 4
-//       tiles of 32 x 32.  fp32 mode: f32 MFMA on the natural [pixel][channel] tiles.  bf16 mode: both operands are
-//       needed pixel-contiguous - the P1 epilogue holds 4 consecutive pixels of one channel per lane (D layout), so it
-//       writes dlinT / xhatT [channel][pixel] as 8-byte bf16 groups for free (the fp32 P3 was 8 192 of the 10 240 MFMA
-//       cycles of a round)
+//       tiles of 32 x 32, on the natural [pixel][channel] tiles (8 192 of the 10 240 MFMA cycles of a round)
 // Per-workgroup partial sums (dWx, sum dlin, sum dz, sum dz xhat) go to `part`; k_gbn_bwd_prep adds them in fixed order.
-template <int MODE, int C>
+template <int C>
 struct GGluBwdCfg {
-    using M = MM<MODE>;
-    static constexpr int KC = (MODE == 0 && C == 128) ? 16 : M::KC;        // fp32 at C = 128: smaller weight chunks, LDS budget
-    static constexpr int XS = C + 1, BS = C + M::PAD;
-    static constexpr int TS = 64 + 8;                                      // bf16 mode: row stride of the pixel-contiguous tiles
-    static constexpr size_t XF_BYTES = (size_t)2 * 32 * XS * 4;            // xhat fp32, 2 row blocks
-    static constexpr size_t DF_BYTES = MODE == 0 ? XF_BYTES : 0;           // dlin fp32 (P3 operand of the fp32 mode)
-    static constexpr size_t XB_BYTES = MODE == 1 ? (size_t)2 * 32 * BS * 2 : 0;
-    static constexpr size_t DB_BYTES = XB_BYTES;
-    static constexpr size_t TT_BYTES = MODE == 1 ? (size_t)2 * C * TS * 2 : 0;    // dlinT | xhatT: [C][64 pixels] bf16 (P3 operands)
-    static constexpr size_t WBUF_BYTES = (size_t)2 * C * (KC + M::PAD) * sizeof(typename M::E);
-    static constexpr size_t LDS_BYTES = XF_BYTES + DF_BYTES + XB_BYTES + DB_BYTES + TT_BYTES + WBUF_BYTES + 2 * C * 4 + 64;
+    static constexpr int KC = C == 128 ? 16 : GEN_KC;                      // C = 128: smaller weight chunks, LDS budget
+    static constexpr int XS = C + GEN_PAD;
+    static constexpr size_t XF_BYTES = (size_t)2 * 32 * XS * 4;            // xhat, 2 row blocks
+    static constexpr size_t DF_BYTES = XF_BYTES;                           // dlin (P2 and P3 operand)
+    static constexpr size_t WBUF_BYTES = (size_t)2 * C * (KC + GEN_PAD) * 4;
+    static constexpr size_t LDS_BYTES = XF_BYTES + DF_BYTES + WBUF_BYTES + 2 * C * 4 + 64;
 };
 
-// PB: dp (the gradient w.r.t. the pooled output) arrives as bf16 (SED_DTYPE_BF16, block 1: written by block 2's dgrad);
-// y is read and dz written in the mode's storage type
-template <int MODE, int C, int PB>
+template <int C>
 __global__ __launch_bounds__(256) void k_gglu_bwd(const void* __restrict__ y_v, const float* __restrict__ bn,
                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
                                                    const void* __restrict__ wg_v, const void* __restrict__ wgT_v,
                                                    const float* __restrict__ bg, const void* __restrict__ dp_v, const float* __restrict__ dp2,
                                                    void* __restrict__ dz_v, float* __restrict__ part, int H, int W, int Ho, int Wo,
                                                    int Q, int use_drop, float p_drop, const uint16_t* __restrict__ mask_in) {
-    using Cfg = GGluBwdCfg<MODE, C>;
-    using M = MM<MODE>;
-    using E = typename M::E;
-    using YT = typename Stor<MODE == 1>::T;
-    using PT = typename Stor<PB>::T;
-    const YT* y = (const YT*)y_v;
-    YT* dz = (YT*)dz_v;
-    const PT* dp = (const PT*)dp_v;
-    constexpr int NB = C / 32, NBW = NB / 2, XS = Cfg::XS, BS = Cfg::BS, KC = Cfg::KC;
+    using Cfg = GGluBwdCfg<C>;
+    const float* y = (const float*)y_v;
+    float* dz = (float*)dz_v;
+    const float* dp = (const float*)dp_v;
+    constexpr int NB = C / 32, NBW = NB / 2, XS = Cfg::XS, KC = Cfg::KC;
     constexpr int TPW = NB * NB / 4;                       // dWx tiles (32 x 32) per wave
     extern __shared__ __attribute__((aligned(16))) unsigned char gsm[];
     float* xf_all = (float*)gsm;
     float* df_all = (float*)(gsm + Cfg::XF_BYTES);
-    E* xb_all = (E*)(gsm + Cfg::XF_BYTES + Cfg::DF_BYTES);
-    E* db_all = (E*)(gsm + Cfg::XF_BYTES + Cfg::DF_BYTES + Cfg::XB_BYTES);
-    __bf16* dlT = (__bf16*)(gsm + Cfg::XF_BYTES + Cfg::DF_BYTES + Cfg::XB_BYTES + Cfg::DB_BYTES);
-    __bf16* xhT = dlT + C * Cfg::TS;
-    E* wbuf = (E*)(gsm + Cfg::XF_BYTES + Cfg::DF_BYTES + Cfg::XB_BYTES + Cfg::DB_BYTES + Cfg::TT_BYTES);
-    constexpr int TS = Cfg::TS;
+    float* wbuf = (float*)(gsm + Cfg::XF_BYTES + Cfg::DF_BYTES);
     float* bn_s = (float*)((unsigned char*)wbuf + Cfg::WBUF_BYTES);
-    const E* wg = (const E*)wg_v;
-    const E* wgT = (const E*)wgT_v;
+    const float* wg = (const float*)wg_v;
+    const float* wgT = (const float*)wgT_v;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = lane & 31, kh = lane >> 5;
     const int g = wv >> 1, hf = wv & 1, nb0 = hf * NBW;
     if (H & 1) {        // the floor-mode pool drops the last row of an odd-height image: its gradient is 0
         const int per_clip = W * C, nbt = Q / (Ho * Wo);
         for (int i = blockIdx.x * 256 + tid; i < nbt * per_clip; i += gridDim.x * 256) {
             const int bb = i / per_clip, r = i % per_clip;
-            st1(dz + ((size_t)bb * H + (H - 1)) * W * C + r, 0.f);
+            dz[((size_t)bb * H + (H - 1)) * W * C + r] = 0.f;
         }
     }
     if (tid < C) { bn_s[tid] = bn[tid]; bn_s[C + tid] = bn[C + tid]; }       // mean, invstd
     __syncthreads();
     float* xf = xf_all + g * 32 * XS;
     float* dfl = df_all + g * 32 * XS;
-    E* xb = xb_all + g * 32 * BS;
-    E* dbl = db_all + g * 32 * BS;
     float gam[NBW], bet[NBW], bgl[NBW];
 #pragma unroll
     for (int nb = 0; nb < NBW; ++nb) {
@@ -316,9 +281,7 @@ __global__ __launch_bounds__(256) void k_gglu_bwd(const void* __restrict__ y_v, 
                 f32x4 v;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[q] = (base >= 0) ? (yv[i][q] - bn_s[4 * c4 + q]) * bn_s[C + 4 * c4 + q] : 0.f;
-                float* d = xf + m * XS + 4 * c4;
-                d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
-                if (MODE == 1) M::st4(xb + m * BS + 4 * c4, v[0], v[1], v[2], v[3]);
+                gen_st4(xf + m * XS + 4 * c4, v);
             }
         }
         // pooled gradients and keep bits of this wave's channels
@@ -331,7 +294,7 @@ __global__ __launch_bounds__(256) void k_gglu_bwd(const void* __restrict__ y_v, 
             for (int jx = 0; jx < 4; ++jx) {
                 const size_t e = (size_t)(q0 + jx) * C + c;
                 // dp2: the second direction plane of gru4.hip's dX (H = 64), added while loading
-                gq[nb][jx] = (live && q0 + jx < Q) ? (dp2 ? ld1(dp + e) + dp2[e] : ld1(dp + e)) * sc : 0.f;
+                gq[nb][jx] = (live && q0 + jx < Q) ? (dp2 ? dp[e] + dp2[e] : dp[e]) * sc : 0.f;
             }
             mk[nb] = (use_drop && live) ? (uint32_t)mask_in[((size_t)rb * NB + nb0 + nb) * 64 + lane] : 0xffffu;
         }
@@ -341,15 +304,11 @@ __global__ __launch_bounds__(256) void k_gglu_bwd(const void* __restrict__ y_v, 
         for (int nb = 0; nb < NBW; ++nb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
-        {
-            const E* a_row = (MODE == 1) ? (const E*)(xb + n * BS) : (const E*)(xf + n * XS);
-            stream_gemm<MODE, NB, NBW, KC>(a_row, [](int ch) { return ch * KC; }, wg, C, C, wbuf, acc, nb0, tid);
-        }
+        stream_gemm<NB, NBW, KC>(xf + n * XS, [](int ch) { return ch * KC; }, wg, C, C, wbuf, acc, nb0, tid);
         float dzg[NBW][16];
 #pragma unroll
         for (int nb = 0; nb < NBW; ++nb) {
             const int c = 32 * (nb0 + nb) + n;
-            float dl4[4], xh4[4];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = mfma32_row(r, lane);
@@ -357,18 +316,7 @@ __global__ __launch_bounds__(256) void k_gglu_bwd(const void* __restrict__ y_v, 
                 const float sg = sigmoidf_fast(fmaf(gam[nb], xh, bet[nb]));
                 const float gg = ((mk[nb] >> r) & 1u) ? gq[nb][r >> 2] : 0.f;
                 const float dl = gg * sg;
-                if (MODE == 0) dfl[row * XS + c] = dl;
-                if (MODE == 1) {
-                    dbl[row * BS + c] = M::cvt(dl);
-                    dl4[r & 3] = dl; xh4[r & 3] = xh;
-                    if ((r & 3) == 3) {     // rows row - 3 .. row are 4 consecutive pixels of this row block: one 8-byte group
-                        const int p0 = 32 * g + row - 3;
-                        bf16x4 vd = {(__bf16)dl4[0], (__bf16)dl4[1], (__bf16)dl4[2], (__bf16)dl4[3]};
-                        bf16x4 vx = {(__bf16)xh4[0], (__bf16)xh4[1], (__bf16)xh4[2], (__bf16)xh4[3]};
-                        *(bf16x4*)(dlT + c * TS + p0) = vd;
-                        *(bf16x4*)(xhT + c * TS + p0) = vx;
-                    }
-                }
+                dfl[row * XS + c] = dl;
                 sdb[nb] += dl;
                 dzg[nb][r] = dl * (1.0f - sg) * (acc[nb][r] + bgl[nb]);
             }
@@ -378,10 +326,7 @@ __global__ __launch_bounds__(256) void k_gglu_bwd(const void* __restrict__ y_v, 
         for (int nb = 0; nb < NBW; ++nb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
-        {
-            const E* a_row = (MODE == 1) ? (const E*)(dbl + n * BS) : (const E*)(dfl + n * XS);
-            stream_gemm<MODE, NB, NBW, KC>(a_row, [](int ch) { return ch * KC; }, wgT, C, C, wbuf, acc, nb0, tid);
-        }
+        stream_gemm<NB, NBW, KC>(dfl + n * XS, [](int ch) { return ch * KC; }, wgT, C, C, wbuf, acc, nb0, tid);
         if (live) {
             int pb[4];
 #pragma unroll
@@ -395,7 +340,7 @@ __global__ __launch_bounds__(256) void k_gglu_bwd(const void* __restrict__ y_v, 
                     const int base = (j == 0) ? pb[0] : (j == 1) ? pb[1] : (j == 2) ? pb[2] : pb[3];
                     if (base >= 0) {
                         const float v = acc[nb][r] + dzg[nb][r];
-                        st1(dz + (size_t)(base + kh * W + df) * C + c, v);
+                        dz[(size_t)(base + kh * W + df) * C + c] = v;
                         sdz[nb] += v;
                         sdzx[nb] += v * xf[mfma32_row(r, lane) * XS + c];
                     }
@@ -403,31 +348,17 @@ __global__ __launch_bounds__(256) void k_gglu_bwd(const void* __restrict__ y_v, 
             }
         }
         // ---- P3: dWx[co][c] += sum over the round's 64 pixels of dlin[p][co] xhat[p][c] ----------------------------------
-        if (MODE == 1) {
-            const __bf16* Ap = dlT + (32 * cob + n) * TS + 8 * kh;       // A[i = co][k = p .. p + 7]
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const bf16x8 a = *(const bf16x8*)(Ap + 16 * ks);
-                if (C == 64) {
-                    dW[0] = MM<1>::mma(a, *(const bf16x8*)(xhT + (32 * (wv & 1) + n) * TS + 16 * ks + 8 * kh), dW[0]);
-                } else {
-#pragma unroll
-                    for (int t = 0; t < TPW; ++t) dW[t] = MM<1>::mma(a, *(const bf16x8*)(xhT + (32 * t + n) * TS + 16 * ks + 8 * kh), dW[t]);
-                }
-            }
-        } else {
-            const float* Ap = df_all + 32 * cob + n;          // A[i = co][k = p]
+        const float* Ap = df_all + 32 * cob + n;              // A[i = co][k = p]
 #pragma unroll 4
-            for (int s = 0; s < 32; ++s) {
-                const int pix = 2 * s + kh;                    // 0..63: row block pix >> 5, row pix & 31 -> contiguous tiles
-                const float a = Ap[pix * XS];
-                const float* bx = xf_all + pix * XS + n;
-                if (C == 64) {
-                    dW[0] = mfma32(a, bx[32 * (wv & 1)], dW[0]);
-                } else {
+        for (int s = 0; s < 32; ++s) {
+            const int pix = 2 * s + kh;                        // 0..63: row block pix >> 5, row pix & 31 -> contiguous tiles
+            const float a = Ap[pix * XS];
+            const float* bx = xf_all + pix * XS + n;
+            if (C == 64) {
+                dW[0] = mfma32(a, bx[32 * (wv & 1)], dW[0]);
+            } else {
 #pragma unroll
-                    for (int t = 0; t < TPW; ++t) dW[t] = mfma32(a, bx[32 * t], dW[t]);
-                }
+                for (int t = 0; t < TPW; ++t) dW[t] = mfma32(a, bx[32 * t], dW[t]);
             }
         }
         __syncthreads();                                       // tiles free for the next round
@@ -461,31 +392,29 @@ int gglu_bwd_grid(int B, int H, int W) {
     return grid > 256 ? 256 : grid;
 }
 
-template <int MODE, int C, int PB>
+template <int C>
 static int gglu_bwd_launch(const void* y, const float* bn, const float* gamma, const float* beta, const void* wg, const void* wgT,
                            const float* bg, const void* dp, const float* dp2, void* dz, float* part, int B, int H, int W, int use_drop,
                            float p_drop, const uint16_t* mask_in, hipStream_t st) {
-    using Cfg = GGluBwdCfg<MODE, C>;
+    using Cfg = GGluBwdCfg<C>;
     static_assert(Cfg::LDS_BYTES <= 160 * 1024, "GLU backward tiles exceed the LDS");
     static thread_local SedAttrOnce attr;
     if (attr.need()) {
-        SED_CHECK_HIP(hipFuncSetAttribute((const void*)k_gglu_bwd<MODE, C, PB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES));
+        SED_CHECK_HIP(hipFuncSetAttribute((const void*)k_gglu_bwd<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_BYTES));
     }
     const int Ho = H / 2, Wo = W / 4, Q = B * Ho * Wo;
-    k_gglu_bwd<MODE, C, PB><<<gglu_bwd_grid(B, H, W), 256, Cfg::LDS_BYTES, st>>>(y, bn, gamma, beta, wg, wgT, bg, dp, dp2, dz, part, H, W, Ho,
+    k_gglu_bwd<C><<<gglu_bwd_grid(B, H, W), 256, Cfg::LDS_BYTES, st>>>(y, bn, gamma, beta, wg, wgT, bg, dp, dp2, dz, part, H, W, Ho,
                                                                              Wo, Q, use_drop, p_drop, mask_in);
     SED_CHECK_LAUNCH();
     return SED_OK;
 }
 
-int launch_gglu_bwd(int mode, int C, const void* y, const float* bn, const float* gamma, const float* beta, const void* wg,
-                    const void* wgT, const float* bg, const void* dp, int dp_bf16, void* dz, float* part, int B, int H, int W,
-                    int use_drop, float p_drop, const uint16_t* mask_in, hipStream_t st, const float* dp2) {
-#define GGLU_CASE(MD, CC, PP) \
-    if (mode == MD && C == CC && dp_bf16 == PP) return gglu_bwd_launch<MD, CC, PP>(y, bn, gamma, beta, wg, wgT, bg, dp, dp2, dz, part, B, H, W, use_drop, p_drop, mask_in, st)
-    GGLU_CASE(0, 64, 0); GGLU_CASE(0, 128, 0);
-#undef GGLU_CASE
-    sed_set_error("gglu backward: unsupported mode %d / channels %d", mode, C);
+int launch_gglu_bwd(int C, const void* y, const float* bn, const float* gamma, const float* beta, const void* wg, const void* wgT,
+                    const float* bg, const void* dp, void* dz, float* part, int B, int H, int W, int use_drop, float p_drop,
+                    const uint16_t* mask_in, hipStream_t st, const float* dp2) {
+    if (C == 64) return gglu_bwd_launch<64>(y, bn, gamma, beta, wg, wgT, bg, dp, dp2, dz, part, B, H, W, use_drop, p_drop, mask_in, st);
+    if (C == 128) return gglu_bwd_launch<128>(y, bn, gamma, beta, wg, wgT, bg, dp, dp2, dz, part, B, H, W, use_drop, p_drop, mask_in, st);
+    sed_set_error("gglu backward: unsupported channels %d", C);
     return SED_ERR_UNSUPPORTED;
 }
 

@@ -1,4 +1,4 @@
-// gkernels.h - host-side launchers of the generic kernel family (gen.h); internal.
+// gkernels.h - host-side launchers of the generic kernel set (gcrnn.hip's operators); internal.
 #pragma once
 #include "common.h"
 
@@ -6,7 +6,7 @@
 struct GenPackArgs {
     int C;
     const float *w1, *w2;                       // conv1 / conv2 weights [co][ci][3][3]
-    void *wpk1, *wpk2, *wpkT1, *wpkT2;          // packed (element type by mode) [n][9 C]; wpkT may be null (eval)
+    void *wpk1, *wpk2, *wpkT1, *wpkT2;          // packed [n][9 C], element type by launch_gen_pack's mode (gpack.h); wpkT may be null (eval)
     const float *glu_w1, *glu_w2, *glu_b1, *glu_b2, *gamma1, *gamma2, *beta1, *beta2;
     void *wg1, *wg2, *wgT1, *wgT2;              // GLU weights folded with gamma [co][c]; transposed raw [c][co] (may be null)
     float *bg1, *bg2;                           // GLU bias folded with beta [C]
@@ -15,13 +15,15 @@ struct GenPackArgs {
                                                 // SGPR counts of k_gen_pack<1> and k_blk0_prep_aux move with its layout
     int f16;                                    // SED_DTYPE_F16 (mode 1 family): the FORWARD panels wpk1 / wpk2 as fp16; everything else bf16
 };
-int launch_gen_pack(const GenPackArgs& a, int mode, hipStream_t st);
-int launch_gconv_fwd(int mode, int C, const float* in, const void* wpk, const float* bias, float* y, double* stat, int B, int H,
-                     int W, hipStream_t st);
-int launch_gconv_dgrad(int mode, int C, const float* dz, const float* yin, const float* coef, const void* wpkT, float* dx, int B,
-                       int H, int W, hipStream_t st);
+int launch_gen_pack(const GenPackArgs& a, int mode, hipStream_t st);      // mode: Geo::mode
+// forward / dgrad of SED_DTYPE_F32 (fp32 MFMA, fp32 storage); the other modes run launch_bconv_*
+int launch_gconv_fwd(int C, const float* in, const void* wpk, const float* bias, float* y, double* stat, int B, int H, int W,
+                     hipStream_t st);
+int launch_gconv_dgrad(int C, const float* dz, const float* yin, const float* coef, const void* wpkT, float* dx, int B, int H,
+                       int W, hipStream_t st);
 int gwgrad_slabs(int C);
-// mode 1: dz, yin, xin are bf16
+// weight gradient of every mode (Geo::mode).  SED_DTYPE_BF16: dz, yin, xin are bf16 and both widths run on the bf16 MFMA;
+// SED_DTYPE_BF16X3: fp32 storage, W = 16 on the bf16 MFMA with split operands, W = 4 exact fp32; SED_DTYPE_F32: exact fp32
 int launch_gwgrad(int mode, int C, const void* dz, const void* yin, const float* coef, const void* xin, float* part, float* g_w, int B,
                   int H, int W, hipStream_t st);
 
@@ -41,15 +43,16 @@ struct GBnArgs {
     int train, update; float eps, momentum;
     float* bn;                                  // out [4][C]: mean, invstd, scale, shift
 };
-// mode 0 (fp32) only: SED_DTYPE_BF16 runs bglu.hip's kernels (p_bf16, dp_bf16 and mode 1 are no longer instantiated)
-int launch_gglu_fwd(int mode, int C, const void* y, const GBnArgs& bn, const void* wg, const float* bg, void* p, int p_bf16, int B,
-                    int H, int W, int block_id, int use_drop, float p_drop, const uint64_t* seed, uint16_t* mask_out, hipStream_t st);
+// fp32 MFMA, fp32 storage (y, p, dp, dz; wg / wgT as packed for SED_DTYPE_F32): the forward of SED_DTYPE_F32, the backward
+// of SED_DTYPE_F32 and SED_DTYPE_BF16X3.  bf16 storage runs bglu.hip's kernels.
+int launch_gglu_fwd(int C, const void* y, const GBnArgs& bn, const void* wg, const float* bg, void* p, int B, int H, int W,
+                    int block_id, int use_drop, float p_drop, const uint64_t* seed, uint16_t* mask_out, hipStream_t st);
 int gglu_bwd_grid(int B, int H, int W);
 // part: [grid][C * C + 3 * C] floats (per-workgroup partial sums: dWx | sdb | sdz | sdzx)
-// mode 1: y is read and dz written as bf16; dp is bf16 when dp_bf16 (block 1) - block 2's dp comes from the GRU in fp32
-int launch_gglu_bwd(int mode, int C, const void* y, const float* bn, const float* gamma, const float* beta, const void* wg,
-                    const void* wgT, const float* bg, const void* dp, int dp_bf16, void* dz, float* part, int B, int H, int W,
-                    int use_drop, float p_drop, const uint16_t* mask_in, hipStream_t st, const float* dp2 = nullptr);
+// dp2 (may be null): a second plane of dp, added while loading (H = 64: the GRU's dX arrives as two direction planes)
+int launch_gglu_bwd(int C, const void* y, const float* bn, const float* gamma, const float* beta, const void* wg, const void* wgT,
+                    const float* bg, const void* dp, void* dz, float* part, int B, int H, int W, int use_drop, float p_drop,
+                    const uint16_t* mask_in, hipStream_t st, const float* dp2 = nullptr);
 #define GPART_SLICES 8
 struct GBnBwdArgs {
     const float* part; int n_part; int C; double N;

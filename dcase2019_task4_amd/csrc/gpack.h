@@ -8,12 +8,11 @@
 #include "gen.h"
 #include "gkernels.h"
 
-// MODE 0 / 1: every packed operand in fp32 / bf16.  MODE 2 (SED_DTYPE_BF16X3): the conv panels as TWO bf16 planes
-// [hi | lo][n][9 C] (w = hi + lo to ~2^-17 relative; bconv.hip), the GLU operands as in MODE 0.
-template <int MODE>
+// DT = Geo::mode.  SED_DTYPE_F32 / SED_DTYPE_BF16: every packed operand in fp32 / bf16.  SED_DTYPE_BF16X3: the conv panels as
+// TWO bf16 planes [hi | lo][n][9 C] (w = hi + lo to ~2^-17 relative; bconv.hip), the GLU operands in fp32.
+template <int DT>
 __device__ __forceinline__ void gen_pack_body(const GenPackArgs& a, int i) {
-    using M = MM<MODE == 2 ? 0 : MODE>;
-    using E = typename M::E;
+    using E = typename Stor<DT == SED_DTYPE_BF16>::T;      // (float -> __bf16 casts round to nearest even: v_cvt_pk_bf16_f32)
     const int C = a.C, CC = C * C;
     if (i < a.n_zero) a.zero[i] = 0.0;
     if (i < 2 * 9 * CC) {
@@ -21,7 +20,7 @@ __device__ __forceinline__ void gen_pack_body(const GenPackArgs& a, int i) {
         const int n = e / (9 * C), r = e % (9 * C), tap = r / C, k = r % C;
         const float* w = layer ? a.w2 : a.w1;
         const float wf = w[((size_t)n * C + k) * 9 + tap], wt = w[((size_t)k * C + n) * 9 + (8 - tap)];
-        if (MODE == 2) {
+        if (DT == SED_DTYPE_BF16X3) {
             __bf16* wpk = (__bf16*)(layer ? a.wpk2 : a.wpk1);
             __bf16* wpkT = (__bf16*)(layer ? a.wpkT2 : a.wpkT1);
             const __bf16 h = (__bf16)wf;
@@ -30,9 +29,9 @@ __device__ __forceinline__ void gen_pack_body(const GenPackArgs& a, int i) {
         } else {
             E* wpk = (E*)(layer ? a.wpk2 : a.wpk1);
             E* wpkT = (E*)(layer ? a.wpkT2 : a.wpkT1);
-            if (MODE == 1 && a.f16) ((_Float16*)wpk)[e] = (_Float16)wf;      // the forward's operand type; the dgrad panel stays bf16
-            else wpk[e] = M::cvt(wf);
-            if (wpkT) wpkT[e] = M::cvt(wt);
+            if (DT == SED_DTYPE_BF16 && a.f16) ((_Float16*)wpk)[e] = (_Float16)wf;      // the forward's operand type; the dgrad panel stays bf16
+            else wpk[e] = (E)wf;
+            if (wpkT) wpkT[e] = (E)wt;
         }
     }
     if (i < 2 * CC) {
@@ -41,8 +40,8 @@ __device__ __forceinline__ void gen_pack_body(const GenPackArgs& a, int i) {
         const float* gam = layer ? a.gamma2 : a.gamma1;
         E* o = (E*)(layer ? a.wg2 : a.wg1);
         E* oT = (E*)(layer ? a.wgT2 : a.wgT1);
-        o[e] = M::cvt(wg[e] * gam[c]);
-        if (oT) oT[(size_t)c * C + co] = M::cvt(wg[e]);
+        o[e] = (E)(wg[e] * gam[c]);
+        if (oT) oT[(size_t)c * C + co] = (E)wg[e];
     }
 }
 // bg[co] = bglu[co] + sum_c Wglu[co][c] beta[c]: one wave per (layer, co) row, coalesced reads, fp64 butterfly
