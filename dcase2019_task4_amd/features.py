@@ -375,7 +375,7 @@ class OneBatchAheadFrontEnd:
         step.moments_ahead = False
         env = os.environ.get("SED_FE_MOMENTS")
         self.moments = (env == "1") if env in ("0", "1") else (step.student._dtype != _lib.DTYPE_F32)
-        step._mom_external = self.moments
+        step.invalidate_batch()
         self.l = _lib.lib()
         self.key = torch.tensor([(int(seed) * 0x9E3779B97F4A7C15 + 0x2545F4914F6CDD1D) & 0x7FFFFFFFFFFFFFFF],
                                 dtype=torch.int64, device=step.device)
@@ -419,6 +419,9 @@ class OneBatchAheadFrontEnd:
             st._moments(x, st.ctx_s)
             if x_ema is not None:
                 st._moments(x_ema, st.ctx_t)
+        # ctx now holds this batch's moments: a plain st.run() may use them only if the batch went into the step's own buffers
+        # (the overlap protocol trains on its other slot through _mom_ready and sets the mark itself after each step)
+        st._mom_valid = self.moments and x is st.x
 
     def _point_step_at(self, i):
         st = self.step
@@ -516,12 +519,16 @@ class OneBatchAheadFrontEnd:
                     if self._cur == 1:
                         for a, b in zip(self._slots[0], self._slots[1]):
                             a.copy_(b)
+                    st._mom_valid = self.moments       # (ctx holds the moments of the batch extracted last, now in slot 0)
                     return self.run()
             self._graphs[self._cur].replay()
         self._cur ^= 1
         self._runs += 1
         st._warm += 1
         st.steps_done += 1
+        # (a replay sets no host flag: ctx holds the moments of the batch in slot _cur, and st.x is slot 0)
+        st._mom_valid = self.moments and self._cur == 0
+        st._resident = False
 
     def flush(self):
         """Train on the batch extracted last without extracting another one."""
@@ -538,6 +545,7 @@ class OneBatchAheadFrontEnd:
         if self.overlap:
             st._warm += 1
             st.steps_done += 1
+        st.invalidate_batch()                          # nothing is staged behind this step: the next batch brings its own moments
         self._primed = False
 
 

@@ -247,8 +247,10 @@ class MeanTeacherStep:
         # leave most of the chip idle - and this step's forwards start at k_blk0_prep: 16 us (B = 24) off the head of the
         # critical chain, every step still computing one pair of moments.  step() / load_batch() + run() never speculates:
         # self.x may ONLY change through load_batch() (or be followed by invalidate_batch()).
+        # Readiness belongs to the BATCH in self.x / self.x_ema, not to the step: whoever writes the moments into ctx marks them
+        # valid (the tail below; a one-batch-ahead front-end's features()), whatever replaces the batch or the state clears
+        # the mark (load_batch, invalidate_batch, load_state_dict), and run() picks its form from the mark alone.
         self.moments_ahead = os.environ.get("SED_MOMENTS_AHEAD", "0") == "1"
-        self._mom_external = False         # features.WaveformFrontEnd: every batch arrives with its moments already in ctx
         self._mom_valid = False            # ctx_s / ctx_t hold the moments of what is in self.x / self.x_ema right now
         self._resident = False            # a run() has consumed the batch in self.x and no load_batch() came since
         self._mom_ready = self._mom_next = False      # the variant being run / captured
@@ -571,7 +573,7 @@ class MeanTeacherStep:
                                 "the gradients of that step were filled with NaN")
         # which form of the step: forwards that find their patch moments in ctx (valid: the previous run left them there) and / or
         # a tail that computes them for the next run (the batch is resident: nothing was loaded since the previous run)
-        key = (self._mom_valid, self._resident) if self.moments_ahead else (self._mom_external, False)
+        key = (self._mom_valid, self._resident and self.moments_ahead)
         self._mom_ready, self._mom_next = key
         graph = self.use_graph and self._warm >= 2
         if graph:
@@ -736,6 +738,7 @@ class MeanTeacherStep:
 
     def load_state_dict(self, sd):
         assert sd.get("format") == 1, "unknown checkpoint format"
+        self.invalidate_batch()
         self.student.load(parameters=sd["model"])
         if self.teacher is not None and sd.get("model_ema") is not None:
             self.teacher.load(parameters=sd["model_ema"])

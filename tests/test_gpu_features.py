@@ -160,8 +160,9 @@ def test_waveform_front_end_one_batch_ahead_equals_serial():
     assert res[0][2] == res[1][2]
 
 
-@pytest.mark.parametrize("fork", ["backward", "gru"])
-def test_waveform_front_end_streaming_pairs_every_batch_with_its_own_target(fork, monkeypatch):
+@pytest.mark.parametrize("fork,fe_moments", [pytest.param("backward", None, id="backward"), pytest.param("gru", None, id="gru"),
+                                             pytest.param("backward", "1", id="backward-moments")])
+def test_waveform_front_end_streaming_pairs_every_batch_with_its_own_target(fork, fe_moments, monkeypatch):
     """with DISTINCT waveforms and targets per step the one-batch-ahead front-end must train on batch k's
     features with batch k's target, every batch exactly once (also across the eager -> graph switch).  feed() / flush() with
     overlap on (two slots, the extraction inside the step's hipGraph, forked at the student's recurrence) must leave the
@@ -172,6 +173,13 @@ def test_waveform_front_end_streaming_pairs_every_batch_with_its_own_target(fork
     # both fork points of the extraction inside the step's graph: after the forwards (default) and from inside the student
     # forward, at its recurrence (sed_crnn_fork_callback)
     monkeypatch.setenv("SED_FE_FORK", fork)
+    # SED_FE_MOMENTS=1 (off by default in fp32): the front-end also writes block 0's patch moments of the batch it extracts, and
+    # the steps read them - eager, captured, in both slots and in flush().  Only with the default fork: forked at the recurrence,
+    # the next batch's moments are not ordered against the teacher forward that still reads this batch's.
+    if fe_moments is None:
+        monkeypatch.delenv("SED_FE_MOMENTS", raising=False)
+    else:
+        monkeypatch.setenv("SED_FE_MOMENTS", fe_moments)
     B, T, n_steps = 8, 628, 7
     waves = [np.stack([synth.make_wave(100 * k + i, 160000) for i in range(B)]).astype(np.float32) for k in range(n_steps)]
     tgts = [synth.make_target(3 + k, B, T // 8) for k in range(n_steps)]
@@ -183,7 +191,7 @@ def test_waveform_front_end_streaming_pairs_every_batch_with_its_own_target(fork
         student.train(); teacher.train()
         st = MeanTeacherStep(student, teacher, B, T, 100, wm, sm, seed=99, use_graph=True)
         fe = WaveformFrontEnd(st, waves[0], FeatureConfig.baseline_16k(), overlap=overlap, seed=7)
-        assert fe.overlap == overlap
+        assert fe.overlap == overlap and fe.moments == (fe_moments == "1")
         losses = []
         for k in range(n_steps):
             fe.feed(waves[k], tgts[max(0, k - lag)][0])

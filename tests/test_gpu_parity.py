@@ -471,7 +471,9 @@ def test_patch_moments_one_step_ahead_are_bit_identical(graph, kw):
     B, T = 8, 216
     tgt, wm, sm = synth.make_target(1, B, T // 8)
     xa, xea = synth.make_input(60, B, T).cuda(), synth.make_input(70, B, T).cuda()
-    xb, xeb = synth.make_input(61, B, T).cuda(), synth.make_input(71, B, T).cuda()
+    # (another LEVEL, not only other values: block 0 normalised with the moments of a batch of the same distribution stays
+    # inside the bf16 family's 5e-3 below, with these it does not)
+    xb, xeb = (2.0 * synth.make_input(61, B, T) + 0.5).cuda(), (2.0 * synth.make_input(71, B, T) + 0.5).cuda()
     res = {}
     for ahead in (False, True):
         s, _ = gu.make_model(0, dropout=0.5, **kw)

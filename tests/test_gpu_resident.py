@@ -92,11 +92,11 @@ def test_gather_equal_length_pool_is_bit_identical_to_logmel_transform(math_dtyp
     assert torch.equal(vc, LogMelTransform(T, sc, math_dtype=math_dtype)(stacked)) and torch.equal(vc, clean)
 
 
-def _train_set(lengths_seed=0, ragged=True, T=628):
+def _train_set(lengths_seed=0, ragged=True, T=628, lengths=(560, 700)):
     from dcase2019_task4_amd.resident import ResidentFeatureSet
     sizes, bsz = (8, 12, 8), (2, 4, 2)                      # 3 steps per epoch (min(8 // 2, 12 // 4, 8 // 2))
     rs_ = np.random.RandomState(lengths_seed)
-    lengths = [int(rs_.randint(560, 700)) if ragged else T for _ in range(sum(sizes))]
+    lengths = [int(rs_.randint(*lengths)) if ragged else T for _ in range(sum(sizes))]
     feats = _clips(lengths, 20 + lengths_seed)
     tgts = []
     for i in range(sum(sizes)):
@@ -111,26 +111,33 @@ def _train_set(lengths_seed=0, ragged=True, T=628):
     return ResidentFeatureSet.from_arrays(feats, tgts, sizes, bsz, frames=T, scaler=sc, seed=5), feats, tgts, sc
 
 
-def _mt_step(rs, seed=99):
+def _mt_step(rs, seed=99, mfma_dtype="f32"):
     from dcase2019_task4_amd.train import MeanTeacherStep
-    student, _ = gu.make_model(0, dropout=0.5)
-    teacher, _ = gu.make_model(1, dropout=0.5)
+    student, _ = gu.make_model(0, dropout=0.5, mfma_dtype=mfma_dtype)
+    teacher, _ = gu.make_model(1, dropout=0.5, mfma_dtype=mfma_dtype)
     student.train(); teacher.train()
     st = MeanTeacherStep(student, teacher, rs.batch, rs.frames, 100, rs.weak_mask, rs.strong_mask, seed=seed, use_graph=True)
     return st, student, teacher
 
 
-def test_resident_front_end_one_batch_ahead_equals_serial_across_epochs():
+@pytest.mark.parametrize("fe_moments", [None, "1"], ids=["default", "moments"])
+def test_resident_front_end_one_batch_ahead_equals_serial_across_epochs(fe_moments, monkeypatch):
     """7 steps over 3-step epochs (two epoch boundaries, the second table drawn while the first epoch runs): the gather of
-    batch k + 1 inside step k's hipGraph must leave models and meters bit-identical to the serial protocol."""
+    batch k + 1 inside step k's hipGraph must leave models and meters bit-identical to the serial protocol.  SED_FE_MOMENTS=1:
+    the front-end also writes block 0's patch moments of batch k + 1 (off by default in fp32) - through the eager steps, the
+    capture, both slots' graphs and the serial protocol's own graph."""
     from dcase2019_task4_amd.resident import ResidentFrontEnd
+    if fe_moments is None:
+        monkeypatch.delenv("SED_FE_MOMENTS", raising=False)
+    else:
+        monkeypatch.setenv("SED_FE_MOMENTS", fe_moments)
     rs = _train_set()[0]
     out = []
     for overlap in (False, True):
         np.random.seed(2024)
         st, s, t = _mt_step(rs)
         fe = ResidentFrontEnd(st, rs, overlap=overlap)
-        assert fe.overlap == overlap
+        assert fe.overlap == overlap and fe.moments == (fe_moments == "1")
         meters = []
         for _ in range(7):
             fe.run()
@@ -139,6 +146,36 @@ def test_resident_front_end_one_batch_ahead_equals_serial_across_epochs():
         out.append((s._flat.clone(), t._flat.clone(), meters))
     assert torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1], out[1][1])
     assert out[0][2] == out[1][2] and all(np.isfinite(m["loss"]) for m in out[0][2])
+
+
+def test_resident_front_end_f16_with_moments_tracks_serial_without(monkeypatch):
+    """The same 7 steps in the fp16-forward mode, where the front-end owns the moments by default: the overlap protocol with
+    them against the serial protocol with SED_FE_MOMENTS=0 (every forward computes its own), same dropout keys, on the
+    student's strong and weak posteriors of every step.  Each leg is within F16_POST_TOL of the exact value, so they are
+    within twice that of each other."""
+    from dcase2019_task4_amd.resident import ResidentFrontEnd
+    from tests.test_gpu_generic import F16_POST_TOL
+    rs = _train_set()[0]
+    out = []
+    for overlap, env in ((False, "0"), (True, None)):
+        if env is None:
+            monkeypatch.delenv("SED_FE_MOMENTS", raising=False)
+        else:
+            monkeypatch.setenv("SED_FE_MOMENTS", env)
+        np.random.seed(2024)
+        st, s, t = _mt_step(rs, mfma_dtype="f16")
+        fe = ResidentFrontEnd(st, rs, overlap=overlap)
+        assert fe.overlap == overlap and fe.moments == (env is None)
+        post = []
+        for _ in range(7):
+            fe.run()
+            post.append((st.strong.clone(), st.weak.clone()))
+        torch.cuda.synchronize()
+        out.append(post)
+    for k, ((s0, w0), (s1, w1)) in enumerate(zip(*out)):
+        es, ew = float((s0 - s1).abs().max()), float((w0 - w1).abs().max())
+        print(f"[resident f16] step {k}: overlap + moments against serial without: strong {es:.2e} weak {ew:.2e}")
+        assert torch.isfinite(s1).all() and es < 2 * F16_POST_TOL and ew < 2 * F16_POST_TOL, (k, es, ew)
 
 
 def test_resident_feeding_equals_host_feeding():
