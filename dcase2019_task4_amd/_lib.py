@@ -122,6 +122,8 @@ _SIGS = {
     "sed_logmel_transform": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, C.c_size_t, C.c_int, _P]),
     "sed_gather_logmel_transform": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P,
                                               _P, C.c_int, _P, _P, C.c_size_t, C.c_int, _P]),
+    "sed_gather_window_logmel_transform": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P,
+                                                     _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, C.c_int, _P]),
     "sed_batch_augment": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "sed_selftest": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "sed_debug_set": (C.c_int, [C.c_int]),

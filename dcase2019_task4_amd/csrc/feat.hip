@@ -695,7 +695,8 @@ __device__ __forceinline__ double amp_db(double a) {
 // No atomics, no initialisation, fixed reduction order: bit-reproducible.
 // Both passes read their input through an addressing policy P - where clip c's linear mel starts, how many frames it has,
 // which noise counter its element 0 draws - so the dense batch (sed_logmel_transform) and the gather from a resident pool
-// (sed_gather_logmel_transform) share every line of the arithmetic.
+// (sed_gather_logmel_transform) share every line of the arithmetic - and so does the gather of windows that start inside a
+// pool item (sed_gather_window_logmel_transform, LmWindow).
 #define LM_CHUNKS 16
 struct LmDense {                 // clip c = rows [c * frames, (c + 1) * frames) of a dense [n_clips][frames][n_mels] batch
     const float* mel;
@@ -724,6 +725,43 @@ struct LmGather {                // clip c = pool clip idx[c] (any length); coun
         const float* s = tgt_pool + (size_t)idx[c] * tgt_elems;
         float* d = tgt_out + (size_t)c * tgt_elems;
         for (int j = chunk * 256 + tid; j < tgt_elems; j += LM_CHUNKS * 256) d[j] = s[j];
+    }
+};
+struct LmWindow {                // clip c = frames [s, s + n) of pool item win[c][0]: s = win[c][1] * pool_ratio, n = min(max_frames, L - s)
+    const float* pool;
+    const int64_t* offset;       // [n_pool] first frame of each item in the pool
+    const int32_t* frames;       // [n_pool] L
+    const int32_t* win;          // [B][2] = {item, start3}; clamped HERE, so no table content leaves the pool or the label pool
+    int n_pool, n_mels, max_frames, pool_ratio;
+    size_t stride;               // S = max_win_frames * n_mels
+    const float* lab_pool;       // every item's label timeline, concatenated along rows, or NULL
+    const int64_t* lab_offset;   // [n_pool] first row of each item's timeline
+    const int32_t* lab_rows;     // [n_pool]
+    float* tgt_out;              // [B][T3][nclass]
+    int tgt_elems, nclass;       // T3 * nclass
+    __device__ __forceinline__ int item(int c) const { return min(max(win[2 * c], 0), n_pool - 1); }
+    // start3 in [0, (L - 1) / pool_ratio]: the window's first frame s is a real frame of the item
+    __device__ __forceinline__ int start3(int c, int i) const { return min(max(win[2 * c + 1], 0), max(frames[i] - 1, 0) / pool_ratio); }
+    __device__ __forceinline__ const float* src(int c) const {
+        const int i = item(c);
+        return pool + ((size_t)offset[i] + (size_t)start3(c, i) * pool_ratio) * n_mels;
+    }
+    __device__ __forceinline__ int len(int c) const {
+        const int i = item(c);
+        return max(min(max_frames, frames[i] - start3(c, i) * pool_ratio), 0);
+    }
+    __device__ __forceinline__ size_t noise_base(int c) const { return (size_t)c * stride; }
+    // rows [start3, start3 + T3) of the item's timeline, 0.0f past its last row.  The window's rows are contiguous in the label
+    // pool, so element j of the output is element j of the source and whole rows are valid or not: one bound, no division.
+    // Plain 4-byte accesses: a window holds T3 * nclass floats (780 at the defaults), and the source starts at row
+    // lab_offset + start3 of nclass floats - 16-byte aligned only when that product is a multiple of 4, which no table promises.
+    __device__ __forceinline__ void copy_target(int c, int chunk, int tid) const {
+        if (!lab_pool) return;
+        const int i = item(c), s3 = start3(c, i);
+        const int n_valid = (int)min(max((int64_t)lab_rows[i] - s3, (int64_t)0) * nclass, (int64_t)tgt_elems);
+        const float* s = lab_pool + ((size_t)lab_offset[i] + s3) * nclass;
+        float* d = tgt_out + (size_t)c * tgt_elems;
+        for (int j = chunk * 256 + tid; j < tgt_elems; j += LM_CHUNKS * 256) d[j] = j < n_valid ? s[j] : 0.0f;
     }
 };
 
@@ -990,6 +1028,34 @@ extern "C" int sed_gather_logmel_transform(const float* pool, const int64_t* cli
         return SED_ERR_WORKSPACE;
     }
     const LmGather p{pool, clip_offset, clip_frames, idx, n_mels, (size_t)max_clip_frames * n_mels, tgt_pool, out_target, tgt_elems};
+    return launch_logmel(p, B, n_mels, max_frames, mean, std, seed_dev, out_clean, out_noisy, ws, math_dtype, (hipStream_t)stream);
+}
+
+extern "C" int sed_gather_window_logmel_transform(const float* pool, const int64_t* clip_offset, const int32_t* clip_frames,
+                                                  int n_pool, int max_win_frames, const int32_t* win, int B, int n_mels,
+                                                  int max_frames, int pool_ratio, const double* mean, const double* std,
+                                                  const uint64_t* seed_dev, float* out_clean, float* out_noisy,
+                                                  const float* label_pool, const int64_t* label_offset, const int32_t* label_rows,
+                                                  int T3, int nclass, float* out_target, void* ws, size_t ws_bytes, int math_dtype,
+                                                  void* stream) {
+    SED_CHECK_ARG(math_dtype == SED_FFT_F64 || math_dtype == SED_FFT_F32, "sed_gather_window_logmel_transform: math_dtype must be SED_FFT_F64 or SED_FFT_F32");
+    SED_CHECK_ARG(pool && clip_offset && clip_frames && win && out_clean, "sed_gather_window_logmel_transform: null argument");
+    SED_CHECK_ARG((mean == nullptr) == (std == nullptr), "sed_gather_window_logmel_transform: mean and std go together");
+    SED_CHECK_ARG(!out_noisy || seed_dev, "sed_gather_window_logmel_transform: noise requested but seed_dev is null");
+    const int n_lab = (label_pool != nullptr) + (label_offset != nullptr) + (label_rows != nullptr) + (out_target != nullptr);
+    SED_CHECK_ARG(n_lab == 0 || n_lab == 4, "sed_gather_window_logmel_transform: label_pool, label_offset, label_rows and out_target go together");
+    SED_CHECK_ARG(n_lab == 0 || (T3 >= 1 && nclass >= 1 && (int64_t)T3 * nclass < (1ll << 31)), "sed_gather_window_logmel_transform: bad target sizes");
+    SED_CHECK_ARG(n_pool >= 1 && max_win_frames >= 1 && B >= 1 && n_mels >= 1 && max_frames >= 1, "sed_gather_window_logmel_transform: bad sizes");
+    SED_CHECK_ARG(pool_ratio >= 1, "sed_gather_window_logmel_transform: pool_ratio < 1");
+    SED_CHECK_ARG((int64_t)max_frames * n_mels < (1ll << 31), "sed_gather_window_logmel_transform: window too long");
+    SED_CHECK_ARG((int64_t)B * max_win_frames * n_mels < (1ll << 32), "sed_gather_window_logmel_transform: too many elements for the noise stream");
+    SED_CHECK_ARG(ws != nullptr, "sed_gather_window_logmel_transform: null workspace");
+    if (ws_bytes < sed_logmel_transform_ws_bytes(B)) {
+        sed_set_error("sed_gather_window_logmel_transform: workspace has %zu bytes, needs %zu", ws_bytes, sed_logmel_transform_ws_bytes(B));
+        return SED_ERR_WORKSPACE;
+    }
+    const LmWindow p{pool, clip_offset, clip_frames, win, n_pool, n_mels, max_frames, pool_ratio, (size_t)max_win_frames * n_mels,
+                     label_pool, label_offset, label_rows, out_target, n_lab ? T3 * nclass : 0, nclass};
     return launch_logmel(p, B, n_mels, max_frames, mean, std, seed_dev, out_clean, out_noisy, ws, math_dtype, (hipStream_t)stream);
 }
 

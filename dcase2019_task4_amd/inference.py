@@ -10,8 +10,9 @@ Recordings longer than one clip: ``LongRecordingSet`` (longrec.py) holds them as
 ``get_long_predictions`` blends the windows' posteriors and decodes each recording's whole timeline with one
 ``sed_stitch_decode`` call.  The device-resident event table it leaves is scored by ``metrics.long_event_counts`` /
 ``long_psds_counts`` / ``validate_long`` (``sed_long_event_counts``, ``sed_long_psds_counts``: columns of any length).
-``stitch_sweep`` decodes K operating points from one blend (``sed_stitch_sweep``), scored by ``metrics.long_sweep_*``.  Out of
-scope there: recording-level weak tags and windows for training.  ``get_predictions`` itself is unchanged.
+``stitch_sweep`` decodes K operating points from one blend (``sed_stitch_sweep``), scored by ``metrics.long_sweep_*``.
+Training on windows of such recordings is ``WindowedFeatureSet`` (longrec.py, through ``train.train``).  Out of scope
+there: recording-level weak tags.  ``get_predictions`` itself is unchanged.
 """
 import ctypes as C
 
@@ -20,8 +21,8 @@ import pandas as pd
 import torch
 
 from . import _lib
-from .longrec import (WEIGHTINGS, LongRecordingSet, check_hop_frames, default_hop_frames, sweep_chunks,      # noqa: F401
-                      window_plan)
+from .longrec import (WEIGHTINGS, LongRecordingSet, WindowedFeatureSet, check_hop_frames, default_hop_frames,      # noqa: F401
+                      encode_timeline, sweep_chunks, window_plan)
 
 
 class _Cfg:

@@ -7,11 +7,16 @@ frames, ``hop_frames`` apart; every window goes through the eval forward as a cl
 clips from a pool by arbitrary offset and length, so overlapping windows are overlapping clips of a ``ResidentFeatureSet``
 whose clip tables point into the recordings.  The dB clamp is per window, as for a clip of its own: a window's input is
 byte for byte what the same frames give as a clip, whatever else the recording holds.
+
+Training on such recordings is ``WindowedFeatureSet``: the recordings and their label timelines stay in HBM once, a batch
+position is a window ``(item, start label frame)`` gathered - features and sliced labels - by
+``sed_gather_window_logmel_transform``, with a fixed number of windows per recording and epoch and fresh crop starts per epoch.
 """
 import numpy as np
 import torch
 
 from . import _lib
+from .augment import AugmentPolicy
 from .resident import ResidentFeatureSet
 
 WEIGHTINGS = {"uniform": 0, "taper": 1}
@@ -160,3 +165,214 @@ class LongRecordingSet(ResidentFeatureSet):
         if cfg is None:
             from .inference import _Cfg as cfg
         return np.diff(self.rec_frame0_host) * self.pooling_time_ratio / (cfg.sample_rate / cfg.hop_length)
+
+
+def encode_timeline(events_of_file, n_rows, class_labels, cfg, pooling_time_ratio=8):
+    """The label timeline [n_rows, nclass] float32 of one strongly labelled file - what the reference does to it, on a
+    timeline of any length: onsets / offsets in seconds become label frames by
+    ``x * cfg.sample_rate // cfg.hop_length // pooling_time_ratio`` (main.py:227-228: float floor division twice, then
+    ``int()``), ``y[onset:offset, class] = 1`` with the offset row excluded and rows beyond the timeline dropped
+    (utils.py:92-94), NaN labels skipped.  ``events_of_file``: a DataFrame with onset, offset, event_label columns, or an
+    iterable of (onset, offset, event_label)."""
+    labels = list(class_labels)
+    y = np.zeros((int(n_rows), len(labels)), dtype=np.float32)
+    if hasattr(events_of_file, "itertuples"):
+        events_of_file = zip(events_of_file["onset"], events_of_file["offset"], events_of_file["event_label"])
+    for onset, offset, label in events_of_file:
+        if label is None or label != label:                    # NaN: a file without events
+            continue
+        on = int(float(onset) * cfg.sample_rate // cfg.hop_length // pooling_time_ratio)
+        off = int(float(offset) * cfg.sample_rate // cfg.hop_length // pooling_time_ratio)
+        y[on:off, labels.index(label)] = 1
+    return y
+
+
+SAMPLINGS = ("random", "grid")
+
+
+class WindowedFeatureSet(ResidentFeatureSet):
+    """A training set whose pool items may be recordings longer than one clip: every batch position is a WINDOW
+    ``(item, start3)`` of ``frames`` feature frames starting at label frame ``start3`` of the item, its target sliced from the
+    item's label timeline by the same launch (``sed_gather_window_logmel_transform``).  Features and timelines are uploaded
+    once; fresh crops per epoch cost one small table.
+
+    Per stream, ``windowed`` says how its items are used.  A non-windowed stream behaves as a ``ResidentFeatureSet``'s: one
+    window at ``start3 = 0`` per item (truncated, padded or exactly ``frames``).  In a windowed stream item i contributes
+    ``n_w(i) = window_plan(L_i, frames, pool, hop3)["n_w"]`` windows every epoch - as many as ``LongRecordingSet`` infers it
+    with - so stream sizes, ``n_steps``, ``rampup_length`` and ``global_step`` are constants of the run.  With
+    ``L3 = max(1, L_i // pool)`` and ``hi = max(0, L3 - T3)``, window j of the item starts at
+      ``sampling="grid"``    ``min(j * hop3, hi)``, the same in every epoch;
+      ``sampling="random"``  an integer uniform on ``[0, hi]``: ``np.random.default_rng([seed, epoch])`` draws ``n_w(i)`` of
+                             them per windowed item, in item order, identically on every rank.
+    An item with ``L3 >= T3`` therefore never yields a window with padded label frames.  The stream permutations come from
+    numpy's GLOBAL generator exactly as ``ResidentFeatureSet.epoch_rows`` draws them (over the streams' window slots; slot =
+    item in a non-windowed stream): random crops never change the number of global draws.
+
+    Not provided: ``from_waveforms``, crop starts finer than one label frame, event-aware (class-balanced) crop sampling,
+    recording-level weak tags."""
+
+    row_shape = (2,)
+
+    @classmethod
+    def from_arrays(cls, features, labels, stream_sizes, batch_sizes, frames, windowed, pooling_time_ratio=8, hop_frames=None,
+                    sampling="random", scaler=None, augment_type="noise", device="cuda", process_group=None, math_dtype="f64",
+                    seed=0, augment=None):
+        """``features[i]``: [L_i, n_mels], any L_i >= 1; ``labels[i]``: [R_i, nclass] float32, any R_i >= 1 - the label
+        timeline of the whole item at label-frame rate (rows a window reaches beyond R_i are 0); ``windowed``: one bool per
+        stream; ``hop_frames``: as ``LongRecordingSet`` (it only sets how many windows an item contributes, and the grid)."""
+        self = cls.__new__(cls)
+        feats, labels, sizes = list(features), list(labels), [int(s) for s in stream_sizes]
+        if sampling not in SAMPLINGS:
+            raise ValueError(f"sampling must be one of {SAMPLINGS}, got {sampling!r}")
+        if len(labels) != len(feats):
+            raise ValueError(f"{len(labels)} label timelines for {len(feats)} items")
+        windowed = [bool(w) for w in windowed]
+        if len(windowed) != len(sizes):
+            raise ValueError(f"windowed has {len(windowed)} entries for {len(sizes)} streams")
+        if batch_sizes is None:
+            raise ValueError("a WindowedFeatureSet is a training set: it needs batch sizes")
+        if augment is not None and not isinstance(augment, AugmentPolicy):
+            raise TypeError(f"augment must be an AugmentPolicy or None, got {type(augment).__name__}")
+        pool = int(pooling_time_ratio)
+        hop = check_hop_frames(hop_frames, frames, pool)
+        # the pool, the scaler and the rank come from the base class (built as a gather-only set; the batch layout follows)
+        self._setup(feats, None, sizes, None, frames, scaler, augment_type, device, process_group, math_dtype, seed)
+        self.augment = augment
+        self.pooling_time_ratio, self.hop_frames, self.hop3, self.T3 = pool, hop, hop // pool, self.frames // pool
+        self.sampling, self.windowed = sampling, windowed
+        self.max_win_frames = min(self.frames, self.max_clip_frames)
+        # the label pool: timelines concatenated along rows
+        labels = [np.asarray(y, dtype=np.float32) for y in labels]
+        nclass = labels[0].shape[1] if labels[0].ndim == 2 else -1
+        for i, y in enumerate(labels):
+            if y.ndim != 2 or y.shape[1] != nclass or y.shape[0] < 1:
+                raise ValueError(f"item {i}: labels of shape {y.shape}, expected [rows >= 1, {nclass}]")
+        rows = np.array([y.shape[0] for y in labels], dtype=np.int64)
+        self.nclass = int(nclass)
+        self.label_rows_host = rows.astype(np.int32)
+        self.label_offset_host = np.concatenate([[0], np.cumsum(rows)[:-1]]).astype(np.int64)
+        self.label_pool = torch.from_numpy(np.concatenate(labels, axis=0)).to(self.device)
+        self.label_offset = torch.from_numpy(self.label_offset_host).to(self.device)
+        self.label_rows = torch.from_numpy(self.label_rows_host).to(self.device)
+        self.target_shape = (self.T3, self.nclass)
+        # the window slots: (item, j) for j < n_w(item) in a windowed stream, (item, 0) otherwise - in item order
+        L = self.clip_frames_host.astype(np.int64)
+        self.start_hi_host = np.maximum(0, np.maximum(1, L // pool) - self.T3)
+        in_windowed = np.repeat(np.array(windowed, dtype=bool), sizes)
+        self.n_w_host = np.array([window_plan(l, self.frames, pool, self.hop3)["n_w"] if w else 1
+                                  for l, w in zip(L, in_windowed)], dtype=np.int64)
+        self.item_windowed = in_windowed
+        self.slot_item = np.repeat(np.arange(self.n_clips, dtype=np.int64), self.n_w_host)
+        self.slot_j = np.concatenate([np.arange(n, dtype=np.int64) for n in self.n_w_host])
+        ends = np.cumsum(sizes)
+        self.window_stream_sizes = [int(self.n_w_host[lo:hi].sum()) for lo, hi in zip(np.r_[0, ends[:-1]], ends)]
+        self._set_batches(self.window_stream_sizes, batch_sizes)
+        return self
+
+    @classmethod
+    def from_events(cls, features, events, filenames, class_labels, cfg, stream_sizes, batch_sizes, frames, windowed,
+                    pooling_time_ratio=8, **kwargs):
+        """Strongly labelled items: ``events`` is the reference's strong DataFrame (filename, onset, offset in SECONDS,
+        event_label), ``filenames[i]`` names item i; every item's timeline has its ``L3 = max(1, L_i // pool)`` rows
+        (``encode_timeline``).  The other arguments are ``from_arrays``'s."""
+        feats = list(features)
+        if len(filenames) != len(feats):
+            raise ValueError(f"{len(filenames)} filenames for {len(feats)} items")
+        by_file = {k: v for k, v in events.groupby("filename")}
+        empty = events.iloc[:0]
+        labels = [encode_timeline(by_file.get(name, empty), max(1, int(np.shape(f)[0]) // int(pooling_time_ratio)), class_labels,
+                                  cfg, pooling_time_ratio) for f, name in zip(feats, filenames)]
+        self = cls.from_arrays(feats, labels, stream_sizes, batch_sizes, frames, windowed, pooling_time_ratio, **kwargs)
+        self.filenames = list(filenames)
+        return self
+
+    # ---- epoch tables --------------------------------------------------------------------------------------------------------
+    def slot_starts(self, epoch):
+        """start3 of every window slot in epoch ``epoch`` [n_slots] int64 (the same on every rank)."""
+        hi = self.start_hi_host[self.slot_item]
+        if self.sampling == "grid":
+            return np.minimum(self.slot_j * self.hop3, hi)
+        rng = np.random.default_rng([self.seed, int(epoch)])
+        start = np.zeros(len(self.slot_item), dtype=np.int64)
+        first = np.concatenate([[0], np.cumsum(self.n_w_host)[:-1]])
+        for i in np.flatnonzero(self.item_windowed):
+            start[first[i]:first[i] + self.n_w_host[i]] = rng.integers(0, self.start_hi_host[i] + 1, size=self.n_w_host[i])
+        return start
+
+    def epoch_windows(self, epoch, rng=None):
+        """One epoch of GLOBAL batches [n_steps, sum(batch_sizes), 2] int64 = (item, start3): the stream permutations of
+        ``epoch_rows`` over the window slots (from ``rng``, default numpy's global generator), the starts of ``epoch``."""
+        rng = np.random if rng is None else rng
+        parts, lo = [], 0
+        for size, b in zip(self.window_stream_sizes, self.batch_sizes):
+            perm = np.asarray(rng.permutation(range(lo, lo + size)), dtype=np.int64)
+            parts.append(perm[:(size // b) * b].reshape(-1, b)[:self.n_steps])
+            lo += size
+        slots = np.concatenate(parts, axis=1)
+        return np.stack([self.slot_item[slots], self.slot_starts(epoch)[slots]], axis=-1)
+
+    def epoch_rows(self, rng=None):
+        raise ValueError("a WindowedFeatureSet's epochs are tables of windows: epoch_windows(epoch, rng)")
+
+    def check_windows(self, win):
+        """``win`` [..., 2] as int64, every row checked: 0 <= item < n_items and 0 <= start3 * pool < L_item."""
+        w = np.asarray(win, dtype=np.int64)
+        if w.ndim < 1 or w.shape[-1] != 2 or w.size == 0:
+            raise _lib.SedError(f"a window table is [..., 2] = (item, start3), got shape {w.shape}")
+        item, start = w[..., 0], w[..., 1]
+        if item.min() < 0 or item.max() >= self.n_clips:
+            raise _lib.SedError(f"window table holds an item outside [0, {self.n_clips})")
+        if start.min() < 0 or (start * self.pooling_time_ratio >= self.clip_frames_host[item]).any():
+            raise _lib.SedError("window table holds a start outside its item")
+        return w
+
+    def epoch_table(self, epoch, rng=None):
+        """This rank's share of epoch ``epoch`` [n_steps, batch, 2] as int32, every row checked (``check_windows``)."""
+        t = self.check_windows(self.local_rows(self.epoch_windows(epoch, rng)))
+        return np.ascontiguousarray(t, dtype=np.int32)
+
+    def draw_table(self, epoch, rng=None):
+        return self.epoch_table(epoch, rng)
+
+    # ---- the gather ----------------------------------------------------------------------------------------------------------
+    def gather(self, win, out_clean, out_noisy=None, key=None, out_target=None, ws=None):
+        """Windows ``win`` (device int32 [B, 2] = (item, start3), validated by the caller) -> out_clean [B, 1, frames, n_mels]
+        (+ out_noisy with the teacher's noise of the device key ``key``, + out_target [B, T3, nclass]) on the current stream."""
+        if not torch.is_tensor(win) or win.dim() != 2 or win.shape[1] != 2 or win.dtype != torch.int32 or not win.is_contiguous():
+            raise _lib.SedError("WindowedFeatureSet.gather takes a contiguous int32 [B, 2] table of (item, start3) windows, not "
+                                "clip indices: its items are not clips")
+        if self.device.type != "cuda":
+            raise _lib.SedError("WindowedFeatureSet.gather needs the set on a GPU device (no CPU fallback)")
+        B = win.shape[0]
+        l = _lib.lib()
+        if ws is None:
+            ws = torch.empty(l.sed_logmel_transform_ws_bytes(B), device=self.device, dtype=torch.uint8)
+        lab = out_target is not None
+        _lib.check(l.sed_gather_window_logmel_transform(
+            _lib.ptr(self.pool), _lib.ptr(self.clip_offset), _lib.ptr(self.clip_frames), self.n_clips, self.max_win_frames,
+            _lib.ptr(win), B, self.n_mels, self.frames, self.pooling_time_ratio, _lib.ptr(self.mean), _lib.ptr(self.std),
+            _lib.ptr(key), _lib.ptr(out_clean), _lib.ptr(out_noisy), _lib.ptr(self.label_pool) if lab else None,
+            _lib.ptr(self.label_offset) if lab else None, _lib.ptr(self.label_rows) if lab else None, self.T3, self.nclass,
+            _lib.ptr(out_target), _lib.ptr(ws), ws.numel(), self.math_dtype, _lib.stream_ptr()),
+            "sed_gather_window_logmel_transform")
+
+    def transform(self, windows, seed=None):
+        """Convenience (tests, tools): host windows [[item, start3], ...] -> (clean[, noisy], target) as new device tensors;
+        ``seed`` is the Philox key of the teacher's noise (a set built with augment_type='noise' requires it)."""
+        w = self.check_windows(np.asarray(windows, dtype=np.int64).reshape(-1, 2))
+        win = torch.from_numpy(w.astype(np.int32)).to(self.device)
+        B = win.shape[0]
+        clean = torch.empty(B, 1, self.frames, self.n_mels, device=self.device, dtype=torch.float32)
+        noisy = key = None
+        if self.noise:
+            if seed is None:
+                raise ValueError("a set with augment_type='noise' needs a seed")
+            noisy = torch.empty_like(clean)
+            key = torch.tensor([int(seed)], dtype=torch.int64, device=self.device)
+        tgt = torch.empty((B,) + self.target_shape, device=self.device, dtype=torch.float32)
+        self.gather(win, clean, noisy, key, tgt)
+        return ((clean, noisy) if self.noise else (clean,)) + (tgt,)
+
+    def eval_batch(self, i0, n):
+        raise _lib.SedError("a WindowedFeatureSet is a training set of windows: eval_batch would address its items as clips "
+                            "(infer long recordings with LongRecordingSet)")

@@ -180,6 +180,11 @@ class ResidentFeatureSet:
         if process_group is not None:
             import torch.distributed as dist
             self.world, self.rank = dist.get_world_size(process_group), dist.get_rank(process_group)
+        self._set_batches(sizes, batch_sizes)
+
+    def _set_batches(self, sizes, batch_sizes):
+        """The batch layout of a training set whose streams hold ``sizes`` entries (clips here; a subclass may count
+        something else); ``batch_sizes`` None: a set for gather / evaluation only."""
         self.batch_sizes = None
         self.n_steps = None
         if batch_sizes is not None:
@@ -193,7 +198,7 @@ class ResidentFeatureSet:
             self.n_steps = min(s // b for s, b in zip(sizes, bs))
             if self.n_steps < 1:
                 raise ValueError(f"a stream has fewer clips than its batch size: {sizes} / {bs}")
-            if self.targets is None:
+            if self.target_shape is None:
                 raise ValueError("a training set needs targets")
             self.batch = sum(bs) // self.world
             self.weak_mask, self.strong_mask = sdist.local_masks(bs, self.world)
@@ -237,6 +242,13 @@ class ResidentFeatureSet:
         if t.size and (t.min() < 0 or t.max() >= self.n_clips):
             raise _lib.SedError(f"epoch table holds an index outside [0, {self.n_clips})")
         return np.ascontiguousarray(t, dtype=np.int32)
+
+    row_shape = ()               # what one batch position of a table row holds: a clip index
+
+    def draw_table(self, epoch, rng=None):
+        """What ResidentFrontEnd uploads for the ``epoch``-th epoch it draws, [n_steps, batch, *row_shape] int32.  Clip
+        tables do not depend on the epoch number."""
+        return self.epoch_table(rng)
 
     def augment_table(self, epoch):
         """This rank's augmentation rows of epoch ``epoch`` (0-based count of drawn epochs) [n_steps, batch, 8] int32, from
@@ -302,7 +314,8 @@ class ResidentFrontEnd(OneBatchAheadFrontEnd):
 
     ``run()`` trains on the next batch of the epoch sequence and gathers the one after it; the sequence runs on across epochs
     (epoch e's table is drawn when its predecessor's first batch is staged).  ``aug_epoch``: the epoch index the set's
-    augmentation policy is asked for when this front-end draws its first table (0; a resumed run passes its epoch)."""
+    augmentation policy - and a WindowedFeatureSet's crop generator - is asked for when this front-end draws its first table
+    (0; a resumed run passes its epoch)."""
 
     def __init__(self, step, rset, overlap=True, seed=None, rng=None, aug_epoch=0):
         if rset.batch_sizes is None:
@@ -318,9 +331,10 @@ class ResidentFrontEnd(OneBatchAheadFrontEnd):
         self.rs = rset
         self.rng = np.random if rng is None else rng
         dev = step.device
-        self.idx = torch.zeros(step.B, device=dev, dtype=torch.int32)          # the batch the next extraction gathers
+        # the batch the next extraction gathers: one table row, [B] clip indices (a WindowedFeatureSet: [B, 2] windows)
+        self.idx = torch.zeros((step.B,) + rset.row_shape, device=dev, dtype=torch.int32)
         self.ws_t = torch.empty(self.l.sed_logmel_transform_ws_bytes(step.B), device=dev, dtype=torch.uint8)
-        self._tables = [torch.empty(rset.n_steps, step.B, device=dev, dtype=torch.int32) for _ in range(2)]
+        self._tables = [torch.empty((rset.n_steps, step.B) + rset.row_shape, device=dev, dtype=torch.int32) for _ in range(2)]
         self._drawn = 0                                # epochs whose table has been drawn
         self._epoch, self._pos = 0, 0                  # the batch the next _stage() puts into self.idx
         self.host_tables = {}                          # epoch -> the host table (kept for the two live epochs)
@@ -341,7 +355,7 @@ class ResidentFrontEnd(OneBatchAheadFrontEnd):
 
     def _draw(self, e):
         while self._drawn <= e:
-            t = self.rs.epoch_table(self.rng)
+            t = self.rs.draw_table(self.aug_epoch + self._drawn, self.rng)
             self.host_tables[self._drawn] = t
             self.host_tables.pop(self._drawn - 2, None)
             # stream order: every row copy of the epoch that used this buffer before was enqueued earlier on this stream

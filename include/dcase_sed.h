@@ -390,6 +390,36 @@ int sed_gather_logmel_transform(const float* pool, const int64_t* clip_offset, c
                                 const double* mean, const double* std, const uint64_t* seed_dev, float* out_clean,
                                 float* out_noisy, const float* tgt_pool, int tgt_elems, float* out_target, void* ws,
                                 size_t ws_bytes, int math_dtype, void* stream);
+/* sed_gather_window_logmel_transform: the same transform chain on B WINDOWS that start inside pool items (training on
+ * recordings longer than one clip: crops of `max_frames` feature frames, their labels sliced from the item's timeline).
+ *   pool, clip_offset, clip_frames, n_pool   as above: item i = frames [clip_offset[i], clip_offset[i] + clip_frames[i])
+ *   win [B][2]  device int32 {item, start3}.  Window b is item i = win[b][0], feature frames [s, s + n) with
+ *               s = win[b][1] * pool_ratio and n = min(max_frames, clip_frames[i] - s).  Everything
+ *               sed_gather_logmel_transform does to a clip is done to these n frames: the top_db clamp is taken over the
+ *               window's own real frames (no frame outside it changes a byte), padding is 0 dB after the log, then the
+ *               normalisation - bit for bit what the same frames give as a pool clip of their own
+ *   max_win_frames  noise counters of batch position b, element e are b * S + e with S = max_win_frames * n_mels; the
+ *               caller gives max_win_frames >= min(max_frames, longest item) (with every window full: sed_logmel_transform's
+ *               layout)
+ *   label_pool  every item's label timeline [label_rows[i]][nclass] fp32 at label-frame rate, concatenated along rows from
+ *               row label_offset[i] (int64);
+ *               out_target[b][u][c] = label_pool[(label_offset[i] + start3 + u) * nclass + c]  for start3 + u < label_rows[i],
+ *                                   = 0.0f beyond.  Values are copied exactly (soft labels, the unlabelled stream's -1).
+ *               label_pool, label_offset, label_rows, out_target: all NULL (no targets) or all non-NULL
+ *   safety      inside the kernel item is clamped to [0, n_pool) and start3 so that s is in [0, clip_frames[i] - 1]: no
+ *               table content can address outside the pool or the label pool (the caller still validates its tables - a
+ *               clamped row is a wrong batch, not a fault)
+ *   mean/std, seed_dev, out_clean, out_noisy (NULL: no noise), ws = sed_logmel_transform_ws_bytes(B), math_dtype: as
+ *               sed_logmel_transform.  Limits: pool_ratio >= 1, max_frames * n_mels < 2^31, T3 * nclass < 2^31,
+ *               B * max_win_frames * n_mels < 2^32.  Two launches on `stream`, no allocation, no atomics, no host
+ *               synchronisation, hipGraph-capturable.
+ * Not provided: crop starts finer than one label frame.                                                                   */
+int sed_gather_window_logmel_transform(const float* pool, const int64_t* clip_offset, const int32_t* clip_frames, int n_pool,
+                                       int max_win_frames, const int32_t* win, int B, int n_mels, int max_frames,
+                                       int pool_ratio, const double* mean, const double* std, const uint64_t* seed_dev,
+                                       float* out_clean, float* out_noisy, const float* label_pool,
+                                       const int64_t* label_offset, const int32_t* label_rows, int T3, int nclass,
+                                       float* out_target, void* ws, size_t ws_bytes, int math_dtype, void* stream);
 
 /* ---- train-time batch augmentation -------------------------------------------------------------
  * Mixup of features and targets, a circular time shift of features and strong targets, and SpecAugment-style time /
