@@ -89,28 +89,42 @@ struct ParamOff {
 };
 ParamOff make_param_off(const Geo& g, int64_t* offsets_out /* may be null */);
 
-// saved-context layout (byte offsets)
+// One region of a buffer layout: where it starts and how many bytes the layout gave it.  Sizes are stated where the layout is
+// built and read from here by everything else (the buffer views, the memsets, RnnBufs::n_zero).
+struct Region {
+    size_t off = 0, bytes = 0;
+    void* v(void* base) const { return (char*)base + off; }
+    float* f(void* base) const { return (float*)v(base); }
+    double* d(void* base) const { return (double*)v(base); }
+    uint16_t* m(void* base) const { return (uint16_t*)v(base); }      // dropout keep bits
+    Region sub(size_t first, size_t n) const { return Region{off + first, n}; }
+};
+// the `put` of every layout: the next 256-byte-aligned region of `bytes` bytes
+struct RegionCursor {
+    size_t o = 0;
+    void operator()(Region& r, size_t bytes) { r = Region{o, bytes}; o = (o + bytes + 255) & ~(size_t)255; }
+};
+
+// saved-context layout; per-block members are indexed by conv block (0: only bn, p, mask)
 struct CtxLayout {
-    size_t acc0;                       // mom0 | stat1 | stat2 contiguous (320 doubles, zeroed by ONE memset)
-    size_t mom0, wz0, wl0, bn0;        // bn0: mean,invstd,scale,shift [4][64]
-    size_t mompart;                    // per-workgroup partial patch moments [parts][54] fp64
-    size_t wpkT1, wpkT2;               // flipped/transposed conv weights for dgrad (train only)
-    size_t p0;
-    size_t wpk1, y1, stat1, bn1, p1;
-    size_t wpk2, y2, stat2, bn2, p2;
-    size_t gates[2], out[2];
-    size_t logits_s, strong_sv, weak_sv, den_sv;
-    size_t mask0, mask1, mask2;        // 16 dropout keep bits per (row block, half, lane), written by forward
+    Region acc0;                       // mom0 | stat[1] | stat[2] contiguous (320 doubles, zeroed by ONE memset)
+    Region mom0, wz0, wl0;
+    Region mompart;                    // per-workgroup partial patch moments [parts][54] fp64
+    Region wpk[3], wpkT[3];            // packed conv weights; flipped/transposed for dgrad (train only)
+    Region y[3], stat[3], bn[3], p[3]; // bn: mean,invstd,scale,shift [4][64]
+    Region gates[2], out[2];
+    Region logits_s, strong_sv, weak_sv, den_sv;
+    Region mask[3];                    // 16 dropout keep bits per (row block, half, lane), written by forward
     size_t total;
 };
 CtxLayout make_ctx_layout(const Geo& g);
 
 struct WsLayout {
-    size_t d_out, dgi[2], dgh[2], hprev[2], d_in, heads_part;   // dgi/dgh/hprev per GRU layer (read by the side stream)
-    size_t dz2, dp1, dz1, dp0, dp2;
-    size_t bwd_acc;                    // gluacc1 | gluacc2 | de0 contiguous doubles, zeroed by ONE memset
-    size_t pad0;                       // 2 KiB that nothing reads (a removed BatchNorm-backward scratch): kept, the ws size must not move
-    size_t gluacc1, gluacc2, coef[3], wg_part, de0, gemm_part;   // coef per conv block (1, 2)
+    Region d_out, dgi[2], dgh[2], hprev[2], d_in, heads_part;   // dgi/dgh/hprev per GRU layer (read by the side stream)
+    Region dz[3], dp[3], coef[3];      // dp[i]: gradient w.r.t. block i's pooled output; dz / coef: blocks 1, 2
+    Region bwd_acc;                    // gluacc[1] | gluacc[2] | de0 contiguous doubles, zeroed by ONE memset
+    Region pad0;                       // 2 KiB that nothing reads (a removed BatchNorm-backward scratch): kept, the ws size must not move
+    Region gluacc[3], de0, wg_part, gemm_part;
     size_t total;
     int wgrad_blocks;
 };

@@ -81,49 +81,47 @@ ParamOff make_param_off(const Geo& g, int64_t* out) {
     return P;
 }
 
-static inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 CtxLayout make_ctx_layout(const Geo& g) {
     CtxLayout L;
-    size_t o = 0;
-    auto put = [&](size_t& f, size_t bytes) { f = o; o = al(o + bytes); };
-    const size_t n0 = (size_t)g.B * g.H1 * g.W1 * 64, n1 = (size_t)g.B * g.H2 * g.W2 * 64, n2 = (size_t)g.B * g.T3 * 64;
+    RegionCursor put;
+    const size_t px[4] = {0, (size_t)g.B * g.H1 * g.W1, (size_t)g.B * g.H2 * g.W2, (size_t)g.B * g.T3};      // pixels of block i's OUTPUT: px[i + 1]
     put(L.acc0, 320 * sizeof(double));
-    L.mom0 = L.acc0; L.stat1 = L.acc0 + 64 * sizeof(double); L.stat2 = L.acc0 + 192 * sizeof(double);
-    put(L.wz0, 64 * 12 * 4); put(L.wl0, 64 * 12 * 4); put(L.bn0, 256 * 4);
+    L.mom0 = L.acc0.sub(0, 64 * sizeof(double));
+    L.stat[1] = L.acc0.sub(64 * sizeof(double), 128 * sizeof(double)); L.stat[2] = L.acc0.sub(192 * sizeof(double), 128 * sizeof(double));
+    put(L.wz0, 64 * 12 * 4); put(L.wl0, 64 * 12 * 4); put(L.bn[0], 256 * 4);
     put(L.mompart, (size_t)x_moments_parts(g) * 54 * sizeof(double));
-    put(L.p0, n0 * 4);
-    put(L.wpk1, (9 + 16) * 4096 * 4); put(L.wpkT1, (9 + 16) * 4096 * 4); put(L.y1, n0 * 4); put(L.bn1, 256 * 4); put(L.p1, n1 * 4);
-    put(L.wpk2, (9 + 16) * 4096 * 4); put(L.wpkT2, (9 + 16) * 4096 * 4); put(L.y2, n1 * 4); put(L.bn2, 256 * 4); put(L.p2, n2 * 4);
+    put(L.p[0], px[1] * 64 * 4);
+    for (int i = 1; i <= 2; ++i) {
+        put(L.wpk[i], (9 + 16) * 4096 * 4); put(L.wpkT[i], (9 + 16) * 4096 * 4); put(L.y[i], px[i] * 64 * 4); put(L.bn[i], 256 * 4);
+        put(L.p[i], px[i + 1] * 64 * 4);
+    }
     const size_t bt = (size_t)g.B * g.T3;
     for (int l = 0; l < 2; ++l) {
         put(L.gates[l], bt * 512 * 4); put(L.out[l], bt * 128 * 4);      // (gi only exists in LDS, gru4.hip)
     }
     put(L.logits_s, bt * g.NC * 4); put(L.strong_sv, bt * g.NC * 4);
     put(L.weak_sv, (size_t)g.B * g.NC * 4); put(L.den_sv, (size_t)g.B * g.NC * 4);
-    auto mask_bytes = [](size_t Q) { return ((Q + 3) / 4) * 2 * 64 * sizeof(uint16_t); };
-    put(L.mask0, mask_bytes((size_t)g.B * g.H1 * g.W1)); put(L.mask1, mask_bytes((size_t)g.B * g.H2 * g.W2));
-    put(L.mask2, mask_bytes((size_t)g.B * g.T3));
-    L.total = o;
+    for (int i = 0; i < 3; ++i) put(L.mask[i], ((px[i + 1] + 3) / 4) * 2 * 64 * sizeof(uint16_t));
+    L.total = put.o;
     return L;
 }
 
 WsLayout make_ws_layout(const Geo& g) {
     WsLayout W;
-    size_t o = 0;
-    auto put = [&](size_t& f, size_t bytes) { f = o; o = al(o + bytes); };
+    RegionCursor put;
     const size_t n0 = (size_t)g.B * g.H1 * g.W1 * 64, n1 = (size_t)g.B * g.H2 * g.W2 * 64, bt = (size_t)g.B * g.T3;
     put(W.d_out, bt * 128 * 4);
     for (int l = 0; l < 2; ++l) { put(W.dgi[l], bt * 384 * 4); put(W.dgh[l], bt * 384 * 4); put(W.hprev[l], bt * 128 * 4); }
     put(W.d_in, 2 * bt * 128 * 4); put(W.heads_part, (size_t)g.B * 2 * (g.NC * 128 + g.NC) * 4);
-    put(W.dp2, 2 * bt * 64 * 4); put(W.dz2, n1 * 4); put(W.dp1, n1 * 4); put(W.dz1, n0 * 4); put(W.dp0, n0 * 4);
-    put(W.pad0, 256 * sizeof(double)); W.coef[0] = 0; put(W.coef[1], 192 * 4); put(W.coef[2], 192 * 4);
-    put(W.bwd_acc, (2 * SED_GLUACC_N + 2 * 64 * 10) * sizeof(double));
-    W.gluacc1 = W.bwd_acc; W.gluacc2 = W.bwd_acc + SED_GLUACC_N * sizeof(double); W.de0 = W.bwd_acc + 2 * SED_GLUACC_N * sizeof(double);
+    put(W.dp[2], 2 * bt * 64 * 4); put(W.dz[2], n1 * 4); put(W.dp[1], n1 * 4); put(W.dz[1], n0 * 4); put(W.dp[0], n0 * 4);
+    put(W.pad0, 256 * sizeof(double)); put(W.coef[1], 192 * 4); put(W.coef[2], 192 * 4);
+    const size_t glu = SED_GLUACC_N * sizeof(double);
+    put(W.bwd_acc, 2 * glu + 2 * 64 * 10 * sizeof(double));      // every fp64 accumulator of the conv-block backward
+    W.gluacc[1] = W.bwd_acc.sub(0, glu); W.gluacc[2] = W.bwd_acc.sub(glu, glu); W.de0 = W.bwd_acc.sub(2 * glu, 2 * 64 * 10 * sizeof(double));
     W.wgrad_blocks = SED_WGRAD_MAX_BLOCKS;
     put(W.wg_part, (size_t)W.wgrad_blocks * 9 * 4096 * 4);
     put(W.gemm_part, gemm_part_floats(4, SED_GRU_SPLITK, 192, 129) * 4);
-    W.total = o;
+    W.total = put.o;
     return W;
 }
 
@@ -163,17 +161,15 @@ extern "C" int sed_crnn_ctx_view(const sed_dims* d, const char* name, size_t* of
     const Geo g = make_geo(d);
     if (g.generic) return gen_ctx_view(g, name, offset, bytes);
     const CtxLayout L = make_ctx_layout(g);
-    const size_t n0 = (size_t)g.B * g.H1 * g.W1 * 64 * 4, n1 = (size_t)g.B * g.H2 * g.W2 * 64 * 4, bt = (size_t)g.B * g.T3;
-    struct { const char* n; size_t o, b; } tab[] = {
-        {"mom0", L.mom0, 64 * 8}, {"wz0", L.wz0, 64 * 12 * 4}, {"wl0", L.wl0, 64 * 12 * 4}, {"bn0", L.bn0, 1024},
-        {"p0", L.p0, n0}, {"y1", L.y1, n0}, {"stat1", L.stat1, 1024}, {"bn1", L.bn1, 1024}, {"p1", L.p1, n1},
-        {"y2", L.y2, n1}, {"stat2", L.stat2, 1024}, {"bn2", L.bn2, 1024}, {"p2", L.p2, bt * 64 * 4},
-        {"gates0", L.gates[0], bt * 512 * 4}, {"gates1", L.gates[1], bt * 512 * 4},
-        {"gru0", L.out[0], bt * 128 * 4}, {"gru1", L.out[1], bt * 128 * 4},
-        {"logits_s", L.logits_s, bt * g.NC * 4}, {"den", L.den_sv, (size_t)g.B * g.NC * 4},
+    struct { const char* n; Region r; } tab[] = {
+        {"mom0", L.mom0}, {"wz0", L.wz0}, {"wl0", L.wl0}, {"bn0", L.bn[0]},
+        {"p0", L.p[0]}, {"y1", L.y[1]}, {"stat1", L.stat[1]}, {"bn1", L.bn[1]}, {"p1", L.p[1]},
+        {"y2", L.y[2]}, {"stat2", L.stat[2]}, {"bn2", L.bn[2]}, {"p2", L.p[2]},
+        {"gates0", L.gates[0]}, {"gates1", L.gates[1]}, {"gru0", L.out[0]}, {"gru1", L.out[1]},
+        {"logits_s", L.logits_s}, {"den", L.den_sv},
     };
     for (auto& t : tab)
-        if (strcmp(t.n, name) == 0) { *offset = t.o; *bytes = t.b; return SED_OK; }
+        if (strcmp(t.n, name) == 0) { *offset = t.r.off; *bytes = t.r.bytes; return SED_OK; }
     sed_set_error("sed_crnn_ctx_view: unknown buffer '%s'", name);
     return SED_ERR_BAD_ARG;
 }
@@ -292,25 +288,82 @@ static SideFork side_fork(hipStream_t st) {
     return SideFork{ok ? sd.s : st, sd.fork, sd.join, ok, false};
 }
 
-#define CTXF(off) ((float*)((char*)ctx + (off)))
-#define CTXD(off) ((double*)((char*)ctx + (off)))
-#define WSF(off) ((float*)((char*)ws + (off)))
-#define WSD(off) ((double*)((char*)ws + (off)))
-#define CTXM(off) ((uint16_t*)((char*)ctx + (off)))
+// ---- one call of the specialised fp32 kernel set -------------------------------------------------------------------------
+// Each stage_* function below holds the ONE launch_* call of its stage, bound to the buffers of a Call.  sed_crnn_forward,
+// crnn_backward_impl and sed_kernel_replay are sequences of stage calls: what differs between them is an argument of the stage.
+struct Call {
+    Geo g; ParamOff P; CtxLayout L; WsLayout W;
+    const float* params; float* grads; const float* x; const uint64_t* seed_dev; void* ctx; void* ws;      // grads, ws: null in a forward
+    int H(int i) const { return i == 1 ? g.H1 : g.H2; }       // the image of conv block i = 1, 2
+    int Wd(int i) const { return i == 1 ? g.W1 : g.W2; }
+    int fwd_drop(int train) const { return (train && g.p > 0.f) ? 1 : 0; }
+    int bwd_drop() const { return (g.p > 0.f) ? 1 : 0; }
+};
 
-// the recurrent tail's buffers in the specialised layouts (ws == null: a forward)
-static RnnBufs rnn_bufs(const CtxLayout& L, void* ctx, const WsLayout* Wp, void* ws) {
+// the recurrent tail's buffers in the specialised layouts
+static RnnBufs rnn_bufs(const Call& c) {
+    const CtxLayout& L = c.L; const WsLayout& W = c.W; void* ctx = c.ctx; void* ws = c.ws;
     RnnBufs R;
-    R.p2 = CTXF(L.p2);
-    for (int l = 0; l < 2; ++l) { R.out[l] = CTXF(L.out[l]); R.gates[l] = CTXF(L.gates[l]); }
-    R.logits_s = CTXF(L.logits_s); R.strong_sv = CTXF(L.strong_sv); R.weak_sv = CTXF(L.weak_sv); R.den_sv = CTXF(L.den_sv);
+    R.p2 = L.p[2].f(ctx);
+    for (int l = 0; l < 2; ++l) { R.out[l] = L.out[l].f(ctx); R.gates[l] = L.gates[l].f(ctx); }
+    R.logits_s = L.logits_s.f(ctx); R.strong_sv = L.strong_sv.f(ctx); R.weak_sv = L.weak_sv.f(ctx); R.den_sv = L.den_sv.f(ctx);
     if (ws == nullptr) return R;
-    const WsLayout& W = *Wp;
-    R.d_out = WSF(W.d_out); R.d_in = WSF(W.d_in); R.dp2 = WSF(W.dp2); R.heads_part = WSF(W.heads_part);
-    for (int l = 0; l < 2; ++l) { R.dgi[l] = WSF(W.dgi[l]); R.dgh[l] = WSF(W.dgh[l]); R.hprev[l] = WSF(W.hprev[l]); }
-    R.gemm_part = WSF(W.gemm_part); R.gemm_part_floats = gemm_part_floats(4, SED_GRU_SPLITK, 192, 129); R.splitk = SED_GRU_SPLITK;
-    R.zero = WSD(W.bwd_acc); R.n_zero = 2 * SED_GLUACC_N + 2 * 64 * 10;      // every fp64 accumulator of the conv-block backward
+    R.d_out = W.d_out.f(ws); R.d_in = W.d_in.f(ws); R.dp2 = W.dp[2].f(ws); R.heads_part = W.heads_part.f(ws);
+    for (int l = 0; l < 2; ++l) { R.dgi[l] = W.dgi[l].f(ws); R.dgh[l] = W.dgh[l].f(ws); R.hprev[l] = W.hprev[l].f(ws); }
+    R.gemm_part = W.gemm_part.f(ws); R.gemm_part_floats = W.gemm_part.bytes / 4; R.splitk = SED_GRU_SPLITK;
+    R.zero = W.bwd_acc.d(ws); R.n_zero = (int)(W.bwd_acc.bytes / sizeof(double));
     return R;
+}
+
+// running: the block's running [mean | var] (the replay hands 128 floats that an update = 0 launch never touches)
+static int stage_blk0_fwd(const Call& c, float* running, int64_t* tracked, int train, int upd, const ConvPackArgs* pack,
+                          int main_kernel_only, int mom_ready, hipStream_t st) {
+    const ParamOff& P = c.P; const CtxLayout& L = c.L; void* ctx = c.ctx;
+    return launch_blk0_forward(c.g, c.x, c.params + P.conv_w[0], c.params + P.conv_b[0], c.params + P.bn_g[0], c.params + P.bn_b[0],
+                               c.params + P.glu_w[0], c.params + P.glu_b[0], running, running + 64, tracked, train, upd, c.seed_dev,
+                               L.mom0.d(ctx), L.mompart.d(ctx), L.wz0.f(ctx), L.wl0.f(ctx), L.bn[0].f(ctx), L.p[0].f(ctx),
+                               c.fwd_drop(train) ? L.mask[0].m(ctx) : nullptr, pack, st, main_kernel_only, nullptr, nullptr, mom_ready);
+}
+static int stage_conv_fwd(const Call& c, int i, bool with_stat, int zero_stat, hipStream_t st) {
+    const CtxLayout& L = c.L; void* ctx = c.ctx;
+    return launch_conv_fwd(L.p[i - 1].f(ctx), L.wpk[i].f(ctx), c.params + c.P.conv_b[i], L.y[i].f(ctx), with_stat ? L.stat[i].d(ctx) : nullptr,
+                           zero_stat, c.g.B, c.H(i), c.Wd(i), st);
+}
+static int stage_glu_fwd(const Call& c, int i, float* running, int64_t* tracked, int train, int upd, hipStream_t st) {
+    const Geo& g = c.g; const ParamOff& P = c.P; const CtxLayout& L = c.L; void* ctx = c.ctx;
+    const int use_drop = c.fwd_drop(train);
+    return launch_glu_pool_fwd(L.y[i].f(ctx), L.stat[i].d(ctx), (double)g.B * c.H(i) * c.Wd(i), c.params + P.bn_g[i], c.params + P.bn_b[i],
+                               running, running + 64, tracked, train, upd, g.eps, g.mom, L.bn[i].f(ctx), c.params + P.glu_w[i],
+                               c.params + P.glu_b[i], L.p[i].f(ctx), g.B, c.H(i), c.Wd(i), i, use_drop, g.p, c.seed_dev,
+                               use_drop ? L.mask[i].m(ctx) : nullptr, st);
+}
+// prep_out != null: the BatchNorm-backward coefficients and the block's parameter gradients are left to the conv dgrad / wgrad
+// kernels (BnBwdPrepArgs, kernels.h); null: k_bn_bwd_prep follows
+static int stage_glu_bwd(const Call& c, int i, int zero_acc, BnBwdPrepArgs* prep_out, hipStream_t st) {
+    const Geo& g = c.g; const ParamOff& P = c.P; const CtxLayout& L = c.L; const WsLayout& W = c.W; void* ctx = c.ctx; void* ws = c.ws;
+    // (block 2: the GRU's dX arrives as two direction planes)
+    return launch_glu_pool_bwd(L.y[i].f(ctx), L.bn[i].f(ctx), c.params + P.glu_w[i], c.params + P.glu_b[i], W.dp[i].f(ws),
+                               i == 2 ? W.dp[i].f(ws) + (size_t)g.B * g.T3 * 64 : nullptr, W.dz[i].f(ws), W.gluacc[i].d(ws), zero_acc, g.B,
+                               c.H(i), c.Wd(i), c.bwd_drop(), g.p, L.mask[i].m(ctx), c.params + P.bn_g[i], W.coef[i].f(ws),
+                               c.grads + P.bn_g[i], c.grads + P.bn_b[i], c.grads + P.glu_w[i], c.grads + P.glu_b[i], c.grads + P.conv_b[i],
+                               prep_out, st);
+}
+static int stage_conv_dgrad(const Call& c, int i, const BnBwdPrepArgs* prep, hipStream_t st) {
+    const WsLayout& W = c.W;
+    return launch_conv_dgrad(W.dz[i].f(c.ws), c.L.y[i].f(c.ctx), W.coef[i].f(c.ws), c.L.wpkT[i].f(c.ctx), W.dp[i - 1].f(c.ws), c.g.B, c.H(i),
+                             c.Wd(i), prep, st);
+}
+static int stage_conv_wgrad(const Call& c, int i, const BnBwdPrepArgs* prep, hipStream_t st) {
+    const WsLayout& W = c.W;
+    return launch_conv_wgrad(W.dz[i].f(c.ws), c.L.y[i].f(c.ctx), W.coef[i].f(c.ws), c.L.p[i - 1].f(c.ctx), W.wg_part.f(c.ws), W.wgrad_blocks,
+                             c.grads + c.P.conv_w[i], c.g.B, c.H(i), c.Wd(i), prep, st);
+}
+static int stage_blk0_bwd(const Call& c, int zero_de, hipStream_t st) {
+    const ParamOff& P = c.P; const CtxLayout& L = c.L; void* ctx = c.ctx;
+    return launch_blk0_backward(c.g, c.x, c.params + P.conv_w[0], c.params + P.conv_b[0], c.params + P.bn_g[0], c.params + P.bn_b[0],
+                                c.params + P.glu_w[0], L.mask[0].m(ctx), L.mom0.d(ctx), L.wz0.f(ctx), L.wl0.f(ctx), L.bn[0].f(ctx),
+                                c.W.dp[0].f(c.ws), c.W.de0.d(c.ws), zero_de, c.grads + P.conv_w[0], c.grads + P.conv_b[0],
+                                c.grads + P.bn_g[0], c.grads + P.bn_b[0], c.grads + P.glu_w[0], c.grads + P.glu_b[0], st);
 }
 
 extern "C" int sed_crnn_forward(const sed_dims* d, const float* params, float* bn_running, int64_t* bn_tracked,
@@ -333,45 +386,32 @@ extern "C" int sed_crnn_forward(const sed_dims* d, const float* params, float* b
         return gen_forward(g, P, params, bn_running, bn_tracked, x, train | (mom_ready ? 4 : 0), update_bn, seed_dev, ctx, ctx_bytes, strong,
                            weak, (hipStream_t)stream);
     }
-    const CtxLayout L = make_ctx_layout(g);
+    const Call c = {g, P, make_ctx_layout(g), make_ws_layout(g), params, nullptr, x, seed_dev, ctx, nullptr};
+    const CtxLayout& L = c.L;
     if (ctx_bytes < L.total) {
         sed_set_error("sed_crnn_forward: ctx has %zu bytes, needs %zu", ctx_bytes, L.total);
         return SED_ERR_WORKSPACE;
     }
-    const int use_drop = (train && g.p > 0.f) ? 1 : 0;
-    SED_CHECK_ARG(!use_drop || seed_dev, "sed_crnn_forward: dropout enabled but seed_dev is null");
+    SED_CHECK_ARG(!c.fwd_drop(train) || seed_dev, "sed_crnn_forward: dropout enabled but seed_dev is null");
     hipStream_t st = (hipStream_t)stream;
     const int upd = (train && update_bn) ? 1 : 0;
-    int64_t* trk[3] = {bn_tracked ? bn_tracked + 0 : nullptr, bn_tracked ? bn_tracked + 1 : nullptr,
-                       bn_tracked ? bn_tracked + 2 : nullptr};
+    auto trk = [&](int i) { return bn_tracked ? bn_tracked + i : nullptr; };
 
     // conv1 / conv2 weights -> [tap][ci][co] + Winograd panels (+ flipped/transposed copies for dgrad); the same threads
     // also zero the fp64 BatchNorm sums of blocks 1 and 2.  In a training forward this rides along in the k_x_moments
     // launch (independent work, extra workgroups) instead of being a launch of its own on the chain.
-    const ConvPackArgs pack = {params + P.conv_w[1], params + P.conv_w[2], CTXF(L.wpk1), CTXF(L.wpk2),
-                               train ? CTXF(L.wpkT1) : nullptr, train ? CTXF(L.wpkT2) : nullptr, CTXD(L.stat1), train ? 256 : 0};
+    const ConvPackArgs pack = {params + P.conv_w[1], params + P.conv_w[2], L.wpk[1].f(ctx), L.wpk[2].f(ctx),
+                               train ? L.wpkT[1].f(ctx) : nullptr, train ? L.wpkT[2].f(ctx) : nullptr, L.stat[1].d(ctx), train ? 256 : 0};
     // ---- conv block 0 ---------------------------------------------------------------------------
-    SED_TRY(launch_blk0_forward(g, x, params + P.conv_w[0], params + P.conv_b[0], params + P.bn_g[0], params + P.bn_b[0],
-                                params + P.glu_w[0], params + P.glu_b[0], bn_running + 0, bn_running + 64, trk[0], train,
-                                upd, seed_dev, CTXD(L.mom0), CTXD(L.mompart), CTXF(L.wz0), CTXF(L.wl0), CTXF(L.bn0), CTXF(L.p0),
-                                use_drop ? CTXM(L.mask0) : nullptr, train ? &pack : nullptr, st, 0, nullptr, nullptr, mom_ready));
+    SED_TRY(stage_blk0_fwd(c, bn_running, trk(0), train, upd, train ? &pack : nullptr, 0, mom_ready, st));
     if (!train) SED_TRY(launch_conv_pack(pack, st));      // (training: done by extra workgroups of k_x_moments / k_blk0_prep_pack)
     // ---- conv blocks 1, 2 -----------------------------------------------------------------------
-    const float* in = CTXF(L.p0);
-    const size_t wpk[3] = {0, L.wpk1, L.wpk2}, yo[3] = {0, L.y1, L.y2}, so[3] = {0, L.stat1, L.stat2},
-                 bo[3] = {0, L.bn1, L.bn2}, po[3] = {0, L.p1, L.p2}, mo[3] = {L.mask0, L.mask1, L.mask2};
-    const int Hs[3] = {0, g.H1, g.H2}, Ws[3] = {0, g.W1, g.W2};
     for (int i = 1; i <= 2; ++i) {
-        SED_TRY(launch_conv_fwd(in, CTXF(wpk[i]), params + P.conv_b[i], CTXF(yo[i]), train ? CTXD(so[i]) : nullptr, 0, g.B,
-                                Hs[i], Ws[i], st));
-        SED_TRY(launch_glu_pool_fwd(CTXF(yo[i]), CTXD(so[i]), (double)g.B * Hs[i] * Ws[i], params + P.bn_g[i], params + P.bn_b[i],
-                                    bn_running + (2 * i) * 64, bn_running + (2 * i + 1) * 64, trk[i], train, upd, g.eps, g.mom,
-                                    CTXF(bo[i]), params + P.glu_w[i], params + P.glu_b[i], CTXF(po[i]), g.B, Hs[i], Ws[i], i,
-                                    use_drop, g.p, seed_dev, use_drop ? CTXM(mo[i]) : nullptr, st));
-        in = CTXF(po[i]);
+        SED_TRY(stage_conv_fwd(c, i, train != 0, 0, st));
+        SED_TRY(stage_glu_fwd(c, i, bn_running + 2 * i * 64, trk(i), train, upd, st));
     }
     // ---- BiGRU + heads --------------------------------------------------------------------------
-    return rnn_forward(g, P, params, rnn_bufs(L, ctx, nullptr, nullptr), train, seed_dev, strong, weak, 0, st);
+    return rnn_forward(g, P, params, rnn_bufs(c), train, seed_dev, strong, weak, 0, st);
 }
 
 // The train-mode BatchNorm statistics of conv block 0 come from the 9 + 45 first / second moments of the 3x3 input patch
@@ -392,7 +432,7 @@ extern "C" int sed_crnn_moments(const sed_dims* d, const float* x, void* ctx, si
             sed_set_error("sed_crnn_moments: ctx has %zu bytes, needs %zu", ctx_bytes, L.total);
             return SED_ERR_WORKSPACE;
         }
-        mompart = CTXD(L.mompart);
+        mompart = L.mompart.d(ctx);
     }
     return launch_x_moments(g, x, mompart, nullptr, (hipStream_t)stream);
 }
@@ -413,28 +453,22 @@ static int crnn_backward_impl(const sed_dims* d, const float* params, const floa
         return gen_backward(g, P, params, x, seed_dev, ctx, ctx_bytes, d_strong, d_weak, grads, ws, ws_bytes, parts, (hipStream_t)stream,
                             side0, hl, ho);
     }
-    const CtxLayout L = make_ctx_layout(g);
-    const WsLayout W = make_ws_layout(g);
-    if (ctx_bytes < L.total || ws_bytes < W.total) {
-        sed_set_error("sed_crnn_backward: ctx %zu/%zu bytes, ws %zu/%zu bytes", ctx_bytes, L.total, ws_bytes, W.total);
+    const Call c = {g, P, make_ctx_layout(g), make_ws_layout(g), params, grads, x, seed_dev, ctx, ws};
+    const WsLayout& W = c.W;
+    if (ctx_bytes < c.L.total || ws_bytes < W.total) {
+        sed_set_error("sed_crnn_backward: ctx %zu/%zu bytes, ws %zu/%zu bytes", ctx_bytes, c.L.total, ws_bytes, W.total);
         return SED_ERR_WORKSPACE;
     }
-    const int use_drop = (g.p > 0.f) ? 1 : 0;
-    SED_CHECK_ARG(!use_drop || seed_dev, "sed_crnn_backward: dropout enabled but seed_dev is null");
+    SED_CHECK_ARG(!c.bwd_drop() || seed_dev, "sed_crnn_backward: dropout enabled but seed_dev is null");
     hipStream_t st = (hipStream_t)stream;
-    const int BT = g.B * g.T3;
     SideFork side = side_fork(st);
     // ---- heads, BiGRU (+ the weight-gradient tail of a parts == 1 / parts == 8 call) --------------
-    const RnnBwd rb = rnn_backward_plan(g, P, rnn_bufs(L, ctx, &W, ws), params, grads, seed_dev, hl, ho, parts, &side);
+    const RnnBwd rb = rnn_backward_plan(g, P, rnn_bufs(c), params, grads, seed_dev, hl, ho, parts, &side);
     SED_TRY(rnn_backward(rb, d_strong, d_weak, st));
     if (!(parts & 2)) return SED_OK;
     // ---- conv blocks 2, 1 -----------------------------------------------------------------------
-    const size_t wpkT[3] = {0, L.wpkT1, L.wpkT2}, yo[3] = {0, L.y1, L.y2}, bo[3] = {0, L.bn1, L.bn2};
-    const size_t pin[3] = {0, L.p0, L.p1}, gacc[3] = {0, W.gluacc1, W.gluacc2}, mo[3] = {L.mask0, L.mask1, L.mask2};
-    const size_t dzo[3] = {0, W.dz1, W.dz2}, dpo[3] = {W.dp0, W.dp1, W.dp2};
-    const int Hs[3] = {0, g.H1, g.H2}, Wd[3] = {0, g.W1, g.W2};
     // every fp64 accumulator of the conv-block backward: zeroed by k_heads_bwd when this call also ran part 1
-    if (!(parts & 1)) SED_CHECK_HIP(hipMemsetAsync(WSD(W.bwd_acc), 0, (2 * SED_GLUACC_N + 2 * 64 * 10) * sizeof(double), st));
+    if (!(parts & 1)) SED_CHECK_HIP(hipMemsetAsync(W.bwd_acc.d(ws), 0, W.bwd_acc.bytes, st));
     // Stream schedule (kernel timeline of one step, tools/timeline.py): the dgrad chain is the critical path.
     //   main: glu2_bwd  prep | dgrad2            | glu1_bwd  prep | dgrad1          | blk0_bwd  finalize |
     //   side:                | wgrad2  heads_fin |                | wgrad1  reduce  GRU dW/db  reduce    | join
@@ -450,29 +484,19 @@ static int crnn_backward_impl(const sed_dims* d, const float* params, const floa
     const bool fuse_prep = (g_sed_debug & (SED_DEBUG_DIRECT_CONV | SED_DEBUG_DIRECT_WGRAD)) == 0;
     BnBwdPrepArgs prep[3] = {};
     for (int i = 2; i >= 1; --i) {
-        const BnBwdPrepArgs* pp = fuse_prep ? &prep[i] : nullptr;
-        // (the BatchNorm-backward coefficients and the block's parameter gradients are produced by the last workgroup
-        // of k_glu_pool_bwd8: no separate 1-workgroup kernel between it and the conv dgrad / wgrad)
-        SED_TRY(launch_glu_pool_bwd(CTXF(yo[i]), CTXF(bo[i]), params + P.glu_w[i], params + P.glu_b[i], WSF(dpo[i]),
-                                    i == 2 ? WSF(dpo[i]) + (size_t)BT * 64 : nullptr,
-                                    WSF(dzo[i]), WSD(gacc[i]), 0, g.B, Hs[i], Wd[i], use_drop, g.p, CTXM(mo[i]),
-                                    params + P.bn_g[i], WSF(W.coef[i]), grads + P.bn_g[i], grads + P.bn_b[i],
-                                    grads + P.glu_w[i], grads + P.glu_b[i], grads + P.conv_b[i], fuse_prep ? &prep[i] : nullptr, st));
+        BnBwdPrepArgs* pp = fuse_prep ? &prep[i] : nullptr;
+        SED_TRY(stage_glu_bwd(c, i, 0, pp, st));
         // block 2: the dgrad - the critical chain - is captured between the two halves of the fork (SideFork); block 1: behind both
         SED_TRY(side.mark(st));
         if (i == 1) SED_TRY(side.start());
-        SED_TRY(launch_conv_dgrad(WSF(dzo[i]), CTXF(yo[i]), WSF(W.coef[i]), CTXF(wpkT[i]), WSF(dpo[i - 1]), g.B, Hs[i], Wd[i], pp, st));
+        SED_TRY(stage_conv_dgrad(c, i, pp, st));
         if (i == 2) SED_TRY(side.start());
-        SED_TRY(launch_conv_wgrad(WSF(dzo[i]), CTXF(yo[i]), WSF(W.coef[i]), CTXF(pin[i]), WSF(W.wg_part), W.wgrad_blocks,
-                                  grads + P.conv_w[i], g.B, Hs[i], Wd[i], pp, side.s));
+        SED_TRY(stage_conv_wgrad(c, i, pp, side.s));
         if (i == 2) SED_TRY(rnn_deferred_weight_grads(rb));      // parts == 3: head column sum behind wgrad2
         if (i == 1) SED_TRY(rnn_tail_weight_grads(rb));          // parts == 3: every GRU dW / db at the very end of the helper stream
     }
     // ---- conv block 0 ---------------------------------------------------------------------------
-    SED_TRY(launch_blk0_backward(g, x, params + P.conv_w[0], params + P.conv_b[0], params + P.bn_g[0], params + P.bn_b[0],
-                                 params + P.glu_w[0], CTXM(L.mask0), CTXD(L.mom0), CTXF(L.wz0), CTXF(L.wl0), CTXF(L.bn0),
-                                 WSF(W.dp0), WSD(W.de0), 0, grads + P.conv_w[0], grads + P.conv_b[0], grads + P.bn_g[0],
-                                 grads + P.bn_b[0], grads + P.glu_w[0], grads + P.glu_b[0], st));
+    SED_TRY(stage_blk0_bwd(c, 0, st));
     return side.join(st);
 }
 
@@ -482,17 +506,27 @@ extern "C" int sed_crnn_backward(const sed_dims* d, const float* params, const f
     return crnn_backward_impl(d, params, x, seed_dev, ctx, ctx_bytes, d_strong, d_weak, grads, ws, ws_bytes, parts, stream, nullptr);
 }
 
+// the argument checks and the loss inputs that sed_mt_loss_backward and sed_mt_step_backward share
+static int heads_loss_args(HeadsLoss& hl, const sed_dims* d, const float* strong_ema, const float* weak_ema, const float* target, int weak_lo,
+                           int weak_hi, int strong_lo, int strong_hi, sed_step_state* state_dev, int advance_state, float* losses,
+                           float* d_strong, float* d_weak, int parts) {
+    SED_CHECK_ARG(d && strong_ema && weak_ema && target && state_dev && losses, "fused loss + backward: null argument");
+    SED_CHECK_ARG(parts == 1 || parts == 3 || parts == 5, "fused loss + backward: parts must include the heads (1, 3 or 5)");
+    SED_CHECK_ARG(weak_lo >= 0 && weak_hi <= d->B && weak_lo <= weak_hi && strong_lo >= 0 && strong_hi <= d->B &&
+                      strong_lo <= strong_hi, "fused loss + backward: bad mask range");
+    hl = {strong_ema, weak_ema, target, weak_lo, weak_hi, strong_lo, strong_hi, state_dev, losses, d_strong, d_weak,
+          advance_state ? state_dev : nullptr};
+    return SED_OK;
+}
+
 extern "C" int sed_mt_loss_backward(const sed_dims* d, const float* params, const float* x, const uint64_t* seed_dev,
                                     void* ctx, size_t ctx_bytes, const float* strong_ema, const float* weak_ema,
                                     const float* target, int weak_lo, int weak_hi, int strong_lo, int strong_hi,
                                     sed_step_state* state_dev, int advance_state, float* losses, float* d_strong,
                                     float* d_weak, float* grads, void* ws, size_t ws_bytes, int parts, void* stream) {
-    SED_CHECK_ARG(d && strong_ema && weak_ema && target && state_dev && losses, "sed_mt_loss_backward: null argument");
-    SED_CHECK_ARG(parts == 1 || parts == 3 || parts == 5, "sed_mt_loss_backward: parts must include the heads (1, 3 or 5)");
-    SED_CHECK_ARG(weak_lo >= 0 && weak_hi <= d->B && weak_lo <= weak_hi && strong_lo >= 0 && strong_hi <= d->B &&
-                      strong_lo <= strong_hi, "sed_mt_loss_backward: bad mask range");
-    HeadsLoss hl = {strong_ema, weak_ema, target, weak_lo, weak_hi, strong_lo, strong_hi, state_dev, losses, d_strong, d_weak,
-                    advance_state ? state_dev : nullptr};
+    HeadsLoss hl;
+    SED_TRY(heads_loss_args(hl, d, strong_ema, weak_ema, target, weak_lo, weak_hi, strong_lo, strong_hi, state_dev, advance_state, losses,
+                            d_strong, d_weak, parts));
     return crnn_backward_impl(d, params, x, seed_dev, ctx, ctx_bytes, nullptr, nullptr, grads, ws, ws_bytes, parts, stream, &hl);
 }
 
@@ -501,12 +535,10 @@ extern "C" int sed_mt_step_backward(const sed_dims* d, const float* params, cons
                                     const float* weak_ema, const float* target, int weak_lo, int weak_hi, int strong_lo,
                                     int strong_hi, sed_step_state* state_dev, int advance_state, float* losses, float* d_strong,
                                     float* d_weak, float* grads, void* ws, size_t ws_bytes, int parts, void* stream) {
-    SED_CHECK_ARG(d && strong && weak && strong_ema && weak_ema && target && state_dev && losses, "sed_mt_step_backward: null argument");
-    SED_CHECK_ARG(parts == 1 || parts == 3 || parts == 5, "sed_mt_step_backward: parts must include the heads (1, 3 or 5)");
-    SED_CHECK_ARG(weak_lo >= 0 && weak_hi <= d->B && weak_lo <= weak_hi && strong_lo >= 0 && strong_hi <= d->B &&
-                      strong_lo <= strong_hi, "sed_mt_step_backward: bad mask range");
-    HeadsLoss hl = {strong_ema, weak_ema, target, weak_lo, weak_hi, strong_lo, strong_hi, state_dev, losses, d_strong, d_weak,
-                    advance_state ? state_dev : nullptr};
+    SED_CHECK_ARG(strong && weak, "sed_mt_step_backward: null argument");
+    HeadsLoss hl;
+    SED_TRY(heads_loss_args(hl, d, strong_ema, weak_ema, target, weak_lo, weak_hi, strong_lo, strong_hi, state_dev, advance_state, losses,
+                            d_strong, d_weak, parts));
     HeadsOut ho = {strong, weak};
     return crnn_backward_impl(d, params, x, seed_dev, ctx, ctx_bytes, nullptr, nullptr, grads, ws, ws_bytes, parts, stream, &hl, &ho);
 }
@@ -521,76 +553,43 @@ extern "C" int sed_kernel_replay(const char* name, const sed_dims* d, const floa
         sed_set_error("sed_kernel_replay: only the C = 64 / H = 64 / fp32 kernel set is replayable");
         return SED_ERR_UNSUPPORTED;
     }
-    const ParamOff P = make_param_off(g, nullptr);
-    const CtxLayout L = make_ctx_layout(g);
-    const WsLayout W = make_ws_layout(g);
-    if (ctx_bytes < L.total || ws_bytes < W.total) {
+    const Call c = {g, make_param_off(g, nullptr), make_ctx_layout(g), make_ws_layout(g), params, grads, x, seed_dev, ctx, ws};
+    if (ctx_bytes < c.L.total || ws_bytes < c.W.total) {
         sed_set_error("sed_kernel_replay: buffers too small");
         return SED_ERR_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    const int use_drop = (g.p > 0.f) ? 1 : 0;
-    const int BT = g.B * g.T3;
-    const size_t wpk[3] = {0, L.wpk1, L.wpk2}, wpkT[3] = {0, L.wpkT1, L.wpkT2}, yo[3] = {0, L.y1, L.y2},
-                 so[3] = {0, L.stat1, L.stat2}, bo[3] = {0, L.bn1, L.bn2}, po[3] = {L.p0, L.p1, L.p2},
-                 mo[3] = {L.mask0, L.mask1, L.mask2};
-    const size_t dzo[3] = {0, W.dz1, W.dz2}, dpo[3] = {W.dp0, W.dp1, W.dp2}, gacc[3] = {0, W.gluacc1, W.gluacc2};
-    const int Hs[3] = {0, g.H1, g.H2}, Wd[3] = {0, g.W1, g.W2};
+    // a training launch that updates no running statistics: the running-stat pointers get 128 floats it never touches
+    float* no_running = c.W.coef[1].f(ws);
     auto is = [&](const char* n) { return strcmp(name, n) == 0; };
-    if (is("x_moments")) return launch_x_moments(g, x, CTXD(L.mompart), nullptr, st);
-    if (is("blk0_fwd")) {
-        return launch_blk0_forward(g, x, params + P.conv_w[0], params + P.conv_b[0], params + P.bn_g[0], params + P.bn_b[0],
-                                   params + P.glu_w[0], params + P.glu_b[0], WSF(W.coef[1]), WSF(W.coef[1]) + 64, nullptr, 1, 0,
-                                   seed_dev, CTXD(L.mom0), CTXD(L.mompart), CTXF(L.wz0), CTXF(L.wl0), CTXF(L.bn0), CTXF(L.p0),
-                                   use_drop ? CTXM(L.mask0) : nullptr, nullptr, st, 1);
-    }
+    auto is_k = [&](const char* fmt, int k) {
+        char nm[32];
+        snprintf(nm, sizeof nm, fmt, k);
+        return is(nm);
+    };
+    if (is("x_moments")) return sed_crnn_moments(d, x, ctx, ctx_bytes, stream);
+    // (the folded weights of the last real forward are still in wz0 / wl0: the main kernel only)
+    if (is("blk0_fwd")) return stage_blk0_fwd(c, no_running, nullptr, 1, 0, nullptr, 1, 0, st);
     for (int i = 1; i <= 2; ++i) {
-        char nm[32];
-        snprintf(nm, sizeof nm, "conv%d_fwd", i);
-        if (is(nm)) return launch_conv_fwd(CTXF(po[i - 1]), CTXF(wpk[i]), params + P.conv_b[i], CTXF(yo[i]), CTXD(so[i]), 1, g.B, Hs[i], Wd[i], st);
-        snprintf(nm, sizeof nm, "glu%d_fwd", i);
-        if (is(nm)) return launch_glu_pool_fwd(CTXF(yo[i]), CTXD(so[i]), (double)g.B * Hs[i] * Wd[i], params + P.bn_g[i], params + P.bn_b[i],
-                                               WSF(W.coef[1]), WSF(W.coef[1]) + 64, nullptr, 1, 0, g.eps, g.mom, CTXF(bo[i]),
-                                               params + P.glu_w[i], params + P.glu_b[i], CTXF(po[i]), g.B, Hs[i], Wd[i], i, use_drop,
-                                               g.p, seed_dev, use_drop ? CTXM(mo[i]) : nullptr, st);
-        snprintf(nm, sizeof nm, "glu%d_bwd", i);
-        if (is(nm)) return launch_glu_pool_bwd(CTXF(yo[i]), CTXF(bo[i]), params + P.glu_w[i], params + P.glu_b[i], WSF(dpo[i]), i == 2 ? WSF(dpo[i]) + (size_t)BT * 64 : nullptr, WSF(dzo[i]), WSD(gacc[i]), 1, g.B, Hs[i], Wd[i], use_drop, g.p, CTXM(mo[i]),
-                                               params + P.bn_g[i], WSF(W.coef[i]), grads + P.bn_g[i], grads + P.bn_b[i], grads + P.glu_w[i], grads + P.glu_b[i], grads + P.conv_b[i], nullptr, st);
-        snprintf(nm, sizeof nm, "conv%d_wgrad", i);
-        if (is(nm)) return launch_conv_wgrad(WSF(dzo[i]), CTXF(yo[i]), WSF(W.coef[i]), CTXF(po[i - 1]), WSF(W.wg_part), W.wgrad_blocks, grads + P.conv_w[i], g.B, Hs[i], Wd[i], nullptr, st);
-        snprintf(nm, sizeof nm, "conv%d_dgrad", i);
-        if (is(nm)) return launch_conv_dgrad(WSF(dzo[i]), CTXF(yo[i]), WSF(W.coef[i]), CTXF(wpkT[i]), WSF(dpo[i - 1]), g.B, Hs[i], Wd[i], nullptr, st);
+        if (is_k("conv%d_fwd", i)) return stage_conv_fwd(c, i, true, 1, st);
+        if (is_k("glu%d_fwd", i)) return stage_glu_fwd(c, i, no_running, nullptr, 1, 0, st);
+        if (is_k("glu%d_bwd", i)) return stage_glu_bwd(c, i, 1, nullptr, st);
+        if (is_k("conv%d_wgrad", i)) return stage_conv_wgrad(c, i, nullptr, st);
+        if (is_k("conv%d_dgrad", i)) return stage_conv_dgrad(c, i, nullptr, st);
     }
+    const RnnBufs R = rnn_bufs(c);
     for (int l = 0; l < g.L; ++l) {
-        char nm[32];
-        snprintf(nm, sizeof nm, "gru%d_fwd", l);
-        if (is(nm)) return launch_gru_fwd(l == 0 ? CTXF(L.p2) : CTXF(L.out[l - 1]), l == 0 ? 64 : 128, params + P.w_ih[l][0], params + P.w_ih[l][1],
-                                          params + P.b_ih[l][0], params + P.b_ih[l][1], params + P.w_hh[l][0], params + P.w_hh[l][1],
-                                          params + P.b_hh[l][0], params + P.b_hh[l][1], CTXF(L.out[l]), CTXF(L.gates[l]), g.B, g.T3, st);
-        snprintf(nm, sizeof nm, "gru%d_bwd", l);
-        if (is(nm)) {
-            const int nin = (l == 0) ? 64 : 128;
-            const bool top = (l == g.L - 1);
-            return launch_gru_bwd(top ? WSF(W.d_out) : WSF(W.d_in), top ? nullptr : WSF(W.d_in) + (size_t)BT * 128, CTXF(L.out[l]),
-                                  CTXF(L.gates[l]), params + P.w_hh[l][0], params + P.w_hh[l][1], params + P.w_ih[l][0],
-                                  params + P.w_ih[l][1], nin, WSF(W.dgi[l]), WSF(W.dgh[l]), WSF(W.hprev[l]),
-                                  l == 0 ? WSF(W.dp2) : WSF(W.d_in), g.B, g.T3, st);
-        }
+        if (is_k("gru%d_fwd", l)) return rnn_gru_fwd64(g, c.P, params, R, l, 1, st);
+        if (is_k("gru%d_bwd", l)) return rnn_gru_bwd64(g, c.P, params, R, l, st);
     }
-    if (is("heads_fwd"))
-        return launch_heads_fwd(CTXF(L.out[g.L - 1]), params + P.dense_w, params + P.dense_b, params + P.soft_w, params + P.soft_b,
-                                CTXF(L.strong_sv), CTXF(L.weak_sv), nullptr, nullptr, CTXF(L.logits_s), CTXF(L.den_sv), g.B, g.T3, g.NC,
-                                use_drop, g.p, seed_dev, st);
+    // (the posteriors go where a training forward saves them)
+    if (is("heads_fwd")) return rnn_heads_fwd(g, c.P, params, R, R.strong_sv, R.weak_sv, false, c.bwd_drop(), seed_dev, st);
     if (is("gru_wgrad")) {
         // every GRU dW / db, as a parts == 1 backward issues them (rnn.hip: one k_gru_wgrad launch + its reduce)
         SideFork side = side_fork(st);
-        return rnn_weight_grads(rnn_backward_plan(g, P, rnn_bufs(L, ctx, &W, ws), params, grads, seed_dev, nullptr, nullptr, 1, &side), st);
+        return rnn_weight_grads(rnn_backward_plan(g, c.P, R, params, grads, seed_dev, nullptr, nullptr, 1, &side), st);
     }
-    if (is("blk0_bwd"))
-        return launch_blk0_backward(g, x, params + P.conv_w[0], params + P.conv_b[0], params + P.bn_g[0], params + P.bn_b[0],
-                                    params + P.glu_w[0], CTXM(L.mask0), CTXD(L.mom0), CTXF(L.wz0), CTXF(L.wl0), CTXF(L.bn0), WSF(W.dp0),
-                                    WSD(W.de0), 1, grads + P.conv_w[0], grads + P.conv_b[0], grads + P.bn_g[0], grads + P.bn_b[0],
-                                    grads + P.glu_w[0], grads + P.glu_b[0], st);
+    if (is("blk0_bwd")) return stage_blk0_bwd(c, 1, st);
     sed_set_error("sed_kernel_replay: unknown kernel '%s'", name);
     return SED_ERR_BAD_ARG;
 }

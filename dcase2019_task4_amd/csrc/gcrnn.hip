@@ -11,7 +11,6 @@
 #include "gpack.h"
 #include "rnn.h"
 
-static inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 // bytes per element of the packed weights (wpk, wpkT, wg, wgT) and of the conv-block activations / gradients in HBM (p0, y1,
 // p1, y2; dz1, dz2, dp0, dp1): bf16 in SED_DTYPE_BF16 mode, fp32 otherwise (gen.h Stor<>); p2 - the GRU input - and dp2 are
 // always fp32
@@ -26,43 +25,36 @@ static inline size_t gru_gemm_part_floats(const Geo& g) {
 }
 
 struct GCtx {
-    size_t acc0, mom0, stat1, stat2;          // fp64: patch moments of block 0 | BatchNorm sums of blocks 1, 2
-    size_t wz0, wl0, bn0, mompart, p0;
-    size_t wpk[3], wpkT[3], wg[3], wgT[3], bg[3], y[3], bn[3], p[3];      // index 1, 2
-    size_t ph[2], yh[3];                      // SED_DTYPE_F16: the forward chain's fp16 p0, p1 / y1, y2 (p[], y[] are then the bf16 copies the backward reads)
-    size_t gi[2], gates[2], out[2], whh[2], whhT[2];
-    size_t wihT[2];                           // [nin][6H]: the two W_ih stacked along K and transposed (dX GEMM operand)
-    size_t xch[2], epoch[2], err;             // cluster recurrence: exchange granules, launch epochs, spin-timeout flag
-    size_t logits_s, strong_sv, weak_sv, den_sv;
-    size_t mask[3];
-    size_t sg0;                               // bf16 family: block 0's GLU gate, one byte per element (blk0.hip SG), 0 bytes otherwise
+    Region acc0, mom0, stat[3];               // fp64: patch moments of block 0 | BatchNorm sums of blocks 1, 2
+    Region wz0, wl0, mompart;
+    Region wpk[3], wpkT[3], wg[3], wgT[3], bg[3], y[3];      // index 1, 2
+    Region bn[3], p[3];                       // index 0, 1, 2
+    Region ph[2], yh[3];                      // SED_DTYPE_F16: the forward chain's fp16 p0, p1 / y1, y2 (p[], y[] are then the bf16 copies the backward reads)
+    Region gi[2], gates[2], out[2], whh[2], whhT[2];
+    Region wihT[2];                           // [nin][6H]: the two W_ih stacked along K and transposed (dX GEMM operand)
+    Region xch[2], epoch[2], err;             // cluster recurrence: exchange granules, launch epochs, spin-timeout flag
+    Region logits_s, strong_sv, weak_sv, den_sv;
+    Region mask[3];
     size_t total;
 };
-// SED_DEBUG_SAVED_GATES: block 0's forward SAVES its GLU gates (one byte per element) and the backward reads them instead of recomputing
-// z on the MFMA + exp2 + rcp per element.  Built and measured in round 6, NOT the default: at B = 64 the backward kernel goes
-// 89 -> 81 us but the student's forward 109 -> 128 us (164 MB of byte stores from a kernel that runs beside the teacher's) -
-// waveform-bf16 0.8008 -> 0.8211 ms, mt-bf16 0.4929 -> 0.4944 (profiles/r06_blk0_saved_gates_ab.txt).
-static inline bool blk0_saves_gates(const Geo& g) { return g.mode == SED_DTYPE_BF16 && (g_sed_debug & SED_DEBUG_SAVED_GATES); }
 static size_t mask_bytes(size_t Q, int C) { return ((Q + 3) / 4) * (size_t)(C / 32) * 64 * sizeof(uint16_t); }
 
 static GCtx make_gctx(const Geo& g) {
     GCtx L;
-    size_t o = 0;
-    auto put = [&](size_t& f, size_t bytes) { f = o; o = al(o + bytes); };
+    RegionCursor put;
     const size_t C = g.C, H = g.H, E = esz(g);
     const size_t n0 = (size_t)g.B * g.H1 * g.W1 * C, n1 = (size_t)g.B * g.H2 * g.W2 * C, n2 = (size_t)g.B * g.T3 * C;
     put(L.acc0, (64 + 4 * C) * sizeof(double));
-    L.mom0 = L.acc0; L.stat1 = L.acc0 + 64 * sizeof(double); L.stat2 = L.stat1 + 2 * C * sizeof(double);
-    put(L.wz0, C * 12 * 4); put(L.wl0, C * 12 * 4); put(L.bn0, 4 * C * 4);
+    L.mom0 = L.acc0.sub(0, 64 * sizeof(double));
+    L.stat[1] = L.acc0.sub(64 * sizeof(double), 2 * C * sizeof(double)); L.stat[2] = L.acc0.sub((64 + 2 * C) * sizeof(double), 2 * C * sizeof(double));
+    put(L.wz0, C * 12 * 4); put(L.wl0, C * 12 * 4); put(L.bn[0], 4 * C * 4);
     put(L.mompart, (size_t)x_moments_parts(g) * 54 * sizeof(double));
-    put(L.p0, n0 * E);
-    L.p[0] = L.p0;
+    put(L.p[0], n0 * E);
     const size_t nn[3] = {0, n0, n1}, np[3] = {n0, n1, n2};
     for (int i = 1; i <= 2; ++i) {
         put(L.wpk[i], 9 * C * C * E); put(L.wpkT[i], 9 * C * C * E); put(L.wg[i], C * C * E); put(L.wgT[i], C * C * E);
         put(L.bg[i], C * 4); put(L.y[i], nn[i] * E); put(L.bn[i], 4 * C * 4); put(L.p[i], np[i] * (i == 2 ? 4 : E));
     }
-    L.ph[0] = L.ph[1] = 0; L.yh[0] = L.yh[1] = L.yh[2] = 0;
     if (g.f16) { put(L.ph[0], n0 * 2); put(L.yh[1], n0 * 2); put(L.ph[1], n1 * 2); put(L.yh[2], n1 * 2); }
     const size_t bt = (size_t)g.B * g.T3;
     for (int l = 0; l < 2; ++l) {
@@ -78,23 +70,20 @@ static GCtx make_gctx(const Geo& g) {
     put(L.weak_sv, (size_t)g.B * g.NC * 4); put(L.den_sv, (size_t)g.B * g.NC * 4);
     put(L.mask[0], mask_bytes((size_t)g.B * g.H1 * g.W1, g.C)); put(L.mask[1], mask_bytes((size_t)g.B * g.H2 * g.W2, g.C));
     put(L.mask[2], mask_bytes((size_t)g.B * g.T3, g.C));
-    // (sized by the MODE alone, never by the debug bit: the caller allocated ctx from sed_crnn_ctx_bytes before any bit was set)
-    put(L.sg0, g.mode == SED_DTYPE_BF16 ? mask_bytes((size_t)g.B * g.H1 * g.W1, g.C) * 8 : 0);
-    L.total = o;
+    L.total = put.o;
     return L;
 }
 
 struct GWs {
-    size_t d_out, dgi[2], dgh[2], hprev[2], d_in, heads_part;
-    size_t dp[3], dz[3], coef[3];             // dp[i]: gradient w.r.t. block i's pooled output; dz / coef: blocks 1, 2
-    size_t glu_part, glu_part2, de0, wg_part, gemm_part;
-    size_t xch[2], epoch[2];
+    Region d_out, dgi[2], dgh[2], hprev[2], d_in, heads_part;
+    Region dp[3], dz[3], coef[3];             // dp[i]: gradient w.r.t. block i's pooled output; dz / coef: blocks 1, 2
+    Region glu_part, glu_part2, de0, wg_part, gemm_part;
+    Region xch[2], epoch[2];
     size_t total;
 };
 static GWs make_gws(const Geo& g) {
     GWs W;
-    size_t o = 0;
-    auto put = [&](size_t& f, size_t bytes) { f = o; o = al(o + bytes); };
+    RegionCursor put;
     const size_t C = g.C, H = g.H, bt = (size_t)g.B * g.T3;
     const size_t n0 = (size_t)g.B * g.H1 * g.W1 * C, n1 = (size_t)g.B * g.H2 * g.W2 * C;
     put(W.d_out, bt * 2 * H * 4);
@@ -103,7 +92,6 @@ static GWs make_gws(const Geo& g) {
     put(W.heads_part, heads_part_floats(g.B, g.T3, g.NC, 2 * H) * 4);
     const size_t E = esz(g);
     put(W.dp[2], 2 * bt * C * 4); put(W.dz[2], n1 * E); put(W.dp[1], n1 * E); put(W.dz[1], n0 * E); put(W.dp[0], n0 * E);
-    W.dz[0] = 0; W.coef[0] = 0;
     put(W.coef[1], 3 * C * 4); put(W.coef[2], 3 * C * 4);
     put(W.glu_part, (size_t)(g.mode == SED_DTYPE_BF16 ? bglu_bwd_grid(g.C, g.B, g.H1, g.W1) : gglu_bwd_grid(g.B, g.H1, g.W1)) * (C * C + 3 * C) * 4);
     put(W.glu_part2, (size_t)GPART_SLICES * (C * C + 3 * C) * 4);
@@ -111,7 +99,7 @@ static GWs make_gws(const Geo& g) {
     put(W.wg_part, (size_t)gwgrad_slabs(g.C) * 9 * C * C * 4);
     put(W.gemm_part, 2 * gru_gemm_part_floats(g) * 4);     // one per GRU layer: their batches may overlap in time
     for (int l = 0; l < 2; ++l) { put(W.xch[l], g.H == 256 ? gclu_xch_bytes(g.B, g.H, 1) : 0); put(W.epoch[l], (size_t)2 * g.B * 4); }
-    W.total = o;
+    W.total = put.o;
     return W;
 }
 
@@ -120,17 +108,14 @@ size_t gen_ws_bytes(const Geo& g) { return make_gws(g).total; }
 
 int gen_ctx_view(const Geo& g, const char* name, size_t* offset, size_t* bytes) {
     const GCtx L = make_gctx(g);
-    const size_t C = g.C, H = g.H, bt = (size_t)g.B * g.T3;
-    const size_t n0 = (size_t)g.B * g.H1 * g.W1 * C * esz(g), n1 = (size_t)g.B * g.H2 * g.W2 * C * esz(g);
-    struct { const char* n; size_t o, b; } tab[] = {
-        {"mom0", L.mom0, 64 * 8}, {"bn0", L.bn0, 4 * C * 4}, {"p0", L.p[0], n0}, {"y1", L.y[1], n0}, {"stat1", L.stat1, 2 * C * 8},
-        {"bn1", L.bn[1], 4 * C * 4}, {"p1", L.p[1], n1}, {"y2", L.y[2], n1}, {"stat2", L.stat2, 2 * C * 8}, {"bn2", L.bn[2], 4 * C * 4},
-        {"p2", L.p[2], bt * C * 4}, {"gates0", L.gates[0], bt * 8 * H * 4}, {"gates1", L.gates[1], bt * 8 * H * 4},
-        {"gru0", L.out[0], bt * 2 * H * 4}, {"gru1", L.out[1], bt * 2 * H * 4}, {"logits_s", L.logits_s, bt * g.NC * 4},
-        {"den", L.den_sv, (size_t)g.B * g.NC * 4}, {"gru_err", L.err, 4},
+    struct { const char* n; Region r; } tab[] = {
+        {"mom0", L.mom0}, {"bn0", L.bn[0]}, {"p0", L.p[0]}, {"y1", L.y[1]}, {"stat1", L.stat[1]}, {"bn1", L.bn[1]}, {"p1", L.p[1]},
+        {"y2", L.y[2]}, {"stat2", L.stat[2]}, {"bn2", L.bn[2]}, {"p2", L.p[2]}, {"gates0", L.gates[0]}, {"gates1", L.gates[1]},
+        {"gru0", L.out[0]}, {"gru1", L.out[1]}, {"logits_s", L.logits_s}, {"den", L.den_sv},
+        {"gru_err", L.err.sub(0, 4)},         // (the counter; its region is a whole 256-byte line)
     };
     for (auto& t : tab)
-        if (strcmp(t.n, name) == 0) { *offset = t.o; *bytes = t.b; return SED_OK; }
+        if (strcmp(t.n, name) == 0) { *offset = t.r.off; *bytes = t.r.bytes; return SED_OK; }
     sed_set_error("sed_crnn_ctx_view: unknown buffer '%s'", name);
     return SED_ERR_BAD_ARG;
 }
@@ -144,47 +129,40 @@ int gen_buffers_init(const Geo& g, void* ctx, size_t ctx_bytes, void* ws, size_t
         if (ctx_bytes < L.total) { sed_set_error("sed_crnn_buffers_init: ctx has %zu bytes, needs %zu", ctx_bytes, L.total); return SED_ERR_WORKSPACE; }
         // xch[0] .. err are laid out back to back apart from the small per-layer W_ih transposes: clear each piece
         for (int l = 0; l < 2; ++l) {
-            if (g.H == 256) SED_CHECK_HIP(hipMemsetAsync((char*)ctx + L.xch[l], 0, gclu_xch_bytes(g.B, g.H, 0), st));
-            SED_CHECK_HIP(hipMemsetAsync((char*)ctx + L.epoch[l], 0, (size_t)2 * g.B * 4, st));
+            if (L.xch[l].bytes) SED_CHECK_HIP(hipMemsetAsync(L.xch[l].v(ctx), 0, L.xch[l].bytes, st));
+            SED_CHECK_HIP(hipMemsetAsync(L.epoch[l].v(ctx), 0, L.epoch[l].bytes, st));
         }
-        SED_CHECK_HIP(hipMemsetAsync((char*)ctx + L.err, 0, 256, st));
+        SED_CHECK_HIP(hipMemsetAsync(L.err.v(ctx), 0, L.err.bytes, st));
     }
     if (ws) {
         const GWs W = make_gws(g);
         if (ws_bytes < W.total) { sed_set_error("sed_crnn_buffers_init: ws has %zu bytes, needs %zu", ws_bytes, W.total); return SED_ERR_WORKSPACE; }
         for (int l = 0; l < 2; ++l) {
-            if (g.H == 256) SED_CHECK_HIP(hipMemsetAsync((char*)ws + W.xch[l], 0, gclu_xch_bytes(g.B, g.H, 1), st));
-            SED_CHECK_HIP(hipMemsetAsync((char*)ws + W.epoch[l], 0, (size_t)2 * g.B * 4, st));
+            if (W.xch[l].bytes) SED_CHECK_HIP(hipMemsetAsync(W.xch[l].v(ws), 0, W.xch[l].bytes, st));
+            SED_CHECK_HIP(hipMemsetAsync(W.epoch[l].v(ws), 0, W.epoch[l].bytes, st));
         }
     }
     return SED_OK;
 }
 
-#define CTXF(off) ((float*)((char*)ctx + (off)))
-#define CTXD(off) ((double*)((char*)ctx + (off)))
-#define CTXV(off) ((void*)((char*)ctx + (off)))
-#define CTXM(off) ((uint16_t*)((char*)ctx + (off)))
-#define WSF(off) ((float*)((char*)ws + (off)))
-#define WSD(off) ((double*)((char*)ws + (off)))
-
 // the recurrent tail's buffers in the generic layouts (ws == null: a forward)
 static RnnBufs rnn_bufs(const Geo& g, const GCtx& L, void* ctx, const GWs* Wp, void* ws) {
     RnnBufs R;
-    R.p2 = CTXF(L.p[2]);
-    R.logits_s = CTXF(L.logits_s); R.strong_sv = CTXF(L.strong_sv); R.weak_sv = CTXF(L.weak_sv); R.den_sv = CTXF(L.den_sv);
-    R.err = (int*)CTXV(L.err);
+    R.p2 = L.p[2].f(ctx);
+    R.logits_s = L.logits_s.f(ctx); R.strong_sv = L.strong_sv.f(ctx); R.weak_sv = L.weak_sv.f(ctx); R.den_sv = L.den_sv.f(ctx);
+    R.err = (int*)L.err.v(ctx);
     for (int l = 0; l < 2; ++l) {
-        R.out[l] = CTXF(L.out[l]); R.gates[l] = CTXF(L.gates[l]);
-        R.gi[l] = CTXF(L.gi[l]); R.wihT[l] = CTXF(L.wihT[l]); R.whh[l] = CTXV(L.whh[l]); R.whhT[l] = CTXV(L.whhT[l]);
-        R.xch[l] = ws ? (void*)((char*)ws + Wp->xch[l]) : CTXV(L.xch[l]);
-        R.epoch[l] = (unsigned int*)(ws ? (void*)((char*)ws + Wp->epoch[l]) : CTXV(L.epoch[l]));
+        R.out[l] = L.out[l].f(ctx); R.gates[l] = L.gates[l].f(ctx);
+        R.gi[l] = L.gi[l].f(ctx); R.wihT[l] = L.wihT[l].f(ctx); R.whh[l] = L.whh[l].v(ctx); R.whhT[l] = L.whhT[l].v(ctx);
+        R.xch[l] = ws ? Wp->xch[l].v(ws) : L.xch[l].v(ctx);
+        R.epoch[l] = (unsigned int*)(ws ? Wp->epoch[l].v(ws) : L.epoch[l].v(ctx));
     }
     if (ws == nullptr) return R;
     const GWs& W = *Wp;
-    R.d_out = WSF(W.d_out); R.d_in = WSF(W.d_in); R.dp2 = WSF(W.dp[2]); R.heads_part = WSF(W.heads_part);
-    for (int l = 0; l < 2; ++l) { R.dgi[l] = WSF(W.dgi[l]); R.dgh[l] = WSF(W.dgh[l]); R.hprev[l] = WSF(W.hprev[l]); }
-    R.gemm_part = WSF(W.gemm_part); R.gemm_part_floats = R.gemm_part_stride = gru_gemm_part_floats(g); R.splitk = gru_splitk(g);
-    R.zero = WSD(W.de0); R.n_zero = 2 * g.C * 10;
+    R.d_out = W.d_out.f(ws); R.d_in = W.d_in.f(ws); R.dp2 = W.dp[2].f(ws); R.heads_part = W.heads_part.f(ws);
+    for (int l = 0; l < 2; ++l) { R.dgi[l] = W.dgi[l].f(ws); R.dgh[l] = W.dgh[l].f(ws); R.hprev[l] = W.hprev[l].f(ws); }
+    R.gemm_part = W.gemm_part.f(ws); R.gemm_part_floats = R.gemm_part_stride = gru_gemm_part_floats(g); R.splitk = gru_splitk(g);
+    R.zero = W.de0.d(ws); R.n_zero = (int)(W.de0.bytes / sizeof(double));
     return R;
 }
 
@@ -194,7 +172,7 @@ int gen_mompart(const Geo& g, void* ctx, size_t ctx_bytes, double** out) {
         sed_set_error("sed_crnn_moments: ctx has %zu bytes, needs %zu", ctx_bytes, L.total);
         return SED_ERR_WORKSPACE;
     }
-    *out = (double*)((char*)ctx + L.mompart);
+    *out = L.mompart.d(ctx);
     return SED_OK;
 }
 
@@ -221,14 +199,14 @@ int gen_forward(const Geo& g, const ParamOff& P, const float* params, float* bn_
     GenPackArgs pk = {};
     pk.C = C;
     pk.w1 = params + P.conv_w[1]; pk.w2 = params + P.conv_w[2];
-    pk.wpk1 = CTXV(L.wpk[1]); pk.wpk2 = CTXV(L.wpk[2]);
-    pk.wpkT1 = train ? CTXV(L.wpkT[1]) : nullptr; pk.wpkT2 = train ? CTXV(L.wpkT[2]) : nullptr;
+    pk.wpk1 = L.wpk[1].v(ctx); pk.wpk2 = L.wpk[2].v(ctx);
+    pk.wpkT1 = train ? L.wpkT[1].v(ctx) : nullptr; pk.wpkT2 = train ? L.wpkT[2].v(ctx) : nullptr;
     pk.glu_w1 = params + P.glu_w[1]; pk.glu_w2 = params + P.glu_w[2]; pk.glu_b1 = params + P.glu_b[1]; pk.glu_b2 = params + P.glu_b[2];
     pk.gamma1 = params + P.bn_g[1]; pk.gamma2 = params + P.bn_g[2]; pk.beta1 = params + P.bn_b[1]; pk.beta2 = params + P.bn_b[2];
-    pk.wg1 = CTXV(L.wg[1]); pk.wg2 = CTXV(L.wg[2]);
-    pk.wgT1 = train ? CTXV(L.wgT[1]) : nullptr; pk.wgT2 = train ? CTXV(L.wgT[2]) : nullptr;
-    pk.bg1 = CTXF(L.bg[1]); pk.bg2 = CTXF(L.bg[2]);
-    pk.zero = CTXD(L.stat1); pk.n_zero = train ? 4 * C : 0;
+    pk.wg1 = L.wg[1].v(ctx); pk.wg2 = L.wg[2].v(ctx);
+    pk.wgT1 = train ? L.wgT[1].v(ctx) : nullptr; pk.wgT2 = train ? L.wgT[2].v(ctx) : nullptr;
+    pk.bg1 = L.bg[1].f(ctx); pk.bg2 = L.bg[2].f(ctx);
+    pk.zero = L.stat[1].d(ctx); pk.n_zero = train ? 4 * C : 0;
     pk.f16 = g.f16 ? 1 : 0;
     // (The packing is independent of block 0, but forking it onto the helper stream is not an option: a forward that
     // itself runs on a forked stream - the teacher's, next to the student's - would fork a second time inside the same
@@ -241,7 +219,7 @@ int gen_forward(const Geo& g, const ParamOff& P, const float* params, float* bn_
         aux.pk = pk; aux.mode = g.mode; aux.n_gnt = 0;
         if (H != 64)
             for (int l = 0; l < g.L && l < 2; ++l) {
-                aux.gw0[l] = params + P.w_ih[l][0]; aux.gw1[l] = params + P.w_ih[l][1]; aux.gout[l] = CTXF(L.wihT[l]);
+                aux.gw0[l] = params + P.w_ih[l][0]; aux.gw1[l] = params + P.w_ih[l][1]; aux.gout[l] = L.wihT[l].f(ctx);
                 aux.gR[l] = 3 * H; aux.gN[l] = (l == 0) ? C : 2 * H;
                 aux.n_gnt = l + 1;
             }
@@ -249,7 +227,7 @@ int gen_forward(const Geo& g, const ParamOff& P, const float* params, float* bn_
         if (H == 256 && g.mode == SED_DTYPE_BF16)
             for (int l = 0; l < g.L && l < 2; ++l) {
                 aux.rw0[l] = params + P.w_hh[l][0]; aux.rw1[l] = params + P.w_hh[l][1];
-                aux.rwp[l] = CTXV(L.whh[l]); aux.rwpT[l] = CTXV(L.whhT[l]);
+                aux.rwp[l] = L.whh[l].v(ctx); aux.rwpT[l] = L.whhT[l].v(ctx);
                 aux.n_grec = l + 1;
             }
     } else {
@@ -259,19 +237,17 @@ int gen_forward(const Geo& g, const ParamOff& P, const float* params, float* bn_
     // ---- conv block 0 -------------------------------------------------------------------------------------------------
     SED_TRY(launch_blk0_forward(g, x, params + P.conv_w[0], params + P.conv_b[0], params + P.bn_g[0], params + P.bn_b[0],
                                 params + P.glu_w[0], params + P.glu_b[0], bn_running + 0, bn_running + C, trk[0], train, upd,
-                                seed_dev, CTXD(L.mom0), CTXD(L.mompart), CTXF(L.wz0), CTXF(L.wl0), CTXF(L.bn0),
-                                g.f16 ? CTXF(L.ph[0]) : CTXF(L.p[0]),
-                                use_drop ? CTXM(L.mask[0]) : nullptr, nullptr, st, 0, aux_pack ? &aux : nullptr,
-                                (g.f16 && keep_b16) ? CTXV(L.p[0]) : nullptr, mom_ready,
-                                (train && !(train & 2) && blk0_saves_gates(g)) ? CTXV(L.sg0) : nullptr));
+                                seed_dev, L.mom0.d(ctx), L.mompart.d(ctx), L.wz0.f(ctx), L.wl0.f(ctx), L.bn[0].f(ctx),
+                                g.f16 ? L.ph[0].f(ctx) : L.p[0].f(ctx),
+                                use_drop ? L.mask[0].m(ctx) : nullptr, nullptr, st, 0, aux_pack ? &aux : nullptr,
+                                (g.f16 && keep_b16) ? L.p[0].v(ctx) : nullptr, mom_ready));
     // ---- conv blocks 1, 2 -----------------------------------------------------------------------------------------------
-    const size_t so[3] = {0, L.stat1, L.stat2};
     const int Hs[3] = {0, g.H1, g.H2}, Wd[3] = {0, g.W1, g.W2};
     auto bn_args = [&](int i) {
         GBnArgs bn;
-        bn.stat = CTXD(so[i]); bn.N = (double)g.B * Hs[i] * Wd[i]; bn.gamma = params + P.bn_g[i]; bn.beta = params + P.bn_b[i];
+        bn.stat = L.stat[i].d(ctx); bn.N = (double)g.B * Hs[i] * Wd[i]; bn.gamma = params + P.bn_g[i]; bn.beta = params + P.bn_b[i];
         bn.run_mean = bn_running + (2 * i) * C; bn.run_var = bn_running + (2 * i + 1) * C; bn.tracked = trk[i];
-        bn.train = train; bn.update = upd; bn.eps = g.eps; bn.momentum = g.mom; bn.bn = CTXF(L.bn[i]);
+        bn.train = train; bn.update = upd; bn.eps = g.eps; bn.momentum = g.mom; bn.bn = L.bn[i].f(ctx);
         return bn;
     };
     for (int i = 1; i <= 2; ++i) {
@@ -279,30 +255,30 @@ int gen_forward(const Geo& g, const ParamOff& P, const float* params, float* bn_
         if (g.f16) {
             // SED_DTYPE_F16: the forward chain runs on the fp16 tensors ph / yh; a training forward also leaves the bf16 copies
             // y[i] / p[i] that the (bf16-family) backward kernels read
-            SED_TRY(launch_bconv_fwd(2, C, CTXV(L.ph[i - 1]), CTXV(L.wpk[i]), params + P.conv_b[i], CTXV(L.yh[i]),
-                                     train ? CTXD(so[i]) : nullptr, g.B, Hs[i], Wd[i], st));
-            SED_TRY(launch_bglu_fwd(C, CTXV(L.yh[i]), bn, params + P.glu_w[i], params + P.glu_b[i], i == 1 ? CTXV(L.ph[1]) : CTXV(L.p[2]),
-                                    i == 1 ? 1 : 0, g.B, Hs[i], Wd[i], i, use_drop, g.p, seed_dev, use_drop ? CTXM(L.mask[i]) : nullptr,
-                                    train ? CTXV(L.wg[i]) : nullptr, train ? CTXF(L.bg[i]) : nullptr, st, 1,
-                                    (i == 1 && keep_b16) ? CTXV(L.p[1]) : nullptr, keep_b16 ? CTXV(L.y[i]) : nullptr));
+            SED_TRY(launch_bconv_fwd(2, C, L.ph[i - 1].v(ctx), L.wpk[i].v(ctx), params + P.conv_b[i], L.yh[i].v(ctx),
+                                     train ? L.stat[i].d(ctx) : nullptr, g.B, Hs[i], Wd[i], st));
+            SED_TRY(launch_bglu_fwd(C, L.yh[i].v(ctx), bn, params + P.glu_w[i], params + P.glu_b[i], i == 1 ? L.ph[1].v(ctx) : L.p[2].v(ctx),
+                                    i == 1 ? 1 : 0, g.B, Hs[i], Wd[i], i, use_drop, g.p, seed_dev, use_drop ? L.mask[i].m(ctx) : nullptr,
+                                    train ? L.wg[i].v(ctx) : nullptr, train ? L.bg[i].f(ctx) : nullptr, st, 1,
+                                    (i == 1 && keep_b16) ? L.p[1].v(ctx) : nullptr, keep_b16 ? L.y[i].v(ctx) : nullptr));
             continue;
         }
         if (g.mode != SED_DTYPE_F32)      // bf16 (bf16 storage) / bf16x3 (fp32 storage, split operands): bconv.hip
-            SED_TRY(launch_bconv_fwd(g.mode == SED_DTYPE_BF16X3, C, CTXV(L.p[i - 1]), CTXV(L.wpk[i]), params + P.conv_b[i], CTXV(L.y[i]),
-                                     train ? CTXD(so[i]) : nullptr, g.B, Hs[i], Wd[i], st));
+            SED_TRY(launch_bconv_fwd(g.mode == SED_DTYPE_BF16X3, C, L.p[i - 1].v(ctx), L.wpk[i].v(ctx), params + P.conv_b[i], L.y[i].v(ctx),
+                                     train ? L.stat[i].d(ctx) : nullptr, g.B, Hs[i], Wd[i], st));
         else
-            SED_TRY(launch_gconv_fwd(C, CTXF(L.p[i - 1]), CTXV(L.wpk[i]), params + P.conv_b[i], CTXF(L.y[i]),
-                                     train ? CTXD(so[i]) : nullptr, g.B, Hs[i], Wd[i], st));
+            SED_TRY(launch_gconv_fwd(C, L.p[i - 1].f(ctx), L.wpk[i].v(ctx), params + P.conv_b[i], L.y[i].f(ctx),
+                                     train ? L.stat[i].d(ctx) : nullptr, g.B, Hs[i], Wd[i], st));
         if (g.mode == SED_DTYPE_BF16)
-            SED_TRY(launch_bglu_fwd(C, CTXV(L.y[i]), bn, params + P.glu_w[i], params + P.glu_b[i], CTXV(L.p[i]), i == 1 ? 1 : 0, g.B,
-                                    Hs[i], Wd[i], i, use_drop, g.p, seed_dev, use_drop ? CTXM(L.mask[i]) : nullptr,
-                                    train ? CTXV(L.wg[i]) : nullptr, train ? CTXF(L.bg[i]) : nullptr, st));
+            SED_TRY(launch_bglu_fwd(C, L.y[i].v(ctx), bn, params + P.glu_w[i], params + P.glu_b[i], L.p[i].v(ctx), i == 1 ? 1 : 0, g.B,
+                                    Hs[i], Wd[i], i, use_drop, g.p, seed_dev, use_drop ? L.mask[i].m(ctx) : nullptr,
+                                    train ? L.wg[i].v(ctx) : nullptr, train ? L.bg[i].f(ctx) : nullptr, st));
         else if (g.mode == SED_DTYPE_BF16X3)
-            SED_TRY(launch_bglu_fwd_x3(C, CTXV(L.y[i]), bn, params + P.glu_w[i], params + P.glu_b[i], CTXV(L.p[i]), g.B, Hs[i], Wd[i], i,
-                                       use_drop, g.p, seed_dev, use_drop ? CTXM(L.mask[i]) : nullptr, st));
+            SED_TRY(launch_bglu_fwd_x3(C, L.y[i].v(ctx), bn, params + P.glu_w[i], params + P.glu_b[i], L.p[i].v(ctx), g.B, Hs[i], Wd[i], i,
+                                       use_drop, g.p, seed_dev, use_drop ? L.mask[i].m(ctx) : nullptr, st));
         else
-            SED_TRY(launch_gglu_fwd(C, CTXV(L.y[i]), bn, CTXV(L.wg[i]), CTXF(L.bg[i]), CTXV(L.p[i]), g.B, Hs[i], Wd[i], i, use_drop, g.p,
-                                    seed_dev, use_drop ? CTXM(L.mask[i]) : nullptr, st));
+            SED_TRY(launch_gglu_fwd(C, L.y[i].v(ctx), bn, L.wg[i].v(ctx), L.bg[i].f(ctx), L.p[i].v(ctx), g.B, Hs[i], Wd[i], i, use_drop, g.p,
+                                    seed_dev, use_drop ? L.mask[i].m(ctx) : nullptr, st));
     }
     // ---- BiGRU + heads ---------------------------------------------------------------------------------------------------
     return rnn_forward(g, P, params, rnn_bufs(g, L, ctx, nullptr, nullptr), train, seed_dev, strong, weak, aux.n_grec, st);
@@ -325,23 +301,23 @@ int gen_backward(const Geo& g, const ParamOff& P, const float* params, const flo
     SED_TRY(rnn_backward(rb, d_strong, d_weak, st));
     if (!(parts & 2)) return SED_OK;
     // ---- conv blocks 2, 1 -------------------------------------------------------------------------------------------------
-    if (!(parts & 1)) SED_CHECK_HIP(hipMemsetAsync(WSD(W.de0), 0, 2 * C * 10 * sizeof(double), st));
+    if (!(parts & 1)) SED_CHECK_HIP(hipMemsetAsync(W.de0.d(ws), 0, W.de0.bytes, st));
     const int Hs[3] = {0, g.H1, g.H2}, Wd[3] = {0, g.W1, g.W2};
     for (int i = 2; i >= 1; --i) {
         // (H = 64: the GRU's dX arrives as two direction planes; the GLU backward adds them while loading)
-        const float* dp2 = (i == 2 && H == 64) ? WSF(W.dp[2]) + (size_t)BT * C : nullptr;
+        const float* dp2 = (i == 2 && H == 64) ? W.dp[2].f(ws) + (size_t)BT * C : nullptr;
         const bool bf16_glu = g.mode == SED_DTYPE_BF16;      // bglu.hip (bf16 storage); fp32 and bf16x3: gglu.hip
         if (bf16_glu)
-            SED_TRY(launch_bglu_bwd(C, CTXV(L.y[i]), CTXF(L.bn[i]), CTXV(L.wg[i]), CTXF(L.bg[i]), CTXV(L.wgT[i]), WSF(W.dp[i]), i == 1 ? 1 : 0,
-                                    WSF(W.dz[i]), WSF(W.glu_part), g.B, Hs[i], Wd[i], use_drop, g.p, CTXM(L.mask[i]), st, dp2));
+            SED_TRY(launch_bglu_bwd(C, L.y[i].v(ctx), L.bn[i].f(ctx), L.wg[i].v(ctx), L.bg[i].f(ctx), L.wgT[i].v(ctx), W.dp[i].f(ws), i == 1 ? 1 : 0,
+                                    W.dz[i].f(ws), W.glu_part.f(ws), g.B, Hs[i], Wd[i], use_drop, g.p, L.mask[i].m(ctx), st, dp2));
         else
-            SED_TRY(launch_gglu_bwd(C, CTXV(L.y[i]), CTXF(L.bn[i]), params + P.bn_g[i], params + P.bn_b[i], CTXV(L.wg[i]), CTXV(L.wgT[i]),
-                                    CTXF(L.bg[i]), WSF(W.dp[i]), WSF(W.dz[i]), WSF(W.glu_part), g.B, Hs[i], Wd[i], use_drop, g.p,
-                                    CTXM(L.mask[i]), st, dp2));
+            SED_TRY(launch_gglu_bwd(C, L.y[i].v(ctx), L.bn[i].f(ctx), params + P.bn_g[i], params + P.bn_b[i], L.wg[i].v(ctx), L.wgT[i].v(ctx),
+                                    L.bg[i].f(ctx), W.dp[i].f(ws), W.dz[i].f(ws), W.glu_part.f(ws), g.B, Hs[i], Wd[i], use_drop, g.p,
+                                    L.mask[i].m(ctx), st, dp2));
         GBnBwdArgs pa;
-        pa.part = WSF(W.glu_part); pa.n_part = bf16_glu ? bglu_bwd_grid(C, g.B, Hs[i], Wd[i]) : gglu_bwd_grid(g.B, Hs[i], Wd[i]); pa.C = C; pa.N = (double)g.B * Hs[i] * Wd[i];
-        pa.part2 = WSF(W.glu_part2);
-        pa.gamma = params + P.bn_g[i]; pa.beta = params + P.bn_b[i]; pa.bn = CTXF(L.bn[i]); pa.coef = WSF(W.coef[i]);
+        pa.part = W.glu_part.f(ws); pa.n_part = bf16_glu ? bglu_bwd_grid(C, g.B, Hs[i], Wd[i]) : gglu_bwd_grid(g.B, Hs[i], Wd[i]); pa.C = C; pa.N = (double)g.B * Hs[i] * Wd[i];
+        pa.part2 = W.glu_part2.f(ws);
+        pa.gamma = params + P.bn_g[i]; pa.beta = params + P.bn_b[i]; pa.bn = L.bn[i].f(ctx); pa.coef = W.coef[i].f(ws);
         pa.g_gamma = grads + P.bn_g[i]; pa.g_beta = grads + P.bn_b[i]; pa.g_wglu = grads + P.glu_w[i]; pa.g_bglu = grads + P.glu_b[i];
         pa.g_convb = grads + P.conv_b[i];
         SED_TRY(launch_gbn_bwd_prep(pa, st));
@@ -349,21 +325,21 @@ int gen_backward(const Geo& g, const ParamOff& P, const float* params, const flo
         // data gradient - the critical chain - is captured between the two halves of the fork (SideFork)
         SED_TRY(side.mark(st));
         if (g.mode != SED_DTYPE_F32)
-            SED_TRY(launch_bconv_dgrad(g.mode == SED_DTYPE_BF16X3, C, WSF(W.dz[i]), CTXV(L.y[i]), WSF(W.coef[i]), CTXV(L.wpkT[i]),
-                                       WSF(W.dp[i - 1]), g.B, Hs[i], Wd[i], st));
+            SED_TRY(launch_bconv_dgrad(g.mode == SED_DTYPE_BF16X3, C, W.dz[i].f(ws), L.y[i].v(ctx), W.coef[i].f(ws), L.wpkT[i].v(ctx),
+                                       W.dp[i - 1].f(ws), g.B, Hs[i], Wd[i], st));
         else
-            SED_TRY(launch_gconv_dgrad(C, WSF(W.dz[i]), CTXF(L.y[i]), WSF(W.coef[i]), CTXV(L.wpkT[i]), WSF(W.dp[i - 1]), g.B, Hs[i], Wd[i],
+            SED_TRY(launch_gconv_dgrad(C, W.dz[i].f(ws), L.y[i].f(ctx), W.coef[i].f(ws), L.wpkT[i].v(ctx), W.dp[i - 1].f(ws), g.B, Hs[i], Wd[i],
                                        st));
         SED_TRY(side.start());
-        SED_TRY(launch_gwgrad(g.mode, C, WSF(W.dz[i]), CTXF(L.y[i]), WSF(W.coef[i]), CTXF(L.p[i - 1]), WSF(W.wg_part), grads + P.conv_w[i], g.B,
+        SED_TRY(launch_gwgrad(g.mode, C, W.dz[i].f(ws), L.y[i].f(ctx), W.coef[i].f(ws), L.p[i - 1].f(ctx), W.wg_part.f(ws), grads + P.conv_w[i], g.B,
                               Hs[i], Wd[i], side.s));
         if (i == 2) SED_TRY(rnn_deferred_weight_grads(rb));      // parts == 3, H = 64: head column sum + GRU dW / db behind wgrad2
     }
     // ---- conv block 0 -----------------------------------------------------------------------------------------------------
     SED_TRY(launch_blk0_backward(g, x, params + P.conv_w[0], params + P.conv_b[0], params + P.bn_g[0], params + P.bn_b[0],
-                                 params + P.glu_w[0], CTXM(L.mask[0]), CTXD(L.mom0), CTXF(L.wz0), CTXF(L.wl0), CTXF(L.bn0), WSF(W.dp[0]),
-                                 WSD(W.de0), 0, grads + P.conv_w[0], grads + P.conv_b[0], grads + P.bn_g[0], grads + P.bn_b[0],
-                                 grads + P.glu_w[0], grads + P.glu_b[0], st, blk0_saves_gates(g) ? CTXV(L.sg0) : nullptr));
+                                 params + P.glu_w[0], L.mask[0].m(ctx), L.mom0.d(ctx), L.wz0.f(ctx), L.wl0.f(ctx), L.bn[0].f(ctx), W.dp[0].f(ws),
+                                 W.de0.d(ws), 0, grads + P.conv_w[0], grads + P.conv_b[0], grads + P.bn_g[0], grads + P.bn_b[0],
+                                 grads + P.glu_w[0], grads + P.glu_b[0], st));
     return side.join(st);
 }
 

@@ -49,6 +49,12 @@ struct RnnBufs {
 
 int rnn_forward(const Geo& g, const ParamOff& P, const float* params, const RnnBufs& R, int train, const uint64_t* seed_dev,
                 float* strong, float* weak, int n_whh_packed, hipStream_t st);
+// what rnn_forward / rnn_backward launch per layer for H = 64, and the heads' forward: one binding each, also re-launched alone
+// by sed_kernel_replay (crnn.hip)
+int rnn_gru_fwd64(const Geo& g, const ParamOff& P, const float* params, const RnnBufs& R, int l, int train, hipStream_t st);
+int rnn_gru_bwd64(const Geo& g, const ParamOff& P, const float* params, const RnnBufs& R, int l, hipStream_t st);      // (not the fused-heads form)
+int rnn_heads_fwd(const Geo& g, const ParamOff& P, const float* params, const RnnBufs& R, float* strong, float* weak, bool save,
+                  int use_drop, const uint64_t* seed_dev, hipStream_t st);
 
 // One backward call's view of the tail.  rnn_backward_plan fills it in (the fuse / defer_colsum / early_gru_w decisions are
 // taken there and nowhere else); the orchestrator then calls rnn_backward in front of its conv-block half,

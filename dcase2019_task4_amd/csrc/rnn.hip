@@ -6,6 +6,31 @@
 #include "rnn.h"
 #include "gkernels.h"
 
+// ---- the launches of the H = 64 tail that sed_kernel_replay (crnn.hip) re-launches alone: each launcher is bound HERE, once;
+//      rnn_forward and rnn_backward below run the same functions ----------------------------------------------------------------
+// the input projection x W_ih^T + b_ih runs inside the recurrence kernel (gi only exists in LDS)
+int rnn_gru_fwd64(const Geo& g, const ParamOff& P, const float* params, const RnnBufs& R, int l, int train, hipStream_t st) {
+    return launch_gru_fwd(l == 0 ? R.p2 : R.out[l - 1], l == 0 ? g.C : 2 * g.H, params + P.w_ih[l][0], params + P.w_ih[l][1],
+                          params + P.b_ih[l][0], params + P.b_ih[l][1], params + P.w_hh[l][0], params + P.w_hh[l][1],
+                          params + P.b_hh[l][0], params + P.b_hh[l][1], R.out[l], train ? R.gates[l] : nullptr, g.B, g.T3, st);
+}
+// The gradient w.r.t. a layer's input is produced INSIDE the recurrence kernel (two extra waves, one block of steps behind), as
+// two direction planes [2][B*T'][nin] that the consumer adds while loading: the layer below's recurrence kernel (planes in d_in),
+// or the block-2 GLU backward for layer 0 (planes in dp2).  The top layer reads the heads' one tensor d_out.
+int rnn_gru_bwd64(const Geo& g, const ParamOff& P, const float* params, const RnnBufs& R, int l, hipStream_t st) {
+    const bool top = l == g.L - 1;
+    return launch_gru_bwd(top ? R.d_out : R.d_in, top ? nullptr : R.d_in + (size_t)g.B * g.T3 * 2 * g.H, R.out[l], R.gates[l],
+                          params + P.w_hh[l][0], params + P.w_hh[l][1], params + P.w_ih[l][0], params + P.w_ih[l][1],
+                          l == 0 ? g.C : 2 * g.H, R.dgi[l], R.dgh[l], R.hprev[l], l == 0 ? R.dp2 : R.d_in, g.B, g.T3, st);
+}
+// save: the posteriors are also kept for the backward (strong_sv, weak_sv)
+int rnn_heads_fwd(const Geo& g, const ParamOff& P, const float* params, const RnnBufs& R, float* strong, float* weak, bool save,
+                  int use_drop, const uint64_t* seed_dev, hipStream_t st) {
+    return launch_heads_fwd(R.out[g.L - 1], params + P.dense_w, params + P.dense_b, params + P.soft_w, params + P.soft_b, strong, weak,
+                            save ? R.strong_sv : nullptr, save ? R.weak_sv : nullptr, R.logits_s, R.den_sv, g.B, g.T3, g.NC, use_drop,
+                            g.p, seed_dev, st, 2 * g.H);
+}
+
 int rnn_forward(const Geo& g, const ParamOff& P, const float* params, const RnnBufs& R, int train, const uint64_t* seed_dev,
                 float* strong, float* weak, int n_whh_packed, hipStream_t st) {
     const int H = g.H, BT = g.B * g.T3, use_drop = (train && g.p > 0.f) ? 1 : 0;
@@ -16,10 +41,7 @@ int rnn_forward(const Geo& g, const ParamOff& P, const float* params, const RnnB
     int nin = g.C;
     for (int l = 0; l < g.L; ++l) {
         if (H == 64) {
-            // the input projection x W_ih^T + b_ih runs inside the recurrence kernel (gi only exists in LDS)
-            SED_TRY(launch_gru_fwd(in, nin, params + P.w_ih[l][0], params + P.w_ih[l][1], params + P.b_ih[l][0], params + P.b_ih[l][1],
-                                   params + P.w_hh[l][0], params + P.w_hh[l][1], params + P.b_hh[l][0], params + P.b_hh[l][1],
-                                   R.out[l], train ? R.gates[l] : nullptr, g.B, g.T3, st));
+            SED_TRY(rnn_gru_fwd64(g, P, params, R, l, train, st));
         } else {
             // gi[bt][dir][3H] = x W_ih[dir]^T + b_ih[dir]: both directions in one launch (ggemm.hip)
             GntBatch gb;
@@ -42,9 +64,7 @@ int rnn_forward(const Geo& g, const ParamOff& P, const float* params, const RnnB
     }
     // ---- heads ----------------------------------------------------------------------------------------------------------
     if (strong == nullptr) return SED_OK;                 // deferred (sed_mt_step_backward)
-    return launch_heads_fwd(in, params + P.dense_w, params + P.dense_b, params + P.soft_w, params + P.soft_b, strong, weak,
-                            train ? R.strong_sv : nullptr, train ? R.weak_sv : nullptr, R.logits_s, R.den_sv, g.B, g.T3, g.NC,
-                            use_drop, g.p, seed_dev, st, 2 * H);
+    return rnn_heads_fwd(g, P, params, R, strong, weak, train != 0, use_drop, seed_dev, st);
 }
 
 RnnBwd rnn_backward_plan(const Geo& g, const ParamOff& P, const RnnBufs& R, const float* params, float* grads,
@@ -148,21 +168,15 @@ int rnn_backward(const RnnBwd& rb, const float* d_strong, const float* d_weak, h
     if (parts & 1) {
         // ---- heads ------------------------------------------------------------------------------------------------------
         const float* h_last = R.out[g.L - 1];
-        if (rb.ho && !rb.fuse)
-            SED_TRY(launch_heads_fwd(h_last, params + P.dense_w, params + P.dense_b, params + P.soft_w, params + P.soft_b, rb.ho->strong,
-                                     rb.ho->weak, R.strong_sv, R.weak_sv, R.logits_s, R.den_sv, g.B, g.T3, g.NC, use_drop, g.p,
-                                     rb.seed_dev, st, 2 * H));
+        if (rb.ho && !rb.fuse) SED_TRY(rnn_heads_fwd(g, P, params, R, rb.ho->strong, rb.ho->weak, true, use_drop, rb.seed_dev, st));
         if (!rb.fuse)
             SED_TRY(launch_heads_bwd(h_last, params + P.dense_w, params + P.soft_w, R.strong_sv, R.weak_sv, R.logits_s, R.den_sv, d_strong,
                                      d_weak, R.d_out, R.heads_part, grads + P.dense_w, grads + P.dense_b, grads + P.soft_w,
                                      grads + P.soft_b, g.B, g.T3, g.NC, use_drop, g.p, rb.seed_dev, (parts & 2) ? R.zero : nullptr,
                                      R.n_zero, rb.defer_colsum ? 1 : 0, rb.hl, st, 2 * H));
         // ---- BiGRU ------------------------------------------------------------------------------------------------------
-        // H = 64: the gradient w.r.t. each layer's input is produced INSIDE the recurrence kernel (two extra waves, one block of
-        // steps behind), as two direction planes [2][B*T'][nin] that the consumer adds while loading: the layer below's
-        // recurrence kernel, or the block-2 GLU backward for layer 0 (planes in dp2).  H = 256: one tensor, from a GEMM.
+        // H = 64: rnn_gru_bwd64 (dX as two direction planes).  H = 256: one tensor, from a GEMM.
         const float* d_cur = R.d_out;
-        const float* d_cur2 = nullptr;
         for (int l = g.L - 1; l >= 0; --l) {
             const int nin = (l == 0) ? g.C : 2 * H;
             float* d_in = (l == 0) ? R.dp2 : R.d_in;
@@ -178,8 +192,7 @@ int rnn_backward(const RnnBwd& rb, const float* d_strong, const float* d_weak, h
                     if (!rb.defer_colsum) SED_TRY(rnn_heads_colsum(rb, st));
                     else if (parts & 4) SED_TRY(launch_heads_fin(R.heads_part, grads + P.dense_w, g.B, g.T3, g.NC, 0, *rb.hl, st));
                 } else
-                    SED_TRY(launch_gru_bwd(d_cur, d_cur2, R.out[l], R.gates[l], params + P.w_hh[l][0], params + P.w_hh[l][1], params + P.w_ih[l][0],
-                                           params + P.w_ih[l][1], nin, R.dgi[l], R.dgh[l], R.hprev[l], d_in, g.B, g.T3, st));
+                    SED_TRY(rnn_gru_bwd64(g, P, params, R, l, st));
             } else {
                 if (g.mode == SED_DTYPE_BF16)
                     SED_TRY(launch_grec_bwd(d_cur, R.out[l], R.gates[l], R.whhT[l], R.dgi[l], R.dgh[l], R.hprev[l], g.B, g.T3, st));
@@ -200,7 +213,6 @@ int rnn_backward(const RnnBwd& rb, const float* d_strong, const float* d_weak, h
                 }
             }
             d_cur = d_in;
-            d_cur2 = (H == 64) ? d_in + (size_t)BT * nin : nullptr;
         }
     }
     // parts == 1 (data-parallel: the GRU + heads gradient bucket must be complete when this call returns so that its

@@ -397,7 +397,7 @@ class OneBatchAheadFrontEnd:
         if self.overlap:
             # lowest priority: the next batch's features must only fill CUs the step leaves idle, never win a CU from it
             lo, _hi = torch.cuda.Stream.priority_range() if hasattr(torch.cuda.Stream, "priority_range") else (0, 0)
-            self._fe_stream = step._stream("front-end", int(os.environ.get("SED_FE_PRIO", lo)))     # (released by step.close())
+            self._fe_stream = step._stream("front-end", lo)     # (released by step.close())
             _lib.check(self.l.sed_stream_prepare(C.c_void_p(self._fe_stream.cuda_stream)), "sed_stream_prepare")
 
     # ---- extraction ------------------------------------------------------------------------------------------------------------

@@ -98,10 +98,8 @@ class MeanTeacherStep:
         self._owned_streams = []
         self.T3, self.NC = self.T // 8, student._nclass
         # the student's output heads are left to sed_mt_step_backward where the library runs them inside the backward recurrence
-        # (csrc/kernels.h heads_fusable; SED_DEFER_HEADS=0/1 overrides for A/B timing)
+        # (csrc/kernels.h heads_fusable)
         self._defer_heads = (student._H == 64 and self.T3 <= 128)
-        if os.environ.get("SED_DEFER_HEADS") in ("0", "1"):
-            self._defer_heads = os.environ["SED_DEFER_HEADS"] == "1"
         self.wlo, self.whi = _slice_range(weak_mask, self.B) if weak_mask is not None else (0, 0)
         self.slo, self.shi = _slice_range(strong_mask, self.B) if strong_mask is not None else (0, 0)
         n = student._flat.numel()
@@ -228,8 +226,7 @@ class MeanTeacherStep:
             self.sync_replicas()
         self.use_graph = bool(use_graph)
         self.overlap = bool(overlap_streams)
-        self._side = (self._stream("teacher", int(os.environ.get("SED_SIDE_PRIO", "0")))
-                      if (self.overlap and teacher is not None) else None)
+        self._side = self._stream("teacher") if (self.overlap and teacher is not None) else None
         self._capture_error = None
         self._graph_a = None
         self._graph_w = None
@@ -250,12 +247,11 @@ class MeanTeacherStep:
         # Readiness belongs to the BATCH in self.x / self.x_ema, not to the step: whoever writes the moments into ctx marks them
         # valid (the tail below; a one-batch-ahead front-end's features()), whatever replaces the batch or the state clears
         # the mark (load_batch, invalidate_batch, load_state_dict), and run() picks its form from the mark alone.
-        self.moments_ahead = os.environ.get("SED_MOMENTS_AHEAD", "0") == "1"
+        self.moments_ahead = False         # (off: measured slower for the resident-batch step; the hand-over tests set it)
         self._mom_valid = False            # ctx_s / ctx_t hold the moments of what is in self.x / self.x_ema right now
         self._resident = False            # a run() has consumed the batch in self.x and no load_batch() came since
         self._mom_ready = self._mom_next = False      # the variant being run / captured
-        self._mom_stream = self._stream("moments", int(os.environ.get("SED_MOM_PRIO", "0")))
-        self._mom_fork = os.environ.get("SED_MOM_FORK", "backward")
+        self._mom_stream = self._stream("moments")
         self._graph_sets = {}              # (mom_ready, mom_next) -> (graph_a, graph_w, graph_c, graph_b)
 
     @property
@@ -297,8 +293,6 @@ class MeanTeacherStep:
 
     def _fwd_bwd(self, after_forward=None, at_recurrence=None):
         self._fork_exc = None
-        if self._mom_next and self._mom_fork == "gru" and at_recurrence is None:
-            at_recurrence = self._moments_ahead
         try:
             self._fwd_bwd_impl(after_forward, at_recurrence)
         finally:
@@ -351,7 +345,7 @@ class MeanTeacherStep:
             self._student_forward(at_recurrence)
         if after_forward is not None:
             after_forward()
-        if self._mom_next and self._mom_fork != "gru":
+        if self._mom_next:
             self._moments_ahead()
         # losses (main.py:93-145) + backward in one call: the heads-backward kernel forms the loss gradient per clip itself
         # (sed_mt_loss as a kernel of its own was 12 us on the critical path).  One process: the whole backward

@@ -769,7 +769,6 @@ int sed_kernel_replay(const char* name, const sed_dims* d, const float* params, 
 #define SED_DEBUG_SEPARATE_HEADS (1 << 24)  /* sed_mt_step_backward: the deferred heads by k_heads_fwd / k_heads_bwd, not fused into the backward recurrence */
 #define SED_DEBUG_SLAB_WGRAD     (1 << 26)  /* fp32 block-2 (W = 4) weight gradient by k_wgrad_wino<4> (one partial slab per tile), not k_wgrad4_os */
 #define SED_DEBUG_STRICT_F32     (1 << 27)  /* strict fp32: no split-bf16 products anywhere in the step */
-#define SED_DEBUG_SAVED_GATES    (1 << 28)  /* bf16: block 0's forward saves its GLU gates and the backward reads them instead of recomputing */
 #define SED_DEBUG_NO_SIDE_STREAM (1 << 30)  /* no helper stream: every kernel on the caller's stream (near-solo kernel times) */
 int sed_debug_set(int flags);
 /* Always 1: the direct kernels behind SED_DEBUG_DIRECT_CONV / SED_DEBUG_DIRECT_WGRAD are part of every build. */

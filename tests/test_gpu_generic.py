@@ -207,46 +207,6 @@ def test_f16_forward_chain_holds_the_north_star_tolerance_at_bf16_speed(B, T, p,
             np.testing.assert_allclose(r["bn"][k].numpy(), v.numpy(), rtol=4e-3, atol=1e-3, err_msg=k)
 
 
-@pytest.mark.parametrize("B,T,p,C,H,dtype", [(8, 216, 0.5, 64, 64, "bf16"), (24, 628, 0.5, 64, 64, "f16"), (4, 216, 0.5, 128, 256, "bf16"),
-                                             (5, 150, 0.0, 64, 64, "bf16")])
-def test_block0_saved_gates_against_the_recomputing_backward(B, T, p, C, H, dtype):
-    """Round 6, measured and NOT the default (debug bit 28 turns it on): in the bf16 family the differentiated
-    forward can store block 0's GLU gate sigmoid(z) as one byte per element and k_blk0_bwd<..., SG = 1> read it instead of
-    recomputing z on the MFMA + exp2 + rcp.  The posteriors are untouched, every gradient outside block 0 agrees to rounding
-    noise, and block 0's parameter gradients move by the quantisation only (<= 1 / 510 per gate, unbiased, inside sums over
-    ~10^5 - 10^6 pixels): asserted within 3e-2 of each gradient's rms (measured 1.2e-2 on the worst element of conv0.weight),
-    inside the distance of either form from the fp32 oracle."""
-    from dcase2019_task4_amd import _lib
-    l = _lib.lib()
-    res = {}
-    for bit in (1 << 28, 0):
-        prev = l.sed_debug_set(bit)
-        try:
-            r = _fwd_bwd(B, T, p, C, H, dtype)
-        finally:
-            l.sed_debug_set(prev)
-        res[bit] = r
-    a, b = res[1 << 28], res[0]                      # a: saved gates, b: the default (recomputed)
-    assert float((a["s"] - b["s"]).abs().max()) < 1e-3 and float((a["w"] - b["w"]).abs().max()) < 1e-3
-    blk0 = ("cnn.cnn.conv0.", "cnn.cnn.batchnorm0.", "cnn.cnn.glu0.")
-    worst = 0.0
-    for n, ga in a["g"].items():
-        gb = b["g"][n]
-        if n.startswith(blk0):
-            if n.endswith("conv0.bias"):
-                continue                                # (exactly-zero gradient in front of a train-mode BatchNorm)
-            rms = float(gb.double().norm()) / np.sqrt(gb.numel()) + 1e-30
-            d = float((ga - gb).abs().max()) / rms
-            worst = max(worst, d)
-            print(f"[saved gates] {n:32s} max|saved - recomputed| / rms {d:.2e}")
-            assert d < 3e-2, (n, d)
-        elif dtype == "bf16" or True:
-            # (the rest of the backward never sees block 0's gates; fp64 atomics make bf16-family runs agree to rounding noise only)
-            rms = float(gb.double().norm()) / np.sqrt(gb.numel()) + 1e-30
-            assert float((ga - gb).abs().max()) / rms < 5e-3, n
-    print(f"[saved gates] {dtype} C={C} H={H} B={B} T={T}: worst block-0 gradient difference / rms {worst:.2e}")
-
-
 def test_f16_stores_saturate_instead_of_overflowing():
     """fp16's range ends at 65504.  Nothing in this model comes near it, but nothing forbids it either (a BatchNorm makes the scale
     of the convolution in front of it free): with conv1's weights scaled by 1e5 its outputs reach ~1e6.  The fp16 stores saturate,
