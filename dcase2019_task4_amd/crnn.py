@@ -144,7 +144,8 @@ class _CRNNFunction(torch.autograd.Function):
                                       _lib.ptr(module._bn_tracked), _lib.ptr(x), int(train), 1, _lib.ptr(seed_t),
                                       _lib.ptr(cbuf), ctx_bytes, _lib.ptr(strong), _lib.ptr(weak), _lib.stream_ptr()),
                    "sed_crnn_forward")
-        module._last_ctx = (cbuf, dims)          # test/debug hook (sed_crnn_ctx_view)
+        module._last_ctx = (cbuf, dims)          # last_attention(); test/debug hook (sed_crnn_ctx_view)
+        module._last_ctx_gen = module._flat_gen
         if ctx.needs_input_grad[1]:
             raise _lib.SedError("the gradient w.r.t. the input features is not implemented (the reference never asks for "
                                 "it: main.py:91 feeds a plain batch tensor)")
@@ -188,6 +189,8 @@ class _CRNNFunction(torch.autograd.Function):
 
 class CRNN(nn.Module):
     """Drop-in for baseline/models/CRNN.py:10-84 on MI355X (see module docstring for scope)."""
+
+    _last_ctx_gen = -1          # the _flat_gen the forward behind _last_ctx ran with (last_attention)
 
     def __init__(self, n_in_channel, nclass, attention=False, activation="Relu", dropout=0, train_cnn=True,
                  rnn_type='BGRU', n_RNN_cell=64, n_layers_RNN=1, dropout_recurrent=0, **kwargs):
@@ -396,6 +399,24 @@ class CRNN(nn.Module):
             n = int(self.ctx_view("gru_err").view(torch.int32)[0].item())
             if n:
                 raise _lib.SedError(f"cluster GRU recurrence: {n} cross-workgroup waits timed out; the outputs are invalid")
+
+    def last_attention(self):
+        """The attention of the LAST forward: ``sof = clamp(softmax(dense_softmax(x), dim=-1), 1e-7, 1)`` (CRNN.py:79) as
+        float32 ``[B, T // 8, nclass]`` on the device, the weights that forward pooled ``weak`` with (``sed_crnn_attention``: one
+        launch that reads the forward's context; eval or train, every ``mfma_dtype``).  Raises ``SedError`` when there is no
+        forward to read, for a module outside the hot path (``attention=False`` models have no attention), and when the
+        parameters were re-laid-out since that forward."""
+        if not self.hot_path:
+            raise _lib.SedError("last_attention: this CRNN configuration is outside the MI355X hot path (CRNN.hot_path is False)")
+        if self._last_ctx is None:
+            raise _lib.SedError("last_attention: no forward has run on this module")
+        if self._last_ctx_gen != self._flat_gen:
+            raise _lib.SedError("last_attention: CRNN parameters were re-laid-out since the last forward")
+        cbuf, dims = self._last_ctx
+        att = torch.empty(dims.B, dims.T // 8, dims.nclass, device=cbuf.device, dtype=torch.float32)
+        _lib.check(_lib.lib().sed_crnn_attention(C.byref(dims), _lib.ptr(cbuf), cbuf.numel(), _lib.ptr(att), _lib.stream_ptr()),
+                   "sed_crnn_attention")
+        return att
 
     def ctx_view(self, name):
         """Test hook: float32 (or float64 for 'mom0'/'stat*') view of an intermediate of the last forward."""

@@ -174,6 +174,22 @@ extern "C" int sed_crnn_ctx_view(const sed_dims* d, const char* name, size_t* of
     return SED_ERR_BAD_ARG;
 }
 
+// The attention the heads of the forward that filled ctx pooled with (heads.hip: k_heads_attention): both kernel sets keep the
+// attention logits of every frame in their ctx's "logits_s" region, whatever `train` and the MFMA dtype were.
+extern "C" int sed_crnn_attention(const sed_dims* d, const void* ctx, size_t ctx_bytes, float* att, void* stream) {
+    if (sed_validate_dims(d) != SED_OK) return SED_ERR_BAD_ARG;      // (the message says what is supported)
+    SED_CHECK_ARG(ctx && att, "sed_crnn_attention: null argument");
+    const size_t need = sed_crnn_ctx_bytes(d);
+    if (ctx_bytes < need) {
+        sed_set_error("sed_crnn_attention: ctx has %zu bytes, needs %zu", ctx_bytes, need);
+        return SED_ERR_BAD_ARG;
+    }
+    size_t off = 0, bytes = 0;
+    SED_TRY(sed_crnn_ctx_view(d, "logits_s", &off, &bytes));
+    const Geo g = make_geo(d);
+    return launch_heads_attention((const float*)((const char*)ctx + off), att, g.B * g.T3, g.NC, (hipStream_t)stream);
+}
+
 // ---- side stream: weight-gradient work that is off the backward critical path (rnn.h: SideFork) ----
 // One helper stream + fork/join event pair exists per (device, caller stream): two host threads (or two models on two
 // GPUs of one process) that call in on different streams never share events.  The pool is created under a mutex, on

@@ -186,6 +186,49 @@ __global__ __launch_bounds__(HD_THREADS) void k_heads_fwd(const float* __restric
     }
 }
 
+// ---- the attention of a forward (sed_crnn_attention) -----------------------------------------------------------------------
+// sof of every frame, rebuilt from the attention logits k_heads_fwd saved in ctx with k_heads_fwd's own arithmetic (same
+// lane layout: 8 threads per frame, thread `sub` takes classes sub and sub + 8; same max shift, __expf, DPP sum order, rcp_fast
+// and clamp), so the values are the ones the forward pooled its weak tags with.  k_heads_fwd itself has no such output: the
+// training step pays nothing for it.
+// The 8-lane reductions of k_heads_fwd (its red8_max / red8_sum lambdas, restated: that kernel's source stays as it is): DPP
+// butterflies quad_perm xor 1, xor 2, then row_half_mirror - the order of the sum is part of what the attention of a forward is.
+__device__ __forceinline__ float ha_red8_sum(float v) {
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
+    return v;
+}
+__device__ __forceinline__ float ha_red8_max(float v) {
+    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true)));
+    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true)));
+    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true)));
+    return v;
+}
+#define HA_THREADS 256
+__global__ __launch_bounds__(HA_THREADS) void k_heads_attention(const float* __restrict__ logits_s, float* __restrict__ att,
+                                                                int n_frames, int NC) {
+    const int f = blockIdx.x * (HA_THREADS / 8) + (threadIdx.x >> 3), sub = threadIdx.x & 7;
+    const bool live = f < n_frames;                    // (whole 8-lane groups: a frame's threads stay or go together)
+    const bool has[2] = {live && sub < NC, live && sub + 8 < NC};
+    const size_t e0 = (size_t)(live ? f : 0) * NC;
+    float ls[2], ex[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) ls[q] = has[q] ? logits_s[e0 + sub + 8 * q] : -3.0e38f;
+    const float mx = ha_red8_max(fmaxf(ls[0], ls[1]));
+#pragma unroll
+    for (int q = 0; q < 2; ++q) ex[q] = has[q] ? __expf(ls[q] - mx) : 0.f;
+    const float inv = rcp_fast(ha_red8_sum(ex[0] + ex[1]));
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+        if (has[q]) att[e0 + sub + 8 * q] = fminf(fmaxf(ex[q] * inv, 1e-7f), 1.0f);
+}
+int launch_heads_attention(const float* logits_s, float* att, int n_frames, int NC, hipStream_t st) {
+    k_heads_attention<<<(n_frames + HA_THREADS / 8 - 1) / (HA_THREADS / 8), HA_THREADS, 0, st>>>(logits_s, att, n_frames, NC);
+    SED_CHECK_LAUNCH();
+    return SED_OK;
+}
+
 // ---- mean-teacher loss terms (main.py:93-145): bce_term / bce_grad live in hfuse.h (shared with the fused form) ----------
 
 // part row layout (matches the flat parameter order dense.weight, dense.bias, dense_softmax.weight,

@@ -226,6 +226,7 @@ int launch_heads_fwd(const float* h /*[B][T][128]*/, const float* wd, const floa
                      float* strong, float* weak, float* strong_sv, float* weak_sv, float* logits_s, float* den, int B, int T,
                      int NC, int use_drop, float p_drop, const uint64_t* seed, hipStream_t st, int HF = 128);
 int launch_heads_colsum(const float* part, float* g_wd, int B, int NC, hipStream_t st, int HF = 128);
+int launch_heads_attention(const float* logits_s /*[n_frames][NC], ctx*/, float* att, int n_frames, int NC, hipStream_t st);
 // ---- device-side step state (sed_step_state): derived fields ------------------------------------------------------
 #ifdef __HIPCC__
 __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {

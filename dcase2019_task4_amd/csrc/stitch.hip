@@ -16,6 +16,8 @@
 // sed_stitch_decode is SWEEP = false, one point.  Both entries go through one host path (st_run).
 // Onsets and offsets alternate along a column, so the offsets in front of a tile are the onsets in front of it minus one
 // when an event is open across the tile's first edge: one count per (tile, class) is enough.
+// sed_stitch_weak (at the end of the file) pools recording-level weak tags over the same tiles and slots: the same blend of the
+// posteriors and of the attention, fp64 sums in a fixed order, two launches, no timeline.
 //
 // Where a tile lives: the tiles of recording r take slots slot0(r) + k, slot0(r) = floor(rec_frame0[r] / ST_TILE) + r.  That
 // is strictly increasing in (r, k) for increasing rec_frame0, needs no table of its own and at most
@@ -82,14 +84,26 @@ __device__ __forceinline__ StRec st_rec(const StArgs& a, int r) {
     return R;
 }
 
-// Blended posterior(s) of timeline frame u of recording R: class q (VEC = false) or classes 4q .. 4q + 3 (VEC = true).
+// The recording whose tiles may hold slot g: the last r with slot0(r) <= g (workgroup-uniform; the caller validates it).
+__device__ __forceinline__ int st_slot_rec(const StArgs& a, long long g) {
+    int lo_r = 0, hi_r = a.n_rec - 1;
+    while (lo_r < hi_r) {
+        const int mid = (lo_r + hi_r + 1) >> 1;
+        if (a.rec_frame0[mid] / ST_TILE + mid <= g) lo_r = mid;
+        else hi_r = mid - 1;
+    }
+    return lo_r;
+}
+
+// Blended value(s) of timeline frame u of recording R from the window tensor `win` [n_win][T3][NC] (the posteriors, or the
+// attention of sed_stitch_weak): class q (VEC = false) or classes 4q .. 4q + 3 (VEC = true).
 template <bool VEC>
-__device__ __forceinline__ f32x4 st_blend(const StArgs& a, const StRec& R, int u, int q) {
+__device__ __forceinline__ f32x4 st_blend(const StArgs& a, const float* win, const StRec& R, int u, int q) {
     const int T3 = a.T3, hop3 = a.hop3, NC = a.NC;
     const int j_lo = u >= T3 ? (u - T3) / hop3 + 1 : 0;                          // the windows j with 0 <= u - j hop3 < T3 ...
     const int j_hi = min(u / hop3, R.nw - 1);                                    // ... that the recording owns
     const int col = VEC ? 4 * q : q;
-    const float* src = a.win_strong + ((size_t)(R.w0 + j_lo) * T3 + (u - j_lo * hop3)) * NC + col;
+    const float* src = win + ((size_t)(R.w0 + j_lo) * T3 + (u - j_lo * hop3)) * NC + col;
     f32x4 p = {0.0f, 0.0f, 0.0f, 0.0f};
     if (j_lo == j_hi) {                                                          // one window: its value, copied exactly
         if (VEC) p = *(const f32x4*)src;
@@ -142,13 +156,7 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_tile(StArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NC = a.NC;
     // ---- which recording, which tile (workgroup-uniform) -----------------------------------------------------------------
     const long long g = blockIdx.x;
-    int lo_r = 0, hi_r = a.n_rec - 1;
-    while (lo_r < hi_r) {                                                        // the last r with slot0(r) <= g
-        const int mid = (lo_r + hi_r + 1) >> 1;
-        if (a.rec_frame0[mid] / ST_TILE + mid <= g) lo_r = mid;
-        else hi_r = mid - 1;
-    }
-    const int r = lo_r;
+    const int r = st_slot_rec(a, g);
     const StRec R = st_rec(a, r);
     if (R.bad) return;                                                           // (k_stitch_scan_cols reports it)
     const long long kt = g - R.slot0;
@@ -176,7 +184,7 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_tile(StArgs a) {
         };
         for (int it = tid; it < ext_n * G; it += ST_THREADS) {
             const int fl = it / G, q = it - fl * G, u = ext_lo + fl;
-            const f32x4 p = st_blend<VEC>(a, R, u, q);
+            const f32x4 p = st_blend<VEC>(a, a.win_strong, R, u, q);
             if (VEC) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) keep(4 * q + k, fl, p[k]);
@@ -425,4 +433,166 @@ extern "C" int sed_stitch_sweep(const float* win_strong, const int32_t* rec_win0
                                 size_t ws_bytes, int32_t* err, void* stream) {
     return st_run("sed_stitch_sweep", true, win_strong, rec_win0, rec_frame0, n_rec, T3, NC, hop3, weighting, n_points, thr, win,
                   timeline, nullptr, ev_ptr, ev_pairs, capacity, ws, ws_bytes, err, stream);
+}
+
+// ---- recording-level weak tags (sed_stitch_weak) ------------------------------------------------------------------------------
+// weak[r, c] = (sum_u P[u, c] A[u, c]) / (sum_u A[u, c]) over the WHOLE timeline of recording r: P the blend of the windows'
+// posteriors, A the same blend of their attention, the products and both sums in fp64 (include/dcase_sed.h).  No timeline is
+// written: a tile's workgroup blends both tensors for its ST_TILE frames (st_blend, no halo) and leaves one (num, den) pair per
+// class in its slot of the workspace; a second launch adds a column's tile pairs.
+// The order of every sum is a function of (L3, NC) alone:
+//   an item is one frame x W classes, W = 4 when NC % 4 == 0, else 1 (VEC only decides whether the four come in one 16-byte
+//     load, so alignment does not change the result); thread (row, q) of the first rows * G threads, G = NC / W,
+//     rows = ST_THREADS / G, adds the items of class group q at frames s + row, s + row + rows, ... in that order;
+//   thread (c, i) adds the rows i, i + 16, ... of class c, thread c the sixteen of those: the tile's pair;
+//   lane l of a column's wave adds the tiles l, l + 64, ..., then an xor butterfly (both partners form the same sum).
+struct StWeakArgs {
+    StArgs t;                // win_strong, the tables, T3 / NC / hop3 / weighting, n_slots, err (st_rec, st_blend)
+    const float* win_att;
+    double* part;            // ws: [n_slots][NC][2] (num, den) of a tile
+    float* weak;             // [n_rec][NC]
+    double* sums;            // [n_rec][NC][2] or null
+};
+#define SW_FOLD 16
+
+template <bool VEC, int W>
+__global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_tile(StWeakArgs wa) {
+    __shared__ double red[ST_THREADS * W * 2];                                   // [rows][NC][2], rows * NC <= ST_THREADS * W
+    __shared__ double fold[ST_MAXC * SW_FOLD * 2];
+    const StArgs& a = wa.t;
+    const int tid = threadIdx.x, NC = a.NC;
+    const long long g = blockIdx.x;
+    const int r = st_slot_rec(a, g);
+    const StRec R = st_rec(a, r);
+    if (R.bad) return;                                                           // (k_stitch_weak_cols reports it)
+    const long long kt = g - R.slot0;
+    if (kt < 0 || kt >= R.tiles) return;                                         // an empty slot
+    const int s = (int)kt * ST_TILE, e = min(s + ST_TILE, R.L3);
+    const int G = NC / W, rows = ST_THREADS / G, row = tid / G, q = tid - row * G;
+    if (row < rows) {
+        double num[W], den[W];
+#pragma unroll
+        for (int k = 0; k < W; ++k) { num[k] = 0.0; den[k] = 0.0; }
+        for (int u = s + row; u < e; u += rows) {
+            f32x4 p, at;
+            if (VEC) {
+                p = st_blend<true>(a, a.win_strong, R, u, q);
+                at = st_blend<true>(a, wa.win_att, R, u, q);
+            } else {
+#pragma unroll
+                for (int k = 0; k < W; ++k) {
+                    p[k] = st_blend<false>(a, a.win_strong, R, u, W * q + k)[0];
+                    at[k] = st_blend<false>(a, wa.win_att, R, u, W * q + k)[0];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < W; ++k) {
+                num[k] += (double)p[k] * (double)at[k];                          // (24 x 24 bits: the product is exact)
+                den[k] += (double)at[k];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            red[((size_t)row * NC + W * q + k) * 2] = num[k];
+            red[((size_t)row * NC + W * q + k) * 2 + 1] = den[k];
+        }
+    }
+    __syncthreads();
+    {
+        const int c = tid / SW_FOLD, i = tid - c * SW_FOLD;                      // ST_THREADS = ST_MAXC * SW_FOLD
+        if (c < NC) {
+            double n = 0.0, d = 0.0;
+            for (int rr = i; rr < rows; rr += SW_FOLD) { n += red[(rr * NC + c) * 2]; d += red[(rr * NC + c) * 2 + 1]; }
+            fold[(c * SW_FOLD + i) * 2] = n;
+            fold[(c * SW_FOLD + i) * 2 + 1] = d;
+        }
+    }
+    __syncthreads();
+    if (tid < NC) {
+        double n = 0.0, d = 0.0;
+        for (int i = 0; i < SW_FOLD; ++i) { n += fold[(tid * SW_FOLD + i) * 2]; d += fold[(tid * SW_FOLD + i) * 2 + 1]; }
+        double* out = wa.part + ((size_t)g * NC + tid) * 2;
+        out[0] = n;
+        out[1] = d;
+    }
+}
+static_assert(ST_THREADS == ST_MAXC * SW_FOLD, "k_stitch_weak_tile folds the rows with one thread per (class, fold lane)");
+
+// One wave per column (recording, class): the tile pairs in the fixed order above; a recording the tables do not describe or
+// cover raises its err bits and has NaN rows.
+__global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_cols(StWeakArgs wa) {
+    const StArgs& a = wa.t;
+    const int lane = threadIdx.x & 63;
+    const long long col = (long long)blockIdx.x * (ST_THREADS / 64) + (threadIdx.x >> 6);
+    if (col >= (long long)a.n_rec * a.NC) return;
+    const int r = (int)(col / a.NC), c = (int)(col - (long long)r * a.NC);
+    const StRec R = st_rec(a, r);
+    double n = 0.0, d = 0.0;
+    if (R.bad) {
+        if (c == 0 && lane == 0) atomicOr(a.err, R.bad);
+        n = d = __builtin_nan("");
+    } else {
+        for (int k = lane; k < R.tiles; k += 64) {
+            const double* p = wa.part + (((size_t)R.slot0 + k) * a.NC + c) * 2;
+            n += p[0];
+            d += p[1];
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            n += __shfl_xor(n, o);
+            d += __shfl_xor(d, o);
+        }
+    }
+    if (lane == 0) {
+        wa.weak[col] = R.bad ? __builtin_nanf("") : (float)(n / d);
+        if (wa.sums) { wa.sums[2 * col] = n; wa.sums[2 * col + 1] = d; }
+    }
+}
+
+static size_t sw_ws_per_slot(int NC) { return (size_t)NC * 2 * sizeof(double); }
+
+extern "C" size_t sed_stitch_weak_ws_bytes(long long total_frames, int n_rec, int nclass) {
+    if (total_frames < 1 || n_rec < 1 || nclass < 1 || nclass > ST_MAXC || total_frames * nclass >= (1ll << 31) ||
+        (long long)n_rec * nclass >= (1ll << 31)) {
+        sed_set_error("sed_stitch_weak_ws_bytes: need total_frames >= 1, n_rec >= 1, 1 <= nclass <= 16, "
+                      "total_frames * nclass < 2^31, n_rec * nclass < 2^31");
+        return 0;
+    }
+    return (size_t)(total_frames / ST_TILE + n_rec + 1) * sw_ws_per_slot(nclass);
+}
+
+extern "C" int sed_stitch_weak(const float* win_strong, const float* win_att, const int32_t* rec_win0, const int64_t* rec_frame0,
+                               int n_rec, int T3, int NC, int hop3, int weighting, float* weak, double* sums, void* ws,
+                               size_t ws_bytes, int32_t* err, void* stream) {
+    const char* what = "sed_stitch_weak";
+    ST_NEED(win_strong && win_att && rec_win0 && rec_frame0 && weak && ws && err, "null argument");
+    ST_NEED(n_rec >= 1 && NC >= 1 && NC <= ST_MAXC && (long long)n_rec * NC < (1ll << 31),
+            "need n_rec >= 1, 1 <= NC <= 16 and n_rec * NC < 2^31");
+    ST_NEED(T3 >= 1 && T3 <= 4096, "need 1 <= T3 <= 4096 (the taper's weight sum stays exact in fp32)");
+    ST_NEED(hop3 >= 1 && hop3 <= T3, "need 1 <= hop3 <= T3");
+    ST_NEED(weighting == 0 || weighting == 1, "weighting is 0 (uniform) or 1 (taper)");
+    ST_NEED(((uintptr_t)ws % 8) == 0, "ws must be 8-byte aligned");
+    // the slot count is derived from the size: only a size sed_stitch_weak_ws_bytes returns describes whole slots for the tables
+    const size_t per_slot = sw_ws_per_slot(NC);
+    ST_NEED(ws_bytes % per_slot == 0 && ws_bytes / per_slot >= (size_t)n_rec + 1,
+            "ws_bytes must be the value sed_stitch_weak_ws_bytes returned for these tables");
+    const size_t n_slots = ws_bytes / per_slot;
+    ST_NEED(n_slots < (1ull << 31), "workspace too large for the tile grid (slots < 2^31)");
+    ST_NEED((long long)(n_slots - n_rec - 1) * ST_TILE * NC < (1ll << 31) + (long long)ST_TILE * NC,
+            "sum L3 * NC must stay below 2^31");
+    StWeakArgs wa = {};
+    wa.t.win_strong = win_strong; wa.t.rec_win0 = rec_win0; wa.t.rec_frame0 = rec_frame0; wa.t.err = err;
+    wa.t.n_rec = n_rec; wa.t.T3 = T3; wa.t.NC = NC; wa.t.hop3 = hop3; wa.t.weighting = weighting; wa.t.n_slots = (int)n_slots;
+    wa.t.K = 1;
+    wa.win_att = win_att; wa.part = (double*)ws; wa.weak = weak; wa.sums = sums;
+    const bool vec = NC % 4 == 0 && ((uintptr_t)win_strong % 16) == 0 && ((uintptr_t)win_att % 16) == 0;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 tiles((unsigned)n_slots), thr256(ST_THREADS);
+    if (vec) hipLaunchKernelGGL((k_stitch_weak_tile<true, 4>), tiles, thr256, 0, st, wa);
+    else if (NC % 4 == 0) hipLaunchKernelGGL((k_stitch_weak_tile<false, 4>), tiles, thr256, 0, st, wa);
+    else hipLaunchKernelGGL((k_stitch_weak_tile<false, 1>), tiles, thr256, 0, st, wa);
+    SED_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_stitch_weak_cols, dim3((unsigned)(((long long)n_rec * NC + 3) / 4)), thr256, 0, st, wa);
+    SED_CHECK_LAUNCH();
+    return SED_OK;
 }

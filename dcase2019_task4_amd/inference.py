@@ -11,8 +11,10 @@ Recordings longer than one clip: ``LongRecordingSet`` (longrec.py) holds them as
 ``sed_stitch_decode`` call.  The device-resident event table it leaves is scored by ``metrics.long_event_counts`` /
 ``long_psds_counts`` / ``validate_long`` (``sed_long_event_counts``, ``sed_long_psds_counts``: columns of any length).
 ``stitch_sweep`` decodes K operating points from one blend (``sed_stitch_sweep``), scored by ``metrics.long_sweep_*``.
-Training on windows of such recordings is ``WindowedFeatureSet`` (longrec.py, through ``train.train``).  Out of scope
-there: recording-level weak tags.  ``get_predictions`` itself is unchanged.
+Training on windows of such recordings is ``WindowedFeatureSet`` (longrec.py, through ``train.train``).  Recording-level
+weak tags: ``get_long_predictions(return_weak=True)`` / ``stitch_weak`` pool them over the whole blended timeline from the
+windows' posteriors and attention (``CRNN.last_attention``, ``sed_stitch_weak``); ``weak_tags_dataframe`` is their table,
+``metrics.validate_long(weak_labels=...)`` their score.  ``get_predictions`` itself is unchanged.
 """
 import ctypes as C
 
@@ -251,13 +253,62 @@ def stitch_sweep(win_strong, rec_win0, rec_frame0, total_frames, hop3, threshold
                         ws_bytes, want_timeline, n_points=K)
 
 
-def long_window_posteriors(model, long_set, nclass, batch_size=64):
+def stitch_weak(win_strong, win_att, rec_win0, rec_frame0, total_frames, hop3, weighting="taper", want_sums=False):
+    """Recording-level weak tags (``sed_stitch_weak``): ``win_strong`` / ``win_att`` [n_win, T3, nclass] cuda float32 - the
+    windows' posteriors and attention (``long_window_posteriors(want_attention=True)``) - are blended like ``stitch_decode``'s
+    timeline and pooled over every recording's whole timeline in fp64, ``weak = sum(P * A) / sum(A)``; no timeline is written.
+    Tables as for ``stitch_decode``.  Returns a dict, all on the device, nothing synchronises: ``weak`` [n_rec, nclass]
+    float32, ``sums`` [n_rec, nclass, 2] float64 (num, den) or None, ``err`` [1] int32 (``STITCH_ERR_BITS`` 16 / 32: the rows
+    of such a recording are NaN)."""
+    if weighting not in WEIGHTINGS:
+        raise ValueError(f"weighting must be one of {sorted(WEIGHTINGS)}, got {weighting!r}")
+    if win_strong.dim() != 3 or win_att.shape != win_strong.shape:
+        raise ValueError(f"win_strong and win_att must both be [n_win, T3, nclass], got {tuple(win_strong.shape)} and "
+                         f"{tuple(win_att.shape)}")
+    n_win, T3, NC = win_strong.shape
+    total, n_rec = int(total_frames), rec_win0.numel() - 1
+    if not 1 <= NC <= 16 or not 1 <= int(hop3) <= T3 <= 4096 or n_rec < 1 or total < 1:
+        raise ValueError(f"need 1 <= nclass <= 16, 1 <= hop3 <= T3 <= 4096, n_rec >= 1, total_frames >= 1; got nclass {NC}, "
+                         f"hop3 {hop3}, T3 {T3}, n_rec {n_rec}, total_frames {total}")
+    if total * NC >= 2 ** 31:
+        raise ValueError(f"{total} timeline frames x {NC} classes: the product must stay below 2^31")
+    if win_strong.device.type != "cuda" or win_att.device != win_strong.device:
+        raise _lib.SedError("stitch_weak needs GPU tensors on one device (no CPU fallback)")
+    dev = win_strong.device
+    win_strong, win_att = win_strong.contiguous().float(), win_att.contiguous().float()
+    out = {"weak": torch.empty(n_rec, NC, dtype=torch.float32, device=dev),
+           "sums": torch.empty(n_rec, NC, 2, dtype=torch.float64, device=dev) if want_sums else None,
+           "err": torch.zeros(1, dtype=torch.int32, device=dev)}
+    l = _lib.lib()
+    ws = _lib.scratch(l.sed_stitch_weak_ws_bytes(total, n_rec, NC), dev)
+    _lib.check(l.sed_stitch_weak(_lib.ptr(win_strong), _lib.ptr(win_att), _lib.ptr(rec_win0), _lib.ptr(rec_frame0), n_rec, T3, NC,
+                                 int(hop3), WEIGHTINGS[weighting], _lib.ptr(out["weak"]), _lib.ptr(out["sums"]), _lib.ptr(ws),
+                                 ws.numel(), _lib.ptr(out["err"]), _lib.stream_ptr()), "sed_stitch_weak")
+    return out
+
+
+def weak_tags_dataframe(weak, filenames, labels, threshold=0.5):
+    """The reference's weak-label table (``filename``, ``event_labels``: the labels with ``weak > threshold``, comma-joined in
+    label order; empty for a recording without tags) from ``weak`` [n_rec, nclass] (a device tensor or an array).
+    ``threshold``: a scalar or one value per class."""
+    weak = weak.detach().cpu().numpy() if torch.is_tensor(weak) else np.asarray(weak)
+    labels, filenames = list(labels), list(filenames)
+    if weak.shape != (len(filenames), len(labels)):
+        raise ValueError(f"weak is {weak.shape}, expected {(len(filenames), len(labels))} (recordings, labels)")
+    on = weak > _per_class(threshold, len(labels), np.float32, "threshold")[None, :]
+    return pd.DataFrame({"filename": filenames,
+                         "event_labels": [",".join(l for l, k in zip(labels, row) if k) for row in on]},
+                        columns=["filename", "event_labels"])
+
+
+def long_window_posteriors(model, long_set, nclass, batch_size=64, want_attention=False):
     """The strong posteriors [n_win, T3, nclass] of every window of ``long_set``, from the eval-mode model ``batch_size``
-    windows at a time; they stay on the device."""
+    windows at a time; they stay on the device.  ``want_attention=True``: ``(win_strong, win_att)``, the attention of the same
+    forwards (``CRNN.last_attention`` per batch), same shape."""
     dev = next(model.parameters()).device
     was_training = model.training
     model.eval()
-    win_strong = None
+    win_strong = win_att = None
     try:
         with torch.no_grad():
             for i0, idx, x in eval_batches(long_set, batch_size, dev):
@@ -267,14 +318,18 @@ def long_window_posteriors(model, long_set, nclass, batch_size=64):
                         raise ValueError(f"the model gives {tuple(strong.shape[1:])} per window, the set and the labels "
                                          f"{(long_set.T3, nclass)}")
                     win_strong = torch.empty(long_set.n_clips, long_set.T3, nclass, dtype=torch.float32, device=dev)
+                    win_att = torch.empty_like(win_strong) if want_attention else None
                 win_strong[i0:i0 + len(idx)].copy_(strong)
+                if want_attention:
+                    win_att[i0:i0 + len(idx)].copy_(model.last_attention())
     finally:
         model.train(was_training)
-    return win_strong
+    return (win_strong, win_att) if want_attention else win_strong
 
 
 def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=None, save_predictions=None, batch_size=64,
-                         cfg=None, threshold=0.5, median_window=None, weighting="taper", return_posteriors=False):
+                         cfg=None, threshold=0.5, median_window=None, weighting="taper", return_posteriors=False,
+                         return_weak=False):
     """Events of recordings of any lengths (a ``LongRecordingSet``): the windows go through the eval-mode model
     ``batch_size`` at a time, their strong posteriors are blended into one timeline per recording (``weighting``: "taper"
     or "uniform"), and ONE threshold, median filter and run-length decode runs over each whole timeline
@@ -285,7 +340,9 @@ def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=
     given), rows ordered (recording, class, time).  ``threshold`` / ``median_window`` (default ``cfg.median_window``): a
     scalar or one value per class.  ``decoder_or_labels``: ``many_hot_encoder.decode_strong`` (the labels are its owner's)
     or a plain list of labels.  ``return_posteriors=True``: also the list of per-recording [L3_r, nclass] device views of
-    the blended timeline and the [n_win, T3, nclass] window posteriors."""
+    the blended timeline and the [n_win, T3, nclass] window posteriors.  ``return_weak=True``: the recording-level weak tags
+    [n_rec, nclass] (a device tensor; ``stitch_weak`` on the same single pass through the model) are appended to what is
+    returned; ``weak_tags_dataframe`` turns them into the weak-label table."""
     if not isinstance(long_set, LongRecordingSet):
         raise TypeError(f"long_set must be a LongRecordingSet, got {type(long_set).__name__}")
     cfg = cfg or _Cfg
@@ -303,13 +360,21 @@ def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=
     NC = len(labels)
     thr = _per_class(threshold, NC, np.float32, "threshold")
     win = _per_class(cfg.median_window if median_window is None else median_window, NC, np.int32, "median_window")
-    win_strong = long_window_posteriors(model, long_set, NC, batch_size)
+    win_strong = long_window_posteriors(model, long_set, NC, batch_size, want_attention=return_weak)
+    if return_weak:
+        win_strong, win_att = win_strong
     out = stitch_decode(win_strong, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3, thr, win,
                         weighting, long_set.capacity(NC), want_timeline=return_posteriors)
-    err = int(out["err"].item())
-    if err:
-        raise _lib.SedError("sed_stitch_decode reported err " + ", ".join(f"bit {b} ({t})" for b, t in STITCH_ERR_BITS.items()
-                                                                          if err & b) + f" (err = {err})")
+    calls = [("sed_stitch_decode", out["err"])]
+    if return_weak:
+        tags = stitch_weak(win_strong, win_att, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3,
+                           weighting)
+        calls.append(("sed_stitch_weak", tags["err"]))
+    for what, word in calls:
+        err = int(word.item())
+        if err:
+            raise _lib.SedError(f"{what} reported err " + ", ".join(f"bit {b} ({t})" for b, t in STITCH_ERR_BITS.items()
+                                                                    if err & b) + f" (err = {err})")
     ev_ptr = out["ev_ptr"].cpu().numpy()
     ev = out["ev_pairs"][:int(ev_ptr[-1])].cpu().numpy()
     per_col = np.diff(ev_ptr)
@@ -325,7 +390,10 @@ def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=
     prediction_df.offset = prediction_df.offset * pool / (cfg.sample_rate / cfg.hop_length)
     if save_predictions is not None:
         prediction_df.to_csv(save_predictions, index=False, sep="\t")
-    if not return_posteriors:
-        return prediction_df
-    f0 = long_set.rec_frame0_host
-    return prediction_df, [out["timeline"][int(f0[r]):int(f0[r + 1])] for r in range(long_set.n_rec)], win_strong
+    result = (prediction_df,)
+    if return_posteriors:
+        f0 = long_set.rec_frame0_host
+        result += ([out["timeline"][int(f0[r]):int(f0[r + 1])] for r in range(long_set.n_rec)], win_strong)
+    if return_weak:
+        result += (tags["weak"],)
+    return result if len(result) > 1 else prediction_df

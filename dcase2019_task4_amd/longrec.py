@@ -209,7 +209,8 @@ class WindowedFeatureSet(ResidentFeatureSet):
     item in a non-windowed stream): random crops never change the number of global draws.
 
     Not provided: ``from_waveforms``, crop starts finer than one label frame, event-aware (class-balanced) crop sampling,
-    recording-level weak tags."""
+    training on recordings that carry only weak labels (the pooled recording-level tag of ``inference.stitch_weak`` has no
+    backward)."""
 
     row_shape = (2,)
 

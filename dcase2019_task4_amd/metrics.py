@@ -34,8 +34,9 @@ on the event table ``inference.stitch_decode`` leaves on the device, or on two `
 pair can be compatible (include/dcase_sed.h) -, and a cluster holds at most 64 events per side: beyond that the call raises,
 nothing is truncated.  K operating points: ``long_sweep_event_counts`` / ``long_sweep_psds_counts`` score the table of
 ``inference.stitch_sweep`` (or K ``RefEvents``) against ONE preparation of the reference side, four launches whatever K is
-(``sed_long_sweep_*``); ``validate_long(one_blend=True)`` uses them.  Not provided there: recording-level weak tags, an exact
-matching of clusters beyond 64 per side.
+(``sed_long_sweep_*``); ``validate_long(one_blend=True)`` uses them.  Recording-level weak tags: ``validate_long(weak_labels=...)``
+pools them once (``inference.stitch_weak``) and scores them with ``weak_counts``.  Not provided there: an exact matching of
+clusters beyond 64 per side.
 
 PSDS (polyphonic sound detection score, Bilen et al., ICASSP 2020): ``sed_psds_counts`` scores the same (operating point,
 clip) grid with the three intersection criteria and returns integer class totals (``psds_counts``, ``PSDSCounts``); the
@@ -144,6 +145,11 @@ class RefEvents:
     def __len__(self):
         return len(self.filenames)
 
+    def weak_labels(self):
+        """``[n_files, nclass]`` uint8: 1 where the file has at least one reference event of the class (the weak tags the
+        strong annotations imply)."""
+        return (np.diff(self.ptr_host).reshape(len(self.filenames), len(self.labels)) > 0).astype(np.uint8)
+
     @property
     def nclass(self):
         return len(self.labels)
@@ -159,14 +165,16 @@ class _DeviceCounts:
         self.err = self.buf[-1:].view(torch.int32)
         self.err_what, self.err_bits = err_what, _ERR_BITS                    # (the long calls put their own wording here)
 
-    def _totals_to_host(self):
-        """The buffer without its error word - one device -> host copy; raises when the word is set."""
-        h = self.buf.cpu().numpy()
-        err = int(h[-1:].view(np.int32)[0])
+    def _totals_to_host(self, extra=None):
+        """The buffer without its error word - one device -> host copy; raises when the word is set.  ``extra``: an int64
+        device vector that travels in the same copy; the result is then ``(totals, extra on the host)``."""
+        n = self.buf.numel()
+        h = (self.buf if extra is None else torch.cat([self.buf, extra])).cpu().numpy()
+        err = int(h[n - 1:n].view(np.int32)[0])
         if err:
             raise _lib.SedError(self.err_what + ": " + "; ".join(m for b, m in self.err_bits.items() if err & b)
                                 + " - nothing was truncated, the counts are invalid")
-        return h[:-1]
+        return h[:n - 1] if extra is None else (h[:n - 1], h[n:])
 
     def check(self):
         return self.host()
@@ -185,10 +193,13 @@ class Counts(_DeviceCounts):
         self.seg = self.buf[n3:-1].view(n_points, nclass, 4)
         self.ev_columns = self.seg_columns = None
 
-    def host(self):
-        """(ev, seg) as numpy arrays - one device -> host copy; raises when a column was over a limit."""
-        h, n3 = self._totals_to_host(), self.K * self.NC * 3
-        return h[:n3].reshape(self.K, self.NC, 3), h[n3:].reshape(self.K, self.NC, 4)
+    def host(self, extra=None):
+        """(ev, seg) as numpy arrays - one device -> host copy; raises when a column was over a limit.  ``extra``: an int64
+        device vector taken along in that copy and returned third."""
+        h, n3 = self._totals_to_host(extra), self.K * self.NC * 3
+        h, tail = h if extra is not None else (h, None)
+        ev, seg = h[:n3].reshape(self.K, self.NC, 3), h[n3:].reshape(self.K, self.NC, 4)
+        return (ev, seg) if extra is None else (ev, seg, tail)
 
 
 class PSDSCounts(_DeviceCounts):
@@ -355,6 +366,14 @@ def _f_measure(p, r):
     if p == 0 and r == 0:
         return 0.0
     return 2 * p * r / (p + r)
+
+
+def f_measure_from_counts(counts):
+    """Clip-level F1 per (point, class) from ``weak_counts`` totals ``[..., 4]`` (tp, fp, fn, tn): ``2 tp / (2 tp + fp + fn)``, 0
+    where that denominator is 0 (evaluation_measures.py:73-83)."""
+    tp, fp, fn = (np.asarray(counts)[..., i].astype(np.float64) for i in range(3))
+    den = 2 * tp + fp + fn
+    return np.divide(2 * tp, den, out=np.zeros_like(den), where=den != 0)
 
 
 def _nanmean(values):
@@ -579,11 +598,7 @@ def get_f_measure_by_class(torch_model, nb_tags, dataloader_, thresholds_=None):
             if y.dim() == 3:                     # strong labels: max over time, binarised at 0.5 (lines 53-57)
                 y = y.max(dim=1).values > 0.5
             weak_counts(pred_weak, y, thr, counts)
-    tp, fp, fn, _ = (v.astype(np.float64) for v in counts.cpu().numpy()[0].T)
-    macro_f_measure = np.zeros(nb_tags)
-    mask_f_score = 2 * tp + fp + fn != 0
-    macro_f_measure[mask_f_score] = 2 * tp[mask_f_score] / (2 * tp + fp + fn)[mask_f_score]
-    return macro_f_measure
+    return f_measure_from_counts(counts.cpu().numpy()[0])
 
 
 def validate(model, dataset, ref, pooling_time_ratio, thresholds=(0.5,), median_windows=(5,), batch_size=64, cfg=None,
@@ -807,7 +822,7 @@ def long_sweep_psds_counts_from_events(ests, ref, dtc=0.5, gtc=0.5, cttc=0.3, co
 
 
 def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, batch_size=64, cfg=None, weighting="taper",
-                  psds=None, one_blend=True, max_table_bytes=1 << 30):
+                  psds=None, one_blend=True, max_table_bytes=1 << 30, weak_labels=None, weak_thresholds=None):
     """``validate`` for a ``LongRecordingSet``: the windows go through the model ONCE, then the K operating points are
     decoded and scored, and ONE device -> host copy ends the call.  ``one_blend=True``: the points are split into chunks
     (``longrec.sweep_chunks``: the event table of a chunk stays within ``max_table_bytes``); per chunk ONE
@@ -819,8 +834,14 @@ def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, 
     a scalar or one value per class; ``median_windows``: the same (or one entry for all points; None: ``cfg.median_window``).
     ``ref``: the ``RefEvents`` of the recordings, in the set's order.  ``psds``: a ``PSDSCounts`` of the same K points, filled
     from the same decodes (read it with ``PSDS.from_counts(psds, ref, long_set.durations())``).
-    Returns one ``(EventMetrics, SegmentMetrics)`` per operating point."""
-    from .inference import long_window_posteriors, stitch_decode, stitch_sweep, sweep_points
+    Returns one ``(EventMetrics, SegmentMetrics)`` per operating point.
+    ``weak_labels``: the recordings' reference tags, an ``[n_rec, nclass]`` 0/1 array or ``"from_ref"``
+    (``ref.weak_labels()``).  The same forwards then also hand out their attention, the recording-level weak tags are pooled
+    ONCE (``inference.stitch_weak``) and scored by ``weak_counts`` at ``weak_thresholds`` (entries as ``thresholds``, the
+    default), and the call returns ``(that list, {"f_measure": [Kw, nclass] float64, "counts": [Kw, nclass, 4] int64 (tp, fp,
+    fn, tn)})`` - still one device -> host copy.  With ``weak_labels=None`` nothing changes."""
+    from .inference import (STITCH_ERR_BITS, _per_class, long_window_posteriors, stitch_decode, stitch_sweep, stitch_weak,
+                            sweep_points)
     from .longrec import LongRecordingSet, sweep_chunks
     cfg = cfg or _Cfg
     thresholds = list(thresholds)
@@ -828,6 +849,21 @@ def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, 
     K = max(len(thresholds), len(median_windows))
     if len(thresholds) not in (1, K) or len(median_windows) not in (1, K) or K < 1:
         raise ValueError("thresholds and median_windows must have equal lengths (or length 1)")
+    if weak_labels is None:
+        if weak_thresholds is not None:
+            raise ValueError("weak_thresholds without weak_labels: there is nothing to score the tags against")
+    else:
+        if isinstance(weak_labels, str):
+            if weak_labels != "from_ref":
+                raise ValueError(f'weak_labels is an [n_rec, nclass] 0/1 array or "from_ref", got {weak_labels!r}')
+            weak_labels = ref.weak_labels()
+        weak_labels = np.asarray(weak_labels)
+        if weak_labels.shape != (len(ref), ref.nclass):
+            raise ValueError(f"weak_labels is {weak_labels.shape}, expected {(len(ref), ref.nclass)} (recordings, classes)")
+        if not np.isin(weak_labels, (0, 1)).all():
+            raise ValueError("weak_labels must hold 0 / 1")
+        weak_thr = np.stack([_per_class(t, ref.nclass, np.float32, "a weak threshold")
+                             for t in (thresholds if weak_thresholds is None else list(weak_thresholds))])
     if not isinstance(long_set, LongRecordingSet):
         raise TypeError(f"long_set must be a LongRecordingSet, got {type(long_set).__name__}")
     if not getattr(model, "hot_path", False):
@@ -843,7 +879,9 @@ def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, 
     if one_blend:
         thr_all, win_all = sweep_points(thresholds, median_windows, NC)
     counts = Counts(K, NC, dev)
-    win_strong = long_window_posteriors(model, long_set, NC, batch_size)
+    win_strong = long_window_posteriors(model, long_set, NC, batch_size, want_attention=weak_labels is not None)
+    if weak_labels is not None:
+        win_strong, win_att = win_strong
     if one_blend:
         cap = long_set.capacity(NC)
         for k0, k1 in sweep_chunks(K, cap, max_table_bytes):
@@ -862,5 +900,16 @@ def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, 
             long_event_counts(out, ref, long_set.pooling_time_ratio, cfg, counts=counts, point=k)
             if psds is not None:
                 long_psds_counts(out, ref, long_set.pooling_time_ratio, cfg, psds.dtc, psds.gtc, psds.cttc, counts=psds, point=k)
-    ev, seg = counts.host()
-    return [(EventMetrics(ref.labels, ev[k]), SegmentMetrics(ref.labels, seg[k])) for k in range(K)]
+    if weak_labels is None:
+        ev, seg = counts.host()
+        return [(EventMetrics(ref.labels, ev[k]), SegmentMetrics(ref.labels, seg[k])) for k in range(K)]
+    tags = stitch_weak(win_strong, win_att, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3, weighting)
+    wc = weak_counts(tags["weak"], torch.from_numpy(weak_labels.astype(np.uint8)), weak_thr)
+    ev, seg, tail = counts.host(torch.cat([wc.reshape(-1), tags["err"].to(torch.int64)]))
+    err = int(tail[-1])
+    if err:
+        raise _lib.SedError("sed_stitch_weak reported err " + ", ".join(f"bit {b} ({t})" for b, t in STITCH_ERR_BITS.items()
+                                                                        if err & b) + f" (err = {err})")
+    wc = tail[:-1].reshape(len(weak_thr), NC, 4)
+    return ([(EventMetrics(ref.labels, ev[k]), SegmentMetrics(ref.labels, seg[k])) for k in range(K)],
+            {"f_measure": f_measure_from_counts(wc), "counts": wc})

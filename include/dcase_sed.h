@@ -209,6 +209,14 @@ int sed_crnn_buffers_init(const sed_dims* d, void* ctx, size_t ctx_bytes, void* 
  * "gru1","wz0","mean0","scale1","shift1",...}. Returns 0 and fills offset/bytes, or <0. */
 int sed_crnn_ctx_view(const sed_dims* d, const char* name, size_t* offset, size_t* bytes);
 
+/* The attention of the forward that filled ctx: att [B][T/8][nclass] fp32 = sof = clamp(softmax(dense_softmax(x), dim = -1),
+ * 1e-7, 1) (models/CRNN.py:79), the weights the heads pooled `weak` with.  Rebuilt from the attention logits that every
+ * sed_crnn_forward keeps in ctx (any `train`, any sed_dims.dtype, both kernel sets) with the heads kernel's own arithmetic
+ * and summation order; the forward's launches are unchanged.  One launch on `stream`, no allocation, hipGraph-capturable.
+ * sed_dims outside the hot path, a null pointer or ctx_bytes < sed_crnn_ctx_bytes(d): SED_ERR_BAD_ARG before any launch.
+ * Overlapping windows' weak tags cannot be combined without it: see sed_stitch_weak. */
+int sed_crnn_attention(const sed_dims* d, const void* ctx, size_t ctx_bytes, float* att, void* stream);
+
 /* ---- mean-teacher loss ---------------------------------------------------------------------
  * Replaces the loss block of main.train (main.py:93-145): target_weak = target.max(-2),
  * BCE(weak[wm]) + BCE(strong[sm]) + w*MSE(strong, strong_ema) + w*MSE(weak, weak_ema), with
@@ -565,6 +573,40 @@ int sed_stitch_sweep(const float* win_strong, const int32_t* rec_win0, const int
                      float* timeline, int64_t* ev_ptr, int32_t* ev_pairs, long long capacity, void* ws, size_t ws_bytes,
                      int32_t* err, void* stream);
 
+/* ---- recording-level weak tags of long recordings -------------------------------------------------
+ * A window's `weak` is a ratio num / den of attention-pooled sums (models/CRNN.py:79-81); the ratios of overlapping
+ * windows cannot be combined into the recording's ratio without the attention mass per frame.  sed_stitch_weak pools over
+ * the whole blended timeline instead.  The definition is the project's own, like the blend; pinned is agreement with a
+ * plain-loop statement that sums with math.fsum (tests/weak_np.py).  For recording r with L3_r timeline frames:
+ *   P[u, c]  the blend of win_strong as sed_stitch_decode defines it (same rounding; a frame covered by one window is
+ *            copied exactly)
+ *   A[u, c]  the SAME blend applied to win_att [n_win][T3][NC]: the windows' attention sof (sed_crnn_attention)
+ *   num[r, c] = sum_u (double)P[u, c] * (double)A[u, c]   (every product exact in fp64)
+ *   den[r, c] = sum_u (double)A[u, c]                     both over u = 0 .. L3_r - 1, in fp64
+ *   weak[r, c] = (float)(num / den)
+ * Frames of the last window beyond L3_r never enter the sums.  No special case for den == 0 (0 / 0 gives NaN) or NaN
+ * inputs (they propagate).  The order of the fp64 sums is fixed by the implementation and depends on (L3_r, NC) only -
+ * not on scheduling, alignment or the other recordings; no float atomics: two calls give identical bytes.
+ * Consequences: a single-window recording reproduces its window's clip-level weak up to the heads kernel's fp32
+ * summation; with hop3 == T3 and L3 a multiple of T3, weak[r] is the den-weighted mean of the windows' tags.
+ *   weak [n_rec][NC] fp32;  sums [n_rec][NC][2] fp64 (num, den) or NULL
+ *   err  one int32, OR-ed (zero it first), the bits of sed_stitch_decode: 16 = malformed rec_win0 / rec_frame0 or more
+ *        tiles than the workspace holds, 32 = a recording with too few windows to cover it.  The weak / sums rows of such
+ *        a recording are written as NaN (never stale, never partial); the address guarantee of sed_stitch_decode holds for
+ *        both window tensors.
+ *   ws   sed_stitch_weak_ws_bytes(sum L3, n_rec, NC) bytes, 8-byte aligned: one (num, den) pair per (tile slot, class);
+ *        ws_bytes must be that value (the tile slots are derived from it)
+ * Two launches on `stream`: a tile pass (one workgroup per sed_stitch_tile_frames() frames of one recording blends both
+ * tensors and reduces its fp64 products; no halo, no timeline is written) and a column pass.  16-byte accesses when
+ * NC % 4 == 0 and both window tensors are 16-byte aligned, a scalar path otherwise (the same summation order).  No host
+ * synchronisation, no allocation, hipGraph-capturable.
+ * Limits, checked before any launch (SED_ERR_BAD_ARG): NC <= 16, 1 <= hop3 <= T3 <= 4096, sum L3 * NC < 2^31.
+ * Not provided: tags per sub-span of a recording, a backward through the pooled tag. */
+size_t sed_stitch_weak_ws_bytes(long long total_frames, int n_rec, int nclass);
+int sed_stitch_weak(const float* win_strong, const float* win_att, const int32_t* rec_win0, const int64_t* rec_frame0,
+                    int n_rec, int T3, int NC, int hop3, int weighting, float* weak, double* sums, void* ws,
+                    size_t ws_bytes, int32_t* err, void* stream);
+
 /* ---- validation scoring ------------------------------------------------------------------------
  * Replaces, after get_predictions, the host-side scoring of the epoch loop (baseline/main.py:328-352):
  *   compute_strong_metrics(predictions, valid_synth_df) (evaluation_measures.py:234-246) = sed_eval's
@@ -699,7 +741,8 @@ int sed_psds_counts(const float* strong, int n_clips, int T, int nclass, int n_p
  *   integer results are bit-reproducible; hipGraph-capturable.  No table content can make a kernel address outside the
  *   arrays as est_capacity / ref_events and n_rec * nclass + 1 describe them.
  * Limits: nclass <= 16, est_capacity and ref_events < 2^31 - 1024, n_rec * nclass < 2^26.  Not provided: an exact
- *   matching for clusters beyond 64 per side, the overall error rate with substitutions, recording-level weak tags. */
+ *   matching for clusters beyond 64 per side, the overall error rate with substitutions.  Recording-level weak tags come
+ *   from sed_stitch_weak and are scored by sed_weak_counts. */
 size_t sed_long_score_ws_bytes(long long est_capacity, long long ref_events, int n_rec, int nclass);
 int sed_long_tile_events(void);
 int sed_long_event_counts(const int64_t* ev_ptr, const int32_t* ev_pairs, double num, double den, const double* est_on,

@@ -42,7 +42,17 @@ workloads at the same 50 thresholds with PSDS:
   The library's point-group size (sed_stitch_sweep_point_group) is recorded; --sweep-decode-only measures sed_stitch_sweep alone
   (a variant build with another group size, SED_LIB), and --candidates FILE,... copies such runs into the result.
 
-Usage: python tools/long_bench.py [--scoring | --sweep] [--rounds 5] [--decode-reps 30] [--out profiles/long_inference.json]"""
+--weak measures the recording-level weak tags (profiles/long_weak.json), on the same two workloads at the default hop:
+  predictions against predictions_with_weak - get_long_predictions without and with return_weak=True, alternated in one run,
+    --rounds rounds, medians: what the tags add to inference already paid for (the attention of every batch, one
+    sed_stitch_weak).  The addition counts as measured only where it exceeds the larger of the two legs' (max - min).
+  sed_stitch_weak alone (the C call on preallocated buffers) against the only route that can be assembled from the parts
+    there were before it - two stitch_decode(want_timeline=True) blends, of the posteriors and of the attention, and a torch
+    fp64 segmented reduction (torch.segment_reduce) of their product -, a device-event pair around the call(s), median of --decode-reps, same run;
+    the fused call counts as faster only where the difference of the medians exceeds the larger (max - min) of the two.
+  sed_crnn_attention alone on the context of one forward of a full batch, the same way.
+
+Usage: python tools/long_bench.py [--scoring | --sweep | --weak] [--rounds 5] [--decode-reps 30] [--out profiles/long_inference.json]"""
 import argparse
 import json
 import os
@@ -409,10 +419,78 @@ def sweep_workload(name, ctx, model, rounds, reps, decode_only):
     return out
 
 
+def weak_workload(name, model, rounds, reps):
+    import ctypes as C
+    n_rec, per = WORKLOADS[name]
+    recs = recordings(n_rec, per)
+    sc = scaler_of(recs[0])
+    names = [f"{name}_{r}.wav" for r in range(n_rec)]
+    labels = _Enc.labels
+    ls = inference.LongRecordingSet.from_arrays(recs, T, scaler=sc, filenames=names)
+    out = {"recordings": n_rec, "windows": ls.n_clips, "timeline_frames": ls.total_frames, "hop3": ls.hop3, "T3": ls.T3}
+    legs = {"predictions": lambda: inference.get_long_predictions(model, ls, labels, POOL, batch_size=BATCH),
+            "predictions_with_weak": lambda: inference.get_long_predictions(model, ls, labels, POOL, batch_size=BATCH,
+                                                                            return_weak=True)}
+    for fn in legs.values():
+        fn()
+    ms = {leg: [] for leg in legs}
+    for _ in range(rounds):
+        for leg, fn in legs.items():
+            ms[leg].append(wall_ms(fn))
+    for leg in legs:
+        out[leg] = stats(ms[leg])
+    a, b = out["predictions"], out["predictions_with_weak"]
+    band = max(max(x["samples_ms"]) - min(x["samples_ms"]) for x in (a, b))
+    out["weak_adds_ms"] = b["median_ms"] - a["median_ms"]
+    out["larger_max_minus_min_ms"] = band
+    out["addition_exceeds_spread"] = bool(out["weak_adds_ms"] > band)
+    # ---- sed_stitch_weak alone against the route composed of earlier parts ----------------------------------------------------
+    win_strong, win_att = inference.long_window_posteriors(model, ls, NCLASS, BATCH, want_attention=True)
+    l, dev, ptr = _lib.lib(), win_strong.device, _lib.ptr
+    total = ls.total_frames
+    weak = torch.empty(n_rec, NCLASS, device=dev)
+    sums = torch.empty(n_rec, NCLASS, 2, dtype=torch.float64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = torch.empty(l.sed_stitch_weak_ws_bytes(total, n_rec, NCLASS), dtype=torch.uint8, device=dev)
+
+    def fused():
+        _lib.check(l.sed_stitch_weak(ptr(win_strong), ptr(win_att), ptr(ls.rec_win0), ptr(ls.rec_frame0), n_rec, ls.T3, NCLASS,
+                                     ls.hop3, 1, ptr(weak), ptr(sums), ptr(ws), ws.numel(), ptr(err), _lib.stream_ptr()),
+                   "sed_stitch_weak")
+    lengths = ls.rec_frame0[1:] - ls.rec_frame0[:-1]
+    thr = torch.full((NCLASS,), 0.5, device=dev)
+    win = torch.full((NCLASS,), 1, dtype=torch.int32, device=dev)
+    state = {}
+
+    def composed():
+        tl = [inference.stitch_decode(w, ls.rec_win0, ls.rec_frame0, total, ls.hop3, thr, win, "taper", ls.capacity(NCLASS),
+                                      want_timeline=True)["timeline"].double() for w in (win_strong, win_att)]
+        num = torch.segment_reduce(tl[0] * tl[1], "sum", lengths=lengths, axis=0, unsafe=True)
+        den = torch.segment_reduce(tl[1], "sum", lengths=lengths, axis=0, unsafe=True)
+        state["weak"] = (num / den).float()
+    out["sed_stitch_weak_alone"] = event_ms(fused, reps)
+    out["composed_route"] = event_ms(composed, reps)
+    assert int(err.item()) == 0
+    out["max_abs_difference_of_the_two_routes"] = float((weak - state["weak"]).abs().max().item())
+    band = max(x["spread"] * x["median_ms"] for x in (out["sed_stitch_weak_alone"], out["composed_route"]))
+    out["composed_minus_fused_ms"] = out["composed_route"]["median_ms"] - out["sed_stitch_weak_alone"]["median_ms"]
+    out["larger_max_minus_min_alone_ms"] = band
+    out["fused_faster"] = bool(out["composed_minus_fused_ms"] > band)
+    # ---- sed_crnn_attention alone, on the context of one full batch ------------------------------------------------------------
+    with torch.no_grad():
+        model(ls.eval_batch(0, min(BATCH, ls.n_clips)))
+    cbuf, dims = model._last_ctx
+    att = torch.empty(dims.B, dims.T // 8, dims.nclass, device=dev)
+    out["sed_crnn_attention_alone"] = dict(event_ms(lambda: _lib.check(l.sed_crnn_attention(
+        C.byref(dims), ptr(cbuf), cbuf.numel(), ptr(att), _lib.stream_ptr()), "sed_crnn_attention"), reps), batch=int(dims.B))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scoring", action="store_true", help="measure the scoring of the long path's event table instead")
     ap.add_argument("--sweep", action="store_true", help="measure the K-point sweep legs alone (profiles/long_sweep.json)")
+    ap.add_argument("--weak", action="store_true", help="measure the recording-level weak tags (profiles/long_weak.json)")
     ap.add_argument("--sweep-decode-only", action="store_true", help="with --sweep: sed_stitch_sweep alone (a variant build)")
     ap.add_argument("--sweep-out", default=os.path.join(REPO, "profiles", "long_sweep.json"))
     ap.add_argument("--candidates", default="", help="with --sweep: earlier --sweep-decode-only results to copy in")
@@ -422,7 +500,8 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(REPO, "profiles", "long_scoring.json" if args.scoring else "long_inference.json")
+        args.out = os.path.join(REPO, "profiles", "long_weak.json" if args.weak else
+                                "long_scoring.json" if args.scoring else "long_inference.json")
     if not torch.cuda.is_available():
         raise SystemExit("long_bench.py measures on the GPU: no device found (nothing is measured on a CPU)")
     if args.rounds < 5 or args.decode_reps < 20:
@@ -436,6 +515,21 @@ def main():
               "not_measured": ["from_waveforms / feature extraction", "other batch sizes, bf16 / wide models",
                                "recordings longer than 1 h", "a run with the GPU to itself (the host is shared)"],
               "workloads": {}}
+    if args.weak:
+        result["timing"] = ("get_long_predictions legs: host clock around each synchronised call, alternated; the calls alone: a "
+                            "device-event pair around the call(s), warm, median of --decode-reps")
+        result["note"] = ("predictions_with_weak against the same run's predictions: what the tags add; the composed route is two "
+                          "stitch_decode(want_timeline=True) blends and a torch fp64 segment_reduce, the only route before "
+                          "sed_stitch_weak; a difference counts only where it exceeds the larger (max - min) of the two legs")
+        result["not_measured"] += ["other nclass than 10", "other hops than the default", "per-kernel counters",
+                                   "validate_long(weak_labels=...)"]
+        for name in args.workloads.split(","):
+            result["workloads"][name] = weak_workload(name, model, args.rounds, args.decode_reps)
+            print(json.dumps({name: result["workloads"][name]}), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(json.dumps(result, indent=1) + "\n")
+        return
     if args.sweep:
         args.scoring, args.out = True, None
     sweep = dict(result, workloads={}, timing="validate_long legs: host clock around each synchronised call, alternated; the calls "
