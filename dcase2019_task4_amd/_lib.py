@@ -63,6 +63,7 @@ _SIGS = {
                                    C.c_longlong, _P, C.c_size_t, _P, _P]),
     "sed_stitch_weak_ws_bytes": (C.c_size_t, [C.c_longlong, C.c_int, C.c_int]),
     "sed_stitch_weak": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P, _P]),
+    "sed_stitch_weak_backward": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     "sed_event_counts": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P,
                                    C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P]),
     "sed_psds_counts": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P,
@@ -89,6 +90,8 @@ _SIGS = {
     "sed_crnn_forward": (C.c_int, [C.POINTER(SedDims), _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P, _P, _P]),
     "sed_crnn_moments": (C.c_int, [C.POINTER(SedDims), _P, _P, C.c_size_t, _P]),
     "sed_crnn_backward": (C.c_int, [C.POINTER(SedDims), _P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P, C.c_size_t, C.c_int, _P]),
+    "sed_crnn_backward_att": (C.c_int, [C.POINTER(SedDims), _P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P, _P, C.c_size_t, C.c_int,
+                                        _P]),
     "sed_crnn_buffers_init": (C.c_int, [C.POINTER(SedDims), _P, C.c_size_t, _P, C.c_size_t, _P]),
     "sed_crnn_ctx_view": (C.c_int, [C.POINTER(SedDims), C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "sed_crnn_attention": (C.c_int, [C.POINTER(SedDims), _P, C.c_size_t, _P, _P]),

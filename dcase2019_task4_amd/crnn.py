@@ -124,6 +124,39 @@ class BidirectionalGRU(nn.Module):
         return recurrent
 
 
+def _crnn_backward(ctx, d_strong, d_weak, d_att=None, att_entry=False):
+    """The backward both autograd nodes share: sed_crnn_backward, or (``att_entry``) sed_crnn_backward_att with ``d_att`` -
+    None is passed as NULL; an absent ``d_strong`` / ``d_weak`` (that node does not materialise unused gradients) is zeros."""
+    l = _lib.lib()
+    if getattr(ctx, "eval_mode", False):
+        raise _lib.SedError("backward through CRNN.forward needs module.train(): the eval-mode backward (running "
+                            "BatchNorm statistics) is not implemented")
+    module, dims = ctx.module, ctx.dims
+    (x,) = ctx.saved_tensors
+    if ctx.flat_version != module._flat_gen:
+        raise _lib.SedError("CRNN parameters were re-laid-out between forward and backward")
+    B, T3, NC = dims.B, dims.T // 8, dims.nclass
+    d_strong = torch.zeros(B, T3, NC, device=x.device) if d_strong is None else d_strong.contiguous().float()
+    d_weak = torch.zeros(B, NC, device=x.device) if d_weak is None else d_weak.contiguous().float()
+    gflat = torch.empty_like(module._flat)
+    ws_bytes = l.sed_crnn_bwd_ws_bytes(C.byref(dims))
+    ws = _lib.scratch(ws_bytes, x.device)
+    _lib.check(l.sed_crnn_buffers_init(C.byref(dims), None, 0, _lib.ptr(ws), ws_bytes, _lib.stream_ptr()),
+               "sed_crnn_buffers_init")
+    head = (C.byref(dims), _lib.ptr(module._flat), _lib.ptr(x), _lib.ptr(ctx.seed_t), _lib.ptr(ctx.cbuf), ctx.cbuf.numel(),
+            _lib.ptr(d_strong), _lib.ptr(d_weak))
+    tail = (_lib.ptr(gflat), _lib.ptr(ws), ws_bytes, 3, _lib.stream_ptr())
+    if att_entry:
+        d_att = None if d_att is None else d_att.contiguous().float()
+        _lib.check(l.sed_crnn_backward_att(*head, _lib.ptr(d_att), *tail), "sed_crnn_backward_att")
+    else:
+        _lib.check(l.sed_crnn_backward(*head, *tail), "sed_crnn_backward")
+    grads = []
+    for i, (o0, o1, shp) in enumerate(module._layout):
+        grads.append(gflat[o0:o1].view(shp) if ctx.needs_input_grad[4 + i] else None)
+    return (None, None, None, None) + tuple(grads)
+
+
 class _CRNNFunction(torch.autograd.Function):
     """One autograd node for the whole network: forward = sed_crnn_forward, backward = sed_crnn_backward."""
 
@@ -162,29 +195,28 @@ class _CRNNFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_strong, d_weak):
+        return _crnn_backward(ctx, d_strong, d_weak)
+
+
+class _CRNNAttFunction(torch.autograd.Function):
+    """``CRNN.forward(return_attention=True)``: forward = sed_crnn_forward + sed_crnn_attention, backward =
+    sed_crnn_backward_att with the three upstream gradients (an absent ``d_att`` is passed as NULL, which enqueues exactly what
+    sed_crnn_backward does).  Refuses what ``_CRNNFunction`` refuses."""
+
+    @staticmethod
+    def forward(ctx, module, x, train, seed_t, *params):
         l = _lib.lib()
-        if getattr(ctx, "eval_mode", False):
-            raise _lib.SedError("backward through CRNN.forward needs module.train(): the eval-mode backward (running "
-                                "BatchNorm statistics) is not implemented")
-        module, dims = ctx.module, ctx.dims
-        (x,) = ctx.saved_tensors
-        if ctx.flat_version != module._flat_gen:
-            raise _lib.SedError("CRNN parameters were re-laid-out between forward and backward")
-        d_strong = d_strong.contiguous().float()
-        d_weak = d_weak.contiguous().float()
-        gflat = torch.empty_like(module._flat)
-        ws_bytes = l.sed_crnn_bwd_ws_bytes(C.byref(dims))
-        ws = _lib.scratch(ws_bytes, x.device)
-        _lib.check(l.sed_crnn_buffers_init(C.byref(dims), None, 0, _lib.ptr(ws), ws_bytes, _lib.stream_ptr()),
-                   "sed_crnn_buffers_init")
-        _lib.check(l.sed_crnn_backward(C.byref(dims), _lib.ptr(module._flat), _lib.ptr(x), _lib.ptr(ctx.seed_t),
-                                       _lib.ptr(ctx.cbuf), ctx.cbuf.numel(), _lib.ptr(d_strong), _lib.ptr(d_weak),
-                                       _lib.ptr(gflat), _lib.ptr(ws), ws_bytes, 3, _lib.stream_ptr()),
-                   "sed_crnn_backward")
-        grads = []
-        for i, (o0, o1, shp) in enumerate(module._layout):
-            grads.append(gflat[o0:o1].view(shp) if ctx.needs_input_grad[4 + i] else None)
-        return (None, None, None, None) + tuple(grads)
+        ctx.set_materialize_grads(False)         # an output the loss does not use arrives as None, not as a tensor of zeros
+        strong, weak = _CRNNFunction.forward(ctx, module, x, train, seed_t, *params)
+        cbuf, dims = module._last_ctx
+        att = torch.empty(dims.B, dims.T // 8, dims.nclass, device=x.device, dtype=torch.float32)
+        _lib.check(l.sed_crnn_attention(C.byref(dims), _lib.ptr(cbuf), cbuf.numel(), _lib.ptr(att), _lib.stream_ptr()),
+                   "sed_crnn_attention")
+        return strong, weak, att
+
+    @staticmethod
+    def backward(ctx, d_strong, d_weak, d_att):
+        return _crnn_backward(ctx, d_strong, d_weak, d_att, att_entry=True)
 
 
 class CRNN(nn.Module):
@@ -347,10 +379,15 @@ class CRNN(nn.Module):
         return torch.tensor([s], dtype=torch.int64, device=device)
 
     # ---- forward (CRNN.py:59-84) -------------------------------------------------------------------
-    def forward(self, x, seed=None):
+    def forward(self, x, seed=None, return_attention=False):
         """x: float32 [B, 1, T, 64] on the GPU -> (strong [B, T//8, nclass], weak [B, nclass]).
-        ``seed`` (int64 device tensor [1]) pins the dropout stream for tests."""
+        ``seed`` (int64 device tensor [1]) pins the dropout stream for tests.
+        ``return_attention=True``: ``(strong, weak, att)``, att [B, T//8, nclass] the attention the forward pooled ``weak`` with
+        (``last_attention``'s values), differentiable like the other two (``sed_crnn_backward_att``): what a loss on a tag pooled
+        outside the network - ``inference.pooled_tags`` - needs.  Hot path only (``SedError`` otherwise)."""
         if not self.hot_path:
+            if return_attention:
+                raise _lib.SedError("return_attention: this CRNN configuration is outside the MI355X hot path (CRNN.hot_path is False)")
             return self._stock_forward(x)
         if x.dim() != 4 or x.shape[1] != 1:
             raise ValueError(f"expected input [B, 1, T, F], got {tuple(x.shape)}")
@@ -364,6 +401,8 @@ class CRNN(nn.Module):
         use_drop = self.training and self._p_drop > 0
         seed_t = (seed if seed is not None else self._next_seed(x.device)) if use_drop else None
         params = list(self.parameters())
+        if return_attention:
+            return _CRNNAttFunction.apply(self, x, self.training, seed_t, *params)
         strong, weak = _CRNNFunction.apply(self, x, self.training, seed_t, *params)
         return strong, weak
 

@@ -456,7 +456,7 @@ extern "C" int sed_crnn_moments(const sed_dims* d, const float* x, void* ctx, si
 static int crnn_backward_impl(const sed_dims* d, const float* params, const float* x, const uint64_t* seed_dev,
                               void* ctx, size_t ctx_bytes, const float* d_strong, const float* d_weak, float* grads,
                               void* ws, size_t ws_bytes, int parts, void* stream, const HeadsLoss* hl,
-                              const HeadsOut* ho = nullptr) {
+                              const HeadsOut* ho = nullptr, const float* d_att = nullptr) {
     SED_TRY(sed_validate_dims(d));
     SED_CHECK_ARG(params && x && ctx && (hl || (d_strong && d_weak)) && grads && ws, "sed_crnn_backward: null argument");
     SED_CHECK_ARG(parts == 1 || parts == 2 || parts == 3 || parts == 5 || parts == 8,
@@ -467,7 +467,7 @@ static int crnn_backward_impl(const sed_dims* d, const float* params, const floa
         SED_CHECK_ARG(!(g.p > 0.f) || seed_dev, "sed_crnn_backward: dropout enabled but seed_dev is null");
         SideFork side0 = side_fork((hipStream_t)stream);
         return gen_backward(g, P, params, x, seed_dev, ctx, ctx_bytes, d_strong, d_weak, grads, ws, ws_bytes, parts, (hipStream_t)stream,
-                            side0, hl, ho);
+                            side0, hl, ho, d_att);
     }
     const Call c = {g, P, make_ctx_layout(g), make_ws_layout(g), params, grads, x, seed_dev, ctx, ws};
     const WsLayout& W = c.W;
@@ -479,7 +479,7 @@ static int crnn_backward_impl(const sed_dims* d, const float* params, const floa
     hipStream_t st = (hipStream_t)stream;
     SideFork side = side_fork(st);
     // ---- heads, BiGRU (+ the weight-gradient tail of a parts == 1 / parts == 8 call) --------------
-    const RnnBwd rb = rnn_backward_plan(g, P, rnn_bufs(c), params, grads, seed_dev, hl, ho, parts, &side);
+    const RnnBwd rb = rnn_backward_plan(g, P, rnn_bufs(c), params, grads, seed_dev, hl, ho, parts, &side, d_att);
     SED_TRY(rnn_backward(rb, d_strong, d_weak, st));
     if (!(parts & 2)) return SED_OK;
     // ---- conv blocks 2, 1 -----------------------------------------------------------------------
@@ -520,6 +520,16 @@ extern "C" int sed_crnn_backward(const sed_dims* d, const float* params, const f
                                  void* ctx, size_t ctx_bytes, const float* d_strong, const float* d_weak, float* grads,
                                  void* ws, size_t ws_bytes, int parts, void* stream) {
     return crnn_backward_impl(d, params, x, seed_dev, ctx, ctx_bytes, d_strong, d_weak, grads, ws, ws_bytes, parts, stream, nullptr);
+}
+
+// sed_crnn_backward with one more upstream gradient, d_att = dLoss/d(sof) (what sed_crnn_attention returns), added in the heads
+// backward (heads.hip: k_heads_bwd_att); d_att == NULL enqueues exactly what sed_crnn_backward does.  A parts value without the
+// heads (2, 8) has no use for it.
+extern "C" int sed_crnn_backward_att(const sed_dims* d, const float* params, const float* x, const uint64_t* seed_dev,
+                                     void* ctx, size_t ctx_bytes, const float* d_strong, const float* d_weak, const float* d_att,
+                                     float* grads, void* ws, size_t ws_bytes, int parts, void* stream) {
+    return crnn_backward_impl(d, params, x, seed_dev, ctx, ctx_bytes, d_strong, d_weak, grads, ws, ws_bytes, parts, stream, nullptr,
+                              nullptr, d_att);
 }
 
 // the argument checks and the loss inputs that sed_mt_loss_backward and sed_mt_step_backward share

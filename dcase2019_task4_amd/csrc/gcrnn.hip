@@ -287,7 +287,7 @@ int gen_forward(const Geo& g, const ParamOff& P, const float* params, float* bn_
 // Backward.  `side`: the helper stream of the caller's stream (owned by crnn.hip), or the caller's own.
 int gen_backward(const Geo& g, const ParamOff& P, const float* params, const float* x, const uint64_t* seed_dev, void* ctx,
                  size_t ctx_bytes, const float* d_strong, const float* d_weak, float* grads, void* ws, size_t ws_bytes, int parts,
-                 hipStream_t st, SideFork& side, const HeadsLoss* hl, const HeadsOut* ho) {
+                 hipStream_t st, SideFork& side, const HeadsLoss* hl, const HeadsOut* ho, const float* d_att) {
     const GCtx L = make_gctx(g);
     const GWs W = make_gws(g);
     if (ctx_bytes < L.total || ws_bytes < W.total) {
@@ -297,7 +297,7 @@ int gen_backward(const Geo& g, const ParamOff& P, const float* params, const flo
     const int C = g.C, H = g.H, BT = g.B * g.T3;
     const int use_drop = (g.p > 0.f) ? 1 : 0;
     // ---- heads, BiGRU (+ the weight-gradient tail of a parts == 1 / parts == 8 call) ------------------------------------------
-    const RnnBwd rb = rnn_backward_plan(g, P, rnn_bufs(g, L, ctx, &W, ws), params, grads, seed_dev, hl, ho, parts, &side);
+    const RnnBwd rb = rnn_backward_plan(g, P, rnn_bufs(g, L, ctx, &W, ws), params, grads, seed_dev, hl, ho, parts, &side, d_att);
     SED_TRY(rnn_backward(rb, d_strong, d_weak, st));
     if (!(parts & 2)) return SED_OK;
     // ---- conv blocks 2, 1 -------------------------------------------------------------------------------------------------

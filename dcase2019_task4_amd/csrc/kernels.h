@@ -290,7 +290,7 @@ int launch_heads_bwd(const float* h, const float* wd, const float* ws, const flo
                      const float* logits_s, const float* den, const float* d_strong, const float* d_weak, float* dh,
                      float* part, float* g_wd, float* g_bd, float* g_ws, float* g_bs, int B, int T, int NC, int use_drop,
                      float p_drop, const uint64_t* seed, double* zero, int n_zero, int defer_colsum, const HeadsLoss* hl, hipStream_t st,
-                     int HF = 128);
+                     int HF = 128, const float* d_att = nullptr);      // d_att: dLoss/d(sof) or null (sed_crnn_backward_att)
 
 // ---- round 5: heads forward + loss + heads backward as the prologue of the top layer's backward recurrence (hfuse.h, gru4.hip) ----
 struct HeadsFuse {

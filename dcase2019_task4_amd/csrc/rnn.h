@@ -63,9 +63,11 @@ struct RnnBwd {
     Geo g; ParamOff P; RnnBufs R;
     const float* params; float* grads; const uint64_t* seed_dev; const HeadsLoss* hl; const HeadsOut* ho; int parts; SideFork* side;
     bool fuse, defer_colsum, early_gru_w;
+    const float* d_att;                          // dLoss/d(sof) [B][T'][NC] (sed_crnn_backward_att) or null: the heads kernel adds it
 };
 RnnBwd rnn_backward_plan(const Geo& g, const ParamOff& P, const RnnBufs& R, const float* params, float* grads,
-                         const uint64_t* seed_dev, const HeadsLoss* hl, const HeadsOut* ho, int parts, SideFork* side);
+                         const uint64_t* seed_dev, const HeadsLoss* hl, const HeadsOut* ho, int parts, SideFork* side,
+                         const float* d_att = nullptr);
 int rnn_backward(const RnnBwd& rb, const float* d_strong, const float* d_weak, hipStream_t st);
 int rnn_weight_grads_layer(const RnnBwd& rb, int l, hipStream_t s2);      // GRU dW / db of one layer | of every layer, top down
 int rnn_weight_grads(const RnnBwd& rb, hipStream_t s2);

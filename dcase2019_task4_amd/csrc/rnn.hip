@@ -68,13 +68,15 @@ int rnn_forward(const Geo& g, const ParamOff& P, const float* params, const RnnB
 }
 
 RnnBwd rnn_backward_plan(const Geo& g, const ParamOff& P, const RnnBufs& R, const float* params, float* grads,
-                         const uint64_t* seed_dev, const HeadsLoss* hl, const HeadsOut* ho, int parts, SideFork* side) {
-    RnnBwd rb = {g, P, R, params, grads, seed_dev, hl, ho, parts, side, false, false, false};
+                         const uint64_t* seed_dev, const HeadsLoss* hl, const HeadsOut* ho, int parts, SideFork* side,
+                         const float* d_att) {
+    RnnBwd rb = {g, P, R, params, grads, seed_dev, hl, ho, parts, side, false, false, false, d_att};
     // ho != null: the forward left the output heads to this call (sed_mt_step_backward).  Fused form (hfuse.h, H = 64): heads
     // forward + loss + heads backward run as the prologue phase of the top layer's backward recurrence, the meters' clip sums, the
     // step-state advance and the head weight gradients' column sum in k_heads_fin where the column sum alone used to be.
-    // Otherwise (H = 256, SED_DEBUG_SEPARATE_HEADS, T / 8 > 128, gradient outputs asked for): k_heads_fwd, then the two-kernel form.
-    rb.fuse = ho && hl && (parts & 1) && heads_fusable(g.H, g.T3) && !(g_sed_debug & SED_DEBUG_SEPARATE_HEADS) && !hl->d_strong_out && !hl->d_weak_out;
+    // Otherwise (H = 256, SED_DEBUG_SEPARATE_HEADS, T / 8 > 128, gradient outputs asked for, an attention gradient given):
+    // k_heads_fwd, then the two-kernel form.
+    rb.fuse = ho && hl && (parts & 1) && heads_fusable(g.H, g.T3) && !(g_sed_debug & SED_DEBUG_SEPARATE_HEADS) && !hl->d_strong_out && !hl->d_weak_out && !d_att;
     // the column sum of the head weight gradients leaves the dX chain whenever something later takes it: the helper stream of
     // the conv-block backward (parts & 2), or the parts == 8 call that follows a parts == 5 one (parts & 4)
     rb.defer_colsum = ((parts & 2) && side->ok) || (parts & 4);
@@ -173,7 +175,7 @@ int rnn_backward(const RnnBwd& rb, const float* d_strong, const float* d_weak, h
             SED_TRY(launch_heads_bwd(h_last, params + P.dense_w, params + P.soft_w, R.strong_sv, R.weak_sv, R.logits_s, R.den_sv, d_strong,
                                      d_weak, R.d_out, R.heads_part, grads + P.dense_w, grads + P.dense_b, grads + P.soft_w,
                                      grads + P.soft_b, g.B, g.T3, g.NC, use_drop, g.p, rb.seed_dev, (parts & 2) ? R.zero : nullptr,
-                                     R.n_zero, rb.defer_colsum ? 1 : 0, rb.hl, st, 2 * H));
+                                     R.n_zero, rb.defer_colsum ? 1 : 0, rb.hl, st, 2 * H, rb.d_att));
         // ---- BiGRU ------------------------------------------------------------------------------------------------------
         // H = 64: rnn_gru_bwd64 (dX as two direction planes).  H = 256: one tensor, from a GEMM.
         const float* d_cur = R.d_out;

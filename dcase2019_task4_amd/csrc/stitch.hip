@@ -17,7 +17,8 @@
 // Onsets and offsets alternate along a column, so the offsets in front of a tile are the onsets in front of it minus one
 // when an event is open across the tile's first edge: one count per (tile, class) is enough.
 // sed_stitch_weak (at the end of the file) pools recording-level weak tags over the same tiles and slots: the same blend of the
-// posteriors and of the attention, fp64 sums in a fixed order, two launches, no timeline.
+// posteriors and of the attention, fp64 sums in a fixed order, two launches, no timeline.  sed_stitch_weak_backward (behind it) is
+// its transpose: the gradient of a loss on the pooled tags w.r.t. both window tensors, a clear and one tile pass, no atomics.
 //
 // Where a tile lives: the tiles of recording r take slots slot0(r) + k, slot0(r) = floor(rec_frame0[r] / ST_TILE) + r.  That
 // is strictly increasing in (r, k) for increasing rec_frame0, needs no table of its own and at most
@@ -593,6 +594,149 @@ extern "C" int sed_stitch_weak(const float* win_strong, const float* win_att, co
     else hipLaunchKernelGGL((k_stitch_weak_tile<false, 1>), tiles, thr256, 0, st, wa);
     SED_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_stitch_weak_cols, dim3((unsigned)(((long long)n_rec * NC + 3) / 4)), thr256, 0, st, wa);
+    SED_CHECK_LAUNCH();
+    return SED_OK;
+}
+
+// ---- backward through the pooled tag (sed_stitch_weak_backward) ---------------------------------------------------------------
+// The transpose of the blend-and-pool above, for a loss on weak[r, c] = num / den: with g = dLoss/dweak[r, c] and t = num / den,
+//   dLoss/dP[u, c] = g A[u, c] / den,   dLoss/dA[u, c] = g (P[u, c] - t) / den,
+// and a blended frame hands window j, local frame v = u - j hop3, the share w / W of either (w the window's weight at v, W the
+// integer sum over the windows covering u): the formulas and their rounding order are in include/dcase_sed.h.
+// A tile's workgroup owns its ST_TILE timeline frames as in k_stitch_weak_tile (no halo): an item is one frame x (1 or 4)
+// classes, it blends both tensors once (st_blend) and scatters to its <= ceil(T3 / hop3) covering windows.  A window element
+// (j, v, c) belongs to exactly one timeline element u = j hop3 + v, so every element has one writer: no atomics, and the bytes
+// do not depend on the tiling or on VEC.  What no timeline frame owns - the tail u >= L3 of a recording's last windows, the
+// windows of a rejected recording - is +0.0f from k_stitch_weak_bwd_zero, which runs first on the same stream and clears both
+// outputs over [0, rec_win0[n_rec]) (the window count lives on the device; a host-side memset would need it).
+// The call has no workspace to derive the slot count from, and the tables are device data: both kernels take it from
+// rec_frame0[n_rec] (sb_slots: the smallest count that st_rec accepts every well-formed table with) and walk the slots with a
+// grid-stride loop over a fixed grid.
+struct StWeakBwdArgs {
+    StArgs t;                // win_strong, the tables, T3 / NC / hop3 / weighting, err; n_slots is filled in on the device
+    const float* win_att;
+    const double* sums;      // [n_rec][NC][2] (num, den) of the forward
+    const float* g_weak;     // [n_rec][NC]
+    float* d_win_strong;     // [n_win][T3][NC]
+    float* d_win_att;
+};
+#define SB_GRID 512
+
+// Tile slots for the tables' own total, or 0 (st_rec then rejects every recording) when it is outside the forward's limits.
+__device__ __forceinline__ int sb_slots(const StArgs& a) {
+    const long long ft = a.rec_frame0[a.n_rec];
+    if (ft < 1 || ft >= (1ll << 31) || ft * a.NC >= (1ll << 31)) return 0;
+    return (int)(ft / ST_TILE + a.n_rec + 1);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_bwd_zero(StWeakBwdArgs wa) {
+    StArgs a = wa.t;
+    a.n_slots = sb_slots(a);
+    const size_t i0 = (size_t)blockIdx.x * ST_THREADS + threadIdx.x, stride = (size_t)gridDim.x * ST_THREADS;
+    for (size_t r = i0; r < (size_t)a.n_rec; r += stride) {
+        const StRec R = st_rec(a, (int)r);
+        if (R.bad) atomicOr(a.err, R.bad);
+    }
+    const long long wt = a.rec_win0[a.n_rec];
+    if (wt <= 0) return;
+    const size_t n = (size_t)wt * a.T3 * a.NC;
+    if (VEC) {
+        const f32x4 z = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (size_t i = i0; i < n / 4; i += stride) {
+            ((f32x4*)wa.d_win_strong)[i] = z;
+            ((f32x4*)wa.d_win_att)[i] = z;
+        }
+    } else {
+        for (size_t i = i0; i < n; i += stride) {
+            wa.d_win_strong[i] = 0.0f;
+            wa.d_win_att[i] = 0.0f;
+        }
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_bwd_tile(StWeakBwdArgs wa) {
+    StArgs a = wa.t;
+    a.n_slots = sb_slots(a);
+    const int tid = threadIdx.x, NC = a.NC, T3 = a.T3, hop3 = a.hop3;
+    constexpr int W = VEC ? 4 : 1;
+    const int G = VEC ? NC >> 2 : NC;
+    for (long long g = blockIdx.x; g < a.n_slots; g += gridDim.x) {
+        const int r = st_slot_rec(a, g);
+        const StRec R = st_rec(a, r);
+        if (R.bad) continue;                                                     // (k_stitch_weak_bwd_zero reports it)
+        const long long kt = g - R.slot0;
+        if (kt < 0 || kt >= R.tiles) continue;                                   // an empty slot
+        const int s = (int)kt * ST_TILE, e = min(s + ST_TILE, R.L3);
+        for (int it = tid; it < (e - s) * G; it += ST_THREADS) {
+            const int fl = it / G, q = it - fl * G, u = s + fl, col = W * q;
+            const f32x4 p = st_blend<VEC>(a, a.win_strong, R, u, q);
+            const f32x4 at = st_blend<VEC>(a, wa.win_att, R, u, q);
+            double dP[W], dA[W];
+#pragma unroll
+            for (int k = 0; k < W; ++k) {
+                const size_t rc = (size_t)r * NC + col + k;
+                const double gk = (double)wa.g_weak[rc], num = wa.sums[2 * rc], den = wa.sums[2 * rc + 1];
+                const double t = num / den;
+                dP[k] = (gk * (double)at[k]) / den;
+                dA[k] = (gk * ((double)p[k] - t)) / den;
+            }
+            const int j_lo = u >= T3 ? (u - T3) / hop3 + 1 : 0;                  // the covering windows, as st_blend takes them
+            const int j_hi = min(u / hop3, R.nw - 1);
+            int wsum = 0;
+            for (int j = j_lo; j <= j_hi; ++j) {
+                const int v = u - j * hop3;
+                wsum += a.weighting ? min(v + 1, T3 - v) : 1;
+            }
+            const double Ws = (double)wsum;
+            for (int j = j_lo; j <= j_hi; ++j) {
+                const int v = u - j * hop3;
+                const double w = (double)(a.weighting ? min(v + 1, T3 - v) : 1);
+                const size_t o = ((size_t)(R.w0 + j) * T3 + v) * NC + col;
+                f32x4 ds, da;
+#pragma unroll
+                for (int k = 0; k < W; ++k) {
+                    ds[k] = (float)((dP[k] * w) / Ws);
+                    da[k] = (float)((dA[k] * w) / Ws);
+                }
+                if (VEC) {
+                    *(f32x4*)(wa.d_win_strong + o) = ds;
+                    *(f32x4*)(wa.d_win_att + o) = da;
+                } else {
+                    wa.d_win_strong[o] = ds[0];
+                    wa.d_win_att[o] = da[0];
+                }
+            }
+        }
+    }
+}
+
+extern "C" int sed_stitch_weak_backward(const float* win_strong, const float* win_att, const int32_t* rec_win0,
+                                        const int64_t* rec_frame0, int n_rec, int T3, int NC, int hop3, int weighting,
+                                        const double* sums, const float* g_weak, float* d_win_strong, float* d_win_att,
+                                        int32_t* err, void* stream) {
+    const char* what = "sed_stitch_weak_backward";
+    ST_NEED(win_strong && win_att && rec_win0 && rec_frame0 && sums && g_weak && d_win_strong && d_win_att && err, "null argument");
+    ST_NEED(n_rec >= 1 && NC >= 1 && NC <= ST_MAXC && (long long)n_rec * NC < (1ll << 31),
+            "need n_rec >= 1, 1 <= NC <= 16 and n_rec * NC < 2^31");
+    ST_NEED(T3 >= 1 && T3 <= 4096, "need 1 <= T3 <= 4096 (the taper's weight sum stays exact in fp32)");
+    ST_NEED(hop3 >= 1 && hop3 <= T3, "need 1 <= hop3 <= T3");
+    ST_NEED(weighting == 0 || weighting == 1, "weighting is 0 (uniform) or 1 (taper)");
+    ST_NEED(((uintptr_t)sums % 8) == 0, "sums must be 8-byte aligned");
+    StWeakBwdArgs wa = {};
+    wa.t.win_strong = win_strong; wa.t.rec_win0 = rec_win0; wa.t.rec_frame0 = rec_frame0; wa.t.err = err;
+    wa.t.n_rec = n_rec; wa.t.T3 = T3; wa.t.NC = NC; wa.t.hop3 = hop3; wa.t.weighting = weighting; wa.t.K = 1;
+    wa.win_att = win_att; wa.sums = sums; wa.g_weak = g_weak; wa.d_win_strong = d_win_strong; wa.d_win_att = d_win_att;
+    const bool vec = NC % 4 == 0 && ((uintptr_t)win_strong % 16) == 0 && ((uintptr_t)win_att % 16) == 0 &&
+                     ((uintptr_t)d_win_strong % 16) == 0 && ((uintptr_t)d_win_att % 16) == 0;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(SB_GRID), thr256(ST_THREADS);
+    if (vec) hipLaunchKernelGGL((k_stitch_weak_bwd_zero<true>), grid, thr256, 0, st, wa);
+    else hipLaunchKernelGGL((k_stitch_weak_bwd_zero<false>), grid, thr256, 0, st, wa);
+    SED_CHECK_LAUNCH();
+    if (vec) hipLaunchKernelGGL((k_stitch_weak_bwd_tile<true>), grid, thr256, 0, st, wa);
+    else hipLaunchKernelGGL((k_stitch_weak_bwd_tile<false>), grid, thr256, 0, st, wa);
     SED_CHECK_LAUNCH();
     return SED_OK;
 }

@@ -14,7 +14,8 @@ Recordings longer than one clip: ``LongRecordingSet`` (longrec.py) holds them as
 Training on windows of such recordings is ``WindowedFeatureSet`` (longrec.py, through ``train.train``).  Recording-level
 weak tags: ``get_long_predictions(return_weak=True)`` / ``stitch_weak`` pool them over the whole blended timeline from the
 windows' posteriors and attention (``CRNN.last_attention``, ``sed_stitch_weak``); ``weak_tags_dataframe`` is their table,
-``metrics.validate_long(weak_labels=...)`` their score.  ``get_predictions`` itself is unchanged.
+``metrics.validate_long(weak_labels=...)`` their score; ``pooled_tags`` is the same tag with a backward
+(``sed_stitch_weak_backward``), what ``train.train_recording_tags`` trains on.  ``get_predictions`` itself is unchanged.
 """
 import ctypes as C
 
@@ -285,6 +286,73 @@ def stitch_weak(win_strong, win_att, rec_win0, rec_frame0, total_frames, hop3, w
                                  int(hop3), WEIGHTINGS[weighting], _lib.ptr(out["weak"]), _lib.ptr(out["sums"]), _lib.ptr(ws),
                                  ws.numel(), _lib.ptr(out["err"]), _lib.stream_ptr()), "sed_stitch_weak")
     return out
+
+
+class _PooledTags(torch.autograd.Function):
+    """forward = sed_stitch_weak with the (num, den) sums kept, backward = sed_stitch_weak_backward."""
+
+    @staticmethod
+    def forward(ctx, win_strong, win_att, rec_win0, rec_frame0, total, hop3, weighting, err):
+        l = _lib.lib()
+        n_win, T3, NC = win_strong.shape
+        n_rec, dev = rec_win0.numel() - 1, win_strong.device
+        weak = torch.empty(n_rec, NC, dtype=torch.float32, device=dev)
+        sums = torch.empty(n_rec, NC, 2, dtype=torch.float64, device=dev)
+        ws = _lib.scratch(l.sed_stitch_weak_ws_bytes(total, n_rec, NC), dev)
+        _lib.check(l.sed_stitch_weak(_lib.ptr(win_strong), _lib.ptr(win_att), _lib.ptr(rec_win0), _lib.ptr(rec_frame0), n_rec, T3, NC,
+                                     hop3, weighting, _lib.ptr(weak), _lib.ptr(sums), _lib.ptr(ws), ws.numel(), _lib.ptr(err),
+                                     _lib.stream_ptr()), "sed_stitch_weak")
+        ctx.save_for_backward(win_strong, win_att, rec_win0, rec_frame0, sums)
+        ctx.hop3, ctx.weighting, ctx.err = hop3, weighting, err          # (err: the library ORs into it, autograd never sees it)
+        return weak
+
+    @staticmethod
+    def backward(ctx, g_weak):
+        l = _lib.lib()
+        win_strong, win_att, rec_win0, rec_frame0, sums = ctx.saved_tensors
+        err = ctx.err
+        n_win, T3, NC = win_strong.shape
+        g_weak = g_weak.contiguous().float()
+        d_strong, d_att = torch.empty_like(win_strong), torch.empty_like(win_att)
+        _lib.check(l.sed_stitch_weak_backward(_lib.ptr(win_strong), _lib.ptr(win_att), _lib.ptr(rec_win0), _lib.ptr(rec_frame0),
+                                              rec_win0.numel() - 1, T3, NC, ctx.hop3, ctx.weighting, _lib.ptr(sums),
+                                              _lib.ptr(g_weak), _lib.ptr(d_strong), _lib.ptr(d_att), _lib.ptr(err),
+                                              _lib.stream_ptr()), "sed_stitch_weak_backward")
+        return d_strong, d_att, None, None, None, None, None, None
+
+
+def pooled_tags(win_strong, win_att, rec_win0, rec_frame0, total_frames, hop3, weighting="taper", n_win=None):
+    """``stitch_weak``'s recording-level tags as a differentiable function of both window tensors: ``(weak, err)``, ``weak``
+    [n_rec, nclass] float32 with an autograd node whose forward is ``sed_stitch_weak`` and whose backward is
+    ``sed_stitch_weak_backward`` (the forward's fp64 sums are kept for it); ``err`` [1] int32 on the device, OR-ed into by both
+    (``STITCH_ERR_BITS`` 16 / 32; nothing synchronises - read it when convenient, the tags and gradients are invalid when it
+    is nonzero).  Arguments as for ``stitch_weak``.  The window tensors must hold exactly ``rec_win0[-1]`` windows: the
+    backward writes every element of both gradients over the tables' own window count, which lives on the device.  ``n_win``:
+    that count where the caller has it on the host (``train_recording_tags`` does) - checked against the tensors here, with
+    no synchronisation; without it the requirement is the caller's."""
+    if weighting not in WEIGHTINGS:
+        raise ValueError(f"weighting must be one of {sorted(WEIGHTINGS)}, got {weighting!r}")
+    if win_strong.dim() != 3 or win_att.shape != win_strong.shape:
+        raise ValueError(f"win_strong and win_att must both be [n_win, T3, nclass], got {tuple(win_strong.shape)} and "
+                         f"{tuple(win_att.shape)}")
+    n_tensor, T3, NC = win_strong.shape
+    if n_win is not None and int(n_win) != n_tensor:
+        raise ValueError(f"the tables describe {int(n_win)} windows, the window tensors hold {n_tensor}")
+    total, n_rec = int(total_frames), rec_win0.numel() - 1
+    if not 1 <= NC <= 16 or not 1 <= int(hop3) <= T3 <= 4096 or n_rec < 1 or total < 1:
+        raise ValueError(f"need 1 <= nclass <= 16, 1 <= hop3 <= T3 <= 4096, n_rec >= 1, total_frames >= 1; got nclass {NC}, "
+                         f"hop3 {hop3}, T3 {T3}, n_rec {n_rec}, total_frames {total}")
+    if total * NC >= 2 ** 31:
+        raise ValueError(f"{total} timeline frames x {NC} classes: the product must stay below 2^31")
+    if win_strong.device.type != "cuda" or win_att.device != win_strong.device:
+        raise _lib.SedError("pooled_tags needs GPU tensors on one device (no CPU fallback)")
+    if rec_win0.dtype != torch.int32 or rec_frame0.dtype != torch.int64 or rec_frame0.numel() != n_rec + 1 or \
+            rec_win0.device != win_strong.device or rec_frame0.device != win_strong.device:
+        raise ValueError("rec_win0 [n_rec + 1] int32 and rec_frame0 [n_rec + 1] int64 must be on the window tensors' device")
+    err = torch.zeros(1, dtype=torch.int32, device=win_strong.device)
+    weak = _PooledTags.apply(win_strong.contiguous().float(), win_att.contiguous().float(), rec_win0.contiguous(),
+                             rec_frame0.contiguous(), total, int(hop3), WEIGHTINGS[weighting], err)
+    return weak, err
 
 
 def weak_tags_dataframe(weak, filenames, labels, threshold=0.5):

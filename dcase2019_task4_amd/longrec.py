@@ -81,6 +81,28 @@ def sweep_chunks(K, capacity_per_point, max_table_bytes, limit=2 ** 31 - 1024):
     return [(k0, min(k0 + per, K)) for k0 in range(0, K, per)]
 
 
+def recording_tag_runs(n_windows, max_windows):
+    """``n_windows`` [n_rec] windows per recording -> ``[(r0, r1), ...]``: runs of consecutive recordings covering
+    ``0 .. n_rec`` once, packed greedily - a run takes recordings while its windows stay within ``max_windows``.  A recording
+    with more than ``max_windows`` windows raises ``ValueError`` (it needs more than one forward: not provided)."""
+    n_windows = np.asarray(n_windows, dtype=np.int64)
+    max_windows = int(max_windows)
+    if n_windows.ndim != 1 or n_windows.size < 1 or (n_windows < 1).any() or max_windows < 1:
+        raise ValueError("need at least one recording, at least one window per recording and max_windows >= 1")
+    if int(n_windows.max()) > max_windows:
+        r = int(n_windows.argmax())
+        raise ValueError(f"recording {r} has {int(n_windows[r])} windows, more than max_windows = {max_windows}: a recording "
+                         "must fit in one forward")
+    runs, r0, used = [], 0, 0
+    for r, n in enumerate(n_windows):
+        if used + int(n) > max_windows:
+            runs.append((r0, r))
+            r0, used = r, 0
+        used += int(n)
+    runs.append((r0, len(n_windows)))
+    return runs
+
+
 class LongRecordingSet(ResidentFeatureSet):
     """Recordings of any lengths, resident in one HBM pool; the set's "clips" are their overlapping windows.
 
@@ -147,11 +169,25 @@ class LongRecordingSet(ResidentFeatureSet):
         self.rec_win0 = torch.from_numpy(self.rec_win0_host).to(self.device)
         self.rec_frame0 = torch.from_numpy(self.rec_frame0_host).to(self.device)
         self._all = None
+        self._tag_batches = None
         if filenames is None:
             filenames = [f"recording_{i}" for i in range(self.n_rec)]
         if len(filenames) != self.n_rec:
             raise ValueError(f"{len(filenames)} filenames for {self.n_rec} recordings")
         self.filenames = list(filenames)
+
+    def tag_batches(self, max_windows):
+        """The batches ``train.train_recording_tags`` runs over this set, built once per ``max_windows`` and kept:
+        ``(runs, at, rec_win0, rec_frame0)`` - ``runs`` from ``recording_tag_runs``; the batch-local tables of every run
+        (rebased to the run's first window / frame) concatenated into one device tensor each, run ``k``'s tables are the
+        slices ``[at[k]:at[k + 1]]``."""
+        if self._tag_batches is None or self._tag_batches[0] != int(max_windows):
+            runs = recording_tag_runs(np.diff(self.rec_win0_host), max_windows)
+            w = np.concatenate([self.rec_win0_host[r0:r1 + 1] - self.rec_win0_host[r0] for r0, r1 in runs]).astype(np.int32)
+            f = np.concatenate([self.rec_frame0_host[r0:r1 + 1] - self.rec_frame0_host[r0] for r0, r1 in runs]).astype(np.int64)
+            at = np.concatenate([[0], np.cumsum([r1 - r0 + 1 for r0, r1 in runs])])
+            self._tag_batches = (int(max_windows), runs, at, torch.from_numpy(w).to(self.device), torch.from_numpy(f).to(self.device))
+        return self._tag_batches[1:]
 
     def capacity(self, nclass):
         """Events ``sed_stitch_decode`` can never exceed: sum over recordings of nclass * ceil(L3 / 2)."""

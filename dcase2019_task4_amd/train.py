@@ -865,3 +865,85 @@ def train(train_loader, model, optimizer, epoch, ema_model=None, weak_mask=None,
             _check_loss(step_obj.meters())
             step_obj.check_health()
     return _epoch_end(step_obj, epoch, start, log)
+
+
+# ---- training on recording-level tags ------------------------------------------------------------------------------------------
+def recording_tag_batches(n_windows, max_windows, seed, epoch):
+    """The batches of one ``train_recording_tags`` epoch: ``n_windows`` [n_rec] windows per recording ->
+    ``(runs, order)``.  ``runs``: ``longrec.recording_tag_runs`` - runs of consecutive recordings covering ``0 .. n_rec`` once,
+    packed greedily within ``max_windows`` windows (a recording with more raises ``ValueError``); ``order``: the permutation
+    of the runs drawn by ``np.random.default_rng([seed, epoch])``, the order the epoch visits them in."""
+    from .longrec import recording_tag_runs
+    runs = recording_tag_runs(n_windows, max_windows)
+    return runs, _tag_batch_order(len(runs), seed, epoch)
+
+
+def _tag_batch_order(n_batches, seed, epoch):
+    return np.random.default_rng([int(seed), int(epoch)]).permutation(n_batches)
+
+
+def recording_tags_loss(long_set, tags_dev, model, run, tables, weighting="taper"):
+    """The loss of one ``train_recording_tags`` batch - the recordings ``run = (r0, r1)`` of ``long_set`` - with its graph:
+    the run's windows through the set's eval gather, ``model(x, return_attention=True)``, ``inference.pooled_tags``, the mean
+    ``binary_cross_entropy`` over the run's (recording, class) pairs.  Returns ``(loss, err)``."""
+    from .inference import pooled_tags
+    r0, r1 = run
+    k, at, win0_all, frame0_all = tables
+    w0, w1 = int(long_set.rec_win0_host[r0]), int(long_set.rec_win0_host[r1])
+    total = int(long_set.rec_frame0_host[r1] - long_set.rec_frame0_host[r0])
+    x = long_set.eval_batch(w0, w1 - w0)
+    strong, _, att = model(x, return_attention=True)
+    weak, err = pooled_tags(strong, att, win0_all[at[k]:at[k + 1]], frame0_all[at[k]:at[k + 1]], total, long_set.hop3, weighting,
+                            n_win=w1 - w0)
+    return torch.nn.functional.binary_cross_entropy(weak, tags_dev[r0:r1]), err
+
+
+def train_recording_tags(long_set, tags, model, optimizer, epoch, ema_model=None, max_windows=64, seed=0, log=None):
+    """One epoch of training on RECORDING-LEVEL tags: ``long_set`` a ``LongRecordingSet`` (recordings of any lengths, as
+    overlapping windows), ``tags`` [n_rec, nclass] float targets in [0, 1] - all the labels a weakly labelled recording has.
+    A window's own ``weak`` cannot be held to the recording's tags (the event may sit in another window), so the loss is on
+    the tag pooled over the whole blended timeline (``inference.pooled_tags``); its gradient reaches every window of the
+    recording through the posteriors and the attention (``sed_stitch_weak_backward``, ``sed_crnn_backward_att``).
+
+    A batch is a run of consecutive recordings of at most ``max_windows`` windows (``LongRecordingSet.tag_batches``; a recording
+    with more raises ``ValueError``), the batch order is drawn from (``seed``, ``epoch``).  Per batch: forward in train mode,
+    mean BCE over the batch's (recording, class) pairs, ``backward()``, ``optimizer.step()`` (a torch optimizer over
+    ``model.parameters()``), and with ``ema_model`` ``update_ema_variables(model, ema_model, 0.999, epoch * n_batches + i)`` as
+    ``train()`` counts steps.  Nothing synchronises inside the epoch: the kernels' error word is read once at its end
+    (nonzero raises ``SedError``), with the mean loss, which is returned."""
+    from .longrec import LongRecordingSet
+    if not isinstance(long_set, LongRecordingSet):
+        raise ValueError("train_recording_tags needs a LongRecordingSet")
+    tags_np = tags.detach().cpu().numpy() if torch.is_tensor(tags) else np.asarray(tags)
+    if tags_np.ndim != 2 or tags_np.shape[0] != long_set.n_rec:
+        raise ValueError(f"tags must be [n_rec = {long_set.n_rec}, nclass], got {tags_np.shape}")
+    if not ((tags_np >= 0) & (tags_np <= 1)).all():
+        raise ValueError("tags must lie in [0, 1]")
+    runs, at, win0_all, frame0_all = long_set.tag_batches(max_windows)
+    order = _tag_batch_order(len(runs), seed, epoch)
+    start = time.time()
+    dev = long_set.device
+    tags_dev = torch.as_tensor(tags_np, dtype=torch.float32).to(dev)
+    model.to(dev)
+    model.train()
+    n_batches = len(runs)
+    loss_sum = torch.zeros((), dtype=torch.float32, device=dev)
+    err_all = torch.zeros(1, dtype=torch.int32, device=dev)
+    for i, k in enumerate(order):
+        optimizer.zero_grad()
+        loss, err = recording_tags_loss(long_set, tags_dev, model, runs[k], (int(k), at, win0_all, frame0_all))
+        loss.backward()
+        optimizer.step()
+        if ema_model is not None:
+            update_ema_variables(model, ema_model, 0.999, int(epoch) * n_batches + i)
+        loss_sum += loss.detach()
+        err_all |= err
+    mean = float(loss_sum.item()) / n_batches
+    bits = int(err_all.item())
+    if bits:
+        raise _lib.SedError(f"train_recording_tags: the pooling kernels raised error bits {bits} (16: malformed tables, 32: a "
+                            "recording its windows do not cover)")
+    assert not (mean != mean or mean > 1e5), 'Loss explosion: {}'.format(mean)
+    if log is not None:
+        log('Epoch: {}\tTime {:.2f}\trecording_tag_loss {:.4g}'.format(epoch, time.time() - start, mean))
+    return mean

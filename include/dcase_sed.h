@@ -196,6 +196,15 @@ size_t sed_crnn_bwd_ws_bytes(const sed_dims* d);
 int sed_crnn_backward(const sed_dims* d, const float* params, const float* x, const uint64_t* seed_dev,
                       void* ctx, size_t ctx_bytes, const float* d_strong, const float* d_weak,
                       float* grads, void* ws, size_t ws_bytes, int parts, void* stream);
+/* sed_crnn_backward with one more upstream gradient: d_att [B][T/8][nclass] fp32 = dLoss/d(sof), sof the attention as
+ * sed_crnn_attention returns it (after the clamp).  The heads backward adds it to the gradient that reaches sof through the
+ * pooling, in front of the clamp's pass mask: ds = (dnum * strong + dden + d_att) * pass; nothing else differs, every other
+ * argument, `parts` value, sed_dims.dtype and both kernel sets as for sed_crnn_backward.  d_att == NULL enqueues exactly
+ * what sed_crnn_backward enqueues (bit-identical gradients).  A loss on anything formed from the attention outside the
+ * network - the recording-level tag of sed_stitch_weak - reaches the parameters through it. */
+int sed_crnn_backward_att(const sed_dims* d, const float* params, const float* x, const uint64_t* seed_dev,
+                          void* ctx, size_t ctx_bytes, const float* d_strong, const float* d_weak, const float* d_att,
+                          float* grads, void* ws, size_t ws_bytes, int parts, void* stream);
 
 /* One-time initialisation of a FRESH ctx and / or backward workspace (either pointer may be NULL): clears the few
  * regions the library reads before it writes them - the wide model's cluster recurrence keeps launch epochs and tagged
@@ -601,11 +610,47 @@ int sed_stitch_sweep(const float* win_strong, const int32_t* rec_win0, const int
  * NC % 4 == 0 and both window tensors are 16-byte aligned, a scalar path otherwise (the same summation order).  No host
  * synchronisation, no allocation, hipGraph-capturable.
  * Limits, checked before any launch (SED_ERR_BAD_ARG): NC <= 16, 1 <= hop3 <= T3 <= 4096, sum L3 * NC < 2^31.
- * Not provided: tags per sub-span of a recording, a backward through the pooled tag. */
+ * Not provided: tags per sub-span of a recording.  The backward through the pooled tag is sed_stitch_weak_backward. */
 size_t sed_stitch_weak_ws_bytes(long long total_frames, int n_rec, int nclass);
 int sed_stitch_weak(const float* win_strong, const float* win_att, const int32_t* rec_win0, const int64_t* rec_frame0,
                     int n_rec, int T3, int NC, int hop3, int weighting, float* weak, double* sums, void* ws,
                     size_t ws_bytes, int32_t* err, void* stream);
+
+/* ---- backward through the pooled tag: training on recording-level tags ----------------------------
+ * The transpose of sed_stitch_weak for a loss on weak[r, c]: the gradient w.r.t. both window tensors.  The inputs are the
+ * forward's, plus
+ *   sums   [n_rec][NC][2] fp64  the (num, den) pairs sed_stitch_weak returned for the same inputs
+ *   g_weak [n_rec][NC]    fp32  dLoss/dweak
+ * For recording r, class c, window j of that recording, local frame v, timeline frame u = j * hop3 + v < L3_r:
+ *   P[u, c], A[u, c]  the blends of win_strong / win_att exactly as sed_stitch_decode defines them (one code)
+ *   w = 1 (uniform) or min(v + 1, T3 - v) (taper);  W(u) = the integer sum of w over the windows covering u
+ * and, every operation an individually rounded fp64 operation in this order (g = g_weak[r, c]),
+ *   t  = num / den
+ *   dP = ((double)g * (double)A[u, c]) / den
+ *   dA = ((double)g * ((double)P[u, c] - t)) / den
+ *   d_win_strong[j, v, c] = (float)((dP * (double)w) / (double)W)
+ *   d_win_att[j, v, c]    = (float)((dA * (double)w) / (double)W)
+ * (a frame covered by one window has w / W = 1).  u >= L3_r - the tail of a recording's last windows - gives +0.0f.
+ * EVERY element of both outputs in [0, rec_win0[n_rec]) is written by the call, +0.0f where nothing above defines it; the
+ * caller need not clear anything.  The gradient is that of the blended values as computed: the fp32 rounding of the blend
+ * itself is not differentiated (every element within 5e-6 of its own magnitude + 1e-9 of the float64 central difference of
+ * sum(g * weak): the bound tests/test_long_weak_bwd_cpu.py asserts).
+ *   err  one int32, OR-ed (zero it first): a recording sed_stitch_weak rejects raises the same bits here (16 malformed
+ *        tables - also a rec_frame0[n_rec] outside 1 .. 2^31 / NC - , 32 too few windows) and its windows are left zero.  A
+ *        caller must treat all outputs as invalid when err != 0.  The address guarantee of sed_stitch_decode holds for all
+ *        four window tensors.  Tables whose recordings share windows are not detected: the shared elements then hold one
+ *        of the recordings' values.
+ * Two launches on `stream`: a clear of both outputs (the window count is device data), then one tile pass - a workgroup
+ * owns sed_stitch_tile_frames() frames of one recording, no halo; each timeline element blends both tensors once and
+ * scatters to its <= ceil(T3 / hop3) covering windows; each window element has exactly one owner, so there are no atomics and
+ * two calls give identical bytes.  16-byte accesses when NC % 4 == 0 and all four window tensors are 16-byte aligned, a
+ * scalar path otherwise (identical bytes).  No workspace, no host synchronisation, no allocation, hipGraph-capturable.
+ * Limits, checked before any launch (SED_ERR_BAD_ARG, outputs untouched): NC <= 16, 1 <= hop3 <= T3 <= 4096,
+ * n_rec * NC < 2^31, no null pointer. */
+int sed_stitch_weak_backward(const float* win_strong, const float* win_att, const int32_t* rec_win0,
+                             const int64_t* rec_frame0, int n_rec, int T3, int NC, int hop3, int weighting,
+                             const double* sums, const float* g_weak, float* d_win_strong, float* d_win_att,
+                             int32_t* err, void* stream);
 
 /* ---- validation scoring ------------------------------------------------------------------------
  * Replaces, after get_predictions, the host-side scoring of the epoch loop (baseline/main.py:328-352):

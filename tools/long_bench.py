@@ -52,7 +52,12 @@ workloads at the same 50 thresholds with PSDS:
     the fused call counts as faster only where the difference of the medians exceeds the larger (max - min) of the two.
   sed_crnn_attention alone on the context of one forward of a full batch, the same way.
 
-Usage: python tools/long_bench.py [--scoring | --sweep | --weak] [--rounds 5] [--decode-reps 30] [--out profiles/long_inference.json]"""
+--tag-train measures training on recording-level tags (profiles/long_tag_train.json), same workloads and hop:
+  sed_stitch_weak_backward alone, and the forward + backward pair, against a torch-autograd restatement of the blend (index_add_)
+  and the fp64 pooling - the only route to the gradient before it - with the largest difference of the two routes' gradients;
+  on 100x3min one train.train_recording_tags epoch against the same batches with a window-level loss, alternated.
+
+Usage: python tools/long_bench.py [--scoring | --sweep | --weak | --tag-train] [--rounds 5] [--decode-reps 30] [--out profiles/long_inference.json]"""
 import argparse
 import json
 import os
@@ -486,11 +491,135 @@ def weak_workload(name, model, rounds, reps):
     return out
 
 
+def tag_train_workload(name, model, rounds, reps):
+    """--tag-train: (a) sed_stitch_weak_backward alone against the torch-autograd restatement of blend + fp64 pooling, the only
+    route to the gradient before it; (b) where every recording fits one forward (100x3min): one train_recording_tags epoch
+    against the same batches' forward + backward + step with a plain window-level loss - what the pooled loss adds."""
+    from dcase2019_task4_amd import train
+    n_rec, per = WORKLOADS[name]
+    recs = recordings(n_rec, per)
+    sc = scaler_of(recs[0])
+    ls = inference.LongRecordingSet.from_arrays(recs, T, scaler=sc, filenames=[f"{name}_{r}.wav" for r in range(n_rec)])
+    out = {"recordings": n_rec, "windows": ls.n_clips, "timeline_frames": ls.total_frames, "hop3": ls.hop3, "T3": ls.T3}
+    model.eval()
+    win_strong, win_att = inference.long_window_posteriors(model, ls, NCLASS, BATCH, want_attention=True)
+    l, dev, ptr = _lib.lib(), win_strong.device, _lib.ptr
+    total, T3, hop3 = ls.total_frames, ls.T3, ls.hop3
+    g = torch.randn(n_rec, NCLASS, device=dev, generator=torch.Generator(dev).manual_seed(1))
+    weak = torch.empty(n_rec, NCLASS, device=dev)
+    sums = torch.empty(n_rec, NCLASS, 2, dtype=torch.float64, device=dev)
+    d_s, d_a = torch.empty_like(win_strong), torch.empty_like(win_att)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = torch.empty(l.sed_stitch_weak_ws_bytes(total, n_rec, NCLASS), dtype=torch.uint8, device=dev)
+
+    def fused_fwd():
+        _lib.check(l.sed_stitch_weak(ptr(win_strong), ptr(win_att), ptr(ls.rec_win0), ptr(ls.rec_frame0), n_rec, T3, NCLASS, hop3, 1,
+                                     ptr(weak), ptr(sums), ptr(ws), ws.numel(), ptr(err), _lib.stream_ptr()), "sed_stitch_weak")
+
+    def fused_bwd():
+        _lib.check(l.sed_stitch_weak_backward(ptr(win_strong), ptr(win_att), ptr(ls.rec_win0), ptr(ls.rec_frame0), n_rec, T3, NCLASS,
+                                              hop3, 1, ptr(sums), ptr(g), ptr(d_s), ptr(d_a), ptr(err), _lib.stream_ptr()),
+                   "sed_stitch_weak_backward")
+    # the restatement's index tables: timeline frame and taper weight of every (window, local frame); frames past the end dropped
+    rec_of_win = np.repeat(np.arange(n_rec), np.diff(ls.rec_win0_host))
+    j = np.arange(ls.n_clips) - ls.rec_win0_host[rec_of_win]
+    v = np.arange(T3)
+    u = j[:, None] * hop3 + v[None, :]
+    ok = u < np.diff(ls.rec_frame0_host)[rec_of_win][:, None]
+    frame = torch.from_numpy((ls.rec_frame0_host[rec_of_win][:, None] + u)[ok]).to(dev)
+    wt = torch.from_numpy(np.broadcast_to(np.minimum(v + 1, T3 - v).astype(np.float32), u.shape)[ok]).to(dev)
+    keep = torch.from_numpy(np.flatnonzero(ok.reshape(-1))).to(dev)
+    rec_of_frame = torch.from_numpy(np.repeat(np.arange(n_rec), np.diff(ls.rec_frame0_host))).to(dev)
+    wsum = torch.zeros(total, device=dev).index_add_(0, frame, wt)
+    state = {}
+
+    def composed_fwd():
+        ps, pa = win_strong.detach().requires_grad_(True), win_att.detach().requires_grad_(True)
+        tl = [torch.zeros(total, NCLASS, device=dev).index_add_(0, frame, wt[:, None] * x.reshape(-1, NCLASS)[keep]) / wsum[:, None]
+              for x in (ps, pa)]
+        P, A = tl[0].double(), tl[1].double()
+        num = torch.zeros(n_rec, NCLASS, dtype=torch.float64, device=dev).index_add_(0, rec_of_frame, P * A)
+        den = torch.zeros(n_rec, NCLASS, dtype=torch.float64, device=dev).index_add_(0, rec_of_frame, A)
+        state["in"], state["loss"] = (ps, pa), (g * (num / den).float()).sum()
+
+    def composed_bwd():
+        state["grads"] = torch.autograd.grad(state["loss"], state["in"], retain_graph=True)
+
+    def both(a, b):
+        def call():
+            a()
+            b()
+        return call
+    fused_fwd()
+    composed_fwd()
+    out["sed_stitch_weak_backward_alone"] = event_ms(fused_bwd, reps)
+    out["composed_backward_alone"] = event_ms(composed_bwd, reps)
+    out["fused_forward_plus_backward"] = event_ms(both(fused_fwd, fused_bwd), reps)
+    out["composed_forward_plus_backward"] = event_ms(both(composed_fwd, composed_bwd), reps)
+    assert int(err.item()) == 0
+    scale = [float(x.abs().max().item()) for x in state["grads"]]
+    out["max_abs_difference_of_the_two_routes"] = {"d_win_strong": float((d_s - state["grads"][0]).abs().max().item()),
+                                                   "d_win_att": float((d_a - state["grads"][1]).abs().max().item()),
+                                                   "largest_gradient": scale}
+    for a, b, key in (("sed_stitch_weak_backward_alone", "composed_backward_alone", "backward"),
+                      ("fused_forward_plus_backward", "composed_forward_plus_backward", "forward_plus_backward")):
+        band = max(x["spread"] * x["median_ms"] for x in (out[a], out[b]))
+        out[key + "_composed_minus_fused_ms"] = out[b]["median_ms"] - out[a]["median_ms"]
+        out[key + "_larger_max_minus_min_ms"] = band
+        out[key + "_fused_faster"] = bool(out[key + "_composed_minus_fused_ms"] > band)
+    del state, win_strong, win_att, d_s, d_a
+    # ---- (b) an epoch on recording tags against the same epoch with a window-level loss ------------------------------------------
+    if int(np.diff(ls.rec_win0_host).max()) > BATCH:
+        out["epoch"] = "not measured: a recording has more windows than one forward holds (max_windows)"
+        return out
+    tags = (np.random.default_rng(2).random((n_rec, NCLASS)) < 0.2).astype(np.float32)
+    tags_dev = torch.from_numpy(tags).to(dev)
+    opt = torch.optim.Adam(model.parameters(), lr=1e-5)
+    runs, _ = train.recording_tag_batches(np.diff(ls.rec_win0_host), BATCH, 0, 0)
+    out["batches_per_epoch"], out["max_windows"] = len(runs), BATCH
+    epoch = [0]
+
+    def pooled():
+        train.train_recording_tags(ls, tags, model, opt, epoch[0], max_windows=BATCH)
+        epoch[0] += 1
+
+    def windowed():
+        model.train()
+        loss_sum = torch.zeros((), device=dev)
+        for r0, r1 in runs:
+            w0, w1 = int(ls.rec_win0_host[r0]), int(ls.rec_win0_host[r1])
+            opt.zero_grad()
+            _, wk = model(ls.eval_batch(w0, w1 - w0))
+            target = tags_dev[r0:r1].repeat_interleave(ls.rec_win0[r0 + 1:r1 + 1] - ls.rec_win0[r0:r1], dim=0, output_size=w1 - w0)
+            loss = torch.nn.functional.binary_cross_entropy(wk, target)
+            loss.backward()
+            opt.step()
+            loss_sum += loss.detach()
+        loss_sum.item()
+    legs = {"epoch_window_level_loss": windowed, "epoch_recording_tags": pooled}
+    for fn in legs.values():
+        fn()
+    ms = {leg: [] for leg in legs}
+    for _ in range(rounds):
+        for leg, fn in legs.items():
+            ms[leg].append(wall_ms(fn))
+    for leg in legs:
+        out[leg] = stats(ms[leg])
+    a, b = out["epoch_window_level_loss"], out["epoch_recording_tags"]
+    band = max(max(x["samples_ms"]) - min(x["samples_ms"]) for x in (a, b))
+    out["pooled_loss_adds_ms"] = b["median_ms"] - a["median_ms"]
+    out["larger_max_minus_min_ms"] = band
+    out["addition_exceeds_spread"] = bool(out["pooled_loss_adds_ms"] > band)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scoring", action="store_true", help="measure the scoring of the long path's event table instead")
     ap.add_argument("--sweep", action="store_true", help="measure the K-point sweep legs alone (profiles/long_sweep.json)")
     ap.add_argument("--weak", action="store_true", help="measure the recording-level weak tags (profiles/long_weak.json)")
+    ap.add_argument("--tag-train", action="store_true",
+                    help="measure the backward through the pooled tag and an epoch on recording tags (profiles/long_tag_train.json)")
     ap.add_argument("--sweep-decode-only", action="store_true", help="with --sweep: sed_stitch_sweep alone (a variant build)")
     ap.add_argument("--sweep-out", default=os.path.join(REPO, "profiles", "long_sweep.json"))
     ap.add_argument("--candidates", default="", help="with --sweep: earlier --sweep-decode-only results to copy in")
@@ -500,7 +629,7 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(REPO, "profiles", "long_weak.json" if args.weak else
+        args.out = os.path.join(REPO, "profiles", "long_tag_train.json" if args.tag_train else "long_weak.json" if args.weak else
                                 "long_scoring.json" if args.scoring else "long_inference.json")
     if not torch.cuda.is_available():
         raise SystemExit("long_bench.py measures on the GPU: no device found (nothing is measured on a CPU)")
@@ -515,6 +644,26 @@ def main():
               "not_measured": ["from_waveforms / feature extraction", "other batch sizes, bf16 / wide models",
                                "recordings longer than 1 h", "a run with the GPU to itself (the host is shared)"],
               "workloads": {}}
+    if args.tag_train:
+        result["model"] = "baseline CRNN, fp32 kernel set; eval mode for the window tensors of (a), train mode (dropout 0.5) in (b)"
+        result["timing"] = ("the calls alone: a device-event pair around the call(s), warm, median of --decode-reps; the epochs: host "
+                            "clock around each synchronised epoch, legs alternated, --rounds rounds")
+        result["note"] = ("(a) the composed route is a torch-autograd restatement of the taper blend (index_add_ over the covered "
+                          "window frames) and the fp64 pooling, backward by autograd.grad on a kept graph - the only route to this "
+                          "gradient before sed_stitch_weak_backward; (b) both epochs run the same batches (runs of recordings within "
+                          "max_windows), forward + backward + Adam step through the autograd nodes; the window-level leg holds every "
+                          "window's own weak output to its recording's tags.  A difference counts only where it exceeds the larger "
+                          "(max - min) of the two legs")
+        result["not_measured"] += ["other nclass than 10", "other hops than the default", "per-kernel counters", "the uniform weighting",
+                                   "an epoch over the 1 h recording (more windows than one forward holds)",
+                                   "f16 models", "ema_model given"]
+        for name in args.workloads.split(","):
+            result["workloads"][name] = tag_train_workload(name, model, args.rounds, args.decode_reps)
+            print(json.dumps({name: result["workloads"][name]}), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(json.dumps(result, indent=1) + "\n")
+        return
     if args.weak:
         result["timing"] = ("get_long_predictions legs: host clock around each synchronised call, alternated; the calls alone: a "
                             "device-event pair around the call(s), warm, median of --decode-reps")
