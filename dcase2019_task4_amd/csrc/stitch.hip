@@ -13,7 +13,8 @@
 //   k_stitch_tile<VEC, 1, SWEEP>  recomputes the tile and writes its (onset, offset) frames at ev_ptr[col] + rank
 // sed_stitch_sweep decodes K operating points from ONE blend per workgroup with the same four launches and the same
 // kernels: SWEEP = true keeps the blend in LDS and loops over a group of points, a column is then (point, recording, class);
-// sed_stitch_decode is SWEEP = false, one point.  Both entries go through one host path (st_run).
+// sed_stitch_decode is SWEEP = false, one point.  Both entries go through one host path (st_run); all four entries share the
+// host front (st_front, st_ws_slots) and, on the device, StTables with st_rec / st_tile / st_blend.
 // Onsets and offsets alternate along a column, so the offsets in front of a tile are the onsets in front of it minus one
 // when an event is open across the tile's first edge: one count per (tile, class) is enough.
 // sed_stitch_weak (at the end of the file) pools recording-level weak tags over the same tiles and slots: the same blend of the
@@ -41,11 +42,18 @@ __device__ __forceinline__ float st_mul(float a, float b) { return a * b; }
 __device__ __forceinline__ float st_add(float a, float b) { return a + b; }
 __device__ __forceinline__ float st_div(float a, float b) { return a / b; }      // correctly rounded (the compiler's default for HIP)
 
-struct StArgs {
-    const float* win_strong;
+// What every entry's kernels share: the tables, the window geometry and the tile slots (st_rec, st_slot_rec, st_tile, st_blend).
+// Every entry's argument struct is this (checked and filled by st_front) plus its own fields.
+struct StTables {
     const int32_t* rec_win0;
     const int64_t* rec_frame0;
-    const float* thr;
+    int32_t* err;
+    int n_rec, T3, NC, hop3, weighting, n_slots;
+};
+
+struct StArgs {              // sed_stitch_decode, sed_stitch_sweep
+    StTables t;
+    const float *win_strong, *thr;
     const int32_t* win;
     float* timeline;
     uint8_t* binary;
@@ -54,10 +62,11 @@ struct StArgs {
     long long capacity;
     int64_t* col_total;      // ws: [K * n_rec * NC]
     int32_t* cnt;            // ws: [K][n_slots][NC] onsets per (point, tile, class); after the scan, the onsets in front of the tile
-    int32_t* err;
-    int n_rec, T3, NC, hop3, weighting, n_slots;
     int K;                   // operating points: 1 for sed_stitch_decode; thr / win are [K][NC], cnt is [K][n_slots][NC]
 };
+
+// The tile slots that tables of total_frames frames in n_rec recordings can occupy (the head of the file: where a tile lives).
+__host__ __device__ inline long long st_slot_count(long long total_frames, int n_rec) { return total_frames / ST_TILE + n_rec + 1; }
 
 struct StRec {
     long long f0;            // first timeline frame of the recording
@@ -66,7 +75,7 @@ struct StRec {
     int bad;                 // 0, or the err bits that keep the recording from being decoded
 };
 
-__device__ __forceinline__ StRec st_rec(const StArgs& a, int r) {
+__device__ __forceinline__ StRec st_rec(const StTables& a, int r) {
     StRec R;
     const long long f0 = a.rec_frame0[r], f1 = a.rec_frame0[r + 1], ft = a.rec_frame0[a.n_rec];
     const long long w0 = a.rec_win0[r], w1 = a.rec_win0[r + 1], wt = a.rec_win0[a.n_rec];
@@ -86,7 +95,7 @@ __device__ __forceinline__ StRec st_rec(const StArgs& a, int r) {
 }
 
 // The recording whose tiles may hold slot g: the last r with slot0(r) <= g (workgroup-uniform; the caller validates it).
-__device__ __forceinline__ int st_slot_rec(const StArgs& a, long long g) {
+__device__ __forceinline__ int st_slot_rec(const StTables& a, long long g) {
     int lo_r = 0, hi_r = a.n_rec - 1;
     while (lo_r < hi_r) {
         const int mid = (lo_r + hi_r + 1) >> 1;
@@ -96,13 +105,31 @@ __device__ __forceinline__ int st_slot_rec(const StArgs& a, long long g) {
     return lo_r;
 }
 
+// Slot g is a tile of recording r, the frames [s, e) of its timeline (s = 0: its first) - or nothing to do (false): an empty slot,
+// or a recording the tables do not describe or cover (the entry's column / clear kernel reports that one).  Workgroup-uniform.
+struct StTile { StRec R; int r, s, e; };
+__device__ __forceinline__ bool st_tile(const StTables& a, long long g, StTile& T) {
+    T.r = st_slot_rec(a, g);
+    T.R = st_rec(a, T.r);
+    const long long kt = g - T.R.slot0;
+    if (T.R.bad || kt < 0 || kt >= T.R.tiles) return false;
+    T.s = (int)kt * ST_TILE;
+    T.e = min(T.s + ST_TILE, T.R.L3);
+    return true;
+}
+
+// The windows st_cover_lo .. st_cover_hi cover timeline frame u of recording R: the j with 0 <= u - j hop3 < T3 that it owns;
+// window j holds the frame at v = u - j hop3 with the integer weight st_weight(v).  For the blend and for its transpose.
+__device__ __forceinline__ int st_cover_lo(const StTables& a, int u) { return u >= a.T3 ? (u - a.T3) / a.hop3 + 1 : 0; }
+__device__ __forceinline__ int st_cover_hi(const StTables& a, const StRec& R, int u) { return min(u / a.hop3, R.nw - 1); }
+__device__ __forceinline__ int st_weight(const StTables& a, int v) { return a.weighting ? min(v + 1, a.T3 - v) : 1; }
+
 // Blended value(s) of timeline frame u of recording R from the window tensor `win` [n_win][T3][NC] (the posteriors, or the
 // attention of sed_stitch_weak): class q (VEC = false) or classes 4q .. 4q + 3 (VEC = true).
 template <bool VEC>
-__device__ __forceinline__ f32x4 st_blend(const StArgs& a, const float* win, const StRec& R, int u, int q) {
+__device__ __forceinline__ f32x4 st_blend(const StTables& a, const float* win, const StRec& R, int u, int q) {
     const int T3 = a.T3, hop3 = a.hop3, NC = a.NC;
-    const int j_lo = u >= T3 ? (u - T3) / hop3 + 1 : 0;                          // the windows j with 0 <= u - j hop3 < T3 ...
-    const int j_hi = min(u / hop3, R.nw - 1);                                    // ... that the recording owns
+    const int j_lo = st_cover_lo(a, u), j_hi = st_cover_hi(a, R, u);
     const int col = VEC ? 4 * q : q;
     const float* src = win + ((size_t)(R.w0 + j_lo) * T3 + (u - j_lo * hop3)) * NC + col;
     f32x4 p = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -115,7 +142,7 @@ __device__ __forceinline__ f32x4 st_blend(const StArgs& a, const float* win, con
     int wsum = 0;
     for (int j = j_lo; j <= j_hi; ++j, src += step) {
         const int v = u - j * hop3;
-        const int wi = a.weighting ? min(v + 1, T3 - v) : 1;
+        const int wi = st_weight(a, v);
         const float w = (float)wi;
         wsum += wi;
         if (VEC) {
@@ -154,15 +181,12 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_tile(StArgs a) {
     __shared__ uint8_t flt[ST_MAXC * ST_FLT];
     __shared__ float s_thr[ST_MAXC];
     __shared__ int s_win[ST_MAXC];       // 0: outside 1 .. 63, the column is not decoded
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NC = a.NC;
-    // ---- which recording, which tile (workgroup-uniform) -----------------------------------------------------------------
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, NC = a.t.NC;
     const long long g = blockIdx.x;
-    const int r = st_slot_rec(a, g);
-    const StRec R = st_rec(a, r);
-    if (R.bad) return;                                                           // (k_stitch_scan_cols reports it)
-    const long long kt = g - R.slot0;
-    if (kt < 0 || kt >= R.tiles) return;                                         // an empty slot
-    const int L3 = R.L3, s = (int)kt * ST_TILE, e = min(s + ST_TILE, L3);
+    StTile T;
+    if (!st_tile(a.t, g, T)) return;
+    const StRec& R = T.R;
+    const int r = T.r, L3 = R.L3, s = T.s, e = T.e;
     const int ext_lo = max(s - ST_HALO, 0), ext_n = min(e + ST_HALO, L3) - ext_lo;
     const int k_lo = SWEEP ? blockIdx.y * ST_SWEEP_GROUP : 0, k_hi = SWEEP ? min(k_lo + ST_SWEEP_GROUP, a.K) : 1;
     auto load_point = [&](int kp) {                                              // threshold and window of point kp, per class
@@ -170,7 +194,7 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_tile(StArgs a) {
             const int w = a.win[kp * NC + tid];
             s_thr[tid] = a.thr[kp * NC + tid];
             s_win[tid] = (w >= 1 && w <= 63) ? w : 0;
-            if (PASS == 0 && kt == 0 && !(w >= 1 && w <= 63)) atomicOr(a.err, 8);
+            if (PASS == 0 && s == 0 && !(w >= 1 && w <= 63)) atomicOr(a.t.err, 8);
         }
         __syncthreads();
     };
@@ -185,7 +209,7 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_tile(StArgs a) {
         };
         for (int it = tid; it < ext_n * G; it += ST_THREADS) {
             const int fl = it / G, q = it - fl * G, u = ext_lo + fl;
-            const f32x4 p = st_blend<VEC>(a, a.win_strong, R, u, q);
+            const f32x4 p = st_blend<VEC>(a.t, a.win_strong, R, u, q);
             if (VEC) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) keep(4 * q + k, fl, p[k]);
@@ -229,10 +253,10 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_tile(StArgs a) {
             }
         }
         // ---- onsets / offsets of the tile: one wave per class, 64 frames per ballot -----------------------------------------
-        const size_t slot = ((size_t)kp * a.n_slots + (size_t)g) * NC;
+        const size_t slot = ((size_t)kp * a.t.n_slots + (size_t)g) * NC;
         for (int c = wave; c < NC; c += ST_THREADS / 64) {
             const uint8_t* f = flt + c * ST_FLT + 1;                             // f[t - s], t = s - 1 .. e
-            const long long col = ((long long)kp * a.n_rec + r) * NC + c;
+            const long long col = ((long long)kp * a.t.n_rec + r) * NC + c;
             int n_on = 0, n_off = 0;
             long long base = 0;
             if (PASS == 1) {
@@ -262,22 +286,22 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_tile(StArgs a) {
 // One wave per column (point, recording, class): the tile counts become the onsets in front of each tile; the total goes to
 // col_total.
 __global__ __launch_bounds__(ST_THREADS) void k_stitch_scan_cols(StArgs a) {
-    const int lane = threadIdx.x & 63;
+    const int lane = threadIdx.x & 63, NC = a.t.NC;
     const long long col = (long long)blockIdx.x * (ST_THREADS / 64) + (threadIdx.x >> 6);
-    const long long per_point = (long long)a.n_rec * a.NC;
+    const long long per_point = (long long)a.t.n_rec * NC;
     if (col >= per_point * a.K) return;
     const int kp = (int)(col / per_point);
     const long long rc = col - kp * per_point;
-    const int r = (int)(rc / a.NC), c = (int)(rc - (long long)r * a.NC);
-    const StRec R = st_rec(a, r);
-    const int w = a.win[kp * a.NC + c];
-    if (R.bad && c == 0 && lane == 0) atomicOr(a.err, R.bad);
+    const int r = (int)(rc / NC), c = (int)(rc - (long long)r * NC);
+    const StRec R = st_rec(a.t, r);
+    const int w = a.win[kp * NC + c];
+    if (R.bad && c == 0 && lane == 0) atomicOr(a.t.err, R.bad);
     long long carry = 0;
     if (!R.bad && w >= 1 && w <= 63) {
-        int32_t* cnt = a.cnt + (size_t)kp * a.n_slots * a.NC;
+        int32_t* cnt = a.cnt + (size_t)kp * a.t.n_slots * NC;
         for (int k0 = 0; k0 < R.tiles; k0 += 64) {
             const int k = k0 + lane;
-            int32_t* p = cnt + ((size_t)R.slot0 + k) * a.NC + c;
+            int32_t* p = cnt + ((size_t)R.slot0 + k) * NC + c;
             const int v = k < R.tiles ? *p : 0;
             int incl = v;
 #pragma unroll
@@ -297,7 +321,7 @@ __global__ __launch_bounds__(1024) void k_stitch_scan_ptr(StArgs a) {
     __shared__ long long part[16];
     __shared__ long long s_carry;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long n = (long long)a.n_rec * a.NC * a.K;
+    const long long n = (long long)a.t.n_rec * a.t.NC * a.K;
     if (tid == 0) { s_carry = 0; a.ev_ptr[0] = 0; }
     __syncthreads();
     for (long long i0 = 0; i0 < n; i0 += 1024) {
@@ -318,7 +342,7 @@ __global__ __launch_bounds__(1024) void k_stitch_scan_ptr(StArgs a) {
         if (tid == 1023) s_carry = before + incl;
         __syncthreads();
     }
-    if (tid == 0 && s_carry > a.capacity) atomicOr(a.err, 2);
+    if (tid == 0 && s_carry > a.capacity) atomicOr(a.t.err, 2);
 }
 
 extern "C" int sed_stitch_tile_frames(void) { return ST_TILE; }
@@ -327,27 +351,26 @@ extern "C" int sed_stitch_tile_frames(void) { return ST_TILE; }
 static size_t st_ws_head(int n_rec, int NC, int K) { return (size_t)K * n_rec * NC * sizeof(int64_t); }
 static size_t st_ws_per_slot(int NC, int K) { return (size_t)K * NC * sizeof(int32_t); }
 
-// Bytes for tables of total_frames frames, or 0 where the sizes are out of range (the sweep's ranges are the narrower ones).
-static size_t st_ws_size(long long total_frames, int n_rec, int NC, int K, bool sweep) {
+// Slots for tables of total_frames frames, or 0 where the sizes are out of range (the sweep's ranges are the narrower ones).
+static size_t st_ws_slot_count(long long total_frames, int n_rec, int NC, int K, bool sweep) {
     if (total_frames < 1 || n_rec < 1 || NC < 1 || NC > ST_MAXC || K < 1 || K > ST_SWEEP_MAXK || total_frames * NC >= (1ll << 31) ||
         (long long)K * n_rec * NC >= (1ll << (sweep ? 26 : 31))) return 0;
-    const long long n_slots = total_frames / ST_TILE + n_rec + 1;
-    if (sweep && n_slots * K >= (1ll << 31)) return 0;
-    return st_ws_head(n_rec, NC, K) + (size_t)n_slots * st_ws_per_slot(NC, K);
+    const long long n_slots = st_slot_count(total_frames, n_rec);
+    return sweep && n_slots * K >= (1ll << 31) ? 0 : (size_t)n_slots;
 }
 
 extern "C" size_t sed_stitch_decode_ws_bytes(long long total_frames, int n_rec, int nclass) {
-    const size_t n = st_ws_size(total_frames, n_rec, nclass, 1, false);
+    const size_t n = st_ws_slot_count(total_frames, n_rec, nclass, 1, false);
     if (!n) sed_set_error("sed_stitch_decode_ws_bytes: need total_frames >= 1, n_rec >= 1, 1 <= nclass <= 16, "
                           "total_frames * nclass < 2^31");
-    return n;
+    return n ? st_ws_head(n_rec, nclass, 1) + n * st_ws_per_slot(nclass, 1) : 0;
 }
 
 extern "C" size_t sed_stitch_sweep_ws_bytes(long long total_frames, int n_rec, int nclass, int n_points) {
-    const size_t n = st_ws_size(total_frames, n_rec, nclass, n_points, true);
+    const size_t n = st_ws_slot_count(total_frames, n_rec, nclass, n_points, true);
     if (!n) sed_set_error("sed_stitch_sweep_ws_bytes: need total_frames >= 1, n_rec >= 1, 1 <= nclass <= 16, 1 <= n_points <= %d, "
                           "total_frames * nclass < 2^31, n_points * n_rec * nclass < 2^26, n_points * slots < 2^31", ST_SWEEP_MAXK);
-    return n;
+    return n ? st_ws_head(n_rec, nclass, n_points) + n * st_ws_per_slot(nclass, n_points) : 0;
 }
 
 extern "C" int sed_stitch_sweep_point_group(void) { return ST_SWEEP_GROUP; }
@@ -369,45 +392,58 @@ static void st_launch_tile(bool vec, bool sweep, dim3 grid, hipStream_t st, cons
         }                                           \
     } while (0)
 
-// Both entries: `what` names the caller in every message; sweep = false is n_points = 1 with sed_stitch_decode's looser
-// workspace rule (any size that holds the tables; the slot count is derived from it) and its binary output.
+// The host front of all four entries (`what` names the entry in every message): the geometry checks - n_points * n_rec * NC
+// columns, n_points = 1 but for the sweep, stay below 2^col_bits - and the tables struct, still without its slot count.
+static int st_front(const char* what, const int32_t* rec_win0, const int64_t* rec_frame0, int32_t* err, int n_rec, int T3, int NC,
+                    int hop3, int weighting, int n_points, int col_bits, StTables* t) {
+    ST_NEED(n_rec >= 1 && NC >= 1 && NC <= ST_MAXC && (long long)n_points * n_rec * NC < (1ll << col_bits),
+            col_bits == 26 ? "need n_rec >= 1, 1 <= NC <= 16 and n_points * n_rec * NC < 2^26"
+                           : "need n_rec >= 1, 1 <= NC <= 16 and n_rec * NC < 2^31");
+    ST_NEED(T3 >= 1 && T3 <= 4096, "need 1 <= T3 <= 4096 (the taper's weight sum stays exact in fp32)");
+    ST_NEED(hop3 >= 1 && hop3 <= T3, "need 1 <= hop3 <= T3");
+    ST_NEED(weighting == 0 || weighting == 1, "weighting is 0 (uniform) or 1 (taper)");
+    *t = StTables{rec_win0, rec_frame0, err, n_rec, T3, NC, hop3, weighting, 0};
+    return SED_OK;
+}
+
+// t->n_slots from the workspace's size: `bytes` of it hold the slots of K points, per_slot each.  whole: only a size the entry's
+// _ws_bytes function returns describes whole slots for the tables (the sweep's layout, sed_stitch_weak); sed_stitch_decode
+// takes any size that holds the tables.  The slots bound the tile grid and the frames the tables may hold.
+static int st_ws_slots(const char* what, size_t bytes, size_t per_slot, bool whole, int K, StTables* t) {
+    const size_t n_slots = bytes / per_slot;
+    if (whole && (bytes % per_slot != 0 || n_slots < (size_t)st_slot_count(1, t->n_rec))) {
+        sed_set_error("%s: ws_bytes must be the value %s_ws_bytes returned for these tables", what, what);
+        return SED_ERR_BAD_ARG;
+    }
+    ST_NEED(n_slots * K < (1ull << 31), "workspace too large for the tile grid (slots, times n_points in a sweep, < 2^31)");
+    ST_NEED((long long)(n_slots - t->n_rec - 1) * ST_TILE * t->NC < (1ll << 31) + (long long)ST_TILE * t->NC,
+            "sum L3 * NC must stay below 2^31");
+    t->n_slots = (int)n_slots;
+    return SED_OK;
+}
+
+// sed_stitch_decode and sed_stitch_sweep: sweep = false is n_points = 1 with the looser workspace rule and the binary output.
 static int st_run(const char* what, bool sweep, const float* win_strong, const int32_t* rec_win0, const int64_t* rec_frame0,
                   int n_rec, int T3, int NC, int hop3, int weighting, int n_points, const float* thr, const int32_t* win,
                   float* timeline, uint8_t* binary, int64_t* ev_ptr, int32_t* ev_pairs, long long capacity, void* ws,
                   size_t ws_bytes, int32_t* err, void* stream) {
     ST_NEED(win_strong && rec_win0 && rec_frame0 && thr && win && ev_ptr && ev_pairs && ws && err, "null argument");
     ST_NEED(n_points >= 1 && n_points <= ST_SWEEP_MAXK, "need 1 <= n_points <= 4096");
-    ST_NEED(n_rec >= 1 && NC >= 1 && NC <= ST_MAXC && (long long)n_points * n_rec * NC < (1ll << (sweep ? 26 : 31)),
-            sweep ? "need n_rec >= 1, 1 <= NC <= 16 and n_points * n_rec * NC < 2^26"
-                  : "need n_rec >= 1, 1 <= NC <= 16 and n_rec * NC < 2^31");
-    ST_NEED(T3 >= 1 && T3 <= 4096, "need 1 <= T3 <= 4096 (the taper's weight sum stays exact in fp32)");
-    ST_NEED(hop3 >= 1 && hop3 <= T3, "need 1 <= hop3 <= T3");
-    ST_NEED(weighting == 0 || weighting == 1, "weighting is 0 (uniform) or 1 (taper)");
+    StTables t;
+    SED_TRY(st_front(what, rec_win0, rec_frame0, err, n_rec, T3, NC, hop3, weighting, n_points, sweep ? 26 : 31, &t));
     ST_NEED(capacity >= 0, "capacity must be >= 0");
     ST_NEED(((uintptr_t)ws % 8) == 0, "ws must be 8-byte aligned");
     const size_t head = st_ws_head(n_rec, NC, n_points), per_slot = st_ws_per_slot(NC, n_points);
-    if (ws_bytes < head + (size_t)(n_rec + 1) * per_slot) {
+    if (ws_bytes < head + (size_t)st_slot_count(1, n_rec) * per_slot) {                  // the fewest slots any tables take
         sed_set_error("%s: workspace of %zu bytes is too small (%s_ws_bytes)", what, ws_bytes, what);
         return SED_ERR_WORKSPACE;
     }
-    // the slot count is derived from the size: with K > 1 only a size sed_stitch_sweep_ws_bytes returns describes whole slots
-    ST_NEED(!sweep || (ws_bytes - head) % per_slot == 0,
-            "ws_bytes must be the value sed_stitch_sweep_ws_bytes returned for these tables");
-    const size_t n_slots = (ws_bytes - head) / per_slot;
-    ST_NEED(n_slots * n_points < (1ull << 31), "workspace too large for the tile grid (n_points * slots < 2^31)");
-    // the slots bound the frames the tables may hold: sum L3 * NC < 2^31
-    ST_NEED((long long)(n_slots - n_rec - 1) * ST_TILE * NC < (1ll << 31) + (long long)ST_TILE * NC,
-            "sum L3 * NC must stay below 2^31");
-    StArgs a = {};
-    a.win_strong = win_strong; a.rec_win0 = rec_win0; a.rec_frame0 = rec_frame0; a.thr = thr; a.win = win;
-    a.timeline = timeline; a.binary = binary; a.ev_ptr = ev_ptr; a.ev_pairs = ev_pairs; a.capacity = capacity;
-    a.col_total = (int64_t*)ws;
-    a.cnt = (int32_t*)((char*)ws + head);
-    a.err = err;
-    a.n_rec = n_rec; a.T3 = T3; a.NC = NC; a.hop3 = hop3; a.weighting = weighting; a.n_slots = (int)n_slots; a.K = n_points;
+    SED_TRY(st_ws_slots(what, ws_bytes - head, per_slot, sweep, n_points, &t));
+    const StArgs a = {t, win_strong, thr, win, timeline, binary, ev_ptr, ev_pairs, capacity, (int64_t*)ws,
+                      (int32_t*)((char*)ws + head), n_points};
     const bool vec = NC % 4 == 0 && ((uintptr_t)win_strong % 16) == 0 && (!timeline || ((uintptr_t)timeline % 16) == 0);
     hipStream_t st = (hipStream_t)stream;
-    const dim3 tiles((unsigned)n_slots, sweep ? (unsigned)((n_points + ST_SWEEP_GROUP - 1) / ST_SWEEP_GROUP) : 1u);
+    const dim3 tiles((unsigned)t.n_slots, sweep ? (unsigned)((n_points + ST_SWEEP_GROUP - 1) / ST_SWEEP_GROUP) : 1u);
     st_launch_tile<0>(vec, sweep, tiles, st, a);
     SED_CHECK_LAUNCH();
     const long long n_cols = (long long)n_points * n_rec * NC;
@@ -448,8 +484,8 @@ extern "C" int sed_stitch_sweep(const float* win_strong, const int32_t* rec_win0
 //   thread (c, i) adds the rows i, i + 16, ... of class c, thread c the sixteen of those: the tile's pair;
 //   lane l of a column's wave adds the tiles l, l + 64, ..., then an xor butterfly (both partners form the same sum).
 struct StWeakArgs {
-    StArgs t;                // win_strong, the tables, T3 / NC / hop3 / weighting, n_slots, err (st_rec, st_blend)
-    const float* win_att;
+    StTables t;
+    const float *win_strong, *win_att;
     double* part;            // ws: [n_slots][NC][2] (num, den) of a tile
     float* weak;             // [n_rec][NC]
     double* sums;            // [n_rec][NC][2] or null
@@ -460,30 +496,25 @@ template <bool VEC, int W>
 __global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_tile(StWeakArgs wa) {
     __shared__ double red[ST_THREADS * W * 2];                                   // [rows][NC][2], rows * NC <= ST_THREADS * W
     __shared__ double fold[ST_MAXC * SW_FOLD * 2];
-    const StArgs& a = wa.t;
+    const StTables& a = wa.t;
     const int tid = threadIdx.x, NC = a.NC;
-    const long long g = blockIdx.x;
-    const int r = st_slot_rec(a, g);
-    const StRec R = st_rec(a, r);
-    if (R.bad) return;                                                           // (k_stitch_weak_cols reports it)
-    const long long kt = g - R.slot0;
-    if (kt < 0 || kt >= R.tiles) return;                                         // an empty slot
-    const int s = (int)kt * ST_TILE, e = min(s + ST_TILE, R.L3);
+    StTile T;
+    if (!st_tile(a, blockIdx.x, T)) return;
     const int G = NC / W, rows = ST_THREADS / G, row = tid / G, q = tid - row * G;
     if (row < rows) {
         double num[W], den[W];
 #pragma unroll
         for (int k = 0; k < W; ++k) { num[k] = 0.0; den[k] = 0.0; }
-        for (int u = s + row; u < e; u += rows) {
+        for (int u = T.s + row; u < T.e; u += rows) {
             f32x4 p, at;
             if (VEC) {
-                p = st_blend<true>(a, a.win_strong, R, u, q);
-                at = st_blend<true>(a, wa.win_att, R, u, q);
+                p = st_blend<true>(a, wa.win_strong, T.R, u, q);
+                at = st_blend<true>(a, wa.win_att, T.R, u, q);
             } else {
 #pragma unroll
                 for (int k = 0; k < W; ++k) {
-                    p[k] = st_blend<false>(a, a.win_strong, R, u, W * q + k)[0];
-                    at[k] = st_blend<false>(a, wa.win_att, R, u, W * q + k)[0];
+                    p[k] = st_blend<false>(a, wa.win_strong, T.R, u, W * q + k)[0];
+                    at[k] = st_blend<false>(a, wa.win_att, T.R, u, W * q + k)[0];
                 }
             }
 #pragma unroll
@@ -512,7 +543,7 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_tile(StWeakArgs wa) 
     if (tid < NC) {
         double n = 0.0, d = 0.0;
         for (int i = 0; i < SW_FOLD; ++i) { n += fold[(tid * SW_FOLD + i) * 2]; d += fold[(tid * SW_FOLD + i) * 2 + 1]; }
-        double* out = wa.part + ((size_t)g * NC + tid) * 2;
+        double* out = wa.part + ((size_t)blockIdx.x * NC + tid) * 2;
         out[0] = n;
         out[1] = d;
     }
@@ -522,7 +553,7 @@ static_assert(ST_THREADS == ST_MAXC * SW_FOLD, "k_stitch_weak_tile folds the row
 // One wave per column (recording, class): the tile pairs in the fixed order above; a recording the tables do not describe or
 // cover raises its err bits and has NaN rows.
 __global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_cols(StWeakArgs wa) {
-    const StArgs& a = wa.t;
+    const StTables& a = wa.t;
     const int lane = threadIdx.x & 63;
     const long long col = (long long)blockIdx.x * (ST_THREADS / 64) + (threadIdx.x >> 6);
     if (col >= (long long)a.n_rec * a.NC) return;
@@ -553,13 +584,10 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_cols(StWeakArgs wa) 
 static size_t sw_ws_per_slot(int NC) { return (size_t)NC * 2 * sizeof(double); }
 
 extern "C" size_t sed_stitch_weak_ws_bytes(long long total_frames, int n_rec, int nclass) {
-    if (total_frames < 1 || n_rec < 1 || nclass < 1 || nclass > ST_MAXC || total_frames * nclass >= (1ll << 31) ||
-        (long long)n_rec * nclass >= (1ll << 31)) {
-        sed_set_error("sed_stitch_weak_ws_bytes: need total_frames >= 1, n_rec >= 1, 1 <= nclass <= 16, "
-                      "total_frames * nclass < 2^31, n_rec * nclass < 2^31");
-        return 0;
-    }
-    return (size_t)(total_frames / ST_TILE + n_rec + 1) * sw_ws_per_slot(nclass);
+    const size_t n = st_ws_slot_count(total_frames, n_rec, nclass, 1, false);
+    if (!n) sed_set_error("sed_stitch_weak_ws_bytes: need total_frames >= 1, n_rec >= 1, 1 <= nclass <= 16, "
+                          "total_frames * nclass < 2^31, n_rec * nclass < 2^31");
+    return n * sw_ws_per_slot(nclass);
 }
 
 extern "C" int sed_stitch_weak(const float* win_strong, const float* win_att, const int32_t* rec_win0, const int64_t* rec_frame0,
@@ -567,28 +595,14 @@ extern "C" int sed_stitch_weak(const float* win_strong, const float* win_att, co
                                size_t ws_bytes, int32_t* err, void* stream) {
     const char* what = "sed_stitch_weak";
     ST_NEED(win_strong && win_att && rec_win0 && rec_frame0 && weak && ws && err, "null argument");
-    ST_NEED(n_rec >= 1 && NC >= 1 && NC <= ST_MAXC && (long long)n_rec * NC < (1ll << 31),
-            "need n_rec >= 1, 1 <= NC <= 16 and n_rec * NC < 2^31");
-    ST_NEED(T3 >= 1 && T3 <= 4096, "need 1 <= T3 <= 4096 (the taper's weight sum stays exact in fp32)");
-    ST_NEED(hop3 >= 1 && hop3 <= T3, "need 1 <= hop3 <= T3");
-    ST_NEED(weighting == 0 || weighting == 1, "weighting is 0 (uniform) or 1 (taper)");
+    StTables t;
+    SED_TRY(st_front(what, rec_win0, rec_frame0, err, n_rec, T3, NC, hop3, weighting, 1, 31, &t));
     ST_NEED(((uintptr_t)ws % 8) == 0, "ws must be 8-byte aligned");
-    // the slot count is derived from the size: only a size sed_stitch_weak_ws_bytes returns describes whole slots for the tables
-    const size_t per_slot = sw_ws_per_slot(NC);
-    ST_NEED(ws_bytes % per_slot == 0 && ws_bytes / per_slot >= (size_t)n_rec + 1,
-            "ws_bytes must be the value sed_stitch_weak_ws_bytes returned for these tables");
-    const size_t n_slots = ws_bytes / per_slot;
-    ST_NEED(n_slots < (1ull << 31), "workspace too large for the tile grid (slots < 2^31)");
-    ST_NEED((long long)(n_slots - n_rec - 1) * ST_TILE * NC < (1ll << 31) + (long long)ST_TILE * NC,
-            "sum L3 * NC must stay below 2^31");
-    StWeakArgs wa = {};
-    wa.t.win_strong = win_strong; wa.t.rec_win0 = rec_win0; wa.t.rec_frame0 = rec_frame0; wa.t.err = err;
-    wa.t.n_rec = n_rec; wa.t.T3 = T3; wa.t.NC = NC; wa.t.hop3 = hop3; wa.t.weighting = weighting; wa.t.n_slots = (int)n_slots;
-    wa.t.K = 1;
-    wa.win_att = win_att; wa.part = (double*)ws; wa.weak = weak; wa.sums = sums;
+    SED_TRY(st_ws_slots(what, ws_bytes, sw_ws_per_slot(NC), true, 1, &t));
+    const StWeakArgs wa = {t, win_strong, win_att, (double*)ws, weak, sums};
     const bool vec = NC % 4 == 0 && ((uintptr_t)win_strong % 16) == 0 && ((uintptr_t)win_att % 16) == 0;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 tiles((unsigned)n_slots), thr256(ST_THREADS);
+    const dim3 tiles((unsigned)t.n_slots), thr256(ST_THREADS);
     if (vec) hipLaunchKernelGGL((k_stitch_weak_tile<true, 4>), tiles, thr256, 0, st, wa);
     else if (NC % 4 == 0) hipLaunchKernelGGL((k_stitch_weak_tile<false, 4>), tiles, thr256, 0, st, wa);
     else hipLaunchKernelGGL((k_stitch_weak_tile<false, 1>), tiles, thr256, 0, st, wa);
@@ -610,29 +624,28 @@ extern "C" int sed_stitch_weak(const float* win_strong, const float* win_att, co
 // windows of a rejected recording - is +0.0f from k_stitch_weak_bwd_zero, which runs first on the same stream and clears both
 // outputs over [0, rec_win0[n_rec]) (the window count lives on the device; a host-side memset would need it).
 // The call has no workspace to derive the slot count from, and the tables are device data: both kernels take it from
-// rec_frame0[n_rec] (sb_slots: the smallest count that st_rec accepts every well-formed table with) and walk the slots with a
-// grid-stride loop over a fixed grid.
+// rec_frame0[n_rec] (sb_tables: st_slot_count of it, the smallest count that st_rec accepts every well-formed table with) and
+// walk the slots with a grid-stride loop over a fixed grid.
 struct StWeakBwdArgs {
-    StArgs t;                // win_strong, the tables, T3 / NC / hop3 / weighting, err; n_slots is filled in on the device
-    const float* win_att;
+    StTables t;              // n_slots is filled in on the device (sb_tables)
+    const float *win_strong, *win_att;
     const double* sums;      // [n_rec][NC][2] (num, den) of the forward
     const float* g_weak;     // [n_rec][NC]
-    float* d_win_strong;     // [n_win][T3][NC]
-    float* d_win_att;
+    float *d_win_strong, *d_win_att;      // [n_win][T3][NC]
 };
 #define SB_GRID 512
 
-// Tile slots for the tables' own total, or 0 (st_rec then rejects every recording) when it is outside the forward's limits.
-__device__ __forceinline__ int sb_slots(const StArgs& a) {
+// The tables with the tile slots of their own total, or 0 slots (st_rec then rejects every recording) when that total is outside
+// the forward's limits.
+__device__ __forceinline__ StTables sb_tables(StTables a) {
     const long long ft = a.rec_frame0[a.n_rec];
-    if (ft < 1 || ft >= (1ll << 31) || ft * a.NC >= (1ll << 31)) return 0;
-    return (int)(ft / ST_TILE + a.n_rec + 1);
+    a.n_slots = (ft < 1 || ft >= (1ll << 31) || ft * a.NC >= (1ll << 31)) ? 0 : (int)st_slot_count(ft, a.n_rec);
+    return a;
 }
 
 template <bool VEC>
 __global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_bwd_zero(StWeakBwdArgs wa) {
-    StArgs a = wa.t;
-    a.n_slots = sb_slots(a);
+    const StTables a = sb_tables(wa.t);
     const size_t i0 = (size_t)blockIdx.x * ST_THREADS + threadIdx.x, stride = (size_t)gridDim.x * ST_THREADS;
     for (size_t r = i0; r < (size_t)a.n_rec; r += stride) {
         const StRec R = st_rec(a, (int)r);
@@ -657,43 +670,34 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_bwd_zero(StWeakBwdAr
 
 template <bool VEC>
 __global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_bwd_tile(StWeakBwdArgs wa) {
-    StArgs a = wa.t;
-    a.n_slots = sb_slots(a);
+    const StTables a = sb_tables(wa.t);
     const int tid = threadIdx.x, NC = a.NC, T3 = a.T3, hop3 = a.hop3;
     constexpr int W = VEC ? 4 : 1;
     const int G = VEC ? NC >> 2 : NC;
     for (long long g = blockIdx.x; g < a.n_slots; g += gridDim.x) {
-        const int r = st_slot_rec(a, g);
-        const StRec R = st_rec(a, r);
-        if (R.bad) continue;                                                     // (k_stitch_weak_bwd_zero reports it)
-        const long long kt = g - R.slot0;
-        if (kt < 0 || kt >= R.tiles) continue;                                   // an empty slot
-        const int s = (int)kt * ST_TILE, e = min(s + ST_TILE, R.L3);
-        for (int it = tid; it < (e - s) * G; it += ST_THREADS) {
-            const int fl = it / G, q = it - fl * G, u = s + fl, col = W * q;
-            const f32x4 p = st_blend<VEC>(a, a.win_strong, R, u, q);
-            const f32x4 at = st_blend<VEC>(a, wa.win_att, R, u, q);
+        StTile T;
+        if (!st_tile(a, g, T)) continue;
+        for (int it = tid; it < (T.e - T.s) * G; it += ST_THREADS) {
+            const int fl = it / G, q = it - fl * G, u = T.s + fl, col = W * q;
+            const f32x4 p = st_blend<VEC>(a, wa.win_strong, T.R, u, q);
+            const f32x4 at = st_blend<VEC>(a, wa.win_att, T.R, u, q);
             double dP[W], dA[W];
 #pragma unroll
             for (int k = 0; k < W; ++k) {
-                const size_t rc = (size_t)r * NC + col + k;
+                const size_t rc = (size_t)T.r * NC + col + k;
                 const double gk = (double)wa.g_weak[rc], num = wa.sums[2 * rc], den = wa.sums[2 * rc + 1];
                 const double t = num / den;
                 dP[k] = (gk * (double)at[k]) / den;
                 dA[k] = (gk * ((double)p[k] - t)) / den;
             }
-            const int j_lo = u >= T3 ? (u - T3) / hop3 + 1 : 0;                  // the covering windows, as st_blend takes them
-            const int j_hi = min(u / hop3, R.nw - 1);
+            const int j_lo = st_cover_lo(a, u), j_hi = st_cover_hi(a, T.R, u);
             int wsum = 0;
-            for (int j = j_lo; j <= j_hi; ++j) {
-                const int v = u - j * hop3;
-                wsum += a.weighting ? min(v + 1, T3 - v) : 1;
-            }
+            for (int j = j_lo; j <= j_hi; ++j) wsum += st_weight(a, u - j * hop3);
             const double Ws = (double)wsum;
             for (int j = j_lo; j <= j_hi; ++j) {
                 const int v = u - j * hop3;
-                const double w = (double)(a.weighting ? min(v + 1, T3 - v) : 1);
-                const size_t o = ((size_t)(R.w0 + j) * T3 + v) * NC + col;
+                const double w = (double)st_weight(a, v);
+                const size_t o = ((size_t)(T.R.w0 + j) * T3 + v) * NC + col;
                 f32x4 ds, da;
 #pragma unroll
                 for (int k = 0; k < W; ++k) {
@@ -718,16 +722,10 @@ extern "C" int sed_stitch_weak_backward(const float* win_strong, const float* wi
                                         int32_t* err, void* stream) {
     const char* what = "sed_stitch_weak_backward";
     ST_NEED(win_strong && win_att && rec_win0 && rec_frame0 && sums && g_weak && d_win_strong && d_win_att && err, "null argument");
-    ST_NEED(n_rec >= 1 && NC >= 1 && NC <= ST_MAXC && (long long)n_rec * NC < (1ll << 31),
-            "need n_rec >= 1, 1 <= NC <= 16 and n_rec * NC < 2^31");
-    ST_NEED(T3 >= 1 && T3 <= 4096, "need 1 <= T3 <= 4096 (the taper's weight sum stays exact in fp32)");
-    ST_NEED(hop3 >= 1 && hop3 <= T3, "need 1 <= hop3 <= T3");
-    ST_NEED(weighting == 0 || weighting == 1, "weighting is 0 (uniform) or 1 (taper)");
+    StTables t;
+    SED_TRY(st_front(what, rec_win0, rec_frame0, err, n_rec, T3, NC, hop3, weighting, 1, 31, &t));
     ST_NEED(((uintptr_t)sums % 8) == 0, "sums must be 8-byte aligned");
-    StWeakBwdArgs wa = {};
-    wa.t.win_strong = win_strong; wa.t.rec_win0 = rec_win0; wa.t.rec_frame0 = rec_frame0; wa.t.err = err;
-    wa.t.n_rec = n_rec; wa.t.T3 = T3; wa.t.NC = NC; wa.t.hop3 = hop3; wa.t.weighting = weighting; wa.t.K = 1;
-    wa.win_att = win_att; wa.sums = sums; wa.g_weak = g_weak; wa.d_win_strong = d_win_strong; wa.d_win_att = d_win_att;
+    const StWeakBwdArgs wa = {t, win_strong, win_att, sums, g_weak, d_win_strong, d_win_att};
     const bool vec = NC % 4 == 0 && ((uintptr_t)win_strong % 16) == 0 && ((uintptr_t)win_att % 16) == 0 &&
                      ((uintptr_t)d_win_strong % 16) == 0 && ((uintptr_t)d_win_att % 16) == 0;
     hipStream_t st = (hipStream_t)stream;

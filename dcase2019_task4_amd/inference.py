@@ -148,6 +148,17 @@ STITCH_ERR_BITS = {2: "more events than the capacity of ev_pairs", 8: "a median 
                    16: "malformed rec_win0 / rec_frame0 tables", 32: "a recording with too few windows to cover it"}
 
 
+def stitch_error_text(entry, err):
+    """The ``SedError`` text for the non-zero error word ``err`` that the stitch entry ``entry`` left."""
+    return f"{entry} reported err " + ", ".join(f"bit {b} ({t})" for b, t in STITCH_ERR_BITS.items() if err & b) + f" (err = {err})"
+
+
+def _weighting_code(weighting):
+    if weighting not in WEIGHTINGS:
+        raise ValueError(f"weighting must be one of {sorted(WEIGHTINGS)}, got {weighting!r}")
+    return WEIGHTINGS[weighting]
+
+
 def _per_class(value, nclass, dtype, what):
     a = np.asarray(value, dtype=dtype).reshape(-1)
     if a.size == 1:
@@ -160,7 +171,7 @@ def _per_class(value, nclass, dtype, what):
 def _stitch_call(entry, win_strong, rec_win0, rec_frame0, total, hop3, thr, win, weighting, capacity, ws_bytes, want_timeline,
                  want_binary=False, n_points=None):
     """The call both stitch entries share: outputs, scratch and ``entry`` (``sed_stitch_sweep`` takes ``n_points``,
-    ``sed_stitch_decode`` a binary timeline).  ``thr`` / ``win``: device tensors, one row of nclass values per point."""
+    ``sed_stitch_decode`` a binary timeline).  ``thr`` / ``win``: device tensors [points, nclass]; ``weighting``: its code."""
     dev = win_strong.device
     win_strong = win_strong.contiguous().float()
     n_win, T3, NC = win_strong.shape
@@ -173,7 +184,7 @@ def _stitch_call(entry, win_strong, rec_win0, rec_frame0, total, hop3, thr, win,
            "timeline": torch.empty(total, NC, dtype=torch.float32, device=dev) if want_timeline else None,
            "binary": torch.empty(total, NC, dtype=torch.uint8, device=dev) if want_binary else None}
     ws = _lib.scratch(ws_bytes, dev)
-    head = (_lib.ptr(win_strong), _lib.ptr(rec_win0), _lib.ptr(rec_frame0), n_rec, T3, NC, int(hop3), WEIGHTINGS[weighting])
+    head = (_lib.ptr(win_strong), _lib.ptr(rec_win0), _lib.ptr(rec_frame0), n_rec, T3, NC, int(hop3), weighting)
     if n_points is None:
         points = (_lib.ptr(thr), _lib.ptr(win), _lib.ptr(out["timeline"]), _lib.ptr(out["binary"]))
     else:
@@ -193,8 +204,7 @@ def stitch_decode(win_strong, rec_win0, rec_frame0, total_frames, hop3, threshol
     [total_frames, nclass] or None.  ``threshold`` / ``median_window``: scalars, per-class sequences or device tensors."""
     if win_strong.device.type != "cuda":
         raise _lib.SedError("stitch_decode needs GPU tensors (no CPU fallback)")
-    if weighting not in WEIGHTINGS:
-        raise ValueError(f"weighting must be one of {sorted(WEIGHTINGS)}, got {weighting!r}")
+    weighting = _weighting_code(weighting)
     dev, NC, total = win_strong.device, win_strong.shape[2], int(total_frames)
     if total * NC >= 2 ** 31:
         raise ValueError(f"{total} timeline frames x {NC} classes: the product must stay below 2^31")
@@ -226,8 +236,7 @@ def stitch_sweep(win_strong, rec_win0, rec_frame0, total_frames, hop3, threshold
     is None: it would be K timelines) plus ``n_points``: ``ev_ptr`` [K * n_rec * nclass + 1] is one CSR over the columns
     ``(k * n_rec + rec) * nclass + c``, ``ev_pairs`` [capacity, 2] (default: K times ``stitch_decode``'s).  Nothing
     synchronises."""
-    if weighting not in WEIGHTINGS:
-        raise ValueError(f"weighting must be one of {sorted(WEIGHTINGS)}, got {weighting!r}")
+    weighting = _weighting_code(weighting)
     if win_strong.dim() != 3:
         raise ValueError(f"win_strong must be [n_win, T3, nclass], got {tuple(win_strong.shape)}")
     NC = win_strong.shape[2]
@@ -254,84 +263,10 @@ def stitch_sweep(win_strong, rec_win0, rec_frame0, total_frames, hop3, threshold
                         ws_bytes, want_timeline, n_points=K)
 
 
-def stitch_weak(win_strong, win_att, rec_win0, rec_frame0, total_frames, hop3, weighting="taper", want_sums=False):
-    """Recording-level weak tags (``sed_stitch_weak``): ``win_strong`` / ``win_att`` [n_win, T3, nclass] cuda float32 - the
-    windows' posteriors and attention (``long_window_posteriors(want_attention=True)``) - are blended like ``stitch_decode``'s
-    timeline and pooled over every recording's whole timeline in fp64, ``weak = sum(P * A) / sum(A)``; no timeline is written.
-    Tables as for ``stitch_decode``.  Returns a dict, all on the device, nothing synchronises: ``weak`` [n_rec, nclass]
-    float32, ``sums`` [n_rec, nclass, 2] float64 (num, den) or None, ``err`` [1] int32 (``STITCH_ERR_BITS`` 16 / 32: the rows
-    of such a recording are NaN)."""
-    if weighting not in WEIGHTINGS:
-        raise ValueError(f"weighting must be one of {sorted(WEIGHTINGS)}, got {weighting!r}")
-    if win_strong.dim() != 3 or win_att.shape != win_strong.shape:
-        raise ValueError(f"win_strong and win_att must both be [n_win, T3, nclass], got {tuple(win_strong.shape)} and "
-                         f"{tuple(win_att.shape)}")
-    n_win, T3, NC = win_strong.shape
-    total, n_rec = int(total_frames), rec_win0.numel() - 1
-    if not 1 <= NC <= 16 or not 1 <= int(hop3) <= T3 <= 4096 or n_rec < 1 or total < 1:
-        raise ValueError(f"need 1 <= nclass <= 16, 1 <= hop3 <= T3 <= 4096, n_rec >= 1, total_frames >= 1; got nclass {NC}, "
-                         f"hop3 {hop3}, T3 {T3}, n_rec {n_rec}, total_frames {total}")
-    if total * NC >= 2 ** 31:
-        raise ValueError(f"{total} timeline frames x {NC} classes: the product must stay below 2^31")
-    if win_strong.device.type != "cuda" or win_att.device != win_strong.device:
-        raise _lib.SedError("stitch_weak needs GPU tensors on one device (no CPU fallback)")
-    dev = win_strong.device
-    win_strong, win_att = win_strong.contiguous().float(), win_att.contiguous().float()
-    out = {"weak": torch.empty(n_rec, NC, dtype=torch.float32, device=dev),
-           "sums": torch.empty(n_rec, NC, 2, dtype=torch.float64, device=dev) if want_sums else None,
-           "err": torch.zeros(1, dtype=torch.int32, device=dev)}
-    l = _lib.lib()
-    ws = _lib.scratch(l.sed_stitch_weak_ws_bytes(total, n_rec, NC), dev)
-    _lib.check(l.sed_stitch_weak(_lib.ptr(win_strong), _lib.ptr(win_att), _lib.ptr(rec_win0), _lib.ptr(rec_frame0), n_rec, T3, NC,
-                                 int(hop3), WEIGHTINGS[weighting], _lib.ptr(out["weak"]), _lib.ptr(out["sums"]), _lib.ptr(ws),
-                                 ws.numel(), _lib.ptr(out["err"]), _lib.stream_ptr()), "sed_stitch_weak")
-    return out
-
-
-class _PooledTags(torch.autograd.Function):
-    """forward = sed_stitch_weak with the (num, den) sums kept, backward = sed_stitch_weak_backward."""
-
-    @staticmethod
-    def forward(ctx, win_strong, win_att, rec_win0, rec_frame0, total, hop3, weighting, err):
-        l = _lib.lib()
-        n_win, T3, NC = win_strong.shape
-        n_rec, dev = rec_win0.numel() - 1, win_strong.device
-        weak = torch.empty(n_rec, NC, dtype=torch.float32, device=dev)
-        sums = torch.empty(n_rec, NC, 2, dtype=torch.float64, device=dev)
-        ws = _lib.scratch(l.sed_stitch_weak_ws_bytes(total, n_rec, NC), dev)
-        _lib.check(l.sed_stitch_weak(_lib.ptr(win_strong), _lib.ptr(win_att), _lib.ptr(rec_win0), _lib.ptr(rec_frame0), n_rec, T3, NC,
-                                     hop3, weighting, _lib.ptr(weak), _lib.ptr(sums), _lib.ptr(ws), ws.numel(), _lib.ptr(err),
-                                     _lib.stream_ptr()), "sed_stitch_weak")
-        ctx.save_for_backward(win_strong, win_att, rec_win0, rec_frame0, sums)
-        ctx.hop3, ctx.weighting, ctx.err = hop3, weighting, err          # (err: the library ORs into it, autograd never sees it)
-        return weak
-
-    @staticmethod
-    def backward(ctx, g_weak):
-        l = _lib.lib()
-        win_strong, win_att, rec_win0, rec_frame0, sums = ctx.saved_tensors
-        err = ctx.err
-        n_win, T3, NC = win_strong.shape
-        g_weak = g_weak.contiguous().float()
-        d_strong, d_att = torch.empty_like(win_strong), torch.empty_like(win_att)
-        _lib.check(l.sed_stitch_weak_backward(_lib.ptr(win_strong), _lib.ptr(win_att), _lib.ptr(rec_win0), _lib.ptr(rec_frame0),
-                                              rec_win0.numel() - 1, T3, NC, ctx.hop3, ctx.weighting, _lib.ptr(sums),
-                                              _lib.ptr(g_weak), _lib.ptr(d_strong), _lib.ptr(d_att), _lib.ptr(err),
-                                              _lib.stream_ptr()), "sed_stitch_weak_backward")
-        return d_strong, d_att, None, None, None, None, None, None
-
-
-def pooled_tags(win_strong, win_att, rec_win0, rec_frame0, total_frames, hop3, weighting="taper", n_win=None):
-    """``stitch_weak``'s recording-level tags as a differentiable function of both window tensors: ``(weak, err)``, ``weak``
-    [n_rec, nclass] float32 with an autograd node whose forward is ``sed_stitch_weak`` and whose backward is
-    ``sed_stitch_weak_backward`` (the forward's fp64 sums are kept for it); ``err`` [1] int32 on the device, OR-ed into by both
-    (``STITCH_ERR_BITS`` 16 / 32; nothing synchronises - read it when convenient, the tags and gradients are invalid when it
-    is nonzero).  Arguments as for ``stitch_weak``.  The window tensors must hold exactly ``rec_win0[-1]`` windows: the
-    backward writes every element of both gradients over the tables' own window count, which lives on the device.  ``n_win``:
-    that count where the caller has it on the host (``train_recording_tags`` does) - checked against the tensors here, with
-    no synchronisation; without it the requirement is the caller's."""
-    if weighting not in WEIGHTINGS:
-        raise ValueError(f"weighting must be one of {sorted(WEIGHTINGS)}, got {weighting!r}")
+def _weak_inputs(who, win_strong, win_att, rec_win0, total_frames, hop3, weighting, n_win=None):
+    """The input checks of ``stitch_weak`` and ``pooled_tags`` (``who``; ``n_win``: the latter's host-side window count).
+    Returns ``(total_frames, hop3, the weighting's code)`` as ints."""
+    weighting = _weighting_code(weighting)
     if win_strong.dim() != 3 or win_att.shape != win_strong.shape:
         raise ValueError(f"win_strong and win_att must both be [n_win, T3, nclass], got {tuple(win_strong.shape)} and "
                          f"{tuple(win_att.shape)}")
@@ -345,13 +280,78 @@ def pooled_tags(win_strong, win_att, rec_win0, rec_frame0, total_frames, hop3, w
     if total * NC >= 2 ** 31:
         raise ValueError(f"{total} timeline frames x {NC} classes: the product must stay below 2^31")
     if win_strong.device.type != "cuda" or win_att.device != win_strong.device:
-        raise _lib.SedError("pooled_tags needs GPU tensors on one device (no CPU fallback)")
-    if rec_win0.dtype != torch.int32 or rec_frame0.dtype != torch.int64 or rec_frame0.numel() != n_rec + 1 or \
+        raise _lib.SedError(f"{who} needs GPU tensors on one device (no CPU fallback)")
+    return total, int(hop3), weighting
+
+
+def _weak_call(win_strong, win_att, rec_win0, rec_frame0, total, hop3, weighting, err, want_sums):
+    """The one ``sed_stitch_weak`` call, on checked contiguous float32 window tensors: ``(weak, sums or None)``."""
+    l = _lib.lib()
+    n_win, T3, NC = win_strong.shape
+    n_rec, dev = rec_win0.numel() - 1, win_strong.device
+    weak = torch.empty(n_rec, NC, dtype=torch.float32, device=dev)
+    sums = torch.empty(n_rec, NC, 2, dtype=torch.float64, device=dev) if want_sums else None
+    ws = _lib.scratch(l.sed_stitch_weak_ws_bytes(total, n_rec, NC), dev)
+    _lib.check(l.sed_stitch_weak(_lib.ptr(win_strong), _lib.ptr(win_att), _lib.ptr(rec_win0), _lib.ptr(rec_frame0), n_rec, T3, NC,
+                                 hop3, weighting, _lib.ptr(weak), _lib.ptr(sums), _lib.ptr(ws), ws.numel(), _lib.ptr(err),
+                                 _lib.stream_ptr()), "sed_stitch_weak")
+    return weak, sums
+
+
+def stitch_weak(win_strong, win_att, rec_win0, rec_frame0, total_frames, hop3, weighting="taper", want_sums=False):
+    """Recording-level weak tags (``sed_stitch_weak``): ``win_strong`` / ``win_att`` [n_win, T3, nclass] cuda float32 - the
+    windows' posteriors and attention (``long_window_posteriors(want_attention=True)``) - are blended like ``stitch_decode``'s
+    timeline and pooled over every recording's whole timeline in fp64, ``weak = sum(P * A) / sum(A)``; no timeline is written.
+    Tables as for ``stitch_decode``.  Returns a dict, all on the device, nothing synchronises: ``weak`` [n_rec, nclass]
+    float32, ``sums`` [n_rec, nclass, 2] float64 (num, den) or None, ``err`` [1] int32 (``STITCH_ERR_BITS`` 16 / 32: the rows
+    of such a recording are NaN)."""
+    total, hop3, weighting = _weak_inputs("stitch_weak", win_strong, win_att, rec_win0, total_frames, hop3, weighting)
+    err = torch.zeros(1, dtype=torch.int32, device=win_strong.device)
+    weak, sums = _weak_call(win_strong.contiguous().float(), win_att.contiguous().float(), rec_win0, rec_frame0, total, hop3,
+                            weighting, err, want_sums)
+    return {"weak": weak, "sums": sums, "err": err}
+
+
+class _PooledTags(torch.autograd.Function):
+    """forward = sed_stitch_weak with the (num, den) sums kept, backward = sed_stitch_weak_backward."""
+
+    @staticmethod
+    def forward(ctx, win_strong, win_att, rec_win0, rec_frame0, total, hop3, weighting, err):
+        weak, sums = _weak_call(win_strong, win_att, rec_win0, rec_frame0, total, hop3, weighting, err, True)
+        ctx.save_for_backward(win_strong, win_att, rec_win0, rec_frame0, sums)
+        ctx.hop3, ctx.weighting, ctx.err = hop3, weighting, err          # (err: the library ORs into it, autograd never sees it)
+        return weak
+
+    @staticmethod
+    def backward(ctx, g_weak):
+        l = _lib.lib()
+        win_strong, win_att, rec_win0, rec_frame0, sums = ctx.saved_tensors
+        n_win, T3, NC = win_strong.shape
+        g_weak = g_weak.contiguous().float()
+        d_strong, d_att = torch.empty_like(win_strong), torch.empty_like(win_att)
+        _lib.check(l.sed_stitch_weak_backward(_lib.ptr(win_strong), _lib.ptr(win_att), _lib.ptr(rec_win0), _lib.ptr(rec_frame0),
+                                              rec_win0.numel() - 1, T3, NC, ctx.hop3, ctx.weighting, _lib.ptr(sums),
+                                              _lib.ptr(g_weak), _lib.ptr(d_strong), _lib.ptr(d_att), _lib.ptr(ctx.err),
+                                              _lib.stream_ptr()), "sed_stitch_weak_backward")
+        return d_strong, d_att, None, None, None, None, None, None
+
+
+def pooled_tags(win_strong, win_att, rec_win0, rec_frame0, total_frames, hop3, weighting="taper", n_win=None):
+    """``stitch_weak``'s recording-level tags as a differentiable function of both window tensors: ``(weak, err)``, ``weak``
+    [n_rec, nclass] float32 with an autograd node whose forward is ``sed_stitch_weak`` and whose backward is
+    ``sed_stitch_weak_backward`` (the forward's fp64 sums are kept for it); ``err`` [1] int32 on the device, OR-ed into by both
+    (``STITCH_ERR_BITS`` 16 / 32; nothing synchronises - read it when convenient, the tags and gradients are invalid when it
+    is nonzero).  Arguments as for ``stitch_weak``.  The window tensors must hold exactly ``rec_win0[-1]`` windows: the
+    backward writes every element of both gradients over the tables' own window count, which lives on the device.  ``n_win``:
+    that count where the caller has it on the host (``train_recording_tags`` does) - checked against the tensors here, with
+    no synchronisation; without it the requirement is the caller's."""
+    total, hop3, weighting = _weak_inputs("pooled_tags", win_strong, win_att, rec_win0, total_frames, hop3, weighting, n_win)
+    if rec_win0.dtype != torch.int32 or rec_frame0.dtype != torch.int64 or rec_frame0.numel() != rec_win0.numel() or \
             rec_win0.device != win_strong.device or rec_frame0.device != win_strong.device:
         raise ValueError("rec_win0 [n_rec + 1] int32 and rec_frame0 [n_rec + 1] int64 must be on the window tensors' device")
     err = torch.zeros(1, dtype=torch.int32, device=win_strong.device)
     weak = _PooledTags.apply(win_strong.contiguous().float(), win_att.contiguous().float(), rec_win0.contiguous(),
-                             rec_frame0.contiguous(), total, int(hop3), WEIGHTINGS[weighting], err)
+                             rec_frame0.contiguous(), total, hop3, weighting, err)
     return weak, err
 
 
@@ -441,8 +441,7 @@ def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=
     for what, word in calls:
         err = int(word.item())
         if err:
-            raise _lib.SedError(f"{what} reported err " + ", ".join(f"bit {b} ({t})" for b, t in STITCH_ERR_BITS.items()
-                                                                    if err & b) + f" (err = {err})")
+            raise _lib.SedError(stitch_error_text(what, err))
     ev_ptr = out["ev_ptr"].cpu().numpy()
     ev = out["ev_pairs"][:int(ev_ptr[-1])].cpu().numpy()
     per_col = np.diff(ev_ptr)

@@ -840,7 +840,7 @@ def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, 
     ONCE (``inference.stitch_weak``) and scored by ``weak_counts`` at ``weak_thresholds`` (entries as ``thresholds``, the
     default), and the call returns ``(that list, {"f_measure": [Kw, nclass] float64, "counts": [Kw, nclass, 4] int64 (tp, fp,
     fn, tn)})`` - still one device -> host copy.  With ``weak_labels=None`` nothing changes."""
-    from .inference import (STITCH_ERR_BITS, _per_class, long_window_posteriors, stitch_decode, stitch_sweep, stitch_weak,
+    from .inference import (_per_class, long_window_posteriors, stitch_decode, stitch_error_text, stitch_sweep, stitch_weak,
                             sweep_points)
     from .longrec import LongRecordingSet, sweep_chunks
     cfg = cfg or _Cfg
@@ -908,8 +908,7 @@ def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, 
     ev, seg, tail = counts.host(torch.cat([wc.reshape(-1), tags["err"].to(torch.int64)]))
     err = int(tail[-1])
     if err:
-        raise _lib.SedError("sed_stitch_weak reported err " + ", ".join(f"bit {b} ({t})" for b, t in STITCH_ERR_BITS.items()
-                                                                        if err & b) + f" (err = {err})")
+        raise _lib.SedError(stitch_error_text("sed_stitch_weak", err))
     wc = tail[:-1].reshape(len(weak_thr), NC, 4)
     return ([(EventMetrics(ref.labels, ev[k]), SegmentMetrics(ref.labels, seg[k])) for k in range(K)],
             {"f_measure": f_measure_from_counts(wc), "counts": wc})
