@@ -232,6 +232,11 @@ int sed_crnn_attention(const sed_dims* d, const void* ctx, size_t ctx_bytes, flo
  * w = state->cons_weight, and its gradient w.r.t. the student outputs.
  *   masks are the reference's Python slices (main.py:241,247) as [lo, hi) row ranges; lo==hi
  *   disables the term (weak_mask / strong_mask = None).
+ *   BCE is nn.BCELoss with its two clamps: each logarithm at -100, the gradient (p - t) / max((1 - p) p, 1e-12); a posterior of
+ *   exactly 0 or 1 gives finite terms and gradients.  The posteriors come from the heads' fast sigmoid (csrc/common.h
+ *   sigmoidf_fast = v_rcp(1 + v_exp(-z)), flushing denormals): for a logit in -88 .. -104 torch keeps a denormal posterior and
+ *   an unclamped logarithm where the kernels give exactly 0 and the -100 clamp - the one zone where the two differ by more
+ *   than rounding (tests/test_gpu_heads_regimes.py pins both sides of it, not the zone).
  *   losses: float[SED_LOSS_FLOATS(B)], ZERO-INITIALISED by the caller once (not per call):
  *     [0,8) = {loss, weak_bce, strong_bce, cons_strong, cons_weak, weak_ema_bce, strong_ema_bce,
  *              cons_weight}  (the meters of main.py:106-149);

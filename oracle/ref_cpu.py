@@ -154,10 +154,10 @@ def crnn_forward(params, x, train, bn_state=None, masks=None, n_layers_RNN=2, up
 
 
 def bce(p, t):
-    """nn.BCELoss() (main.py:62): mean of -(t log p + (1-t) log(1-p)), each log clamped to >= -100."""
-    lp = torch.clamp(torch.log(p), min=-100.0)
-    l1p = torch.clamp(torch.log(1.0 - p), min=-100.0)
-    return -(t * lp + (1.0 - t) * l1p).mean()
+    """nn.BCELoss() (main.py:62): mean of -(t log p + (1-t) log(1-p)), each log clamped to >= -100, WITH BCELoss's own
+    backward (p - t) / max((1 - p) p, 1e-12) / numel.  It is the operator itself: clamp(log p, -100) under autograd gives
+    inf * 0 = NaN at p == 0 and p == 1, where BCELoss (and the kernels' bce_grad) stay finite."""
+    return F.binary_cross_entropy(p, t.to(p.dtype))
 
 
 def sigmoid_rampup(current, rampup_length):

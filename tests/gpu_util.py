@@ -22,6 +22,53 @@ def make_model(seed=0, dropout=0.5, device="cuda", n_layers=2, nclass=10, C=64, 
     return m.to(device), params
 
 
+HEAD_NAMES = ("dense.weight", "dense.bias", "dense_softmax.weight", "dense_softmax.bias")
+# the ladder's biases: sigmoid logits from exact 0 (-120) through posteriors below the 1e-12 gradient clamp (-40, -30) to exact 1
+# (30, 120), none in -88 .. -104 (include/dcase_sed.h: sigmoidf_fast); attention logits from the dominant class down past the
+# 1e-7 clamp (ln 1e-7 = -16.1: -13 stays 17 x above it, -19 and below are clamped in every frame)
+_LADDER_D = [-120., -40., -30., -8., -3., 0., 3., 8., 30., 120.]
+_LADDER_S = [0., -2., -5., -10., -13., -19., -25., -40., -90., -120.]
+_LADDER_D16 = _LADDER_D + [-60., -20., -1., 1., 20., 60.]
+_LADDER_S16 = _LADDER_S + [-1., -7., -22., -30., -60., -100.]
+
+
+def steer_heads(params, steering):
+    """The four head tensors of ``params`` moved into a confident regime (a randomly initialised CRNN keeps every posterior in
+    0.4 .. 0.6 and no attention value near the clamp); everything in front of the heads stays as make_params gives it.
+    "ladder": exact saturation - posteriors exactly 0 and 1, attention clamped in every frame of half the classes;
+    "confident": no cliff - at the shapes of tests/test_gpu_heads_regimes.py, in eval mode and in train mode without dropout,
+    posteriors between 1.4e-4 and 1 - 1.8e-4 (the widest: (2, 1040), train mode) and 9 - 19 % of the attention clamped at
+    (3, 136) and (2, 1040) (profiles/heads_regimes.md has the table).  Returns a new dict."""
+    out = dict(params)
+    if steering is None:
+        return out
+    nc = params["dense.bias"].numel()
+    dt = params["dense.bias"].dtype
+    if steering == "ladder":
+        d, s = {1: ([30.], [0.]), 10: (_LADDER_D, _LADDER_S), 16: (_LADDER_D16, _LADDER_S16)}[nc]
+        out["dense.weight"] = params["dense.weight"] * 0.25
+        out["dense.bias"] = torch.tensor(d, dtype=dt)
+        out["dense_softmax.bias"] = torch.tensor(s, dtype=dt)
+    elif steering == "confident":
+        out["dense.weight"] = params["dense.weight"] * 12
+        out["dense.bias"] = torch.linspace(-5, 5, nc, dtype=torch.float64).to(dt)
+        out["dense_softmax.weight"] = params["dense_softmax.weight"] * 30
+        out["dense_softmax.bias"] = torch.linspace(6, -6, nc, dtype=torch.float64).to(dt)
+    else:
+        raise ValueError(steering)
+    return out
+
+
+def steer_model(model, params, steering):
+    """steer_heads on ``params`` and the same four tensors written into ``model`` (in place); returns the steered params."""
+    out = steer_heads(params, steering)
+    named = dict(model.named_parameters())
+    with torch.no_grad():
+        for n in HEAD_NAMES:
+            named[n].copy_(out[n])
+    return out
+
+
 def set_bn(model, bn_state):
     bufs = dict(model.named_buffers())
     with torch.no_grad():
