@@ -81,6 +81,15 @@ _SIGS = {
     "sed_long_sweep_psds_counts": (C.c_int, [_P, _P, C.c_double, C.c_double, _P, _P, C.c_longlong, _P, _P, _P, C.c_longlong,
                                              C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P,
                                              C.c_size_t, _P]),
+    "sed_error_counts": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P,
+                                   C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P]),
+    "sed_long_error_ws_bytes": (C.c_size_t, [C.c_longlong, C.c_longlong, C.c_int, C.c_int]),
+    "sed_long_sweep_error_ws_bytes": (C.c_size_t, [C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int]),
+    "sed_long_error_counts": (C.c_int, [_P, _P, C.c_double, C.c_double, _P, _P, C.c_longlong, _P, _P, _P, C.c_longlong, C.c_int,
+                                        C.c_int, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "sed_long_sweep_error_counts": (C.c_int, [_P, _P, C.c_double, C.c_double, _P, _P, C.c_longlong, _P, _P, _P, C.c_longlong,
+                                              C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P,
+                                              _P, C.c_size_t, _P]),
     "sed_weak_counts": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P]),
     "sed_version": (C.c_int, []),
     "sed_param_count": (C.c_int, [C.POINTER(SedDims)]),

@@ -14,12 +14,13 @@
 //   k_ls_match     one wave per tile of LS_TILE reference events.  "i starts a cluster" is a local test (two bisections in
 //                  the estimated onsets), so a wave finds the clusters that START in its tile with one ballot, their ends with
 //                  a second ballot over the next tile (further ones only on the error path), and solves each with sc_max_matching
-//                  (score.h: the augmenting-path ballot search k_event_counts runs; only the source of the masks differs)
+//                  (score.h: sc_match_tile, which k_error_counts runs on a clip's merged lists as well)
 //   k_ls_segments  one thread per segment: segment s is covered iff the last event whose first segment is <= s has
 //                  seg(pmax) > s - two bisections, no bitmap, no events x segments loop
 //   k_lp_detect    one thread per detection: DTC and, for the non-relevant ones, CTTC against every other class
 //   k_lp_truth     one thread per ground truth: GTC over the relevant detections
 //   k_ls_final / k_lp_final   per-column outputs and the class totals
+//   k_le_*         the overall error rate with substitutions (sed_long_error_counts, sed_long_sweep_error_counts): further down
 // The PSDS sums skip events that cannot overlap (bisection on the onsets for the upper end, on pmax for the lower end):
 // every skipped term is +0.0 and the sum starts at 0.0, so the bits are those of the full sequential sum.
 // Counts are integers, the atomics are integer atomics: results are bit-reproducible.  Every offset is validated against the
@@ -129,32 +130,7 @@ __global__ __launch_bounds__(LS_PREP_THREADS) void k_ls_prep(LsArgs a) {
     }
 }
 
-// first j in [0, n) with !(x[j] far below r), i.e. the number of j with r - x[j] > tol (x sorted)
-__device__ __forceinline__ int ls_count_below(const double* x, int n, double r, double tol) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (r - x[mid] > tol) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-// first j in [0, n] with x[j] - r > tol (x sorted)
-__device__ __forceinline__ int ls_first_above(const double* x, int n, double r, double tol) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (x[mid] - r > tol) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
-// A cut in front of reference i is a pair (i, j): the first i references and the first j estimated events lie before it.  It
-// is valid iff jlo(i) <= j <= jhi(i), jlo(i) = first j with E[j] - R[i - 1] > t_collar, jhi(i) = number of j with
-// R[i] - E[j] > t_collar - the differences are formed as the compatibility test forms them, so that no pair the test accepts
-// can straddle a cut whatever the rounding.  The cluster of references i0 .. i1 - 1 (i0, i1 consecutive indices with a
-// valid cut) holds the estimated events jhi(i0) .. jlo(i1) - 1; estimated events outside these ranges match nothing.
+// The clusters between the valid cuts of a column and their matching: sc_match_tile (score.h).
 __global__ __launch_bounds__(256) void k_ls_match(LsArgs a) {
     const int lane = threadIdx.x & 63;
     const long long g = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -177,78 +153,9 @@ __global__ __launch_bounds__(256) void k_ls_match(LsArgs a) {
     const long long kt = gl - (pr / LS_TILE + rcol);
     if (kt < 0 || kt * LS_TILE >= n_ref) return;
     const int i_base = (int)kt * LS_TILE;
-    const double* R = a.ref_on + pr;
-    const double* Roff = a.ref_off + pr;
-    const double* E = a.est_on + pe;
-    const double* Eoff = a.est_off + pe;
-    const double tc = a.t_collar;
-    // lane l: reference i_base + l (first ballot) and i_base + 64 + l (second); index n_ref is the column's end
-    int jlo[2], jhi[2];
-    unsigned long long starts[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int i = i_base + h * LS_TILE + lane;
-        bool bnd = false;
-        jlo[h] = jhi[h] = 0;
-        if (i <= n_ref) {
-            jlo[h] = i > 0 ? ls_first_above(E, n_est, R[i - 1], tc) : 0;
-            jhi[h] = i < n_ref ? ls_count_below(E, n_est, R[i], tc) : n_est;
-            bnd = jlo[h] <= jhi[h];
-        }
-        starts[h] = __ballot(bnd);
-    }
-    unsigned long long todo = starts[0];
-    if (n_ref - i_base < 64) todo &= (1ull << (n_ref - i_base)) - 1;     // a cluster starts at a reference, not at the end
-    int ntp = 0, flags = 0;
-    while (todo) {
-        const int s = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        const unsigned long long later = starts[0] & ((~0ull << s) << 1);
-        int nr, j1;
-        if (later) {
-            const int t = __ffsll((long long)later) - 1;
-            nr = t - s;
-            j1 = sc_lane_read(jlo[0], t);
-        } else if (starts[1]) {
-            const int t = __ffsll((long long)starts[1]) - 1;
-            nr = 64 + t - s;
-            j1 = sc_lane_read(jlo[1], t);
-        } else {                               // more than 64 references (bit 1): walk on to the cluster's end for bit 2
-            nr = 0;
-            j1 = 0;
-            for (int base = i_base + 2 * LS_TILE; nr == 0; base += LS_TILE) {       // ends: index n_ref is always a cut
-                const int i = base + lane;
-                const int jl = i <= n_ref ? ls_first_above(E, n_est, R[i - 1], tc) : 0;
-                const int jh = i < n_ref ? ls_count_below(E, n_est, R[i], tc) : n_est;
-                const unsigned long long m = __ballot(i <= n_ref && jl <= jh);
-                if (m) {
-                    const int t = __ffsll((long long)m) - 1;
-                    nr = base + t - (i_base + s);
-                    j1 = sc_lane_read(jl, t);
-                }
-            }
-        }
-        const int j0 = sc_lane_read(jhi[0], s);
-        const int ne = j1 - j0;
-        if (nr > SC_MAXEV) flags |= SC_ERR_MANY_REF;
-        if (ne > SC_MAXEV) flags |= SC_ERR_MANY_EST;
-        if (nr > SC_MAXEV || ne > SC_MAXEV || ne <= 0) continue;
-        // ---- the cluster: lane r holds reference i0 + r and the mask of the estimated events compatible with it ----------
-        const int i0 = i_base + s;
-        const bool has_ref = lane < nr;
-        double r_on = 0.0, r_off = 0.0;
-        if (has_ref) {
-            r_on = R[i0 + lane];
-            r_off = Roff[i0 + lane];
-        }
-        const double tol_off = sc_offset_tolerance(r_on, r_off, tc, a.pct);
-        unsigned long long adj = 0;
-        for (int e = 0; e < ne; ++e) {
-            const bool hit = has_ref && sc_compatible(r_on, r_off, tol_off, E, Eoff, j0 + e, tc);
-            adj |= (unsigned long long)hit << e;
-        }
-        ntp += sc_max_matching(adj, ne, lane);
-    }
+    int flags = 0;
+    const int ntp = sc_match_tile(a.ref_on + pr, a.ref_off + pr, n_ref, a.est_on + pe, a.est_off + pe, n_est, i_base, a.t_collar,
+                                  a.pct, lane, flags);
     if (lane == 0) {
         if (ntp > 0) atomicAdd(a.cnt + col * LS_CW, ntp);
         if (flags) {
@@ -470,6 +377,155 @@ __global__ __launch_bounds__(256) void k_lp_final(LsArgs a) {
     if (mine > 0) atomicAdd(a.tot_a + c * W + v, (unsigned long long)mine);
 }
 
+// ---- overall error rate with substitutions ----------------------------------------------------------------------------------
+// (include/dcase_sed.h, "overall error rate".)  Nany of a recording is a ONE-CLASS problem on the onset-sorted union of its
+// class columns, so after k_ls_prep (the class columns, as for the other calls):
+//   k_le_columns   one thread per merged column - (point, recording) on the estimated side, recording on the reference side:
+//                  its offsets, the OR of its class columns' err bits, its counters zeroed
+//   k_le_merge     one thread per event: its rank in the union is its index in its own column plus a bisection count in each
+//                  other column of the recording (ties by class, then index), so every slot of the merged table has exactly
+//                  one writer and there is no atomic.  The reference side is merged once, whatever K is
+//   k_ls_match     the kernel of the class-wise calls, on the merged table with nclass = 1
+//   k_le_segments  one thread per segment: ls_covered per class gives a 16-bit mask per side, sc_segment_sdi the segment's
+//                  part of (S, D, I)
+//   k_le_final     one thread per (point, recording): outputs and totals
+struct LeArgs {
+    LsArgs c;                        // the class columns, as k_ls_prep validated them
+    int64_t *m_eptr, *m_rptr;        // ws [K * n_rec + 1], [n_rec + 1]: CSR offsets of the merged columns
+    double *m_eon, *m_eoff;          // ws [est_cap] each: a (point, recording)'s events of all classes by onset
+    double *m_ron, *m_roff;          // ws [ref_cap] each
+    int32_t *m_flags, *m_rflags;     // ws [K * n_rec], [n_rec]
+    int32_t* m_cnt;                  // ws [K * n_rec][LS_CW]: [0] Nany, [1..3] S / D / I, [4] k_ls_match's err bits
+    int32_t *ev_out, *seg_out;
+    unsigned long long *ev_tot, *seg_tot;
+};
+
+__global__ __launch_bounds__(256) void k_le_columns(LeArgs a) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long n_e = (long long)a.c.K * a.c.n_rec;
+    if (t >= n_e + a.c.n_rec) return;
+    const int side = t >= n_e;
+    const long long mc = side ? t - n_e : t;
+    const int32_t* flags = side ? a.c.rflags : a.c.flags;
+    const int64_t* ptr = side ? a.c.ref_ptr : a.c.est_ptr;
+    int64_t* m_ptr = side ? a.m_rptr : a.m_eptr;
+    int f = 0;
+    for (int c = 0; c < a.c.NC; ++c) f |= flags[mc * a.c.NC + c];
+    (side ? a.m_rflags : a.m_flags)[mc] = f;
+    m_ptr[mc] = ptr[mc * a.c.NC];
+    if (mc + 1 == (side ? a.c.n_rec : n_e)) m_ptr[mc + 1] = ptr[(mc + 1) * a.c.NC];
+    if (!side)
+        for (int i = 0; i < LS_CW; ++i) a.m_cnt[mc * LS_CW + i] = 0;
+}
+
+// the number of x[0 .. n) (sorted) that are < v, or <= v
+__device__ __forceinline__ int le_count(const double* x, int n, double v, bool or_equal) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (x[mid] < v || (or_equal && x[mid] == v)) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void k_le_merge(LeArgs a, unsigned est_blocks) {
+    const int side = blockIdx.x >= est_blocks;
+    const long long i = (long long)(blockIdx.x - (side ? est_blocks : 0)) * 256 + threadIdx.x;
+    const int NC = a.c.NC;
+    const int64_t* ptr = side ? a.c.ref_ptr : a.c.est_ptr;
+    const long long cap = side ? a.c.ref_cap : a.c.est_cap;
+    const long long ncols = (long long)a.c.n_rec * NC * (side ? 1 : a.c.K);
+    const int32_t* flags = side ? a.c.rflags : a.c.flags;
+    const double* on = side ? a.c.ref_on : a.c.est_on;
+    const double* off = side ? a.c.ref_off : a.c.est_off;
+    if (i >= cap) return;
+    long long p0;
+    int n;
+    const long long col = lp_column(ptr, ncols, cap, i, p0, n);
+    if (col < 0) return;
+    const long long col0 = col - col % NC;                           // the recording's first column
+    int f = 0;
+    for (int c = 0; c < NC; ++c) f |= flags[col0 + c];
+    if (f) return;                                                   // not scored (k_ls_prep reported it): nothing reads its slots
+    const int c = (int)(col - col0);
+    const double v = on[i];
+    long long rank = i - p0;
+    for (int c2 = 0; c2 < NC; ++c2) {
+        if (c2 == c) continue;
+        long long q0;
+        int m;
+        ls_range(ptr, col0 + c2, cap, q0, m);
+        rank += le_count(on + q0, m, v, c2 < c);
+    }
+    // every column of the recording is valid, so its events are [ptr[col0], ptr[col0 + NC]) and rank is below their number
+    const long long at = ptr[col0] + rank;
+    (side ? a.m_ron : a.m_eon)[at] = v;
+    (side ? a.m_roff : a.m_eoff)[at] = off[i];
+}
+
+__global__ __launch_bounds__(256) void k_le_segments(LeArgs a) {
+    const long long mc = blockIdx.x;                                 // (point, recording)
+    const int lane = threadIdx.x & 63, NC = a.c.NC;
+    const int file_seg = ls_file_segments(a.c, mc);
+    if (file_seg > SC_MAXSEG) {
+        if (blockIdx.y == 0 && threadIdx.x == 0) atomicOr(a.c.err, SC_ERR_SEGMENTS);
+        return;
+    }
+    if (a.m_flags[mc] | a.m_rflags[mc % a.c.n_rec]) return;
+    int S = 0, D = 0, I = 0;
+    for (int s = blockIdx.y * 256 + threadIdx.x; s < file_seg; s += LS_SEG_SPLIT * 256) {
+        unsigned ref_mask = 0, est_mask = 0;
+        for (int c = 0; c < NC; ++c) {
+            const long long col = mc * NC + c;
+            long long pr, pe;
+            int n_ref, n_est;
+            ls_range(a.c.ref_ptr, ls_rcol(a.c, col), a.c.ref_cap, pr, n_ref);
+            ls_range(a.c.est_ptr, col, a.c.est_cap, pe, n_est);
+            ref_mask |= (unsigned)ls_covered(a.c.ref_on + pr, a.c.ref_pmax + pr, n_ref, s, a.c.res) << c;
+            est_mask |= (unsigned)ls_covered(a.c.est_on + pe, a.c.est_pmax + pe, n_est, s, a.c.res) << c;
+        }
+        sc_segment_sdi(ref_mask, est_mask, S, D, I);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        S += __shfl_xor(S, o);
+        D += __shfl_xor(D, o);
+        I += __shfl_xor(I, o);
+    }
+    if (lane == 0) {
+        if (S) atomicAdd(a.m_cnt + mc * LS_CW + 1, S);
+        if (D) atomicAdd(a.m_cnt + mc * LS_CW + 2, D);
+        if (I) atomicAdd(a.m_cnt + mc * LS_CW + 3, I);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_le_final(LeArgs a) {
+    const long long mc = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (mc >= (long long)a.c.K * a.c.n_rec) return;
+    const int kp = (int)(mc / a.c.n_rec), NC = a.c.NC;
+    const int32_t* k = a.m_cnt + mc * LS_CW;
+    const bool ok = (a.m_flags[mc] | a.m_rflags[mc % a.c.n_rec] | k[4]) == 0 && ls_file_segments(a.c, mc) <= SC_MAXSEG;
+    int n_ref = 0, n_est = 0;
+    for (int c = 0; c < NC; ++c) {
+        long long p0;
+        int n;
+        ls_range(a.c.ref_ptr, ls_rcol(a.c, mc * NC + c), a.c.ref_cap, p0, n);
+        n_ref += n;
+        ls_range(a.c.est_ptr, mc * NC + c, a.c.est_cap, p0, n);
+        n_est += n;
+    }
+    const int ev[3] = {n_ref, n_est, ok ? k[0] : 0};
+    const int sg[3] = {ok ? k[1] : 0, ok ? k[2] : 0, ok ? k[3] : 0};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        if (a.ev_out) a.ev_out[mc * 3 + i] = ev[i];
+        if (ev[i] > 0) atomicAdd(a.ev_tot + kp * 3 + i, (unsigned long long)ev[i]);
+        if (a.seg_out) a.seg_out[mc * 3 + i] = sg[i];
+        if (sg[i] > 0) atomicAdd(a.seg_tot + kp * 3 + i, (unsigned long long)sg[i]);
+    }
+}
+
 // ---- host -------------------------------------------------------------------------------------------------------------------
 extern "C" int sed_long_tile_events(void) { return LS_TILE; }
 
@@ -621,6 +677,122 @@ static int ls_psds_counts(const char* what, const int64_t* ev_ptr, const int32_t
     hipLaunchKernelGGL(k_lp_final, dim3(ls_blocks(ecols * (2 + nclass), 256)), dim3(256), 0, st, a);
     SED_CHECK_LAUNCH();
     return SED_OK;
+}
+
+// the merged tables behind the workspace of the class-wise calls
+struct LeWs { size_t eptr, rptr, eon, eoff, ron, roff, flags, rflags, cnt, total; };
+static LeWs le_ws(long long est_cap, long long ref_cap, int n_rec, int nclass, int K) {
+    LeWs w;
+    size_t o = ls_align(ls_ws(est_cap, ref_cap, (long long)n_rec * nclass, K).total);
+    const size_t n_e = (size_t)K * n_rec;
+    w.eptr = o;   o += ls_align((n_e + 1) * sizeof(int64_t));
+    w.rptr = o;   o += ls_align(((size_t)n_rec + 1) * sizeof(int64_t));
+    w.eon = o;    o += ls_align((size_t)est_cap * sizeof(double));
+    w.eoff = o;   o += ls_align((size_t)est_cap * sizeof(double));
+    w.ron = o;    o += ls_align((size_t)ref_cap * sizeof(double));
+    w.roff = o;   o += ls_align((size_t)ref_cap * sizeof(double));
+    w.flags = o;  o += ls_align(n_e * sizeof(int32_t));
+    w.rflags = o; o += ls_align((size_t)n_rec * sizeof(int32_t));
+    w.cnt = o;    o += ls_align(n_e * LS_CW * sizeof(int32_t));
+    w.total = o;
+    return w;
+}
+
+extern "C" size_t sed_long_sweep_error_ws_bytes(long long est_capacity, long long ref_events, int n_rec, int nclass,
+                                                int n_points) {
+    if (!ls_sizes_ok(est_capacity, ref_events, n_rec, nclass, n_points)) {
+        sed_set_error("sed_long_sweep_error_ws_bytes: %s", LS_NEED);
+        return 0;
+    }
+    return le_ws(est_capacity, ref_events, n_rec, nclass, n_points).total;
+}
+
+extern "C" size_t sed_long_error_ws_bytes(long long est_capacity, long long ref_events, int n_rec, int nclass) {
+    if (!ls_sizes_ok(est_capacity, ref_events, n_rec, nclass, 1)) {
+        sed_set_error("sed_long_error_ws_bytes: %s", LS_NEED);
+        return 0;
+    }
+    return le_ws(est_capacity, ref_events, n_rec, nclass, 1).total;
+}
+
+// Six launches whatever n_points is; the reference side is validated (k_ls_prep) and merged (k_le_merge) ONCE.
+static int ls_error_counts(const char* what, const int64_t* ev_ptr, const int32_t* ev_pairs, double num, double den,
+                           const double* est_on, const double* est_off, long long est_capacity, const int64_t* ref_ptr,
+                           const double* ref_on, const double* ref_off, long long ref_events, int n_rec, int nclass, int K,
+                           double t_collar, double percentage_of_length, double time_resolution, int32_t* ev_overall,
+                           int32_t* seg_overall, int64_t* ev_overall_total, int64_t* seg_overall_total, int32_t* err, void* ws,
+                           size_t ws_bytes, void* stream) {
+    if (!(ev_overall_total && seg_overall_total)) {
+        sed_set_error("%s: null argument", what);
+        return SED_ERR_BAD_ARG;
+    }
+    if (!(t_collar >= 0.0 && percentage_of_length >= 0.0 && time_resolution > 0.0)) {
+        sed_set_error("%s: need t_collar >= 0, percentage_of_length >= 0, time_resolution > 0", what);
+        return SED_ERR_BAD_ARG;
+    }
+    LeArgs a;
+    SED_TRY(ls_fill(a.c, what, ev_ptr, ev_pairs, num, den, est_on, est_off, est_capacity, ref_ptr, ref_on, ref_off, ref_events,
+                    n_rec, nclass, K, err, ws, ws_bytes));
+    const LeWs w = le_ws(est_capacity, ref_events, n_rec, nclass, K);
+    if (ws_bytes < w.total) {
+        sed_set_error("%s: workspace of %zu bytes is too small (%zu needed)", what, ws_bytes, w.total);
+        return SED_ERR_WORKSPACE;
+    }
+    a.c.t_collar = t_collar; a.c.pct = percentage_of_length; a.c.res = time_resolution;
+    char* b = (char*)ws;
+    a.m_eptr = (int64_t*)(b + w.eptr); a.m_rptr = (int64_t*)(b + w.rptr);
+    a.m_eon = (double*)(b + w.eon); a.m_eoff = (double*)(b + w.eoff);
+    a.m_ron = (double*)(b + w.ron); a.m_roff = (double*)(b + w.roff);
+    a.m_flags = (int32_t*)(b + w.flags); a.m_rflags = (int32_t*)(b + w.rflags); a.m_cnt = (int32_t*)(b + w.cnt);
+    a.ev_out = ev_overall; a.seg_out = seg_overall;
+    a.ev_tot = (unsigned long long*)ev_overall_total; a.seg_tot = (unsigned long long*)seg_overall_total;
+    // the merged table as k_ls_match sees it: one class, the same recordings and points
+    LsArgs m = LsArgs{};
+    m.est_ptr = a.m_eptr; m.est_on = a.m_eon; m.est_off = a.m_eoff;
+    m.ref_ptr = a.m_rptr; m.ref_on = a.m_ron; m.ref_off = a.m_roff;
+    m.est_cap = est_capacity; m.ref_cap = ref_events; m.n_rec = n_rec; m.NC = 1; m.K = K;
+    m.n_slots = (int)(ref_events / LS_TILE + n_rec + 1);
+    m.t_collar = t_collar; m.pct = percentage_of_length; m.res = time_resolution;
+    m.flags = a.m_flags; m.rflags = a.m_rflags; m.cnt = a.m_cnt; m.err = err;
+    const long long ncols = (long long)n_rec * nclass, ecols = ncols * K, mcols = (long long)n_rec * K;
+    const unsigned est_blocks = ls_blocks(est_capacity, 256);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_ls_prep, dim3((unsigned)(ecols + ncols)), dim3(LS_PREP_THREADS), 0, st, a.c);
+    SED_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_le_columns, dim3(ls_blocks(mcols + n_rec, 256)), dim3(256), 0, st, a);
+    SED_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_le_merge, dim3(est_blocks + ls_blocks(ref_events, 256)), dim3(256), 0, st, a, est_blocks);
+    SED_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_ls_match, dim3(ls_blocks((long long)m.n_slots * K, 4)), dim3(256), 0, st, m);
+    SED_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_le_segments, dim3((unsigned)mcols, LS_SEG_SPLIT), dim3(256), 0, st, a);
+    SED_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_le_final, dim3(ls_blocks(mcols, 256)), dim3(256), 0, st, a);
+    SED_CHECK_LAUNCH();
+    return SED_OK;
+}
+
+extern "C" int sed_long_error_counts(const int64_t* ev_ptr, const int32_t* ev_pairs, double num, double den, const double* est_on,
+                                     const double* est_off, long long est_capacity, const int64_t* ref_ptr, const double* ref_on,
+                                     const double* ref_off, long long ref_events, int n_rec, int nclass, double t_collar,
+                                     double percentage_of_length, double time_resolution, int32_t* ev_overall,
+                                     int32_t* seg_overall, int64_t* ev_overall_total, int64_t* seg_overall_total, int32_t* err,
+                                     void* ws, size_t ws_bytes, void* stream) {
+    return ls_error_counts("sed_long_error_counts", ev_ptr, ev_pairs, num, den, est_on, est_off, est_capacity, ref_ptr, ref_on,
+                           ref_off, ref_events, n_rec, nclass, 1, t_collar, percentage_of_length, time_resolution, ev_overall,
+                           seg_overall, ev_overall_total, seg_overall_total, err, ws, ws_bytes, stream);
+}
+
+extern "C" int sed_long_sweep_error_counts(const int64_t* ev_ptr, const int32_t* ev_pairs, double num, double den,
+                                           const double* est_on, const double* est_off, long long est_capacity,
+                                           const int64_t* ref_ptr, const double* ref_on, const double* ref_off,
+                                           long long ref_events, int n_rec, int nclass, int n_points, double t_collar,
+                                           double percentage_of_length, double time_resolution, int32_t* ev_overall,
+                                           int32_t* seg_overall, int64_t* ev_overall_total, int64_t* seg_overall_total,
+                                           int32_t* err, void* ws, size_t ws_bytes, void* stream) {
+    return ls_error_counts("sed_long_sweep_error_counts", ev_ptr, ev_pairs, num, den, est_on, est_off, est_capacity, ref_ptr,
+                           ref_on, ref_off, ref_events, n_rec, nclass, n_points, t_collar, percentage_of_length, time_resolution,
+                           ev_overall, seg_overall, ev_overall_total, seg_overall_total, err, ws, ws_bytes, stream);
 }
 
 extern "C" int sed_long_event_counts(const int64_t* ev_ptr, const int32_t* ev_pairs, double num, double den, const double* est_on,

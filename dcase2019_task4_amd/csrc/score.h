@@ -81,6 +81,120 @@ __device__ __forceinline__ int sc_max_matching(unsigned long long adj, int n_est
     return size;
 }
 
+// ---- clusters of two onset-sorted lists --------------------------------------------------------------------------------------
+// first j in [0, n) with !(x[j] far below r), i.e. the number of j with r - x[j] > tol (x sorted)
+__device__ __forceinline__ int sc_count_below(const double* x, int n, double r, double tol) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (r - x[mid] > tol) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+// first j in [0, n] with x[j] - r > tol (x sorted)
+__device__ __forceinline__ int sc_first_above(const double* x, int n, double r, double tol) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (x[mid] - r > tol) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+
+// A cut in front of reference i is a pair (i, j): the first i references and the first j estimated events lie before it.  It
+// is valid iff jlo(i) <= j <= jhi(i), jlo(i) = first j with E[j] - R[i - 1] > t_collar, jhi(i) = number of j with
+// R[i] - E[j] > t_collar - the differences are formed as the compatibility test forms them, so that no pair the test accepts
+// can straddle a cut whatever the rounding.  The cluster of references i0 .. i1 - 1 (i0, i1 consecutive indices with a
+// valid cut) holds the estimated events jhi(i0) .. jlo(i1) - 1; estimated events outside these ranges match nothing.
+//
+// sc_match_tile, called by a whole wave: the sum of the maximum matchings of the clusters that START among the references
+// i_base .. i_base + 63 of R / Roff[0 .. n_ref) against E / Eoff[0 .. n_est), both sorted by onset.  "i starts a cluster" is a
+// local test (two bisections in the estimated onsets), so the wave finds the starts with one ballot and their ends with a
+// second ballot over the next 64 references (further ones only on the error path).  A cluster of more than SC_MAXEV per side
+// raises SC_ERR_MANY_REF / SC_ERR_MANY_EST in `flags` and is not matched.
+__device__ __forceinline__ int sc_match_tile(const double* R, const double* Roff, int n_ref, const double* E, const double* Eoff,
+                                             int n_est, int i_base, double tc, double pct, int lane, int& flags) {
+    // lane l: reference i_base + l (first ballot) and i_base + 64 + l (second); index n_ref is the column's end
+    int jlo[2], jhi[2];
+    unsigned long long starts[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int i = i_base + h * SC_MAXEV + lane;
+        bool bnd = false;
+        jlo[h] = jhi[h] = 0;
+        if (i <= n_ref) {
+            jlo[h] = i > 0 ? sc_first_above(E, n_est, R[i - 1], tc) : 0;
+            jhi[h] = i < n_ref ? sc_count_below(E, n_est, R[i], tc) : n_est;
+            bnd = jlo[h] <= jhi[h];
+        }
+        starts[h] = __ballot(bnd);
+    }
+    unsigned long long todo = starts[0];
+    if (n_ref - i_base < 64) todo &= (1ull << (n_ref - i_base)) - 1;     // a cluster starts at a reference, not at the end
+    int ntp = 0;
+    while (todo) {
+        const int s = __ffsll((long long)todo) - 1;
+        todo &= todo - 1;
+        const unsigned long long later = starts[0] & ((~0ull << s) << 1);
+        int nr, j1;
+        if (later) {
+            const int t = __ffsll((long long)later) - 1;
+            nr = t - s;
+            j1 = sc_lane_read(jlo[0], t);
+        } else if (starts[1]) {
+            const int t = __ffsll((long long)starts[1]) - 1;
+            nr = 64 + t - s;
+            j1 = sc_lane_read(jlo[1], t);
+        } else {                               // more than 64 references (bit 1): walk on to the cluster's end for bit 2
+            nr = 0;
+            j1 = 0;
+            for (int base = i_base + 2 * SC_MAXEV; nr == 0; base += SC_MAXEV) {     // ends: index n_ref is always a cut
+                const int i = base + lane;
+                const int jl = i <= n_ref ? sc_first_above(E, n_est, R[i - 1], tc) : 0;
+                const int jh = i < n_ref ? sc_count_below(E, n_est, R[i], tc) : n_est;
+                const unsigned long long m = __ballot(i <= n_ref && jl <= jh);
+                if (m) {
+                    const int t = __ffsll((long long)m) - 1;
+                    nr = base + t - (i_base + s);
+                    j1 = sc_lane_read(jl, t);
+                }
+            }
+        }
+        const int j0 = sc_lane_read(jhi[0], s);
+        const int ne = j1 - j0;
+        if (nr > SC_MAXEV) flags |= SC_ERR_MANY_REF;
+        if (ne > SC_MAXEV) flags |= SC_ERR_MANY_EST;
+        if (nr > SC_MAXEV || ne > SC_MAXEV || ne <= 0) continue;
+        // ---- the cluster: lane r holds reference i0 + r and the mask of the estimated events compatible with it ----------
+        const int i0 = i_base + s;
+        const bool has_ref = lane < nr;
+        double r_on = 0.0, r_off = 0.0;
+        if (has_ref) {
+            r_on = R[i0 + lane];
+            r_off = Roff[i0 + lane];
+        }
+        const double tol_off = sc_offset_tolerance(r_on, r_off, tc, pct);
+        unsigned long long adj = 0;
+        for (int e = 0; e < ne; ++e) {
+            const bool hit = has_ref && sc_compatible(r_on, r_off, tol_off, E, Eoff, j0 + e, tc);
+            adj |= (unsigned long long)hit << e;
+        }
+        ntp += sc_max_matching(adj, ne, lane);
+    }
+    return ntp;
+}
+
+// ---- segment-based overall error rate ---------------------------------------------------------------------------------------
+// one segment's part of (S, D, I) from the masks of the classes active in it on each side
+__device__ __forceinline__ void sc_segment_sdi(unsigned ref_mask, unsigned est_mask, int& S, int& D, int& I) {
+    const int fn = __popc(ref_mask & ~est_mask), fp = __popc(est_mask & ~ref_mask);
+    S += min(fn, fp);
+    D += max(0, fn - fp);
+    I += max(0, fp - fn);
+}
+
 // ---- PSDS -------------------------------------------------------------------------------------------------------------------
 // I(a, b) = max(0, min(a.off, b.off) - max(a.on, b.on))
 __device__ __forceinline__ double sc_overlap(double a_on, double a_off, double b_on, double b_off) {

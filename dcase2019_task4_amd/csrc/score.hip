@@ -1,5 +1,6 @@
 // score.hip - validation scoring on the device: event-based, segment-based and clip-level (weak) counts, and the PSDS
-// intersection counts (k_psds_counts, further down).
+// intersection counts (k_psds_counts, further down) and the counts of the overall error rate with substitutions
+// (k_error_counts, after it).
 //
 // Reference ops (baseline/main.py:328-352, evaluation_measures.py:19-102,124-182,234-246), host-side, once per epoch:
 //   compute_strong_metrics(predictions, valid_df) -> sed_eval EventBasedMetrics(t_collar = 0.2, percentage_of_length = 0.2,
@@ -245,6 +246,171 @@ __global__ __launch_bounds__(1024) void k_psds_counts(PsArgs a) {
     if (lane == 0 && flags) atomicOr(a.err, flags);
 }
 
+// ---- overall error rate with substitutions ----------------------------------------------------------------------------------
+// (include/dcase_sed.h, "overall error rate", holds the definitions and the decision about sed_eval's greedy count.)
+//
+// k_error_counts: the grid and the decode of k_event_counts, both sides of all the clip's classes staged in LDS as in
+// k_psds_counts.  Then the labels are dropped:
+//   event-based: thread (class c, lane i) owns estimated event i and reference event i of class c and ranks each among ALL the
+//     clip's events of its side by (onset, class, index) - a count over broadcast LDS reads, no assumption about the order
+//     inside a column - and writes it to its rank in the merged lists (they take the place of the decode buffers).  Wave w
+//     then owns the merged references 64 w .. 64 w + 63: sc_match_tile, the code k_ls_match runs on a long column.
+//     Nany = the sum over the waves.  A merged cluster beyond 64 per side raises bit 1 / 2; the clip is then not scored.
+//   segment-based: one thread per segment; the events' segment ranges (ints, in place of the staged seconds) give a 16-bit
+//     mask of active classes per side, and sc_segment_sdi the segment's part of (S, D, I).
+// The workgroup's sums are integer LDS atomics, the totals integer global atomics: bit-reproducible.
+struct ErArgs {
+    ScArgs s;
+    double t_collar, pct, res;
+    int32_t *ev_overall, *seg_overall; unsigned long long *ev_total, *seg_total; int32_t* err;
+    int tpad;                        // bytes of one raw / flt buffer, at least ER_TPAD: two of them per class hold the merged lists
+};
+#define ER_HEAD 256                  // int32: [0, 16) n_est, [16, 32) n_ref per class, then file segments, flags, Nany, S, D, I
+#define ER_TPAD (SC_MAXEV * 16)      // per class 64 events x (onset, offset) x 2 sides of fp64 = 2 * ER_TPAD bytes
+
+__device__ __forceinline__ int wave_isum(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// the number of events (c2, i2) of x[NC][64] (n[c2] of them in class c2) in front of event (c, i) with onset `on`, by
+// (onset, class, index)
+__device__ __forceinline__ int er_rank(const double* x, const int* n, int NC, double on, int c, int i) {
+    int rank = 0;
+    for (int c2 = 0; c2 < NC; ++c2) {
+        const int n2 = n[c2];
+        for (int i2 = 0; i2 < n2; ++i2) {
+            const double o = x[c2 * SC_MAXEV + i2];
+            rank += o < on || (o == on && (c2 < c || (c2 == c && i2 < i)));
+        }
+    }
+    return rank;
+}
+
+__global__ __launch_bounds__(1024) void k_error_counts(ErArgs a) {
+    extern __shared__ __align__(16) uint8_t smem[];
+    const int NC = a.s.NC, n = blockIdx.x, k = blockIdx.y, N = gridDim.x;
+    const int tid = threadIdx.x, c = tid >> 6, lane = tid & 63;
+    double* ev = (double*)smem;                                     // [4][NC][64]: estimated onsets, offsets, reference onsets, offsets
+    int* hd = (int*)(smem + (size_t)NC * SC_MAXEV * 32);
+    int *s_nest = hd, *s_nref = hd + SC_MAXNC, *s_acc = hd + 2 * SC_MAXNC;      // s_acc: file segments, flags, Nany, S, D, I
+    uint8_t* dec = smem + (size_t)NC * SC_MAXEV * 32 + ER_HEAD;
+    if (tid < 6) s_acc[tid] = 0;
+    const ScColumn col = sc_stage_column(a.s, a.tpad, dec, ev + c * SC_MAXEV, ev + (NC + c) * SC_MAXEV);
+    const int n_est = col.n_est, n_ref = col.n_ref;
+    if (lane < n_ref && n_ref <= SC_MAXEV) {
+        ev[(2 * NC + c) * SC_MAXEV + lane] = a.s.ref_on[col.r0 + lane];
+        ev[(3 * NC + c) * SC_MAXEV + lane] = a.s.ref_off[col.r0 + lane];
+    }
+    if (lane == 0) {
+        s_nest[c] = max(n_est, 0);
+        s_nref[c] = max(n_ref, 0);
+        if (col.flags) atomicOr(a.err, col.flags);
+    }
+    const bool bad_column = __syncthreads_or(col.flags != 0);       // (the barrier that publishes the staged events)
+    int n_sys = 0, n_all_ref = 0;
+    for (int c2 = 0; c2 < NC; ++c2) {
+        n_sys += s_nest[c2];
+        n_all_ref += s_nref[c2];
+    }
+    if (!bad_column) {                                              // every column holds 0 .. 64 events per side
+        const bool has_est = lane < n_est, has_ref = lane < n_ref;
+        double e_on = 0.0, e_off = 0.0, r_on = 0.0, r_off = 0.0;
+        if (has_est) {
+            e_on = ev[c * SC_MAXEV + lane];
+            e_off = ev[(NC + c) * SC_MAXEV + lane];
+        }
+        if (has_ref) {
+            r_on = ev[(2 * NC + c) * SC_MAXEV + lane];
+            r_off = ev[(3 * NC + c) * SC_MAXEV + lane];
+        }
+        // ---- merge by onset: the decode buffers are dead, the merged lists take their place --------------------------------
+        const int cap = NC * SC_MAXEV;
+        double* m_ron = (double*)dec;                               // [cap] each
+        double *m_roff = m_ron + cap, *m_eon = m_ron + 2 * cap, *m_eoff = m_ron + 3 * cap;
+        if (has_est) {
+            const int at = er_rank(ev, s_nest, NC, e_on, c, lane);
+            m_eon[at] = e_on;
+            m_eoff[at] = e_off;
+        }
+        if (has_ref) {
+            const int at = er_rank(ev + 2 * NC * SC_MAXEV, s_nref, NC, r_on, c, lane);
+            m_ron[at] = r_on;
+            m_roff[at] = r_off;
+        }
+        int rlo = 0, rhi = 0, elo = 0, ehi = 0;
+        if (has_ref) {
+            rlo = sc_seg_index(floor(r_on / a.res));
+            rhi = sc_seg_index(ceil(r_off / a.res));
+        }
+        if (has_est) {
+            elo = sc_seg_index(floor(e_on / a.res));
+            ehi = sc_seg_index(ceil(e_off / a.res));
+        }
+        const int col_seg = wave_imax(max(rhi, ehi));
+        if (lane == 0 && col_seg > 0) atomicMax(&s_acc[0], col_seg);
+        __syncthreads();                                            // the merged lists are complete, the staged seconds are dead
+        int* sg = (int*)smem;                                       // [4][NC][64]: estimated first / end segment, reference first / end
+        sg[c * SC_MAXEV + lane] = elo;
+        sg[(NC + c) * SC_MAXEV + lane] = ehi;
+        sg[(2 * NC + c) * SC_MAXEV + lane] = rlo;
+        sg[(3 * NC + c) * SC_MAXEV + lane] = rhi;
+        // ---- event-based: wave c owns the merged references 64 c .. 64 c + 63 ----------------------------------------------
+        if (c * SC_MAXEV < n_all_ref) {                             // wave-uniform
+            int flags = 0;
+            const int got = sc_match_tile(m_ron, m_roff, n_all_ref, m_eon, m_eoff, n_sys, c * SC_MAXEV, a.t_collar, a.pct, lane,
+                                          flags);
+            if (lane == 0) {
+                if (got > 0) atomicAdd(&s_acc[2], got);
+                if (flags) atomicOr(&s_acc[1], flags);
+            }
+        }
+        __syncthreads();
+        // ---- segment-based: one thread per segment ---------------------------------------------------------------------------
+        const int file_seg = s_acc[0];
+        if (file_seg > SC_MAXSEG) {
+            if (tid == 0) s_acc[1] |= SC_ERR_SEGMENTS;
+        } else {
+            int S = 0, D = 0, I = 0;
+            for (int s = tid; s < file_seg; s += NC * 64) {
+                unsigned ref_mask = 0, est_mask = 0;
+                for (int c2 = 0; c2 < NC; ++c2) {
+                    bool ea = false, ra = false;
+                    for (int e = 0; e < s_nest[c2]; ++e) ea |= s >= sg[c2 * SC_MAXEV + e] && s < sg[(NC + c2) * SC_MAXEV + e];
+                    for (int r = 0; r < s_nref[c2]; ++r)
+                        ra |= s >= sg[(2 * NC + c2) * SC_MAXEV + r] && s < sg[(3 * NC + c2) * SC_MAXEV + r];
+                    est_mask |= (unsigned)ea << c2;
+                    ref_mask |= (unsigned)ra << c2;
+                }
+                sc_segment_sdi(ref_mask, est_mask, S, D, I);
+            }
+            S = wave_isum(S); D = wave_isum(D); I = wave_isum(I);
+            if (lane == 0) {
+                if (S) atomicAdd(&s_acc[3], S);
+                if (D) atomicAdd(&s_acc[4], D);
+                if (I) atomicAdd(&s_acc[5], I);
+            }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const int flags = bad_column ? 0 : s_acc[1];                // (a column's own bits went to err above)
+        const bool ok = !bad_column && flags == 0;
+        const size_t o = (size_t)k * N + n;
+        const int evo[3] = {n_all_ref, n_sys, ok ? s_acc[2] : 0};
+        const int sgo[3] = {ok ? s_acc[3] : 0, ok ? s_acc[4] : 0, ok ? s_acc[5] : 0};
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            if (a.ev_overall) a.ev_overall[o * 3 + i] = evo[i];
+            if (evo[i] > 0) atomicAdd(a.ev_total + (size_t)k * 3 + i, (unsigned long long)evo[i]);
+            if (a.seg_overall) a.seg_overall[o * 3 + i] = sgo[i];
+            if (sgo[i] > 0) atomicAdd(a.seg_total + (size_t)k * 3 + i, (unsigned long long)sgo[i]);
+        }
+        if (flags) atomicOr(a.err, flags);
+    }
+}
+
 // one wave per (threshold set, class): intermediate_at_measures (evaluation_measures.py:86-102) over all clips
 __global__ __launch_bounds__(64) void k_weak_counts(const float* __restrict__ weak, const uint8_t* __restrict__ labels,
                                                     const float* __restrict__ thr, int N, int NC,
@@ -302,16 +468,16 @@ static int sc_tpad(const float* strong, int T) { return strong ? (T + 1 + 15) / 
 
 // One workgroup per (clip, operating point), one wave per class; SLOT = bytes of LDS per event slot in front of SC_HEAD and
 // the decode buffers.  A template on the kernel: each kernel has its own once-flag for its own raised LDS limit.
-template <class Args, void (*KERNEL)(Args), int SLOT>
+template <class Args, void (*KERNEL)(Args), int SLOT, int HEAD = SC_HEAD>
 static int sc_launch(const Args& a, int n_clips, int n_points, void* stream) {
     const int nclass = a.s.NC;
-    const size_t lds = (size_t)nclass * SC_MAXEV * SLOT + SC_HEAD + (size_t)nclass * 2 * a.tpad;
+    const size_t lds = (size_t)nclass * SC_MAXEV * SLOT + HEAD + (size_t)nclass * 2 * a.tpad;
     if (lds > 64 * 1024) {           // long clips with many classes only: at 16 classes x 2048 frames k_event_counts needs 82 KB
                                      // and k_psds_counts (32 KB of events + 65 KB of decode buffers) 97 KB of the CU's 160 KB
         static thread_local SedAttrOnce once;
         if (once.need())
             SED_CHECK_HIP(hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                              SC_MAXNC * SC_MAXEV * SLOT + SC_HEAD + SC_MAXNC * 2 * ((PP_MAXT + 16) / 16 * 16)));
+                                              SC_MAXNC * SC_MAXEV * SLOT + HEAD + SC_MAXNC * 2 * ((PP_MAXT + 16) / 16 * 16)));
     }
     KERNEL<<<dim3(n_clips, n_points), nclass * 64, lds, (hipStream_t)stream>>>(a);
     SED_CHECK_LAUNCH();
@@ -334,6 +500,25 @@ extern "C" int sed_event_counts(const float* strong, int n_clips, int T, int ncl
     a.ev_total = (unsigned long long*)ev_total; a.seg_total = (unsigned long long*)seg_total; a.err = err;
     a.tpad = sc_tpad(strong, T);
     return sc_launch<EvArgs, k_event_counts, 16>(a, n_clips, n_points, stream);
+}
+
+extern "C" int sed_error_counts(const float* strong, int n_clips, int T, int nclass, int n_points, const float* thr,
+                                const int32_t* win, double num, double den, const int32_t* est_ptr, const double* est_on,
+                                const double* est_off, const int32_t* ref_ptr, const double* ref_on, const double* ref_off,
+                                double t_collar, double percentage_of_length, double time_resolution, int32_t* ev_overall,
+                                int32_t* seg_overall, int64_t* ev_overall_total, int64_t* seg_overall_total, int32_t* err,
+                                void* stream) {
+    SED_CHECK_ARG(ev_overall_total && seg_overall_total && err, "sed_error_counts: null argument");
+    SED_CHECK_ARG(t_collar >= 0.0 && percentage_of_length >= 0.0 && time_resolution > 0.0,
+                  "sed_error_counts: need t_collar >= 0, percentage_of_length >= 0, time_resolution > 0");
+    ErArgs a;
+    SED_TRY(sc_fill(a.s, "sed_error_counts", strong, n_clips, T, nclass, n_points, thr, win, num, den, est_ptr, est_on,
+                    est_off, ref_ptr, ref_on, ref_off));
+    a.t_collar = t_collar; a.pct = percentage_of_length; a.res = time_resolution;
+    a.ev_overall = ev_overall; a.seg_overall = seg_overall;
+    a.ev_total = (unsigned long long*)ev_overall_total; a.seg_total = (unsigned long long*)seg_overall_total; a.err = err;
+    a.tpad = sc_tpad(strong, T) > ER_TPAD ? sc_tpad(strong, T) : ER_TPAD;
+    return sc_launch<ErArgs, k_error_counts, 32, ER_HEAD>(a, n_clips, n_points, stream);
 }
 
 extern "C" int sed_psds_counts(const float* strong, int n_clips, int T, int nclass, int n_points, const float* thr,

@@ -24,8 +24,25 @@ Definitions (per file and class; label equality is the column):
   over the summed counts; class-wise ``ER = (Nfn + Nfp) / Nref``.
 
 Limits: at most 64 reference and 64 estimated events per (file, class) - a column beyond that raises, it is never
-truncated -, ``T <= 2048`` output frames, at most 16 classes.  The overall error rate *with substitutions* needs a second,
-label-agnostic matching and is **not provided**: ``results_overall_metrics()['error_rate']`` holds NaN.
+truncated -, ``T <= 2048`` output frames, at most 16 classes.
+
+Overall error rate *with substitutions* (``error_counts``, ``long_error_counts``, ``long_sweep_error_counts`` and their
+``*_from_events`` forms -> ``ErrorCounts``; ``error_rate=True`` of ``validate`` / ``validate_long`` /
+``compute_strong_metrics``; ``EventMetrics`` / ``SegmentMetrics(overall=...)``).  It needs a second, label-agnostic pass
+over each file, which the default paths do not launch: without it ``results_overall_metrics()['error_rate']`` holds NaN.
+
+* segment-based (sed_eval's, exactly): per segment ``fn_s`` / ``fp_s`` = the classes active only in the reference / only in
+  the estimate; ``S += min(fn_s, fp_s)``, ``D += max(0, fn_s - fp_s)``, ``I += max(0, fp_s - fn_s)``;
+  ``ER = (S + D + I) / Nref``, ``Nref = sum_c (Ntp_c + Nfn_c)``.  ``S + D = sum_c Nfn_c`` and ``S + I = sum_c Nfp_c``.
+* event-based: ``Nany`` = the size of a maximum bipartite matching over ALL events of the file under the compatibility test
+  with the label ignored; ``Nsubs = Nany - Ntp``, ``Nfn = Nref - Nany``, ``Nfp = Nsys - Nany``,
+  ``ER = (Nsubs + Nfn + Nfp) / Nref``; ``Ntp <= Nany <= min(Nref, Nsys)``.  A decision: sed_eval finds substitutions by a
+  greedy pass over what its label-wise matching left over, a count that depends on the list order and on which maximum
+  matching its matcher returned - not a function of the two event sets, so it cannot be pinned.  That pass is itself a
+  time-compatible matching: sed_eval's ``Nsubs`` is never larger than this one and its ER never smaller; they agree
+  whenever the greedy pass is maximum.  Pinned: exact agreement with ``tests/error_rate_np.py``.
+* limit: at most 64 events per side in one CLUSTER of the file's events of all classes merged by onset (clips and long
+  recordings alike); beyond that the call raises, nothing is truncated.
 
 Long recordings (``long_event_counts``, ``long_psds_counts``, ``validate_long``, ``long_*_from_events``): the same definitions
 on the event table ``inference.stitch_decode`` leaves on the device, or on two ``RefEvents``, WITHOUT the limit per column
@@ -35,8 +52,9 @@ pair can be compatible (include/dcase_sed.h) -, and a cluster holds at most 64 e
 nothing is truncated.  K operating points: ``long_sweep_event_counts`` / ``long_sweep_psds_counts`` score the table of
 ``inference.stitch_sweep`` (or K ``RefEvents``) against ONE preparation of the reference side, four launches whatever K is
 (``sed_long_sweep_*``); ``validate_long(one_blend=True)`` uses them.  Recording-level weak tags: ``validate_long(weak_labels=...)``
-pools them once (``inference.stitch_weak``) and scores them with ``weak_counts``.  Not provided there: an exact matching of
-clusters beyond 64 per side.
+pools them once (``inference.stitch_weak``) and scores them with ``weak_counts``.  The overall error rate:
+``validate_long(error_rate=True)`` (``sed_long_error_counts`` / ``sed_long_sweep_error_counts``, six launches whatever K is, the
+reference side merged once).  Not provided there: an exact matching of clusters beyond 64 per side.
 
 PSDS (polyphonic sound detection score, Bilen et al., ICASSP 2020): ``sed_psds_counts`` scores the same (operating point,
 clip) grid with the three intersection criteria and returns integer class totals (``psds_counts``, ``PSDSCounts``); the
@@ -82,6 +100,14 @@ _LONG_ERR_BITS = {1: "a cluster of more than 64 reference events whose onsets ch
                   16: "malformed event offsets",
                   64: "a column whose onsets decrease (both sides must be sorted by onset)",
                   128: "the decoded event table is invalid (sed_stitch_decode reported an error)"}
+
+# the overall-error-rate calls: the matching runs on the file's events of ALL classes merged by onset
+_ERROR_ERR_BITS = {**_ERR_BITS,
+                   1: "more than 64 reference events in a (file, class) column or in one cluster of the file's merged events",
+                   2: "more than 64 estimated events in a (file, class) column or in one cluster of the file's merged events"}
+_LONG_ERROR_ERR_BITS = {**_LONG_ERR_BITS,
+                        1: "a cluster of more than 64 reference events, all classes merged, whose onsets chain within t_collar",
+                        2: "a cluster of more than 64 estimated events, all classes merged, whose onsets chain within t_collar"}
 
 
 def _pack(df, filenames, labels):
@@ -222,6 +248,34 @@ class PSDSCounts(_DeviceCounts):
         return self._totals_to_host().reshape(self.K, self.NC, 2 + self.NC)
 
 
+class ErrorCounts(_DeviceCounts):
+    """Totals of one or more ``error_counts`` calls, on the device: ``ev [K, 3]`` (Nref, Nsys, Nany) and ``seg [K, 3]``
+    (S, D, I) int64 per operating point - the counts of the OVERALL error rate (module docstring) -, and the error word, in
+    ONE buffer so that ``host()`` is one copy.  ``ev_files [K, N, 3]`` / ``seg_files [K, N, 3]`` int32 hold the last call's
+    per-file counts when it was asked for them."""
+
+    def __init__(self, n_points, nclass, device):
+        _DeviceCounts.__init__(self, n_points, 1, 6, device, "sed_error_counts")
+        self.NC = nclass
+        self.err_bits = _ERROR_ERR_BITS
+        self.ev = self.buf[:n_points * 3].view(n_points, 3)
+        self.seg = self.buf[n_points * 3:-1].view(n_points, 3)
+        self.ev_files = self.seg_files = None
+
+    def parse(self, h):
+        """(ev, seg) from a host copy of ``buf`` (int64 numpy, the error word last); raises when the word is set."""
+        h = np.asarray(h, np.int64)
+        err = int(h[-1:].view(np.int32)[0])
+        if err:
+            raise _lib.SedError(self.err_what + ": " + "; ".join(m for b, m in self.err_bits.items() if err & b)
+                                + " - nothing was truncated, the counts are invalid")
+        return h[:self.K * 3].reshape(self.K, 3), h[self.K * 3:-1].reshape(self.K, 3)
+
+    def host(self):
+        """(ev, seg) as numpy arrays - one device -> host copy; raises when a file was over a limit."""
+        return self.parse(self.buf.cpu().numpy())
+
+
 def operating_points(thresholds=(0.5,), median_windows=(5,), device="cuda"):
     """K operating points as device arrays ``(thr [K] float32, win [K] int32)``: sequences of equal length, or one of them of
     length 1.  Build them once outside a loop or a graph capture."""
@@ -335,6 +389,38 @@ def psds_counts_from_events(est, ref, dtc=0.5, gtc=0.5, cttc=0.3, per_column=Fal
     return _psds_target(_given_args(est, ref, "psds_counts_from_events"), dtc, gtc, cttc, None, per_column)
 
 
+def _error_target(est, t_collar, percentage_of_length, time_resolution, counts, per_file):
+    args, n, K, NC, device, _ = est
+    if counts is None:
+        counts = ErrorCounts(K, NC, device)
+    if (counts.K, counts.NC) != (K, NC):
+        raise ValueError("counts was built for another number of operating points / classes")
+    if per_file:
+        counts.ev_files = torch.empty(K, n, 3, dtype=torch.int32, device=device)
+        counts.seg_files = torch.empty(K, n, 3, dtype=torch.int32, device=device)
+    _lib.check(_lib.lib().sed_error_counts(
+        *args, float(t_collar), float(percentage_of_length), float(time_resolution),
+        _lib.ptr(counts.ev_files) if per_file else None, _lib.ptr(counts.seg_files) if per_file else None,
+        _lib.ptr(counts.ev), _lib.ptr(counts.seg), _lib.ptr(counts.err), _lib.stream_ptr()), "sed_error_counts")
+    return counts
+
+
+def error_counts(strong, ref, thresholds=(0.5,), median_windows=(5,), pooling_time_ratio=1, cfg=None, t_collar=0.200,
+                 percentage_of_length=0.2, time_resolution=1.0, clip_offset=0, counts=None, per_file=False):
+    """``event_counts`` for the OVERALL error rate: the same posteriors, operating points and seconds -> ``ErrorCounts``
+    (device tensors, no synchronisation; pass ``counts`` to accumulate batches).  ``per_file``: ``counts.ev_files /
+    seg_files [K, n, 3]`` of this call."""
+    est = _posterior_args(strong, ref, thresholds, median_windows, pooling_time_ratio, cfg, clip_offset, "error_counts")
+    return _error_target(est, t_collar, percentage_of_length, time_resolution, counts, per_file)
+
+
+def error_counts_from_events(est, ref, t_collar=0.200, percentage_of_length=0.2, time_resolution=1.0, per_file=False):
+    """The scoring stage alone: ``est`` is a ``RefEvents`` holding the ESTIMATED events of the same files and classes.  One
+    operating point."""
+    return _error_target(_given_args(est, ref, "error_counts_from_events"), t_collar, percentage_of_length, time_resolution,
+                         None, per_file)
+
+
 def weak_counts(weak, labels, thresholds, counts=None):
     """``weak [n, nclass]`` cuda float32, ``labels [n, nclass]`` 0/1, ``thresholds [K, nclass]`` (or ``[nclass]``) ->
     ``[K, nclass, 4]`` int64 (tp, fp, fn, tn) with ``pred = weak > thr`` (intermediate_at_measures,
@@ -413,13 +499,23 @@ class _Metrics:
                 for g, keys in (("f_measure", ("f_measure", "precision", "recall")),
                                 ("error_rate", ("error_rate", "deletion_rate", "insertion_rate")))}
 
+    overall_sdi = None               # (Nsubs, Nfn, Nfp) of the overall error rate, when the object was given ``overall=``
+
+    def _totals(self):
+        return {k: sum(c[k] for c in self.class_wise.values()) for k in ("Ntp", "Nref", "Nsys", "Nfp", "Nfn")}
+
     def results_overall_metrics(self):
         """Micro-averaged F-measure over the summed counts.  The overall error rate of sed_eval counts substitutions, which
-        needs a second, label-agnostic matching: it is NOT computed - the four error-rate keys hold NaN."""
-        tot = {k: sum(c[k] for c in self.class_wise.values()) for k in ("Ntp", "Nref", "Nsys", "Nfp", "Nfn")}
+        needs a second, label-agnostic matching (``error_counts`` and its long forms): built with ``overall=`` its totals,
+        the four error-rate keys hold ``(S + D + I) / Nref`` and its three parts, NaN when ``Nref == 0``; without, NaN."""
+        tot = self._totals()
         nan = float("nan")
-        return {"f_measure": self._scores(tot)["f_measure"],
-                "error_rate": {"error_rate": nan, "substitution_rate": nan, "deletion_rate": nan, "insertion_rate": nan}}
+        er = {"error_rate": nan, "substitution_rate": nan, "deletion_rate": nan, "insertion_rate": nan}
+        if self.overall_sdi is not None:
+            s, d, i = self.overall_sdi
+            er = {"error_rate": _ratio(s + d + i, tot["Nref"], nan), "substitution_rate": _ratio(s, tot["Nref"], nan),
+                  "deletion_rate": _ratio(d, tot["Nref"], nan), "insertion_rate": _ratio(i, tot["Nref"], nan)}
+        return {"f_measure": self._scores(tot)["f_measure"], "error_rate": er}
 
     def results(self):
         return {"overall": self.results_overall_metrics(), "class_wise": self.results_class_wise_metrics(),
@@ -429,8 +525,12 @@ class _Metrics:
         ov, av = self.results_overall_metrics()["f_measure"], self.results_class_wise_average_metrics()
         lines = [f"{self.name} metrics ({self._params()})",
                  "  Overall (micro-average): F {:6.2f} %  P {:6.2f} %  R {:6.2f} %".format(
-                     100 * ov["f_measure"], 100 * ov["precision"], 100 * ov["recall"]),
-                 "  Class-wise average (macro-average): F {:6.2f} %  P {:6.2f} %  R {:6.2f} %  ER {:5.2f}".format(
+                     100 * ov["f_measure"], 100 * ov["precision"], 100 * ov["recall"])]
+        if self.overall_sdi is not None:
+            er = self.results_overall_metrics()["error_rate"]
+            lines.append("  Overall error rate: ER {:5.2f}  S {:5.2f}  D {:5.2f}  I {:5.2f}".format(
+                er["error_rate"], er["substitution_rate"], er["deletion_rate"], er["insertion_rate"]))
+        lines += ["  Class-wise average (macro-average): F {:6.2f} %  P {:6.2f} %  R {:6.2f} %  ER {:5.2f}".format(
                      100 * av["f_measure"]["f_measure"], 100 * av["f_measure"]["precision"], 100 * av["f_measure"]["recall"],
                      av["error_rate"]["error_rate"]),
                  "  {:30s} {:>6s} {:>6s} {:>8s} {:>8s} {:>8s} {:>6s}".format("Event label", "Nref", "Nsys", "F", "Pre", "Rec", "ER")]
@@ -447,10 +547,19 @@ class EventMetrics(_Metrics):
     reports to main.py and its logs (``Nfp = Nsys - Ntp``, ``Nfn = Nref - Ntp``)."""
     name = "Event based"
 
-    def __init__(self, labels, counts, t_collar=0.200, percentage_of_length=0.2):
+    def __init__(self, labels, counts, t_collar=0.200, percentage_of_length=0.2, overall=None):
         c = np.asarray(counts, np.int64).reshape(-1, 3)
         self.t_collar, self.percentage_of_length = t_collar, percentage_of_length
         super().__init__(labels, c[:, 0], c[:, 1], c[:, 2], c[:, 2] - c[:, 0], c[:, 1] - c[:, 0])
+        if overall is not None:
+            # (Nref, Nsys, Nany) of the same files, ``ErrorCounts.host()[0][k]``: Nany = size of a maximum matching with the
+            # labels ignored, so Nsubs = Nany - Ntp, Nfn = Nref - Nany, Nfp = Nsys - Nany
+            nref, nsys, nany = (int(v) for v in np.asarray(overall, np.int64).reshape(3))
+            tot = self._totals()
+            if (nref, nsys) != (tot["Nref"], tot["Nsys"]) or not tot["Ntp"] <= nany <= min(nref, nsys):
+                raise ValueError(f"overall (Nref, Nsys, Nany) = {(nref, nsys, nany)} does not belong to these class counts "
+                                 f"(Nref {tot['Nref']}, Nsys {tot['Nsys']}, Ntp {tot['Ntp']})")
+            self.overall_sdi = (nany - tot["Ntp"], nref - nany, nsys - nany)
 
     def _params(self):
         return f"onset-offset, t_collar {self.t_collar:.2f} s, offset (length) {100 * self.percentage_of_length:.0f} %"
@@ -461,11 +570,19 @@ class SegmentMetrics(_Metrics):
     (``Nref = Ntp + Nfn``, ``Nsys = Ntp + Nfp``)."""
     name = "Segment based"
 
-    def __init__(self, labels, counts, time_resolution=1.0):
+    def __init__(self, labels, counts, time_resolution=1.0, overall=None):
         c = np.asarray(counts, np.int64).reshape(-1, 4)
         self.time_resolution = time_resolution
         self.Ntn = {l: int(v) for l, v in zip(labels, c[:, 3])}
         super().__init__(labels, c[:, 0], c[:, 0] + c[:, 2], c[:, 0] + c[:, 1], c[:, 1], c[:, 2])
+        if overall is not None:
+            # (S, D, I) of the same files, ``ErrorCounts.host()[1][k]``: S + D = sum Nfn, S + I = sum Nfp
+            s_, d_, i_ = (int(v) for v in np.asarray(overall, np.int64).reshape(3))
+            tot = self._totals()
+            if min(s_, d_, i_) < 0 or s_ + d_ != tot["Nfn"] or s_ + i_ != tot["Nfp"]:
+                raise ValueError(f"overall (S, D, I) = {(s_, d_, i_)} does not belong to these class counts "
+                                 f"(Nfn {tot['Nfn']}, Nfp {tot['Nfp']})")
+            self.overall_sdi = (s_, d_, i_)
 
     def _params(self):
         return f"time resolution {self.time_resolution:.2f} s"
@@ -555,10 +672,11 @@ class PSDS:
 
 
 # ---- drop-ins with the reference's signatures -------------------------------------------------------------------------------
-def compute_strong_metrics(predictions, valid_df, pooling_time_ratio=None, cfg=None, device="cuda"):
+def compute_strong_metrics(predictions, valid_df, pooling_time_ratio=None, cfg=None, device="cuda", error_rate=False):
     """Drop-in for evaluation_measures.compute_strong_metrics (lines 234-246): event tables in, the event-based metric out,
     both metrics logged.  The two tables are packed and matched by ``sed_event_counts`` (given-events mode): the device
-    matcher serves this route too.  Files = ``valid_df.filename.unique()``, classes = the labels of both tables."""
+    matcher serves this route too.  Files = ``valid_df.filename.unique()``, classes = the labels of both tables.
+    ``error_rate=True``: one ``sed_error_counts`` call more, and both metrics carry the overall error rate."""
     cfg = cfg or _Cfg
     if pooling_time_ratio is not None:
         LOG.warning("pooling_time_ratio is deprecated, use it in get_predictions() instead.")
@@ -569,7 +687,8 @@ def compute_strong_metrics(predictions, valid_df, pooling_time_ratio=None, cfg=N
     ref = RefEvents.from_dataframe(valid_df, files, labels, device)
     est = RefEvents.from_dataframe(predictions, files, labels, device)
     ev, seg = event_counts_from_events(est, ref).host()
-    metric_event, metric_segment = EventMetrics(labels, ev[0]), SegmentMetrics(labels, seg[0])
+    ev_o, seg_o = error_counts_from_events(est, ref).host() if error_rate else ([None], [None])
+    metric_event, metric_segment = EventMetrics(labels, ev[0], overall=ev_o[0]), SegmentMetrics(labels, seg[0], overall=seg_o[0])
     LOG.info(metric_event)
     LOG.info(metric_segment)
     return metric_event
@@ -601,14 +720,23 @@ def get_f_measure_by_class(torch_model, nb_tags, dataloader_, thresholds_=None):
     return f_measure_from_counts(counts.cpu().numpy()[0])
 
 
+def _metric_pairs(labels, ev, seg, overall=None):
+    """One ``(EventMetrics, SegmentMetrics)`` per operating point; ``overall``: ``ErrorCounts.host()`` of the same points."""
+    ev_o, seg_o = overall if overall is not None else ([None] * len(ev), [None] * len(ev))
+    return [(EventMetrics(labels, ev[k], overall=ev_o[k]), SegmentMetrics(labels, seg[k], overall=seg_o[k]))
+            for k in range(len(ev))]
+
+
 def validate(model, dataset, ref, pooling_time_ratio, thresholds=(0.5,), median_windows=(5,), batch_size=64, cfg=None,
-             psds=None):
+             psds=None, error_rate=False):
     """The fused route for the epoch loop (main.py:324-328 without the event table): ``dataset`` as
     ``inference.get_predictions`` accepts it, forward ``batch_size`` clips at a time, ``sed_event_counts`` per batch into
     running totals, ONE device -> host copy at the end.  ``ref``: the ``RefEvents`` of the same clips in the same order.
     Returns one ``(EventMetrics, SegmentMetrics)`` per operating point.  ``psds``: a ``PSDSCounts`` of the same operating
     points; every batch's posteriors then also go through ``sed_psds_counts`` into it (same forward, same operating-point
-    tensors; read it with ``PSDS.from_counts``)."""
+    tensors; read it with ``PSDS.from_counts``).  ``error_rate=True``: every batch also goes through ``sed_error_counts``, and
+    the metrics carry the overall error rate (``results_overall_metrics()["error_rate"]``); still one copy at the end.  The
+    default issues no launch more than before."""
     from .resident import ResidentFeatureSet
     if not getattr(model, "hot_path", False):
         raise _lib.SedError("validate needs a CRNN on the HIP hot path")
@@ -621,6 +749,7 @@ def validate(model, dataset, ref, pooling_time_ratio, thresholds=(0.5,), median_
         raise ValueError(f"{len(dataset)} clips but reference events of {len(ref)}")
     thr, win = operating_points(thresholds, median_windows, dev)
     counts = Counts(thr.numel(), ref.nclass, dev)
+    errors = ErrorCounts(thr.numel(), ref.nclass, dev) if error_rate else None
     if psds is not None and (psds.K, psds.NC) != (counts.K, counts.NC):
         raise ValueError("psds was built for another number of operating points / classes")
     was_training = model.training
@@ -633,10 +762,15 @@ def validate(model, dataset, ref, pooling_time_ratio, thresholds=(0.5,), median_
                 if psds is not None:
                     psds_counts(strong, ref, thr, win, pooling_time_ratio, cfg, psds.dtc, psds.gtc, psds.cttc, clip_offset=i0,
                                 counts=psds)
+                if errors is not None:
+                    error_counts(strong, ref, thr, win, pooling_time_ratio, cfg, clip_offset=i0, counts=errors)
     finally:
         model.train(was_training)
-    ev, seg = counts.host()
-    return [(EventMetrics(ref.labels, ev[k]), SegmentMetrics(ref.labels, seg[k])) for k in range(thr.numel())]
+    if errors is None:
+        ev, seg = counts.host()
+        return _metric_pairs(ref.labels, ev, seg)
+    ev, seg, tail = counts.host(errors.buf)
+    return _metric_pairs(ref.labels, ev, seg, errors.parse(tail))
 
 
 # ---- long recordings: the event table of sed_stitch_decode / sed_stitch_sweep (or given events) of any length ------------------
@@ -742,6 +876,64 @@ def _long_psds_target(sweep, est_args, est_cap, K, ref, dtc, gtc, cttc, counts, 
     return counts
 
 
+def _long_error_target(sweep, est_args, est_cap, K, ref, t_collar, percentage_of_length, time_resolution, counts, point0,
+                       per_file):
+    n, NC, dev = len(ref), ref.nclass, ref.device
+    fn, ws_fn, lead = (("sed_long_sweep_error_counts", "sed_long_sweep_error_ws_bytes", (K,)) if sweep
+                       else ("sed_long_error_counts", "sed_long_error_ws_bytes", ()))
+    if counts is None:
+        counts = ErrorCounts(point0 + K, NC, dev)
+    _long_rows(counts, K, NC, point0, fn)
+    counts.err_bits = _LONG_ERROR_ERR_BITS
+    if per_file:
+        counts.ev_files = torch.empty(*lead, n, 3, dtype=torch.int32, device=dev)
+        counts.seg_files = torch.empty(*lead, n, 3, dtype=torch.int32, device=dev)
+    _long_counts_call(fn, ws_fn, lead, est_args, est_cap, ref,
+                      (float(t_collar), float(percentage_of_length), float(time_resolution),
+                       _lib.ptr(counts.ev_files) if per_file else None, _lib.ptr(counts.seg_files) if per_file else None,
+                       _lib.ptr(counts.ev[point0]), _lib.ptr(counts.seg[point0])), counts.err)
+    return counts
+
+
+def long_error_counts(decoded, ref, pooling_time_ratio, cfg=None, t_collar=0.200, percentage_of_length=0.2, time_resolution=1.0,
+                      counts=None, point=0, per_file=False):
+    """``long_event_counts`` for the OVERALL error rate: the totals ACCUMULATE into row ``point`` of an ``ErrorCounts``
+    (None: a new one of ``point + 1`` rows); ``per_file``: ``counts.ev_files / seg_files [n_rec, 3]`` of this call.  The
+    limit of 64 events per side holds per cluster of the recording's events of ALL classes merged by onset."""
+    est_args, cap, _ = _decoded_args(decoded, ref, pooling_time_ratio, cfg, "long_error_counts", K=1)
+    counts = _long_error_target(False, est_args, cap, 1, ref, t_collar, percentage_of_length, time_resolution, counts, point,
+                                per_file)
+    _fold_decode_err(counts, decoded)
+    return counts
+
+
+def long_error_from_events(est, ref, t_collar=0.200, percentage_of_length=0.2, time_resolution=1.0, counts=None, point=0,
+                           per_file=False):
+    """The scoring stage alone on two ``RefEvents`` (both sorted by onset inside a column)."""
+    est_args, cap, _ = _events_args([est], ref, "long_error_from_events")
+    return _long_error_target(False, est_args, cap, 1, ref, t_collar, percentage_of_length, time_resolution, counts, point,
+                              per_file)
+
+
+def long_sweep_error_counts(decoded, ref, pooling_time_ratio, cfg=None, t_collar=0.200, percentage_of_length=0.2,
+                            time_resolution=1.0, counts=None, point0=0, per_file=False):
+    """``long_error_counts`` for the K operating points ``inference.stitch_sweep`` decoded: ONE ``sed_long_sweep_error_counts``
+    call into rows ``point0 .. point0 + K - 1``, the reference side validated and merged once; ``per_file``: ``[K, n_rec, 3]``."""
+    est_args, cap, K = _decoded_args(decoded, ref, pooling_time_ratio, cfg, "long_sweep_error_counts")
+    counts = _long_error_target(True, est_args, cap, K, ref, t_collar, percentage_of_length, time_resolution, counts, point0,
+                                per_file)
+    _fold_decode_err(counts, decoded)
+    return counts
+
+
+def long_sweep_error_from_events(ests, ref, t_collar=0.200, percentage_of_length=0.2, time_resolution=1.0, counts=None,
+                                 point0=0, per_file=False):
+    """The scoring stage alone: ``ests`` is a list of K ``RefEvents`` scored in one call against the one reference side."""
+    est_args, cap, K = _events_args(ests, ref, "long_sweep_error_from_events")
+    return _long_error_target(True, est_args, cap, K, ref, t_collar, percentage_of_length, time_resolution, counts, point0,
+                              per_file)
+
+
 def long_event_counts(decoded, ref, pooling_time_ratio, cfg=None, t_collar=0.200, percentage_of_length=0.2, time_resolution=1.0,
                       counts=None, point=0, per_column=False):
     """Event- and segment-based counts of long recordings: ``decoded`` is the dict ``inference.stitch_decode`` returns (the
@@ -822,7 +1014,7 @@ def long_sweep_psds_counts_from_events(ests, ref, dtc=0.5, gtc=0.5, cttc=0.3, co
 
 
 def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, batch_size=64, cfg=None, weighting="taper",
-                  psds=None, one_blend=True, max_table_bytes=1 << 30, weak_labels=None, weak_thresholds=None):
+                  psds=None, one_blend=True, max_table_bytes=1 << 30, weak_labels=None, weak_thresholds=None, error_rate=False):
     """``validate`` for a ``LongRecordingSet``: the windows go through the model ONCE, then the K operating points are
     decoded and scored, and ONE device -> host copy ends the call.  ``one_blend=True``: the points are split into chunks
     (``longrec.sweep_chunks``: the event table of a chunk stays within ``max_table_bytes``); per chunk ONE
@@ -839,7 +1031,9 @@ def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, 
     (``ref.weak_labels()``).  The same forwards then also hand out their attention, the recording-level weak tags are pooled
     ONCE (``inference.stitch_weak``) and scored by ``weak_counts`` at ``weak_thresholds`` (entries as ``thresholds``, the
     default), and the call returns ``(that list, {"f_measure": [Kw, nclass] float64, "counts": [Kw, nclass, 4] int64 (tp, fp,
-    fn, tn)})`` - still one device -> host copy.  With ``weak_labels=None`` nothing changes."""
+    fn, tn)})`` - still one device -> host copy.  With ``weak_labels=None`` nothing changes.
+    ``error_rate=True``: every decode is also scored by ``long_sweep_error_counts`` (``one_blend``) / ``long_error_counts``
+    (per point), and the metrics of every point carry the overall error rate; the default issues no launch more than before."""
     from .inference import (_per_class, long_window_posteriors, stitch_decode, stitch_error_text, stitch_sweep, stitch_weak,
                             sweep_points)
     from .longrec import LongRecordingSet, sweep_chunks
@@ -879,6 +1073,7 @@ def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, 
     if one_blend:
         thr_all, win_all = sweep_points(thresholds, median_windows, NC)
     counts = Counts(K, NC, dev)
+    errors = ErrorCounts(K, NC, dev) if error_rate else None
     win_strong = long_window_posteriors(model, long_set, NC, batch_size, want_attention=weak_labels is not None)
     if weak_labels is not None:
         win_strong, win_att = win_strong
@@ -889,6 +1084,8 @@ def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, 
                                torch.from_numpy(thr_all[k0:k1]).to(dev), torch.from_numpy(win_all[k0:k1]).to(dev), weighting,
                                (k1 - k0) * cap)
             long_sweep_event_counts(out, ref, long_set.pooling_time_ratio, cfg, counts=counts, point0=k0)
+            if errors is not None:
+                long_sweep_error_counts(out, ref, long_set.pooling_time_ratio, cfg, counts=errors, point0=k0)
             if psds is not None:
                 long_sweep_psds_counts(out, ref, long_set.pooling_time_ratio, cfg, psds.dtc, psds.gtc, psds.cttc, counts=psds,
                                        point0=k0)
@@ -898,17 +1095,24 @@ def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, 
                                 thresholds[k % len(thresholds)], median_windows[k % len(median_windows)], weighting,
                                 long_set.capacity(NC), want_timeline=False)
             long_event_counts(out, ref, long_set.pooling_time_ratio, cfg, counts=counts, point=k)
+            if errors is not None:
+                long_error_counts(out, ref, long_set.pooling_time_ratio, cfg, counts=errors, point=k)
             if psds is not None:
                 long_psds_counts(out, ref, long_set.pooling_time_ratio, cfg, psds.dtc, psds.gtc, psds.cttc, counts=psds, point=k)
+    n_err = errors.buf.numel() if errors is not None else 0          # the error totals travel last in the one copy
     if weak_labels is None:
-        ev, seg = counts.host()
-        return [(EventMetrics(ref.labels, ev[k]), SegmentMetrics(ref.labels, seg[k])) for k in range(K)]
+        if errors is None:
+            ev, seg = counts.host()
+            return _metric_pairs(ref.labels, ev, seg)
+        ev, seg, tail = counts.host(errors.buf)
+        return _metric_pairs(ref.labels, ev, seg, errors.parse(tail))
     tags = stitch_weak(win_strong, win_att, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3, weighting)
     wc = weak_counts(tags["weak"], torch.from_numpy(weak_labels.astype(np.uint8)), weak_thr)
-    ev, seg, tail = counts.host(torch.cat([wc.reshape(-1), tags["err"].to(torch.int64)]))
+    ev, seg, tail = counts.host(torch.cat([wc.reshape(-1), tags["err"].to(torch.int64)] + ([errors.buf] if n_err else [])))
+    overall = errors.parse(tail[len(tail) - n_err:]) if n_err else None
+    tail = tail[:len(tail) - n_err]
     err = int(tail[-1])
     if err:
         raise _lib.SedError(stitch_error_text("sed_stitch_weak", err))
     wc = tail[:-1].reshape(len(weak_thr), NC, 4)
-    return ([(EventMetrics(ref.labels, ev[k]), SegmentMetrics(ref.labels, seg[k])) for k in range(K)],
-            {"f_measure": f_measure_from_counts(wc), "counts": wc})
+    return (_metric_pairs(ref.labels, ev, seg, overall), {"f_measure": f_measure_from_counts(wc), "counts": wc})

@@ -689,7 +689,7 @@ int sed_stitch_weak_backward(const float* win_strong, const float* win_att, cons
  *              invalid when err != 0.
  * Limits: T <= 2048, nclass <= 16 (the scoring limits and the err bits are defined once, in csrc/score.h, for
  * these calls and the sed_long_* ones).  The overall error rate with substitutions (a second, label-agnostic
- * matching) is not computed.
+ * matching) comes from sed_error_counts ("overall error rate", below).
  * sed_weak_counts: weak [n_clips][nclass] fp32, labels [n_clips][nclass] uint8, thr [n_points][nclass] ->
  *   counts [n_points][nclass][4] int64 (tp, fp, fn, tn) with pred = weak > thr, ACCUMULATED (chain the batches).
  * Both: one launch on `stream`, no allocation, hipGraph-capturable. */
@@ -791,7 +791,8 @@ int sed_psds_counts(const float* strong, int n_clips, int T, int nclass, int n_p
  *   integer results are bit-reproducible; hipGraph-capturable.  No table content can make a kernel address outside the
  *   arrays as est_capacity / ref_events and n_rec * nclass + 1 describe them.
  * Limits: nclass <= 16, est_capacity and ref_events < 2^31 - 1024, n_rec * nclass < 2^26.  Not provided: an exact
- *   matching for clusters beyond 64 per side, the overall error rate with substitutions.  Recording-level weak tags come
+ *   matching for clusters beyond 64 per side.  The overall error rate with substitutions comes from
+ *   sed_long_error_counts / sed_long_sweep_error_counts ("overall error rate", below).  Recording-level weak tags come
  *   from sed_stitch_weak and are scored by sed_weak_counts. */
 size_t sed_long_score_ws_bytes(long long est_capacity, long long ref_events, int n_rec, int nclass);
 int sed_long_tile_events(void);
@@ -839,6 +840,78 @@ int sed_long_sweep_psds_counts(const int64_t* ev_ptr, const int32_t* ev_pairs, d
                                const int64_t* ref_ptr, const double* ref_on, const double* ref_off, long long ref_events,
                                int n_rec, int nclass, int n_points, double dtc, double gtc, double cttc, int32_t* columns,
                                int64_t* totals, int32_t* err, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- overall error rate -------------------------------------------------------------------------
+ * The headline of both sed_eval reports is the OVERALL error rate, ER = (S + D + I) / Nref, in which an error of one
+ * class against an error of another class counts once, as a substitution.  sed_error_counts, sed_long_error_counts and
+ * sed_long_sweep_error_counts produce its integer counts per file (clip / recording; per (point, recording) in a sweep)
+ * beside the class-wise calls above; the rates are host arithmetic (metrics.EventMetrics / SegmentMetrics, overall=).
+ *
+ * Segment-based (sed_eval's, exactly).  Segment cover and the file's segment count are those of sed_event_counts.  For
+ * segment s let R_s / E_s be the set of classes with a reference / estimated event covering s, fn_s = |R_s \ E_s|,
+ * fp_s = |E_s \ R_s|:   S += min(fn_s, fp_s),  D += max(0, fn_s - fp_s),  I += max(0, fp_s - fn_s).
+ *   ER = (S + D + I) / Nref with Nref = sum over classes of (Ntp_c + Nfn_c) of seg_total.  Against seg_total of the same
+ *   inputs:  S + D = sum_c Nfn_c  and  S + I = sum_c Nfp_c.
+ * Event-based.  r and e are TIME-COMPATIBLE iff the compatibility test of sed_event_counts holds with the label ignored:
+ *   |r.on - e.on| <= t_collar and |r.off - e.off| <= max(t_collar, percentage_of_length * (r.off - r.on)).
+ *   Nany = size of a MAXIMUM bipartite matching over ALL events of the file under time-compatibility.  With Ntp = sum_c
+ *   Ntp_c of the label-wise matching (ev_total), Nref and Nsys the numbers of events of all classes:
+ *     Nsubs = Nany - Ntp,  Nfn = Nref - Nany,  Nfp = Nsys - Nany,  ER = (Nsubs + Nfn + Nfp) / Nref.
+ *   Every same-label matching is a time-compatible matching, so Ntp <= Nany <= min(Nref, Nsys).
+ *   THIS IS A DECISION.  sed_eval finds substitutions by a greedy pass over the events its label-wise matching left over;
+ *   that count depends on the order of the lists and on WHICH maximum matching its matcher returned, so it is not a function
+ *   of the two event sets and cannot be pinned.  Label-wise matching plus greedy substitutions is itself a time-compatible
+ *   matching: sed_eval's Nsubs is never larger than this one and its ER never smaller, and the two agree whenever the
+ *   greedy pass is itself maximum.  Parity with sed_eval stays UNPINNED, as for the rest of the section; pinned is exact
+ *   agreement with tests/error_rate_np.py (sets per segment; scipy's matching on the double-loop matrix).
+ *
+ * sed_error_counts: the arguments of sed_event_counts up to time_resolution (posteriors decoded at n_points operating
+ *   points, or given events), then
+ *   ev_overall        [n_points][n_clips][3] int32 (Nref, Nsys, Nany) or NULL
+ *   seg_overall       [n_points][n_clips][3] int32 (S, D, I) or NULL
+ *   ev_overall_total  [n_points][3], seg_overall_total [n_points][3] int64, ACCUMULATED over clips (zero them first)
+ *   err               the error word of sed_event_counts, same bits.  The clip's events of all classes are merged by onset
+ *                     per side and cut into clusters by the valid-cut rule of the long calls above, applied to the MERGED
+ *                     lists; each cluster is matched exactly.  More than 64 events per side in one merged cluster raises
+ *                     bit 1 / 2 (as does a single column beyond 64); the clip is then not scored (Nany = S = D = I = 0,
+ *                     Nref and Nsys as they are) and nothing is truncated.
+ *   One launch: one workgroup per (point, clip), all class columns decoded into LDS as for sed_psds_counts.
+ * sed_long_error_counts / sed_long_sweep_error_counts: the arguments of sed_long_event_counts /
+ *   sed_long_sweep_event_counts (both sides of every class column sorted by onset), outputs ev_overall / seg_overall
+ *   [n_rec][3] ([K][n_rec][3]) int32 or NULL (every element is written), the totals [3] ([K][3]) int64 ACCUMULATED, err
+ *   with the bits of sed_long_event_counts (1 / 2: a MERGED cluster beyond 64 per side; 64: a class column whose onsets
+ *   decrease - a recording with any such column is not scored).  ws: sed_long_error_ws_bytes / sed_long_sweep_error_ws_bytes
+ *   bytes, 8-byte aligned (the workspace of the class-wise call plus the merged tables).
+ *   Per recording and side the onset-sorted union of the class columns is built in the workspace - an event's rank is its
+ *   index in its own column plus one bisection count per other column, ties by (class, index): no atomics, one writer per
+ *   slot - and the cluster / tile matching of sed_long_event_counts runs on it as a one-class problem.  The reference side
+ *   is validated and merged once per call, not once per point.  Segments: one thread per segment, a 16-bit class mask per
+ *   side.  Six launches whatever K is.
+ * All three share the guarantees of the calls they sit beside: no allocation, no host synchronisation, no float atomics,
+ * integer bit-reproducible results, hipGraph-capturable; no table content can make a kernel address outside its arrays.
+ * Not provided: sed_eval's order-dependent greedy count, an exact matching for merged clusters beyond 64 per side,
+ * substitutions per class pair, error rates of the weak tags. */
+int sed_error_counts(const float* strong, int n_clips, int T, int nclass, int n_points, const float* thr,
+                     const int32_t* win, double num, double den, const int32_t* est_ptr, const double* est_on,
+                     const double* est_off, const int32_t* ref_ptr, const double* ref_on, const double* ref_off,
+                     double t_collar, double percentage_of_length, double time_resolution, int32_t* ev_overall,
+                     int32_t* seg_overall, int64_t* ev_overall_total, int64_t* seg_overall_total, int32_t* err,
+                     void* stream);
+size_t sed_long_error_ws_bytes(long long est_capacity, long long ref_events, int n_rec, int nclass);
+size_t sed_long_sweep_error_ws_bytes(long long est_capacity, long long ref_events, int n_rec, int nclass, int n_points);
+int sed_long_error_counts(const int64_t* ev_ptr, const int32_t* ev_pairs, double num, double den, const double* est_on,
+                          const double* est_off, long long est_capacity, const int64_t* ref_ptr, const double* ref_on,
+                          const double* ref_off, long long ref_events, int n_rec, int nclass, double t_collar,
+                          double percentage_of_length, double time_resolution, int32_t* ev_overall, int32_t* seg_overall,
+                          int64_t* ev_overall_total, int64_t* seg_overall_total, int32_t* err, void* ws, size_t ws_bytes,
+                          void* stream);
+int sed_long_sweep_error_counts(const int64_t* ev_ptr, const int32_t* ev_pairs, double num, double den,
+                                const double* est_on, const double* est_off, long long est_capacity,
+                                const int64_t* ref_ptr, const double* ref_on, const double* ref_off, long long ref_events,
+                                int n_rec, int nclass, int n_points, double t_collar, double percentage_of_length,
+                                double time_resolution, int32_t* ev_overall, int32_t* seg_overall,
+                                int64_t* ev_overall_total, int64_t* seg_overall_total, int32_t* err, void* ws,
+                                size_t ws_bytes, void* stream);
 
 /* ---- single-kernel replay (measurement) ----------------------------------------------------
  * Re-launches ONE kernel of the step on the buffers left by a finished sed_crnn_forward +

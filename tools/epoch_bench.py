@@ -16,8 +16,12 @@ than `frames`).  Device-event timing; prints one JSON object (and writes it to -
   (e) validation scoring over 1 168 and 400 resident clips: metrics.validate at one operating point and at 50 thresholds, the
       DataFrame route (get_predictions + compute_strong_metrics), sed_event_counts alone, and - next to them, in the same
       run - validate(..., psds=...) and sed_psds_counts alone at the same operating points (--only-e: this leg only)
+      error_rate (with --only-e; --only-error-rate: alone, into the "clips" key of profiles/error_rate.json): validate(...,
+      error_rate=True) against the same run's validate(...) at one point and at 50 thresholds, the two legs alternated, 5
+      rounds, medians and spread = (max - min) / median; sed_error_counts alone beside sed_event_counts (device events, median
+      of 30); the largest merged cluster met
 
-Usage: python tools/epoch_bench.py [--shapes 24:f32,64:bf16] [--only-a | --only-aug | --only-e] [--out FILE]"""
+Usage: python tools/epoch_bench.py [--shapes 24:f32,64:bf16] [--only-a | --only-aug | --only-e | --only-error-rate] [--out FILE]"""
 import argparse
 import json
 import os
@@ -307,9 +311,127 @@ def leg_e(feats, sc, sizes=(1168, 400), reps=20):
     return out
 
 
+def alternated(legs, rounds):
+    """``legs``: name -> call ending in a device -> host copy.  One warm call each, then ``rounds`` rounds in which the legs
+    alternate; per leg the median, spread = (max - min) / median and the samples of a host clock around the call."""
+    for fn in legs.values():
+        fn()
+    ms = {name: [] for name in legs}
+    for _ in range(rounds):
+        for name, fn in legs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ms[name].append((time.perf_counter() - t0) * 1e3)
+    return {name: {"median_ms": round(float(np.median(v)), 3), "spread": round(float((max(v) - min(v)) / np.median(v)), 4),
+                   "max_minus_min_ms": round(float(max(v) - min(v)), 3), "samples_ms": [round(x, 3) for x in v]}
+            for name, v in ms.items()}
+
+
+def difference(legs, plain, added):
+    """What ``added`` costs over ``plain`` and whether that lies outside the larger (max - min) of the two legs."""
+    d = legs[added]["median_ms"] - legs[plain]["median_ms"]
+    band = max(legs[plain]["max_minus_min_ms"], legs[added]["max_minus_min_ms"])
+    return {"added_ms": round(d, 3), "larger_max_minus_min_ms": band, "outside_the_band": bool(abs(d) > band)}
+
+
+def events_alone(fn, reps=30):
+    """Median and spread of ``reps`` single device-event pairs around fn(), after 3 warm calls."""
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    t = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        t.append(e0.elapsed_time(e1))
+    return {"median_ms": round(float(np.median(t)), 4), "spread": round(float((max(t) - min(t)) / np.median(t)), 4), "reps": reps}
+
+
+def leg_e_error_rate(feats, sc, sizes=(1168, 400), rounds=5):
+    """What the overall error rate adds to validation: validate(..., error_rate=True) against the same run's validate(...) at
+    one operating point and at 50 thresholds, legs alternated, ``rounds`` rounds; and the sed_error_counts launches alone
+    beside the sed_event_counts launches on the same posteriors (device events, median of 30).  The annotations are those of
+    leg (e)."""
+    import pandas as pd
+    from dcase2019_task4_amd import metrics
+    from long_bench import largest_cluster
+    model, _ = bench.build_models("cuda", seed=0)
+    model.eval()
+    labels = [f"c{i}" for i in range(NCLASS)]
+    base = sum(SIZES[:2])
+    out = []
+    for n in sizes:
+        ds = type("DS", (), {"__len__": lambda self: n, "get_sample": lambda self, k: (feats[base + k], np.zeros(1)),
+                             "filenames": pd.Series([f"clip_{i}.wav" for i in range(n)])})()
+        res = ResidentFeatureSet.for_eval(ds, T, sc)
+        files = res.filenames.tolist()
+        rs = np.random.RandomState(n)
+        rows = []
+        for f in files:
+            for _ in range(rs.randint(0, 6)):
+                on = rs.uniform(0.0, 9.0)
+                rows.append((f, on, min(10.0, on + rs.uniform(0.25, 5.0)), labels[rs.randint(NCLASS)]))
+        valid_df = pd.DataFrame(rows, columns=["filename", "onset", "offset", "event_label"])
+        ref = metrics.RefEvents.from_dataframe(valid_df, files, labels)
+        thr50 = [float(v) for v in np.linspace(0.01, 0.99, 50)]
+        with torch.no_grad():
+            strong = torch.cat([model(res.eval_batch(i0, min(64, n - i0)))[0] for i0 in range(0, n, 64)])
+        points = {"1_point": metrics.operating_points((0.5,), (5,), "cuda"), "50_thresholds": metrics.operating_points(thr50, (5,), "cuda")}
+        leg = {"clips": n, "batch_size": 64, "reference_events": len(rows), "rounds": rounds}
+        for name, (thr, win) in points.items():
+            kw = dict(thresholds=thr, median_windows=win, batch_size=64)
+            t = alternated({"validate": lambda: metrics.validate(model, res, ref, 8, **kw),
+                            "validate_error_rate": lambda: metrics.validate(model, res, ref, 8, error_rate=True, **kw)}, rounds)
+            t["difference"] = difference(t, "validate", "validate_error_rate")
+            counts, errors = metrics.Counts(thr.numel(), NCLASS, "cuda"), metrics.ErrorCounts(thr.numel(), NCLASS, "cuda")
+            t["sed_event_counts_alone"] = events_alone(lambda: [
+                metrics.event_counts(strong[i0:i0 + 64], ref, thr, win, 8, clip_offset=i0, counts=counts) for i0 in range(0, n, 64)])
+            t["sed_error_counts_alone"] = events_alone(lambda: [
+                metrics.error_counts(strong[i0:i0 + 64], ref, thr, win, 8, clip_offset=i0, counts=errors) for i0 in range(0, n, 64)])
+            counts.host(), errors.host()                      # raise when an error word is set
+            # the merged clusters: a cluster holds at most the clip's events, so the per-clip totals bound it at every point
+            per_file = metrics.error_counts(strong, ref, thr, win, 8, per_file=True).ev_files.cpu().numpy()
+            t["most_events_in_a_clip"] = {"reference": int(per_file[..., 0].max()), "estimated": int(per_file[..., 1].max())}
+            leg[name] = t
+        m_e, m_s = metrics.validate(model, res, ref, 8, batch_size=64, error_rate=True)[0]
+        leg["overall_error_rate_at_0.5"] = {"event_based": m_e.results_overall_metrics()["error_rate"],
+                                            "segment_based": m_s.results_overall_metrics()["error_rate"]}
+        # exactly, at the one point: the largest cluster of the clips' merged onsets (estimated events from a host decode)
+        from dcase2019_task4_amd.inference import get_predictions
+        from oracle import postprocess_np as pp
+        enc = type("Enc", (), {"labels": labels, "decode_strong": lambda self, m: pp.decode_strong(m, labels)})()
+        df = get_predictions(model, res, enc.decode_strong, 8, batch_size=64)
+        est_on = {f: g["onset"].to_numpy(np.float64) for f, g in df.groupby("filename")}
+        ref_on = {f: g["onset"].to_numpy(np.float64) for f, g in valid_df.groupby("filename")}
+        none = np.zeros(0)
+        sizes_1 = [largest_cluster(np.sort(ref_on.get(f, none)), np.sort(est_on.get(f, none))) for f in files]
+        leg["largest_merged_cluster_at_0.5"] = {"reference": max(s[0] for s in sizes_1), "estimated": max(s[1] for s in sizes_1)}
+        out.append(leg)
+        print(json.dumps(leg), flush=True)
+    return out
+
+
+def update_json(path, key, value):
+    """profiles/error_rate.json is written by two tools: each replaces its own key."""
+    doc = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            doc = json.load(f)
+    doc[key] = value
+    with open(path, "w") as f:
+        f.write(json.dumps(doc, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="24:f32,64:bf16")
+    ap.add_argument("--only-error-rate", action="store_true",
+                    help="the error_rate leg of (e) only: validate(error_rate=True) against validate (--out: profiles/error_rate.json)")
     ap.add_argument("--only-a", action="store_true", help="leg (a) only (for a kernel trace of the resident epoch)")
     ap.add_argument("--only-aug", action="store_true", help="leg (a') only: the plain and the augmented resident epoch, alternated")
     ap.add_argument("--only-e", action="store_true", help="leg (e) only: validation scoring")
@@ -323,6 +445,14 @@ def main():
                                            "longer_than_frames": int((lengths > T).sum()), "frames": T,
                                            "bytes": int(lengths.sum()) * N_MELS * 4}, "legs": []}
     build_s = None
+    if a.only_error_rate:
+        doc = {"tool": "tools/epoch_bench.py --only-error-rate", "device": dev.name, "frames": T,
+               "timing": "validate legs: host clock around each synchronised call, the two legs alternated in one run, 5 rounds, "
+                         "medians, spread = (max - min) / median; the calls alone: device events, median of 30",
+               "sets": leg_e_error_rate(feats, sc)}
+        print(json.dumps(doc))
+        update_json(a.out or os.path.join(REPO, "profiles", "error_rate.json"), "clips", doc)
+        return
     if a.only_aug:
         result["command"] = f"python tools/epoch_bench.py --only-aug --shapes {a.shapes}"
     with tempfile.TemporaryDirectory() as tmp:
@@ -360,6 +490,8 @@ def main():
             result["d_get_predictions"] = leg_d(feats, sc, tmp)
         if not a.only_a and not a.only_aug:
             result["e_validation_scoring"] = leg_e(feats, sc)
+            if a.only_e:
+                result["e_error_rate"] = leg_e_error_rate(feats, sc)
             result["command"] = "python tools/epoch_bench.py" + (" --only-e" if a.only_e else f" --shapes {a.shapes}")
     result["pool"]["build_s"] = build_s
     result["total_s"] = round(time.perf_counter() - t0, 1)

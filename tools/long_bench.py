@@ -57,7 +57,17 @@ workloads at the same 50 thresholds with PSDS:
   and the fp64 pooling - the only route to the gradient before it - with the largest difference of the two routes' gradients;
   on 100x3min one train.train_recording_tags epoch against the same batches with a window-level loss, alternated.
 
-Usage: python tools/long_bench.py [--scoring | --sweep | --weak | --tag-train] [--rounds 5] [--decode-reps 30] [--out profiles/long_inference.json]"""
+--error-rate measures the overall error rate with substitutions (the "long" key of profiles/error_rate.json), same workloads,
+references and hop as --scoring:
+  validate_long(..., error_rate=True) against the same run's validate_long(...) at one operating point and at 50, the two legs
+    alternated in one run, --rounds rounds, medians, spread = (max - min) / median; the difference counts only where it lies
+    outside the larger (max - min) of its two legs.
+  sed_long_error_counts beside sed_long_event_counts on one decoded table and sed_long_sweep_error_counts beside
+    sed_long_sweep_event_counts on the K = 50 table: a device-event pair around the Python call, median of --decode-reps.
+  The operating points start at the first of --scoring's 50 thresholds from which no cluster of a recording's events of ALL
+  classes merged exceeds 64 per side; the largest merged cluster met is reported.
+
+Usage: python tools/long_bench.py [--scoring | --sweep | --weak | --tag-train | --error-rate] [--rounds 5] [--decode-reps 30] [--out profiles/long_inference.json]"""
 import argparse
 import json
 import os
@@ -424,6 +434,103 @@ def sweep_workload(name, ctx, model, rounds, reps, decode_only):
     return out
 
 
+def largest_merged_cluster(table, ref_ev, n_rec, K, den):
+    """(reference, estimated) events of the largest cluster over all (point, recording) of a decoded table when the events of
+    ALL classes are merged by onset - what bounds sed_long_error_counts (64 per side)."""
+    ev_ptr = table["ev_ptr"].cpu().numpy()
+    on = table["ev_pairs"][:int(ev_ptr[-1]), 0].cpu().numpy().astype(np.int64) * POOL / den
+    ref_ptr = ref_ev.ptr_host.astype(np.int64)
+    best = (0, 0)
+    for k in range(K):
+        for r in range(n_rec):
+            a, b = ev_ptr[(k * n_rec + r) * NCLASS], ev_ptr[(k * n_rec + r + 1) * NCLASS]
+            ra, rb = ref_ptr[r * NCLASS], ref_ptr[(r + 1) * NCLASS]
+            s = largest_cluster(np.sort(ref_ev.onset_host[ra:rb]), np.sort(on[a:b]))
+            best = (max(best[0], s[0]), max(best[1], s[1]))
+    return best
+
+
+def error_rate_workload(name, model, rounds, reps):
+    """validate_long(..., error_rate=True) against the same run's validate_long(...) at one operating point and at 50, the two
+    legs alternated; the three long entry points alone beside the class-wise ones.  The operating points start at the lowest
+    of the scoring workload's 50 thresholds from which no MERGED cluster exceeds 64 events per side."""
+    from dcase2019_task4_amd import metrics
+    info, ctx = scoring_workload(name, model, rounds, reps, setup_only=True)
+    ls, ref_ev, window, win_strong = ctx["ls"], ctx["ref_ev"], ctx["window"], ctx["win_strong"]
+    n_rec, cap = ls.n_rec, ls.capacity(NCLASS)
+    den = inference._Cfg.sample_rate / inference._Cfg.hop_length
+
+    def sweep_table(thrs):
+        return inference.stitch_sweep(win_strong, ls.rec_win0, ls.rec_frame0, ls.total_frames, ls.hop3, thrs, [window], "taper",
+                                      len(thrs) * cap)
+
+    def one_table(thr):
+        return inference.stitch_decode(win_strong, ls.rec_win0, ls.rec_frame0, ls.total_frames, ls.hop3, thr, window, "taper", cap,
+                                       want_timeline=False)
+    first = None
+    for k, thr in enumerate(ctx["thr50"]):
+        biggest = largest_merged_cluster(one_table(thr), ref_ev, n_rec, 1, den)
+        if max(biggest) <= 64:
+            first = k
+            break
+    out = {k: info[k] for k in ("recordings", "windows", "timeline_frames", "median_window", "reference_events")}
+    out["rounds"] = rounds
+    if first is None:
+        out["error"] = f"merged clusters beyond 64 events per side at every threshold tried (the last: {biggest})"
+        return out
+    lo, hi = ctx["thr50"][first], ctx["thr50"][-1]
+    thr50 = [lo + (hi - lo) * k / 49.0 for k in range(50)]
+    tab1, tab50 = one_table(lo), sweep_table(thr50)
+    out["first_threshold_index_of_the_scoring_workload"] = first
+    out["largest_merged_cluster"] = {"1_point": dict(zip(("reference", "estimated"), largest_merged_cluster(tab1, ref_ev, n_rec, 1, den))),
+                                     "50_points": dict(zip(("reference", "estimated"),
+                                                           largest_merged_cluster(tab50, ref_ev, n_rec, 50, den)))}
+    out["estimated_events"] = {"1_point": int(tab1["ev_ptr"][-1].item()), "50_points": int(tab50["ev_ptr"][-1].item())}
+    state = {}
+    for what, thrs in (("1_point", [lo]), ("50_points", thr50)):
+        def run(error_rate, thrs=thrs, what=what):
+            def fn():
+                state[what, error_rate] = metrics.validate_long(model, ls, ref_ev, thrs, [window], batch_size=BATCH,
+                                                                error_rate=error_rate)
+            return fn
+        legs = {"validate_long": run(False), "validate_long_error_rate": run(True)}
+        try:
+            for fn in legs.values():
+                fn()
+        except _lib.SedError as e:                                    # e.g. a merged cluster beyond 64 at one of the points
+            out[what] = {"error": str(e)}
+            continue
+        ms = {leg: [] for leg in legs}
+        for _ in range(rounds):
+            for leg, fn in legs.items():
+                ms[leg].append(wall_ms(fn))
+        t = {leg: stats(ms[leg]) for leg in legs}
+        a, b = t["validate_long"], t["validate_long_error_rate"]
+        band = max(max(x["samples_ms"]) - min(x["samples_ms"]) for x in (a, b))
+        t["difference"] = {"added_ms": b["median_ms"] - a["median_ms"], "larger_max_minus_min_ms": band,
+                           "outside_the_band": bool(abs(b["median_ms"] - a["median_ms"]) > band)}
+        same = all(p[0].class_wise == q[0].class_wise and p[1].class_wise == q[1].class_wise
+                   for p, q in zip(state[what, False], state[what, True]))
+        t["class_wise_counts_identical"] = bool(same)
+        e, s = state[what, True][0]
+        t["overall_error_rate_point_0"] = {"event_based": e.results_overall_metrics()["error_rate"],
+                                           "segment_based": s.results_overall_metrics()["error_rate"]}
+        out[what] = t
+    ec1, er1 = metrics.Counts(1, NCLASS, "cuda"), metrics.ErrorCounts(1, NCLASS, "cuda")
+    ec50, er50 = metrics.Counts(50, NCLASS, "cuda"), metrics.ErrorCounts(50, NCLASS, "cuda")
+    alone = {"sed_long_event_counts": lambda: metrics.long_event_counts(tab1, ref_ev, POOL, counts=ec1),
+             "sed_long_error_counts": lambda: metrics.long_error_counts(tab1, ref_ev, POOL, counts=er1),
+             "sed_long_sweep_event_counts": lambda: metrics.long_sweep_event_counts(tab50, ref_ev, POOL, counts=ec50),
+             "sed_long_sweep_error_counts": lambda: metrics.long_sweep_error_counts(tab50, ref_ev, POOL, counts=er50)}
+    out["alone"] = {what: event_ms(call, reps) for what, call in alone.items()}
+    for c in (ec1, er1, ec50, er50):
+        try:
+            c.host()                                                  # raises when the error word is set
+        except _lib.SedError as e:
+            out["alone"]["error"] = str(e)
+    return out
+
+
 def weak_workload(name, model, rounds, reps):
     import ctypes as C
     n_rec, per = WORKLOADS[name]
@@ -620,6 +727,8 @@ def main():
     ap.add_argument("--weak", action="store_true", help="measure the recording-level weak tags (profiles/long_weak.json)")
     ap.add_argument("--tag-train", action="store_true",
                     help="measure the backward through the pooled tag and an epoch on recording tags (profiles/long_tag_train.json)")
+    ap.add_argument("--error-rate", action="store_true",
+                    help="measure what validate_long(error_rate=True) adds (the \"long\" key of profiles/error_rate.json)")
     ap.add_argument("--sweep-decode-only", action="store_true", help="with --sweep: sed_stitch_sweep alone (a variant build)")
     ap.add_argument("--sweep-out", default=os.path.join(REPO, "profiles", "long_sweep.json"))
     ap.add_argument("--candidates", default="", help="with --sweep: earlier --sweep-decode-only results to copy in")
@@ -629,7 +738,8 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(REPO, "profiles", "long_tag_train.json" if args.tag_train else "long_weak.json" if args.weak else
+        args.out = os.path.join(REPO, "profiles", "error_rate.json" if args.error_rate else
+                                "long_tag_train.json" if args.tag_train else "long_weak.json" if args.weak else
                                 "long_scoring.json" if args.scoring else "long_inference.json")
     if not torch.cuda.is_available():
         raise SystemExit("long_bench.py measures on the GPU: no device found (nothing is measured on a CPU)")
@@ -644,6 +754,24 @@ def main():
               "not_measured": ["from_waveforms / feature extraction", "other batch sizes, bf16 / wide models",
                                "recordings longer than 1 h", "a run with the GPU to itself (the host is shared)"],
               "workloads": {}}
+    if args.error_rate:
+        result["timing"] = ("validate_long legs: host clock around each synchronised call, the two legs alternated in one run, "
+                            "--rounds rounds, medians, spread = (max - min) / median; the calls alone: a device-event pair around "
+                            "the Python call (workspace allocation and the launches), warm, median of --decode-reps")
+        result["note"] = ("validate_long(..., error_rate=True) against the same run's validate_long(...); a difference counts "
+                          "only where it lies outside the larger (max - min) of its two legs")
+        result["not_measured"] += ["the kernels one by one", "given-events mode", "other nclass than 10", "with PSDS or weak tags"]
+        for name in args.workloads.split(","):
+            result["workloads"][name] = error_rate_workload(name, model, args.rounds, args.decode_reps)
+            print(json.dumps({name: result["workloads"][name]}), flush=True)
+        path, doc = args.out, {}
+        if os.path.exists(path):                                      # tools/epoch_bench.py writes the "clips" key of the same file
+            with open(path) as f:
+                doc = json.load(f)
+        doc["long"] = result
+        with open(path, "w") as f:
+            f.write(json.dumps(doc, indent=1) + "\n")
+        return
     if args.tag_train:
         result["model"] = "baseline CRNN, fp32 kernel set; eval mode for the window tensors of (a), train mode (dropout 0.5) in (b)"
         result["timing"] = ("the calls alone: a device-event pair around the call(s), warm, median of --decode-reps; the epochs: host "
