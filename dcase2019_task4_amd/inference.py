@@ -15,7 +15,10 @@ Training on windows of such recordings is ``WindowedFeatureSet`` (longrec.py, th
 weak tags: ``get_long_predictions(return_weak=True)`` / ``stitch_weak`` pool them over the whole blended timeline from the
 windows' posteriors and attention (``CRNN.last_attention``, ``sed_stitch_weak``); ``weak_tags_dataframe`` is their table,
 ``metrics.validate_long(weak_labels=...)`` their score; ``pooled_tags`` is the same tag with a backward
-(``sed_stitch_weak_backward``), what ``train.train_recording_tags`` trains on.  ``get_predictions`` itself is unchanged.
+(``sed_stitch_weak_backward``), what ``train.train_recording_tags`` trains on.  Two-threshold (hysteresis) decode:
+``stitch_hysteresis`` / ``get_long_predictions(threshold_high=...)`` keep the low-threshold events in which a high-threshold
+event starts (one ``stitch_sweep`` of both thresholds, then ``sed_events_hysteresis``).  ``get_predictions`` itself is
+unchanged.
 """
 import ctypes as C
 
@@ -145,7 +148,8 @@ def get_predictions(model, valid_dataset, decoder, pooling_time_ratio=1, save_pr
 
 
 STITCH_ERR_BITS = {2: "more events than the capacity of ev_pairs", 8: "a median window outside 1 .. 63",
-                   16: "malformed rec_win0 / rec_frame0 tables", 32: "a recording with too few windows to cover it"}
+                   16: "malformed rec_win0 / rec_frame0 tables", 32: "a recording with too few windows to cover it",
+                   64: "event onsets that do not strictly increase inside a column (sed_events_hysteresis)"}
 
 
 def stitch_error_text(entry, err):
@@ -261,6 +265,82 @@ def stitch_sweep(win_strong, rec_win0, rec_frame0, total_frames, hop3, threshold
         raise ValueError(f"sed_stitch_sweep_ws_bytes: {l.sed_last_error().decode()}")
     return _stitch_call("sed_stitch_sweep", win_strong, rec_win0, rec_frame0, total, hop3, thr, win, weighting, capacity,
                         ws_bytes, want_timeline, n_points=K)
+
+
+def events_hysteresis(lo_ptr, hi_ptr, pairs, capacity=None, err=None):
+    """``sed_events_hysteresis``: the events of the low table ``lo_ptr`` [n_cols + 1] that an event of the high table
+    ``hi_ptr`` [n_cols + 1] confirms (some high onset inside the low event); both are int64 CSR offsets on the device into the
+    one ``pairs`` [pairs_capacity, 2] int32 array.  Returns ``(out_ptr [n_cols + 1] int64, out_pairs [capacity, 2] int32,
+    err [1] int32)``; ``capacity`` defaults to ``pairs_capacity`` (it cannot overflow), ``err`` to a new zeroed word - a given
+    one is OR-ed into.  Three launches, nothing synchronises."""
+    if pairs.device.type != "cuda":
+        raise _lib.SedError("events_hysteresis needs GPU tensors (no CPU fallback)")
+    if (lo_ptr.dtype, hi_ptr.dtype, pairs.dtype) != (torch.int64, torch.int64, torch.int32) or lo_ptr.numel() != hi_ptr.numel() \
+            or lo_ptr.numel() < 2 or pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise ValueError("events_hysteresis: lo_ptr / hi_ptr int64 [n_cols + 1] and pairs int32 [capacity, 2] expected")
+    dev, pairs = pairs.device, pairs.contiguous()
+    lo_ptr, hi_ptr = lo_ptr.contiguous(), hi_ptr.contiguous()
+    n_cols, pairs_cap = lo_ptr.numel() - 1, pairs.shape[0]
+    capacity = pairs_cap if capacity is None else int(capacity)
+    l = _lib.lib()
+    ws_bytes = l.sed_events_hysteresis_ws_bytes(pairs_cap, n_cols)
+    if ws_bytes == 0:
+        raise ValueError(f"sed_events_hysteresis_ws_bytes: {l.sed_last_error().decode()}")
+    out_ptr = torch.empty(n_cols + 1, dtype=torch.int64, device=dev)
+    out_pairs = torch.empty(max(capacity, 1), 2, dtype=torch.int32, device=dev)
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = _lib.scratch(ws_bytes, dev)
+    _lib.check(l.sed_events_hysteresis(_lib.ptr(lo_ptr), _lib.ptr(hi_ptr), _lib.ptr(pairs), pairs_cap, n_cols, _lib.ptr(out_ptr),
+                                       _lib.ptr(out_pairs), capacity, _lib.ptr(ws), ws.numel(), _lib.ptr(err), _lib.stream_ptr()),
+               "sed_events_hysteresis")
+    return out_ptr, out_pairs, err
+
+
+def hysteresis_points(thresholds_low, thresholds_high, median_windows, nclass):
+    """K threshold pairs as host arrays ``(thr_lo [K, nclass], thr_hi [K, nclass], win [K, nclass])``, entries as in
+    ``sweep_points`` (a sequence of length 1 is broadcast).  ValueError where the lengths disagree or some ``thr_hi < thr_lo``
+    (a NaN threshold included)."""
+    lo, hi, mw = list(thresholds_low), list(thresholds_high), list(median_windows)
+    K = max(len(lo), len(hi), len(mw))
+    if K < 1 or any(len(x) not in (1, K) for x in (lo, hi, mw)):
+        raise ValueError("thresholds_low, thresholds_high and median_windows must have equal lengths (or length 1)")
+    thr_lo, win = sweep_points([lo[k % len(lo)] for k in range(K)], [mw[k % len(mw)] for k in range(K)], nclass)
+    thr_hi, _ = sweep_points([hi[k % len(hi)] for k in range(K)], [1], nclass)
+    if not (thr_hi >= thr_lo).all():
+        k, c = np.argwhere(~(thr_hi >= thr_lo))[0]
+        raise ValueError(f"hysteresis needs thr_hi >= thr_lo: pair {k}, class {c} has {thr_hi[k, c]} < {thr_lo[k, c]}")
+    return thr_lo, thr_hi, win
+
+
+def stitch_hysteresis(win_strong, rec_win0, rec_frame0, total_frames, hop3, thresholds_low, thresholds_high, median_windows,
+                      weighting="taper", capacity=None, want_timeline=False):
+    """Two-threshold decode at K threshold pairs: per (pair, recording, class) the events ``stitch_decode`` gives at the low
+    threshold that hold the onset of an event it gives at the high threshold, both with the pair's ONE median window (the
+    definition is in include/dcase_sed.h; at window 1 it is frame-domain hysteresis, for wider windows it is "filter both, then
+    select").  ``thresholds_low`` / ``thresholds_high`` / ``median_windows``: host sequences of K entries as in
+    ``sweep_points``; ``ValueError`` where some ``thr_hi < thr_lo``, before anything is launched.  ONE ``stitch_sweep`` of 2K
+    points ordered ``[lo_0 .. lo_{K-1}, hi_0 .. hi_{K-1}]``, then ONE ``sed_events_hysteresis`` on its table.
+    Returns the dict of ``stitch_sweep`` with ``n_points = K`` (``ev_ptr`` [K * n_rec * nclass + 1], ``ev_pairs``
+    [capacity, 2]; default capacity: K times ``stitch_decode``'s), so every ``metrics.long_sweep_*`` call takes it unchanged;
+    ``err`` is the sweep's word with the select's bits OR-ed in on the device.  Nothing synchronises.
+    Clip sets need no path of their own: a batch of clip posteriors ``[n, T, nclass]`` is n one-window recordings
+    (``rec_win0 = arange(n + 1)``, ``rec_frame0 = arange(n + 1) * T``, ``hop3 = T``)."""
+    if win_strong.dim() != 3:
+        raise ValueError(f"win_strong must be [n_win, T3, nclass], got {tuple(win_strong.shape)}")
+    NC = win_strong.shape[2]
+    thr_lo, thr_hi, win = hysteresis_points(thresholds_low, thresholds_high, median_windows, NC)
+    if win_strong.device.type != "cuda":
+        raise _lib.SedError("stitch_hysteresis needs GPU tensors (no CPU fallback)")
+    dev, K, n_rec = win_strong.device, thr_lo.shape[0], rec_win0.numel() - 1
+    if capacity is None:
+        capacity = K * NC * ((int(total_frames) + n_rec) // 2)
+    out = stitch_sweep(win_strong, rec_win0, rec_frame0, total_frames, hop3, torch.from_numpy(np.concatenate([thr_lo, thr_hi])).to(dev),
+                       torch.from_numpy(np.concatenate([win, win])).to(dev), weighting, 2 * int(capacity), want_timeline)
+    n_cols = K * n_rec * NC
+    ev_ptr, ev_pairs, err = events_hysteresis(out["ev_ptr"][:n_cols + 1], out["ev_ptr"][n_cols:], out["ev_pairs"], int(capacity),
+                                              out["err"])
+    return {"ev_ptr": ev_ptr, "ev_pairs": ev_pairs, "err": err, "timeline": out["timeline"], "binary": None, "n_points": K}
 
 
 def _weak_inputs(who, win_strong, win_att, rec_win0, total_frames, hop3, weighting, n_win=None):
@@ -397,7 +477,7 @@ def long_window_posteriors(model, long_set, nclass, batch_size=64, want_attentio
 
 def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=None, save_predictions=None, batch_size=64,
                          cfg=None, threshold=0.5, median_window=None, weighting="taper", return_posteriors=False,
-                         return_weak=False):
+                         return_weak=False, threshold_high=None):
     """Events of recordings of any lengths (a ``LongRecordingSet``): the windows go through the eval-mode model
     ``batch_size`` at a time, their strong posteriors are blended into one timeline per recording (``weighting``: "taper"
     or "uniform"), and ONE threshold, median filter and run-length decode runs over each whole timeline
@@ -410,7 +490,9 @@ def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=
     or a plain list of labels.  ``return_posteriors=True``: also the list of per-recording [L3_r, nclass] device views of
     the blended timeline and the [n_win, T3, nclass] window posteriors.  ``return_weak=True``: the recording-level weak tags
     [n_rec, nclass] (a device tensor; ``stitch_weak`` on the same single pass through the model) are appended to what is
-    returned; ``weak_tags_dataframe`` turns them into the weak-label table."""
+    returned; ``weak_tags_dataframe`` turns them into the weak-label table.  ``threshold_high`` (a scalar or one value per
+    class, ``>= threshold``): the two-threshold decode of ``stitch_hysteresis`` at one pair - ``threshold`` draws the events,
+    an event is kept when ``threshold_high`` confirms it; None changes nothing."""
     if not isinstance(long_set, LongRecordingSet):
         raise TypeError(f"long_set must be a LongRecordingSet, got {type(long_set).__name__}")
     cfg = cfg or _Cfg
@@ -428,12 +510,19 @@ def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=
     NC = len(labels)
     thr = _per_class(threshold, NC, np.float32, "threshold")
     win = _per_class(cfg.median_window if median_window is None else median_window, NC, np.int32, "median_window")
+    if threshold_high is not None:
+        hysteresis_points([thr], [threshold_high], [win], NC)                    # (ValueError before any forward)
     win_strong = long_window_posteriors(model, long_set, NC, batch_size, want_attention=return_weak)
     if return_weak:
         win_strong, win_att = win_strong
-    out = stitch_decode(win_strong, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3, thr, win,
-                        weighting, long_set.capacity(NC), want_timeline=return_posteriors)
-    calls = [("sed_stitch_decode", out["err"])]
+    if threshold_high is None:
+        out = stitch_decode(win_strong, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3, thr, win,
+                            weighting, long_set.capacity(NC), want_timeline=return_posteriors)
+        calls = [("sed_stitch_decode", out["err"])]
+    else:
+        out = stitch_hysteresis(win_strong, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3, [thr],
+                                [threshold_high], [win], weighting, long_set.capacity(NC), want_timeline=return_posteriors)
+        calls = [("sed_stitch_sweep + sed_events_hysteresis", out["err"])]
     if return_weak:
         tags = stitch_weak(win_strong, win_att, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3,
                            weighting)

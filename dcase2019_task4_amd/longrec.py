@@ -68,16 +68,19 @@ def window_plan(L, frames, pool=8, hop3=None):
 MAX_SWEEP_POINTS = 4096          # operating points per sed_stitch_sweep / sed_long_sweep_* call
 
 
-def sweep_chunks(K, capacity_per_point, max_table_bytes, limit=2 ** 31 - 1024):
+def sweep_chunks(K, capacity_per_point, max_table_bytes, limit=2 ** 31 - 1024, pair=False):
     """The ranges ``[(k0, k1), ...]`` that split ``K`` operating points into ``sed_stitch_sweep`` calls: consecutive, covering
     ``0 .. K`` once, each as long as possible with its event table ``(k1 - k0) * capacity_per_point`` rows of 8 bytes
     (``ev_pairs``) within ``max_table_bytes`` and its capacity below ``limit`` (what the scorers accept); never fewer than one
-    point per chunk, never more than ``MAX_SWEEP_POINTS``."""
+    point per chunk, never more than ``MAX_SWEEP_POINTS``.  ``pair=True`` (the two-threshold decode: ``K`` is twice the number
+    of threshold pairs): every chunk holds an even number of points, never fewer than two - the two decodes of whole pairs."""
     K, cap = int(K), int(capacity_per_point)
-    if K < 1 or cap < 0:
-        raise ValueError(f"need K >= 1 and capacity_per_point >= 0, got {K}, {cap}")
+    if K < 1 or cap < 0 or (pair and K % 2):
+        raise ValueError(f"need K >= 1 (even for pairs) and capacity_per_point >= 0, got {K}, {cap}")
     per = K if cap == 0 else min(int(max_table_bytes) // (8 * cap), (int(limit) - 1) // cap)
     per = max(1, min(per, K, MAX_SWEEP_POINTS))
+    if pair:
+        per = max(2, per - per % 2)
     return [(k0, min(k0 + per, K)) for k0 in range(0, K, per)]
 
 

@@ -54,7 +54,9 @@ nothing is truncated.  K operating points: ``long_sweep_event_counts`` / ``long_
 (``sed_long_sweep_*``); ``validate_long(one_blend=True)`` uses them.  Recording-level weak tags: ``validate_long(weak_labels=...)``
 pools them once (``inference.stitch_weak``) and scores them with ``weak_counts``.  The overall error rate:
 ``validate_long(error_rate=True)`` (``sed_long_error_counts`` / ``sed_long_sweep_error_counts``, six launches whatever K is, the
-reference side merged once).  Not provided there: an exact matching of clusters beyond 64 per side.
+reference side merged once).  Two-threshold decode: ``validate_long(thresholds_high=...)`` scores the table of
+``inference.stitch_hysteresis`` with the same sweep scorers.  Not provided there: an exact matching of clusters beyond 64 per
+side.
 
 PSDS (polyphonic sound detection score, Bilen et al., ICASSP 2020): ``sed_psds_counts`` scores the same (operating point,
 clip) grid with the three intersection criteria and returns integer class totals (``psds_counts``, ``PSDSCounts``); the
@@ -1014,7 +1016,8 @@ def long_sweep_psds_counts_from_events(ests, ref, dtc=0.5, gtc=0.5, cttc=0.3, co
 
 
 def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, batch_size=64, cfg=None, weighting="taper",
-                  psds=None, one_blend=True, max_table_bytes=1 << 30, weak_labels=None, weak_thresholds=None, error_rate=False):
+                  psds=None, one_blend=True, max_table_bytes=1 << 30, weak_labels=None, weak_thresholds=None, error_rate=False,
+                  thresholds_high=None):
     """``validate`` for a ``LongRecordingSet``: the windows go through the model ONCE, then the K operating points are
     decoded and scored, and ONE device -> host copy ends the call.  ``one_blend=True``: the points are split into chunks
     (``longrec.sweep_chunks``: the event table of a chunk stays within ``max_table_bytes``); per chunk ONE
@@ -1033,9 +1036,15 @@ def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, 
     default), and the call returns ``(that list, {"f_measure": [Kw, nclass] float64, "counts": [Kw, nclass, 4] int64 (tp, fp,
     fn, tn)})`` - still one device -> host copy.  With ``weak_labels=None`` nothing changes.
     ``error_rate=True``: every decode is also scored by ``long_sweep_error_counts`` (``one_blend``) / ``long_error_counts``
-    (per point), and the metrics of every point carry the overall error rate; the default issues no launch more than before."""
-    from .inference import (_per_class, long_window_posteriors, stitch_decode, stitch_error_text, stitch_sweep, stitch_weak,
-                            sweep_points)
+    (per point), and the metrics of every point carry the overall error rate; the default issues no launch more than before.
+    ``thresholds_high``: K entries as ``thresholds`` (or one entry for all points), each ``>=`` its point's threshold: every
+    point is decoded with two thresholds (``inference.stitch_hysteresis``: ``thresholds`` draws the events, an event is kept
+    when the high threshold confirms it).  The chunks are then made of 2 x points sweep points, so a pair never straddles a
+    chunk, and per chunk one ``sed_events_hysteresis`` runs between the sweep and the same scorers.  ``one_blend=False``
+    raises: the two decodes of a pair come from one sweep.  With ``thresholds_high=None`` nothing changes and no launch is
+    added."""
+    from .inference import (_per_class, hysteresis_points, long_window_posteriors, stitch_decode, stitch_error_text,
+                            stitch_hysteresis, stitch_sweep, stitch_weak, sweep_points)
     from .longrec import LongRecordingSet, sweep_chunks
     cfg = cfg or _Cfg
     thresholds = list(thresholds)
@@ -1043,6 +1052,12 @@ def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, 
     K = max(len(thresholds), len(median_windows))
     if len(thresholds) not in (1, K) or len(median_windows) not in (1, K) or K < 1:
         raise ValueError("thresholds and median_windows must have equal lengths (or length 1)")
+    if thresholds_high is not None:
+        thresholds_high = list(thresholds_high)
+        if not one_blend:
+            raise ValueError("thresholds_high needs one_blend=True: the two decodes of a pair come from one sweep")
+        if len(thresholds_high) not in (1, K):
+            raise ValueError(f"thresholds_high must have {K} entries (or one)")
     if weak_labels is None:
         if weak_thresholds is not None:
             raise ValueError("weak_thresholds without weak_labels: there is nothing to score the tags against")
@@ -1070,7 +1085,10 @@ def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, 
     NC = ref.nclass
     if psds is not None and (psds.K, psds.NC) != (K, NC):
         raise ValueError("psds was built for another number of operating points / classes")
-    if one_blend:
+    if thresholds_high is not None:
+        thr_all, thr_high, win_all = hysteresis_points([thresholds[k % len(thresholds)] for k in range(K)], thresholds_high,
+                                                       median_windows, NC)
+    elif one_blend:
         thr_all, win_all = sweep_points(thresholds, median_windows, NC)
     counts = Counts(K, NC, dev)
     errors = ErrorCounts(K, NC, dev) if error_rate else None
@@ -1079,10 +1097,18 @@ def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, 
         win_strong, win_att = win_strong
     if one_blend:
         cap = long_set.capacity(NC)
-        for k0, k1 in sweep_chunks(K, cap, max_table_bytes):
-            out = stitch_sweep(win_strong, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3,
-                               torch.from_numpy(thr_all[k0:k1]).to(dev), torch.from_numpy(win_all[k0:k1]).to(dev), weighting,
-                               (k1 - k0) * cap)
+        if thresholds_high is not None:                                          # chunks of 2 x points sweep points
+            chunks = [(k0 // 2, k1 // 2) for k0, k1 in sweep_chunks(2 * K, cap, max_table_bytes, pair=True)]
+        else:
+            chunks = sweep_chunks(K, cap, max_table_bytes)
+        for k0, k1 in chunks:
+            if thresholds_high is not None:
+                out = stitch_hysteresis(win_strong, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3,
+                                        thr_all[k0:k1], thr_high[k0:k1], win_all[k0:k1], weighting, (k1 - k0) * cap)
+            else:
+                out = stitch_sweep(win_strong, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3,
+                                   torch.from_numpy(thr_all[k0:k1]).to(dev), torch.from_numpy(win_all[k0:k1]).to(dev), weighting,
+                                   (k1 - k0) * cap)
             long_sweep_event_counts(out, ref, long_set.pooling_time_ratio, cfg, counts=counts, point0=k0)
             if errors is not None:
                 long_sweep_error_counts(out, ref, long_set.pooling_time_ratio, cfg, counts=errors, point0=k0)

@@ -587,6 +587,53 @@ int sed_stitch_sweep(const float* win_strong, const int32_t* rec_win0, const int
                      float* timeline, int64_t* ev_ptr, int32_t* ev_pairs, long long capacity, void* ws, size_t ws_bytes,
                      int32_t* err, void* stream);
 
+/* ---- two-threshold (hysteresis) decode, in the event domain -------------------------------------
+ * A low threshold draws the event boundaries, a high threshold decides whether the event exists.  The definition is the
+ * project's own; pinned is exact agreement with a plain-loop numpy statement (tests/hysteresis_np.py).  Per column (point
+ * pair k, recording, class c), with thr_lo[k, c] <= thr_hi[k, c] and ONE median window win[k, c]:
+ *   E_lo = the event list sed_stitch_decode defines for (thr_lo, win)
+ *   E_hi = the event list sed_stitch_decode defines for (thr_hi, win)
+ *   the result is the events [on, off) of E_lo, in order, for which some event of E_hi has on <= on_hi < off.
+ * Why this is hysteresis: P > thr is monotone in thr and a binary median filter is monotone in its input, so for the same
+ * window the filtered high decisions are a subset of the filtered low ones and every event of E_hi lies inside exactly one
+ * event of E_lo.  Consequences:
+ *   thr_hi == thr_lo reproduces sed_stitch_decode's table byte for byte (ev_ptr and the ev_pairs in front of ev_ptr's end).
+ *   win == 1: frame-domain hysteresis with strict > on both thresholds - the connected runs of P > thr_lo that hold a frame
+ *     with P > thr_hi (the semantics of skimage.filters.apply_hysteresis_threshold; no parity with that package is claimed,
+ *     pinned is agreement with scipy.ndimage.label on the low decisions).
+ *   win > 1: the rule is "filter both decisions, then select".  It is NOT "hysteresis, then filter": the two differ where
+ *     the filter removes or merges what the frame-domain rule would have kept apart.
+ *   NaN posteriors decide 0 at both thresholds (sed_stitch_decode's decision).
+ * sed_events_hysteresis is the select alone, on two event tables that share one pairs array:
+ *   lo_ptr, hi_ptr [n_cols + 1] int64  CSR offsets into pairs; for a sed_stitch_sweep of 2K points ordered [lo_0 .. lo_{K-1},
+ *                                      hi_0 .. hi_{K-1}] they are ev_ptr and ev_ptr + K * n_rec * NC, n_cols = K * n_rec * NC
+ *   pairs   [pairs_capacity][2] int32  (onset, exclusive offset), onsets strictly increasing inside a column
+ *   out_ptr [n_cols + 1] int64         CSR offsets of the kept events, column for column: ALWAYS the true counts
+ *   out_pairs [out_capacity][2] int32  the kept events; must not be `pairs`
+ *   err     one int32, OR-ed (the bit meanings follow the stitch entries; zero it first or hand over the sweep's word):
+ *              2 = more kept events than out_capacity: nothing is written at or beyond it, never a truncated table
+ *             16 = a column whose bounds in lo_ptr or hi_ptr are not 0 <= ptr[c] <= ptr[c + 1] <= pairs_capacity: the column is
+ *                  skipped (none of its events is kept).  A lo_ptr that is not non-decreasing can moreover leave events that
+ *                  the bisection assigns to no column: they are dropped.  (A sweep that overflowed its own capacity raises
+ *                  this bit here too: its ev_ptr runs past pairs_capacity.)
+ *             64 = onsets that do not strictly increase inside a lo or a hi column: what that column keeps is undefined
+ *            No table content can make a kernel address outside lo_ptr / hi_ptr [0, n_cols], pairs [0, pairs_capacity) or
+ *            the outputs: every offset is validated before it is used as an index.  A caller must treat every output as
+ *            invalid when err != 0.
+ *   ws      sed_events_hysteresis_ws_bytes(pairs_capacity, n_cols) bytes, 8-byte aligned; ws_bytes must be that value
+ * The work is flat over the indices of pairs, not over columns (a column has no length limit): a flag pass (a thread finds
+ * the low column of its index by bisection over lo_ptr, bisects that column of the high table for the first onset >= its
+ * own; wave ballots, one count per workgroup), a one-workgroup scan of the counts, a write pass.  Three launches on `stream`
+ * whatever n_cols is (two when pairs_capacity is 0), grids sized from pairs_capacity.  No host synchronisation, no
+ * allocation, no atomics but the OR into err, integer results bit-reproducible, hipGraph-capturable.
+ * Limits, checked before any launch (SED_ERR_BAD_ARG; a wrong ws_bytes: SED_ERR_WORKSPACE): 1 <= n_cols < 2^26,
+ * 0 <= pairs_capacity < 2^31, pairs / out_pairs / ws 8-byte aligned, no null pointer.
+ * Not provided: "hysteresis, then filter", different windows for the two thresholds, a binary timeline. */
+size_t sed_events_hysteresis_ws_bytes(long long pairs_capacity, long long n_cols);
+int sed_events_hysteresis(const int64_t* lo_ptr, const int64_t* hi_ptr, const int32_t* pairs, long long pairs_capacity,
+                          long long n_cols, int64_t* out_ptr, int32_t* out_pairs, long long out_capacity, void* ws,
+                          size_t ws_bytes, int32_t* err, void* stream);
+
 /* ---- recording-level weak tags of long recordings -------------------------------------------------
  * A window's `weak` is a ratio num / den of attention-pooled sums (models/CRNN.py:79-81); the ratios of overlapping
  * windows cannot be combined into the recording's ratio without the attention mass per frame.  sed_stitch_weak pools over

@@ -67,7 +67,16 @@ references and hop as --scoring:
   The operating points start at the first of --scoring's 50 thresholds from which no cluster of a recording's events of ALL
   classes merged exceeds 64 per side; the largest merged cluster met is reported.
 
-Usage: python tools/long_bench.py [--scoring | --sweep | --weak | --tag-train | --error-rate] [--rounds 5] [--decode-reps 30] [--out profiles/long_inference.json]"""
+--hysteresis measures the two-threshold decode (profiles/long_hysteresis.json), same workloads, references, hop and 50 low
+thresholds as --scoring; the high threshold of a pair lies halfway between its low one and the 0.99 quantile:
+  validate_long(thresholds_high=...) at the 50 pairs against the same run's validate_long at the 50 low thresholds, the two legs
+    alternated in one run, --rounds rounds, medians, spread = (max - min) / median: what hysteresis adds to work already paid
+    for; the difference counts only where it lies outside the larger (max - min) of its two legs.
+  sed_events_hysteresis alone on the table of one 100-point sweep (a device-event pair around the Python call, median of
+    --decode-reps) against the only route there was before it: both tables copied to the host, a vectorised numpy select,
+    the result uploaded again (host clock, same reps); the two routes' tables are compared.
+
+Usage: python tools/long_bench.py [--scoring | --sweep | --weak | --tag-train | --error-rate | --hysteresis] [--rounds 5] [--decode-reps 30] [--out profiles/long_inference.json]"""
 import argparse
 import json
 import os
@@ -531,6 +540,81 @@ def error_rate_workload(name, model, rounds, reps):
     return out
 
 
+def host_select(ev_ptr, pairs, n_cols):
+    """The two-threshold select on the host, vectorised: the table of 2 x n_cols columns [lo | hi] as numpy arrays ->
+    (out_ptr, out_pairs).  One searchsorted over (column, onset) keys: the first high onset >= the low onset, in the same
+    column and in front of the low offset."""
+    n_lo, n_all = int(ev_ptr[n_cols]), int(ev_ptr[2 * n_cols])
+    col = np.repeat(np.arange(2 * n_cols, dtype=np.int64), np.diff(ev_ptr))
+    key = (col % n_cols) << 32
+    lo_on, lo_off, hi_on = key[:n_lo] + pairs[:n_lo, 0], key[:n_lo] + pairs[:n_lo, 1], key[n_lo:n_all] + pairs[n_lo:n_all, 0]
+    j = np.searchsorted(hi_on, lo_on, side="left")
+    keep = (j < len(hi_on)) & (np.r_[hi_on, 0][j] < lo_off)
+    out_ptr = np.r_[0, np.cumsum(keep)][ev_ptr[:n_cols + 1]]
+    return out_ptr.astype(np.int64), pairs[:n_lo][keep]
+
+
+def hysteresis_workload(name, model, rounds, reps):
+    """(a) validate_long at 50 threshold pairs against the same run's validate_long at the same 50 low thresholds, alternated;
+    (b) sed_events_hysteresis alone on the 100-point table against the host route (both tables copied down, the numpy select,
+    the result uploaded).  The high threshold of a pair lies halfway between its low one and the workload's 0.99 quantile."""
+    from dcase2019_task4_amd import metrics
+    info, ctx = scoring_workload(name, model, rounds, reps, setup_only=True)
+    ls, ref_ev, window, win_strong = ctx["ls"], ctx["ref_ev"], ctx["window"], ctx["win_strong"]
+    lo50 = ctx["thr50"]
+    hi50 = [t + 0.5 * (lo50[-1] - t) for t in lo50]
+    out = {k: info[k] for k in ("recordings", "windows", "timeline_frames", "median_window", "reference_events")}
+    out.update(rounds=rounds, pairs=50)
+    state = {}
+    legs = {"validate_long_50": lambda: state.__setitem__("plain", metrics.validate_long(model, ls, ref_ev, lo50, [window],
+                                                                                          batch_size=BATCH)),
+            "validate_long_50_hysteresis": lambda: state.__setitem__("hyst", metrics.validate_long(
+                model, ls, ref_ev, lo50, [window], batch_size=BATCH, thresholds_high=hi50))}
+    for fn in legs.values():
+        fn()
+    ms = {leg: [] for leg in legs}
+    for _ in range(rounds):
+        for leg, fn in legs.items():
+            ms[leg].append(wall_ms(fn))
+    t = {leg: stats(ms[leg]) for leg in legs}
+    a, b = t["validate_long_50"], t["validate_long_50_hysteresis"]
+    band = max(max(x["samples_ms"]) - min(x["samples_ms"]) for x in (a, b))
+    t["difference"] = {"added_ms": b["median_ms"] - a["median_ms"], "larger_max_minus_min_ms": band,
+                       "outside_the_band": bool(abs(b["median_ms"] - a["median_ms"]) > band)}
+    t["estimated_events_point_0"] = {what: int(sum(v["Nsys"] for v in state[what][0][0].class_wise.values()))
+                                     for what in ("plain", "hyst")}
+    out["validate_long"] = t
+    # (b) the select alone, on the table of one sweep of 100 points [lo_0 .. lo_49, hi_0 .. hi_49]
+    cap, n_cols = ls.capacity(NCLASS), 50 * ls.n_rec * NCLASS
+    table = inference.stitch_sweep(win_strong, ls.rec_win0, ls.rec_frame0, ls.total_frames, ls.hop3, lo50 + hi50, [window], "taper",
+                                   100 * cap)
+    assert int(table["err"].item()) == 0
+    ev_ptr, pairs = table["ev_ptr"], table["ev_pairs"]
+    lo_ptr, hi_ptr = ev_ptr[:n_cols + 1], ev_ptr[n_cols:]
+
+    def device():
+        state["dev"] = inference.events_hysteresis(lo_ptr, hi_ptr, pairs, 50 * cap)
+
+    def host():
+        p = ev_ptr.cpu().numpy()
+        q = pairs[:int(p[-1])].cpu().numpy()
+        out_ptr, out_pairs = host_select(p, q, n_cols)
+        state["host"] = (torch.from_numpy(out_ptr).cuda(), torch.from_numpy(np.ascontiguousarray(out_pairs)).cuda())
+    for _ in range(3):
+        host()
+    host_ms = stats([wall_ms(host) for _ in range(reps)])
+    out["select_alone"] = {"sed_events_hysteresis": event_ms(device, reps),
+                           "host_copy_numpy_select_upload": {"median_ms": host_ms["median_ms"], "spread": host_ms["spread"],
+                                                             "reps": reps, "timing": "host clock around the synchronised route"}}
+    d_ptr, d_pairs, d_err = state["dev"]
+    h_ptr, h_pairs = state["host"]
+    n = int(h_ptr[-1].item())
+    out["select_alone"].update(low_events=int(ev_ptr[n_cols].item()), high_events=int((ev_ptr[-1] - ev_ptr[n_cols]).item()),
+                               kept_events=n, err=int(d_err.item()),
+                               routes_identical=bool(torch.equal(d_ptr, h_ptr) and torch.equal(d_pairs[:n], h_pairs)))
+    return out
+
+
 def weak_workload(name, model, rounds, reps):
     import ctypes as C
     n_rec, per = WORKLOADS[name]
@@ -729,6 +813,8 @@ def main():
                     help="measure the backward through the pooled tag and an epoch on recording tags (profiles/long_tag_train.json)")
     ap.add_argument("--error-rate", action="store_true",
                     help="measure what validate_long(error_rate=True) adds (the \"long\" key of profiles/error_rate.json)")
+    ap.add_argument("--hysteresis", action="store_true",
+                    help="measure the two-threshold decode (profiles/long_hysteresis.json)")
     ap.add_argument("--sweep-decode-only", action="store_true", help="with --sweep: sed_stitch_sweep alone (a variant build)")
     ap.add_argument("--sweep-out", default=os.path.join(REPO, "profiles", "long_sweep.json"))
     ap.add_argument("--candidates", default="", help="with --sweep: earlier --sweep-decode-only results to copy in")
@@ -738,7 +824,8 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(REPO, "profiles", "error_rate.json" if args.error_rate else
+        args.out = os.path.join(REPO, "profiles", "long_hysteresis.json" if args.hysteresis else
+                                "error_rate.json" if args.error_rate else
                                 "long_tag_train.json" if args.tag_train else "long_weak.json" if args.weak else
                                 "long_scoring.json" if args.scoring else "long_inference.json")
     if not torch.cuda.is_available():
@@ -754,6 +841,23 @@ def main():
               "not_measured": ["from_waveforms / feature extraction", "other batch sizes, bf16 / wide models",
                                "recordings longer than 1 h", "a run with the GPU to itself (the host is shared)"],
               "workloads": {}}
+    if args.hysteresis:
+        result["timing"] = ("validate_long legs: host clock around each synchronised call, the two legs alternated in one run, "
+                            "--rounds rounds, medians, spread = (max - min) / median; sed_events_hysteresis alone: a device-event "
+                            "pair around the Python call (output and workspace allocation, three launches), warm, median of "
+                            "--decode-reps; the host route: host clock around the synchronised route, same reps")
+        result["note"] = ("validate_long(thresholds_high=...) at 50 pairs against the same run's validate_long at the same 50 low "
+                          "thresholds; a difference counts only where it lies outside the larger (max - min) of its two legs.  The "
+                          "host route is the only one there was before sed_events_hysteresis")
+        result["not_measured"] += ["other K than 50", "other median windows", "the kernels one by one", "with PSDS, weak tags or "
+                                   "the error rate", "max_table_bytes small enough to split the pairs into chunks"]
+        for name in args.workloads.split(","):
+            result["workloads"][name] = hysteresis_workload(name, model, args.rounds, args.decode_reps)
+            print(json.dumps({name: result["workloads"][name]}), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(json.dumps(result, indent=1) + "\n")
+        return
     if args.error_rate:
         result["timing"] = ("validate_long legs: host clock around each synchronised call, the two legs alternated in one run, "
                             "--rounds rounds, medians, spread = (max - min) / median; the calls alone: a device-event pair around "
