@@ -17,8 +17,10 @@ windows' posteriors and attention (``CRNN.last_attention``, ``sed_stitch_weak``)
 ``metrics.validate_long(weak_labels=...)`` their score; ``pooled_tags`` is the same tag with a backward
 (``sed_stitch_weak_backward``), what ``train.train_recording_tags`` trains on.  Two-threshold (hysteresis) decode:
 ``stitch_hysteresis`` / ``get_long_predictions(threshold_high=...)`` keep the low-threshold events in which a high-threshold
-event starts (one ``stitch_sweep`` of both thresholds, then ``sed_events_hysteresis``).  ``get_predictions`` itself is
-unchanged.
+event starts (one ``stitch_sweep`` of both thresholds, then ``sed_events_hysteresis``).  Minimum event length and gap
+merging: ``events_process`` / ``get_long_predictions(min_event_length=..., min_event_gap=...)`` drop short events and fuse
+events across short gaps on any of these tables (``sed_events_process``; ``process_points`` turns seconds into frames).
+``get_predictions`` itself is unchanged.
 """
 import ctypes as C
 
@@ -149,7 +151,8 @@ def get_predictions(model, valid_dataset, decoder, pooling_time_ratio=1, save_pr
 
 STITCH_ERR_BITS = {2: "more events than the capacity of ev_pairs", 8: "a median window outside 1 .. 63",
                    16: "malformed rec_win0 / rec_frame0 tables", 32: "a recording with too few windows to cover it",
-                   64: "event onsets that do not strictly increase inside a column (sed_events_hysteresis)"}
+                   64: "events that are not sorted and disjoint inside a column (sed_events_hysteresis: onsets that do not "
+                       "strictly increase; sed_events_process)"}
 
 
 def stitch_error_text(entry, err):
@@ -343,6 +346,95 @@ def stitch_hysteresis(win_strong, rec_win0, rec_frame0, total_frames, hop3, thre
     return {"ev_ptr": ev_ptr, "ev_pairs": ev_pairs, "err": err, "timeline": out["timeline"], "binary": None, "n_points": K}
 
 
+PROCESS_ORDERS = {"drop_merge": 0, "merge_drop": 1}
+
+
+def _order_code(order):
+    if order not in PROCESS_ORDERS:
+        raise ValueError(f"order must be one of {sorted(PROCESS_ORDERS)}, got {order!r}")
+    return PROCESS_ORDERS[order]
+
+
+def process_points(min_event_lengths, min_event_gaps, nclass, frame_seconds, K):
+    """Minimum event lengths and gaps in seconds as the host arrays ``(min_len [K, nclass] int32, max_gap [K, nclass] int32)``
+    in label frames of ``frame_seconds`` each, the parameters of ``events_process``.  Entries as in ``sweep_points``: sequences
+    of K entries or one, every entry a scalar or one value per class; ``None`` disables that half (``min_len = 0``,
+    ``max_gap = -1``).  ``min_len = ceil(length / frame_seconds - 1e-9)``: an event must last at least ``length``;
+    ``max_gap = floor(gap / frame_seconds + 1e-9)``: gaps up to ``gap`` are closed.  ValueError for negative or NaN seconds
+    and for wrong lengths."""
+    K, frame_seconds = int(K), float(frame_seconds)
+    if K < 1 or not frame_seconds > 0:
+        raise ValueError("process_points: K >= 1 and frame_seconds > 0 expected")
+
+    def frames(entries, what, disabled, to_frames):
+        if entries is None:
+            return np.full((K, nclass), disabled, dtype=np.int32)
+        entries = list(entries)
+        if len(entries) not in (1, K):
+            raise ValueError(f"{what} must have {K} entries (or one)")
+        sec = np.stack([_per_class(entries[k % len(entries)], nclass, np.float64, what) for k in range(K)])
+        if not (sec >= 0).all() or not np.isfinite(sec).all():
+            raise ValueError(f"{what}: finite seconds >= 0 expected")
+        fr = to_frames(sec / frame_seconds)
+        if (fr >= 2 ** 31).any():
+            raise ValueError(f"{what}: more than 2^31 frames")
+        return np.ascontiguousarray(fr.astype(np.int32))
+
+    return (frames(min_event_lengths, "min_event_lengths", 0, lambda f: np.ceil(f - 1e-9)),
+            frames(min_event_gaps, "min_event_gaps", -1, lambda f: np.floor(f + 1e-9)))
+
+
+def events_process(ev_ptr, ev_pairs, n_rec, nclass, min_len, max_gap, order="drop_merge", capacity=None, err=None):
+    """``sed_events_process``: minimum event length and gap merging on a CSR event table on the device - ``ev_ptr``
+    [K * n_rec * nclass + 1] int64 in the sweep's column order, ``ev_pairs`` [pairs_capacity, 2] int32 (the table of
+    ``stitch_decode``, ``stitch_sweep`` or ``stitch_hysteresis``).  ``min_len`` / ``max_gap``: label frames, host ``[K, nclass]``
+    arrays (``process_points`` makes them from seconds) or device int32 tensors.  ``order``: ``"drop_merge"`` (drop the events
+    shorter than ``min_len``, then fuse those a gap of at most ``max_gap`` separates) or ``"merge_drop"``; the definition is
+    in include/dcase_sed.h.  Returns ``(out_ptr [n_cols + 1] int64, out_pairs [capacity, 2] int32, err [1] int32)``;
+    ``capacity`` defaults to ``pairs_capacity`` (the result never has more events than the input), ``err`` to a new zeroed
+    word - a given one is OR-ed into.  Five launches, nothing synchronises."""
+    order = _order_code(order)
+    if ev_pairs.device.type != "cuda":
+        raise _lib.SedError("events_process needs GPU tensors (no CPU fallback)")
+    n_rec, nclass = int(n_rec), int(nclass)
+    if (ev_ptr.dtype, ev_pairs.dtype) != (torch.int64, torch.int32) or ev_ptr.numel() < 2 or ev_pairs.dim() != 2 \
+            or ev_pairs.shape[1] != 2:
+        raise ValueError("events_process: ev_ptr int64 [n_cols + 1] and ev_pairs int32 [capacity, 2] expected")
+    n_cols, pairs_cap = ev_ptr.numel() - 1, ev_pairs.shape[0]
+    if n_rec < 1 or nclass < 1 or n_cols % (n_rec * nclass):
+        raise ValueError(f"events_process: {n_cols} columns are no multiple of {n_rec} recordings x {nclass} classes")
+    K = n_cols // (n_rec * nclass)
+    dev, ev_pairs, ev_ptr = ev_pairs.device, ev_pairs.contiguous(), ev_ptr.contiguous()
+    params = []
+    for name, p in (("min_len", min_len), ("max_gap", max_gap)):
+        if not torch.is_tensor(p):
+            p = torch.from_numpy(np.ascontiguousarray(np.asarray(p, dtype=np.int32).reshape(-1))).to(dev)
+        if p.device != dev or p.dtype != torch.int32 or p.numel() != K * nclass:
+            raise ValueError(f"events_process: {name} must be int32 [{K}, {nclass}] (host array or tensor on the table's device)")
+        params.append(p.contiguous())
+    capacity = pairs_cap if capacity is None else int(capacity)
+    l = _lib.lib()
+    ws_bytes = l.sed_events_process_ws_bytes(pairs_cap, n_cols)
+    if ws_bytes == 0:
+        raise ValueError(f"sed_events_process_ws_bytes: {l.sed_last_error().decode()}")
+    out_ptr = torch.empty(n_cols + 1, dtype=torch.int64, device=dev)
+    out_pairs = torch.empty(max(capacity, 1), 2, dtype=torch.int32, device=dev)
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = _lib.scratch(ws_bytes, dev)
+    _lib.check(l.sed_events_process(_lib.ptr(ev_ptr), _lib.ptr(ev_pairs), pairs_cap, n_cols, n_rec, nclass, _lib.ptr(params[0]),
+                                    _lib.ptr(params[1]), order, _lib.ptr(out_ptr), _lib.ptr(out_pairs), capacity, _lib.ptr(ws),
+                                    ws.numel(), _lib.ptr(err), _lib.stream_ptr()), "sed_events_process")
+    return out_ptr, out_pairs, err
+
+
+def process_decoded(out, n_rec, nclass, min_len, max_gap, order="drop_merge"):
+    """``events_process`` on the dict a stitch entry returned: the same dict with the processed table (same capacity), its
+    ``err`` the decode's own word with the step's bits OR-ed in on the device."""
+    ev_ptr, ev_pairs, err = events_process(out["ev_ptr"], out["ev_pairs"], n_rec, nclass, min_len, max_gap, order, err=out["err"])
+    return dict(out, ev_ptr=ev_ptr, ev_pairs=ev_pairs, err=err)
+
+
 def _weak_inputs(who, win_strong, win_att, rec_win0, total_frames, hop3, weighting, n_win=None):
     """The input checks of ``stitch_weak`` and ``pooled_tags`` (``who``; ``n_win``: the latter's host-side window count).
     Returns ``(total_frames, hop3, the weighting's code)`` as ints."""
@@ -477,7 +569,8 @@ def long_window_posteriors(model, long_set, nclass, batch_size=64, want_attentio
 
 def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=None, save_predictions=None, batch_size=64,
                          cfg=None, threshold=0.5, median_window=None, weighting="taper", return_posteriors=False,
-                         return_weak=False, threshold_high=None):
+                         return_weak=False, threshold_high=None, min_event_length=None, min_event_gap=None,
+                         process_order="drop_merge"):
     """Events of recordings of any lengths (a ``LongRecordingSet``): the windows go through the eval-mode model
     ``batch_size`` at a time, their strong posteriors are blended into one timeline per recording (``weighting``: "taper"
     or "uniform"), and ONE threshold, median filter and run-length decode runs over each whole timeline
@@ -492,7 +585,11 @@ def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=
     [n_rec, nclass] (a device tensor; ``stitch_weak`` on the same single pass through the model) are appended to what is
     returned; ``weak_tags_dataframe`` turns them into the weak-label table.  ``threshold_high`` (a scalar or one value per
     class, ``>= threshold``): the two-threshold decode of ``stitch_hysteresis`` at one pair - ``threshold`` draws the events,
-    an event is kept when ``threshold_high`` confirms it; None changes nothing."""
+    an event is kept when ``threshold_high`` confirms it; None changes nothing.  ``min_event_length`` / ``min_event_gap``
+    (seconds, each a scalar or one value per class): events shorter than the length are dropped and events a gap of at most
+    ``min_event_gap`` separates are fused, in the order ``process_order`` ("drop_merge" or "merge_drop") - one
+    ``events_process`` on the decoded table (after the two-threshold select when ``threshold_high`` is given), in frames of
+    ``pooling_time_ratio * hop_length / sample_rate`` seconds (``process_points``).  Both None: no launch, the same frame."""
     if not isinstance(long_set, LongRecordingSet):
         raise TypeError(f"long_set must be a LongRecordingSet, got {type(long_set).__name__}")
     cfg = cfg or _Cfg
@@ -512,6 +609,12 @@ def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=
     win = _per_class(cfg.median_window if median_window is None else median_window, NC, np.int32, "median_window")
     if threshold_high is not None:
         hysteresis_points([thr], [threshold_high], [win], NC)                    # (ValueError before any forward)
+    process = min_event_length is not None or min_event_gap is not None
+    if process:
+        _order_code(process_order)
+        min_len, max_gap = process_points(None if min_event_length is None else [min_event_length],
+                                          None if min_event_gap is None else [min_event_gap], NC,
+                                          pool * cfg.hop_length / cfg.sample_rate, 1)
     win_strong = long_window_posteriors(model, long_set, NC, batch_size, want_attention=return_weak)
     if return_weak:
         win_strong, win_att = win_strong
@@ -523,6 +626,9 @@ def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=
         out = stitch_hysteresis(win_strong, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3, [thr],
                                 [threshold_high], [win], weighting, long_set.capacity(NC), want_timeline=return_posteriors)
         calls = [("sed_stitch_sweep + sed_events_hysteresis", out["err"])]
+    if process:
+        out = process_decoded(out, long_set.n_rec, NC, min_len, max_gap, process_order)
+        calls = [(calls[0][0] + " + sed_events_process", out["err"])]
     if return_weak:
         tags = stitch_weak(win_strong, win_att, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3,
                            weighting)

@@ -55,7 +55,9 @@ nothing is truncated.  K operating points: ``long_sweep_event_counts`` / ``long_
 pools them once (``inference.stitch_weak``) and scores them with ``weak_counts``.  The overall error rate:
 ``validate_long(error_rate=True)`` (``sed_long_error_counts`` / ``sed_long_sweep_error_counts``, six launches whatever K is, the
 reference side merged once).  Two-threshold decode: ``validate_long(thresholds_high=...)`` scores the table of
-``inference.stitch_hysteresis`` with the same sweep scorers.  Not provided there: an exact matching of clusters beyond 64 per
+``inference.stitch_hysteresis`` with the same sweep scorers.  Minimum event length and gap merging:
+``validate_long(min_event_lengths=..., min_event_gaps=...)`` puts every decoded table through ``inference.events_process``
+in front of the same scorers.  Not provided there: an exact matching of clusters beyond 64 per
 side.
 
 PSDS (polyphonic sound detection score, Bilen et al., ICASSP 2020): ``sed_psds_counts`` scores the same (operating point,
@@ -1017,7 +1019,7 @@ def long_sweep_psds_counts_from_events(ests, ref, dtc=0.5, gtc=0.5, cttc=0.3, co
 
 def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, batch_size=64, cfg=None, weighting="taper",
                   psds=None, one_blend=True, max_table_bytes=1 << 30, weak_labels=None, weak_thresholds=None, error_rate=False,
-                  thresholds_high=None):
+                  thresholds_high=None, min_event_lengths=None, min_event_gaps=None, process_order="drop_merge"):
     """``validate`` for a ``LongRecordingSet``: the windows go through the model ONCE, then the K operating points are
     decoded and scored, and ONE device -> host copy ends the call.  ``one_blend=True``: the points are split into chunks
     (``longrec.sweep_chunks``: the event table of a chunk stays within ``max_table_bytes``); per chunk ONE
@@ -1042,9 +1044,15 @@ def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, 
     when the high threshold confirms it).  The chunks are then made of 2 x points sweep points, so a pair never straddles a
     chunk, and per chunk one ``sed_events_hysteresis`` runs between the sweep and the same scorers.  ``one_blend=False``
     raises: the two decodes of a pair come from one sweep.  With ``thresholds_high=None`` nothing changes and no launch is
-    added."""
-    from .inference import (_per_class, hysteresis_points, long_window_posteriors, stitch_decode, stitch_error_text,
-                            stitch_hysteresis, stitch_sweep, stitch_weak, sweep_points)
+    added.
+    ``min_event_lengths`` / ``min_event_gaps``: seconds, K entries as ``thresholds`` (or one entry for all points; several
+    points may share a threshold and differ only here), each a scalar or one value per class: every decoded table goes
+    through ``inference.events_process`` (events shorter than the length dropped, events a gap of at most ``min_event_gaps``
+    separates fused, in the order ``process_order``) before the scorers - per chunk one call on the chunk's whole table, after
+    the two-threshold select; with ``one_blend=False`` one call per point.  Still one device -> host copy; both None: nothing
+    changes and no launch is added."""
+    from .inference import (_order_code, _per_class, hysteresis_points, long_window_posteriors, process_decoded, process_points,
+                            stitch_decode, stitch_error_text, stitch_hysteresis, stitch_sweep, stitch_weak, sweep_points)
     from .longrec import LongRecordingSet, sweep_chunks
     cfg = cfg or _Cfg
     thresholds = list(thresholds)
@@ -1083,6 +1091,11 @@ def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, 
     if long_set.n_rec != len(ref):
         raise ValueError(f"{long_set.n_rec} recordings but reference events of {len(ref)}")
     NC = ref.nclass
+    process = min_event_lengths is not None or min_event_gaps is not None
+    if process:
+        _order_code(process_order)
+        min_len, max_gap = process_points(min_event_lengths, min_event_gaps, ref.nclass,
+                                          long_set.pooling_time_ratio * cfg.hop_length / cfg.sample_rate, K)
     if psds is not None and (psds.K, psds.NC) != (K, NC):
         raise ValueError("psds was built for another number of operating points / classes")
     if thresholds_high is not None:
@@ -1109,6 +1122,8 @@ def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, 
                 out = stitch_sweep(win_strong, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3,
                                    torch.from_numpy(thr_all[k0:k1]).to(dev), torch.from_numpy(win_all[k0:k1]).to(dev), weighting,
                                    (k1 - k0) * cap)
+            if process:
+                out = process_decoded(out, long_set.n_rec, NC, min_len[k0:k1], max_gap[k0:k1], process_order)
             long_sweep_event_counts(out, ref, long_set.pooling_time_ratio, cfg, counts=counts, point0=k0)
             if errors is not None:
                 long_sweep_error_counts(out, ref, long_set.pooling_time_ratio, cfg, counts=errors, point0=k0)
@@ -1120,6 +1135,8 @@ def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, 
             out = stitch_decode(win_strong, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3,
                                 thresholds[k % len(thresholds)], median_windows[k % len(median_windows)], weighting,
                                 long_set.capacity(NC), want_timeline=False)
+            if process:
+                out = process_decoded(out, long_set.n_rec, NC, min_len[k:k + 1], max_gap[k:k + 1], process_order)
             long_event_counts(out, ref, long_set.pooling_time_ratio, cfg, counts=counts, point=k)
             if errors is not None:
                 long_error_counts(out, ref, long_set.pooling_time_ratio, cfg, counts=errors, point=k)

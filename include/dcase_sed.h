@@ -634,6 +634,60 @@ int sed_events_hysteresis(const int64_t* lo_ptr, const int64_t* hi_ptr, const in
                           long long n_cols, int64_t* out_ptr, int32_t* out_pairs, long long out_capacity, void* ws,
                           size_t ws_bytes, int32_t* err, void* stream);
 
+/* ---- minimum event length and gap merging, in the event domain --------------------------------------
+ * The post-processing step applied to a decoded event table: drop events shorter than a minimum length, fuse events that a
+ * short gap separates.  The definition is the project's own; pinned is exact agreement with a plain-loop numpy statement
+ * (tests/event_process_np.py), which in turn agrees with a frame-domain (raster) statement on tables whose gaps are at
+ * least 1 frame - every decode's.  Per column the events e_0 .. e_{n-1} are sorted and disjoint, on_i < off_i <= on_{i+1};
+ * each column has two int32 parameters in label frames, min_len (m) and max_gap (g):
+ *   DROP(m)   keeps the events with off - on >= m; m <= 0 keeps everything.
+ *   MERGE(g)  joins two consecutive events of the list it receives when on_next - off_prev <= g; a maximal chain becomes
+ *             one event [on_first, off_last).  g < 0 merges nothing, g = 0 fuses only abutting events.
+ *   order 0   DROP then MERGE (the order of dcase_util's process_events(minimum_event_length, minimum_event_gap); no
+ *             parity with that package is claimed).  The predecessor of a kept event is the previous KEPT event of its
+ *             column: two events fuse across any number of dropped ones when their gap is at most g.
+ *   order 1   MERGE then DROP: a binary closing followed by an opening.
+ * The two orders differ: with m = 3, g = 2 the list [0,1) [2,3) [4,5) becomes empty under order 0 and [0,5) under order 1.
+ * Both are idempotent.  With m <= 0 and g < 0 the output is the input byte for byte (ev_ptr, and the ev_pairs in front of its
+ * end).  All differences are formed in 64 bits.  The median filter does not replace this step: its window couples the two
+ * lengths, is symmetric and ends at 63.
+ *   ev_ptr  [n_cols + 1] int64         CSR offsets into pairs; n_cols = K * n_rec * NC in the sweep's column order
+ *                                      (k * n_rec + rec) * NC + c (K = 1: the table of sed_stitch_decode)
+ *   pairs   [pairs_capacity][2] int32  (onset, exclusive offset)
+ *   min_len, max_gap [K][NC] int32     device arrays; column col uses entry (col / (n_rec * NC)) * NC + col % NC
+ *   order   0 or 1
+ *   out_ptr [n_cols + 1] int64         CSR offsets of the result, column for column: ALWAYS the true counts
+ *   out_pairs [out_capacity][2] int32  the result; must not be `pairs`.  It never holds more events than the input.
+ *   err     one int32, OR-ed (the bits follow sed_events_hysteresis; zero it first or hand over the decode's own word):
+ *              2 = more result events than out_capacity: nothing is written at or beyond it
+ *             16 = a column whose bounds are not 0 <= ev_ptr[c] <= ev_ptr[c + 1] <= pairs_capacity: the column is skipped
+ *                  (none of its events reaches the result).  An ev_ptr that is not non-decreasing can moreover leave
+ *                  events that the bisection assigns to no column or to a neighbour: what the columns around the broken
+ *                  entry hold is undefined.
+ *             64 = a column that is not sorted and disjoint (some on >= off, or off > the next on): its result is undefined
+ *            No table content can make a kernel address outside ev_ptr [0, n_cols], pairs [0, pairs_capacity), the
+ *            parameter arrays or the outputs: every offset is validated before it is used as an index.  A caller must
+ *            treat every output as invalid when err != 0.
+ *   ws      sed_events_process_ws_bytes(pairs_capacity, n_cols) bytes, 8-byte aligned; ws_bytes must be that value
+ * The work is flat over the indices of pairs (a column has no length limit), on two flags per index.  Order 0: A = kept,
+ * B = head (a kept event without a kept predecessor in its column within g); a head's rank among the heads is its output
+ * slot, it writes its onset there and its predecessor's offset into the slot before, and the thread of a column writes the
+ * offset of the column's last kept event.  Order 1: A = head of a chain, B = a chain's last event whose merged event is at
+ * least m long; it writes the pair (onset of the last A at or before it, its own offset) at its rank.  "The last A index in
+ * front of p" is read from the ballot words of p's workgroup and a scanned per-workgroup maximum, so no thread's work grows
+ * with a column, a chain or a run of dropped events.  Five launches on `stream` whatever K, n_cols and the column lengths
+ * are (three when pairs_capacity is 0): flag A, scan (maximum), flag B, scan (sum; capacity check), write.  No host
+ * synchronisation, no allocation, no atomics but the OR into err, integer results bit-reproducible, hipGraph-capturable.
+ * Limits, checked before any launch (SED_ERR_BAD_ARG; a wrong ws_bytes: SED_ERR_WORKSPACE): 1 <= n_cols < 2^26,
+ * n_cols a multiple of n_rec * NC, n_rec >= 1, NC >= 1, 0 <= pairs_capacity < 2^31, out_capacity >= 0, pairs / out_pairs /
+ * ws 8-byte aligned, no null pointer.
+ * Not provided: a binary timeline, different orders per class, minimum lengths in front of the median filter. */
+size_t sed_events_process_ws_bytes(long long pairs_capacity, long long n_cols);
+int sed_events_process(const int64_t* ev_ptr, const int32_t* pairs, long long pairs_capacity, long long n_cols,
+                       int n_rec, int NC, const int32_t* min_len, const int32_t* max_gap, int order,
+                       int64_t* out_ptr, int32_t* out_pairs, long long out_capacity,
+                       void* ws, size_t ws_bytes, int32_t* err, void* stream);
+
 /* ---- recording-level weak tags of long recordings -------------------------------------------------
  * A window's `weak` is a ratio num / den of attention-pooled sums (models/CRNN.py:79-81); the ratios of overlapping
  * windows cannot be combined into the recording's ratio without the attention mass per frame.  sed_stitch_weak pools over

@@ -76,7 +76,16 @@ thresholds as --scoring; the high threshold of a pair lies halfway between its l
     --decode-reps) against the only route there was before it: both tables copied to the host, a vectorised numpy select,
     the result uploaded again (host clock, same reps); the two routes' tables are compared.
 
-Usage: python tools/long_bench.py [--scoring | --sweep | --weak | --tag-train | --error-rate | --hysteresis] [--rounds 5] [--decode-reps 30] [--out profiles/long_inference.json]"""
+--process measures minimum event length and gap merging (profiles/long_process.json), same workloads, references, hop and 50
+thresholds as --scoring, min_event_length 0.25 s and min_event_gap 0.15 s at every point, order "drop_merge":
+  validate_long(min_event_lengths=..., min_event_gaps=...) against the same run's validate_long without them, the two legs
+    alternated in one run, --rounds rounds, medians, spread = (max - min) / median; the difference counts only where it lies
+    outside the larger (max - min) of its two legs.
+  sed_events_process alone on the table of one 50-point sweep (a device-event pair around the Python call, median of
+    --decode-reps) against the only route there was before it: the table copied to the host, a vectorised numpy restatement,
+    the result uploaded again (host clock, same reps); the two routes' tables are compared.
+
+Usage: python tools/long_bench.py [--scoring | --sweep | --weak | --tag-train | --error-rate | --hysteresis | --process] [--rounds 5] [--decode-reps 30] [--out profiles/long_inference.json]"""
 import argparse
 import json
 import os
@@ -615,6 +624,86 @@ def hysteresis_workload(name, model, rounds, reps):
     return out
 
 
+def host_process(ev_ptr, pairs, n_rec, NC, min_len, max_gap):
+    """Minimum length, then gap merging (order 0) on the host, vectorised over the whole flat table: numpy arrays ->
+    (out_ptr, out_pairs)."""
+    n_cols = len(ev_ptr) - 1
+    col = np.repeat(np.arange(n_cols, dtype=np.int64), np.diff(ev_ptr))
+    par = (col // (n_rec * NC)) * NC + col % NC
+    on, off = pairs[:, 0].astype(np.int64), pairs[:, 1].astype(np.int64)
+    m = min_len.reshape(-1).astype(np.int64)[par]
+    keep = (m <= 0) | (off - on >= m)
+    on, off, col = on[keep], off[keep], col[keep]
+    g = max_gap.reshape(-1).astype(np.int64)[par[keep]]
+    head = np.ones(len(on), dtype=bool)
+    head[1:] = (col[1:] != col[:-1]) | (on[1:] - off[:-1] > g[1:])
+    tail = np.r_[head[1:], True] if len(on) else head
+    out_ptr = np.r_[0, np.cumsum(np.bincount(col[head], minlength=n_cols))].astype(np.int64)
+    return out_ptr, np.stack([on[head], off[tail]], 1).astype(np.int32)
+
+
+def process_workload(name, model, rounds, reps, seconds=(0.25, 0.15), order="drop_merge"):
+    """(a) validate_long at 50 thresholds with a minimum event length and gap against the same run's validate_long without
+    them, alternated; (b) sed_events_process alone on the 50-point table against the host route (the table copied down, the
+    numpy restatement, the result uploaded)."""
+    from dcase2019_task4_amd import metrics
+    info, ctx = scoring_workload(name, model, rounds, reps, setup_only=True)
+    ls, ref_ev, window, win_strong, thr50 = ctx["ls"], ctx["ref_ev"], ctx["window"], ctx["win_strong"], ctx["thr50"]
+    out = {k: info[k] for k in ("recordings", "windows", "timeline_frames", "median_window", "reference_events")}
+    frame_seconds = ls.pooling_time_ratio * inference._Cfg.hop_length / inference._Cfg.sample_rate
+    min_len, max_gap = inference.process_points([seconds[0]], [seconds[1]], NCLASS, frame_seconds, 50)
+    out.update(rounds=rounds, points=50, min_event_length_s=seconds[0], min_event_gap_s=seconds[1], order=order,
+               min_len_frames=int(min_len[0, 0]), max_gap_frames=int(max_gap[0, 0]))
+    state = {}
+    legs = {"validate_long_50": lambda: state.__setitem__("plain", metrics.validate_long(model, ls, ref_ev, thr50, [window],
+                                                                                          batch_size=BATCH)),
+            "validate_long_50_process": lambda: state.__setitem__("proc", metrics.validate_long(
+                model, ls, ref_ev, thr50, [window], batch_size=BATCH, min_event_lengths=[seconds[0]], min_event_gaps=[seconds[1]],
+                process_order=order))}
+    for fn in legs.values():
+        fn()
+    ms = {leg: [] for leg in legs}
+    for _ in range(rounds):
+        for leg, fn in legs.items():
+            ms[leg].append(wall_ms(fn))
+    t = {leg: stats(ms[leg]) for leg in legs}
+    a, b = t["validate_long_50"], t["validate_long_50_process"]
+    band = max(max(x["samples_ms"]) - min(x["samples_ms"]) for x in (a, b))
+    t["difference"] = {"added_ms": b["median_ms"] - a["median_ms"], "larger_max_minus_min_ms": band,
+                       "outside_the_band": bool(abs(b["median_ms"] - a["median_ms"]) > band)}
+    t["estimated_events_point_0"] = {what: int(sum(v["Nsys"] for v in state[what][0][0].class_wise.values()))
+                                     for what in ("plain", "proc")}
+    out["validate_long"] = t
+    # (b) the call alone, on the table of one sweep of the 50 points
+    cap = ls.capacity(NCLASS)
+    table = inference.stitch_sweep(win_strong, ls.rec_win0, ls.rec_frame0, ls.total_frames, ls.hop3, thr50, [window], "taper", 50 * cap)
+    assert int(table["err"].item()) == 0
+    ev_ptr, pairs = table["ev_ptr"], table["ev_pairs"]
+    d_len, d_gap = torch.from_numpy(min_len).cuda(), torch.from_numpy(max_gap).cuda()
+
+    def device():
+        state["dev"] = inference.events_process(ev_ptr, pairs, ls.n_rec, NCLASS, d_len, d_gap, order)
+
+    def host():
+        p = ev_ptr.cpu().numpy()
+        q = pairs[:int(p[-1])].cpu().numpy()
+        out_ptr, out_pairs = host_process(p, q, ls.n_rec, NCLASS, min_len, max_gap)
+        state["host"] = (torch.from_numpy(out_ptr).cuda(), torch.from_numpy(np.ascontiguousarray(out_pairs)).cuda())
+    for _ in range(3):
+        host()
+    host_ms = stats([wall_ms(host) for _ in range(reps)])
+    out["process_alone"] = {"sed_events_process": event_ms(device, reps),
+                            "host_copy_numpy_process_upload": {"median_ms": host_ms["median_ms"], "spread": host_ms["spread"],
+                                                               "reps": reps, "timing": "host clock around the synchronised route"}}
+    d_ptr, d_pairs, d_err = state["dev"]
+    h_ptr, h_pairs = state["host"]
+    n = int(h_ptr[-1].item())
+    out["process_alone"].update(pairs_capacity=int(pairs.shape[0]), input_events=int(ev_ptr[-1].item()), result_events=n,
+                                err=int(d_err.item()),
+                                routes_identical=bool(torch.equal(d_ptr, h_ptr) and torch.equal(d_pairs[:n], h_pairs)))
+    return out
+
+
 def weak_workload(name, model, rounds, reps):
     import ctypes as C
     n_rec, per = WORKLOADS[name]
@@ -815,6 +904,8 @@ def main():
                     help="measure what validate_long(error_rate=True) adds (the \"long\" key of profiles/error_rate.json)")
     ap.add_argument("--hysteresis", action="store_true",
                     help="measure the two-threshold decode (profiles/long_hysteresis.json)")
+    ap.add_argument("--process", action="store_true",
+                    help="measure minimum event length and gap merging (profiles/long_process.json)")
     ap.add_argument("--sweep-decode-only", action="store_true", help="with --sweep: sed_stitch_sweep alone (a variant build)")
     ap.add_argument("--sweep-out", default=os.path.join(REPO, "profiles", "long_sweep.json"))
     ap.add_argument("--candidates", default="", help="with --sweep: earlier --sweep-decode-only results to copy in")
@@ -824,7 +915,8 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(REPO, "profiles", "long_hysteresis.json" if args.hysteresis else
+        args.out = os.path.join(REPO, "profiles", "long_process.json" if args.process else
+                                "long_hysteresis.json" if args.hysteresis else
                                 "error_rate.json" if args.error_rate else
                                 "long_tag_train.json" if args.tag_train else "long_weak.json" if args.weak else
                                 "long_scoring.json" if args.scoring else "long_inference.json")
@@ -841,6 +933,25 @@ def main():
               "not_measured": ["from_waveforms / feature extraction", "other batch sizes, bf16 / wide models",
                                "recordings longer than 1 h", "a run with the GPU to itself (the host is shared)"],
               "workloads": {}}
+    if args.process:
+        result["timing"] = ("validate_long legs: host clock around each synchronised call, the two legs alternated in one run, "
+                            "--rounds rounds, medians, spread = (max - min) / median; sed_events_process alone: a device-event "
+                            "pair around the Python call (output and workspace allocation, five launches), warm, median of "
+                            "--decode-reps; the host route: host clock around the synchronised route, same reps")
+        result["note"] = ("validate_long(min_event_lengths=[0.25], min_event_gaps=[0.15]) at 50 points against the same run's "
+                          "validate_long at the same points; a difference counts only where it lies outside the larger "
+                          "(max - min) of its two legs.  The host route is the only one there was before sed_events_process.  "
+                          "The order timed is drop_merge (order 0)")
+        result["not_measured"] += ["the order merge_drop", "other K than 50", "other median windows", "other lengths and gaps",
+                                   "the kernels one by one", "with PSDS, weak tags, the error rate or a high threshold",
+                                   "max_table_bytes small enough to split the points into chunks"]
+        for name in args.workloads.split(","):
+            result["workloads"][name] = process_workload(name, model, args.rounds, args.decode_reps)
+            print(json.dumps({name: result["workloads"][name]}), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(json.dumps(result, indent=1) + "\n")
+        return
     if args.hysteresis:
         result["timing"] = ("validate_long legs: host clock around each synchronised call, the two legs alternated in one run, "
                             "--rounds rounds, medians, spread = (max - min) / median; sed_events_hysteresis alone: a device-event "
