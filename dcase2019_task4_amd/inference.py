@@ -20,6 +20,9 @@ windows' posteriors and attention (``CRNN.last_attention``, ``sed_stitch_weak``)
 event starts (one ``stitch_sweep`` of both thresholds, then ``sed_events_hysteresis``).  Minimum event length and gap
 merging: ``events_process`` / ``get_long_predictions(min_event_length=..., min_event_gap=...)`` drop short events and fuse
 events across short gaps on any of these tables (``sed_events_process``; ``process_points`` turns seconds into frames).
+Confidence scores: ``events_scores`` / ``get_long_predictions(event_scores=True)`` give every event of such a table the maximum
+and the mean of the blended timeline over its frames (``sed_events_scores``), ``events_select`` /
+``get_long_predictions(min_event_score=...)`` keep the events whose score exceeds a minimum (``sed_events_select``).
 ``get_predictions`` itself is unchanged.
 """
 import ctypes as C
@@ -435,6 +438,127 @@ def process_decoded(out, n_rec, nclass, min_len, max_gap, order="drop_merge"):
     return dict(out, ev_ptr=ev_ptr, ev_pairs=ev_pairs, err=err)
 
 
+SCORE_KEYS = {"max": 0, "mean": 1}
+
+
+def _score_key_code(key):
+    if key not in SCORE_KEYS:
+        raise ValueError(f"key must be one of {sorted(SCORE_KEYS)}, got {key!r}")
+    return SCORE_KEYS[key]
+
+
+def _table_shape(who, ev_ptr, ev_pairs, n_rec, nclass):
+    """The checks every event-table front shares: ``(n_cols, pairs_capacity, K)``."""
+    if (ev_ptr.dtype, ev_pairs.dtype) != (torch.int64, torch.int32) or ev_ptr.numel() < 2 or ev_pairs.dim() != 2 \
+            or ev_pairs.shape[1] != 2:
+        raise ValueError(f"{who}: ev_ptr int64 [n_cols + 1] and ev_pairs int32 [capacity, 2] expected")
+    n_cols, pairs_cap = ev_ptr.numel() - 1, ev_pairs.shape[0]
+    if n_rec < 1 or nclass < 1 or n_cols % (n_rec * nclass):
+        raise ValueError(f"{who}: {n_cols} columns are no multiple of {n_rec} recordings x {nclass} classes")
+    return n_cols, pairs_cap, n_cols // (n_rec * nclass)
+
+
+def events_scores(out_or_table, timeline, rec_frame0, n_rec, nclass, want=("max", "mean"), err=None):
+    """``sed_events_scores``: per event of a CSR table on the device the maximum and the mean of ``timeline``
+    [total_frames, nclass] (cuda float32: what a stitch entry writes; a batch of clips is ``strong`` reshaped with
+    ``rec_frame0 = arange(n + 1) * T3``) over the event's frames - the definition is in include/dcase_sed.h.
+    ``out_or_table``: the dict a stitch entry returned or a pair ``(ev_ptr, ev_pairs)``, ``ev_ptr`` [K * n_rec * nclass + 1]
+    int64 in the sweep's column order, ``ev_pairs`` [pairs_capacity, 2] int32.  ``want``: which of ``"max"`` / ``"mean"``.
+    Returns ``(score_max, score_mean, err)``: float32 [pairs_capacity] device tensors indexed like ``ev_pairs`` (an unwanted
+    one is None; entries at and beyond ``ev_ptr[-1]`` are not written), ``err`` [1] int32 - a new zeroed word by default, a
+    given one is OR-ed into (``STITCH_ERR_BITS``).  One launch, nothing synchronises."""
+    ev_ptr, ev_pairs = (out_or_table["ev_ptr"], out_or_table["ev_pairs"]) if isinstance(out_or_table, dict) else out_or_table
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in SCORE_KEYS for w in want):
+        raise ValueError(f"want must name one or both of {sorted(SCORE_KEYS)}, got {want!r}")
+    if ev_pairs.device.type != "cuda" or timeline.device.type != "cuda":
+        raise _lib.SedError("events_scores needs GPU tensors (no CPU fallback)")
+    n_rec, nclass = int(n_rec), int(nclass)
+    n_cols, pairs_cap, _ = _table_shape("events_scores", ev_ptr, ev_pairs, n_rec, nclass)
+    if timeline.dtype != torch.float32 or timeline.numel() % nclass or rec_frame0.dtype != torch.int64 \
+            or rec_frame0.numel() != n_rec + 1:
+        raise ValueError(f"events_scores: timeline float32 [total_frames, {nclass}] and rec_frame0 int64 [{n_rec + 1}] expected")
+    dev, ev_pairs, ev_ptr = ev_pairs.device, ev_pairs.contiguous(), ev_ptr.contiguous()
+    timeline, rec_frame0 = timeline.contiguous(), rec_frame0.contiguous()
+    score_max = torch.empty(pairs_cap, dtype=torch.float32, device=dev) if "max" in want else None
+    score_mean = torch.empty(pairs_cap, dtype=torch.float32, device=dev) if "mean" in want else None
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().sed_events_scores(_lib.ptr(timeline), timeline.numel() // nclass, _lib.ptr(rec_frame0), n_rec, nclass,
+                                            _lib.ptr(ev_ptr), _lib.ptr(ev_pairs), pairs_cap, n_cols, _lib.ptr(score_max),
+                                            _lib.ptr(score_mean), _lib.ptr(err), _lib.stream_ptr()), "sed_events_scores")
+    return score_max, score_mean, err
+
+
+def events_select(ev_ptr, ev_pairs, score_max, score_mean, n_rec, nclass, min_score, key="max", capacity=None, err=None):
+    """``sed_events_select``: the events of a CSR table whose score exceeds the minimum of their (point, class) - strictly,
+    and a NaN score is never kept.  ``key``: ``"max"`` or ``"mean"``, the score that decides (it must be given); the other
+    one may be None.  ``min_score``: a scalar, one value per class, a host ``[K, nclass]`` array or a device float32 tensor of
+    K * nclass values.  Returns ``(out_ptr [n_cols + 1] int64, out_pairs [capacity, 2] int32, out_score_max, out_score_mean,
+    err [1] int32)``: the kept events in order with their scores compacted alongside (None where the input was None);
+    ``capacity`` defaults to the input's (it cannot overflow), ``err`` to a new zeroed word - a given one is OR-ed into.
+    Three launches, nothing synchronises."""
+    key = _score_key_code(key)
+    if ev_pairs.device.type != "cuda":
+        raise _lib.SedError("events_select needs GPU tensors (no CPU fallback)")
+    n_rec, nclass = int(n_rec), int(nclass)
+    n_cols, pairs_cap, K = _table_shape("events_select", ev_ptr, ev_pairs, n_rec, nclass)
+    dev, ev_pairs, ev_ptr = ev_pairs.device, ev_pairs.contiguous(), ev_ptr.contiguous()
+    if (score_max, score_mean)[key] is None:
+        raise ValueError(f"events_select: key {('max', 'mean')[key]!r} needs that score array")
+    scores = []
+    for name, s in (("score_max", score_max), ("score_mean", score_mean)):
+        if s is not None and (s.device != dev or s.dtype != torch.float32 or s.numel() != pairs_cap):
+            raise ValueError(f"events_select: {name} must be float32 [{pairs_cap}] on the table's device")
+        scores.append(None if s is None else s.contiguous())
+    if not torch.is_tensor(min_score):
+        m = np.asarray(min_score, dtype=np.float32)
+        m = np.tile(_per_class(m, nclass, np.float32, "min_score"), (K, 1)) if m.size in (1, nclass) else m
+        min_score = torch.from_numpy(np.ascontiguousarray(m.reshape(-1))).to(dev)
+    if min_score.device != dev or min_score.dtype != torch.float32 or min_score.numel() != K * nclass:
+        raise ValueError(f"events_select: min_score must be a scalar, {nclass} values or float32 [{K}, {nclass}] "
+                         "(host array or tensor on the table's device)")
+    min_score = min_score.contiguous()
+    capacity = pairs_cap if capacity is None else int(capacity)
+    l = _lib.lib()
+    ws_bytes = l.sed_events_select_ws_bytes(pairs_cap, n_cols)
+    if ws_bytes == 0:
+        raise ValueError(f"sed_events_select_ws_bytes: {l.sed_last_error().decode()}")
+    out_ptr = torch.empty(n_cols + 1, dtype=torch.int64, device=dev)
+    out_pairs = torch.empty(max(capacity, 1), 2, dtype=torch.int32, device=dev)
+    outs = [None if s is None else torch.empty(max(capacity, 1), dtype=torch.float32, device=dev) for s in scores]
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = _lib.scratch(ws_bytes, dev)
+    _lib.check(l.sed_events_select(_lib.ptr(ev_ptr), _lib.ptr(ev_pairs), _lib.ptr(scores[0]), _lib.ptr(scores[1]), pairs_cap, n_cols,
+                                   n_rec, nclass, key, _lib.ptr(min_score), _lib.ptr(out_ptr), _lib.ptr(out_pairs),
+                                   _lib.ptr(outs[0]), _lib.ptr(outs[1]), capacity, _lib.ptr(ws), ws.numel(), _lib.ptr(err),
+                                   _lib.stream_ptr()), "sed_events_select")
+    return out_ptr, out_pairs, outs[0], outs[1], err
+
+
+def score_decoded(out, rec_frame0, n_rec, nclass, want=("max", "mean")):
+    """``events_scores`` on the dict a stitch entry returned (decoded with ``want_timeline=True``; ``ValueError`` without a
+    timeline): the same dict plus ``score_max`` / ``score_mean`` (None when not wanted), its ``err`` the decode's own word
+    with the scorer's bits OR-ed in on the device."""
+    if out.get("timeline") is None:
+        raise ValueError("score_decoded needs the blended timeline: decode with want_timeline=True")
+    score_max, score_mean, err = events_scores(out, out["timeline"], rec_frame0, n_rec, nclass, want, err=out["err"])
+    return dict(out, score_max=score_max, score_mean=score_mean, err=err)
+
+
+def select_decoded(out, rec_frame0, n_rec, nclass, min_score, key="max"):
+    """``events_select`` on the dict a stitch entry returned: the same dict with the selected table and its compacted scores,
+    same capacity.  A dict ``score_decoded`` has not scored yet is scored first (``ValueError`` without a timeline)."""
+    _score_key_code(key)
+    if out.get("score_" + key) is None:
+        out = score_decoded(out, rec_frame0, n_rec, nclass)
+    ev_ptr, ev_pairs, score_max, score_mean, err = events_select(out["ev_ptr"], out["ev_pairs"], out.get("score_max"),
+                                                                 out.get("score_mean"), n_rec, nclass, min_score, key,
+                                                                 err=out["err"])
+    return dict(out, ev_ptr=ev_ptr, ev_pairs=ev_pairs, score_max=score_max, score_mean=score_mean, err=err)
+
+
 def _weak_inputs(who, win_strong, win_att, rec_win0, total_frames, hop3, weighting, n_win=None):
     """The input checks of ``stitch_weak`` and ``pooled_tags`` (``who``; ``n_win``: the latter's host-side window count).
     Returns ``(total_frames, hop3, the weighting's code)`` as ints."""
@@ -570,7 +694,7 @@ def long_window_posteriors(model, long_set, nclass, batch_size=64, want_attentio
 def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=None, save_predictions=None, batch_size=64,
                          cfg=None, threshold=0.5, median_window=None, weighting="taper", return_posteriors=False,
                          return_weak=False, threshold_high=None, min_event_length=None, min_event_gap=None,
-                         process_order="drop_merge"):
+                         process_order="drop_merge", event_scores=False, min_event_score=None, score_key="max"):
     """Events of recordings of any lengths (a ``LongRecordingSet``): the windows go through the eval-mode model
     ``batch_size`` at a time, their strong posteriors are blended into one timeline per recording (``weighting``: "taper"
     or "uniform"), and ONE threshold, median filter and run-length decode runs over each whole timeline
@@ -589,7 +713,12 @@ def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=
     (seconds, each a scalar or one value per class): events shorter than the length are dropped and events a gap of at most
     ``min_event_gap`` separates are fused, in the order ``process_order`` ("drop_merge" or "merge_drop") - one
     ``events_process`` on the decoded table (after the two-threshold select when ``threshold_high`` is given), in frames of
-    ``pooling_time_ratio * hop_length / sample_rate`` seconds (``process_points``).  Both None: no launch, the same frame."""
+    ``pooling_time_ratio * hop_length / sample_rate`` seconds (``process_points``).  Both None: no launch, the same frame.
+    ``event_scores=True``: the final table (after the two-threshold select and ``events_process`` where asked for) is scored
+    on the blended timeline (``events_scores``: the decode it already runs writes the timeline) and the columns ``score_max``
+    / ``score_mean`` are appended to the frame and the TSV.  ``min_event_score`` (a scalar or one value per class; implies the
+    scoring): only the events whose ``score_key`` ("max" or "mean") score exceeds it are kept (``events_select``, before the
+    host copy).  With the defaults nothing new is launched and the frame is column for column the same."""
     if not isinstance(long_set, LongRecordingSet):
         raise TypeError(f"long_set must be a LongRecordingSet, got {type(long_set).__name__}")
     cfg = cfg or _Cfg
@@ -615,20 +744,37 @@ def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=
         min_len, max_gap = process_points(None if min_event_length is None else [min_event_length],
                                           None if min_event_gap is None else [min_event_gap], NC,
                                           pool * cfg.hop_length / cfg.sample_rate, 1)
+    _score_key_code(score_key)
+    if not isinstance(event_scores, (bool, np.bool_)):
+        raise ValueError(f"event_scores must be True or False, got {event_scores!r}")
+    scored = bool(event_scores) or min_event_score is not None
+    if min_event_score is not None:
+        min_score = _per_class(min_event_score, NC, np.float32, "min_event_score").reshape(1, NC)
+        if np.isnan(min_score).any():
+            raise ValueError("min_event_score: NaN keeps no event; pass None to keep all")
+    want_timeline = return_posteriors or scored
     win_strong = long_window_posteriors(model, long_set, NC, batch_size, want_attention=return_weak)
     if return_weak:
         win_strong, win_att = win_strong
     if threshold_high is None:
         out = stitch_decode(win_strong, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3, thr, win,
-                            weighting, long_set.capacity(NC), want_timeline=return_posteriors)
+                            weighting, long_set.capacity(NC), want_timeline=want_timeline)
         calls = [("sed_stitch_decode", out["err"])]
     else:
         out = stitch_hysteresis(win_strong, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3, [thr],
-                                [threshold_high], [win], weighting, long_set.capacity(NC), want_timeline=return_posteriors)
+                                [threshold_high], [win], weighting, long_set.capacity(NC), want_timeline=want_timeline)
         calls = [("sed_stitch_sweep + sed_events_hysteresis", out["err"])]
     if process:
         out = process_decoded(out, long_set.n_rec, NC, min_len, max_gap, process_order)
         calls = [(calls[0][0] + " + sed_events_process", out["err"])]
+    if scored:                                                                   # words of their own: the table's stays as it was
+        score_max, score_mean, word = events_scores(out, out["timeline"], long_set.rec_frame0, long_set.n_rec, NC)
+        calls.append(("sed_events_scores", word))
+        if min_event_score is not None:
+            ev_ptr, ev_pairs, score_max, score_mean, word = events_select(out["ev_ptr"], out["ev_pairs"], score_max, score_mean,
+                                                                          long_set.n_rec, NC, min_score, score_key)
+            out = dict(out, ev_ptr=ev_ptr, ev_pairs=ev_pairs)
+            calls.append(("sed_events_select (min_event_score)", word))
     if return_weak:
         tags = stitch_weak(win_strong, win_att, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3,
                            weighting)
@@ -650,6 +796,9 @@ def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=
                                  columns=["event_label", "onset", "offset", "filename"])
     prediction_df.onset = prediction_df.onset * pool / (cfg.sample_rate / cfg.hop_length)
     prediction_df.offset = prediction_df.offset * pool / (cfg.sample_rate / cfg.hop_length)
+    if scored:
+        prediction_df["score_max"] = score_max[:len(ev)].cpu().numpy()
+        prediction_df["score_mean"] = score_mean[:len(ev)].cpu().numpy()
     if save_predictions is not None:
         prediction_df.to_csv(save_predictions, index=False, sep="\t")
     result = (prediction_df,)

@@ -688,6 +688,67 @@ int sed_events_process(const int64_t* ev_ptr, const int32_t* pairs, long long pa
                        int64_t* out_ptr, int32_t* out_pairs, long long out_capacity,
                        void* ws, size_t ws_bytes, int32_t* err, void* stream);
 
+/* ---- confidence scores of decoded events, and a select by score, in the event domain ------------------
+ * Every decode leaves a CSR table of (onset, offset) pairs; sed_events_scores says how confident the posteriors were in each
+ * event, sed_events_select keeps the events whose score exceeds a minimum.  The definitions are the project's own; pinned is
+ * agreement with a plain-loop numpy statement (tests/event_scores_np.py): maxima bitwise, means within one fp32 step.
+ *   timeline   [total_frames][NC] fp32   what a stitch entry writes, or any fp32 array of that shape.  A batch of n clips is
+ *                                        n one-window recordings: `strong` reshaped, rec_frame0 = arange(n + 1) * T3
+ *   rec_frame0 [n_rec + 1] int64         device: recording r owns the frames rec_frame0[r] .. rec_frame0[r + 1] - 1 (L3_r)
+ *   ev_ptr [n_cols + 1] int64, ev_pairs [pairs_capacity][2] int32   a table in the sweep's column order, column (k, rec, c) =
+ *                                        (k * n_rec + rec) * NC + c; n_cols = K * n_rec * NC (K = 1: sed_stitch_decode's)
+ *   score_max, score_mean [pairs_capacity] fp32, indexed like ev_pairs; either may be NULL, not both.  Only the indices below
+ *                                        ev_ptr[n_cols] that belong to a valid column are written.
+ * Event i = [on, off) of column (k, rec, c), 0 <= on < off <= L3_rec, over P[u] = timeline[(rec_frame0[rec] + u) * NC + c],
+ * on <= u < off:
+ *   score_max[i]   the largest non-NaN P[u], NaN when every frame is NaN: a copy of an input value, no arithmetic.  (The sign
+ *                  of a zero maximum is unspecified when the span holds both +0.0 and -0.0; a sigmoid gives no -0.0.)
+ *   score_mean[i]  (float)(S / (double)(off - on)), S the fp64 sum of the P[u], each widened exactly.  A NaN frame makes the
+ *                  mean NaN.  The order of the sum is a function of off - on alone - not of position, column or neighbours:
+ *                  events of at most sed_events_scores_short_frames() frames are summed in increasing u; a longer one as 64
+ *                  partial sums (partial l: the frames on + l, on + l + 64, ... in increasing order) combined by a fixed
+ *                  butterfly.  So the mean is the same bits from call to call, under graph replay, and wherever the event lies.
+ *   An event that sed_events_process fused across a gap is scored over its whole span, the gap's frames included.
+ *   err    one int32, OR-ed, the family's bits:
+ *            16 = a column whose bounds are not 0 <= ev_ptr[c] <= ev_ptr[c + 1] <= pairs_capacity, or a recording whose bounds
+ *                 are not 0 <= rec_frame0[r] <= rec_frame0[r + 1] <= total_frames: nothing of it is read or written.
+ *                 (As in sed_events_hysteresis, an ev_ptr that is not non-decreasing can moreover leave events that the
+ *                 bisection assigns to no column: they are not scored.)
+ *            64 = an event with on < 0, off > L3 or on >= off: its two scores are NaN and no frame of it is read
+ *          No table content can make the kernel address outside timeline [0, total_frames * NC), ev_ptr [0, n_cols],
+ *          ev_pairs or the outputs [0, pairs_capacity).
+ * ONE launch on `stream` whatever K and the number of events are, flat over the indices of ev_pairs (grid sized from
+ * pairs_capacity; none when it is 0).  No LDS tiles, no workspace, no host synchronisation, no allocation, no atomics but the
+ * OR into err, hipGraph-capturable.
+ * Limits, checked before any launch (SED_ERR_BAD_ARG): no null pointer except one of the two outputs, 1 <= NC <= 16,
+ * n_rec >= 1, 1 <= n_cols < 2^26 a multiple of n_rec * NC, 0 <= pairs_capacity < 2^31, total_frames * NC < 2^31, ev_pairs
+ * 8-byte aligned, no output overlapping an input or the other output.
+ *
+ * sed_events_select: an event of column (k, rec, c) is kept iff score[i] > min_score[k][c] - strict, like the decode's
+ * P > thr; a NaN score is never kept.
+ *   key        0: score_max decides, 1: score_mean.  The key's array must be given; the other one and its output go together
+ *              or are both NULL.
+ *   min_score  [K][NC] fp32, device
+ *   out_ptr [n_cols + 1] int64   CSR offsets of the kept events, column for column: ALWAYS the true counts
+ *   out_pairs [out_capacity][2], out_score_max / out_score_mean [out_capacity]   the kept events in order and their scores
+ *              (copies); none of them may be its input
+ *   err        2 = more kept events than out_capacity: nothing is written at or beyond it, never a truncated table
+ *             16 = a column with broken bounds, as above: none of its events is kept
+ *   ws         sed_events_select_ws_bytes(pairs_capacity, n_cols) bytes, 8-byte aligned; ws_bytes must be that value
+ * Three launches (two when pairs_capacity is 0): a flag pass with wave ballots and one count per workgroup, a one-workgroup
+ * scan, a write pass.  Limits and host checks as for sed_events_hysteresis, and n_rec, NC >= 1, n_cols a multiple of
+ * n_rec * NC (SED_ERR_BAD_ARG; a wrong ws_bytes: SED_ERR_WORKSPACE).
+ * Not provided: scoring without a written timeline, the position of the peak frame, scores weighted by the attention. */
+int sed_events_scores_short_frames(void);
+int sed_events_scores(const float* timeline, long long total_frames, const int64_t* rec_frame0, int n_rec, int NC,
+                      const int64_t* ev_ptr, const int32_t* ev_pairs, long long pairs_capacity, long long n_cols,
+                      float* score_max, float* score_mean, int32_t* err, void* stream);
+size_t sed_events_select_ws_bytes(long long pairs_capacity, long long n_cols);
+int sed_events_select(const int64_t* ev_ptr, const int32_t* ev_pairs, const float* score_max, const float* score_mean,
+                      long long pairs_capacity, long long n_cols, int n_rec, int NC, int key, const float* min_score,
+                      int64_t* out_ptr, int32_t* out_pairs, float* out_score_max, float* out_score_mean,
+                      long long out_capacity, void* ws, size_t ws_bytes, int32_t* err, void* stream);
+
 /* ---- recording-level weak tags of long recordings -------------------------------------------------
  * A window's `weak` is a ratio num / den of attention-pooled sums (models/CRNN.py:79-81); the ratios of overlapping
  * windows cannot be combined into the recording's ratio without the attention mass per frame.  sed_stitch_weak pools over

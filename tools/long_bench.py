@@ -85,7 +85,20 @@ thresholds as --scoring, min_event_length 0.25 s and min_event_gap 0.15 s at eve
     --decode-reps) against the only route there was before it: the table copied to the host, a vectorised numpy restatement,
     the result uploaded again (host clock, same reps); the two routes' tables are compared.
 
-Usage: python tools/long_bench.py [--scoring | --sweep | --weak | --tag-train | --error-rate | --hysteresis | --process] [--rounds 5] [--decode-reps 30] [--out profiles/long_inference.json]"""
+--scores measures the event scores and the select by score (profiles/long_scores.json), same workloads, hop and 50 thresholds as
+--scoring, median window 7:
+  get_long_predictions(event_scores=True) against the same run's plain call, the two legs alternated in one run, --rounds
+    rounds, medians, spread = (max - min) / median; the difference counts only where it lies outside the larger (max - min)
+    of its two legs.
+  sed_events_scores alone on the table of one 50-point sweep (a device-event pair around the Python call, median of
+    --decode-reps) against the only route there was before it: timeline and table copied to the host, np.maximum.reduceat /
+    np.add.reduceat, the result uploaded again (host clock, same reps); the run asserts identical maxima and every mean
+    within one fp32 step.
+  sed_events_select alone (the maximum against the next point's thresholds) against a host boolean-mask select, compared.
+  --boundary-libs A.so,B.so: the scorer alone on the same table under builds of the library with other short / long
+    boundaries (-DEVS_SHORT_FRAMES=n for csrc/evscore.hip), each in a process of its own.
+
+Usage: python tools/long_bench.py [--scoring | --sweep | --weak | --tag-train | --error-rate | --hysteresis | --process | --scores] [--rounds 5] [--decode-reps 30] [--out profiles/long_inference.json]"""
 import argparse
 import json
 import os
@@ -704,6 +717,161 @@ def process_workload(name, model, rounds, reps, seconds=(0.25, 0.15), order="dro
     return out
 
 
+def host_scores(tl, f0, n_rec, NC, ev_ptr, pairs):
+    """Maximum and mean per event on the host with reduceat over the class-major timeline: numpy arrays -> (max, mean) fp32."""
+    total = tl.shape[0]
+    col = np.repeat(np.arange(len(ev_ptr) - 1, dtype=np.int64), np.diff(ev_ptr))
+    base = (col % NC) * total + f0[(col // NC) % n_rec]
+    idx = np.stack([base + pairs[:, 0], base + pairs[:, 1]], 1).reshape(-1)
+    x = np.r_[np.ascontiguousarray(tl.T).reshape(-1), np.float32(0)]                  # (an end index may be the array's length)
+    if len(idx) == 0:
+        return np.zeros(0, np.float32), np.zeros(0, np.float32)
+    smax = np.maximum.reduceat(x, idx)[::2]
+    ssum = np.add.reduceat(x.astype(np.float64), idx)[::2]
+    return smax, (ssum / (pairs[:, 1] - pairs[:, 0])).astype(np.float32)
+
+
+def host_score_select(ev_ptr, pairs, smax, smean, n_rec, NC, mins):
+    """The select by a boolean mask on the host: numpy arrays -> (out_ptr, out_pairs, out_max, out_mean)."""
+    n_cols = len(ev_ptr) - 1
+    col = np.repeat(np.arange(n_cols, dtype=np.int64), np.diff(ev_ptr))
+    keep = smax > mins.reshape(-1)[(col // (n_rec * NC)) * NC + col % NC]
+    out_ptr = np.r_[0, np.cumsum(np.bincount(col[keep], minlength=n_cols))].astype(np.int64)
+    return out_ptr, pairs[keep], smax[keep], smean[keep]
+
+
+def scores_alone(timeline, rec_frame0, n_rec, ev_ptr, pairs, reps):
+    """sed_events_scores through its Python front, device events around the call."""
+    state = {}
+
+    def device():
+        state["dev"] = inference.events_scores((ev_ptr, pairs), timeline, rec_frame0, n_rec, NCLASS)
+    t = event_ms(device, reps)
+    t["short_frames"] = int(_lib.lib().sed_events_scores_short_frames())
+    return t, state["dev"]
+
+
+def scores_child(path, reps):
+    """Part (d) in a process of its own (another library through SED_LIB): the table and timeline the parent saved."""
+    z = np.load(path)
+    dev = lambda a: torch.from_numpy(a).cuda()
+    t, (smax, smean, err) = scores_alone(dev(z["timeline"]), dev(z["rec_frame0"]), int(z["n_rec"]), dev(z["ev_ptr"]), dev(z["ev_pairs"]),
+                                         reps)
+    n = int(z["ev_ptr"][-1])
+    t.update(err=int(err.item()), maxima_identical=bool(np.array_equal(smax[:n].cpu().numpy(), z["score_max"])),
+             means_identical=bool(np.array_equal(smean[:n].cpu().numpy(), z["score_mean"])))
+    print(json.dumps(t), flush=True)
+
+
+def scores_workload(name, model, rounds, reps, boundary_libs):
+    """(a) get_long_predictions with and without event_scores=True, alternated; (b) sed_events_scores alone on the 50-point
+    sweep table against the host route (timeline and table copied down, numpy reduceat, the result uploaded); (c)
+    sed_events_select alone against a host boolean-mask select; (d) part (b)'s device leg under the other short / long
+    boundaries given as libraries."""
+    import subprocess
+    import tempfile
+    info, ctx = scoring_workload(name, model, rounds, reps, setup_only=True)
+    ls, window, win_strong, thr50 = ctx["ls"], ctx["window"], ctx["win_strong"], ctx["thr50"]
+    out = {k: info[k] for k in ("recordings", "windows", "timeline_frames", "median_window")}
+    out.update(rounds=rounds, points=50)
+    enc = _Enc().decode_strong
+    state = {}
+    legs = {"get_long_predictions": lambda: state.__setitem__("plain", inference.get_long_predictions(
+                model, ls, enc, POOL, batch_size=BATCH, median_window=window)),
+            "get_long_predictions_event_scores": lambda: state.__setitem__("scored", inference.get_long_predictions(
+                model, ls, enc, POOL, batch_size=BATCH, median_window=window, event_scores=True))}
+    for fn in legs.values():
+        fn()
+    ms = {leg: [] for leg in legs}
+    for _ in range(rounds):
+        for leg, fn in legs.items():
+            ms[leg].append(wall_ms(fn))
+    t = {leg: stats(ms[leg]) for leg in legs}
+    a, b = t["get_long_predictions"], t["get_long_predictions_event_scores"]
+    band = max(max(x["samples_ms"]) - min(x["samples_ms"]) for x in (a, b))
+    t["difference"] = {"added_ms": b["median_ms"] - a["median_ms"], "larger_max_minus_min_ms": band,
+                       "outside_the_band": bool(abs(b["median_ms"] - a["median_ms"]) > band)}
+    t["event_rows"] = len(state["plain"])
+    assert state["scored"][list(state["plain"].columns)].equals(state["plain"])
+    out["get_long_predictions"] = t
+    # (b) the scorer alone, on the table of one sweep of the 50 points
+    cap = ls.capacity(NCLASS)
+    table = inference.stitch_sweep(win_strong, ls.rec_win0, ls.rec_frame0, ls.total_frames, ls.hop3, thr50, [window], "taper", 50 * cap,
+                                   want_timeline=True)
+    assert int(table["err"].item()) == 0
+    ev_ptr, pairs, timeline = table["ev_ptr"], table["ev_pairs"], table["timeline"]
+    f0_host = np.asarray(ls.rec_frame0_host, dtype=np.int64)
+
+    def host():
+        p = ev_ptr.cpu().numpy()
+        q = pairs[:int(p[-1])].cpu().numpy().astype(np.int64)
+        smax, smean = host_scores(timeline.cpu().numpy(), f0_host, ls.n_rec, NCLASS, p, q)
+        state["host"] = (torch.from_numpy(smax).cuda(), torch.from_numpy(smean).cuda())
+    for _ in range(3):
+        host()
+    host_ms = stats([wall_ms(host) for _ in range(reps)])
+    dev_t, (d_max, d_mean, d_err) = scores_alone(timeline, ls.rec_frame0, ls.n_rec, ev_ptr, pairs, reps)
+    n = int(ev_ptr[-1].item())
+    h_max, h_mean = (x.cpu().numpy() for x in state["host"])
+    g_max, g_mean = d_max[:n].cpu().numpy(), d_mean[:n].cpu().numpy()
+    assert not np.isnan(h_max).any() and int(d_err.item()) == 0
+    assert np.array_equal(g_max, h_max), "the maxima of the two routes differ"
+    steps = np.abs(g_mean.astype(np.float64) - h_mean.astype(np.float64)) / np.spacing(h_mean)
+    assert (steps <= 1).all(), "a mean of the two routes differs by more than one fp32 step"
+    lengths = (pairs[:n, 1] - pairs[:n, 0]).cpu().numpy()
+    out["scores_alone"] = {"sed_events_scores": dev_t,
+                           "host_copy_numpy_reduceat_upload": {"median_ms": host_ms["median_ms"], "spread": host_ms["spread"],
+                                                               "reps": reps, "timing": "host clock around the synchronised route"},
+                           "pairs_capacity": int(pairs.shape[0]), "events": n, "err": int(d_err.item()),
+                           "event_frames": {"median": float(np.median(lengths)), "max": int(lengths.max()),
+                                            "longer_than_short_frames": int((lengths > dev_t["short_frames"]).sum())},
+                           "maxima_identical": True, "means_within_one_fp32_step": True,
+                           "means_differing_by_one_step": int((steps > 0).sum())}
+    # (c) the select alone: the maximum against the next point's threshold
+    mins = np.stack(thr50[1:] + thr50[-1:]).astype(np.float32)
+    d_mins = torch.from_numpy(mins).cuda()
+
+    def device_select():
+        state["sel"] = inference.events_select(ev_ptr, pairs, d_max, d_mean, ls.n_rec, NCLASS, d_mins)
+
+    def host_select_route():
+        p = ev_ptr.cpu().numpy()
+        m = int(p[-1])
+        res = host_score_select(p, pairs[:m].cpu().numpy(), d_max[:m].cpu().numpy(), d_mean[:m].cpu().numpy(), ls.n_rec, NCLASS, mins)
+        state["host_sel"] = [torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in res]
+    for _ in range(3):
+        host_select_route()
+    host_ms = stats([wall_ms(host_select_route) for _ in range(reps)])
+    sel_t = event_ms(device_select, reps)
+    s_ptr, s_pairs, s_max, s_mean, s_err = state["sel"]
+    h = state["host_sel"]
+    m = int(h[0][-1].item())
+    out["select_alone"] = {"sed_events_select": sel_t,
+                           "host_copy_numpy_mask_upload": {"median_ms": host_ms["median_ms"], "spread": host_ms["spread"], "reps": reps,
+                                                           "timing": "host clock around the synchronised route"},
+                           "input_events": n, "kept_events": m, "err": int(s_err.item()),
+                           "routes_identical": bool(torch.equal(s_ptr, h[0]) and torch.equal(s_pairs[:m], h[1]) and
+                                                    torch.equal(s_max[:m], h[2]) and torch.equal(s_mean[:m], h[3]))}
+    assert out["select_alone"]["routes_identical"]
+    # (d) the other short / long boundaries, each library in a process of its own on the same table
+    tried = {str(dev_t["short_frames"]): dict(dev_t, library="the build under test")}
+    if boundary_libs:
+        with tempfile.TemporaryDirectory() as tmp:
+            path = os.path.join(tmp, "table.npz")
+            np.savez(path, timeline=timeline.cpu().numpy(), rec_frame0=f0_host, n_rec=ls.n_rec, ev_ptr=ev_ptr.cpu().numpy(),
+                     ev_pairs=pairs.cpu().numpy(), score_max=g_max, score_mean=g_mean)
+            for lib in boundary_libs:
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--scores-child", path, "--decode-reps", str(reps)],
+                                   env=dict(os.environ, SED_LIB=os.path.abspath(lib), SED_ALLOW_VARIANT="1"), capture_output=True, text=True, timeout=600)
+                if r.returncode != 0:
+                    raise SystemExit(f"--scores-child under {lib} failed:\n{r.stdout}\n{r.stderr}")
+                res = json.loads(r.stdout.strip().splitlines()[-1])
+                assert res["err"] == 0 and res["maxima_identical"], res
+                tried[str(res["short_frames"])] = res
+    out["short_frames_tried"] = tried
+    return out
+
+
 def weak_workload(name, model, rounds, reps):
     import ctypes as C
     n_rec, per = WORKLOADS[name]
@@ -906,6 +1074,11 @@ def main():
                     help="measure the two-threshold decode (profiles/long_hysteresis.json)")
     ap.add_argument("--process", action="store_true",
                     help="measure minimum event length and gap merging (profiles/long_process.json)")
+    ap.add_argument("--scores", action="store_true",
+                    help="measure the event scores and the select by score (profiles/long_scores.json)")
+    ap.add_argument("--boundary-libs", default="",
+                    help="with --scores: comma-separated builds of the library with other EVS_SHORT_FRAMES (csrc/evscore.hip)")
+    ap.add_argument("--scores-child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--sweep-decode-only", action="store_true", help="with --sweep: sed_stitch_sweep alone (a variant build)")
     ap.add_argument("--sweep-out", default=os.path.join(REPO, "profiles", "long_sweep.json"))
     ap.add_argument("--candidates", default="", help="with --sweep: earlier --sweep-decode-only results to copy in")
@@ -915,7 +1088,7 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(REPO, "profiles", "long_process.json" if args.process else
+        args.out = os.path.join(REPO, "profiles", "long_scores.json" if args.scores else "long_process.json" if args.process else
                                 "long_hysteresis.json" if args.hysteresis else
                                 "error_rate.json" if args.error_rate else
                                 "long_tag_train.json" if args.tag_train else "long_weak.json" if args.weak else
@@ -924,6 +1097,8 @@ def main():
         raise SystemExit("long_bench.py measures on the GPU: no device found (nothing is measured on a CPU)")
     if args.rounds < 5 or args.decode_reps < 20:
         raise SystemExit("need --rounds >= 5 and --decode-reps >= 20")
+    if args.scores_child:
+        return scores_child(args.scores_child, args.decode_reps)
     model, _ = bench.build_models("cuda", seed=0, mfma_dtype="f32")
     model.eval()
     result = {"tool": "tools/long_bench.py", "device": torch.cuda.get_device_name(0), "frames": T, "batch_size": BATCH,
@@ -933,6 +1108,26 @@ def main():
               "not_measured": ["from_waveforms / feature extraction", "other batch sizes, bf16 / wide models",
                                "recordings longer than 1 h", "a run with the GPU to itself (the host is shared)"],
               "workloads": {}}
+    if args.scores:
+        result["timing"] = ("get_long_predictions legs: host clock around each synchronised call, the two legs alternated in one run, "
+                            "--rounds rounds, medians, spread = (max - min) / median; sed_events_scores / sed_events_select alone: "
+                            "a device-event pair around the Python call (output allocation included), warm, median of --decode-reps; "
+                            "the host routes: host clock around the synchronised route, same reps")
+        result["note"] = ("get_long_predictions(event_scores=True) against the same run's plain call, default hop, median window 7; "
+                          "a difference counts only where it lies outside the larger (max - min) of its two legs.  The host routes "
+                          "are the only ones there were before sed_events_scores / sed_events_select.  short_frames_tried: the "
+                          "scorer alone on the same 50-point table under libraries built with other EVS_SHORT_FRAMES, each in a "
+                          "process of its own")
+        result["not_measured"] += ["the kernels one by one", "other K than 50", "other median windows", "the key score_mean",
+                                   "min_event_score through get_long_predictions", "NaN posteriors"]
+        libs = [x for x in args.boundary_libs.split(",") if x]
+        for name in args.workloads.split(","):
+            result["workloads"][name] = scores_workload(name, model, args.rounds, args.decode_reps, libs)
+            print(json.dumps({name: result["workloads"][name]}), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(json.dumps(result, indent=1) + "\n")
+        return
     if args.process:
         result["timing"] = ("validate_long legs: host clock around each synchronised call, the two legs alternated in one run, "
                             "--rounds rounds, medians, spread = (max - min) / median; sed_events_process alone: a device-event "
