@@ -16,6 +16,8 @@
 // sed_events_select   keeps the events whose score exceeds the minimum of their (point, class).  Three launches, the shape of
 //   hyst.hip: k_evs_flag (wave ballots, one count per workgroup), k_evs_scan (one workgroup), k_evs_write (the kept pairs and
 //   their scores at their rank; thread c <= n_cols writes out_ptr[c] and validates column c).
+// sed_events_tag_scores   per event the largest span tag among the spans it touches: k_evs_score<EvsTagArgs>, the same kernel
+//   over the coordinate map rows = spans (the tag gate is this score and sed_events_select with key 0).
 // Every ptr entry is validated before it is used as an index; the timeline is addressed only inside a validated recording.
 #include "common.h"
 #include "kernels.h"
@@ -40,7 +42,22 @@ struct EvsArgs {
 // The running maximum that skips NaN: m is NaN until the first non-NaN value.  Comparisons and copies only.
 __device__ __forceinline__ float evs_max(float m, float v) { return (v == v && (m != m || v > m)) ? v : m; }
 
-__global__ __launch_bounds__(HY_THREADS) void k_evs_score(EvsArgs e) {
+// sed_events_tag_scores is the same kernel over another coordinate map: the "timeline" is the span tags [total_spans][NC], the
+// recording table rec_span0, and an event [on, off) in frames touches the rows on / span3 .. (off - 1) / span3 of its recording.
+// evs_unit is the frames per row: the constant 1 for the scores (the map folds away), span3 for the tag scores.
+struct EvsTagArgs {
+    EvsArgs e;                   // tl = tags, total = total_spans, f0 = rec_span0, smean = null
+    int span3;
+};
+__device__ __forceinline__ const EvsArgs& evs_args(const EvsArgs& a) { return a; }
+__device__ __forceinline__ const EvsArgs& evs_args(const EvsTagArgs& a) { return a.e; }
+__device__ __forceinline__ long long evs_unit(const EvsArgs&) { return 1; }
+__device__ __forceinline__ long long evs_unit(const EvsTagArgs& a) { return a.span3; }
+
+template <class Args>
+__global__ __launch_bounds__(HY_THREADS) void k_evs_score(Args args) {
+    const EvsArgs& e = evs_args(args);
+    const long long unit = evs_unit(args);
     const int lane = threadIdx.x & 63;
     const long long i = (long long)blockIdx.x * HY_THREADS + threadIdx.x;
     const float nan = __builtin_nanf("");
@@ -60,13 +77,14 @@ __global__ __launch_bounds__(HY_THREADS) void k_evs_score(EvsArgs e) {
             if (fa >= 0 && fa <= fb && fb <= e.total) {
                 const hy_i32x2 ev = *(const hy_i32x2*)(e.pairs + 2 * (size_t)i);
                 const long long on = ev.x, off = ev.y;
-                if (on < 0 || off > fb - fa || on >= off) {
+                if (on < 0 || off > (fb - fa) * unit || on >= off) {
                     atomicOr(e.err, 64);
                     if (e.smax) e.smax[i] = nan;
                     if (e.smean) e.smean[i] = nan;
                 } else {
-                    base = (fa + on) * e.NC + cls;                                   // < total * NC < 2^31, and so is the last frame
-                    len = off - on;
+                    const long long lo = on / unit, hi = (off - 1) / unit;           // the rows the event touches: hi < fb - fa
+                    base = (fa + lo) * e.NC + cls;                                   // < total * NC < 2^31, and so is the last row
+                    len = hi - lo + 1;
                     if (len <= EVS_SHORT_FRAMES) {
                         const float* p = e.tl + base;
                         float m = nan;
@@ -153,7 +171,34 @@ extern "C" int sed_events_scores(const float* timeline, long long total_frames, 
     const EvsArgs e = {timeline, total_frames, rec_frame0, n_rec, NC, ev_ptr, ev_pairs, pairs_capacity, n_cols,
                        score_max, score_mean, err};
     const long long items = pairs_capacity > n_cols ? pairs_capacity : n_cols;
-    hipLaunchKernelGGL(k_evs_score, dim3((unsigned)evs_blocks(items)), dim3(HY_THREADS), 0, (hipStream_t)stream, e);
+    hipLaunchKernelGGL(k_evs_score<EvsArgs>, dim3((unsigned)evs_blocks(items)), dim3(HY_THREADS), 0, (hipStream_t)stream, e);
+    SED_CHECK_LAUNCH();
+    return SED_OK;
+}
+
+extern "C" int sed_events_tag_scores(const float* tags, long long total_spans, const int64_t* rec_span0, int span3, int n_rec,
+                                     int NC, const int64_t* ev_ptr, const int32_t* ev_pairs, long long pairs_capacity,
+                                     long long n_cols, float* tag_score, int32_t* err, void* stream) {
+#define NEED(cond, msg) EVS_NEED("sed_events_tag_scores", cond, msg)
+    NEED(tags && rec_span0 && ev_ptr && ev_pairs && tag_score && err, "null argument");
+    NEED(span3 >= 1, "need span3 >= 1");
+    NEED(NC >= 1 && NC <= 16 && n_rec >= 1, "need 1 <= NC <= 16 and n_rec >= 1");
+    NEED(n_cols >= 1 && n_cols < (1ll << 26) && n_cols % ((long long)n_rec * NC) == 0,
+         "need 1 <= n_cols < 2^26, a multiple of n_rec * NC (K * n_rec * NC columns)");
+    NEED(pairs_capacity >= 0 && pairs_capacity < (1ll << 31), "need 0 <= pairs_capacity < 2^31");
+    NEED(total_spans >= 0 && total_spans * NC < (1ll << 31), "need 0 <= total_spans and total_spans * NC < 2^31");
+    NEED(((uintptr_t)ev_pairs % 8) == 0, "ev_pairs must be 8-byte aligned");
+    const size_t out_bytes = (size_t)pairs_capacity * sizeof(float);
+    const void* in[4] = {tags, rec_span0, ev_ptr, ev_pairs};
+    const size_t in_bytes[4] = {(size_t)total_spans * NC * sizeof(float), (size_t)(n_rec + 1) * sizeof(int64_t),
+                                (size_t)(n_cols + 1) * sizeof(int64_t), (size_t)pairs_capacity * 2 * sizeof(int32_t)};
+    for (int k = 0; k < 4; ++k) NEED(evs_disjoint(tag_score, out_bytes, in[k], in_bytes[k]), "the output overlaps an input");
+#undef NEED
+    if (pairs_capacity == 0) return SED_OK;
+    const EvsTagArgs a = {{tags, total_spans, rec_span0, n_rec, NC, ev_ptr, ev_pairs, pairs_capacity, n_cols, tag_score, nullptr, err},
+                          span3};
+    const long long items = pairs_capacity > n_cols ? pairs_capacity : n_cols;
+    hipLaunchKernelGGL(k_evs_score<EvsTagArgs>, dim3((unsigned)evs_blocks(items)), dim3(HY_THREADS), 0, (hipStream_t)stream, a);
     SED_CHECK_LAUNCH();
     return SED_OK;
 }

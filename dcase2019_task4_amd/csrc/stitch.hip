@@ -20,6 +20,8 @@
 // sed_stitch_weak (at the end of the file) pools recording-level weak tags over the same tiles and slots: the same blend of the
 // posteriors and of the attention, fp64 sums in a fixed order, two launches, no timeline.  sed_stitch_weak_backward (behind it) is
 // its transpose: the gradient of a loss on the pooled tags w.r.t. both window tensors, a clear and one tile pass, no atomics.
+// sed_stitch_span_tags pools the same tags per span of span3 frames: the two kernels of sed_stitch_weak over another tile
+// descriptor (StSpanArgs), slots span * ceil(span3 / ST_TILE) + k.
 //
 // Where a tile lives: the tiles of recording r take slots slot0(r) + k, slot0(r) = floor(rec_frame0[r] / ST_TILE) + r.  That
 // is strictly increasing in (r, k) for increasing rec_frame0, needs no table of its own and at most
@@ -30,6 +32,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "post.h"
+#include <type_traits>
 
 #define ST_TILE 512          // timeline frames per workgroup
 #define ST_HALO 32           // 63 / 2 + 1: the widest median window's reach plus the neighbour the edge predicates read
@@ -492,14 +495,68 @@ struct StWeakArgs {
 };
 #define SW_FOLD 16
 
-template <bool VEC, int W>
-__global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_tile(StWeakArgs wa) {
+// sed_stitch_span_tags pools the same pairs per SPAN of span3 frames with the same two kernels (Args = StSpanArgs): a tile is then
+// ST_TILE frames of one span counted from the span's first frame, its slot is span * tps + k (tps = ceil(span3 / ST_TILE)), and
+// the column pass runs over the rows (span, class) of `weak` / `sums`.  The order of a span's sums is therefore the order
+// above with L3 = the span's length.
+struct StSpanArgs {
+    StWeakArgs w;            // t.n_slots is not used (no recording-slot layout); part [total_spans * tps][NC][2], weak / sums per span
+    const int64_t* rec_span0;
+    long long total_spans;
+    int span3, tps;
+};
+__host__ __device__ __forceinline__ const StWeakArgs& sw_args(const StWeakArgs& a) { return a; }
+__host__ __device__ __forceinline__ const StWeakArgs& sw_args(const StSpanArgs& a) { return a.w; }
+
+// Span g of the tables: the recording that holds it (one bisection over rec_span0: the last r with rec_span0[r] <= g), validated
+// - the recording as st_rec does, its spans against ceil(L3 / span3) and total_spans, g inside them - and the span's frames
+// [s, e) of that recording's timeline.  bad: 0, or the err bits that make the span's row NaN.  Wave-uniform.
+struct StSpan { StRec R; int r, s, e, bad; };
+__device__ __forceinline__ StSpan st_span_of(const StSpanArgs& sa, int r, long long g) {      // span g as one of recording r's
+    StSpan S;
+    S.r = r;
+    S.R = st_rec(sa.w.t, r);
+    S.s = S.e = 0;
+    S.bad = S.R.bad;
+    if (S.bad) return S;
+    const long long p0 = sa.rec_span0[r], p1 = sa.rec_span0[r + 1];
+    const long long n_spans = ((long long)S.R.L3 + sa.span3 - 1) / sa.span3;
+    if (p0 < 0 || p1 - p0 != n_spans || p1 > sa.total_spans || g < p0 || g >= p1) { S.bad = 16; return S; }
+    const long long s = (g - p0) * sa.span3;                                     // < L3: g - p0 < ceil(L3 / span3)
+    S.s = (int)s;
+    S.e = (int)min(s + sa.span3, (long long)S.R.L3);
+    return S;
+}
+__device__ __forceinline__ StSpan st_span(const StSpanArgs& sa, long long g) {
+    int lo_r = 0, hi_r = sa.w.t.n_rec - 1;
+    while (lo_r < hi_r) {
+        const int mid = (lo_r + hi_r + 1) >> 1;
+        if (sa.rec_span0[mid] <= g) lo_r = mid;
+        else hi_r = mid - 1;
+    }
+    return st_span_of(sa, lo_r, g);
+}
+
+template <bool VEC, int W, class Args>
+__global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_tile(Args args) {
     __shared__ double red[ST_THREADS * W * 2];                                   // [rows][NC][2], rows * NC <= ST_THREADS * W
     __shared__ double fold[ST_MAXC * SW_FOLD * 2];
+    const StWeakArgs& wa = sw_args(args);
     const StTables& a = wa.t;
     const int tid = threadIdx.x, NC = a.NC;
     StTile T;
-    if (!st_tile(a, blockIdx.x, T)) return;
+    if constexpr (std::is_same<Args, StSpanArgs>::value) {                       // frame 0 of the tile walk is the span's first frame
+        const long long g = blockIdx.x / args.tps, kt = blockIdx.x - g * args.tps;
+        const StSpan S = st_span(args, g);
+        const long long s = (long long)S.s + kt * ST_TILE;
+        if (S.bad || s >= S.e) return;
+        T.R = S.R;
+        T.r = S.r;
+        T.s = (int)s;
+        T.e = (int)min(s + ST_TILE, (long long)S.e);
+    } else {
+        if (!st_tile(a, blockIdx.x, T)) return;
+    }
     const int G = NC / W, rows = ST_THREADS / G, row = tid / G, q = tid - row * G;
     if (row < rows) {
         double num[W], den[W];
@@ -550,22 +607,45 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_tile(StWeakArgs wa) 
 }
 static_assert(ST_THREADS == ST_MAXC * SW_FOLD, "k_stitch_weak_tile folds the rows with one thread per (class, fold lane)");
 
-// One wave per column (recording, class): the tile pairs in the fixed order above; a recording the tables do not describe or
-// cover raises its err bits and has NaN rows.
-__global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_cols(StWeakArgs wa) {
+// One wave per column (recording, class) - or per row (span, class) of the span tags: the tile pairs in the fixed order above; a
+// recording the tables do not describe or cover raises its err bits and has NaN rows, and so has a span that no valid
+// recording holds.  In a span call wave r < n_rec moreover validates recording r (a recording whose spans own no row).
+template <class Args>
+__global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_cols(Args args) {
+    const StWeakArgs& wa = sw_args(args);
     const StTables& a = wa.t;
     const int lane = threadIdx.x & 63;
     const long long col = (long long)blockIdx.x * (ST_THREADS / 64) + (threadIdx.x >> 6);
-    if (col >= (long long)a.n_rec * a.NC) return;
-    const int r = (int)(col / a.NC), c = (int)(col - (long long)r * a.NC);
-    const StRec R = st_rec(a, r);
+    long long n_rows = a.n_rec, slot0 = 0;
+    int bad = 0, tiles = 0;
+    if constexpr (std::is_same<Args, StSpanArgs>::value) {
+        n_rows = args.total_spans;
+        if (col < a.n_rec && lane == 0) {
+            const StSpan S = st_span_of(args, (int)col, args.rec_span0[col]);    // (its first span, if it has one)
+            if (S.bad) atomicOr(a.err, S.bad);
+        }
+    }
+    if (col >= n_rows * a.NC) return;
+    const long long r = col / a.NC;
+    const int c = (int)(col - r * a.NC);
+    if constexpr (std::is_same<Args, StSpanArgs>::value) {
+        const StSpan S = st_span(args, r);
+        bad = S.bad;
+        tiles = (S.e - S.s + ST_TILE - 1) / ST_TILE;
+        slot0 = r * args.tps;
+    } else {
+        const StRec R = st_rec(a, (int)r);
+        bad = R.bad;
+        tiles = R.tiles;
+        slot0 = R.slot0;
+    }
     double n = 0.0, d = 0.0;
-    if (R.bad) {
-        if (c == 0 && lane == 0) atomicOr(a.err, R.bad);
+    if (bad) {
+        if (c == 0 && lane == 0) atomicOr(a.err, bad);
         n = d = __builtin_nan("");
     } else {
-        for (int k = lane; k < R.tiles; k += 64) {
-            const double* p = wa.part + (((size_t)R.slot0 + k) * a.NC + c) * 2;
+        for (int k = lane; k < tiles; k += 64) {
+            const double* p = wa.part + (((size_t)slot0 + k) * a.NC + c) * 2;
             n += p[0];
             d += p[1];
         }
@@ -576,12 +656,30 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_cols(StWeakArgs wa) 
         }
     }
     if (lane == 0) {
-        wa.weak[col] = R.bad ? __builtin_nanf("") : (float)(n / d);
+        wa.weak[col] = bad ? __builtin_nanf("") : (float)(n / d);
         if (wa.sums) { wa.sums[2 * col] = n; wa.sums[2 * col + 1] = d; }
     }
 }
 
 static size_t sw_ws_per_slot(int NC) { return (size_t)NC * 2 * sizeof(double); }
+
+// The two launches of sed_stitch_weak (Args = StWeakArgs) and of sed_stitch_span_tags (StSpanArgs): n_tiles workgroups of the
+// tile pass, one wave per column of the column pass.
+template <class Args>
+static int sw_launch(const Args& args, unsigned n_tiles, long long n_waves, void* stream) {
+    const StWeakArgs& wa = sw_args(args);
+    const int NC = wa.t.NC;
+    const bool vec = NC % 4 == 0 && ((uintptr_t)wa.win_strong % 16) == 0 && ((uintptr_t)wa.win_att % 16) == 0;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 tiles(n_tiles), thr256(ST_THREADS);
+    if (vec) hipLaunchKernelGGL((k_stitch_weak_tile<true, 4, Args>), tiles, thr256, 0, st, args);
+    else if (NC % 4 == 0) hipLaunchKernelGGL((k_stitch_weak_tile<false, 4, Args>), tiles, thr256, 0, st, args);
+    else hipLaunchKernelGGL((k_stitch_weak_tile<false, 1, Args>), tiles, thr256, 0, st, args);
+    SED_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_stitch_weak_cols<Args>, dim3((unsigned)((n_waves + 3) / 4)), thr256, 0, st, args);
+    SED_CHECK_LAUNCH();
+    return SED_OK;
+}
 
 extern "C" size_t sed_stitch_weak_ws_bytes(long long total_frames, int n_rec, int nclass) {
     const size_t n = st_ws_slot_count(total_frames, n_rec, nclass, 1, false);
@@ -600,16 +698,42 @@ extern "C" int sed_stitch_weak(const float* win_strong, const float* win_att, co
     ST_NEED(((uintptr_t)ws % 8) == 0, "ws must be 8-byte aligned");
     SED_TRY(st_ws_slots(what, ws_bytes, sw_ws_per_slot(NC), true, 1, &t));
     const StWeakArgs wa = {t, win_strong, win_att, (double*)ws, weak, sums};
-    const bool vec = NC % 4 == 0 && ((uintptr_t)win_strong % 16) == 0 && ((uintptr_t)win_att % 16) == 0;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 tiles((unsigned)t.n_slots), thr256(ST_THREADS);
-    if (vec) hipLaunchKernelGGL((k_stitch_weak_tile<true, 4>), tiles, thr256, 0, st, wa);
-    else if (NC % 4 == 0) hipLaunchKernelGGL((k_stitch_weak_tile<false, 4>), tiles, thr256, 0, st, wa);
-    else hipLaunchKernelGGL((k_stitch_weak_tile<false, 1>), tiles, thr256, 0, st, wa);
-    SED_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_stitch_weak_cols, dim3((unsigned)(((long long)n_rec * NC + 3) / 4)), thr256, 0, st, wa);
-    SED_CHECK_LAUNCH();
-    return SED_OK;
+    return sw_launch(wa, (unsigned)t.n_slots, (long long)n_rec * NC, stream);
+}
+
+// ---- span-level weak tags (sed_stitch_span_tags) ------------------------------------------------------------------------------
+// The slots of a call: tps = ceil(span3 / ST_TILE) per span, or 0 where a size is out of range.
+static long long sp_tps(int span3) { return ((long long)span3 + ST_TILE - 1) / ST_TILE; }
+static size_t sp_slot_count(long long total_frames, long long total_spans, int n_rec, int NC, int span3) {
+    if (total_frames < 1 || n_rec < 1 || NC < 1 || NC > ST_MAXC || span3 < 1 || total_spans < n_rec || total_spans > total_frames ||
+        total_frames * NC >= (1ll << 31) || total_spans * NC >= (1ll << 31) || total_spans * sp_tps(span3) >= (1ll << 31)) return 0;
+    return (size_t)(total_spans * sp_tps(span3));
+}
+
+extern "C" size_t sed_stitch_span_tags_ws_bytes(long long total_frames, long long total_spans, int n_rec, int nclass, int span3) {
+    const size_t n = sp_slot_count(total_frames, total_spans, n_rec, nclass, span3);
+    if (!n) sed_set_error("sed_stitch_span_tags_ws_bytes: need span3 >= 1, 1 <= n_rec <= total_spans <= total_frames, "
+                          "1 <= nclass <= 16, total_frames * nclass < 2^31, total_spans * ceil(span3 / %d) < 2^31", ST_TILE);
+    return n * sw_ws_per_slot(nclass);
+}
+
+extern "C" int sed_stitch_span_tags(const float* win_strong, const float* win_att, const int32_t* rec_win0,
+                                    const int64_t* rec_frame0, const int64_t* rec_span0, long long total_frames,
+                                    long long total_spans, int n_rec, int T3, int NC, int hop3, int weighting, int span3,
+                                    float* tags, double* sums, void* ws, size_t ws_bytes, int32_t* err, void* stream) {
+    const char* what = "sed_stitch_span_tags";
+    ST_NEED(win_strong && win_att && rec_win0 && rec_frame0 && rec_span0 && tags && ws && err, "null argument");
+    StTables t;
+    SED_TRY(st_front(what, rec_win0, rec_frame0, err, n_rec, T3, NC, hop3, weighting, 1, 31, &t));
+    ST_NEED(((uintptr_t)ws % 8) == 0, "ws must be 8-byte aligned");
+    const size_t n_slots = sp_slot_count(total_frames, total_spans, n_rec, NC, span3);
+    ST_NEED(n_slots, "need span3 >= 1, n_rec <= total_spans <= total_frames, total_frames * NC < 2^31 and "
+                     "total_spans * ceil(span3 / tile) < 2^31");
+    ST_NEED(ws_bytes == n_slots * sw_ws_per_slot(NC), "ws_bytes must be the value sed_stitch_span_tags_ws_bytes returned for these sizes");
+    t.n_slots = 0x7fffffff;                                                      // (st_rec's slot check is the recording layout's)
+    const StSpanArgs sa = {{t, win_strong, win_att, (double*)ws, tags, sums}, rec_span0, total_spans, span3, (int)sp_tps(span3)};
+    const long long rows = total_spans * NC;
+    return sw_launch(sa, (unsigned)n_slots, rows > n_rec ? rows : n_rec, stream);
 }
 
 // ---- backward through the pooled tag (sed_stitch_weak_backward) ---------------------------------------------------------------

@@ -23,6 +23,10 @@ events across short gaps on any of these tables (``sed_events_process``; ``proce
 Confidence scores: ``events_scores`` / ``get_long_predictions(event_scores=True)`` give every event of such a table the maximum
 and the mean of the blended timeline over its frames (``sed_events_scores``), ``events_select`` /
 ``get_long_predictions(min_event_score=...)`` keep the events whose score exceeds a minimum (``sed_events_select``).
+Span-level weak tags and the tag gate: ``stitch_span_tags`` / ``get_long_predictions(tag_span=...)`` pool the weak tag per span
+of time (``sed_stitch_span_tags``, ``span_table``, ``span_tags_dataframe``), ``events_tag_scores`` gives every event the largest
+tag of the spans it touches (``sed_events_tag_scores``) and ``gate_decoded`` / ``get_long_predictions(min_span_tag=...)`` keep
+the events that touch a confident span (``events_select`` on that score).
 ``get_predictions`` itself is unchanged.
 """
 import ctypes as C
@@ -665,6 +669,143 @@ def weak_tags_dataframe(weak, filenames, labels, threshold=0.5):
                         columns=["filename", "event_labels"])
 
 
+def span_table(long_set_or_L3s, span3, device=None):
+    """The span offsets of recordings cut into spans of ``span3`` label frames (include/dcase_sed.h: recording r with L3_r
+    frames has ceil(L3_r / span3) spans, only the last may be shorter).  ``long_set_or_L3s``: a ``LongRecordingSet`` or the
+    recordings' lengths in label frames.  ``span3`` is clamped to the longest recording, so an "infinite" span is one span per
+    recording.  Returns ``(rec_span0 host int64 [n_rec + 1], rec_span0 on the device, total_spans, span3 clamped)``; the device
+    is the set's, or ``device`` - given lengths and no device, the device table is None and nothing touches a GPU."""
+    if isinstance(long_set_or_L3s, LongRecordingSet):
+        L3s = np.diff(long_set_or_L3s.rec_frame0_host)
+        device = long_set_or_L3s.rec_frame0.device if device is None else device
+    else:
+        L3s = np.asarray(list(long_set_or_L3s), dtype=np.int64).reshape(-1)
+    if L3s.size < 1 or (L3s < 1).any():
+        raise ValueError("span_table: at least one recording, every length >= 1 label frame")
+    if isinstance(span3, (float, np.floating)) and not np.isfinite(span3):
+        if not span3 > 0:
+            raise ValueError(f"span3 must be >= 1 label frame, got {span3!r}")
+        span3 = int(L3s.max())
+    if int(span3) != span3 or span3 < 1:
+        raise ValueError(f"span3 must be a whole number of label frames >= 1, got {span3!r}")
+    span3 = int(min(int(span3), int(L3s.max())))
+    host = np.concatenate([[0], np.cumsum((L3s + span3 - 1) // span3)]).astype(np.int64)
+    dev_table = None if device is None else torch.from_numpy(host).to(device)
+    return host, dev_table, int(host[-1]), span3
+
+
+def stitch_span_tags(win_strong, win_att, rec_win0, rec_frame0, total_frames, hop3, span3, weighting="taper", want_sums=False,
+                     rec_frame0_host=None):
+    """Span-level weak tags (``sed_stitch_span_tags``): ``stitch_weak``'s blend and fp64 pooling per span of ``span3`` label
+    frames of every recording instead of per recording (the definition is in include/dcase_sed.h); arguments as for
+    ``stitch_weak``.  The span table needs the recordings' lengths on the host: ``rec_frame0_host`` (a ``LongRecordingSet``
+    has it) - without it ``rec_frame0`` is copied to the host once.  ``span3`` is clamped to the longest recording.  Returns a
+    dict, the tensors on the device: ``tags`` [total_spans, nclass] float32, ``sums`` [total_spans, nclass, 2] float64 (num,
+    den) or None, ``rec_span0`` [n_rec + 1] int64, ``rec_span0_host``, ``total_spans``, ``span3`` (clamped), ``err`` [1] int32
+    (``STITCH_ERR_BITS`` 16 / 32: the rows of such a recording are NaN).  Two launches."""
+    total, hop3, weighting = _weak_inputs("stitch_span_tags", win_strong, win_att, rec_win0, total_frames, hop3, weighting)
+    if rec_frame0_host is None:
+        rec_frame0_host = rec_frame0.cpu().numpy()
+    dev = win_strong.device
+    host, rec_span0, total_spans, span3 = span_table(np.diff(np.asarray(rec_frame0_host, dtype=np.int64)), span3, dev)
+    n_win, T3, NC = win_strong.shape
+    n_rec = rec_win0.numel() - 1
+    l = _lib.lib()
+    ws_bytes = l.sed_stitch_span_tags_ws_bytes(total, total_spans, n_rec, NC, span3)
+    if ws_bytes == 0:
+        raise ValueError(f"sed_stitch_span_tags_ws_bytes: {l.sed_last_error().decode()}")
+    win_strong, win_att = win_strong.contiguous().float(), win_att.contiguous().float()
+    tags = torch.empty(total_spans, NC, dtype=torch.float32, device=dev)
+    sums = torch.empty(total_spans, NC, 2, dtype=torch.float64, device=dev) if want_sums else None
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = _lib.scratch(ws_bytes, dev)
+    _lib.check(l.sed_stitch_span_tags(_lib.ptr(win_strong), _lib.ptr(win_att), _lib.ptr(rec_win0), _lib.ptr(rec_frame0),
+                                      _lib.ptr(rec_span0), total, total_spans, n_rec, T3, NC, hop3, weighting, span3, _lib.ptr(tags),
+                                      _lib.ptr(sums), _lib.ptr(ws), ws.numel(), _lib.ptr(err), _lib.stream_ptr()),
+               "sed_stitch_span_tags")
+    return {"tags": tags, "sums": sums, "rec_span0": rec_span0, "rec_span0_host": host, "total_spans": total_spans, "span3": span3,
+            "err": err}
+
+
+def events_tag_scores(out_or_table, tags, rec_span0, span3, n_rec, nclass, err=None):
+    """``sed_events_tag_scores``: per event of a CSR table on the device the largest non-NaN span tag among the spans it
+    touches (``tags`` [total_spans, nclass] cuda float32 and ``rec_span0`` [n_rec + 1] int64 as ``stitch_span_tags`` returns
+    them, ``span3`` the clamped span length it used).  ``out_or_table`` as for ``events_scores``.  Returns ``(tag_score
+    float32 [pairs_capacity], err [1] int32)``; a given ``err`` is OR-ed into.  One launch, nothing synchronises."""
+    ev_ptr, ev_pairs = (out_or_table["ev_ptr"], out_or_table["ev_pairs"]) if isinstance(out_or_table, dict) else out_or_table
+    if ev_pairs.device.type != "cuda" or tags.device.type != "cuda":
+        raise _lib.SedError("events_tag_scores needs GPU tensors (no CPU fallback)")
+    n_rec, nclass, span3 = int(n_rec), int(nclass), int(span3)
+    n_cols, pairs_cap, _ = _table_shape("events_tag_scores", ev_ptr, ev_pairs, n_rec, nclass)
+    if tags.dtype != torch.float32 or tags.numel() % nclass or rec_span0.dtype != torch.int64 or rec_span0.numel() != n_rec + 1 \
+            or span3 < 1:
+        raise ValueError(f"events_tag_scores: tags float32 [total_spans, {nclass}], rec_span0 int64 [{n_rec + 1}] and "
+                         "span3 >= 1 expected")
+    dev, ev_pairs, ev_ptr = ev_pairs.device, ev_pairs.contiguous(), ev_ptr.contiguous()
+    tags, rec_span0 = tags.contiguous(), rec_span0.contiguous()
+    tag_score = torch.empty(pairs_cap, dtype=torch.float32, device=dev)
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().sed_events_tag_scores(_lib.ptr(tags), tags.numel() // nclass, _lib.ptr(rec_span0), span3, n_rec, nclass,
+                                                _lib.ptr(ev_ptr), _lib.ptr(ev_pairs), pairs_cap, n_cols, _lib.ptr(tag_score),
+                                                _lib.ptr(err), _lib.stream_ptr()), "sed_events_tag_scores")
+    return tag_score, err
+
+
+def gate_decoded(out, span_tags, n_rec, nclass, min_tag):
+    """The tag gate on the dict a stitch entry returned: an event is kept iff the largest tag of the spans it touches exceeds
+    ``min_tag`` of its (point, class) - strictly, and an event whose spans are all NaN is never kept.  ``span_tags``: the dict
+    of ``stitch_span_tags``; ``min_tag``: a scalar, one value per class, a host ``[K, nclass]`` array or a device float32
+    tensor, as ``events_select``'s ``min_score``.  ``events_tag_scores``, then ``events_select`` with the tag score as the
+    key: four launches, nothing synchronises.  Returns the same dict with the gated table (same capacity) and ``tag_score``,
+    the kept events' scores; its ``err`` is the decode's own word with both steps' bits OR-ed in on the device.  Scores a
+    ``score_decoded`` left in the dict belong to the table before the gate and are dropped."""
+    tag_score, err = events_tag_scores(out, span_tags["tags"], span_tags["rec_span0"], span_tags["span3"], n_rec, nclass,
+                                       err=out["err"])
+    ev_ptr, ev_pairs, tag_score, _, err = events_select(out["ev_ptr"], out["ev_pairs"], tag_score, None, n_rec, nclass, min_tag,
+                                                        "max", err=err)
+    out = {k: v for k, v in out.items() if k not in ("score_max", "score_mean")}
+    return dict(out, ev_ptr=ev_ptr, ev_pairs=ev_pairs, tag_score=tag_score, err=err)
+
+
+def span_tags_dataframe(tags, rec_span0, span3, filenames, labels, threshold=0.5, frame_seconds=None, L3s=None):
+    """The span-level twin of ``weak_tags_dataframe``: one row per (recording, span) with ``filename``, ``onset``, ``offset``
+    (seconds: span s of a recording covers the label frames ``s * span3 .. (s + 1) * span3`` of ``frame_seconds`` each -
+    default: the frame of baseline/config.py at pooling ratio 1; the last span's offset is cut at the recording's end when
+    its length ``L3s`` in label frames is given) and ``event_labels``: the labels whose tag exceeds ``threshold`` (a scalar or
+    one value per class), comma-joined in label order.  ``tags`` [total_spans, nclass]: a device tensor or an array;
+    ``rec_span0`` [n_rec + 1]: the host table of ``span_table``."""
+    tags = tags.detach().cpu().numpy() if torch.is_tensor(tags) else np.asarray(tags)
+    rec_span0 = rec_span0.cpu().numpy() if torch.is_tensor(rec_span0) else np.asarray(rec_span0, dtype=np.int64)
+    labels, filenames, span3 = list(labels), list(filenames), int(span3)
+    if rec_span0.shape != (len(filenames) + 1,) or tags.shape != (int(rec_span0[-1]), len(labels)) or span3 < 1:
+        raise ValueError(f"tags is {tags.shape}, rec_span0 {rec_span0.shape}: expected {(int(rec_span0[-1]), len(labels))} "
+                         f"(spans, labels) and {(len(filenames) + 1,)}")
+    frame_seconds = _Cfg.hop_length / _Cfg.sample_rate if frame_seconds is None else float(frame_seconds)
+    per_rec = np.diff(rec_span0)
+    rec = np.repeat(np.arange(len(filenames)), per_rec)
+    s = np.arange(len(rec)) - np.repeat(rec_span0[:-1], per_rec)
+    off = (s + 1) * span3
+    if L3s is not None:
+        off = np.minimum(off, np.asarray(list(L3s), dtype=np.int64)[rec])
+    on = tags > _per_class(threshold, len(labels), np.float32, "threshold")[None, :]
+    return pd.DataFrame({"filename": np.asarray(filenames, dtype=object)[rec], "onset": s * span3 * frame_seconds,
+                         "offset": off * frame_seconds,
+                         "event_labels": [",".join(l for l, k in zip(labels, row) if k) for row in on]},
+                        columns=["filename", "onset", "offset", "event_labels"])
+
+
+def tag_span_frames(tag_span, frame_seconds):
+    """``tag_span`` seconds as whole label frames of ``frame_seconds`` each: rounded down, at least 1 (an infinite span stays
+    infinite: ``span_table`` clamps it).  ValueError unless ``tag_span > 0``."""
+    tag_span = float(tag_span)
+    if not tag_span > 0:
+        raise ValueError(f"tag_span must be > 0 seconds, got {tag_span!r}")
+    if np.isinf(tag_span):
+        return tag_span
+    return max(int(np.floor(tag_span / float(frame_seconds) + 1e-9)), 1)
+
+
 def long_window_posteriors(model, long_set, nclass, batch_size=64, want_attention=False):
     """The strong posteriors [n_win, T3, nclass] of every window of ``long_set``, from the eval-mode model ``batch_size``
     windows at a time; they stay on the device.  ``want_attention=True``: ``(win_strong, win_att)``, the attention of the same
@@ -694,7 +835,8 @@ def long_window_posteriors(model, long_set, nclass, batch_size=64, want_attentio
 def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=None, save_predictions=None, batch_size=64,
                          cfg=None, threshold=0.5, median_window=None, weighting="taper", return_posteriors=False,
                          return_weak=False, threshold_high=None, min_event_length=None, min_event_gap=None,
-                         process_order="drop_merge", event_scores=False, min_event_score=None, score_key="max"):
+                         process_order="drop_merge", event_scores=False, min_event_score=None, score_key="max", tag_span=None,
+                         min_span_tag=None, return_span_tags=False):
     """Events of recordings of any lengths (a ``LongRecordingSet``): the windows go through the eval-mode model
     ``batch_size`` at a time, their strong posteriors are blended into one timeline per recording (``weighting``: "taper"
     or "uniform"), and ONE threshold, median filter and run-length decode runs over each whole timeline
@@ -718,7 +860,20 @@ def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=
     on the blended timeline (``events_scores``: the decode it already runs writes the timeline) and the columns ``score_max``
     / ``score_mean`` are appended to the frame and the TSV.  ``min_event_score`` (a scalar or one value per class; implies the
     scoring): only the events whose ``score_key`` ("max" or "mean") score exceeds it are kept (``events_select``, before the
-    host copy).  With the defaults nothing new is launched and the frame is column for column the same."""
+    host copy).  ``tag_span`` (seconds, rounded down to whole label frames, at least 1; ``float("inf")``: one span per
+    recording): span-level weak tags are pooled over spans of that length from the same single pass through the model
+    (``stitch_span_tags``).  ``min_span_tag`` (a scalar or one value per class; NaN raises): the tag gate - an event is kept
+    only when it touches a span whose tag exceeds it (``gate_decoded``), right after the decode (after the two-threshold
+    select), BEFORE ``events_process`` and the event scores: mask, then post-process.  ``return_span_tags=True`` appends
+    ``(tags [total_spans, nclass] device tensor, rec_span0 host, span3)`` to what is returned (``span_tags_dataframe`` makes
+    their table).  ``min_span_tag`` or ``return_span_tags`` without ``tag_span``: ``ValueError`` before any forward.  With the
+    defaults nothing new is launched and the frame is column for column the same."""
+    if tag_span is None and (min_span_tag is not None or return_span_tags):
+        raise ValueError("min_span_tag / return_span_tags need tag_span: the length of a span in seconds")
+    if tag_span is not None and not float(tag_span) > 0:
+        raise ValueError(f"tag_span must be > 0 seconds, got {tag_span!r}")
+    if min_span_tag is not None and np.isnan(np.asarray(min_span_tag, dtype=np.float64)).any():
+        raise ValueError("min_span_tag: NaN keeps no event; pass None to keep all")
     if not isinstance(long_set, LongRecordingSet):
         raise TypeError(f"long_set must be a LongRecordingSet, got {type(long_set).__name__}")
     cfg = cfg or _Cfg
@@ -752,9 +907,18 @@ def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=
         min_score = _per_class(min_event_score, NC, np.float32, "min_event_score").reshape(1, NC)
         if np.isnan(min_score).any():
             raise ValueError("min_event_score: NaN keeps no event; pass None to keep all")
+    if not isinstance(return_span_tags, (bool, np.bool_)):
+        raise ValueError(f"return_span_tags must be True or False, got {return_span_tags!r}")
+    if tag_span is not None:
+        span3 = tag_span_frames(tag_span, pool * cfg.hop_length / cfg.sample_rate)
+        if min_span_tag is not None:
+            min_tag = _per_class(min_span_tag, NC, np.float32, "min_span_tag").reshape(1, NC)
+            if np.isnan(min_tag).any():
+                raise ValueError("min_span_tag: NaN keeps no event; pass None to keep all")
     want_timeline = return_posteriors or scored
-    win_strong = long_window_posteriors(model, long_set, NC, batch_size, want_attention=return_weak)
-    if return_weak:
+    want_att = return_weak or tag_span is not None
+    win_strong = long_window_posteriors(model, long_set, NC, batch_size, want_attention=want_att)
+    if want_att:
         win_strong, win_att = win_strong
     if threshold_high is None:
         out = stitch_decode(win_strong, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3, thr, win,
@@ -764,6 +928,12 @@ def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=
         out = stitch_hysteresis(win_strong, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3, [thr],
                                 [threshold_high], [win], weighting, long_set.capacity(NC), want_timeline=want_timeline)
         calls = [("sed_stitch_sweep + sed_events_hysteresis", out["err"])]
+    if tag_span is not None:
+        span_tags = stitch_span_tags(win_strong, win_att, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames,
+                                     long_set.hop3, span3, weighting, rec_frame0_host=long_set.rec_frame0_host)
+        if min_span_tag is not None:                                             # mask, then post-process
+            out = gate_decoded(out, span_tags, long_set.n_rec, NC, min_tag)
+            calls = [(calls[0][0] + " + sed_events_tag_scores + sed_events_select (min_span_tag)", out["err"])]
     if process:
         out = process_decoded(out, long_set.n_rec, NC, min_len, max_gap, process_order)
         calls = [(calls[0][0] + " + sed_events_process", out["err"])]
@@ -779,6 +949,8 @@ def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=
         tags = stitch_weak(win_strong, win_att, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3,
                            weighting)
         calls.append(("sed_stitch_weak", tags["err"]))
+    if tag_span is not None:
+        calls.append(("sed_stitch_span_tags", span_tags["err"]))
     for what, word in calls:
         err = int(word.item())
         if err:
@@ -807,4 +979,6 @@ def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=
         result += ([out["timeline"][int(f0[r]):int(f0[r + 1])] for r in range(long_set.n_rec)], win_strong)
     if return_weak:
         result += (tags["weak"],)
+    if return_span_tags:
+        result += ((span_tags["tags"], span_tags["rec_span0_host"], span_tags["span3"]),)
     return result if len(result) > 1 else prediction_df

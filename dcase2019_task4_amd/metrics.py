@@ -1019,7 +1019,8 @@ def long_sweep_psds_counts_from_events(ests, ref, dtc=0.5, gtc=0.5, cttc=0.3, co
 
 def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, batch_size=64, cfg=None, weighting="taper",
                   psds=None, one_blend=True, max_table_bytes=1 << 30, weak_labels=None, weak_thresholds=None, error_rate=False,
-                  thresholds_high=None, min_event_lengths=None, min_event_gaps=None, process_order="drop_merge"):
+                  thresholds_high=None, min_event_lengths=None, min_event_gaps=None, process_order="drop_merge", tag_span=None,
+                  min_span_tags=None):
     """``validate`` for a ``LongRecordingSet``: the windows go through the model ONCE, then the K operating points are
     decoded and scored, and ONE device -> host copy ends the call.  ``one_blend=True``: the points are split into chunks
     (``longrec.sweep_chunks``: the event table of a chunk stays within ``max_table_bytes``); per chunk ONE
@@ -1050,9 +1051,18 @@ def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, 
     through ``inference.events_process`` (events shorter than the length dropped, events a gap of at most ``min_event_gaps``
     separates fused, in the order ``process_order``) before the scorers - per chunk one call on the chunk's whole table, after
     the two-threshold select; with ``one_blend=False`` one call per point.  Still one device -> host copy; both None: nothing
+    changes and no launch is added.
+    ``tag_span`` (seconds, as in ``inference.get_long_predictions``) with ``min_span_tags`` (K entries as ``thresholds``, or
+    one entry for all points, each a scalar or one value per class; NaN raises): the tag gate.  The forwards also hand out their
+    attention, the span-level weak tags are pooled ONCE per call (``inference.stitch_span_tags``), and every decoded table goes
+    through ``inference.gate_decoded`` - an event is kept only when it touches a span whose tag exceeds its point's minimum -
+    after the two-threshold select and before ``events_process`` and the scorers: per chunk one gate on the chunk's whole
+    table, with ``one_blend=False`` one per point.  Still one device -> host copy: the gate's error bits are OR-ed into the
+    decode's word and the span tags' word into the first table's.  One of the two without the other raises; both None: nothing
     changes and no launch is added."""
-    from .inference import (_order_code, _per_class, hysteresis_points, long_window_posteriors, process_decoded, process_points,
-                            stitch_decode, stitch_error_text, stitch_hysteresis, stitch_sweep, stitch_weak, sweep_points)
+    from .inference import (_order_code, _per_class, gate_decoded, hysteresis_points, long_window_posteriors, process_decoded,
+                            process_points, stitch_decode, stitch_error_text, stitch_hysteresis, stitch_span_tags, stitch_sweep,
+                            stitch_weak, sweep_points, tag_span_frames)
     from .longrec import LongRecordingSet, sweep_chunks
     cfg = cfg or _Cfg
     thresholds = list(thresholds)
@@ -1066,6 +1076,20 @@ def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, 
             raise ValueError("thresholds_high needs one_blend=True: the two decodes of a pair come from one sweep")
         if len(thresholds_high) not in (1, K):
             raise ValueError(f"thresholds_high must have {K} entries (or one)")
+    if (tag_span is None) != (min_span_tags is None):
+        raise ValueError("tag_span and min_span_tags go together: the span length in seconds and the K minimum tags")
+    gate = tag_span is not None
+    if gate:
+        min_span_tags = list(min_span_tags)
+        if len(min_span_tags) not in (1, K):
+            raise ValueError(f"min_span_tags must have {K} entries (or one)")
+        tag_span = float(tag_span)
+        if not tag_span > 0:
+            raise ValueError(f"tag_span must be > 0 seconds, got {tag_span!r}")
+        min_tag = np.stack([_per_class(min_span_tags[k % len(min_span_tags)], ref.nclass, np.float32, "a minimum span tag")
+                            for k in range(K)])
+        if np.isnan(min_tag).any():
+            raise ValueError("min_span_tags: NaN keeps no event")
     if weak_labels is None:
         if weak_thresholds is not None:
             raise ValueError("weak_thresholds without weak_labels: there is nothing to score the tags against")
@@ -1096,6 +1120,8 @@ def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, 
         _order_code(process_order)
         min_len, max_gap = process_points(min_event_lengths, min_event_gaps, ref.nclass,
                                           long_set.pooling_time_ratio * cfg.hop_length / cfg.sample_rate, K)
+    if gate:
+        span3 = tag_span_frames(tag_span, long_set.pooling_time_ratio * cfg.hop_length / cfg.sample_rate)
     if psds is not None and (psds.K, psds.NC) != (K, NC):
         raise ValueError("psds was built for another number of operating points / classes")
     if thresholds_high is not None:
@@ -1105,9 +1131,21 @@ def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, 
         thr_all, win_all = sweep_points(thresholds, median_windows, NC)
     counts = Counts(K, NC, dev)
     errors = ErrorCounts(K, NC, dev) if error_rate else None
-    win_strong = long_window_posteriors(model, long_set, NC, batch_size, want_attention=weak_labels is not None)
-    if weak_labels is not None:
+    win_strong = long_window_posteriors(model, long_set, NC, batch_size, want_attention=weak_labels is not None or gate)
+    if weak_labels is not None or gate:
         win_strong, win_att = win_strong
+    if gate:                                                                     # pooled once; its word travels with the first table's
+        span_tags = stitch_span_tags(win_strong, win_att, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames,
+                                     long_set.hop3, span3, weighting, rec_frame0_host=long_set.rec_frame0_host)
+        span_err = span_tags["err"]
+
+    def gated(out, k0, k1):
+        nonlocal span_err
+        if span_err is not None:
+            out["err"].bitwise_or_(span_err)
+            span_err = None
+        return gate_decoded(out, span_tags, long_set.n_rec, NC, min_tag[k0:k1])
+
     if one_blend:
         cap = long_set.capacity(NC)
         if thresholds_high is not None:                                          # chunks of 2 x points sweep points
@@ -1122,6 +1160,8 @@ def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, 
                 out = stitch_sweep(win_strong, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3,
                                    torch.from_numpy(thr_all[k0:k1]).to(dev), torch.from_numpy(win_all[k0:k1]).to(dev), weighting,
                                    (k1 - k0) * cap)
+            if gate:
+                out = gated(out, k0, k1)
             if process:
                 out = process_decoded(out, long_set.n_rec, NC, min_len[k0:k1], max_gap[k0:k1], process_order)
             long_sweep_event_counts(out, ref, long_set.pooling_time_ratio, cfg, counts=counts, point0=k0)
@@ -1135,6 +1175,8 @@ def validate_long(model, long_set, ref, thresholds=(0.5,), median_windows=None, 
             out = stitch_decode(win_strong, long_set.rec_win0, long_set.rec_frame0, long_set.total_frames, long_set.hop3,
                                 thresholds[k % len(thresholds)], median_windows[k % len(median_windows)], weighting,
                                 long_set.capacity(NC), want_timeline=False)
+            if gate:
+                out = gated(out, k, k + 1)
             if process:
                 out = process_decoded(out, long_set.n_rec, NC, min_len[k:k + 1], max_gap[k:k + 1], process_order)
             long_event_counts(out, ref, long_set.pooling_time_ratio, cfg, counts=counts, point=k)

@@ -777,7 +777,7 @@ int sed_events_select(const int64_t* ev_ptr, const int32_t* ev_pairs, const floa
  * NC % 4 == 0 and both window tensors are 16-byte aligned, a scalar path otherwise (the same summation order).  No host
  * synchronisation, no allocation, hipGraph-capturable.
  * Limits, checked before any launch (SED_ERR_BAD_ARG): NC <= 16, 1 <= hop3 <= T3 <= 4096, sum L3 * NC < 2^31.
- * Not provided: tags per sub-span of a recording.  The backward through the pooled tag is sed_stitch_weak_backward. */
+ * Tags per sub-span of a recording: sed_stitch_span_tags.  The backward through the pooled tag is sed_stitch_weak_backward. */
 size_t sed_stitch_weak_ws_bytes(long long total_frames, int n_rec, int nclass);
 int sed_stitch_weak(const float* win_strong, const float* win_att, const int32_t* rec_win0, const int64_t* rec_frame0,
                     int n_rec, int T3, int NC, int hop3, int weighting, float* weak, double* sums, void* ws,
@@ -818,6 +818,68 @@ int sed_stitch_weak_backward(const float* win_strong, const float* win_att, cons
                              const int64_t* rec_frame0, int n_rec, int T3, int NC, int hop3, int weighting,
                              const double* sums, const float* g_weak, float* d_win_strong, float* d_win_att,
                              int32_t* err, void* stream);
+
+/* ---- span-level weak tags of long recordings, and a tag-gated decode --------------------------------
+ * The recording-level tag says "class c occurs somewhere in recording r"; the span tags say it per span of span3 label frames,
+ * and the gate lets them veto the strong decode the way task-4 systems mask a clip's strong posteriors with its weak
+ * prediction.  The definitions are the project's own; pinned is agreement with a plain-loop statement (tests/span_tags_np.py).
+ *
+ * Spans.  span3 >= 1; recording r with L3_r timeline frames has S_r = ceil(L3_r / span3) spans, span s covers the frames
+ * [s * span3, min((s + 1) * span3, L3_r)) - only the last may be shorter.  rec_span0 [n_rec + 1] int64 (device) holds the span
+ * offsets: rec_span0[r + 1] - rec_span0[r] == S_r, total_spans = rec_span0[n_rec].
+ *
+ * Span tags.  P, A: the blends of win_strong / win_att exactly as for the recording-level tag above (one code; a frame covered
+ * by one window is copied exactly).  For span g of recording r, class c, over the span's frames u, in fp64:
+ *   num[g, c] = sum_u (double)P[u, c] * (double)A[u, c],  den[g, c] = sum_u (double)A[u, c],  tag[g, c] = (float)(num / den)
+ * No special case for den == 0 or NaN inputs.
+ *   tags [total_spans][NC] fp32;  sums [total_spans][NC][2] fp64 (num, den) or NULL
+ * The order of the sums is a function of the span's length in frames and of NC alone - not of the span's position, its
+ * recording, alignment or the 16-byte / scalar path - and it is the order the recording-level tag uses for a recording of that
+ * length: the tile pass walks a span from ITS first frame with the recording-level tile body, the span pass is the
+ * recording-level column pass.  A recording with one span (span3 >= L3_r) gets tags and sums bit-identical to the
+ * recording-level ones; two spans of equal length over equal frames give equal bits.
+ *   err  one int32, OR-ed (zero it first): 16 = malformed rec_win0 / rec_frame0 / rec_span0 - also a rec_span0 that disagrees
+ *        with ceil(L3_r / span3) or reaches beyond total_spans - , 32 = a recording whose windows do not cover it.  Every tags /
+ *        sums row in [0, total_spans) is written by the call: NaN where the row belongs to such a recording or to none, never
+ *        stale.  (The recording of a row is found by bisection: a rec_span0 that is not increasing can moreover leave rows of a
+ *        well-formed recording that the bisection assigns to another one; they are NaN too.)  The address guarantee of the
+ *        stitched decode holds for both window tensors, the outputs and the workspace.
+ *   ws   the _ws_bytes value for (sum L3, total_spans, n_rec, NC, span3), 8-byte aligned: one (num, den) pair per (tile slot,
+ *        class), slot = span * ceil(span3 / tile frames) + k; ws_bytes must be that value
+ * Two launches on `stream`, a tile pass and a span pass; no timeline is written, no float atomics, no host synchronisation, no
+ * allocation, hipGraph-capturable.
+ * Limits, checked before any launch (SED_ERR_BAD_ARG, outputs untouched): NC <= 16, 1 <= hop3 <= T3 <= 4096, span3 >= 1,
+ * n_rec <= total_spans <= total_frames, total_frames * NC < 2^31, total_spans * NC < 2^31, tile slots < 2^31 (a caller clamps
+ * an "infinite" span3 to the longest recording).
+ *
+ * Tag score of an event.  For event i = [on, off) of column (k, rec, c) of a CSR table (layout as for the event scores above):
+ *   tag_score[i] = the largest non-NaN tags[rec_span0[rec] + s][c] over s = on / span3 .. (off - 1) / span3, NaN when every
+ *   such tag is NaN: a copy of an input value, no arithmetic.  An event that ends on a span boundary does not touch the next
+ *   span.  It is the event-score kernel's maximum under a coordinate map (rows = spans), one launch, flat over ev_pairs; the
+ *   split between events reduced by their thread and by their wave is the event scores', applied to the spans touched.
+ *   err  16 as for the event scores (columns; rec_span0 against total_spans), 64 = an event with on < 0, on >= off or
+ *        off > S_rec * span3: its score is NaN and nothing of it is read.
+ * Limits and overlap checks as for the event scores (total_spans * NC < 2^31 in the place of the frames), span3 >= 1.
+ *
+ * The gate.  An event is kept iff tag_score > min_tag[k][c]: strict, a NaN score is never kept.  That IS the select by score
+ * above with key = 0 and the tag score in the score_max slot; there is no other kernel.  Consequences (tests pin them):
+ *   1. with one span per recording a column is kept whole or dropped whole, exactly where the recording-level tag exceeds
+ *      min_tag: the clip-level weak mask;
+ *   2. an event that lies across a span boundary is kept when either side is confident;
+ *   3. min_tag = -inf returns the table byte for byte;  4. a K-point call equals K one-point calls;
+ *   5. the rule is "keep whole events that touch a confident span", NOT "zero the posteriors of unconfident spans, then
+ *      decode", which cuts events at span boundaries.  By hand: span3 = 4, one class, tags (0.9, 0.1), min_tag 0.5, one
+ *      decoded event [2, 7).  The gate keeps [2, 7) whole (it touches span 0); masking the posteriors of span 1 first and
+ *      decoding would give [2, 4).
+ * Not provided: a backward through the span tags, overlapping or per-recording span lengths, masking in the frame domain. */
+size_t sed_stitch_span_tags_ws_bytes(long long total_frames, long long total_spans, int n_rec, int nclass, int span3);
+int sed_stitch_span_tags(const float* win_strong, const float* win_att, const int32_t* rec_win0, const int64_t* rec_frame0,
+                         const int64_t* rec_span0, long long total_frames, long long total_spans, int n_rec, int T3, int NC,
+                         int hop3, int weighting, int span3, float* tags, double* sums, void* ws, size_t ws_bytes, int32_t* err,
+                         void* stream);
+int sed_events_tag_scores(const float* tags, long long total_spans, const int64_t* rec_span0, int span3, int n_rec, int NC,
+                          const int64_t* ev_ptr, const int32_t* ev_pairs, long long pairs_capacity, long long n_cols,
+                          float* tag_score, int32_t* err, void* stream);
 
 /* ---- validation scoring ------------------------------------------------------------------------
  * Replaces, after get_predictions, the host-side scoring of the epoch loop (baseline/main.py:328-352):

@@ -872,6 +872,123 @@ def scores_workload(name, model, rounds, reps, boundary_libs):
     return out
 
 
+def host_tag_gate(ev_ptr, pairs, tags, rec_span0, span3, n_rec, NC, mins):
+    """The tag gate on the host: reduceat of the class-major tags over the events' span ranges, then a boolean mask: numpy arrays
+    -> (out_ptr, out_pairs, kept tag scores)."""
+    n_cols, total = len(ev_ptr) - 1, tags.shape[0]
+    col = np.repeat(np.arange(n_cols, dtype=np.int64), np.diff(ev_ptr))
+    base = (col % NC) * total + rec_span0[(col // NC) % n_rec]
+    lo, hi = pairs[:, 0].astype(np.int64) // span3, (pairs[:, 1].astype(np.int64) - 1) // span3 + 1
+    idx = np.stack([base + lo, base + hi], 1).reshape(-1)
+    x = np.r_[np.ascontiguousarray(tags.T).reshape(-1), np.float32(0)]                # (an end index may be the array's length)
+    score = np.maximum.reduceat(x, idx)[::2] if len(idx) else np.zeros(0, np.float32)
+    keep = score > mins.reshape(-1)[(col // (n_rec * NC)) * NC + col % NC]
+    out_ptr = np.r_[0, np.cumsum(np.bincount(col[keep], minlength=n_cols))].astype(np.int64)
+    return out_ptr, pairs[keep], score[keep]
+
+
+def span_tags_workload(name, model, rounds, reps, tag_span=10.0, min_tag=0.5):
+    """--span-tags: (a) get_long_predictions(tag_span=10 s, min_span_tag=0.5) against the same run's plain call; (b) validate_long
+    with the gate at 50 points against the same run's call without it; (c) sed_stitch_span_tags alone at span3 = T3, 1 and one
+    span per recording against two stitch_decode(want_timeline=True) blends and a torch fp64 segment_reduce over the spans; (d)
+    sed_events_tag_scores + sed_events_select alone on the 50-point table against the host route (tables and tags copied
+    down, reduceat on the coarsened pairs, a boolean mask, upload)."""
+    from dcase2019_task4_amd import metrics
+    info, ctx = scoring_workload(name, model, rounds, reps, setup_only=True)
+    ls, ref_ev, window, win_strong, thr50 = ctx["ls"], ctx["ref_ev"], ctx["window"], ctx["win_strong"], ctx["thr50"]
+    out = {k: info[k] for k in ("recordings", "windows", "timeline_frames", "median_window", "reference_events")}
+    frame_seconds = ls.pooling_time_ratio * inference._Cfg.hop_length / inference._Cfg.sample_rate
+    span3 = inference.tag_span_frames(tag_span, frame_seconds)
+    out.update(rounds=rounds, points=50, tag_span_s=tag_span, span3=span3, T3=ls.T3, hop3=ls.hop3, min_span_tag=min_tag)
+    labels, state = _Enc.labels, {}
+
+    def alternate(legs):
+        for fn in legs.values():
+            fn()
+        ms = {leg: [] for leg in legs}
+        for _ in range(rounds):
+            for leg, fn in legs.items():
+                ms[leg].append(wall_ms(fn))
+        t = {leg: stats(ms[leg]) for leg in legs}
+        a, b = (t[leg] for leg in legs)
+        band = max(max(x["samples_ms"]) - min(x["samples_ms"]) for x in (a, b))
+        t["difference"] = {"added_ms": b["median_ms"] - a["median_ms"], "larger_max_minus_min_ms": band,
+                           "outside_the_band": bool(abs(b["median_ms"] - a["median_ms"]) > band)}
+        return t
+    out["get_long_predictions"] = alternate({
+        "predictions": lambda: state.__setitem__("plain_df", inference.get_long_predictions(model, ls, labels, POOL, batch_size=BATCH)),
+        "predictions_gated": lambda: state.__setitem__("gated_df", inference.get_long_predictions(
+            model, ls, labels, POOL, batch_size=BATCH, tag_span=tag_span, min_span_tag=min_tag))})
+    out["get_long_predictions"]["events"] = {"plain": len(state["plain_df"]), "gated": len(state["gated_df"])}
+    out["validate_long"] = alternate({
+        "validate_long_50": lambda: state.__setitem__("plain", metrics.validate_long(model, ls, ref_ev, thr50, [window], batch_size=BATCH)),
+        "validate_long_50_gated": lambda: state.__setitem__("gated", metrics.validate_long(
+            model, ls, ref_ev, thr50, [window], batch_size=BATCH, tag_span=tag_span, min_span_tags=[min_tag]))})
+    out["validate_long"]["estimated_events_point_0"] = {what: int(sum(v["Nsys"] for v in state[what][0][0].class_wise.values()))
+                                                        for what in ("plain", "gated")}
+    # (c) the span tags alone
+    _, win_att = inference.long_window_posteriors(model, ls, NCLASS, BATCH, want_attention=True)
+    dev, total = win_strong.device, ls.total_frames
+    thr = torch.full((NCLASS,), 0.5, device=dev)
+    win = torch.full((NCLASS,), 1, dtype=torch.int32, device=dev)
+    lengths_host = np.diff(ls.rec_frame0_host)
+    out["span_tags_alone"] = {}
+    for what, s3 in (("span3_T3", ls.T3), ("span3_1", 1), ("whole_recording", int(lengths_host.max()))):
+        host, _, total_spans, s3 = inference.span_table(lengths_host, s3)
+        span_len = torch.from_numpy(np.concatenate([np.minimum(s3, L - np.arange(0, L, s3)) for L in lengths_host])).to(dev)
+
+        def fused(s3=s3):
+            state["tags"] = inference.stitch_span_tags(win_strong, win_att, ls.rec_win0, ls.rec_frame0, total, ls.hop3, s3,
+                                                       rec_frame0_host=ls.rec_frame0_host)
+
+        def composed(span_len=span_len):
+            tl = [inference.stitch_decode(w, ls.rec_win0, ls.rec_frame0, total, ls.hop3, thr, win, "taper", ls.capacity(NCLASS),
+                                          want_timeline=True)["timeline"].double() for w in (win_strong, win_att)]
+            num = torch.segment_reduce(tl[0] * tl[1], "sum", lengths=span_len, axis=0, unsafe=True)
+            den = torch.segment_reduce(tl[1], "sum", lengths=span_len, axis=0, unsafe=True)
+            state["composed"] = (num / den).float()
+        t = {"total_spans": total_spans, "span3": s3, "sed_stitch_span_tags": event_ms(fused, reps), "composed_route": event_ms(composed, reps)}
+        assert int(state["tags"]["err"].item()) == 0
+        t["max_abs_difference_of_the_two_routes"] = float((state["tags"]["tags"] - state["composed"]).abs().max().item())
+        band = max(x["spread"] * x["median_ms"] for x in (t["sed_stitch_span_tags"], t["composed_route"]))
+        t["composed_minus_fused_ms"] = t["composed_route"]["median_ms"] - t["sed_stitch_span_tags"]["median_ms"]
+        t["larger_max_minus_min_ms"] = band
+        t["outside_the_band"] = bool(abs(t["composed_minus_fused_ms"]) > band)
+        out["span_tags_alone"][what] = t
+    # (d) the gate alone, on the table of one sweep of the 50 points
+    cap = ls.capacity(NCLASS)
+    table = inference.stitch_sweep(win_strong, ls.rec_win0, ls.rec_frame0, total, ls.hop3, thr50, [window], "taper", 50 * cap)
+    assert int(table["err"].item()) == 0
+    span_tags = inference.stitch_span_tags(win_strong, win_att, ls.rec_win0, ls.rec_frame0, total, ls.hop3, span3,
+                                           rec_frame0_host=ls.rec_frame0_host)
+    mins = np.full((50, NCLASS), min_tag, np.float32)
+    d_mins = torch.from_numpy(mins).cuda()
+
+    def device():
+        state["dev"] = inference.gate_decoded(table, span_tags, ls.n_rec, NCLASS, d_mins)
+
+    def host():
+        p = table["ev_ptr"].cpu().numpy()
+        q = table["ev_pairs"][:int(p[-1])].cpu().numpy()
+        out_ptr, out_pairs, kept = host_tag_gate(p, q, span_tags["tags"].cpu().numpy(), span_tags["rec_span0"].cpu().numpy(),
+                                                 span_tags["span3"], ls.n_rec, NCLASS, mins)
+        state["host"] = (torch.from_numpy(out_ptr).cuda(), torch.from_numpy(np.ascontiguousarray(out_pairs)).cuda())
+    for _ in range(3):
+        host()
+    host_ms = stats([wall_ms(host) for _ in range(reps)])
+    g = {"sed_events_tag_scores_plus_sed_events_select": event_ms(device, reps),
+         "host_copy_reduceat_mask_upload": {"median_ms": host_ms["median_ms"], "spread": host_ms["spread"], "reps": reps,
+                                            "timing": "host clock around the synchronised route"}}
+    h_ptr, h_pairs = state["host"]
+    n = int(h_ptr[-1].item())
+    identical = bool(torch.equal(state["dev"]["ev_ptr"], h_ptr) and torch.equal(state["dev"]["ev_pairs"][:n], h_pairs))
+    assert identical, "the device gate and the host route disagree"
+    g.update(pairs_capacity=int(table["ev_pairs"].shape[0]), input_events=int(table["ev_ptr"][-1].item()), result_events=n,
+             err=int(state["dev"]["err"].item()), routes_identical=identical)
+    out["gate_alone"] = g
+    return out
+
+
 def weak_workload(name, model, rounds, reps):
     import ctypes as C
     n_rec, per = WORKLOADS[name]
@@ -1076,6 +1193,8 @@ def main():
                     help="measure minimum event length and gap merging (profiles/long_process.json)")
     ap.add_argument("--scores", action="store_true",
                     help="measure the event scores and the select by score (profiles/long_scores.json)")
+    ap.add_argument("--span-tags", action="store_true",
+                    help="measure the span-level weak tags and the tag gate (profiles/long_span_tags.json)")
     ap.add_argument("--boundary-libs", default="",
                     help="with --scores: comma-separated builds of the library with other EVS_SHORT_FRAMES (csrc/evscore.hip)")
     ap.add_argument("--scores-child", default=None, help=argparse.SUPPRESS)
@@ -1088,7 +1207,7 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(REPO, "profiles", "long_scores.json" if args.scores else "long_process.json" if args.process else
+        args.out = os.path.join(REPO, "profiles", "long_span_tags.json" if args.span_tags else "long_scores.json" if args.scores else "long_process.json" if args.process else
                                 "long_hysteresis.json" if args.hysteresis else
                                 "error_rate.json" if args.error_rate else
                                 "long_tag_train.json" if args.tag_train else "long_weak.json" if args.weak else
@@ -1108,6 +1227,25 @@ def main():
               "not_measured": ["from_waveforms / feature extraction", "other batch sizes, bf16 / wide models",
                                "recordings longer than 1 h", "a run with the GPU to itself (the host is shared)"],
               "workloads": {}}
+    if args.span_tags:
+        result["timing"] = ("get_long_predictions / validate_long legs: host clock around each synchronised call, the two legs "
+                            "alternated in one run, --rounds rounds, medians, spread = (max - min) / median; the calls alone: a "
+                            "device-event pair around the Python call (output and workspace allocation included), warm, median of "
+                            "--decode-reps; the host route: host clock around the synchronised route, same reps")
+        result["note"] = ("get_long_predictions(tag_span=10 s, min_span_tag=0.5) against the same run's plain call; validate_long "
+                          "with the gate at 50 points against the same run's call without it; a difference counts only where it "
+                          "lies outside the larger (max - min) of its two legs.  The composed route (two stitch_decode blends and "
+                          "a torch fp64 segment_reduce over the spans) and the host gate are the only routes there were before")
+        result["not_measured"] += ["other nclass than 10", "other hops than the default", "recordings beyond 1 h",
+                                   "the kernels one by one", "other K than 50", "other span lengths through the two callers",
+                                   "with a high threshold, events_process or the event scores behind the gate"]
+        for name in args.workloads.split(","):
+            result["workloads"][name] = span_tags_workload(name, model, args.rounds, args.decode_reps)
+            print(json.dumps({name: result["workloads"][name]}), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(json.dumps(result, indent=1) + "\n")
+        return
     if args.scores:
         result["timing"] = ("get_long_predictions legs: host clock around each synchronised call, the two legs alternated in one run, "
                             "--rounds rounds, medians, spread = (max - min) / median; sed_events_scores / sed_events_select alone: "
