@@ -1,8 +1,8 @@
 // evproc.hip - minimum event length and gap merging on a CSR event table: sed_events_process drops the events of a column
 // that are shorter than min_len and fuses consecutive events whose gap is at most max_gap, in either order (the definition
-// is in include/dcase_sed.h).  The second event-domain operator beside hyst.hip, on the same flat geometry (evtable.h holds
-// the helpers hyst.hip wrote first; hyst.hip itself is untouched and keeps its copies): a
-// thread owns one index of `pairs`, a wave's decisions are one ballot word, one-workgroup scans carry them across workgroups.
+// is in include/dcase_sed.h).  An event-domain operator on the flat geometry and the compaction of evtable.h, which the
+// select of evscore.hip shares (hyst.hip alone keeps its own copies): a thread owns one index of `pairs`, a wave's decisions
+// are one ballot word, one-workgroup scans carry them across workgroups.  The scan kernel of both files lives here.
 //
 // Both orders are the same two questions, asked of two flag words A and B per index:
 //   "the last index < p with A set"      the A words of p's workgroup, then the scanned per-workgroup maximum (ev_last_before)
@@ -30,20 +30,12 @@
 #include "evtable.h"
 
 struct EvpArgs {
-    const int64_t* ptr;
-    const int32_t* pairs;
-    long long cap, n_cols;       // pairs_capacity; columns
+    EvTable t;                   // bal / cnt: the flags B and their counts
+    uint64_t* bal_a;             // ws: [n_blocks][HY_WAVES] the flags A of 64 indices
+    int32_t* last_a;             // ws: [n_blocks + 1] the last A index of a workgroup; after the scan that of all workgroups before it
     long long span;              // n_rec * NC: the columns of one point
     int NC;
     const int32_t *min_len, *max_gap;                // [n_cols / span][NC]
-    int64_t* out_ptr;
-    int32_t* out_pairs;
-    long long out_cap;
-    uint64_t *bal_a, *bal_b;     // ws: [n_blocks][HY_WAVES] the flags A and B of 64 indices
-    int32_t* last_a;             // ws: [n_blocks + 1] the last A index of a workgroup; after the scan that of all workgroups before it
-    int32_t* cnt_b;              // ws: [n_blocks + 1] B flags per workgroup; after the scan those in front of it, then the total
-    int32_t* err;
-    long long n_blocks;          // ceil(cap / HY_THREADS)
 };
 
 // The last index < p with its A flag set, -1 when there is none; 0 <= p <= cap.  At most HY_WAVES words and one carry.
@@ -56,29 +48,24 @@ __device__ __forceinline__ long long ev_last_before(const EvpArgs& e, long long 
     return word ? w * 64 + 63 - __clzll((long long)word) : (long long)e.last_a[q / HY_THREADS];
 }
 
-// The parameters' entry of column c: (point, class).
-__device__ __forceinline__ long long ev_param(const EvpArgs& e, long long c) { return (c / e.span) * e.NC + c % e.NC; }
-
-__device__ __forceinline__ bool ev_bit(const uint64_t* bal, long long i) { return (bal[i >> 6] >> (i & 63)) & 1ull; }
-
 template <int ORDER>
 __global__ __launch_bounds__(HY_THREADS) void k_evp_flag(EvpArgs e) {
     __shared__ uint64_t s_word[HY_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long long i = (long long)blockIdx.x * HY_THREADS + tid;
     bool flag = false;
-    if (i < e.cap) {
+    if (i < e.t.cap) {
         long long a, b;
-        const long long c = hy_column(e.ptr, e.n_cols, i);
-        if (hy_bounds(e.ptr, c, e.cap, a, b) && i >= a && i < b) {                   // i is event i - a of column c
-            const hy_i32x2 ev = *(const hy_i32x2*)(e.pairs + 2 * (size_t)i);
+        const long long c = hy_column(e.t.ptr, e.t.n_cols, i);
+        if (hy_bounds(e.t.ptr, c, e.t.cap, a, b) && i >= a && i < b) {               // i is event i - a of column c
+            const hy_i32x2 ev = *(const hy_i32x2*)(e.t.pairs + 2 * (size_t)i);
             const long long on = ev.x, off = ev.y;
-            if (on >= off || (i + 1 < b && e.pairs[2 * (size_t)(i + 1)] < off)) atomicOr(e.err, 64);
+            if (on >= off || (i + 1 < b && e.t.pairs[2 * (size_t)(i + 1)] < off)) atomicOr(e.t.err, 64);
             if (ORDER == 0) {
-                const long long m = e.min_len[ev_param(e, c)];
+                const long long m = e.min_len[ev_param(e.span, e.NC, c)];
                 flag = m <= 0 || off - on >= m;
             } else {
-                flag = i == a || on - (long long)e.pairs[2 * (size_t)(i - 1) + 1] > (long long)e.max_gap[ev_param(e, c)];
+                flag = i == a || on - (long long)e.t.pairs[2 * (size_t)(i - 1) + 1] > (long long)e.max_gap[ev_param(e.span, e.NC, c)];
             }
         }
     }
@@ -99,40 +86,28 @@ __global__ __launch_bounds__(HY_THREADS) void k_evp_flag(EvpArgs e) {
 
 template <int ORDER>
 __global__ __launch_bounds__(HY_THREADS) void k_evp_link(EvpArgs e) {
-    __shared__ int s_cnt[HY_WAVES];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long i = (long long)blockIdx.x * HY_THREADS + tid;
+    const long long i = (long long)blockIdx.x * HY_THREADS + threadIdx.x;
     bool flag = false;
     if (ORDER == 0) {
-        if (i < e.cap && ev_bit(e.bal_a, i)) {                                       // kept: its column's bounds were valid
-            const long long c = hy_column(e.ptr, e.n_cols, i);
+        if (i < e.t.cap && ev_bit(e.bal_a, i)) {                                     // kept: its column's bounds were valid
+            const long long c = hy_column(e.t.ptr, e.t.n_cols, i);
             const long long pred = ev_last_before(e, i);
-            flag = pred < e.ptr[c] ||
-                   (long long)e.pairs[2 * (size_t)i] - (long long)e.pairs[2 * (size_t)pred + 1] > (long long)e.max_gap[ev_param(e, c)];
+            flag = pred < e.t.ptr[c] ||
+                   (long long)e.t.pairs[2 * (size_t)i] - (long long)e.t.pairs[2 * (size_t)pred + 1] >
+                       (long long)e.max_gap[ev_param(e.span, e.NC, c)];
         }
-    } else if (i < e.cap) {
+    } else if (i < e.t.cap) {
         long long a, b;
-        const long long c = hy_column(e.ptr, e.n_cols, i);
-        if (hy_bounds(e.ptr, c, e.cap, a, b) && i >= a && i < b) {
-            const long long par = ev_param(e, c), off = e.pairs[2 * (size_t)i + 1];
-            if (i + 1 == b || (long long)e.pairs[2 * (size_t)(i + 1)] - off > (long long)e.max_gap[par]) {   // a chain ends here
+        const long long c = hy_column(e.t.ptr, e.t.n_cols, i);
+        if (hy_bounds(e.t.ptr, c, e.t.cap, a, b) && i >= a && i < b) {
+            const long long par = ev_param(e.span, e.NC, c), off = e.t.pairs[2 * (size_t)i + 1];
+            if (i + 1 == b || (long long)e.t.pairs[2 * (size_t)(i + 1)] - off > (long long)e.max_gap[par]) {   // a chain ends here
                 const long long head = ev_last_before(e, i + 1), m = e.min_len[par];
-                flag = head >= a && (m <= 0 || off - (long long)e.pairs[2 * (size_t)head] >= m);
+                flag = head >= a && (m <= 0 || off - (long long)e.t.pairs[2 * (size_t)head] >= m);
             }
         }
     }
-    const uint64_t word = __ballot(flag);
-    if (lane == 0) {
-        e.bal_b[(size_t)blockIdx.x * HY_WAVES + wave] = word;
-        s_cnt[wave] = __popcll(word);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int n = 0;
-#pragma unroll
-        for (int w = 0; w < HY_WAVES; ++w) n += s_cnt[w];
-        e.cnt_b[blockIdx.x] = n;
-    }
+    ev_ballot_count(flag, e.t.bal, e.t.cnt);
 }
 
 // One workgroup, a fixed order: v[b] = the maximum (MAX; -1 for none) or the sum of v[0 .. b - 1], v[n] = that of all n.  The
@@ -173,101 +148,60 @@ __global__ __launch_bounds__(1024) void k_evp_scan(int32_t* v, long long n, long
 template <int ORDER>
 __global__ __launch_bounds__(HY_THREADS) void k_evp_write(EvpArgs e) {
     const long long i = (long long)blockIdx.x * HY_THREADS + threadIdx.x;
-    if (i < e.cap && ev_bit(e.bal_b, i)) {
-        const long long dst = hy_flagged_before(e.bal_b, e.cnt_b, e.n_blocks, i);
+    if (i < e.t.cap && ev_bit(e.t.bal, i)) {
+        const long long dst = hy_flagged_before(e.t.bal, e.t.cnt, e.t.n_blocks, i);
         if (ORDER == 0) {                                                            // a head: its onset, its predecessor's offset
-            if (dst < e.out_cap) e.out_pairs[2 * (size_t)dst] = e.pairs[2 * (size_t)i];
+            if (dst < e.t.out_cap) e.t.out_pairs[2 * (size_t)dst] = e.t.pairs[2 * (size_t)i];
             const long long pred = ev_last_before(e, i);
-            if (pred >= 0 && dst >= 1 && dst - 1 < e.out_cap && pred >= e.ptr[hy_column(e.ptr, e.n_cols, i)])
-                e.out_pairs[2 * (size_t)(dst - 1) + 1] = e.pairs[2 * (size_t)pred + 1];
-        } else if (dst < e.out_cap) {                                                // a chain's last event: the merged pair
+            if (pred >= 0 && dst >= 1 && dst - 1 < e.t.out_cap && pred >= e.t.ptr[hy_column(e.t.ptr, e.t.n_cols, i)])
+                e.t.out_pairs[2 * (size_t)(dst - 1) + 1] = e.t.pairs[2 * (size_t)pred + 1];
+        } else if (dst < e.t.out_cap) {                                              // a chain's last event: the merged pair
             const long long head = ev_last_before(e, i + 1);                         // (>= its column's start: k_evp_link saw it)
             if (head >= 0) {
-                const hy_i32x2 ev = {e.pairs[2 * (size_t)head], e.pairs[2 * (size_t)i + 1]};
-                *(hy_i32x2*)(e.out_pairs + 2 * (size_t)dst) = ev;
+                const hy_i32x2 ev = {e.t.pairs[2 * (size_t)head], e.t.pairs[2 * (size_t)i + 1]};
+                *(hy_i32x2*)(e.t.out_pairs + 2 * (size_t)dst) = ev;
             }
         }
     }
-    if (i <= e.n_cols) {
-        const long long p = e.ptr[i];
-        e.out_ptr[i] = hy_flagged_before(e.bal_b, e.cnt_b, e.n_blocks, p < 0 ? 0 : (p > e.cap ? e.cap : p));
-        long long a, b;
-        if (i < e.n_cols) {
-            if (!hy_bounds(e.ptr, i, e.cap, a, b)) {
-                atomicOr(e.err, 16);
-            } else if (ORDER == 0) {                                                 // the column's last kept event closes its last slot
-                const long long last = ev_last_before(e, b), dst = hy_flagged_before(e.bal_b, e.cnt_b, e.n_blocks, b) - 1;
-                if (last >= a && dst >= 0 && dst < e.out_cap) e.out_pairs[2 * (size_t)dst + 1] = e.pairs[2 * (size_t)last + 1];
-            }
-        }
+    long long a, b;
+    if (ev_write_ptr(e.t, i, a, b) && ORDER == 0) {                                  // the column's last kept event closes its last slot
+        const long long last = ev_last_before(e, b), dst = hy_flagged_before(e.t.bal, e.t.cnt, e.t.n_blocks, b) - 1;
+        if (last >= a && dst >= 0 && dst < e.t.out_cap) e.t.out_pairs[2 * (size_t)dst + 1] = e.t.pairs[2 * (size_t)last + 1];
     }
 }
 
-static long long evp_blocks(long long cap) { return (cap + HY_THREADS - 1) / HY_THREADS; }
-static size_t evp_bal_bytes(long long cap) { return (size_t)evp_blocks(cap) * HY_WAVES * sizeof(uint64_t); }
-
-static bool evp_sizes_ok(long long pairs_capacity, long long n_cols) {
-    return pairs_capacity >= 0 && pairs_capacity < (1ll << 31) && n_cols >= 1 && n_cols < (1ll << 26);
+int launch_ev_scan(const EvTable& t, hipStream_t st) {
+    hipLaunchKernelGGL(k_evp_scan<false>, dim3(1), dim3(1024), 0, st, t.cnt, t.n_blocks, t.out_cap, t.err);
+    SED_CHECK_LAUNCH();
+    return SED_OK;
 }
 
 extern "C" size_t sed_events_process_ws_bytes(long long pairs_capacity, long long n_cols) {
-    if (!evp_sizes_ok(pairs_capacity, n_cols)) {
-        sed_set_error("sed_events_process_ws_bytes: need 0 <= pairs_capacity < 2^31 and 1 <= n_cols < 2^26");
-        return 0;
-    }
-    return 2 * evp_bal_bytes(pairs_capacity) + 2 * (size_t)(evp_blocks(pairs_capacity) + 1) * sizeof(int32_t);
+    return ev_ws_bytes("sed_events_process", pairs_capacity, n_cols, 2);
 }
-
-#define EVP_NEED(cond, msg)                                         \
-    do {                                                            \
-        if (!(cond)) {                                              \
-            sed_set_error("sed_events_process: %s", msg);           \
-            return SED_ERR_BAD_ARG;                                 \
-        }                                                           \
-    } while (0)
 
 template <int ORDER>
 static int evp_launch(const EvpArgs& e, hipStream_t st) {
-    if (e.n_blocks) {                                                                // (an empty pairs array has nothing to flag)
-        hipLaunchKernelGGL(k_evp_flag<ORDER>, dim3((unsigned)e.n_blocks), dim3(HY_THREADS), 0, st, e);
+    if (e.t.n_blocks) {                                                              // (an empty pairs array has nothing to flag)
+        hipLaunchKernelGGL(k_evp_flag<ORDER>, dim3((unsigned)e.t.n_blocks), dim3(HY_THREADS), 0, st, e);
         SED_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(k_evp_scan<true>, dim3(1), dim3(1024), 0, st, e.last_a, e.n_blocks, e.out_cap, e.err);
+    hipLaunchKernelGGL(k_evp_scan<true>, dim3(1), dim3(1024), 0, st, e.last_a, e.t.n_blocks, e.t.out_cap, e.t.err);
     SED_CHECK_LAUNCH();
-    if (e.n_blocks) {
-        hipLaunchKernelGGL(k_evp_link<ORDER>, dim3((unsigned)e.n_blocks), dim3(HY_THREADS), 0, st, e);
-        SED_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(k_evp_scan<false>, dim3(1), dim3(1024), 0, st, e.cnt_b, e.n_blocks, e.out_cap, e.err);
-    SED_CHECK_LAUNCH();
-    const long long items = e.cap > e.n_cols + 1 ? e.cap : e.n_cols + 1;
-    hipLaunchKernelGGL(k_evp_write<ORDER>, dim3((unsigned)evp_blocks(items)), dim3(HY_THREADS), 0, st, e);
-    SED_CHECK_LAUNCH();
-    return SED_OK;
+    return ev_launch_compact(k_evp_link<ORDER>, k_evp_write<ORDER>, e, st);
 }
 
 extern "C" int sed_events_process(const int64_t* ev_ptr, const int32_t* pairs, long long pairs_capacity, long long n_cols,
                                   int n_rec, int NC, const int32_t* min_len, const int32_t* max_gap, int order,
                                   int64_t* out_ptr, int32_t* out_pairs, long long out_capacity, void* ws, size_t ws_bytes,
                                   int32_t* err, void* stream) {
-    EVP_NEED(ev_ptr && pairs && min_len && max_gap && out_ptr && out_pairs && ws && err, "null argument");
-    EVP_NEED(evp_sizes_ok(pairs_capacity, n_cols), "need 0 <= pairs_capacity < 2^31 and 1 <= n_cols < 2^26");
-    EVP_NEED(n_rec >= 1 && NC >= 1, "n_rec and NC must be >= 1");
-    EVP_NEED(n_cols % ((long long)n_rec * NC) == 0, "n_cols must be a multiple of n_rec * NC (K * n_rec * NC columns)");
-    EVP_NEED(order == 0 || order == 1, "order must be 0 (drop, then merge) or 1 (merge, then drop)");
-    EVP_NEED(out_capacity >= 0, "out_capacity must be >= 0");
-    EVP_NEED(((uintptr_t)pairs % 8) == 0 && ((uintptr_t)out_pairs % 8) == 0 && ((uintptr_t)ws % 8) == 0,
-             "pairs, out_pairs and ws must be 8-byte aligned");
-    EVP_NEED(out_pairs != pairs, "out_pairs must not be pairs (the call does not run in place)");
-    if (ws_bytes != sed_events_process_ws_bytes(pairs_capacity, n_cols)) {
-        sed_set_error("sed_events_process: ws_bytes must be the value sed_events_process_ws_bytes returned for these sizes");
-        return SED_ERR_WORKSPACE;
-    }
-    const long long n_blocks = evp_blocks(pairs_capacity);
-    const size_t bal = evp_bal_bytes(pairs_capacity);
-    char* w = (char*)ws;
-    const EvpArgs e = {ev_ptr, pairs, pairs_capacity, n_cols, (long long)n_rec * NC, NC, min_len, max_gap, out_ptr, out_pairs,
-                       out_capacity, (uint64_t*)w, (uint64_t*)(w + bal), (int32_t*)(w + 2 * bal),
-                       (int32_t*)(w + 2 * bal) + (n_blocks + 1), err, n_blocks};
+    const char* who = "sed_events_process";
+    EV_NEED(who, ev_ptr && pairs && min_len && max_gap && out_ptr && out_pairs && ws && err, "null argument");
+    EV_NEED(who, order == 0 || order == 1, "order must be 0 (drop, then merge) or 1 (merge, then drop)");
+    EvpArgs e = {{ev_ptr, pairs, pairs_capacity, n_cols, out_ptr, out_pairs, out_capacity, nullptr, nullptr, err,
+                  ev_blocks(pairs_capacity)}, (uint64_t*)ws, nullptr, (long long)n_rec * NC, NC, min_len, max_gap};
+    if (const int rc = ev_check(who, "pairs", "call", e.t, n_rec, NC, ws, ws_bytes, 2)) return rc;
+    e.last_a = (int32_t*)((char*)ws + 2 * ev_bal_bytes(pairs_capacity));             // (behind the planes A and B)
     return order == 0 ? evp_launch<0>(e, (hipStream_t)stream) : evp_launch<1>(e, (hipStream_t)stream);
 }
+

@@ -1,6 +1,6 @@
 // evscore.hip - confidence scores of decoded events and a select by score, in the event domain (the definitions are in
-// include/dcase_sed.h).  The third and fourth event-domain operators beside hyst.hip and evproc.hip, on the same flat
-// geometry (evtable.h): a thread owns one index of `pairs`.
+// include/dcase_sed.h).  The third and fourth event-domain operators beside hyst.hip and evproc.hip, on the flat geometry
+// of evtable.h: a thread owns one index of `pairs`.
 //
 // sed_events_scores   per event the maximum and the mean of the blended timeline over its frames.  ONE launch:
 //   k_evs_score   a thread finds the column of its index (hy_column / hy_bounds), from it the recording and the class,
@@ -13,9 +13,9 @@
 //                 Thread c < n_cols validates column c's bounds, thread r < n_rec recording r's (err 16).
 //   No LDS, no workspace, no atomics but the OR into err.  The timeline is read with a stride of NC floats: it is a few MB
 //   and cache-resident in the project's workloads.
-// sed_events_select   keeps the events whose score exceeds the minimum of their (point, class).  Three launches, the shape of
-//   hyst.hip: k_evs_flag (wave ballots, one count per workgroup), k_evs_scan (one workgroup), k_evs_write (the kept pairs and
-//   their scores at their rank; thread c <= n_cols writes out_ptr[c] and validates column c).
+// sed_events_select   keeps the events whose score exceeds the minimum of their (point, class).  Three launches, the
+//   compaction of evtable.h: k_evs_flag (wave ballots, one count per workgroup), the scan of evproc.hip (one workgroup),
+//   k_evs_write (the kept pairs and their scores at their rank; thread c <= n_cols writes out_ptr[c] and validates column c).
 // sed_events_tag_scores   per event the largest span tag among the spans it touches: k_evs_score<EvsTagArgs>, the same kernel
 //   over the coordinate map rows = spans (the tag gate is this score and sed_events_select with key 0).
 // Every ptr entry is validated before it is used as an index; the timeline is addressed only inside a validated recording.
@@ -128,6 +128,7 @@ __global__ __launch_bounds__(HY_THREADS) void k_evs_score(Args args) {
     }
 }
 
+
 extern "C" int sed_events_scores_short_frames(void) { return EVS_SHORT_FRAMES; }
 
 static bool evs_disjoint(const void* x, size_t nx, const void* y, size_t ny) {
@@ -135,220 +136,109 @@ static bool evs_disjoint(const void* x, size_t nx, const void* y, size_t ny) {
     return nx == 0 || ny == 0 || a + nx <= b || b + ny <= a;
 }
 
-#define EVS_NEED(who, cond, msg)                                    \
-    do {                                                            \
-        if (!(cond)) {                                              \
-            sed_set_error(who ": %s", msg);                         \
-            return SED_ERR_BAD_ARG;                                 \
-        }                                                           \
-    } while (0)
-
-static long long evs_blocks(long long n) { return (n + HY_THREADS - 1) / HY_THREADS; }
+// What sed_events_scores and sed_events_tag_scores share behind their own null checks: the other checks and the launch.
+// `who`: the entry's name, `rows`: its name for e.total, `out`: its word for an output; span3 = 0: the event scores.
+static int evs_launch(const char* who, const char* rows, const char* out, const EvsArgs& e, int span3, hipStream_t st) {
+    EV_NEED(who, e.NC >= 1 && e.NC <= 16 && e.n_rec >= 1, "need 1 <= NC <= 16 and n_rec >= 1");
+    EV_NEED(who, e.n_cols >= 1 && e.n_cols < (1ll << 26) && e.n_cols % ((long long)e.n_rec * e.NC) == 0,
+            "need 1 <= n_cols < 2^26, a multiple of n_rec * NC (K * n_rec * NC columns)");
+    EV_NEED(who, e.cap >= 0 && e.cap < (1ll << 31), "need 0 <= pairs_capacity < 2^31");
+    EV_NEED(who, e.total >= 0 && e.total * e.NC < (1ll << 31), "need 0 <= %s and %s * NC < 2^31", rows, rows);
+    EV_NEED(who, ((uintptr_t)e.pairs % 8) == 0, "ev_pairs must be 8-byte aligned");
+    const size_t out_bytes = (size_t)e.cap * sizeof(float);
+    const void* in[4] = {e.tl, e.f0, e.ptr, e.pairs};
+    const size_t in_bytes[4] = {(size_t)e.total * e.NC * sizeof(float), (size_t)(e.n_rec + 1) * sizeof(int64_t),
+                                (size_t)(e.n_cols + 1) * sizeof(int64_t), (size_t)e.cap * 2 * sizeof(int32_t)};
+    for (int k = 0; k < 4; ++k)
+        EV_NEED(who, (!e.smax || evs_disjoint(e.smax, out_bytes, in[k], in_bytes[k])) &&
+                         (!e.smean || evs_disjoint(e.smean, out_bytes, in[k], in_bytes[k])),
+                "%s output overlaps an input", out);
+    EV_NEED(who, !e.smax || !e.smean || evs_disjoint(e.smax, out_bytes, e.smean, out_bytes), "score_max overlaps score_mean");
+    if (e.cap == 0) return SED_OK;
+    const dim3 grid((unsigned)ev_blocks(e.cap > e.n_cols ? e.cap : e.n_cols));
+    const EvsTagArgs a = {e, span3};
+    if (span3) hipLaunchKernelGGL(k_evs_score<EvsTagArgs>, grid, dim3(HY_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(k_evs_score<EvsArgs>, grid, dim3(HY_THREADS), 0, st, e);
+    SED_CHECK_LAUNCH();
+    return SED_OK;
+}
 
 extern "C" int sed_events_scores(const float* timeline, long long total_frames, const int64_t* rec_frame0, int n_rec, int NC,
                                  const int64_t* ev_ptr, const int32_t* ev_pairs, long long pairs_capacity, long long n_cols,
                                  float* score_max, float* score_mean, int32_t* err, void* stream) {
-#define NEED(cond, msg) EVS_NEED("sed_events_scores", cond, msg)
-    NEED(timeline && rec_frame0 && ev_ptr && ev_pairs && err, "null argument");
-    NEED(score_max || score_mean, "score_max and score_mean are both null");
-    NEED(NC >= 1 && NC <= 16 && n_rec >= 1, "need 1 <= NC <= 16 and n_rec >= 1");
-    NEED(n_cols >= 1 && n_cols < (1ll << 26) && n_cols % ((long long)n_rec * NC) == 0,
-         "need 1 <= n_cols < 2^26, a multiple of n_rec * NC (K * n_rec * NC columns)");
-    NEED(pairs_capacity >= 0 && pairs_capacity < (1ll << 31), "need 0 <= pairs_capacity < 2^31");
-    NEED(total_frames >= 0 && total_frames * NC < (1ll << 31), "need 0 <= total_frames and total_frames * NC < 2^31");
-    NEED(((uintptr_t)ev_pairs % 8) == 0, "ev_pairs must be 8-byte aligned");
-    const size_t out_bytes = (size_t)pairs_capacity * sizeof(float);
-    const void* in[4] = {timeline, rec_frame0, ev_ptr, ev_pairs};
-    const size_t in_bytes[4] = {(size_t)total_frames * NC * sizeof(float), (size_t)(n_rec + 1) * sizeof(int64_t),
-                                (size_t)(n_cols + 1) * sizeof(int64_t), (size_t)pairs_capacity * 2 * sizeof(int32_t)};
-    for (int k = 0; k < 4; ++k)
-        NEED((!score_max || evs_disjoint(score_max, out_bytes, in[k], in_bytes[k])) &&
-                 (!score_mean || evs_disjoint(score_mean, out_bytes, in[k], in_bytes[k])),
-             "an output overlaps an input");
-    NEED(!score_max || !score_mean || evs_disjoint(score_max, out_bytes, score_mean, out_bytes), "score_max overlaps score_mean");
-#undef NEED
-    if (pairs_capacity == 0) return SED_OK;
-    const EvsArgs e = {timeline, total_frames, rec_frame0, n_rec, NC, ev_ptr, ev_pairs, pairs_capacity, n_cols,
-                       score_max, score_mean, err};
-    const long long items = pairs_capacity > n_cols ? pairs_capacity : n_cols;
-    hipLaunchKernelGGL(k_evs_score<EvsArgs>, dim3((unsigned)evs_blocks(items)), dim3(HY_THREADS), 0, (hipStream_t)stream, e);
-    SED_CHECK_LAUNCH();
-    return SED_OK;
+    const char* who = "sed_events_scores";
+    EV_NEED(who, timeline && rec_frame0 && ev_ptr && ev_pairs && err, "null argument");
+    EV_NEED(who, score_max || score_mean, "score_max and score_mean are both null");
+    return evs_launch(who, "total_frames", "an", {timeline, total_frames, rec_frame0, n_rec, NC, ev_ptr, ev_pairs, pairs_capacity,
+                                                  n_cols, score_max, score_mean, err}, 0, (hipStream_t)stream);
 }
 
 extern "C" int sed_events_tag_scores(const float* tags, long long total_spans, const int64_t* rec_span0, int span3, int n_rec,
                                      int NC, const int64_t* ev_ptr, const int32_t* ev_pairs, long long pairs_capacity,
                                      long long n_cols, float* tag_score, int32_t* err, void* stream) {
-#define NEED(cond, msg) EVS_NEED("sed_events_tag_scores", cond, msg)
-    NEED(tags && rec_span0 && ev_ptr && ev_pairs && tag_score && err, "null argument");
-    NEED(span3 >= 1, "need span3 >= 1");
-    NEED(NC >= 1 && NC <= 16 && n_rec >= 1, "need 1 <= NC <= 16 and n_rec >= 1");
-    NEED(n_cols >= 1 && n_cols < (1ll << 26) && n_cols % ((long long)n_rec * NC) == 0,
-         "need 1 <= n_cols < 2^26, a multiple of n_rec * NC (K * n_rec * NC columns)");
-    NEED(pairs_capacity >= 0 && pairs_capacity < (1ll << 31), "need 0 <= pairs_capacity < 2^31");
-    NEED(total_spans >= 0 && total_spans * NC < (1ll << 31), "need 0 <= total_spans and total_spans * NC < 2^31");
-    NEED(((uintptr_t)ev_pairs % 8) == 0, "ev_pairs must be 8-byte aligned");
-    const size_t out_bytes = (size_t)pairs_capacity * sizeof(float);
-    const void* in[4] = {tags, rec_span0, ev_ptr, ev_pairs};
-    const size_t in_bytes[4] = {(size_t)total_spans * NC * sizeof(float), (size_t)(n_rec + 1) * sizeof(int64_t),
-                                (size_t)(n_cols + 1) * sizeof(int64_t), (size_t)pairs_capacity * 2 * sizeof(int32_t)};
-    for (int k = 0; k < 4; ++k) NEED(evs_disjoint(tag_score, out_bytes, in[k], in_bytes[k]), "the output overlaps an input");
-#undef NEED
-    if (pairs_capacity == 0) return SED_OK;
-    const EvsTagArgs a = {{tags, total_spans, rec_span0, n_rec, NC, ev_ptr, ev_pairs, pairs_capacity, n_cols, tag_score, nullptr, err},
-                          span3};
-    const long long items = pairs_capacity > n_cols ? pairs_capacity : n_cols;
-    hipLaunchKernelGGL(k_evs_score<EvsTagArgs>, dim3((unsigned)evs_blocks(items)), dim3(HY_THREADS), 0, (hipStream_t)stream, a);
-    SED_CHECK_LAUNCH();
-    return SED_OK;
+    const char* who = "sed_events_tag_scores";
+    EV_NEED(who, tags && rec_span0 && ev_ptr && ev_pairs && tag_score && err, "null argument");
+    EV_NEED(who, span3 >= 1, "need span3 >= 1");
+    return evs_launch(who, "total_spans", "the", {tags, total_spans, rec_span0, n_rec, NC, ev_ptr, ev_pairs, pairs_capacity,
+                                                 n_cols, tag_score, nullptr, err}, span3, (hipStream_t)stream);
 }
 
 // ---- select by score ---------------------------------------------------------------------------------------------------
 
 struct EvsSelArgs {
-    const int64_t* ptr;
-    const int32_t* pairs;
+    EvTable t;                           // bal / cnt: the keep decisions and their counts
     const float *key, *smax, *smean;     // key: the array compared; smax / smean: what is compacted alongside (or null)
-    long long cap, n_cols;
     long long span;                      // n_rec * NC: the columns of one point
     int NC;
     const float* min_score;              // [n_cols / span][NC]
-    int64_t* out_ptr;
-    int32_t* out_pairs;
     float *out_smax, *out_smean;
-    long long out_cap;
-    uint64_t* bal;                       // ws: [n_blocks][HY_WAVES] the keep decisions of 64 indices
-    int32_t* cnt;                        // ws: [n_blocks + 1] kept per workgroup; after the scan the kept in front of it, then the total
-    int32_t* err;
-    long long n_blocks;                  // ceil(cap / HY_THREADS)
 };
 
 __global__ __launch_bounds__(HY_THREADS) void k_evs_flag(EvsSelArgs e) {
-    __shared__ int s_cnt[HY_WAVES];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long i = (long long)blockIdx.x * HY_THREADS + tid;
+    const long long i = (long long)blockIdx.x * HY_THREADS + (int)threadIdx.x;
     bool keep = false;
-    if (i < e.cap) {
+    if (i < e.t.cap) {
         long long a, b;
-        const long long c = hy_column(e.ptr, e.n_cols, i);
-        if (hy_bounds(e.ptr, c, e.cap, a, b) && i >= a && i < b)                     // (a NaN score compares false)
-            keep = e.key[i] > e.min_score[(c / e.span) * e.NC + c % e.NC];
+        const long long c = hy_column(e.t.ptr, e.t.n_cols, i);
+        if (hy_bounds(e.t.ptr, c, e.t.cap, a, b) && i >= a && i < b)                 // (a NaN score compares false)
+            keep = e.key[i] > e.min_score[ev_param(e.span, e.NC, c)];
     }
-    const uint64_t word = __ballot(keep);
-    if (lane == 0) {
-        e.bal[(size_t)blockIdx.x * HY_WAVES + wave] = word;
-        s_cnt[wave] = __popcll(word);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int n = 0;
-#pragma unroll
-        for (int w = 0; w < HY_WAVES; ++w) n += s_cnt[w];
-        e.cnt[blockIdx.x] = n;
-    }
-}
-
-// One workgroup, a fixed order: v[b] = the sum of v[0 .. b - 1], v[n] = the sum of all n (below 2^31: an index is kept at
-// most once), checked against the output capacity.
-__global__ __launch_bounds__(1024) void k_evs_scan(int32_t* v, long long n, long long out_cap, int32_t* err) {
-    __shared__ int part[16];
-    __shared__ int s_carry;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) s_carry = 0;
-    __syncthreads();
-    for (long long i0 = 0; i0 < n; i0 += 1024) {
-        const long long i = i0 + tid;
-        const int x = i < n ? v[i] : 0;
-        int incl = x;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int m = __shfl_up(incl, o);
-            if (lane >= o) incl += m;
-        }
-        if (lane == 63) part[wave] = incl;
-        __syncthreads();
-        int before = s_carry;
-        for (int k = 0; k < wave; ++k) before += part[k];
-        if (i < n) v[i] = before + incl - x;
-        __syncthreads();
-        if (tid == 1023) s_carry = before + incl;
-        __syncthreads();
-    }
-    if (tid == 0) {
-        v[n] = s_carry;
-        if (s_carry > out_cap) atomicOr(err, 2);
-    }
+    ev_ballot_count(keep, e.t.bal, e.t.cnt);
 }
 
 __global__ __launch_bounds__(HY_THREADS) void k_evs_write(EvsSelArgs e) {
     const long long i = (long long)blockIdx.x * HY_THREADS + threadIdx.x;
-    if (i < e.cap && ((e.bal[i >> 6] >> (i & 63)) & 1ull)) {
-        const long long dst = hy_flagged_before(e.bal, e.cnt, e.n_blocks, i);
-        if (dst < e.out_cap) {
-            *(hy_i32x2*)(e.out_pairs + 2 * (size_t)dst) = *(const hy_i32x2*)(e.pairs + 2 * (size_t)i);
+    if (i < e.t.cap && ev_bit(e.t.bal, i)) {
+        const long long dst = hy_flagged_before(e.t.bal, e.t.cnt, e.t.n_blocks, i);
+        if (dst < e.t.out_cap) {
+            *(hy_i32x2*)(e.t.out_pairs + 2 * (size_t)dst) = *(const hy_i32x2*)(e.t.pairs + 2 * (size_t)i);
             if (e.smax) e.out_smax[dst] = e.smax[i];
             if (e.smean) e.out_smean[dst] = e.smean[i];
         }
     }
-    if (i <= e.n_cols) {
-        const long long p = e.ptr[i];
-        e.out_ptr[i] = hy_flagged_before(e.bal, e.cnt, e.n_blocks, p < 0 ? 0 : (p > e.cap ? e.cap : p));
-        long long a, b;
-        if (i < e.n_cols && !hy_bounds(e.ptr, i, e.cap, a, b)) atomicOr(e.err, 16);
-    }
-}
-
-static size_t evs_bal_bytes(long long cap) { return (size_t)evs_blocks(cap) * HY_WAVES * sizeof(uint64_t); }
-
-static bool evs_sizes_ok(long long pairs_capacity, long long n_cols) {
-    return pairs_capacity >= 0 && pairs_capacity < (1ll << 31) && n_cols >= 1 && n_cols < (1ll << 26);
+    long long a, b;
+    ev_write_ptr(e.t, i, a, b);
 }
 
 extern "C" size_t sed_events_select_ws_bytes(long long pairs_capacity, long long n_cols) {
-    if (!evs_sizes_ok(pairs_capacity, n_cols)) {
-        sed_set_error("sed_events_select_ws_bytes: need 0 <= pairs_capacity < 2^31 and 1 <= n_cols < 2^26");
-        return 0;
-    }
-    return evs_bal_bytes(pairs_capacity) + (size_t)(evs_blocks(pairs_capacity) + 1) * sizeof(int32_t);
+    return ev_ws_bytes("sed_events_select", pairs_capacity, n_cols, 1);
 }
 
 extern "C" int sed_events_select(const int64_t* ev_ptr, const int32_t* ev_pairs, const float* score_max, const float* score_mean,
                                  long long pairs_capacity, long long n_cols, int n_rec, int NC, int key, const float* min_score,
                                  int64_t* out_ptr, int32_t* out_pairs, float* out_score_max, float* out_score_mean,
                                  long long out_capacity, void* ws, size_t ws_bytes, int32_t* err, void* stream) {
-#define NEED(cond, msg) EVS_NEED("sed_events_select", cond, msg)
-    NEED(ev_ptr && ev_pairs && min_score && out_ptr && out_pairs && ws && err, "null argument");
-    NEED(key == 0 || key == 1, "key must be 0 (score_max) or 1 (score_mean)");
-    NEED(key == 0 ? score_max != nullptr : score_mean != nullptr, "the key's score array is null");
-    NEED((score_max != nullptr) == (out_score_max != nullptr) && (score_mean != nullptr) == (out_score_mean != nullptr),
-         "a score array and its output go together or are both null");
-    NEED(evs_sizes_ok(pairs_capacity, n_cols), "need 0 <= pairs_capacity < 2^31 and 1 <= n_cols < 2^26");
-    NEED(n_rec >= 1 && NC >= 1, "n_rec and NC must be >= 1");
-    NEED(n_cols % ((long long)n_rec * NC) == 0, "n_cols must be a multiple of n_rec * NC (K * n_rec * NC columns)");
-    NEED(out_capacity >= 0, "out_capacity must be >= 0");
-    NEED(((uintptr_t)ev_pairs % 8) == 0 && ((uintptr_t)out_pairs % 8) == 0 && ((uintptr_t)ws % 8) == 0,
-         "ev_pairs, out_pairs and ws must be 8-byte aligned");
-    NEED(out_pairs != ev_pairs, "out_pairs must not be ev_pairs (the select does not run in place)");
-    NEED((!score_max || out_score_max != score_max) && (!score_mean || out_score_mean != score_mean),
-         "an out_score array must not be its input (the select does not run in place)");
-#undef NEED
-    if (ws_bytes != sed_events_select_ws_bytes(pairs_capacity, n_cols)) {
-        sed_set_error("sed_events_select: ws_bytes must be the value sed_events_select_ws_bytes returned for these sizes");
-        return SED_ERR_WORKSPACE;
-    }
-    const long long n_blocks = evs_blocks(pairs_capacity);
-    const EvsSelArgs e = {ev_ptr, ev_pairs, key == 0 ? score_max : score_mean, score_max, score_mean, pairs_capacity, n_cols,
-                          (long long)n_rec * NC, NC, min_score, out_ptr, out_pairs, out_score_max, out_score_mean, out_capacity,
-                          (uint64_t*)ws, (int32_t*)((char*)ws + evs_bal_bytes(pairs_capacity)), err, n_blocks};
-    hipStream_t st = (hipStream_t)stream;
-    if (n_blocks) {                                                                  // (an empty pairs array has nothing to flag)
-        hipLaunchKernelGGL(k_evs_flag, dim3((unsigned)n_blocks), dim3(HY_THREADS), 0, st, e);
-        SED_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(k_evs_scan, dim3(1), dim3(1024), 0, st, e.cnt, n_blocks, out_capacity, err);
-    SED_CHECK_LAUNCH();
-    const long long items = pairs_capacity > n_cols + 1 ? pairs_capacity : n_cols + 1;
-    hipLaunchKernelGGL(k_evs_write, dim3((unsigned)evs_blocks(items)), dim3(HY_THREADS), 0, st, e);
-    SED_CHECK_LAUNCH();
-    return SED_OK;
+    const char* who = "sed_events_select";
+    EV_NEED(who, ev_ptr && ev_pairs && min_score && out_ptr && out_pairs && ws && err, "null argument");
+    EV_NEED(who, key == 0 || key == 1, "key must be 0 (score_max) or 1 (score_mean)");
+    EV_NEED(who, key == 0 ? score_max != nullptr : score_mean != nullptr, "the key's score array is null");
+    EV_NEED(who, (score_max != nullptr) == (out_score_max != nullptr) && (score_mean != nullptr) == (out_score_mean != nullptr),
+            "a score array and its output go together or are both null");
+    EV_NEED(who, (!score_max || out_score_max != score_max) && (!score_mean || out_score_mean != score_mean),
+            "an out_score array must not be its input (the select does not run in place)");
+    EvsSelArgs e = {{ev_ptr, ev_pairs, pairs_capacity, n_cols, out_ptr, out_pairs, out_capacity, nullptr, nullptr, err,
+                     ev_blocks(pairs_capacity)}, key == 0 ? score_max : score_mean, score_max, score_mean, (long long)n_rec * NC,
+                    NC, min_score, out_score_max, out_score_mean};
+    if (const int rc = ev_check(who, "ev_pairs", "select", e.t, n_rec, NC, ws, ws_bytes, 1)) return rc;
+    return ev_launch_compact(k_evs_flag, k_evs_write, e, (hipStream_t)stream);
 }

@@ -277,6 +277,41 @@ def stitch_sweep(win_strong, rec_win0, rec_frame0, total_frames, hop3, threshold
                         ws_bytes, want_timeline, n_points=K)
 
 
+def _table_shape(who, ev_ptr, ev_pairs, n_rec, nclass, *beside):
+    """The checks every event-table front shares (``beside``: further tensors that have to be on the GPU).  Returns the
+    contiguous table and its sizes: ``(ev_ptr, ev_pairs, n_cols, pairs_capacity, K)``."""
+    if any(t.device.type != "cuda" for t in (ev_pairs,) + beside):
+        raise _lib.SedError(f"{who} needs GPU tensors (no CPU fallback)")
+    if (ev_ptr.dtype, ev_pairs.dtype) != (torch.int64, torch.int32) or ev_ptr.numel() < 2 or ev_pairs.dim() != 2 \
+            or ev_pairs.shape[1] != 2:
+        raise ValueError(f"{who}: ev_ptr int64 [n_cols + 1] and ev_pairs int32 [capacity, 2] expected")
+    n_cols, pairs_cap = ev_ptr.numel() - 1, ev_pairs.shape[0]
+    if n_rec < 1 or nclass < 1 or n_cols % (n_rec * nclass):
+        raise ValueError(f"{who}: {n_cols} columns are no multiple of {n_rec} recordings x {nclass} classes")
+    return ev_ptr.contiguous(), ev_pairs.contiguous(), n_cols, pairs_cap, n_cols // (n_rec * nclass)
+
+
+def _compact_call(entry, head, n_cols, pairs_cap, dev, capacity, err, beside=()):
+    """The call the compacting event-table entries share behind their own checks: the workspace size (``ValueError`` with
+    the library's text), ``out_ptr``, ``out_pairs`` and one float32 array of ``capacity`` rows per entry of ``beside`` that is
+    not None, ``err`` (a new zeroed word by default) and scratch, then ``entry(*head, the outputs, capacity, ws, its size, err,
+    stream)``.  ``capacity`` defaults to ``pairs_cap``.  Returns ``(out_ptr, out_pairs, [the row arrays], err)``."""
+    capacity = pairs_cap if capacity is None else int(capacity)
+    l = _lib.lib()
+    ws_bytes = getattr(l, entry + "_ws_bytes")(pairs_cap, n_cols)
+    if ws_bytes == 0:
+        raise ValueError(f"{entry}_ws_bytes: {l.sed_last_error().decode()}")
+    out_ptr = torch.empty(n_cols + 1, dtype=torch.int64, device=dev)
+    out_pairs = torch.empty(max(capacity, 1), 2, dtype=torch.int32, device=dev)
+    rows = [None if s is None else torch.empty(max(capacity, 1), dtype=torch.float32, device=dev) for s in beside]
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = _lib.scratch(ws_bytes, dev)
+    _lib.check(getattr(l, entry)(*head, _lib.ptr(out_ptr), _lib.ptr(out_pairs), *map(_lib.ptr, rows), capacity, _lib.ptr(ws),
+                                 ws.numel(), _lib.ptr(err), _lib.stream_ptr()), entry)
+    return out_ptr, out_pairs, rows, err
+
+
 def events_hysteresis(lo_ptr, hi_ptr, pairs, capacity=None, err=None):
     """``sed_events_hysteresis``: the events of the low table ``lo_ptr`` [n_cols + 1] that an event of the high table
     ``hi_ptr`` [n_cols + 1] confirms (some high onset inside the low event); both are int64 CSR offsets on the device into the
@@ -288,22 +323,10 @@ def events_hysteresis(lo_ptr, hi_ptr, pairs, capacity=None, err=None):
     if (lo_ptr.dtype, hi_ptr.dtype, pairs.dtype) != (torch.int64, torch.int64, torch.int32) or lo_ptr.numel() != hi_ptr.numel() \
             or lo_ptr.numel() < 2 or pairs.dim() != 2 or pairs.shape[1] != 2:
         raise ValueError("events_hysteresis: lo_ptr / hi_ptr int64 [n_cols + 1] and pairs int32 [capacity, 2] expected")
-    dev, pairs = pairs.device, pairs.contiguous()
-    lo_ptr, hi_ptr = lo_ptr.contiguous(), hi_ptr.contiguous()
+    pairs, lo_ptr, hi_ptr = pairs.contiguous(), lo_ptr.contiguous(), hi_ptr.contiguous()
     n_cols, pairs_cap = lo_ptr.numel() - 1, pairs.shape[0]
-    capacity = pairs_cap if capacity is None else int(capacity)
-    l = _lib.lib()
-    ws_bytes = l.sed_events_hysteresis_ws_bytes(pairs_cap, n_cols)
-    if ws_bytes == 0:
-        raise ValueError(f"sed_events_hysteresis_ws_bytes: {l.sed_last_error().decode()}")
-    out_ptr = torch.empty(n_cols + 1, dtype=torch.int64, device=dev)
-    out_pairs = torch.empty(max(capacity, 1), 2, dtype=torch.int32, device=dev)
-    if err is None:
-        err = torch.zeros(1, dtype=torch.int32, device=dev)
-    ws = _lib.scratch(ws_bytes, dev)
-    _lib.check(l.sed_events_hysteresis(_lib.ptr(lo_ptr), _lib.ptr(hi_ptr), _lib.ptr(pairs), pairs_cap, n_cols, _lib.ptr(out_ptr),
-                                       _lib.ptr(out_pairs), capacity, _lib.ptr(ws), ws.numel(), _lib.ptr(err), _lib.stream_ptr()),
-               "sed_events_hysteresis")
+    head = (_lib.ptr(lo_ptr), _lib.ptr(hi_ptr), _lib.ptr(pairs), pairs_cap, n_cols)
+    out_ptr, out_pairs, _, err = _compact_call("sed_events_hysteresis", head, n_cols, pairs_cap, pairs.device, capacity, err)
     return out_ptr, out_pairs, err
 
 
@@ -400,38 +423,18 @@ def events_process(ev_ptr, ev_pairs, n_rec, nclass, min_len, max_gap, order="dro
     in include/dcase_sed.h.  Returns ``(out_ptr [n_cols + 1] int64, out_pairs [capacity, 2] int32, err [1] int32)``;
     ``capacity`` defaults to ``pairs_capacity`` (the result never has more events than the input), ``err`` to a new zeroed
     word - a given one is OR-ed into.  Five launches, nothing synchronises."""
-    order = _order_code(order)
-    if ev_pairs.device.type != "cuda":
-        raise _lib.SedError("events_process needs GPU tensors (no CPU fallback)")
-    n_rec, nclass = int(n_rec), int(nclass)
-    if (ev_ptr.dtype, ev_pairs.dtype) != (torch.int64, torch.int32) or ev_ptr.numel() < 2 or ev_pairs.dim() != 2 \
-            or ev_pairs.shape[1] != 2:
-        raise ValueError("events_process: ev_ptr int64 [n_cols + 1] and ev_pairs int32 [capacity, 2] expected")
-    n_cols, pairs_cap = ev_ptr.numel() - 1, ev_pairs.shape[0]
-    if n_rec < 1 or nclass < 1 or n_cols % (n_rec * nclass):
-        raise ValueError(f"events_process: {n_cols} columns are no multiple of {n_rec} recordings x {nclass} classes")
-    K = n_cols // (n_rec * nclass)
-    dev, ev_pairs, ev_ptr = ev_pairs.device, ev_pairs.contiguous(), ev_ptr.contiguous()
-    params = []
+    order, n_rec, nclass = _order_code(order), int(n_rec), int(nclass)
+    ev_ptr, ev_pairs, n_cols, pairs_cap, K = _table_shape("events_process", ev_ptr, ev_pairs, n_rec, nclass)
+    dev, params = ev_pairs.device, []
     for name, p in (("min_len", min_len), ("max_gap", max_gap)):
         if not torch.is_tensor(p):
             p = torch.from_numpy(np.ascontiguousarray(np.asarray(p, dtype=np.int32).reshape(-1))).to(dev)
         if p.device != dev or p.dtype != torch.int32 or p.numel() != K * nclass:
             raise ValueError(f"events_process: {name} must be int32 [{K}, {nclass}] (host array or tensor on the table's device)")
         params.append(p.contiguous())
-    capacity = pairs_cap if capacity is None else int(capacity)
-    l = _lib.lib()
-    ws_bytes = l.sed_events_process_ws_bytes(pairs_cap, n_cols)
-    if ws_bytes == 0:
-        raise ValueError(f"sed_events_process_ws_bytes: {l.sed_last_error().decode()}")
-    out_ptr = torch.empty(n_cols + 1, dtype=torch.int64, device=dev)
-    out_pairs = torch.empty(max(capacity, 1), 2, dtype=torch.int32, device=dev)
-    if err is None:
-        err = torch.zeros(1, dtype=torch.int32, device=dev)
-    ws = _lib.scratch(ws_bytes, dev)
-    _lib.check(l.sed_events_process(_lib.ptr(ev_ptr), _lib.ptr(ev_pairs), pairs_cap, n_cols, n_rec, nclass, _lib.ptr(params[0]),
-                                    _lib.ptr(params[1]), order, _lib.ptr(out_ptr), _lib.ptr(out_pairs), capacity, _lib.ptr(ws),
-                                    ws.numel(), _lib.ptr(err), _lib.stream_ptr()), "sed_events_process")
+    head = (_lib.ptr(ev_ptr), _lib.ptr(ev_pairs), pairs_cap, n_cols, n_rec, nclass, _lib.ptr(params[0]), _lib.ptr(params[1]),
+            order)
+    out_ptr, out_pairs, _, err = _compact_call("sed_events_process", head, n_cols, pairs_cap, dev, capacity, err)
     return out_ptr, out_pairs, err
 
 
@@ -451,15 +454,25 @@ def _score_key_code(key):
     return SCORE_KEYS[key]
 
 
-def _table_shape(who, ev_ptr, ev_pairs, n_rec, nclass):
-    """The checks every event-table front shares: ``(n_cols, pairs_capacity, K)``."""
-    if (ev_ptr.dtype, ev_pairs.dtype) != (torch.int64, torch.int32) or ev_ptr.numel() < 2 or ev_pairs.dim() != 2 \
-            or ev_pairs.shape[1] != 2:
-        raise ValueError(f"{who}: ev_ptr int64 [n_cols + 1] and ev_pairs int32 [capacity, 2] expected")
-    n_cols, pairs_cap = ev_ptr.numel() - 1, ev_pairs.shape[0]
-    if n_rec < 1 or nclass < 1 or n_cols % (n_rec * nclass):
-        raise ValueError(f"{who}: {n_cols} columns are no multiple of {n_rec} recordings x {nclass} classes")
-    return n_cols, pairs_cap, n_cols // (n_rec * nclass)
+def _scores_call(who, out_or_table, rows, rec0, n_rec, nclass, wanted, err, expected, extra=()):
+    """What ``events_scores`` and ``events_tag_scores`` share: the table from the dict of a stitch entry or a pair, its checks
+    and those of ``rows`` [*, nclass] float32, ``rec0`` [n_rec + 1] int64 and ``extra``, the ints >= 1 the entry takes in front
+    of ``n_rec`` (``ValueError`` with ``expected``), one float32 [pairs_capacity] output per true entry of ``wanted``, ``err``,
+    and the call ``sed_<who>``.  Returns ``([the outputs or None], err)``."""
+    ev_ptr, ev_pairs = (out_or_table["ev_ptr"], out_or_table["ev_pairs"]) if isinstance(out_or_table, dict) else out_or_table
+    n_rec, nclass = int(n_rec), int(nclass)
+    ev_ptr, ev_pairs, n_cols, pairs_cap, _ = _table_shape(who, ev_ptr, ev_pairs, n_rec, nclass, rows)
+    if rows.dtype != torch.float32 or rows.numel() % nclass or rec0.dtype != torch.int64 or rec0.numel() != n_rec + 1 \
+            or any(x < 1 for x in extra):
+        raise ValueError(f"{who}: {expected.format(nclass=nclass, n_rec1=n_rec + 1)}")
+    rows, rec0 = rows.contiguous(), rec0.contiguous()
+    outs = [torch.empty(pairs_cap, dtype=torch.float32, device=ev_pairs.device) if w else None for w in wanted]
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=ev_pairs.device)
+    _lib.check(getattr(_lib.lib(), "sed_" + who)(_lib.ptr(rows), rows.numel() // nclass, _lib.ptr(rec0), *extra, n_rec, nclass,
+                                                 _lib.ptr(ev_ptr), _lib.ptr(ev_pairs), pairs_cap, n_cols, *map(_lib.ptr, outs),
+                                                 _lib.ptr(err), _lib.stream_ptr()), "sed_" + who)
+    return outs, err
 
 
 def events_scores(out_or_table, timeline, rec_frame0, n_rec, nclass, want=("max", "mean"), err=None):
@@ -471,26 +484,12 @@ def events_scores(out_or_table, timeline, rec_frame0, n_rec, nclass, want=("max"
     Returns ``(score_max, score_mean, err)``: float32 [pairs_capacity] device tensors indexed like ``ev_pairs`` (an unwanted
     one is None; entries at and beyond ``ev_ptr[-1]`` are not written), ``err`` [1] int32 - a new zeroed word by default, a
     given one is OR-ed into (``STITCH_ERR_BITS``).  One launch, nothing synchronises."""
-    ev_ptr, ev_pairs = (out_or_table["ev_ptr"], out_or_table["ev_pairs"]) if isinstance(out_or_table, dict) else out_or_table
     want = (want,) if isinstance(want, str) else tuple(want)
     if not want or any(w not in SCORE_KEYS for w in want):
         raise ValueError(f"want must name one or both of {sorted(SCORE_KEYS)}, got {want!r}")
-    if ev_pairs.device.type != "cuda" or timeline.device.type != "cuda":
-        raise _lib.SedError("events_scores needs GPU tensors (no CPU fallback)")
-    n_rec, nclass = int(n_rec), int(nclass)
-    n_cols, pairs_cap, _ = _table_shape("events_scores", ev_ptr, ev_pairs, n_rec, nclass)
-    if timeline.dtype != torch.float32 or timeline.numel() % nclass or rec_frame0.dtype != torch.int64 \
-            or rec_frame0.numel() != n_rec + 1:
-        raise ValueError(f"events_scores: timeline float32 [total_frames, {nclass}] and rec_frame0 int64 [{n_rec + 1}] expected")
-    dev, ev_pairs, ev_ptr = ev_pairs.device, ev_pairs.contiguous(), ev_ptr.contiguous()
-    timeline, rec_frame0 = timeline.contiguous(), rec_frame0.contiguous()
-    score_max = torch.empty(pairs_cap, dtype=torch.float32, device=dev) if "max" in want else None
-    score_mean = torch.empty(pairs_cap, dtype=torch.float32, device=dev) if "mean" in want else None
-    if err is None:
-        err = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().sed_events_scores(_lib.ptr(timeline), timeline.numel() // nclass, _lib.ptr(rec_frame0), n_rec, nclass,
-                                            _lib.ptr(ev_ptr), _lib.ptr(ev_pairs), pairs_cap, n_cols, _lib.ptr(score_max),
-                                            _lib.ptr(score_mean), _lib.ptr(err), _lib.stream_ptr()), "sed_events_scores")
+    (score_max, score_mean), err = _scores_call("events_scores", out_or_table, timeline, rec_frame0, n_rec, nclass,
+                                                ("max" in want, "mean" in want), err,
+                                                "timeline float32 [total_frames, {nclass}] and rec_frame0 int64 [{n_rec1}] expected")
     return score_max, score_mean, err
 
 
@@ -502,12 +501,9 @@ def events_select(ev_ptr, ev_pairs, score_max, score_mean, n_rec, nclass, min_sc
     err [1] int32)``: the kept events in order with their scores compacted alongside (None where the input was None);
     ``capacity`` defaults to the input's (it cannot overflow), ``err`` to a new zeroed word - a given one is OR-ed into.
     Three launches, nothing synchronises."""
-    key = _score_key_code(key)
-    if ev_pairs.device.type != "cuda":
-        raise _lib.SedError("events_select needs GPU tensors (no CPU fallback)")
-    n_rec, nclass = int(n_rec), int(nclass)
-    n_cols, pairs_cap, K = _table_shape("events_select", ev_ptr, ev_pairs, n_rec, nclass)
-    dev, ev_pairs, ev_ptr = ev_pairs.device, ev_pairs.contiguous(), ev_ptr.contiguous()
+    key, n_rec, nclass = _score_key_code(key), int(n_rec), int(nclass)
+    ev_ptr, ev_pairs, n_cols, pairs_cap, K = _table_shape("events_select", ev_ptr, ev_pairs, n_rec, nclass)
+    dev = ev_pairs.device
     if (score_max, score_mean)[key] is None:
         raise ValueError(f"events_select: key {('max', 'mean')[key]!r} needs that score array")
     scores = []
@@ -523,21 +519,9 @@ def events_select(ev_ptr, ev_pairs, score_max, score_mean, n_rec, nclass, min_sc
         raise ValueError(f"events_select: min_score must be a scalar, {nclass} values or float32 [{K}, {nclass}] "
                          "(host array or tensor on the table's device)")
     min_score = min_score.contiguous()
-    capacity = pairs_cap if capacity is None else int(capacity)
-    l = _lib.lib()
-    ws_bytes = l.sed_events_select_ws_bytes(pairs_cap, n_cols)
-    if ws_bytes == 0:
-        raise ValueError(f"sed_events_select_ws_bytes: {l.sed_last_error().decode()}")
-    out_ptr = torch.empty(n_cols + 1, dtype=torch.int64, device=dev)
-    out_pairs = torch.empty(max(capacity, 1), 2, dtype=torch.int32, device=dev)
-    outs = [None if s is None else torch.empty(max(capacity, 1), dtype=torch.float32, device=dev) for s in scores]
-    if err is None:
-        err = torch.zeros(1, dtype=torch.int32, device=dev)
-    ws = _lib.scratch(ws_bytes, dev)
-    _lib.check(l.sed_events_select(_lib.ptr(ev_ptr), _lib.ptr(ev_pairs), _lib.ptr(scores[0]), _lib.ptr(scores[1]), pairs_cap, n_cols,
-                                   n_rec, nclass, key, _lib.ptr(min_score), _lib.ptr(out_ptr), _lib.ptr(out_pairs),
-                                   _lib.ptr(outs[0]), _lib.ptr(outs[1]), capacity, _lib.ptr(ws), ws.numel(), _lib.ptr(err),
-                                   _lib.stream_ptr()), "sed_events_select")
+    head = (_lib.ptr(ev_ptr), _lib.ptr(ev_pairs), _lib.ptr(scores[0]), _lib.ptr(scores[1]), pairs_cap, n_cols, n_rec, nclass, key,
+            _lib.ptr(min_score))
+    out_ptr, out_pairs, outs, err = _compact_call("sed_events_select", head, n_cols, pairs_cap, dev, capacity, err, scores)
     return out_ptr, out_pairs, outs[0], outs[1], err
 
 
@@ -732,23 +716,9 @@ def events_tag_scores(out_or_table, tags, rec_span0, span3, n_rec, nclass, err=N
     touches (``tags`` [total_spans, nclass] cuda float32 and ``rec_span0`` [n_rec + 1] int64 as ``stitch_span_tags`` returns
     them, ``span3`` the clamped span length it used).  ``out_or_table`` as for ``events_scores``.  Returns ``(tag_score
     float32 [pairs_capacity], err [1] int32)``; a given ``err`` is OR-ed into.  One launch, nothing synchronises."""
-    ev_ptr, ev_pairs = (out_or_table["ev_ptr"], out_or_table["ev_pairs"]) if isinstance(out_or_table, dict) else out_or_table
-    if ev_pairs.device.type != "cuda" or tags.device.type != "cuda":
-        raise _lib.SedError("events_tag_scores needs GPU tensors (no CPU fallback)")
-    n_rec, nclass, span3 = int(n_rec), int(nclass), int(span3)
-    n_cols, pairs_cap, _ = _table_shape("events_tag_scores", ev_ptr, ev_pairs, n_rec, nclass)
-    if tags.dtype != torch.float32 or tags.numel() % nclass or rec_span0.dtype != torch.int64 or rec_span0.numel() != n_rec + 1 \
-            or span3 < 1:
-        raise ValueError(f"events_tag_scores: tags float32 [total_spans, {nclass}], rec_span0 int64 [{n_rec + 1}] and "
-                         "span3 >= 1 expected")
-    dev, ev_pairs, ev_ptr = ev_pairs.device, ev_pairs.contiguous(), ev_ptr.contiguous()
-    tags, rec_span0 = tags.contiguous(), rec_span0.contiguous()
-    tag_score = torch.empty(pairs_cap, dtype=torch.float32, device=dev)
-    if err is None:
-        err = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().sed_events_tag_scores(_lib.ptr(tags), tags.numel() // nclass, _lib.ptr(rec_span0), span3, n_rec, nclass,
-                                                _lib.ptr(ev_ptr), _lib.ptr(ev_pairs), pairs_cap, n_cols, _lib.ptr(tag_score),
-                                                _lib.ptr(err), _lib.stream_ptr()), "sed_events_tag_scores")
+    (tag_score,), err = _scores_call("events_tag_scores", out_or_table, tags, rec_span0, n_rec, nclass, (True,), err,
+                                     "tags float32 [total_spans, {nclass}], rec_span0 int64 [{n_rec1}] and span3 >= 1 expected",
+                                     extra=(int(span3),))
     return tag_score, err
 
 
