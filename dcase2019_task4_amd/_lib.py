@@ -71,6 +71,8 @@ _SIGS = {
     "sed_events_select_ws_bytes": (C.c_size_t, [C.c_longlong, C.c_longlong]),
     "sed_events_select": (C.c_int, [_P, _P, _P, _P, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P,
                                     C.c_longlong, _P, C.c_size_t, _P, _P]),
+    "sed_events_rasterize": (C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, _P, _P, C.c_int, C.c_int, _P, C.c_longlong, _P, C.c_int, _P,
+                                       _P]),
     "sed_stitch_weak_ws_bytes": (C.c_size_t, [C.c_longlong, C.c_int, C.c_int]),
     "sed_stitch_weak": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P, _P]),
     "sed_stitch_weak_backward": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),

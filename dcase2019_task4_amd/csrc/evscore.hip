@@ -131,11 +131,6 @@ __global__ __launch_bounds__(HY_THREADS) void k_evs_score(Args args) {
 
 extern "C" int sed_events_scores_short_frames(void) { return EVS_SHORT_FRAMES; }
 
-static bool evs_disjoint(const void* x, size_t nx, const void* y, size_t ny) {
-    const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y;
-    return nx == 0 || ny == 0 || a + nx <= b || b + ny <= a;
-}
-
 // What sed_events_scores and sed_events_tag_scores share behind their own null checks: the other checks and the launch.
 // `who`: the entry's name, `rows`: its name for e.total, `out`: its word for an output; span3 = 0: the event scores.
 static int evs_launch(const char* who, const char* rows, const char* out, const EvsArgs& e, int span3, hipStream_t st) {
@@ -150,10 +145,10 @@ static int evs_launch(const char* who, const char* rows, const char* out, const 
     const size_t in_bytes[4] = {(size_t)e.total * e.NC * sizeof(float), (size_t)(e.n_rec + 1) * sizeof(int64_t),
                                 (size_t)(e.n_cols + 1) * sizeof(int64_t), (size_t)e.cap * 2 * sizeof(int32_t)};
     for (int k = 0; k < 4; ++k)
-        EV_NEED(who, (!e.smax || evs_disjoint(e.smax, out_bytes, in[k], in_bytes[k])) &&
-                         (!e.smean || evs_disjoint(e.smean, out_bytes, in[k], in_bytes[k])),
+        EV_NEED(who, (!e.smax || ev_disjoint(e.smax, out_bytes, in[k], in_bytes[k])) &&
+                         (!e.smean || ev_disjoint(e.smean, out_bytes, in[k], in_bytes[k])),
                 "%s output overlaps an input", out);
-    EV_NEED(who, !e.smax || !e.smean || evs_disjoint(e.smax, out_bytes, e.smean, out_bytes), "score_max overlaps score_mean");
+    EV_NEED(who, !e.smax || !e.smean || ev_disjoint(e.smax, out_bytes, e.smean, out_bytes), "score_max overlaps score_mean");
     if (e.cap == 0) return SED_OK;
     const dim3 grid((unsigned)ev_blocks(e.cap > e.n_cols ? e.cap : e.n_cols));
     const EvsTagArgs a = {e, span3};

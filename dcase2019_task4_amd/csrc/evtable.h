@@ -1,4 +1,4 @@
-// evtable.h - what an event-domain operator needs of a CSR event table, stated once for evproc.hip and evscore.hip: the
+// evtable.h - what an event-domain operator needs of a CSR event table, stated once for evproc.hip, evscore.hip and raster.hip: the
 // geometry of a flat pass over the indices of its pairs array, the column lookup, the validation of a column's bounds, the
 // rank of an index among the flagged ones, and the compaction built from them.  A flat pass gives every index of pairs one
 // thread; a wave's decisions are one ballot word, a workgroup's count is the popcounts of its four words, a one-workgroup
@@ -111,6 +111,12 @@ static size_t ev_ws_bytes(const char* who, long long pairs_capacity, long long n
         return 0;
     }
     return planes * (ev_bal_bytes(pairs_capacity) + ev_cnt_bytes(pairs_capacity));
+}
+
+// The byte ranges [x, x + nx) and [y, y + ny) share nothing (an empty range shares nothing with anything).
+static bool ev_disjoint(const void* x, size_t nx, const void* y, size_t ny) {
+    const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y;
+    return nx == 0 || ny == 0 || a + nx <= b || b + ny <= a;
 }
 
 #define EV_NEED(who, cond, fmt, ...)                                \

@@ -27,6 +27,10 @@ Span-level weak tags and the tag gate: ``stitch_span_tags`` / ``get_long_predict
 of time (``sed_stitch_span_tags``, ``span_table``, ``span_tags_dataframe``), ``events_tag_scores`` gives every event the largest
 tag of the spans it touches (``sed_events_tag_scores``) and ``gate_decoded`` / ``get_long_predictions(min_span_tag=...)`` keep
 the events that touch a confident span (``events_select`` on that score).
+Pseudo strong labels: ``events_rasterize`` / ``rasterize_decoded`` turn any of these tables back into label rows
+(``sed_events_rasterize``), ``WindowedFeatureSet.relabel`` / ``ResidentFeatureSet.relabel`` write them in place into a training
+set's label pool, and ``pseudo_label`` runs the whole chain of ``get_long_predictions`` and ends in the pool instead of a
+DataFrame.
 ``get_predictions`` itself is unchanged.
 """
 import ctypes as C
@@ -738,6 +742,115 @@ def gate_decoded(out, span_tags, n_rec, nclass, min_tag):
     return dict(out, ev_ptr=ev_ptr, ev_pairs=ev_pairs, tag_score=tag_score, err=err)
 
 
+RASTER_COMBINES = {"replace": 0, "max": 1}
+RASTER_ERR_BITS = {8: "a class whose operating point lies outside the table's points",
+                   16: "malformed ev_ptr / rec_frame0 tables or destination rows outside the pool",
+                   64: "events that are not sorted and disjoint inside their recording"}
+
+
+def _combine_code(combine):
+    if combine not in RASTER_COMBINES:
+        raise ValueError(f"combine must be one of {sorted(RASTER_COMBINES)}, got {combine!r}")
+    return RASTER_COMBINES[combine]
+
+
+def rows_overlap(row0, n_rows):
+    """True when two of the row ranges ``[row0[r], row0[r] + n_rows[r])`` share a row (empty ranges share nothing)."""
+    row0, n_rows = np.asarray(row0, dtype=np.int64).reshape(-1), np.asarray(n_rows, dtype=np.int64).reshape(-1)
+    keep = n_rows > 0
+    row0, n_rows = row0[keep], n_rows[keep]
+    order = np.argsort(row0, kind="stable")
+    return bool((row0[order][1:] < (row0 + n_rows)[order][:-1]).any())
+
+
+def events_rasterize(out_or_table, rec_frame0, n_rec, nclass, dst=None, dst_row0=None, values=None, point=None,
+                     combine="replace", err=None, rec_frame0_host=None):
+    """``sed_events_rasterize``: a CSR event table on the device turned into label rows [*, nclass] float32, in place in
+    ``dst`` - the definition is in include/dcase_sed.h.  ``out_or_table``: the dict a stitch entry returned or a pair
+    ``(ev_ptr, ev_pairs)``, ``ev_ptr`` [K * n_rec * nclass + 1] int64 in the sweep's column order; ``rec_frame0`` [n_rec + 1]
+    int64 on the device.  ``dst``: a contiguous cuda float32 tensor of ``dst_rows * nclass`` elements (a label pool); None
+    allocates ``[total_frames, nclass]`` (the rows of the dict's timeline where it has one, else one host read of
+    ``rec_frame0[-1]``).  ``dst_row0`` [n_rec]: the first ``dst`` row of every recording - a host sequence or a device int64
+    tensor; None: ``rec_frame0`` itself, a contiguous timeline.  ``values`` [pairs_capacity] float32 on the device: the value
+    of every event (``score_max`` / ``score_mean`` of ``events_scores`` for soft labels), None: 1.0.  ``point``: the operating
+    point each class is taken from - None (point 0), an int, one int per class, or a device int32 tensor [nclass].
+    ``combine``: ``"replace"`` (covered elements take the value, the recordings' other elements +0.0) or ``"max"`` (covered
+    elements take the larger of value and old content, the others stay); anything else raises ``ValueError``.  Recordings
+    whose destination rows overlap are refused (``ValueError``) when ``dst_row0`` is a host sequence and ``rec_frame0_host``
+    is given; with device tables that is the caller's responsibility.  Returns ``(dst, err)``: ``err`` [1] int32 - a new zeroed
+    word by default, a given one is OR-ed into (``RASTER_ERR_BITS``; non-zero: ``dst`` is invalid).  Two launches, nothing
+    synchronises."""
+    combine, n_rec, nclass = _combine_code(combine), int(n_rec), int(nclass)
+    timeline = out_or_table.get("timeline") if isinstance(out_or_table, dict) else None
+    ev_ptr, ev_pairs = (out_or_table["ev_ptr"], out_or_table["ev_pairs"]) if isinstance(out_or_table, dict) else out_or_table
+    ev_ptr, ev_pairs, n_cols, pairs_cap, K = _table_shape("events_rasterize", ev_ptr, ev_pairs, n_rec, nclass, rec_frame0)
+    dev = ev_pairs.device
+    if rec_frame0.dtype != torch.int64 or rec_frame0.numel() != n_rec + 1:
+        raise ValueError(f"events_rasterize: rec_frame0 int64 [{n_rec + 1}] expected")
+    rec_frame0 = rec_frame0.contiguous()
+    if values is not None and (not torch.is_tensor(values) or values.device != dev or values.dtype != torch.float32
+                               or values.numel() != pairs_cap):
+        raise ValueError(f"events_rasterize: values must be float32 [{pairs_cap}] on the table's device")
+    values = None if values is None else values.contiguous()
+    if point is not None and not torch.is_tensor(point):
+        pts = _per_class(point, nclass, np.int64, "point")
+        if (pts < 0).any() or (pts >= K).any():
+            raise ValueError(f"events_rasterize: point must lie in [0, {K}), got {pts.tolist()}")
+        point = torch.from_numpy(pts.astype(np.int32)).to(dev)
+    if point is not None and (point.device != dev or point.dtype != torch.int32 or point.numel() != nclass):
+        raise ValueError(f"events_rasterize: point must be int32 [{nclass}] (host values or a tensor on the table's device)")
+    point = None if point is None else point.contiguous()
+    if dst is None:
+        total = timeline.shape[0] if timeline is not None else int(rec_frame0[-1].item())
+        dst = torch.empty(total, nclass, dtype=torch.float32, device=dev)
+    if not torch.is_tensor(dst) or dst.device != dev or dst.dtype != torch.float32 or not dst.is_contiguous() \
+            or dst.numel() % nclass:
+        raise ValueError(f"events_rasterize: dst must be a contiguous float32 tensor of rows x {nclass} on the table's device")
+    dst_rows = dst.numel() // nclass
+    if dst_row0 is not None and not torch.is_tensor(dst_row0):
+        row0 = np.asarray(dst_row0, dtype=np.int64).reshape(-1)
+        if row0.size != n_rec:
+            raise ValueError(f"events_rasterize: dst_row0 must hold {n_rec} rows, got {row0.size}")
+        if rec_frame0_host is not None:
+            L3 = np.diff(np.asarray(rec_frame0_host, dtype=np.int64).reshape(-1))
+            if L3.size != n_rec:
+                raise ValueError(f"events_rasterize: rec_frame0_host must hold {n_rec + 1} entries")
+            if (row0 < 0).any() or (row0 + L3 > dst_rows).any():
+                raise ValueError(f"events_rasterize: a recording's rows reach outside the {dst_rows} rows of dst")
+            if rows_overlap(row0, L3):
+                raise ValueError("events_rasterize: two recordings' destination rows overlap")
+        dst_row0 = torch.from_numpy(np.ascontiguousarray(row0)).to(dev)
+    if dst_row0 is not None and (dst_row0.device != dev or dst_row0.dtype != torch.int64 or dst_row0.numel() != n_rec):
+        raise ValueError(f"events_rasterize: dst_row0 must be int64 [{n_rec}] (host values or a tensor on the table's device)")
+    dst_row0 = None if dst_row0 is None else dst_row0.contiguous()
+    if err is None:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().sed_events_rasterize(_lib.ptr(ev_ptr), _lib.ptr(ev_pairs), _lib.ptr(values), pairs_cap, K,
+                                               _lib.ptr(point), _lib.ptr(rec_frame0), n_rec, nclass, _lib.ptr(dst), dst_rows,
+                                               _lib.ptr(dst_row0), combine, _lib.ptr(err), _lib.stream_ptr()),
+               "sed_events_rasterize")
+    return dst, err
+
+
+def rasterize_decoded(out, rec_frame0, n_rec, nclass, soft=None, point=None):
+    """``events_rasterize`` on the dict a stitch entry, ``process_decoded``, ``select_decoded`` or ``gate_decoded`` returned:
+    the same dict plus ``labels`` [total_frames, nclass] float32, the table as a contiguous label timeline (hard 0 / 1 labels;
+    ``soft="max"`` / ``"mean"``: every event carries that score of the dict's ``timeline`` - ``events_scores`` on the table
+    as it is now; ``ValueError`` without a timeline).  ``point`` as for ``events_rasterize``.  Its ``err`` is the dict's own
+    word with the bits of both steps OR-ed in on the device."""
+    values, err = None, out["err"]
+    if soft is not None:
+        _score_key_code(soft)
+        if out.get("timeline") is None:
+            raise ValueError("rasterize_decoded(soft=...) needs the blended timeline: decode with want_timeline=True")
+        score_max, score_mean, err = events_scores(out, out["timeline"], rec_frame0, n_rec, nclass, (soft,), err=err)
+        values = score_max if soft == "max" else score_mean
+    total = next((out[k].shape[0] for k in ("timeline", "binary") if out.get(k) is not None), None)
+    dst = None if total is None else torch.empty(total, int(nclass), dtype=torch.float32, device=out["ev_pairs"].device)
+    labels, err = events_rasterize(out, rec_frame0, n_rec, nclass, dst=dst, values=values, point=point, err=err)
+    return dict(out, labels=labels, err=err)
+
+
 def span_tags_dataframe(tags, rec_span0, span3, filenames, labels, threshold=0.5, frame_seconds=None, L3s=None):
     """The span-level twin of ``weak_tags_dataframe``: one row per (recording, span) with ``filename``, ``onset``, ``offset``
     (seconds: span s of a recording covers the label frames ``s * span3 .. (s + 1) * span3`` of ``frame_seconds`` each -
@@ -806,7 +919,7 @@ def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=
                          cfg=None, threshold=0.5, median_window=None, weighting="taper", return_posteriors=False,
                          return_weak=False, threshold_high=None, min_event_length=None, min_event_gap=None,
                          process_order="drop_merge", event_scores=False, min_event_score=None, score_key="max", tag_span=None,
-                         min_span_tag=None, return_span_tags=False):
+                         min_span_tag=None, return_span_tags=False, return_table=False):
     """Events of recordings of any lengths (a ``LongRecordingSet``): the windows go through the eval-mode model
     ``batch_size`` at a time, their strong posteriors are blended into one timeline per recording (``weighting``: "taper"
     or "uniform"), and ONE threshold, median filter and run-length decode runs over each whole timeline
@@ -836,8 +949,65 @@ def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=
     only when it touches a span whose tag exceeds it (``gate_decoded``), right after the decode (after the two-threshold
     select), BEFORE ``events_process`` and the event scores: mask, then post-process.  ``return_span_tags=True`` appends
     ``(tags [total_spans, nclass] device tensor, rec_span0 host, span3)`` to what is returned (``span_tags_dataframe`` makes
-    their table).  ``min_span_tag`` or ``return_span_tags`` without ``tag_span``: ``ValueError`` before any forward.  With the
-    defaults nothing new is launched and the frame is column for column the same."""
+    their table).  ``min_span_tag`` or ``return_span_tags`` without ``tag_span``: ``ValueError`` before any forward.
+    ``return_table=True`` appends the device dict of the FINAL table to what is returned: ``ev_ptr``, ``ev_pairs``,
+    ``timeline`` (or None when nothing asked for it) and, when scored, ``score_max`` / ``score_mean`` indexed like
+    ``ev_pairs`` - what ``events_rasterize`` and ``relabel`` take.  With the defaults nothing new is launched and the frame is
+    column for column the same."""
+    if not isinstance(return_table, (bool, np.bool_)):
+        raise ValueError(f"return_table must be True or False, got {return_table!r}")
+    s = _long_events(model, long_set, decoder_or_labels, pooling_time_ratio, batch_size, cfg, threshold, median_window, weighting,
+                     return_posteriors, return_weak, threshold_high, min_event_length, min_event_gap, process_order, event_scores,
+                     min_event_score, score_key, tag_span, min_span_tag, return_span_tags)
+    labels, pool, cfg, NC, out, scored = s["labels"], s["pool"], s["cfg"], s["NC"], s["out"], s["scored"]
+    ev_ptr = out["ev_ptr"].cpu().numpy()
+    ev = out["ev_pairs"][:int(ev_ptr[-1])].cpu().numpy()
+    per_col = np.diff(ev_ptr)
+    col = np.repeat(np.arange(per_col.size), per_col)
+    rec, cls = col // NC, col % NC
+    per_rec = per_col.reshape(long_set.n_rec, NC).sum(1)
+    index = np.arange(len(col)) - np.repeat(np.r_[0, np.cumsum(per_rec)[:-1]], per_rec)     # 0 .. k - 1 per recording
+    prediction_df = pd.DataFrame({"event_label": np.asarray(labels, dtype=object)[cls],
+                                  "onset": ev[:, 0].astype(np.int64), "offset": ev[:, 1].astype(np.int64),
+                                  "filename": np.asarray(long_set.filenames, dtype=object)[rec]}, index=index,
+                                 columns=["event_label", "onset", "offset", "filename"])
+    prediction_df.onset = prediction_df.onset * pool / (cfg.sample_rate / cfg.hop_length)
+    prediction_df.offset = prediction_df.offset * pool / (cfg.sample_rate / cfg.hop_length)
+    if scored:
+        prediction_df["score_max"] = s["score_max"][:len(ev)].cpu().numpy()
+        prediction_df["score_mean"] = s["score_mean"][:len(ev)].cpu().numpy()
+    if save_predictions is not None:
+        prediction_df.to_csv(save_predictions, index=False, sep="\t")
+    result = (prediction_df,)
+    if return_posteriors:
+        f0 = long_set.rec_frame0_host
+        result += ([out["timeline"][int(f0[r]):int(f0[r + 1])] for r in range(long_set.n_rec)], s["win_strong"])
+    if return_weak:
+        result += (s["weak"],)
+    if return_span_tags:
+        span_tags = s["span_tags"]
+        result += ((span_tags["tags"], span_tags["rec_span0_host"], span_tags["span3"]),)
+    if return_table:
+        result += (_final_table(s),)
+    return result if len(result) > 1 else prediction_df
+
+
+def _final_table(s):
+    """The device dict of the final table of one ``_long_events`` chain (``get_long_predictions(return_table=True)``)."""
+    table = {"ev_ptr": s["out"]["ev_ptr"], "ev_pairs": s["out"]["ev_pairs"], "timeline": s["out"]["timeline"]}
+    if s["scored"]:
+        table.update(score_max=s["score_max"], score_mean=s["score_mean"])
+    return table
+
+
+def _long_events(model, long_set, decoder_or_labels, pooling_time_ratio, batch_size, cfg, threshold, median_window, weighting,
+                 return_posteriors, return_weak, threshold_high, min_event_length, min_event_gap, process_order, event_scores,
+                 min_event_score, score_key, tag_span, min_span_tag, return_span_tags, known_tags=None):
+    """The device chain ``get_long_predictions`` and ``pseudo_label`` share (the arguments are the former's): the checks, the
+    forwards, the decode, the gate, ``events_process``, the scores and the select, and ONE check of every error word.
+    ``known_tags`` [n_rec, nclass] (``pseudo_label``): the gate runs on these tags with one span per recording and a minimum of
+    0.5 in the place of pooled span tags.  Returns a dict: ``out`` (the final table's dict), ``scored``, ``score_max`` /
+    ``score_mean``, ``win_strong``, ``weak``, ``span_tags``, ``labels``, ``pool``, ``cfg``, ``NC``."""
     if tag_span is None and (min_span_tag is not None or return_span_tags):
         raise ValueError("min_span_tag / return_span_tags need tag_span: the length of a span in seconds")
     if tag_span is not None and not float(tag_span) > 0:
@@ -885,6 +1055,12 @@ def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=
             min_tag = _per_class(min_span_tag, NC, np.float32, "min_span_tag").reshape(1, NC)
             if np.isnan(min_tag).any():
                 raise ValueError("min_span_tag: NaN keeps no event; pass None to keep all")
+    if known_tags is not None:
+        if min_span_tag is not None:
+            raise ValueError("known_tags and min_span_tag are two gates: pass one of them")
+        known = known_tags.detach().cpu().numpy() if torch.is_tensor(known_tags) else np.asarray(known_tags)
+        if known.shape != (long_set.n_rec, NC) or not np.isin(known, (0, 1)).all():
+            raise ValueError(f"known_tags must be [{long_set.n_rec}, {NC}] of 0 / 1, got shape {known.shape}")
     want_timeline = return_posteriors or scored
     want_att = return_weak or tag_span is not None
     win_strong = long_window_posteriors(model, long_set, NC, batch_size, want_attention=want_att)
@@ -904,6 +1080,12 @@ def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=
         if min_span_tag is not None:                                             # mask, then post-process
             out = gate_decoded(out, span_tags, long_set.n_rec, NC, min_tag)
             calls = [(calls[0][0] + " + sed_events_tag_scores + sed_events_select (min_span_tag)", out["err"])]
+    if known_tags is not None:                                                   # the same gate on given tags: one span each
+        given = {"tags": torch.from_numpy(np.ascontiguousarray(known, dtype=np.float32)).to(dev),
+                 "rec_span0": torch.arange(long_set.n_rec + 1, dtype=torch.int64, device=dev),
+                 "span3": int(np.diff(long_set.rec_frame0_host).max())}
+        out = gate_decoded(out, given, long_set.n_rec, NC, 0.5)
+        calls = [(calls[0][0] + " + sed_events_tag_scores + sed_events_select (known_tags)", out["err"])]
     if process:
         out = process_decoded(out, long_set.n_rec, NC, min_len, max_gap, process_order)
         calls = [(calls[0][0] + " + sed_events_process", out["err"])]
@@ -925,30 +1107,57 @@ def get_long_predictions(model, long_set, decoder_or_labels, pooling_time_ratio=
         err = int(word.item())
         if err:
             raise _lib.SedError(stitch_error_text(what, err))
-    ev_ptr = out["ev_ptr"].cpu().numpy()
-    ev = out["ev_pairs"][:int(ev_ptr[-1])].cpu().numpy()
-    per_col = np.diff(ev_ptr)
-    col = np.repeat(np.arange(per_col.size), per_col)
-    rec, cls = col // NC, col % NC
-    per_rec = per_col.reshape(long_set.n_rec, NC).sum(1)
-    index = np.arange(len(col)) - np.repeat(np.r_[0, np.cumsum(per_rec)[:-1]], per_rec)     # 0 .. k - 1 per recording
-    prediction_df = pd.DataFrame({"event_label": np.asarray(labels, dtype=object)[cls],
-                                  "onset": ev[:, 0].astype(np.int64), "offset": ev[:, 1].astype(np.int64),
-                                  "filename": np.asarray(long_set.filenames, dtype=object)[rec]}, index=index,
-                                 columns=["event_label", "onset", "offset", "filename"])
-    prediction_df.onset = prediction_df.onset * pool / (cfg.sample_rate / cfg.hop_length)
-    prediction_df.offset = prediction_df.offset * pool / (cfg.sample_rate / cfg.hop_length)
-    if scored:
-        prediction_df["score_max"] = score_max[:len(ev)].cpu().numpy()
-        prediction_df["score_mean"] = score_mean[:len(ev)].cpu().numpy()
-    if save_predictions is not None:
-        prediction_df.to_csv(save_predictions, index=False, sep="\t")
-    result = (prediction_df,)
-    if return_posteriors:
-        f0 = long_set.rec_frame0_host
-        result += ([out["timeline"][int(f0[r]):int(f0[r + 1])] for r in range(long_set.n_rec)], win_strong)
-    if return_weak:
-        result += (tags["weak"],)
-    if return_span_tags:
-        result += ((span_tags["tags"], span_tags["rec_span0_host"], span_tags["span3"]),)
-    return result if len(result) > 1 else prediction_df
+    return {"out": out, "scored": scored, "score_max": score_max if scored else None, "score_mean": score_mean if scored else None,
+            "win_strong": win_strong, "weak": tags["weak"] if return_weak else None,
+            "span_tags": span_tags if tag_span is not None else None, "labels": labels, "pool": pool, "cfg": cfg, "NC": NC}
+
+
+PSEUDO_LABEL_KWARGS = ("pooling_time_ratio", "batch_size", "cfg", "threshold", "median_window", "weighting", "threshold_high",
+                       "tag_span", "min_span_tag", "min_event_length", "min_event_gap", "process_order", "min_event_score",
+                       "score_key", "known_tags")
+
+
+def pseudo_label(model, long_set, target_set, items, labels, soft=None, combine="replace", **decode_kwargs):
+    """One self-training stage on the device: the recordings of ``long_set`` are inferred with ``model`` (the EMA teacher, as a
+    rule), decoded, gated and cleaned exactly as ``get_long_predictions`` does with the same arguments, and the final table is
+    written as strong labels into ``target_set`` (a ``WindowedFeatureSet`` or a ``ResidentFeatureSet`` holding targets):
+    recording r becomes the labels of its pool item ``items[r]``, in place (``relabel``) - no DataFrame, no label upload, the
+    set is not rebuilt.  ``labels``: the class labels (or a bound ``decode_strong``).  ``soft``: None (hard 0 / 1 labels),
+    ``"max"`` or ``"mean"`` (every event carries that score of the blended timeline); ``combine``: ``"replace"`` or ``"max"``
+    (keep given labels and add the pseudo events).  ``decode_kwargs`` are ``get_long_predictions``' own (``PSEUDO_LABEL_KWARGS``:
+    threshold, median_window, weighting, threshold_high, tag_span / min_span_tag, min_event_length / min_event_gap /
+    process_order, min_event_score / score_key, batch_size, cfg, pooling_time_ratio), and ``known_tags`` [n_rec, nclass] (a
+    tensor or array of 0 / 1): the tags a weakly labelled recording is KNOWN to hold replace pooled tags in the gate, one span
+    per recording - an event of a class the recording does not hold is dropped (``gate_decoded`` with these tags and a minimum
+    of 0.5, right after the decode like the tag gate; not together with ``min_span_tag``).  ``relabel``'s refusals (items,
+    lengths, classes) are raised before any forward; the chain's error words are checked once before the pool is touched, the
+    rasterise's own word after it.  Returns a dict: ``events_per_class`` [n_rec, nclass] int64 (one host copy of the counts)
+    and ``table``, the device dict of ``get_long_predictions(return_table=True)``."""
+    unknown = sorted(set(decode_kwargs) - set(PSEUDO_LABEL_KWARGS))
+    if unknown:
+        raise TypeError(f"pseudo_label: unexpected arguments {unknown} (it takes {list(PSEUDO_LABEL_KWARGS)})")
+    if soft is not None:
+        _score_key_code(soft)
+    _combine_code(combine)
+    if not isinstance(long_set, LongRecordingSet):
+        raise TypeError(f"long_set must be a LongRecordingSet, got {type(long_set).__name__}")
+    if not hasattr(target_set, "relabel"):
+        raise TypeError(f"target_set must be a set with a label pool (relabel), got {type(target_set).__name__}")
+    kw = dict(pooling_time_ratio=None, batch_size=64, cfg=None, threshold=0.5, median_window=None, weighting="taper",
+              threshold_high=None, min_event_length=None, min_event_gap=None, process_order="drop_merge", min_event_score=None,
+              score_key="max", tag_span=None, min_span_tag=None, known_tags=None)
+    kw.update(decode_kwargs)
+    n_labels = len(getattr(getattr(labels, "__self__", None), "labels", None) or ([] if callable(labels) else list(labels)))
+    target_set.check_relabel(items, long_set.rec_frame0_host, n_labels)          # (before any forward)
+    s = _long_events(model, long_set, labels, return_posteriors=False, return_weak=False, event_scores=soft is not None,
+                     return_span_tags=False, **kw)
+    table = _final_table(s)
+    err = target_set.relabel(items, table, long_set.rec_frame0_host, nclass=s["NC"],
+                             values=None if soft is None else table["score_" + soft], combine=combine)
+    counts = (table["ev_ptr"][1:] - table["ev_ptr"][:-1]).cpu().numpy().reshape(long_set.n_rec, s["NC"])
+    word = int(err.item())
+    if word:
+        raise _lib.SedError("sed_events_rasterize reported err " + ", ".join(f"bit {b} ({t})" for b, t in RASTER_ERR_BITS.items()
+                                                                              if word & b) + f" (err = {word}): the labels of "
+                            "the items named are invalid")
+    return {"events_per_class": counts, "table": table}

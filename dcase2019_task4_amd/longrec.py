@@ -247,6 +247,9 @@ class WindowedFeatureSet(ResidentFeatureSet):
     numpy's GLOBAL generator exactly as ``ResidentFeatureSet.epoch_rows`` draws them (over the streams' window slots; slot =
     item in a non-windowed stream): random crops never change the number of global draws.
 
+    ``relabel(items, table, rec_frame0_host, ...)`` (inherited) rewrites the label timelines of whole items in place from a
+    decoded event table on the device - pseudo strong labels for the next round (``inference.pseudo_label``).
+
     Not provided: ``from_waveforms``, crop starts finer than one label frame, event-aware (class-balanced) crop sampling,
     training on recordings that carry only weak labels (the pooled recording-level tag of ``inference.stitch_weak`` has no
     backward)."""
@@ -395,6 +398,11 @@ class WindowedFeatureSet(ResidentFeatureSet):
             _lib.ptr(self.label_offset) if lab else None, _lib.ptr(self.label_rows) if lab else None, self.T3, self.nclass,
             _lib.ptr(out_target), _lib.ptr(ws), ws.numel(), self.math_dtype, _lib.stream_ptr()),
             "sed_gather_window_logmel_transform")
+
+    def _label_layout(self):
+        """The label pool of ``relabel`` / ``check_relabel`` (resident.py): item i owns the rows ``label_offset[i] ..
+        label_offset[i] + label_rows[i] - 1`` of ``label_pool``."""
+        return self.label_pool, self.label_offset_host, self.label_rows_host.astype(np.int64), self.nclass, "label_rows"
 
     def transform(self, windows, seed=None):
         """Convenience (tests, tools): host windows [[item, start3], ...] -> (clean[, noisy], target) as new device tensors;

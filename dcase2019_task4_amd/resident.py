@@ -277,6 +277,62 @@ class ResidentFeatureSet:
             _lib.ptr(out_clean), _lib.ptr(out_noisy), _lib.ptr(self.targets) if out_target is not None else None, tgt_elems,
             _lib.ptr(out_target), _lib.ptr(ws), ws.numel(), self.math_dtype, _lib.stream_ptr()), "sed_gather_logmel_transform")
 
+    # ---- labels rewritten in place --------------------------------------------------------------------------------------------
+    def _label_layout(self):
+        """Where this set's labels live: ``(pool, row0, rows, nclass, what)`` - the contiguous float32 tensor of label rows,
+        per item the first row and the number of rows (host int64), and a word for an item's length in the messages."""
+        if self.targets is None:
+            raise ValueError("this set holds no targets: there is nothing to relabel")
+        T3, nclass = self.target_shape
+        n = np.arange(self.n_clips, dtype=np.int64)
+        return self.targets, n * T3, np.full(self.n_clips, T3, dtype=np.int64), nclass, "T3"
+
+    def check_relabel(self, items, rec_frame0_host, nclass=None):
+        """The host checks of ``relabel``, before any launch (``ValueError``): ``items`` distinct and inside the set, every
+        recording exactly as long as its item's labels, the classes equal.  Returns ``(items, the first pool row of each)``."""
+        pool, row0, rows, n_cls, what = self._label_layout()
+        items = np.asarray(items, dtype=np.int64).reshape(-1)
+        f0 = np.asarray(rec_frame0_host, dtype=np.int64).reshape(-1)
+        if items.size < 1 or f0.size != items.size + 1:
+            raise ValueError(f"relabel: {items.size} items for a table of {f0.size - 1} recordings")
+        if items.min() < 0 or items.max() >= self.n_clips:
+            raise ValueError(f"relabel: items must lie in [0, {self.n_clips})")
+        if np.unique(items).size != items.size:
+            raise ValueError("relabel: an item is named twice (two recordings would write the same label rows)")
+        if nclass is not None and int(nclass) != n_cls:
+            raise ValueError(f"relabel: the table has {int(nclass)} classes, the set's labels {n_cls}")
+        L3 = np.diff(f0)
+        for r in np.flatnonzero(L3 != rows[items]):
+            raise ValueError(f"relabel: recording {r} has {int(L3[r])} label frames, item {int(items[r])} has {what} = "
+                             f"{int(rows[items[r]])}")
+        return items, row0[items]
+
+    def relabel(self, items, out_or_table, rec_frame0_host, nclass=None, values=None, point=None, combine="replace", err=None):
+        """Rewrite the strong labels of the items ``items`` IN PLACE from a decoded event table on the device
+        (``inference.events_rasterize``, ``sed_events_rasterize``): recording r of the table becomes the labels of item
+        ``items[r]``.  ``out_or_table``: the dict of a stitch entry / ``get_long_predictions(return_table=True)`` or a pair
+        ``(ev_ptr, ev_pairs)``; ``rec_frame0_host`` [n_rec + 1]: the recordings' label-frame offsets on the host (a
+        ``LongRecordingSet`` has them); ``values`` / ``point`` / ``combine`` / ``err`` as for ``events_rasterize`` (soft labels,
+        per-class operating points, ``"replace"`` or ``"max"``).  Checked on the host before any launch (``ValueError``):
+        ``items`` in range and distinct, every recording's length equal to its item's label rows, ``nclass`` (given, or the
+        columns of the dict's timeline) equal to the set's; a set without targets raises.  The label tensor keeps its
+        ``data_ptr()``: a captured step graph and the one-batch-ahead front-end read the new labels at their next gather - a
+        batch the front-end has ALREADY gathered when ``relabel`` is called still carries the old labels, so relabelling
+        during an epoch takes effect one batch later (between epochs, or before ``train.train``, nothing is in flight).  The
+        other items keep their labels bit for bit.  Returns the device error word ``err`` [1] int32 (non-zero: the items'
+        labels are invalid); nothing synchronises."""
+        from . import inference
+        if nclass is None and isinstance(out_or_table, dict) and out_or_table.get("timeline") is not None:
+            nclass = out_or_table["timeline"].shape[-1]
+        items, row0 = self.check_relabel(items, rec_frame0_host, nclass)
+        pool, _, _, n_cls, _ = self._label_layout()
+        f0 = np.ascontiguousarray(rec_frame0_host, dtype=np.int64).reshape(-1)
+        ev_pairs = out_or_table["ev_pairs"] if isinstance(out_or_table, dict) else out_or_table[1]
+        rec_frame0 = torch.from_numpy(f0).to(ev_pairs.device)
+        _, err = inference.events_rasterize(out_or_table, rec_frame0, items.size, n_cls, dst=pool, dst_row0=row0, values=values,
+                                            point=point, combine=combine, err=err, rec_frame0_host=f0)
+        return err
+
     def transform(self, indices, seed=None):
         """Convenience (tests, tools): host indices -> (clean[, noisy], target or None) as new device tensors; ``seed`` is the
         Philox key of the teacher's noise (a set built with augment_type='noise' requires it)."""

@@ -881,6 +881,63 @@ int sed_events_tag_scores(const float* tags, long long total_spans, const int64_
                           const int64_t* ev_ptr, const int32_t* ev_pairs, long long pairs_capacity, long long n_cols,
                           float* tag_score, int32_t* err, void* stream);
 
+/* ---- pseudo strong labels: an event table rasterised into the rows of a label pool ------------------
+ * The training side reads its strong labels as rows [*][NC] fp32 in HBM (the label pool the gather kernels slice); every
+ * decode, gate, process and select leaves a CSR event table.  sed_events_rasterize turns a table back into label rows at
+ * their place in such a pool, in place: the teacher's cleaned events become the next round's strong labels without a host
+ * copy.  The definition is the project's own; pinned is bitwise agreement with a plain-loop statement
+ * (tests/rasterize_np.py: for every recording, class and event, for u in range(on, off)).
+ *   ev_ptr [n_points * n_rec * NC + 1] int64, ev_pairs [pairs_capacity][2] int32   a table in the sweep's column order
+ *                                        (layout as for the event scores above; n_points = 1: sed_stitch_decode's)
+ *   point [NC] int32                     device, or NULL for all zero: class c is taken from operating point point[c], its
+ *                                        column is (point[c] * n_rec + rec) * NC + c - a tuned system keeps a point per class
+ *   value [pairs_capacity] fp32          indexed like ev_pairs, or NULL: every event has the value 1.0f.  Otherwise the event's
+ *                                        value is copied bit for bit (NaN payloads, -0.0f and denormals as they are);
+ *                                        score_max / score_mean of sed_events_scores are the intended soft labels
+ *   rec_frame0 [n_rec + 1] int64         device: recording r has L3_r = rec_frame0[r + 1] - rec_frame0[r] rows
+ *   dst [dst_rows][NC] fp32              the pool
+ *   dst_row0 [n_rec] int64               device, or NULL: row u of recording r is dst row dst_row0[r] + u; NULL means
+ *                                        rec_frame0[r] + u, a contiguous timeline.  Exactly the L3_r rows of each valid
+ *                                        recording are addressed; no other byte of dst is read or written.
+ * For row u of recording r and class c: i = the event of the selected column with on_i <= u < off_i (columns hold disjoint
+ * events with non-decreasing onsets: at most one), v = value[i] or 1.0f.
+ *   combine = 0 (replace)  a covered element takes v, an uncovered one +0.0f: every addressed element is written exactly once
+ *   combine = 1 (maximum)  a covered element takes (v > old) ? v : old - a NaN v never replaces anything, a NaN old stays - ,
+ *                          an uncovered one is left as it is.  M calls form the union of M models' tables; one call on given
+ *                          strong labels adds pseudo events to them.
+ * Events are never cut except at L3_r, and an event beyond L3_r is an error, not a clip.
+ *   err    one int32, OR-ed, the family's bits:
+ *             8 = point[c] outside [0, n_points): class c is rasterised in no recording, its elements are not written
+ *            16 = a column whose bounds are not 0 <= ev_ptr[col] <= ev_ptr[col + 1] <= pairs_capacity (any column of the
+ *                 table, selected or not), a recording whose bounds are not 0 <= rec_frame0[r] <= rec_frame0[r + 1] <=
+ *                 dst_rows (the rows of distinct destinations cannot number more than dst_rows), or a recording with
+ *                 dst_row0[r] < 0 or dst_row0[r] + L3_r > dst_rows: nothing of such a column or recording is read or written.
+ *                 (As in sed_events_hysteresis, an ev_ptr that is not non-decreasing can moreover leave events that the
+ *                 bisection assigns to no column: they are not checked.)
+ *                 (The recording of a row is found by bisection: a rec_frame0 that is not non-decreasing can moreover leave
+ *                 rows of a well-formed recording that the bisection assigns to another one; they are not written.)
+ *            64 = an event of a valid column that `point` selects, in a recording with valid frame bounds, with on < 0,
+ *                 on >= off, off > L3_r, or on smaller than the previous event's off in the same column (touching events are
+ *                 valid).  Every such event index is checked, not only those a row meets; what the column's elements hold
+ *                 afterwards is unspecified (inside the addressed rows).
+ *          No table content can make a kernel address outside ev_ptr, ev_pairs, value, point, rec_frame0, dst_row0 or the
+ *          addressed rows of dst.  A caller treats dst as invalid when err != 0.  Two recordings whose destination rows overlap
+ *          are a host error: the entry only guarantees in-bounds writes (the Python fronts refuse them).
+ * Two launches on `stream` whatever n_points and the number of events are (one when dst_rows is 0): a check pass flat over
+ * the indices of ev_pairs that writes nothing but err, and a row pass - a gather, flat over the timeline rows: a thread finds
+ * its recording by bisection over rec_frame0 and per class the last event with on <= u by bisection over the column's
+ * onsets.  The destination is not cleared first.  16-byte stores when NC % 4 == 0 and dst is 16-byte aligned, a scalar path
+ * otherwise (identical bytes).  No workspace, no host synchronisation, no allocation, no atomics but the OR into err,
+ * hipGraph-capturable, identical bytes from call to call.
+ * Limits, checked before any launch (SED_ERR_BAD_ARG, err untouched): no null pointer except value, point and dst_row0,
+ * 1 <= NC <= 16, n_rec >= 1, 1 <= n_points <= 4096, n_points * n_rec * NC < 2^26, 0 <= pairs_capacity < 2^31, 0 <= dst_rows,
+ * dst_rows * NC < 2^31, ev_pairs 8-byte aligned, dst 4-byte aligned, combine 0 or 1, dst overlapping no input (err included).
+ * Not provided: per-frame "ignore" labels, events cut at window or span boundaries, sub-frame onsets, feature pools. */
+int sed_events_rasterize(const int64_t* ev_ptr, const int32_t* ev_pairs, const float* value, long long pairs_capacity,
+                         int n_points, const int32_t* point, const int64_t* rec_frame0, int n_rec, int NC,
+                         float* dst, long long dst_rows, const int64_t* dst_row0, int combine,
+                         int32_t* err, void* stream);
+
 /* ---- validation scoring ------------------------------------------------------------------------
  * Replaces, after get_predictions, the host-side scoring of the epoch loop (baseline/main.py:328-352):
  *   compute_strong_metrics(predictions, valid_synth_df) (evaluation_measures.py:234-246) = sed_eval's

@@ -98,7 +98,14 @@ thresholds as --scoring, min_event_length 0.25 s and min_event_gap 0.15 s at eve
   --boundary-libs A.so,B.so: the scorer alone on the same table under builds of the library with other short / long
     boundaries (-DEVS_SHORT_FRAMES=n for csrc/evscore.hip), each in a process of its own.
 
-Usage: python tools/long_bench.py [--scoring | --sweep | --weak | --tag-train | --error-rate | --hysteresis | --process | --scores] [--rounds 5] [--decode-reps 30] [--out profiles/long_inference.json]"""
+--rasterize measures the pseudo strong labels (profiles/long_rasterize.json), same workloads, hop and 50 thresholds:
+  sed_events_rasterize alone on point 0 of the 50-point sweep table, the points given per class (a device-event pair around the
+    Python call, median of --decode-reps), against the only earlier route: the table copied to the host, a vectorised numpy
+    rasterise (difference array + cumsum) and an upload into the pool; the run asserts that the two routes' rows are identical.
+  pseudo_label into a WindowedFeatureSet over the same recordings against the same run's get_long_predictions with the same
+    arguments, alternated, --rounds rounds; a difference counts only outside the larger (max - min) of the two legs.
+
+Usage: python tools/long_bench.py [--scoring | --sweep | --weak | --tag-train | --error-rate | --hysteresis | --process | --scores | --span-tags | --rasterize] [--rounds 5] [--decode-reps 30] [--out profiles/long_inference.json]"""
 import argparse
 import json
 import os
@@ -989,6 +996,83 @@ def span_tags_workload(name, model, rounds, reps, tag_span=10.0, min_tag=0.5):
     return out
 
 
+def host_rasterize(ev_ptr, pairs, rec_frame0, n_rec, NC, total):
+    """Point 0 of a table as label rows on the host: a difference array over the flat rows and a cumsum: numpy arrays ->
+    [total, NC] float32 of 0 / 1."""
+    n_cols = n_rec * NC
+    p = ev_ptr[:n_cols + 1]
+    q = pairs[int(p[0]):int(p[-1])].astype(np.int64)
+    col = np.repeat(np.arange(n_cols, dtype=np.int64), np.diff(p))
+    base, cls = rec_frame0[col // NC], col % NC
+    d = np.zeros((total + 1, NC), np.int32)
+    np.add.at(d, (base + q[:, 0], cls), 1)
+    np.add.at(d, (base + q[:, 1], cls), -1)
+    return (np.cumsum(d[:-1], axis=0) > 0).astype(np.float32)
+
+
+def rasterize_workload(name, model, rounds, reps):
+    """--rasterize: (a) sed_events_rasterize alone on point 0 of the 50-point table against the host route (table copied down,
+    difference array + cumsum, upload into the pool), rows asserted identical; (b) pseudo_label into a WindowedFeatureSet over
+    the same recordings against the same run's get_long_predictions with the same arguments, alternated."""
+    from dcase2019_task4_amd.longrec import WindowedFeatureSet
+    info, ctx = scoring_workload(name, model, rounds, reps, setup_only=True)
+    ls, window, win_strong, thr50 = ctx["ls"], ctx["window"], ctx["win_strong"], ctx["thr50"]
+    out = {k: info[k] for k in ("recordings", "windows", "timeline_frames", "median_window")}
+    out.update(rounds=rounds, points=50, label_rows=ls.total_frames, nclass=NCLASS)
+    total, n_rec, state = ls.total_frames, ls.n_rec, {}
+    table = inference.stitch_sweep(win_strong, ls.rec_win0, ls.rec_frame0, total, ls.hop3, thr50, [window], "taper",
+                                   50 * ls.capacity(NCLASS))
+    assert int(table["err"].item()) == 0
+    pool = torch.full((total, NCLASS), float("nan"), device=win_strong.device)
+    point = torch.zeros(NCLASS, dtype=torch.int32, device=win_strong.device)        # one point per class: here all point 0
+
+    def device():
+        state["err"] = inference.events_rasterize(table, ls.rec_frame0, n_rec, NCLASS, dst=pool, point=point)[1]
+
+    def host():
+        p = table["ev_ptr"][:n_rec * NCLASS + 1].cpu().numpy()
+        q = table["ev_pairs"][:int(p[-1])].cpu().numpy()
+        state["host_pool"].copy_(torch.from_numpy(host_rasterize(p, q, ls.rec_frame0_host, n_rec, NCLASS, total)))
+    state["host_pool"] = torch.full_like(pool, float("nan"))
+    for _ in range(3):
+        host()
+    host_ms = stats([wall_ms(host) for _ in range(reps)])
+    g = {"sed_events_rasterize": event_ms(device, reps),
+         "host_copy_cumsum_upload": {"median_ms": host_ms["median_ms"], "spread": host_ms["spread"], "reps": reps,
+                                     "timing": "host clock around the synchronised route"}}
+    identical = bool(torch.equal(pool.view(torch.int32), state["host_pool"].view(torch.int32)))
+    assert identical and int(state["err"].item()) == 0, "the device rasterise and the host route disagree"
+    g.update(pairs_capacity=int(table["ev_pairs"].shape[0]), table_events=int(table["ev_ptr"][-1].item()),
+             point_0_events=int(table["ev_ptr"][n_rec * NCLASS].item()), covered_elements=int(pool.sum().item()),
+             routes_identical=identical)
+    out["rasterize_alone"] = g
+    # (b) pseudo_label against get_long_predictions, the same arguments
+    recs = recordings(*WORKLOADS[name])
+    L3s = np.diff(ls.rec_frame0_host)
+    target = WindowedFeatureSet.from_arrays(recs, [np.zeros((int(L), NCLASS), np.float32) for L in L3s], (n_rec,), (1,), T, [True],
+                                            scaler=scaler_of(recs[0]), augment_type=None)
+    items, labels = list(range(n_rec)), _Enc.labels
+    kw = dict(pooling_time_ratio=POOL, batch_size=BATCH, threshold=thr50[0], median_window=window)
+    legs = {"get_long_predictions": lambda: state.__setitem__("df", inference.get_long_predictions(model, ls, labels, **kw)),
+            "pseudo_label": lambda: state.__setitem__("pl", inference.pseudo_label(model, ls, target, items, labels, **kw))}
+    for fn in legs.values():
+        fn()
+    ms = {leg: [] for leg in legs}
+    for _ in range(rounds):
+        for leg, fn in legs.items():
+            ms[leg].append(wall_ms(fn))
+    t = {leg: stats(ms[leg]) for leg in legs}
+    a, b = t["get_long_predictions"], t["pseudo_label"]
+    band = max(max(x["samples_ms"]) - min(x["samples_ms"]) for x in (a, b))
+    t["difference"] = {"pseudo_label_minus_predictions_ms": b["median_ms"] - a["median_ms"], "larger_max_minus_min_ms": band,
+                       "inside_the_band": bool(abs(b["median_ms"] - a["median_ms"]) <= band)}
+    t["events"] = {"frame_rows": len(state["df"]), "pseudo_label": int(state["pl"]["events_per_class"].sum())}
+    assert t["events"]["frame_rows"] == t["events"]["pseudo_label"]
+    assert torch.equal(target.label_pool.view(torch.int32), pool.view(torch.int32)), "pseudo_label's rows are not point 0's"
+    out["pseudo_label"] = t
+    return out
+
+
 def weak_workload(name, model, rounds, reps):
     import ctypes as C
     n_rec, per = WORKLOADS[name]
@@ -1195,6 +1279,8 @@ def main():
                     help="measure the event scores and the select by score (profiles/long_scores.json)")
     ap.add_argument("--span-tags", action="store_true",
                     help="measure the span-level weak tags and the tag gate (profiles/long_span_tags.json)")
+    ap.add_argument("--rasterize", action="store_true",
+                    help="measure the pseudo strong labels: sed_events_rasterize and pseudo_label (profiles/long_rasterize.json)")
     ap.add_argument("--boundary-libs", default="",
                     help="with --scores: comma-separated builds of the library with other EVS_SHORT_FRAMES (csrc/evscore.hip)")
     ap.add_argument("--scores-child", default=None, help=argparse.SUPPRESS)
@@ -1207,7 +1293,7 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(REPO, "profiles", "long_span_tags.json" if args.span_tags else "long_scores.json" if args.scores else "long_process.json" if args.process else
+        args.out = os.path.join(REPO, "profiles", "long_rasterize.json" if args.rasterize else "long_span_tags.json" if args.span_tags else "long_scores.json" if args.scores else "long_process.json" if args.process else
                                 "long_hysteresis.json" if args.hysteresis else
                                 "error_rate.json" if args.error_rate else
                                 "long_tag_train.json" if args.tag_train else "long_weak.json" if args.weak else
@@ -1227,6 +1313,26 @@ def main():
               "not_measured": ["from_waveforms / feature extraction", "other batch sizes, bf16 / wide models",
                                "recordings longer than 1 h", "a run with the GPU to itself (the host is shared)"],
               "workloads": {}}
+    if args.rasterize:
+        result["timing"] = ("sed_events_rasterize alone: a device-event pair around the Python call (no allocation: the pool is "
+                            "given), warm, median of --decode-reps; the host route: host clock around the synchronised route, same "
+                            "reps; pseudo_label / get_long_predictions: host clock around each synchronised call, the two legs "
+                            "alternated in one run, --rounds rounds, medians, spread = (max - min) / median")
+        result["note"] = ("the host route (table copied down, numpy difference array + cumsum, upload into the pool) is the only "
+                          "route there was before; the run asserts that both routes' rows are identical bit for bit, and that "
+                          "pseudo_label leaves the same rows in the set's label pool.  pseudo_label against get_long_predictions: "
+                          "the same arguments (point 0's thresholds, median window 7); a difference counts only where it lies "
+                          "outside the larger (max - min) of the two legs")
+        result["not_measured"] += ["other nclass than 10", "combine=\"max\"", "soft values", "the two kernels one by one",
+                                   "a scatter form (a clear, then one thread or wave per event): not written",
+                                   "relabel while a training step is in flight"]
+        for name in args.workloads.split(","):
+            result["workloads"][name] = rasterize_workload(name, model, args.rounds, args.decode_reps)
+            print(json.dumps({name: result["workloads"][name]}), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(json.dumps(result, indent=1) + "\n")
+        return
     if args.span_tags:
         result["timing"] = ("get_long_predictions / validate_long legs: host clock around each synchronised call, the two legs "
                             "alternated in one run, --rounds rounds, medians, spread = (max - min) / median; the calls alone: a "
