@@ -73,6 +73,10 @@ _SIGS = {
                                     C.c_longlong, _P, C.c_size_t, _P, _P]),
     "sed_events_rasterize": (C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, _P, _P, C.c_int, C.c_int, _P, C.c_longlong, _P, C.c_int, _P,
                                        _P]),
+    "sed_window_activity_ws_bytes": (C.c_size_t, [C.c_longlong, C.c_int, C.c_int]),
+    "sed_window_activity": (C.c_int, [_P, _P, C.c_longlong, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, C.c_size_t, _P, _P]),
+    "sed_window_event_starts": (C.c_int, [_P, _P, _P, _P, C.c_longlong, _P, _P, C.c_int, _P, C.c_longlong, C.c_int, C.c_int, C.c_int,
+                                          _P, _P, _P, _P, _P, _P, _P, _P]),
     "sed_stitch_weak_ws_bytes": (C.c_size_t, [C.c_longlong, C.c_int, C.c_int]),
     "sed_stitch_weak": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P, _P]),
     "sed_stitch_weak_backward": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),

@@ -226,7 +226,8 @@ def encode_timeline(events_of_file, n_rows, class_labels, cfg, pooling_time_rati
     return y
 
 
-SAMPLINGS = ("random", "grid")
+SAMPLINGS = ("random", "grid", "events")
+CROP_ERR_BITS = {8: "nclass above 16", 16: "an item index or an item's label rows out of range", 32: "a start_hi outside its item"}
 
 
 class WindowedFeatureSet(ResidentFeatureSet):
@@ -242,7 +243,17 @@ class WindowedFeatureSet(ResidentFeatureSet):
     ``L3 = max(1, L_i // pool)`` and ``hi = max(0, L3 - T3)``, window j of the item starts at
       ``sampling="grid"``    ``min(j * hop3, hi)``, the same in every epoch;
       ``sampling="random"``  an integer uniform on ``[0, hi]``: ``np.random.default_rng([seed, epoch])`` draws ``n_w(i)`` of
-                             them per windowed item, in item order, identically on every rank.
+                             them per windowed item, in item order, identically on every rank;
+      ``sampling="events"``  event-aware: a slot is, with probability ``event_fraction``, given a class drawn uniformly
+                             among the classes the item's timeline holds and then a start with probability proportional to
+                             the active frames (label > 0) of that class its window covers - so the window holds at least
+                             one; every other slot, and every slot of an item without events, is uniform on ``[0, hi]``.
+                             The draws are the host's (``event_draws``: ``default_rng([seed, epoch])``, identical on every
+                             rank); the starts come from the label pool where it lives (``sed_window_activity``,
+                             ``sed_window_event_starts``; the definition is in include/dcase_sed.h), recomputed on every
+                             call: labels rewritten in place by ``relabel`` move the next epoch's crops.  The set must be
+                             on a GPU (``SedError`` otherwise: no CPU fallback).  ``event_weights()`` and
+                             ``slot_classes(epoch)`` are its diagnostics.
     An item with ``L3 >= T3`` therefore never yields a window with padded label frames.  The stream permutations come from
     numpy's GLOBAL generator exactly as ``ResidentFeatureSet.epoch_rows`` draws them (over the streams' window slots; slot =
     item in a non-windowed stream): random crops never change the number of global draws.
@@ -250,8 +261,8 @@ class WindowedFeatureSet(ResidentFeatureSet):
     ``relabel(items, table, rec_frame0_host, ...)`` (inherited) rewrites the label timelines of whole items in place from a
     decoded event table on the device - pseudo strong labels for the next round (``inference.pseudo_label``).
 
-    Not provided: ``from_waveforms``, crop starts finer than one label frame, event-aware (class-balanced) crop sampling,
-    training on recordings that carry only weak labels (the pooled recording-level tag of ``inference.stitch_weak`` has no
+    Not provided: ``from_waveforms``, crop starts finer than one label frame, class balance across the whole set (the
+    event-aware draw balances the classes of each item), training on recordings that carry only weak labels (the pooled recording-level tag of ``inference.stitch_weak`` has no
     backward)."""
 
     row_shape = (2,)
@@ -259,14 +270,17 @@ class WindowedFeatureSet(ResidentFeatureSet):
     @classmethod
     def from_arrays(cls, features, labels, stream_sizes, batch_sizes, frames, windowed, pooling_time_ratio=8, hop_frames=None,
                     sampling="random", scaler=None, augment_type="noise", device="cuda", process_group=None, math_dtype="f64",
-                    seed=0, augment=None):
+                    seed=0, augment=None, event_fraction=0.5):
         """``features[i]``: [L_i, n_mels], any L_i >= 1; ``labels[i]``: [R_i, nclass] float32, any R_i >= 1 - the label
         timeline of the whole item at label-frame rate (rows a window reaches beyond R_i are 0); ``windowed``: one bool per
-        stream; ``hop_frames``: as ``LongRecordingSet`` (it only sets how many windows an item contributes, and the grid)."""
+        stream; ``hop_frames``: as ``LongRecordingSet`` (it only sets how many windows an item contributes, and the grid);
+        ``event_fraction`` in [0, 1]: the share of slots ``sampling="events"`` draws event-aware."""
         self = cls.__new__(cls)
         feats, labels, sizes = list(features), list(labels), [int(s) for s in stream_sizes]
         if sampling not in SAMPLINGS:
             raise ValueError(f"sampling must be one of {SAMPLINGS}, got {sampling!r}")
+        if not 0.0 <= float(event_fraction) <= 1.0:
+            raise ValueError(f"event_fraction must lie in [0, 1], got {event_fraction!r}")
         if len(labels) != len(feats):
             raise ValueError(f"{len(labels)} label timelines for {len(feats)} items")
         windowed = [bool(w) for w in windowed]
@@ -282,7 +296,7 @@ class WindowedFeatureSet(ResidentFeatureSet):
         self._setup(feats, None, sizes, None, frames, scaler, augment_type, device, process_group, math_dtype, seed)
         self.augment = augment
         self.pooling_time_ratio, self.hop_frames, self.hop3, self.T3 = pool, hop, hop // pool, self.frames // pool
-        self.sampling, self.windowed = sampling, windowed
+        self.sampling, self.windowed, self.event_fraction, self._crop = sampling, windowed, float(event_fraction), None
         self.max_win_frames = min(self.frames, self.max_clip_frames)
         # the label pool: timelines concatenated along rows
         labels = [np.asarray(y, dtype=np.float32) for y in labels]
@@ -335,12 +349,106 @@ class WindowedFeatureSet(ResidentFeatureSet):
         hi = self.start_hi_host[self.slot_item]
         if self.sampling == "grid":
             return np.minimum(self.slot_j * self.hop3, hi)
+        if self.sampling == "events":
+            return self._event_slots(epoch)[0]
         rng = np.random.default_rng([self.seed, int(epoch)])
         start = np.zeros(len(self.slot_item), dtype=np.int64)
         first = np.concatenate([[0], np.cumsum(self.n_w_host)[:-1]])
         for i in np.flatnonzero(self.item_windowed):
             start[first[i]:first[i] + self.n_w_host[i]] = rng.integers(0, self.start_hi_host[i] + 1, size=self.n_w_host[i])
         return start
+
+    def event_draws(self, epoch):
+        """The host draws of ``sampling="events"`` for epoch ``epoch``, over all window slots, in this order: ``u`` uint64
+        uniform on [0, 2^64), ``v`` int64 uniform on [0, 2^31), ``m`` bool, true with probability ``event_fraction``."""
+        n = len(self.slot_item)
+        rng = np.random.default_rng([self.seed, int(epoch)])
+        u = rng.integers(0, 2 ** 64, n, dtype=np.uint64)
+        v = rng.integers(0, 2 ** 31, n)
+        m = rng.random(n) < self.event_fraction
+        return u, v, m
+
+    def _crop_tables(self):
+        """The device tables of the event-aware draw, built on first use and kept: the CSR label rows, ``start_hi`` (0 for an
+        item of a non-windowed stream: its one window starts at 0), the slots' items, and the entries' outputs."""
+        if self.device.type != "cuda":
+            raise _lib.SedError('WindowedFeatureSet: sampling="events" needs the set on a GPU device (no CPU fallback)')
+        if self._crop is None:
+            n, nc, n_slots, dev = self.n_clips, self.nclass, len(self.slot_item), self.device
+            total = int(self.label_rows_host.astype(np.int64).sum())
+            ws_bytes = _lib.lib().sed_window_activity_ws_bytes(total, n, nc)
+            if ws_bytes == 0:
+                raise _lib.SedError(f"sed_window_activity_ws_bytes: {_lib.lib().sed_last_error().decode()}")
+            self._crop = {
+                "total": total,
+                "row0": torch.from_numpy(np.r_[self.label_offset_host, total].astype(np.int64)).to(dev),
+                "hi": torch.from_numpy(np.where(self.item_windowed, self.start_hi_host, 0).astype(np.int32)).to(dev),
+                "slot_item": torch.from_numpy(self.slot_item.astype(np.int32)).to(dev),
+                "A": torch.empty((total + n) * nc, dtype=torch.int32, device=dev),
+                "B": torch.empty((total + n) * nc, dtype=torch.int64, device=dev),
+                "W": torch.empty(n, nc, dtype=torch.int64, device=dev),
+                "present": torch.empty(n, dtype=torch.int32, device=dev),
+                "ws": _lib.scratch(ws_bytes, dev),
+                "out": torch.empty(2 * n_slots + 1, dtype=torch.int32, device=dev),       # start3 | chosen class | err
+            }
+        return self._crop
+
+    def _window_activity(self, t):
+        p = _lib.ptr
+        t["out"][-1:].zero_()
+        _lib.check(_lib.lib().sed_window_activity(p(self.label_pool), p(t["row0"]), t["total"], self.n_clips, self.nclass, p(t["hi"]),
+                                                  self.T3, p(t["A"]), p(t["B"]), p(t["W"]), p(t["present"]), p(t["ws"]),
+                                                  t["ws"].numel(), p(t["out"][-1:]), _lib.stream_ptr()), "sed_window_activity")
+
+    @staticmethod
+    def _crop_err(err):
+        if err:
+            raise _lib.SedError("event-aware crop sampling: " + "; ".join(s for b, s in CROP_ERR_BITS.items() if err & b)
+                                + f" (err {err})")
+
+    def _event_slots(self, epoch):
+        """(start3, chosen class) of every window slot in epoch ``epoch``, int64 [n_slots] each: the host draws, the two
+        entries on the set's device, one copy back."""
+        t = self._crop_tables()
+        n_slots = len(self.slot_item)
+        self._event_launch(t, *self._event_upload(epoch))
+        host = t["out"].cpu().numpy().astype(np.int64)
+        self._crop_err(int(host[-1]))
+        return host[:n_slots], host[n_slots:2 * n_slots]
+
+    def _event_upload(self, epoch):
+        """The draws of ``epoch`` on the set's device: (u as the int64 of the same bits, v int32, m uint8 - false on the slots
+        of non-windowed items, whose ``hi`` of 0 then gives start 0 and class -1)."""
+        u, v, m = self.event_draws(epoch)
+        m = m & self.item_windowed[self.slot_item]
+        return (torch.from_numpy(u.view(np.int64)).to(self.device), torch.from_numpy(v.astype(np.int32)).to(self.device),
+                torch.from_numpy(m.astype(np.uint8)).to(self.device))
+
+    def _event_launch(self, t, u_d, v_d, m_d):
+        """The two entries on the current stream; nothing synchronises."""
+        n_slots, p, out = len(self.slot_item), _lib.ptr, t["out"]
+        self._window_activity(t)
+        _lib.check(_lib.lib().sed_window_event_starts(
+            p(u_d), p(v_d), p(m_d), p(t["slot_item"]), n_slots, p(t["hi"]), p(self.clip_frames), self.pooling_time_ratio,
+            p(t["row0"]), t["total"], self.n_clips, self.nclass, self.T3, p(t["A"]), p(t["B"]), p(t["W"]), p(t["present"]),
+            p(out[:n_slots]), p(out[n_slots:2 * n_slots]), p(out[-1:]), _lib.stream_ptr()), "sed_window_event_starts")
+
+    def slot_classes(self, epoch):
+        """The class every window slot of epoch ``epoch`` was drawn for under ``sampling="events"``, int64 [n_slots]; -1: a
+        uniform draw (a diagnostic: it runs the draw again)."""
+        if self.sampling != "events":
+            raise ValueError('slot_classes is defined for sampling="events"')
+        return self._event_slots(epoch)[1]
+
+    def event_weights(self):
+        """``(W, present)`` of the label pool as it is now: ``W`` [n_items, nclass] int64, the activity of class c that the
+        windows of item i starting on ``[0, hi]`` cover, counted once per window (``hi`` = 0 for an item of a non-windowed
+        stream); ``present`` [n_items] uint32, bit c set when ``W[i, c] > 0``."""
+        t = self._crop_tables()
+        self._window_activity(t)
+        err = int(t["out"][-1].item())
+        self._crop_err(err)
+        return t["W"].cpu().numpy(), t["present"].cpu().numpy().view(np.uint32)
 
     def epoch_windows(self, epoch, rng=None):
         """One epoch of GLOBAL batches [n_steps, sum(batch_sizes), 2] int64 = (item, start3): the stream permutations of

@@ -938,6 +938,69 @@ int sed_events_rasterize(const int64_t* ev_ptr, const int32_t* ev_pairs, const f
                          float* dst, long long dst_rows, const int64_t* dst_row0, int combine,
                          int32_t* err, void* stream);
 
+/* ---- event-aware crop starts for windowed training, drawn from the label pool ------------------------
+ * Uniform crop starts spend most windows of a sparsely labelled recording on silence.  These two entries draw the starts
+ * of sed_gather_window_logmel_transform's windows from the label pool where it lives (since sed_events_rasterize the labels
+ * that say where events are may exist in HBM only).  The definition is the project's own and uses integers only; pinned is
+ * exact agreement with a plain-loop statement (tests/crop_np.py).
+ *
+ * Item i owns the R_i >= 1 label rows [label_row0[i], label_row0[i + 1]) of label_pool [total_label_rows][nclass] fp32
+ * (label_row0: device int64 [n_items + 1], a CSR over the rows).  hi = start_hi[i] >= 0 is its last legal start, T3 the
+ * window length in label frames.  A row is ACTIVE for class c when label_pool[row][c] > 0 (NaN, -0.0f and anything <= 0 are
+ * inactive, a soft label counts as active).
+ *   a_c(s)  = active rows of class c in [s, min(s + T3, R))             C_c(s) = sum of a_c(s') over s' <= s, s in [0, hi]
+ *   W_c     = C_c(hi); class c is PRESENT in the item when W_c > 0;     P = the number of present classes
+ * All randomness is the caller's: per window slot u (uint64, uniform on [0, 2^64)), v (int32 >= 0) and m (uint8).
+ *   m == 0 or P == 0:  start = (u * (hi + 1)) >> 64  (the high 64 bits of the 64 x 64 bit product), chosen class -1
+ *   otherwise:         c = the (v % P)-th present class in class order, target = (u * W_c) >> 64,
+ *                      start = the smallest s with C_c(s) > target
+ * so a_c(start) > 0 - the window holds an active frame of c - and a start's probability is proportional to the activity of
+ * c its window covers.
+ *
+ * sed_window_activity: one segmented scan over the pool, flat over rows, of the triples (n, a, b) under
+ *   (n1, a1, b1) o (n2, a2, b2) = (n1 + n2, a1 + a2, b1 + b2 + a1 * n2), reset at every item's first row.  In front of row x
+ * of an item it leaves A(x) = the active rows before x and B(x) = A(0) + ... + A(x - 1), for x in [0, R]:
+ *   A [(total_label_rows + n_items)][nclass] int32, B likewise int64: item i's R_i + 1 rows start at row label_row0[i] + i.
+ * Beyond R both are extended on read, A(x) = A(R) and B(x) = B(R) + (x - R) * A(R); then
+ *   C_c(s) = B(s + 1 + T3) - B(T3) - B(s + 1).
+ *   W [n_items][nclass] int64, present [n_items] uint32 (bit c: W_c > 0): written from three reads of B per class.
+ *   ws = sed_window_activity_ws_bytes(total_label_rows, n_items, nclass) bytes, 8-byte aligned (0 and sed_last_error for
+ *   sizes outside the limits below).
+ * Four launches on `stream` whatever the items' lengths are: the reduction of every tile of 256 rows, a one-workgroup scan
+ * of the tiles' reductions, the tiles' scans behind their carries, and a thread per item for W and present.  No item is
+ * walked by one thread or one workgroup.  Wave steps are shuffles, waves meet in LDS; integer arithmetic only, so the
+ * bytes do not depend on the geometry.
+ *
+ * sed_window_event_starts: one thread per slot j < n_slots reads u[j], v[j], m[j], i = slot_item[j] (int32), start_hi[i] and
+ * the tables above, and writes start3[j] and chosen[j] (int32 each; chosen = -1 for a uniform draw).  The start is found by
+ * bisection of C_c over [0, hi]: it lies in [0, hi] whatever the tables hold.  One launch (none for n_slots == 0).
+ *
+ *   err    one int32, OR-ed, the family's bits:
+ *             8 = nclass > 16 (the mask's width): one launch that raises the bit; nothing else is read or written
+ *            16 = an item whose rows are not 0 <= label_row0[i] < label_row0[i + 1] <= total_label_rows: neither its W /
+ *                 present (activity) nor a slot that names it (starts) is written; a slot_item outside [0, n_items): that
+ *                 slot is not written.  (The item of a row is found by bisection: a label_row0 that is not non-decreasing can
+ *                 moreover leave rows that the bisection assigns to no valid item; they are neither read nor written.)
+ *            32 = start_hi[i] < 0 (activity: the item's W / present are not written), or in sed_window_event_starts
+ *                 start_hi[i] < 0 or start_hi[i] * pool_ratio >= clip_frames[i] - a start the gather's caller would refuse:
+ *                 the slot is not written
+ *          No table content can make a kernel address outside its arguments.  A caller treats the outputs as invalid when
+ *          err != 0.
+ * No host synchronisation, no allocation, no atomics but the OR into err, hipGraph-capturable, identical bytes from call to
+ * call.  Limits, checked before any launch (SED_ERR_BAD_ARG, err untouched; SED_ERR_WORKSPACE for a ws_bytes that is not the
+ * size function's value): no null pointer, 1 <= total_label_rows < 2^31, 1 <= n_items < 2^26, nclass >= 1, T3 >= 1,
+ * pool_ratio >= 1, 0 <= n_slots < 2^31, u, B, W and ws 8-byte aligned.
+ * Not provided: class balance across items, weights from event scores, starts finer than a label frame.               */
+size_t sed_window_activity_ws_bytes(long long total_label_rows, int n_items, int nclass);
+int sed_window_activity(const float* label_pool, const int64_t* label_row0, long long total_label_rows, int n_items,
+                        int nclass, const int32_t* start_hi, int T3, int32_t* A, int64_t* B, int64_t* W,
+                        uint32_t* present, void* ws, size_t ws_bytes, int32_t* err, void* stream);
+int sed_window_event_starts(const uint64_t* u, const int32_t* v, const uint8_t* m, const int32_t* slot_item,
+                            long long n_slots, const int32_t* start_hi, const int32_t* clip_frames, int pool_ratio,
+                            const int64_t* label_row0, long long total_label_rows, int n_items, int nclass, int T3,
+                            const int32_t* A, const int64_t* B, const int64_t* W, const uint32_t* present,
+                            int32_t* start3, int32_t* chosen, int32_t* err, void* stream);
+
 /* ---- validation scoring ------------------------------------------------------------------------
  * Replaces, after get_predictions, the host-side scoring of the epoch loop (baseline/main.py:328-352):
  *   compute_strong_metrics(predictions, valid_synth_df) (evaluation_measures.py:234-246) = sed_eval's
