@@ -21,7 +21,8 @@
 // posteriors and of the attention, fp64 sums in a fixed order, two launches, no timeline.  sed_stitch_weak_backward (behind it) is
 // its transpose: the gradient of a loss on the pooled tags w.r.t. both window tensors, a clear and one tile pass, no atomics.
 // sed_stitch_span_tags pools the same tags per span of span3 frames: the two kernels of sed_stitch_weak over another tile
-// descriptor (StSpanArgs), slots span * ceil(span3 / ST_TILE) + k.
+// descriptor (StSpanArgs), slots span * ceil(span3 / ST_TILE) + k.  sed_stitch_span_tags_backward is the weak backward's two
+// kernels with the row of g / sums looked up per frame (StSpanBwdArgs).
 //
 // Where a tile lives: the tiles of recording r take slots slot0(r) + k, slot0(r) = floor(rec_frame0[r] / ST_TILE) + r.  That
 // is strictly increasing in (r, k) for increasing rec_frame0, needs no table of its own and at most
@@ -767,13 +768,39 @@ __device__ __forceinline__ StTables sb_tables(StTables a) {
     return a;
 }
 
-template <bool VEC>
-__global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_bwd_zero(StWeakBwdArgs wa) {
+// sed_stitch_span_tags_backward runs the same two kernels (Args = StSpanBwdArgs): the tiles stay the recordings' - a window
+// element's owner is a timeline frame whatever the spans are - and only the ROW that frame u of recording r takes g, num and den
+// from changes, from r to rec_span0[r] + u / span3.  A recording's span offsets are validated as the forward validates them
+// (sb_rec_bad) before any is used as an index: a row is then < total_spans.
+struct StSpanBwdArgs {
+    StWeakBwdArgs w;         // sums [total_spans][NC][2], g_weak [total_spans][NC]
+    const int64_t* rec_span0;
+    long long total_spans;
+    int span3;
+};
+__host__ __device__ __forceinline__ const StWeakBwdArgs& sb_args(const StWeakBwdArgs& a) { return a; }
+__host__ __device__ __forceinline__ const StWeakBwdArgs& sb_args(const StSpanBwdArgs& a) { return a.w; }
+
+// What keeps recording r (R = st_rec of it) out of the backward: R.bad, or 16 for span offsets the forward rejects.
+__device__ __forceinline__ int sb_rec_bad(const StWeakBwdArgs&, const StRec& R, int) { return R.bad; }
+__device__ __forceinline__ int sb_rec_bad(const StSpanBwdArgs& sa, const StRec& R, int r) {
+    if (R.bad) return R.bad;
+    const long long p0 = sa.rec_span0[r], p1 = sa.rec_span0[r + 1];
+    const long long n_spans = ((long long)R.L3 + sa.span3 - 1) / sa.span3;
+    return (p0 < 0 || p1 > sa.total_spans || p1 < p0 || p1 - p0 != n_spans) ? 16 : 0;   // (in this order: no overflow)
+}
+// The row of g_weak / sums that frame u of (valid) recording r reads.
+__device__ __forceinline__ size_t sb_row(const StWeakBwdArgs&, int r, int) { return (size_t)r; }
+__device__ __forceinline__ size_t sb_row(const StSpanBwdArgs& sa, int r, int u) { return (size_t)(sa.rec_span0[r] + u / sa.span3); }
+
+template <bool VEC, class Args>
+__global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_bwd_zero(Args args) {
+    const StWeakBwdArgs& wa = sb_args(args);
     const StTables a = sb_tables(wa.t);
     const size_t i0 = (size_t)blockIdx.x * ST_THREADS + threadIdx.x, stride = (size_t)gridDim.x * ST_THREADS;
     for (size_t r = i0; r < (size_t)a.n_rec; r += stride) {
-        const StRec R = st_rec(a, (int)r);
-        if (R.bad) atomicOr(a.err, R.bad);
+        const int bad = sb_rec_bad(args, st_rec(a, (int)r), (int)r);
+        if (bad) atomicOr(a.err, bad);
     }
     const long long wt = a.rec_win0[a.n_rec];
     if (wt <= 0) return;
@@ -792,8 +819,9 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_bwd_zero(StWeakBwdAr
     }
 }
 
-template <bool VEC>
-__global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_bwd_tile(StWeakBwdArgs wa) {
+template <bool VEC, class Args>
+__global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_bwd_tile(Args args) {
+    const StWeakBwdArgs& wa = sb_args(args);
     const StTables a = sb_tables(wa.t);
     const int tid = threadIdx.x, NC = a.NC, T3 = a.T3, hop3 = a.hop3;
     constexpr int W = VEC ? 4 : 1;
@@ -801,14 +829,18 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_bwd_tile(StWeakBwdAr
     for (long long g = blockIdx.x; g < a.n_slots; g += gridDim.x) {
         StTile T;
         if (!st_tile(a, g, T)) continue;
+        if constexpr (std::is_same<Args, StSpanBwdArgs>::value) {
+            if (sb_rec_bad(args, T.R, T.r)) continue;
+        }
         for (int it = tid; it < (T.e - T.s) * G; it += ST_THREADS) {
             const int fl = it / G, q = it - fl * G, u = T.s + fl, col = W * q;
             const f32x4 p = st_blend<VEC>(a, wa.win_strong, T.R, u, q);
             const f32x4 at = st_blend<VEC>(a, wa.win_att, T.R, u, q);
+            const size_t row = sb_row(args, T.r, u);
             double dP[W], dA[W];
 #pragma unroll
             for (int k = 0; k < W; ++k) {
-                const size_t rc = (size_t)T.r * NC + col + k;
+                const size_t rc = row * NC + col + k;
                 const double gk = (double)wa.g_weak[rc], num = wa.sums[2 * rc], den = wa.sums[2 * rc + 1];
                 const double t = num / den;
                 dP[k] = (gk * (double)at[k]) / den;
@@ -840,6 +872,23 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_bwd_tile(StWeakBwdAr
     }
 }
 
+// The two launches of sed_stitch_weak_backward (Args = StWeakBwdArgs) and of sed_stitch_span_tags_backward (StSpanBwdArgs).
+template <class Args>
+static int sb_launch(const Args& args, void* stream) {
+    const StWeakBwdArgs& wa = sb_args(args);
+    const bool vec = wa.t.NC % 4 == 0 && ((uintptr_t)wa.win_strong % 16) == 0 && ((uintptr_t)wa.win_att % 16) == 0 &&
+                     ((uintptr_t)wa.d_win_strong % 16) == 0 && ((uintptr_t)wa.d_win_att % 16) == 0;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(SB_GRID), thr256(ST_THREADS);
+    if (vec) hipLaunchKernelGGL((k_stitch_weak_bwd_zero<true, Args>), grid, thr256, 0, st, args);
+    else hipLaunchKernelGGL((k_stitch_weak_bwd_zero<false, Args>), grid, thr256, 0, st, args);
+    SED_CHECK_LAUNCH();
+    if (vec) hipLaunchKernelGGL((k_stitch_weak_bwd_tile<true, Args>), grid, thr256, 0, st, args);
+    else hipLaunchKernelGGL((k_stitch_weak_bwd_tile<false, Args>), grid, thr256, 0, st, args);
+    SED_CHECK_LAUNCH();
+    return SED_OK;
+}
+
 extern "C" int sed_stitch_weak_backward(const float* win_strong, const float* win_att, const int32_t* rec_win0,
                                         const int64_t* rec_frame0, int n_rec, int T3, int NC, int hop3, int weighting,
                                         const double* sums, const float* g_weak, float* d_win_strong, float* d_win_att,
@@ -850,15 +899,23 @@ extern "C" int sed_stitch_weak_backward(const float* win_strong, const float* wi
     SED_TRY(st_front(what, rec_win0, rec_frame0, err, n_rec, T3, NC, hop3, weighting, 1, 31, &t));
     ST_NEED(((uintptr_t)sums % 8) == 0, "sums must be 8-byte aligned");
     const StWeakBwdArgs wa = {t, win_strong, win_att, sums, g_weak, d_win_strong, d_win_att};
-    const bool vec = NC % 4 == 0 && ((uintptr_t)win_strong % 16) == 0 && ((uintptr_t)win_att % 16) == 0 &&
-                     ((uintptr_t)d_win_strong % 16) == 0 && ((uintptr_t)d_win_att % 16) == 0;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid(SB_GRID), thr256(ST_THREADS);
-    if (vec) hipLaunchKernelGGL((k_stitch_weak_bwd_zero<true>), grid, thr256, 0, st, wa);
-    else hipLaunchKernelGGL((k_stitch_weak_bwd_zero<false>), grid, thr256, 0, st, wa);
-    SED_CHECK_LAUNCH();
-    if (vec) hipLaunchKernelGGL((k_stitch_weak_bwd_tile<true>), grid, thr256, 0, st, wa);
-    else hipLaunchKernelGGL((k_stitch_weak_bwd_tile<false>), grid, thr256, 0, st, wa);
-    SED_CHECK_LAUNCH();
-    return SED_OK;
+    return sb_launch(wa, stream);
+}
+
+// ---- backward through the span tags (sed_stitch_span_tags_backward) -----------------------------------------------------------
+extern "C" int sed_stitch_span_tags_backward(const float* win_strong, const float* win_att, const int32_t* rec_win0,
+                                             const int64_t* rec_frame0, const int64_t* rec_span0, long long total_spans, int n_rec,
+                                             int T3, int NC, int hop3, int weighting, int span3, const double* sums,
+                                             const float* g_tags, float* d_win_strong, float* d_win_att, int32_t* err,
+                                             void* stream) {
+    const char* what = "sed_stitch_span_tags_backward";
+    ST_NEED(win_strong && win_att && rec_win0 && rec_frame0 && rec_span0 && sums && g_tags && d_win_strong && d_win_att && err,
+            "null argument");
+    StTables t;
+    SED_TRY(st_front(what, rec_win0, rec_frame0, err, n_rec, T3, NC, hop3, weighting, 1, 31, &t));
+    ST_NEED(span3 >= 1 && total_spans >= n_rec && total_spans < (1ll << 31) && total_spans * NC < (1ll << 31),
+            "need span3 >= 1, n_rec <= total_spans and total_spans * NC < 2^31");
+    ST_NEED(((uintptr_t)sums % 8) == 0, "sums must be 8-byte aligned");
+    const StSpanBwdArgs sa = {{t, win_strong, win_att, sums, g_tags, d_win_strong, d_win_att}, rec_span0, total_spans, span3};
+    return sb_launch(sa, stream);
 }

@@ -715,6 +715,85 @@ def stitch_span_tags(win_strong, win_att, rec_win0, rec_frame0, total_frames, ho
             "err": err}
 
 
+class _PooledSpanTags(torch.autograd.Function):
+    """forward = sed_stitch_span_tags with the (num, den) sums kept, backward = sed_stitch_span_tags_backward."""
+
+    @staticmethod
+    def forward(ctx, win_strong, win_att, rec_win0, rec_frame0, rec_span0, total, total_spans, hop3, weighting, span3, ws_bytes,
+                err):
+        l = _lib.lib()
+        n_win, T3, NC = win_strong.shape
+        n_rec, dev = rec_win0.numel() - 1, win_strong.device
+        tags = torch.empty(total_spans, NC, dtype=torch.float32, device=dev)
+        sums = torch.empty(total_spans, NC, 2, dtype=torch.float64, device=dev)
+        ws = _lib.scratch(ws_bytes, dev)
+        _lib.check(l.sed_stitch_span_tags(_lib.ptr(win_strong), _lib.ptr(win_att), _lib.ptr(rec_win0), _lib.ptr(rec_frame0),
+                                          _lib.ptr(rec_span0), total, total_spans, n_rec, T3, NC, hop3, weighting, span3,
+                                          _lib.ptr(tags), _lib.ptr(sums), _lib.ptr(ws), ws.numel(), _lib.ptr(err),
+                                          _lib.stream_ptr()), "sed_stitch_span_tags")
+        ctx.save_for_backward(win_strong, win_att, rec_win0, rec_frame0, rec_span0, sums)
+        ctx.total_spans, ctx.hop3, ctx.weighting, ctx.span3, ctx.err = total_spans, hop3, weighting, span3, err
+        return tags
+
+    @staticmethod
+    def backward(ctx, g_tags):
+        l = _lib.lib()
+        win_strong, win_att, rec_win0, rec_frame0, rec_span0, sums = ctx.saved_tensors
+        n_win, T3, NC = win_strong.shape
+        g_tags = g_tags.contiguous().float()
+        d_strong, d_att = torch.empty_like(win_strong), torch.empty_like(win_att)
+        _lib.check(l.sed_stitch_span_tags_backward(_lib.ptr(win_strong), _lib.ptr(win_att), _lib.ptr(rec_win0),
+                                                   _lib.ptr(rec_frame0), _lib.ptr(rec_span0), ctx.total_spans,
+                                                   rec_win0.numel() - 1, T3, NC, ctx.hop3, ctx.weighting, ctx.span3,
+                                                   _lib.ptr(sums), _lib.ptr(g_tags), _lib.ptr(d_strong), _lib.ptr(d_att),
+                                                   _lib.ptr(ctx.err), _lib.stream_ptr()), "sed_stitch_span_tags_backward")
+        return (d_strong, d_att) + (None,) * 10
+
+
+def pooled_span_tags(win_strong, win_att, rec_win0, rec_frame0, total_frames, hop3, span3, weighting="taper", n_win=None,
+                     rec_frame0_host=None, span_tables=None):
+    """``stitch_span_tags``'s span-level tags as a differentiable function of both window tensors: an autograd node whose
+    forward is ``sed_stitch_span_tags`` (its fp64 sums are kept) and whose backward is ``sed_stitch_span_tags_backward``.
+    Arguments and host checks as for ``pooled_tags`` (the window tensors must hold exactly ``rec_win0[-1]`` windows; ``n_win``:
+    that count where the caller has it on the host), ``span3`` / ``rec_frame0_host`` as for ``stitch_span_tags``: the span
+    table comes from ``span_table`` (``span3`` clamped to the longest recording) and is copied to the device - unless the
+    caller has one for exactly these recordings already, ``span_tables = (rec_span0 host, rec_span0 on the device)``
+    (``train_span_tags`` prepares its batches' once per epoch); it is then checked against the lengths on the host and
+    nothing is copied.  Returns a dict like ``stitch_span_tags``'s: ``tags`` [total_spans, nclass] float32 (differentiable),
+    ``rec_span0``, ``rec_span0_host``, ``total_spans``, ``span3`` (clamped), ``err`` [1] int32 on the device, OR-ed into by
+    forward and backward (``STITCH_ERR_BITS`` 16 / 32: tags and gradients are invalid when it is nonzero).  With
+    ``rec_frame0_host`` nothing synchronises."""
+    total, hop3, weighting = _weak_inputs("pooled_span_tags", win_strong, win_att, rec_win0, total_frames, hop3, weighting, n_win)
+    if rec_win0.dtype != torch.int32 or rec_frame0.dtype != torch.int64 or rec_frame0.numel() != rec_win0.numel() or \
+            rec_win0.device != win_strong.device or rec_frame0.device != win_strong.device:
+        raise ValueError("rec_win0 [n_rec + 1] int32 and rec_frame0 [n_rec + 1] int64 must be on the window tensors' device")
+    if rec_frame0_host is None:
+        rec_frame0_host = rec_frame0.cpu().numpy()
+    L3s = np.diff(np.asarray(rec_frame0_host, dtype=np.int64).reshape(-1))
+    n_rec, dev = rec_win0.numel() - 1, win_strong.device
+    if L3s.size != n_rec:
+        raise ValueError(f"rec_frame0_host describes {L3s.size} recordings, the tables {n_rec}")
+    if span_tables is None:
+        host, rec_span0, total_spans, span3 = span_table(L3s, span3, dev)
+    else:
+        host, _, total_spans, span3 = span_table(L3s, span3)
+        given, rec_span0 = span_tables
+        if not np.array_equal(np.asarray(given, dtype=np.int64).reshape(-1), host):
+            raise ValueError("span_tables is not span_table's for these recordings and this span3")
+        if rec_span0.dtype != torch.int64 or rec_span0.numel() != n_rec + 1 or rec_span0.device != dev:
+            raise ValueError("span_tables' device table must be [n_rec + 1] int64 on the window tensors' device")
+    NC = win_strong.shape[2]
+    l = _lib.lib()
+    ws_bytes = l.sed_stitch_span_tags_ws_bytes(total, total_spans, n_rec, NC, span3)
+    if ws_bytes == 0:
+        raise ValueError(f"sed_stitch_span_tags_ws_bytes: {l.sed_last_error().decode()}")
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    tags = _PooledSpanTags.apply(win_strong.contiguous().float(), win_att.contiguous().float(), rec_win0.contiguous(),
+                                 rec_frame0.contiguous(), rec_span0.contiguous(), total, total_spans, hop3, weighting, span3,
+                                 ws_bytes, err)
+    return {"tags": tags, "rec_span0": rec_span0, "rec_span0_host": host, "total_spans": total_spans, "span3": span3, "err": err}
+
+
 def events_tag_scores(out_or_table, tags, rec_span0, span3, n_rec, nclass, err=None):
     """``sed_events_tag_scores``: per event of a CSR table on the device the largest non-NaN span tag among the spans it
     touches (``tags`` [total_spans, nclass] cuda float32 and ``rec_span0`` [n_rec + 1] int64 as ``stitch_span_tags`` returns

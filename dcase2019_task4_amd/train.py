@@ -947,3 +947,119 @@ def train_recording_tags(long_set, tags, model, optimizer, epoch, ema_model=None
     if log is not None:
         log('Epoch: {}\tTime {:.2f}\trecording_tag_loss {:.4g}'.format(epoch, time.time() - start, mean))
     return mean
+
+
+# ---- training on span-level tags -----------------------------------------------------------------------------------------------
+def span_tag_plan(rec_win0_host, rec_frame0_host, span_tags, max_windows, span3):
+    """The host-side plan of one ``train_span_tags`` epoch, nothing touches a GPU: the runs of ``recording_tag_runs``, the span
+    table of the whole set and, per run, the count of KNOWN (span, class) pairs - a NaN target is unknown.  Returns a dict:
+    ``runs``, ``rec_span0`` (host int64 [n_rec + 1]), ``total_spans``, ``span3`` (clamped as ``inference.span_table`` clamps
+    it), ``targets`` float32 [total_spans, nclass] (the NaNs replaced by 0), ``known`` float32 (1 where the target is known),
+    ``counts`` int64 [n_runs] and ``ran`` (the runs with at least one known pair: the others are skipped, no forward and no
+    optimizer step).  ValueError for targets of another shape than the span table's or outside [0, 1]."""
+    from .inference import span_table
+    from .longrec import recording_tag_runs
+    rec_win0_host, rec_frame0_host = np.asarray(rec_win0_host, dtype=np.int64), np.asarray(rec_frame0_host, dtype=np.int64)
+    rec_span0, _, total_spans, span3 = span_table(np.diff(rec_frame0_host), span3)
+    tags_np = span_tags.detach().cpu().numpy() if torch.is_tensor(span_tags) else np.asarray(span_tags)
+    if tags_np.ndim != 2 or tags_np.shape[0] != total_spans:
+        raise ValueError(f"span_tags must be [total_spans = {total_spans}, nclass] for spans of {span3} label frames, got "
+                         f"{tags_np.shape}")
+    known = ~np.isnan(tags_np)
+    if not ((tags_np[known] >= 0) & (tags_np[known] <= 1)).all():
+        raise ValueError("span_tags must lie in [0, 1] (NaN: unknown)")
+    runs = recording_tag_runs(np.diff(rec_win0_host), max_windows)
+    counts = np.asarray([int(known[rec_span0[r0]:rec_span0[r1]].sum()) for r0, r1 in runs], dtype=np.int64)
+    return {"runs": runs, "rec_span0": rec_span0, "total_spans": total_spans, "span3": span3,
+            "targets": np.where(known, tags_np, 0).astype(np.float32), "known": known.astype(np.float32), "counts": counts,
+            "ran": [k for k in range(len(runs)) if counts[k] > 0]}
+
+
+def span_tags_loss(long_set, span_tags_dev, known_dev, model, run, tables, span3, weighting="taper"):
+    """The loss of one ``train_span_tags`` batch - the recordings ``run = (r0, r1)`` of ``long_set`` - with its graph: the run's
+    windows through the set's eval gather, ``model(x, return_attention=True)``, ``inference.pooled_span_tags``, then the
+    ``binary_cross_entropy`` summed over the run's KNOWN (span, class) pairs and divided by their count.  ``span_tags_dev`` /
+    ``known_dev`` [total_spans of the set, nclass] float32: the targets (0 where unknown) and the 0 / 1 mask of the known
+    pairs; ``tables = (k, at, rec_win0, rec_frame0, rec_span0, rec_span0_host, counts)``: ``tag_batches``' tables, the runs'
+    rebased span tables concatenated the same way, the set's span offsets and the runs' known-pair counts on the host.
+    The sum is taken as the masked mean over all the run's pairs times pairs / known (a host number): with every pair known
+    that is ``recording_tags_loss``'s mean BCE operation for operation.  Returns ``(loss, err)``; nothing synchronises."""
+    from .inference import pooled_span_tags
+    r0, r1 = run
+    k, at, win0_all, frame0_all, span0_all, span0_host, counts = tables
+    w0, w1 = int(long_set.rec_win0_host[r0]), int(long_set.rec_win0_host[r1])
+    frames_host = long_set.rec_frame0_host[r0:r1 + 1] - long_set.rec_frame0_host[r0]
+    g0, g1 = int(span0_host[r0]), int(span0_host[r1])
+    x = long_set.eval_batch(w0, w1 - w0)
+    strong, _, att = model(x, return_attention=True)
+    out = pooled_span_tags(strong, att, win0_all[at[k]:at[k + 1]], frame0_all[at[k]:at[k + 1]], int(frames_host[-1]),
+                           long_set.hop3, span3, weighting, n_win=w1 - w0, rec_frame0_host=frames_host,
+                           span_tables=(span0_host[r0:r1 + 1] - g0, span0_all[at[k]:at[k + 1]]))
+    target, known = span_tags_dev[g0:g1], known_dev[g0:g1]
+    loss = torch.nn.functional.binary_cross_entropy(out["tags"], target, weight=known)
+    return loss * (target.numel() / int(counts[k])), out["err"]
+
+
+def train_span_tags(long_set, span_tags, model, optimizer, epoch, tag_span=None, span3=None, ema_model=None, max_windows=64,
+                    seed=0, log=None):
+    """One epoch of training on SPAN-LEVEL tags: ``train_recording_tags`` with one target vector per span of every recording
+    instead of one per recording - a long recording assembled from weakly labelled clips, or coarse annotations of an hour
+    of audio.  ``span_tags`` [total_spans, nclass] floats in [0, 1], the rows in ``inference.span_table(long_set, span3)``'s
+    order (its total must match, ``ValueError`` otherwise); a NaN target is "unknown" and that (span, class) pair takes no
+    part.  Exactly one of ``tag_span`` (seconds, rounded down to label frames by ``inference.tag_span_frames``) and
+    ``span3`` (label frames) gives the span length; it is clamped to the longest recording.
+
+    The loss is on ``inference.pooled_span_tags``: its gradient reaches the windows through ``sed_stitch_span_tags_backward``
+    and ``sed_crnn_backward_att``, localised to the span - a class absent from a span pushes that span's posteriors down.
+    Batches, their order from (``seed``, ``epoch``), the optimizer and EMA steps (``epoch * n_batches + i``, ``i`` the batch's
+    place in that order) and the end-of-epoch checks are ``train_recording_tags``'s; a batch without a known pair is skipped
+    (no forward, no optimizer or EMA step - the host knows from the targets).  Per batch the BCE is summed over its known
+    pairs and divided by their count.  Nothing synchronises inside the epoch: the masks, counts and span tables are prepared
+    once at its start, the kernels' error word is read once at its end (nonzero raises ``SedError``), with the mean loss over
+    the batches that ran, which is returned.  A recording with more than ``max_windows`` windows raises ``ValueError``."""
+    from .inference import _Cfg, tag_span_frames
+    from .longrec import LongRecordingSet
+    if not isinstance(long_set, LongRecordingSet):
+        raise ValueError("train_span_tags needs a LongRecordingSet")
+    if (tag_span is None) == (span3 is None):
+        raise ValueError("give exactly one of tag_span (seconds) and span3 (label frames)")
+    if span3 is None:
+        span3 = tag_span_frames(tag_span, long_set.pooling_time_ratio * _Cfg.hop_length / _Cfg.sample_rate)
+    plan = span_tag_plan(long_set.rec_win0_host, long_set.rec_frame0_host, span_tags, max_windows, span3)
+    if not plan["ran"]:
+        raise ValueError("span_tags has no known target: every entry is NaN")
+    runs, at, win0_all, frame0_all = long_set.tag_batches(max_windows)
+    assert runs == plan["runs"]
+    order = _tag_batch_order(len(runs), seed, epoch)
+    start = time.time()
+    dev = long_set.device
+    span0_host, span3 = plan["rec_span0"], plan["span3"]
+    span0_all = torch.from_numpy(np.concatenate([span0_host[r0:r1 + 1] - span0_host[r0] for r0, r1 in runs])).to(dev)
+    tags_dev, known_dev = torch.from_numpy(plan["targets"]).to(dev), torch.from_numpy(plan["known"]).to(dev)
+    model.to(dev)
+    model.train()
+    n_batches, n_ran = len(runs), 0
+    loss_sum = torch.zeros((), dtype=torch.float32, device=dev)
+    err_all = torch.zeros(1, dtype=torch.int32, device=dev)
+    for i, k in enumerate(order):
+        if plan["counts"][k] == 0:
+            continue
+        optimizer.zero_grad()
+        loss, err = span_tags_loss(long_set, tags_dev, known_dev, model, runs[k],
+                                   (int(k), at, win0_all, frame0_all, span0_all, span0_host, plan["counts"]), span3)
+        loss.backward()
+        optimizer.step()
+        if ema_model is not None:
+            update_ema_variables(model, ema_model, 0.999, int(epoch) * n_batches + i)
+        loss_sum += loss.detach()
+        err_all |= err
+        n_ran += 1
+    mean = float(loss_sum.item()) / n_ran
+    bits = int(err_all.item())
+    if bits:
+        raise _lib.SedError(f"train_span_tags: the pooling kernels raised error bits {bits} (16: malformed tables, 32: a "
+                            "recording its windows do not cover)")
+    assert not (mean != mean or mean > 1e5), 'Loss explosion: {}'.format(mean)
+    if log is not None:
+        log('Epoch: {}\tTime {:.2f}\tspan_tag_loss {:.4g}'.format(epoch, time.time() - start, mean))
+    return mean

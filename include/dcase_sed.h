@@ -871,12 +871,39 @@ int sed_stitch_weak_backward(const float* win_strong, const float* win_att, cons
  *      decode", which cuts events at span boundaries.  By hand: span3 = 4, one class, tags (0.9, 0.1), min_tag 0.5, one
  *      decoded event [2, 7).  The gate keeps [2, 7) whole (it touches span 0); masking the posteriors of span 1 first and
  *      decoding would give [2, 4).
- * Not provided: a backward through the span tags, overlapping or per-recording span lengths, masking in the frame domain. */
+ *
+ * Backward through the span tags: sed_stitch_span_tags_backward, the gradient of a loss on tags[g, c] w.r.t. both window
+ * tensors.  It is sed_stitch_weak_backward's definition with ONE change: timeline frame u of recording r takes g, num and den
+ * from row = rec_span0[r] + u / span3 of g_tags / sums, not from row r.  The same individually rounded fp64 operations in the
+ * same order (t = num / den, dP = (g * A) / den, dA = (g * (P - t)) / den, outputs (float)((dP * w) / W), (float)((dA * w) / W)).
+ *   sums   [total_spans][NC][2] fp64  the (num, den) pairs sed_stitch_span_tags returned for the same inputs
+ *   g_tags [total_spans][NC]    fp32  dLoss/dtags
+ * EVERY element of both outputs in [0, rec_win0[n_rec]) is written, +0.0f in the tails u >= L3_r and for rejected recordings.
+ * Consequences (tests pin them): with one span per recording (span3 >= max L3, rec_span0 = 0 .. n_rec) the outputs are
+ * byte-identical to sed_stitch_weak_backward's on the same sums; a span's gradient does not depend on the span's position,
+ * its recording or the tiling; a g_tags row of zeros gives zeros (of either sign) on that span's frames.  The gradient is
+ * that of the blended values as computed; against the float64 central difference an element is within
+ * 5e-6 |fd| + 1e-9 + 2^-22 |g| (w / W) / den (tests/test_span_tags_bwd_cpu.py: a short span's den is small, and the fp32
+ * rounding of the blended P and A enters dA absolutely).
+ *   err  one int32, OR-ed (zero it first): 16 = malformed rec_win0 / rec_frame0 / rec_span0 - also a rec_span0 that disagrees
+ *        with ceil(L3_r / span3) or reaches beyond total_spans, checked per recording in the clear pass - , 32 = a recording
+ *        whose windows do not cover it.  Such a recording's windows are left +0.0f; no row outside [0, total_spans) is read.
+ * Two launches on `stream` (clear, then the tile pass over the recordings' tiles: sed_stitch_weak_backward's two kernels with
+ * the row lookup).  No atomics, no workspace, no host synchronisation, no allocation, hipGraph-capturable.  16-byte accesses
+ * when NC % 4 == 0 and all four window tensors are 16-byte aligned, a scalar path otherwise (identical bytes).
+ * Limits, checked before any launch (SED_ERR_BAD_ARG, outputs untouched): NC <= 16, 1 <= hop3 <= T3 <= 4096, span3 >= 1,
+ * n_rec <= total_spans, total_spans * NC < 2^31, sums 8-byte aligned, no null pointer.
+ *
+ * Not provided: overlapping or per-recording span lengths, masking in the frame domain. */
 size_t sed_stitch_span_tags_ws_bytes(long long total_frames, long long total_spans, int n_rec, int nclass, int span3);
 int sed_stitch_span_tags(const float* win_strong, const float* win_att, const int32_t* rec_win0, const int64_t* rec_frame0,
                          const int64_t* rec_span0, long long total_frames, long long total_spans, int n_rec, int T3, int NC,
                          int hop3, int weighting, int span3, float* tags, double* sums, void* ws, size_t ws_bytes, int32_t* err,
                          void* stream);
+int sed_stitch_span_tags_backward(const float* win_strong, const float* win_att, const int32_t* rec_win0,
+                                  const int64_t* rec_frame0, const int64_t* rec_span0, long long total_spans, int n_rec, int T3,
+                                  int NC, int hop3, int weighting, int span3, const double* sums, const float* g_tags,
+                                  float* d_win_strong, float* d_win_att, int32_t* err, void* stream);
 int sed_events_tag_scores(const float* tags, long long total_spans, const int64_t* rec_span0, int span3, int n_rec, int NC,
                           const int64_t* ev_ptr, const int32_t* ev_pairs, long long pairs_capacity, long long n_cols,
                           float* tag_score, int32_t* err, void* stream);

@@ -57,6 +57,13 @@ workloads at the same 50 thresholds with PSDS:
   and the fp64 pooling - the only route to the gradient before it - with the largest difference of the two routes' gradients;
   on 100x3min one train.train_recording_tags epoch against the same batches with a window-level loss, alternated.
 
+--span-tag-train measures training on span-level tags (profiles/long_span_tag_train.json), same workloads and hop, tag_span 10 s:
+  sed_stitch_span_tags_backward alone, and the forward + backward pair, against a torch-autograd restatement of the blend
+    (index_add_) and a per-span fp64 segment_reduce - the only route to the gradient before it - with the largest difference of
+    the two routes' gradients;
+  the same call at one span per recording beside sed_stitch_weak_backward on the same sums (and whether their bytes are equal);
+  on 100x3min one train.train_span_tags epoch against train.train_recording_tags over the same batches, alternated.
+
 --error-rate measures the overall error rate with substitutions (the "long" key of profiles/error_rate.json), same workloads,
 references and hop as --scoring:
   validate_long(..., error_rate=True) against the same run's validate_long(...) at one operating point and at 50, the two legs
@@ -105,7 +112,7 @@ thresholds as --scoring, min_event_length 0.25 s and min_event_gap 0.15 s at eve
   pseudo_label into a WindowedFeatureSet over the same recordings against the same run's get_long_predictions with the same
     arguments, alternated, --rounds rounds; a difference counts only outside the larger (max - min) of the two legs.
 
-Usage: python tools/long_bench.py [--scoring | --sweep | --weak | --tag-train | --error-rate | --hysteresis | --process | --scores | --span-tags | --rasterize] [--rounds 5] [--decode-reps 30] [--out profiles/long_inference.json]"""
+Usage: python tools/long_bench.py [--scoring | --sweep | --weak | --tag-train | --span-tag-train | --error-rate | --hysteresis | --process | --scores | --span-tags | --rasterize] [--rounds 5] [--decode-reps 30] [--out profiles/long_inference.json]"""
 import argparse
 import json
 import os
@@ -1262,6 +1269,157 @@ def tag_train_workload(name, model, rounds, reps):
     return out
 
 
+def span_tag_train_workload(name, model, rounds, reps, tag_span=10.0):
+    """--span-tag-train: (a) sed_stitch_span_tags_backward alone, and forward + backward, at ``tag_span`` seconds against the
+    torch-autograd restatement of the blend (index_add_) and a per-span fp64 segment_reduce - the only route to this gradient
+    before it; (b) the same call at one span per recording beside sed_stitch_weak_backward on the same sums; (c) where every
+    recording fits one forward (100x3min): one train_span_tags epoch against train_recording_tags over the same batches."""
+    from dcase2019_task4_amd import train
+    n_rec, per = WORKLOADS[name]
+    recs = recordings(n_rec, per)
+    sc = scaler_of(recs[0])
+    ls = inference.LongRecordingSet.from_arrays(recs, T, scaler=sc, filenames=[f"{name}_{r}.wav" for r in range(n_rec)])
+    cfg = inference._Cfg
+    span3 = inference.tag_span_frames(tag_span, POOL * cfg.hop_length / cfg.sample_rate)
+    out = {"recordings": n_rec, "windows": ls.n_clips, "timeline_frames": ls.total_frames, "hop3": ls.hop3, "T3": ls.T3,
+           "tag_span_s": tag_span}
+    model.eval()
+    win_strong, win_att = inference.long_window_posteriors(model, ls, NCLASS, BATCH, want_attention=True)
+    l, dev, ptr = _lib.lib(), win_strong.device, _lib.ptr
+    total, T3, hop3 = ls.total_frames, ls.T3, ls.hop3
+    d_s, d_a = torch.empty_like(win_strong), torch.empty_like(win_att)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def span_calls(span3):
+        """(forward, backward, state) of the two C calls at this span length, on buffers of their own."""
+        host, span0, n_spans, span3 = inference.span_table(ls, span3)
+        g = torch.randn(n_spans, NCLASS, device=dev, generator=torch.Generator(dev).manual_seed(1))
+        tags = torch.empty(n_spans, NCLASS, device=dev)
+        sums = torch.empty(n_spans, NCLASS, 2, dtype=torch.float64, device=dev)
+        ws = torch.empty(l.sed_stitch_span_tags_ws_bytes(total, n_spans, n_rec, NCLASS, span3), dtype=torch.uint8, device=dev)
+
+        def fwd():
+            _lib.check(l.sed_stitch_span_tags(ptr(win_strong), ptr(win_att), ptr(ls.rec_win0), ptr(ls.rec_frame0), ptr(span0), total,
+                                              n_spans, n_rec, T3, NCLASS, hop3, 1, span3, ptr(tags), ptr(sums), ptr(ws), ws.numel(),
+                                              ptr(err), _lib.stream_ptr()), "sed_stitch_span_tags")
+
+        def bwd():
+            _lib.check(l.sed_stitch_span_tags_backward(ptr(win_strong), ptr(win_att), ptr(ls.rec_win0), ptr(ls.rec_frame0), ptr(span0),
+                                                       n_spans, n_rec, T3, NCLASS, hop3, 1, span3, ptr(sums), ptr(g), ptr(d_s),
+                                                       ptr(d_a), ptr(err), _lib.stream_ptr()), "sed_stitch_span_tags_backward")
+        return fwd, bwd, {"host": host, "n_spans": n_spans, "span3": span3, "g": g, "sums": sums}
+    fused_fwd, fused_bwd, sp = span_calls(span3)
+    out["span3"], out["total_spans"] = sp["span3"], sp["n_spans"]
+    # the restatement's index tables (tag_train_workload's), and the span lengths in timeline order
+    rec_of_win = np.repeat(np.arange(n_rec), np.diff(ls.rec_win0_host))
+    j = np.arange(ls.n_clips) - ls.rec_win0_host[rec_of_win]
+    v = np.arange(T3)
+    u = j[:, None] * hop3 + v[None, :]
+    L3s = np.diff(ls.rec_frame0_host)
+    ok = u < L3s[rec_of_win][:, None]
+    frame = torch.from_numpy((ls.rec_frame0_host[rec_of_win][:, None] + u)[ok]).to(dev)
+    wt = torch.from_numpy(np.broadcast_to(np.minimum(v + 1, T3 - v).astype(np.float32), u.shape)[ok]).to(dev)
+    keep = torch.from_numpy(np.flatnonzero(ok.reshape(-1))).to(dev)
+    lengths = torch.from_numpy(np.concatenate([np.minimum(sp["span3"], L - np.arange(0, L, sp["span3"])) for L in L3s])).to(dev)
+    assert lengths.numel() == sp["n_spans"] and int(lengths.sum().item()) == total
+    wsum = torch.zeros(total, device=dev).index_add_(0, frame, wt)
+    state = {}
+
+    def composed_fwd():
+        ps, pa = win_strong.detach().requires_grad_(True), win_att.detach().requires_grad_(True)
+        tl = [torch.zeros(total, NCLASS, device=dev).index_add_(0, frame, wt[:, None] * x.reshape(-1, NCLASS)[keep]) / wsum[:, None]
+              for x in (ps, pa)]
+        P, A = tl[0].double(), tl[1].double()
+        num = torch.segment_reduce(P * A, "sum", lengths=lengths, axis=0, unsafe=True)
+        den = torch.segment_reduce(A, "sum", lengths=lengths, axis=0, unsafe=True)
+        state["in"], state["loss"] = (ps, pa), (sp["g"] * (num / den).float()).sum()
+
+    def composed_bwd():
+        state["grads"] = torch.autograd.grad(state["loss"], state["in"], retain_graph=True)
+
+    def both(a, b):
+        def call():
+            a()
+            b()
+        return call
+    fused_fwd()
+    composed_fwd()
+    out["sed_stitch_span_tags_backward_alone"] = event_ms(fused_bwd, reps)
+    out["composed_backward_alone"] = event_ms(composed_bwd, reps)
+    out["fused_forward_plus_backward"] = event_ms(both(fused_fwd, fused_bwd), reps)
+    out["composed_forward_plus_backward"] = event_ms(both(composed_fwd, composed_bwd), reps)
+    assert int(err.item()) == 0
+    out["max_abs_difference_of_the_two_routes"] = {"d_win_strong": float((d_s - state["grads"][0]).abs().max().item()),
+                                                   "d_win_att": float((d_a - state["grads"][1]).abs().max().item()),
+                                                   "largest_gradient": [float(x.abs().max().item()) for x in state["grads"]]}
+    for a, b, key in (("sed_stitch_span_tags_backward_alone", "composed_backward_alone", "backward"),
+                      ("fused_forward_plus_backward", "composed_forward_plus_backward", "forward_plus_backward")):
+        band = max(x["spread"] * x["median_ms"] for x in (out[a], out[b]))
+        out[key + "_composed_minus_fused_ms"] = out[b]["median_ms"] - out[a]["median_ms"]
+        out[key + "_larger_max_minus_min_ms"] = band
+        out[key + "_fused_faster"] = bool(out[key + "_composed_minus_fused_ms"] > band)
+    del state
+    # ---- (b) one span per recording, beside sed_stitch_weak_backward in the same run ---------------------------------------------
+    one_fwd, one_bwd, one = span_calls(int(L3s.max()))
+    assert one["n_spans"] == n_rec
+    one_fwd()
+
+    def weak_bwd():
+        _lib.check(l.sed_stitch_weak_backward(ptr(win_strong), ptr(win_att), ptr(ls.rec_win0), ptr(ls.rec_frame0), n_rec, T3, NCLASS,
+                                              hop3, 1, ptr(one["sums"]), ptr(one["g"]), ptr(d_s), ptr(d_a), ptr(err),
+                                              _lib.stream_ptr()), "sed_stitch_weak_backward")
+    one_bwd()
+    span_bytes = (d_s.clone(), d_a.clone())
+    weak_bwd()
+    b = {"one_span_per_recording_equals_weak_backward_bitwise":
+         bool(torch.equal(span_bytes[0].view(torch.int32), d_s.view(torch.int32))
+              and torch.equal(span_bytes[1].view(torch.int32), d_a.view(torch.int32)))}
+    legs = {"sed_stitch_span_tags_backward_alone": one_bwd, "sed_stitch_weak_backward_alone": weak_bwd}
+    for leg, fn in legs.items():
+        b[leg] = event_ms(fn, reps)
+    band = max(x["spread"] * x["median_ms"] for x in (b[k] for k in legs))
+    b["span_minus_weak_ms"] = b["sed_stitch_span_tags_backward_alone"]["median_ms"] - b["sed_stitch_weak_backward_alone"]["median_ms"]
+    b["larger_max_minus_min_ms"] = band
+    b["difference_exceeds_spread"] = bool(abs(b["span_minus_weak_ms"]) > band)
+    out["one_span_per_recording"] = b
+    assert int(err.item()) == 0
+    del span_bytes, win_strong, win_att, d_s, d_a
+    # ---- (c) an epoch on span tags against the epoch on recording tags over the same batches -------------------------------------
+    if int(np.diff(ls.rec_win0_host).max()) > BATCH:
+        out["epoch"] = "not measured: a recording has more windows than one forward holds (max_windows)"
+        return out
+    rng = np.random.default_rng(2)
+    tags = (rng.random((n_rec, NCLASS)) < 0.2).astype(np.float32)
+    span_tags = (rng.random((sp["n_spans"], NCLASS)) < 0.2).astype(np.float32)
+    opt = torch.optim.Adam(model.parameters(), lr=1e-5)
+    runs, _ = train.recording_tag_batches(np.diff(ls.rec_win0_host), BATCH, 0, 0)
+    out["batches_per_epoch"], out["max_windows"] = len(runs), BATCH
+    epoch = [0]
+
+    def rec_level():
+        train.train_recording_tags(ls, tags, model, opt, epoch[0], max_windows=BATCH)
+        epoch[0] += 1
+
+    def span_level():
+        train.train_span_tags(ls, span_tags, model, opt, epoch[0], span3=sp["span3"], max_windows=BATCH)
+        epoch[0] += 1
+    legs = {"epoch_recording_tags": rec_level, "epoch_span_tags": span_level}
+    for fn in legs.values():
+        fn()
+    ms = {leg: [] for leg in legs}
+    for _ in range(rounds):
+        for leg, fn in legs.items():
+            ms[leg].append(wall_ms(fn))
+    for leg in legs:
+        out[leg] = stats(ms[leg])
+    a, b = out["epoch_recording_tags"], out["epoch_span_tags"]
+    band = max(max(x["samples_ms"]) - min(x["samples_ms"]) for x in (a, b))
+    out["span_tags_add_ms"] = b["median_ms"] - a["median_ms"]
+    out["larger_max_minus_min_ms"] = band
+    out["addition_exceeds_spread"] = bool(out["span_tags_add_ms"] > band)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scoring", action="store_true", help="measure the scoring of the long path's event table instead")
@@ -1269,6 +1427,8 @@ def main():
     ap.add_argument("--weak", action="store_true", help="measure the recording-level weak tags (profiles/long_weak.json)")
     ap.add_argument("--tag-train", action="store_true",
                     help="measure the backward through the pooled tag and an epoch on recording tags (profiles/long_tag_train.json)")
+    ap.add_argument("--span-tag-train", action="store_true",
+                    help="measure the backward through the span tags and an epoch on span tags (profiles/long_span_tag_train.json)")
     ap.add_argument("--error-rate", action="store_true",
                     help="measure what validate_long(error_rate=True) adds (the \"long\" key of profiles/error_rate.json)")
     ap.add_argument("--hysteresis", action="store_true",
@@ -1296,6 +1456,7 @@ def main():
         args.out = os.path.join(REPO, "profiles", "long_rasterize.json" if args.rasterize else "long_span_tags.json" if args.span_tags else "long_scores.json" if args.scores else "long_process.json" if args.process else
                                 "long_hysteresis.json" if args.hysteresis else
                                 "error_rate.json" if args.error_rate else
+                                "long_span_tag_train.json" if args.span_tag_train else
                                 "long_tag_train.json" if args.tag_train else "long_weak.json" if args.weak else
                                 "long_scoring.json" if args.scoring else "long_inference.json")
     if not torch.cuda.is_available():
@@ -1425,6 +1586,28 @@ def main():
         doc["long"] = result
         with open(path, "w") as f:
             f.write(json.dumps(doc, indent=1) + "\n")
+        return
+    if args.span_tag_train:
+        result["model"] = "baseline CRNN, fp32 kernel set; eval mode for the window tensors of (a) and (b), train mode (dropout 0.5) in (c)"
+        result["timing"] = ("the calls alone: a device-event pair around the call(s), warm, median of --decode-reps; the epochs: host "
+                            "clock around each synchronised epoch, legs alternated, --rounds rounds")
+        result["note"] = ("(a) tag_span 10 s; the composed route is a torch-autograd restatement of the taper blend (index_add_ over "
+                          "the covered window frames) and a per-span fp64 segment_reduce, backward by autograd.grad on a kept graph - "
+                          "the only route to this gradient before sed_stitch_span_tags_backward; (b) one span per recording: the "
+                          "same call beside sed_stitch_weak_backward on the same sums and gradients, in the same run; (c) both "
+                          "epochs run the same batches (runs of recordings within max_windows), forward + backward + Adam step "
+                          "through the autograd nodes, every target known.  A difference counts only where it exceeds the larger "
+                          "(max - min) of the two legs")
+        result["not_measured"] += ["other nclass than 10", "other hops than the default", "other span lengths than 10 s and one span "
+                                   "per recording", "per-kernel counters", "the uniform weighting", "unknown (NaN) targets",
+                                   "an epoch over the 1 h recording (more windows than one forward holds)",
+                                   "f16 models", "ema_model given", "LDS staging of a span row's g / num / den: not written"]
+        for name in args.workloads.split(","):
+            result["workloads"][name] = span_tag_train_workload(name, model, args.rounds, args.decode_reps)
+            print(json.dumps({name: result["workloads"][name]}), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(json.dumps(result, indent=1) + "\n")
         return
     if args.tag_train:
         result["model"] = "baseline CRNN, fp32 kernel set; eval mode for the window tensors of (a), train mode (dropout 0.5) in (b)"
