@@ -26,7 +26,9 @@ and the mean of the blended timeline over its frames (``sed_events_scores``), ``
 Span-level weak tags and the tag gate: ``stitch_span_tags`` / ``get_long_predictions(tag_span=...)`` pool the weak tag per span
 of time (``sed_stitch_span_tags``, ``span_table``, ``span_tags_dataframe``), ``events_tag_scores`` gives every event the largest
 tag of the spans it touches (``sed_events_tag_scores``) and ``gate_decoded`` / ``get_long_predictions(min_span_tag=...)`` keep
-the events that touch a confident span (``events_select`` on that score).
+the events that touch a confident span (``events_select`` on that score); ``pooled_span_tags`` is the span tag with a backward.
+Both levels of pooled tags share one forward call, one backward call and one autograd node, in which a row description
+(``_tags_forward``) selects the level and with it the C entry.
 Pseudo strong labels: ``events_rasterize`` / ``rasterize_decoded`` turn any of these tables back into label rows
 (``sed_events_rasterize``), ``WindowedFeatureSet.relabel`` / ``ResidentFeatureSet.relabel`` write them in place into a training
 set's label pool, and ``pseudo_label`` runs the whole chain of ``get_long_predictions`` and ends in the pool instead of a
@@ -572,18 +574,77 @@ def _weak_inputs(who, win_strong, win_att, rec_win0, total_frames, hop3, weighti
     return total, int(hop3), weighting
 
 
-def _weak_call(win_strong, win_att, rec_win0, rec_frame0, total, hop3, weighting, err, want_sums):
-    """The one ``sed_stitch_weak`` call, on checked contiguous float32 window tensors: ``(weak, sums or None)``."""
+# The rows being pooled, ``rows`` below: None - one row per recording (``sed_stitch_weak`` / ``sed_stitch_weak_backward``) - or
+# ``(rec_span0 on the device, total_spans, span3, ws_bytes)`` (``sed_stitch_span_tags`` / ``sed_stitch_span_tags_backward``).
+def _tags_forward(win_strong, win_att, rec_win0, rec_frame0, total, hop3, weighting, rows, err, want_sums):
+    """The one forward call of the pooled tags, on checked contiguous float32 window tensors: ``(tags, sums or None)``."""
     l = _lib.lib()
     n_win, T3, NC = win_strong.shape
     n_rec, dev = rec_win0.numel() - 1, win_strong.device
-    weak = torch.empty(n_rec, NC, dtype=torch.float32, device=dev)
-    sums = torch.empty(n_rec, NC, 2, dtype=torch.float64, device=dev) if want_sums else None
-    ws = _lib.scratch(l.sed_stitch_weak_ws_bytes(total, n_rec, NC), dev)
-    _lib.check(l.sed_stitch_weak(_lib.ptr(win_strong), _lib.ptr(win_att), _lib.ptr(rec_win0), _lib.ptr(rec_frame0), n_rec, T3, NC,
-                                 hop3, weighting, _lib.ptr(weak), _lib.ptr(sums), _lib.ptr(ws), ws.numel(), _lib.ptr(err),
-                                 _lib.stream_ptr()), "sed_stitch_weak")
-    return weak, sums
+    n_rows = n_rec if rows is None else rows[1]
+    tags = torch.empty(n_rows, NC, dtype=torch.float32, device=dev)
+    sums = torch.empty(n_rows, NC, 2, dtype=torch.float64, device=dev) if want_sums else None
+    ws = _lib.scratch(l.sed_stitch_weak_ws_bytes(total, n_rec, NC) if rows is None else rows[3], dev)
+    head = (_lib.ptr(win_strong), _lib.ptr(win_att), _lib.ptr(rec_win0), _lib.ptr(rec_frame0))
+    tail = (_lib.ptr(tags), _lib.ptr(sums), _lib.ptr(ws), ws.numel(), _lib.ptr(err), _lib.stream_ptr())
+    if rows is None:
+        _lib.check(l.sed_stitch_weak(*head, n_rec, T3, NC, hop3, weighting, *tail), "sed_stitch_weak")
+    else:
+        rec_span0, total_spans, span3, _ = rows
+        _lib.check(l.sed_stitch_span_tags(*head, _lib.ptr(rec_span0), total, total_spans, n_rec, T3, NC, hop3, weighting, span3,
+                                          *tail), "sed_stitch_span_tags")
+    return tags, sums
+
+
+def _tags_backward(win_strong, win_att, rec_win0, rec_frame0, hop3, weighting, rows, sums, g_tags, err):
+    """The one backward call of the pooled tags, from the forward's sums: ``(d_win_strong, d_win_att)``."""
+    l = _lib.lib()
+    n_win, T3, NC = win_strong.shape
+    n_rec = rec_win0.numel() - 1
+    d_strong, d_att = torch.empty_like(win_strong), torch.empty_like(win_att)
+    head = (_lib.ptr(win_strong), _lib.ptr(win_att), _lib.ptr(rec_win0), _lib.ptr(rec_frame0))
+    tail = (_lib.ptr(sums), _lib.ptr(g_tags), _lib.ptr(d_strong), _lib.ptr(d_att), _lib.ptr(err), _lib.stream_ptr())
+    if rows is None:
+        _lib.check(l.sed_stitch_weak_backward(*head, n_rec, T3, NC, hop3, weighting, *tail), "sed_stitch_weak_backward")
+    else:
+        rec_span0, total_spans, span3, _ = rows
+        _lib.check(l.sed_stitch_span_tags_backward(*head, _lib.ptr(rec_span0), total_spans, n_rec, T3, NC, hop3, weighting, span3,
+                                                   *tail), "sed_stitch_span_tags_backward")
+    return d_strong, d_att
+
+
+class _PooledTags(torch.autograd.Function):
+    """forward = ``_tags_forward`` with the (num, den) sums kept, backward = ``_tags_backward``; ``rows`` selects the level."""
+
+    @staticmethod
+    def forward(ctx, win_strong, win_att, rec_win0, rec_frame0, total, hop3, weighting, rows, err):
+        tags, sums = _tags_forward(win_strong, win_att, rec_win0, rec_frame0, total, hop3, weighting, rows, err, True)
+        ctx.save_for_backward(win_strong, win_att, rec_win0, rec_frame0, sums, *(() if rows is None else rows[:1]))
+        ctx.hop3, ctx.weighting, ctx.err = hop3, weighting, err          # (err: the library ORs into it, autograd never sees it)
+        ctx.rows = None if rows is None else rows[1:]
+        return tags
+
+    @staticmethod
+    def backward(ctx, g_tags):
+        win_strong, win_att, rec_win0, rec_frame0, sums, *rec_span0 = ctx.saved_tensors
+        rows = None if ctx.rows is None else (rec_span0[0],) + ctx.rows
+        return _tags_backward(win_strong, win_att, rec_win0, rec_frame0, ctx.hop3, ctx.weighting, rows, sums,
+                              g_tags.contiguous().float(), ctx.err) + (None,) * 7
+
+
+def _pooled(who, win_strong, win_att, rec_win0, rec_frame0, total_frames, hop3, weighting, n_win, span=None):
+    """``pooled_tags`` and ``pooled_span_tags``: the input checks, the tables' dtype / device check, the rows - one per recording,
+    or with ``span = (span3, rec_frame0_host, span_tables)`` those of ``_span_rows`` - and the node.  Returns ``(tags, err,
+    _span_rows' dict or None)``."""
+    total, hop3, weighting = _weak_inputs(who, win_strong, win_att, rec_win0, total_frames, hop3, weighting, n_win)
+    if rec_win0.dtype != torch.int32 or rec_frame0.dtype != torch.int64 or rec_frame0.numel() != rec_win0.numel() or \
+            rec_win0.device != win_strong.device or rec_frame0.device != win_strong.device:
+        raise ValueError("rec_win0 [n_rec + 1] int32 and rec_frame0 [n_rec + 1] int64 must be on the window tensors' device")
+    spans, rows = (None, None) if span is None else _span_rows(win_strong, rec_win0, rec_frame0, total, *span)
+    err = torch.zeros(1, dtype=torch.int32, device=win_strong.device)
+    tags = _PooledTags.apply(win_strong.contiguous().float(), win_att.contiguous().float(), rec_win0.contiguous(),
+                             rec_frame0.contiguous(), total, hop3, weighting, rows, err)
+    return tags, err, spans
 
 
 def stitch_weak(win_strong, win_att, rec_win0, rec_frame0, total_frames, hop3, weighting="taper", want_sums=False):
@@ -595,33 +656,9 @@ def stitch_weak(win_strong, win_att, rec_win0, rec_frame0, total_frames, hop3, w
     of such a recording are NaN)."""
     total, hop3, weighting = _weak_inputs("stitch_weak", win_strong, win_att, rec_win0, total_frames, hop3, weighting)
     err = torch.zeros(1, dtype=torch.int32, device=win_strong.device)
-    weak, sums = _weak_call(win_strong.contiguous().float(), win_att.contiguous().float(), rec_win0, rec_frame0, total, hop3,
-                            weighting, err, want_sums)
+    weak, sums = _tags_forward(win_strong.contiguous().float(), win_att.contiguous().float(), rec_win0, rec_frame0, total, hop3,
+                               weighting, None, err, want_sums)
     return {"weak": weak, "sums": sums, "err": err}
-
-
-class _PooledTags(torch.autograd.Function):
-    """forward = sed_stitch_weak with the (num, den) sums kept, backward = sed_stitch_weak_backward."""
-
-    @staticmethod
-    def forward(ctx, win_strong, win_att, rec_win0, rec_frame0, total, hop3, weighting, err):
-        weak, sums = _weak_call(win_strong, win_att, rec_win0, rec_frame0, total, hop3, weighting, err, True)
-        ctx.save_for_backward(win_strong, win_att, rec_win0, rec_frame0, sums)
-        ctx.hop3, ctx.weighting, ctx.err = hop3, weighting, err          # (err: the library ORs into it, autograd never sees it)
-        return weak
-
-    @staticmethod
-    def backward(ctx, g_weak):
-        l = _lib.lib()
-        win_strong, win_att, rec_win0, rec_frame0, sums = ctx.saved_tensors
-        n_win, T3, NC = win_strong.shape
-        g_weak = g_weak.contiguous().float()
-        d_strong, d_att = torch.empty_like(win_strong), torch.empty_like(win_att)
-        _lib.check(l.sed_stitch_weak_backward(_lib.ptr(win_strong), _lib.ptr(win_att), _lib.ptr(rec_win0), _lib.ptr(rec_frame0),
-                                              rec_win0.numel() - 1, T3, NC, ctx.hop3, ctx.weighting, _lib.ptr(sums),
-                                              _lib.ptr(g_weak), _lib.ptr(d_strong), _lib.ptr(d_att), _lib.ptr(ctx.err),
-                                              _lib.stream_ptr()), "sed_stitch_weak_backward")
-        return d_strong, d_att, None, None, None, None, None, None
 
 
 def pooled_tags(win_strong, win_att, rec_win0, rec_frame0, total_frames, hop3, weighting="taper", n_win=None):
@@ -633,14 +670,7 @@ def pooled_tags(win_strong, win_att, rec_win0, rec_frame0, total_frames, hop3, w
     backward writes every element of both gradients over the tables' own window count, which lives on the device.  ``n_win``:
     that count where the caller has it on the host (``train_recording_tags`` does) - checked against the tensors here, with
     no synchronisation; without it the requirement is the caller's."""
-    total, hop3, weighting = _weak_inputs("pooled_tags", win_strong, win_att, rec_win0, total_frames, hop3, weighting, n_win)
-    if rec_win0.dtype != torch.int32 or rec_frame0.dtype != torch.int64 or rec_frame0.numel() != rec_win0.numel() or \
-            rec_win0.device != win_strong.device or rec_frame0.device != win_strong.device:
-        raise ValueError("rec_win0 [n_rec + 1] int32 and rec_frame0 [n_rec + 1] int64 must be on the window tensors' device")
-    err = torch.zeros(1, dtype=torch.int32, device=win_strong.device)
-    weak = _PooledTags.apply(win_strong.contiguous().float(), win_att.contiguous().float(), rec_win0.contiguous(),
-                             rec_frame0.contiguous(), total, hop3, weighting, err)
-    return weak, err
+    return _pooled("pooled_tags", win_strong, win_att, rec_win0, rec_frame0, total_frames, hop3, weighting, n_win)[:2]
 
 
 def weak_tags_dataframe(weak, filenames, labels, threshold=0.5):
@@ -682,91 +712,12 @@ def span_table(long_set_or_L3s, span3, device=None):
     return host, dev_table, int(host[-1]), span3
 
 
-def stitch_span_tags(win_strong, win_att, rec_win0, rec_frame0, total_frames, hop3, span3, weighting="taper", want_sums=False,
-                     rec_frame0_host=None):
-    """Span-level weak tags (``sed_stitch_span_tags``): ``stitch_weak``'s blend and fp64 pooling per span of ``span3`` label
-    frames of every recording instead of per recording (the definition is in include/dcase_sed.h); arguments as for
-    ``stitch_weak``.  The span table needs the recordings' lengths on the host: ``rec_frame0_host`` (a ``LongRecordingSet``
-    has it) - without it ``rec_frame0`` is copied to the host once.  ``span3`` is clamped to the longest recording.  Returns a
-    dict, the tensors on the device: ``tags`` [total_spans, nclass] float32, ``sums`` [total_spans, nclass, 2] float64 (num,
-    den) or None, ``rec_span0`` [n_rec + 1] int64, ``rec_span0_host``, ``total_spans``, ``span3`` (clamped), ``err`` [1] int32
-    (``STITCH_ERR_BITS`` 16 / 32: the rows of such a recording are NaN).  Two launches."""
-    total, hop3, weighting = _weak_inputs("stitch_span_tags", win_strong, win_att, rec_win0, total_frames, hop3, weighting)
-    if rec_frame0_host is None:
-        rec_frame0_host = rec_frame0.cpu().numpy()
-    dev = win_strong.device
-    host, rec_span0, total_spans, span3 = span_table(np.diff(np.asarray(rec_frame0_host, dtype=np.int64)), span3, dev)
-    n_win, T3, NC = win_strong.shape
-    n_rec = rec_win0.numel() - 1
-    l = _lib.lib()
-    ws_bytes = l.sed_stitch_span_tags_ws_bytes(total, total_spans, n_rec, NC, span3)
-    if ws_bytes == 0:
-        raise ValueError(f"sed_stitch_span_tags_ws_bytes: {l.sed_last_error().decode()}")
-    win_strong, win_att = win_strong.contiguous().float(), win_att.contiguous().float()
-    tags = torch.empty(total_spans, NC, dtype=torch.float32, device=dev)
-    sums = torch.empty(total_spans, NC, 2, dtype=torch.float64, device=dev) if want_sums else None
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    ws = _lib.scratch(ws_bytes, dev)
-    _lib.check(l.sed_stitch_span_tags(_lib.ptr(win_strong), _lib.ptr(win_att), _lib.ptr(rec_win0), _lib.ptr(rec_frame0),
-                                      _lib.ptr(rec_span0), total, total_spans, n_rec, T3, NC, hop3, weighting, span3, _lib.ptr(tags),
-                                      _lib.ptr(sums), _lib.ptr(ws), ws.numel(), _lib.ptr(err), _lib.stream_ptr()),
-               "sed_stitch_span_tags")
-    return {"tags": tags, "sums": sums, "rec_span0": rec_span0, "rec_span0_host": host, "total_spans": total_spans, "span3": span3,
-            "err": err}
-
-
-class _PooledSpanTags(torch.autograd.Function):
-    """forward = sed_stitch_span_tags with the (num, den) sums kept, backward = sed_stitch_span_tags_backward."""
-
-    @staticmethod
-    def forward(ctx, win_strong, win_att, rec_win0, rec_frame0, rec_span0, total, total_spans, hop3, weighting, span3, ws_bytes,
-                err):
-        l = _lib.lib()
-        n_win, T3, NC = win_strong.shape
-        n_rec, dev = rec_win0.numel() - 1, win_strong.device
-        tags = torch.empty(total_spans, NC, dtype=torch.float32, device=dev)
-        sums = torch.empty(total_spans, NC, 2, dtype=torch.float64, device=dev)
-        ws = _lib.scratch(ws_bytes, dev)
-        _lib.check(l.sed_stitch_span_tags(_lib.ptr(win_strong), _lib.ptr(win_att), _lib.ptr(rec_win0), _lib.ptr(rec_frame0),
-                                          _lib.ptr(rec_span0), total, total_spans, n_rec, T3, NC, hop3, weighting, span3,
-                                          _lib.ptr(tags), _lib.ptr(sums), _lib.ptr(ws), ws.numel(), _lib.ptr(err),
-                                          _lib.stream_ptr()), "sed_stitch_span_tags")
-        ctx.save_for_backward(win_strong, win_att, rec_win0, rec_frame0, rec_span0, sums)
-        ctx.total_spans, ctx.hop3, ctx.weighting, ctx.span3, ctx.err = total_spans, hop3, weighting, span3, err
-        return tags
-
-    @staticmethod
-    def backward(ctx, g_tags):
-        l = _lib.lib()
-        win_strong, win_att, rec_win0, rec_frame0, rec_span0, sums = ctx.saved_tensors
-        n_win, T3, NC = win_strong.shape
-        g_tags = g_tags.contiguous().float()
-        d_strong, d_att = torch.empty_like(win_strong), torch.empty_like(win_att)
-        _lib.check(l.sed_stitch_span_tags_backward(_lib.ptr(win_strong), _lib.ptr(win_att), _lib.ptr(rec_win0),
-                                                   _lib.ptr(rec_frame0), _lib.ptr(rec_span0), ctx.total_spans,
-                                                   rec_win0.numel() - 1, T3, NC, ctx.hop3, ctx.weighting, ctx.span3,
-                                                   _lib.ptr(sums), _lib.ptr(g_tags), _lib.ptr(d_strong), _lib.ptr(d_att),
-                                                   _lib.ptr(ctx.err), _lib.stream_ptr()), "sed_stitch_span_tags_backward")
-        return (d_strong, d_att) + (None,) * 10
-
-
-def pooled_span_tags(win_strong, win_att, rec_win0, rec_frame0, total_frames, hop3, span3, weighting="taper", n_win=None,
-                     rec_frame0_host=None, span_tables=None):
-    """``stitch_span_tags``'s span-level tags as a differentiable function of both window tensors: an autograd node whose
-    forward is ``sed_stitch_span_tags`` (its fp64 sums are kept) and whose backward is ``sed_stitch_span_tags_backward``.
-    Arguments and host checks as for ``pooled_tags`` (the window tensors must hold exactly ``rec_win0[-1]`` windows; ``n_win``:
-    that count where the caller has it on the host), ``span3`` / ``rec_frame0_host`` as for ``stitch_span_tags``: the span
-    table comes from ``span_table`` (``span3`` clamped to the longest recording) and is copied to the device - unless the
-    caller has one for exactly these recordings already, ``span_tables = (rec_span0 host, rec_span0 on the device)``
-    (``train_span_tags`` prepares its batches' once per epoch); it is then checked against the lengths on the host and
-    nothing is copied.  Returns a dict like ``stitch_span_tags``'s: ``tags`` [total_spans, nclass] float32 (differentiable),
-    ``rec_span0``, ``rec_span0_host``, ``total_spans``, ``span3`` (clamped), ``err`` [1] int32 on the device, OR-ed into by
-    forward and backward (``STITCH_ERR_BITS`` 16 / 32: tags and gradients are invalid when it is nonzero).  With
-    ``rec_frame0_host`` nothing synchronises."""
-    total, hop3, weighting = _weak_inputs("pooled_span_tags", win_strong, win_att, rec_win0, total_frames, hop3, weighting, n_win)
-    if rec_win0.dtype != torch.int32 or rec_frame0.dtype != torch.int64 or rec_frame0.numel() != rec_win0.numel() or \
-            rec_win0.device != win_strong.device or rec_frame0.device != win_strong.device:
-        raise ValueError("rec_win0 [n_rec + 1] int32 and rec_frame0 [n_rec + 1] int64 must be on the window tensors' device")
+def _span_rows(win_strong, rec_win0, rec_frame0, total, span3, rec_frame0_host=None, span_tables=None):
+    """The span table of a span-level call, resolved once: the recordings' lengths from ``rec_frame0_host`` (without it
+    ``rec_frame0`` is copied to the host), then ``span_table``'s table copied to the device - or, with ``span_tables = (rec_span0
+    host, rec_span0 on the device)``, the caller's, checked against the lengths on the host and nothing copied - and the
+    workspace size (0: ``ValueError`` with the library's reason).  Returns ``(the keys rec_span0, rec_span0_host, total_spans
+    and span3 (clamped) of the fronts' dicts, the rows for _tags_forward)``."""
     if rec_frame0_host is None:
         rec_frame0_host = rec_frame0.cpu().numpy()
     L3s = np.diff(np.asarray(rec_frame0_host, dtype=np.int64).reshape(-1))
@@ -782,16 +733,47 @@ def pooled_span_tags(win_strong, win_att, rec_win0, rec_frame0, total_frames, ho
             raise ValueError("span_tables is not span_table's for these recordings and this span3")
         if rec_span0.dtype != torch.int64 or rec_span0.numel() != n_rec + 1 or rec_span0.device != dev:
             raise ValueError("span_tables' device table must be [n_rec + 1] int64 on the window tensors' device")
-    NC = win_strong.shape[2]
     l = _lib.lib()
-    ws_bytes = l.sed_stitch_span_tags_ws_bytes(total, total_spans, n_rec, NC, span3)
+    ws_bytes = l.sed_stitch_span_tags_ws_bytes(total, total_spans, n_rec, win_strong.shape[2], span3)
     if ws_bytes == 0:
         raise ValueError(f"sed_stitch_span_tags_ws_bytes: {l.sed_last_error().decode()}")
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    tags = _PooledSpanTags.apply(win_strong.contiguous().float(), win_att.contiguous().float(), rec_win0.contiguous(),
-                                 rec_frame0.contiguous(), rec_span0.contiguous(), total, total_spans, hop3, weighting, span3,
-                                 ws_bytes, err)
-    return {"tags": tags, "rec_span0": rec_span0, "rec_span0_host": host, "total_spans": total_spans, "span3": span3, "err": err}
+    return ({"rec_span0": rec_span0, "rec_span0_host": host, "total_spans": total_spans, "span3": span3},
+            (rec_span0.contiguous(), total_spans, span3, ws_bytes))
+
+
+def stitch_span_tags(win_strong, win_att, rec_win0, rec_frame0, total_frames, hop3, span3, weighting="taper", want_sums=False,
+                     rec_frame0_host=None):
+    """Span-level weak tags (``sed_stitch_span_tags``): ``stitch_weak``'s blend and fp64 pooling per span of ``span3`` label
+    frames of every recording instead of per recording (the definition is in include/dcase_sed.h); arguments as for
+    ``stitch_weak``.  The span table needs the recordings' lengths on the host: ``rec_frame0_host`` (a ``LongRecordingSet``
+    has it) - without it ``rec_frame0`` is copied to the host once.  ``span3`` is clamped to the longest recording.  Returns a
+    dict, the tensors on the device: ``tags`` [total_spans, nclass] float32, ``sums`` [total_spans, nclass, 2] float64 (num,
+    den) or None, ``rec_span0`` [n_rec + 1] int64, ``rec_span0_host``, ``total_spans``, ``span3`` (clamped), ``err`` [1] int32
+    (``STITCH_ERR_BITS`` 16 / 32: the rows of such a recording are NaN).  Two launches."""
+    total, hop3, weighting = _weak_inputs("stitch_span_tags", win_strong, win_att, rec_win0, total_frames, hop3, weighting)
+    spans, rows = _span_rows(win_strong, rec_win0, rec_frame0, total, span3, rec_frame0_host)
+    err = torch.zeros(1, dtype=torch.int32, device=win_strong.device)
+    tags, sums = _tags_forward(win_strong.contiguous().float(), win_att.contiguous().float(), rec_win0, rec_frame0, total, hop3,
+                               weighting, rows, err, want_sums)
+    return {"tags": tags, "sums": sums, **spans, "err": err}
+
+
+def pooled_span_tags(win_strong, win_att, rec_win0, rec_frame0, total_frames, hop3, span3, weighting="taper", n_win=None,
+                     rec_frame0_host=None, span_tables=None):
+    """``stitch_span_tags``'s span-level tags as a differentiable function of both window tensors: ``pooled_tags``' node with
+    ``sed_stitch_span_tags`` (its fp64 sums are kept) as the forward and ``sed_stitch_span_tags_backward`` as the backward.
+    Arguments and host checks as for ``pooled_tags`` (the window tensors must hold exactly ``rec_win0[-1]`` windows; ``n_win``:
+    that count where the caller has it on the host), ``span3`` / ``rec_frame0_host`` as for ``stitch_span_tags``: the span
+    table comes from ``span_table`` (``span3`` clamped to the longest recording) and is copied to the device - unless the
+    caller has one for exactly these recordings already, ``span_tables = (rec_span0 host, rec_span0 on the device)``
+    (``train_span_tags`` prepares its batches' once per epoch); it is then checked against the lengths on the host and
+    nothing is copied.  Returns a dict like ``stitch_span_tags``'s: ``tags`` [total_spans, nclass] float32 (differentiable),
+    ``rec_span0``, ``rec_span0_host``, ``total_spans``, ``span3`` (clamped), ``err`` [1] int32 on the device, OR-ed into by
+    forward and backward (``STITCH_ERR_BITS`` 16 / 32: tags and gradients are invalid when it is nonzero).  With
+    ``rec_frame0_host`` nothing synchronises."""
+    tags, err, spans = _pooled("pooled_span_tags", win_strong, win_att, rec_win0, rec_frame0, total_frames, hop3, weighting, n_win,
+                               (span3, rec_frame0_host, span_tables))
+    return {"tags": tags, **spans, "err": err}
 
 
 def events_tag_scores(out_or_table, tags, rec_span0, span3, n_rec, nclass, err=None):

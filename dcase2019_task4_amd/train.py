@@ -882,20 +882,84 @@ def _tag_batch_order(n_batches, seed, epoch):
     return np.random.default_rng([int(seed), int(epoch)]).permutation(n_batches)
 
 
+def _tags_loss(long_set, model, run, tables, targets, known=None, spans=None, weighting="taper"):
+    """The loss of one batch of either level - the recordings ``run = (r0, r1)`` of ``long_set`` - with its graph: the run's
+    windows through the set's eval gather, ``model(x, return_attention=True)``, the pooled tags (``inference._pooled``), the
+    BCE.  ``tables = (k, at, rec_win0, rec_frame0)``: ``tag_batches``' tables.  ``spans`` None: one row per recording, the
+    plain mean ``binary_cross_entropy`` against ``targets[r0:r1]``.  ``spans = (span3, rec_span0 of every run rebased and
+    concatenated like the tables, the set's span offsets on the host, the runs' known-pair counts)``: the rows are the run's
+    spans, the BCE weighted by ``known`` and scaled by pairs / known pairs (a host number).  Returns ``(loss, err)``; nothing
+    synchronises."""
+    from .inference import _pooled
+    r0, r1 = run
+    k, at, win0_all, frame0_all = tables
+    w0, w1 = int(long_set.rec_win0_host[r0]), int(long_set.rec_win0_host[r1])
+    frames_host = long_set.rec_frame0_host[r0:r1 + 1] - long_set.rec_frame0_host[r0]
+    g0, g1, span = r0, r1, None
+    if spans is not None:
+        span3, span0_all, span0_host, counts = spans
+        g0, g1 = int(span0_host[r0]), int(span0_host[r1])
+        span = (span3, frames_host, (span0_host[r0:r1 + 1] - g0, span0_all[at[k]:at[k + 1]]))
+    x = long_set.eval_batch(w0, w1 - w0)
+    strong, _, att = model(x, return_attention=True)
+    tags, err, _ = _pooled("pooled_tags" if spans is None else "pooled_span_tags", strong, att, win0_all[at[k]:at[k + 1]],
+                           frame0_all[at[k]:at[k + 1]], int(frames_host[-1]), long_set.hop3, weighting, w1 - w0, span)
+    target = targets[g0:g1]
+    if spans is None:
+        return torch.nn.functional.binary_cross_entropy(tags, target), err
+    loss = torch.nn.functional.binary_cross_entropy(tags, target, weight=known[g0:g1])
+    return loss * (target.numel() / int(counts[k])), err
+
+
+def _tags_epoch(who, label, long_set, targets, known, counts, spans, model, optimizer, epoch, ema_model, max_windows, seed, log):
+    """The one epoch on pooled tags, behind ``train_recording_tags`` and ``train_span_tags`` (``who``, for the messages;
+    ``label``: the loss's name in the log line).  ``targets`` [rows, nclass]: host floats, one row per recording or per span;
+    ``known`` / ``counts`` / ``spans = (span3, the set's span offsets on the host)``: ``span_tag_plan``'s mask, known-pair
+    counts and span table, or None at the recording level - every run is then visited.  A run with a count of 0 is skipped:
+    no forward, no optimizer or EMA step, though it keeps its place ``i`` in the order.  Returns the mean loss over the runs
+    that ran."""
+    runs, at, win0_all, frame0_all = long_set.tag_batches(max_windows)
+    order = _tag_batch_order(len(runs), seed, epoch)
+    start = time.time()
+    dev = long_set.device
+    if spans is not None:
+        span3, span0_host = spans
+        span0_all = torch.from_numpy(np.concatenate([span0_host[r0:r1 + 1] - span0_host[r0] for r0, r1 in runs])).to(dev)
+        spans, known = (span3, span0_all, span0_host, counts), torch.from_numpy(known).to(dev)
+    targets = torch.as_tensor(targets, dtype=torch.float32).to(dev)
+    model.to(dev)
+    model.train()
+    n_batches, n_ran = len(runs), 0
+    loss_sum = torch.zeros((), dtype=torch.float32, device=dev)
+    err_all = torch.zeros(1, dtype=torch.int32, device=dev)
+    for i, k in enumerate(order):
+        if counts is not None and counts[k] == 0:
+            continue
+        optimizer.zero_grad()
+        loss, err = _tags_loss(long_set, model, runs[k], (int(k), at, win0_all, frame0_all), targets, known, spans)
+        loss.backward()
+        optimizer.step()
+        if ema_model is not None:
+            update_ema_variables(model, ema_model, 0.999, int(epoch) * n_batches + i)
+        loss_sum += loss.detach()
+        err_all |= err
+        n_ran += 1
+    mean = float(loss_sum.item()) / n_ran
+    bits = int(err_all.item())
+    if bits:
+        raise _lib.SedError(f"{who}: the pooling kernels raised error bits {bits} (16: malformed tables, 32: a "
+                            "recording its windows do not cover)")
+    assert not (mean != mean or mean > 1e5), 'Loss explosion: {}'.format(mean)
+    if log is not None:
+        log('Epoch: {}\tTime {:.2f}\t{} {:.4g}'.format(epoch, time.time() - start, label, mean))
+    return mean
+
+
 def recording_tags_loss(long_set, tags_dev, model, run, tables, weighting="taper"):
     """The loss of one ``train_recording_tags`` batch - the recordings ``run = (r0, r1)`` of ``long_set`` - with its graph:
     the run's windows through the set's eval gather, ``model(x, return_attention=True)``, ``inference.pooled_tags``, the mean
     ``binary_cross_entropy`` over the run's (recording, class) pairs.  Returns ``(loss, err)``."""
-    from .inference import pooled_tags
-    r0, r1 = run
-    k, at, win0_all, frame0_all = tables
-    w0, w1 = int(long_set.rec_win0_host[r0]), int(long_set.rec_win0_host[r1])
-    total = int(long_set.rec_frame0_host[r1] - long_set.rec_frame0_host[r0])
-    x = long_set.eval_batch(w0, w1 - w0)
-    strong, _, att = model(x, return_attention=True)
-    weak, err = pooled_tags(strong, att, win0_all[at[k]:at[k + 1]], frame0_all[at[k]:at[k + 1]], total, long_set.hop3, weighting,
-                            n_win=w1 - w0)
-    return torch.nn.functional.binary_cross_entropy(weak, tags_dev[r0:r1]), err
+    return _tags_loss(long_set, model, run, tables, tags_dev, weighting=weighting)
 
 
 def train_recording_tags(long_set, tags, model, optimizer, epoch, ema_model=None, max_windows=64, seed=0, log=None):
@@ -919,34 +983,8 @@ def train_recording_tags(long_set, tags, model, optimizer, epoch, ema_model=None
         raise ValueError(f"tags must be [n_rec = {long_set.n_rec}, nclass], got {tags_np.shape}")
     if not ((tags_np >= 0) & (tags_np <= 1)).all():
         raise ValueError("tags must lie in [0, 1]")
-    runs, at, win0_all, frame0_all = long_set.tag_batches(max_windows)
-    order = _tag_batch_order(len(runs), seed, epoch)
-    start = time.time()
-    dev = long_set.device
-    tags_dev = torch.as_tensor(tags_np, dtype=torch.float32).to(dev)
-    model.to(dev)
-    model.train()
-    n_batches = len(runs)
-    loss_sum = torch.zeros((), dtype=torch.float32, device=dev)
-    err_all = torch.zeros(1, dtype=torch.int32, device=dev)
-    for i, k in enumerate(order):
-        optimizer.zero_grad()
-        loss, err = recording_tags_loss(long_set, tags_dev, model, runs[k], (int(k), at, win0_all, frame0_all))
-        loss.backward()
-        optimizer.step()
-        if ema_model is not None:
-            update_ema_variables(model, ema_model, 0.999, int(epoch) * n_batches + i)
-        loss_sum += loss.detach()
-        err_all |= err
-    mean = float(loss_sum.item()) / n_batches
-    bits = int(err_all.item())
-    if bits:
-        raise _lib.SedError(f"train_recording_tags: the pooling kernels raised error bits {bits} (16: malformed tables, 32: a "
-                            "recording its windows do not cover)")
-    assert not (mean != mean or mean > 1e5), 'Loss explosion: {}'.format(mean)
-    if log is not None:
-        log('Epoch: {}\tTime {:.2f}\trecording_tag_loss {:.4g}'.format(epoch, time.time() - start, mean))
-    return mean
+    return _tags_epoch("train_recording_tags", "recording_tag_loss", long_set, tags_np, None, None, None, model, optimizer, epoch,
+                       ema_model, max_windows, seed, log)
 
 
 # ---- training on span-level tags -----------------------------------------------------------------------------------------------
@@ -984,20 +1022,7 @@ def span_tags_loss(long_set, span_tags_dev, known_dev, model, run, tables, span3
     rebased span tables concatenated the same way, the set's span offsets and the runs' known-pair counts on the host.
     The sum is taken as the masked mean over all the run's pairs times pairs / known (a host number): with every pair known
     that is ``recording_tags_loss``'s mean BCE operation for operation.  Returns ``(loss, err)``; nothing synchronises."""
-    from .inference import pooled_span_tags
-    r0, r1 = run
-    k, at, win0_all, frame0_all, span0_all, span0_host, counts = tables
-    w0, w1 = int(long_set.rec_win0_host[r0]), int(long_set.rec_win0_host[r1])
-    frames_host = long_set.rec_frame0_host[r0:r1 + 1] - long_set.rec_frame0_host[r0]
-    g0, g1 = int(span0_host[r0]), int(span0_host[r1])
-    x = long_set.eval_batch(w0, w1 - w0)
-    strong, _, att = model(x, return_attention=True)
-    out = pooled_span_tags(strong, att, win0_all[at[k]:at[k + 1]], frame0_all[at[k]:at[k + 1]], int(frames_host[-1]),
-                           long_set.hop3, span3, weighting, n_win=w1 - w0, rec_frame0_host=frames_host,
-                           span_tables=(span0_host[r0:r1 + 1] - g0, span0_all[at[k]:at[k + 1]]))
-    target, known = span_tags_dev[g0:g1], known_dev[g0:g1]
-    loss = torch.nn.functional.binary_cross_entropy(out["tags"], target, weight=known)
-    return loss * (target.numel() / int(counts[k])), out["err"]
+    return _tags_loss(long_set, model, run, tables[:4], span_tags_dev, known_dev, (span3,) + tuple(tables[4:]), weighting)
 
 
 def train_span_tags(long_set, span_tags, model, optimizer, epoch, tag_span=None, span3=None, ema_model=None, max_windows=64,
@@ -1011,12 +1036,13 @@ def train_span_tags(long_set, span_tags, model, optimizer, epoch, tag_span=None,
 
     The loss is on ``inference.pooled_span_tags``: its gradient reaches the windows through ``sed_stitch_span_tags_backward``
     and ``sed_crnn_backward_att``, localised to the span - a class absent from a span pushes that span's posteriors down.
-    Batches, their order from (``seed``, ``epoch``), the optimizer and EMA steps (``epoch * n_batches + i``, ``i`` the batch's
-    place in that order) and the end-of-epoch checks are ``train_recording_tags``'s; a batch without a known pair is skipped
-    (no forward, no optimizer or EMA step - the host knows from the targets).  Per batch the BCE is summed over its known
-    pairs and divided by their count.  Nothing synchronises inside the epoch: the masks, counts and span tables are prepared
-    once at its start, the kernels' error word is read once at its end (nonzero raises ``SedError``), with the mean loss over
-    the batches that ran, which is returned.  A recording with more than ``max_windows`` windows raises ``ValueError``."""
+    The epoch is ``train_recording_tags``'s own (one loop serves both): batches, their order from (``seed``, ``epoch``), the
+    optimizer and EMA steps (``epoch * n_batches + i``, ``i`` the batch's place in that order) and the end-of-epoch checks; a
+    batch without a known pair is skipped (no forward, no optimizer or EMA step - the host knows from the targets).  Per batch
+    the BCE is summed over its known pairs and divided by their count.  Nothing synchronises inside the epoch: the masks,
+    counts and span tables are prepared once at its start, the kernels' error word is read once at its end (nonzero raises
+    ``SedError``), with the mean loss over the batches that ran, which is returned.  A recording with more than
+    ``max_windows`` windows raises ``ValueError``."""
     from .inference import _Cfg, tag_span_frames
     from .longrec import LongRecordingSet
     if not isinstance(long_set, LongRecordingSet):
@@ -1028,38 +1054,6 @@ def train_span_tags(long_set, span_tags, model, optimizer, epoch, tag_span=None,
     plan = span_tag_plan(long_set.rec_win0_host, long_set.rec_frame0_host, span_tags, max_windows, span3)
     if not plan["ran"]:
         raise ValueError("span_tags has no known target: every entry is NaN")
-    runs, at, win0_all, frame0_all = long_set.tag_batches(max_windows)
-    assert runs == plan["runs"]
-    order = _tag_batch_order(len(runs), seed, epoch)
-    start = time.time()
-    dev = long_set.device
-    span0_host, span3 = plan["rec_span0"], plan["span3"]
-    span0_all = torch.from_numpy(np.concatenate([span0_host[r0:r1 + 1] - span0_host[r0] for r0, r1 in runs])).to(dev)
-    tags_dev, known_dev = torch.from_numpy(plan["targets"]).to(dev), torch.from_numpy(plan["known"]).to(dev)
-    model.to(dev)
-    model.train()
-    n_batches, n_ran = len(runs), 0
-    loss_sum = torch.zeros((), dtype=torch.float32, device=dev)
-    err_all = torch.zeros(1, dtype=torch.int32, device=dev)
-    for i, k in enumerate(order):
-        if plan["counts"][k] == 0:
-            continue
-        optimizer.zero_grad()
-        loss, err = span_tags_loss(long_set, tags_dev, known_dev, model, runs[k],
-                                   (int(k), at, win0_all, frame0_all, span0_all, span0_host, plan["counts"]), span3)
-        loss.backward()
-        optimizer.step()
-        if ema_model is not None:
-            update_ema_variables(model, ema_model, 0.999, int(epoch) * n_batches + i)
-        loss_sum += loss.detach()
-        err_all |= err
-        n_ran += 1
-    mean = float(loss_sum.item()) / n_ran
-    bits = int(err_all.item())
-    if bits:
-        raise _lib.SedError(f"train_span_tags: the pooling kernels raised error bits {bits} (16: malformed tables, 32: a "
-                            "recording its windows do not cover)")
-    assert not (mean != mean or mean > 1e5), 'Loss explosion: {}'.format(mean)
-    if log is not None:
-        log('Epoch: {}\tTime {:.2f}\tspan_tag_loss {:.4g}'.format(epoch, time.time() - start, mean))
-    return mean
+    assert long_set.tag_batches(max_windows)[0] == plan["runs"]
+    return _tags_epoch("train_span_tags", "span_tag_loss", long_set, plan["targets"], plan["known"], plan["counts"],
+                       (plan["span3"], plan["rec_span0"]), model, optimizer, epoch, ema_model, max_windows, seed, log)

@@ -276,6 +276,31 @@ def test_two_calls_and_a_graph_replay_give_identical_bytes():
         assert first["ds"].tobytes() == other["ds"].tobytes() and first["da"].tobytes() == other["da"].tobytes()
 
 
+# ---- the autograd node -------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("NC", [10, 12])
+def test_pooled_tags_backward_gives_the_bytes_of_the_direct_call(NC):
+    from dcase2019_task4_amd.inference import pooled_tags, stitch_weak
+    T3, hop3 = 8, 3
+    L3s = [_tile() + 9, 5, 40]
+    rec_win0, rec_frame0 = _tables(L3s, T3, hop3)
+    rs = np.random.RandomState(211 + NC)
+    p, a = _inputs(rs, rec_win0[-1], T3, NC)
+    tp, ta = torch.from_numpy(p).cuda().requires_grad_(True), torch.from_numpy(a).cuda().requires_grad_(True)
+    w0, f0 = torch.from_numpy(rec_win0).cuda(), torch.from_numpy(rec_frame0).cuda()
+    weak, err = pooled_tags(tp, ta, w0, f0, int(rec_frame0[-1]), hop3, n_win=int(rec_win0[-1]))
+    plain = stitch_weak(tp.detach(), ta.detach(), w0, f0, int(rec_frame0[-1]), hop3, want_sums=True)
+    assert weak.requires_grad and torch.equal(weak.detach(), plain["weak"])
+    g = rs.standard_normal((len(L3s), NC)).astype(np.float32)
+    weak.backward(torch.from_numpy(g).cuda())
+    torch.cuda.synchronize()
+    assert int(err.item()) == 0 and int(plain["err"].item()) == 0
+    call = BwdCall(p, a, rec_win0, rec_frame0, hop3, 1, g)
+    call.sums = plain["sums"]                                                    # stitch_weak's own sums, not the helper's forward
+    want = call.run()
+    assert want["err"] == 0 and want["ds"].any() and want["da"].any()
+    assert tp.grad.cpu().numpy().tobytes() == want["ds"].tobytes() and ta.grad.cpu().numpy().tobytes() == want["da"].tobytes()
+
+
 # ---- sed_crnn_backward_att -----------------------------------------------------------------------------------------------------------
 WIDTHS = [dict(), dict(C=128, H=256)]
 WIDTH_IDS = ["base", "wide"]

@@ -183,6 +183,26 @@ def stats(v):
     return {"median_ms": med, "spread": float((v.max() - v.min()) / med), "samples_ms": [float(x) for x in v]}
 
 
+def alternate_legs(legs, rounds):
+    """One warm-up call of every leg, then the legs alternated for ``rounds`` rounds under the host clock: {leg: stats}."""
+    for fn in legs.values():
+        fn()
+    ms = {leg: [] for leg in legs}
+    for _ in range(rounds):
+        for leg, fn in legs.items():
+            ms[leg].append(wall_ms(fn))
+    return {leg: stats(ms[leg]) for leg in legs}
+
+
+def addition(out, key, a, b):
+    """What leg ``b`` adds to leg ``a`` (their ``stats``), written to ``out``: the difference of the medians as ``key``, the
+    larger (max - min) of the two legs, and whether the difference exceeds it."""
+    band = max(max(x["samples_ms"]) - min(x["samples_ms"]) for x in (a, b))
+    out[key] = b["median_ms"] - a["median_ms"]
+    out["larger_max_minus_min_ms"] = band
+    out["addition_exceeds_spread"] = bool(out[key] > band)
+
+
 def decode_alone(model, ls, reps):
     """The four launches of sed_stitch_decode on the set's real window posteriors, one device-event pair per call."""
     _, _, win_strong = inference.get_long_predictions(model, ls, _Enc.labels, batch_size=BATCH, return_posteriors=True)
@@ -606,13 +626,7 @@ def hysteresis_workload(name, model, rounds, reps):
                                                                                           batch_size=BATCH)),
             "validate_long_50_hysteresis": lambda: state.__setitem__("hyst", metrics.validate_long(
                 model, ls, ref_ev, lo50, [window], batch_size=BATCH, thresholds_high=hi50))}
-    for fn in legs.values():
-        fn()
-    ms = {leg: [] for leg in legs}
-    for _ in range(rounds):
-        for leg, fn in legs.items():
-            ms[leg].append(wall_ms(fn))
-    t = {leg: stats(ms[leg]) for leg in legs}
+    t = alternate_legs(legs, rounds)
     a, b = t["validate_long_50"], t["validate_long_50_hysteresis"]
     band = max(max(x["samples_ms"]) - min(x["samples_ms"]) for x in (a, b))
     t["difference"] = {"added_ms": b["median_ms"] - a["median_ms"], "larger_max_minus_min_ms": band,
@@ -687,13 +701,7 @@ def process_workload(name, model, rounds, reps, seconds=(0.25, 0.15), order="dro
             "validate_long_50_process": lambda: state.__setitem__("proc", metrics.validate_long(
                 model, ls, ref_ev, thr50, [window], batch_size=BATCH, min_event_lengths=[seconds[0]], min_event_gaps=[seconds[1]],
                 process_order=order))}
-    for fn in legs.values():
-        fn()
-    ms = {leg: [] for leg in legs}
-    for _ in range(rounds):
-        for leg, fn in legs.items():
-            ms[leg].append(wall_ms(fn))
-    t = {leg: stats(ms[leg]) for leg in legs}
+    t = alternate_legs(legs, rounds)
     a, b = t["validate_long_50"], t["validate_long_50_process"]
     band = max(max(x["samples_ms"]) - min(x["samples_ms"]) for x in (a, b))
     t["difference"] = {"added_ms": b["median_ms"] - a["median_ms"], "larger_max_minus_min_ms": band,
@@ -794,13 +802,7 @@ def scores_workload(name, model, rounds, reps, boundary_libs):
                 model, ls, enc, POOL, batch_size=BATCH, median_window=window)),
             "get_long_predictions_event_scores": lambda: state.__setitem__("scored", inference.get_long_predictions(
                 model, ls, enc, POOL, batch_size=BATCH, median_window=window, event_scores=True))}
-    for fn in legs.values():
-        fn()
-    ms = {leg: [] for leg in legs}
-    for _ in range(rounds):
-        for leg, fn in legs.items():
-            ms[leg].append(wall_ms(fn))
-    t = {leg: stats(ms[leg]) for leg in legs}
+    t = alternate_legs(legs, rounds)
     a, b = t["get_long_predictions"], t["get_long_predictions_event_scores"]
     band = max(max(x["samples_ms"]) - min(x["samples_ms"]) for x in (a, b))
     t["difference"] = {"added_ms": b["median_ms"] - a["median_ms"], "larger_max_minus_min_ms": band,
@@ -917,13 +919,7 @@ def span_tags_workload(name, model, rounds, reps, tag_span=10.0, min_tag=0.5):
     labels, state = _Enc.labels, {}
 
     def alternate(legs):
-        for fn in legs.values():
-            fn()
-        ms = {leg: [] for leg in legs}
-        for _ in range(rounds):
-            for leg, fn in legs.items():
-                ms[leg].append(wall_ms(fn))
-        t = {leg: stats(ms[leg]) for leg in legs}
+        t = alternate_legs(legs, rounds)
         a, b = (t[leg] for leg in legs)
         band = max(max(x["samples_ms"]) - min(x["samples_ms"]) for x in (a, b))
         t["difference"] = {"added_ms": b["median_ms"] - a["median_ms"], "larger_max_minus_min_ms": band,
@@ -1062,13 +1058,7 @@ def rasterize_workload(name, model, rounds, reps):
     kw = dict(pooling_time_ratio=POOL, batch_size=BATCH, threshold=thr50[0], median_window=window)
     legs = {"get_long_predictions": lambda: state.__setitem__("df", inference.get_long_predictions(model, ls, labels, **kw)),
             "pseudo_label": lambda: state.__setitem__("pl", inference.pseudo_label(model, ls, target, items, labels, **kw))}
-    for fn in legs.values():
-        fn()
-    ms = {leg: [] for leg in legs}
-    for _ in range(rounds):
-        for leg, fn in legs.items():
-            ms[leg].append(wall_ms(fn))
-    t = {leg: stats(ms[leg]) for leg in legs}
+    t = alternate_legs(legs, rounds)
     a, b = t["get_long_predictions"], t["pseudo_label"]
     band = max(max(x["samples_ms"]) - min(x["samples_ms"]) for x in (a, b))
     t["difference"] = {"pseudo_label_minus_predictions_ms": b["median_ms"] - a["median_ms"], "larger_max_minus_min_ms": band,
@@ -1092,19 +1082,8 @@ def weak_workload(name, model, rounds, reps):
     legs = {"predictions": lambda: inference.get_long_predictions(model, ls, labels, POOL, batch_size=BATCH),
             "predictions_with_weak": lambda: inference.get_long_predictions(model, ls, labels, POOL, batch_size=BATCH,
                                                                             return_weak=True)}
-    for fn in legs.values():
-        fn()
-    ms = {leg: [] for leg in legs}
-    for _ in range(rounds):
-        for leg, fn in legs.items():
-            ms[leg].append(wall_ms(fn))
-    for leg in legs:
-        out[leg] = stats(ms[leg])
-    a, b = out["predictions"], out["predictions_with_weak"]
-    band = max(max(x["samples_ms"]) - min(x["samples_ms"]) for x in (a, b))
-    out["weak_adds_ms"] = b["median_ms"] - a["median_ms"]
-    out["larger_max_minus_min_ms"] = band
-    out["addition_exceeds_spread"] = bool(out["weak_adds_ms"] > band)
+    out.update(alternate_legs(legs, rounds))
+    addition(out, "weak_adds_ms", out["predictions"], out["predictions_with_weak"])
     # ---- sed_stitch_weak alone against the route composed of earlier parts ----------------------------------------------------
     win_strong, win_att = inference.long_window_posteriors(model, ls, NCLASS, BATCH, want_attention=True)
     l, dev, ptr = _lib.lib(), win_strong.device, _lib.ptr
@@ -1147,11 +1126,9 @@ def weak_workload(name, model, rounds, reps):
     return out
 
 
-def tag_train_workload(name, model, rounds, reps):
-    """--tag-train: (a) sed_stitch_weak_backward alone against the torch-autograd restatement of blend + fp64 pooling, the only
-    route to the gradient before it; (b) where every recording fits one forward (100x3min): one train_recording_tags epoch
-    against the same batches' forward + backward + step with a plain window-level loss - what the pooled loss adds."""
-    from dcase2019_task4_amd import train
+def tag_train_setup(name, model):
+    """What --tag-train and --span-tag-train start from: the workload's set, the common ``out`` fields, the windows' posteriors
+    and attention in eval mode, gradient buffers for both and an error word."""
     n_rec, per = WORKLOADS[name]
     recs = recordings(n_rec, per)
     sc = scaler_of(recs[0])
@@ -1159,25 +1136,15 @@ def tag_train_workload(name, model, rounds, reps):
     out = {"recordings": n_rec, "windows": ls.n_clips, "timeline_frames": ls.total_frames, "hop3": ls.hop3, "T3": ls.T3}
     model.eval()
     win_strong, win_att = inference.long_window_posteriors(model, ls, NCLASS, BATCH, want_attention=True)
-    l, dev, ptr = _lib.lib(), win_strong.device, _lib.ptr
-    total, T3, hop3 = ls.total_frames, ls.T3, ls.hop3
-    g = torch.randn(n_rec, NCLASS, device=dev, generator=torch.Generator(dev).manual_seed(1))
-    weak = torch.empty(n_rec, NCLASS, device=dev)
-    sums = torch.empty(n_rec, NCLASS, 2, dtype=torch.float64, device=dev)
-    d_s, d_a = torch.empty_like(win_strong), torch.empty_like(win_att)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    ws = torch.empty(l.sed_stitch_weak_ws_bytes(total, n_rec, NCLASS), dtype=torch.uint8, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=win_strong.device)
+    return ls, out, win_strong, win_att, torch.empty_like(win_strong), torch.empty_like(win_att), err
 
-    def fused_fwd():
-        _lib.check(l.sed_stitch_weak(ptr(win_strong), ptr(win_att), ptr(ls.rec_win0), ptr(ls.rec_frame0), n_rec, T3, NCLASS, hop3, 1,
-                                     ptr(weak), ptr(sums), ptr(ws), ws.numel(), ptr(err), _lib.stream_ptr()), "sed_stitch_weak")
 
-    def fused_bwd():
-        _lib.check(l.sed_stitch_weak_backward(ptr(win_strong), ptr(win_att), ptr(ls.rec_win0), ptr(ls.rec_frame0), n_rec, T3, NCLASS,
-                                              hop3, 1, ptr(sums), ptr(g), ptr(d_s), ptr(d_a), ptr(err), _lib.stream_ptr()),
-                   "sed_stitch_weak_backward")
-    # the restatement's index tables: timeline frame and taper weight of every (window, local frame); frames past the end dropped
-    rec_of_win = np.repeat(np.arange(n_rec), np.diff(ls.rec_win0_host))
+def blend_tables(ls, dev):
+    """The index tables of the blend's torch restatement: per (window, local frame) that lies inside its recording the timeline
+    frame and the taper weight, the kept elements' flat indices, and the weight sum of every timeline frame."""
+    T3, hop3 = ls.T3, ls.hop3
+    rec_of_win = np.repeat(np.arange(ls.n_rec), np.diff(ls.rec_win0_host))
     j = np.arange(ls.n_clips) - ls.rec_win0_host[rec_of_win]
     v = np.arange(T3)
     u = j[:, None] * hop3 + v[None, :]
@@ -1185,17 +1152,23 @@ def tag_train_workload(name, model, rounds, reps):
     frame = torch.from_numpy((ls.rec_frame0_host[rec_of_win][:, None] + u)[ok]).to(dev)
     wt = torch.from_numpy(np.broadcast_to(np.minimum(v + 1, T3 - v).astype(np.float32), u.shape)[ok]).to(dev)
     keep = torch.from_numpy(np.flatnonzero(ok.reshape(-1))).to(dev)
-    rec_of_frame = torch.from_numpy(np.repeat(np.arange(n_rec), np.diff(ls.rec_frame0_host))).to(dev)
-    wsum = torch.zeros(total, device=dev).index_add_(0, frame, wt)
+    return frame, wt, keep, torch.zeros(ls.total_frames, device=dev).index_add_(0, frame, wt)
+
+
+def fused_against_composed(out, ls, win_strong, win_att, g, pool, fused_fwd, fused_bwd, bwd_key, d_s, d_a, err, reps):
+    """The fused backward call alone (``out[bwd_key]``), and the forward + backward pair, against the torch-autograd restatement:
+    the blend by index_add_ over ``blend_tables``, then ``pool(P, A) -> (num, den)``, the workload's own fp64 pooling of the two
+    blended timelines into the rows ``g`` weighs.  Writes the four timings, the largest difference of the two routes' gradients
+    (the fused ones are in ``d_s`` / ``d_a``) and, for either pair, the difference, the band and whether fused is faster."""
+    dev, total = win_strong.device, ls.total_frames
+    frame, wt, keep, wsum = blend_tables(ls, dev)
     state = {}
 
     def composed_fwd():
         ps, pa = win_strong.detach().requires_grad_(True), win_att.detach().requires_grad_(True)
         tl = [torch.zeros(total, NCLASS, device=dev).index_add_(0, frame, wt[:, None] * x.reshape(-1, NCLASS)[keep]) / wsum[:, None]
               for x in (ps, pa)]
-        P, A = tl[0].double(), tl[1].double()
-        num = torch.zeros(n_rec, NCLASS, dtype=torch.float64, device=dev).index_add_(0, rec_of_frame, P * A)
-        den = torch.zeros(n_rec, NCLASS, dtype=torch.float64, device=dev).index_add_(0, rec_of_frame, A)
+        num, den = pool(tl[0].double(), tl[1].double())
         state["in"], state["loss"] = (ps, pa), (g * (num / den).float()).sum()
 
     def composed_bwd():
@@ -1208,31 +1181,69 @@ def tag_train_workload(name, model, rounds, reps):
         return call
     fused_fwd()
     composed_fwd()
-    out["sed_stitch_weak_backward_alone"] = event_ms(fused_bwd, reps)
+    out[bwd_key] = event_ms(fused_bwd, reps)
     out["composed_backward_alone"] = event_ms(composed_bwd, reps)
     out["fused_forward_plus_backward"] = event_ms(both(fused_fwd, fused_bwd), reps)
     out["composed_forward_plus_backward"] = event_ms(both(composed_fwd, composed_bwd), reps)
     assert int(err.item()) == 0
-    scale = [float(x.abs().max().item()) for x in state["grads"]]
     out["max_abs_difference_of_the_two_routes"] = {"d_win_strong": float((d_s - state["grads"][0]).abs().max().item()),
                                                    "d_win_att": float((d_a - state["grads"][1]).abs().max().item()),
-                                                   "largest_gradient": scale}
-    for a, b, key in (("sed_stitch_weak_backward_alone", "composed_backward_alone", "backward"),
+                                                   "largest_gradient": [float(x.abs().max().item()) for x in state["grads"]]}
+    for a, b, key in ((bwd_key, "composed_backward_alone", "backward"),
                       ("fused_forward_plus_backward", "composed_forward_plus_backward", "forward_plus_backward")):
         band = max(x["spread"] * x["median_ms"] for x in (out[a], out[b]))
         out[key + "_composed_minus_fused_ms"] = out[b]["median_ms"] - out[a]["median_ms"]
         out[key + "_larger_max_minus_min_ms"] = band
         out[key + "_fused_faster"] = bool(out[key + "_composed_minus_fused_ms"] > band)
-    del state, win_strong, win_att, d_s, d_a
-    # ---- (b) an epoch on recording tags against the same epoch with a window-level loss ------------------------------------------
+
+
+def tag_epoch_setup(out, ls, model):
+    """The optimizer and the runs of the epoch legs, or None (said in ``out``) where a recording does not fit one forward."""
+    from dcase2019_task4_amd import train
     if int(np.diff(ls.rec_win0_host).max()) > BATCH:
         out["epoch"] = "not measured: a recording has more windows than one forward holds (max_windows)"
-        return out
-    tags = (np.random.default_rng(2).random((n_rec, NCLASS)) < 0.2).astype(np.float32)
-    tags_dev = torch.from_numpy(tags).to(dev)
-    opt = torch.optim.Adam(model.parameters(), lr=1e-5)
+        return None
     runs, _ = train.recording_tag_batches(np.diff(ls.rec_win0_host), BATCH, 0, 0)
     out["batches_per_epoch"], out["max_windows"] = len(runs), BATCH
+    return torch.optim.Adam(model.parameters(), lr=1e-5), runs
+
+
+def tag_train_workload(name, model, rounds, reps):
+    """--tag-train: (a) sed_stitch_weak_backward alone against the torch-autograd restatement of blend + fp64 pooling, the only
+    route to the gradient before it; (b) where every recording fits one forward (100x3min): one train_recording_tags epoch
+    against the same batches' forward + backward + step with a plain window-level loss - what the pooled loss adds."""
+    from dcase2019_task4_amd import train
+    ls, out, win_strong, win_att, d_s, d_a, err = tag_train_setup(name, model)
+    l, dev, ptr = _lib.lib(), win_strong.device, _lib.ptr
+    n_rec, total, T3, hop3 = ls.n_rec, ls.total_frames, ls.T3, ls.hop3
+    g = torch.randn(n_rec, NCLASS, device=dev, generator=torch.Generator(dev).manual_seed(1))
+    weak = torch.empty(n_rec, NCLASS, device=dev)
+    sums = torch.empty(n_rec, NCLASS, 2, dtype=torch.float64, device=dev)
+    ws = torch.empty(l.sed_stitch_weak_ws_bytes(total, n_rec, NCLASS), dtype=torch.uint8, device=dev)
+
+    def fused_fwd():
+        _lib.check(l.sed_stitch_weak(ptr(win_strong), ptr(win_att), ptr(ls.rec_win0), ptr(ls.rec_frame0), n_rec, T3, NCLASS, hop3, 1,
+                                     ptr(weak), ptr(sums), ptr(ws), ws.numel(), ptr(err), _lib.stream_ptr()), "sed_stitch_weak")
+
+    def fused_bwd():
+        _lib.check(l.sed_stitch_weak_backward(ptr(win_strong), ptr(win_att), ptr(ls.rec_win0), ptr(ls.rec_frame0), n_rec, T3, NCLASS,
+                                              hop3, 1, ptr(sums), ptr(g), ptr(d_s), ptr(d_a), ptr(err), _lib.stream_ptr()),
+                   "sed_stitch_weak_backward")
+    rec_of_frame = torch.from_numpy(np.repeat(np.arange(n_rec), np.diff(ls.rec_frame0_host))).to(dev)
+
+    def pool(P, A):
+        return (torch.zeros(n_rec, NCLASS, dtype=torch.float64, device=dev).index_add_(0, rec_of_frame, P * A),
+                torch.zeros(n_rec, NCLASS, dtype=torch.float64, device=dev).index_add_(0, rec_of_frame, A))
+    fused_against_composed(out, ls, win_strong, win_att, g, pool, fused_fwd, fused_bwd, "sed_stitch_weak_backward_alone", d_s, d_a,
+                           err, reps)
+    del win_strong, win_att, d_s, d_a
+    # ---- (b) an epoch on recording tags against the same epoch with a window-level loss ------------------------------------------
+    epoch_setup = tag_epoch_setup(out, ls, model)
+    if epoch_setup is None:
+        return out
+    opt, runs = epoch_setup
+    tags = (np.random.default_rng(2).random((n_rec, NCLASS)) < 0.2).astype(np.float32)
+    tags_dev = torch.from_numpy(tags).to(dev)
     epoch = [0]
 
     def pooled():
@@ -1252,20 +1263,8 @@ def tag_train_workload(name, model, rounds, reps):
             opt.step()
             loss_sum += loss.detach()
         loss_sum.item()
-    legs = {"epoch_window_level_loss": windowed, "epoch_recording_tags": pooled}
-    for fn in legs.values():
-        fn()
-    ms = {leg: [] for leg in legs}
-    for _ in range(rounds):
-        for leg, fn in legs.items():
-            ms[leg].append(wall_ms(fn))
-    for leg in legs:
-        out[leg] = stats(ms[leg])
-    a, b = out["epoch_window_level_loss"], out["epoch_recording_tags"]
-    band = max(max(x["samples_ms"]) - min(x["samples_ms"]) for x in (a, b))
-    out["pooled_loss_adds_ms"] = b["median_ms"] - a["median_ms"]
-    out["larger_max_minus_min_ms"] = band
-    out["addition_exceeds_spread"] = bool(out["pooled_loss_adds_ms"] > band)
+    out.update(alternate_legs({"epoch_window_level_loss": windowed, "epoch_recording_tags": pooled}, rounds))
+    addition(out, "pooled_loss_adds_ms", out["epoch_window_level_loss"], out["epoch_recording_tags"])
     return out
 
 
@@ -1275,20 +1274,12 @@ def span_tag_train_workload(name, model, rounds, reps, tag_span=10.0):
     before it; (b) the same call at one span per recording beside sed_stitch_weak_backward on the same sums; (c) where every
     recording fits one forward (100x3min): one train_span_tags epoch against train_recording_tags over the same batches."""
     from dcase2019_task4_amd import train
-    n_rec, per = WORKLOADS[name]
-    recs = recordings(n_rec, per)
-    sc = scaler_of(recs[0])
-    ls = inference.LongRecordingSet.from_arrays(recs, T, scaler=sc, filenames=[f"{name}_{r}.wav" for r in range(n_rec)])
+    ls, out, win_strong, win_att, d_s, d_a, err = tag_train_setup(name, model)
+    out["tag_span_s"] = tag_span
     cfg = inference._Cfg
     span3 = inference.tag_span_frames(tag_span, POOL * cfg.hop_length / cfg.sample_rate)
-    out = {"recordings": n_rec, "windows": ls.n_clips, "timeline_frames": ls.total_frames, "hop3": ls.hop3, "T3": ls.T3,
-           "tag_span_s": tag_span}
-    model.eval()
-    win_strong, win_att = inference.long_window_posteriors(model, ls, NCLASS, BATCH, want_attention=True)
     l, dev, ptr = _lib.lib(), win_strong.device, _lib.ptr
-    total, T3, hop3 = ls.total_frames, ls.T3, ls.hop3
-    d_s, d_a = torch.empty_like(win_strong), torch.empty_like(win_att)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    n_rec, total, T3, hop3 = ls.n_rec, ls.total_frames, ls.T3, ls.hop3
 
     def span_calls(span3):
         """(forward, backward, state) of the two C calls at this span length, on buffers of their own."""
@@ -1310,55 +1301,15 @@ def span_tag_train_workload(name, model, rounds, reps, tag_span=10.0):
         return fwd, bwd, {"host": host, "n_spans": n_spans, "span3": span3, "g": g, "sums": sums}
     fused_fwd, fused_bwd, sp = span_calls(span3)
     out["span3"], out["total_spans"] = sp["span3"], sp["n_spans"]
-    # the restatement's index tables (tag_train_workload's), and the span lengths in timeline order
-    rec_of_win = np.repeat(np.arange(n_rec), np.diff(ls.rec_win0_host))
-    j = np.arange(ls.n_clips) - ls.rec_win0_host[rec_of_win]
-    v = np.arange(T3)
-    u = j[:, None] * hop3 + v[None, :]
     L3s = np.diff(ls.rec_frame0_host)
-    ok = u < L3s[rec_of_win][:, None]
-    frame = torch.from_numpy((ls.rec_frame0_host[rec_of_win][:, None] + u)[ok]).to(dev)
-    wt = torch.from_numpy(np.broadcast_to(np.minimum(v + 1, T3 - v).astype(np.float32), u.shape)[ok]).to(dev)
-    keep = torch.from_numpy(np.flatnonzero(ok.reshape(-1))).to(dev)
     lengths = torch.from_numpy(np.concatenate([np.minimum(sp["span3"], L - np.arange(0, L, sp["span3"])) for L in L3s])).to(dev)
     assert lengths.numel() == sp["n_spans"] and int(lengths.sum().item()) == total
-    wsum = torch.zeros(total, device=dev).index_add_(0, frame, wt)
-    state = {}
 
-    def composed_fwd():
-        ps, pa = win_strong.detach().requires_grad_(True), win_att.detach().requires_grad_(True)
-        tl = [torch.zeros(total, NCLASS, device=dev).index_add_(0, frame, wt[:, None] * x.reshape(-1, NCLASS)[keep]) / wsum[:, None]
-              for x in (ps, pa)]
-        P, A = tl[0].double(), tl[1].double()
-        num = torch.segment_reduce(P * A, "sum", lengths=lengths, axis=0, unsafe=True)
-        den = torch.segment_reduce(A, "sum", lengths=lengths, axis=0, unsafe=True)
-        state["in"], state["loss"] = (ps, pa), (sp["g"] * (num / den).float()).sum()
-
-    def composed_bwd():
-        state["grads"] = torch.autograd.grad(state["loss"], state["in"], retain_graph=True)
-
-    def both(a, b):
-        def call():
-            a()
-            b()
-        return call
-    fused_fwd()
-    composed_fwd()
-    out["sed_stitch_span_tags_backward_alone"] = event_ms(fused_bwd, reps)
-    out["composed_backward_alone"] = event_ms(composed_bwd, reps)
-    out["fused_forward_plus_backward"] = event_ms(both(fused_fwd, fused_bwd), reps)
-    out["composed_forward_plus_backward"] = event_ms(both(composed_fwd, composed_bwd), reps)
-    assert int(err.item()) == 0
-    out["max_abs_difference_of_the_two_routes"] = {"d_win_strong": float((d_s - state["grads"][0]).abs().max().item()),
-                                                   "d_win_att": float((d_a - state["grads"][1]).abs().max().item()),
-                                                   "largest_gradient": [float(x.abs().max().item()) for x in state["grads"]]}
-    for a, b, key in (("sed_stitch_span_tags_backward_alone", "composed_backward_alone", "backward"),
-                      ("fused_forward_plus_backward", "composed_forward_plus_backward", "forward_plus_backward")):
-        band = max(x["spread"] * x["median_ms"] for x in (out[a], out[b]))
-        out[key + "_composed_minus_fused_ms"] = out[b]["median_ms"] - out[a]["median_ms"]
-        out[key + "_larger_max_minus_min_ms"] = band
-        out[key + "_fused_faster"] = bool(out[key + "_composed_minus_fused_ms"] > band)
-    del state
+    def pool(P, A):
+        return (torch.segment_reduce(P * A, "sum", lengths=lengths, axis=0, unsafe=True),
+                torch.segment_reduce(A, "sum", lengths=lengths, axis=0, unsafe=True))
+    fused_against_composed(out, ls, win_strong, win_att, sp["g"], pool, fused_fwd, fused_bwd, "sed_stitch_span_tags_backward_alone",
+                           d_s, d_a, err, reps)
     # ---- (b) one span per recording, beside sed_stitch_weak_backward in the same run ---------------------------------------------
     one_fwd, one_bwd, one = span_calls(int(L3s.max()))
     assert one["n_spans"] == n_rec
@@ -1385,15 +1336,13 @@ def span_tag_train_workload(name, model, rounds, reps, tag_span=10.0):
     assert int(err.item()) == 0
     del span_bytes, win_strong, win_att, d_s, d_a
     # ---- (c) an epoch on span tags against the epoch on recording tags over the same batches -------------------------------------
-    if int(np.diff(ls.rec_win0_host).max()) > BATCH:
-        out["epoch"] = "not measured: a recording has more windows than one forward holds (max_windows)"
+    epoch_setup = tag_epoch_setup(out, ls, model)
+    if epoch_setup is None:
         return out
+    opt = epoch_setup[0]
     rng = np.random.default_rng(2)
     tags = (rng.random((n_rec, NCLASS)) < 0.2).astype(np.float32)
     span_tags = (rng.random((sp["n_spans"], NCLASS)) < 0.2).astype(np.float32)
-    opt = torch.optim.Adam(model.parameters(), lr=1e-5)
-    runs, _ = train.recording_tag_batches(np.diff(ls.rec_win0_host), BATCH, 0, 0)
-    out["batches_per_epoch"], out["max_windows"] = len(runs), BATCH
     epoch = [0]
 
     def rec_level():
@@ -1403,20 +1352,8 @@ def span_tag_train_workload(name, model, rounds, reps, tag_span=10.0):
     def span_level():
         train.train_span_tags(ls, span_tags, model, opt, epoch[0], span3=sp["span3"], max_windows=BATCH)
         epoch[0] += 1
-    legs = {"epoch_recording_tags": rec_level, "epoch_span_tags": span_level}
-    for fn in legs.values():
-        fn()
-    ms = {leg: [] for leg in legs}
-    for _ in range(rounds):
-        for leg, fn in legs.items():
-            ms[leg].append(wall_ms(fn))
-    for leg in legs:
-        out[leg] = stats(ms[leg])
-    a, b = out["epoch_recording_tags"], out["epoch_span_tags"]
-    band = max(max(x["samples_ms"]) - min(x["samples_ms"]) for x in (a, b))
-    out["span_tags_add_ms"] = b["median_ms"] - a["median_ms"]
-    out["larger_max_minus_min_ms"] = band
-    out["addition_exceeds_spread"] = bool(out["span_tags_add_ms"] > band)
+    out.update(alternate_legs({"epoch_recording_tags": rec_level, "epoch_span_tags": span_level}, rounds))
+    addition(out, "span_tags_add_ms", out["epoch_recording_tags"], out["epoch_span_tags"])
     return out
 
 
