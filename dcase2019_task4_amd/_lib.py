@@ -85,6 +85,11 @@ _SIGS = {
                                        C.c_int, _P, _P, _P, C.c_size_t, _P, _P]),
     "sed_stitch_span_tags_backward": (C.c_int, [_P, _P, _P, _P, _P, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                 C.c_int, _P, _P, _P, _P, _P, _P]),
+    "sed_stitch_piece_span_tags_ws_bytes": (C.c_size_t, [C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int]),
+    "sed_stitch_piece_span_tags": (C.c_int, [_P, _P, _P, _P, _P, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.c_int, C.c_int, _P, _P, _P, _P, C.c_size_t, _P, _P]),
+    "sed_stitch_piece_span_tags_backward": (C.c_int, [_P, _P, _P, _P, _P, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                      C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "sed_events_tag_scores": (C.c_int, [_P, C.c_longlong, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_longlong, C.c_longlong, _P, _P,
                                         _P]),
     "sed_event_counts": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P,

@@ -22,7 +22,10 @@
 // its transpose: the gradient of a loss on the pooled tags w.r.t. both window tensors, a clear and one tile pass, no atomics.
 // sed_stitch_span_tags pools the same tags per span of span3 frames: the two kernels of sed_stitch_weak over another tile
 // descriptor (StSpanArgs), slots span * ceil(span3 / ST_TILE) + k.  sed_stitch_span_tags_backward is the weak backward's two
-// kernels with the row of g / sums looked up per frame (StSpanBwdArgs).
+// kernels with the row of g / sums looked up per frame (StSpanBwdArgs).  sed_stitch_piece_span_tags and its backward are the
+// span pair with one more table, rec_span_off: a "recording" is then a PIECE of one - some consecutive spans and exactly the
+// windows that cover them -, its first span starts at local frame rec_span_off[r], and the frames in front of its first and
+// behind its last span belong to no span (StPieceArgs, StPieceBwdArgs).
 //
 // Where a tile lives: the tiles of recording r take slots slot0(r) + k, slot0(r) = floor(rec_frame0[r] / ST_TILE) + r.  That
 // is strictly increasing in (r, k) for increasing rec_frame0, needs no table of its own and at most
@@ -506,14 +509,30 @@ struct StSpanArgs {
     long long total_spans;
     int span3, tps;
 };
+// sed_stitch_piece_span_tags: the span call over PIECES.  Piece r owns the windows and local frames 0 .. L3_r of its table rows
+// like a recording, and n_r = rec_span0[r + 1] - rec_span0[r] >= 1 spans of which span k covers the local frames
+// [off_r + k * span3, min(off_r + (k + 1) * span3, L3_r)), off_r = rec_span_off[r] >= 0: n_r need not be ceil(L3_r / span3), the
+// frames below off_r and from off_r + n_r * span3 on belong to no span.  Everything else is the span call's, in the same code.
+struct StPieceArgs {
+    StSpanArgs s;
+    const int32_t* rec_span_off;         // [n_rec]
+};
 __host__ __device__ __forceinline__ const StWeakArgs& sw_args(const StWeakArgs& a) { return a; }
 __host__ __device__ __forceinline__ const StWeakArgs& sw_args(const StSpanArgs& a) { return a.w; }
+__host__ __device__ __forceinline__ const StWeakArgs& sw_args(const StPieceArgs& a) { return a.s.w; }
+__host__ __device__ __forceinline__ const StSpanArgs& sp_args(const StSpanArgs& a) { return a; }
+__host__ __device__ __forceinline__ const StSpanArgs& sp_args(const StPieceArgs& a) { return a.s; }
+template <class Args> constexpr bool sw_spans = std::is_same<Args, StSpanArgs>::value || std::is_same<Args, StPieceArgs>::value;
 
 // Span g of the tables: the recording that holds it (one bisection over rec_span0: the last r with rec_span0[r] <= g), validated
 // - the recording as st_rec does, its spans against ceil(L3 / span3) and total_spans, g inside them - and the span's frames
-// [s, e) of that recording's timeline.  bad: 0, or the err bits that make the span's row NaN.  Wave-uniform.
+// [s, e) of that recording's timeline.  bad: 0, or the err bits that make the span's row NaN.  Wave-uniform.  A piece
+// (StPieceArgs) is validated by off >= 0, n >= 1 and off + (n - 1) * span3 < L3 in the place of the ceil rule: its last span
+// then holds a frame.
 struct StSpan { StRec R; int r, s, e, bad; };
-__device__ __forceinline__ StSpan st_span_of(const StSpanArgs& sa, int r, long long g) {      // span g as one of recording r's
+template <class Args>
+__device__ __forceinline__ StSpan st_span_of(const Args& args, int r, long long g) {          // span g as one of recording r's
+    const StSpanArgs& sa = sp_args(args);
     StSpan S;
     S.r = r;
     S.R = st_rec(sa.w.t, r);
@@ -521,21 +540,34 @@ __device__ __forceinline__ StSpan st_span_of(const StSpanArgs& sa, int r, long l
     S.bad = S.R.bad;
     if (S.bad) return S;
     const long long p0 = sa.rec_span0[r], p1 = sa.rec_span0[r + 1];
-    const long long n_spans = ((long long)S.R.L3 + sa.span3 - 1) / sa.span3;
-    if (p0 < 0 || p1 - p0 != n_spans || p1 > sa.total_spans || g < p0 || g >= p1) { S.bad = 16; return S; }
-    const long long s = (g - p0) * sa.span3;                                     // < L3: g - p0 < ceil(L3 / span3)
+    long long s;
+    if constexpr (std::is_same<Args, StPieceArgs>::value) {
+        const long long off = args.rec_span_off[r];
+        // (in this order: 0 <= p0 < p1 <= total_spans < 2^31 first, so the product stays below 2^62)
+        if (p0 < 0 || p1 > sa.total_spans || p1 <= p0 || off < 0 || off + (p1 - p0 - 1) * sa.span3 >= S.R.L3 || g < p0 || g >= p1) {
+            S.bad = 16;
+            return S;
+        }
+        s = off + (g - p0) * sa.span3;                                           // < L3: g - p0 <= n - 1
+    } else {
+        const long long n_spans = ((long long)S.R.L3 + sa.span3 - 1) / sa.span3;
+        if (p0 < 0 || p1 - p0 != n_spans || p1 > sa.total_spans || g < p0 || g >= p1) { S.bad = 16; return S; }
+        s = (g - p0) * sa.span3;                                                 // < L3: g - p0 < ceil(L3 / span3)
+    }
     S.s = (int)s;
     S.e = (int)min(s + sa.span3, (long long)S.R.L3);
     return S;
 }
-__device__ __forceinline__ StSpan st_span(const StSpanArgs& sa, long long g) {
+template <class Args>
+__device__ __forceinline__ StSpan st_span(const Args& args, long long g) {
+    const StSpanArgs& sa = sp_args(args);
     int lo_r = 0, hi_r = sa.w.t.n_rec - 1;
     while (lo_r < hi_r) {
         const int mid = (lo_r + hi_r + 1) >> 1;
         if (sa.rec_span0[mid] <= g) lo_r = mid;
         else hi_r = mid - 1;
     }
-    return st_span_of(sa, lo_r, g);
+    return st_span_of(args, lo_r, g);
 }
 
 template <bool VEC, int W, class Args>
@@ -546,8 +578,9 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_tile(Args args) {
     const StTables& a = wa.t;
     const int tid = threadIdx.x, NC = a.NC;
     StTile T;
-    if constexpr (std::is_same<Args, StSpanArgs>::value) {                       // frame 0 of the tile walk is the span's first frame
-        const long long g = blockIdx.x / args.tps, kt = blockIdx.x - g * args.tps;
+    if constexpr (sw_spans<Args>) {                                              // frame 0 of the tile walk is the span's first frame
+        const int tps = sp_args(args).tps;
+        const long long g = blockIdx.x / tps, kt = blockIdx.x - g * tps;
         const StSpan S = st_span(args, g);
         const long long s = (long long)S.s + kt * ST_TILE;
         if (S.bad || s >= S.e) return;
@@ -619,21 +652,21 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_cols(Args args) {
     const long long col = (long long)blockIdx.x * (ST_THREADS / 64) + (threadIdx.x >> 6);
     long long n_rows = a.n_rec, slot0 = 0;
     int bad = 0, tiles = 0;
-    if constexpr (std::is_same<Args, StSpanArgs>::value) {
-        n_rows = args.total_spans;
+    if constexpr (sw_spans<Args>) {
+        n_rows = sp_args(args).total_spans;
         if (col < a.n_rec && lane == 0) {
-            const StSpan S = st_span_of(args, (int)col, args.rec_span0[col]);    // (its first span, if it has one)
+            const StSpan S = st_span_of(args, (int)col, sp_args(args).rec_span0[col]);    // (its first span, if it has one)
             if (S.bad) atomicOr(a.err, S.bad);
         }
     }
     if (col >= n_rows * a.NC) return;
     const long long r = col / a.NC;
     const int c = (int)(col - r * a.NC);
-    if constexpr (std::is_same<Args, StSpanArgs>::value) {
+    if constexpr (sw_spans<Args>) {
         const StSpan S = st_span(args, r);
         bad = S.bad;
         tiles = (S.e - S.s + ST_TILE - 1) / ST_TILE;
-        slot0 = r * args.tps;
+        slot0 = r * sp_args(args).tps;
     } else {
         const StRec R = st_rec(a, (int)r);
         bad = R.bad;
@@ -664,8 +697,8 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_cols(Args args) {
 
 static size_t sw_ws_per_slot(int NC) { return (size_t)NC * 2 * sizeof(double); }
 
-// The two launches of sed_stitch_weak (Args = StWeakArgs) and of sed_stitch_span_tags (StSpanArgs): n_tiles workgroups of the
-// tile pass, one wave per column of the column pass.
+// The two launches of sed_stitch_weak (Args = StWeakArgs), of sed_stitch_span_tags (StSpanArgs) and of
+// sed_stitch_piece_span_tags (StPieceArgs): n_tiles workgroups of the tile pass, one wave per column of the column pass.
 template <class Args>
 static int sw_launch(const Args& args, unsigned n_tiles, long long n_waves, void* stream) {
     const StWeakArgs& wa = sw_args(args);
@@ -718,23 +751,57 @@ extern "C" size_t sed_stitch_span_tags_ws_bytes(long long total_frames, long lon
     return n * sw_ws_per_slot(nclass);
 }
 
-extern "C" int sed_stitch_span_tags(const float* win_strong, const float* win_att, const int32_t* rec_win0,
-                                    const int64_t* rec_frame0, const int64_t* rec_span0, long long total_frames,
-                                    long long total_spans, int n_rec, int T3, int NC, int hop3, int weighting, int span3,
-                                    float* tags, double* sums, void* ws, size_t ws_bytes, int32_t* err, void* stream) {
-    const char* what = "sed_stitch_span_tags";
-    ST_NEED(win_strong && win_att && rec_win0 && rec_frame0 && rec_span0 && tags && ws && err, "null argument");
+// The host side of sed_stitch_span_tags (rec_span_off null) and of sed_stitch_piece_span_tags.
+static int sp_run(const char* what, const float* win_strong, const float* win_att, const int32_t* rec_win0, const int64_t* rec_frame0,
+                  const int64_t* rec_span0, const int32_t* rec_span_off, long long total_frames, long long total_spans, int n_rec,
+                  int T3, int NC, int hop3, int weighting, int span3, float* tags, double* sums, void* ws, size_t ws_bytes,
+                  int32_t* err, void* stream) {
     StTables t;
     SED_TRY(st_front(what, rec_win0, rec_frame0, err, n_rec, T3, NC, hop3, weighting, 1, 31, &t));
     ST_NEED(((uintptr_t)ws % 8) == 0, "ws must be 8-byte aligned");
     const size_t n_slots = sp_slot_count(total_frames, total_spans, n_rec, NC, span3);
     ST_NEED(n_slots, "need span3 >= 1, n_rec <= total_spans <= total_frames, total_frames * NC < 2^31 and "
                      "total_spans * ceil(span3 / tile) < 2^31");
-    ST_NEED(ws_bytes == n_slots * sw_ws_per_slot(NC), "ws_bytes must be the value sed_stitch_span_tags_ws_bytes returned for these sizes");
+    if (ws_bytes != n_slots * sw_ws_per_slot(NC)) {
+        sed_set_error("%s: ws_bytes must be the value %s_ws_bytes returned for these sizes", what, what);
+        return SED_ERR_BAD_ARG;
+    }
     t.n_slots = 0x7fffffff;                                                      // (st_rec's slot check is the recording layout's)
     const StSpanArgs sa = {{t, win_strong, win_att, (double*)ws, tags, sums}, rec_span0, total_spans, span3, (int)sp_tps(span3)};
-    const long long rows = total_spans * NC;
-    return sw_launch(sa, (unsigned)n_slots, rows > n_rec ? rows : n_rec, stream);
+    const long long rows = total_spans * NC, n_waves = rows > n_rec ? rows : n_rec;
+    if (!rec_span_off) return sw_launch(sa, (unsigned)n_slots, n_waves, stream);
+    const StPieceArgs pa = {sa, rec_span_off};
+    return sw_launch(pa, (unsigned)n_slots, n_waves, stream);
+}
+
+extern "C" int sed_stitch_span_tags(const float* win_strong, const float* win_att, const int32_t* rec_win0,
+                                    const int64_t* rec_frame0, const int64_t* rec_span0, long long total_frames,
+                                    long long total_spans, int n_rec, int T3, int NC, int hop3, int weighting, int span3,
+                                    float* tags, double* sums, void* ws, size_t ws_bytes, int32_t* err, void* stream) {
+    const char* what = "sed_stitch_span_tags";
+    ST_NEED(win_strong && win_att && rec_win0 && rec_frame0 && rec_span0 && tags && ws && err, "null argument");
+    return sp_run(what, win_strong, win_att, rec_win0, rec_frame0, rec_span0, nullptr, total_frames, total_spans, n_rec, T3, NC,
+                  hop3, weighting, span3, tags, sums, ws, ws_bytes, err, stream);
+}
+
+// ---- span tags of pieces (sed_stitch_piece_span_tags) ------------------------------------------------------------------------
+extern "C" size_t sed_stitch_piece_span_tags_ws_bytes(long long total_frames, long long total_spans, int n_rec, int nclass,
+                                                      int span3) {
+    const size_t n = sp_slot_count(total_frames, total_spans, n_rec, nclass, span3);
+    if (!n) sed_set_error("sed_stitch_piece_span_tags_ws_bytes: need span3 >= 1, 1 <= n_rec <= total_spans <= total_frames, "
+                          "1 <= nclass <= 16, total_frames * nclass < 2^31, total_spans * ceil(span3 / %d) < 2^31", ST_TILE);
+    return n * sw_ws_per_slot(nclass);
+}
+
+extern "C" int sed_stitch_piece_span_tags(const float* win_strong, const float* win_att, const int32_t* rec_win0,
+                                          const int64_t* rec_frame0, const int64_t* rec_span0, long long total_frames,
+                                          long long total_spans, int n_rec, int T3, int NC, int hop3, int weighting, int span3,
+                                          const int32_t* rec_span_off, float* tags, double* sums, void* ws, size_t ws_bytes,
+                                          int32_t* err, void* stream) {
+    const char* what = "sed_stitch_piece_span_tags";
+    ST_NEED(win_strong && win_att && rec_win0 && rec_frame0 && rec_span0 && rec_span_off && tags && ws && err, "null argument");
+    return sp_run(what, win_strong, win_att, rec_win0, rec_frame0, rec_span0, rec_span_off, total_frames, total_spans, n_rec, T3,
+                  NC, hop3, weighting, span3, tags, sums, ws, ws_bytes, err, stream);
 }
 
 // ---- backward through the pooled tag (sed_stitch_weak_backward) ---------------------------------------------------------------
@@ -778,8 +845,15 @@ struct StSpanBwdArgs {
     long long total_spans;
     int span3;
 };
+// sed_stitch_piece_span_tags_backward (StPieceBwdArgs): frame u of piece r reads row rec_span0[r] + (u - off_r) / span3; a frame
+// with u < off_r or (u - off_r) / span3 >= n_r belongs to no span and its window elements keep the clear pass's +0.0f.
+struct StPieceBwdArgs {
+    StSpanBwdArgs s;
+    const int32_t* rec_span_off;         // [n_rec]
+};
 __host__ __device__ __forceinline__ const StWeakBwdArgs& sb_args(const StWeakBwdArgs& a) { return a; }
 __host__ __device__ __forceinline__ const StWeakBwdArgs& sb_args(const StSpanBwdArgs& a) { return a.w; }
+__host__ __device__ __forceinline__ const StWeakBwdArgs& sb_args(const StPieceBwdArgs& a) { return a.s.w; }
 
 // What keeps recording r (R = st_rec of it) out of the backward: R.bad, or 16 for span offsets the forward rejects.
 __device__ __forceinline__ int sb_rec_bad(const StWeakBwdArgs&, const StRec& R, int) { return R.bad; }
@@ -789,9 +863,23 @@ __device__ __forceinline__ int sb_rec_bad(const StSpanBwdArgs& sa, const StRec& 
     const long long n_spans = ((long long)R.L3 + sa.span3 - 1) / sa.span3;
     return (p0 < 0 || p1 > sa.total_spans || p1 < p0 || p1 - p0 != n_spans) ? 16 : 0;   // (in this order: no overflow)
 }
-// The row of g_weak / sums that frame u of (valid) recording r reads.
-__device__ __forceinline__ size_t sb_row(const StWeakBwdArgs&, int r, int) { return (size_t)r; }
-__device__ __forceinline__ size_t sb_row(const StSpanBwdArgs& sa, int r, int u) { return (size_t)(sa.rec_span0[r] + u / sa.span3); }
+__device__ __forceinline__ int sb_rec_bad(const StPieceBwdArgs& pa, const StRec& R, int r) {
+    if (R.bad) return R.bad;
+    const StSpanBwdArgs& sa = pa.s;
+    const long long p0 = sa.rec_span0[r], p1 = sa.rec_span0[r + 1], off = pa.rec_span_off[r];
+    return (p0 < 0 || p1 > sa.total_spans || p1 <= p0 || off < 0 || off + (p1 - p0 - 1) * sa.span3 >= R.L3) ? 16 : 0;   // (no overflow)
+}
+// The row of g_weak / sums that frame u of (valid) recording r reads; false: the frame belongs to no span (pieces only).
+__device__ __forceinline__ bool sb_row(const StWeakBwdArgs&, int r, int, size_t& row) { row = (size_t)r; return true; }
+__device__ __forceinline__ bool sb_row(const StSpanBwdArgs& sa, int r, int u, size_t& row) {
+    row = (size_t)(sa.rec_span0[r] + u / sa.span3);
+    return true;
+}
+__device__ __forceinline__ bool sb_row(const StPieceBwdArgs& pa, int r, int u, size_t& row) {
+    const long long p0 = pa.s.rec_span0[r], k = (long long)u - pa.rec_span_off[r];
+    row = (size_t)(p0 + k / pa.s.span3);
+    return k >= 0 && k / pa.s.span3 < pa.s.rec_span0[r + 1] - p0;
+}
 
 template <bool VEC, class Args>
 __global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_bwd_zero(Args args) {
@@ -829,14 +917,15 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_bwd_tile(Args args) 
     for (long long g = blockIdx.x; g < a.n_slots; g += gridDim.x) {
         StTile T;
         if (!st_tile(a, g, T)) continue;
-        if constexpr (std::is_same<Args, StSpanBwdArgs>::value) {
+        if constexpr (!std::is_same<Args, StWeakBwdArgs>::value) {
             if (sb_rec_bad(args, T.R, T.r)) continue;
         }
         for (int it = tid; it < (T.e - T.s) * G; it += ST_THREADS) {
             const int fl = it / G, q = it - fl * G, u = T.s + fl, col = W * q;
+            size_t row;
+            if (!sb_row(args, T.r, u, row)) continue;
             const f32x4 p = st_blend<VEC>(a, wa.win_strong, T.R, u, q);
             const f32x4 at = st_blend<VEC>(a, wa.win_att, T.R, u, q);
-            const size_t row = sb_row(args, T.r, u);
             double dP[W], dA[W];
 #pragma unroll
             for (int k = 0; k < W; ++k) {
@@ -872,7 +961,8 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_bwd_tile(Args args) 
     }
 }
 
-// The two launches of sed_stitch_weak_backward (Args = StWeakBwdArgs) and of sed_stitch_span_tags_backward (StSpanBwdArgs).
+// The two launches of sed_stitch_weak_backward (Args = StWeakBwdArgs), of sed_stitch_span_tags_backward (StSpanBwdArgs) and of
+// sed_stitch_piece_span_tags_backward (StPieceBwdArgs).
 template <class Args>
 static int sb_launch(const Args& args, void* stream) {
     const StWeakBwdArgs& wa = sb_args(args);
@@ -902,7 +992,23 @@ extern "C" int sed_stitch_weak_backward(const float* win_strong, const float* wi
     return sb_launch(wa, stream);
 }
 
-// ---- backward through the span tags (sed_stitch_span_tags_backward) -----------------------------------------------------------
+// ---- backward through the span tags (sed_stitch_span_tags_backward, sed_stitch_piece_span_tags_backward) ---------------------
+// The host side of both: rec_span_off null is the span entry.
+static int sb_run(const char* what, const float* win_strong, const float* win_att, const int32_t* rec_win0, const int64_t* rec_frame0,
+                  const int64_t* rec_span0, const int32_t* rec_span_off, long long total_spans, int n_rec, int T3, int NC, int hop3,
+                  int weighting, int span3, const double* sums, const float* g_tags, float* d_win_strong, float* d_win_att,
+                  int32_t* err, void* stream) {
+    StTables t;
+    SED_TRY(st_front(what, rec_win0, rec_frame0, err, n_rec, T3, NC, hop3, weighting, 1, 31, &t));
+    ST_NEED(span3 >= 1 && total_spans >= n_rec && total_spans < (1ll << 31) && total_spans * NC < (1ll << 31),
+            "need span3 >= 1, n_rec <= total_spans and total_spans * NC < 2^31");
+    ST_NEED(((uintptr_t)sums % 8) == 0, "sums must be 8-byte aligned");
+    const StSpanBwdArgs sa = {{t, win_strong, win_att, sums, g_tags, d_win_strong, d_win_att}, rec_span0, total_spans, span3};
+    if (!rec_span_off) return sb_launch(sa, stream);
+    const StPieceBwdArgs pa = {sa, rec_span_off};
+    return sb_launch(pa, stream);
+}
+
 extern "C" int sed_stitch_span_tags_backward(const float* win_strong, const float* win_att, const int32_t* rec_win0,
                                              const int64_t* rec_frame0, const int64_t* rec_span0, long long total_spans, int n_rec,
                                              int T3, int NC, int hop3, int weighting, int span3, const double* sums,
@@ -911,11 +1017,18 @@ extern "C" int sed_stitch_span_tags_backward(const float* win_strong, const floa
     const char* what = "sed_stitch_span_tags_backward";
     ST_NEED(win_strong && win_att && rec_win0 && rec_frame0 && rec_span0 && sums && g_tags && d_win_strong && d_win_att && err,
             "null argument");
-    StTables t;
-    SED_TRY(st_front(what, rec_win0, rec_frame0, err, n_rec, T3, NC, hop3, weighting, 1, 31, &t));
-    ST_NEED(span3 >= 1 && total_spans >= n_rec && total_spans < (1ll << 31) && total_spans * NC < (1ll << 31),
-            "need span3 >= 1, n_rec <= total_spans and total_spans * NC < 2^31");
-    ST_NEED(((uintptr_t)sums % 8) == 0, "sums must be 8-byte aligned");
-    const StSpanBwdArgs sa = {{t, win_strong, win_att, sums, g_tags, d_win_strong, d_win_att}, rec_span0, total_spans, span3};
-    return sb_launch(sa, stream);
+    return sb_run(what, win_strong, win_att, rec_win0, rec_frame0, rec_span0, nullptr, total_spans, n_rec, T3, NC, hop3, weighting,
+                  span3, sums, g_tags, d_win_strong, d_win_att, err, stream);
+}
+
+extern "C" int sed_stitch_piece_span_tags_backward(const float* win_strong, const float* win_att, const int32_t* rec_win0,
+                                                   const int64_t* rec_frame0, const int64_t* rec_span0, long long total_spans,
+                                                   int n_rec, int T3, int NC, int hop3, int weighting, int span3,
+                                                   const int32_t* rec_span_off, const double* sums, const float* g_tags,
+                                                   float* d_win_strong, float* d_win_att, int32_t* err, void* stream) {
+    const char* what = "sed_stitch_piece_span_tags_backward";
+    ST_NEED(win_strong && win_att && rec_win0 && rec_frame0 && rec_span0 && rec_span_off && sums && g_tags && d_win_strong &&
+                d_win_att && err, "null argument");
+    return sb_run(what, win_strong, win_att, rec_win0, rec_frame0, rec_span0, rec_span_off, total_spans, n_rec, T3, NC, hop3,
+                  weighting, span3, sums, g_tags, d_win_strong, d_win_att, err, stream);
 }

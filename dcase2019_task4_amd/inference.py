@@ -27,6 +27,9 @@ Span-level weak tags and the tag gate: ``stitch_span_tags`` / ``get_long_predict
 of time (``sed_stitch_span_tags``, ``span_table``, ``span_tags_dataframe``), ``events_tag_scores`` gives every event the largest
 tag of the spans it touches (``sed_events_tag_scores``) and ``gate_decoded`` / ``get_long_predictions(min_span_tag=...)`` keep
 the events that touch a confident span (``events_select`` on that score); ``pooled_span_tags`` is the span tag with a backward.
+Both take ``span_off``: the tables then describe PIECES of recordings - consecutive spans with exactly the windows that cover them
+(``longrec.span_pieces``; ``sed_stitch_piece_span_tags`` and its backward) - which is how ``train.train_span_tags(split_long=True)``
+trains on a recording with more windows than one forward holds.
 Both levels of pooled tags share one forward call, one backward call and one autograd node, in which a row description
 (``_tags_forward``) selects the level and with it the C entry.
 Pseudo strong labels: ``events_rasterize`` / ``rasterize_decoded`` turn any of these tables back into label rows
@@ -575,7 +578,9 @@ def _weak_inputs(who, win_strong, win_att, rec_win0, total_frames, hop3, weighti
 
 
 # The rows being pooled, ``rows`` below: None - one row per recording (``sed_stitch_weak`` / ``sed_stitch_weak_backward``) - or
-# ``(rec_span0 on the device, total_spans, span3, ws_bytes)`` (``sed_stitch_span_tags`` / ``sed_stitch_span_tags_backward``).
+# ``(rec_span0 on the device, total_spans, span3, ws_bytes, rec_span_off on the device or None)``: ``sed_stitch_span_tags`` /
+# ``sed_stitch_span_tags_backward`` without ``rec_span_off``, the piece entries ``sed_stitch_piece_span_tags`` /
+# ``sed_stitch_piece_span_tags_backward`` with it.
 def _tags_forward(win_strong, win_att, rec_win0, rec_frame0, total, hop3, weighting, rows, err, want_sums):
     """The one forward call of the pooled tags, on checked contiguous float32 window tensors: ``(tags, sums or None)``."""
     l = _lib.lib()
@@ -590,9 +595,13 @@ def _tags_forward(win_strong, win_att, rec_win0, rec_frame0, total, hop3, weight
     if rows is None:
         _lib.check(l.sed_stitch_weak(*head, n_rec, T3, NC, hop3, weighting, *tail), "sed_stitch_weak")
     else:
-        rec_span0, total_spans, span3, _ = rows
-        _lib.check(l.sed_stitch_span_tags(*head, _lib.ptr(rec_span0), total, total_spans, n_rec, T3, NC, hop3, weighting, span3,
-                                          *tail), "sed_stitch_span_tags")
+        rec_span0, total_spans, span3, _, span_off = rows
+        if span_off is None:
+            _lib.check(l.sed_stitch_span_tags(*head, _lib.ptr(rec_span0), total, total_spans, n_rec, T3, NC, hop3, weighting, span3,
+                                              *tail), "sed_stitch_span_tags")
+        else:
+            _lib.check(l.sed_stitch_piece_span_tags(*head, _lib.ptr(rec_span0), total, total_spans, n_rec, T3, NC, hop3, weighting,
+                                                    span3, _lib.ptr(span_off), *tail), "sed_stitch_piece_span_tags")
     return tags, sums
 
 
@@ -607,9 +616,14 @@ def _tags_backward(win_strong, win_att, rec_win0, rec_frame0, hop3, weighting, r
     if rows is None:
         _lib.check(l.sed_stitch_weak_backward(*head, n_rec, T3, NC, hop3, weighting, *tail), "sed_stitch_weak_backward")
     else:
-        rec_span0, total_spans, span3, _ = rows
-        _lib.check(l.sed_stitch_span_tags_backward(*head, _lib.ptr(rec_span0), total_spans, n_rec, T3, NC, hop3, weighting, span3,
-                                                   *tail), "sed_stitch_span_tags_backward")
+        rec_span0, total_spans, span3, _, span_off = rows
+        if span_off is None:
+            _lib.check(l.sed_stitch_span_tags_backward(*head, _lib.ptr(rec_span0), total_spans, n_rec, T3, NC, hop3, weighting,
+                                                       span3, *tail), "sed_stitch_span_tags_backward")
+        else:
+            _lib.check(l.sed_stitch_piece_span_tags_backward(*head, _lib.ptr(rec_span0), total_spans, n_rec, T3, NC, hop3, weighting,
+                                                             span3, _lib.ptr(span_off), *tail),
+                       "sed_stitch_piece_span_tags_backward")
     return d_strong, d_att
 
 
@@ -619,22 +633,23 @@ class _PooledTags(torch.autograd.Function):
     @staticmethod
     def forward(ctx, win_strong, win_att, rec_win0, rec_frame0, total, hop3, weighting, rows, err):
         tags, sums = _tags_forward(win_strong, win_att, rec_win0, rec_frame0, total, hop3, weighting, rows, err, True)
-        ctx.save_for_backward(win_strong, win_att, rec_win0, rec_frame0, sums, *(() if rows is None else rows[:1]))
+        tables = () if rows is None else tuple(t for t in (rows[0], rows[4]) if t is not None)
+        ctx.save_for_backward(win_strong, win_att, rec_win0, rec_frame0, sums, *tables)
         ctx.hop3, ctx.weighting, ctx.err = hop3, weighting, err          # (err: the library ORs into it, autograd never sees it)
-        ctx.rows = None if rows is None else rows[1:]
+        ctx.rows = None if rows is None else rows[1:4]
         return tags
 
     @staticmethod
     def backward(ctx, g_tags):
-        win_strong, win_att, rec_win0, rec_frame0, sums, *rec_span0 = ctx.saved_tensors
-        rows = None if ctx.rows is None else (rec_span0[0],) + ctx.rows
+        win_strong, win_att, rec_win0, rec_frame0, sums, *tables = ctx.saved_tensors
+        rows = None if ctx.rows is None else (tables[0],) + ctx.rows + (tables[1] if len(tables) > 1 else None,)
         return _tags_backward(win_strong, win_att, rec_win0, rec_frame0, ctx.hop3, ctx.weighting, rows, sums,
                               g_tags.contiguous().float(), ctx.err) + (None,) * 7
 
 
 def _pooled(who, win_strong, win_att, rec_win0, rec_frame0, total_frames, hop3, weighting, n_win, span=None):
     """``pooled_tags`` and ``pooled_span_tags``: the input checks, the tables' dtype / device check, the rows - one per recording,
-    or with ``span = (span3, rec_frame0_host, span_tables)`` those of ``_span_rows`` - and the node.  Returns ``(tags, err,
+    or with ``span = (span3, rec_frame0_host, span_tables[, span_off])`` those of ``_span_rows`` - and the node.  Returns ``(tags, err,
     _span_rows' dict or None)``."""
     total, hop3, weighting = _weak_inputs(who, win_strong, win_att, rec_win0, total_frames, hop3, weighting, n_win)
     if rec_win0.dtype != torch.int32 or rec_frame0.dtype != torch.int64 or rec_frame0.numel() != rec_win0.numel() or \
@@ -712,46 +727,76 @@ def span_table(long_set_or_L3s, span3, device=None):
     return host, dev_table, int(host[-1]), span3
 
 
-def _span_rows(win_strong, rec_win0, rec_frame0, total, span3, rec_frame0_host=None, span_tables=None):
+def _span_rows(win_strong, rec_win0, rec_frame0, total, span3, rec_frame0_host=None, span_tables=None, span_off=None):
     """The span table of a span-level call, resolved once: the recordings' lengths from ``rec_frame0_host`` (without it
     ``rec_frame0`` is copied to the host), then ``span_table``'s table copied to the device - or, with ``span_tables = (rec_span0
     host, rec_span0 on the device)``, the caller's, checked against the lengths on the host and nothing copied - and the
     workspace size (0: ``ValueError`` with the library's reason).  Returns ``(the keys rec_span0, rec_span0_host, total_spans
-    and span3 (clamped) of the fronts' dicts, the rows for _tags_forward)``."""
+    and span3 (clamped) of the fronts' dicts, the rows for _tags_forward)``.
+
+    ``span_off`` - a device int32 [n_rec] tensor, or ``(host, device)`` where the caller has both - makes the call one over
+    PIECES (include/dcase_sed.h: ``sed_stitch_piece_span_tags``): ``span_tables`` is then required and is the pieces' own
+    table, ``span3`` is taken as given, and what is checked on the host is the piece rule - ``off >= 0``, at least one span
+    per piece, ``off + (n - 1) * span3 < L3``."""
     if rec_frame0_host is None:
         rec_frame0_host = rec_frame0.cpu().numpy()
     L3s = np.diff(np.asarray(rec_frame0_host, dtype=np.int64).reshape(-1))
     n_rec, dev = rec_win0.numel() - 1, win_strong.device
     if L3s.size != n_rec:
         raise ValueError(f"rec_frame0_host describes {L3s.size} recordings, the tables {n_rec}")
-    if span_tables is None:
+    off_dev = None
+    if span_off is not None:
+        if span_tables is None:
+            raise ValueError("span_off needs span_tables = (rec_span0 host, rec_span0 on the device): the pieces' own span table")
+        off_host, off_dev = span_off if isinstance(span_off, tuple) else (span_off.cpu().numpy(), span_off)
+        off_host = np.asarray(off_host, dtype=np.int64).reshape(-1)
+        host, rec_span0 = np.asarray(span_tables[0], dtype=np.int64).reshape(-1), span_tables[1]
+        if isinstance(span3, (float, np.floating)) and not np.isfinite(span3) or int(span3) != span3 or span3 < 1:
+            raise ValueError(f"span3 must be a whole number of label frames >= 1, got {span3!r}")
+        span3, n = int(span3), np.diff(host)
+        if host.size != n_rec + 1 or off_host.size != n_rec or host[0] != 0 or (n < 1).any() or (off_host < 0).any() or \
+                (off_host + (n - 1) * span3 >= L3s).any():
+            raise ValueError("span_off / span_tables do not describe pieces: need rec_span0[0] == 0, off >= 0, at least one span "
+                             "per piece and off + (n - 1) * span3 < L3")
+        if off_dev.dtype != torch.int32 or off_dev.numel() != n_rec or off_dev.device != dev:
+            raise ValueError("span_off must be [n_rec] int32 on the window tensors' device")
+        total_spans, off_dev = int(host[-1]), off_dev.contiguous()
+    elif span_tables is None:
         host, rec_span0, total_spans, span3 = span_table(L3s, span3, dev)
     else:
         host, _, total_spans, span3 = span_table(L3s, span3)
         given, rec_span0 = span_tables
         if not np.array_equal(np.asarray(given, dtype=np.int64).reshape(-1), host):
             raise ValueError("span_tables is not span_table's for these recordings and this span3")
+    if span_tables is not None:
         if rec_span0.dtype != torch.int64 or rec_span0.numel() != n_rec + 1 or rec_span0.device != dev:
             raise ValueError("span_tables' device table must be [n_rec + 1] int64 on the window tensors' device")
     l = _lib.lib()
-    ws_bytes = l.sed_stitch_span_tags_ws_bytes(total, total_spans, n_rec, win_strong.shape[2], span3)
+    ws_name = "sed_stitch_span_tags_ws_bytes" if off_dev is None else "sed_stitch_piece_span_tags_ws_bytes"
+    ws_bytes = getattr(l, ws_name)(total, total_spans, n_rec, win_strong.shape[2], span3)
     if ws_bytes == 0:
-        raise ValueError(f"sed_stitch_span_tags_ws_bytes: {l.sed_last_error().decode()}")
+        raise ValueError(f"{ws_name}: {l.sed_last_error().decode()}")
     return ({"rec_span0": rec_span0, "rec_span0_host": host, "total_spans": total_spans, "span3": span3},
-            (rec_span0.contiguous(), total_spans, span3, ws_bytes))
+            (rec_span0.contiguous(), total_spans, span3, ws_bytes, off_dev))
 
 
 def stitch_span_tags(win_strong, win_att, rec_win0, rec_frame0, total_frames, hop3, span3, weighting="taper", want_sums=False,
-                     rec_frame0_host=None):
+                     rec_frame0_host=None, span_tables=None, span_off=None):
     """Span-level weak tags (``sed_stitch_span_tags``): ``stitch_weak``'s blend and fp64 pooling per span of ``span3`` label
     frames of every recording instead of per recording (the definition is in include/dcase_sed.h); arguments as for
     ``stitch_weak``.  The span table needs the recordings' lengths on the host: ``rec_frame0_host`` (a ``LongRecordingSet``
     has it) - without it ``rec_frame0`` is copied to the host once.  ``span3`` is clamped to the longest recording.  Returns a
     dict, the tensors on the device: ``tags`` [total_spans, nclass] float32, ``sums`` [total_spans, nclass, 2] float64 (num,
     den) or None, ``rec_span0`` [n_rec + 1] int64, ``rec_span0_host``, ``total_spans``, ``span3`` (clamped), ``err`` [1] int32
-    (``STITCH_ERR_BITS`` 16 / 32: the rows of such a recording are NaN).  Two launches."""
+    (``STITCH_ERR_BITS`` 16 / 32: the rows of such a recording are NaN).  Two launches.
+
+    ``span_off`` None: today's entry.  ``span_off`` [n_rec] int32 on the device: the tables describe PIECES of recordings
+    (``longrec.span_pieces``, ``sed_stitch_piece_span_tags``) - a piece owns its table rows' windows and frames like a
+    recording, ``span_tables = (rec_span0 host, rec_span0 on the device)`` (required) says how many spans it holds and
+    ``span_off[r]`` at which local frame its first span starts; ``span3`` is not clamped.  A span's tags and sums are then
+    bit-equal to the whole recording's, given the same window posteriors."""
     total, hop3, weighting = _weak_inputs("stitch_span_tags", win_strong, win_att, rec_win0, total_frames, hop3, weighting)
-    spans, rows = _span_rows(win_strong, rec_win0, rec_frame0, total, span3, rec_frame0_host)
+    spans, rows = _span_rows(win_strong, rec_win0, rec_frame0, total, span3, rec_frame0_host, span_tables, span_off)
     err = torch.zeros(1, dtype=torch.int32, device=win_strong.device)
     tags, sums = _tags_forward(win_strong.contiguous().float(), win_att.contiguous().float(), rec_win0, rec_frame0, total, hop3,
                                weighting, rows, err, want_sums)
@@ -759,7 +804,7 @@ def stitch_span_tags(win_strong, win_att, rec_win0, rec_frame0, total_frames, ho
 
 
 def pooled_span_tags(win_strong, win_att, rec_win0, rec_frame0, total_frames, hop3, span3, weighting="taper", n_win=None,
-                     rec_frame0_host=None, span_tables=None):
+                     rec_frame0_host=None, span_tables=None, span_off=None):
     """``stitch_span_tags``'s span-level tags as a differentiable function of both window tensors: ``pooled_tags``' node with
     ``sed_stitch_span_tags`` (its fp64 sums are kept) as the forward and ``sed_stitch_span_tags_backward`` as the backward.
     Arguments and host checks as for ``pooled_tags`` (the window tensors must hold exactly ``rec_win0[-1]`` windows; ``n_win``:
@@ -770,9 +815,14 @@ def pooled_span_tags(win_strong, win_att, rec_win0, rec_frame0, total_frames, ho
     nothing is copied.  Returns a dict like ``stitch_span_tags``'s: ``tags`` [total_spans, nclass] float32 (differentiable),
     ``rec_span0``, ``rec_span0_host``, ``total_spans``, ``span3`` (clamped), ``err`` [1] int32 on the device, OR-ed into by
     forward and backward (``STITCH_ERR_BITS`` 16 / 32: tags and gradients are invalid when it is nonzero).  With
-    ``rec_frame0_host`` nothing synchronises."""
+    ``rec_frame0_host`` nothing synchronises.
+
+    ``span_off`` (None: today's entries and bytes): as for ``stitch_span_tags`` - the tables describe pieces, the same node
+    runs ``sed_stitch_piece_span_tags`` and ``sed_stitch_piece_span_tags_backward``, and the gradient is that of exactly the
+    loss terms of the pieces' spans (window elements whose frame belongs to no span of the piece get +0.0).  A device tensor
+    is copied to the host once for the check; ``(host, device)`` copies nothing."""
     tags, err, spans = _pooled("pooled_span_tags", win_strong, win_att, rec_win0, rec_frame0, total_frames, hop3, weighting, n_win,
-                               (span3, rec_frame0_host, span_tables))
+                               (span3, rec_frame0_host, span_tables, span_off))
     return {"tags": tags, **spans, "err": err}
 
 

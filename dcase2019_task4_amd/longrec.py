@@ -12,6 +12,8 @@ Training on such recordings is ``WindowedFeatureSet``: the recordings and their 
 position is a window ``(item, start label frame)`` gathered - features and sliced labels - by
 ``sed_gather_window_logmel_transform``, with a fixed number of windows per recording and epoch and fresh crop starts per epoch.
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -106,6 +108,97 @@ def recording_tag_runs(n_windows, max_windows):
     return runs
 
 
+def cover_lo(u, T3, hop3):
+    """The first window that covers timeline frame ``u`` (``st_cover_lo`` of csrc/stitch.hip, restated)."""
+    u, T3, hop3 = int(u), int(T3), int(hop3)
+    return (u - T3) // hop3 + 1 if u >= T3 else 0
+
+
+def cover_hi(u, n_w, hop3):
+    """The last window of a recording's ``n_w`` that covers timeline frame ``u`` (``st_cover_hi``, restated)."""
+    return min(int(u) // int(hop3), int(n_w) - 1)
+
+
+SpanPiece = collections.namedtuple("SpanPiece", "rec s0 s1 j0 j1 off L3")
+SpanPiece.__doc__ = """A piece of recording ``rec``: its spans ``s0 .. s1 - 1`` and its windows ``j0 .. j1`` (both ends included),
+exactly those that cover the spans' frames.  As a "recording" of ``sed_stitch_piece_span_tags`` it has ``L3`` local frames
+(local frame 0 is the recording's frame ``j0 * hop3``) and its first span starts at local frame ``off``."""
+
+
+def span_windows(s0, s1, n_w, L3, T3, hop3, span3):
+    """``(j0, j1)``: the windows of a recording (``n_w`` windows, ``L3`` frames) that cover the frames of its spans
+    ``s0 .. s1 - 1``; the piece that holds the last span takes the recording's last window."""
+    n_spans = -(-int(L3) // int(span3))
+    j0 = cover_lo(s0 * span3, T3, hop3)
+    j1 = n_w - 1 if s1 >= n_spans else cover_hi(min(s1 * span3, L3) - 1, n_w, hop3)
+    return j0, j1
+
+
+def span_pieces(n_windows, L3s, T3, hop3, span3, max_windows):
+    """The batches of one span-tag epoch over recordings of ANY length, pure numpy: a list of batches, a batch a list of
+    ``SpanPiece``.  ``n_windows`` / ``L3s`` [n_rec]: windows and timeline frames per recording; ``span3`` label frames per
+    span (as ``inference.span_table`` clamped it).
+
+    A recording with at most ``max_windows`` windows is never split: runs of such recordings are packed exactly as
+    ``recording_tag_runs`` packs them, a batch of them is one piece per recording with ``off = 0`` and all its spans.  A
+    recording with more windows gets batches of its own, one piece each, formed greedily over its spans in order: spans join a
+    piece while the windows that cover them (``span_windows``) stay within ``max_windows``.  The boundary windows of
+    neighbouring pieces cover spans of both, so they are forwarded in both batches.  A span that alone needs more than
+    ``max_windows`` windows raises ``ValueError``."""
+    n_windows, L3s = np.asarray(n_windows, dtype=np.int64), np.asarray(L3s, dtype=np.int64)
+    T3, hop3, span3, max_windows = int(T3), int(hop3), int(span3), int(max_windows)
+    if n_windows.ndim != 1 or n_windows.size < 1 or L3s.shape != n_windows.shape or (n_windows < 1).any() or (L3s < 1).any() \
+            or max_windows < 1:
+        raise ValueError("need at least one recording, at least one window and one frame per recording and max_windows >= 1")
+    if not 1 <= hop3 <= T3 or span3 < 1:
+        raise ValueError(f"need 1 <= hop3 <= T3 and span3 >= 1, got hop3 {hop3}, T3 {T3}, span3 {span3}")
+    if ((n_windows - 1) * hop3 + T3 < L3s).any():
+        raise ValueError("a recording's windows do not cover its frames")
+    batches, short = [], []
+
+    def flush():
+        if short:
+            for r0, r1 in recording_tag_runs(n_windows[short[0]:short[-1] + 1], max_windows):
+                batches.append([SpanPiece(r, 0, -(-int(L3s[r]) // span3), 0, int(n_windows[r]) - 1, 0, int(L3s[r]))
+                                for r in range(short[0] + r0, short[0] + r1)])
+            short.clear()
+
+    for r, (n_w, L3) in enumerate(zip(n_windows.tolist(), L3s.tolist())):
+        if n_w <= max_windows:
+            short.append(r)
+            continue
+        flush()
+        n_spans, s0 = -(-L3 // span3), 0
+        while s0 < n_spans:
+            j0, j1 = span_windows(s0, s0 + 1, n_w, L3, T3, hop3, span3)
+            if j1 - j0 + 1 > max_windows:
+                raise ValueError(f"span {s0} of recording {r} alone needs {j1 - j0 + 1} windows, more than max_windows = "
+                                 f"{max_windows}")
+            s1 = s0 + 1
+            while s1 < n_spans and span_windows(s0, s1 + 1, n_w, L3, T3, hop3, span3)[1] - j0 + 1 <= max_windows:
+                s1 += 1
+            j1 = span_windows(s0, s1, n_w, L3, T3, hop3, span3)[1]
+            batches.append([SpanPiece(r, s0, s1, j0, j1, s0 * span3 - j0 * hop3, min(L3, j1 * hop3 + T3) - j0 * hop3)])
+            s0 = s1
+    flush()
+    return batches
+
+
+def span_piece_tables(batch, rec_win0_host, rec_span0_host):
+    """The tables of one ``span_pieces`` batch: ``(rec_win0 int32 [n + 1], rec_frame0 int64 [n + 1], rec_span0 int64 [n + 1],
+    rec_span_off int32 [n], first window of the set, windows, first span row of the set, span rows)`` - the first three rebased
+    to the batch, as ``sed_stitch_piece_span_tags`` takes them; the batch's windows and span rows are contiguous in the set."""
+    n_w = [p.j1 - p.j0 + 1 for p in batch]
+    w0 = int(rec_win0_host[batch[0].rec]) + batch[0].j0
+    g0 = int(rec_span0_host[batch[0].rec]) + batch[0].s0
+    for a, b in zip(batch[:-1], batch[1:]):              # (pieces of one batch are whole consecutive recordings)
+        assert b.rec == a.rec + 1 and a.j1 + 1 == int(rec_win0_host[b.rec] - rec_win0_host[a.rec]) and b.j0 == b.s0 == 0
+    return (np.concatenate([[0], np.cumsum(n_w)]).astype(np.int32),
+            np.concatenate([[0], np.cumsum([p.L3 for p in batch])]).astype(np.int64),
+            np.concatenate([[0], np.cumsum([p.s1 - p.s0 for p in batch])]).astype(np.int64),
+            np.asarray([p.off for p in batch], dtype=np.int32), w0, int(sum(n_w)), g0, int(sum(p.s1 - p.s0 for p in batch)))
+
+
 class LongRecordingSet(ResidentFeatureSet):
     """Recordings of any lengths, resident in one HBM pool; the set's "clips" are their overlapping windows.
 
@@ -173,6 +266,7 @@ class LongRecordingSet(ResidentFeatureSet):
         self.rec_frame0 = torch.from_numpy(self.rec_frame0_host).to(self.device)
         self._all = None
         self._tag_batches = None
+        self._span_tag_batches = None
         if filenames is None:
             filenames = [f"recording_{i}" for i in range(self.n_rec)]
         if len(filenames) != self.n_rec:
@@ -191,6 +285,30 @@ class LongRecordingSet(ResidentFeatureSet):
             at = np.concatenate([[0], np.cumsum([r1 - r0 + 1 for r0, r1 in runs])])
             self._tag_batches = (int(max_windows), runs, at, torch.from_numpy(w).to(self.device), torch.from_numpy(f).to(self.device))
         return self._tag_batches[1:]
+
+    def span_tag_batches(self, max_windows, span3):
+        """The batches ``train.train_span_tags(split_long=True)`` runs over this set, built once per ``(max_windows, span3)``
+        and kept: a dict with ``batches`` (``span_pieces``' - a recording with more than ``max_windows`` windows is cut into
+        pieces, whose boundary windows are forwarded in both neighbours), ``at`` and the device tensors ``rec_win0``,
+        ``rec_frame0``, ``rec_span0``, ``rec_span_off`` - the batch-local tables of ``span_piece_tables`` concatenated, batch
+        ``k``'s are the slices ``[at[k]:at[k + 1]]`` (``rec_span_off`` carries one unused entry per batch to share ``at``) - and
+        on the host ``tables`` (the same per batch), ``win`` [(first window, windows)] for ``eval_batch``, ``rows`` [(first span
+        row, span rows)] of the set's span table and ``forwarded`` (windows forwarded per epoch / windows of the set).
+        ``span3`` is taken as given (``inference.span_table`` clamps it to the longest recording)."""
+        key = (int(max_windows), int(span3))
+        if self._span_tag_batches is None or self._span_tag_batches[0] != key:
+            L3s = np.diff(self.rec_frame0_host)
+            batches = span_pieces(np.diff(self.rec_win0_host), L3s, self.T3, self.hop3, key[1], key[0])
+            span0 = np.concatenate([[0], np.cumsum((L3s + key[1] - 1) // key[1])]).astype(np.int64)
+            tables = [span_piece_tables(b, self.rec_win0_host, span0) for b in batches]
+            dev = lambda i, pad: torch.from_numpy(np.concatenate([np.r_[t[i], pad] for t in tables])).to(self.device)
+            self._span_tag_batches = (key, {
+                "batches": batches, "at": np.concatenate([[0], np.cumsum([len(b) + 1 for b in batches])]),
+                "rec_win0": dev(0, np.zeros(0, np.int32)), "rec_frame0": dev(1, np.zeros(0, np.int64)),
+                "rec_span0": dev(2, np.zeros(0, np.int64)), "rec_span_off": dev(3, np.zeros(1, np.int32)),
+                "tables": [t[:4] for t in tables], "win": [t[4:6] for t in tables], "rows": [t[6:8] for t in tables],
+                "forwarded": sum(t[5] for t in tables) / float(self.n_clips)})
+        return self._span_tag_batches[1]
 
     def capacity(self, nclass):
         """Events ``sed_stitch_decode`` can never exceed: sum over recordings of nclass * ceil(L3 / 2)."""

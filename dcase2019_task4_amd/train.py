@@ -882,21 +882,31 @@ def _tag_batch_order(n_batches, seed, epoch):
     return np.random.default_rng([int(seed), int(epoch)]).permutation(n_batches)
 
 
-def _tags_loss(long_set, model, run, tables, targets, known=None, spans=None, weighting="taper"):
+def _tags_loss(long_set, model, run, tables, targets, known=None, spans=None, weighting="taper", pieces=None):
     """The loss of one batch of either level - the recordings ``run = (r0, r1)`` of ``long_set`` - with its graph: the run's
     windows through the set's eval gather, ``model(x, return_attention=True)``, the pooled tags (``inference._pooled``), the
     BCE.  ``tables = (k, at, rec_win0, rec_frame0)``: ``tag_batches``' tables.  ``spans`` None: one row per recording, the
     plain mean ``binary_cross_entropy`` against ``targets[r0:r1]``.  ``spans = (span3, rec_span0 of every run rebased and
     concatenated like the tables, the set's span offsets on the host, the runs' known-pair counts)``: the rows are the run's
-    spans, the BCE weighted by ``known`` and scaled by pairs / known pairs (a host number).  Returns ``(loss, err)``; nothing
-    synchronises."""
+    spans, the BCE weighted by ``known`` and scaled by pairs / known pairs (a host number).  ``pieces``: the dict of
+    ``LongRecordingSet.span_tag_batches`` - the batch is then its batch ``k`` (``run`` is not used), pieces of recordings with
+    their own tables and ``rec_span_off``, pooled by the piece entries.  Returns ``(loss, err)``; nothing synchronises."""
     from .inference import _pooled
-    r0, r1 = run
     k, at, win0_all, frame0_all = tables
-    w0, w1 = int(long_set.rec_win0_host[r0]), int(long_set.rec_win0_host[r1])
-    frames_host = long_set.rec_frame0_host[r0:r1 + 1] - long_set.rec_frame0_host[r0]
-    g0, g1, span = r0, r1, None
-    if spans is not None:
+    if pieces is None:
+        r0, r1 = run
+        w0, w1 = int(long_set.rec_win0_host[r0]), int(long_set.rec_win0_host[r1])
+        frames_host = long_set.rec_frame0_host[r0:r1 + 1] - long_set.rec_frame0_host[r0]
+        g0, g1, span = r0, r1, None
+    else:
+        _, frames_host, span0_local, off_host = pieces["tables"][k]
+        w0, g0 = pieces["win"][k][0], pieces["rows"][k][0]
+        w1, g1 = w0 + pieces["win"][k][1], g0 + pieces["rows"][k][1]
+    if spans is not None and pieces is not None:
+        span3, span0_all, _, counts = spans
+        span = (span3, frames_host, (span0_local, span0_all[at[k]:at[k + 1]]),
+                (off_host, pieces["rec_span_off"][at[k]:at[k + 1] - 1]))
+    elif spans is not None:
         span3, span0_all, span0_host, counts = spans
         g0, g1 = int(span0_host[r0]), int(span0_host[r1])
         span = (span3, frames_host, (span0_host[r0:r1 + 1] - g0, span0_all[at[k]:at[k + 1]]))
@@ -911,18 +921,25 @@ def _tags_loss(long_set, model, run, tables, targets, known=None, spans=None, we
     return loss * (target.numel() / int(counts[k])), err
 
 
-def _tags_epoch(who, label, long_set, targets, known, counts, spans, model, optimizer, epoch, ema_model, max_windows, seed, log):
+def _tags_epoch(who, label, long_set, targets, known, counts, spans, model, optimizer, epoch, ema_model, max_windows, seed, log,
+                pieces=None):
     """The one epoch on pooled tags, behind ``train_recording_tags`` and ``train_span_tags`` (``who``, for the messages;
     ``label``: the loss's name in the log line).  ``targets`` [rows, nclass]: host floats, one row per recording or per span;
     ``known`` / ``counts`` / ``spans = (span3, the set's span offsets on the host)``: ``span_tag_plan``'s mask, known-pair
     counts and span table, or None at the recording level - every run is then visited.  A run with a count of 0 is skipped:
-    no forward, no optimizer or EMA step, though it keeps its place ``i`` in the order.  Returns the mean loss over the runs
-    that ran."""
-    runs, at, win0_all, frame0_all = long_set.tag_batches(max_windows)
+    no forward, no optimizer or EMA step, though it keeps its place ``i`` in the order.  ``pieces``: the dict of
+    ``LongRecordingSet.span_tag_batches`` (``train_span_tags(split_long=True)``) - its batches take the place of the runs, the
+    rest of the epoch is the same.  Returns the mean loss over the runs that ran."""
+    dev = long_set.device
+    if pieces is None:
+        runs, at, win0_all, frame0_all = long_set.tag_batches(max_windows)
+    else:
+        runs, at, win0_all, frame0_all = pieces["batches"], pieces["at"], pieces["rec_win0"], pieces["rec_frame0"]
     order = _tag_batch_order(len(runs), seed, epoch)
     start = time.time()
-    dev = long_set.device
-    if spans is not None:
+    if pieces is not None:
+        spans, known = (spans[0], pieces["rec_span0"], spans[1], counts), torch.from_numpy(known).to(dev)
+    elif spans is not None:
         span3, span0_host = spans
         span0_all = torch.from_numpy(np.concatenate([span0_host[r0:r1 + 1] - span0_host[r0] for r0, r1 in runs])).to(dev)
         spans, known = (span3, span0_all, span0_host, counts), torch.from_numpy(known).to(dev)
@@ -936,7 +953,7 @@ def _tags_epoch(who, label, long_set, targets, known, counts, spans, model, opti
         if counts is not None and counts[k] == 0:
             continue
         optimizer.zero_grad()
-        loss, err = _tags_loss(long_set, model, runs[k], (int(k), at, win0_all, frame0_all), targets, known, spans)
+        loss, err = _tags_loss(long_set, model, runs[k], (int(k), at, win0_all, frame0_all), targets, known, spans, pieces=pieces)
         loss.backward()
         optimizer.step()
         if ema_model is not None:
@@ -988,15 +1005,22 @@ def train_recording_tags(long_set, tags, model, optimizer, epoch, ema_model=None
 
 
 # ---- training on span-level tags -----------------------------------------------------------------------------------------------
-def span_tag_plan(rec_win0_host, rec_frame0_host, span_tags, max_windows, span3):
+def span_tag_plan(rec_win0_host, rec_frame0_host, span_tags, max_windows, span3, split_long=False, T3=None, hop3=None):
     """The host-side plan of one ``train_span_tags`` epoch, nothing touches a GPU: the runs of ``recording_tag_runs``, the span
     table of the whole set and, per run, the count of KNOWN (span, class) pairs - a NaN target is unknown.  Returns a dict:
     ``runs``, ``rec_span0`` (host int64 [n_rec + 1]), ``total_spans``, ``span3`` (clamped as ``inference.span_table`` clamps
     it), ``targets`` float32 [total_spans, nclass] (the NaNs replaced by 0), ``known`` float32 (1 where the target is known),
     ``counts`` int64 [n_runs] and ``ran`` (the runs with at least one known pair: the others are skipped, no forward and no
-    optimizer step).  ValueError for targets of another shape than the span table's or outside [0, 1]."""
+    optimizer step).  ValueError for targets of another shape than the span table's or outside [0, 1].
+
+    ``split_long=True`` (it needs the windows' geometry ``T3`` / ``hop3`` in label frames): a recording with more than
+    ``max_windows`` windows does not raise but is cut into PIECES (``longrec.span_pieces``) - runs of consecutive spans with
+    exactly the windows that cover them, one batch each.  ``runs`` is then the list of batches (lists of
+    ``longrec.SpanPiece``), ``counts`` / ``ran`` are per batch, and two more keys say what the cut costs: boundary windows of
+    neighbouring pieces cover spans of both and are forwarded in BOTH batches, ``forwarded_windows`` is the number of windows
+    an epoch forwards and ``forwarded`` its ratio to the set's windows (1.0 without a long recording)."""
     from .inference import span_table
-    from .longrec import recording_tag_runs
+    from .longrec import recording_tag_runs, span_piece_tables, span_pieces
     rec_win0_host, rec_frame0_host = np.asarray(rec_win0_host, dtype=np.int64), np.asarray(rec_frame0_host, dtype=np.int64)
     rec_span0, _, total_spans, span3 = span_table(np.diff(rec_frame0_host), span3)
     tags_np = span_tags.detach().cpu().numpy() if torch.is_tensor(span_tags) else np.asarray(span_tags)
@@ -1006,11 +1030,21 @@ def span_tag_plan(rec_win0_host, rec_frame0_host, span_tags, max_windows, span3)
     known = ~np.isnan(tags_np)
     if not ((tags_np[known] >= 0) & (tags_np[known] <= 1)).all():
         raise ValueError("span_tags must lie in [0, 1] (NaN: unknown)")
-    runs = recording_tag_runs(np.diff(rec_win0_host), max_windows)
-    counts = np.asarray([int(known[rec_span0[r0]:rec_span0[r1]].sum()) for r0, r1 in runs], dtype=np.int64)
+    extra = {}
+    if split_long:
+        if T3 is None or hop3 is None:
+            raise ValueError("split_long needs T3 and hop3, the windows' length and hop in label frames")
+        runs = span_pieces(np.diff(rec_win0_host), np.diff(rec_frame0_host), T3, hop3, span3, max_windows)
+        tables = [span_piece_tables(b, rec_win0_host, rec_span0) for b in runs]
+        counts = np.asarray([int(known[t[6]:t[6] + t[7]].sum()) for t in tables], dtype=np.int64)
+        forwarded = int(sum(t[5] for t in tables))
+        extra = {"forwarded_windows": forwarded, "forwarded": forwarded / float(rec_win0_host[-1] - rec_win0_host[0])}
+    else:
+        runs = recording_tag_runs(np.diff(rec_win0_host), max_windows)
+        counts = np.asarray([int(known[rec_span0[r0]:rec_span0[r1]].sum()) for r0, r1 in runs], dtype=np.int64)
     return {"runs": runs, "rec_span0": rec_span0, "total_spans": total_spans, "span3": span3,
             "targets": np.where(known, tags_np, 0).astype(np.float32), "known": known.astype(np.float32), "counts": counts,
-            "ran": [k for k in range(len(runs)) if counts[k] > 0]}
+            "ran": [k for k in range(len(runs)) if counts[k] > 0], **extra}
 
 
 def span_tags_loss(long_set, span_tags_dev, known_dev, model, run, tables, span3, weighting="taper"):
@@ -1026,7 +1060,7 @@ def span_tags_loss(long_set, span_tags_dev, known_dev, model, run, tables, span3
 
 
 def train_span_tags(long_set, span_tags, model, optimizer, epoch, tag_span=None, span3=None, ema_model=None, max_windows=64,
-                    seed=0, log=None):
+                    seed=0, log=None, split_long=False):
     """One epoch of training on SPAN-LEVEL tags: ``train_recording_tags`` with one target vector per span of every recording
     instead of one per recording - a long recording assembled from weakly labelled clips, or coarse annotations of an hour
     of audio.  ``span_tags`` [total_spans, nclass] floats in [0, 1], the rows in ``inference.span_table(long_set, span3)``'s
@@ -1042,7 +1076,18 @@ def train_span_tags(long_set, span_tags, model, optimizer, epoch, tag_span=None,
     the BCE is summed over its known pairs and divided by their count.  Nothing synchronises inside the epoch: the masks,
     counts and span tables are prepared once at its start, the kernels' error word is read once at its end (nonzero raises
     ``SedError``), with the mean loss over the batches that ran, which is returned.  A recording with more than
-    ``max_windows`` windows raises ``ValueError``."""
+    ``max_windows`` windows raises ``ValueError`` - unless ``split_long=True``.
+
+    ``split_long=True``: a span's tag depends only on the windows that cover the span, so such a recording is trained in
+    PIECES (``longrec.span_pieces``, ``LongRecordingSet.span_tag_batches``): runs of consecutive spans with exactly the windows
+    that cover them, as many spans as fit in ``max_windows`` windows, one batch per piece; shorter recordings are batched as
+    before.  A piece's tags are bit-equal to the whole recording's on the same window posteriors and its gradient is that of
+    exactly its own spans' loss terms (``sed_stitch_piece_span_tags`` and its backward) - nothing is cut on the host and no
+    blend changes.  The price: boundary windows of neighbouring pieces cover spans of both, so they are forwarded in BOTH
+    batches (``span_tag_plan(..., split_long=True)["forwarded"]`` is the ratio of forwarded windows to windows); and a model
+    in train mode sees each piece as a batch of its own (dropout masks and batch statistics are per batch, as for any two
+    batches).  The epoch is the same loop over the plan's batches.  A span that alone needs more than ``max_windows`` windows
+    raises ``ValueError``.  Recording-level tags (``train_recording_tags``) still need a recording in one forward."""
     from .inference import _Cfg, tag_span_frames
     from .longrec import LongRecordingSet
     if not isinstance(long_set, LongRecordingSet):
@@ -1051,9 +1096,15 @@ def train_span_tags(long_set, span_tags, model, optimizer, epoch, tag_span=None,
         raise ValueError("give exactly one of tag_span (seconds) and span3 (label frames)")
     if span3 is None:
         span3 = tag_span_frames(tag_span, long_set.pooling_time_ratio * _Cfg.hop_length / _Cfg.sample_rate)
-    plan = span_tag_plan(long_set.rec_win0_host, long_set.rec_frame0_host, span_tags, max_windows, span3)
+    plan = span_tag_plan(long_set.rec_win0_host, long_set.rec_frame0_host, span_tags, max_windows, span3, bool(split_long),
+                         long_set.T3, long_set.hop3)
     if not plan["ran"]:
         raise ValueError("span_tags has no known target: every entry is NaN")
-    assert long_set.tag_batches(max_windows)[0] == plan["runs"]
+    pieces = None
+    if split_long:
+        pieces = long_set.span_tag_batches(max_windows, plan["span3"])
+        assert pieces["batches"] == plan["runs"]
+    else:
+        assert long_set.tag_batches(max_windows)[0] == plan["runs"]
     return _tags_epoch("train_span_tags", "span_tag_loss", long_set, plan["targets"], plan["known"], plan["counts"],
-                       (plan["span3"], plan["rec_span0"]), model, optimizer, epoch, ema_model, max_windows, seed, log)
+                       (plan["span3"], plan["rec_span0"]), model, optimizer, epoch, ema_model, max_windows, seed, log, pieces)

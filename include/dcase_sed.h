@@ -894,6 +894,30 @@ int sed_stitch_weak_backward(const float* win_strong, const float* win_att, cons
  * Limits, checked before any launch (SED_ERR_BAD_ARG, outputs untouched): NC <= 16, 1 <= hop3 <= T3 <= 4096, span3 >= 1,
  * n_rec <= total_spans, total_spans * NC < 2^31, sums 8-byte aligned, no null pointer.
  *
+ *
+ * Span tags of PIECES: sed_stitch_piece_span_tags and sed_stitch_piece_span_tags_backward.  A span's tag depends only on the
+ * windows that cover the span, so the spans of a recording with more windows than one forward holds can be pooled - and
+ * trained on - in pieces: a piece is a run of consecutive spans plus exactly the windows that cover them.  The two entries are
+ * the span entries with one more device table, rec_span_off [n_rec] int32, and a "recording" of the call is a piece.  It owns
+ *   the windows rec_win0[r] .. rec_win0[r + 1], the local frames 0 .. L3_r from rec_frame0 (frame u of window j is local frame
+ *   j * hop3 + u, as in a recording), and n_r = rec_span0[r + 1] - rec_span0[r] spans;
+ *   span k of piece r covers the local frames [off_r + k * span3, min(off_r + (k + 1) * span3, L3_r)), off_r = rec_span_off[r].
+ * A piece starts at a window boundary, not at a span boundary in general: the local frames below off_r and from
+ * off_r + n_r * span3 on belong to no span.  Everything else is the definition above in the same code: the blend, the fp64 num /
+ * den, tag = (float)(num / den), a tile walk that starts at the span's own first frame - so the order of a span's sums depends on
+ * its length and NC alone, and a span pooled from a piece that holds all the windows covering it has the BITS the whole
+ * recording's call gives it - and the backward's individually rounded fp64 operations in their order.  In the backward, frame
+ * u of piece r reads row rec_span0[r] + (u - off_r) / span3; the window elements of a frame that belongs to no span are +0.0f
+ * like the tails.  A piece's gradient is that of exactly the loss terms of its spans: over pieces that partition a recording's
+ * spans, every window element is nonzero in at most one piece, and the element-wise sum is the whole call's gradient.
+ *   err  16 also for a piece with off_r < 0, n_r < 1, off_r + (n_r - 1) * span3 >= L3_r (its last span would be empty) or a
+ *        rec_span0 outside 0 .. total_spans, checked per piece before any value is used as an index; the rule
+ *        n_r == ceil(L3_r / span3) of the span entries does NOT apply.  Such a piece's rows are NaN in the forward, its windows
+ *        +0.0f in the backward; the other pieces are unaffected.  The address guarantee holds for every tensor whatever the
+ *        tables contain.
+ * With off = 0 and n_r = ceil(L3_r / span3) everywhere both entries return the span entries' bytes.  Launches, paths, workspace
+ * (sed_stitch_piece_span_tags_ws_bytes: the span entry's value) and host-side limits are the span entries'.
+ *
  * Not provided: overlapping or per-recording span lengths, masking in the frame domain. */
 size_t sed_stitch_span_tags_ws_bytes(long long total_frames, long long total_spans, int n_rec, int nclass, int span3);
 int sed_stitch_span_tags(const float* win_strong, const float* win_att, const int32_t* rec_win0, const int64_t* rec_frame0,
@@ -904,6 +928,17 @@ int sed_stitch_span_tags_backward(const float* win_strong, const float* win_att,
                                   const int64_t* rec_frame0, const int64_t* rec_span0, long long total_spans, int n_rec, int T3,
                                   int NC, int hop3, int weighting, int span3, const double* sums, const float* g_tags,
                                   float* d_win_strong, float* d_win_att, int32_t* err, void* stream);
+size_t sed_stitch_piece_span_tags_ws_bytes(long long total_frames, long long total_spans, int n_rec, int nclass, int span3);
+int sed_stitch_piece_span_tags(const float* win_strong, const float* win_att, const int32_t* rec_win0,
+                               const int64_t* rec_frame0, const int64_t* rec_span0, long long total_frames,
+                               long long total_spans, int n_rec, int T3, int NC, int hop3, int weighting, int span3,
+                               const int32_t* rec_span_off, float* tags, double* sums, void* ws, size_t ws_bytes, int32_t* err,
+                               void* stream);
+int sed_stitch_piece_span_tags_backward(const float* win_strong, const float* win_att, const int32_t* rec_win0,
+                                        const int64_t* rec_frame0, const int64_t* rec_span0, long long total_spans, int n_rec,
+                                        int T3, int NC, int hop3, int weighting, int span3, const int32_t* rec_span_off,
+                                        const double* sums, const float* g_tags, float* d_win_strong, float* d_win_att,
+                                        int32_t* err, void* stream);
 int sed_events_tag_scores(const float* tags, long long total_spans, const int64_t* rec_span0, int span3, int n_rec, int NC,
                           const int64_t* ev_ptr, const int32_t* ev_pairs, long long pairs_capacity, long long n_cols,
                           float* tag_score, int32_t* err, void* stream);

@@ -64,6 +64,16 @@ workloads at the same 50 thresholds with PSDS:
   the same call at one span per recording beside sed_stitch_weak_backward on the same sums (and whether their bytes are equal);
   on 100x3min one train.train_span_tags epoch against train.train_recording_tags over the same batches, alternated.
 
+--span-pieces measures span-tag training of a recording longer than one forward (profiles/long_span_pieces.json), the 1 h
+workload, tag_span 10 s, max_windows 64, every target known:
+  one train.train_span_tags(split_long=True) epoch - the recording trained in pieces - against the only earlier route: the
+    recording cut on the host at span boundaries into recordings of at most 64 windows (another set, another blend at every
+    cut) and today's train.train_span_tags over those; the two legs alternated in one run, --rounds rounds, medians,
+    spread = (max - min) / median; a difference counts only where it exceeds the larger (max - min) of the two legs.
+  sed_stitch_piece_span_tags and its backward alone beside sed_stitch_span_tags and its backward on the same tables (the whole
+    recording as one piece with off = 0), a device-event pair around the call, median of --decode-reps, and whether the bytes
+    are equal.
+
 --error-rate measures the overall error rate with substitutions (the "long" key of profiles/error_rate.json), same workloads,
 references and hop as --scoring:
   validate_long(..., error_rate=True) against the same run's validate_long(...) at one operating point and at 50, the two legs
@@ -112,7 +122,7 @@ thresholds as --scoring, min_event_length 0.25 s and min_event_gap 0.15 s at eve
   pseudo_label into a WindowedFeatureSet over the same recordings against the same run's get_long_predictions with the same
     arguments, alternated, --rounds rounds; a difference counts only outside the larger (max - min) of the two legs.
 
-Usage: python tools/long_bench.py [--scoring | --sweep | --weak | --tag-train | --span-tag-train | --error-rate | --hysteresis | --process | --scores | --span-tags | --rasterize] [--rounds 5] [--decode-reps 30] [--out profiles/long_inference.json]"""
+Usage: python tools/long_bench.py [--scoring | --sweep | --weak | --tag-train | --span-tag-train | --span-pieces | --error-rate | --hysteresis | --process | --scores | --span-tags | --rasterize] [--rounds 5] [--decode-reps 30] [--out profiles/long_inference.json]"""
 import argparse
 import json
 import os
@@ -1357,6 +1367,91 @@ def span_tag_train_workload(name, model, rounds, reps, tag_span=10.0):
     return out
 
 
+def span_pieces_workload(name, model, rounds, reps, tag_span=10.0):
+    """--span-pieces: (a) the piece entries alone beside the span entries on the whole recording's tables (one piece, off = 0);
+    (b) one train_span_tags(split_long=True) epoch against the host-cut route - the recording cut at span boundaries into
+    recordings of at most BATCH windows, today's train_span_tags over that set - alternated."""
+    from dcase2019_task4_amd import train
+    from dcase2019_task4_amd.longrec import window_plan
+    ls, out, win_strong, win_att, d_s, d_a, err = tag_train_setup(name, model)
+    cfg = inference._Cfg
+    span3 = inference.tag_span_frames(tag_span, POOL * cfg.hop_length / cfg.sample_rate)
+    l, dev, ptr = _lib.lib(), win_strong.device, _lib.ptr
+    n_rec, total, T3, hop3 = ls.n_rec, ls.total_frames, ls.T3, ls.hop3
+    host, span0, n_spans, span3 = inference.span_table(ls, span3)
+    out.update(tag_span_s=tag_span, span3=span3, total_spans=n_spans, max_windows=BATCH)
+    # ---- (a) the entries alone ---------------------------------------------------------------------------------------------------
+    g = torch.randn(n_spans, NCLASS, device=dev, generator=torch.Generator(dev).manual_seed(1))
+    tags = torch.empty(n_spans, NCLASS, device=dev)
+    sums = torch.empty(n_spans, NCLASS, 2, dtype=torch.float64, device=dev)
+    off = torch.zeros(n_rec, dtype=torch.int32, device=dev)
+    ws = torch.empty(l.sed_stitch_span_tags_ws_bytes(total, n_spans, n_rec, NCLASS, span3), dtype=torch.uint8, device=dev)
+    assert ws.numel() == l.sed_stitch_piece_span_tags_ws_bytes(total, n_spans, n_rec, NCLASS, span3)
+    head = (ptr(win_strong), ptr(win_att), ptr(ls.rec_win0), ptr(ls.rec_frame0), ptr(span0))
+    geo = (n_rec, T3, NCLASS, hop3, 1, span3)
+    f_tail = (ptr(tags), ptr(sums), ptr(ws), ws.numel(), ptr(err), _lib.stream_ptr())
+    b_tail = (ptr(sums), ptr(g), ptr(d_s), ptr(d_a), ptr(err), _lib.stream_ptr())
+    calls = {
+        "sed_stitch_span_tags": lambda: _lib.check(l.sed_stitch_span_tags(*head, total, n_spans, *geo, *f_tail), "span forward"),
+        "sed_stitch_piece_span_tags": lambda: _lib.check(l.sed_stitch_piece_span_tags(*head, total, n_spans, *geo, ptr(off), *f_tail),
+                                                         "piece forward"),
+        "sed_stitch_span_tags_backward": lambda: _lib.check(l.sed_stitch_span_tags_backward(*head, n_spans, *geo, *b_tail),
+                                                            "span backward"),
+        "sed_stitch_piece_span_tags_backward": lambda: _lib.check(
+            l.sed_stitch_piece_span_tags_backward(*head, n_spans, *geo, ptr(off), *b_tail), "piece backward")}
+    alone, kept = {}, {}
+    for key, fn in calls.items():
+        fn()
+        kept[key] = [x.clone() for x in ((tags, sums) if "backward" not in key else (d_s, d_a))]
+    alone["bytes_equal"] = bool(all(torch.equal(x.view(torch.uint8), y.view(torch.uint8)) for a, b in
+                                    (("sed_stitch_span_tags", "sed_stitch_piece_span_tags"),
+                                     ("sed_stitch_span_tags_backward", "sed_stitch_piece_span_tags_backward"))
+                                    for x, y in zip(kept[a], kept[b])))
+    for key, fn in calls.items():
+        alone[key] = event_ms(fn, reps)
+    for a, b, key in (("sed_stitch_span_tags", "sed_stitch_piece_span_tags", "forward"),
+                      ("sed_stitch_span_tags_backward", "sed_stitch_piece_span_tags_backward", "backward")):
+        band = max(x["spread"] * x["median_ms"] for x in (alone[a], alone[b]))
+        alone[key + "_piece_minus_span_ms"] = alone[b]["median_ms"] - alone[a]["median_ms"]
+        alone[key + "_larger_max_minus_min_ms"] = band
+        alone[key + "_difference_exceeds_spread"] = bool(abs(alone[key + "_piece_minus_span_ms"]) > band)
+    assert int(err.item()) == 0
+    out["entries_alone"] = alone
+    del kept, win_strong, win_att, d_s, d_a
+    # ---- (b) the epoch in pieces against the host-cut route ------------------------------------------------------------------------
+    span_tags = (np.random.default_rng(2).random((n_spans, NCLASS)) < 0.2).astype(np.float32)
+    plan = train.span_tag_plan(ls.rec_win0_host, ls.rec_frame0_host, span_tags, BATCH, span3, split_long=True, T3=T3, hop3=hop3)
+    out["pieces"] = {"batches_per_epoch": len(plan["runs"]), "forwarded_windows": plan["forwarded_windows"],
+                     "forwarded_over_windows": plan["forwarded"]}
+    # the cut: as many whole spans per recording as give at most BATCH windows
+    per = max(k for k in range(1, n_spans + 1) if window_plan(k * span3 * POOL, T, POOL, hop3)["n_w"] <= BATCH)
+    n_rec_h, per_rec = WORKLOADS[name]
+    recs = recordings(n_rec_h, per_rec)
+    assert n_rec_h == 1
+    cuts = [recs[0][a * POOL:min(a + per * span3, total) * POOL] for a in range(0, total, per * span3)]
+    cut_set = inference.LongRecordingSet.from_arrays(cuts, T, scaler=scaler_of(recs[0]))
+    assert inference.span_table(cut_set, span3)[2] == n_spans and int(np.diff(cut_set.rec_win0_host).max()) <= BATCH
+    cut_plan = train.span_tag_plan(cut_set.rec_win0_host, cut_set.rec_frame0_host, span_tags, BATCH, span3)
+    out["host_cut"] = {"recordings": cut_set.n_rec, "spans_per_recording": per, "batches_per_epoch": len(cut_plan["runs"]),
+                       "forwarded_windows": cut_set.n_clips, "forwarded_over_windows": cut_set.n_clips / float(ls.n_clips)}
+    opt = torch.optim.Adam(model.parameters(), lr=1e-5)
+    epoch = [0]
+
+    def in_pieces():
+        train.train_span_tags(ls, span_tags, model, opt, epoch[0], span3=span3, max_windows=BATCH, split_long=True)
+        epoch[0] += 1
+
+    def host_cut():
+        train.train_span_tags(cut_set, span_tags, model, opt, epoch[0], span3=span3, max_windows=BATCH)
+        epoch[0] += 1
+    out.update(alternate_legs({"epoch_host_cut": host_cut, "epoch_in_pieces": in_pieces}, rounds))
+    band = max(max(x["samples_ms"]) - min(x["samples_ms"]) for x in (out["epoch_host_cut"], out["epoch_in_pieces"]))
+    out["pieces_minus_host_cut_ms"] = out["epoch_in_pieces"]["median_ms"] - out["epoch_host_cut"]["median_ms"]
+    out["larger_max_minus_min_ms"] = band
+    out["difference_exceeds_spread"] = bool(abs(out["pieces_minus_host_cut_ms"]) > band)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scoring", action="store_true", help="measure the scoring of the long path's event table instead")
@@ -1366,6 +1461,9 @@ def main():
                     help="measure the backward through the pooled tag and an epoch on recording tags (profiles/long_tag_train.json)")
     ap.add_argument("--span-tag-train", action="store_true",
                     help="measure the backward through the span tags and an epoch on span tags (profiles/long_span_tag_train.json)")
+    ap.add_argument("--span-pieces", action="store_true",
+                    help="measure a span-tag epoch over the 1 h recording in pieces against the host-cut route "
+                         "(profiles/long_span_pieces.json)")
     ap.add_argument("--error-rate", action="store_true",
                     help="measure what validate_long(error_rate=True) adds (the \"long\" key of profiles/error_rate.json)")
     ap.add_argument("--hysteresis", action="store_true",
@@ -1393,6 +1491,7 @@ def main():
         args.out = os.path.join(REPO, "profiles", "long_rasterize.json" if args.rasterize else "long_span_tags.json" if args.span_tags else "long_scores.json" if args.scores else "long_process.json" if args.process else
                                 "long_hysteresis.json" if args.hysteresis else
                                 "error_rate.json" if args.error_rate else
+                                "long_span_pieces.json" if args.span_pieces else
                                 "long_span_tag_train.json" if args.span_tag_train else
                                 "long_tag_train.json" if args.tag_train else "long_weak.json" if args.weak else
                                 "long_scoring.json" if args.scoring else "long_inference.json")
@@ -1523,6 +1622,31 @@ def main():
         doc["long"] = result
         with open(path, "w") as f:
             f.write(json.dumps(doc, indent=1) + "\n")
+        return
+    if args.span_pieces:
+        result["model"] = "baseline CRNN, fp32 kernel set; eval mode for the window tensors of the calls alone, train mode (dropout 0.5) in the epochs"
+        result["timing"] = ("the calls alone: a device-event pair around the call, warm, median of --decode-reps; the epochs: host clock "
+                            "around each synchronised epoch, the two legs alternated in one run, --rounds rounds, medians, "
+                            "spread = (max - min) / median")
+        result["note"] = ("tag_span 10 s, max_windows 64, every target known.  epoch_in_pieces: train_span_tags(split_long=True) over "
+                          "the recording's own set - boundary windows of neighbouring pieces are forwarded in both batches "
+                          "(forwarded_over_windows), tags and gradients are the whole recording's.  epoch_host_cut: the only earlier "
+                          "route - the recording cut on the host at span boundaries into recordings of at most 64 windows, a second "
+                          "set (a second pool), today's train_span_tags; frames near a cut lose covering windows, so its blend, tags "
+                          "and gradients differ from the recording's.  The two legs do different arithmetic: the rows are times, "
+                          "not a comparison of results.  A difference counts only where it exceeds the larger (max - min) of the "
+                          "two legs")
+        result["not_measured"] += ["other nclass than 10", "other hops than the default", "other span lengths than 10 s",
+                                   "other max_windows than 64", "unknown (NaN) targets", "the 100x3min workload (no recording there "
+                                   "has more windows than one forward holds: the plan is today's)", "per-kernel counters",
+                                   "the uniform weighting", "f16 models", "ema_model given", "the loss curves of the two routes",
+                                   "recording-level tags of such a recording: every window in one step, out of scope"]
+        for name in [n for n in args.workloads.split(",") if WORKLOADS[n][0] == 1]:
+            result["workloads"][name] = span_pieces_workload(name, model, args.rounds, args.decode_reps)
+            print(json.dumps({name: result["workloads"][name]}), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(json.dumps(result, indent=1) + "\n")
         return
     if args.span_tag_train:
         result["model"] = "baseline CRNN, fp32 kernel set; eval mode for the window tensors of (a) and (b), train mode (dropout 0.5) in (c)"
