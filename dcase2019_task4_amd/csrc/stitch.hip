@@ -20,12 +20,13 @@
 // sed_stitch_weak (at the end of the file) pools recording-level weak tags over the same tiles and slots: the same blend of the
 // posteriors and of the attention, fp64 sums in a fixed order, two launches, no timeline.  sed_stitch_weak_backward (behind it) is
 // its transpose: the gradient of a loss on the pooled tags w.r.t. both window tensors, a clear and one tile pass, no atomics.
-// sed_stitch_span_tags pools the same tags per span of span3 frames: the two kernels of sed_stitch_weak over another tile
-// descriptor (StSpanArgs), slots span * ceil(span3 / ST_TILE) + k.  sed_stitch_span_tags_backward is the weak backward's two
-// kernels with the row of g / sums looked up per frame (StSpanBwdArgs).  sed_stitch_piece_span_tags and its backward are the
-// span pair with one more table, rec_span_off: a "recording" is then a PIECE of one - some consecutive spans and exactly the
-// windows that cover them -, its first span starts at local frame rec_span_off[r], and the frames in front of its first and
-// behind its last span belong to no span (StPieceArgs, StPieceBwdArgs).
+// sed_stitch_span_tags pools the same tags per span of span3 frames, slots span * ceil(span3 / ST_TILE) + k, and
+// sed_stitch_piece_span_tags per span of a PIECE of a recording - some consecutive spans and exactly the windows that cover
+// them, the first span at local frame rec_span_off[r], the frames in front of the first and behind the last span in no span.
+// All six pooled entries are the same four kernels over one argument struct per direction (StPoolArgs, StPoolBwdArgs); which row
+// of tags / sums / g a frame belongs to is said once, by StRows: the rule that validates a recording's rows (st_rec_rows), the
+// frames of a span (st_span_frames) and the row of a frame (st_frame_row).  Rows per recording or per span is a template
+// parameter of the kernels (SPANS); spans or pieces is rows.rec_span_off at run time.
 //
 // Where a tile lives: the tiles of recording r take slots slot0(r) + k, slot0(r) = floor(rec_frame0[r] / ST_TILE) + r.  That
 // is strictly increasing in (r, k) for increasing rec_frame0, needs no table of its own and at most
@@ -36,7 +37,6 @@
 #include "common.h"
 #include "kernels.h"
 #include "post.h"
-#include <type_traits>
 
 #define ST_TILE 512          // timeline frames per workgroup
 #define ST_HALO 32           // 63 / 2 + 1: the widest median window's reach plus the neighbour the edge predicates read
@@ -490,98 +490,95 @@ extern "C" int sed_stitch_sweep(const float* win_strong, const int32_t* rec_win0
 //     rows = ST_THREADS / G, adds the items of class group q at frames s + row, s + row + rows, ... in that order;
 //   thread (c, i) adds the rows i, i + 16, ... of class c, thread c the sixteen of those: the tile's pair;
 //   lane l of a column's wave adds the tiles l, l + 64, ..., then an xor butterfly (both partners form the same sum).
-struct StWeakArgs {
-    StTables t;
-    const float *win_strong, *win_att;
-    double* part;            // ws: [n_slots][NC][2] (num, den) of a tile
-    float* weak;             // [n_rec][NC]
-    double* sums;            // [n_rec][NC][2] or null
-};
 #define SW_FOLD 16
 
-// sed_stitch_span_tags pools the same pairs per SPAN of span3 frames with the same two kernels (Args = StSpanArgs): a tile is then
-// ST_TILE frames of one span counted from the span's first frame, its slot is span * tps + k (tps = ceil(span3 / ST_TILE)), and
-// the column pass runs over the rows (span, class) of `weak` / `sums`.  The order of a span's sums is therefore the order
-// above with L3 = the span's length.
-struct StSpanArgs {
-    StWeakArgs w;            // t.n_slots is not used (no recording-slot layout); part [total_spans * tps][NC][2], weak / sums per span
-    const int64_t* rec_span0;
+// Which row of tags / sums / g a timeline frame of recording r belongs to: the one description of all three levels.
+//   rec_span0 null: one row per recording, row r (sed_stitch_weak); the other fields are not used.
+//   rec_span0 set, rec_span_off null: recording r owns the n_r = rec_span0[r + 1] - rec_span0[r] rows from rec_span0[r] on, row k
+//     the SPAN of local frames [k * span3, min((k + 1) * span3, L3_r)), and the spans tile the recording: n_r = ceil(L3_r / span3)
+//     (sed_stitch_span_tags).
+//   rec_span_off set: the tables describe PIECES.  Piece r owns the windows and local frames 0 .. L3_r of its table rows like a
+//     recording, its span k covers [off_r + k * span3, min(off_r + (k + 1) * span3, L3_r)), off_r = rec_span_off[r] >= 0, and n_r >= 1
+//     need not be the ceiling, only off_r + (n_r - 1) * span3 < L3_r (the last span holds a frame): the frames below off_r and
+//     from off_r + n_r * span3 on belong to no span (sed_stitch_piece_span_tags).
+// In the forward a span's tile is ST_TILE frames counted from the span's first frame, its slot is span * tps + k
+// (tps = ceil(span3 / ST_TILE)), and the order of a span's sums is the order above with L3 = the span's length.
+struct StRows {
+    const int64_t* rec_span0;            // [n_rec + 1] or null
+    const int32_t* rec_span_off;         // [n_rec] or null
     long long total_spans;
     int span3, tps;
 };
-// sed_stitch_piece_span_tags: the span call over PIECES.  Piece r owns the windows and local frames 0 .. L3_r of its table rows
-// like a recording, and n_r = rec_span0[r + 1] - rec_span0[r] >= 1 spans of which span k covers the local frames
-// [off_r + k * span3, min(off_r + (k + 1) * span3, L3_r)), off_r = rec_span_off[r] >= 0: n_r need not be ceil(L3_r / span3), the
-// frames below off_r and from off_r + n_r * span3 on belong to no span.  Everything else is the span call's, in the same code.
-struct StPieceArgs {
-    StSpanArgs s;
-    const int32_t* rec_span_off;         // [n_rec]
+struct StPoolArgs {          // sed_stitch_weak, sed_stitch_span_tags, sed_stitch_piece_span_tags
+    StTables t;              // span level: n_slots is not used (no recording-slot layout)
+    const float *win_strong, *win_att;
+    double* part;            // ws: [n_slots][NC][2] (num, den) of a tile; span level [total_spans * tps][NC][2]
+    float* weak;             // [rows][NC], rows = n_rec or total_spans
+    double* sums;            // [rows][NC][2] or null
+    StRows rows;
 };
-__host__ __device__ __forceinline__ const StWeakArgs& sw_args(const StWeakArgs& a) { return a; }
-__host__ __device__ __forceinline__ const StWeakArgs& sw_args(const StSpanArgs& a) { return a.w; }
-__host__ __device__ __forceinline__ const StWeakArgs& sw_args(const StPieceArgs& a) { return a.s.w; }
-__host__ __device__ __forceinline__ const StSpanArgs& sp_args(const StSpanArgs& a) { return a; }
-__host__ __device__ __forceinline__ const StSpanArgs& sp_args(const StPieceArgs& a) { return a.s; }
-template <class Args> constexpr bool sw_spans = std::is_same<Args, StSpanArgs>::value || std::is_same<Args, StPieceArgs>::value;
+
+// The rows of recording r (R = st_rec of it), validated before any is used as an index: 0 and Q - its n rows from row0 on, which
+// its local frames [off, end) belong to, span by span -, or the err bits that keep the recording out: R.bad, or 16 for span tables
+// that break the level's rule.  `spans` is rows.rec_span0 != null (a compile-time constant in the tile kernels).
+struct StRecRows { int row0, n, off, end; };    // (rows are < 2^31: total_spans is)
+__device__ __forceinline__ int st_rec_rows(const StRows& w, bool spans, const StRec& R, int r, StRecRows& Q) {
+    Q = StRecRows{r, 1, 0, R.L3};
+    if (R.bad || !spans) return R.bad;
+    const long long p0 = w.rec_span0[r], p1 = w.rec_span0[r + 1];
+    // (in this order: 0 <= p0 < p1 <= total_spans < 2^31 first, so the product below stays under 2^62)
+    if (p0 < 0 || p1 > w.total_spans || p1 <= p0) return 16;
+    const long long off = w.rec_span_off ? w.rec_span_off[r] : 0, last = off + (p1 - p0 - 1) * w.span3, end = last + w.span3;
+    if (off < 0 || last >= R.L3) return 16;                                      // the last span holds a frame
+    if (!w.rec_span_off && end < R.L3) return 16;                                // ... and reaches the end: n = ceil(L3 / span3)
+    Q = StRecRows{(int)p0, (int)(p1 - p0), (int)off, (int)min(end, (long long)R.L3)};
+    return 0;
+}
+// Span k, 0 <= k < Q.n, of a recording st_rec_rows accepted covers its local frames [s, e), s < L3 by either rule.
+__device__ __forceinline__ void st_span_frames(const StRows& w, const StRecRows& Q, int k, int& s, int& e) {
+    const long long s0 = Q.off + (long long)k * w.span3;
+    s = (int)s0;
+    e = (int)min(s0 + w.span3, (long long)Q.end);
+}
+// The row that local frame u of such a recording reads; false: the frame belongs to no span (pieces only).
+__device__ __forceinline__ bool st_frame_row(const StRows& w, bool spans, const StRecRows& Q, int u, size_t& row) {
+    row = (size_t)Q.row0 + (spans ? (u - Q.off) / w.span3 : 0);
+    return !spans || (u >= Q.off && u < Q.end);
+}
 
 // Span g of the tables: the recording that holds it (one bisection over rec_span0: the last r with rec_span0[r] <= g), validated
-// - the recording as st_rec does, its spans against ceil(L3 / span3) and total_spans, g inside them - and the span's frames
-// [s, e) of that recording's timeline.  bad: 0, or the err bits that make the span's row NaN.  Wave-uniform.  A piece
-// (StPieceArgs) is validated by off >= 0, n >= 1 and off + (n - 1) * span3 < L3 in the place of the ceil rule: its last span
-// then holds a frame.
+// (st_rec_rows, and g inside its rows), and the span's frames [s, e) of that recording's timeline.  bad: 0, or the err bits that
+// make the span's row NaN.  Wave-uniform.
 struct StSpan { StRec R; int r, s, e, bad; };
-template <class Args>
-__device__ __forceinline__ StSpan st_span_of(const Args& args, int r, long long g) {          // span g as one of recording r's
-    const StSpanArgs& sa = sp_args(args);
-    StSpan S;
-    S.r = r;
-    S.R = st_rec(sa.w.t, r);
-    S.s = S.e = 0;
-    S.bad = S.R.bad;
-    if (S.bad) return S;
-    const long long p0 = sa.rec_span0[r], p1 = sa.rec_span0[r + 1];
-    long long s;
-    if constexpr (std::is_same<Args, StPieceArgs>::value) {
-        const long long off = args.rec_span_off[r];
-        // (in this order: 0 <= p0 < p1 <= total_spans < 2^31 first, so the product stays below 2^62)
-        if (p0 < 0 || p1 > sa.total_spans || p1 <= p0 || off < 0 || off + (p1 - p0 - 1) * sa.span3 >= S.R.L3 || g < p0 || g >= p1) {
-            S.bad = 16;
-            return S;
-        }
-        s = off + (g - p0) * sa.span3;                                           // < L3: g - p0 <= n - 1
-    } else {
-        const long long n_spans = ((long long)S.R.L3 + sa.span3 - 1) / sa.span3;
-        if (p0 < 0 || p1 - p0 != n_spans || p1 > sa.total_spans || g < p0 || g >= p1) { S.bad = 16; return S; }
-        s = (g - p0) * sa.span3;                                                 // < L3: g - p0 < ceil(L3 / span3)
-    }
-    S.s = (int)s;
-    S.e = (int)min(s + sa.span3, (long long)S.R.L3);
-    return S;
-}
-template <class Args>
-__device__ __forceinline__ StSpan st_span(const Args& args, long long g) {
-    const StSpanArgs& sa = sp_args(args);
-    int lo_r = 0, hi_r = sa.w.t.n_rec - 1;
+__device__ __forceinline__ StSpan st_span(const StTables& a, const StRows& w, long long g) {
+    int lo_r = 0, hi_r = a.n_rec - 1;
     while (lo_r < hi_r) {
         const int mid = (lo_r + hi_r + 1) >> 1;
-        if (sa.rec_span0[mid] <= g) lo_r = mid;
+        if (w.rec_span0[mid] <= g) lo_r = mid;
         else hi_r = mid - 1;
     }
-    return st_span_of(args, lo_r, g);
+    StSpan S;
+    StRecRows Q;
+    S.r = lo_r;
+    S.R = st_rec(a, lo_r);
+    S.s = S.e = 0;
+    S.bad = st_rec_rows(w, true, S.R, lo_r, Q);
+    if (!S.bad && (g < Q.row0 || g >= Q.row0 + Q.n)) S.bad = 16;
+    if (!S.bad) st_span_frames(w, Q, (int)(g - Q.row0), S.s, S.e);
+    return S;
 }
 
-template <bool VEC, int W, class Args>
-__global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_tile(Args args) {
+template <bool VEC, int W, bool SPANS>
+__global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_tile(StPoolArgs wa) {
     __shared__ double red[ST_THREADS * W * 2];                                   // [rows][NC][2], rows * NC <= ST_THREADS * W
     __shared__ double fold[ST_MAXC * SW_FOLD * 2];
-    const StWeakArgs& wa = sw_args(args);
     const StTables& a = wa.t;
     const int tid = threadIdx.x, NC = a.NC;
     StTile T;
-    if constexpr (sw_spans<Args>) {                                              // frame 0 of the tile walk is the span's first frame
-        const int tps = sp_args(args).tps;
+    if constexpr (SPANS) {                                                       // frame 0 of the tile walk is the span's first frame
+        const int tps = wa.rows.tps;
         const long long g = blockIdx.x / tps, kt = blockIdx.x - g * tps;
-        const StSpan S = st_span(args, g);
+        const StSpan S = st_span(a, wa.rows, g);
         const long long s = (long long)S.s + kt * ST_TILE;
         if (S.bad || s >= S.e) return;
         T.R = S.R;
@@ -644,29 +641,29 @@ static_assert(ST_THREADS == ST_MAXC * SW_FOLD, "k_stitch_weak_tile folds the row
 // One wave per column (recording, class) - or per row (span, class) of the span tags: the tile pairs in the fixed order above; a
 // recording the tables do not describe or cover raises its err bits and has NaN rows, and so has a span that no valid
 // recording holds.  In a span call wave r < n_rec moreover validates recording r (a recording whose spans own no row).
-template <class Args>
-__global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_cols(Args args) {
-    const StWeakArgs& wa = sw_args(args);
+template <bool SPANS>
+__global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_cols(StPoolArgs wa) {
     const StTables& a = wa.t;
     const int lane = threadIdx.x & 63;
     const long long col = (long long)blockIdx.x * (ST_THREADS / 64) + (threadIdx.x >> 6);
     long long n_rows = a.n_rec, slot0 = 0;
     int bad = 0, tiles = 0;
-    if constexpr (sw_spans<Args>) {
-        n_rows = sp_args(args).total_spans;
+    if constexpr (SPANS) {
+        n_rows = wa.rows.total_spans;
         if (col < a.n_rec && lane == 0) {
-            const StSpan S = st_span_of(args, (int)col, sp_args(args).rec_span0[col]);    // (its first span, if it has one)
-            if (S.bad) atomicOr(a.err, S.bad);
+            StRecRows Q;
+            const int rec_bad = st_rec_rows(wa.rows, true, st_rec(a, (int)col), (int)col, Q);
+            if (rec_bad) atomicOr(a.err, rec_bad);
         }
     }
     if (col >= n_rows * a.NC) return;
     const long long r = col / a.NC;
     const int c = (int)(col - r * a.NC);
-    if constexpr (sw_spans<Args>) {
-        const StSpan S = st_span(args, r);
+    if constexpr (SPANS) {
+        const StSpan S = st_span(a, wa.rows, r);
         bad = S.bad;
         tiles = (S.e - S.s + ST_TILE - 1) / ST_TILE;
-        slot0 = r * sp_args(args).tps;
+        slot0 = r * wa.rows.tps;
     } else {
         const StRec R = st_rec(a, (int)r);
         bad = R.bad;
@@ -697,20 +694,18 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_cols(Args args) {
 
 static size_t sw_ws_per_slot(int NC) { return (size_t)NC * 2 * sizeof(double); }
 
-// The two launches of sed_stitch_weak (Args = StWeakArgs), of sed_stitch_span_tags (StSpanArgs) and of
-// sed_stitch_piece_span_tags (StPieceArgs): n_tiles workgroups of the tile pass, one wave per column of the column pass.
-template <class Args>
-static int sw_launch(const Args& args, unsigned n_tiles, long long n_waves, void* stream) {
-    const StWeakArgs& wa = sw_args(args);
+// The two launches of the three forward entries: n_tiles workgroups of the tile pass, one wave per column of the column pass.
+template <bool SPANS>
+static int sw_launch(const StPoolArgs& wa, unsigned n_tiles, long long n_waves, void* stream) {
     const int NC = wa.t.NC;
     const bool vec = NC % 4 == 0 && ((uintptr_t)wa.win_strong % 16) == 0 && ((uintptr_t)wa.win_att % 16) == 0;
     hipStream_t st = (hipStream_t)stream;
     const dim3 tiles(n_tiles), thr256(ST_THREADS);
-    if (vec) hipLaunchKernelGGL((k_stitch_weak_tile<true, 4, Args>), tiles, thr256, 0, st, args);
-    else if (NC % 4 == 0) hipLaunchKernelGGL((k_stitch_weak_tile<false, 4, Args>), tiles, thr256, 0, st, args);
-    else hipLaunchKernelGGL((k_stitch_weak_tile<false, 1, Args>), tiles, thr256, 0, st, args);
+    if (vec) hipLaunchKernelGGL((k_stitch_weak_tile<true, 4, SPANS>), tiles, thr256, 0, st, wa);
+    else if (NC % 4 == 0) hipLaunchKernelGGL((k_stitch_weak_tile<false, 4, SPANS>), tiles, thr256, 0, st, wa);
+    else hipLaunchKernelGGL((k_stitch_weak_tile<false, 1, SPANS>), tiles, thr256, 0, st, wa);
     SED_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_stitch_weak_cols<Args>, dim3((unsigned)((n_waves + 3) / 4)), thr256, 0, st, args);
+    hipLaunchKernelGGL(k_stitch_weak_cols<SPANS>, dim3((unsigned)((n_waves + 3) / 4)), thr256, 0, st, wa);
     SED_CHECK_LAUNCH();
     return SED_OK;
 }
@@ -731,8 +726,8 @@ extern "C" int sed_stitch_weak(const float* win_strong, const float* win_att, co
     SED_TRY(st_front(what, rec_win0, rec_frame0, err, n_rec, T3, NC, hop3, weighting, 1, 31, &t));
     ST_NEED(((uintptr_t)ws % 8) == 0, "ws must be 8-byte aligned");
     SED_TRY(st_ws_slots(what, ws_bytes, sw_ws_per_slot(NC), true, 1, &t));
-    const StWeakArgs wa = {t, win_strong, win_att, (double*)ws, weak, sums};
-    return sw_launch(wa, (unsigned)t.n_slots, (long long)n_rec * NC, stream);
+    const StPoolArgs wa = {t, win_strong, win_att, (double*)ws, weak, sums, StRows{}};
+    return sw_launch<false>(wa, (unsigned)t.n_slots, (long long)n_rec * NC, stream);
 }
 
 // ---- span-level weak tags (sed_stitch_span_tags) ------------------------------------------------------------------------------
@@ -744,11 +739,15 @@ static size_t sp_slot_count(long long total_frames, long long total_spans, int n
     return (size_t)(total_spans * sp_tps(span3));
 }
 
-extern "C" size_t sed_stitch_span_tags_ws_bytes(long long total_frames, long long total_spans, int n_rec, int nclass, int span3) {
+static size_t sp_ws_bytes(const char* what, long long total_frames, long long total_spans, int n_rec, int nclass, int span3) {
     const size_t n = sp_slot_count(total_frames, total_spans, n_rec, nclass, span3);
-    if (!n) sed_set_error("sed_stitch_span_tags_ws_bytes: need span3 >= 1, 1 <= n_rec <= total_spans <= total_frames, "
-                          "1 <= nclass <= 16, total_frames * nclass < 2^31, total_spans * ceil(span3 / %d) < 2^31", ST_TILE);
+    if (!n) sed_set_error("%s: need span3 >= 1, 1 <= n_rec <= total_spans <= total_frames, "
+                          "1 <= nclass <= 16, total_frames * nclass < 2^31, total_spans * ceil(span3 / %d) < 2^31", what, ST_TILE);
     return n * sw_ws_per_slot(nclass);
+}
+
+extern "C" size_t sed_stitch_span_tags_ws_bytes(long long total_frames, long long total_spans, int n_rec, int nclass, int span3) {
+    return sp_ws_bytes("sed_stitch_span_tags_ws_bytes", total_frames, total_spans, n_rec, nclass, span3);
 }
 
 // The host side of sed_stitch_span_tags (rec_span_off null) and of sed_stitch_piece_span_tags.
@@ -767,11 +766,10 @@ static int sp_run(const char* what, const float* win_strong, const float* win_at
         return SED_ERR_BAD_ARG;
     }
     t.n_slots = 0x7fffffff;                                                      // (st_rec's slot check is the recording layout's)
-    const StSpanArgs sa = {{t, win_strong, win_att, (double*)ws, tags, sums}, rec_span0, total_spans, span3, (int)sp_tps(span3)};
-    const long long rows = total_spans * NC, n_waves = rows > n_rec ? rows : n_rec;
-    if (!rec_span_off) return sw_launch(sa, (unsigned)n_slots, n_waves, stream);
-    const StPieceArgs pa = {sa, rec_span_off};
-    return sw_launch(pa, (unsigned)n_slots, n_waves, stream);
+    const StPoolArgs wa = {t, win_strong, win_att, (double*)ws, tags, sums,
+                           StRows{rec_span0, rec_span_off, total_spans, span3, (int)sp_tps(span3)}};
+    const long long rows = total_spans * NC;
+    return sw_launch<true>(wa, (unsigned)n_slots, rows > n_rec ? rows : n_rec, stream);
 }
 
 extern "C" int sed_stitch_span_tags(const float* win_strong, const float* win_att, const int32_t* rec_win0,
@@ -787,10 +785,7 @@ extern "C" int sed_stitch_span_tags(const float* win_strong, const float* win_at
 // ---- span tags of pieces (sed_stitch_piece_span_tags) ------------------------------------------------------------------------
 extern "C" size_t sed_stitch_piece_span_tags_ws_bytes(long long total_frames, long long total_spans, int n_rec, int nclass,
                                                       int span3) {
-    const size_t n = sp_slot_count(total_frames, total_spans, n_rec, nclass, span3);
-    if (!n) sed_set_error("sed_stitch_piece_span_tags_ws_bytes: need span3 >= 1, 1 <= n_rec <= total_spans <= total_frames, "
-                          "1 <= nclass <= 16, total_frames * nclass < 2^31, total_spans * ceil(span3 / %d) < 2^31", ST_TILE);
-    return n * sw_ws_per_slot(nclass);
+    return sp_ws_bytes("sed_stitch_piece_span_tags_ws_bytes", total_frames, total_spans, n_rec, nclass, span3);
 }
 
 extern "C" int sed_stitch_piece_span_tags(const float* win_strong, const float* win_att, const int32_t* rec_win0,
@@ -818,12 +813,16 @@ extern "C" int sed_stitch_piece_span_tags(const float* win_strong, const float* 
 // The call has no workspace to derive the slot count from, and the tables are device data: both kernels take it from
 // rec_frame0[n_rec] (sb_tables: st_slot_count of it, the smallest count that st_rec accepts every well-formed table with) and
 // walk the slots with a grid-stride loop over a fixed grid.
-struct StWeakBwdArgs {
+// At the span level the tiles stay the recordings' - a window element's owner is a timeline frame whatever the spans are - and
+// only the ROW that a frame takes g, num and den from changes (st_frame_row); a frame of a piece that belongs to no span leaves
+// its window elements at the clear pass's +0.0f.
+struct StPoolBwdArgs {       // sed_stitch_weak_backward, sed_stitch_span_tags_backward, sed_stitch_piece_span_tags_backward
     StTables t;              // n_slots is filled in on the device (sb_tables)
     const float *win_strong, *win_att;
-    const double* sums;      // [n_rec][NC][2] (num, den) of the forward
-    const float* g_weak;     // [n_rec][NC]
+    const double* sums;      // [rows][NC][2] (num, den) of the forward, rows = n_rec or total_spans
+    const float* g_weak;     // [rows][NC]
     float *d_win_strong, *d_win_att;      // [n_win][T3][NC]
+    StRows rows;             // (tps is not used)
 };
 #define SB_GRID 512
 
@@ -835,59 +834,13 @@ __device__ __forceinline__ StTables sb_tables(StTables a) {
     return a;
 }
 
-// sed_stitch_span_tags_backward runs the same two kernels (Args = StSpanBwdArgs): the tiles stay the recordings' - a window
-// element's owner is a timeline frame whatever the spans are - and only the ROW that frame u of recording r takes g, num and den
-// from changes, from r to rec_span0[r] + u / span3.  A recording's span offsets are validated as the forward validates them
-// (sb_rec_bad) before any is used as an index: a row is then < total_spans.
-struct StSpanBwdArgs {
-    StWeakBwdArgs w;         // sums [total_spans][NC][2], g_weak [total_spans][NC]
-    const int64_t* rec_span0;
-    long long total_spans;
-    int span3;
-};
-// sed_stitch_piece_span_tags_backward (StPieceBwdArgs): frame u of piece r reads row rec_span0[r] + (u - off_r) / span3; a frame
-// with u < off_r or (u - off_r) / span3 >= n_r belongs to no span and its window elements keep the clear pass's +0.0f.
-struct StPieceBwdArgs {
-    StSpanBwdArgs s;
-    const int32_t* rec_span_off;         // [n_rec]
-};
-__host__ __device__ __forceinline__ const StWeakBwdArgs& sb_args(const StWeakBwdArgs& a) { return a; }
-__host__ __device__ __forceinline__ const StWeakBwdArgs& sb_args(const StSpanBwdArgs& a) { return a.w; }
-__host__ __device__ __forceinline__ const StWeakBwdArgs& sb_args(const StPieceBwdArgs& a) { return a.s.w; }
-
-// What keeps recording r (R = st_rec of it) out of the backward: R.bad, or 16 for span offsets the forward rejects.
-__device__ __forceinline__ int sb_rec_bad(const StWeakBwdArgs&, const StRec& R, int) { return R.bad; }
-__device__ __forceinline__ int sb_rec_bad(const StSpanBwdArgs& sa, const StRec& R, int r) {
-    if (R.bad) return R.bad;
-    const long long p0 = sa.rec_span0[r], p1 = sa.rec_span0[r + 1];
-    const long long n_spans = ((long long)R.L3 + sa.span3 - 1) / sa.span3;
-    return (p0 < 0 || p1 > sa.total_spans || p1 < p0 || p1 - p0 != n_spans) ? 16 : 0;   // (in this order: no overflow)
-}
-__device__ __forceinline__ int sb_rec_bad(const StPieceBwdArgs& pa, const StRec& R, int r) {
-    if (R.bad) return R.bad;
-    const StSpanBwdArgs& sa = pa.s;
-    const long long p0 = sa.rec_span0[r], p1 = sa.rec_span0[r + 1], off = pa.rec_span_off[r];
-    return (p0 < 0 || p1 > sa.total_spans || p1 <= p0 || off < 0 || off + (p1 - p0 - 1) * sa.span3 >= R.L3) ? 16 : 0;   // (no overflow)
-}
-// The row of g_weak / sums that frame u of (valid) recording r reads; false: the frame belongs to no span (pieces only).
-__device__ __forceinline__ bool sb_row(const StWeakBwdArgs&, int r, int, size_t& row) { row = (size_t)r; return true; }
-__device__ __forceinline__ bool sb_row(const StSpanBwdArgs& sa, int r, int u, size_t& row) {
-    row = (size_t)(sa.rec_span0[r] + u / sa.span3);
-    return true;
-}
-__device__ __forceinline__ bool sb_row(const StPieceBwdArgs& pa, int r, int u, size_t& row) {
-    const long long p0 = pa.s.rec_span0[r], k = (long long)u - pa.rec_span_off[r];
-    row = (size_t)(p0 + k / pa.s.span3);
-    return k >= 0 && k / pa.s.span3 < pa.s.rec_span0[r + 1] - p0;
-}
-
-template <bool VEC, class Args>
-__global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_bwd_zero(Args args) {
-    const StWeakBwdArgs& wa = sb_args(args);
+template <bool VEC>
+__global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_bwd_zero(StPoolBwdArgs wa) {
     const StTables a = sb_tables(wa.t);
     const size_t i0 = (size_t)blockIdx.x * ST_THREADS + threadIdx.x, stride = (size_t)gridDim.x * ST_THREADS;
     for (size_t r = i0; r < (size_t)a.n_rec; r += stride) {
-        const int bad = sb_rec_bad(args, st_rec(a, (int)r), (int)r);
+        StRecRows Q;
+        const int bad = st_rec_rows(wa.rows, wa.rows.rec_span0 != nullptr, st_rec(a, (int)r), (int)r, Q);
         if (bad) atomicOr(a.err, bad);
     }
     const long long wt = a.rec_win0[a.n_rec];
@@ -907,9 +860,8 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_bwd_zero(Args args) 
     }
 }
 
-template <bool VEC, class Args>
-__global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_bwd_tile(Args args) {
-    const StWeakBwdArgs& wa = sb_args(args);
+template <bool VEC, bool SPANS>
+__global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_bwd_tile(StPoolBwdArgs wa) {
     const StTables a = sb_tables(wa.t);
     const int tid = threadIdx.x, NC = a.NC, T3 = a.T3, hop3 = a.hop3;
     constexpr int W = VEC ? 4 : 1;
@@ -917,13 +869,12 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_bwd_tile(Args args) 
     for (long long g = blockIdx.x; g < a.n_slots; g += gridDim.x) {
         StTile T;
         if (!st_tile(a, g, T)) continue;
-        if constexpr (!std::is_same<Args, StWeakBwdArgs>::value) {
-            if (sb_rec_bad(args, T.R, T.r)) continue;
-        }
+        StRecRows Q;
+        if (st_rec_rows(wa.rows, SPANS, T.R, T.r, Q)) continue;
         for (int it = tid; it < (T.e - T.s) * G; it += ST_THREADS) {
             const int fl = it / G, q = it - fl * G, u = T.s + fl, col = W * q;
             size_t row;
-            if (!sb_row(args, T.r, u, row)) continue;
+            if (!st_frame_row(wa.rows, SPANS, Q, u, row)) continue;
             const f32x4 p = st_blend<VEC>(a, wa.win_strong, T.R, u, q);
             const f32x4 at = st_blend<VEC>(a, wa.win_att, T.R, u, q);
             double dP[W], dA[W];
@@ -961,20 +912,18 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_weak_bwd_tile(Args args) 
     }
 }
 
-// The two launches of sed_stitch_weak_backward (Args = StWeakBwdArgs), of sed_stitch_span_tags_backward (StSpanBwdArgs) and of
-// sed_stitch_piece_span_tags_backward (StPieceBwdArgs).
-template <class Args>
-static int sb_launch(const Args& args, void* stream) {
-    const StWeakBwdArgs& wa = sb_args(args);
+// The two launches of the three backward entries.
+template <bool SPANS>
+static int sb_launch(const StPoolBwdArgs& wa, void* stream) {
     const bool vec = wa.t.NC % 4 == 0 && ((uintptr_t)wa.win_strong % 16) == 0 && ((uintptr_t)wa.win_att % 16) == 0 &&
                      ((uintptr_t)wa.d_win_strong % 16) == 0 && ((uintptr_t)wa.d_win_att % 16) == 0;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(SB_GRID), thr256(ST_THREADS);
-    if (vec) hipLaunchKernelGGL((k_stitch_weak_bwd_zero<true, Args>), grid, thr256, 0, st, args);
-    else hipLaunchKernelGGL((k_stitch_weak_bwd_zero<false, Args>), grid, thr256, 0, st, args);
+    if (vec) hipLaunchKernelGGL(k_stitch_weak_bwd_zero<true>, grid, thr256, 0, st, wa);
+    else hipLaunchKernelGGL(k_stitch_weak_bwd_zero<false>, grid, thr256, 0, st, wa);
     SED_CHECK_LAUNCH();
-    if (vec) hipLaunchKernelGGL((k_stitch_weak_bwd_tile<true, Args>), grid, thr256, 0, st, args);
-    else hipLaunchKernelGGL((k_stitch_weak_bwd_tile<false, Args>), grid, thr256, 0, st, args);
+    if (vec) hipLaunchKernelGGL((k_stitch_weak_bwd_tile<true, SPANS>), grid, thr256, 0, st, wa);
+    else hipLaunchKernelGGL((k_stitch_weak_bwd_tile<false, SPANS>), grid, thr256, 0, st, wa);
     SED_CHECK_LAUNCH();
     return SED_OK;
 }
@@ -988,8 +937,8 @@ extern "C" int sed_stitch_weak_backward(const float* win_strong, const float* wi
     StTables t;
     SED_TRY(st_front(what, rec_win0, rec_frame0, err, n_rec, T3, NC, hop3, weighting, 1, 31, &t));
     ST_NEED(((uintptr_t)sums % 8) == 0, "sums must be 8-byte aligned");
-    const StWeakBwdArgs wa = {t, win_strong, win_att, sums, g_weak, d_win_strong, d_win_att};
-    return sb_launch(wa, stream);
+    const StPoolBwdArgs wa = {t, win_strong, win_att, sums, g_weak, d_win_strong, d_win_att, StRows{}};
+    return sb_launch<false>(wa, stream);
 }
 
 // ---- backward through the span tags (sed_stitch_span_tags_backward, sed_stitch_piece_span_tags_backward) ---------------------
@@ -1003,10 +952,9 @@ static int sb_run(const char* what, const float* win_strong, const float* win_at
     ST_NEED(span3 >= 1 && total_spans >= n_rec && total_spans < (1ll << 31) && total_spans * NC < (1ll << 31),
             "need span3 >= 1, n_rec <= total_spans and total_spans * NC < 2^31");
     ST_NEED(((uintptr_t)sums % 8) == 0, "sums must be 8-byte aligned");
-    const StSpanBwdArgs sa = {{t, win_strong, win_att, sums, g_tags, d_win_strong, d_win_att}, rec_span0, total_spans, span3};
-    if (!rec_span_off) return sb_launch(sa, stream);
-    const StPieceBwdArgs pa = {sa, rec_span_off};
-    return sb_launch(pa, stream);
+    const StPoolBwdArgs wa = {t, win_strong, win_att, sums, g_tags, d_win_strong, d_win_att,
+                              StRows{rec_span0, rec_span_off, total_spans, span3, 0}};
+    return sb_launch<true>(wa, stream);
 }
 
 extern "C" int sed_stitch_span_tags_backward(const float* win_strong, const float* win_att, const int32_t* rec_win0,

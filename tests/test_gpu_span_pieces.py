@@ -301,6 +301,51 @@ def test_a_malformed_piece_raises_bit_16_and_only_its_rows_and_windows_are_lost(
             assert gb[name][w0[r]:w0[r + 1]].tobytes() == cb[name][w0[r]:w0[r + 1]].tobytes() and gb[name][w0[r]:w0[r + 1]].any(), (name, r)
 
 
+@pytest.mark.parametrize("NC", [4, 3])
+def test_one_table_short_of_the_ceiling_is_malformed_for_spans_and_a_piece_at_off_zero(NC):
+    """The span entries and the piece entries run the same kernels; only rec_span_off (null or not) tells them apart.  Recordings
+    of 23 and 12 frames (5 and 2 windows, hop3 = 4, taper), span3 = 4, rec_span0 = [0, 4, 7]: recording 0 is given 4 spans where
+    the ceiling is 6, recording 1 its 3.  The span entries reject recording 0 (bit 16, NaN rows, +0.0f windows); the piece
+    entries at off = [0, 0] take it: its four spans are the first four of the clean call and its frames from 16 on own no span.
+    Recording 1 is the clean call's in both.  NC = 4 takes the 16-byte path, NC = 3 the scalar one."""
+    hop3, weighting, span3 = 4, 1, 4
+    w0, f0 = np.array([0, 5, 7], np.int32), np.array([0, 23, 35], np.int64)
+    s0, off = np.array([0, 4, 7], np.int64), np.zeros(2, np.int32)
+    rs = np.random.RandomState(995 + NC)
+    p, a = _inputs(rs, 7, T3, NC)
+    clean = SpanCall(p, a, w0, f0, hop3, weighting, span3).run()
+    assert clean["err"] == 0 and clean["tags"].shape[0] == 9 and not np.isnan(clean["tags"]).any()
+    g = _g(rs, 9, NC)
+    g[g == 0] = 0.5
+    cb = SpanBwdCall(p, a, w0, f0, hop3, weighting, span3, g, clean["sums"]).run()
+    assert cb["err"] == 0
+    rows = np.r_[0:4, 6:9]                                                         # the clean rows behind the table's seven
+    frame = 4 * np.arange(5)[:, None] + np.arange(T3)[None, :]                     # recording 0: the frame of window element (j, v)
+    zero = np.zeros(1, np.float32).tobytes()
+    # the span entries: recording 0 is malformed
+    got = SpanCall(p, a, w0, f0, hop3, weighting, span3, rec_span0=s0).run()
+    assert got["err"] == 16 and got["tags"].shape[0] == 7
+    assert np.isnan(got["tags"][:4]).all() and np.isnan(got["sums"][:4]).all()
+    assert got["tags"][4:].tobytes() == clean["tags"][6:].tobytes() and got["sums"][4:].tobytes() == clean["sums"][6:].tobytes()
+    bsums, bg = np.ones((7, NC, 2)), np.ones((7, NC), np.float32)
+    bsums[4:], bg[4:] = clean["sums"][6:], g[6:]
+    gb = SpanBwdCall(p, a, w0, f0, hop3, weighting, span3, bg, bsums, rec_span0=s0).run()
+    assert gb["err"] == 16
+    for name in ("ds", "da"):
+        assert gb[name][:5].tobytes() == zero * (5 * T3 * NC), name
+        assert gb[name][5:].tobytes() == cb[name][5:].tobytes() and gb[name][5:].any(), name
+    # the piece entries: the same tables describe a piece of four spans and the whole of recording 1
+    got = PieceCall(p, a, w0, f0, s0, off, hop3, weighting, span3).run()
+    assert got["err"] == 0 and got["tags"].shape[0] == 7
+    assert got["tags"].tobytes() == clean["tags"][rows].tobytes() and got["sums"].tobytes() == clean["sums"][rows].tobytes()
+    gb = PieceBwdCall(p, a, w0, f0, s0, off, hop3, weighting, span3, g[rows], clean["sums"][rows]).run()
+    assert gb["err"] == 0
+    for name in ("ds", "da"):
+        assert gb[name][:5][frame >= 16].tobytes() == zero * (int((frame >= 16).sum()) * NC), name
+        assert gb[name][:5][frame < 16].tobytes() == cb[name][:5][frame < 16].tobytes() and gb[name][:5][frame < 16].any(), name
+        assert gb[name][5:].tobytes() == cb[name][5:].tobytes() and gb[name][5:].any(), name
+
+
 def test_bad_host_arguments_return_before_any_launch():
     p, a, w0, f0, s0, off, hop3, span3, rs = _one_set(10)
     call = PieceCall(p, a, w0, f0, s0, off, hop3, 1, span3)
